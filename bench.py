@@ -15,9 +15,9 @@ Launching: `python bench.py --gpus N` starts its own N ranks (fresh child proces
 GPU); under `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` it is one of the ranks.
 `--total-steps T` renders a FIXED T-spp image split over the ranks ("scaling": "strong"; north star: 256 / 1024 spp over 8 GPUs).
 
-Timed region: exactly `--steps` frames between barrier + synchronize brackets, MAX over ranks.  A region shorter than 0.25 s says
-little (20 steps are 41 ms), so the bracketed K-step region is repeated until 0.25 s of it have been timed; `value` and
-`ms_per_step` are over all repeats (`repeats` in the line).
+Timed region: exactly `--steps` frames between barrier + synchronize brackets, MAX over ranks, timed once; `ms_per_step` is that
+region over the frames in it.  `--dump-outputs DIR` writes what a caller of the timed path receives after its last step - the
+reduced accumulator - as DIR/accum.npy (float32; a fixed, seeded sample of its pixels when the whole would exceed 64 MB).
 
 Roofline: the traversal kernels fetch ~21 MB of node and triangle records over and over, from the
 vector L1s, the L2s and the Infinity Cache - so the line prices the extend kernel at EVERY memory level it uses: bytes per launch
@@ -41,7 +41,7 @@ sys.path.insert(0, ROOT)
 # vector L1 64 B per clock and CU = 256 CUs x 64 B x 2.4 GHz (the table's max clock: the chip clocks lower under load, so the fraction
 # is a lower estimate)
 PEAK_GBS = {"hbm": 8000.0, "l2": 34500.0, "vl1d": 256 * 64 * 2.4}
-MIN_TIMED_S = 0.25      # repeat the K-step region until this much has been timed
+DUMP_LIMIT_BYTES = 64 * 10**6   # --dump-outputs: at most this much in all
 
 # The BASELINE.json configurations that fit one GPU (config 1 is the CPU plumbing case).  `python bench.py` = config 3, the one the
 # metric is quoted on; the others are parity-test cases that can be timed / profiled with --config (tools/r3_pmc.sh).
@@ -88,8 +88,9 @@ def parse_args():
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl", help="nccl = RCCL over xGMI (default); gloo only for rehearsals")
     ap.add_argument("--same-device", action="store_true", help="rehearsal on a 1-GPU box: every rank uses GPU 0 (requires --backend gloo)")
     ap.add_argument("--no-single", action="store_true", help="skip the untimed single-context pass (profiler runs: only the timed workload's launches)")
-    ap.add_argument("--no-repeat", action="store_true", help="time the K-step region once, however short it is")
+    ap.add_argument("--no-repeat", action="store_true", help="no effect: the timed region always runs exactly --steps frames, once")
     ap.add_argument("--dump-accum", default=None, help="rank 0 writes the reduced accumulator (npy) here after the timed region")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="rank 0 writes the timed path's outputs after its last step as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -176,8 +177,7 @@ def main():
     import numpy as np
     # Load order decides which HIP runtime the process runs on: torch first = the ROCm 7.0 runtime bundled in the torch wheel, librt355.so
     # first = the system's ROCm 7.2 (the library's RUNPATH).  A single context is 12 % faster on the former (732 against 645 M samples/s,
-    # EXPERIMENTS.md (44)); RT355_IMPORT_ORDER=lib-first selects the latter for A/B runs.  Either way librt355.so is loaded before HIP
-    # INITIALISES (importing torch does not initialise it), which is when its request for sixteen hardware queues has to be in place.
+    # EXPERIMENTS.md (44)); RT355_IMPORT_ORDER=lib-first selects the latter for A/B runs.
     from magr_ray_tracer_amd import _lib
     if os.environ.get("RT355_IMPORT_ORDER") != "lib-first":
         import torch
@@ -275,29 +275,27 @@ def main():
         d.reset_stage_times()
     barrier()
 
-    # ---- timed region: this rank's frames (dealt to its lanes) + the accumulator reduction, repeated -----------------------------
-    dts, render_s, reduce_s = [], 0.0, 0.0
-    while True:
-        barrier()
-        t0 = time.perf_counter()
-        if my_steps > 0:
-            groups.render(cam, my_steps)
-        groups.synchronize()
-        t1 = time.perf_counter()
-        reduce_all()
-        t2 = time.perf_counter()
-        barrier()
-        dts.append(max_over_ranks(time.perf_counter() - t0))
-        render_s += t1 - t0
-        reduce_s += t2 - t1
-        if args.no_repeat or sum(dts) >= MIN_TIMED_S or len(dts) >= 256:
-            break
-    dt, repeats = sum(dts), len(dts)
-    frames_job = job_frames * repeats            # 1-spp frames of the whole job in the timed region
-    frames_mine = my_steps * repeats
+    # ---- timed region: this rank's frames (dealt to its lanes) + the accumulator reduction, once ------------------------------------
+    barrier()
+    t0 = time.perf_counter()
+    if my_steps > 0:
+        groups.render(cam, my_steps)
+    groups.synchronize()
+    t1 = time.perf_counter()
+    reduce_all()
+    t2 = time.perf_counter()
+    barrier()
+    dt = max_over_ranks(time.perf_counter() - t0)
+    render_s, reduce_s, repeats = t1 - t0, t2 - t1, 1
+    frames_job = job_frames                      # 1-spp frames of the whole job in the timed region
+    frames_mine = my_steps
     checksum = float(reduced[..., :3].sum().item())
-    if args.dump_accum and rank == 0:
-        np.save(args.dump_accum, reduced.cpu().numpy())
+    if rank == 0 and (args.dump_accum or args.dump_outputs):
+        acc = reduced.cpu().numpy()
+        if args.dump_accum:
+            np.save(args.dump_accum, acc)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, acc)
     per_rank = [[render_s, reduce_s]]
     if world > 1:
         mine = torch.tensor([render_s, reduce_s], dtype=torch.float64, device=f"cuda:{local}" if args.backend == "nccl" else "cpu")
@@ -357,7 +355,7 @@ def main():
     samples = W * H * frames_job
     value = samples / dt / 1e6
 
-    steps_timed = (args.total_steps if args.total_steps > 0 else args.steps) * repeats
+    steps_timed = args.total_steps if args.total_steps > 0 else args.steps
     if rank == 0:
         ms_per_step = dt / max(frames_mine, 1) * 1e3             # per frame THIS GPU rendered (the job-level roofline's time base)
         roof = {"bound": None, "kernel": "extend = " + kernel_name, "achieved": None, "peak": None, "unit": "GB/s", "frac": None, "traffic": None}
@@ -448,6 +446,22 @@ def main():
     groups.close()
     if world > 1:
         torch.distributed.destroy_process_group()
+
+
+def dump_outputs(d, acc):
+    """DIR/accum.npy: the reduced (H, W, 4) float32 accumulator the timed path leaves to its caller.  Larger than DUMP_LIMIT_BYTES:
+    a fixed, seeded sample of its pixels instead - accum.npy (n, 4) float32 and accum_pixels.npy (n,) float64, the pixels' row-major
+    indices - so that two builds dump the same pixels."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    flat = acc.reshape(-1, acc.shape[-1])
+    if acc.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(d, "accum.npy"), acc)
+        return
+    n = (DUMP_LIMIT_BYTES - 4096) // (flat.itemsize * flat.shape[1] + 8)
+    pix = np.sort(np.random.default_rng(20241015).choice(flat.shape[0], size=n, replace=False))
+    np.save(os.path.join(d, "accum.npy"), np.ascontiguousarray(flat[pix]))
+    np.save(os.path.join(d, "accum_pixels.npy"), pix.astype(np.float64))
 
 
 def _seed_stream(out, first):

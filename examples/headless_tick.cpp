@@ -64,7 +64,7 @@ int main(int argc, char** argv)
     try {
         // ONE Renderer, as in the reference.  `lanes` > 1 makes it render the accumulation as that many interleaved sample streams
         // (rt_group_*, include/rt355.h): Tick() then adds `lanes` frames to the accumulator, whose kernels
-        // overlap on the GPU.  The library arranges the hardware queues itself and says so on stderr if it could not.
+        // overlap on the GPU.  The library says so on stderr when the process's hardware queues serialise them.
         Renderer r(W, H);
         r.lanes = lanes;
         Scene& s = r.scene;

@@ -1216,9 +1216,8 @@ extern "C" int rt_postproc(RtCtx* ctx, int32_t frames, float vignette, float gam
 // lane order.  (Reference: one Renderer, one in-order queue, renderer.cpp:26-94; the group is what stands behind Renderer::Tick here.)
 //
 // HIP maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4, the null stream included) and runs kernels of streams
-// that share one after the other.  The library asks for 16 when it is loaded (before HIP initialises, unless the application already
-// did; eight lanes + the process's own streams + RCCL's need more than 8: with 8 queues eight lanes run four at a time), and rt_group_create MEASURES how many of its streams really run side by side, so a caller is told instead of silently serialised.
-__attribute__((constructor)) static void rt355_request_hw_queues() { setenv("GPU_MAX_HW_QUEUES", "16", 0); }
+// that share one after the other.  The library leaves that setting to the process that loads it; rt_group_create MEASURES how many of
+// its streams really run side by side, so a caller is told instead of silently serialised.
 
 __global__ void k_spin(long long ticks, int* sink)
 {
@@ -1313,7 +1312,7 @@ extern "C" int rt_group_create(const RtConfig* cfg, int32_t lanes, RtGroup** out
         if (!warned) {
             warned = true;
             fprintf(stderr, "librt355: %d lanes requested but only %d of their HIP streams run concurrently (GPU_MAX_HW_QUEUES=%s; HIP serialises streams that "
-                            "share a hardware queue - set GPU_MAX_HW_QUEUES >= lanes + 1 before the process initialises HIP, or load librt355 first)\n",
+                            "share a hardware queue)\n",
                     lanes, g->concurrent, getenv("GPU_MAX_HW_QUEUES") ? getenv("GPU_MAX_HW_QUEUES") : "unset");
         }
     }

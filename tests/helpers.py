@@ -1,4 +1,6 @@
 """Shared helpers of the parity tests."""
+import os
+
 import numpy as np
 
 from magr_ray_tracer_amd import scenes
@@ -29,6 +31,16 @@ def mismatch(a, b):
 def assert_bits(a, b, what):
     n = mismatch(a, b)
     assert n == 0, f"{what}: {n}/{np.asarray(a).size} elements differ"
+
+
+def assert_concurrency(measured, lanes):
+    """`measured` = how many of `lanes` HIP streams the library found running side by side.  HIP maps a process's streams onto
+    GPU_MAX_HW_QUEUES hardware queues (default 4, the null stream included): with one queue per lane beside the null stream every lane
+    must run concurrently; with fewer the library can only report fewer, but never none and never more than `lanes`."""
+    queues = int(os.environ.get("GPU_MAX_HW_QUEUES", "4"))
+    assert 1 <= measured <= lanes, (measured, lanes)
+    if queues >= lanes + 1:
+        assert measured == lanes, f"{measured} of {lanes} streams concurrent on {queues} hardware queues"
 
 
 def max_rel(a, b, floor=1e-6):

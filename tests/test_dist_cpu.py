@@ -214,3 +214,26 @@ def test_bench_launcher_reports_a_failing_rank():
     assert r.returncode != 0
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert "no HIP device" in r.stderr or "RtError" in r.stderr or "hip" in r.stderr.lower()
+
+
+def test_bench_dump_outputs_whole_or_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: the accumulator whole when it fits the 64 MB cap, else the same seeded pixel sample on every run,
+    with the pixels' indices beside it, within the cap."""
+    sys.path.insert(0, ROOT)
+    import bench
+    small = np.arange(90 * 160 * 4, dtype=np.float32).reshape(90, 160, 4)
+    bench.dump_outputs(str(tmp_path / "s"), small)
+    assert sorted(os.listdir(tmp_path / "s")) == ["accum.npy"]
+    got = np.load(tmp_path / "s" / "accum.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small)
+    big = np.random.default_rng(1).random((2160, 3840, 4), dtype=np.float32)   # config 5's 4K accumulator: 133 MB
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), big)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["accum.npy", "accum_pixels.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= bench.DUMP_LIMIT_BYTES
+    acc, pix = np.load(tmp_path / "a" / "accum.npy"), np.load(tmp_path / "a" / "accum_pixels.npy")
+    assert acc.dtype == np.float32 and pix.dtype == np.float64 and acc.shape == (pix.size, 4) and pix.size > 1_000_000
+    assert np.all(np.diff(pix) > 0) and np.array_equal(acc, big.reshape(-1, 4)[pix.astype(np.int64)])
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))

@@ -4,9 +4,10 @@ The reference reads textures through its vendored lib/stb_image.h (LoadImageF, t
 vendored src/tiny_obj_loader.h (Scene::LoadModel, src/scene.cpp:178-243).  oracle/build_ref.sh compiles those headers where they lie,
 behind oracle/ref_io_runner.cpp, into oracle/_ref/libref_io.so (tests/ref_io.py binds it).  Two kinds of test:
 
-  * live (need libref_io.so; it is built in the container that holds /root/reference and travels to the GPU box): the host library's
-    LoadTexture / LoadModel / SavePNG against the compiled reference on the reference's own asset files (where present), on synthetic
-    image files of every variant and on randomized OBJ + MTL files - bit for bit;
+  * live: the host library's LoadTexture / LoadModel / SavePNG against the compiled reference (libref_io.so, built only where the
+    reference exists) on the reference's own asset files (where present), on synthetic image files of every variant and on randomized
+    OBJ + MTL files - bit for bit.  Without libref_io.so the reference's answers to the synthetic files come from
+    tests/golden/io_replay.npz (tests/ref_io.py; generator tests/golden/make_io_replay.py);
   * golden (run anywhere): tests/golden/assets_ref.npz holds small input FILES (bytes) with what the compiled reference made of them
     (tests/golden/make_io_golden.py wrote it); the host library has to reproduce those outputs.
 
@@ -27,7 +28,7 @@ from test_io_postproc_cpu import _png_bytes, _stb_float
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLDEN = os.path.join(HERE, "golden", "assets_ref.npz")
 ASSETS = "/root/reference/assets"
-live = pytest.mark.skipif(not ref_io.available(), reason="oracle/_ref/libref_io.so not built (needs /root/reference)")
+live = pytest.mark.skipif(not ref_io.available(), reason="neither oracle/_ref/libref_io.so nor tests/golden/io_replay.npz")
 
 
 def bits(a):
