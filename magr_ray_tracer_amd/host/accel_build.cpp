@@ -100,6 +100,21 @@ BVH2::Refs BVH2::CreateBVHPrimData(int startIdx) const
     return refs;
 }
 
+// The box a reference contributes to its node's bounds.  Deliberate departure from the reference (bvh.cpp): a fragment clipped
+// by a spatial split contributes its box rounded outward by one ulp per side on all three axes.  Unpadded, the left child's bmax
+// and the right child's bmin both end exactly on the split plane c; a ray with D == +-0 on that axis and its origin on c gets
+// (c - O) * rD = 0 * inf = NaN in its slab test, fminf / fmaxf drop that slab to the wrong side and BOTH children are rejected
+// although the triangle (or sphere) crosses the ray inside them (tests/test_groundtruth_cpu.py); the rounding of the clipped
+// polygon's corners can likewise leave a fragment's exact box a hair inside the primitive on the other axes.  Only node bounds are
+// padded: the fragments' own boxes, from which later splits are chosen and clipped, stay exact, so the tree has the shape the
+// exact boxes give it (padded boxes would never shrink below two ulps and a sliver could be split again forever).
+static void RefBounds(const BVHPrimData& r, float mn[4], float mx[4])
+{
+    for (int k = 0; k < 4; k++) { mn[k] = r.box.bmin[k]; mx[k] = r.box.bmax[k]; }
+    if (r.clipped)
+        for (int k = 0; k < 3; k++) { mn[k] = nextafterf(mn[k], -INFINITY); mx[k] = nextafterf(mx[k], INFINITY); }
+}
+
 void BVH2::UpdateNodeBounds(uint32_t nodeIdx, const Refs& refs)
 {
     if (nodeIdx >= bvhNodes.size()) bvhNodes.resize((size_t)(bvhNodes.size() * 1.5));
@@ -107,10 +122,10 @@ void BVH2::UpdateNodeBounds(uint32_t nodeIdx, const Refs& refs)
     n.aabbMin = RtFloat4{ RT_REALLYFAR, RT_REALLYFAR, RT_REALLYFAR, 0 };
     n.aabbMax = RtFloat4{ -RT_REALLYFAR, -RT_REALLYFAR, -RT_REALLYFAR, 0 };
     for (const BVHPrimData& r : refs) {
-        n.aabbMin = RtFloat4{ fminf(n.aabbMin.x, r.box.bmin[0]), fminf(n.aabbMin.y, r.box.bmin[1]),
-                              fminf(n.aabbMin.z, r.box.bmin[2]), fminf(n.aabbMin.w, r.box.bmin[3]) };
-        n.aabbMax = RtFloat4{ fmaxf(n.aabbMax.x, r.box.bmax[0]), fmaxf(n.aabbMax.y, r.box.bmax[1]),
-                              fmaxf(n.aabbMax.z, r.box.bmax[2]), fmaxf(n.aabbMax.w, r.box.bmax[3]) };
+        float mn[4], mx[4];
+        RefBounds(r, mn, mx);
+        n.aabbMin = RtFloat4{ fminf(n.aabbMin.x, mn[0]), fminf(n.aabbMin.y, mn[1]), fminf(n.aabbMin.z, mn[2]), fminf(n.aabbMin.w, mn[3]) };
+        n.aabbMax = RtFloat4{ fmaxf(n.aabbMax.x, mx[0]), fmaxf(n.aabbMax.y, mx[1]), fmaxf(n.aabbMax.z, mx[2]), fmaxf(n.aabbMax.w, mx[3]) };
     }
 }
 
@@ -215,7 +230,11 @@ BVH2::TNode* BVH2::BuildSubtree(Refs refs, float rootArea, int depth, int& budge
     TNode* n = new TNode();
     n->bmin[0] = n->bmin[1] = n->bmin[2] = RT_REALLYFAR; n->bmin[3] = 0;
     n->bmax[0] = n->bmax[1] = n->bmax[2] = -RT_REALLYFAR; n->bmax[3] = 0;
-    for (const BVHPrimData& r : refs) for (int k = 0; k < 4; k++) { n->bmin[k] = fminf(n->bmin[k], r.box.bmin[k]); n->bmax[k] = fmaxf(n->bmax[k], r.box.bmax[k]); }
+    for (const BVHPrimData& r : refs) {
+        float mn[4], mx[4];
+        RefBounds(r, mn, mx);   // (as UpdateNodeBounds: the arrays stay those of the sequential build)
+        for (int k = 0; k < 4; k++) { n->bmin[k] = fminf(n->bmin[k], mn[k]); n->bmax[k] = fmaxf(n->bmax[k], mx[k]); }
+    }
     int objectAxis = 0, spatialAxis = -1;
     float objectPos = 0, overlap = 0, spatialPos = RT_REALLYFAR, spatialCost = RT_REALLYFAR;
     float objectCost = FindBestObjectSplitPlane(objectAxis, objectPos, overlap, refs);
@@ -477,8 +496,8 @@ void BVH2::SpatialSplit(int axis, float splitPos, const Refs& refs, Refs& left, 
                 rok = ClipSphereToAABB(rclip, float3(prim.obj.sphere.pos), prim.obj.sphere.r, rout);
             }
             clippedCount++;
-            if (lok) left.push_back({ lout, r.idx });
-            if (rok) right.push_back({ rout, r.idx });
+            if (lok) left.push_back({ lout, r.idx, true });
+            if (rok) right.push_back({ rout, r.idx, true });
         } else if (mx <= splitPos) left.push_back(r);
         else right.push_back(r);
     }

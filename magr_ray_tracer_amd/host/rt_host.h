@@ -55,7 +55,7 @@ struct Aabb {
     float Center(int axis) const { return (bmin[axis] + bmax[axis]) * 0.5f; }
 };
 
-struct BVHPrimData { Aabb box; uint32_t idx = 0; };
+struct BVHPrimData { Aabb box; uint32_t idx = 0; bool clipped = false; };   // clipped: a fragment of a spatial split (see RefBounds)
 
 // reference: src/bvh.h:4-40
 class BVH2 {

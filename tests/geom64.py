@@ -1,0 +1,541 @@
+"""Float64 ground truth of ray traversal: brute-force closest hit and any-hit over every primitive a test added, and generators of
+adversarial ray sets.
+
+Every traversal test elsewhere is relative (HIP against the oracle, the oracle against the reference's kernels) and all of them walk
+the node arrays of the same host builder, so a tree that loses a hit loses it everywhere.  Here the answer comes from the primitives
+alone: the triangles and spheres a test added, per BLAS, never `primIdx` or the node arrays.
+
+The kernels' acceptance rules (test_prim, rt355_kernels.h; primitives.cl:11-89):
+    triangle  |det| >= 1e-8, u >= 0, v >= 0, u + v <= 1, 0 <= t <= ray.t
+    sphere    b = oc.D, c = oc.oc - r^2, d = b^2 - c > 0; nearest root -b -+ sqrt(d) with 0 < t < ray.t (the formula takes D as
+              unit, see _sph_group)
+    connect   occluded iff some primitive is accepted with t < tmax
+A ray is DECIDABLE when float32 rounding cannot change the answer: the nearest hit and every primitive that nearly competes with it
+are clear of their edges, of grazing incidence, of t = 0 and of tmax, and the second-nearest hit is farther than both error bounds.
+Only decidable rays are asserted.  Planes are not part of the ground truth: the builder gives them an empty box (accel_build.cpp,
+reference behaviour), so traversal never reports one.
+"""
+import hashlib
+
+import numpy as np
+
+from magr_ray_tracer_amd import _lib as W
+
+# ---- decidability thresholds (one place; fixed, never tuned per case) -------------------------------------------------------------
+EPS32 = 2.0 ** -24          # float32 unit roundoff
+# Each float32 quantity of the kernel's triangle / sphere test is a chain of a few roundings per operand (origin and vertex
+# differences, a cross product and a dot of fused multiply-adds, a reciprocal; the instance transform adds three dots), each
+# eps * |operand|.  The bounds below are first-order conditioning estimates with all operand magnitudes summed, times 16 roundings:
+# about twice the longest chain.  (On the CPU suite's scenes the largest error seen is a few percent of its bound.)
+K_ULP = 16
+# The kernel drops a triangle whose |det| is below 1e-8 (an absolute cut, whatever the triangle's size): a hit whose |det| is within
+# a factor 100 of it may fall on either side once det carries its own rounding.
+DET_FLOOR = 1e-6
+# Grazing measure |det| / (|e1| |e2| |D|) = sine of the angle between ray and triangle plane.  Below 1e-3 the barycentric error
+# bound (which grows as 1 / sine) is no longer first order: such a hit is never decided.
+GRAZE_MIN = 1e-3
+# A sphere hit whose discriminant lies within this fraction of r^2 |D|^2 of zero is a tangent ray: which of 0, 1 or 2 roots float32
+# sees is not decided (the kernel's d <= 0 test, and its unit-D formula for a D whose length is 1 only to a few ulp).
+SPHERE_TANGENT = 1e-5
+# |D|^2 farther than this from 1: the kernel's sphere test (written for a unit D) does not measure t in ray-parameter units
+NONUNIT_D = 1e-3
+FAR = np.float32(1e30)      # RT_REALLYFAR: ray.t of an extension ray before traversal
+
+# minimum decidable fraction of a ray set: a set must not pass by being all ambiguous
+# (shadow rays: each ends 2 * RT_EPSILON short of the point it samples on a light, so the light's own triangle - and its neighbour
+# across the quad's diagonal - sits just beyond tmax; seen at a shallow angle that contact is inside the error bound of t.  In a
+# closed room, whose walls see a ceiling light at shallow angles, that is up to a third of the shadow rays of the later bounces)
+# (bounce rays: a sphere that an extension ray with a non-unit D passes through is an ambiguous contact, see _sph_group; later
+# bounces carry more such directions - up to 11 % of the rays of a scene with spheres)
+MIN_DECIDABLE = {"camera": 0.95, "bounce": 0.85, "adversarial": 0.80, "shadow": 0.60}
+
+
+def _cross(a, b):
+    return np.stack([a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1], a[..., 2] * b[..., 0] - a[..., 0] * b[..., 2],
+                     a[..., 0] * b[..., 1] - a[..., 1] * b[..., 0]], axis=-1)
+
+
+def _norm(a):
+    return np.sqrt((a * a).sum(-1))
+
+
+# ---- scene description (what the test added) ----------------------------------------------------------------------------------------
+class GTScene:
+    """Wraps a magr_ray_tracer_amd Scene: every triangle and sphere goes through here, so the ground truth knows each primitive's
+    global index (its position in the primitive array: the order of addition) and its BLAS."""
+
+    def __init__(self, scene):
+        self.s = scene
+        self.blas = [self._new()]
+
+    @staticmethod
+    def _new():
+        return dict(tri=[], tri_idx=[], sph_c=[], sph_r=[], sph_idx=[])
+
+    def triangles(self, verts, mat):
+        v = np.ascontiguousarray(verts, dtype=np.float32).reshape(-1, 3, 3)
+        b = self.blas[-1]
+        b["tri"].append(v.astype(np.float64))
+        b["tri_idx"].append(np.arange(self.s.num_prims, self.s.num_prims + len(v)))
+        self.s.AddTriangles(v, mat)
+
+    def sphere(self, pos, r, mat):
+        b = self.blas[-1]
+        b["sph_c"].append(np.asarray(pos, np.float32).astype(np.float64))
+        b["sph_r"].append(float(np.float32(r)))
+        b["sph_idx"].append(self.s.num_prims)
+        self.s.AddSphere(pos, r, mat)
+
+    def light(self, verts, mat):
+        """An emissive triangle (a light); it is geometry like any other."""
+        self.triangles(np.asarray(verts, np.float32).reshape(1, 3, 3), mat)
+
+    def build_blas(self, alpha):
+        """Close the current BLAS: BuildBLAS over the primitives added since the previous one."""
+        start = min([int(a[0]) for a in self.blas[-1]["tri_idx"]] + self.blas[-1]["sph_idx"])
+        self.s.BuildBLAS(start, alpha)
+        self.blas.append(self._new())
+
+    def finish(self):
+        """Scene arrays (BVH4 collapse and TLAS built) and the frozen per-BLAS primitive sets."""
+        if not (self.blas[-1]["tri"] or self.blas[-1]["sph_idx"]):
+            self.blas.pop()
+        sa = self.s.arrays()
+        assert len(sa.blas) == len(self.blas), (len(sa.blas), len(self.blas))
+        self.sets = []
+        for b in self.blas:
+            tri = np.concatenate(b["tri"]) if b["tri"] else np.zeros((0, 3, 3))
+            tid = np.concatenate(b["tri_idx"]) if b["tri_idx"] else np.zeros(0, np.int64)
+            self.sets.append(dict(tri=tri, tri_idx=tid, sph_c=np.array(b["sph_c"]).reshape(-1, 3), sph_r=np.array(b["sph_r"]),
+                                  sph_idx=np.array(b["sph_idx"], np.int64)))
+        # exact duplicates (the same three float32 vertices in the same order, in the same BLAS) are ties: any of them is the right answer
+        n = len(sa.prims)
+        self.dup = np.arange(n)
+        seen = {}
+        for b, st in enumerate(self.sets):
+            for v, i in zip(st["tri"], st["tri_idx"]):
+                k = (b, v.astype(np.float32).tobytes())
+                self.dup[i] = seen.setdefault(k, int(i))
+        self.sa = sa
+        return sa
+
+
+def instance_maps(sa):
+    """Per BLAS: (A, t) of invT (world -> instance: p' = A p + t) in float64 of the uploaded float32 values, and the inverse map."""
+    out = []
+    for inst in sa.blas:
+        T = inst["invT"].astype(np.float64).reshape(4, 4)
+        A, t = T[:3, :3], T[:3, 3]
+        Ai = np.linalg.inv(A)
+        out.append((A, t, Ai))
+    return out
+
+
+# ---- per-group brute force ------------------------------------------------------------------------------------------------------------
+def _tri_group(O, D, tmax, extra, V, idx, dup, out):
+    """Triangles V (M,3,3) against rays O, D (n,3) in the primitives' own space.  Updates the running per-ray record `out`."""
+    M = len(V)
+    if M == 0:
+        return
+    v0, e1, e2 = V[:, 0], V[:, 1] - V[:, 0], V[:, 2] - V[:, 0]
+    l1, l2 = _norm(e1), _norm(e2)
+    nD = _norm(D)
+    step = max(1, 400000 // M)
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        for s in range(0, len(O), step):
+            sl = slice(s, s + step)
+            o, d, tm, ex, nd = O[sl, None, :], D[sl, None, :], tmax[sl, None], extra[sl, None], nD[sl, None]
+            pvec = _cross(np.broadcast_to(d, (d.shape[0], M, 3)), e2[None])
+            det = (e1[None] * pvec).sum(-1)
+            tvec = o - v0[None]
+            inv = 1.0 / det
+            u = (tvec * pvec).sum(-1) * inv
+            qvec = _cross(tvec, e1[None])
+            v = (d * qvec).sum(-1) * inv
+            t = (e2[None] * qvec).sum(-1) * inv
+            adet = np.abs(det)
+            # absolute error of the origin-to-vertex difference (and of the instance transform); the edges, cross products and dots
+            # carry relative errors, which enter through 1 / graze
+            mag = _norm(tvec) + ex
+            graze = adet / (l1 * l2 * nd)
+            tol_b = K_ULP * EPS32 * (mag * nd * np.maximum(l1, l2) / adet + 1.0 / graze)
+            tol_t = K_ULP * EPS32 * (mag + np.abs(t) * nd) * l1 * l2 / adet
+            m = np.minimum(np.minimum(u, v), 1.0 - u - v)
+            finite = np.isfinite(t) & np.isfinite(m) & np.isfinite(tol_b)
+            good = finite & (adet >= DET_FLOOR) & (graze >= GRAZE_MIN)
+            sure = good & (m > tol_b) & (t > tol_t) & (t < tm - tol_t)
+            maybe = finite & (m >= -tol_b) & (t >= -tol_t) & (t <= tm + tol_t)
+            # a ray parallel to the plane (det ~ 0): no hit unless it runs IN the plane, which is a degenerate contact
+            npl = _cross(e1, e2)
+            npl = npl / np.maximum(_norm(npl), 1e-300)[:, None]
+            inplane = ~finite & (np.abs((tvec * npl[None]).sum(-1)) <= K_ULP * EPS32 * mag)
+            amb = (maybe & ~sure) | inplane
+            _merge(out, sl, t, np.where(finite, tol_t, np.inf), sure, amb, idx, dup, u=u, v=v, tol_b=tol_b)
+
+
+def _sph_group(O, D, tmax, extra, C, R, idx, dup, out):
+    M = len(C)
+    if M == 0:
+        return
+    # The kernel's formula (b = oc.D, c = oc.oc - r^2, roots -b -+ sqrt(b^2 - c)) takes D as unit.  For a D of unit length to a few
+    # ulp (camera rays, rays into instances under a rigid transform) it is the geometric quadratic, evaluated here with a = |D|^2 and
+    # its deviation from 1 carried in the bounds.  Shade's extension rays may have a D whose xyz are far from unit (the reference
+    # normalises a float4 whose w lane is not zero): the kernel's "t" of a sphere is then not the ray
+    # parameter the slab tests prune with, whether the sphere is reported depends on the visit order, and every sphere such a ray
+    # passes through is an ambiguous contact.
+    a = (D * D).sum(-1)[:, None]
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        oc = O[:, None, :] - C[None]
+        b = (oc * D[:, None, :]).sum(-1)
+        c = (oc * oc).sum(-1) - (R * R)[None]
+        disc = b * b - a * c
+        S = (oc * oc).sum(-1) + (R * R)[None]
+        nonunit = np.abs(a - 1.0) > NONUNIT_D
+        dev = np.where(nonunit, 0.0, np.abs(a - 1.0))          # (a non-unit ray's contacts are ambiguous anyway: geometric bounds)
+        err_disc = K_ULP * EPS32 * (S * a + b * b) + dev * np.abs(c)
+        sq = np.sqrt(np.maximum(disc, 0.0))
+        t0, t1 = (-b - sq) / a, (-b + sq) / a
+        noc = np.sqrt(S)
+        # |sqrt(d') - sqrt(d)| <= |d' - d| / (sqrt(d) + sqrt(d - |d' - d|)): exact, not first order, near a tangent
+        tol = (K_ULP * EPS32 * (noc + extra[:, None]) + dev * (np.abs(b) + sq) / a +
+               err_disc / (sq + np.sqrt(np.maximum(disc - err_disc, 0.0))))
+        tm = tmax[:, None]
+        tangent = np.abs(disc) <= np.maximum(2.0 * err_disc, SPHERE_TANGENT * (R * R)[None] * a)
+        real = (disc > 0) & ~tangent
+        # nearest accepted root; either root within its error of 0 or of tmax is a contact that float32 may see either way
+        near0 = real & (np.abs(t0) <= tol) | real & (np.abs(t1) <= tol) | real & (np.abs(t0 - tm) <= tol) | real & (np.abs(t1 - tm) <= tol)
+        tt = np.where(real & (t0 > tol) & (t0 < tm - tol), t0, np.where(real & (t1 > tol) & (t1 < tm - tol), t1, np.inf))
+        sure = np.isfinite(tt) & ~near0 & ~nonunit
+        amb = near0 | (tangent & (t1 >= -tol) & (t0 <= tm + tol)) | (nonunit & (disc > -err_disc) & (t1 > -tol) & (t0 < tm + tol))
+        tamb = np.where(near0, np.minimum(np.where(np.abs(t0) <= tol, t0, np.inf), np.where(np.abs(t1) <= tol, t1, np.inf)), t0)
+        tamb = np.where(near0 & ~np.isfinite(tamb), tm, tamb)
+        t = np.where(sure, tt, tamb)
+        _merge(out, slice(0, len(O)), t, tol, sure, amb, idx, dup)
+
+
+def _merge(out, sl, t, tol_t, sure, amb, idx, dup, u=None, v=None, tol_b=None):
+    """One group's (n, M) results -> per-ray record of the group (rows `sl` of `out`): nearest sure hit, the nearest sure hit of
+    another duplicate class (its lower bound t - tol), and the nearest ambiguous contact (its lower bound)."""
+    n = t.shape[0]
+    rows = np.arange(n)
+    ts = np.where(sure, t, np.inf)
+    j = np.argmin(ts, axis=1)
+    gd = dup[idx]
+    out["t"][sl] = ts[rows, j]
+    out["tol"][sl] = np.where(np.isfinite(ts[rows, j]), tol_t[rows, j], 0.0)
+    out["prim"][sl] = np.where(np.isfinite(ts[rows, j]), idx[j], -1)
+    out["dup"][sl] = np.where(np.isfinite(ts[rows, j]), gd[j], -1)
+    out["t2"][sl] = np.where(sure & (gd[None, :] != gd[j][:, None]), t - tol_t, np.inf).min(axis=1)
+    out["amb"][sl] = np.where(amb, np.where(np.isfinite(t), t - tol_t, -np.inf), np.inf).min(axis=1)
+    out["any_sure"][sl] = sure.any(axis=1)
+    out["tri"][sl] = u is not None
+    if u is not None:
+        out["u"][sl], out["v"][sl], out["tol_b"][sl] = u[rows, j], v[rows, j], tol_b[rows, j]
+
+
+def _group_record(n):
+    return dict(t=np.full(n, np.inf), tol=np.zeros(n), t2=np.full(n, np.inf), amb=np.full(n, np.inf), prim=np.full(n, -1, np.int64),
+                dup=np.full(n, -1, np.int64), u=np.zeros(n), v=np.zeros(n), tol_b=np.zeros(n), tri=np.zeros(n, bool),
+                any_sure=np.zeros(n, bool))
+
+
+def closest_hit(gt, O, D, tmax=None):
+    """Float64 closest hit of world rays O, D (float32 arrays (n,3) or (n,4)) over every primitive of the GTScene `gt`.
+    Returns a dict of per-ray arrays: hit, prim, dup (duplicate class), t, tol (error bound of t), u, v, tol_b (triangles),
+    tri (hit is a triangle), any_sure (some primitive is surely hit before tmax), decidable."""
+    # (traversal tests primitives in instance space, where transformRay has zeroed the w lanes: xyz only)
+    O = np.asarray(O, np.float32)[:, :3].astype(np.float64)
+    D = np.asarray(D, np.float32)[:, :3].astype(np.float64)
+    n = len(O)
+    tm = np.full(n, float(FAR)) if tmax is None else np.asarray(tmax, np.float32).astype(np.float64)
+    key = hashlib.sha1(O.tobytes() + D.tobytes() + tm.tobytes()).hexdigest()
+    cache = gt.__dict__.setdefault("_cache", {})
+    if key in cache:
+        return cache[key]
+    groups = []
+    for st, (A, tr, _) in zip(gt.sets, instance_maps(gt.sa)):
+        Oi, Di = O @ A.T + tr, D @ A.T
+        # the instance transform rounds the origin to eps * (|A| |O| + |t|): carried as an extra origin magnitude
+        ident = np.array_equal(A, np.eye(3)) and not tr.any()
+        extra = np.zeros(n) if ident else np.abs(A).sum(1).max() * _norm(O) + _norm(tr)
+        for kind in ("tri", "sph"):
+            g = _group_record(n)
+            if kind == "tri":
+                _tri_group(Oi, Di, tm, extra, st["tri"], st["tri_idx"], gt.dup, g)
+            else:
+                _sph_group(Oi, Di, tm, extra, st["sph_c"], st["sph_r"], st["sph_idx"], gt.dup, g)
+            groups.append(g)
+    T = np.stack([g["t"] for g in groups])
+    w = np.argmin(T, axis=0)
+    rows = np.arange(n)
+    out = {k: np.stack([g[k] for g in groups])[w, rows] for k in groups[0]}
+    lower = np.stack([g["t"] - g["tol"] for g in groups])
+    lower[w, rows] = np.inf
+    out["t2"] = np.minimum(out["t2"], lower.min(axis=0))          # the other groups' nearest sure hits compete with the winner
+    out["amb"] = np.stack([g["amb"] for g in groups]).min(axis=0)
+    out["any_sure"] = np.stack([g["any_sure"] for g in groups]).any(axis=0)
+    hit = np.isfinite(out["t"])
+    # decidable: no ambiguous contact and no competitor within the error bounds of the winner (miss: none anywhere before tmax)
+    lim = np.where(hit, out["t"] + out["tol"], np.inf)
+    dec = np.where(hit, (out["amb"] > lim) & (out["t2"] > lim), out["amb"] == np.inf)
+    out.update(hit=hit, decidable=dec)
+    cache[key] = out
+    return out
+
+
+def any_hit(gt, O, D, tmax):
+    """Float64 occlusion of shadow rays (origin, dir, tmax): occluded iff some primitive is hit with 0 <= t < tmax.
+    Returns (occluded, decidable): a ray with one sure hit is occluded whatever else; a ray without is decided only if no
+    primitive comes near it."""
+    r = closest_hit(gt, O, D, tmax)
+    occ = r["any_sure"]
+    dec = occ | (r["amb"] == np.inf)
+    return occ, dec
+
+
+# ---- ray records ----------------------------------------------------------------------------------------------------------------------------
+def make_rays(O, D):
+    """RtRay records ready for rt_debug_set_rays / Oracle.extend: rD = 1.0f / D in float32 (all four lanes, as initRay), t = 1e30."""
+    O = np.asarray(O, np.float32)
+    D = np.asarray(D, np.float32)
+    r = np.zeros(len(O), dtype=W.Ray)
+    r["O"][:, :3], r["D"][:, :3] = O[:, :3], D[:, :3]
+    with np.errstate(divide="ignore", over="ignore"):
+        r["rD"] = np.float32(1.0) / r["D"]
+    r["t"], r["primIdx"], r["pixelIdx"] = FAR, -1, np.arange(len(O))
+    r["intensity"] = 1.0
+    r["bounces"] = 1
+    return r
+
+
+def _unit32(v):
+    v = np.asarray(v, np.float64)
+    return (v / _norm(v)[:, None]).astype(np.float32)
+
+
+def _rand_dirs(rng, n):
+    return _unit32(rng.normal(size=(n, 3)))
+
+
+def scene_bounds(sa):
+    root = sa.tlas[0]
+    return root["aabbMin"][:3].astype(np.float64), root["aabbMax"][:3].astype(np.float64)
+
+
+def box_planes(sa, accel):
+    """(axis, value) of every box face in the uploaded arrays: BVH2 nodes or BVH4 child boxes, and TLAS nodes."""
+    pl = []
+    if accel == W.ACCEL_BVH4:
+        live = sa.bvh4["count"] != -1
+        for k in (0, 1, 2):
+            for f in ("aabbMin", "aabbMax"):
+                vals = sa.bvh4[f][..., k][live & (sa.bvh4["count"] >= 0) & (np.abs(sa.bvh4[f][..., k]) < 1e29)]
+                pl += [(k, x) for x in np.unique(vals)]
+    else:
+        for k in (0, 1, 2):
+            for f in ("aabbMin", "aabbMax"):
+                vals = sa.bvh2[f][:, k][np.abs(sa.bvh2[f][:, k]) < 1e29]
+                pl += [(k, x) for x in np.unique(vals)]
+    for k in (0, 1, 2):
+        for f in ("aabbMin", "aabbMax"):
+            pl += [(k, x) for x in np.unique(sa.tlas[f][:, k])]
+    return pl
+
+
+def split_planes(sa):
+    """SBVH split planes: the faces a left and a right child share (left.bmax == right.bmin on the split axis)."""
+    n = sa.bvh2
+    inner = np.where(n["count"] == 0)[0]
+    inner = inner[n["first"][inner] + 1 < len(n)]
+    out = []
+    for i in inner:
+        c1, c2 = n[n["first"][i]], n[n["first"][i] + 1]
+        for k in (0, 1, 2):
+            if c1["aabbMax"][k] == c2["aabbMin"][k]:
+                out.append((k, c1["aabbMax"][k]))
+            if c2["aabbMax"][k] == c1["aabbMin"][k]:
+                out.append((k, c2["aabbMax"][k]))
+    return out
+
+
+def axis_rays_on_planes(rng, sa, planes, n):
+    """Origins exactly on the given (axis, value) planes, inside the scene box; directions axis-parallel with one or two zero
+    components (+0.0 and -0.0 both).  Half the rays run IN their plane (the plane's own component of D is a signed zero)."""
+    lo, hi = scene_bounds(sa)
+    pick = rng.integers(0, len(planes), n)
+    O = (lo + (hi - lo) * rng.uniform(0.02, 0.98, (n, 3))).astype(np.float32)
+    D = np.zeros((n, 3), np.float32)
+    zs = np.where(rng.random((n, 3)) < 0.5, np.float32(-0.0), np.float32(0.0))
+    for i in range(n):
+        a, val = planes[pick[i]]
+        O[i, a] = val
+        D[i] = zs[i]
+        other = [k for k in (0, 1, 2) if k != a]
+        if rng.random() < 0.5:                    # in the plane, along one other axis
+            D[i, other[rng.integers(0, 2)]] = rng.choice([-1.0, 1.0])
+        elif rng.random() < 0.5:                  # in the plane, two non-zero components
+            v = rng.normal(size=2)
+            v /= np.linalg.norm(v)
+            D[i, other[0]], D[i, other[1]] = v
+        else:                                     # across the plane: two zero components
+            D[i, a] = rng.choice([-1.0, 1.0])
+    return make_rays(O, D)
+
+
+def axis_rays(rng, sa, n):
+    """Axis-parallel rays from random origins in the scene box: one or two zero components, signed zeros."""
+    lo, hi = scene_bounds(sa)
+    O = (lo + (hi - lo) * rng.uniform(0.02, 0.98, (n, 3))).astype(np.float32)
+    D = np.where(rng.random((n, 3)) < 0.5, np.float32(-0.0), np.float32(0.0))
+    a = rng.integers(0, 3, n)
+    two = rng.random(n) < 0.5
+    for i in range(n):
+        if two[i]:
+            D[i, a[i]] = rng.choice([-1.0, 1.0])
+        else:
+            k = [x for x in (0, 1, 2) if x != a[i]]
+            v = rng.normal(size=2)
+            v /= np.linalg.norm(v)
+            D[i, k[0]], D[i, k[1]] = v
+    return make_rays(O, D)
+
+
+def inside_box_rays(rng, boxes, n):
+    """Origins inside the given boxes ((k,3) min, (k,3) max), random directions and (a quarter) axis directions."""
+    mn, mx = boxes
+    pick = rng.integers(0, len(mn), n)
+    O = (mn[pick] + (mx[pick] - mn[pick]) * rng.uniform(0.05, 0.95, (n, 3))).astype(np.float32)
+    D = _rand_dirs(rng, n)
+    ax = rng.random(n) < 0.25
+    D[ax] = 0
+    D[ax, rng.integers(0, 3, int(ax.sum()))] = rng.choice([-1.0, 1.0], int(ax.sum()))
+    return make_rays(O, D)
+
+
+def node_boxes(sa, accel):
+    if accel == W.ACCEL_BVH4:
+        live = sa.bvh4["count"] >= 0
+        return sa.bvh4["aabbMin"][live][:, :3].astype(np.float64), sa.bvh4["aabbMax"][live][:, :3].astype(np.float64)
+    ok = sa.bvh2["aabbMax"][:, 0] >= sa.bvh2["aabbMin"][:, 0]
+    return sa.bvh2["aabbMin"][ok][:, :3].astype(np.float64), sa.bvh2["aabbMax"][ok][:, :3].astype(np.float64)
+
+
+def tlas_leaf_boxes(sa):
+    leaf = sa.tlas["leftRight"] == 0
+    return sa.tlas["aabbMin"][leaf][:, :3].astype(np.float64), sa.tlas["aabbMax"][leaf][:, :3].astype(np.float64)
+
+
+def _world(gt, b, P):
+    A, t, Ai = instance_maps(gt.sa)[b]
+    return (P - t) @ Ai.T
+
+
+def inside_sphere_rays(rng, gt, n):
+    C, R = [], []
+    for b, st in enumerate(gt.sets):
+        for c, r in zip(st["sph_c"], st["sph_r"]):
+            C.append(_world(gt, b, c[None])[0])
+            R.append(r)
+    C, R = np.array(C), np.array(R)
+    pick = rng.integers(0, len(C), n)
+    d = rng.normal(size=(n, 3))
+    d /= _norm(d)[:, None]
+    O = (C[pick] + d * (R[pick] * rng.uniform(0.0, 0.9, n))[:, None]).astype(np.float32)
+    return make_rays(O, _rand_dirs(rng, n))
+
+
+def world_triangles(gt):
+    """(M,3,3) world-space vertices of every triangle (float64), with global indices."""
+    V, I = [], []
+    for b, st in enumerate(gt.sets):
+        if len(st["tri"]):
+            V.append(_world(gt, b, st["tri"].reshape(-1, 3)).reshape(-1, 3, 3))
+            I.append(st["tri_idx"])
+    return np.concatenate(V), np.concatenate(I)
+
+
+def far_rays(rng, gt, n, dist=2e3):
+    """Origins thousands of units away (250 scene extents), aimed at triangle centroids: robust hits deep in the tree.  (Only for scenes without spheres: the
+    kernels' sphere test forms c = |oc|^2 - r^2 in float32, which from that far away cancels to an error of several units, so every sphere
+    anywhere near such a ray is rightly undecidable.)"""
+    V, _ = world_triangles(gt)
+    c = V[rng.integers(0, len(V), n)].mean(1)
+    d = rng.normal(size=(n, 3))
+    d /= _norm(d)[:, None]
+    O = (c + dist * d).astype(np.float32)
+    return make_rays(O, _unit32(c - O.astype(np.float64)))
+
+
+def tiny_component_rays(rng, gt, n):
+    """Directions with one or two components of ~1e-30 (rD ~ 1e30) or of a subnormal 1e-39 (rD overflows to +-inf without a zero
+    in D), aimed near triangle centroids from inside the scene."""
+    V, _ = world_triangles(gt)
+    c = V[rng.integers(0, len(V), n)].mean(1)
+    D = np.zeros((n, 3), np.float32)
+    a = rng.integers(0, 3, n)
+    D[np.arange(n), a] = rng.choice([-1.0, 1.0], n)
+    tiny = np.where(rng.random(n) < 0.5, np.float32(1e-30), np.float32(1e-39))
+    for i in range(n):
+        others = [k for k in (0, 1, 2) if k != a[i]]
+        for k in (others if rng.random() < 0.5 else others[:1]):
+            D[i, k] = tiny[i] * rng.choice([-1.0, 1.0])
+    O = (c - D.astype(np.float64) * rng.uniform(0.5, 3.0, n)[:, None]).astype(np.float32)
+    return make_rays(O, D)
+
+
+def vertex_edge_rays(rng, gt, n, V=None, box=None):
+    """Rays aimed exactly at triangle vertices and edge midpoints (of V, world space; default every triangle) from random origins
+    in `box` (default the scene box): contacts on an edge.  Expected to be classified undecidable (not asserted)."""
+    V = world_triangles(gt)[0] if V is None else V
+    lo, hi = scene_bounds(gt.sa) if box is None else (np.asarray(box[0], np.float64), np.asarray(box[1], np.float64))
+    tri = V[rng.integers(0, len(V), n)]
+    k = rng.integers(0, 3, n)
+    P = np.where((rng.random(n) < 0.5)[:, None], tri[np.arange(n), k], 0.5 * (tri[np.arange(n), k] + tri[np.arange(n), (k + 1) % 3]))
+    O = (lo + (hi - lo) * rng.uniform(0.02, 0.98, (n, 3))).astype(np.float32)
+    return make_rays(O, _unit32(P - O.astype(np.float64)))
+
+
+# ---- comparison ------------------------------------------------------------------------------------------------------------------------
+def compare(gt, rays, got, kind, what):
+    """Assert `got` (RtRay records after extend) against the float64 closest hit of `rays` (the records before extend).
+    Returns the decidable fraction.  kind: "camera", "bounce" or "adversarial" (minimum decidable fraction)."""
+    r = closest_hit(gt, rays["O"], rays["D"])
+    dec = r["decidable"]
+    frac = float(dec.mean()) if len(dec) else 1.0
+    assert frac >= MIN_DECIDABLE[kind], f"{what}: only {frac:.3f} of {len(dec)} rays decidable (floor {MIN_DECIDABLE[kind]})"
+    hit = r["hit"]
+    gp = got["primIdx"].astype(np.int64)
+    bad_hit = dec & (hit != (gp != -1))
+    ok_prim = np.where(gp >= 0, gt.dup[np.maximum(gp, 0)] == r["dup"], False)
+    bad_prim = dec & hit & (gp != -1) & ~ok_prim
+    idx = np.where(bad_hit | bad_prim)[0]
+    if len(idx):
+        lines = [f"  ray {i}: O={rays['O'][i][:3].tolist()} D={rays['D'][i][:3].tolist()} truth prim {r['prim'][i]} t={r['t'][i]:.7g}, "
+                 f"got prim {gp[i]} t={float(got['t'][i]):.7g}" for i in idx[:8]]
+        raise AssertionError(f"{what}: {len(idx)} of {int(dec.sum())} decidable rays wrong (missed {int((bad_hit & hit).sum())}, "
+                             f"phantom {int((bad_hit & ~hit).sum())}, other primitive {int(bad_prim.sum())})\n" + "\n".join(lines))
+    h = dec & hit
+    tg = got["t"].astype(np.float64)
+    et = np.abs(tg[h] - r["t"][h])
+    assert np.all(et <= r["tol"][h]), f"{what}: t off by {et.max():.3g} (bound {r['tol'][h][np.argmax(et - r['tol'][h])]:.3g})"
+    tri = h & r["tri"]
+    for f in ("u", "v"):
+        e = np.abs(got[f][tri].astype(np.float64) - r[f][tri])
+        assert np.all(e <= r["tol_b"][tri]), f"{what}: {f} off by {e.max():.3g}"
+    Ot, Dt = rays["O"][h][:, :3].astype(np.float64), rays["D"][h][:, :3].astype(np.float64)
+    I = Ot + Dt * r["t"][h][:, None]
+    eI = _norm(got["I"][h][:, :3].astype(np.float64) - I)
+    bI = r["tol"][h] * _norm(Dt) + K_ULP * EPS32 * (_norm(I) + _norm(Ot))
+    assert np.all(eI <= bI), f"{what}: hit point off by {eI.max():.3g}"
+    return frac
+
+
+def rows_differ(a, b):
+    """Per row of two float32 arrays (n, k): does any element differ bit for bit (+0 and -0 count as equal)?"""
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    bad = (a.view(np.uint32) != b.view(np.uint32)) & ~((a == 0) & (b == 0))
+    return bad.reshape(len(a), -1).any(axis=1)
+
+
+def mismatch_rows(a, b):
+    return int(rows_differ(a, b).sum())

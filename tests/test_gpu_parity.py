@@ -616,8 +616,15 @@ def test_persistent_wavefronts_vs_oracle(accel, monkeypatch):
     assert bits_equal(out[0][0], out[1][0]) and np.array_equal(out[0][1], out[1][1]) and np.array_equal(out[0][3], out[1][3])
 
 
-@pytest.mark.parametrize("stack,flat", [("lds", "0,0"), ("spill", "0,0"), ("spill", "1,0"), ("lds", "1,1")])
-def test_persistent_wavefronts_through_a_tlas_vs_oracle(stack, flat, monkeypatch):
+_TLAS_CACHE = {}
+
+
+@pytest.mark.parametrize("stack,flat,backup", [pytest.param("lds", "0,0", "1", id="lds-0,0"), pytest.param("spill", "0,0", "1", id="spill-0,0"),
+                                               pytest.param("spill", "1,0", "1", id="spill-1,0"), pytest.param("lds", "1,1", "1", id="lds-1,1"),
+                                               pytest.param("lds", "0,0", "0", id="lds-0,0-no-backup"),
+                                               pytest.param("spill", "0,0", "0", id="spill-0,0-no-backup"),
+                                               pytest.param("spill", "1,0", "0", id="spill-1,0-no-backup")])
+def test_persistent_wavefronts_through_a_tlas_vs_oracle(stack, flat, backup, monkeypatch):
     """k_trace_persist_tlas (BASELINE config 5's kernel: persistent wavefronts through a multi-BLAS TLAS, TLAS entries on the BLAS stack
     column, the ray transformed once on entering an instance and fetched back from the queue on leaving it).  One workgroup per CU
     brings its long-queue threshold down to 65,536 rays, so a 640x360 frame runs bounces >= 1 and connect through the event loop and
@@ -631,6 +638,8 @@ def test_persistent_wavefronts_through_a_tlas_vs_oracle(stack, flat, monkeypatch
     # "e,c": extend / connect through the kernel's event loop (0) or its one-ray-per-lane branch striding over the queue (1; the library's
     # default for multi-BLAS scenes is 1,0)
     monkeypatch.setenv("RT355_TLAS_FLAT", flat)
+    # "backup" 0: RT355_TLAS_BACKUP=0, the world ray is fetched back from the queue on leaving an instance instead of waiting in LDS
+    monkeypatch.setenv("RT355_TLAS_BACKUP", backup)
     Wd, Hd = 960, 540          # bounce 1 still holds more than 65,536 rays
     from magr_ray_tracer_amd.scenes import Scene, _std_materials, box_tris, param_surface
 
@@ -652,11 +661,12 @@ def test_persistent_wavefronts_through_a_tlas_vs_oracle(stack, flat, monkeypatch
         return s, dict(origin=(0.4, 2.2, 5.5), forward=(0.05, 0.2, 0.97), fov=65.0, aperture=0.02)
 
     for name, fn in (("two SBVH BLAS", lambda: scenes.two_blas_scene(0.0, 48)), ("three BLAS, one rotated", three_blas)):
-        s, view = fn()
-        sa = s.arrays()
-        cam = scenes.camera_for(view, Wd, Hd)
-        o = Oracle(sa, Wd, Hd, **DEFAULT)
-        ref, seeds, e, c = o.render(cam, 2)
+        if name not in _TLAS_CACHE:     # the scene and the oracle's frame do not depend on the kernel path: once per scene
+            s, view = fn()
+            sa = s.arrays()
+            cam = scenes.camera_for(view, Wd, Hd)
+            _TLAS_CACHE[name] = (sa, cam) + tuple(Oracle(sa, Wd, Hd, **DEFAULT).render(cam, 2))
+        sa, cam, ref, seeds, e, c = _TLAS_CACHE[name]
         out = []
         for variant in (0, 4):
             d = Device(Wd, Hd, extend_variant=variant, **DEFAULT)
