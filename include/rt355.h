@@ -58,7 +58,8 @@ typedef struct RtConfig {
                                  * > 0 also selects 256-slot tiles (39 KB of LDS instead of 78): 1 leaves room for the kernels of
                                  * other contexts (best when several sample streams share the GPU)                               */
     int32_t persist_blocks_per_cu; /* workgroups per CU of the persistent traversal grids: 0 = what the hardware admits (7 extend / 6 connect);
-                                 * 4 is best when three contexts share the GPU (their workgroups then fit beside each other)      */
+                                 * 4 is best when three contexts share the GPU (their workgroups then fit beside each other);
+                                 * a group of several lanes picks 2 when four or more of its streams run side by side, else 3       */
     int32_t reserved[1];
 } RtConfig;
 
@@ -141,13 +142,16 @@ int rt_share_scene(RtCtx* ctx, RtCtx* from);
  * accumulator is the sum of the lanes' accumulators in lane order and, after k frames in all, holds k samples per pixel - prep()
  * divides by k exactly as with one stream (postproc.cl:71).  A group of ONE lane is the reference's single Renderer bit for bit.
  * HIP runs kernels of streams that share a hardware queue one after the other (GPU_MAX_HW_QUEUES, the process's own setting):
- * rt_group_create measures how many of the group's streams really run side by side (rt_group_concurrency) and writes one line to
- * stderr when that is fewer than `lanes`. */
+ * rt_group_create measures which of the group's streams really run side by side (S of them: rt_group_concurrency) and writes one
+ * line to stderr when S is fewer than `lanes`.  Frame j of the group is lane (j mod lanes)'s sample, issued on worker stream j mod S:
+ * with S < lanes a lane's frames move between those S streams, strictly in order (each waits on an event recorded behind the lane's
+ * last work), so that no queue renders more frames than another.  rt_stream of a lane is the stream its last frame ran on; work the
+ * caller queues there lands behind it.  The environment variable RT355_GROUP_STREAMS=k caps S at k (tests, A/B runs). */
 typedef struct RtGroup RtGroup;
 int rt_group_create(const RtConfig* cfg, int32_t lanes, RtGroup** out);      /* lanes 1..8; cfg as for rt_create (row band included)   */
 int rt_group_destroy(RtGroup* g);
 int rt_group_lanes(RtGroup* g);
-int rt_group_concurrency(RtGroup* g);                                        /* streams measured to run concurrently at creation        */
+int rt_group_concurrency(RtGroup* g);                                        /* S: streams measured to run concurrently at creation     */
 RtCtx* rt_group_lane(RtGroup* g, int32_t m);                                 /* lane m's context (counters, stage times, debug stages)  */
 uint64_t rt_group_frames(RtGroup* g);                                        /* frames rendered by all lanes since the last reset       */
 int rt_group_upload_scene(RtGroup* g,

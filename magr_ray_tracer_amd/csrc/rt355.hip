@@ -43,7 +43,9 @@ struct SceneBag {
 
 struct RtCtx {
     RtConfig cfg{};
-    hipStream_t stream = nullptr;
+    hipStream_t stream = nullptr;         // where this context's work is queued: `home`, unless a group has moved its frames (rt_group_render)
+    hipStream_t home = nullptr;           // the context's own stream
+    bool queued = true;                   // asynchronous work queued since a group marked the end of this context's last frame
     DevScene sc{};
     DevQueues q{};
     DevVariant var{};
@@ -223,8 +225,9 @@ extern "C" int rt_create(const RtConfig* cfg, RtCtx** out)
         if (c.shade_blocks_per_cu > 0 && c.shade_blocks_per_cu <= 16) ctx->shadeGrid = prop.multiProcessorCount * c.shade_blocks_per_cu;
         if (const char* g = getenv("RT355_SHADE_PER_CU")) { int v = atoi(g); if (v > 0 && v <= 16) ctx->shadeGrid = prop.multiProcessorCount * v; }   // tuning / over-subscription tests
     }
-    hipError_t e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking);
+    hipError_t e = hipStreamCreateWithFlags(&ctx->home, hipStreamNonBlocking);
     if (e != hipSuccess) return fail(RT_E_DEVICE, "hipStreamCreate failed: %s", hipGetErrorString(e));
+    ctx->stream = ctx->home;
     DevQueues& q = ctx->q;
     const size_t n = (size_t)ctx->nPix, nS = n * (size_t)c.max_bounces;
     int rc = RT_OK;
@@ -275,7 +278,7 @@ static void ctx_free(RtCtx* ctx)   // every owned resource; safe on a partially 
     if (ctx->dPostF) (void)hipFree(ctx->dPostF);
     if (ctx->dPostB) (void)hipFree(ctx->dPostB);
     for (auto& e : ctx->evPool) { if (e.a) (void)hipEventDestroy(e.a); if (e.b) (void)hipEventDestroy(e.b); }
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
+    if (ctx->home) (void)hipStreamDestroy(ctx->home);
     delete ctx;
 }
 extern "C" int rt_destroy(RtCtx* ctx)
@@ -802,12 +805,13 @@ extern "C" int rt_bind_accum(RtCtx* ctx, void* devicePtr)
     return RT_OK;
 }
 extern "C" void* rt_accum_device_ptr(RtCtx* ctx) { return ctx ? (void*)ctx->q.accum : nullptr; }
-extern "C" void* rt_stream(RtCtx* ctx) { return ctx ? (void*)ctx->stream : nullptr; }
+extern "C" void* rt_stream(RtCtx* ctx) { if (ctx) ctx->queued = true; return ctx ? (void*)ctx->stream : nullptr; }   // (the caller may queue work there)
 
 extern "C" int rt_reset(RtCtx* ctx)
 {
     if (!ctx) return fail(RT_E_INVALID, "rt_reset: null context");
     HIPCHK(hipSetDevice(ctx->cfg.device));
+    ctx->queued = true;
     hipLaunchKernelGGL(k_reset, dim3((ctx->nPix + kBlock - 1) / kBlock), dim3(kBlock), 0, ctx->stream, ctx->q.accum, ctx->firstPixel, ctx->nPix);
     HIPCHK(hipGetLastError());
     return RT_OK;
@@ -831,6 +835,7 @@ static void frame_state_reset(RtCtx* ctx)
 extern "C" int rt_stage_begin_frame(RtCtx* ctx)
 {
     if (!ctx) return fail(RT_E_INVALID, "rt_stage_begin_frame: null context");
+    ctx->queued = true;
     hipLaunchKernelGGL(k_begin_frame, dim3(1), dim3(256), 0, ctx->stream, ctx->q);
     HIPCHK(hipGetLastError());
     frame_state_reset(ctx);
@@ -839,6 +844,7 @@ extern "C" int rt_stage_begin_frame(RtCtx* ctx)
 static int generate(RtCtx* ctx, const RtCamera* cam, const RtSettings* s, int beginFrame)
 {
     if (beginFrame) frame_state_reset(ctx);
+    ctx->queued = true;
     LAUNCH(ctx, ST_GENERATE, k_generate, grid_for(ctx->nPix), 0, ctx->q, *cam, s ? s->antiAliasing : 1, beginFrame);
     HIPCHK(hipGetLastError());
     ctx->primaryRays += (uint64_t)ctx->nPix;
@@ -853,6 +859,7 @@ extern "C" int rt_stage_generate(RtCtx* ctx, const RtCamera* cam, const RtSettin
 extern "C" int rt_stage_extend(RtCtx* ctx, int32_t bounce, int32_t renderBVH)
 {
     int rc = need_scene(ctx, "rt_stage_extend"); if (rc) return rc;
+    ctx->queued = true;
     if (bounce < 0 || bounce > ctx->cfg.max_bounces) return fail(RT_E_INVALID, "rt_stage_extend: bounce %d outside [0, %d]", bounce, ctx->cfg.max_bounces);
     if (ctx->persist || ctx->persist4 || ctx->persistTlas) { // a queue head is good for one launch per frame; re-arm it if this stage is run again
         if (ctx->cursorUsed[bounce]) HIPCHK(hipMemsetAsync(ctx->q.cursor + bounce, 0, sizeof(int32_t), ctx->stream));
@@ -903,6 +910,7 @@ extern "C" int rt_stage_extend(RtCtx* ctx, int32_t bounce, int32_t renderBVH)
 extern "C" int rt_stage_shade(RtCtx* ctx, int32_t bounce)
 {
     int rc = need_scene(ctx, "rt_stage_shade"); if (rc) return rc;
+    ctx->queued = true;
     // the shadow queue and the counter rows are sized by cfg.max_bounces, not by the compile-time maximum
     if (bounce < 0 || bounce >= ctx->cfg.max_bounces) return fail(RT_E_INVALID, "rt_stage_shade: bounce %d outside [0, %d)", bounce, ctx->cfg.max_bounces);
     // The scan state of bounce b is armed by generate (b = 0) or by shade(b-1); re-arm it by hand when this
@@ -930,6 +938,7 @@ extern "C" int rt_stage_shade(RtCtx* ctx, int32_t bounce)
 extern "C" int rt_stage_connect(RtCtx* ctx, int32_t b0, int32_t b1)
 {
     int rc = need_scene(ctx, "rt_stage_connect"); if (rc) return rc;
+    ctx->queued = true;
     if (b0 < 0 || b1 < b0 || b1 >= ctx->cfg.max_bounces) return fail(RT_E_INVALID, "rt_stage_connect: bounce range [%d,%d] outside [0, %d)", b0, b1, ctx->cfg.max_bounces);
     const int cap = ctx->nPix * (b1 - b0 + 1);
     if (ctx->persist || ctx->persist4 || ctx->persistTlas) {
@@ -1218,6 +1227,14 @@ extern "C" int rt_postproc(RtCtx* ctx, int32_t frames, float vignette, float gam
 // HIP maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4, the null stream included) and runs kernels of streams
 // that share one after the other.  The library leaves that setting to the process that loads it; rt_group_create MEASURES how many of
 // its streams really run side by side, so a caller is told instead of silently serialised.
+//
+// Fewer concurrent streams than lanes must not leave a lane's frames queued behind another's: two lanes on one queue render twice
+// as many frames in series as the rest, which finish at half-time and leave the chip to one context (4 lanes on 3 queues: 41 % of
+// the bench's timed region, profiles/r04_group_streams.txt).  So the group keeps a lane's SAMPLES where they are (frame j is
+// lane j mod L's, with its seeds, accumulator and counters) but issues frame j on worker stream j mod S, the S lane streams found to
+// run side by side.  A lane's `stream` is then the worker that ran its last frame, and everything else it queues (reset, seeds, sum,
+// reads, synchronize, stage events) lands behind that frame.  A move to another worker waits on an event recorded right after the
+// lane's last frame - not on the other lanes' frames queued behind it there - or, when the lane has queued more work since, after that.
 
 __global__ void k_spin(long long ticks, int* sink)
 {
@@ -1243,43 +1260,55 @@ struct RtGroup {
     float4* sum = nullptr;              // lane-ordered sum of the lanes' accumulators (own buffer)
     std::vector<hipEvent_t> done;       // one per lane: "this lane's queued frames are finished", for the sum on lane 0's stream
     uint64_t frames = 0;                // frames rendered by all lanes since the last reset (= the divisor of prep())
-    int concurrent = 0;                 // streams measured to run side by side at creation
+    int concurrent = 0;                 // S = worker.size(): streams measured to run side by side at creation
+    std::vector<int> worker;            // the lanes whose home streams run side by side: frames are issued on these
+    std::vector<hipEvent_t> moved;      // one per lane: the end of its last frame (or of work queued since), waited on by the worker it moves to
     int nextLane = 0;                   // round-robin position, so that successive one-frame calls visit all lanes
+    int nextWorker = 0;                 // the same over the workers
 };
 static constexpr int kMaxLanes = 8;
 
 static void group_free(RtGroup* g)
 {
     if (!g) return;
+    for (RtCtx* c : g->lane) { (void)hipStreamSynchronize(c->stream); c->stream = c->home; }   // a lane may sit on another's stream
     for (RtCtx* c : g->lane) ctx_free(c);
     for (hipEvent_t e : g->done) (void)hipEventDestroy(e);
+    for (hipEvent_t e : g->moved) (void)hipEventDestroy(e);
     if (g->sum) (void)hipFree(g->sum);
     delete g;
 }
-// How many of the group's streams execute concurrently: one single-wave kernel that naps for ~1 ms, first on one stream, then on
-// every stream at once, both timed on the host.  Streams that share a hardware queue run their naps one after the other, so the
-// second figure is `depth` times the first, depth = the longest chain of serialised streams; the answer is lanes / depth.
-static int measure_concurrency(RtGroup* g)
+// Which of the group's streams execute concurrently: one single-wave kernel that naps for ~1 ms, on one stream alone and then on
+// every stream of a candidate set at once, both timed on the host.  Streams that share a hardware queue run their naps one after
+// the other, so a set whose naps take about as long as one nap runs side by side.  Greedy in lane order: lane 0, then each lane
+// whose stream keeps the set concurrent.  Measured, not predicted: which queue a stream lands on is the runtime's business.
+static std::vector<int> measure_workers(RtGroup* g)
 {
     const int n = (int)g->lane.size();
-    if (n <= 1) return n;
+    std::vector<int> set{ 0 };
+    if (n <= 1) return set;
     int rate = 0;
     if (hipDeviceGetAttribute(&rate, hipDeviceAttributeWallClockRate, g->lane[0]->cfg.device) != hipSuccess || rate <= 0) rate = 100000;   // kHz
     const long long ticks = (long long)rate;        // 1 ms
     int* sink = (int*)g->lane[0]->q.fault;          // never written (ticks >= 0)
-    auto run = [&](int streams) {
+    auto run = [&](const std::vector<int>& lanes) {
         const auto t0 = std::chrono::steady_clock::now();
-        for (int m = 0; m < streams; m++) hipLaunchKernelGGL(k_spin, dim3(1), dim3(64), 0, g->lane[(size_t)m]->stream, ticks, sink);
-        for (int m = 0; m < streams; m++) (void)hipStreamSynchronize(g->lane[(size_t)m]->stream);
+        for (int m : lanes) hipLaunchKernelGGL(k_spin, dim3(1), dim3(64), 0, g->lane[(size_t)m]->home, ticks, sink);
+        for (int m : lanes) (void)hipStreamSynchronize(g->lane[(size_t)m]->home);
         return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     };
-    (void)run(n);                                    // warms the code object up on every stream
     // the best of three each: a host thread that is descheduled for a millisecond must not read as a serialised stream
-    float one = run(1), all = run(n);
-    for (int k = 0; k < 2; k++) { one = std::min(one, run(1)); all = std::min(all, run(n)); }
-    if (one <= 0 || all <= 0) return 0;
-    const int depth = std::max(1, std::min(n, (int)std::lround(all / one)));
-    return std::max(1, n / depth);
+    auto best = [&](const std::vector<int>& lanes) { float t = run(lanes); for (int k = 0; k < 2; k++) t = std::min(t, run(lanes)); return t; };
+    std::vector<int> all(n);
+    for (int m = 0; m < n; m++) all[(size_t)m] = m;
+    (void)run(all);                                  // warms the code object up on every stream
+    const float one = best(set);
+    if (one <= 0) return set;
+    for (int m = 1; m < n; m++) {
+        std::vector<int> cand = set; cand.push_back(m);
+        if (best(cand) < 1.5f * one) set = cand;     // serialised: >= 2 naps
+    }
+    return set;
 }
 
 extern "C" int rt_group_create(const RtConfig* cfg, int32_t lanes, RtGroup** out)
@@ -1292,21 +1321,31 @@ extern "C" int rt_group_create(const RtConfig* cfg, int32_t lanes, RtGroup** out
         RtConfig c = *cfg;
         if (lanes > 1) {   // contexts that share the GPU get the footprints that fit BESIDE each other
             if (c.shade_blocks_per_cu == 0) c.shade_blocks_per_cu = 1;
-            if (c.persist_blocks_per_cu == 0) c.persist_blocks_per_cu = 2;
         }
         if (m > 0) c.profile = 0;   // HIP-event brackets on the first lane only
         RtCtx* ctx = nullptr;
         const int rc = rt_create(&c, &ctx);
         if (rc != RT_OK) return rc;
         g->lane.push_back(ctx);
-        hipEvent_t e;
-        if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return fail(RT_E_DEVICE, "rt_group_create: hipEventCreate failed");
-        g->done.push_back(e);
+        for (auto* ev : { &g->done, &g->moved }) {
+            hipEvent_t e;
+            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return fail(RT_E_DEVICE, "rt_group_create: hipEventCreate failed");
+            ev->push_back(e);
+        }
     }
     const size_t px = (size_t)cfg->width * cfg->height;
     if (hipMalloc((void**)&g->sum, px * sizeof(float4)) != hipSuccess) return fail(RT_E_NOMEM, "rt_group_create: hipMalloc of the group accumulator failed");
     HIPCHK(hipMemset(g->sum, 0, px * sizeof(float4)));
-    g->concurrent = measure_concurrency(g);
+    g->worker = measure_workers(g);
+    if (const char* t = getenv("RT355_GROUP_STREAMS")) {   // at most this many workers (tests of the routing; A/B runs)
+        const int k = atoi(t);
+        if (k >= 1 && k < (int)g->worker.size()) g->worker.resize((size_t)k);
+    }
+    g->concurrent = (int)g->worker.size();
+    // the persistent traversal grids (sized at scene upload) of S concurrent lanes: S grids beside each other.  2 per CU was tuned
+    // for four; 3 for three or fewer (profiles/r04_group_streams.txt)
+    if (lanes > 1 && cfg->persist_blocks_per_cu == 0)
+        for (RtCtx* c : g->lane) c->cfg.persist_blocks_per_cu = g->concurrent >= 4 ? 2 : 3;
     if (g->concurrent < lanes) {
         static bool warned = false;
         if (!warned) {
@@ -1367,7 +1406,7 @@ extern "C" int rt_group_reset(RtGroup* g)
 {
     if (!g) return fail(RT_E_INVALID, "rt_group_reset: null group");
     for (RtCtx* c : g->lane) { const int rc = rt_reset(c); if (rc != RT_OK) return rc; }
-    g->frames = 0; g->nextLane = 0;
+    g->frames = 0; g->nextLane = 0; g->nextWorker = 0;
     return RT_OK;
 }
 // `frames` frames in all, dealt to the lanes round-robin (continuing where the last call stopped) and queued interleaved, so that the
@@ -1377,11 +1416,30 @@ extern "C" int rt_group_render(RtGroup* g, const RtCamera* cam, const RtSettings
 {
     if (!g || !cam) return fail(RT_E_INVALID, "rt_group_render: null argument");
     if (frames <= 0) return fail(RT_E_INVALID, "rt_group_render: frames must be > 0");
-    const int n = (int)g->lane.size();
+    const int n = (int)g->lane.size(), S = (int)g->worker.size();
+    HIPCHK(hipSetDevice(g->lane[0]->cfg.device));
     for (int f = 0; f < frames; f++) {
-        const int rc = rt_render(g->lane[(size_t)g->nextLane], cam, settings, 1);
-        if (rc != RT_OK) return rc;
+        RtCtx* c = g->lane[(size_t)g->nextLane];
+        hipEvent_t moved = g->moved[(size_t)g->nextLane];
+        const hipStream_t w = g->lane[(size_t)g->worker[(size_t)g->nextWorker]]->home;
+        if (S == n) {   // frame j's worker is lane j's own stream
+            const int rc = rt_render(c, cam, settings, 1);
+            if (rc != RT_OK) return rc;
+        } else {
+            if (c->stream != w) {
+                // `moved` marks the end of the lane's last frame; the frames of other lanes queued behind it on that stream must not
+                // be waited for.  Work the lane queued after its frame (a reset, the group sum) sits behind them and must be.
+                if (c->queued) HIPCHK(hipEventRecord(moved, c->stream));
+                HIPCHK(hipStreamWaitEvent(w, moved, 0));
+                c->stream = w;
+            }
+            const int rc = rt_render(c, cam, settings, 1);
+            if (rc != RT_OK) return rc;
+            HIPCHK(hipEventRecord(moved, w));
+            c->queued = false;
+        }
         g->nextLane = (g->nextLane + 1) % n;
+        g->nextWorker = (g->nextWorker + 1) % S;
     }
     g->frames += (uint64_t)frames;
     return RT_OK;
@@ -1410,6 +1468,7 @@ extern "C" int rt_group_sum(RtGroup* g, void* devicePtr)
     // the lanes must not start overwriting their accumulators before the sum has read them
     HIPCHK(hipEventRecord(g->done[0], c0->stream));
     for (int m = 1; m < n; m++) HIPCHK(hipStreamWaitEvent(g->lane[(size_t)m]->stream, g->done[0], 0));
+    for (RtCtx* c : g->lane) c->queued = true;
     return RT_OK;
 }
 extern "C" int rt_group_read_accum(RtGroup* g, RtFloat4* out)

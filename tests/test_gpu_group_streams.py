@@ -1,0 +1,112 @@
+"""A group's frames on fewer worker streams than lanes (rt_group_render, RT355_GROUP_STREAMS): every lane's samples stay its own.
+
+Frame j of a group is lane j mod L's sample, issued on worker stream j mod S.  Whatever S is, every lane's accumulator, seeds and
+work counters, and the group's lane-ordered sum, must be those of the oracle rendering lane m's sample stream alone - and so the
+same bits for every S.  The sequence mixes calls of even and odd frame counts (the round-robin continues across calls) with a
+reset, lane reads and the group sum in between, so that an operation queued on a stream the lane has left would show."""
+import numpy as np
+import pytest
+
+from magr_ray_tracer_amd import scenes
+from magr_ray_tracer_amd import dist as rdist
+from magr_ray_tracer_amd.renderer import Group
+from oracle.oracle_py import Oracle, seed_stream
+from helpers import DEFAULT, assert_bits
+
+Wd, Hd, FIRST = 160, 90, 1
+CALLS_A, CALLS_B = (4, 3), (5,)      # render(4), render(3); reset; render(5)
+
+
+def _scene():
+    s, view = scenes.sponza_class(0.2)
+    sa = s.arrays()
+    return sa, scenes.camera_for(view, Wd, Hd)
+
+
+def _oracle(sa, cam, lanes):
+    """Per lane: accumulator and seeds after CALLS_A, then after the reset and CALLS_B, and the work counters of both."""
+    o = Oracle(sa, Wd, Hd, **DEFAULT)
+    na, nb = rdist.lane_frames(sum(CALLS_A), lanes), rdist.lane_frames(sum(CALLS_B), lanes)
+    out = []
+    for m in range(lanes):
+        seeds = seed_stream((FIRST + m) * Wd * Hd, Wd * Hd)
+        acc_a, e, c = np.zeros((Hd, Wd, 4), np.float32), {}, {}
+        for n, tag in ((na[m], "a"), (nb[m], "b")):
+            acc = np.zeros((Hd, Wd, 4), np.float32)
+            if n:
+                acc, seeds, ee, cc = o.render(cam, n, accum=acc, seeds=seeds.copy())
+                for k, v in ee.items(): e[k] = e.get(k, 0) + v
+                for k, v in cc.items(): c[k] = c.get(k, 0) + v
+            if tag == "a":
+                acc_a, seeds_a = acc, seeds.copy()
+        out.append(dict(acc_a=acc_a, seeds_a=seeds_a, acc_b=acc, seeds_b=seeds.copy(), e=e, c=c))
+    return out
+
+
+def _render(sa, cam, lanes, streams, monkeypatch):
+    if streams is None:
+        monkeypatch.delenv("RT355_GROUP_STREAMS", raising=False)
+    else:
+        monkeypatch.setenv("RT355_GROUP_STREAMS", str(streams))
+    g = Group(Wd, Hd, lanes=lanes, **DEFAULT)
+    try:
+        g.upload(sa)
+        g.seed(FIRST)
+        got = dict(S=g.concurrency())
+        for f in CALLS_A:
+            g.render(cam, f)
+        got["acc_a"] = [d.read_accum() for d in g.devs]
+        got["seeds_a"] = [d.get_seeds() for d in g.devs]
+        got["sum_a"] = g.read_accum()
+        g.reset()
+        for f in CALLS_B:
+            g.render(cam, f)
+        got["sum_b"] = g.read_accum()
+        got["acc_b"] = [d.read_accum() for d in g.devs]
+        got["seeds_b"] = [d.get_seeds() for d in g.devs]
+        got["ctr"] = [d.counters() for d in g.devs]
+        got["frames"] = g.frames()
+    finally:
+        g.close()
+    return got
+
+
+def _ctr_vs_oracle(dev, e, c, what):
+    """As test_gpu_parity._ctr_equal: extend counters are the reference's; connect's node / triangle counts follow its own order."""
+    for k in ("rays", "tlas_visits", "inst_visits", "node_visits", "prim_tests"):
+        assert dev["extend_" + k] == e.get(k, 0), (what, "extend_" + k, dev["extend_" + k], e.get(k, 0))
+    for k in ("rays", "tlas_visits", "inst_visits"):
+        assert dev["connect_" + k] == c.get(k, 0), (what, "connect_" + k, dev["connect_" + k], c.get(k, 0))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("lanes", [4, 8])
+def test_group_frames_on_fewer_streams_are_bit_exact(lanes, monkeypatch):
+    sa, cam = _scene()
+    ref = _oracle(sa, cam, lanes)
+    runs = {}
+    for streams in (None, 1, 2, 3):                  # None: as measured (= lanes where the process has a queue per lane)
+        got = _render(sa, cam, lanes, streams, monkeypatch)
+        measured = runs[None]["S"] if streams is not None else got["S"]
+        assert 1 <= got["S"] <= lanes
+        if streams is not None:
+            assert got["S"] == min(streams, measured), (streams, got["S"], measured)
+        assert got["frames"] == sum(CALLS_B)
+        exp_a = exp_b = None
+        for m in range(lanes):
+            r, tag = ref[m], f"lanes={lanes} S={got['S']} lane {m}"
+            assert_bits(got["acc_a"][m], r["acc_a"], tag + " accumulator after render(4), render(3)")
+            assert np.array_equal(got["seeds_a"][m], r["seeds_a"]), tag + " seeds after render(4), render(3)"
+            assert_bits(got["acc_b"][m], r["acc_b"], tag + " accumulator after reset, render(5)")
+            assert np.array_equal(got["seeds_b"][m], r["seeds_b"]), tag + " seeds after reset, render(5)"
+            _ctr_vs_oracle(got["ctr"][m], r["e"], r["c"], tag)
+            exp_a = r["acc_a"] if exp_a is None else exp_a + r["acc_a"]
+            exp_b = r["acc_b"] if exp_b is None else exp_b + r["acc_b"]
+        assert_bits(got["sum_a"], exp_a, f"lanes={lanes} S={got['S']} group sum after render(4), render(3)")
+        assert_bits(got["sum_b"], exp_b, f"lanes={lanes} S={got['S']} group sum after reset, render(5)")
+        runs[streams] = got
+    base = runs[None]
+    for streams, got in runs.items():
+        for m in range(lanes):
+            assert got["ctr"][m] == base["ctr"][m], (lanes, streams, m)
+            assert_bits(got["acc_b"][m], base["acc_b"][m], f"lanes={lanes} S={got['S']} vs measured S, lane {m}")
