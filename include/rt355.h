@@ -231,6 +231,34 @@ int rt_debug_get_shadow(RtCtx* ctx, int32_t firstBounce, int32_t lastBounce, RtS
 int rt_debug_enable_steps(RtCtx* ctx, int32_t on);
 int rt_debug_get_steps(RtCtx* ctx, int32_t* out, int32_t capacity, int32_t* n);
 
+/* The kernels' math functions on their own (tests/test_gpu_math.py): the very device functions the generate and shade kernels call,
+ * evaluated on device 0.  Per element, `in` and `out` hold (32-bit words):
+ *   RT_MATH_EXP / SIN / COS / ACOS   x                                  -> float
+ *   RT_MATH_ATAN                     x                                  -> float atan2(x, 1), i.e. the atan of atan2
+ *   RT_MATH_F2I                      x                                  -> int32 as the GPU converts (NaN -> 0, saturating)
+ *   RT_MATH_ATAN2                    y, x                               -> float
+ *   RT_MATH_SPHERE_TEXEL             N.x, N.y, N.z, N.w, texW, texH (int32) -> int32 x, y: texel column and row of a sphere hit
+ *   RT_MATH_NORMALIZE4               v.x, v.y, v.z, v.w                 -> float4
+ *   RT_MATH_LENGTH4                  v.x, v.y, v.z, v.w                 -> float
+ * The library built with the reference's builtins (librt355_refb.so) evaluates its ocml functions; it has no ACOS, ATAN or ATAN2
+ * (it calls acospi / atan2pi only inside the texel lookup) and returns RT_E_UNSUPPORTED for them. */
+#define RT_MATH_EXP           0
+#define RT_MATH_SIN           1
+#define RT_MATH_COS           2
+#define RT_MATH_ACOS          3
+#define RT_MATH_ATAN          4
+#define RT_MATH_F2I           5
+#define RT_MATH_ATAN2         6
+#define RT_MATH_SPHERE_TEXEL  7
+#define RT_MATH_NORMALIZE4    8
+#define RT_MATH_LENGTH4       9
+int rt_debug_math(int32_t fn, const void* in, void* out, int64_t n);
+/* Sweep of a one-argument function (EXP ... F2I) over every float32 bit pattern of blocks [firstBlock, firstBlock + nBlocks) of
+ * 2^20 inputs each (block b: bits b<<20 ...; 4096 blocks in all).  hashes[k] = sum mod 2^64 over the block of
+ * splitmix64((uint64_t)in_bits << 32 | out_bits), every NaN output counted as 0x7fc00000: independent of evaluation order. */
+#define RT_MATH_SWEEP_BLOCK_BITS 20
+int rt_debug_math_sweep(int32_t fn, int32_t firstBlock, int32_t nBlocks, uint64_t* hashes);
+
 #ifdef __cplusplus
 }
 #endif

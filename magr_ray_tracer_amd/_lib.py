@@ -59,6 +59,11 @@ SHADING_SIMPLE, SHADING_NEE = 0, 1
 SAMPLING_HEMISPHERE, SAMPLING_COSINE = 0, 1
 ACCEL_BVH2, ACCEL_BVH4 = 0, 1
 PRIM_SPHERE, PRIM_PLANE, PRIM_TRIANGLE = 0, 1, 2
+# rt_debug_math function ids (include/rt355.h): 32-bit words in / out per element
+MATH_EXP, MATH_SIN, MATH_COS, MATH_ACOS, MATH_ATAN, MATH_F2I, MATH_ATAN2, MATH_SPHERE_TEXEL, MATH_NORMALIZE4, MATH_LENGTH4 = range(10)
+MATH_WORDS = {MATH_EXP: (1, 1), MATH_SIN: (1, 1), MATH_COS: (1, 1), MATH_ACOS: (1, 1), MATH_ATAN: (1, 1), MATH_F2I: (1, 1),
+              MATH_ATAN2: (2, 1), MATH_SPHERE_TEXEL: (6, 2), MATH_NORMALIZE4: (4, 4), MATH_LENGTH4: (4, 1)}
+MATH_SWEEP_BLOCK_BITS = 20
 MAX_BOUNCES = 7
 
 DEVICE_SYMBOLS = [
@@ -66,7 +71,8 @@ DEVICE_SYMBOLS = [
     "rt_get_seeds", "rt_bind_accum", "rt_accum_device_ptr", "rt_stream", "rt_reset", "rt_render", "rt_synchronize", "rt_focus",
     "rt_read_accum", "rt_write_accum", "rt_postproc", "rt_read_counters", "rt_reset_counters", "rt_read_stage_times", "rt_reset_stage_times", "rt_set_profile",
     "rt_stage_begin_frame", "rt_stage_generate", "rt_stage_extend", "rt_stage_shade", "rt_stage_connect",
-    "rt_debug_get_rays", "rt_debug_set_rays", "rt_debug_get_shadow", "rt_debug_enable_steps", "rt_debug_get_steps", "rt_validate_scene",
+    "rt_debug_get_rays", "rt_debug_set_rays", "rt_debug_get_shadow", "rt_debug_enable_steps", "rt_debug_get_steps", "rt_debug_math",
+    "rt_debug_math_sweep", "rt_validate_scene",
     "rt_group_create", "rt_group_destroy", "rt_group_lanes", "rt_group_concurrency", "rt_group_lane", "rt_group_frames", "rt_group_upload_scene", "rt_group_share_scene",
     "rt_group_seed", "rt_group_reset", "rt_group_render", "rt_group_synchronize", "rt_group_sum", "rt_group_read_accum", "rt_group_focus",
     "rt_group_postproc"]
@@ -155,6 +161,8 @@ def _bind_device(lib):
         lib.rt_debug_get_shadow.argtypes = [vp, i32, i32, vp, i32, C.POINTER(i32)]
         lib.rt_debug_get_steps.argtypes = [vp, vp, i32, C.POINTER(i32)]
         lib.rt_debug_enable_steps.argtypes = [vp, i32]
+        lib.rt_debug_math.argtypes = [i32, vp, vp, i64]
+        lib.rt_debug_math_sweep.argtypes = [i32, i32, i32, vp]
         lib.rt_validate_scene.argtypes = [i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32]
         lib.rt_group_create.argtypes = [vp, i32, C.POINTER(vp)]
         lib.rt_group_destroy.argtypes = [vp]

@@ -87,7 +87,8 @@ def build_oracle(force=False):
     odir = os.path.join(ROOT, "oracle")
     src = os.path.join(odir, "oracle.c")
     out = os.path.join(odir, "liboracle.so")
-    if force or _stale(out, [src, os.path.join(odir, "oracle.h"), os.path.join(ROOT, "include", "rt355_types.h")]):
+    if force or _stale(out, [src, os.path.join(odir, "oracle.h"), os.path.join(ROOT, "include", "rt355.h"),
+                            os.path.join(ROOT, "include", "rt355_types.h")]):
         _run(["gcc"] + ORACLE_FLAGS + [src, "-o", out, "-lm"])
     return out
 

@@ -164,8 +164,9 @@ RT_FORCEINLINE float4 normalize4(float4 v)
 // device library's versions lean on hardware approximations (v_exp_f32, v_sin_f32 ...) that no CPU reproduces, and one last-bit
 // difference in a Fresnel draw or a texel index flips a whole path; so this path and the CPU oracle both evaluate the single-precision
 // Cephes algorithms (S. Moshier: expf.c, sinf.c, asinf.c, atanf.c) as plain sequences of IEEE + - * / sqrt - transcribed separately
-// here and in oracle/oracle.c - and agree bit for bit on every scene.  They are within 2 ulp of the correctly rounded value, i.e. as
-// close to the reference's builtins as those are to each other.
+// here and in oracle/oracle.c - and agree bit for bit on every input (tests/test_gpu_math.py).  Error against float64 (DESIGN.md section
+// 2, asserted by tests/test_math_cpu.py): exp <= 1 ulp, acos <= 1.3 ulp, atan <= 2.9 ulp, atan2 <= 3.4 ulp, sin / cos <= 1.32 * 2^-24
+// absolute for |x| <= 8192 (0 beyond).
 #ifdef RT355_REF_BUILTINS
 RT_FORCEINLINE float rt_expf(float x) { return __ocml_exp_f32(x); }
 RT_FORCEINLINE float rt_sinf(float x) { return __ocml_sin_f32(x); }
@@ -212,6 +213,8 @@ RT_FORCEINLINE float rt_sinf(float x)
     if (x != x) return x;
     bool neg = x < 0.0f;
     const float ax = neg ? -x : x;
+    if (x == 0.0f) return x;   // sin(-0) = -0
+    if (ax == INFINITY) return x - x;   // NaN
     if (ax > 8192.0f) return 0.0f;
     int j; const float r = rt_trig_reduce(ax, j);
     if (j > 3) { neg = !neg; j -= 4; }
@@ -223,6 +226,7 @@ RT_FORCEINLINE float rt_cosf(float x)
 {
     if (x != x) return x;
     const float ax = x < 0.0f ? -x : x;
+    if (ax == INFINITY) return x - x;   // NaN
     if (ax > 8192.0f) return 0.0f;
     int j; const float r = rt_trig_reduce(ax, j);
     bool neg = false;
@@ -261,7 +265,7 @@ RT_FORCEINLINE float rt_acosf(float x)
 }
 RT_FORCEINLINE float rt_atanf(float x)
 {
-    const bool neg = x < 0.0f;
+    const bool neg = signbit(x);   // atan(-0) = -0
     float a = neg ? -x : x, y;
     if (a > 2.414213562373095f) { y = 1.5707963267948966192f; a = -(1.0f / a); }
     else if (a > 0.4142135623730950f) { y = 0.7853981633974483096f; a = (a - 1.0f) / (a + 1.0f); }
@@ -283,6 +287,7 @@ RT_FORCEINLINE float rt_atan2f(float y, float x)
         if (y == 0.0f) return signbit(x) ? copysignf(3.14159265358979323846f, y) : y;
         return y > 0.0f ? 1.5707963267948966192f : -1.5707963267948966192f;
     }
+    if (isinf(x) && isinf(y)) return copysignf(x > 0.0f ? 0.7853981633974483096f : 2.3561944901923449288f, y);
     float z = rt_atanf(y / x);
     if (x < 0.0f) z = signbit(y) ? z - 3.14159265358979323846f : z + 3.14159265358979323846f;
     return z;
@@ -1583,6 +1588,20 @@ RT_FORCEINLINE float4 prim_normal(const RtPrimitive* p, float4 I) // primitives.
 // is defined C++ rather than a poison fptosi.  It matters: a sphere hit found with w-lane-polluted dots has a non-unit normal,
 // acos(N.y) is then NaN and the reference's kernels read texel row 0 (tests/test_gpu_reference.py, whole-frame comparison).
 RT_FORCEINLINE int f2i_gpu(float x) { return x != x ? 0 : (x >= 2147483648.0f ? 2147483647 : (x <= -2147483648.0f ? (int)(-2147483647 - 1) : (int)x)); }
+// Texel column / row of a sphere hit with normal N (primitives.cl:130-133).  The seam N.z = +-0, N.x < 0 gives ux = 1 or 0 by the
+// sign of N.z, and the pole N.y = -1 gives uy = 1: x = texW and y = texH are the reference's indices there (tests/test_gpu_math.py).
+RT_FORCEINLINE void sphere_texel_xy(float4 N, int texW, int texH, int& x, int& y)
+{
+#ifdef RT355_REF_BUILTINS
+    float ux = (1.0f + __ocml_atan2pi_f32(N.z, N.x)) * 0.5f;   // primitives.cl:130 (int + float is a float add; * 0.5 is exact in any precision)
+    float uy = __ocml_acospi_f32(N.y);                         // :131
+#else
+    float ux = (float)((1 + rt_atan2f(N.z, N.x) / 3.14159265358979323846) * 0.5);
+    float uy = rt_acosf(N.y) / 3.14159265358979323846f;
+#endif
+    x = f2i_gpu(ux * (float)texW);
+    y = f2i_gpu(uy * (float)texH);
+}
 RT_FORCEINLINE uint32_t f2u_gpu(float x) { return !(x > 0.0f) ? 0u : (x >= 4294967296.0f ? 0xffffffffu : (uint32_t)x); }
 RT_FORCEINLINE float4 texel(const DevScene& sc, long long i) { return i >= 0 && i < (long long)sc.nTex ? sc.tex[i] : splat(0.0f); }
 // The scalar fields of a Material (bytes 32..63: specular, n1, n2, isDielectric | texIdx, texW, texH, isLight) fetched as two 16-byte
@@ -1614,14 +1633,8 @@ RT_FORCEINLINE float4 albedo_of(const DevScene& sc, const RtPrimitive* prim, con
             int x = f2i_gpu(ux * (float)texW), y = f2i_gpu(uy * (float)texH);
             albedo = texel(sc, (long long)texIdx + x + (long long)y * texW);
         } else if (type == RT_PRIM_SPHERE) {
-#ifdef RT355_REF_BUILTINS
-            float ux = (1.0f + __ocml_atan2pi_f32(ray.N.z, ray.N.x)) * 0.5f;   // primitives.cl:130 (int + float is a float add; * 0.5 is exact in any precision)
-            float uy = __ocml_acospi_f32(ray.N.y);                             // :131
-#else
-            float ux = (float)((1 + rt_atan2f(ray.N.z, ray.N.x) / 3.14159265358979323846) * 0.5);
-            float uy = rt_acosf(ray.N.y) / 3.14159265358979323846f;
-#endif
-            int x = f2i_gpu(ux * (float)texW), y = f2i_gpu(uy * (float)texH);
+            int x, y;
+            sphere_texel_xy(ray.N, texW, texH, x, y);
             albedo = texel(sc, (long long)texIdx + x + (long long)y * texW);
         } else {
             float u = fmodf(ray.u, 1.f), v = fmodf(ray.v, 1.f);

@@ -107,6 +107,17 @@ void     orc_test_cosine_hemisphere(const float N[4], uint32_t* seed, float out[
 void     orc_test_triangle(const float v0[3], const float v1[3], const float v2[3], const float O[3], const float D[3], float out[4]);
 uint32_t orc_test_wang_hash(uint32_t s);
 
+/* The math functions of the path on their own: the function ids and in / out layouts of rt_debug_math and the block hash of
+ * rt_debug_math_sweep (include/rt355.h).  threads is capped at 16. */
+int orc_math(int32_t fn, const void* in, void* out, int64_t n);
+int orc_math_sweep(int32_t fn, int32_t firstBlock, int32_t nBlocks, uint64_t* hashes, int32_t threads);
+/* Exhaustive error of a one-argument function (EXP ... ATAN; ATAN is atan2(x, 1)) over every float in [lo, hi] against libm double:
+ * in ulps of the float spacing at the exact value (subnormal spacing below FLT_MIN), or with `absolute` in units of 2^-24.  A NaN, or an
+ * infinity where the exact value does not round to one, counts as an infinite error.  `above` counts the inputs whose error exceeds `bound`; `arg` is the input of the
+ * largest error (the smallest in magnitude among ties). */
+typedef struct OrcMathError { double max_err; float arg; uint64_t above; uint64_t count; } OrcMathError;
+int orc_math_error(int32_t fn, float lo, float hi, int32_t absolute, double bound, int32_t threads, OrcMathError* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,6 +47,9 @@ def lib():
         L.orc_render_bands.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]
         L.orc_trace_normals.argtypes = [vp, vp, vp, i32, vp]
         L.orc_postproc.argtypes = [vp, i32, i32, i32, C.c_float, C.c_float, C.c_float, vp, vp]
+        L.orc_math.argtypes = [i32, vp, vp, C.c_int64]
+        L.orc_math_sweep.argtypes = [i32, i32, i32, vp, i32]
+        L.orc_math_error.argtypes = [i32, C.c_float, C.c_float, i32, C.c_double, i32, vp]
         _lib = L
     return _lib
 
@@ -68,6 +71,44 @@ def postproc(accum, frames, vignette=0.0, gamma=0.9, chromatic=0.0):
     b = np.zeros((H, W, 4), np.uint8)
     lib().orc_postproc(_p(a), W, H, int(frames), float(vignette), float(gamma), float(chromatic), _p(f), _p(b))
     return f, b
+
+
+OrcMathError = np.dtype([("max_err", "<f8"), ("arg", "<f4"), ("above", "<u8"), ("count", "<u8")], align=True)
+
+
+def math_threads():
+    """Threads of the exhaustive sweeps: the CPUs this process may use, at most 16."""
+    return max(1, min(16, len(os.sched_getaffinity(0))))
+
+
+def math(fn, x):
+    """orc_math: x is an (n, in_words) array of 32-bit words (any 4-byte dtype); returns (n, out_words) uint32 (rt_debug_math layout)."""
+    from magr_ray_tracer_amd import _lib as W
+    wi, wo = W.MATH_WORDS[fn]
+    a = np.ascontiguousarray(x).view(np.uint32).reshape(-1, wi)
+    out = np.zeros((len(a), wo), np.uint32)
+    if lib().orc_math(fn, _p(a), _p(out), len(a)) != 0:
+        raise ValueError(f"orc_math: bad function id {fn}")
+    return out
+
+
+def math_sweep(fn, first_block=0, n_blocks=None):
+    """orc_math_sweep: block hashes of a one-argument function (rt_debug_math_sweep layout)."""
+    from magr_ray_tracer_amd import _lib as W
+    if n_blocks is None:
+        n_blocks = (1 << (32 - W.MATH_SWEEP_BLOCK_BITS)) - first_block
+    h = np.zeros(n_blocks, np.uint64)
+    if lib().orc_math_sweep(fn, first_block, n_blocks, _p(h), math_threads()) != 0:
+        raise ValueError("orc_math_sweep: bad argument")
+    return h
+
+
+def math_error(fn, lo, hi, absolute=False, bound=np.inf):
+    """orc_math_error: exhaustive error over the floats in [lo, hi] against libm double; dict max_err, arg, above, count."""
+    r = np.zeros((), OrcMathError)
+    if lib().orc_math_error(fn, lo, hi, int(absolute), float(bound), math_threads(), r.ctypes.data_as(C.c_void_p)) != 0:
+        raise ValueError("orc_math_error: bad argument")
+    return {"max_err": float(r["max_err"]), "arg": np.float32(r["arg"]), "above": int(r["above"]), "count": int(r["count"])}
 
 
 class Oracle:
