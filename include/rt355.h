@@ -134,6 +134,20 @@ int rt_validate_scene(int32_t accel,
  * are this library's way to keep a GPU full.) */
 int rt_share_scene(RtCtx* ctx, RtCtx* from);
 
+/* ---- acceleration structures on the GPU ----------------------------------------------------------------------------------------
+ * Linear BVH (Karras radix tree over 63-bit Morton | index keys, then a bottom-up SAH collapse) over the primitives
+ * [first, first + count) of prims[nPrims], built on `device` (a HIP ordinal) and written in the wire format BVH2::BuildBLAS writes:
+ * the root is node nodeBase, children are adjacent (first, first + 1), a leaf indexes primIdx at idxBase + (start of its range in key
+ * order), primIdx[0, count) receives global primitive ids.  nodes[] needs room for 2 * count - 1 records (nodeCap); *nNodes receives
+ * the number written (2 * leaves - 1).  Node and index ids are global, so the arrays can be appended behind the BLASes of either
+ * builder.  The tree is a pure function of the primitives and the options: identical on every call and equal, array for array, to
+ * the host restatement rth_build_bvh2_lbvh (rt355_host.h).  Its height is <= 63 (rt_validate_scene accepts it).  Synchronous, on a
+ * stream of its own; opts NULL = defaults (max_leaf 8, C_t = C_i = 1).  Errors (count <= 0, range outside nPrims, nodeCap too small,
+ * bad options, a bad device) return RT_E_* before anything is launched or written.  stats may be NULL. */
+int rt_build_bvh2(int32_t device, const RtBuildOptions* opts, const RtPrimitive* prims, int32_t nPrims, int32_t first, int32_t count,
+                  uint32_t nodeBase, uint32_t idxBase, RtBVHNode2* nodes, int32_t nodeCap, int32_t* nNodes, uint32_t* primIdx,
+                  RtBuildStats* stats);
+
 /* ---- lanes: one accumulation as several interleaved sample streams behind one handle -------------------------------------------
  * What stands behind Renderer::Tick() (renderer.cpp:26-63) when a GPU is to be kept full: `lanes` contexts (own HIP stream, queues,
  * accumulator, seed slice) that share ONE device copy of the scene; their frames are queued interleaved so that the tails of one

@@ -45,6 +45,16 @@ int rth_build_blas(RthScene* s, int startIdx, float alpha);
 /* Threads for the following BuildBLAS calls: 1 = the reference's sequential loop; > 1 = task-parallel subtrees numbered
  * afterwards in the reference's LIFO order (identical arrays). */
 int rth_set_build_threads(RthScene* s, int threads);
+/* The linear BVH builder (rt_build_bvh2, rt355.h) over primitives [startIdx, end), appended as BuildBLAS appends a BLAS: instance
+ * record, node and primIdx arrays, rth_bvh_stats; rth_build_bvh4 / rth_build_tlas / rth_renderer_* take it unchanged.  device >= 0:
+ * on that GPU; -1: the host restatement (identical arrays).  opts NULL = defaults.  Returns RT_E_* and leaves the scene unchanged
+ * when the build is refused. */
+int rth_build_blas_lbvh(RthScene* s, int startIdx, int device, const RtBuildOptions* opts);
+int rth_lbvh_stats(RthScene* s, RtBuildStats* out);   /* statistics of the scene's last rth_build_blas_lbvh */
+/* The host restatement on caller arrays: rt_build_bvh2's contract without the device (stats->device_ms = 0). */
+int rth_build_bvh2_lbvh(const RtBuildOptions* opts, const RtPrimitive* prims, int32_t nPrims, int32_t first, int32_t count,
+                        uint32_t nodeBase, uint32_t idxBase, RtBVHNode2* nodes, int32_t nodeCap, int32_t* nNodes, uint32_t* primIdx,
+                        RtBuildStats* stats);
 int rth_build_bvh4(RthScene* s);            /* new BVH4(*bvh2) (scene.cpp:71)                    */
 int rth_build_tlas(RthScene* s);            /* new TLAS(*bvh2); Build() (renderer.cpp:12-13)     */
 /* BVH4::Convert + Collapse (bvh.cpp:695-787) on a caller-provided BVH2 node array, one BLAS rooted at node 0; out[n] */

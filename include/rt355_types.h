@@ -131,6 +131,23 @@ typedef struct RtTLASNode {
     uint32_t _pad[2];
 } RtTLASNode;
 
+/* Options and statistics of the linear BVH builder (rt_build_bvh2 in rt355.h, rth_build_bvh2_lbvh / rth_build_blas_lbvh in
+ * rt355_host.h).  Not part of the reference's wire format. */
+typedef struct RtBuildOptions {
+    int32_t max_leaf;            /* largest leaf the SAH collapse may form: RT_MIN_LEAF_PRIMS..127 (default 8)           */
+    float   cost_traverse;       /* C_t: cost of an interior node per unit of its area (default 1)                      */
+    float   cost_intersect;      /* C_i: cost of one primitive test per unit of its leaf's area (default 1)             */
+    int32_t _reserved;
+} RtBuildOptions;
+typedef struct RtBuildStats {
+    int32_t nodes, leaves, depth;  /* node records written (2 * leaves - 1), leaves, height in edges (BVH2::Depth)       */
+    int32_t morton_bits;           /* bits per axis of the Morton codes (k)                                            */
+    float   sah_cost;              /* BVH2::TotalCost of the tree (the host builder's stat_sah_cost metric)            */
+    float   device_ms;             /* GPU time from the first kernel to the last (0 for the host restatement)          */
+    float   wall_ms;               /* the whole call, transfers and allocations included                                */
+    int32_t _reserved;
+} RtBuildStats;
+
 RT_STATIC_ASSERT(sizeof(RtRay) == 128 && offsetof(RtRay, t) == 96 && offsetof(RtRay, primIdx) == 100 &&
                  offsetof(RtRay, pixelIdx) == 108 && offsetof(RtRay, inside) == 112 &&
                  offsetof(RtRay, lastSpecular) == 113 && offsetof(RtRay, u) == 116 && offsetof(RtRay, v) == 120,
@@ -150,6 +167,7 @@ RT_STATIC_ASSERT(sizeof(RtSettings) == 40 && offsetof(RtSettings, numInRays) == 
 RT_STATIC_ASSERT(sizeof(RtBVHNode2) == 48 && offsetof(RtBVHNode2, first) == 32, "BVHNode2 layout");
 RT_STATIC_ASSERT(sizeof(RtBVHNode4) == 160 && offsetof(RtBVHNode4, first) == 128 && offsetof(RtBVHNode4, count) == 144, "BVHNode4 layout");
 RT_STATIC_ASSERT(sizeof(RtBVHInstance) == 68 && offsetof(RtBVHInstance, invT) == 4, "BVHInstance layout");
+RT_STATIC_ASSERT(sizeof(RtBuildOptions) == 16 && sizeof(RtBuildStats) == 32, "build options / stats layout");
 RT_STATIC_ASSERT(sizeof(RtTLASNode) == 48 && offsetof(RtTLASNode, leftRight) == 32 && offsetof(RtTLASNode, BLASidx) == 36, "TLASNode layout");
 
 #ifdef __cplusplus

@@ -46,12 +46,15 @@ Config = np.dtype([(n, "<i4") for n in ("width", "height", "y0", "y1", "max_boun
                                          "shade_blocks_per_cu", "persist_blocks_per_cu")] +
                   [("reserved", "<i4", 1)])
 
+BuildOptions = np.dtype([("max_leaf", "<i4"), ("cost_traverse", "<f4"), ("cost_intersect", "<f4"), ("_reserved", "<i4")])
+BuildStats = np.dtype([("nodes", "<i4"), ("leaves", "<i4"), ("depth", "<i4"), ("morton_bits", "<i4"), ("sah_cost", "<f4"),
+                       ("device_ms", "<f4"), ("wall_ms", "<f4"), ("_reserved", "<i4")])
 KernelInfo = np.dtype([(n, "<i4") for n in ("layout", "persist", "persist4", "stack_entries", "persist_grid", "persist_grid_connect",
                                              "shade_grid", "n_blas")])
 
 _SIZES = {"Ray": (Ray, 128), "ShadowRay": (ShadowRay, 96), "Material": (Material, 80), "Primitive": (Primitive, 128),
           "Camera": (Camera, 128), "Settings": (Settings, 40), "BVHNode2": (BVHNode2, 48), "BVHNode4": (BVHNode4, 160),
-          "BVHInstance": (BVHInstance, 68), "TLASNode": (TLASNode, 48), "ShadowRecord": (ShadowRecord, 48), "Config": (Config, 64)}
+          "BVHInstance": (BVHInstance, 68), "TLASNode": (TLASNode, 48), "BuildOptions": (BuildOptions, 16), "BuildStats": (BuildStats, 32), "ShadowRecord": (ShadowRecord, 48), "Config": (Config, 64)}
 for _n, (_d, _s) in _SIZES.items():
     assert _d.itemsize == _s, (_n, _d.itemsize, _s)
 
@@ -65,6 +68,7 @@ MATH_WORDS = {MATH_EXP: (1, 1), MATH_SIN: (1, 1), MATH_COS: (1, 1), MATH_ACOS: (
               MATH_ATAN2: (2, 1), MATH_SPHERE_TEXEL: (6, 2), MATH_NORMALIZE4: (4, 4), MATH_LENGTH4: (4, 1)}
 MATH_SWEEP_BLOCK_BITS = 20
 MAX_BOUNCES = 7
+RT_OK, RT_E_INVALID, RT_E_DEVICE, RT_E_NOMEM, RT_E_UNSUPPORTED = 0, -1, -2, -3, -4
 
 DEVICE_SYMBOLS = [
     "rt_last_error", "rt_device_count", "rt_kernel_info", "rt_create", "rt_destroy", "rt_upload_scene", "rt_share_scene", "rt_set_seeds", "rt_seed_default",
@@ -72,7 +76,7 @@ DEVICE_SYMBOLS = [
     "rt_read_accum", "rt_write_accum", "rt_postproc", "rt_read_counters", "rt_reset_counters", "rt_read_stage_times", "rt_reset_stage_times", "rt_set_profile",
     "rt_stage_begin_frame", "rt_stage_generate", "rt_stage_extend", "rt_stage_shade", "rt_stage_connect",
     "rt_debug_get_rays", "rt_debug_set_rays", "rt_debug_get_shadow", "rt_debug_enable_steps", "rt_debug_get_steps", "rt_debug_math",
-    "rt_debug_math_sweep", "rt_validate_scene",
+    "rt_debug_math_sweep", "rt_validate_scene", "rt_build_bvh2",
     "rt_group_create", "rt_group_destroy", "rt_group_lanes", "rt_group_concurrency", "rt_group_lane", "rt_group_frames", "rt_group_upload_scene", "rt_group_share_scene",
     "rt_group_seed", "rt_group_reset", "rt_group_render", "rt_group_synchronize", "rt_group_sum", "rt_group_read_accum", "rt_group_focus",
     "rt_group_postproc"]
@@ -83,7 +87,8 @@ HOST_SYMBOLS = [
     "rth_bvh2_nodes", "rth_bvh4_nodes", "rth_prim_idx", "rth_tlas_nodes", "rth_blas_nodes", "rth_bvh_stats", "rth_camera",
     "rth_renderer_create", "rth_renderer_destroy", "rth_renderer_init", "rth_renderer_set_camera", "rth_renderer_tick",
     "rth_renderer_read", "rth_renderer_camera", "rth_seed_stream", "rth_load_model", "rth_save_png",
-    "rth_set_build_threads", "rth_renderer_save_frame", "rth_renderer_camera_move", "rth_renderer_camera_mouse", "rth_renderer_camera_zoom", "rth_renderer_frames", "rth_renderer_set_lanes"]
+    "rth_set_build_threads", "rth_renderer_save_frame", "rth_renderer_camera_move", "rth_renderer_camera_mouse", "rth_renderer_camera_zoom", "rth_renderer_frames", "rth_renderer_set_lanes",
+    "rth_build_blas_lbvh", "rth_build_bvh2_lbvh", "rth_lbvh_stats"]
 
 _dev = None
 _host = None
@@ -164,6 +169,7 @@ def _bind_device(lib):
         lib.rt_debug_math.argtypes = [i32, vp, vp, i64]
         lib.rt_debug_math_sweep.argtypes = [i32, i32, i32, vp]
         lib.rt_validate_scene.argtypes = [i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32]
+        lib.rt_build_bvh2.argtypes = [i32, vp, vp, i32, i32, i32, C.c_uint32, C.c_uint32, vp, i32, C.POINTER(i32), vp, vp]
         lib.rt_group_create.argtypes = [vp, i32, C.POINTER(vp)]
         lib.rt_group_destroy.argtypes = [vp]
         lib.rt_group_lanes.argtypes = [vp]
@@ -205,6 +211,10 @@ def host_lib():
         lib.rth_add_triangles.argtypes = [vp, vp, vp, i32, cp, i32]
         lib.rth_build_blas.argtypes = [vp, i32, C.c_float]
         lib.rth_build_bvh4.argtypes = [vp]
+        lib.rth_build_blas_lbvh.argtypes = [vp, i32, i32, vp]
+        lib.rth_build_bvh2_lbvh.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, vp, C.c_int32,
+                                            C.POINTER(C.c_int32), vp, vp]
+        lib.rth_lbvh_stats.argtypes = [vp, vp]
         lib.rth_set_build_threads.argtypes = [vp, i32]
         lib.rth_build_tlas.argtypes = [vp]
         lib.rth_bvh4_from_nodes.argtypes = [vp, i32, vp]

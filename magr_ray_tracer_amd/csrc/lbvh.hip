@@ -1,0 +1,238 @@
+// lbvh.hip — rt_build_bvh2 (include/rt355.h): the linear BVH builder on the GPU.  The algorithm and every value it computes are
+// defined in lbvh_common.h; this file only distributes that work over kernels.  host/lbvh_host.cpp runs the same rules in sequence
+// (rth_build_bvh2_lbvh) and must produce identical arrays (tests/test_gpu_lbvh.py).
+//
+//   k_lbvh_boxes     primitive boxes + centroid key bounds (workgroup reduction in LDS, then one atomicMin / atomicMax per workgroup)
+//   k_lbvh_keys      Morton key | local index, value = local index
+//   radix sort       hipcub::DeviceRadixSort::SortPairs over the L = 3k + b significant bits
+//   k_lbvh_karras    internal nodes: children, sorted range, parent links
+//   k_lbvh_bottomup  one thread per leaf climbs while it is the second to reach a node (atomic ticket per node, no waiting)
+//   k_lbvh_survive   internal nodes emitted as interior nodes; exclusive scan (hipcub::DeviceScan) gives their pair slots
+//   k_lbvh_emit      RtBVHNode2 records and primIdx
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+#include <chrono>
+#include <cstdarg>
+#include <cstdio>
+#include "../../include/rt355.h"
+#include "lbvh_common.h"
+
+using namespace lbvh;
+
+int rt355_set_error(int code, const char* msg);   // rt355.hip: sets the text rt_last_error() returns
+
+namespace {
+
+constexpr int kBlock = 256;
+
+__global__ void __launch_bounds__(kBlock) k_lbvh_boxes(const RtPrimitive* prims, uint32_t n, Box* boxes, uint32_t* cb)
+{
+    __shared__ uint32_t s[6];
+    if (threadIdx.x < 6) s[threadIdx.x] = threadIdx.x < 3 ? kKeyMinInit : kKeyMaxInit;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i < n) {
+        const Box b = prim_box(prims[i]);
+        boxes[i] = b;
+        for (int a = 0; a < 3; a++) {
+            const float c = centroid(b, a);
+            if (finite_(c)) { atomicMin(&s[a], order_key(c)); atomicMax(&s[3 + a], order_key(c)); }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) atomicMin(&cb[threadIdx.x], s[threadIdx.x]);
+    else if (threadIdx.x < 6) atomicMax(&cb[threadIdx.x], s[threadIdx.x]);
+}
+
+__global__ void __launch_bounds__(kBlock) k_lbvh_keys(const Box* boxes, uint32_t n, const uint32_t* cb, int k, int bIdx,
+                                                      uint64_t* keys, uint32_t* vals)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    float clo[3], scale[3];
+    quantizer(cb, cb + 3, k, clo, scale);
+    keys[i] = make_key(boxes[i], clo, scale, k, bIdx, i);
+    vals[i] = i;
+}
+
+struct Kids { uint32_t left, right, first; };
+
+__global__ void __launch_bounds__(kBlock) k_lbvh_karras(const uint64_t* keys, uint32_t n, Kids* kids, uint32_t* parent)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i + 1 >= n) return;
+    Kids c; uint32_t last;
+    karras_node(keys, n, i, c.left, c.right, c.first, last);
+    kids[i] = c;
+    parent[c.left] = i;
+    parent[c.right] = i;
+}
+
+// Records cross workgroups here: a node's two children are written by whichever threads climbed to them, anywhere on the chip.  Each
+// hand-off is the agent-scope release / acquire of the ticket (cdna_hip_programming §6 Guideline 16): the writer stores its record
+// with plain stores, releases at agent scope and drains its stores before it draws the ticket; the thread that draws the second
+// ticket acquires at agent scope before it loads the sibling's record.  Nobody waits: the first visitor just stops.  The record
+// array is read through plain (not const / restrict) pointers so that the loads stay on the vector path behind the acquire.
+__global__ void __launch_bounds__(kBlock) k_lbvh_bottomup(const Box* boxes, const uint32_t* vals, uint32_t n, NodeRec* rec,
+                                                          const uint32_t* parent, const Kids* kids, uint32_t* tickets, Params P)
+{
+    const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
+    if (k >= n) return;
+    uint32_t node = n - 1 + k;
+    rec[node] = leaf_rec(boxes[vals[k]], k, P);
+    for (uint32_t p = parent[node]; p != kNone; p = parent[p]) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if (__hip_atomic_fetch_add(&tickets[p], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0) return;
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        const Kids c = kids[p];
+        const NodeRec L = rec[c.left], R = rec[c.right];
+        rec[p] = combine(L, R, c.first, P);
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) k_lbvh_survive(const NodeRec* rec, const uint32_t* parent, uint32_t nInternal,
+                                                         uint32_t maxLeaf, uint32_t* flags)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i < nInternal) flags[i] = survives(rec, parent, i, maxLeaf);
+}
+
+__global__ void __launch_bounds__(kBlock) k_lbvh_emit(const NodeRec* rec, const Kids* kids, const uint32_t* flags, const uint32_t* rank,
+                                                      const uint32_t* vals, uint32_t n, uint32_t first, uint32_t nodeBase,
+                                                      uint32_t idxBase, RtBVHNode2* nodes, uint32_t* primIdx)
+{
+    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+    if (t >= n) return;
+    const uint32_t nInternal = n - 1;
+    primIdx[t] = first + vals[t];
+    if (t == 0) nodes[0] = emit(rec[0], 0, nInternal, rank, nodeBase, idxBase);
+    if (t < nInternal && flags[t]) {
+        const uint32_t slot = 1 + 2 * rank[t];
+        nodes[slot] = emit(rec[kids[t].left], kids[t].left, nInternal, rank, nodeBase, idxBase);
+        nodes[slot + 1] = emit(rec[kids[t].right], kids[t].right, nInternal, rank, nodeBase, idxBase);
+    }
+}
+
+int lfail(int code, const char* fmt, ...)   // the message goes to rt_last_error()
+{
+    char buf[512];
+    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
+    return rt355_set_error(code, buf);
+}
+
+size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Everything one build allocates on the device; freed on every exit path.
+struct Work {
+    void* mem = nullptr;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[2] = { nullptr, nullptr };
+    int prevDevice = -1;                      // the caller's current device, restored on the way out
+    ~Work()
+    {
+        if (stream) (void)hipStreamSynchronize(stream);
+        if (mem) (void)hipFree(mem);
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        if (stream) (void)hipStreamDestroy(stream);
+        if (prevDevice >= 0) (void)hipSetDevice(prevDevice);
+    }
+};
+
+} // namespace
+
+#define LCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
+    return lfail(RT_E_DEVICE, "rt_build_bvh2: %s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
+
+extern "C" int rt_build_bvh2(int32_t device, const RtBuildOptions* opt, const RtPrimitive* prims, int32_t nPrims, int32_t first,
+                             int32_t count, uint32_t nodeBase, uint32_t idxBase, RtBVHNode2* nodes, int32_t nodeCap, int32_t* nNodes,
+                             uint32_t* primIdx, RtBuildStats* stats)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    Params P;
+    if (const char* msg = check_args(opt, prims, nPrims, first, count, nodeBase, idxBase, nodes, nodeCap, nNodes, primIdx, P))
+        return lfail(RT_E_INVALID, "rt_build_bvh2: %s", msg);
+    int nDev = 0;
+    if (hipGetDeviceCount(&nDev) != hipSuccess || nDev <= 0) return lfail(RT_E_DEVICE, "rt_build_bvh2: no HIP device");
+    if (device < 0 || device >= nDev) return lfail(RT_E_INVALID, "rt_build_bvh2: device %d out of range (%d devices)", device, nDev);
+    Work w;
+    LCHK(hipGetDevice(&w.prevDevice));
+    LCHK(hipSetDevice(device));
+
+    const uint32_t n = (uint32_t)count, nInt = n - 1, nTree = 2 * n - 1;
+    const int bIdx = index_bits(n), k = axis_bits(n), keyBits = 3 * k + bIdx;
+    LCHK(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
+    LCHK(hipEventCreate(&w.ev[0]));
+    LCHK(hipEventCreate(&w.ev[1]));
+
+    size_t sortBytes = 0, scanBytes = 0;
+    LCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, sortBytes, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr,
+                                            (uint32_t*)nullptr, (int)n, 0, keyBits, w.stream));
+    if (nInt > 0) LCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, scanBytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)nInt, w.stream));
+
+    // one allocation, carved: [cb | tickets | parent] first (the words the memsets initialise), then the rest
+    const size_t nI = nInt > 0 ? nInt : 1;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { const size_t o = off; off += align_up(bytes); return o; };
+    const size_t oCb = carve(6 * sizeof(uint32_t)), oTick = carve(nI * sizeof(uint32_t)), oPar = carve(nTree * sizeof(uint32_t));
+    const size_t oPrim = carve(n * sizeof(RtPrimitive)), oBox = carve(n * sizeof(Box)), oK0 = carve(n * 8ull), oK1 = carve(n * 8ull);
+    const size_t oV0 = carve(n * 4ull), oV1 = carve(n * 4ull), oKids = carve(nI * sizeof(Kids)), oRec = carve(nTree * sizeof(NodeRec));
+    const size_t oFlag = carve(nI * 4ull), oRank = carve(nI * 4ull), oNodes = carve(nTree * sizeof(RtBVHNode2)), oIdx = carve(n * 4ull);
+    const size_t oSort = carve(sortBytes), oScan = carve(scanBytes);
+    if (hipMalloc(&w.mem, off) != hipSuccess) { w.mem = nullptr; return lfail(RT_E_NOMEM, "rt_build_bvh2: %zu bytes of device memory", off); }
+    char* base = (char*)w.mem;
+    auto at = [&](size_t o) { return (void*)(base + o); };
+    uint32_t* cb = (uint32_t*)at(oCb);
+    uint32_t* tickets = (uint32_t*)at(oTick);
+    uint32_t* parent = (uint32_t*)at(oPar);
+    RtPrimitive* dPrims = (RtPrimitive*)at(oPrim);
+    Box* boxes = (Box*)at(oBox);
+    uint64_t *k0 = (uint64_t*)at(oK0), *k1 = (uint64_t*)at(oK1);
+    uint32_t *v0 = (uint32_t*)at(oV0), *v1 = (uint32_t*)at(oV1);
+    Kids* kids = (Kids*)at(oKids);
+    NodeRec* rec = (NodeRec*)at(oRec);
+    uint32_t *flags = (uint32_t*)at(oFlag), *rank = (uint32_t*)at(oRank);
+    RtBVHNode2* dNodes = (RtBVHNode2*)at(oNodes);
+    uint32_t* dIdx = (uint32_t*)at(oIdx);
+
+    LCHK(hipMemcpyAsync(dPrims, prims + first, n * sizeof(RtPrimitive), hipMemcpyHostToDevice, w.stream));
+    const uint32_t cbInit[6] = { kKeyMinInit, kKeyMinInit, kKeyMinInit, kKeyMaxInit, kKeyMaxInit, kKeyMaxInit };
+    LCHK(hipMemcpyAsync(cb, cbInit, sizeof cbInit, hipMemcpyHostToDevice, w.stream));
+    LCHK(hipMemsetAsync(tickets, 0, nI * sizeof(uint32_t), w.stream));
+    LCHK(hipMemsetAsync(parent, 0xff, nTree * sizeof(uint32_t), w.stream));
+    LCHK(hipStreamSynchronize(w.stream));   // the host arrays are the caller's: nothing of them is read after this point
+
+    const dim3 blk(kBlock), gN((n + kBlock - 1) / kBlock), gI((nI + kBlock - 1) / kBlock);
+    LCHK(hipEventRecord(w.ev[0], w.stream));
+    hipLaunchKernelGGL(k_lbvh_boxes, gN, blk, 0, w.stream, dPrims, n, boxes, cb);
+    hipLaunchKernelGGL(k_lbvh_keys, gN, blk, 0, w.stream, boxes, n, cb, k, bIdx, k0, v0);
+    LCHK(hipcub::DeviceRadixSort::SortPairs(at(oSort), sortBytes, k0, k1, v0, v1, (int)n, 0, keyBits, w.stream));
+    if (nInt > 0) hipLaunchKernelGGL(k_lbvh_karras, gI, blk, 0, w.stream, k1, n, kids, parent);
+    hipLaunchKernelGGL(k_lbvh_bottomup, gN, blk, 0, w.stream, boxes, v1, n, rec, parent, kids, tickets, P);
+    if (nInt > 0) {
+        hipLaunchKernelGGL(k_lbvh_survive, gI, blk, 0, w.stream, rec, parent, nInt, P.maxLeaf, flags);
+        LCHK(hipcub::DeviceScan::ExclusiveSum(at(oScan), scanBytes, flags, rank, (int)nInt, w.stream));
+    }
+    hipLaunchKernelGGL(k_lbvh_emit, gN, blk, 0, w.stream, rec, kids, flags, rank, v1, n, (uint32_t)first, nodeBase, idxBase, dNodes, dIdx);
+    LCHK(hipGetLastError());
+    LCHK(hipEventRecord(w.ev[1], w.stream));
+
+    NodeRec root;
+    LCHK(hipMemcpyAsync(&root, rec, sizeof root, hipMemcpyDeviceToHost, w.stream));
+    LCHK(hipStreamSynchronize(w.stream));
+    const uint32_t outNodes = 2 * root.leaves - 1;
+    if (root.leaves < 1 || outNodes > nTree) return lfail(RT_E_DEVICE, "rt_build_bvh2: inconsistent device result (%u leaves)", root.leaves);
+    LCHK(hipMemcpyAsync(nodes, dNodes, outNodes * sizeof(RtBVHNode2), hipMemcpyDeviceToHost, w.stream));
+    LCHK(hipMemcpyAsync(primIdx, dIdx, n * sizeof(uint32_t), hipMemcpyDeviceToHost, w.stream));
+    LCHK(hipStreamSynchronize(w.stream));
+    *nNodes = (int32_t)outNodes;
+    if (stats) {
+        float ms = 0;
+        LCHK(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
+        stats->nodes = (int32_t)outNodes; stats->leaves = (int32_t)root.leaves; stats->depth = (int32_t)root.height;
+        stats->morton_bits = k; stats->sah_cost = root.total; stats->device_ms = ms;
+        stats->wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->_reserved = 0;
+    }
+    return RT_OK;
+}

@@ -30,6 +30,7 @@ static int fail(int code, const char* fmt, ...)
     g_err = buf;
     return code;
 }
+int rt355_set_error(int code, const char* msg) { g_err = msg; return code; }   // for the other source files of this library (lbvh.hip)
 #define HIPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
     return fail(RT_E_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
 

@@ -72,6 +72,22 @@ int rth_build_blas(RthScene* s, int startIdx, float alpha)
     if (!s || startIdx < 0 || startIdx >= (int)s->scene.primitives.size()) { g_herr = "rth_build_blas: bad start index"; return -1; }
     GUARD(s->scene.bvh2->alpha = alpha; s->scene.bvh2->BuildBLAS(true, startIdx))
 }
+int rth_build_blas_lbvh(RthScene* s, int startIdx, int device, const RtBuildOptions* opts)
+{
+    if (!s || startIdx < 0 || startIdx >= (int)s->scene.primitives.size()) { g_herr = "rth_build_blas_lbvh: bad start index"; return RT_E_INVALID; }
+    try { s->scene.bvh2->BuildBLASLBVH(startIdx, device, opts); return 0; }
+    catch (const LbvhError& e) { g_herr = e.what(); return e.code; }
+    catch (const std::exception& e) { g_herr = e.what(); return RT_E_NOMEM; }
+}
+int rth_build_bvh2_lbvh(const RtBuildOptions* opts, const RtPrimitive* prims, int32_t nPrims, int32_t first, int32_t count, uint32_t nodeBase,
+                        uint32_t idxBase, RtBVHNode2* nodes, int32_t nodeCap, int32_t* nNodes, uint32_t* primIdx, RtBuildStats* stats)
+{
+    std::string err;
+    const int rc = LbvhBuildHost(opts, prims, nPrims, first, count, nodeBase, idxBase, nodes, nodeCap, nNodes, primIdx, stats, err);
+    if (rc != RT_OK) g_herr = err;
+    return rc;
+}
+int rth_lbvh_stats(RthScene* s, RtBuildStats* out) { if (!s || !out) return -1; *out = s->scene.bvh2->lastLbvh; return 0; }
 int rth_set_build_threads(RthScene* s, int threads) { if (!s) return -1; s->scene.bvh2->buildThreads = threads < 1 ? 1 : threads; return 0; }
 int rth_build_bvh4(RthScene* s) { GUARD(s->scene.BuildBVH4()) }
 // BVH4::Convert + Collapse (bvh.cpp:695-787) on a caller-provided BVH2 node array with ONE BLAS rooted at node 0: how the tests feed

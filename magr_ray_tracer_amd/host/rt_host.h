@@ -10,6 +10,7 @@
 #pragma once
 #include <cstdint>
 #include <map>
+#include <stdexcept>
 #include <string>
 #include <vector>
 #include "../../include/rt355_types.h"
@@ -62,6 +63,11 @@ class BVH2 {
 public:
     BVH2(std::vector<RtPrimitive>& prims, std::vector<RtBVHInstance>& blasNodes);
     void     BuildBLAS(bool statistics, int startIdx);
+    // The linear BVH builder (csrc/lbvh_common.h) over primitives [startIdx, end): appends a BLAS exactly as BuildBLAS does (instance
+    // record, nodes, primIdx, statistics).  device >= 0: rt_build_bvh2 on that GPU; -1: the host restatement.  Throws LbvhError and
+    // leaves everything unchanged when the build is refused.
+    void     BuildBLASLBVH(int startIdx, int device, const RtBuildOptions* opt);
+    RtBuildStats lastLbvh{};     // statistics of the last BuildBLASLBVH
     int      buildThreads = 1;   // > 1: subtrees are built by parallel tasks, then numbered in the reference's LIFO order (same arrays)
     uint32_t Depth(uint32_t nodeIdx) const;
     uint32_t Count(uint32_t nodeIdx) const;
@@ -90,6 +96,12 @@ private:
     std::vector<RtPrimitive>& primitives_;
     uint32_t rootNodeIdx_ = 0, nodesUsed_ = 0;
 };
+
+struct LbvhError : std::runtime_error { int code; LbvhError(int c, const std::string& m) : std::runtime_error(m), code(c) {} };
+// The linear builder's sequential host restatement (rth_build_bvh2_lbvh); err receives the message of a refused call.
+int LbvhBuildHost(const RtBuildOptions* opt, const RtPrimitive* prims, int32_t nPrims, int32_t first, int32_t count, uint32_t nodeBase,
+                  uint32_t idxBase, RtBVHNode2* nodes, int32_t nodeCap, int32_t* nNodes, uint32_t* primIdx, RtBuildStats* stats,
+                  std::string& err);
 
 // reference: src/bvh.h:41-56
 class BVH4 {

@@ -123,10 +123,31 @@ class Scene:
         return n
 
     # reference: BVH2::BuildBLAS (bvh.cpp:46-82), bvh2->alpha = 1 -> plain SAH BVH, 0 -> full SBVH
-    def BuildBLAS(self, startIdx=0, alpha=1.0, threads=1):
-        """threads > 1: task-parallel build, numbered afterwards in the reference's LIFO order (identical arrays)."""
-        self._lib.rth_set_build_threads(self._h, int(threads))
-        self._chk(self._lib.rth_build_blas(self._h, int(startIdx), float(alpha)))
+    def BuildBLAS(self, startIdx=0, alpha=1.0, threads=1, builder="sah", device=0, **lbvh_options):
+        """A BLAS over the primitives [startIdx, end).
+
+        builder="sah" (default): the reference's binned SAH / SBVH builder; threads > 1: task-parallel build, numbered afterwards in
+        the reference's LIFO order (identical arrays).
+        builder="lbvh": the linear BVH builder (rt_build_bvh2) on HIP device `device`, or its host restatement when device is None
+        (identical arrays); lbvh_options: max_leaf, cost_traverse, cost_intersect.  It has no spatial splits: alpha must stay 1."""
+        if builder == "sah":
+            if lbvh_options:
+                raise ValueError(f"options {sorted(lbvh_options)} apply to builder='lbvh' only")
+            self._lib.rth_set_build_threads(self._h, int(threads))
+            self._chk(self._lib.rth_build_blas(self._h, int(startIdx), float(alpha)))
+        elif builder == "lbvh":
+            if alpha != 1.0:
+                raise ValueError("builder='lbvh' has no spatial splits: alpha must be 1")
+            opts = build_options(**lbvh_options)
+            self._chk(self._lib.rth_build_blas_lbvh(self._h, int(startIdx), -1 if device is None else int(device), _lib.ptr(opts)))
+        else:
+            raise ValueError(f"unknown builder {builder!r} (expected 'sah' or 'lbvh')")
+
+    def lbvh_stats(self):
+        """Statistics of the last builder='lbvh' BuildBLAS (RtBuildStats)."""
+        st = np.zeros((), _lib.BuildStats)
+        self._chk(self._lib.rth_lbvh_stats(self._h, _lib.ptr(st)))
+        return _stats_dict(st)
 
     def BuildBVH4(self):
         self._chk(self._lib.rth_build_bvh4(self._h))
@@ -162,6 +183,56 @@ class Scene:
             bvh2=_view(L.rth_bvh2_nodes, self._h, _lib.BVHNode2), bvh4=_view(L.rth_bvh4_nodes, self._h, _lib.BVHNode4),
             primIdx=_view(L.rth_prim_idx, self._h, np.dtype("<u4")), tlas=_view(L.rth_tlas_nodes, self._h, _lib.TLASNode),
             blas=_view(L.rth_blas_nodes, self._h, _lib.BVHInstance))
+
+
+LBVH_DEFAULTS = dict(max_leaf=8, cost_traverse=1.0, cost_intersect=1.0)   # lbvh_common.h
+
+
+def build_options(max_leaf=None, cost_traverse=None, cost_intersect=None):
+    """RtBuildOptions of the linear builder; None = its default."""
+    o = np.zeros((), _lib.BuildOptions)
+    o["max_leaf"] = LBVH_DEFAULTS["max_leaf"] if max_leaf is None else int(max_leaf)
+    o["cost_traverse"] = LBVH_DEFAULTS["cost_traverse"] if cost_traverse is None else float(cost_traverse)
+    o["cost_intersect"] = LBVH_DEFAULTS["cost_intersect"] if cost_intersect is None else float(cost_intersect)
+    return o
+
+
+def _stats_dict(st):
+    return {k: (float(st[k]) if k in ("sah_cost", "device_ms", "wall_ms") else int(st[k]))
+            for k in ("nodes", "leaves", "depth", "morton_bits", "sah_cost", "device_ms", "wall_ms")}
+
+
+class BuildError(RuntimeError):
+    def __init__(self, code, msg):
+        super().__init__(f"{msg} (RT_E code {code})")
+        self.code = code
+
+
+def build_lbvh(prims, first=0, count=None, device=None, node_base=0, idx_base=0, node_cap=None, **options):
+    """The linear BVH builder on a primitive array (Primitive records): rt_build_bvh2 on HIP device `device`, or its host
+    restatement (rth_build_bvh2_lbvh) when device is None.  Returns (nodes, primIdx, stats); raises BuildError (with .code, an RT_E_*
+    value) when the call is refused.  node_cap defaults to what the call needs (2 * count - 1)."""
+    p = np.ascontiguousarray(prims, dtype=_lib.Primitive)
+    n = len(p) - int(first) if count is None else int(count)
+    cap = max(2 * n - 1, 1) if node_cap is None else int(node_cap)
+    nodes = np.zeros(max(cap, 1), _lib.BVHNode2)
+    idx = np.zeros(max(n, 1), np.uint32)
+    st = np.zeros((), _lib.BuildStats)
+    written = C.c_int32(0)
+    opts = build_options(**options)
+    if device is None:
+        L = _lib.host_lib()
+        rc = L.rth_build_bvh2_lbvh(_lib.ptr(opts), _lib.ptr(p), len(p), int(first), n, int(node_base), int(idx_base), _lib.ptr(nodes), cap,
+                                   C.byref(written), _lib.ptr(idx), _lib.ptr(st))
+        msg = L.rth_last_error
+    else:
+        L = _lib.device_lib()
+        rc = L.rt_build_bvh2(int(device), _lib.ptr(opts), _lib.ptr(p), len(p), int(first), n, int(node_base), int(idx_base), _lib.ptr(nodes),
+                             cap, C.byref(written), _lib.ptr(idx), _lib.ptr(st))
+        msg = L.rt_last_error
+    if rc != 0:
+        raise BuildError(rc, msg().decode())
+    return nodes[:written.value].copy(), idx[:n].copy(), _stats_dict(st)
 
 
 def make_camera(width, height, origin, forward, fov=110.0, aperture=0.1, focalLength=1.0, type=0):

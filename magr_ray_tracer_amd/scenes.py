@@ -91,10 +91,11 @@ def bunny_class(n=187, alpha=1.0):
 
 
 # ----------------------------------------------------------------------------------------- config 3/4
-def sponza_class(detail=1.0, alpha=1.0):
+def sponza_class(detail=1.0, alpha=1.0, builder="sah", device=0):
     """Atrium ('sponza-class'): 36 x 14 m floor, 14 m high, open roof slot with sky, two storeys of
     fluted columns carrying round arches along both long sides, ribbed walls, six hanging drapes.
-    detail=1.0 gives ~262k triangles (Crytek Sponza has 262,267); the generator is RNG-free."""
+    detail=1.0 gives ~262k triangles (Crytek Sponza has 262,267); the generator is RNG-free.
+    builder="lbvh": the linear BVH builder on HIP device `device` (None: its host restatement) instead of the SAH builder."""
     s = Scene()
     _std_materials(s)
     d = float(detail)
@@ -149,7 +150,7 @@ def sponza_class(detail=1.0, alpha=1.0):
     first_extra = s.num_prims
     s.AddQuad((-2, 13.2, -2), (2, 13.2, -2), (2, 13.2, 2), (-2, 13.2, 2), "white-light")
     del first_extra
-    s.BuildBLAS(0, alpha)
+    s.BuildBLAS(0, alpha, builder=builder, device=device)
     view = dict(origin=(-15.0, 3.2, 0.6), forward=(-0.97, -0.10, -0.05), fov=75.0, aperture=0.02)
     return s, view
 
@@ -269,10 +270,11 @@ def two_blas_scene(alpha=0.0, n=24):
     return s, view
 
 
-def config5_scene(alpha=0.0, decimate=1):
+def config5_scene(alpha=0.0, decimate=1, builder="sah", device=0):
     """BASELINE config 5: robo-orb (35,600 tris) + terrarium_bot (40,012 tris), each its own BLAS under a TLAS, SBVH
     alpha (0 = full spatial splits), glass on the terrarium dome.  Geometry: magr_ray_tracer_amd/assets/*.npz (converted
-    from the glTF files that ship with the reference; CC-BY-4.0, see assets/ATTRIBUTION.md)."""
+    from the glTF files that ship with the reference; CC-BY-4.0, see assets/ATTRIBUTION.md).
+    builder="lbvh" (alpha is then ignored): both BLAS by the linear BVH builder on HIP device `device` (None: host restatement)."""
     import os
     from . import gltf
     adir = os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets")
@@ -294,10 +296,11 @@ def config5_scene(alpha=0.0, decimate=1):
     place("robo_orb.npz", 1.9, (-1.5, 0.0, 0.0), {"Coat": "mirror", "Coat_2": "mirror", "Butt": "red", "material": "green"}, "white")
     s.AddQuad((-9, 0, -9), (-9, 0, 9), (9, 0, 9), (9, 0, -9), "grey")
     s.AddQuad((-1.5, 5.5, -1.5), (1.5, 5.5, -1.5), (1.5, 5.5, 1.5), (-1.5, 5.5, 1.5), "white-light")
-    s.BuildBLAS(0, alpha)
+    blas = dict(builder="lbvh", device=device) if builder == "lbvh" else dict(alpha=alpha)
+    s.BuildBLAS(0, **blas)
     start = s.num_prims
     place("terrarium_bot.npz", 2.4, (1.7, 0.0, 0.0), {"glass": "white-glass", "ground": "sand", "inside": "sand", "pipes": "red"}, "white")
-    s.BuildBLAS(start, alpha)
+    s.BuildBLAS(start, **blas)
     view = dict(origin=(0.3, 2.3, 5.4), forward=(0.03, 0.2, 0.98), fov=62.0, aperture=0.02)
     return s, view
 
