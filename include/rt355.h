@@ -148,6 +148,46 @@ int rt_build_bvh2(int32_t device, const RtBuildOptions* opts, const RtPrimitive*
                   uint32_t nodeBase, uint32_t idxBase, RtBVHNode2* nodes, int32_t nodeCap, int32_t* nNodes, uint32_t* primIdx,
                   RtBuildStats* stats);
 
+/* ---- in-place scene updates (animation) ----------------------------------------------------------------------------------------
+ * What Renderer::Tick's disabled animation hook (renderer.cpp:29-37: scene.Animate, tlas->Build, the node buffers' CopyToDevice) needs,
+ * without a host rebuild or a re-upload.  The topology stays: primitive count, primIdx, node children and leaf ranges, every
+ * primitive's objType and matIdx (the light list and the materials depend on them) and every instance's bvhIdx.
+ *   prims: count records replacing [first, first + count) of the uploaded primitives (NULL / 0: geometry unchanged);
+ *   blas:  nBlas instances replacing the uploaded ones, of which only invT may differ (NULL: transforms unchanged).
+ * Then every BLAS is refit on the device (a leaf's box: the union of its primitives' boxes by BVH2::CreateBVHPrimData's rule, unclipped;
+ * an interior node's: the union of its children), the derived records are rewritten on the device and the TLAS is rebuilt on the
+ * device by TLAS::Build's rules (at most 256 instances).  The arrays are then bit for bit those of a fresh rt_upload_scene of the
+ * scene refit on the host (rth_set_primitives + rth_refit + rth_build_tlas, rt355_host.h).
+ * Refusals return before anything is written: RT_E_INVALID for a changed objType / matIdx / bvhIdx, a range outside the upload, a
+ * singular invT or a wrong instance count; RT_E_UNSUPPORTED for BVH4 contexts, scenes the update cannot handle (a TLAS not built by
+ * TLAS::Build's rules, a node reachable twice) and a rebuilt TLAS deeper than RT_TLAS_STACK (the work is staged: the bound scene then
+ * renders exactly as before).  The update waits for the streams of every context holding the scene (rt_share_scene partners, all
+ * lanes and worker streams of a group), not for other device work; each of them re-derives its traversal kernels (rt_kernel_info)
+ * before its next launch when the TLAS depth changed.  Synchronous; stats may be NULL.  Accumulators are not reset. */
+typedef struct RtUpdateStats {
+    double  gpu_ms;               /* GPU time of the update (staging + commit)                                                 */
+    int32_t prims, nodes;         /* primitives replaced; BVH2 nodes refit (those reachable from the BLAS roots)               */
+    int32_t tlas_nodes, tlas_depth;
+    int32_t reconfigured;         /* 1: the TLAS depth changed, so the holders re-derive their traversal configuration          */
+    int32_t reserved[3];
+} RtUpdateStats;
+int rt_update_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
+                    RtUpdateStats* stats);
+/* Device arrays of the context's scene copy, for tests: `which` is one of RT_SCENE_*.  *bytes receives the array's size; out NULL:
+ * only that.  Waits for the context's stream. */
+#define RT_SCENE_PRIMS         0   /* the wire primitives                                  */
+#define RT_SCENE_BVH           1   /* the wire BVH2 (or BVH4) nodes                        */
+#define RT_SCENE_TLAS          2   /* the wire TLAS nodes                                  */
+#define RT_SCENE_INSTANCES     3   /* the wire instances (RtBVHInstance)                   */
+#define RT_SCENE_PAIRS         4   /* layout-1 pair records (empty in layout 0 and BVH4)   */
+#define RT_SCENE_TRI_RECS      5   /* layout-1 triangle records                            */
+#define RT_SCENE_SHADE_RECS    6
+#define RT_SCENE_LIGHT_RECS    7
+#define RT_SCENE_TLAS_PAIRS    8
+#define RT_SCENE_TLAS_PAIRS_P  9
+#define RT_SCENE_INST_RECS    10
+int rt_debug_get_scene_array(RtCtx* ctx, int32_t which, void* out, int64_t capacityBytes, int64_t* bytes);
+
 /* ---- lanes: one accumulation as several interleaved sample streams behind one handle -------------------------------------------
  * What stands behind Renderer::Tick() (renderer.cpp:26-63) when a GPU is to be kept full: `lanes` contexts (own HIP stream, queues,
  * accumulator, seed slice) that share ONE device copy of the scene; their frames are queued interleaved so that the tails of one
@@ -174,6 +214,8 @@ int rt_group_upload_scene(RtGroup* g,
                           const void* bvhNodes, int32_t nNodes, const uint32_t* primIdx, int32_t nIdx,
                           const RtTLASNode* tlas, int32_t nTlas, const RtBVHInstance* blas, int32_t nBlas);
 int rt_group_share_scene(RtGroup* g, RtGroup* from);                         /* e.g. the row bands of one frame: one device copy        */
+int rt_group_update_scene(RtGroup* g, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
+                          RtUpdateStats* stats);                             /* rt_update_scene for the group's copy (all lanes)        */
 int rt_group_seed(RtGroup* g, uint64_t firstStream);                         /* a single Renderer: 0; rank r of a sample split: r*lanes */
 int rt_group_reset(RtGroup* g);                                              /* resetKernel on every lane; frames = 0                   */
 int rt_group_render(RtGroup* g, const RtCamera* cam, const RtSettings* settings, int32_t frames);   /* `frames` in all, round-robin   */

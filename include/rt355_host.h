@@ -55,6 +55,12 @@ int rth_lbvh_stats(RthScene* s, RtBuildStats* out);   /* statistics of the scene
 int rth_build_bvh2_lbvh(const RtBuildOptions* opts, const RtPrimitive* prims, int32_t nPrims, int32_t first, int32_t count,
                         uint32_t nodeBase, uint32_t idxBase, RtBVHNode2* nodes, int32_t nodeCap, int32_t* nNodes, uint32_t* primIdx,
                         RtBuildStats* stats);
+/* The host restatement of rt_update_scene (rt355.h): rth_set_primitives replaces primitives [first, first + count), which must keep
+ * their objType and matIdx; rth_refit refits every BLAS of the scene's BVH2 in place by the rules rt_update_scene runs on the device
+ * (csrc/refit_common.h).  The caller then runs rth_build_tlas (and rth_build_bvh4 if it renders a BVH4).  Both return RT_E_* and
+ * change nothing when refused. */
+int rth_set_primitives(RthScene* s, int first, int count, const RtPrimitive* prims);
+int rth_refit(RthScene* s);
 int rth_build_bvh4(RthScene* s);            /* new BVH4(*bvh2) (scene.cpp:71)                    */
 int rth_build_tlas(RthScene* s);            /* new TLAS(*bvh2); Build() (renderer.cpp:12-13)     */
 /* BVH4::Convert + Collapse (bvh.cpp:695-787) on a caller-provided BVH2 node array, one BLAS rooted at node 0; out[n] */

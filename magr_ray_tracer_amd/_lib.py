@@ -69,6 +69,12 @@ MATH_WORDS = {MATH_EXP: (1, 1), MATH_SIN: (1, 1), MATH_COS: (1, 1), MATH_ACOS: (
 MATH_SWEEP_BLOCK_BITS = 20
 MAX_BOUNCES = 7
 RT_OK, RT_E_INVALID, RT_E_DEVICE, RT_E_NOMEM, RT_E_UNSUPPORTED = 0, -1, -2, -3, -4
+# rt_debug_get_scene_array ids (include/rt355.h): name -> (id, record dtype)
+SCENE_ARRAYS = {"prims": 0, "bvh": 1, "tlas": 2, "instances": 3, "pairs": 4, "triRecs": 5, "shadeRecs": 6, "lightRecs": 7,
+                "tlasPairs": 8, "tlasPairsP": 9, "instRecs": 10}
+UpdateStats = np.dtype([("gpu_ms", "<f8"), ("prims", "<i4"), ("nodes", "<i4"), ("tlas_nodes", "<i4"), ("tlas_depth", "<i4"),
+                        ("reconfigured", "<i4"), ("reserved", "<i4", 3)])
+assert UpdateStats.itemsize == 40
 
 DEVICE_SYMBOLS = [
     "rt_last_error", "rt_device_count", "rt_kernel_info", "rt_create", "rt_destroy", "rt_upload_scene", "rt_share_scene", "rt_set_seeds", "rt_seed_default",
@@ -76,7 +82,7 @@ DEVICE_SYMBOLS = [
     "rt_read_accum", "rt_write_accum", "rt_postproc", "rt_read_counters", "rt_reset_counters", "rt_read_stage_times", "rt_reset_stage_times", "rt_set_profile",
     "rt_stage_begin_frame", "rt_stage_generate", "rt_stage_extend", "rt_stage_shade", "rt_stage_connect",
     "rt_debug_get_rays", "rt_debug_set_rays", "rt_debug_get_shadow", "rt_debug_enable_steps", "rt_debug_get_steps", "rt_debug_math",
-    "rt_debug_math_sweep", "rt_validate_scene", "rt_build_bvh2",
+    "rt_debug_math_sweep", "rt_validate_scene", "rt_build_bvh2", "rt_update_scene", "rt_group_update_scene", "rt_debug_get_scene_array",
     "rt_group_create", "rt_group_destroy", "rt_group_lanes", "rt_group_concurrency", "rt_group_lane", "rt_group_frames", "rt_group_upload_scene", "rt_group_share_scene",
     "rt_group_seed", "rt_group_reset", "rt_group_render", "rt_group_synchronize", "rt_group_sum", "rt_group_read_accum", "rt_group_focus",
     "rt_group_postproc"]
@@ -88,7 +94,7 @@ HOST_SYMBOLS = [
     "rth_renderer_create", "rth_renderer_destroy", "rth_renderer_init", "rth_renderer_set_camera", "rth_renderer_tick",
     "rth_renderer_read", "rth_renderer_camera", "rth_seed_stream", "rth_load_model", "rth_save_png",
     "rth_set_build_threads", "rth_renderer_save_frame", "rth_renderer_camera_move", "rth_renderer_camera_mouse", "rth_renderer_camera_zoom", "rth_renderer_frames", "rth_renderer_set_lanes",
-    "rth_build_blas_lbvh", "rth_build_bvh2_lbvh", "rth_lbvh_stats"]
+    "rth_build_blas_lbvh", "rth_build_bvh2_lbvh", "rth_lbvh_stats", "rth_set_primitives", "rth_refit"]
 
 _dev = None
 _host = None
@@ -170,6 +176,9 @@ def _bind_device(lib):
         lib.rt_debug_math_sweep.argtypes = [i32, i32, i32, vp]
         lib.rt_validate_scene.argtypes = [i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32]
         lib.rt_build_bvh2.argtypes = [i32, vp, vp, i32, i32, i32, C.c_uint32, C.c_uint32, vp, i32, C.POINTER(i32), vp, vp]
+        lib.rt_update_scene.argtypes = [vp, vp, i32, i32, vp, i32, vp]
+        lib.rt_group_update_scene.argtypes = [vp, vp, i32, i32, vp, i32, vp]
+        lib.rt_debug_get_scene_array.argtypes = [vp, i32, vp, i64, C.POINTER(i64)]
         lib.rt_group_create.argtypes = [vp, i32, C.POINTER(vp)]
         lib.rt_group_destroy.argtypes = [vp]
         lib.rt_group_lanes.argtypes = [vp]
@@ -215,6 +224,8 @@ def host_lib():
         lib.rth_build_bvh2_lbvh.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, vp, C.c_int32,
                                             C.POINTER(C.c_int32), vp, vp]
         lib.rth_lbvh_stats.argtypes = [vp, vp]
+        lib.rth_set_primitives.argtypes = [vp, i32, i32, vp]
+        lib.rth_refit.argtypes = [vp]
         lib.rth_set_build_threads.argtypes = [vp, i32]
         lib.rth_build_tlas.argtypes = [vp]
         lib.rth_bvh4_from_nodes.argtypes = [vp, i32, vp]

@@ -39,11 +39,12 @@ def _run(cmd):
 def build_device(force=False):
     src = os.path.join(PKG, "csrc", "rt355.hip")
     lbvh = os.path.join(PKG, "csrc", "lbvh.hip")      # rt_build_bvh2: the GPU linear BVH builder
-    deps = [src, lbvh, os.path.join(PKG, "csrc", "rt355_kernels.h"), os.path.join(PKG, "csrc", "lbvh_common.h"),
-            os.path.join(ROOT, "include", "rt355.h"), os.path.join(ROOT, "include", "rt355_types.h")]
+    refit = os.path.join(PKG, "csrc", "refit.hip")    # rt_update_scene: BLAS refit, derived records and TLAS rebuild on the GPU
+    deps = [src, lbvh, refit, os.path.join(PKG, "csrc", "rt355_kernels.h"), os.path.join(PKG, "csrc", "lbvh_common.h"),
+            os.path.join(PKG, "csrc", "refit_common.h"), os.path.join(ROOT, "include", "rt355.h"), os.path.join(ROOT, "include", "rt355_types.h")]
     out = os.path.join(PKG, "librt355.so")
     if force or _stale(out, deps):
-        _run([HIPCC] + DEVICE_FLAGS + [src, lbvh, "-o", out])
+        _run([HIPCC] + DEVICE_FLAGS + [src, lbvh, refit, "-o", out])
     return out
 
 
@@ -53,21 +54,23 @@ def build_device_refb(force=False):
     (uncurated whole-frame comparison with the reference's kernels); the shipped library is librt355.so."""
     src = os.path.join(PKG, "csrc", "rt355.hip")
     lbvh = os.path.join(PKG, "csrc", "lbvh.hip")      # same entry points as librt355.so (the ctypes binding declares them all)
-    deps = [src, lbvh, os.path.join(PKG, "csrc", "rt355_kernels.h"), os.path.join(PKG, "csrc", "lbvh_common.h"),
-            os.path.join(ROOT, "include", "rt355.h"), os.path.join(ROOT, "include", "rt355_types.h")]
+    refit = os.path.join(PKG, "csrc", "refit.hip")
+    deps = [src, lbvh, refit, os.path.join(PKG, "csrc", "rt355_kernels.h"), os.path.join(PKG, "csrc", "lbvh_common.h"),
+            os.path.join(PKG, "csrc", "refit_common.h"), os.path.join(ROOT, "include", "rt355.h"), os.path.join(ROOT, "include", "rt355_types.h")]
     out = os.path.join(PKG, "librt355_refb.so")
     if force or _stale(out, deps):
         # -Bsymbolic: this library defines the same global symbols as librt355.so (C-ABI entry points, the kernels' host stubs).  Loaded
         # into a process that already holds librt355.so, its own references would otherwise bind to THAT library's definitions - and
         # launch the other build's kernels
-        _run([HIPCC] + DEVICE_FLAGS + ["-DRT355_REF_BUILTINS", "-Wl,-Bsymbolic", src, lbvh, "-o", out])
+        _run([HIPCC] + DEVICE_FLAGS + ["-DRT355_REF_BUILTINS", "-Wl,-Bsymbolic", src, lbvh, refit, "-o", out])
     return out
 
 
 def build_host(force=False):
     hdir = os.path.join(PKG, "host")
     srcs = [os.path.join(hdir, f) for f in sorted(os.listdir(hdir)) if f.endswith(".cpp")]
-    deps = srcs + [os.path.join(hdir, "rt_host.h"), os.path.join(PKG, "csrc", "lbvh_common.h"), os.path.join(ROOT, "include", "rt355.h"),
+    deps = srcs + [os.path.join(hdir, "rt_host.h"), os.path.join(PKG, "csrc", "lbvh_common.h"), os.path.join(PKG, "csrc", "refit_common.h"),
+                   os.path.join(ROOT, "include", "rt355.h"),
                    os.path.join(ROOT, "include", "rt355_host.h"), os.path.join(ROOT, "include", "rt355_types.h")]
     out = os.path.join(PKG, "librt355_host.so")
     if force or _stale(out, deps):

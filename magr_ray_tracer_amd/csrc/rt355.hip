@@ -16,6 +16,7 @@
 #include <vector>
 #include "../../include/rt355.h"
 #include "rt355_kernels.h"
+#include "refit_common.h"
 
 using namespace rt355dev;
 
@@ -36,10 +37,33 @@ int rt355_set_error(int code, const char* msg) { g_err = msg; return code; }   /
 
 // The device copy of a scene (uploaded arrays + derived layouts).  Contexts that render the same scene - sample-stream lanes, the
 // row bands of one frame - can hold ONE copy (rt_share_scene): less HBM, and one working set in the L2s / Infinity Cache instead of one per context.
+struct RtCtx;
 struct SceneBag {
     std::vector<void*> allocs;
     int device = 0;
-    ~SceneBag() { (void)hipSetDevice(device); for (void* p : allocs) (void)hipFree(p); }
+    // rt_update_scene: what an in-place update needs of the upload, kept beside the device copy
+    DevScene sc{};                            // the device arrays (an update rewrites them in place: every holder's copy of sc stays valid)
+    std::vector<RtCtx*> holders;              // the contexts rendering from this copy: an update waits for their streams
+    uint64_t generation = 0;                  // bumped when an update changes what configure_traversal depends on (the TLAS depth)
+    int tlasDepth = 0;
+    const char* refitRefusal = nullptr;       // why this scene cannot be updated in place (NULL: it can)
+    int32_t nPrims = 0, nNodes = 0, nIdx = 0, nLights = 0, nTlas = 0, nBlas = 0, nPairs = 0, accel = 0, layout = 0;
+    std::vector<int32_t> primType, primMat;   // host shadow of every primitive's objType / matIdx (the light list and materials depend on them)
+    std::vector<RtBVHInstance> inst;          // the instances as last uploaded or updated
+    uint32_t *dParent = nullptr, *dLeaves = nullptr, *dPairNode = nullptr, *dTickets = nullptr;   // refit topology (walked from the BLAS roots)
+    uint32_t nLeaves = 0, nReach = 0;
+    // staging of an update (allocated by the first one): nothing live is written before the new TLAS has passed
+    RtPrimitive* sPrims = nullptr; RtBVHNode2* sNodes = nullptr; RtBVHInstance* sInst = nullptr; RtTLASNode* sTlas = nullptr;
+    RtFloat4 *sTp = nullptr, *sTpP = nullptr, *sIr = nullptr; int32_t* sStatus = nullptr;
+    hipStream_t stream = nullptr;             // where updates run
+    hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };   // brackets of the staging and of the commit
+    ~SceneBag()
+    {
+        (void)hipSetDevice(device);
+        if (stream) (void)hipStreamDestroy(stream);
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        for (void* p : allocs) (void)hipFree(p);
+    }
 };
 
 struct RtCtx {
@@ -53,6 +77,7 @@ struct RtCtx {
     int nPix = 0, firstPixel = 0, gridMax = 0;
     bool sceneLoaded = false, ownAccum = true;
     std::shared_ptr<SceneBag> scene;      // shared by the contexts of rt_share_scene, freed with the last of them
+    uint64_t sceneGen = 0;                // the SceneBag generation this context's traversal configuration was derived for
     bool singleBlas = false;              // the TLAS root is a leaf
     std::vector<void*> queueAllocs;
     float* dFocus = nullptr;
@@ -86,10 +111,12 @@ enum { ST_GENERATE, ST_EXTEND, ST_SHADE, ST_COMPACT, ST_CONNECT, ST_ACCUM };
 
 extern "C" const char* rt_last_error(void) { return g_err.c_str(); }
 extern "C" int rt_device_count(void) { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess) return 0; return n; }
+static int sync_scene_config(RtCtx* ctx);
 extern "C" int rt_kernel_info(RtCtx* ctx, RtKernelInfo* out)
 {
     if (!ctx || !out) return fail(RT_E_INVALID, "rt_kernel_info: null argument");
     if (!ctx->sceneLoaded) return fail(RT_E_INVALID, "rt_kernel_info: no scene uploaded");
+    if (const int rc = sync_scene_config(ctx)) return rc;
     *out = RtKernelInfo{ ctx->layout, ctx->persist ? 1 : (ctx->persistTlas ? (ctx->spillStack ? 3 : 2) : 0), ctx->persist4 ? 1 : 0, ctx->spillStack ? ctx->spillCap : ctx->stackEntries, ctx->persistGrid, ctx->persistGridConnect,
                          ctx->shadeGrid, ctx->sc.nBlas };
     return RT_OK;
@@ -106,6 +133,22 @@ template <class T> static int dalloc(std::vector<void*>& bag, T** p, size_t coun
     return RT_OK;
 }
 static void free_bag(std::vector<void*>& bag) { for (void* p : bag) (void)hipFree(p); bag.clear(); }
+
+// A context holds at most one device copy of a scene; the copy knows its holders (rt_update_scene waits for them and reconfigures them).
+static void scene_release(RtCtx* ctx)
+{
+    if (!ctx->scene) return;
+    auto& h = ctx->scene->holders;
+    h.erase(std::remove(h.begin(), h.end(), ctx), h.end());
+    ctx->scene.reset();
+}
+static void scene_hold(RtCtx* ctx, const std::shared_ptr<SceneBag>& bag)
+{
+    scene_release(ctx);
+    ctx->scene = bag;
+    bag->holders.push_back(ctx);
+    ctx->sceneGen = bag->generation;
+}
 
 // LDS traversal stack: one column per lane; sized at upload to what this scene's trees can need
 // (never more than the reference kernels' 32 / 64 entries).
@@ -273,7 +316,7 @@ static void ctx_free(RtCtx* ctx)   // every owned resource; safe on a partially 
     if (!ctx) return;
     (void)hipSetDevice(ctx->cfg.device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-    ctx->scene.reset(); free_bag(ctx->queueAllocs);
+    scene_release(ctx); free_bag(ctx->queueAllocs);
     if (ctx->dRayIO) (void)hipFree(ctx->dRayIO);
     if (ctx->dSpill) (void)hipFree(ctx->dSpill);
     if (ctx->dPostF) (void)hipFree(ctx->dPostF);
@@ -416,6 +459,35 @@ extern "C" int rt_validate_scene(int32_t accel, const RtPrimitive* prims, int32_
                           nullptr, nullptr, nullptr);
 }
 
+// What rt_update_scene needs of an upload: the counts, the host shadow of the fields an update must keep, and the refit topology on
+// the device (parents, reachable leaves, pair id -> node id).  A scene the update cannot handle records why (refitRefusal).
+static int prepare_update(RtCtx* ctx, const DevScene& sc, const RtPrimitive* prims, int32_t nPrims, const void* bvhNodes, int32_t nNodes, int32_t nIdx,
+                          int32_t nLights, int32_t nTlas, const RtBVHInstance* blas, int32_t nBlas, const std::vector<uint32_t>& pairNode, int tlasDepth)
+{
+    SceneBag& b = *ctx->scene;
+    b.sc = sc;
+    b.nPrims = nPrims; b.nNodes = nNodes; b.nIdx = nIdx; b.nLights = nLights; b.nTlas = nTlas; b.nBlas = nBlas;
+    b.nPairs = (int32_t)pairNode.size(); b.accel = ctx->cfg.accel; b.layout = ctx->layout; b.tlasDepth = tlasDepth;
+    if (ctx->cfg.accel != RT_ACCEL_BVH2) { b.refitRefusal = "BVH4 scenes cannot be refit"; return RT_OK; }
+    if (nBlas > refit::kMaxInstances) { b.refitRefusal = "more than 256 instances (TLAS::Build's limit)"; return RT_OK; }
+    if (nTlas != 2 * nBlas) { b.refitRefusal = "the TLAS does not have TLAS::Build's 2 x instances nodes"; return RT_OK; }
+    refit::Topology t;
+    if (const char* why = refit::build_topology((const RtBVHNode2*)bvhNodes, nNodes, blas, nBlas, t)) { b.refitRefusal = why; return RT_OK; }
+    b.primType.resize((size_t)nPrims); b.primMat.resize((size_t)nPrims);
+    for (int32_t i = 0; i < nPrims; i++) { b.primType[(size_t)i] = prims[i].objType; b.primMat[(size_t)i] = prims[i].matIdx; }
+    b.inst.assign(blas, blas + nBlas);
+    b.nLeaves = (uint32_t)t.leaves.size(); b.nReach = (uint32_t)t.order.size();
+    int rc = dalloc(b.allocs, &b.dParent, t.parent.size());
+    if (rc == RT_OK) rc = dalloc(b.allocs, &b.dLeaves, t.leaves.size());
+    if (rc == RT_OK) rc = dalloc(b.allocs, &b.dTickets, (size_t)nNodes);
+    if (rc == RT_OK) rc = dalloc(b.allocs, &b.dPairNode, pairNode.size());
+    if (rc != RT_OK) return rc;
+    HIPCHK(hipMemcpy(b.dParent, t.parent.data(), sizeof(uint32_t) * t.parent.size(), hipMemcpyHostToDevice));
+    if (!t.leaves.empty()) HIPCHK(hipMemcpy(b.dLeaves, t.leaves.data(), sizeof(uint32_t) * t.leaves.size(), hipMemcpyHostToDevice));
+    if (!pairNode.empty()) HIPCHK(hipMemcpy(b.dPairNode, pairNode.data(), sizeof(uint32_t) * pairNode.size(), hipMemcpyHostToDevice));
+    return RT_OK;
+}
+
 extern "C" int rt_upload_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t nPrims, const RtMaterial* mats, int32_t nMats,
                                const RtFloat4* textures, int32_t nTexels, const uint32_t* lights, int32_t nLights,
                                const void* bvhNodes, int32_t nNodes, const uint32_t* primIdx, int32_t nIdx,
@@ -430,7 +502,7 @@ extern "C" int rt_upload_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t nPr
     }
     HIPCHK(hipSetDevice(ctx->cfg.device));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    ctx->scene = std::make_shared<SceneBag>();   // (a copy shared with other contexts lives on with them)
+    scene_hold(ctx, std::make_shared<SceneBag>());   // (a copy shared with other contexts lives on with them)
     ctx->scene->device = ctx->cfg.device;
     ctx->sceneLoaded = false; ctx->persist = false; ctx->persist4 = false; ctx->layout = 0;   // nothing usable until this upload has succeeded
     ctx->sc = DevScene{};
@@ -456,14 +528,9 @@ extern "C" int rt_upload_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t nPr
     if (rc == RT_OK) rc = upload(ctx, &sc.blas, blas, (size_t)nBlas);
     if (rc == RT_OK) { // dense shading records (k_shade): geometric normal + material id + type per primitive
         std::vector<float4> recs((size_t)nPrims);
-        for (int32_t i = 0; i < nPrims; i++) {
-            const RtPrimitive& p = prims[i];
-            const RtFloat4 N = p.objType == RT_PRIM_TRIANGLE ? p.obj.triangle.N : (p.objType == RT_PRIM_PLANE ? p.obj.plane.N : RtFloat4{ 0, 0, 0, 0 });
-            uint32_t tag = ((uint32_t)p.objType << 28) | ((uint32_t)p.matIdx & 0x07ffffffu) | (std::signbit(N.w) ? 0x08000000u : 0u);
-            // a triangle/plane normal with a non-zero w lane cannot be represented: mark it like a sphere (reference-layout path)
-            if (p.objType != RT_PRIM_SPHERE && N.w != 0.0f) tag = ((uint32_t)RT_PRIM_SPHERE << 28) | ((uint32_t)p.matIdx & 0x07ffffffu);
-            float w; memcpy(&w, &tag, 4);
-            recs[(size_t)i] = make_float4(N.x, N.y, N.z, w);
+        for (int32_t i = 0; i < nPrims; i++) {   // refit_common.h (k_shade_recs rewrites them)
+            const RtFloat4 r = refit::shade_rec(prims[i]);
+            recs[(size_t)i] = make_float4(r.x, r.y, r.z, r.w);
         }
         rc = upload(ctx, &sc.shadeRecs, recs.data(), recs.size());
     }
@@ -471,9 +538,7 @@ extern "C" int rt_upload_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t nPr
         std::vector<float4> lr(std::max<size_t>((size_t)nLights, 1) * 8, make_float4(0, 0, 0, 0));
         for (int32_t i = 0; i < nLights; i++) {
             const RtPrimitive& p = prims[lights[i]];
-            memcpy(&lr[(size_t)i * 8], &p.obj, 64);
-            float t; int32_t ty = p.objType; memcpy(&t, &ty, 4);
-            lr[(size_t)i * 8 + 4] = make_float4(t, p.area, 0, 0);
+            refit::light_rec(p, (RtFloat4*)&lr[(size_t)i * 8]);   // refit_common.h (k_light_recs rewrites words 0..4)
             const RtFloat4& e = mats[p.matIdx].emittance;
             lr[(size_t)i * 8 + 5] = make_float4(e.x, e.y, e.z, e.w);
         }
@@ -481,6 +546,7 @@ extern "C" int rt_upload_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t nPr
     }
     // Derived layout 1 (rt355_kernels.h, traverse_bvh2_packed): only for BVH2, when the encodings fit.
     ctx->layout = 0;
+    std::vector<uint32_t> pairNode;   // pair id -> node id (rt_update_scene rewrites the pairs' boxes)
     if (rc == RT_OK && ctx->cfg.accel == RT_ACCEL_BVH2 && ctx->cfg.extend_variant != 1 && nIdx < (1 << 24)) {
         const RtBVHNode2* n2 = (const RtBVHNode2*)bvhNodes;
         bool fits = true;
@@ -505,27 +571,14 @@ extern "C" int rt_upload_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t nPr
             auto entry = [&](uint32_t i) { return n2[i].count > 0 ? (0x80000000u | (n2[i].count << 24) | n2[i].first) : newId[i]; };
             auto f2u = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
             std::vector<float4> pairs(std::max<size_t>(order.size(), 1) * 4, make_float4(0, 0, 0, 0));
-            for (size_t k = 0; k < order.size(); k++) {
+            for (size_t k = 0; k < order.size(); k++) {   // (box rule: refit_common.h, k_pair_boxes rewrites them)
                 const uint32_t i = order[k];
-                const RtBVHNode2& a = n2[n2[i].first]; const RtBVHNode2& b = n2[n2[i].first + 1];
-                pairs[k * 4 + 0] = make_float4(a.aabbMin.x, a.aabbMin.y, a.aabbMin.z, a.aabbMax.x);
-                pairs[k * 4 + 1] = make_float4(a.aabbMax.y, a.aabbMax.z, b.aabbMin.x, b.aabbMin.y);
-                pairs[k * 4 + 2] = make_float4(b.aabbMin.z, b.aabbMax.x, b.aabbMax.y, b.aabbMax.z);
+                refit::pair_boxes(n2[n2[i].first], n2[n2[i].first + 1], (RtFloat4*)&pairs[k * 4]);
                 pairs[k * 4 + 3] = make_float4(f2u(entry(n2[i].first)), f2u(entry(n2[i].first + 1)), 0, 0);
             }
             std::vector<float4> recs((size_t)nIdx * 3);
-            for (int32_t s = 0; s < nIdx; s++) {
-                const RtPrimitive& p = prims[primIdx[s]];
-                const RtTriangle& t = p.obj.triangle;
-                const bool plain = p.objType == RT_PRIM_TRIANGLE && t.v0.w == 0.0f && t.v1.w == 0.0f && t.v2.w == 0.0f;
-                // v0 and the edges v1 - v0, v2 - v0: the first two operations of the reference's triangle test (primitives.cl:49-50), done
-                // here once with the same IEEE subtraction (this file is built with -ffp-contract=off like the kernels)
-                const float e1x = t.v1.x - t.v0.x, e1y = t.v1.y - t.v0.y, e1z = t.v1.z - t.v0.z;
-                const float e2x = t.v2.x - t.v0.x, e2y = t.v2.y - t.v0.y, e2z = t.v2.z - t.v0.z;
-                recs[(size_t)s * 3 + 0] = make_float4(t.v0.x, t.v0.y, t.v0.z, e1x);
-                recs[(size_t)s * 3 + 1] = make_float4(e1y, e1z, e2x, e2y);
-                recs[(size_t)s * 3 + 2] = make_float4(e2z, f2u(primIdx[s]), f2u(plain ? 0u : 1u), 0);
-            }
+            for (int32_t s = 0; s < nIdx; s++) refit::tri_rec(prims[primIdx[s]], primIdx[s], (RtFloat4*)&recs[(size_t)s * 3]);   // refit_common.h
+            pairNode = order;
             std::vector<uint32_t> roots((size_t)nBlas);
             for (int32_t b = 0; b < nBlas; b++) roots[b] = entry(blas[b].bvhIdx);
             rc = upload(ctx, &sc.pairs, pairs.data(), pairs.size());
@@ -575,65 +628,38 @@ extern "C" int rt_upload_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t nPr
             for (int32_t b = 0; b < nBlas; b++) roots[b] = newId[blas[b].bvhIdx];
             if (rc == RT_OK) rc = upload(ctx, &sc.rootEntry, roots.data(), roots.size());
             std::vector<float4> recs((size_t)nIdx * 3);
-            for (int32_t s = 0; s < nIdx; s++) {
-                const RtPrimitive& p = prims[primIdx[s]];
-                const RtTriangle& t = p.obj.triangle;
-                const bool plain = p.objType == RT_PRIM_TRIANGLE && t.v0.w == 0.0f && t.v1.w == 0.0f && t.v2.w == 0.0f;
-                // v0 and the edges v1 - v0, v2 - v0: the first two operations of the reference's triangle test (primitives.cl:49-50), done
-                // here once with the same IEEE subtraction (this file is built with -ffp-contract=off like the kernels)
-                const float e1x = t.v1.x - t.v0.x, e1y = t.v1.y - t.v0.y, e1z = t.v1.z - t.v0.z;
-                const float e2x = t.v2.x - t.v0.x, e2y = t.v2.y - t.v0.y, e2z = t.v2.z - t.v0.z;
-                recs[(size_t)s * 3 + 0] = make_float4(t.v0.x, t.v0.y, t.v0.z, e1x);
-                recs[(size_t)s * 3 + 1] = make_float4(e1y, e1z, e2x, e2y);
-                recs[(size_t)s * 3 + 2] = make_float4(e2z, f2u(primIdx[s]), f2u(plain ? 0u : 1u), 0);
-            }
+            for (int32_t s = 0; s < nIdx; s++) refit::tri_rec(prims[primIdx[s]], primIdx[s], (RtFloat4*)&recs[(size_t)s * 3]);   // refit_common.h
             rc = upload(ctx, &sc.quads, quads.data(), quads.size());
             if (rc == RT_OK) rc = upload(ctx, &sc.triRecs, recs.data(), recs.size());
             if (rc == RT_OK) ctx->layout = 1;
         }
     }
     if (rc == RT_OK) { // derived TLAS records and instance records (traverse_tlas / traverse_instance)
-        auto f2u = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
         auto enc = [&](uint32_t n) { return tlas[n].leftRight == 0 ? (0x80000000u | tlas[n].BLASidx) : n; };
         std::vector<float4> tp((size_t)nTlas * 4, make_float4(0, 0, 0, 0));
-        for (int32_t i = 0; i < nTlas; i++) {
-            const uint32_t lr = tlas[i].leftRight;
-            if (lr == 0) continue;
-            const RtTLASNode& a = tlas[lr & 0xffffu]; const RtTLASNode& b = tlas[lr >> 16];
-            tp[(size_t)i * 4 + 0] = make_float4(a.aabbMin.x, a.aabbMin.y, a.aabbMin.z, a.aabbMax.x);
-            tp[(size_t)i * 4 + 1] = make_float4(a.aabbMax.y, a.aabbMax.z, b.aabbMin.x, b.aabbMin.y);
-            tp[(size_t)i * 4 + 2] = make_float4(b.aabbMin.z, b.aabbMax.x, b.aabbMax.y, b.aabbMax.z);
-            tp[(size_t)i * 4 + 3] = make_float4(f2u(enc(lr & 0xffffu)), f2u(enc(lr >> 16)), 0, 0);
-        }
+        for (int32_t i = 0; i < nTlas; i++) refit::tlas_pair(tlas, (uint32_t)i, false, (RtFloat4*)&tp[(size_t)i * 4]);   // refit_common.h (k_tlas_build)
         std::vector<uint32_t> roots((size_t)nBlas, 0u);
         if (ctx->layout == 1) HIPCHK(hipMemcpy(roots.data(), sc.rootEntry, sizeof(uint32_t) * (size_t)nBlas, hipMemcpyDeviceToHost));
         std::vector<float4> ir((size_t)nBlas * 4);
-        for (int32_t b = 0; b < nBlas; b++) {
-            const float* T = blas[b].invT;
-            ir[(size_t)b * 4 + 0] = make_float4(T[0], T[1], T[2], T[3]);
-            ir[(size_t)b * 4 + 1] = make_float4(T[4], T[5], T[6], T[7]);
-            ir[(size_t)b * 4 + 2] = make_float4(T[8], T[9], T[10], T[11]);
-            ir[(size_t)b * 4 + 3] = make_float4(f2u(roots[(size_t)b]), f2u(blas[b].bvhIdx), 0, 0);
-        }
+        for (int32_t b = 0; b < nBlas; b++) refit::inst_rec(blas[b], roots[(size_t)b], (RtFloat4*)&ir[(size_t)b * 4]);   // refit_common.h
         rc = upload(ctx, &sc.tlasPairs, tp.data(), tp.size());
         if (rc == RT_OK) rc = upload(ctx, &sc.instRecs, ir.data(), ir.size());
         sc.tlasRoot = enc(0);
         // the same records with the children in the tagged encoding of k_trace_persist_tlas (TLAS interior / instance ids on the BLAS stack)
         auto encP = [&](uint32_t n) { return tlas[n].leftRight == 0 ? (kTagInst | tlas[n].BLASidx) : (kTagTlas | n); };
-        for (int32_t i = 0; i < nTlas; i++) {
-            const uint32_t lr = tlas[i].leftRight;
-            if (lr != 0) tp[(size_t)i * 4 + 3] = make_float4(f2u(encP(lr & 0xffffu)), f2u(encP(lr >> 16)), 0, 0);
-        }
+        for (int32_t i = 0; i < nTlas; i++) refit::tlas_pair(tlas, (uint32_t)i, true, (RtFloat4*)&tp[(size_t)i * 4]);
         if (rc == RT_OK) rc = upload(ctx, &sc.tlasPairsP, tp.data(), tp.size());
         sc.tlasRootP = encP(0);
     }
-    if (rc != RT_OK) { ctx->scene.reset(); ctx->sceneLoaded = false; return rc; }
+    if (rc != RT_OK) { scene_release(ctx); ctx->sceneLoaded = false; return rc; }
     sc.nLights = nLights; sc.nPrims = nPrims; sc.nBlas = nBlas; sc.nTex = nTexels;
+    rc = prepare_update(ctx, sc, prims, nPrims, bvhNodes, nNodes, nIdx, nLights, nTlas, blas, nBlas, pairNode, tlasDepth);
+    if (rc != RT_OK) { scene_release(ctx); ctx->sceneLoaded = false; return rc; }
     ctx->singleBlas = tlas[0].leftRight == 0;
     ctx->sc = sc;
     ctx->stackEntries = stackEntries; ctx->tlasDepth = tlasDepth; ctx->nInterior = nInterior;
     rc = configure_traversal(ctx);
-    if (rc != RT_OK) { ctx->scene.reset(); return rc; }
+    if (rc != RT_OK) { scene_release(ctx); return rc; }
     ctx->sceneLoaded = true;
     return RT_OK;
 }
@@ -753,12 +779,168 @@ extern "C" int rt_share_scene(RtCtx* ctx, RtCtx* from)
     HIPCHK(hipSetDevice(ctx->cfg.device));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     ctx->sceneLoaded = false;
-    ctx->scene = from->scene;
+    scene_hold(ctx, from->scene);
     ctx->sc = from->sc;
-    ctx->layout = from->layout; ctx->maxDepth2 = from->maxDepth2; ctx->stackEntries = from->stackEntries; ctx->singleBlas = from->singleBlas; ctx->tlasDepth = from->tlasDepth; ctx->nInterior = from->nInterior;
+    ctx->layout = from->layout; ctx->maxDepth2 = from->maxDepth2; ctx->stackEntries = from->stackEntries; ctx->singleBlas = from->singleBlas; ctx->tlasDepth = from->scene->tlasDepth; ctx->nInterior = from->nInterior;
     const int rc = configure_traversal(ctx);
-    if (rc != RT_OK) { ctx->scene.reset(); return rc; }
+    if (rc != RT_OK) { scene_release(ctx); return rc; }
     ctx->sceneLoaded = true;
+    return RT_OK;
+}
+
+// ---- in-place scene updates (rt_update_scene; kernels: refit.hip, rules: refit_common.h) ------------------------------------------
+namespace refitdev {
+hipError_t launch_refit(hipStream_t s, RtBVHNode2* nodes, uint32_t nNodes, const RtPrimitive* prims, const uint32_t* primIdx,
+                        const uint32_t* leaves, uint32_t nLeaves, const uint32_t* parent, uint32_t* tickets);
+hipError_t launch_tlas(hipStream_t s, const RtBVHNode2* nodes, const RtBVHInstance* inst, int n, const uint32_t* rootEntry,
+                       RtTLASNode* tlas, RtFloat4* tp, RtFloat4* tpP, RtFloat4* ir, int32_t* status);
+hipError_t launch_records(hipStream_t s, const RtPrimitive* prims, const RtBVHNode2* nodes, const uint32_t* primIdx, uint32_t nIdx,
+                          const uint32_t* lights, uint32_t nLights, uint32_t first, uint32_t count, const uint32_t* pairNode,
+                          uint32_t nPairs, RtFloat4* pairs, RtFloat4* triRecs, RtFloat4* shadeRecs, RtFloat4* lightRecs);
+}
+
+// A holder of a scene copy that an update has changed re-derives its traversal configuration (the TLAS depth decides persistTlas,
+// the spill choice, the TLAS stack bytes and the spill buffer) before its next launch.
+static int sync_scene_config(RtCtx* ctx)
+{
+    if (!ctx->scene || ctx->sceneGen == ctx->scene->generation) return RT_OK;
+    ctx->tlasDepth = ctx->scene->tlasDepth;
+    const int rc = configure_traversal(ctx);
+    if (rc != RT_OK) return rc;
+    ctx->sceneGen = ctx->scene->generation;
+    return RT_OK;
+}
+
+template <class T> static T* mut(const T* p) { return const_cast<T*>(p); }   // the scene's own allocations, read-only for the renderers
+
+static int update_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
+                        RtUpdateStats* stats)
+{
+    // ---- refusals: before anything is written
+    if (b.refitRefusal) return fail(RT_E_UNSUPPORTED, "rt_update_scene: %s", b.refitRefusal);
+    if (count < 0 || (count > 0 && !prims)) return fail(RT_E_INVALID, "rt_update_scene: bad primitive count %d / NULL records", count);
+    if (count > 0 && (first < 0 || (int64_t)first + count > (int64_t)b.nPrims))
+        return fail(RT_E_INVALID, "rt_update_scene: primitive range [%d, %lld) outside the %d uploaded", first, (long long)first + count, b.nPrims);
+    for (int32_t i = 0; i < count; i++) {
+        const size_t g = (size_t)first + (size_t)i;
+        if (prims[i].objType != b.primType[g] || prims[i].matIdx != b.primMat[g])
+            return fail(RT_E_INVALID, "rt_update_scene: primitive %zu changes its objType / matIdx (%d / %d -> %d / %d): topology must not change", g,
+                        b.primType[g], b.primMat[g], prims[i].objType, prims[i].matIdx);
+    }
+    if (blas) {
+        if (nBlas != b.nBlas) return fail(RT_E_INVALID, "rt_update_scene: %d instances given, %d uploaded", nBlas, b.nBlas);
+        for (int32_t k = 0; k < nBlas; k++) {
+            if (blas[k].bvhIdx != b.inst[(size_t)k].bvhIdx) return fail(RT_E_INVALID, "rt_update_scene: instance %d changes its bvhIdx", k);
+            if (refit::singular(blas[k].invT)) return fail(RT_E_INVALID, "rt_update_scene: instance %d: the transform is singular", k);
+        }
+    }
+    HIPCHK(hipSetDevice(b.device));
+    // ---- staging buffers (first update)
+    if (!b.sPrims) {
+        int rc = dalloc(b.allocs, &b.sPrims, (size_t)b.nPrims);
+        if (rc == RT_OK) rc = dalloc(b.allocs, &b.sNodes, (size_t)b.nNodes);
+        if (rc == RT_OK) rc = dalloc(b.allocs, &b.sInst, (size_t)b.nBlas);
+        if (rc == RT_OK) rc = dalloc(b.allocs, &b.sTlas, (size_t)b.nTlas);
+        if (rc == RT_OK) rc = dalloc(b.allocs, &b.sTp, (size_t)b.nTlas * 4);
+        if (rc == RT_OK) rc = dalloc(b.allocs, &b.sTpP, (size_t)b.nTlas * 4);
+        if (rc == RT_OK) rc = dalloc(b.allocs, &b.sIr, (size_t)b.nBlas * 4);
+        if (rc == RT_OK) rc = dalloc(b.allocs, &b.sStatus, 2);
+        if (rc != RT_OK) { b.sPrims = nullptr; return rc; }
+        HIPCHK(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));
+        for (hipEvent_t& e : b.ev) HIPCHK(hipEventCreate(&e));
+    }
+    const DevScene& sc = b.sc;
+    hipStream_t s = b.stream;
+    // ---- stage: the new primitives, the refit tree and the rebuilt TLAS in scratch
+    HIPCHK(hipEventRecord(b.ev[0], s));
+    HIPCHK(hipMemcpyAsync(b.sPrims, sc.prims, sizeof(RtPrimitive) * (size_t)b.nPrims, hipMemcpyDeviceToDevice, s));
+    if (count) HIPCHK(hipMemcpyAsync(b.sPrims + first, prims, sizeof(RtPrimitive) * (size_t)count, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(b.sNodes, sc.bvh2, sizeof(RtBVHNode2) * (size_t)b.nNodes, hipMemcpyDeviceToDevice, s));
+    if (blas) HIPCHK(hipMemcpyAsync(b.sInst, blas, sizeof(RtBVHInstance) * (size_t)b.nBlas, hipMemcpyHostToDevice, s));
+    else HIPCHK(hipMemcpyAsync(b.sInst, sc.blas, sizeof(RtBVHInstance) * (size_t)b.nBlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(refitdev::launch_refit(s, b.sNodes, (uint32_t)b.nNodes, b.sPrims, sc.primIdx, b.dLeaves, b.nLeaves, b.dParent, b.dTickets));
+    HIPCHK(refitdev::launch_tlas(s, b.sNodes, b.sInst, b.nBlas, b.layout == 1 ? sc.rootEntry : nullptr, b.sTlas, b.sTp, b.sTpP, b.sIr, b.sStatus));
+    int32_t status[2] = { 0, 0 };
+    HIPCHK(hipEventRecord(b.ev[1], s));
+    HIPCHK(hipMemcpyAsync(status, b.sStatus, sizeof status, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (status[0] == 1) return fail(RT_E_INVALID, "rt_update_scene: an instance transform is singular");
+    if (status[0] != 0) return fail(RT_E_UNSUPPORTED, "rt_update_scene: the TLAS clustering found no partner (boxes of area >= RT_REALLYFAR or NaN)");
+    if (status[1] > RT_TLAS_STACK)
+        return fail(RT_E_UNSUPPORTED, "rt_update_scene: the rebuilt TLAS is %d levels deep, the traversal stack holds %d; the scene is unchanged", status[1], RT_TLAS_STACK);
+    // ---- commit: no kernel of a context holding this copy may read the arrays while they are rewritten
+    for (RtCtx* h : b.holders) {
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (h->home != h->stream) HIPCHK(hipStreamSynchronize(h->home));
+    }
+    HIPCHK(hipEventRecord(b.ev[2], s));
+    if (count) HIPCHK(hipMemcpyAsync(mut(sc.prims) + first, b.sPrims + first, sizeof(RtPrimitive) * (size_t)count, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(mut(sc.bvh2), b.sNodes, sizeof(RtBVHNode2) * (size_t)b.nNodes, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(mut(sc.blas), b.sInst, sizeof(RtBVHInstance) * (size_t)b.nBlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(mut(sc.tlas), b.sTlas, sizeof(RtTLASNode) * (size_t)b.nTlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(mut(sc.tlasPairs), b.sTp, sizeof(float4) * 4 * (size_t)b.nTlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(mut(sc.tlasPairsP), b.sTpP, sizeof(float4) * 4 * (size_t)b.nTlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(mut(sc.instRecs), b.sIr, sizeof(float4) * 4 * (size_t)b.nBlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(refitdev::launch_records(s, sc.prims, sc.bvh2, sc.primIdx, (uint32_t)b.nIdx, sc.lights, (uint32_t)b.nLights, (uint32_t)std::max(first, 0),
+                                    (uint32_t)count, b.dPairNode, (uint32_t)b.nPairs, b.layout == 1 ? (RtFloat4*)mut(sc.pairs) : nullptr,
+                                    b.layout == 1 ? (RtFloat4*)mut(sc.triRecs) : nullptr, (RtFloat4*)mut(sc.shadeRecs), (RtFloat4*)mut(sc.lightRecs)));
+    HIPCHK(hipEventRecord(b.ev[3], s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (blas) b.inst.assign(blas, blas + nBlas);
+    const bool reconfigure = status[1] != b.tlasDepth;
+    if (reconfigure) { b.tlasDepth = status[1]; b.generation++; }
+    if (stats) {
+        float ms = 0, ms2 = 0;   // GPU time of both phases (not the wait for the holders in between)
+        (void)hipEventElapsedTime(&ms, b.ev[0], b.ev[1]); (void)hipEventElapsedTime(&ms2, b.ev[2], b.ev[3]);
+        ms += ms2;
+        *stats = RtUpdateStats{};
+        stats->gpu_ms = ms; stats->prims = count; stats->nodes = (int32_t)b.nReach; stats->tlas_nodes = b.nTlas; stats->tlas_depth = status[1];
+        stats->reconfigured = reconfigure ? 1 : 0;
+    }
+    return RT_OK;
+}
+extern "C" int rt_update_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
+                               RtUpdateStats* stats)
+{
+    if (!ctx) return fail(RT_E_INVALID, "rt_update_scene: null context");
+    if (!ctx->sceneLoaded || !ctx->scene) return fail(RT_E_INVALID, "rt_update_scene: no scene uploaded");
+    if (ctx->cfg.accel != RT_ACCEL_BVH2) return fail(RT_E_UNSUPPORTED, "rt_update_scene: BVH4 contexts cannot refit (rebuild and upload instead)");
+    return update_scene(*ctx->scene, prims, first, count, blas, nBlas, stats);
+}
+extern "C" int rt_group_update_scene(RtGroup* g, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
+                                     RtUpdateStats* stats)
+{
+    if (!g) return fail(RT_E_INVALID, "rt_group_update_scene: null group");
+    return rt_update_scene(rt_group_lane(g, 0), prims, first, count, blas, nBlas, stats);   // every lane holds lane 0's copy
+}
+extern "C" int rt_debug_get_scene_array(RtCtx* ctx, int32_t which, void* out, int64_t capacityBytes, int64_t* bytes)
+{
+    if (!ctx || !bytes) return fail(RT_E_INVALID, "rt_debug_get_scene_array: null argument");
+    if (!ctx->sceneLoaded || !ctx->scene) return fail(RT_E_INVALID, "rt_debug_get_scene_array: no scene uploaded");
+    const SceneBag& b = *ctx->scene;
+    const DevScene& sc = b.sc;
+    const void* src = nullptr; size_t n = 0;
+    switch (which) {
+    case RT_SCENE_PRIMS:        src = sc.prims; n = sizeof(RtPrimitive) * (size_t)b.nPrims; break;
+    case RT_SCENE_BVH:          src = b.accel == RT_ACCEL_BVH4 ? (const void*)sc.bvh4 : (const void*)sc.bvh2;
+                                n = (b.accel == RT_ACCEL_BVH4 ? sizeof(RtBVHNode4) : sizeof(RtBVHNode2)) * (size_t)b.nNodes; break;
+    case RT_SCENE_TLAS:         src = sc.tlas; n = sizeof(RtTLASNode) * (size_t)b.nTlas; break;
+    case RT_SCENE_INSTANCES:    src = sc.blas; n = sizeof(RtBVHInstance) * (size_t)b.nBlas; break;
+    case RT_SCENE_PAIRS:        src = sc.pairs; n = sc.pairs ? sizeof(float4) * 4 * (size_t)b.nPairs : 0; break;
+    case RT_SCENE_TRI_RECS:     src = sc.triRecs; n = sc.triRecs ? sizeof(float4) * 3 * (size_t)b.nIdx : 0; break;
+    case RT_SCENE_SHADE_RECS:   src = sc.shadeRecs; n = sizeof(float4) * (size_t)b.nPrims; break;
+    case RT_SCENE_LIGHT_RECS:   src = sc.lightRecs; n = sizeof(float4) * 8 * (size_t)b.nLights; break;
+    case RT_SCENE_TLAS_PAIRS:   src = sc.tlasPairs; n = sizeof(float4) * 4 * (size_t)b.nTlas; break;
+    case RT_SCENE_TLAS_PAIRS_P: src = sc.tlasPairsP; n = sizeof(float4) * 4 * (size_t)b.nTlas; break;
+    case RT_SCENE_INST_RECS:    src = sc.instRecs; n = sizeof(float4) * 4 * (size_t)b.nBlas; break;
+    default: return fail(RT_E_INVALID, "rt_debug_get_scene_array: unknown array %d", which);
+    }
+    *bytes = (int64_t)n;
+    if (!out || n == 0) return RT_OK;
+    if (capacityBytes < (int64_t)n) return fail(RT_E_INVALID, "rt_debug_get_scene_array: %zu bytes needed, capacity %lld", n, (long long)capacityBytes);
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipMemcpy(out, src, n, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 
@@ -823,7 +1005,7 @@ static int need_scene(RtCtx* ctx, const char* who)
 {
     if (!ctx) return fail(RT_E_INVALID, "%s: null context", who);
     if (!ctx->sceneLoaded) return fail(RT_E_INVALID, "%s: no scene uploaded", who);
-    return RT_OK;
+    return sync_scene_config(ctx);
 }
 static inline dim3 grid_for(int n) { return dim3((unsigned)std::max(1, (n + kBlock - 1) / kBlock)); }
 

@@ -115,6 +115,22 @@ int rth_bvh4_from_nodes(const RtBVHNode2* nodes, int n, RtBVHNode4* out)
         return 0;
     } catch (const std::exception& e) { g_herr = e.what(); return -1; }
 }
+int rth_set_primitives(RthScene* s, int first, int count, const RtPrimitive* prims)
+{
+    if (!s) { g_herr = "rth_set_primitives: null scene"; return RT_E_INVALID; }
+    std::string err;
+    const int rc = SetPrimitivesHost(s->scene.primitives, first, count, prims, err);
+    if (rc != RT_OK) g_herr = err;
+    return rc;
+}
+int rth_refit(RthScene* s)
+{
+    if (!s || !s->scene.bvh2) { g_herr = "rth_refit: null scene"; return RT_E_INVALID; }
+    std::string err;
+    const int rc = RefitHost(s->scene.bvh2->bvhNodes, s->scene.bvh2->primIdx, s->scene.primitives, s->scene.blasNodes, err);
+    if (rc != RT_OK) g_herr = err;
+    return rc;
+}
 int rth_build_tlas(RthScene* s) { GUARD(delete s->tlas; s->tlas = new TLAS(*s->scene.bvh2); s->tlas->Build()) }
 int rth_set_instance_transform(RthScene* s, int blas, const float invT[16])
 {

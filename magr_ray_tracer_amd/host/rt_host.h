@@ -103,6 +103,12 @@ int LbvhBuildHost(const RtBuildOptions* opt, const RtPrimitive* prims, int32_t n
                   uint32_t idxBase, RtBVHNode2* nodes, int32_t nodeCap, int32_t* nNodes, uint32_t* primIdx, RtBuildStats* stats,
                   std::string& err);
 
+// In-place updates (refit_host.cpp, the host restatement of rt_update_scene): replace primitives keeping objType / matIdx, then refit
+// every BLAS by the rules of csrc/refit_common.h; err receives why a call is refused (RT_E_* returned, nothing changed).
+int SetPrimitivesHost(std::vector<RtPrimitive>& prims, int32_t first, int32_t count, const RtPrimitive* in, std::string& err);
+int RefitHost(std::vector<RtBVHNode2>& nodes, const std::vector<uint32_t>& primIdx, const std::vector<RtPrimitive>& prims,
+              const std::vector<RtBVHInstance>& inst, std::string& err);
+
 // reference: src/bvh.h:41-56
 class BVH4 {
 public:

@@ -14,6 +14,20 @@ class RtError(RuntimeError):
     pass
 
 
+def _update_args(prims, first, instances):
+    p = None if prims is None else np.ascontiguousarray(prims, dtype=_lib.Primitive)
+    b = None if instances is None else np.ascontiguousarray(instances, dtype=_lib.BVHInstance)
+    st = np.zeros((), dtype=_lib.UpdateStats)
+    args = (_lib.ptr(p) if p is not None and len(p) else None, int(first), 0 if p is None else len(p),
+            _lib.ptr(b) if b is not None else None, 0 if b is None else len(b), _lib.ptr(st))
+    return args, (p, b), st
+
+
+def _update_dict(st):
+    return {"gpu_ms": float(st["gpu_ms"]), "prims": int(st["prims"]), "nodes": int(st["nodes"]), "tlas_nodes": int(st["tlas_nodes"]),
+            "tlas_depth": int(st["tlas_depth"]), "reconfigured": bool(st["reconfigured"])}
+
+
 class Device:
     def __init__(self, width, height, y0=0, y1=None, shading=_lib.SHADING_NEE, sampling=_lib.SAMPLING_COSINE,
                  accel=_lib.ACCEL_BVH2, russian_roulette=True, filter_fireflies=True, max_bounces=_lib.MAX_BOUNCES,
@@ -78,6 +92,24 @@ class Device:
     def share_scene(self, other):
         """Render the scene `other` (a Device on the same GPU, same accel) holds, from ITS device copy (rt_share_scene)."""
         self._chk(self._lib.rt_share_scene(self._h, other._h))
+
+    def update_scene(self, prims=None, first=0, instances=None):
+        """Update the bound scene in place on the GPU (rt_update_scene): `prims` replace primitives [first, first + len(prims)) keeping
+        their objType / matIdx, `instances` replace the instances (only invT may change); every BLAS is refit, the derived records are
+        rewritten and the TLAS is rebuilt on the device.  Every context holding the scene sees the update.  Returns the stats."""
+        args, keep, st = _update_args(prims, first, instances)
+        self._chk(self._lib.rt_update_scene(self._h, *args))
+        return _update_dict(st)
+
+    def scene_array(self, name):
+        """A device array of the bound scene as raw bytes (rt_debug_get_scene_array; names: _lib.SCENE_ARRAYS)."""
+        which = _lib.SCENE_ARRAYS[name]
+        n = C.c_int64(0)
+        self._chk(self._lib.rt_debug_get_scene_array(self._h, which, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.uint8)
+        if n.value:
+            self._chk(self._lib.rt_debug_get_scene_array(self._h, which, _lib.ptr(out), n.value, C.byref(n)))
+        return out
 
     def kernel_info(self):
         """Which traversal kernels this context runs for the uploaded scene (rt_kernel_info)."""
@@ -278,6 +310,12 @@ class Group:
     def share_scene(self, other):
         """Render the scene another Group on the same GPU holds, from its device copy."""
         self._chk(self._lib.rt_group_share_scene(self._h, other._h))
+
+    def update_scene(self, prims=None, first=0, instances=None):
+        """Device.update_scene for the group's scene copy (rt_group_update_scene): every lane sees the update."""
+        args, keep, st = _update_args(prims, first, instances)
+        self._chk(self._lib.rt_group_update_scene(self._h, *args))
+        return _update_dict(st)
 
     def seed(self, first_stream=0):
         self._chk(self._lib.rt_group_seed(self._h, int(first_stream)))

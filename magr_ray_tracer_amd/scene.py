@@ -155,6 +155,17 @@ class Scene:
     def BuildTLAS(self):
         self._chk(self._lib.rth_build_tlas(self._h))
 
+    def SetPrimitives(self, first, prims):
+        """Replace primitives [first, first + len(prims)) with records of the same objType and matIdx (rth_set_primitives), e.g. the
+        `arrays().prims` of a second Scene built with the same calls and moved vertices.  The trees are not touched: Refit() next."""
+        p = np.ascontiguousarray(prims, dtype=_lib.Primitive)
+        self._chk(self._lib.rth_set_primitives(self._h, int(first), len(p), _lib.ptr(p) if len(p) else None))
+
+    def Refit(self):
+        """Refit every BLAS of the BVH2 in place by the rules rt_update_scene runs on the GPU (rth_refit); arrays() / BuildTLAS() then
+        rebuild the TLAS (and the BVH4) from the refit tree."""
+        self._chk(self._lib.rth_refit(self._h))
+
     def SetInstanceTransform(self, blas, invT):
         self._chk(self._lib.rth_set_instance_transform(self._h, int(blas), _lib.fvec(np.asarray(invT, dtype=np.float32).ravel())))
 
