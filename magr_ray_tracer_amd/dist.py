@@ -150,7 +150,19 @@ class Groups:
             g.synchronize()
 
     def sum_into(self, tensor):
-        """Every group adds up its lanes (lane order) into its rows of `tensor`; the bands of a rank are disjoint."""
+        """The rank's accumulator into `tensor` (H, W, 4): every group adds up its lanes (lane order) into its rows, and the rows no
+        group owns are set to +0.0, so that the all_reduce of the ranks' tensors adds exact zeros there.  rt_group_sum writes only
+        the group's own rows; without the zeroing, a tensor reused across reductions would add the previous reduced image in the
+        other ranks' rows.  The zeroing runs on torch's current stream and the sums on the lanes' HIP streams, which torch does not
+        wait for - so only the complement is written here (it never overlaps the sums); the caller synchronises both before the
+        all_reduce.  When the groups cover every row (the sample plan, one rank) nothing is zeroed."""
+        H = tensor.shape[0]
+        owned = sorted((g.y0, g.y1) for g in self.groups)
+        y = 0
+        for y0, y1 in owned + [(H, H)]:
+            if y0 > y:
+                tensor[y:y0].zero_()
+            y = max(y, y1)
         for g in self.groups:
             g.sum_into(tensor)
 

@@ -311,3 +311,33 @@ def post_test_accum(rows):
     return a
 
 
+# ---- the image a bench.py run reduces -----------------------------------------------------------------------------------------
+def bench_oracle_image(o, cam, shard, world, lanes, total, warmup=0, band_rows=None):
+    """The accumulator `bench.py --gpus world --shard shard --lanes lanes --total-steps total --warmup warmup` reduces, rendered by the
+    oracle `o`: every rank runs one group of `lanes` lanes per context of its plan (dist.plans); lane m renders its seed slice, first
+    its share of the warmup's frames (their accumulation is discarded by the reset, their RNG state is not) and then its share of the
+    timed frames; a group's lanes are added in lane order, the ranks' zero-padded accumulators in rank order.  Exact for the band plans
+    (a pixel has one non-zero addend) and for two ranks of the sample plan (two addends commute)."""
+    from magr_ray_tracer_amd import dist as rdist
+    from oracle.oracle_py import seed_stream
+    Wd, Hd = o.width, o.height
+    exp = np.zeros((Hd, Wd, 4), np.float32)
+    for rank in range(world):
+        mine = rdist.rank_frames(total, rank, world) if shard == "samples" else total
+        warm = rdist.lane_frames(warmup * (lanes if shard == "samples" else 1), lanes)
+        timed = rdist.lane_frames(mine, lanes)
+        part = np.zeros((Hd, Wd, 4), np.float32)
+        for k in range(len(rdist.plans(shard, Wd, Hd, rank, world, 0, lanes, band_rows))):
+            group = None
+            for m in range(lanes):
+                p = rdist.plans(shard, Wd, Hd, rank, world, m, lanes, band_rows)[k]
+                seeds = seed_stream(p["seed_first"], p["seed_count"])
+                if warm[m]:
+                    _, seeds, _, _ = o.render(cam, warm[m], seeds=seeds, y0=p["y0"], y1=p["y1"])
+                acc = np.zeros((Hd, Wd, 4), np.float32)
+                if timed[m]:
+                    o.render(cam, timed[m], accum=acc, seeds=seeds, y0=p["y0"], y1=p["y1"])
+                group = acc if group is None else group + acc
+            part = part + group
+        exp = exp + part
+    return exp

@@ -237,3 +237,46 @@ def test_bench_dump_outputs_whole_or_fixed_sample(tmp_path):
     assert np.all(np.diff(pix) > 0) and np.array_equal(acc, big.reshape(-1, 4)[pix.astype(np.int64)])
     for f in files:
         assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+
+
+class _BandStandIn:
+    """A renderer.Group as dist.Groups sees it: rows [y0, y1) and a sum_into that writes only those rows (as rt_group_sum does)."""
+
+    def __init__(self, y0, y1, value):
+        self.y0, self.y1, self.value = y0, y1, value
+
+    def sum_into(self, tensor):
+        import torch
+        rows = tensor[self.y0:self.y1]
+        rows.copy_(self.value + torch.arange(rows.numel(), dtype=rows.dtype).reshape(rows.shape))
+
+
+@pytest.mark.parametrize("layout", ["bands", "ibands", "full"])
+def test_groups_sum_into_zeroes_the_rows_the_rank_does_not_own(layout):
+    """dist.Groups.sum_into on a tensor reused across reductions (bench.py's `reduced`, which holds the previous all-reduced image):
+    the rows no group of this rank owns must come out +0.0, so that the all_reduce adds exact zeros there, and the owned rows must hold
+    what the groups summed.  Twice in a row, as the warmup's reduce and the timed region's."""
+    import torch
+    W, H, world = 13, 37, 3
+    if layout == "bands":
+        owned = [rdist.band_rows(H, 1, world)]
+    elif layout == "ibands":
+        owned = rdist.interleaved_bands(H, 1, world, 5)
+    else:
+        owned = [(0, H)]
+    t = torch.full((H, W, 4), -7.25, dtype=torch.float32)       # the previous all-reduce's image
+    for call in range(2):
+        groups = rdist.Groups([_BandStandIn(y0, y1, 1000.0 * (k + 1) + call) for k, (y0, y1) in enumerate(owned)])
+        groups.sum_into(t)
+        got = t.numpy()
+        mine = np.zeros(H, bool)
+        for k, (y0, y1) in enumerate(owned):
+            mine[y0:y1] = True
+            band = got[y0:y1]
+            exp = 1000.0 * (k + 1) + call + np.arange(band.size, dtype=np.float32).reshape(band.shape)
+            assert np.array_equal(band, exp), (layout, call, y0, y1)
+        rest = got[~mine]
+        assert layout != "full" or rest.size == 0
+        assert not np.signbit(rest).any() and (rest.view(np.uint32) == 0).all(), (layout, call, "unowned rows are not +0.0")
+        if layout != "full":
+            assert mine.any() and not mine.all()

@@ -9,7 +9,7 @@ import pytest
 from magr_ray_tracer_amd import _lib as W, scenes
 from magr_ray_tracer_amd.renderer import Device, Renderer, RtError
 from oracle.oracle_py import Oracle, seed_stream
-from helpers import DEFAULT, assert_bits, assert_concurrency, bits_equal, build, max_rel
+from helpers import DEFAULT, assert_bits, assert_concurrency, bench_oracle_image, bits_equal, build, max_rel
 
 pytestmark = pytest.mark.gpu
 
@@ -1204,7 +1204,6 @@ def test_bench_fixed_image_split_over_two_ranks_with_lanes_inside_bands(tmp_path
     import os
     import subprocess
     import sys
-    from magr_ray_tracer_amd import dist as rdist
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     Wd, Hd, total, lanes, rows = 320, 180, 5, 2, 23
     dump = tmp_path / "acc.npy"
@@ -1226,16 +1225,7 @@ def test_bench_fixed_image_split_over_two_ranks_with_lanes_inside_bands(tmp_path
     cam["focalLength"] = d.focus(Wd // 2, Hd // 2, cam)
     d.close()
     o = Oracle(sa, Wd, Hd, **DEFAULT)
-    exp = np.zeros((Hd, Wd, 4), np.float32)
-    for rank in range(2):
-        for p0 in rdist.plans("ibands", Wd, Hd, rank, 2, band_rows=rows):
-            band = None
-            for m, frames in enumerate(rdist.lane_frames(total, lanes)):      # [3, 2]
-                p = rdist.plans("ibands", Wd, Hd, rank, 2, m, lanes, band_rows=rows)[[q["y0"] for q in rdist.plans("ibands", Wd, Hd, rank, 2, band_rows=rows)].index(p0["y0"])]
-                acc = np.zeros((Hd, Wd, 4), np.float32)
-                o.render(cam, frames, accum=acc, seeds=seed_stream(p["seed_first"], p["seed_count"]), y0=p["y0"], y1=p["y1"])
-                band = acc if band is None else band + acc
-            exp = exp + band
+    exp = bench_oracle_image(o, cam, "ibands", 2, lanes, total, band_rows=rows)     # lanes' frames [3, 2]
     assert_bits(got, exp, "fixed 5-spp image, two ranks x interleaved bands x two lanes")
 
 
