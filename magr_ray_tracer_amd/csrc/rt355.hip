@@ -22,7 +22,10 @@ using namespace rt355dev;
 
 // workgroups of 256 threads the hardware admits per CU whatever the occupancy query says: any kernel / kernels with <= 96 SGPRs
 static constexpr int kAdmitAnySgpr = 6, kAdmit96Sgpr = 7;
-static constexpr int kSpillCap = 20, kFitSeven = 22;   // LDS stack entries per lane: 22 x 1 KB per workgroup is the most with which seven workgroups share a CU's 160 KB; a spilling kernel keeps 20
+// LDS words per lane of k_trace_persist_tlas: 22 x 1 KB per workgroup is the most with which seven workgroups share a CU's 160 KB; the
+// world ray (O, D, 1/D) and the TLAS level's pruning distance wait in 10 of them while a lane is inside an instance, so a spilling
+// kernel keeps 12 stack entries in LDS
+static constexpr int kFitSeven = 22, kBackupWords = 10, kSpillCap = kFitSeven - kBackupWords;
 static thread_local std::string g_err;
 static int fail(int code, const char* fmt, ...)
 {
@@ -89,25 +92,33 @@ struct RtCtx {
     RtStageTimes times{};
     int maxDepth2 = 0, tlasDepth = 0;
     int layout = 0;   // 0 = traverse the reference arrays as uploaded, 1 = derived pair/triangle-record layout
-    bool persist = false;   // persistent-wavefront traversal (layout 1, single BLAS)
-    bool persist4 = false;  // ... over the BVH4
-    bool persistTlas = false;   // ... through a multi-BLAS TLAS (BVH2, layout 1): k_trace_persist_tlas
-    bool spillStack = false;    // ... with the deep end of the traversal stacks in global memory (trees deeper than the LDS share of 7 workgroups per CU)
+    int trav = 0;           // the traversal kernels (Traversal, set by configure_traversal)
+    int coherent = 1;       // RT355_COHERENT: wave-uniform node records through the scalar cache on bounce 0 (1), every bounce of the TLAS kernel (2, lab), off (0)
     uint32_t* dSpill = nullptr; size_t spillWords = 0;
     int xcdFirst = -1;      // the XCD this context's sparse queues start on (PersistTune.xcdFirst)
-    int spillCap = kSpillCap;   // LDS entries per lane of a spilling kernel (RT355_SPILL_CAP: tests force the spill path with a tiny cap, >= 6)
+    int spillCap = kSpillCap;   // LDS stack entries per lane of a spilling kernel (RT355_SPILL_CAP: tests force the spill path with a tiny cap, >= 6)
     int nInterior = 0;          // records of the dense pair table (their ids must fit the 29-bit field of the tagged stack entries)
     bool cursorUsed[2 * (RT_MAX_BOUNCES + 2)] = {};   // work-queue heads consumed since the last k_begin_frame
     bool shadeRun[RT_MAX_BOUNCES + 1] = {};           // shade(b) launched since the last k_begin_frame
     bool generated = false;                           // generate launched since the last k_begin_frame
     int stackEntries = RT_BVH2_STACK, persistGrid = 0, persistGridConnect = 0;
-    PersistTune tune{ 112, 24, 6, 8, 0, 0 }, tuneConnect{ 128, 32, 6, 16, 0, 0 }, tune4{ 64, 20, 6, 8, 0, 0 };   // extend (BVH2), connect, extend (BVH4): measured optima (tools/tune_extend.sh, tune_connect.sh, tune_persist.sh)
+    PersistTune tune{}, tuneConnect{}, tune4{};   // extend (BVH2), connect, extend (BVH4): set by configure_traversal
     float4* dPostF = nullptr; uchar4* dPostB = nullptr;   // post-processing outputs (lazy)
     int32_t* dSteps = nullptr;   // per-ray `steps` buffer, only bound while rt_debug_enable_steps is on
     int shadeTile = kTile;  // k_shade tile = workgroup size: kTile (512), or 256 for contexts that share the GPU (RtConfig.shade_blocks_per_cu > 0)
     int shadeGrid = 1024;   // workgroups of k_shade (what the CUs hold at once; the kernel does not depend on it); set in rt_create
 };
 enum { ST_GENERATE, ST_EXTEND, ST_SHADE, ST_COMPACT, ST_CONNECT, ST_ACCUM };
+// The traversal kernels of a context (layout 1 only; the first four values are RtKernelInfo.persist):
+enum Traversal {
+    TRAV_NESTED,        // the one-ray-per-lane nested loops (k_extend / k_connect)
+    TRAV_BVH2,          // persistent wavefronts over the BVH2 of a single BLAS (k_trace_persist)
+    TRAV_TLAS,          // ... through a multi-BLAS TLAS (k_trace_persist_tlas)
+    TRAV_TLAS_SPILL,    // ... with the deep end of the traversal stacks in global memory (trees deeper than the LDS share of 7 workgroups per CU)
+    TRAV_BVH4,          // ... over the BVH4 of a single BLAS (k_trace_persist4)
+};
+static bool persistent(const RtCtx* c) { return c->trav != TRAV_NESTED; }
+static bool tlas_trav(const RtCtx* c) { return c->trav == TRAV_TLAS || c->trav == TRAV_TLAS_SPILL; }
 
 extern "C" const char* rt_last_error(void) { return g_err.c_str(); }
 extern "C" int rt_device_count(void) { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess) return 0; return n; }
@@ -117,7 +128,7 @@ extern "C" int rt_kernel_info(RtCtx* ctx, RtKernelInfo* out)
     if (!ctx || !out) return fail(RT_E_INVALID, "rt_kernel_info: null argument");
     if (!ctx->sceneLoaded) return fail(RT_E_INVALID, "rt_kernel_info: no scene uploaded");
     if (const int rc = sync_scene_config(ctx)) return rc;
-    *out = RtKernelInfo{ ctx->layout, ctx->persist ? 1 : (ctx->persistTlas ? (ctx->spillStack ? 3 : 2) : 0), ctx->persist4 ? 1 : 0, ctx->spillStack ? ctx->spillCap : ctx->stackEntries, ctx->persistGrid, ctx->persistGridConnect,
+    *out = RtKernelInfo{ ctx->layout, ctx->trav == TRAV_BVH4 ? 0 : ctx->trav, ctx->trav == TRAV_BVH4 ? 1 : 0, ctx->trav == TRAV_TLAS_SPILL ? ctx->spillCap : ctx->stackEntries, ctx->persistGrid, ctx->persistGridConnect,
                          ctx->shadeGrid, ctx->sc.nBlas };
     return RT_OK;
 }
@@ -153,12 +164,74 @@ static void scene_hold(RtCtx* ctx, const std::shared_ptr<SceneBag>& bag)
 // LDS traversal stack: one column per lane; sized at upload to what this scene's trees can need
 // (never more than the reference kernels' 32 / 64 entries).
 static size_t stack_bytes(const RtCtx* c) { return (size_t)c->stackEntries * kBlock * sizeof(uint32_t); }
-// k_trace_persist_tlas keeps its pending TLAS siblings (<= one per level) on the same column; with spillStack only the first kSpillCap
-// entries of a column live in LDS
+// k_trace_persist_tlas keeps its pending TLAS siblings (<= one per level) on the same column; with TRAV_TLAS_SPILL only the first spillCap
+// entries of a column live in LDS.  The world-ray backup sits behind them.
 static int tlas_stack_entries(const RtCtx* c) { return c->stackEntries + c->tlasDepth + 1; }
-static constexpr int kBackupWords = 10;   // the world ray (O, D, 1/D) + the TLAS level's pruning distance, kept in LDS across an instance visit (PersistTune.backup)
-static int tlas_lds_entries(const RtCtx* c) { return c->spillStack ? c->spillCap : tlas_stack_entries(c); }
-static size_t tlas_stack_bytes(const RtCtx* c) { return (size_t)(tlas_lds_entries(c) + (c->tune.backup ? kBackupWords : 0)) * kBlock * sizeof(uint32_t); }
+static int tlas_lds_entries(const RtCtx* c) { return c->trav == TRAV_TLAS_SPILL ? c->spillCap : tlas_stack_entries(c); }
+static size_t tlas_stack_bytes(const RtCtx* c) { return (size_t)(tlas_lds_entries(c) + kBackupWords) * kBlock * sizeof(uint32_t); }
+static inline dim3 grid_for(int n) { return dim3((unsigned)std::max(1, (n + kBlock - 1) / kBlock)); }
+
+// The traversal launch of a stage: the one place that maps (stage, bounce, steps wanted) to a kernel instantiation, its grid, its dynamic
+// LDS and its PersistTune.  A persistent kernel takes (scene, queues, b0, b1, renderBVH, tune); where none runs, the nested one-ray-per-lane
+// kernel takes (scene, queues, bounce, renderBVH) for extend and (scene, queues, b0, b1) for connect.  `rays`: the stage's queue capacity.
+using PersistKernel = void (*)(DevScene, DevQueues, int, int, int, PersistTune);
+using NestedKernel = void (*)(DevScene, DevQueues, int, int);
+struct TraceLaunch {
+    PersistKernel persist = nullptr;
+    NestedKernel nested = nullptr;
+    dim3 grid;
+    size_t lds = 0;
+    PersistTune tune{};
+};
+static TraceLaunch trace_launch(const RtCtx* c, int stage, int bounce, bool steps, int rays)
+{
+    TraceLaunch L;
+    L.grid = grid_for(rays);
+    L.lds = stack_bytes(c);
+    const bool connect = stage == ST_CONNECT;
+    const bool bvh4 = c->cfg.accel == RT_ACCEL_BVH4, l1 = c->layout == 1;
+    switch (c->trav) {
+    case TRAV_NESTED:
+        if (connect) L.nested = bvh4 ? (l1 ? k_connect<RT_ACCEL_BVH4, 1> : k_connect<RT_ACCEL_BVH4, 0>) : (l1 ? k_connect<RT_ACCEL_BVH2, 1> : k_connect<RT_ACCEL_BVH2, 0>);
+        else L.nested = bvh4 ? (l1 ? k_extend<RT_ACCEL_BVH4, 1> : k_extend<RT_ACCEL_BVH4, 0>) : (l1 ? k_extend<RT_ACCEL_BVH2, 1> : k_extend<RT_ACCEL_BVH2, 0>);
+        break;
+    case TRAV_BVH2:
+        L.tune = connect ? c->tuneConnect : c->tune;
+        if (connect) { L.persist = k_trace_persist<true>; L.grid = dim3(c->persistGridConnect); }
+        else if (bounce > 0 || c->cfg.extend_variant == 3) { L.persist = steps ? k_trace_persist<false, false, true> : k_trace_persist<false>; L.grid = dim3(c->persistGrid); }
+        else if (c->cfg.extend_variant == 5) L.nested = k_extend<RT_ACCEL_BVH2, 1>;
+        // bounce 0 through the same kernel with one workgroup per 256 rays: its "queue not longer than the grid" branch is the plain
+        // one-ray-per-lane loop without the TLAS code of k_extend (60 instead of 86 VGPRs: 8 instead of 5 waves per SIMD)
+        else L.persist = c->coherent ? k_trace_persist<false, true> : (steps ? k_trace_persist<false, false, true> : k_trace_persist<false>);
+        break;
+    case TRAV_BVH4:
+        L.tune = connect ? c->tuneConnect : c->tune4;
+        L.persist = connect ? k_trace_persist4<true> : k_trace_persist4<false>;
+        if (connect || bounce > 0) L.grid = dim3(connect ? c->persistGridConnect : c->persistGrid);
+        break;
+    case TRAV_TLAS:
+    case TRAV_TLAS_SPILL: {
+        const bool spill = c->trav == TRAV_TLAS_SPILL;
+        L.lds = tlas_stack_bytes(c);
+        if (connect) {
+            L.tune = c->tuneConnect;
+            L.persist = spill ? k_trace_persist_tlas<true, false, true> : k_trace_persist_tlas<true>;
+            L.grid = dim3(c->persistGridConnect);
+            break;
+        }
+        L.tune = c->tune;
+        // bounce 0 with one workgroup per 256 rays: the kernel's short-queue branch (coherent primary rays); every SPILL launch runs on
+        // the persistent grid, which bounds the global stack columns
+        if (bounce > 0 || spill) L.grid = dim3(c->persistGrid);
+        const bool coh = c->coherent && (bounce == 0 || c->coherent == 2) && (c->tune.flat || !spill);   // (through the one-ray-per-lane branch)
+        if (steps) L.persist = spill ? k_trace_persist_tlas<false, true, true> : k_trace_persist_tlas<false, true>;
+        else if (coh) L.persist = spill ? k_trace_persist_tlas<false, false, true, true> : k_trace_persist_tlas<false, false, false, true>;
+        else L.persist = spill ? k_trace_persist_tlas<false, false, true> : k_trace_persist_tlas<false>;
+        break;
+    }
+    }
+    return L;
+}
 
 // ---- profiling brackets --------------------------------------------------------------
 // Stage timing: a fixed ring of HIP event pairs on the context's stream.  Recording never forces a device sync: when the ring
@@ -504,7 +577,7 @@ extern "C" int rt_upload_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t nPr
     HIPCHK(hipStreamSynchronize(ctx->stream));
     scene_hold(ctx, std::make_shared<SceneBag>());   // (a copy shared with other contexts lives on with them)
     ctx->scene->device = ctx->cfg.device;
-    ctx->sceneLoaded = false; ctx->persist = false; ctx->persist4 = false; ctx->layout = 0;   // nothing usable until this upload has succeeded
+    ctx->sceneLoaded = false; ctx->trav = TRAV_NESTED; ctx->layout = 0;   // nothing usable until this upload has succeeded
     ctx->sc = DevScene{};
     DevScene sc{};
     int rc = upload(ctx, &sc.prims, prims, (size_t)nPrims);
@@ -664,80 +737,66 @@ extern "C" int rt_upload_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t nPr
     return RT_OK;
 }
 
-// What a context derives from its configuration once it has a scene: which traversal kernels run and how their persistent grids are sized.
+// What a context derives from its configuration once it has a scene: which traversal kernels run, with which launch parameters, and how
+// their persistent grids are sized.  Every RT355_* knob of the traversal is read here.
 static int configure_traversal(RtCtx* ctx)
 {
-    // persistent-wavefront traversal: layout 1 and a TLAS whose root is a leaf (one BLAS)
-    ctx->persist = ctx->layout == 1 && ctx->cfg.accel == RT_ACCEL_BVH2 && ctx->singleBlas && ctx->cfg.extend_variant != 2;
-    ctx->persist4 = ctx->layout == 1 && ctx->cfg.accel == RT_ACCEL_BVH4 && ctx->singleBlas && ctx->cfg.extend_variant != 2;
-    // ... and through a TLAS with several BLAS (BASELINE config 5): TLAS entries ride on the BLAS stack column, so the TLAS must be shallow
-    // (<= 8 levels: <= 256 instances in a balanced tree) and the pair-table ids must leave the three tag bits free; extend_variant 4 keeps
-    // the one-ray-per-lane nested loops (A/B runs)
-    ctx->persistTlas = ctx->layout == 1 && ctx->cfg.accel == RT_ACCEL_BVH2 && !ctx->singleBlas && ctx->cfg.extend_variant != 2 && ctx->cfg.extend_variant != 4 &&
-                       ctx->tlasDepth <= 8 && ctx->nInterior < (1 << 29);
+    // persistent wavefronts need layout 1: over the BVH2 or the BVH4 of a single BLAS (the TLAS root is a leaf), or through a TLAS with
+    // several BLAS (BASELINE config 5) - TLAS entries ride on the BLAS stack column, so the TLAS must be shallow (<= 8 levels: <= 256
+    // instances in a balanced tree) and the pair-table ids must leave the three tag bits free; extend_variant 4 keeps the one-ray-per-lane
+    // nested loops for multi-BLAS scenes (A/B runs)
+    ctx->trav = TRAV_NESTED;
+    if (ctx->layout == 1 && ctx->cfg.extend_variant != 2) {
+        if (ctx->singleBlas) ctx->trav = ctx->cfg.accel == RT_ACCEL_BVH2 ? TRAV_BVH2 : (ctx->cfg.accel == RT_ACCEL_BVH4 ? TRAV_BVH4 : TRAV_NESTED);
+        else if (ctx->cfg.accel == RT_ACCEL_BVH2 && ctx->cfg.extend_variant != 4 && ctx->tlasDepth <= 8 && ctx->nInterior < (1 << 29)) ctx->trav = TRAV_TLAS;
+    }
     // deep trees (an SBVH at alpha = 0: config 5's second BLAS has 63 levels): a full LDS column per lane would leave two workgroups per
     // CU, so the column is capped and its deep end spills to global memory (rt355_kernels.h, stk_push / stk_pop)
-    // the world ray of a lane waits in LDS while the lane is inside an instance (10 words per lane) instead of being fetched back from the
-    // queue on the way out: one global round trip less per instance visit (config 5: 1.5 visits among a ray's dozen events).  The stack
-    // column's LDS share shrinks accordingly (12 + 10 words per lane keep seven workgroups per CU).  RT355_TLAS_BACKUP=0 switches it off.
-    const bool backup = !(getenv("RT355_TLAS_BACKUP") && atoi(getenv("RT355_TLAS_BACKUP")) == 0);
-    ctx->tune.backup = ctx->tuneConnect.backup = ctx->persistTlas && backup ? 1 : 0;   // (the LDS size of the occupancy query below depends on it)
-    ctx->spillCap = backup ? kSpillCap - kBackupWords + 2 : kSpillCap;
+    ctx->spillCap = kSpillCap;
     bool forceSpill = false;
     if (const char* t = getenv("RT355_SPILL_CAP")) { const int v = atoi(t); if (v >= 6 && v <= 64) { ctx->spillCap = v; forceSpill = true; } }
     // (columns of up to 22 entries stay whole in LDS, backup beside them: 5-6 workgroups per CU without the spill branches beat 7 with them,
     // 1,923 against 1,849 and 1,327 against 1,310 M samples/s on two-BLAS scenes of 16 and 22 entries - tools/middepth_tlas.py)
-    ctx->spillStack = ctx->persistTlas && (tlas_stack_entries(ctx) > kFitSeven || forceSpill) && tlas_stack_entries(ctx) > ctx->spillCap &&
-                      !(getenv("RT355_NO_SPILL") && atoi(getenv("RT355_NO_SPILL")));
-    if (ctx->persistTlas && !ctx->spillStack && tlas_stack_entries(ctx) > RT_BVH4_STACK + 9) ctx->persistTlas = false;
-    if (ctx->persist || ctx->persist4 || ctx->persistTlas) {
-        int perCU = 0; hipDeviceProp_t prop;
-        HIPCHK(hipGetDeviceProperties(&prop, ctx->cfg.device));
-        if (ctx->persist) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, k_trace_persist<false>, kBlock, stack_bytes(ctx)));
-        else if (ctx->persistTlas && ctx->spillStack) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, (k_trace_persist_tlas<false, false, true>), kBlock, tlas_stack_bytes(ctx)));
-        else if (ctx->persistTlas) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, k_trace_persist_tlas<false>, kBlock, tlas_stack_bytes(ctx)));
-        else HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, k_trace_persist4<false>, kBlock, stack_bytes(ctx)));
-        // the closest-hit instantiations use ~90 SGPRs, the any-hit ones ~100: the hardware admits 7 resp. 6 workgroups per CU where
-        // the occupancy query may say more (see rt_create); a surplus workgroup would strand its static first chunk until another exits
-        ctx->persistGrid = std::min(ctx->gridMax, std::max(1, std::min(perCU, kAdmit96Sgpr)) * prop.multiProcessorCount);
-        ctx->persistGridConnect = std::min(ctx->gridMax, std::max(1, std::min(perCU, kAdmitAnySgpr)) * prop.multiProcessorCount);
-        if (ctx->cfg.persist_blocks_per_cu > 0) {
-            const int d = std::min(ctx->cfg.persist_blocks_per_cu, std::max(1, perCU));
-            ctx->persistGrid = std::min(ctx->persistGrid, std::min(ctx->gridMax, d * prop.multiProcessorCount));
-            ctx->persistGridConnect = std::min(ctx->persistGridConnect, std::min(ctx->gridMax, d * prop.multiProcessorCount));
-            ctx->tune.leafK = 16;   // contexts sharing the GPU: hold triangle events back until 16 lanes wait on a leaf (+1 % with three lanes, -0.6 % alone)
-        } else {
-            // a context with the GPU to itself: chunks after the first are dealt round-robin too (no atomic, no round trip per dequeue):
-            // 716 -> 725 M samples/s; with three contexts sharing the GPU the dynamic queue is 0.9 % better (profiles/r02_fixed_chunks.txt)
-            ctx->tune.fixedChunks = ctx->tuneConnect.fixedChunks = ctx->tune4.fixedChunks = 1;
-        }
-        if (const char* t = getenv("RT355_TUNE")) { // "chunk,refill,inner,leafK[,blocksPerCU]" (tuning aid)
-            int a = 0, b = 0, c = 0, l = 0, d = 0;
-            int k = sscanf(t, "%d,%d,%d,%d,%d", &a, &b, &c, &l, &d);
-            if (k >= 4 && a > 0 && b > 0 && b <= 64 && c > 0 && l > 0 && l <= 64) ctx->tune = ctx->tuneConnect = ctx->tune4 = PersistTune{ a, b, c, l, 0, 0 };
-            if (k == 5 && d > 0) ctx->persistGrid = ctx->persistGridConnect = std::min(ctx->gridMax, std::min(d, std::max(1, perCU)) * prop.multiProcessorCount);
-        }
-        if (const char* t = getenv("RT355_CONNECT_BLOCKS")) { const int d = atoi(t); if (d > 0) ctx->persistGridConnect = std::min(ctx->gridMax, std::min(d, std::max(1, perCU)) * prop.multiProcessorCount); }   // (lab)
-        if (const char* t = getenv("RT355_FIXED_CHUNKS")) { int a = 0, b = 0; if (sscanf(t, "%d,%d", &a, &b) == 2) { ctx->tune.fixedChunks = ctx->tune4.fixedChunks = a; ctx->tuneConnect.fixedChunks = b; } }   // extend, connect (tuning aid)
-        if (const char* t = getenv("RT355_TUNE_CONNECT")) { // same fields, connect launches only
-            int a = 0, b = 0, c = 0, l = 0;
-            if (sscanf(t, "%d,%d,%d,%d", &a, &b, &c, &l) == 4 && a > 0 && b > 0 && b <= 64 && c > 0 && l > 0 && l <= 64) ctx->tuneConnect = PersistTune{ a, b, c, l, 0, 0 };
-        }
+    if (ctx->trav == TRAV_TLAS && (tlas_stack_entries(ctx) > kFitSeven || forceSpill) && tlas_stack_entries(ctx) > ctx->spillCap &&
+        !(getenv("RT355_NO_SPILL") && atoi(getenv("RT355_NO_SPILL"))))
+        ctx->trav = TRAV_TLAS_SPILL;
+    if (ctx->trav == TRAV_TLAS && tlas_stack_entries(ctx) > RT_BVH4_STACK + 9) ctx->trav = TRAV_NESTED;
+    // bounce 0 (RT355_COHERENT=2: every bounce of k_trace_persist_tlas, lab; 0: off for A/B runs): wave-uniform node records come through
+    // the scalar cache (traverse_bvh2_packed_coherent, k_trace_persist_tlas<COH>)
+    ctx->coherent = getenv("RT355_COHERENT") ? atoi(getenv("RT355_COHERENT")) : 1;
+
+    // extend (BVH2), connect, extend (BVH4): measured optima (tools/tune_extend.sh, tune_connect.sh, tune_persist.sh)
+    ctx->tune = PersistTune{ 112, 24, 6, 8, 0 }; ctx->tuneConnect = PersistTune{ 128, 32, 6, 16, 0 }; ctx->tune4 = PersistTune{ 64, 20, 6, 8, 0 };
+    if (ctx->cfg.persist_blocks_per_cu > 0) {
+        ctx->tune.leafK = 16;   // contexts sharing the GPU: hold triangle events back until 16 lanes wait on a leaf (+1 % with three lanes, -0.6 % alone)
+    } else {
+        // a context with the GPU to itself: chunks after the first are dealt round-robin too (no atomic, no round trip per dequeue):
+        // 716 -> 725 M samples/s; with three contexts sharing the GPU the dynamic queue is 0.9 % better (profiles/r02_fixed_chunks.txt)
+        ctx->tune.fixedChunks = ctx->tuneConnect.fixedChunks = ctx->tune4.fixedChunks = 1;
     }
-    ctx->tune.backup = ctx->tuneConnect.backup = 0;
-    if (ctx->persistTlas) {
+    int tuneBlocks = 0;
+    if (const char* t = getenv("RT355_TUNE")) { // "chunk,refill,inner,leafK[,blocksPerCU]" (tuning aid)
+        int a = 0, b = 0, c = 0, l = 0, d = 0;
+        int k = sscanf(t, "%d,%d,%d,%d,%d", &a, &b, &c, &l, &d);
+        if (k >= 4 && a > 0 && b > 0 && b <= 64 && c > 0 && l > 0 && l <= 64) ctx->tune = ctx->tuneConnect = ctx->tune4 = PersistTune{ a, b, c, l, 0 };
+        if (k == 5 && d > 0) tuneBlocks = d;
+    }
+    if (const char* t = getenv("RT355_FIXED_CHUNKS")) { int a = 0, b = 0; if (sscanf(t, "%d,%d", &a, &b) == 2) { ctx->tune.fixedChunks = ctx->tune4.fixedChunks = a; ctx->tuneConnect.fixedChunks = b; } }   // extend, connect (tuning aid)
+    if (const char* t = getenv("RT355_TUNE_CONNECT")) { // same fields, connect launches only
+        int a = 0, b = 0, c = 0, l = 0;
+        if (sscanf(t, "%d,%d,%d,%d", &a, &b, &c, &l) == 4 && a > 0 && b > 0 && b <= 64 && c > 0 && l > 0 && l <= 64) ctx->tuneConnect = PersistTune{ a, b, c, l, 0 };
+    }
+    if (tlas_trav(ctx)) {
         // Multi-BLAS scenes so far are open scenes whose rays take a dozen events (config 5: 1 TLAS visit, 1.5 instance entries, 7.7 box
         // pairs, 1.9 triangles per ray): extend runs the kernel's one-ray-per-lane branch over every queue (measured per bounce at 4K:
         // 522 / 446 / 198 us against 654 / 562 / 194 through the event loop and 730 / 643 / 237 through the nested loops at two
         // workgroups per CU), connect - unoccluded shadow rays cross the whole scene - the event loop (646 against 690 / 1,418 us).
         // RT355_TLAS_FLAT="e,c" overrides (A/B runs).  profiles/r03_config5_per_bounce.txt
         ctx->tune.flat = 1; ctx->tuneConnect.flat = 0;
-        ctx->tune.backup = ctx->tuneConnect.backup = backup ? 1 : 0;   // (set here, after RT355_TUNE has been parsed: that assignment resets the struct)
         if (const char* t = getenv("RT355_TLAS_FLAT")) { int a = 0, b = 0; if (sscanf(t, "%d,%d", &a, &b) == 2) { ctx->tune.flat = a; ctx->tuneConnect.flat = b; } }
     }
     // sparse queues (the one-ray-per-lane branches) stay on as few XCDs as hold them at 1,024 rays each, so that their rays share an L2
-    // (EXPERIMENTS.md (54): 16,384 before the thinning below made spreading the better default); contexts start on different XCDs.
-    // (set here, after RT355_TUNE has been parsed: that assignment resets the struct)
+    // (EXPERIMENTS.md (54): 16,384 before the thinning below made spreading the better default); contexts start on different XCDs
     {
         static std::atomic<int> serial{ 0 };
         if (ctx->xcdFirst < 0) ctx->xcdFirst = serial.fetch_add(1) & 7;
@@ -745,14 +804,33 @@ static int configure_traversal(RtCtx* ctx)
         if (const char* t = getenv("RT355_XCD_RAYS")) rays = std::max(0, atoi(t));
         ctx->tune.xcdRays = ctx->tuneConnect.xcdRays = ctx->tune4.xcdRays = rays;
         ctx->tune.xcdFirst = ctx->tuneConnect.xcdFirst = ctx->tune4.xcdFirst = ctx->xcdFirst;
-        // ... and on few lanes of every participating wave when they hold at most 16 rays per wave (sparse_slot; RT355_THIN=0: off)
+        // ... and on few lanes of every participating wave when they hold at most 16 rays per wave (sparse_map; RT355_THIN=0: off)
         int thin = 16;
         if (const char* t = getenv("RT355_THIN")) thin = std::min(64, std::max(0, atoi(t)));
         ctx->tune.thin = ctx->tuneConnect.thin = ctx->tune4.thin = thin;
     }
+
+    if (persistent(ctx)) {
+        int perCU = 0; hipDeviceProp_t prop;
+        HIPCHK(hipGetDeviceProperties(&prop, ctx->cfg.device));
+        const TraceLaunch L = trace_launch(ctx, ST_EXTEND, 1, false, ctx->nPix);   // what extend runs on the persistent grid
+        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, L.persist, kBlock, L.lds));
+        // the closest-hit instantiations use ~90 SGPRs, the any-hit ones ~100: the hardware admits 7 resp. 6 workgroups per CU where
+        // the occupancy query may say more (see rt_create); a surplus workgroup would strand its static first chunk until another exits
+        const int mp = prop.multiProcessorCount;
+        ctx->persistGrid = std::min(ctx->gridMax, std::max(1, std::min(perCU, kAdmit96Sgpr)) * mp);
+        ctx->persistGridConnect = std::min(ctx->gridMax, std::max(1, std::min(perCU, kAdmitAnySgpr)) * mp);
+        if (ctx->cfg.persist_blocks_per_cu > 0) {
+            const int d = std::min(ctx->cfg.persist_blocks_per_cu, std::max(1, perCU));
+            ctx->persistGrid = std::min(ctx->persistGrid, std::min(ctx->gridMax, d * mp));
+            ctx->persistGridConnect = std::min(ctx->persistGridConnect, std::min(ctx->gridMax, d * mp));
+        }
+        if (tuneBlocks > 0) ctx->persistGrid = ctx->persistGridConnect = std::min(ctx->gridMax, std::min(tuneBlocks, std::max(1, perCU)) * mp);
+        if (const char* t = getenv("RT355_CONNECT_BLOCKS")) { const int d = atoi(t); if (d > 0) ctx->persistGridConnect = std::min(ctx->gridMax, std::min(d, std::max(1, perCU)) * mp); }   // (lab)
+    }
     ctx->q.spill = nullptr; ctx->q.spillStride = 0; ctx->q.stackCap = 0;
-    ctx->q.tlasLdsEntries = ctx->persistTlas ? (uint32_t)tlas_lds_entries(ctx) : 0u;
-    if (ctx->spillStack) {   // every SPILL launch runs on a persistent grid (bounce 0 too), so the global columns are bounded by the grids
+    ctx->q.tlasLdsEntries = tlas_trav(ctx) ? (uint32_t)tlas_lds_entries(ctx) : 0u;
+    if (ctx->trav == TRAV_TLAS_SPILL) {   // every SPILL launch runs on a persistent grid (bounce 0 too), so the global columns are bounded by the grids
         const size_t stride = (size_t)std::max(ctx->persistGrid, ctx->persistGridConnect) * kBlock;
         const size_t words = stride * (size_t)(tlas_stack_entries(ctx) - ctx->spillCap);
         if (words > ctx->spillWords) {
@@ -799,7 +877,7 @@ hipError_t launch_records(hipStream_t s, const RtPrimitive* prims, const RtBVHNo
                           uint32_t nPairs, RtFloat4* pairs, RtFloat4* triRecs, RtFloat4* shadeRecs, RtFloat4* lightRecs);
 }
 
-// A holder of a scene copy that an update has changed re-derives its traversal configuration (the TLAS depth decides persistTlas,
+// A holder of a scene copy that an update has changed re-derives its traversal configuration (the TLAS depth decides the traversal kernels,
 // the spill choice, the TLAS stack bytes and the spill buffer) before its next launch.
 static int sync_scene_config(RtCtx* ctx)
 {
@@ -1007,7 +1085,6 @@ static int need_scene(RtCtx* ctx, const char* who)
     if (!ctx->sceneLoaded) return fail(RT_E_INVALID, "%s: no scene uploaded", who);
     return sync_scene_config(ctx);
 }
-static inline dim3 grid_for(int n) { return dim3((unsigned)std::max(1, (n + kBlock - 1) / kBlock)); }
 
 static void frame_state_reset(RtCtx* ctx)
 {
@@ -1044,49 +1121,14 @@ extern "C" int rt_stage_extend(RtCtx* ctx, int32_t bounce, int32_t renderBVH)
     int rc = need_scene(ctx, "rt_stage_extend"); if (rc) return rc;
     ctx->queued = true;
     if (bounce < 0 || bounce > ctx->cfg.max_bounces) return fail(RT_E_INVALID, "rt_stage_extend: bounce %d outside [0, %d]", bounce, ctx->cfg.max_bounces);
-    if (ctx->persist || ctx->persist4 || ctx->persistTlas) { // a queue head is good for one launch per frame; re-arm it if this stage is run again
+    if (persistent(ctx)) { // a queue head is good for one launch per frame; re-arm it if this stage is run again
         if (ctx->cursorUsed[bounce]) HIPCHK(hipMemsetAsync(ctx->q.cursor + bounce, 0, sizeof(int32_t), ctx->stream));
         ctx->cursorUsed[bounce] = true;
     }
     const bool wantSteps = renderBVH != 0 || ctx->q.steps != nullptr;   // only then does the event loop keep the per-ray `steps`
-    // bounce 0: primary rays are coherent and finish together, refilling buys nothing -> one ray per lane
-    if (ctx->persistTlas) {
-        // bounce 0 with one workgroup per 256 rays: the kernel's short-queue branch = the nested one-ray-per-lane loops (coherent primary rays)
-        const dim3 g = bounce > 0 || ctx->spillStack ? dim3(ctx->persistGrid) : grid_for(ctx->nPix);
-        // bounce 0 through the one-ray-per-lane branch: wave-uniform node records through the scalar cache (RT355_COHERENT=0: A/B runs)
-        static const int cohOn = getenv("RT355_COHERENT") ? atoi(getenv("RT355_COHERENT")) : 1;   // (2: every bounce - lab)
-        const bool coh = cohOn && (bounce == 0 || cohOn == 2) && (ctx->tune.flat || !ctx->spillStack);
-        if (ctx->spillStack) {
-            if (wantSteps) LAUNCH(ctx, ST_EXTEND, (k_trace_persist_tlas<false, true, true>), g, tlas_stack_bytes(ctx), ctx->sc, ctx->q, bounce, bounce, renderBVH, ctx->tune);
-            else if (coh) LAUNCH(ctx, ST_EXTEND, (k_trace_persist_tlas<false, false, true, true>), g, tlas_stack_bytes(ctx), ctx->sc, ctx->q, bounce, bounce, renderBVH, ctx->tune);
-            else LAUNCH(ctx, ST_EXTEND, (k_trace_persist_tlas<false, false, true>), g, tlas_stack_bytes(ctx), ctx->sc, ctx->q, bounce, bounce, renderBVH, ctx->tune);
-        }
-        else if (wantSteps) LAUNCH(ctx, ST_EXTEND, (k_trace_persist_tlas<false, true>), g, tlas_stack_bytes(ctx), ctx->sc, ctx->q, bounce, bounce, renderBVH, ctx->tune);
-        else if (coh) LAUNCH(ctx, ST_EXTEND, (k_trace_persist_tlas<false, false, false, true>), g, tlas_stack_bytes(ctx), ctx->sc, ctx->q, bounce, bounce, renderBVH, ctx->tune);
-        else LAUNCH(ctx, ST_EXTEND, (k_trace_persist_tlas<false>), g, tlas_stack_bytes(ctx), ctx->sc, ctx->q, bounce, bounce, renderBVH, ctx->tune);
-    } else if (ctx->persist4)
-        LAUNCH(ctx, ST_EXTEND, (k_trace_persist4<false>), bounce > 0 ? dim3(ctx->persistGrid) : grid_for(ctx->nPix), stack_bytes(ctx), ctx->sc, ctx->q, bounce, bounce, renderBVH, ctx->tune4);
-    else if (ctx->persist && (bounce > 0 || ctx->cfg.extend_variant == 3)) {
-        if (wantSteps) LAUNCH(ctx, ST_EXTEND, (k_trace_persist<false, false, true>), dim3(ctx->persistGrid), stack_bytes(ctx), ctx->sc, ctx->q, bounce, bounce, renderBVH, ctx->tune);
-        else LAUNCH(ctx, ST_EXTEND, (k_trace_persist<false>), dim3(ctx->persistGrid), stack_bytes(ctx), ctx->sc, ctx->q, bounce, bounce, renderBVH, ctx->tune);
-    } else if (ctx->persist && ctx->cfg.extend_variant != 5)
-        // bounce 0 through the same kernel with one workgroup per 256 rays: its "queue not longer than the grid" branch is the plain
-        // one-ray-per-lane loop without the TLAS code of k_extend (60 instead of 86 VGPRs: 8 instead of 5 waves per SIMD)
-    {
-        // bounce 0: wave-uniform node records come through the scalar cache (traverse_bvh2_packed_coherent; RT355_COHERENT=0 switches it off for A/B runs)
-        static const bool coherent = !(getenv("RT355_COHERENT") && atoi(getenv("RT355_COHERENT")) == 0);
-        if (coherent && bounce == 0) LAUNCH(ctx, ST_EXTEND, (k_trace_persist<false, true>), grid_for(ctx->nPix), stack_bytes(ctx), ctx->sc, ctx->q, bounce, bounce, renderBVH, ctx->tune);
-        else if (wantSteps) LAUNCH(ctx, ST_EXTEND, (k_trace_persist<false, false, true>), grid_for(ctx->nPix), stack_bytes(ctx), ctx->sc, ctx->q, bounce, bounce, renderBVH, ctx->tune);
-        else LAUNCH(ctx, ST_EXTEND, (k_trace_persist<false>), grid_for(ctx->nPix), stack_bytes(ctx), ctx->sc, ctx->q, bounce, bounce, renderBVH, ctx->tune);
-    }
-    else if (ctx->cfg.accel == RT_ACCEL_BVH4 && ctx->layout == 1)
-        LAUNCH(ctx, ST_EXTEND, (k_extend<RT_ACCEL_BVH4, 1>), grid_for(ctx->nPix), stack_bytes(ctx), ctx->sc, ctx->q, bounce, renderBVH);
-    else if (ctx->cfg.accel == RT_ACCEL_BVH4)
-        LAUNCH(ctx, ST_EXTEND, (k_extend<RT_ACCEL_BVH4, 0>), grid_for(ctx->nPix), stack_bytes(ctx), ctx->sc, ctx->q, bounce, renderBVH);
-    else if (ctx->layout == 1)
-        LAUNCH(ctx, ST_EXTEND, (k_extend<RT_ACCEL_BVH2, 1>), grid_for(ctx->nPix), stack_bytes(ctx), ctx->sc, ctx->q, bounce, renderBVH);
-    else
-        LAUNCH(ctx, ST_EXTEND, (k_extend<RT_ACCEL_BVH2, 0>), grid_for(ctx->nPix), stack_bytes(ctx), ctx->sc, ctx->q, bounce, renderBVH);
+    const TraceLaunch L = trace_launch(ctx, ST_EXTEND, bounce, wantSteps, ctx->nPix);
+    if (L.persist) LAUNCH(ctx, ST_EXTEND, L.persist, L.grid, L.lds, ctx->sc, ctx->q, bounce, bounce, renderBVH, L.tune);
+    else LAUNCH(ctx, ST_EXTEND, L.nested, L.grid, L.lds, ctx->sc, ctx->q, bounce, renderBVH);
     HIPCHK(hipGetLastError());
     return RT_OK;
 }
@@ -1123,28 +1165,14 @@ extern "C" int rt_stage_connect(RtCtx* ctx, int32_t b0, int32_t b1)
     int rc = need_scene(ctx, "rt_stage_connect"); if (rc) return rc;
     ctx->queued = true;
     if (b0 < 0 || b1 < b0 || b1 >= ctx->cfg.max_bounces) return fail(RT_E_INVALID, "rt_stage_connect: bounce range [%d,%d] outside [0, %d)", b0, b1, ctx->cfg.max_bounces);
-    const int cap = ctx->nPix * (b1 - b0 + 1);
-    if (ctx->persist || ctx->persist4 || ctx->persistTlas) {
+    if (persistent(ctx)) {
         const int ci = (RT_MAX_BOUNCES + 2) + b0;
         if (ctx->cursorUsed[ci]) HIPCHK(hipMemsetAsync(ctx->q.cursor + ci, 0, sizeof(int32_t), ctx->stream));
         ctx->cursorUsed[ci] = true;
     }
-    if (ctx->persistTlas && ctx->spillStack)
-        LAUNCH(ctx, ST_CONNECT, (k_trace_persist_tlas<true, false, true>), dim3(ctx->persistGridConnect), tlas_stack_bytes(ctx), ctx->sc, ctx->q, b0, b1, 0, ctx->tuneConnect);
-    else if (ctx->persistTlas)
-        LAUNCH(ctx, ST_CONNECT, (k_trace_persist_tlas<true>), dim3(ctx->persistGridConnect), tlas_stack_bytes(ctx), ctx->sc, ctx->q, b0, b1, 0, ctx->tuneConnect);
-    else if (ctx->persist4)
-        LAUNCH(ctx, ST_CONNECT, (k_trace_persist4<true>), dim3(ctx->persistGridConnect), stack_bytes(ctx), ctx->sc, ctx->q, b0, b1, 0, ctx->tuneConnect);
-    else if (ctx->persist)
-        LAUNCH(ctx, ST_CONNECT, (k_trace_persist<true>), dim3(ctx->persistGridConnect), stack_bytes(ctx), ctx->sc, ctx->q, b0, b1, 0, ctx->tuneConnect);
-    else if (ctx->cfg.accel == RT_ACCEL_BVH4 && ctx->layout == 1)
-        LAUNCH(ctx, ST_CONNECT, (k_connect<RT_ACCEL_BVH4, 1>), grid_for(cap), stack_bytes(ctx), ctx->sc, ctx->q, b0, b1);
-    else if (ctx->cfg.accel == RT_ACCEL_BVH4)
-        LAUNCH(ctx, ST_CONNECT, (k_connect<RT_ACCEL_BVH4, 0>), grid_for(cap), stack_bytes(ctx), ctx->sc, ctx->q, b0, b1);
-    else if (ctx->layout == 1)
-        LAUNCH(ctx, ST_CONNECT, (k_connect<RT_ACCEL_BVH2, 1>), grid_for(cap), stack_bytes(ctx), ctx->sc, ctx->q, b0, b1);
-    else
-        LAUNCH(ctx, ST_CONNECT, (k_connect<RT_ACCEL_BVH2, 0>), grid_for(cap), stack_bytes(ctx), ctx->sc, ctx->q, b0, b1);
+    const TraceLaunch L = trace_launch(ctx, ST_CONNECT, b0, false, ctx->nPix * (b1 - b0 + 1));
+    if (L.persist) LAUNCH(ctx, ST_CONNECT, L.persist, L.grid, L.lds, ctx->sc, ctx->q, b0, b1, 0, L.tune);
+    else LAUNCH(ctx, ST_CONNECT, L.nested, L.grid, L.lds, ctx->sc, ctx->q, b0, b1);
     ev_begin(ctx, ST_ACCUM);
     for (int b = b0; b <= b1; b++)
         hipLaunchKernelGGL(k_accumulate, dim3(std::min(grid_for(ctx->nPix).x, 2048u)), dim3(kBlock), 0, ctx->stream, ctx->q, b);

@@ -83,7 +83,7 @@ struct DevQueues {
     unsigned long long* ctrConnect; // [gridMax][kCtrCols]
     uint32_t* spill;   // [spillEntries][spillStride] deep ends of the traversal stacks (SPILL instantiations), may be null
     uint32_t spillStride, stackCap;   // lanes of the largest SPILL launch; LDS entries per lane of those launches
-    uint32_t tlasLdsEntries;          // LDS stack entries per lane of k_trace_persist_tlas (the world-ray backup, if any, sits behind them)
+    uint32_t tlasLdsEntries;          // LDS stack entries per lane of k_trace_persist_tlas (the world-ray backup sits behind them)
     int32_t nPix, firstPixel, width, height;
 };
 // k_shade hands its tiles out by ticket.  ONE counter: any running workgroup draws the smallest tile not drawn yet, so the ordered scan
@@ -841,7 +841,13 @@ __global__ __launch_bounds__(kBlock) void k_extend(DevScene sc, DevQueues q, int
 static constexpr int kTpWaves = 8192;
 __device__ unsigned long long g_tp[9][kTpWaves][4];
 #endif
-struct PersistTune { int chunk, refill, inner, leafK, fixedChunks, flat = 0, backup = 0, xcdRays = 0, xcdFirst = 0, thin = 0; };   // thin: a queue of at most `thin` rays per participating wave is spread evenly over the waves (few lanes of each) instead of filling the first waves   // xcdRays: a sparse queue's rays are kept on as few XCDs as hold them at this many rays each (one-ray-per-lane branches; 0 = spread over all eight)   // backup: k_trace_persist_tlas keeps the world ray in LDS across an instance visit (10 words per lane behind the stack column) instead of fetching it back from the queue   // flat: k_trace_persist_tlas runs every queue through its one-ray-per-lane branch, 64 rays per wave and round (short traversals: config 5's open scene)   // rays per dequeue, idle lanes that trigger a top-up, events between checks, lanes on a leaf that trigger the triangle path, chunks dealt round-robin instead of dequeued
+struct PersistTune {
+    int chunk, refill, inner, leafK;   // rays per dequeue, idle lanes that trigger a top-up, events between checks, lanes on a leaf that trigger the triangle path
+    int fixedChunks;                   // chunks dealt round-robin instead of dequeued
+    int flat = 0;                      // k_trace_persist_tlas runs every queue through its one-ray-per-lane branch, 64 rays per wave and round (short traversals: config 5's open scene)
+    int xcdRays = 0, xcdFirst = 0;     // a sparse queue's rays are kept on as few XCDs as hold them at this many rays each (one-ray-per-lane branches; 0 = spread over all eight)
+    int thin = 0;                      // a queue of at most `thin` rays per participating wave is spread evenly over the waves (few lanes of each) instead of filling the first waves
+};
 
 // A sparse queue on few XCDs: workgroup ids go to the eight XCDs round-robin and every XCD has its own L2, so the few thousand rays of a late
 // bounce spread over all of them fetch every node record from the Infinity Cache once PER XCD.  With `xcdRays` > 0 only the workgroups of
@@ -862,57 +868,160 @@ RT_FORCEINLINE int xcd_pack(int n, int xcdRays, int xcdFirst, int& waves)
     return ((int)(blockIdx.x >> 3) * nx + xcd) * wpb + wave;
 }
 
-// The queue slot of this lane in a launch that is not shorter than its queue (the one-ray-per-lane loops), or n for a lane without one.
-// Sparse queues are (1) kept on few XCDs (xcd_pack) and (2) THINNED: in the one-ray-per-lane loop a wave pays for the union of its lanes'
-// states every iteration - a node fetch AND a leaf's triangle fetches, one after the other - so a ray advances at the pace of its 63
-// wave-mates; a queue of at most `thin` rays per participating wave therefore takes a few lanes of EVERY wave instead of all lanes of the
-// first ones (config 2's late launches 93 / 88 / 72 / 65 / 48 -> 83 / 60 / 38 / 33 / 29 us, EXPERIMENTS.md (55)).
-RT_FORCEINLINE int sparse_slot(int n, const PersistTune& t, int waveId, int lane)
+// How the one-ray-per-lane loops map a queue to waves: the wave's first item (< 0: it sits the launch out), the stride between its items,
+// and the rays per item (lanes 0..per-1 take rays item * per + lane).  Sparse queues are (1) kept on few XCDs (xcd_pack) and (2) THINNED:
+// in the one-ray-per-lane loop a wave pays for the union of its lanes' states every iteration - a node fetch AND a leaf's triangle fetches,
+// one after the other - so a ray advances at the pace of its 63 wave-mates; a queue of at most `thin` rays per participating wave therefore
+// takes a few lanes of EVERY wave instead of all lanes of the first ones (config 2's late launches 93 / 88 / 72 / 65 / 48 -> 83 / 60 / 38 /
+// 33 / 29 us, EXPERIMENTS.md (55)).
+struct SparseMap { int first, stride, per; };
+RT_FORCEINLINE SparseMap sparse_map(int n, const PersistTune& t, int waveId)
 {
-    if (t.xcdRays <= 0 && t.thin <= 0) return waveId * 64 + lane;
-    int waves;
-    const int w = xcd_pack(n, t.xcdRays, t.xcdFirst, waves);
-    if (w < 0) return n;
-    const int per = (n + waves - 1) / waves;      // (<= 64: the queue is not longer than the launch)
-    if (t.thin > 0 && per <= t.thin) return lane < per ? w * per + lane : n;
-    return w * 64 + lane;
+    SparseMap m = { waveId, (int)gridDim.x * (kBlock / 64), 64 };
+    if (t.xcdRays <= 0 && t.thin <= 0) return m;
+    m.first = xcd_pack(n, t.xcdRays, t.xcdFirst, m.stride);
+    if (t.thin > 0 && (long long)m.stride * t.thin >= (long long)n) m.per = max(1, (n + m.stride - 1) / m.stride);
+    return m;
 }
+
+// Primary rays: a wave takes an 8x8 pixel tile instead of a 64x1 strip - only when the queue of bounce 0 IS the pixel grid and its sides are
+// multiples of 8 (an injected shorter queue keeps the strip mapping).  Any slot -> lane map is legal: every slot is traced on its own.
+template <bool OCC> RT_FORCEINLINE bool primary_tiles(const DevQueues& q, int b0, int n)
+{
+    return !OCC && b0 == 0 && n == q.nPix && ((q.width | (q.nPix / q.width)) & 7) == 0;
+}
+RT_FORCEINLINE int tile_slot(const DevQueues& q, int tile, int lane)
+{
+    const int tilesX = q.width >> 3, ty = tile / tilesX, tx = tile - ty * tilesX;
+    return ((ty << 3) + (lane >> 3)) * q.width + (tx << 3) + (lane & 7);
+}
+
+// The queue slot of this lane in a launch that is not shorter than its queue (one ray per lane), or >= n for a lane without one.
+template <bool OCC> RT_FORCEINLINE int short_queue_slot(const DevQueues& q, int b0, int n, const PersistTune& t, int waveId, int lane)
+{
+    if (primary_tiles<OCC>(q, b0, n) && (long long)gridDim.x * kBlock >= (long long)q.nPix) return tile_slot(q, waveId, lane);   // a wave for every tile
+    if (b0 == 0 && n == q.nPix) return waveId * 64 + lane;
+    const SparseMap m = sparse_map(n, t, waveId);
+    return m.first < 0 || lane >= m.per ? n : m.first * m.per + lane;
+}
+
+// The queue of a persistent launch and its dequeue head: extend -> rays [0, nRays[b0]); connect -> shadow rays [nShadow[b0], nShadow[b1+1])
+struct QueueWindow { int first, n; int32_t* cursor; };
+template <bool OCC> RT_FORCEINLINE QueueWindow queue_window(const DevQueues& q, int b0, int b1)
+{
+    const int first = OCC ? q.nShadow[b0] : 0;
+    return { first, OCC ? q.nShadow[b1 + 1] - first : q.nRays[b0], q.cursor + (OCC ? (RT_MAX_BOUNCES + 2) + b0 : b0) };
+}
+
+// The instance of a one-BLAS scene: rows 0..2 of its invT (translation in .w) and its encoded BLAS root
+struct OneInstance { float4 t0, t1, t2; uint32_t root; };
+RT_FORCEINLINE OneInstance one_instance(const DevScene& sc)
+{
+    const uint32_t b = sc.tlas[0].BLASidx;
+    const float* T = sc.blas[b].invT;
+    return { mk4(T[0], T[1], T[2], T[3]), mk4(T[4], T[5], T[6], T[7]), mk4(T[8], T[9], T[10], T[11]), sc.rootEntry[b] };
+}
+
+// transformRay (tlas.cl:3-8): the ray O, D into the space of the instance with inverse-transform rows t0..t2, rD = 1 / D - the
+// arithmetic of traverse_instance
+RT_FORCEINLINE void transform_ray(TRay& r, float4 O, float4 D, float4 t0, float4 t1, float4 t2)
+{
+    const float4 Dv = mk4(D.x, D.y, D.z, 0.0f), Ov = mk4(O.x, O.y, O.z, 0.0f);
+    r.dx = dot3(mk4(t0.x, t0.y, t0.z, 0), Dv); r.dy = dot3(mk4(t1.x, t1.y, t1.z, 0), Dv); r.dz = dot3(mk4(t2.x, t2.y, t2.z, 0), Dv);
+    r.ox = dot3(mk4(t0.x, t0.y, t0.z, 0), Ov) + t0.w; r.oy = dot3(mk4(t1.x, t1.y, t1.z, 0), Ov) + t1.w;
+    r.oz = dot3(mk4(t2.x, t2.y, t2.z, 0), Ov) + t2.w;
+    r.rx = 1.0f / r.dx; r.ry = 1.0f / r.dy; r.rz = 1.0f / r.dz;
+}
+
+// Queue slot `idx` as a new ray with r.t = its tmax (extend: kFar; connect: t_light): the world ray as k_extend / k_connect build it
+// (rD = 1 / D, three IEEE divides) or, given `inst`, that ray in the instance's object space
+template <bool OCC> RT_FORCEINLINE void queue_ray(TRay& r, const DevQueues& q, int b0, int qFirst, int idx, const OneInstance* inst = nullptr)
+{
+    float4 O, D; float tmax;
+    if (OCC) { const float4 a = q.sA[qFirst + idx], b = q.sB[qFirst + idx]; O = a; D = b; tmax = a.w; }
+    else { O = q.O[b0 & 1][idx]; D = q.D[b0 & 1][idx]; tmax = kFar; }
+    if (inst) transform_ray(r, O, D, inst->t0, inst->t1, inst->t2);
+    else {
+        r.ox = O.x; r.oy = O.y; r.oz = O.z; r.dx = D.x; r.dy = D.y; r.dz = D.z;
+        r.rx = 1.0f / D.x; r.ry = 1.0f / D.y; r.rz = 1.0f / D.z;
+    }
+    r.t = tmax; r.prim = -1; r.u = 0.0f; r.v = 0.0f;
+}
+
+// What a traced queue slot leaves behind: extend -> the hit record and, where kept, `steps` and the heat map (wavefront.cl:66-67);
+// connect -> an occluded shadow ray loses its contribution
+template <bool OCC, bool STEPS>
+RT_FORCEINLINE void store_result(const DevQueues& q, int qFirst, int idx, const TRay& r, int steps, bool occluded, int renderBVH)
+{
+    if (OCC) { if (occluded) q.sC[qFirst + idx] = splat(0.0f); }
+    else {
+        q.hit[idx] = mk4(r.t, __int_as_float(r.prim), r.u, r.v);
+        if (STEPS) {
+            if (q.steps) q.steps[idx] = steps;
+            if (renderBVH) q.accum[q.firstPixel + idx] = splat((float)(uint32_t)steps / 255.f);
+        }
+    }
+}
+
+// Work distribution of the event loops (every member wave-uniform).  The first chunk of a wave is static (chunk id = global wave id, no
+// atomic, so the launch does not start with thousands of waves hammering one counter); further chunks are dealt round-robin
+// (tune.fixedChunks: no atomic, no round trip - a context with the GPU to itself) or dequeued with one atomic per wave (balances waves that
+// other contexts' kernels slow down).  Whenever at least tune.refill lanes are idle, they are topped up by ballot + prefix count.
+struct ChunkDealer {
+    int next, end, round = 0;
+    bool exhausted = false;
+#ifdef RT355_TAIL_PROBE
+    unsigned long long tpDry = 0;   // when the wave found the queue dry (0: never)
+#endif
+    RT_FORCEINLINE ChunkDealer(int waveId, int chunk, int n) : next(min(waveId * chunk, n)), end(min(waveId * chunk + chunk, n)) {}
+    // One top-up: false once the queue is dry and every lane idle (the wave exits).  Else `idx` is the queue slot this lane takes up (-1:
+    // none), and `dealt` has grown by the rays handed out.
+    RT_FORCEINLINE bool refill(bool idle, int& idx, uint32_t& dealt, const QueueWindow& w, const PersistTune& t, int nWaves, int waveId, int lane)
+    {
+        idx = -1;
+        const unsigned long long idleMask = __ballot(idle);
+        const int nIdle = __popcll(idleMask);
+        if (nIdle == 64 && exhausted && next >= end) return false;
+        if (nIdle < t.refill || (exhausted && next >= end)) return true;
+        if (next >= end) {
+            int c = 0;
+            if (t.fixedChunks) { round++; c = round * nWaves * t.chunk + waveId * t.chunk; }
+            else {
+                if (lane == 0) c = atomicAdd(w.cursor, t.chunk);
+                c = __shfl(c, 0, 64) + nWaves * t.chunk;
+            }
+            next = c; end = min(c + t.chunk, w.n);
+            if (c >= w.n) { exhausted = true; next = end = 0; }
+#ifdef RT355_TAIL_PROBE
+            if (exhausted) tpDry = wall_clock64();
+#endif
+        }
+        if (next < end) {
+            const int i = next + __popcll(idleMask & ((1ull << lane) - 1ull));
+            if (idle && i < end) idx = i;
+            dealt += (uint32_t)min(nIdle, end - next);
+            next = min(next + nIdle, end);
+        }
+        return true;
+    }
+};
 
 // Short queue (late bounces, and bounce 0 when it is launched with one workgroup per 256 rays): every wave gets at most one 64-ray chunk
 // and nothing is left to refill from, so run the plain one-ray-per-lane loop, which has less per-step overhead than the refill machine.
-template <bool OCC, bool COH>
-RT_FORCEINLINE void trace_short_queue(const DevScene& sc, const DevQueues& q, int b0, int qFirst, int n, int renderBVH, const float* T,
-                                      uint32_t rootEntry, uint32_t* stk, int waveId, int lane, const PersistTune& tune)
+template <bool OCC, bool COH, bool BVH4 = false>
+RT_FORCEINLINE void trace_short_queue(const DevScene& sc, const DevQueues& q, int b0, const QueueWindow& w, int renderBVH, const OneInstance& one,
+                                      uint32_t* stk, int waveId, int lane, const PersistTune& tune)
 {
     WorkCtr wc = { 0, 0, 0, 0 };
     uint32_t rays = 0;
-    TRay r; r.t = 0; r.prim = -1; r.u = r.v = 0; r.ox = r.oy = r.oz = r.dx = r.dy = r.dz = r.rx = r.ry = r.rz = 0;
-    int idx = waveId * 64 + lane;
-    if (!(b0 == 0 && n == q.nPix)) idx = sparse_slot(n, tune, waveId, lane);
-    if (!OCC && b0 == 0 && ((q.width | (q.nPix / q.width)) & 7) == 0 && n == q.nPix && (long long)gridDim.x * kBlock >= (long long)q.nPix) {
-        // primary rays: a wave takes an 8x8 pixel tile instead of a 64x1 strip (the queue of bounce 0 is the pixel grid - only when it IS
-        // the whole grid and the launch has a wave for every tile; an injected shorter queue or a smaller grid keeps the strip mapping)
-        const int tilesX = q.width >> 3, ty = waveId / tilesX, tx = waveId - ty * tilesX;
-        idx = ((ty << 3) + (lane >> 3)) * q.width + (tx << 3) + (lane & 7);
-    }
-    if (idx < n) {
-        float4 O, D; float tmax;
-        if (OCC) { const float4 a = q.sA[qFirst + idx], b = q.sB[qFirst + idx]; O = a; D = b; tmax = a.w; }
-        else { O = q.O[b0 & 1][idx]; D = q.D[b0 & 1][idx]; tmax = kFar; }
-        const float4 Dv = mk4(D.x, D.y, D.z, 0.0f), Ov = mk4(O.x, O.y, O.z, 0.0f);
-        r.dx = dot3(mk4(T[0], T[1], T[2], 0), Dv); r.dy = dot3(mk4(T[4], T[5], T[6], 0), Dv); r.dz = dot3(mk4(T[8], T[9], T[10], 0), Dv);
-        r.ox = dot3(mk4(T[0], T[1], T[2], 0), Ov) + T[3]; r.oy = dot3(mk4(T[4], T[5], T[6], 0), Ov) + T[7];
-        r.oz = dot3(mk4(T[8], T[9], T[10], 0), Ov) + T[11];
-        r.rx = 1.0f / r.dx; r.ry = 1.0f / r.dy; r.rz = 1.0f / r.dz;
-        r.t = tmax; r.prim = -1; r.u = 0.0f; r.v = 0.0f;
+    const int idx = short_queue_slot<OCC>(q, b0, w.n, tune, waveId, lane);
+    if (idx < w.n) {
+        TRay r;
+        queue_ray<OCC>(r, q, b0, w.first, idx, &one);
         rays = 1; wc.inst = 1;
-        const int st = COH ? traverse_bvh2_packed_coherent(sc, r, rootEntry, stk, wc) : traverse_bvh2_packed<OCC>(sc, r, rootEntry, stk, wc);
-        if (OCC) { if (st == -1) q.sC[qFirst + idx] = splat(0.0f); }
-        else {
-            q.hit[idx] = mk4(r.t, __int_as_float(r.prim), r.u, r.v);
-            if (q.steps) q.steps[idx] = st;
-            if (renderBVH) q.accum[q.firstPixel + idx] = splat((float)(uint32_t)st / 255.f);
-        }
+        const int st = BVH4 ? traverse_bvh4_packed<OCC>(sc, r, one.root, stk, wc)
+                     : COH ? traverse_bvh2_packed_coherent(sc, r, one.root, stk, wc) : traverse_bvh2_packed<OCC>(sc, r, one.root, stk, wc);
+        store_result<OCC, true>(q, w.first, idx, r, st, st == -1, renderBVH);
     }
     flush_counters(OCC ? q.ctrConnect : q.ctrExtend, rays, wc, stk);
 }
@@ -924,18 +1033,11 @@ RT_FORCEINLINE void trace_short_queue(const DevScene& sc, const DevQueues& q, in
 template <bool OCC, bool COH = false, bool STEPS = false>
 __global__ __launch_bounds__(kBlock) void k_trace_persist(DevScene sc, DevQueues q, int b0, int b1, int renderBVH, PersistTune tune)
 {
-    const int kChunk = tune.chunk, kRefill = tune.refill, kInner = tune.inner, kLeafK = tune.leafK;
+    const int kInner = tune.inner, kLeafK = tune.leafK;
     extern __shared__ uint32_t stk[];
     const int lane = threadIdx.x & 63;
-    // queue window: extend -> rays [0, nRays[b0]); connect -> shadow rays [nShadow[b0], nShadow[b1+1])
-    const int qFirst = OCC ? q.nShadow[b0] : 0;
-    const int n = OCC ? q.nShadow[b1 + 1] - qFirst : q.nRays[b0];
-    int32_t* cursor = q.cursor + (OCC ? (RT_MAX_BOUNCES + 2) + b0 : b0);
-    const RtBVHInstance* inst = sc.blas + sc.tlas[0].BLASidx;
-    const uint32_t rootEntry = sc.rootEntry[sc.tlas[0].BLASidx];
-    float T[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) T[k] = inst->invT[k];
+    const QueueWindow w = queue_window<OCC>(q, b0, b1);
+    const OneInstance one = one_instance(sc);
 
     WorkCtr wc = { 0, 0, 0, 0 };
     uint32_t rays = 0;
@@ -947,58 +1049,20 @@ __global__ __launch_bounds__(kBlock) void k_trace_persist(DevScene sc, DevQueues
     const int nWaves = gridDim.x * (kBlock / 64), waveId = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
 #ifdef RT355_TAIL_PROBE
     const unsigned long long tp0 = wall_clock64();
-    unsigned long long tpDry = 0;
-#define TAIL_PROBE_EXIT() if (lane == 0 && waveId < kTpWaves) { unsigned long long* w = g_tp[OCC ? 8 : b0][waveId]; w[0] = tp0; w[1] = tpDry; w[2] = wall_clock64(); w[3] = rays; }
+#define TAIL_PROBE_EXIT(tpDry) if (lane == 0 && waveId < kTpWaves) { unsigned long long* p = g_tp[OCC ? 8 : b0][waveId]; p[0] = tp0; p[1] = tpDry; p[2] = wall_clock64(); p[3] = rays; }
 #endif
-    if (n <= nWaves * 64) {
-        trace_short_queue<OCC, COH>(sc, q, b0, qFirst, n, renderBVH, T, rootEntry, stk, waveId, lane, tune);
+    if (w.n <= nWaves * 64) {
+        trace_short_queue<OCC, COH>(sc, q, b0, w, renderBVH, one, stk, waveId, lane, tune);
 #ifdef RT355_TAIL_PROBE
-        TAIL_PROBE_EXIT()
+        TAIL_PROBE_EXIT(0ull)
 #endif
         return;
     }
-    int chunkNext = min(waveId * kChunk, n), chunkEnd = min(waveId * kChunk + kChunk, n);   // wave-uniform
-    bool exhausted = false;                                                                  // wave-uniform
-    int round = 0;
-
+    ChunkDealer deal(waveId, tune.chunk, w.n);
     for (;;) {
-        const unsigned long long idleMask = __ballot(slot < 0);
-        const int nIdle = __popcll(idleMask);
-        if (nIdle == 64 && exhausted && chunkNext >= chunkEnd) break;
-        if (nIdle >= kRefill && !(exhausted && chunkNext >= chunkEnd)) {
-            if (chunkNext >= chunkEnd) {           // dequeue a chunk for this wave
-                int c = 0;
-                if (tune.fixedChunks) { round++; c = round * nWaves * kChunk + waveId * kChunk; }   // chunks dealt round-robin: no atomic, no round trip (a context with the GPU to itself)
-                else {                                                                           // dequeued: balances waves that other contexts' kernels slow down
-                    if (lane == 0) c = atomicAdd(cursor, kChunk);
-                    c = __shfl(c, 0, 64) + nWaves * kChunk;
-                }
-                chunkNext = c; chunkEnd = min(c + kChunk, n);
-                if (c >= n) { exhausted = true; chunkNext = chunkEnd = 0; }
-#ifdef RT355_TAIL_PROBE
-                if (exhausted) tpDry = wall_clock64();
-#endif
-            }
-            if (chunkNext < chunkEnd) {
-                const int rank = __popcll(idleMask & ((1ull << lane) - 1ull));
-                const int idx = chunkNext + rank;
-                if (slot < 0 && idx < chunkEnd) {
-                    float4 O, D; float tmax;
-                    if (OCC) { const float4 a = q.sA[qFirst + idx], b = q.sB[qFirst + idx]; O = a; D = b; tmax = a.w; }
-                    else { O = q.O[b0 & 1][idx]; D = q.D[b0 & 1][idx]; tmax = kFar; }
-                    // transformRay (tlas.cl:3-8) of the single instance, same arithmetic as traverse_instance
-                    const float4 Dv = mk4(D.x, D.y, D.z, 0.0f), Ov = mk4(O.x, O.y, O.z, 0.0f);
-                    r.dx = dot3(mk4(T[0], T[1], T[2], 0), Dv); r.dy = dot3(mk4(T[4], T[5], T[6], 0), Dv); r.dz = dot3(mk4(T[8], T[9], T[10], 0), Dv);
-                    r.ox = dot3(mk4(T[0], T[1], T[2], 0), Ov) + T[3]; r.oy = dot3(mk4(T[4], T[5], T[6], 0), Ov) + T[7];
-                    r.oz = dot3(mk4(T[8], T[9], T[10], 0), Ov) + T[11];
-                    r.rx = 1.0f / r.dx; r.ry = 1.0f / r.dy; r.rz = 1.0f / r.dz;
-                    r.t = tmax; r.prim = -1; r.u = 0.0f; r.v = 0.0f;
-                    tLight = tmax; cur = rootEntry; sp = 0; steps = 0; slot = idx;
-                }
-                wRays += (uint32_t)min(nIdle, chunkEnd - chunkNext);
-                chunkNext = min(chunkNext + nIdle, chunkEnd);
-            }
-        }
+        int idx;
+        if (!deal.refill(slot < 0, idx, wRays, w, tune, nWaves, waveId, lane)) break;
+        if (idx >= 0) { queue_ray<OCC>(r, q, b0, w.first, idx, &one); tLight = r.t; cur = one.root; sp = 0; steps = 0; slot = idx; }
 #pragma unroll 1
         for (int it = 0; it < kInner; it++) {
             // One event per lane and iteration, but the wave issues only ONE of the two code paths: triangle tests
@@ -1048,21 +1112,11 @@ __global__ __launch_bounds__(kBlock) void k_trace_persist(DevScene sc, DevQueues
                     }
                 }
             }
-            if (done) {
-                if (OCC) { if (occluded) q.sC[qFirst + slot] = splat(0.0f); }
-                else {
-                    q.hit[slot] = mk4(r.t, __int_as_float(r.prim), r.u, r.v);
-                    if (STEPS) {
-                        if (q.steps) q.steps[slot] = steps;
-                        if (renderBVH) q.accum[q.firstPixel + slot] = splat((float)(uint32_t)steps / 255.f);
-                    }
-                }
-                slot = -1;
-            }
+            if (done) { store_result<OCC, STEPS>(q, w.first, slot, r, steps, occluded, renderBVH); slot = -1; }
         }
     }
 #ifdef RT355_TAIL_PROBE
-    TAIL_PROBE_EXIT()
+    TAIL_PROBE_EXIT(deal.tpDry)
 #endif
     if (lane == 0) { rays = wRays; wc.inst = wRays; wc.node = wNode; wc.prim = wPrim; if (STEPS) { wc.nodeIss = wNodeIss; wc.leafIss = wLeafIss; wc.evNode = wNode; wc.evPrim = wPrim; } }   // the wave's totals enter the reduction once
     flush_counters(OCC ? q.ctrConnect : q.ctrExtend, rays, wc, stk);
@@ -1079,8 +1133,8 @@ __global__ __launch_bounds__(kBlock) void k_trace_persist(DevScene sc, DevQueues
 // A lane is either in TLAS space (world ray in its registers, spBase = 0) or inside an instance (object-space ray in its registers;
 // spBase = the stack height at entry, so "sp == spBase" means the instance's tree is exhausted).  The ray is transformed ONCE, at the
 // moment the lane enters the instance (transformRay, tlas.cl:3-8, the arithmetic of traverse_instance), kept in registers over all
-// events of that instance, and the world ray is fetched back from the queue when the lane leaves it (tlas.cl:21-23 restores a 128-byte
-// backup; <= nBlas times per ray).  TLAS interior nodes go through the same code path as BLAS interior nodes - one 64-byte record,
+// events of that instance, and the world ray waits in LDS until the lane leaves it (tlas.cl:21-23 restores a 128-byte backup; <= nBlas
+// times per ray).  TLAS interior nodes go through the same code path as BLAS interior nodes - one 64-byte record,
 // two slab tests, near child first, far child pushed (tlas.cl:48-75 is bvh.cl:41-52 with other names) - only the table differs.
 // Visit order, pruning distances (tLight = ray.t on entering the level: tlas.cl:31, bvh.cl:19), `steps` (BLAS levels only: tlas.cl:44)
 // and all work counters are those of traverse_tlas, so hits and counters are bit-identical to the one-ray-per-lane kernels.
@@ -1116,57 +1170,113 @@ template <bool SPILL> RT_FORCEINLINE uint32_t stk_pop(const uint32_t* stk, const
     --sp;
     return (!SPILL || sp < q.stackCap) ? stk[sp * kBlock + threadIdx.x] : q.spill[(size_t)(sp - q.stackCap) * q.spillStride + gl];
 }
+// Enter the instance of TLAS leaf `cur` (instanceIntersect, tlas.cl:9-26): the world ray and the TLAS level's pruning distance wait in
+// LDS, 10 words behind the lane's stack column (the reference keeps a 128-byte copy of the Ray, tlas.cl:12,21-23); the object-space ray
+// takes their place, cur = the encoded BLAS root, and the BLAS level prunes against ray.t on entry (bvh.cl:19).
+RT_FORCEINLINE void inst_enter(const DevScene& sc, const DevQueues& q, uint32_t* stk, TRay& r, uint32_t& cur, uint32_t sp, uint32_t& spBase,
+                               bool& inInst, float& tLight)
+{
+    const float4* ir = sc.instRecs + (size_t)(cur & kIdMask) * 4;
+    const float4 t0 = ir[0], t1 = ir[1], t2 = ir[2], t3 = ir[3];
+    const float4 Dv = mk4(r.dx, r.dy, r.dz, 0.0f), Ov = mk4(r.ox, r.oy, r.oz, 0.0f);
+    r.dx = dot3(mk4(t0.x, t0.y, t0.z, 0), Dv); r.dy = dot3(mk4(t1.x, t1.y, t1.z, 0), Dv); r.dz = dot3(mk4(t2.x, t2.y, t2.z, 0), Dv);
+    r.ox = dot3(mk4(t0.x, t0.y, t0.z, 0), Ov) + t0.w; r.oy = dot3(mk4(t1.x, t1.y, t1.z, 0), Ov) + t1.w;
+    r.oz = dot3(mk4(t2.x, t2.y, t2.z, 0), Ov) + t2.w;
+    uint32_t* bk = stk + q.tlasLdsEntries * kBlock + threadIdx.x;
+    bk[0] = __float_as_uint(Ov.x); bk[kBlock] = __float_as_uint(Ov.y); bk[2 * kBlock] = __float_as_uint(Ov.z);
+    bk[3 * kBlock] = __float_as_uint(Dv.x); bk[4 * kBlock] = __float_as_uint(Dv.y); bk[5 * kBlock] = __float_as_uint(Dv.z);
+    bk[6 * kBlock] = __float_as_uint(r.rx); bk[7 * kBlock] = __float_as_uint(r.ry); bk[8 * kBlock] = __float_as_uint(r.rz);
+    bk[9 * kBlock] = __float_as_uint(tLight);   // (extend: 1e30; connect: t_light)
+    r.rx = 1.0f / r.dx; r.ry = 1.0f / r.dy; r.rz = 1.0f / r.dz;   // (transform_ray, written out: the world ray's 1/D goes to LDS first)
+    cur = __float_as_uint(t3.x);
+    spBase = sp; inInst = true; tLight = r.t;
+}
+// ... and leave it, its tree exhausted: back to the world ray and the TLAS level's pruning distance (tlas.cl:21-23, :31)
+RT_FORCEINLINE void inst_exit(const DevQueues& q, const uint32_t* stk, TRay& r, uint32_t& spBase, bool& inInst, float& tLight)
+{
+    const uint32_t* bk = stk + q.tlasLdsEntries * kBlock + threadIdx.x;
+    r.ox = __uint_as_float(bk[0]); r.oy = __uint_as_float(bk[kBlock]); r.oz = __uint_as_float(bk[2 * kBlock]);
+    r.dx = __uint_as_float(bk[3 * kBlock]); r.dy = __uint_as_float(bk[4 * kBlock]); r.dz = __uint_as_float(bk[5 * kBlock]);
+    r.rx = __uint_as_float(bk[6 * kBlock]); r.ry = __uint_as_float(bk[7 * kBlock]); r.rz = __uint_as_float(bk[8 * kBlock]);
+    tLight = __uint_as_float(bk[9 * kBlock]);
+    inInst = false; spBase = 0;
+}
+// One interior event (a TLAS or a BLAS node: the same 64-byte record, only the table differs).  Returns true when the lane pops: no child
+// is entered.  connect: TLAS nodes near child first (tlas.cl:58-63), BLAS nodes the child the ray leaves later first; extend: near child
+// first, far child pushed, `steps` counted on BLAS levels (STEPS).
 // COH (extend of bounce 0 through the one-ray-per-lane branch): while every lane of the wave that is on an interior node is on the SAME
 // one - primary rays of an 8x8 pixel tile, the first levels of the TLAS and of each BLAS - its record comes once through the scalar cache
 // instead of 64 times through the vector memory pipeline (as in traverse_bvh2_packed_coherent; same arithmetic, order and counters).
+template <bool OCC, bool SPILL, bool COH, bool STEPS>
+RT_FORCEINLINE bool tlas_node(const DevScene& sc, const DevQueues& q, uint32_t* stk, uint32_t gl, const TRay& r, uint32_t& cur, uint32_t& sp,
+                              float tLight, int& steps)
+{
+    const bool isT = (cur & kTagTlas) != 0u;
+    if (OCC) {
+        const float4* p = (isT ? sc.tlasPairsP : sc.pairs) + (size_t)(cur & kIdMask) * 4;
+        const float4 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
+        const uint32_t e1 = __float_as_uint(q3.x), e2 = __float_as_uint(q3.y);
+        float n1, x1, n2, x2;
+        const bool h1 = slab_both(r, mk4(q0.x, q0.y, q0.z, 0.0f), mk4(q0.w, q1.x, q1.y, 0.0f), n1, x1);
+        const bool h2 = slab_both(r, mk4(q1.z, q1.w, q2.x, 0.0f), mk4(q2.y, q2.z, q2.w, 0.0f), n2, x2);
+        if (h1 && h2) { const bool firstIs2 = isT ? (n2 < n1) : (x2 > x1); cur = firstIs2 ? e2 : e1; stk_push<SPILL>(stk, q, gl, sp, firstIs2 ? e1 : e2); }
+        else if (h1 || h2) cur = h1 ? e1 : e2;
+        else return true;
+        return false;
+    }
+    float d1, d2;
+    uint32_t e1, e2;
+    const uint32_t ucur = COH ? __builtin_amdgcn_readfirstlane(cur) : 0u;
+    if (COH && __ballot(cur != ucur) == 0ull) {   // (the slab tests are written out here too: they read the record from scalar registers)
+        const ConstF4 cp = (ConstF4)(uintptr_t)((ucur & kTagTlas) != 0u ? sc.tlasPairsP : sc.pairs) + (size_t)(ucur & kIdMask) * 4;
+        const fvec4 a = cp[0], b = cp[1], c = cp[2], d = cp[3];
+        d1 = slab(r, mk4(a.x, a.y, a.z, 0.0f), mk4(a.w, b.x, b.y, 0.0f));
+        d2 = slab(r, mk4(b.z, b.w, c.x, 0.0f), mk4(c.y, c.z, c.w, 0.0f));
+        e1 = __float_as_uint(d.x); e2 = __float_as_uint(d.y);
+    } else {
+        const float4* p = (isT ? sc.tlasPairsP : sc.pairs) + (size_t)(cur & kIdMask) * 4;
+        const float4 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
+        d1 = slab(r, mk4(q0.x, q0.y, q0.z, 0.0f), mk4(q0.w, q1.x, q1.y, 0.0f));
+        d2 = slab(r, mk4(q1.z, q1.w, q2.x, 0.0f), mk4(q2.y, q2.z, q2.w, 0.0f));
+        e1 = __float_as_uint(q3.x); e2 = __float_as_uint(q3.y);
+    }
+    if (d1 > d2) { float d = d1; d1 = d2; d2 = d; uint32_t e = e1; e1 = e2; e2 = e; }
+    if (d1 >= tLight) return true;
+    if (STEPS && !isT) steps++;
+    cur = e1;
+    if (d2 < tLight) { stk_push<SPILL>(stk, q, gl, sp, e2); if (STEPS && !isT) steps++; }
+    return false;
+}
 template <bool OCC, bool STEPS = false, bool SPILL = false, bool COH = false>
 __global__ __launch_bounds__(kBlock, 7) void k_trace_persist_tlas(DevScene sc, DevQueues q, int b0, int b1, int renderBVH, PersistTune tune)
 {
-    const int kChunk = tune.chunk, kRefill = tune.refill, kInner = tune.inner, kLeafK = tune.leafK;
+    const int kInner = tune.inner, kLeafK = tune.leafK;
     extern __shared__ uint32_t stk[];
     const int lane = threadIdx.x & 63;
-    const int qFirst = OCC ? q.nShadow[b0] : 0;
-    const int n = OCC ? q.nShadow[b1 + 1] - qFirst : q.nRays[b0];
-    int32_t* cursor = q.cursor + (OCC ? (RT_MAX_BOUNCES + 2) + b0 : b0);
+    const QueueWindow w = queue_window<OCC>(q, b0, b1);
     const int nWaves = gridDim.x * (kBlock / 64), waveId = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
     const uint32_t gl = blockIdx.x * kBlock + threadIdx.x;    // this lane's column of the spill stack
 
-    if (n <= nWaves * 64 || tune.flat) {
+    if (w.n <= nWaves * 64 || tune.flat) {
         // Short queue (late bounces; bounce 0 when launched with one workgroup per 256 rays): one ray per lane and nothing to refill
         // from, so every lane just runs its own state machine to the end - the same states and the same single stack column as the
-        // event loop below (world ray re-fetched on leaving an instance instead of a nine-register backup), without the wave-level
-        // path selection.  tune.flat: ANY queue this way, the persistent grid striding over it 64 rays per wave and round - scenes whose
-        // rays take a dozen events (an open scene: most rays leave through the TLAS root or end on the floor) finish before the event
-        // loop's bookkeeping pays, but still want the seven workgroups per CU that the capped stack column allows.
+        // event loop below, without the wave-level path selection.  tune.flat: ANY queue this way, the persistent grid striding over it
+        // 64 rays per wave and round - scenes whose rays take a dozen events (an open scene: most rays leave through the TLAS root or end
+        // on the floor) finish before the event loop's bookkeeping pays, but still want the seven workgroups per CU that the capped
+        // stack column allows.
         WorkCtr wc = { 0, 0, 0, 0 };
         uint32_t rays = 0;
-        // primary rays: a wave takes an 8x8 pixel tile instead of 64 pixels of a scan line (see trace_short_queue) - any slot -> lane map
-        // is legal, every slot is traced on its own
-        const bool tiled = !OCC && b0 == 0 && n == q.nPix && ((q.width | (q.nPix / q.width)) & 7) == 0;
-        const int tilesX = q.width >> 3;
-        int packWaves = nWaves;
-        const int packId = (tune.xcdRays > 0 || tune.thin) && !tiled ? xcd_pack(n, tune.xcdRays, tune.xcdFirst, packWaves) : waveId;   // a sparse queue on few XCDs
-        // ... and on few lanes of every participating wave (see trace_short_queue)
-        int per = 64;
-        if (tune.thin > 0 && !tiled && (long long)packWaves * tune.thin >= (long long)n) per = max(1, (n + packWaves - 1) / packWaves);
-        for (int item = packId < 0 ? n : packId; (long long)item * per < (long long)n; item += packWaves) {
-            int idx = item * per + lane;
-            if (tiled) { const int ty = item / tilesX, tx = item - ty * tilesX; idx = ((ty << 3) + (lane >> 3)) * q.width + (tx << 3) + (lane & 7); }
-            if (lane >= per || idx >= n) continue;
+        const bool tiled = primary_tiles<OCC>(q, b0, w.n);
+        const SparseMap m = tiled ? SparseMap{ waveId, nWaves, 64 } : sparse_map(w.n, tune, waveId);
+        for (int item = m.first < 0 ? w.n : m.first; (long long)item * m.per < (long long)w.n; item += m.stride) {
+            const int idx = tiled ? tile_slot(q, item, lane) : item * m.per + lane;
+            if (lane >= m.per || idx >= w.n) continue;
             TRay r;
-            float tmax;
-            {
-                float4 O, D;
-                if (OCC) { const float4 a = q.sA[qFirst + idx], b = q.sB[qFirst + idx]; O = a; D = b; tmax = a.w; }
-                else { O = q.O[b0 & 1][idx]; D = q.D[b0 & 1][idx]; tmax = kFar; }
-                r.ox = O.x; r.oy = O.y; r.oz = O.z; r.dx = D.x; r.dy = D.y; r.dz = D.z;
-                r.rx = 1.0f / D.x; r.ry = 1.0f / D.y; r.rz = 1.0f / D.z;
-            }
-            r.t = tmax; r.prim = -1; r.u = 0.0f; r.v = 0.0f;
+            queue_ray<OCC>(r, q, b0, w.first, idx);
             rays++;
             uint32_t cur = sc.tlasRootP, sp = 0, spBase = 0;
             bool inInst = false, occluded = false;
-            float tLight = tmax;
+            float tLight = r.t;
             int steps = 0;
             for (;;) {
                 bool needPop = false;
@@ -1180,89 +1290,20 @@ __global__ __launch_bounds__(kBlock, 7) void k_trace_persist_tlas(DevScene sc, D
                     if (OCC && occluded) break;
                     needPop = true;
                 } else if ((cur & kTagMask) == kTagInst) {
-                    const float4* ir = sc.instRecs + (size_t)(cur & kIdMask) * 4;
-                    const float4 t0 = ir[0], t1 = ir[1], t2 = ir[2], t3 = ir[3];
-                    const float4 Dv = mk4(r.dx, r.dy, r.dz, 0.0f), Ov = mk4(r.ox, r.oy, r.oz, 0.0f);
-                    r.dx = dot3(mk4(t0.x, t0.y, t0.z, 0), Dv); r.dy = dot3(mk4(t1.x, t1.y, t1.z, 0), Dv); r.dz = dot3(mk4(t2.x, t2.y, t2.z, 0), Dv);
-                    r.ox = dot3(mk4(t0.x, t0.y, t0.z, 0), Ov) + t0.w; r.oy = dot3(mk4(t1.x, t1.y, t1.z, 0), Ov) + t1.w;
-                    r.oz = dot3(mk4(t2.x, t2.y, t2.z, 0), Ov) + t2.w;
-                    if (tune.backup) {   // the world ray waits in LDS (the reference keeps a 128-byte copy of the Ray, tlas.cl:12,21-23)
-                        uint32_t* bk = stk + q.tlasLdsEntries * kBlock + threadIdx.x;
-                        bk[0] = __float_as_uint(Ov.x); bk[kBlock] = __float_as_uint(Ov.y); bk[2 * kBlock] = __float_as_uint(Ov.z);
-                        bk[3 * kBlock] = __float_as_uint(Dv.x); bk[4 * kBlock] = __float_as_uint(Dv.y); bk[5 * kBlock] = __float_as_uint(Dv.z);
-                        bk[6 * kBlock] = __float_as_uint(r.rx); bk[7 * kBlock] = __float_as_uint(r.ry); bk[8 * kBlock] = __float_as_uint(r.rz);
-                    }
-                    r.rx = 1.0f / r.dx; r.ry = 1.0f / r.dy; r.rz = 1.0f / r.dz;
                     wc.inst++;
-                    cur = __float_as_uint(t3.x);
-                    spBase = sp; inInst = true; tLight = r.t;
+                    inst_enter(sc, q, stk, r, cur, sp, spBase, inInst, tLight);
                     continue;
                 } else {
-                    const bool isT = (cur & kTagTlas) != 0u;
-                    if (isT) wc.tlas++; else wc.node++;
-                    if (OCC) {
-                        const float4* p = (isT ? sc.tlasPairsP : sc.pairs) + (size_t)(cur & kIdMask) * 4;
-                        const float4 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
-                        const uint32_t e1 = __float_as_uint(q3.x), e2 = __float_as_uint(q3.y);
-                        float n1, x1, n2, x2;
-                        const bool h1 = slab_both(r, mk4(q0.x, q0.y, q0.z, 0.0f), mk4(q0.w, q1.x, q1.y, 0.0f), n1, x1);
-                        const bool h2 = slab_both(r, mk4(q1.z, q1.w, q2.x, 0.0f), mk4(q2.y, q2.z, q2.w, 0.0f), n2, x2);
-                        if (h1 && h2) { const bool firstIs2 = isT ? (n2 < n1) : (x2 > x1); cur = firstIs2 ? e2 : e1; stk_push<SPILL>(stk, q, gl, sp, firstIs2 ? e1 : e2); }
-                        else if (h1 || h2) cur = h1 ? e1 : e2;
-                        else needPop = true;
-                    } else {
-                        float d1, d2;
-                        uint32_t e1, e2;
-                        const uint32_t ucur = COH ? __builtin_amdgcn_readfirstlane(cur) : 0u;
-                        if (COH && __ballot(cur != ucur) == 0ull) {   // (the slab tests are written out here too: they read the record from scalar registers)
-                            const ConstF4 cp = (ConstF4)(uintptr_t)((ucur & kTagTlas) != 0u ? sc.tlasPairsP : sc.pairs) + (size_t)(ucur & kIdMask) * 4;
-                            const fvec4 a = cp[0], b = cp[1], c = cp[2], d = cp[3];
-                            d1 = slab(r, mk4(a.x, a.y, a.z, 0.0f), mk4(a.w, b.x, b.y, 0.0f));
-                            d2 = slab(r, mk4(b.z, b.w, c.x, 0.0f), mk4(c.y, c.z, c.w, 0.0f));
-                            e1 = __float_as_uint(d.x); e2 = __float_as_uint(d.y);
-                        } else {
-                            const float4* p = (isT ? sc.tlasPairsP : sc.pairs) + (size_t)(cur & kIdMask) * 4;
-                            const float4 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
-                            d1 = slab(r, mk4(q0.x, q0.y, q0.z, 0.0f), mk4(q0.w, q1.x, q1.y, 0.0f));
-                            d2 = slab(r, mk4(q1.z, q1.w, q2.x, 0.0f), mk4(q2.y, q2.z, q2.w, 0.0f));
-                            e1 = __float_as_uint(q3.x); e2 = __float_as_uint(q3.y);
-                        }
-                        if (d1 > d2) { float d = d1; d1 = d2; d2 = d; uint32_t e = e1; e1 = e2; e2 = e; }
-                        if (d1 >= tLight) needPop = true;
-                        else {
-                            if (!isT) steps++;
-                            cur = e1;
-                            if (d2 < tLight) { stk_push<SPILL>(stk, q, gl, sp, e2); if (!isT) steps++; }
-                        }
-                    }
+                    if ((cur & kTagTlas) != 0u) wc.tlas++; else wc.node++;
+                    needPop = tlas_node<OCC, SPILL, COH, true>(sc, q, stk, gl, r, cur, sp, tLight, steps);
                 }
                 if (needPop) {
-                    if (inInst && sp == spBase) {
-                        if (tune.backup) {
-                            const uint32_t* bk = stk + q.tlasLdsEntries * kBlock + threadIdx.x;
-                            r.ox = __uint_as_float(bk[0]); r.oy = __uint_as_float(bk[kBlock]); r.oz = __uint_as_float(bk[2 * kBlock]);
-                            r.dx = __uint_as_float(bk[3 * kBlock]); r.dy = __uint_as_float(bk[4 * kBlock]); r.dz = __uint_as_float(bk[5 * kBlock]);
-                            r.rx = __uint_as_float(bk[6 * kBlock]); r.ry = __uint_as_float(bk[7 * kBlock]); r.rz = __uint_as_float(bk[8 * kBlock]);
-                            tLight = tmax;
-                        } else {
-                            float4 O, D;
-                            if (OCC) { const float4 a = q.sA[qFirst + idx], b = q.sB[qFirst + idx]; O = a; D = b; tLight = a.w; }
-                            else { O = q.O[b0 & 1][idx]; D = q.D[b0 & 1][idx]; tLight = kFar; }
-                            r.ox = O.x; r.oy = O.y; r.oz = O.z; r.dx = D.x; r.dy = D.y; r.dz = D.z;
-                            r.rx = 1.0f / D.x; r.ry = 1.0f / D.y; r.rz = 1.0f / D.z;
-                        }
-                        inInst = false; spBase = 0;
-                    }
+                    if (inInst && sp == spBase) inst_exit(q, stk, r, spBase, inInst, tLight);
                     if (sp == 0) break;
                     cur = stk_pop<SPILL>(stk, q, gl, sp);
                 }
             }
-            if (OCC) { if (occluded) q.sC[qFirst + idx] = splat(0.0f); }
-            else {
-                q.hit[idx] = mk4(r.t, __int_as_float(r.prim), r.u, r.v);
-                if (q.steps) q.steps[idx] = steps;
-                if (renderBVH) q.accum[q.firstPixel + idx] = splat((float)(uint32_t)steps / 255.f);
-            }
+            store_result<OCC, true>(q, w.first, idx, r, steps, occluded, renderBVH);
         }
         flush_counters(OCC ? q.ctrConnect : q.ctrExtend, rays, wc, stk);
         return;
@@ -1274,47 +1315,11 @@ __global__ __launch_bounds__(kBlock, 7) void k_trace_persist_tlas(DevScene sc, D
     bool inInst = false;
     int slot = -1, steps = 0;
     float tLight = 0;
-    int chunkNext = min(waveId * kChunk, n), chunkEnd = min(waveId * kChunk + kChunk, n);   // wave-uniform
-    bool exhausted = false;
-    int round = 0;
-
-    // the world ray of queue slot `idx` into r (k_extend / k_connect: rD = 1 / D, three IEEE divides)
-    auto world_ray = [&](int idx, float& tmax) {
-        float4 O, D;
-        if (OCC) { const float4 a = q.sA[qFirst + idx], b = q.sB[qFirst + idx]; O = a; D = b; tmax = a.w; }
-        else { O = q.O[b0 & 1][idx]; D = q.D[b0 & 1][idx]; tmax = kFar; }
-        r.ox = O.x; r.oy = O.y; r.oz = O.z; r.dx = D.x; r.dy = D.y; r.dz = D.z;
-        r.rx = 1.0f / D.x; r.ry = 1.0f / D.y; r.rz = 1.0f / D.z;
-    };
-
+    ChunkDealer deal(waveId, tune.chunk, w.n);
     for (;;) {
-        const unsigned long long idleMask = __ballot(slot < 0);
-        const int nIdle = __popcll(idleMask);
-        if (nIdle == 64 && exhausted && chunkNext >= chunkEnd) break;
-        if (nIdle >= kRefill && !(exhausted && chunkNext >= chunkEnd)) {
-            if (chunkNext >= chunkEnd) {
-                int c = 0;
-                if (tune.fixedChunks) { round++; c = round * nWaves * kChunk + waveId * kChunk; }
-                else {
-                    if (lane == 0) c = atomicAdd(cursor, kChunk);
-                    c = __shfl(c, 0, 64) + nWaves * kChunk;
-                }
-                chunkNext = c; chunkEnd = min(c + kChunk, n);
-                if (c >= n) { exhausted = true; chunkNext = chunkEnd = 0; }
-            }
-            if (chunkNext < chunkEnd) {
-                const int rank = __popcll(idleMask & ((1ull << lane) - 1ull));
-                const int idx = chunkNext + rank;
-                if (slot < 0 && idx < chunkEnd) {
-                    float tmax;
-                    world_ray(idx, tmax);
-                    r.t = tmax; r.prim = -1; r.u = 0.0f; r.v = 0.0f;
-                    tLight = tmax; cur = sc.tlasRootP; sp = 0; spBase = 0; inInst = false; steps = 0; slot = idx;
-                }
-                wRays += (uint32_t)min(nIdle, chunkEnd - chunkNext);
-                chunkNext = min(chunkNext + nIdle, chunkEnd);
-            }
-        }
+        int idx;
+        if (!deal.refill(slot < 0, idx, wRays, w, tune, nWaves, waveId, lane)) break;
+        if (idx >= 0) { queue_ray<OCC>(r, q, b0, w.first, idx); tLight = r.t; cur = sc.tlasRootP; sp = 0; spBase = 0; inInst = false; steps = 0; slot = idx; }
 #pragma unroll 1
         for (int it = 0; it < kInner; it++) {
             const bool act = slot >= 0, atLeaf = act && (cur & kLeafBit) != 0u;
@@ -1322,9 +1327,9 @@ __global__ __launch_bounds__(kBlock, 7) void k_trace_persist_tlas(DevScene sc, D
             const bool atNode = act && !atLeaf && !atInst;
             const unsigned long long lm = __ballot(atLeaf), im = __ballot(atNode), xm = __ballot(atInst);
             if ((lm | im | xm) == 0ull) break;
-            if (xm != 0ull) {
-                // enter an instance (instanceIntersect, tlas.cl:9-26): rare (<= nBlas per ray) and short, so it goes first and alone
+            if (xm != 0ull) {   // entering an instance is rare (<= nBlas per ray) and short, so it goes first and alone
                 wInst += (uint32_t)__popcll(xm);
+                // (inst_enter, inst_exit and store_result written out: with all three shared the any-hit instantiations exceed 72 VGPRs)
                 if (atInst) {
                     const float4* ir = sc.instRecs + (size_t)(cur & kIdMask) * 4;
                     const float4 t0 = ir[0], t1 = ir[1], t2 = ir[2], t3 = ir[3];
@@ -1332,16 +1337,16 @@ __global__ __launch_bounds__(kBlock, 7) void k_trace_persist_tlas(DevScene sc, D
                     r.dx = dot3(mk4(t0.x, t0.y, t0.z, 0), Dv); r.dy = dot3(mk4(t1.x, t1.y, t1.z, 0), Dv); r.dz = dot3(mk4(t2.x, t2.y, t2.z, 0), Dv);
                     r.ox = dot3(mk4(t0.x, t0.y, t0.z, 0), Ov) + t0.w; r.oy = dot3(mk4(t1.x, t1.y, t1.z, 0), Ov) + t1.w;
                     r.oz = dot3(mk4(t2.x, t2.y, t2.z, 0), Ov) + t2.w;
-                    if (tune.backup) {
+                    {
                         uint32_t* bk = stk + q.tlasLdsEntries * kBlock + threadIdx.x;
                         bk[0] = __float_as_uint(Ov.x); bk[kBlock] = __float_as_uint(Ov.y); bk[2 * kBlock] = __float_as_uint(Ov.z);
                         bk[3 * kBlock] = __float_as_uint(Dv.x); bk[4 * kBlock] = __float_as_uint(Dv.y); bk[5 * kBlock] = __float_as_uint(Dv.z);
                         bk[6 * kBlock] = __float_as_uint(r.rx); bk[7 * kBlock] = __float_as_uint(r.ry); bk[8 * kBlock] = __float_as_uint(r.rz);
-                        bk[9 * kBlock] = __float_as_uint(tLight);       // the TLAS level's pruning distance (connect: t_light; extend: 1e30)
+                        bk[9 * kBlock] = __float_as_uint(tLight);
                     }
                     r.rx = 1.0f / r.dx; r.ry = 1.0f / r.dy; r.rz = 1.0f / r.dz;
-                    cur = __float_as_uint(t3.x);          // encoded BLAS root (interior id or leaf)
-                    spBase = sp; inInst = true; tLight = r.t;   // intersectBVH2 prunes against ray.t on entry (bvh.cl:19)
+                    cur = __float_as_uint(t3.x);
+                    spBase = sp; inInst = true; tLight = r.t;
                 }
                 continue;
             }
@@ -1358,56 +1363,24 @@ __global__ __launch_bounds__(kBlock, 7) void k_trace_persist_tlas(DevScene sc, D
                 }
             } else {
                 if (STEPS) wNodeIss++;
-                const bool isT = (cur & kTagTlas) != 0u;
-                const unsigned long long tm = __ballot(atNode && isT);
+                const unsigned long long tm = __ballot(atNode && (cur & kTagTlas) != 0u);
                 wTlas += (uint32_t)__popcll(tm); wNode += (uint32_t)(__popcll(im) - __popcll(tm));
-                if (atNode) {
-                    const float4* p = (isT ? sc.tlasPairsP : sc.pairs) + (size_t)(cur & kIdMask) * 4;
-                    const float4 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
-                    uint32_t e1 = __float_as_uint(q3.x), e2 = __float_as_uint(q3.y);
-                    if (OCC) {
-                        float n1, x1, n2, x2;
-                        const bool h1 = slab_both(r, mk4(q0.x, q0.y, q0.z, 0.0f), mk4(q0.w, q1.x, q1.y, 0.0f), n1, x1);
-                        const bool h2 = slab_both(r, mk4(q1.z, q1.w, q2.x, 0.0f), mk4(q2.y, q2.z, q2.w, 0.0f), n2, x2);
-                        if (h1 && h2) {
-                            const bool firstIs2 = isT ? (n2 < n1) : (x2 > x1);   // TLAS: the reference's near-first (tlas.cl:58-63); BLAS: later exit first
-                            cur = firstIs2 ? e2 : e1; stk_push<SPILL>(stk, q, gl, sp, firstIs2 ? e1 : e2);
-                        }
-                        else if (h1 || h2) cur = h1 ? e1 : e2;
-                        else needPop = true;
-                    } else {
-                        float d1 = slab(r, mk4(q0.x, q0.y, q0.z, 0.0f), mk4(q0.w, q1.x, q1.y, 0.0f));
-                        float d2 = slab(r, mk4(q1.z, q1.w, q2.x, 0.0f), mk4(q2.y, q2.z, q2.w, 0.0f));
-                        if (d1 > d2) { float d = d1; d1 = d2; d2 = d; uint32_t e = e1; e1 = e2; e2 = e; }
-                        if (d1 >= tLight) needPop = true;
-                        else {
-                            if (STEPS && !isT) steps++;
-                            cur = e1;
-                            if (d2 < tLight) { stk_push<SPILL>(stk, q, gl, sp, e2); if (STEPS && !isT) steps++; }
-                        }
-                    }
-                }
+                if (atNode) needPop = tlas_node<OCC, SPILL, false, STEPS>(sc, q, stk, gl, r, cur, sp, tLight, steps);
             }
             if (needPop) {
-                if (inInst && sp == spBase) {   // the instance's tree is exhausted: back to world space (tlas.cl:21-23)
-                    if (tune.backup) {
-                        const uint32_t* bk = stk + q.tlasLdsEntries * kBlock + threadIdx.x;
-                        r.ox = __uint_as_float(bk[0]); r.oy = __uint_as_float(bk[kBlock]); r.oz = __uint_as_float(bk[2 * kBlock]);
-                        r.dx = __uint_as_float(bk[3 * kBlock]); r.dy = __uint_as_float(bk[4 * kBlock]); r.dz = __uint_as_float(bk[5 * kBlock]);
-                        r.rx = __uint_as_float(bk[6 * kBlock]); r.ry = __uint_as_float(bk[7 * kBlock]); r.rz = __uint_as_float(bk[8 * kBlock]);
-                        tLight = __uint_as_float(bk[9 * kBlock]);
-                    } else {
-                        float tmax;
-                        world_ray(slot, tmax);
-                        tLight = tmax;
-                    }
-                    inInst = false; spBase = 0;   // the TLAS level prunes against the ray.t of ITS entry (tlas.cl:31)
+                if (inInst && sp == spBase) {
+                    const uint32_t* bk = stk + q.tlasLdsEntries * kBlock + threadIdx.x;
+                    r.ox = __uint_as_float(bk[0]); r.oy = __uint_as_float(bk[kBlock]); r.oz = __uint_as_float(bk[2 * kBlock]);
+                    r.dx = __uint_as_float(bk[3 * kBlock]); r.dy = __uint_as_float(bk[4 * kBlock]); r.dz = __uint_as_float(bk[5 * kBlock]);
+                    r.rx = __uint_as_float(bk[6 * kBlock]); r.ry = __uint_as_float(bk[7 * kBlock]); r.rz = __uint_as_float(bk[8 * kBlock]);
+                    tLight = __uint_as_float(bk[9 * kBlock]);
+                    inInst = false; spBase = 0;
                 }
                 if (sp == 0) done = true;
                 else cur = stk_pop<SPILL>(stk, q, gl, sp);
             }
             if (done) {
-                if (OCC) { if (occluded) q.sC[qFirst + slot] = splat(0.0f); }
+                if (OCC) { if (occluded) q.sC[w.first + slot] = splat(0.0f); }
                 else {
                     q.hit[slot] = mk4(r.t, __int_as_float(r.prim), r.u, r.v);
                     if (STEPS) {
@@ -1434,92 +1407,25 @@ __global__ __launch_bounds__(kBlock, 7) void k_trace_persist_tlas(DevScene sc, D
 template <bool OCC>
 __global__ __launch_bounds__(kBlock) void k_trace_persist4(DevScene sc, DevQueues q, int b0, int b1, int renderBVH, PersistTune tune)
 {
-    const int kChunk = tune.chunk, kRefill = tune.refill, kInner = tune.inner, kLeafK = tune.leafK;
+    const int kInner = tune.inner, kLeafK = tune.leafK;
     extern __shared__ uint32_t stk[];
     const int lane = threadIdx.x & 63;
-    const int qFirst = OCC ? q.nShadow[b0] : 0;
-    const int n = OCC ? q.nShadow[b1 + 1] - qFirst : q.nRays[b0];
-    int32_t* cursor = q.cursor + (OCC ? (RT_MAX_BOUNCES + 2) + b0 : b0);
-    const RtBVHInstance* inst = sc.blas + sc.tlas[0].BLASidx;
-    const uint32_t rootNode = sc.rootEntry[sc.tlas[0].BLASidx];   // id of the root in the dense quad table
-    float T[12];
-#pragma unroll
-    for (int k = 0; k < 12; k++) T[k] = inst->invT[k];
+    const QueueWindow w = queue_window<OCC>(q, b0, b1);
+    const OneInstance one = one_instance(sc);   // (root: the id in the dense quad table)
+    const int nWaves = gridDim.x * (kBlock / 64), waveId = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    if (w.n <= nWaves * 64) { trace_short_queue<OCC, false, true>(sc, q, b0, w, renderBVH, one, stk, waveId, lane, tune); return; }
 
     WorkCtr wc = { 0, 0, 0, 0 };
-    uint32_t rays = 0;
+    uint32_t wRays = 0;   // rays taken up by this wave (wave-uniform)
     TRay r; r.t = 0; r.prim = -1; r.u = r.v = 0; r.ox = r.oy = r.oz = r.dx = r.dy = r.dz = r.rx = r.ry = r.rz = 0;
     uint32_t cur = 0, sp = 0, leafMask = 0, e0 = 0, e1 = 0, e2 = 0, e3 = 0;
     int slot = -1, steps = 0;
     float tLight = 0;
-    const int nWaves = gridDim.x * (kBlock / 64), waveId = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
-
-    auto setup = [&](int idx) {
-        float4 O, D; float tmax;
-        if (OCC) { const float4 a = q.sA[qFirst + idx], b = q.sB[qFirst + idx]; O = a; D = b; tmax = a.w; }
-        else { O = q.O[b0 & 1][idx]; D = q.D[b0 & 1][idx]; tmax = kFar; }
-        const float4 Dv = mk4(D.x, D.y, D.z, 0.0f), Ov = mk4(O.x, O.y, O.z, 0.0f);
-        r.dx = dot3(mk4(T[0], T[1], T[2], 0), Dv); r.dy = dot3(mk4(T[4], T[5], T[6], 0), Dv); r.dz = dot3(mk4(T[8], T[9], T[10], 0), Dv);
-        r.ox = dot3(mk4(T[0], T[1], T[2], 0), Ov) + T[3]; r.oy = dot3(mk4(T[4], T[5], T[6], 0), Ov) + T[7];
-        r.oz = dot3(mk4(T[8], T[9], T[10], 0), Ov) + T[11];
-        r.rx = 1.0f / r.dx; r.ry = 1.0f / r.dy; r.rz = 1.0f / r.dz;
-        r.t = tmax; r.prim = -1; r.u = 0.0f; r.v = 0.0f;
-        tLight = tmax;
-    };
-    auto finish = [&](int idx, int st, bool occluded) {
-        if (OCC) { if (occluded) q.sC[qFirst + idx] = splat(0.0f); }
-        else {
-            q.hit[idx] = mk4(r.t, __int_as_float(r.prim), r.u, r.v);
-            if (q.steps) q.steps[idx] = st;
-            if (renderBVH) q.accum[q.firstPixel + idx] = splat((float)(uint32_t)st / 255.f);
-        }
-    };
-
-    if (n <= nWaves * 64) {   // short queue: plain one-ray-per-lane loop
-        int idx = b0 == 0 && n == q.nPix ? waveId * 64 + lane : sparse_slot(n, tune, waveId, lane);
-        if (!OCC && b0 == 0 && ((q.width | (q.nPix / q.width)) & 7) == 0 && n == q.nPix && (long long)gridDim.x * kBlock >= (long long)q.nPix) {   // primary rays: 8x8 pixel tile per wave (see trace_short_queue)
-            const int tilesX = q.width >> 3, ty = waveId / tilesX, tx = waveId - ty * tilesX;
-            idx = ((ty << 3) + (lane >> 3)) * q.width + (tx << 3) + (lane & 7);
-        }
-        if (idx < n) {
-            setup(idx);
-            rays = 1; wc.inst = 1;
-            const int st = traverse_bvh4_packed<OCC>(sc, r, rootNode, stk, wc);
-            finish(idx, st, st == -1);
-        }
-        flush_counters(OCC ? q.ctrConnect : q.ctrExtend, rays, wc, stk);
-        return;
-    }
-    int chunkNext = min(waveId * kChunk, n), chunkEnd = min(waveId * kChunk + kChunk, n);
-    bool exhausted = false;
-    int round = 0;
-
+    ChunkDealer deal(waveId, tune.chunk, w.n);
     for (;;) {
-        const unsigned long long idleMask = __ballot(slot < 0);
-        const int nIdle = __popcll(idleMask);
-        if (nIdle == 64 && exhausted && chunkNext >= chunkEnd) break;
-        if (nIdle >= kRefill && !(exhausted && chunkNext >= chunkEnd)) {
-            if (chunkNext >= chunkEnd) {
-                int c = 0;
-                if (tune.fixedChunks) { round++; c = round * nWaves * kChunk + waveId * kChunk; }   // see k_trace_persist
-                else {
-                    if (lane == 0) c = atomicAdd(cursor, kChunk);
-                    c = __shfl(c, 0, 64) + nWaves * kChunk;
-                }
-                chunkNext = c; chunkEnd = min(c + kChunk, n);
-                if (c >= n) { exhausted = true; chunkNext = chunkEnd = 0; }
-            }
-            if (chunkNext < chunkEnd) {
-                const int rank = __popcll(idleMask & ((1ull << lane) - 1ull));
-                const int idx = chunkNext + rank;
-                if (slot < 0 && idx < chunkEnd) {
-                    setup(idx);
-                    cur = rootNode; sp = 0; steps = 0; leafMask = 0; slot = idx;
-                    rays++; wc.inst++;
-                }
-                chunkNext = min(chunkNext + nIdle, chunkEnd);
-            }
-        }
+        int idx;
+        if (!deal.refill(slot < 0, idx, wRays, w, tune, nWaves, waveId, lane)) break;
+        if (idx >= 0) { queue_ray<OCC>(r, q, b0, w.first, idx, &one); tLight = r.t; cur = one.root; sp = 0; steps = 0; leafMask = 0; slot = idx; }
 #pragma unroll 1
         for (int it = 0; it < kInner; it++) {
             const bool act = slot >= 0, atLeaf = act && leafMask != 0u;
@@ -1561,9 +1467,11 @@ __global__ __launch_bounds__(kBlock) void k_trace_persist4(DevScene sc, DevQueue
                 leafMask = m;
                 if (m == 0u) { if (sp == 0) done = true; else cur = STK(--sp); }
             }
-            if (done) { finish(slot, steps, occluded); slot = -1; leafMask = 0; }
+            if (done) { store_result<OCC, true>(q, w.first, slot, r, steps, occluded, renderBVH); slot = -1; leafMask = 0; }
         }
     }
+    uint32_t rays = 0;
+    if (lane == 0) { rays = wRays; wc.inst = wRays; }   // the wave's total enters the reduction once
     flush_counters(OCC ? q.ctrConnect : q.ctrExtend, rays, wc, stk);
 }
 

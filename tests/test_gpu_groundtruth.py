@@ -37,8 +37,6 @@ CASES = {
     "bvh4-one-ray-per-lane": ("one", 1, 2, {}, dict(persist4=0, persist=0)),
     "tlas-lds": ("multi", 0, 0, {"RT355_NO_SPILL": "1"}, dict(persist=2)),
     "tlas-spill": ("multi", 0, 0, {"RT355_SPILL_CAP": "6"}, dict(persist=3)),
-    "tlas-lds-no-backup": ("multi", 0, 0, {"RT355_NO_SPILL": "1", "RT355_TLAS_BACKUP": "0"}, dict(persist=2)),
-    "tlas-spill-no-backup": ("multi", 0, 0, {"RT355_SPILL_CAP": "6", "RT355_TLAS_BACKUP": "0"}, dict(persist=3)),
     "tlas-flat-0,0": ("multi", 0, 0, {"RT355_TLAS_FLAT": "0,0", "RT355_SPILL_CAP": "6"}, dict(persist=3)),
     "tlas-flat-1,0": ("multi", 0, 0, {"RT355_TLAS_FLAT": "1,0", "RT355_NO_SPILL": "1"}, dict(persist=2)),
     "tlas-flat-1,1": ("multi", 0, 0, {"RT355_TLAS_FLAT": "1,1", "RT355_SPILL_CAP": "6"}, dict(persist=3)),

@@ -619,14 +619,11 @@ def test_persistent_wavefronts_vs_oracle(accel, monkeypatch):
 _TLAS_CACHE = {}
 
 
-@pytest.mark.parametrize("stack,flat,backup", [pytest.param("lds", "0,0", "1", id="lds-0,0"), pytest.param("spill", "0,0", "1", id="spill-0,0"),
-                                               pytest.param("spill", "1,0", "1", id="spill-1,0"), pytest.param("lds", "1,1", "1", id="lds-1,1"),
-                                               pytest.param("lds", "0,0", "0", id="lds-0,0-no-backup"),
-                                               pytest.param("spill", "0,0", "0", id="spill-0,0-no-backup"),
-                                               pytest.param("spill", "1,0", "0", id="spill-1,0-no-backup")])
-def test_persistent_wavefronts_through_a_tlas_vs_oracle(stack, flat, backup, monkeypatch):
+@pytest.mark.parametrize("stack,flat", [pytest.param("lds", "0,0", id="lds-0,0"), pytest.param("spill", "0,0", id="spill-0,0"),
+                                        pytest.param("spill", "1,0", id="spill-1,0"), pytest.param("lds", "1,1", id="lds-1,1")])
+def test_persistent_wavefronts_through_a_tlas_vs_oracle(stack, flat, monkeypatch):
     """k_trace_persist_tlas (BASELINE config 5's kernel: persistent wavefronts through a multi-BLAS TLAS, TLAS entries on the BLAS stack
-    column, the ray transformed once on entering an instance and fetched back from the queue on leaving it).  One workgroup per CU
+    column, the ray transformed once on entering an instance, the world ray waiting in LDS until the lane leaves it).  One workgroup per CU
     brings its long-queue threshold down to 65,536 rays, so a 640x360 frame runs bounces >= 1 and connect through the event loop and
     the later bounces through its per-lane branch.  Two scenes: two SBVH BLAS (glass sphere in one), and three BLAS of which one
     carries a real inverse transform.  Accumulator, RNG state, every work counter (TLAS visits and instance visits included) and the
@@ -638,8 +635,6 @@ def test_persistent_wavefronts_through_a_tlas_vs_oracle(stack, flat, backup, mon
     # "e,c": extend / connect through the kernel's event loop (0) or its one-ray-per-lane branch striding over the queue (1; the library's
     # default for multi-BLAS scenes is 1,0)
     monkeypatch.setenv("RT355_TLAS_FLAT", flat)
-    # "backup" 0: RT355_TLAS_BACKUP=0, the world ray is fetched back from the queue on leaving an instance instead of waiting in LDS
-    monkeypatch.setenv("RT355_TLAS_BACKUP", backup)
     Wd, Hd = 960, 540          # bounce 1 still holds more than 65,536 rays
     from magr_ray_tracer_amd.scenes import Scene, _std_materials, box_tris, param_surface
 

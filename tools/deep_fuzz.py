@@ -28,8 +28,6 @@ for seed in range(first, first + count):
         if multi:
             for k in ("RT355_SPILL_CAP", "RT355_NO_SPILL", "RT355_TLAS_FLAT"):
                 os.environ.pop(k, None)
-            # every other scene without the world-ray backup in LDS (RT355_TLAS_BACKUP=0: the world ray is fetched back from the queue)
-            os.environ["RT355_TLAS_BACKUP"] = "0" if seed % 2 else "1"
             T.test_fuzz_random_multi_blas_soups(seed, _Env(), big)
         else:
             (T.test_fuzz_random_mixed_scenes if mixed else T.test_fuzz_random_triangle_soups)(seed, big)

@@ -1,4 +1,4 @@
-"""Multi-BLAS scenes whose stack column needs 13..22 entries: spill (cap 12) + world ray in LDS, or the whole column in LDS without the backup?
+"""Multi-BLAS scenes whose stack column needs 13..22 entries: spill (cap 12), or the whole column in LDS (the world ray in LDS either way)?
 usage (GPU box): python tools/middepth_tlas.py   - runs each policy in a child process (the library reads its switches at upload)"""
 import os
 import subprocess
@@ -30,6 +30,6 @@ if len(sys.argv) > 1 and sys.argv[1] == "child":
     sys.exit(0)
 
 for alpha, n in ((1.0, 48), (1.0, 160), (0.0, 48)):
-    for env in ({"RT355_TLAS_BACKUP": "1"}, {"RT355_TLAS_BACKUP": "0"}, {"RT355_TLAS_BACKUP": "0", "RT355_NO_SPILL": "1"}, {"RT355_TLAS_BACKUP": "1", "RT355_NO_SPILL": "1"}):
+    for env in ({}, {"RT355_NO_SPILL": "1"}):
         print(env, flush=True)
         subprocess.run([sys.executable, __file__, "child", str(alpha), str(n)], env=dict(os.environ, **env))
