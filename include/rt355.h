@@ -147,6 +147,26 @@ int rt_share_scene(RtCtx* ctx, RtCtx* from);
 int rt_build_bvh2(int32_t device, const RtBuildOptions* opts, const RtPrimitive* prims, int32_t nPrims, int32_t first, int32_t count,
                   uint32_t nodeBase, uint32_t idxBase, RtBVHNode2* nodes, int32_t nodeCap, int32_t* nNodes, uint32_t* primIdx,
                   RtBuildStats* stats);
+/* The default SAH BLAS on the GPU: BVH2::BuildBLAS with alpha = 1 (binned SAH, object splits only; rt355_host.h rth_build_blas)
+ * over the primitives [first, first + count) of prims[nPrims], on `device`.  Its nodes and primIdx equal, byte for byte, what
+ * BuildBLAS(startIdx = first) appends when first + count == nPrims and nodeBase / idxBase are the scene's node and primIdx counts:
+ * the root is node nodeBase, the r-th interior node in BuildBLAS's LIFO pop order (right child popped first) has its children at
+ * nodeBase + 1 + 2r and nodeBase + 2 + 2r, leaves take primIdx[idxBase + o, + count) in pop order, at most 2 * count - 1 nodes.
+ * The rules live in csrc/sah_common.h; the host restatement rth_build_bvh2_sah (rt355_host.h) gives the same arrays.  Any depth.
+ * Synchronous, on a stream of its own; the caller's device is restored.  stats: nodes, leaves, depth (BVH2::Depth), sah_cost
+ * (BVH2::TotalCost, identical), morton_bits 0, device_ms, wall_ms; may be NULL.
+ * Refusals write nothing to the caller's arrays:
+ *   RT_E_INVALID      the argument checks of rt_build_bvh2 (count <= 0 or > 2^30, range outside nPrims, nodeCap < 2 * count - 1,
+ *                     ids overflowing 32 bits, a missing array, a bad device);
+ *   RT_E_UNSUPPORTED  inputs on which BuildBLAS has no defined result: a primitive box or centroid that is not finite; a node
+ *                     whose bin index would be computed from a NaN or an infinity (a centroid extent that overflows, or one so
+ *                     small that 8 / extent overflows); a node of more than RT_MIN_LEAF_PRIMS refs with no leaf decision and no
+ *                     object split below RT_REALLYFAR (node areas near 1e30: coordinates of about 1e15 and beyond). */
+int rt_build_bvh2_sah(int32_t device, const RtPrimitive* prims, int32_t nPrims, int32_t first, int32_t count, uint32_t nodeBase,
+                      uint32_t idxBase, RtBVHNode2* nodes, int32_t nodeCap, int32_t* nNodes, uint32_t* primIdx, RtBuildStats* stats);
+/* Wall-clock split of this process's last successful rt_build_bvh2_sah (measurement aid, tools/sah_gpu_bench.py): out[0] allocation
+ * and upload, out[1] the level passes, out[2] numbering and emit, out[3] download (ms), out[4] the number of level passes. */
+int rt_debug_sah_phases(float* out);
 
 /* ---- in-place scene updates (animation) ----------------------------------------------------------------------------------------
  * What Renderer::Tick's disabled animation hook (renderer.cpp:29-37: scene.Animate, tlas->Build, the node buffers' CopyToDevice) needs,

@@ -82,7 +82,7 @@ DEVICE_SYMBOLS = [
     "rt_read_accum", "rt_write_accum", "rt_postproc", "rt_read_counters", "rt_reset_counters", "rt_read_stage_times", "rt_reset_stage_times", "rt_set_profile",
     "rt_stage_begin_frame", "rt_stage_generate", "rt_stage_extend", "rt_stage_shade", "rt_stage_connect",
     "rt_debug_get_rays", "rt_debug_set_rays", "rt_debug_get_shadow", "rt_debug_enable_steps", "rt_debug_get_steps", "rt_debug_math",
-    "rt_debug_math_sweep", "rt_validate_scene", "rt_build_bvh2", "rt_update_scene", "rt_group_update_scene", "rt_debug_get_scene_array",
+    "rt_debug_math_sweep", "rt_validate_scene", "rt_build_bvh2", "rt_build_bvh2_sah", "rt_debug_sah_phases", "rt_update_scene", "rt_group_update_scene", "rt_debug_get_scene_array",
     "rt_group_create", "rt_group_destroy", "rt_group_lanes", "rt_group_concurrency", "rt_group_lane", "rt_group_frames", "rt_group_upload_scene", "rt_group_share_scene",
     "rt_group_seed", "rt_group_reset", "rt_group_render", "rt_group_synchronize", "rt_group_sum", "rt_group_read_accum", "rt_group_focus",
     "rt_group_postproc"]
@@ -94,7 +94,8 @@ HOST_SYMBOLS = [
     "rth_renderer_create", "rth_renderer_destroy", "rth_renderer_init", "rth_renderer_set_camera", "rth_renderer_tick",
     "rth_renderer_read", "rth_renderer_camera", "rth_seed_stream", "rth_load_model", "rth_save_png",
     "rth_set_build_threads", "rth_renderer_save_frame", "rth_renderer_camera_move", "rth_renderer_camera_mouse", "rth_renderer_camera_zoom", "rth_renderer_frames", "rth_renderer_set_lanes",
-    "rth_build_blas_lbvh", "rth_build_bvh2_lbvh", "rth_lbvh_stats", "rth_set_primitives", "rth_refit"]
+    "rth_build_blas_lbvh", "rth_build_bvh2_lbvh", "rth_lbvh_stats", "rth_set_primitives", "rth_refit",
+    "rth_build_blas_sah_gpu", "rth_build_bvh2_sah"]
 
 _dev = None
 _host = None
@@ -176,6 +177,8 @@ def _bind_device(lib):
         lib.rt_debug_math_sweep.argtypes = [i32, i32, i32, vp]
         lib.rt_validate_scene.argtypes = [i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32]
         lib.rt_build_bvh2.argtypes = [i32, vp, vp, i32, i32, i32, C.c_uint32, C.c_uint32, vp, i32, C.POINTER(i32), vp, vp]
+        lib.rt_build_bvh2_sah.argtypes = [i32, vp, i32, i32, i32, C.c_uint32, C.c_uint32, vp, i32, C.POINTER(i32), vp, vp]
+        lib.rt_debug_sah_phases.argtypes = [vp]
         lib.rt_update_scene.argtypes = [vp, vp, i32, i32, vp, i32, vp]
         lib.rt_group_update_scene.argtypes = [vp, vp, i32, i32, vp, i32, vp]
         lib.rt_debug_get_scene_array.argtypes = [vp, i32, vp, i64, C.POINTER(i64)]
@@ -224,6 +227,9 @@ def host_lib():
         lib.rth_build_bvh2_lbvh.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, vp, C.c_int32,
                                             C.POINTER(C.c_int32), vp, vp]
         lib.rth_lbvh_stats.argtypes = [vp, vp]
+        lib.rth_build_blas_sah_gpu.argtypes = [vp, i32, i32]
+        lib.rth_build_bvh2_sah.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, vp, C.c_int32,
+                                           C.POINTER(C.c_int32), vp, vp]
         lib.rth_set_primitives.argtypes = [vp, i32, i32, vp]
         lib.rth_refit.argtypes = [vp]
         lib.rth_set_build_threads.argtypes = [vp, i32]

@@ -40,11 +40,13 @@ def build_device(force=False):
     src = os.path.join(PKG, "csrc", "rt355.hip")
     lbvh = os.path.join(PKG, "csrc", "lbvh.hip")      # rt_build_bvh2: the GPU linear BVH builder
     refit = os.path.join(PKG, "csrc", "refit.hip")    # rt_update_scene: BLAS refit, derived records and TLAS rebuild on the GPU
-    deps = [src, lbvh, refit, os.path.join(PKG, "csrc", "rt355_kernels.h"), os.path.join(PKG, "csrc", "lbvh_common.h"),
-            os.path.join(PKG, "csrc", "refit_common.h"), os.path.join(ROOT, "include", "rt355.h"), os.path.join(ROOT, "include", "rt355_types.h")]
+    sah = os.path.join(PKG, "csrc", "sah.hip")        # rt_build_bvh2_sah: the default SAH BLAS built on the GPU
+    deps = [src, lbvh, refit, sah, os.path.join(PKG, "csrc", "rt355_kernels.h"), os.path.join(PKG, "csrc", "lbvh_common.h"),
+            os.path.join(PKG, "csrc", "refit_common.h"), os.path.join(PKG, "csrc", "sah_common.h"), os.path.join(ROOT, "include", "rt355.h"),
+            os.path.join(ROOT, "include", "rt355_types.h")]
     out = os.path.join(PKG, "librt355.so")
     if force or _stale(out, deps):
-        _run([HIPCC] + DEVICE_FLAGS + [src, lbvh, refit, "-o", out])
+        _run([HIPCC] + DEVICE_FLAGS + [src, lbvh, refit, sah, "-o", out])
     return out
 
 
@@ -55,14 +57,16 @@ def build_device_refb(force=False):
     src = os.path.join(PKG, "csrc", "rt355.hip")
     lbvh = os.path.join(PKG, "csrc", "lbvh.hip")      # same entry points as librt355.so (the ctypes binding declares them all)
     refit = os.path.join(PKG, "csrc", "refit.hip")
-    deps = [src, lbvh, refit, os.path.join(PKG, "csrc", "rt355_kernels.h"), os.path.join(PKG, "csrc", "lbvh_common.h"),
-            os.path.join(PKG, "csrc", "refit_common.h"), os.path.join(ROOT, "include", "rt355.h"), os.path.join(ROOT, "include", "rt355_types.h")]
+    sah = os.path.join(PKG, "csrc", "sah.hip")
+    deps = [src, lbvh, refit, sah, os.path.join(PKG, "csrc", "rt355_kernels.h"), os.path.join(PKG, "csrc", "lbvh_common.h"),
+            os.path.join(PKG, "csrc", "refit_common.h"), os.path.join(PKG, "csrc", "sah_common.h"), os.path.join(ROOT, "include", "rt355.h"),
+            os.path.join(ROOT, "include", "rt355_types.h")]
     out = os.path.join(PKG, "librt355_refb.so")
     if force or _stale(out, deps):
         # -Bsymbolic: this library defines the same global symbols as librt355.so (C-ABI entry points, the kernels' host stubs).  Loaded
         # into a process that already holds librt355.so, its own references would otherwise bind to THAT library's definitions - and
         # launch the other build's kernels
-        _run([HIPCC] + DEVICE_FLAGS + ["-DRT355_REF_BUILTINS", "-Wl,-Bsymbolic", src, lbvh, refit, "-o", out])
+        _run([HIPCC] + DEVICE_FLAGS + ["-DRT355_REF_BUILTINS", "-Wl,-Bsymbolic", src, lbvh, refit, sah, "-o", out])
     return out
 
 
@@ -70,6 +74,7 @@ def build_host(force=False):
     hdir = os.path.join(PKG, "host")
     srcs = [os.path.join(hdir, f) for f in sorted(os.listdir(hdir)) if f.endswith(".cpp")]
     deps = srcs + [os.path.join(hdir, "rt_host.h"), os.path.join(PKG, "csrc", "lbvh_common.h"), os.path.join(PKG, "csrc", "refit_common.h"),
+                   os.path.join(PKG, "csrc", "sah_common.h"),
                    os.path.join(ROOT, "include", "rt355.h"),
                    os.path.join(ROOT, "include", "rt355_host.h"), os.path.join(ROOT, "include", "rt355_types.h")]
     out = os.path.join(PKG, "librt355_host.so")

@@ -1,0 +1,443 @@
+// sah.hip — rt_build_bvh2_sah (include/rt355.h): the default SAH BLAS (BVH2::BuildBLAS with alpha = 1) built on the GPU.  The
+// formulation and every value it computes are defined in sah_common.h; this file only distributes that work over kernels.
+// host/sah_host.cpp runs the same steps in sequence (rth_build_bvh2_sah); both equal BuildBLAS's arrays byte for byte.
+//
+// Per level (the open nodes are the build ids [lb, le); a position p of the ref arrays belongs to node nid[p] or to none):
+//   k_sah_reduce    node-bounds and centroid-bounds keys of the open nodes (LDS slots per workgroup, then 64-bit atomicMin / Max)
+//   k_sah_bins      bin counts and bin-box keys per (open node, axis, bin), the same way; flags a NaN / infinite bin index
+//   k_sah_decide    one thread per open node: the sweep and the decision
+//   k_sah_small     one thread per small node: its whole subtree (build_small)
+//   k_sah_flag      partition flags; hipcub::DeviceScan gives each ref its rank among the refs going left
+//   k_sah_count     forced leaves, the children's contribution to the scan that places them; k_sah_children writes them
+//   k_sah_scatter   the stable partition of every split segment into the other ref array (other positions are copied)
+// The host reads back three words per level (splits, open children, status).  Then, with kernel boundaries between levels:
+//   k_sah_up        interior counts, heights and TotalCost bottom-up; k_sah_down: pop ranks, ref offsets, output ids top-down
+//   k_sah_emit      RtBVHNode2 records (level part and small subtrees); k_sah_emit_refs: primIdx
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+#include <chrono>
+#include <cstdarg>
+#include <cstdio>
+#include <utility>
+#include <vector>
+#include "../../include/rt355.h"
+#include "sah_common.h"
+
+using namespace sah;
+
+int rt355_set_error(int code, const char* msg);   // rt355.hip: sets the text rt_last_error() returns
+
+namespace {
+
+constexpr int kBlock = 256;
+constexpr int kSlots = 16;   // open nodes a workgroup's positions can meet: each holds > kSmall refs
+static_assert(kBlock / (kSmall + 1) + 2 <= kSlots, "a workgroup's kBlock positions meet at most kSlots open nodes");
+constexpr int kCnt = 3 * kBins;                     // bin counts per open node
+constexpr int kKeys = 6 + kBinKeys;                 // 64-bit keys per open node and fold direction
+
+// phases of the last build, for rt_debug_sah_phases: upload, level passes, numbering + emit, download (ms), levels
+float g_phases[5] = { 0, 0, 0, 0, 0 };
+
+__device__ inline void lds_min(uint64_t* p, uint64_t v) { __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+__device__ inline void lds_max(uint64_t* p, uint64_t v) { __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+__device__ inline void glb_min(uint64_t* p, uint64_t v) { __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ inline void glb_max(uint64_t* p, uint64_t v) { __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__global__ void __launch_bounds__(kBlock) k_sah_prims(const RtPrimitive* prims, uint32_t n, Prim* P, uint32_t* cur, uint32_t* nid,
+                                                      uint32_t* owner, uint32_t* status)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const Prim d = prim_data(prims[i]);
+    P[i] = d;
+    cur[i] = i; nid[i] = 0; owner[i] = kNone;
+    if (!prim_finite(d)) atomicOr(status, kBadInput);
+}
+
+// rank among the level's open nodes of the node that holds position p, or kNone
+__device__ inline uint32_t open_rank(const uint32_t* nid, const BNode* bn, uint32_t p, uint32_t n)
+{
+    if (p >= n) return kNone;
+    const uint32_t id = nid[p];
+    if (id == kNone) return kNone;
+    return bn[id].kind == kOpen ? bn[id].big : kNone;
+}
+
+__global__ void __launch_bounds__(kBlock) k_sah_reduce(const Prim* P, const uint32_t* cur, const uint32_t* nid, const BNode* bn, uint32_t n,
+                                                       uint64_t* kmin, uint64_t* kmax, uint32_t* status)
+{
+    __shared__ uint64_t smin[kSlots * 6], smax[kSlots * 6];
+    __shared__ uint32_t sfirst;
+    for (int t = threadIdx.x; t < kSlots * 6; t += kBlock) { smin[t] = kKeyMinEmpty; smax[t] = kKeyMaxEmpty; }
+    if (threadIdx.x == 0) sfirst = kNone;
+    __syncthreads();
+    const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t br = open_rank(nid, bn, p, n);
+    if (br != kNone) atomicMin(&sfirst, br);
+    __syncthreads();
+    if (br != kNone) {
+        const uint32_t slot = br - sfirst;
+        if (slot >= (uint32_t)kSlots) atomicOr(status, kInternal);
+        else {
+            const uint32_t i = cur[p];
+            uint64_t km[6], kx[6];
+            node_keys(P[i], i, km, kx);
+            for (int j = 0; j < 6; j++) { lds_min(&smin[slot * 6 + j], km[j]); lds_max(&smax[slot * 6 + j], kx[j]); }
+        }
+    }
+    __syncthreads();
+    if (sfirst == kNone) return;
+    for (int t = threadIdx.x; t < kSlots * 6; t += kBlock) {   // touched slots only: their ranks are < the level's open nodes
+        if (smin[t] != kKeyMinEmpty) glb_min(&kmin[sfirst * 6 + t], smin[t]);
+        if (smax[t] != kKeyMaxEmpty) glb_max(&kmax[sfirst * 6 + t], smax[t]);
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) k_sah_bins(const Prim* P, const uint32_t* cur, const uint32_t* nid, const BNode* bn, uint32_t n,
+                                                     const uint64_t* kmin, const uint64_t* kmax, uint64_t* bkmin, uint64_t* bkmax,
+                                                     uint32_t* bcnt, uint32_t* status)
+{
+    __shared__ uint64_t smin[kSlots * kBinKeys], smax[kSlots * kBinKeys];
+    __shared__ uint32_t scnt[kSlots * kCnt];
+    __shared__ uint32_t sfirst;
+    for (int t = threadIdx.x; t < kSlots * kBinKeys; t += kBlock) { smin[t] = kKeyMinEmpty; smax[t] = kKeyMaxEmpty; }
+    for (int t = threadIdx.x; t < kSlots * kCnt; t += kBlock) scnt[t] = 0;
+    if (threadIdx.x == 0) sfirst = kNone;
+    __syncthreads();
+    const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+    const uint32_t br = open_rank(nid, bn, p, n);
+    if (br != kNone) atomicMin(&sfirst, br);
+    __syncthreads();
+    if (br != kNone) {
+        const uint32_t slot = br - sfirst;
+        if (slot >= (uint32_t)kSlots) atomicOr(status, kInternal);
+        else {
+            const uint32_t i = cur[p];
+            const Prim d = P[i];
+            float mn[3], mx[3], cmin[3], cmax[3];
+            node_from_keys(kmin + br * 6, kmax + br * 6, mn, mx, cmin, cmax);
+            for (int a = 0; a < 3; a++) {
+                if (cmin[a] == cmax[a]) continue;
+                int b;
+                if (!bin_of(d.c[a], cmin[a], cmax[a], b)) { atomicOr(status, kBadBin); continue; }
+                const int s = a * kBins + b;
+                atomicAdd(&scnt[slot * kCnt + s], 1u);
+                for (int k = 0; k < 3; k++) {
+                    lds_min(&smin[slot * kBinKeys + s * 3 + k], key_min(d.mn[k], i));
+                    lds_max(&smax[slot * kBinKeys + s * 3 + k], key_max(d.mx[k], i));
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (sfirst == kNone) return;
+    for (int t = threadIdx.x; t < kSlots * kBinKeys; t += kBlock) {
+        if (smin[t] != kKeyMinEmpty) glb_min(&bkmin[sfirst * kBinKeys + t], smin[t]);
+        if (smax[t] != kKeyMaxEmpty) glb_max(&bkmax[sfirst * kBinKeys + t], smax[t]);
+    }
+    for (int t = threadIdx.x; t < kSlots * kCnt; t += kBlock)
+        if (scnt[t]) atomicAdd(&bcnt[sfirst * kCnt + t], scnt[t]);
+}
+
+__global__ void __launch_bounds__(kBlock) k_sah_decide(BNode* bn, uint32_t lb, uint32_t le, const uint64_t* kmin, const uint64_t* kmax,
+                                                       const uint64_t* bkmin, const uint64_t* bkmax, const uint32_t* bcnt, uint32_t* status)
+{
+    const uint32_t id = lb + blockIdx.x * kBlock + threadIdx.x;
+    if (id >= le) return;
+    BNode N = bn[id];
+    if (N.kind != kOpen) return;
+    float cmin[3], cmax[3];
+    node_from_keys(kmin + N.big * 6, kmax + N.big * 6, N.mn, N.mx, cmin, cmax);
+    Bins B;
+    bins_from_keys(bkmin + (size_t)N.big * kBinKeys, bkmax + (size_t)N.big * kBinKeys, bcnt + (size_t)N.big * kCnt, B);
+    Decision d;
+    if (!decide(N.cnt, N.mn, N.mx, cmin, cmax, B, d)) { atomicOr(status, kNoDecision); return; }
+    apply_decision(N, d);
+    bn[id] = N;
+}
+
+__global__ void __launch_bounds__(kBlock) k_sah_small(const Prim* P, const uint32_t* cur, BNode* bn, uint32_t lb, uint32_t le, uint32_t* sA,
+                                                      uint32_t* sB, uint32_t* sout, LNode* snodes, uint32_t* status)
+{
+    const uint32_t id = lb + blockIdx.x * kBlock + threadIdx.x;
+    if (id >= le) return;
+    BNode& N = bn[id];
+    if (N.kind != kSmallRoot) return;
+    const uint32_t h = N.home;
+    for (uint32_t j = 0; j < N.cnt; j++) sA[h + j] = cur[h + j];
+    SubResult r;
+    const int rc = build_small(P, sA + h, sB + h, N.cnt, sout + h, snodes + 2 * (size_t)h, r);
+    if (rc) { atomicOr(status, rc == kErrBin ? kBadBin : kNoDecision); return; }
+    apply_small(N, snodes[2 * (size_t)h], r);
+}
+
+__global__ void __launch_bounds__(kBlock) k_sah_flag(const Prim* P, const uint32_t* cur, const uint32_t* nid, const BNode* bn, uint32_t n,
+                                                     uint32_t* f)
+{
+    const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+    if (p > n) return;
+    uint32_t v = 0;
+    if (p < n && nid[p] != kNone) {
+        const BNode& N = bn[nid[p]];
+        if (N.kind == kSplit) v = goes_left(P[cur[p]], N.axis, N.pos) ? 1 : 0;
+    }
+    f[p] = v;
+}
+
+__global__ void __launch_bounds__(kBlock) k_sah_count(BNode* bn, uint32_t lb, uint32_t le, const uint32_t* F, uint64_t* v)
+{
+    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+    if (lb + t >= le) return;
+    BNode& N = bn[lb + t];
+    v[t] = N.kind == kSplit ? count_split(N, F[N.home + N.cnt] - F[N.home]) : 0;
+}
+
+__global__ void __launch_bounds__(kBlock) k_sah_children(BNode* bn, uint32_t lb, uint32_t le, uint32_t cap, const uint64_t* v,
+                                                         const uint64_t* V, uint32_t* summary)
+{
+    const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+    if (lb + t >= le) return;
+    if (lb + t == le - 1) { const uint64_t all = V[t] + v[t]; summary[0] = (uint32_t)all; summary[1] = (uint32_t)(all >> 32); }
+    BNode& N = bn[lb + t];
+    if (N.kind != kSplit) return;
+    BNode L, R;
+    make_children(N, V[t], le, L, R);
+    if (N.left + 1 >= cap) { atomicOr(&summary[2], kInternal); return; }
+    bn[N.left] = L;
+    bn[N.left + 1] = R;
+}
+
+__global__ void __launch_bounds__(kBlock) k_sah_scatter(const uint32_t* cur, const uint32_t* nid, const BNode* bn, uint32_t n,
+                                                        const uint32_t* f, const uint32_t* F, uint32_t* nxt, uint32_t* nidN, uint32_t* owner)
+{
+    const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+    if (p >= n) return;
+    const uint32_t id = nid[p];
+    if (id == kNone) { nxt[p] = cur[p]; nidN[p] = kNone; return; }
+    const BNode& N = bn[id];
+    if (N.kind == kSplit) {
+        const bool left = f[p] != 0;
+        const uint32_t dst = scatter_dst(N, p, F[p] - F[N.home], left);   // inside [home, home + cnt): a permutation of it
+        nxt[dst] = cur[p];
+        nidN[dst] = left ? N.left : N.left + 1;
+    } else {
+        nxt[p] = cur[p]; nidN[p] = kNone; owner[p] = id;
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) k_sah_up(BNode* bn, uint32_t lb, uint32_t le)
+{
+    const uint32_t id = lb + blockIdx.x * kBlock + threadIdx.x;
+    if (id >= le || bn[id].kind != kSplit) return;
+    const uint32_t l = bn[id].left;
+    up(bn[id], bn[l], bn[l + 1]);
+}
+
+__global__ void __launch_bounds__(kBlock) k_sah_down(BNode* bn, uint32_t lb, uint32_t le)
+{
+    const uint32_t id = lb + blockIdx.x * kBlock + threadIdx.x;
+    if (id >= le || bn[id].kind != kSplit) return;
+    const uint32_t l = bn[id].left;
+    down(bn[id], bn[l], bn[l + 1]);
+}
+
+__global__ void __launch_bounds__(kBlock) k_sah_emit(const BNode* bn, uint32_t total, const LNode* snodes, uint32_t nodeBase,
+                                                     uint32_t idxBase, RtBVHNode2* nodes, uint32_t outCap, uint32_t* status)
+{
+    const uint32_t id = blockIdx.x * kBlock + threadIdx.x;
+    if (id >= total) return;
+    const BNode& N = bn[id];
+    if (N.kind != kSmallRoot) {
+        if (N.gid >= outCap) { atomicOr(status, kInternal); return; }
+        nodes[N.gid] = emit_level(N, nodeBase, idxBase);
+        return;
+    }
+    for (uint32_t j = 0; j < 2 * N.interiors + 1; j++) {
+        const uint32_t o = small_index(N, j);
+        if (o >= outCap || j >= 2 * N.cnt - 1) { atomicOr(status, kInternal); return; }
+        nodes[o] = emit_small(N, snodes[2 * (size_t)N.home + j], nodeBase, idxBase);
+    }
+}
+
+__global__ void __launch_bounds__(kBlock) k_sah_emit_refs(const BNode* bn, const uint32_t* owner, const uint32_t* cur, const uint32_t* sout,
+                                                          uint32_t n, uint32_t first, uint32_t* primIdx, uint32_t* status)
+{
+    const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
+    if (p >= n) return;
+    const uint32_t o = owner[p];
+    if (o == kNone) { atomicOr(status, kInternal); return; }
+    const BNode& N = bn[o];
+    const uint32_t dst = N.offset + (p - N.home);
+    if (dst >= n) { atomicOr(status, kInternal); return; }
+    primIdx[dst] = first + (N.kind == kSmallRoot ? sout[p] : cur[p]);
+}
+
+int sfail(int code, const char* fmt, ...)   // the message goes to rt_last_error()
+{
+    char buf[512];
+    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
+    return rt355_set_error(code, buf);
+}
+
+size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
+dim3 grid(uint32_t threads) { return dim3((threads + kBlock - 1) / kBlock); }
+double ms_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
+
+// Everything one build allocates on the device; freed on every exit path.
+struct Work {
+    void* mem = nullptr;
+    hipStream_t stream = nullptr;
+    hipEvent_t ev[2] = { nullptr, nullptr };
+    int prevDevice = -1;                      // the caller's current device, restored on the way out
+    ~Work()
+    {
+        if (stream) (void)hipStreamSynchronize(stream);
+        if (mem) (void)hipFree(mem);
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        if (stream) (void)hipStreamDestroy(stream);
+        if (prevDevice >= 0) (void)hipSetDevice(prevDevice);
+    }
+};
+
+} // namespace
+
+#define SCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
+    return sfail(RT_E_DEVICE, "rt_build_bvh2_sah: %s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
+
+extern "C" int rt_debug_sah_phases(float* out)
+{
+    if (!out) return RT_E_INVALID;
+    for (int i = 0; i < 5; i++) out[i] = g_phases[i];
+    return RT_OK;
+}
+
+extern "C" int rt_build_bvh2_sah(int32_t device, const RtPrimitive* prims, int32_t nPrims, int32_t first, int32_t count, uint32_t nodeBase,
+                                 uint32_t idxBase, RtBVHNode2* nodes, int32_t nodeCap, int32_t* nNodes, uint32_t* primIdx, RtBuildStats* stats)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    if (const char* msg = check_args(prims, nPrims, first, count, nodeBase, idxBase, nodes, nodeCap, nNodes, primIdx))
+        return sfail(RT_E_INVALID, "rt_build_bvh2_sah: %s", msg);
+    int nDev = 0;
+    if (hipGetDeviceCount(&nDev) != hipSuccess || nDev <= 0) return sfail(RT_E_DEVICE, "rt_build_bvh2_sah: no HIP device");
+    if (device < 0 || device >= nDev) return sfail(RT_E_INVALID, "rt_build_bvh2_sah: device %d out of range (%d devices)", device, nDev);
+    Work w;
+    SCHK(hipGetDevice(&w.prevDevice));
+    SCHK(hipSetDevice(device));
+    SCHK(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
+    SCHK(hipEventCreate(&w.ev[0]));
+    SCHK(hipEventCreate(&w.ev[1]));
+
+    const uint32_t n = (uint32_t)count, cap = 2 * n - 1, bigMax = n / (kSmall + 1) + 1;
+    size_t scan32 = 0, scan64 = 0;
+    SCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan32, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)(n + 1), w.stream));
+    SCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan64, (uint64_t*)nullptr, (uint64_t*)nullptr, (int)cap, w.stream));
+    size_t scanBytes = scan32 > scan64 ? scan32 : scan64;
+
+    // one allocation, carved
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { const size_t o = off; off += align_up(bytes); return o; };
+    const size_t oSum = carve(4 * sizeof(uint32_t)), oPrim = carve(n * sizeof(RtPrimitive)), oP = carve(n * sizeof(Prim));
+    const size_t oCur = carve(n * 4ull), oNxt = carve(n * 4ull), oNid = carve(n * 4ull), oNidN = carve(n * 4ull), oOwn = carve(n * 4ull);
+    const size_t of = carve((n + 1) * 4ull), oF = carve((n + 1) * 4ull), oSA = carve(n * 4ull), oSB = carve(n * 4ull), oSout = carve(n * 4ull);
+    const size_t oSn = carve(2ull * n * sizeof(LNode)), oBn = carve((size_t)cap * sizeof(BNode)), ov = carve(cap * 8ull), oV = carve(cap * 8ull);
+    const size_t oKA = carve((size_t)bigMax * kKeys * 8), oKB = carve((size_t)bigMax * (kKeys * 8 + kCnt * 4));
+    const size_t oNodes = carve((size_t)cap * sizeof(RtBVHNode2)), oIdx = carve(n * 4ull), oScan = carve(scanBytes);
+    if (hipMalloc(&w.mem, off) != hipSuccess) { w.mem = nullptr; return sfail(RT_E_NOMEM, "rt_build_bvh2_sah: %zu bytes of device memory", off); }
+    char* base = (char*)w.mem;
+    auto at = [&](size_t o) { return (void*)(base + o); };
+    uint32_t* summary = (uint32_t*)at(oSum);
+    RtPrimitive* dPrims = (RtPrimitive*)at(oPrim);
+    Prim* P = (Prim*)at(oP);
+    uint32_t *cur = (uint32_t*)at(oCur), *nxt = (uint32_t*)at(oNxt), *nid = (uint32_t*)at(oNid), *nidN = (uint32_t*)at(oNidN);
+    uint32_t *owner = (uint32_t*)at(oOwn), *f = (uint32_t*)at(of), *F = (uint32_t*)at(oF);
+    uint32_t *sA = (uint32_t*)at(oSA), *sB = (uint32_t*)at(oSB), *sout = (uint32_t*)at(oSout);
+    LNode* snodes = (LNode*)at(oSn);
+    BNode* bn = (BNode*)at(oBn);
+    uint64_t *v = (uint64_t*)at(ov), *V = (uint64_t*)at(oV), *keysA = (uint64_t*)at(oKA), *keysB = (uint64_t*)at(oKB);
+    RtBVHNode2* dNodes = (RtBVHNode2*)at(oNodes);
+    uint32_t* dIdx = (uint32_t*)at(oIdx);
+    const double tAlloc = ms_since(t0);
+
+    const BNode root = open_node(0, n, 0);
+    SCHK(hipMemcpyAsync(dPrims, prims + first, n * sizeof(RtPrimitive), hipMemcpyHostToDevice, w.stream));
+    SCHK(hipMemcpyAsync(bn, &root, sizeof root, hipMemcpyHostToDevice, w.stream));
+    SCHK(hipMemsetAsync(summary, 0, 4 * sizeof(uint32_t), w.stream));
+    SCHK(hipEventRecord(w.ev[0], w.stream));
+    hipLaunchKernelGGL(k_sah_prims, grid(n), dim3(kBlock), 0, w.stream, dPrims, n, P, cur, nid, owner, summary + 2);
+    SCHK(hipGetLastError());
+    uint32_t hs[4] = { 0, 0, 0, 0 };
+    SCHK(hipMemcpyAsync(hs, summary, sizeof hs, hipMemcpyDeviceToHost, w.stream));
+    SCHK(hipStreamSynchronize(w.stream));   // the host arrays are the caller's: nothing of them is read after this point
+    if (hs[2]) return sfail(RT_E_UNSUPPORTED, "rt_build_bvh2_sah: %s", status_text(hs[2]));
+    const double tUpload = ms_since(t0) - tAlloc;
+
+    // level passes
+    std::vector<std::pair<uint32_t, uint32_t>> levels;
+    uint32_t lb = 0, le = 1, nBig = n > kSmall ? 1 : 0;
+    for (;;) {
+        levels.emplace_back(lb, le);
+        const uint32_t K = le - lb;
+        uint64_t *kmin = keysA, *bkmin = keysA + (size_t)nBig * 6, *kmax = keysB, *bkmax = keysB + (size_t)nBig * 6;
+        uint32_t* bcnt = (uint32_t*)(keysB + (size_t)nBig * kKeys);
+        if (nBig) {
+            SCHK(hipMemsetAsync(keysA, 0xff, (size_t)nBig * kKeys * 8, w.stream));
+            SCHK(hipMemsetAsync(keysB, 0, (size_t)nBig * (kKeys * 8 + kCnt * 4), w.stream));
+            hipLaunchKernelGGL(k_sah_reduce, grid(n), dim3(kBlock), 0, w.stream, P, cur, nid, bn, n, kmin, kmax, summary + 2);
+            hipLaunchKernelGGL(k_sah_bins, grid(n), dim3(kBlock), 0, w.stream, P, cur, nid, bn, n, kmin, kmax, bkmin, bkmax, bcnt, summary + 2);
+        }
+        hipLaunchKernelGGL(k_sah_decide, grid(K), dim3(kBlock), 0, w.stream, bn, lb, le, kmin, kmax, bkmin, bkmax, bcnt, summary + 2);
+        hipLaunchKernelGGL(k_sah_small, grid(K), dim3(kBlock), 0, w.stream, P, cur, bn, lb, le, sA, sB, sout, snodes, summary + 2);
+        hipLaunchKernelGGL(k_sah_flag, grid(n + 1), dim3(kBlock), 0, w.stream, P, cur, nid, bn, n, f);
+        SCHK(hipcub::DeviceScan::ExclusiveSum(at(oScan), scanBytes, f, F, (int)(n + 1), w.stream));
+        hipLaunchKernelGGL(k_sah_count, grid(K), dim3(kBlock), 0, w.stream, bn, lb, le, F, v);
+        SCHK(hipcub::DeviceScan::ExclusiveSum(at(oScan), scanBytes, v, V, (int)K, w.stream));
+        hipLaunchKernelGGL(k_sah_children, grid(K), dim3(kBlock), 0, w.stream, bn, lb, le, cap, v, V, summary);
+        hipLaunchKernelGGL(k_sah_scatter, grid(n), dim3(kBlock), 0, w.stream, cur, nid, bn, n, f, F, nxt, nidN, owner);
+        SCHK(hipGetLastError());
+        std::swap(cur, nxt);
+        std::swap(nid, nidN);
+        SCHK(hipMemcpyAsync(hs, summary, sizeof hs, hipMemcpyDeviceToHost, w.stream));
+        SCHK(hipStreamSynchronize(w.stream));
+        if (hs[2]) return sfail(RT_E_UNSUPPORTED, "rt_build_bvh2_sah: %s", status_text(hs[2]));
+        if (hs[0] == 0) break;
+        if ((uint64_t)le + 2ull * hs[0] > cap || hs[1] > bigMax)
+            return sfail(RT_E_DEVICE, "rt_build_bvh2_sah: inconsistent device result (%u splits, %u open nodes)", hs[0], hs[1]);
+        lb = le; le += 2 * hs[0]; nBig = hs[1];
+    }
+    const double tLevels = ms_since(t0) - tAlloc - tUpload;
+
+    // numbering and emit
+    for (size_t l = levels.size(); l-- > 0;)
+        hipLaunchKernelGGL(k_sah_up, grid(levels[l].second - levels[l].first), dim3(kBlock), 0, w.stream, bn, levels[l].first, levels[l].second);
+    for (const auto& L : levels)
+        hipLaunchKernelGGL(k_sah_down, grid(L.second - L.first), dim3(kBlock), 0, w.stream, bn, L.first, L.second);
+    const uint32_t total = levels.back().second;
+    hipLaunchKernelGGL(k_sah_emit, grid(total), dim3(kBlock), 0, w.stream, bn, total, snodes, nodeBase, idxBase, dNodes, cap, summary + 2);
+    hipLaunchKernelGGL(k_sah_emit_refs, grid(n), dim3(kBlock), 0, w.stream, bn, owner, cur, sout, n, (uint32_t)first, dIdx, summary + 2);
+    SCHK(hipGetLastError());
+    SCHK(hipEventRecord(w.ev[1], w.stream));
+    BNode top;
+    SCHK(hipMemcpyAsync(&top, bn, sizeof top, hipMemcpyDeviceToHost, w.stream));
+    SCHK(hipMemcpyAsync(hs, summary, sizeof hs, hipMemcpyDeviceToHost, w.stream));
+    SCHK(hipStreamSynchronize(w.stream));
+    const uint32_t outNodes = 2 * top.interiors + 1;
+    if (hs[2] || outNodes > cap)
+        return sfail(RT_E_DEVICE, "rt_build_bvh2_sah: inconsistent device result (%s, %u nodes)", status_text(hs[2]), outNodes);
+    const double tNumber = ms_since(t0) - tAlloc - tUpload - tLevels;
+    SCHK(hipMemcpyAsync(nodes, dNodes, outNodes * sizeof(RtBVHNode2), hipMemcpyDeviceToHost, w.stream));
+    SCHK(hipMemcpyAsync(primIdx, dIdx, n * sizeof(uint32_t), hipMemcpyDeviceToHost, w.stream));
+    SCHK(hipStreamSynchronize(w.stream));
+    *nNodes = (int32_t)outNodes;
+    const double tDownload = ms_since(t0) - tAlloc - tUpload - tLevels - tNumber;
+    g_phases[0] = (float)(tAlloc + tUpload); g_phases[1] = (float)tLevels; g_phases[2] = (float)tNumber; g_phases[3] = (float)tDownload;
+    g_phases[4] = (float)levels.size();
+    if (stats) {
+        float ms = 0;
+        SCHK(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
+        stats->nodes = (int32_t)outNodes; stats->leaves = (int32_t)top.interiors + 1; stats->depth = (int32_t)top.depth;
+        stats->morton_bits = 0; stats->sah_cost = top.cost; stats->device_ms = ms;
+        stats->wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        stats->_reserved = 0;
+    }
+    return RT_OK;
+}

@@ -68,6 +68,10 @@ public:
     // leaves everything unchanged when the build is refused.
     void     BuildBLASLBVH(int startIdx, int device, const RtBuildOptions* opt);
     RtBuildStats lastLbvh{};     // statistics of the last BuildBLASLBVH
+    // The GPU build of BuildBLAS with alpha = 1 (csrc/sah_common.h) over primitives [startIdx, end): appends exactly what
+    // BuildBLAS(alpha = 1) appends.  device >= 0: rt_build_bvh2_sah on that GPU; -1: the host restatement.  Throws LbvhError and
+    // leaves everything unchanged when the build is refused.
+    void     BuildBLASSAHGPU(int startIdx, int device);
     int      buildThreads = 1;   // > 1: subtrees are built by parallel tasks, then numbered in the reference's LIFO order (same arrays)
     uint32_t Depth(uint32_t nodeIdx) const;
     uint32_t Count(uint32_t nodeIdx) const;
@@ -102,6 +106,10 @@ struct LbvhError : std::runtime_error { int code; LbvhError(int c, const std::st
 int LbvhBuildHost(const RtBuildOptions* opt, const RtPrimitive* prims, int32_t nPrims, int32_t first, int32_t count, uint32_t nodeBase,
                   uint32_t idxBase, RtBVHNode2* nodes, int32_t nodeCap, int32_t* nNodes, uint32_t* primIdx, RtBuildStats* stats,
                   std::string& err);
+
+// The GPU SAH build's sequential host restatement (rth_build_bvh2_sah); err receives the message of a refused call.
+int SahBuildHost(const RtPrimitive* prims, int32_t nPrims, int32_t first, int32_t count, uint32_t nodeBase, uint32_t idxBase,
+                 RtBVHNode2* nodes, int32_t nodeCap, int32_t* nNodes, uint32_t* primIdx, RtBuildStats* stats, std::string& err);
 
 // In-place updates (refit_host.cpp, the host restatement of rt_update_scene): replace primitives keeping objType / matIdx, then refit
 // every BLAS by the rules of csrc/refit_common.h; err receives why a call is refused (RT_E_* returned, nothing changed).

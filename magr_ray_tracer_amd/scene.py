@@ -129,7 +129,9 @@ class Scene:
         builder="sah" (default): the reference's binned SAH / SBVH builder; threads > 1: task-parallel build, numbered afterwards in
         the reference's LIFO order (identical arrays).
         builder="lbvh": the linear BVH builder (rt_build_bvh2) on HIP device `device`, or its host restatement when device is None
-        (identical arrays); lbvh_options: max_leaf, cost_traverse, cost_intersect.  It has no spatial splits: alpha must stay 1."""
+        (identical arrays); lbvh_options: max_leaf, cost_traverse, cost_intersect.  It has no spatial splits: alpha must stay 1.
+        builder="sah_gpu": builder="sah" with alpha 1, built on HIP device `device` (rt_build_bvh2_sah) or by its host restatement
+        when device is None; the arrays equal builder="sah"'s byte for byte.  alpha and threads must stay 1."""
         if builder == "sah":
             if lbvh_options:
                 raise ValueError(f"options {sorted(lbvh_options)} apply to builder='lbvh' only")
@@ -140,8 +142,16 @@ class Scene:
                 raise ValueError("builder='lbvh' has no spatial splits: alpha must be 1")
             opts = build_options(**lbvh_options)
             self._chk(self._lib.rth_build_blas_lbvh(self._h, int(startIdx), -1 if device is None else int(device), _lib.ptr(opts)))
+        elif builder == "sah_gpu":
+            if lbvh_options:
+                raise ValueError(f"options {sorted(lbvh_options)} apply to builder='lbvh' only")
+            if alpha != 1.0:
+                raise ValueError("builder='sah_gpu' has no spatial splits: alpha must be 1")
+            if threads != 1:
+                raise ValueError("builder='sah_gpu' takes no host threads: threads must be 1")
+            self._chk(self._lib.rth_build_blas_sah_gpu(self._h, int(startIdx), -1 if device is None else int(device)))
         else:
-            raise ValueError(f"unknown builder {builder!r} (expected 'sah' or 'lbvh')")
+            raise ValueError(f"unknown builder {builder!r} (expected 'sah', 'lbvh' or 'sah_gpu')")
 
     def lbvh_stats(self):
         """Statistics of the last builder='lbvh' BuildBLAS (RtBuildStats)."""
@@ -240,6 +250,35 @@ def build_lbvh(prims, first=0, count=None, device=None, node_base=0, idx_base=0,
         L = _lib.device_lib()
         rc = L.rt_build_bvh2(int(device), _lib.ptr(opts), _lib.ptr(p), len(p), int(first), n, int(node_base), int(idx_base), _lib.ptr(nodes),
                              cap, C.byref(written), _lib.ptr(idx), _lib.ptr(st))
+        msg = L.rt_last_error
+    if rc != 0:
+        raise BuildError(rc, msg().decode())
+    return nodes[:written.value].copy(), idx[:n].copy(), _stats_dict(st)
+
+
+def build_sah_gpu(prims, first=0, count=None, device=None, node_base=0, idx_base=0, node_cap=None, nodes=None, idx=None):
+    """BVH2::BuildBLAS with alpha 1 on a primitive array: rt_build_bvh2_sah on HIP device `device`, or its host restatement
+    (rth_build_bvh2_sah) when device is None.  Returns (nodes, primIdx, stats); raises BuildError (with .code, an RT_E_* value) when
+    the call is refused.  node_cap defaults to what the call needs (2 * count - 1).  nodes / idx: the caller's arrays to write into
+    (at least node_cap / count records), e.g. pre-filled to see that a refused call leaves them alone."""
+    p = np.ascontiguousarray(prims, dtype=_lib.Primitive)
+    n = len(p) - int(first) if count is None else int(count)
+    cap = max(2 * n - 1, 1) if node_cap is None else int(node_cap)
+    nodes = np.zeros(max(cap, 1), _lib.BVHNode2) if nodes is None else nodes
+    idx = np.zeros(max(n, 1), np.uint32) if idx is None else idx
+    if nodes.dtype != _lib.BVHNode2 or len(nodes) < cap or idx.dtype != np.uint32 or len(idx) < max(n, 1):
+        raise ValueError("nodes / idx: BVHNode2[node_cap] and uint32[count] arrays expected")
+    st = np.zeros((), _lib.BuildStats)
+    written = C.c_int32(0)
+    if device is None:
+        L = _lib.host_lib()
+        rc = L.rth_build_bvh2_sah(_lib.ptr(p), len(p), int(first), n, int(node_base), int(idx_base), _lib.ptr(nodes), cap,
+                                  C.byref(written), _lib.ptr(idx), _lib.ptr(st))
+        msg = L.rth_last_error
+    else:
+        L = _lib.device_lib()
+        rc = L.rt_build_bvh2_sah(int(device), _lib.ptr(p), len(p), int(first), n, int(node_base), int(idx_base), _lib.ptr(nodes), cap,
+                                 C.byref(written), _lib.ptr(idx), _lib.ptr(st))
         msg = L.rt_last_error
     if rc != 0:
         raise BuildError(rc, msg().decode())

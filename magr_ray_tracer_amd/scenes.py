@@ -95,7 +95,8 @@ def sponza_class(detail=1.0, alpha=1.0, builder="sah", device=0):
     """Atrium ('sponza-class'): 36 x 14 m floor, 14 m high, open roof slot with sky, two storeys of
     fluted columns carrying round arches along both long sides, ribbed walls, six hanging drapes.
     detail=1.0 gives ~262k triangles (Crytek Sponza has 262,267); the generator is RNG-free.
-    builder="lbvh": the linear BVH builder on HIP device `device` (None: its host restatement) instead of the SAH builder."""
+    builder="lbvh": the linear BVH builder on HIP device `device` (None: its host restatement) instead of the SAH builder;
+    builder="sah_gpu" (alpha 1): the SAH builder's tree built on HIP device `device` (None: its host restatement)."""
     s = Scene()
     _std_materials(s)
     d = float(detail)
@@ -274,7 +275,8 @@ def config5_scene(alpha=0.0, decimate=1, builder="sah", device=0):
     """BASELINE config 5: robo-orb (35,600 tris) + terrarium_bot (40,012 tris), each its own BLAS under a TLAS, SBVH
     alpha (0 = full spatial splits), glass on the terrarium dome.  Geometry: magr_ray_tracer_amd/assets/*.npz (converted
     from the glTF files that ship with the reference; CC-BY-4.0, see assets/ATTRIBUTION.md).
-    builder="lbvh" (alpha is then ignored): both BLAS by the linear BVH builder on HIP device `device` (None: host restatement)."""
+    builder="lbvh" (alpha is then ignored): both BLAS by the linear BVH builder on HIP device `device` (None: host restatement).
+    builder="sah_gpu" (alpha must be 1): both BLAS by the SAH builder's GPU build on `device` (None: host restatement)."""
     import os
     from . import gltf
     adir = os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets")
@@ -296,7 +298,9 @@ def config5_scene(alpha=0.0, decimate=1, builder="sah", device=0):
     place("robo_orb.npz", 1.9, (-1.5, 0.0, 0.0), {"Coat": "mirror", "Coat_2": "mirror", "Butt": "red", "material": "green"}, "white")
     s.AddQuad((-9, 0, -9), (-9, 0, 9), (9, 0, 9), (9, 0, -9), "grey")
     s.AddQuad((-1.5, 5.5, -1.5), (1.5, 5.5, -1.5), (1.5, 5.5, 1.5), (-1.5, 5.5, 1.5), "white-light")
-    blas = dict(builder="lbvh", device=device) if builder == "lbvh" else dict(alpha=alpha)
+    if builder == "sah_gpu" and alpha != 1.0:
+        raise ValueError("builder='sah_gpu' has no spatial splits: alpha must be 1")
+    blas = dict(builder=builder, device=device) if builder in ("lbvh", "sah_gpu") else dict(alpha=alpha)
     s.BuildBLAS(0, **blas)
     start = s.num_prims
     place("terrarium_bot.npz", 2.4, (1.7, 0.0, 0.0), {"glass": "white-glass", "ground": "sand", "inside": "sand", "pipes": "red"}, "white")
