@@ -193,6 +193,58 @@ typedef struct RtUpdateStats {
 } RtUpdateStats;
 int rt_update_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
                     RtUpdateStats* stats);
+/* ---- in-place rebuilds (a bound scene changes its topology without leaving the device) -------------------------------------------
+ * rt_update_scene keeps the trees and only refits their boxes; once the motion outgrows the build-time topology (vertices scrambled
+ * across triangles, a BLAS torn apart, SBVH leaves that lose their clipped boxes) the trees are valid but slow.  rt_rebuild_scene
+ * takes the same replacement records (prims / first / count and blas / nBlas as for rt_update_scene: objType, matIdx and bvhIdx
+ * must stay, only invT of an instance may differ; either may be absent) and then builds every distinct BLAS of the scene anew on
+ * the device over its own primitive range, in increasing order of the ranges and numbered the way the host appends BLAS after BLAS
+ * (nodeBase of BLAS k = the nodes of BLAS 0..k-1, idxBase likewise), with
+ *   RT_REBUILD_SAH   rt_build_bvh2_sah's tree (BVH2::BuildBLAS, alpha 1; opts ignored), or
+ *   RT_REBUILD_LBVH  rt_build_bvh2's tree (opts as there, NULL = defaults);
+ * every instance's bvhIdx becomes its BLAS's new root, the TLAS is rebuilt by TLAS::Build's rules and every derived array is
+ * produced on the device.  No node, index or record array crosses the bus; the host reads the few words per build step the builders
+ * read anyway, plus counts, depths and status.  Afterwards the arrays rt_debug_get_scene_array returns, their sizes included, are
+ * bit for bit those of a fresh rt_upload_scene of the scene built from scratch on the host from the new primitives with the same
+ * builder (rth_rebuild + rth_build_tlas, rt355_host.h), and rt_kernel_info of every holder equals the fresh context's.  The call
+ * waits for the streams of every context holding the scene (as rt_update_scene does); each holder takes the new arrays, stack size
+ * and traversal kernels before its next launch.  rt_update_scene works on the rebuilt scene (instance records handed to later calls
+ * carry the new bvhIdx: RT_SCENE_INSTANCES, or the host restatement's).  Synchronous; accumulators are not
+ * reset.  The first two rebuilds of a scene copy allocate (two sets of the arrays at capacity, which later rebuilds alternate
+ * between); the copy uploaded originally stays allocated beside them until the scene copy is freed.
+ * Refusals change nothing (the work is staged in the set that is not live; the bound scene renders exactly as before):
+ *   RT_E_INVALID      what rt_update_scene answers with it, an unknown builder, bad opts (the builder's own argument checks);
+ *   RT_E_UNSUPPORTED  a BVH4 context; a scene whose BLAS do not each cover one contiguous primitive range, ranges disjoint and in the
+ *                     order of their roots (found at rt_upload_scene; rt_blas_ranges tells beforehand), more than 256 instances or
+ *                     a TLAS not of TLAS::Build's shape; whatever the builder refuses on these primitives (rt_build_bvh2_sah);
+ *                     a new BLAS that needs more than RT_BVH4_STACK stack entries (the SAH builder makes a tree 65 levels deep
+ *                     out of thin triangles on a geometric ladder over 190 octaves; rth_rebuild refuses it by the same rule); a rebuilt TLAS deeper than RT_TLAS_STACK; and
+ *                     new trees that would change the scene's derived layout (RtKernelInfo.layout: a leaf of more than 127
+ *                     primitives - the SAH builder makes one out of 128 coincident triangles - takes layout 0 at upload).
+ *                     Not following a layout change is a deliberate limit: upload the rebuilt scene in that case. */
+#define RT_REBUILD_SAH   0
+#define RT_REBUILD_LBVH  1
+typedef struct RtRebuildStats {
+    double  gpu_ms;               /* from the first to the last GPU operation of the rebuild on its stream                     */
+    double  wall_ms;              /* the whole call                                                                            */
+    double  stage_ms, build_ms, derive_ms, tlas_ms, commit_ms;   /* split: host time until the staging copies are queued (checks and
+                                   * first-use allocation included; the copies run during build_ms), the BLAS builds (wall, their
+                                   * per-level host round trips included, as in gpu_ms), the derived arrays and the TLAS (GPU
+                                   * events), waiting for the holders and swapping the arrays (wall)                            */
+    int32_t prims, blas_built;    /* primitives replaced; BLAS built                                                           */
+    int32_t nodes, n_idx;         /* BVH2 nodes and primIdx entries of the rebuilt scene                                       */
+    int32_t max_depth;            /* height of the deepest new BLAS (edges)                                                    */
+    int32_t tlas_nodes, tlas_depth;
+    int32_t reconfigured;         /* 1: the stack size or the TLAS depth changed (the holders always take the new arrays)      */
+    int32_t reserved[2];
+} RtRebuildStats;
+int rt_rebuild_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
+                     int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats);
+/* The primitive range [first, first + count) of every instance's BLAS in wire arrays, as rt_upload_scene finds them for
+ * rt_rebuild_scene (csrc/rebuild_common.h); firstOut / countOut hold nBlas entries (either may be NULL).  RT_E_UNSUPPORTED with the
+ * reason in rt_last_error() when the scene is not of the shape rt_rebuild_scene takes.  No device needed. */
+int rt_blas_ranges(const RtBVHNode2* nodes, int32_t nNodes, const uint32_t* primIdx, int32_t nIdx, int32_t nPrims,
+                   const RtBVHInstance* blas, int32_t nBlas, int32_t* firstOut, int32_t* countOut);
 /* Device arrays of the context's scene copy, for tests: `which` is one of RT_SCENE_*.  *bytes receives the array's size; out NULL:
  * only that.  Waits for the context's stream. */
 #define RT_SCENE_PRIMS         0   /* the wire primitives                                  */
@@ -236,6 +288,8 @@ int rt_group_upload_scene(RtGroup* g,
 int rt_group_share_scene(RtGroup* g, RtGroup* from);                         /* e.g. the row bands of one frame: one device copy        */
 int rt_group_update_scene(RtGroup* g, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
                           RtUpdateStats* stats);                             /* rt_update_scene for the group's copy (all lanes)        */
+int rt_group_rebuild_scene(RtGroup* g, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
+                           int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats);   /* rt_rebuild_scene for the group's copy */
 int rt_group_seed(RtGroup* g, uint64_t firstStream);                         /* a single Renderer: 0; rank r of a sample split: r*lanes */
 int rt_group_reset(RtGroup* g);                                              /* resetKernel on every lane; frames = 0                   */
 int rt_group_render(RtGroup* g, const RtCamera* cam, const RtSettings* settings, int32_t frames);   /* `frames` in all, round-robin   */

@@ -68,6 +68,16 @@ int rth_build_bvh2_sah(const RtPrimitive* prims, int32_t nPrims, int32_t first, 
  * change nothing when refused. */
 int rth_set_primitives(RthScene* s, int first, int count, const RtPrimitive* prims);
 int rth_refit(RthScene* s);
+/* The host restatement of rt_rebuild_scene's BLAS rebuild (rt355.h): discards the scene's BVH2 and builds every distinct BLAS again
+ * over the primitive range it covers (in increasing order of the ranges, appended as BuildBLAS appends BLAS after BLAS) with the host
+ * restatement of the chosen builder: RT_REBUILD_SAH (rth_build_bvh2_sah; opts ignored) or RT_REBUILD_LBVH (rth_build_bvh2_lbvh, opts
+ * NULL = defaults).  Instance transforms stay, every bvhIdx becomes its BLAS's new root.  The caller then runs rth_build_tlas (and
+ * rth_build_bvh4).  Returns RT_E_* and changes nothing when refused (a scene whose BLAS do not cover contiguous, disjoint, ordered
+ * ranges; whatever the builder refuses). */
+int rth_rebuild(RthScene* s, int builder, const RtBuildOptions* opts);
+/* rt_blas_ranges (rt355.h) of the scene's arrays: the primitive range of every instance's BLAS; RT_E_UNSUPPORTED (rt_last_error() has
+ * the reason) when the scene is not of the shape a rebuild takes. */
+int rth_blas_ranges(RthScene* s, int32_t* firstOut, int32_t* countOut);
 int rth_build_bvh4(RthScene* s);            /* new BVH4(*bvh2) (scene.cpp:71)                    */
 int rth_build_tlas(RthScene* s);            /* new TLAS(*bvh2); Build() (renderer.cpp:12-13)     */
 /* BVH4::Convert + Collapse (bvh.cpp:695-787) on a caller-provided BVH2 node array, one BLAS rooted at node 0; out[n] */

@@ -75,6 +75,11 @@ SCENE_ARRAYS = {"prims": 0, "bvh": 1, "tlas": 2, "instances": 3, "pairs": 4, "tr
 UpdateStats = np.dtype([("gpu_ms", "<f8"), ("prims", "<i4"), ("nodes", "<i4"), ("tlas_nodes", "<i4"), ("tlas_depth", "<i4"),
                         ("reconfigured", "<i4"), ("reserved", "<i4", 3)])
 assert UpdateStats.itemsize == 40
+REBUILD_SAH, REBUILD_LBVH = 0, 1   # rt_rebuild_scene builders
+RebuildStats = np.dtype([(n, "<f8") for n in ("gpu_ms", "wall_ms", "stage_ms", "build_ms", "derive_ms", "tlas_ms", "commit_ms")] +
+                        [(n, "<i4") for n in ("prims", "blas_built", "nodes", "n_idx", "max_depth", "tlas_nodes", "tlas_depth", "reconfigured")] +
+                        [("reserved", "<i4", 2)])
+assert RebuildStats.itemsize == 96
 
 DEVICE_SYMBOLS = [
     "rt_last_error", "rt_device_count", "rt_kernel_info", "rt_create", "rt_destroy", "rt_upload_scene", "rt_share_scene", "rt_set_seeds", "rt_seed_default",
@@ -83,6 +88,7 @@ DEVICE_SYMBOLS = [
     "rt_stage_begin_frame", "rt_stage_generate", "rt_stage_extend", "rt_stage_shade", "rt_stage_connect",
     "rt_debug_get_rays", "rt_debug_set_rays", "rt_debug_get_shadow", "rt_debug_enable_steps", "rt_debug_get_steps", "rt_debug_math",
     "rt_debug_math_sweep", "rt_validate_scene", "rt_build_bvh2", "rt_build_bvh2_sah", "rt_debug_sah_phases", "rt_update_scene", "rt_group_update_scene", "rt_debug_get_scene_array",
+    "rt_rebuild_scene", "rt_group_rebuild_scene", "rt_blas_ranges",
     "rt_group_create", "rt_group_destroy", "rt_group_lanes", "rt_group_concurrency", "rt_group_lane", "rt_group_frames", "rt_group_upload_scene", "rt_group_share_scene",
     "rt_group_seed", "rt_group_reset", "rt_group_render", "rt_group_synchronize", "rt_group_sum", "rt_group_read_accum", "rt_group_focus",
     "rt_group_postproc"]
@@ -95,7 +101,7 @@ HOST_SYMBOLS = [
     "rth_renderer_read", "rth_renderer_camera", "rth_seed_stream", "rth_load_model", "rth_save_png",
     "rth_set_build_threads", "rth_renderer_save_frame", "rth_renderer_camera_move", "rth_renderer_camera_mouse", "rth_renderer_camera_zoom", "rth_renderer_frames", "rth_renderer_set_lanes",
     "rth_build_blas_lbvh", "rth_build_bvh2_lbvh", "rth_lbvh_stats", "rth_set_primitives", "rth_refit",
-    "rth_build_blas_sah_gpu", "rth_build_bvh2_sah"]
+    "rth_build_blas_sah_gpu", "rth_build_bvh2_sah", "rth_rebuild", "rth_blas_ranges"]
 
 _dev = None
 _host = None
@@ -182,6 +188,9 @@ def _bind_device(lib):
         lib.rt_update_scene.argtypes = [vp, vp, i32, i32, vp, i32, vp]
         lib.rt_group_update_scene.argtypes = [vp, vp, i32, i32, vp, i32, vp]
         lib.rt_debug_get_scene_array.argtypes = [vp, i32, vp, i64, C.POINTER(i64)]
+        lib.rt_rebuild_scene.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp, vp]
+        lib.rt_group_rebuild_scene.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp, vp]
+        lib.rt_blas_ranges.argtypes = [vp, i32, vp, i32, i32, vp, i32, vp, vp]
         lib.rt_group_create.argtypes = [vp, i32, C.POINTER(vp)]
         lib.rt_group_destroy.argtypes = [vp]
         lib.rt_group_lanes.argtypes = [vp]
@@ -232,6 +241,8 @@ def host_lib():
                                            C.POINTER(C.c_int32), vp, vp]
         lib.rth_set_primitives.argtypes = [vp, i32, i32, vp]
         lib.rth_refit.argtypes = [vp]
+        lib.rth_rebuild.argtypes = [vp, i32, vp]
+        lib.rth_blas_ranges.argtypes = [vp, vp, vp]
         lib.rth_set_build_threads.argtypes = [vp, i32]
         lib.rth_build_tlas.argtypes = [vp]
         lib.rth_bvh4_from_nodes.argtypes = [vp, i32, vp]

@@ -24,6 +24,9 @@ HOST_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wa
 ORACLE_FLAGS = ["-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-fopenmp", "-Wall", "-D_GNU_SOURCE"]
 
 
+REBUILD_HEADERS = [os.path.join(PKG, "csrc", h) for h in ("rebuild_common.h", "rebuild_dev.h", "build_cores.h")]
+
+
 def _stale(out, srcs):
     if not os.path.exists(out):
         return True
@@ -41,12 +44,13 @@ def build_device(force=False):
     lbvh = os.path.join(PKG, "csrc", "lbvh.hip")      # rt_build_bvh2: the GPU linear BVH builder
     refit = os.path.join(PKG, "csrc", "refit.hip")    # rt_update_scene: BLAS refit, derived records and TLAS rebuild on the GPU
     sah = os.path.join(PKG, "csrc", "sah.hip")        # rt_build_bvh2_sah: the default SAH BLAS built on the GPU
-    deps = [src, lbvh, refit, sah, os.path.join(PKG, "csrc", "rt355_kernels.h"), os.path.join(PKG, "csrc", "lbvh_common.h"),
+    rebuild = os.path.join(PKG, "csrc", "rebuild.hip")  # rt_rebuild_scene: what upload derives from a BVH2, derived on the GPU
+    deps = [src, lbvh, refit, sah, rebuild, *REBUILD_HEADERS, os.path.join(PKG, "csrc", "rt355_kernels.h"), os.path.join(PKG, "csrc", "lbvh_common.h"),
             os.path.join(PKG, "csrc", "refit_common.h"), os.path.join(PKG, "csrc", "sah_common.h"), os.path.join(ROOT, "include", "rt355.h"),
             os.path.join(ROOT, "include", "rt355_types.h")]
     out = os.path.join(PKG, "librt355.so")
     if force or _stale(out, deps):
-        _run([HIPCC] + DEVICE_FLAGS + [src, lbvh, refit, sah, "-o", out])
+        _run([HIPCC] + DEVICE_FLAGS + [src, lbvh, refit, sah, rebuild, "-o", out])
     return out
 
 
@@ -58,7 +62,8 @@ def build_device_refb(force=False):
     lbvh = os.path.join(PKG, "csrc", "lbvh.hip")      # same entry points as librt355.so (the ctypes binding declares them all)
     refit = os.path.join(PKG, "csrc", "refit.hip")
     sah = os.path.join(PKG, "csrc", "sah.hip")
-    deps = [src, lbvh, refit, sah, os.path.join(PKG, "csrc", "rt355_kernels.h"), os.path.join(PKG, "csrc", "lbvh_common.h"),
+    rebuild = os.path.join(PKG, "csrc", "rebuild.hip")
+    deps = [src, lbvh, refit, sah, rebuild, *REBUILD_HEADERS, os.path.join(PKG, "csrc", "rt355_kernels.h"), os.path.join(PKG, "csrc", "lbvh_common.h"),
             os.path.join(PKG, "csrc", "refit_common.h"), os.path.join(PKG, "csrc", "sah_common.h"), os.path.join(ROOT, "include", "rt355.h"),
             os.path.join(ROOT, "include", "rt355_types.h")]
     out = os.path.join(PKG, "librt355_refb.so")
@@ -66,7 +71,7 @@ def build_device_refb(force=False):
         # -Bsymbolic: this library defines the same global symbols as librt355.so (C-ABI entry points, the kernels' host stubs).  Loaded
         # into a process that already holds librt355.so, its own references would otherwise bind to THAT library's definitions - and
         # launch the other build's kernels
-        _run([HIPCC] + DEVICE_FLAGS + ["-DRT355_REF_BUILTINS", "-Wl,-Bsymbolic", src, lbvh, refit, sah, "-o", out])
+        _run([HIPCC] + DEVICE_FLAGS + ["-DRT355_REF_BUILTINS", "-Wl,-Bsymbolic", src, lbvh, refit, sah, rebuild, "-o", out])
     return out
 
 
@@ -74,7 +79,7 @@ def build_host(force=False):
     hdir = os.path.join(PKG, "host")
     srcs = [os.path.join(hdir, f) for f in sorted(os.listdir(hdir)) if f.endswith(".cpp")]
     deps = srcs + [os.path.join(hdir, "rt_host.h"), os.path.join(PKG, "csrc", "lbvh_common.h"), os.path.join(PKG, "csrc", "refit_common.h"),
-                   os.path.join(PKG, "csrc", "sah_common.h"),
+                   os.path.join(PKG, "csrc", "sah_common.h"), os.path.join(PKG, "csrc", "rebuild_common.h"),
                    os.path.join(ROOT, "include", "rt355.h"),
                    os.path.join(ROOT, "include", "rt355_host.h"), os.path.join(ROOT, "include", "rt355_types.h")]
     out = os.path.join(PKG, "librt355_host.so")

@@ -16,6 +16,7 @@
 #include <cstdio>
 #include "../../include/rt355.h"
 #include "lbvh_common.h"
+#include "build_cores.h"
 
 using namespace lbvh;
 
@@ -123,7 +124,7 @@ int lfail(int code, const char* fmt, ...)   // the message goes to rt_last_error
 
 size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// Everything one build allocates on the device; freed on every exit path.
+// Everything one rt_build_bvh2 call allocates on the device; freed on every exit path.
 struct Work {
     void* mem = nullptr;
     hipStream_t stream = nullptr;
@@ -139,15 +140,112 @@ struct Work {
     }
 };
 
+// The carved workspace of one build of n primitives (everything but the primitives and the output arrays):
+// [cb | tickets | parent] first (the words the memsets initialise), then the rest
+struct Carve { size_t oCb, oTick, oPar, oBox, oK0, oK1, oV0, oV1, oKids, oRec, oFlag, oRank, oSort, oScan, sortBytes, scanBytes, total; };
+hipError_t carve_work(uint32_t n, hipStream_t s, Carve& c)
+{
+    const uint32_t nInt = n - 1, nTree = 2 * n - 1;
+    const int keyBits = 3 * axis_bits(n) + index_bits(n);
+    c.sortBytes = c.scanBytes = 0;
+    hipError_t e = hipcub::DeviceRadixSort::SortPairs(nullptr, c.sortBytes, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr,
+                                                      (uint32_t*)nullptr, (int)n, 0, keyBits, s);
+    if (e != hipSuccess) return e;
+    if (nInt > 0) e = hipcub::DeviceScan::ExclusiveSum(nullptr, c.scanBytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)nInt, s);
+    if (e != hipSuccess) return e;
+    const size_t nI = nInt > 0 ? nInt : 1;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { const size_t o = off; off += align_up(bytes); return o; };
+    c.oCb = carve(6 * sizeof(uint32_t)); c.oTick = carve(nI * sizeof(uint32_t)); c.oPar = carve(nTree * sizeof(uint32_t));
+    c.oBox = carve(n * sizeof(Box)); c.oK0 = carve(n * 8ull); c.oK1 = carve(n * 8ull);
+    c.oV0 = carve(n * 4ull); c.oV1 = carve(n * 4ull); c.oKids = carve(nI * sizeof(Kids)); c.oRec = carve(nTree * sizeof(NodeRec));
+    c.oFlag = carve(nI * 4ull); c.oRank = carve(nI * 4ull);
+    c.oSort = carve(c.sortBytes); c.oScan = carve(c.scanBytes);
+    c.total = off;
+    return hipSuccess;
+}
+
 } // namespace
 
 #define LCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
-    return lfail(RT_E_DEVICE, "rt_build_bvh2: %s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
+    return lfail(RT_E_DEVICE, "%s: %s failed: %s", who, #expr, hipGetErrorString(e_)); } while (0)
 
+namespace lbvhdev {
+
+const char* check_args(const RtBuildOptions* opts, int32_t nPrims, int32_t first, int32_t count, uint32_t nodeBase, uint32_t idxBase, Params& P)
+{
+    static const RtPrimitive prim{}; static const RtBVHNode2 node{}; static const int32_t n = 0; static const uint32_t idx = 0;   // (only their presence is checked)
+    return lbvh::check_args(opts, &prim, nPrims, first, count, nodeBase, idxBase, &node, count > 0 ? 2 * count - 1 : 0, &n, &idx, P);
+}
+
+int work_bytes(const char* who, uint32_t n, hipStream_t s, size_t* bytes)
+{
+    Carve c;
+    LCHK(carve_work(n, s, c));
+    *bytes = c.total;
+    return RT_OK;
+}
+
+// The build proper (build_cores.h): everything stays on the device; the host reads the root's record.
+int build(const char* who, hipStream_t stream, void* work, const Params& P, const RtPrimitive* dPrims, uint32_t n, uint32_t first,
+          uint32_t nodeBase, uint32_t idxBase, RtBVHNode2* dNodes, uint32_t* dIdx, hipEvent_t evBegin, hipEvent_t evEnd, Built* out)
+{
+    const uint32_t nInt = n - 1, nTree = 2 * n - 1;
+    const int bIdx = index_bits(n), k = axis_bits(n), keyBits = 3 * k + bIdx;
+    const size_t nI = nInt > 0 ? nInt : 1;
+    Carve c;
+    LCHK(carve_work(n, stream, c));
+    char* base = (char*)work;
+    auto at = [&](size_t o) { return (void*)(base + o); };
+    uint32_t* cb = (uint32_t*)at(c.oCb);
+    uint32_t* tickets = (uint32_t*)at(c.oTick);
+    uint32_t* parent = (uint32_t*)at(c.oPar);
+    Box* boxes = (Box*)at(c.oBox);
+    uint64_t *k0 = (uint64_t*)at(c.oK0), *k1 = (uint64_t*)at(c.oK1);
+    uint32_t *v0 = (uint32_t*)at(c.oV0), *v1 = (uint32_t*)at(c.oV1);
+    Kids* kids = (Kids*)at(c.oKids);
+    NodeRec* rec = (NodeRec*)at(c.oRec);
+    uint32_t *flags = (uint32_t*)at(c.oFlag), *rank = (uint32_t*)at(c.oRank);
+
+    const uint32_t cbInit[6] = { kKeyMinInit, kKeyMinInit, kKeyMinInit, kKeyMaxInit, kKeyMaxInit, kKeyMaxInit };
+    LCHK(hipMemcpyAsync(cb, cbInit, sizeof cbInit, hipMemcpyHostToDevice, stream));
+    LCHK(hipMemsetAsync(tickets, 0, nI * sizeof(uint32_t), stream));
+    LCHK(hipMemsetAsync(parent, 0xff, nTree * sizeof(uint32_t), stream));
+    LCHK(hipStreamSynchronize(stream));   // (rt_build_bvh2: nothing of the caller's host arrays is read after this point)
+
+    const dim3 blk(kBlock), gN((n + kBlock - 1) / kBlock), gI((nI + kBlock - 1) / kBlock);
+    if (evBegin) LCHK(hipEventRecord(evBegin, stream));
+    hipLaunchKernelGGL(k_lbvh_boxes, gN, blk, 0, stream, dPrims, n, boxes, cb);
+    hipLaunchKernelGGL(k_lbvh_keys, gN, blk, 0, stream, boxes, n, cb, k, bIdx, k0, v0);
+    LCHK(hipcub::DeviceRadixSort::SortPairs(at(c.oSort), c.sortBytes, k0, k1, v0, v1, (int)n, 0, keyBits, stream));
+    if (nInt > 0) hipLaunchKernelGGL(k_lbvh_karras, gI, blk, 0, stream, k1, n, kids, parent);
+    hipLaunchKernelGGL(k_lbvh_bottomup, gN, blk, 0, stream, boxes, v1, n, rec, parent, kids, tickets, P);
+    if (nInt > 0) {
+        hipLaunchKernelGGL(k_lbvh_survive, gI, blk, 0, stream, rec, parent, nInt, P.maxLeaf, flags);
+        LCHK(hipcub::DeviceScan::ExclusiveSum(at(c.oScan), c.scanBytes, flags, rank, (int)nInt, stream));
+    }
+    hipLaunchKernelGGL(k_lbvh_emit, gN, blk, 0, stream, rec, kids, flags, rank, v1, n, first, nodeBase, idxBase, dNodes, dIdx);
+    LCHK(hipGetLastError());
+    if (evEnd) LCHK(hipEventRecord(evEnd, stream));
+
+    NodeRec root;
+    LCHK(hipMemcpyAsync(&root, rec, sizeof root, hipMemcpyDeviceToHost, stream));
+    LCHK(hipStreamSynchronize(stream));
+    const uint32_t outNodes = 2 * root.leaves - 1;
+    if (root.leaves < 1 || outNodes > nTree) return lfail(RT_E_DEVICE, "%s: inconsistent device result (%u leaves)", who, root.leaves);
+    *out = Built{};
+    out->nodes = outNodes; out->leaves = root.leaves; out->depth = root.height; out->mortonBits = (uint32_t)k; out->cost = root.total;
+    return RT_OK;
+}
+
+} // namespace lbvhdev
+
+// The C-ABI entry: allocate, upload, build (lbvhdev::build), download.
 extern "C" int rt_build_bvh2(int32_t device, const RtBuildOptions* opt, const RtPrimitive* prims, int32_t nPrims, int32_t first,
                              int32_t count, uint32_t nodeBase, uint32_t idxBase, RtBVHNode2* nodes, int32_t nodeCap, int32_t* nNodes,
                              uint32_t* primIdx, RtBuildStats* stats)
 {
+    const char* who = "rt_build_bvh2";
     const auto t0 = std::chrono::steady_clock::now();
     Params P;
     if (const char* msg = check_args(opt, prims, nPrims, first, count, nodeBase, idxBase, nodes, nodeCap, nNodes, primIdx, P))
@@ -158,79 +256,33 @@ extern "C" int rt_build_bvh2(int32_t device, const RtBuildOptions* opt, const Rt
     Work w;
     LCHK(hipGetDevice(&w.prevDevice));
     LCHK(hipSetDevice(device));
-
-    const uint32_t n = (uint32_t)count, nInt = n - 1, nTree = 2 * n - 1;
-    const int bIdx = index_bits(n), k = axis_bits(n), keyBits = 3 * k + bIdx;
     LCHK(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
     LCHK(hipEventCreate(&w.ev[0]));
     LCHK(hipEventCreate(&w.ev[1]));
 
-    size_t sortBytes = 0, scanBytes = 0;
-    LCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, sortBytes, (uint64_t*)nullptr, (uint64_t*)nullptr, (uint32_t*)nullptr,
-                                            (uint32_t*)nullptr, (int)n, 0, keyBits, w.stream));
-    if (nInt > 0) LCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, scanBytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)nInt, w.stream));
-
-    // one allocation, carved: [cb | tickets | parent] first (the words the memsets initialise), then the rest
-    const size_t nI = nInt > 0 ? nInt : 1;
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { const size_t o = off; off += align_up(bytes); return o; };
-    const size_t oCb = carve(6 * sizeof(uint32_t)), oTick = carve(nI * sizeof(uint32_t)), oPar = carve(nTree * sizeof(uint32_t));
-    const size_t oPrim = carve(n * sizeof(RtPrimitive)), oBox = carve(n * sizeof(Box)), oK0 = carve(n * 8ull), oK1 = carve(n * 8ull);
-    const size_t oV0 = carve(n * 4ull), oV1 = carve(n * 4ull), oKids = carve(nI * sizeof(Kids)), oRec = carve(nTree * sizeof(NodeRec));
-    const size_t oFlag = carve(nI * 4ull), oRank = carve(nI * 4ull), oNodes = carve(nTree * sizeof(RtBVHNode2)), oIdx = carve(n * 4ull);
-    const size_t oSort = carve(sortBytes), oScan = carve(scanBytes);
-    if (hipMalloc(&w.mem, off) != hipSuccess) { w.mem = nullptr; return lfail(RT_E_NOMEM, "rt_build_bvh2: %zu bytes of device memory", off); }
-    char* base = (char*)w.mem;
-    auto at = [&](size_t o) { return (void*)(base + o); };
-    uint32_t* cb = (uint32_t*)at(oCb);
-    uint32_t* tickets = (uint32_t*)at(oTick);
-    uint32_t* parent = (uint32_t*)at(oPar);
-    RtPrimitive* dPrims = (RtPrimitive*)at(oPrim);
-    Box* boxes = (Box*)at(oBox);
-    uint64_t *k0 = (uint64_t*)at(oK0), *k1 = (uint64_t*)at(oK1);
-    uint32_t *v0 = (uint32_t*)at(oV0), *v1 = (uint32_t*)at(oV1);
-    Kids* kids = (Kids*)at(oKids);
-    NodeRec* rec = (NodeRec*)at(oRec);
-    uint32_t *flags = (uint32_t*)at(oFlag), *rank = (uint32_t*)at(oRank);
-    RtBVHNode2* dNodes = (RtBVHNode2*)at(oNodes);
-    uint32_t* dIdx = (uint32_t*)at(oIdx);
-
+    const uint32_t n = (uint32_t)count, nTree = 2 * n - 1;
+    size_t workBytes = 0;
+    if (const int rc = lbvhdev::work_bytes(who, n, w.stream, &workBytes)) return rc;
+    // one allocation: the core's workspace, then the primitives and the output arrays
+    const size_t oPrim = align_up(workBytes), oNodes = oPrim + align_up(n * sizeof(RtPrimitive)), oIdx = oNodes + align_up((size_t)nTree * sizeof(RtBVHNode2));
+    const size_t bytes = oIdx + align_up(n * 4ull);
+    if (hipMalloc(&w.mem, bytes) != hipSuccess) { w.mem = nullptr; return lfail(RT_E_NOMEM, "rt_build_bvh2: %zu bytes of device memory", bytes); }
+    RtPrimitive* dPrims = (RtPrimitive*)((char*)w.mem + oPrim);
+    RtBVHNode2* dNodes = (RtBVHNode2*)((char*)w.mem + oNodes);
+    uint32_t* dIdx = (uint32_t*)((char*)w.mem + oIdx);
     LCHK(hipMemcpyAsync(dPrims, prims + first, n * sizeof(RtPrimitive), hipMemcpyHostToDevice, w.stream));
-    const uint32_t cbInit[6] = { kKeyMinInit, kKeyMinInit, kKeyMinInit, kKeyMaxInit, kKeyMaxInit, kKeyMaxInit };
-    LCHK(hipMemcpyAsync(cb, cbInit, sizeof cbInit, hipMemcpyHostToDevice, w.stream));
-    LCHK(hipMemsetAsync(tickets, 0, nI * sizeof(uint32_t), w.stream));
-    LCHK(hipMemsetAsync(parent, 0xff, nTree * sizeof(uint32_t), w.stream));
-    LCHK(hipStreamSynchronize(w.stream));   // the host arrays are the caller's: nothing of them is read after this point
 
-    const dim3 blk(kBlock), gN((n + kBlock - 1) / kBlock), gI((nI + kBlock - 1) / kBlock);
-    LCHK(hipEventRecord(w.ev[0], w.stream));
-    hipLaunchKernelGGL(k_lbvh_boxes, gN, blk, 0, w.stream, dPrims, n, boxes, cb);
-    hipLaunchKernelGGL(k_lbvh_keys, gN, blk, 0, w.stream, boxes, n, cb, k, bIdx, k0, v0);
-    LCHK(hipcub::DeviceRadixSort::SortPairs(at(oSort), sortBytes, k0, k1, v0, v1, (int)n, 0, keyBits, w.stream));
-    if (nInt > 0) hipLaunchKernelGGL(k_lbvh_karras, gI, blk, 0, w.stream, k1, n, kids, parent);
-    hipLaunchKernelGGL(k_lbvh_bottomup, gN, blk, 0, w.stream, boxes, v1, n, rec, parent, kids, tickets, P);
-    if (nInt > 0) {
-        hipLaunchKernelGGL(k_lbvh_survive, gI, blk, 0, w.stream, rec, parent, nInt, P.maxLeaf, flags);
-        LCHK(hipcub::DeviceScan::ExclusiveSum(at(oScan), scanBytes, flags, rank, (int)nInt, w.stream));
-    }
-    hipLaunchKernelGGL(k_lbvh_emit, gN, blk, 0, w.stream, rec, kids, flags, rank, v1, n, (uint32_t)first, nodeBase, idxBase, dNodes, dIdx);
-    LCHK(hipGetLastError());
-    LCHK(hipEventRecord(w.ev[1], w.stream));
-
-    NodeRec root;
-    LCHK(hipMemcpyAsync(&root, rec, sizeof root, hipMemcpyDeviceToHost, w.stream));
-    LCHK(hipStreamSynchronize(w.stream));
-    const uint32_t outNodes = 2 * root.leaves - 1;
-    if (root.leaves < 1 || outNodes > nTree) return lfail(RT_E_DEVICE, "rt_build_bvh2: inconsistent device result (%u leaves)", root.leaves);
-    LCHK(hipMemcpyAsync(nodes, dNodes, outNodes * sizeof(RtBVHNode2), hipMemcpyDeviceToHost, w.stream));
+    lbvhdev::Built b{};
+    if (const int rc = lbvhdev::build(who, w.stream, w.mem, P, dPrims, n, (uint32_t)first, nodeBase, idxBase, dNodes, dIdx, w.ev[0], w.ev[1], &b)) return rc;
+    LCHK(hipMemcpyAsync(nodes, dNodes, b.nodes * sizeof(RtBVHNode2), hipMemcpyDeviceToHost, w.stream));
     LCHK(hipMemcpyAsync(primIdx, dIdx, n * sizeof(uint32_t), hipMemcpyDeviceToHost, w.stream));
     LCHK(hipStreamSynchronize(w.stream));
-    *nNodes = (int32_t)outNodes;
+    *nNodes = (int32_t)b.nodes;
     if (stats) {
         float ms = 0;
         LCHK(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
-        stats->nodes = (int32_t)outNodes; stats->leaves = (int32_t)root.leaves; stats->depth = (int32_t)root.height;
-        stats->morton_bits = k; stats->sah_cost = root.total; stats->device_ms = ms;
+        stats->nodes = (int32_t)b.nodes; stats->leaves = (int32_t)b.leaves; stats->depth = (int32_t)b.depth;
+        stats->morton_bits = (int32_t)b.mortonBits; stats->sah_cost = b.cost; stats->device_ms = ms;
         stats->wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
         stats->_reserved = 0;
     }

@@ -1,0 +1,167 @@
+// rebuild.hip — what rt_upload_scene derives from a BVH2 on the host, derived on the device (rt_rebuild_scene, include/rt355.h;
+// driven by rt355.hip).  The rules are rebuild_common.h's and refit_common.h's, which the upload path and the host restatement share.
+//
+// Pair ids are positions in a breadth-first walk, so they are produced level by level.  Per BLAS and level l (frontier: the interior
+// nodes of that level, left to right; cnt[l] of them, the first has pair id base[l]):
+//   k_rb_frontier   one thread per frontier node: its pair id (newId, pairNode), its children's parent links, and a flag per child
+//                   that is an interior node; hipcub::DeviceScan ranks the flags
+//   k_rb_next       writes the flagged children to the next frontier at their ranks; cnt[l + 1], base[l + 1]
+// The host knows each tree's height and interior count from the builder, so it launches the levels without reading anything back;
+// the last level checks that the walk ended where the builder said (status).  Every position comes from a scan: no atomic decides
+// where anything is written, two runs give the same arrays.  Then, over all BLAS:
+//   k_rb_pairs      one thread per pair id: the pair record (refit::pair_boxes + rebuild::pair_entries, what rebuild::pair_record packs)
+//   k_rb_leaf_flag / k_rb_leaf_list   the leaves (refit topology) in node order, by a scan; the largest leaf (status)
+//   k_rb_roots      one thread per instance: the packed entry of its BLAS root
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+#include "../../include/rt355.h"
+#include "rebuild_common.h"
+#include "rebuild_dev.h"
+
+namespace rebuilddev {
+
+using namespace rebuild;
+
+constexpr int kBlock = 256;
+
+__global__ void __launch_bounds__(64) k_rb_begin(const RtBVHNode2* nodes, uint32_t root, uint32_t pairBase, uint32_t* front, uint32_t* ctr)
+{
+    if (threadIdx.x != 0) return;
+    const bool interior = nodes[root].count == 0;
+    front[0] = root;
+    ctr[kCnt + 0] = interior ? 1u : 0u;
+    ctr[kBase + 0] = pairBase;
+}
+
+__global__ void __launch_bounds__(kBlock) k_rb_frontier(const RtBVHNode2* nodes, uint32_t nNodes, const uint32_t* front, uint32_t ub, uint32_t level,
+                                                        uint32_t pairCap, uint32_t* newId, uint32_t* pairNode, uint32_t* parent, uint32_t* flags,
+                                                        uint32_t* ctr)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= ub) return;
+    uint32_t f0 = 0, f1 = 0;
+    if (i < ctr[kCnt + level]) {
+        const uint32_t node = front[i], id = ctr[kBase + level] + i;
+        const uint32_t c = node < nNodes ? nodes[node].first : nNodes;   // (both tests below: c + 1 wraps for c = 0xffffffff)
+        if (id >= pairCap || c >= nNodes || c + 1 >= nNodes) atomicOr(&ctr[kStatus], kWalk);
+        else {
+            newId[node] = id; pairNode[id] = node;
+            parent[c] = node; parent[c + 1] = node;
+            f0 = nodes[c].count == 0 ? 1u : 0u;
+            f1 = nodes[c + 1].count == 0 ? 1u : 0u;
+        }
+    }
+    flags[2 * i] = f0; flags[2 * i + 1] = f1;
+}
+
+// expectEnd != kNone: this is the tree's last level with interior nodes; the walk must end here, at that pair id
+__global__ void __launch_bounds__(kBlock) k_rb_next(const RtBVHNode2* nodes, const uint32_t* front, uint32_t ub, uint32_t level, const uint32_t* flags,
+                                                    const uint32_t* ranks, uint32_t* next, uint32_t nextCap, uint32_t expectEnd, uint32_t* ctr)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= ub) return;
+    const uint32_t cnt = ctr[kCnt + level];
+    if (i == 0) {
+        const uint32_t n = ranks[2 * ub - 1] + flags[2 * ub - 1], end = ctr[kBase + level] + cnt;
+        ctr[kCnt + level + 1] = n; ctr[kBase + level + 1] = end;
+        if (cnt > ub || n > nextCap) atomicOr(&ctr[kStatus], kWalk);
+        if (expectEnd != kNone && (n != 0 || end != expectEnd)) atomicOr(&ctr[kStatus], kWalk);
+    }
+    if (i >= cnt) return;
+    const uint32_t c = nodes[front[i]].first;
+    for (uint32_t k = 0; k < 2; k++)
+        if (flags[2 * i + k]) { const uint32_t r = ranks[2 * i + k]; if (r < nextCap) next[r] = c + k; }
+}
+
+__global__ void __launch_bounds__(kBlock) k_rb_pairs(const RtBVHNode2* nodes, const uint32_t* pairNode, const uint32_t* newId, uint32_t nPairs,
+                                                     RtFloat4* pairs)
+{
+    const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
+    if (k >= nPairs) return;
+    const uint32_t node = pairNode[k], c = nodes[node].first;
+    RtFloat4 r[3];
+    uint32_t e[2];
+    refit::pair_boxes(nodes[c], nodes[c + 1], r);
+    pair_entries(nodes, node, newId, e);
+    for (int w = 0; w < 3; w++) pairs[(size_t)k * 4 + w] = r[w];
+    *reinterpret_cast<uint4*>(&pairs[(size_t)k * 4 + 3]) = make_uint4(e[0], e[1], 0u, 0u);   // (pair_record's fourth word, as bits)
+}
+
+__global__ void __launch_bounds__(kBlock) k_rb_leaf_flag(const RtBVHNode2* nodes, uint32_t nNodes, uint32_t* flags, uint32_t* ctr)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= nNodes) return;
+    const uint32_t c = nodes[i].count;
+    flags[i] = c > 0 ? 1u : 0u;
+    if (c > kMaxPackedLeaf) atomicMax(&ctr[kLargestLeaf], c);   // a value, not a position
+}
+__global__ void __launch_bounds__(kBlock) k_rb_leaf_list(const uint32_t* flags, const uint32_t* ranks, uint32_t nNodes, uint32_t nLeaves,
+                                                         uint32_t* leaves, uint32_t* ctr)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= nNodes) return;
+    if (i == nNodes - 1 && ranks[i] + flags[i] != nLeaves) atomicOr(&ctr[kStatus], kWalk);
+    if (flags[i] && ranks[i] < nLeaves) leaves[ranks[i]] = i;
+}
+
+__global__ void __launch_bounds__(kBlock) k_rb_roots(const RtBVHNode2* nodes, const RtBVHInstance* inst, uint32_t nInst, const uint32_t* newId,
+                                                     uint32_t* rootEntry)
+{
+    const uint32_t b = blockIdx.x * kBlock + threadIdx.x;
+    if (b >= nInst) return;
+    const uint32_t root = inst[b].bvhIdx;
+    rootEntry[b] = child_entry(nodes[root], nodes[root].count > 0 ? 0u : newId[root]);
+}
+
+static dim3 grid(uint32_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
+
+hipError_t scan_bytes(uint32_t items, hipStream_t s, size_t* bytes)
+{
+    *bytes = 0;
+    return hipcub::DeviceScan::ExclusiveSum(nullptr, *bytes, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)items, s);
+}
+
+hipError_t begin(hipStream_t s, const Work& w, uint32_t* parent, uint32_t nNodes)
+{
+    hipError_t e = hipMemsetAsync(w.ctr, 0, sizeof(uint32_t) * kCtrWords, s);
+    if (e != hipSuccess) return e;
+    return hipMemsetAsync(parent, 0xff, sizeof(uint32_t) * nNodes, s);   // roots keep kNone
+}
+
+hipError_t number_blas(hipStream_t s, const Work& w, const RtBVHNode2* nodes, uint32_t nNodes, uint32_t root, uint32_t interiors, uint32_t depth,
+                       uint32_t pairBase, uint32_t pairCap, uint32_t* pairNode, uint32_t* parent)
+{
+    if (depth > kMaxLevels) return hipErrorInvalidValue;
+    uint32_t *front = w.frontA, *next = w.frontB;
+    size_t scanBytes = w.scanBytes;
+    if (depth > 0 && interiors == 0) return hipErrorInvalidValue;   // (the caller has checked the builder's result)
+    hipLaunchKernelGGL(k_rb_begin, dim3(1), dim3(64), 0, s, nodes, root, pairBase, front, w.ctr);
+    for (uint32_t l = 0; l < depth; l++) {
+        const uint64_t full = l < 31 ? (1ull << l) : (1ull << 31);
+        const uint32_t ub = (uint32_t)(full < interiors ? full : interiors);
+        hipLaunchKernelGGL(k_rb_frontier, grid(ub), dim3(kBlock), 0, s, nodes, nNodes, front, ub, l, pairCap, w.newId, pairNode, parent, w.flags, w.ctr);
+        hipError_t e = hipcub::DeviceScan::ExclusiveSum(w.scan, scanBytes, w.flags, w.ranks, (int)(2 * ub), s);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(k_rb_next, grid(ub), dim3(kBlock), 0, s, nodes, front, ub, l, w.flags, w.ranks, next, w.frontCap,
+                           l + 1 == depth ? pairBase + interiors : kNone, w.ctr);
+        uint32_t* t = front; front = next; next = t;
+    }
+    return hipGetLastError();
+}
+
+hipError_t finish(hipStream_t s, const Work& w, const RtBVHNode2* nodes, uint32_t nNodes, uint32_t nPairs, uint32_t nLeaves, const RtBVHInstance* inst,
+                  uint32_t nInst, const uint32_t* pairNode, RtFloat4* pairs, uint32_t* rootEntry, uint32_t* leaves)
+{
+    hipLaunchKernelGGL(k_rb_leaf_flag, grid(nNodes), dim3(kBlock), 0, s, nodes, nNodes, w.flags, w.ctr);
+    size_t scanBytes = w.scanBytes;
+    hipError_t e = hipcub::DeviceScan::ExclusiveSum(w.scan, scanBytes, w.flags, w.ranks, (int)nNodes, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_rb_leaf_list, grid(nNodes), dim3(kBlock), 0, s, w.flags, w.ranks, nNodes, nLeaves, leaves, w.ctr);
+    if (pairs) {
+        if (nPairs) hipLaunchKernelGGL(k_rb_pairs, grid(nPairs), dim3(kBlock), 0, s, nodes, pairNode, w.newId, nPairs, pairs);
+        hipLaunchKernelGGL(k_rb_roots, grid(nInst), dim3(kBlock), 0, s, nodes, inst, nInst, w.newId, rootEntry);
+    }
+    return hipGetLastError();
+}
+
+} // namespace rebuilddev

@@ -1,0 +1,124 @@
+// rebuild_common.h — the rules by which a scene's derived layout follows from its BVH2 (rt_upload_scene derives it on the host,
+// rt_rebuild_scene on the device: rebuild.hip), and the detection of the primitive range each BLAS covers.  Compiled by hipcc for the
+// device path and by g++ for the host restatement (host/rebuild_host.cpp, rth_rebuild), like refit_common.h.
+//
+//   pair ids     interior nodes are renumbered breadth-first, BLAS by BLAS in the order in which the instances first name their
+//                roots: level by level, parents in frontier order, child `first` before `first + 1`, interior children only.
+//   pair record  both child boxes (refit::pair_boxes) and the children's entries: a leaf is 0x80000000 | count << 24 | first (so a
+//                leaf holds at most kMaxPackedLeaf primitives and primIdx fewer than 2^24 slots), an interior node is its pair id.
+//   stack        a BLAS of height h (edges, the root counts 0) needs h entries; a context keeps clamp(max h + 1, 6, RT_BVH4_STACK).
+#pragma once
+#include <stdint.h>
+#include <vector>
+#include "../../include/rt355_types.h"
+#include "refit_common.h"
+
+namespace rebuild {
+
+constexpr uint32_t kNone = 0xffffffffu;
+constexpr uint32_t kMaxPackedLeaf = 127;          // primitives of a leaf in the packed entry
+constexpr int32_t kMaxPackedIdx = 1 << 24;        // primIdx slots the packed entry addresses
+constexpr int kMinStackEntries = 6;               // flush_counters reuses 36 words of the LDS stack
+
+// the packed entry of node n in layout 1 (newId: its pair id if it is an interior node)
+LB_HD uint32_t child_entry(uint32_t first, uint32_t count, uint32_t newId)
+{
+    return count > 0 ? (refit::kLeafBit | (count << 24) | first) : newId;
+}
+LB_HD uint32_t child_entry(const RtBVHNode2& n, uint32_t newId) { return child_entry(n.first, n.count, newId); }
+// the packed entries of both children of interior node `node`; newId maps node ids to pair ids
+LB_HD void pair_entries(const RtBVHNode2* nodes, uint32_t node, const uint32_t* newId, uint32_t e[2])
+{
+    const uint32_t c = nodes[node].first;
+    for (uint32_t k = 0; k < 2; k++) {
+        const uint32_t count = nodes[c + k].count;   // (an interior node's pair id is only read for interior nodes)
+        e[k] = child_entry(nodes[c + k].first, count, count > 0 ? 0u : newId[c + k]);
+    }
+}
+// the pair record of interior node `node`: both child boxes, then {entries, 0, 0} as bit patterns
+LB_HD void pair_record(const RtBVHNode2* nodes, uint32_t node, const uint32_t* newId, RtFloat4 out[4])
+{
+    const uint32_t c = nodes[node].first;
+    uint32_t e[2];
+    refit::pair_boxes(nodes[c], nodes[c + 1], out);
+    pair_entries(nodes, node, newId, e);
+    out[3] = refit::f4(refit::u2f(e[0]), refit::u2f(e[1]), 0.0f, 0.0f);
+}
+// does the scene take the derived layout 1?  (BVH2 only; extend_variant 1 keeps the reference arrays)
+LB_HD bool takes_layout1(bool variantAllows, int32_t nIdx, uint32_t largestLeaf)
+{
+    return variantAllows && nIdx < kMaxPackedIdx && largestLeaf <= kMaxPackedLeaf;
+}
+// A BLAS whose traversal needs more than RT_BVH4_STACK entries (BVH2: its height in edges) is refused: by rt_upload_scene
+// (validate_scene), by rt_rebuild_scene for a tree it has just built, and by the host restatement rth_rebuild alike
+LB_HD bool exceeds_stack(int64_t need) { return need > (int64_t)RT_BVH4_STACK; }
+// LDS stack entries of a context whose deepest BLAS needs `need` (not exceeds_stack(need), checked by the caller)
+LB_HD int stack_entries(int need)
+{
+    const int e = need + 1 > kMinStackEntries ? need + 1 : kMinStackEntries;
+    return e < RT_BVH4_STACK ? e : RT_BVH4_STACK;
+}
+
+// ---- BLAS ranges (host only) ------------------------------------------------------------------------------------------------------
+// A scene can be rebuilt BLAS by BLAS when the primitives each distinct BLAS references form one contiguous range (a primitive may be
+// referenced several times, as SBVH leaves do), the ranges are disjoint and they come in the order of the roots - what appending BLAS
+// after BLAS (BVH2::BuildBLAS) produces.  ranges: one per distinct BLAS in increasing order; instBlas[i]: the range of instance i.
+// Returns NULL or why the scene is not of that shape.  Checks every index it follows.
+struct BlasRange { uint32_t root, first, count; };
+inline const char* find_blas_ranges(const RtBVHNode2* n, int32_t nNodes, const uint32_t* primIdx, int32_t nIdx, int32_t nPrims,
+                                    const RtBVHInstance* inst, int32_t nInst, std::vector<BlasRange>& ranges, std::vector<int32_t>& instBlas)
+{
+    ranges.clear(); instBlas.assign((size_t)(nInst > 0 ? nInst : 0), -1);
+    if (!n || !primIdx || !inst || nNodes <= 0 || nIdx <= 0 || nPrims <= 0 || nInst <= 0) return "missing array";
+    std::vector<int32_t> owner((size_t)nPrims, -1), rootBlas((size_t)nNodes, -1);
+    std::vector<uint8_t> seen((size_t)nNodes, 0);
+    std::vector<uint32_t> stack;
+    for (int32_t b = 0; b < nInst; b++) {
+        const uint32_t root = inst[b].bvhIdx;
+        if (root >= (uint32_t)nNodes) return "an instance's bvhIdx is out of range";
+        if (rootBlas[root] >= 0) { instBlas[(size_t)b] = rootBlas[root]; continue; }
+        if (seen[root]) return "a BLAS root is also a node of another BLAS";
+        const int32_t k = (int32_t)ranges.size();
+        rootBlas[root] = k; instBlas[(size_t)b] = k;
+        uint32_t lo = kNone, hi = 0, distinct = 0;
+        stack.assign(1, root); seen[root] = 1;
+        while (!stack.empty()) {
+            const uint32_t i = stack.back(); stack.pop_back();
+            if (n[i].count > 0) {
+                if ((uint64_t)n[i].first + n[i].count > (uint64_t)nIdx) return "a leaf range exceeds primIdx";
+                for (uint32_t s = n[i].first; s < n[i].first + n[i].count; s++) {
+                    const uint32_t p = primIdx[s];
+                    if (p >= (uint32_t)nPrims) return "primIdx out of range";
+                    if (owner[p] == k) continue;
+                    if (owner[p] >= 0) return "two BLAS reference the same primitive";
+                    owner[p] = k; distinct++;
+                    if (p < lo) lo = p;
+                    if (p > hi) hi = p;
+                }
+                continue;
+            }
+            for (uint32_t c = n[i].first; c <= n[i].first + 1; c++) {
+                if (c >= (uint32_t)nNodes || c < n[i].first) return "a child index is out of range";
+                if (seen[c]) return "a node is reachable twice";
+                seen[c] = 1; stack.push_back(c);
+            }
+        }
+        if (distinct == 0 || hi - lo + 1 != distinct) return "the primitives of a BLAS are not one contiguous range";
+        ranges.push_back(BlasRange{ root, lo, distinct });
+    }
+    // in the order of the roots
+    std::vector<int32_t> byFirst(ranges.size());
+    for (size_t k = 0; k < ranges.size(); k++) byFirst[k] = (int32_t)k;
+    for (size_t a = 1; a < byFirst.size(); a++)   // insertion sort by range start (few BLAS, usually sorted already)
+        for (size_t j = a; j > 0 && ranges[(size_t)byFirst[j]].first < ranges[(size_t)byFirst[j - 1]].first; j--) std::swap(byFirst[j], byFirst[j - 1]);
+    for (size_t a = 1; a < byFirst.size(); a++)
+        if (ranges[(size_t)byFirst[a]].root < ranges[(size_t)byFirst[a - 1]].root) return "the primitive ranges are not in the order of the BLAS roots";
+    std::vector<BlasRange> sorted(ranges.size());
+    std::vector<int32_t> newOf(ranges.size());
+    for (size_t a = 0; a < byFirst.size(); a++) { sorted[a] = ranges[(size_t)byFirst[a]]; newOf[(size_t)byFirst[a]] = (int32_t)a; }
+    ranges.swap(sorted);
+    for (int32_t& v : instBlas) v = newOf[(size_t)v];
+    return nullptr;
+}
+
+} // namespace rebuild

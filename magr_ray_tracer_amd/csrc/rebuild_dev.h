@@ -1,0 +1,29 @@
+// rebuild_dev.h — the interface between rt355.hip's rt_rebuild_scene and rebuild.hip's kernels.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../include/rt355.h"
+
+namespace rebuilddev {
+
+constexpr uint32_t kMaxLevels = RT_BVH4_STACK;     // a BLAS deeper than the traversal stack is refused before it is numbered
+// the counter words (Work::ctr): frontier sizes and first pair ids per level, then the status words the host reads
+constexpr uint32_t kCnt = 0, kBase = kMaxLevels + 2, kStatus = 2 * (kMaxLevels + 2), kLargestLeaf = kStatus + 1, kCtrWords = kStatus + 2;
+constexpr uint32_t kWalk = 1;                      // status bit: the walk did not end where the builder said (an inconsistent tree)
+
+// scratch of the derivation, sized for a scene of nPrims primitives: flags / ranks / newId 2 * nPrims words, frontA / frontB frontCap
+// (>= nPrims) words, ctr kCtrWords words, scan: scan_bytes(2 * nPrims)
+struct Work { uint32_t *flags, *ranks, *newId, *frontA, *frontB, *ctr; uint32_t frontCap; void* scan; size_t scanBytes; };
+
+hipError_t scan_bytes(uint32_t items, hipStream_t s, size_t* bytes);
+// zeroes the counters and clears the parent links of nodes [0, nNodes)
+hipError_t begin(hipStream_t s, const Work& w, uint32_t* parent, uint32_t nNodes);
+// numbers the interior nodes of the BLAS at `root` (height `depth`, `interiors` interior nodes) from pair id pairBase on: newId,
+// pairNode, parent links
+hipError_t number_blas(hipStream_t s, const Work& w, const RtBVHNode2* nodes, uint32_t nNodes, uint32_t root, uint32_t interiors, uint32_t depth,
+                       uint32_t pairBase, uint32_t pairCap, uint32_t* pairNode, uint32_t* parent);
+// the leaf list, and (pairs != NULL: layout 1) the pair records and the instances' root entries
+hipError_t finish(hipStream_t s, const Work& w, const RtBVHNode2* nodes, uint32_t nNodes, uint32_t nPairs, uint32_t nLeaves, const RtBVHInstance* inst,
+                  uint32_t nInst, const uint32_t* pairNode, RtFloat4* pairs, uint32_t* rootEntry, uint32_t* leaves);
+
+} // namespace rebuilddev

@@ -17,6 +17,9 @@
 #include "../../include/rt355.h"
 #include "rt355_kernels.h"
 #include "refit_common.h"
+#include "rebuild_common.h"
+#include "rebuild_dev.h"
+#include "build_cores.h"
 
 using namespace rt355dev;
 
@@ -58,13 +61,35 @@ struct SceneBag {
     // staging of an update (allocated by the first one): nothing live is written before the new TLAS has passed
     RtPrimitive* sPrims = nullptr; RtBVHNode2* sNodes = nullptr; RtBVHInstance* sInst = nullptr; RtTLASNode* sTlas = nullptr;
     RtFloat4 *sTp = nullptr, *sTpP = nullptr, *sIr = nullptr; int32_t* sStatus = nullptr;
+    size_t sNodesCap = 0;                     // records sNodes holds (a rebuild changes the node count)
     hipStream_t stream = nullptr;             // where updates run
     hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };   // brackets of the staging and of the commit
+    // rt_rebuild_scene: what it needs of the upload, and its device memory (allocated by the first rebuilds, then reused)
+    const char* rebuildRefusal = nullptr;     // why this scene cannot be rebuilt in place (NULL: it can)
+    std::vector<rebuild::BlasRange> ranges;   // the primitive range of every distinct BLAS, in increasing order
+    std::vector<int32_t> instBlas;            // instance -> its range
+    bool variantLayout1 = false;              // the holders' extend_variant admits the derived layout 1
+    int stackEntries = RT_BVH2_STACK, nInterior = 0;   // what the holders take over after a rebuild (sync_scene_config)
+    // Everything a rebuild changes, twice at capacity (2 * nPrims nodes, nPrims indices bound every tree of both builders): a rebuild
+    // writes the set that is not live and the commit swaps the pointers; the upload's own arrays stay behind until the copy is freed.
+    struct RebuildSet {
+        bool allocated = false;
+        RtPrimitive* prims = nullptr; RtBVHNode2* nodes = nullptr; uint32_t* primIdx = nullptr; RtBVHInstance* blas = nullptr; RtTLASNode* tlas = nullptr;
+        RtFloat4 *tp = nullptr, *tpP = nullptr, *ir = nullptr, *pairs = nullptr, *triRecs = nullptr, *shadeRecs = nullptr, *lightRecs = nullptr;
+        uint32_t *rootEntry = nullptr, *parent = nullptr, *leaves = nullptr, *tickets = nullptr, *pairNode = nullptr;
+    } rset[2];
+    int rnext = 0;                            // the set the next rebuild writes
+    void* rwork = nullptr; size_t rworkBytes = 0;   // the builders' workspace (grown on demand)
+    rebuilddev::Work dw{};                    // scratch of the derivation
+    int32_t* rStatus = nullptr;               // k_tlas_build's status words
+    hipEvent_t rev[4] = { nullptr, nullptr, nullptr, nullptr };
     ~SceneBag()
     {
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamDestroy(stream);
         for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : rev) if (e) (void)hipEventDestroy(e);
+        if (rwork) (void)hipFree(rwork);
         for (void* p : allocs) (void)hipFree(p);
     }
 };
@@ -90,7 +115,7 @@ struct RtCtx {
     struct Ev { hipEvent_t a, b; int stage; };
     std::vector<Ev> evPool; size_t evUsed = 0;
     RtStageTimes times{};
-    int maxDepth2 = 0, tlasDepth = 0;
+    int tlasDepth = 0;
     int layout = 0;   // 0 = traverse the reference arrays as uploaded, 1 = derived pair/triangle-record layout
     int trav = 0;           // the traversal kernels (Traversal, set by configure_traversal)
     int coherent = 1;       // RT355_COHERENT: wave-uniform node records through the scalar cache on bounce 0 (1), every bounce of the TLAS kernel (2, lab), off (0)
@@ -506,7 +531,7 @@ static int validate_scene(int accel, const RtPrimitive* prims, int32_t nPrims, c
         int need = accel == RT_ACCEL_BVH4 ? bvh4_stack_need((const RtBVHNode4*)bvhNodes, nNodes, blas[b].bvhIdx)
                                           : bvh2_depth((const RtBVHNode2*)bvhNodes, nNodes, blas[b].bvhIdx);
         if (need < 0) return fail(RT_E_INVALID, "instance %d: malformed BVH (child index out of range or cycle)", b);
-        if (need > stackCap) return fail(RT_E_UNSUPPORTED, "instance %d: traversal needs %d stack entries, at most %d are supported", b, need, stackCap);
+        if (rebuild::exceeds_stack(need)) return fail(RT_E_UNSUPPORTED, "instance %d: traversal needs %d stack entries, at most %d are supported", b, need, stackCap);
         stackNeed = std::max(stackNeed, need);
     }
     if (accel == RT_ACCEL_BVH2) {
@@ -518,7 +543,7 @@ static int validate_scene(int accel, const RtPrimitive* prims, int32_t nPrims, c
         for (int32_t i = 0; i < nNodes; i++) for (int k = 0; k < 4; k++) if (n4[i].first[k] != RT_INVALID && n4[i].count[k] > 0 &&
             (int64_t)n4[i].first[k] + n4[i].count[k] > (int64_t)nIdx) return fail(RT_E_INVALID, "bvh4 node %d: leaf range exceeds primIdx", i);
     }
-    if (stackEntriesOut) *stackEntriesOut = std::min(stackCap, std::max(stackNeed + 1, 6)); // >= 6: flush_counters reuses 36 words of it
+    if (stackEntriesOut) *stackEntriesOut = rebuild::stack_entries(stackNeed);   // (rebuild_common.h: rt_rebuild_scene sizes it the same way)
     if (texPadOut) *texPadOut = texPad;
     if (tlasDepthOut) *tlasDepthOut = tlasDepth;
     return RT_OK;
@@ -534,8 +559,8 @@ extern "C" int rt_validate_scene(int32_t accel, const RtPrimitive* prims, int32_
 
 // What rt_update_scene needs of an upload: the counts, the host shadow of the fields an update must keep, and the refit topology on
 // the device (parents, reachable leaves, pair id -> node id).  A scene the update cannot handle records why (refitRefusal).
-static int prepare_update(RtCtx* ctx, const DevScene& sc, const RtPrimitive* prims, int32_t nPrims, const void* bvhNodes, int32_t nNodes, int32_t nIdx,
-                          int32_t nLights, int32_t nTlas, const RtBVHInstance* blas, int32_t nBlas, const std::vector<uint32_t>& pairNode, int tlasDepth)
+static int prepare_update(RtCtx* ctx, const DevScene& sc, const RtPrimitive* prims, int32_t nPrims, const void* bvhNodes, int32_t nNodes, const uint32_t* primIdx,
+                          int32_t nIdx, int32_t nLights, int32_t nTlas, const RtBVHInstance* blas, int32_t nBlas, const std::vector<uint32_t>& pairNode, int tlasDepth)
 {
     SceneBag& b = *ctx->scene;
     b.sc = sc;
@@ -549,6 +574,10 @@ static int prepare_update(RtCtx* ctx, const DevScene& sc, const RtPrimitive* pri
     b.primType.resize((size_t)nPrims); b.primMat.resize((size_t)nPrims);
     for (int32_t i = 0; i < nPrims; i++) { b.primType[(size_t)i] = prims[i].objType; b.primMat[(size_t)i] = prims[i].matIdx; }
     b.inst.assign(blas, blas + nBlas);
+    b.variantLayout1 = ctx->cfg.extend_variant != 1;
+    {   // rt_rebuild_scene: the primitive range of each BLAS (rebuild_common.h)
+        b.rebuildRefusal = rebuild::find_blas_ranges((const RtBVHNode2*)bvhNodes, nNodes, primIdx, nIdx, nPrims, blas, nBlas, b.ranges, b.instBlas);
+    }
     b.nLeaves = (uint32_t)t.leaves.size(); b.nReach = (uint32_t)t.order.size();
     int rc = dalloc(b.allocs, &b.dParent, t.parent.size());
     if (rc == RT_OK) rc = dalloc(b.allocs, &b.dLeaves, t.leaves.size());
@@ -620,11 +649,11 @@ extern "C" int rt_upload_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t nPr
     // Derived layout 1 (rt355_kernels.h, traverse_bvh2_packed): only for BVH2, when the encodings fit.
     ctx->layout = 0;
     std::vector<uint32_t> pairNode;   // pair id -> node id (rt_update_scene rewrites the pairs' boxes)
-    if (rc == RT_OK && ctx->cfg.accel == RT_ACCEL_BVH2 && ctx->cfg.extend_variant != 1 && nIdx < (1 << 24)) {
+    if (rc == RT_OK && ctx->cfg.accel == RT_ACCEL_BVH2) {   // (the rules: rebuild_common.h, shared with rt_rebuild_scene's kernels)
         const RtBVHNode2* n2 = (const RtBVHNode2*)bvhNodes;
-        bool fits = true;
-        for (int32_t i = 0; i < nNodes && fits; i++) if (n2[i].count > 127) fits = false;
-        if (fits) {
+        uint32_t largestLeaf = 0;
+        for (int32_t i = 0; i < nNodes; i++) largestLeaf = std::max(largestLeaf, n2[i].count);
+        if (rebuild::takes_layout1(ctx->cfg.extend_variant != 1, nIdx, largestLeaf)) {
             // Interior nodes are renumbered breadth-first, BLAS by BLAS, and stored densely: the reference array interleaves leaves
             // and interior nodes (children are allocated in pairs), so a table indexed by the reference's node id would be half
             // holes; breadth-first puts the top levels of the (first) tree, which every ray visits, into the first records.
@@ -641,19 +670,14 @@ extern "C" int rt_upload_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t nPr
                         if (n2[c].count == 0 && newId[c] == 0xffffffffu) { newId[c] = (uint32_t)order.size(); order.push_back(c); }
                 }
             }
-            auto entry = [&](uint32_t i) { return n2[i].count > 0 ? (0x80000000u | (n2[i].count << 24) | n2[i].first) : newId[i]; };
-            auto f2u = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
             std::vector<float4> pairs(std::max<size_t>(order.size(), 1) * 4, make_float4(0, 0, 0, 0));
-            for (size_t k = 0; k < order.size(); k++) {   // (box rule: refit_common.h, k_pair_boxes rewrites them)
-                const uint32_t i = order[k];
-                refit::pair_boxes(n2[n2[i].first], n2[n2[i].first + 1], (RtFloat4*)&pairs[k * 4]);
-                pairs[k * 4 + 3] = make_float4(f2u(entry(n2[i].first)), f2u(entry(n2[i].first + 1)), 0, 0);
-            }
+            for (size_t k = 0; k < order.size(); k++)   // (box rule: refit_common.h, k_pair_boxes rewrites them)
+                rebuild::pair_record(n2, order[k], newId.data(), (RtFloat4*)&pairs[k * 4]);
             std::vector<float4> recs((size_t)nIdx * 3);
             for (int32_t s = 0; s < nIdx; s++) refit::tri_rec(prims[primIdx[s]], primIdx[s], (RtFloat4*)&recs[(size_t)s * 3]);   // refit_common.h
             pairNode = order;
             std::vector<uint32_t> roots((size_t)nBlas);
-            for (int32_t b = 0; b < nBlas; b++) roots[b] = entry(blas[b].bvhIdx);
+            for (int32_t b = 0; b < nBlas; b++) roots[b] = rebuild::child_entry(n2[blas[b].bvhIdx], newId[blas[b].bvhIdx]);
             rc = upload(ctx, &sc.pairs, pairs.data(), pairs.size());
             if (rc == RT_OK) rc = upload(ctx, &sc.triRecs, recs.data(), recs.size());
             if (rc == RT_OK) rc = upload(ctx, &sc.rootEntry, roots.data(), roots.size());
@@ -726,11 +750,12 @@ extern "C" int rt_upload_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t nPr
     }
     if (rc != RT_OK) { scene_release(ctx); ctx->sceneLoaded = false; return rc; }
     sc.nLights = nLights; sc.nPrims = nPrims; sc.nBlas = nBlas; sc.nTex = nTexels;
-    rc = prepare_update(ctx, sc, prims, nPrims, bvhNodes, nNodes, nIdx, nLights, nTlas, blas, nBlas, pairNode, tlasDepth);
+    rc = prepare_update(ctx, sc, prims, nPrims, bvhNodes, nNodes, primIdx, nIdx, nLights, nTlas, blas, nBlas, pairNode, tlasDepth);
     if (rc != RT_OK) { scene_release(ctx); ctx->sceneLoaded = false; return rc; }
     ctx->singleBlas = tlas[0].leftRight == 0;
     ctx->sc = sc;
     ctx->stackEntries = stackEntries; ctx->tlasDepth = tlasDepth; ctx->nInterior = nInterior;
+    ctx->scene->stackEntries = stackEntries; ctx->scene->nInterior = nInterior;
     rc = configure_traversal(ctx);
     if (rc != RT_OK) { scene_release(ctx); return rc; }
     ctx->sceneLoaded = true;
@@ -851,6 +876,7 @@ extern "C" int rt_share_scene(RtCtx* ctx, RtCtx* from)
     if (!ctx || !from) return fail(RT_E_INVALID, "rt_share_scene: null context");
     if (ctx == from) return RT_OK;
     if (!from->sceneLoaded) return fail(RT_E_INVALID, "rt_share_scene: the source context has no scene");
+    if (const int rc = sync_scene_config(from)) return rc;   // (a rebuild may have swapped the arrays since `from` last launched)
     if (ctx->cfg.device != from->cfg.device) return fail(RT_E_INVALID, "rt_share_scene: contexts on different devices (%d, %d)", ctx->cfg.device, from->cfg.device);
     if (ctx->cfg.accel != from->cfg.accel || ctx->cfg.extend_variant != from->cfg.extend_variant)
         return fail(RT_E_INVALID, "rt_share_scene: the contexts differ in accel / extend_variant, which the derived layout depends on");
@@ -859,7 +885,7 @@ extern "C" int rt_share_scene(RtCtx* ctx, RtCtx* from)
     ctx->sceneLoaded = false;
     scene_hold(ctx, from->scene);
     ctx->sc = from->sc;
-    ctx->layout = from->layout; ctx->maxDepth2 = from->maxDepth2; ctx->stackEntries = from->stackEntries; ctx->singleBlas = from->singleBlas; ctx->tlasDepth = from->scene->tlasDepth; ctx->nInterior = from->nInterior;
+    ctx->layout = from->layout; ctx->stackEntries = from->stackEntries; ctx->singleBlas = from->singleBlas; ctx->tlasDepth = from->scene->tlasDepth; ctx->nInterior = from->nInterior;
     const int rc = configure_traversal(ctx);
     if (rc != RT_OK) { scene_release(ctx); return rc; }
     ctx->sceneLoaded = true;
@@ -883,6 +909,8 @@ static int sync_scene_config(RtCtx* ctx)
 {
     if (!ctx->scene || ctx->sceneGen == ctx->scene->generation) return RT_OK;
     ctx->tlasDepth = ctx->scene->tlasDepth;
+    ctx->sc = ctx->scene->sc;   // a rebuild swaps the arrays and changes the trees' depth and pair count
+    ctx->stackEntries = ctx->scene->stackEntries; ctx->nInterior = ctx->scene->nInterior;
     const int rc = configure_traversal(ctx);
     if (rc != RT_OK) return rc;
     ctx->sceneGen = ctx->scene->generation;
@@ -916,7 +944,8 @@ static int update_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, in
     // ---- staging buffers (first update)
     if (!b.sPrims) {
         int rc = dalloc(b.allocs, &b.sPrims, (size_t)b.nPrims);
-        if (rc == RT_OK) rc = dalloc(b.allocs, &b.sNodes, (size_t)b.nNodes);
+        b.sNodesCap = (size_t)std::max(b.nNodes, 2 * b.nPrims);   // (room for every tree a rebuild can bind later)
+        if (rc == RT_OK) rc = dalloc(b.allocs, &b.sNodes, b.sNodesCap);
         if (rc == RT_OK) rc = dalloc(b.allocs, &b.sInst, (size_t)b.nBlas);
         if (rc == RT_OK) rc = dalloc(b.allocs, &b.sTlas, (size_t)b.nTlas);
         if (rc == RT_OK) rc = dalloc(b.allocs, &b.sTp, (size_t)b.nTlas * 4);
@@ -924,8 +953,8 @@ static int update_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, in
         if (rc == RT_OK) rc = dalloc(b.allocs, &b.sIr, (size_t)b.nBlas * 4);
         if (rc == RT_OK) rc = dalloc(b.allocs, &b.sStatus, 2);
         if (rc != RT_OK) { b.sPrims = nullptr; return rc; }
-        HIPCHK(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));
-        for (hipEvent_t& e : b.ev) HIPCHK(hipEventCreate(&e));
+        if (!b.stream) HIPCHK(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));   // (a rebuild may have made it already)
+        for (hipEvent_t& e : b.ev) if (!e) HIPCHK(hipEventCreate(&e));
     }
     const DevScene& sc = b.sc;
     hipStream_t s = b.stream;
@@ -990,6 +1019,226 @@ extern "C" int rt_group_update_scene(RtGroup* g, const RtPrimitive* prims, int32
 {
     if (!g) return fail(RT_E_INVALID, "rt_group_update_scene: null group");
     return rt_update_scene(rt_group_lane(g, 0), prims, first, count, blas, nBlas, stats);   // every lane holds lane 0's copy
+}
+// ---- in-place rebuilds (rt_rebuild_scene; builders: sah.hip / lbvh.hip, derivation: rebuild.hip, rules: rebuild_common.h) ----------
+static int rebuild_alloc(SceneBag& b, SceneBag::RebuildSet& t)
+{
+    const size_t nP = (size_t)b.nPrims, nB = (size_t)b.nBlas, nT = (size_t)b.nTlas, nL = std::max<size_t>((size_t)b.nLights, 1);
+    int rc = RT_OK;
+    // every piece is made once: a call that ran out of memory half way is taken up where it stopped
+    auto need = [&](auto** p, size_t count) { if (rc == RT_OK && !*p) rc = dalloc(b.allocs, p, count); };
+    if (!b.stream) HIPCHK(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));
+    for (hipEvent_t& e : b.rev) if (!e) HIPCHK(hipEventCreate(&e));
+    // the scratch both sets share
+    if (!b.dw.scanBytes) HIPCHK(rebuilddev::scan_bytes((uint32_t)(2 * nP), b.stream, &b.dw.scanBytes));
+    char* scan = (char*)b.dw.scan;
+    need(&b.dw.flags, 2 * nP); need(&b.dw.ranks, 2 * nP); need(&b.dw.newId, 2 * nP); need(&b.dw.frontA, nP); need(&b.dw.frontB, nP);
+    need(&scan, b.dw.scanBytes); need(&b.rStatus, 2); need(&b.dw.ctr, rebuilddev::kCtrWords);
+    b.dw.scan = scan; b.dw.frontCap = (uint32_t)nP;
+    if (rc != RT_OK || t.allocated) return rc;
+    need(&t.prims, nP); need(&t.nodes, 2 * nP); need(&t.primIdx, nP); need(&t.blas, nB); need(&t.tlas, nT);
+    need(&t.tp, nT * 4); need(&t.tpP, nT * 4); need(&t.ir, nB * 4); need(&t.pairs, nP * 4); need(&t.triRecs, nP * 3);
+    need(&t.shadeRecs, nP); need(&t.lightRecs, nL * 8); need(&t.rootEntry, nB); need(&t.parent, 2 * nP); need(&t.leaves, nP);
+    need(&t.tickets, 2 * nP); need(&t.pairNode, nP);
+    if (rc != RT_OK) return rc;
+    t.allocated = true;
+    return RT_OK;
+}
+
+static double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b)
+{
+    return std::chrono::duration<double, std::milli>(b - a).count();
+}
+
+static int rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
+                         int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats)
+{
+    using clock = std::chrono::steady_clock;
+    const auto t0 = clock::now();
+    const char* who = "rt_rebuild_scene";
+    // ---- refusals that need no device work
+    if (b.refitRefusal) return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: %s", b.refitRefusal);
+    if (b.rebuildRefusal) return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: %s", b.rebuildRefusal);
+    if (builder != RT_REBUILD_SAH && builder != RT_REBUILD_LBVH) return fail(RT_E_INVALID, "rt_rebuild_scene: unknown builder %d", builder);
+    if (count < 0 || (count > 0 && !prims)) return fail(RT_E_INVALID, "rt_rebuild_scene: bad primitive count %d / NULL records", count);
+    if (count > 0 && (first < 0 || (int64_t)first + count > (int64_t)b.nPrims))
+        return fail(RT_E_INVALID, "rt_rebuild_scene: primitive range [%d, %lld) outside the %d uploaded", first, (long long)first + count, b.nPrims);
+    for (int32_t i = 0; i < count; i++) {
+        const size_t g = (size_t)first + (size_t)i;
+        if (prims[i].objType != b.primType[g] || prims[i].matIdx != b.primMat[g])
+            return fail(RT_E_INVALID, "rt_rebuild_scene: primitive %zu changes its objType / matIdx (%d / %d -> %d / %d)", g,
+                        b.primType[g], b.primMat[g], prims[i].objType, prims[i].matIdx);
+    }
+    if (blas) {
+        if (nBlas != b.nBlas) return fail(RT_E_INVALID, "rt_rebuild_scene: %d instances given, %d uploaded", nBlas, b.nBlas);
+        for (int32_t k = 0; k < nBlas; k++) {
+            if (blas[k].bvhIdx != b.inst[(size_t)k].bvhIdx) return fail(RT_E_INVALID, "rt_rebuild_scene: instance %d changes its bvhIdx", k);
+            if (refit::singular(blas[k].invT)) return fail(RT_E_INVALID, "rt_rebuild_scene: instance %d: the transform is singular", k);
+        }
+    }
+    HIPCHK(hipSetDevice(b.device));
+    SceneBag::RebuildSet& t = b.rset[b.rnext];
+    if (const int rc = rebuild_alloc(b, t)) return rc;
+    hipStream_t s = b.stream;
+    // the builders' own argument checks, BLAS by BLAS (the arrays are the set's: node and index ids as the host appends BLAS after BLAS)
+    lbvh::Params P{};
+    {
+        uint32_t nodeBase = 0, idxBase = 0;
+        for (const rebuild::BlasRange& r : b.ranges) {
+            const int32_t cap = 2 * (int32_t)r.count - 1;
+            const char* msg = builder == RT_REBUILD_SAH ? sahdev::check_args(b.nPrims, (int32_t)r.first, (int32_t)r.count, nodeBase, idxBase)
+                                                        : lbvhdev::check_args(opts, b.nPrims, (int32_t)r.first, (int32_t)r.count, nodeBase, idxBase, P);
+            if (msg) return fail(RT_E_INVALID, "rt_rebuild_scene: %s", msg);
+            nodeBase += (uint32_t)cap; idxBase += r.count;
+        }
+    }
+    {   // the builders' workspace
+        size_t need = 0;
+        for (const rebuild::BlasRange& r : b.ranges) {
+            size_t bytes = 0;
+            const int rc = builder == RT_REBUILD_SAH ? sahdev::work_bytes(who, r.count, s, &bytes) : lbvhdev::work_bytes(who, r.count, s, &bytes);
+            if (rc != RT_OK) return rc;
+            need = std::max(need, bytes);
+        }
+        if (need > b.rworkBytes) {
+            HIPCHK(hipStreamSynchronize(s));
+            if (b.rwork) (void)hipFree(b.rwork);
+            b.rwork = nullptr; b.rworkBytes = 0;
+            if (hipMalloc(&b.rwork, need) != hipSuccess) { b.rwork = nullptr; return fail(RT_E_NOMEM, "rt_rebuild_scene: %zu bytes of builder workspace", need); }
+            b.rworkBytes = need;
+        }
+    }
+    const DevScene& sc = b.sc;
+    // ---- stage: the new primitives into the set that is not live
+    HIPCHK(hipEventRecord(b.rev[0], s));
+    HIPCHK(hipMemcpyAsync(t.prims, sc.prims, sizeof(RtPrimitive) * (size_t)b.nPrims, hipMemcpyDeviceToDevice, s));
+    if (count) HIPCHK(hipMemcpyAsync(t.prims + first, prims, sizeof(RtPrimitive) * (size_t)count, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(t.lightRecs, sc.lightRecs, sizeof(float4) * 8 * std::max<size_t>((size_t)b.nLights, 1), hipMemcpyDeviceToDevice, s));   // (the emittance words stay)
+    const auto t1 = clock::now();
+    // ---- every BLAS anew, in the order of the ranges
+    const size_t nR = b.ranges.size();
+    std::vector<uint32_t> rootOf(nR), interiors(nR), depth(nR);
+    uint32_t nNodes = 0, nIdx = 0, maxDepth = 0;
+    for (size_t k = 0; k < nR; k++) {
+        const rebuild::BlasRange& r = b.ranges[k];
+        Built built{};
+        const int rc = builder == RT_REBUILD_SAH
+            ? sahdev::build(who, s, b.rwork, t.prims + r.first, r.count, r.first, nNodes, nIdx, t.nodes + nNodes, t.primIdx + nIdx, nullptr, nullptr, &built)
+            : lbvhdev::build(who, s, b.rwork, P, t.prims + r.first, r.count, r.first, nNodes, nIdx, t.nodes + nNodes, t.primIdx + nIdx, nullptr, nullptr, &built);
+        if (rc != RT_OK) return rc;
+        if (built.nodes == 0 || (built.nodes & 1u) == 0 || built.nodes > 2 * r.count - 1)
+            return fail(RT_E_DEVICE, "rt_rebuild_scene: inconsistent builder result (%u nodes for %u primitives)", built.nodes, r.count);
+        if ((built.depth == 0) != (built.nodes == 1))
+            return fail(RT_E_DEVICE, "rt_rebuild_scene: inconsistent builder result (height %u with %u nodes)", built.depth, built.nodes);
+        if (rebuild::exceeds_stack(built.depth))   // validate_scene's rule
+            return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: the new BLAS %zu needs %u stack entries, at most %d are supported; the scene is unchanged", k,
+                        built.depth, RT_BVH4_STACK);
+        rootOf[k] = nNodes; interiors[k] = (built.nodes - 1) / 2; depth[k] = built.depth;
+        maxDepth = std::max(maxDepth, built.depth);
+        nNodes += built.nodes; nIdx += r.count;
+    }
+    const auto t2 = clock::now();
+    // ---- the instances (host: at most 256 records), then everything upload derives
+    std::vector<RtBVHInstance> inst = b.inst;
+    if (blas) inst.assign(blas, blas + nBlas);
+    for (int32_t i = 0; i < b.nBlas; i++) inst[(size_t)i].bvhIdx = rootOf[(size_t)b.instBlas[(size_t)i]];
+    HIPCHK(hipMemcpyAsync(t.blas, inst.data(), sizeof(RtBVHInstance) * (size_t)b.nBlas, hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(b.rev[1], s));
+    HIPCHK(rebuilddev::begin(s, b.dw, t.parent, nNodes));
+    uint32_t nPairs = 0;
+    {   // pair ids: BLAS by BLAS in the order in which the instances first name them
+        std::vector<uint8_t> done(nR, 0);
+        for (int32_t i = 0; i < b.nBlas; i++) {
+            const size_t k = (size_t)b.instBlas[(size_t)i];
+            if (done[k]) continue;
+            done[k] = 1;
+            HIPCHK(rebuilddev::number_blas(s, b.dw, t.nodes, nNodes, rootOf[k], interiors[k], depth[k], nPairs, (uint32_t)b.nPrims, t.pairNode, t.parent));
+            nPairs += interiors[k];
+        }
+    }
+    const uint32_t nLeaves = nNodes - nPairs;
+    const bool layout1 = b.layout == 1;
+    HIPCHK(rebuilddev::finish(s, b.dw, t.nodes, nNodes, nPairs, nLeaves, t.blas, (uint32_t)b.nBlas, t.pairNode, layout1 ? t.pairs : nullptr, t.rootEntry, t.leaves));
+    HIPCHK(refitdev::launch_records(s, t.prims, t.nodes, t.primIdx, nIdx, sc.lights, (uint32_t)b.nLights, 0u, (uint32_t)b.nPrims, nullptr, 0u, nullptr,
+                                    layout1 ? t.triRecs : nullptr, t.shadeRecs, t.lightRecs));
+    HIPCHK(hipEventRecord(b.rev[2], s));
+    HIPCHK(refitdev::launch_tlas(s, t.nodes, t.blas, b.nBlas, layout1 ? t.rootEntry : nullptr, t.tlas, t.tp, t.tpP, t.ir, b.rStatus));
+    HIPCHK(hipEventRecord(b.rev[3], s));
+    int32_t status[2] = { 0, 0 };
+    uint32_t walk[2] = { 0, 0 };
+    HIPCHK(hipMemcpyAsync(status, b.rStatus, sizeof status, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(walk, b.dw.ctr + rebuilddev::kStatus, sizeof walk, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (walk[0]) return fail(RT_E_DEVICE, "rt_rebuild_scene: the breadth-first walk does not match the builder's tree (inconsistent device result)");
+    if (status[0] == 1) return fail(RT_E_INVALID, "rt_rebuild_scene: an instance transform is singular");
+    if (status[0] != 0) return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: the TLAS clustering found no partner (boxes of area >= RT_REALLYFAR or NaN)");
+    if (status[1] > RT_TLAS_STACK)
+        return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: the rebuilt TLAS is %d levels deep, the traversal stack holds %d; the scene is unchanged", status[1], RT_TLAS_STACK);
+    if (rebuild::takes_layout1(b.variantLayout1, (int32_t)nIdx, std::max(walk[1], 1u)) != layout1)
+        return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: the new trees would change the scene's derived layout (largest leaf %u primitives, %u index slots; "
+                    "layout %d is bound): upload the rebuilt scene instead; the scene is unchanged", walk[1], nIdx, b.layout);
+    const auto t3 = clock::now();
+    // ---- commit: swap the arrays once no kernel of a holder reads the old ones
+    for (RtCtx* h : b.holders) {
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (h->home != h->stream) HIPCHK(hipStreamSynchronize(h->home));
+    }
+    DevScene n = b.sc;
+    n.prims = t.prims; n.bvh2 = t.nodes; n.primIdx = t.primIdx; n.blas = t.blas; n.tlas = t.tlas;
+    n.tlasPairs = (const float4*)t.tp; n.tlasPairsP = (const float4*)t.tpP; n.instRecs = (const float4*)t.ir;
+    n.shadeRecs = (const float4*)t.shadeRecs; n.lightRecs = (const float4*)t.lightRecs;
+    if (layout1 && nPairs == 0) HIPCHK(hipMemsetAsync(t.pairs, 0, sizeof(float4) * 4, s));   // no interior node: one zero record, as at upload
+    if (layout1) { n.pairs = (const float4*)t.pairs; n.triRecs = (const float4*)t.triRecs; n.rootEntry = t.rootEntry; }
+    b.sc = n;
+    b.dParent = t.parent; b.dLeaves = t.leaves; b.dTickets = t.tickets; b.dPairNode = t.pairNode;
+    b.nNodes = (int32_t)nNodes; b.nIdx = (int32_t)nIdx; b.nPairs = layout1 ? (int32_t)nPairs : 0; b.nLeaves = nLeaves; b.nReach = nNodes;
+    b.inst = inst;
+    const bool reconfigure = status[1] != b.tlasDepth || rebuild::stack_entries((int)std::max(maxDepth, 1u)) != b.stackEntries;
+    b.tlasDepth = status[1];
+    b.stackEntries = rebuild::stack_entries((int)std::max(maxDepth, 1u));
+    b.nInterior = layout1 ? (int)nPairs : 0;
+    b.generation++;   // every holder takes the new arrays (and re-derives its traversal kernels) before its next launch
+    b.rnext ^= 1;
+    const auto t4 = clock::now();
+    if (stats) {
+        float ms = 0, derive = 0, tlas = 0;
+        (void)hipEventElapsedTime(&ms, b.rev[0], b.rev[3]); (void)hipEventElapsedTime(&derive, b.rev[1], b.rev[2]); (void)hipEventElapsedTime(&tlas, b.rev[2], b.rev[3]);
+        *stats = RtRebuildStats{};
+        stats->gpu_ms = ms; stats->wall_ms = ms_between(t0, t4);
+        stats->stage_ms = ms_between(t0, t1); stats->build_ms = ms_between(t1, t2); stats->derive_ms = derive; stats->tlas_ms = tlas;
+        stats->commit_ms = ms_between(t3, t4);
+        stats->prims = count; stats->blas_built = (int32_t)nR; stats->nodes = (int32_t)nNodes; stats->n_idx = (int32_t)nIdx;
+        stats->max_depth = (int32_t)maxDepth; stats->tlas_nodes = b.nTlas; stats->tlas_depth = status[1]; stats->reconfigured = reconfigure ? 1 : 0;
+    }
+    return RT_OK;
+}
+extern "C" int rt_rebuild_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
+                                int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats)
+{
+    if (!ctx) return fail(RT_E_INVALID, "rt_rebuild_scene: null context");
+    if (!ctx->sceneLoaded || !ctx->scene) return fail(RT_E_INVALID, "rt_rebuild_scene: no scene uploaded");
+    if (ctx->cfg.accel != RT_ACCEL_BVH2) return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: BVH4 contexts cannot rebuild in place (build on the host and upload instead)");
+    return rebuild_scene(*ctx->scene, prims, first, count, blas, nBlas, builder, opts, stats);
+}
+extern "C" int rt_group_rebuild_scene(RtGroup* g, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
+                                      int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats)
+{
+    if (!g) return fail(RT_E_INVALID, "rt_group_rebuild_scene: null group");
+    return rt_rebuild_scene(rt_group_lane(g, 0), prims, first, count, blas, nBlas, builder, opts, stats);   // every lane holds lane 0's copy
+}
+// The primitive range of every instance's BLAS (rebuild_common.h), for callers that want to know beforehand whether rt_rebuild_scene
+// will take a scene; no device needed.
+extern "C" int rt_blas_ranges(const RtBVHNode2* nodes, int32_t nNodes, const uint32_t* primIdx, int32_t nIdx, int32_t nPrims,
+                              const RtBVHInstance* blas, int32_t nBlas, int32_t* firstOut, int32_t* countOut)
+{
+    std::vector<rebuild::BlasRange> ranges; std::vector<int32_t> instBlas;
+    if (const char* why = rebuild::find_blas_ranges(nodes, nNodes, primIdx, nIdx, nPrims, blas, nBlas, ranges, instBlas))
+        return fail(why == std::string("missing array") ? RT_E_INVALID : RT_E_UNSUPPORTED, "rt_blas_ranges: %s", why);
+    for (int32_t i = 0; i < nBlas; i++) {
+        if (firstOut) firstOut[i] = (int32_t)ranges[(size_t)instBlas[(size_t)i]].first;
+        if (countOut) countOut[i] = (int32_t)ranges[(size_t)instBlas[(size_t)i]].count;
+    }
+    return RT_OK;
 }
 extern "C" int rt_debug_get_scene_array(RtCtx* ctx, int32_t which, void* out, int64_t capacityBytes, int64_t* bytes)
 {

@@ -22,6 +22,7 @@
 #include <vector>
 #include "../../include/rt355.h"
 #include "sah_common.h"
+#include "build_cores.h"
 
 using namespace sah;
 
@@ -283,7 +284,7 @@ size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 dim3 grid(uint32_t threads) { return dim3((threads + kBlock - 1) / kBlock); }
 double ms_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
 
-// Everything one build allocates on the device; freed on every exit path.
+// Everything one rt_build_bvh2_sah call allocates on the device; freed on every exit path.
 struct Work {
     void* mem = nullptr;
     hipStream_t stream = nullptr;
@@ -299,10 +300,35 @@ struct Work {
     }
 };
 
+// The carved workspace of one build of n primitives (everything but the primitives and the output arrays)
+struct Carve {
+    size_t oSum, oP, oCur, oNxt, oNid, oNidN, oOwn, of, oF, oSA, oSB, oSout, oSn, oBn, ov, oV, oKA, oKB, oScan, scanBytes, total;
+};
+hipError_t carve_work(uint32_t n, hipStream_t s, Carve& c)
+{
+    const uint32_t cap = 2 * n - 1, bigMax = n / (kSmall + 1) + 1;
+    size_t scan32 = 0, scan64 = 0;
+    hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, scan32, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)(n + 1), s);
+    if (e != hipSuccess) return e;
+    e = hipcub::DeviceScan::ExclusiveSum(nullptr, scan64, (uint64_t*)nullptr, (uint64_t*)nullptr, (int)cap, s);
+    if (e != hipSuccess) return e;
+    c.scanBytes = scan32 > scan64 ? scan32 : scan64;
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { const size_t o = off; off += align_up(bytes); return o; };
+    c.oSum = carve(4 * sizeof(uint32_t)); c.oP = carve(n * sizeof(Prim));
+    c.oCur = carve(n * 4ull); c.oNxt = carve(n * 4ull); c.oNid = carve(n * 4ull); c.oNidN = carve(n * 4ull); c.oOwn = carve(n * 4ull);
+    c.of = carve((n + 1) * 4ull); c.oF = carve((n + 1) * 4ull); c.oSA = carve(n * 4ull); c.oSB = carve(n * 4ull); c.oSout = carve(n * 4ull);
+    c.oSn = carve(2ull * n * sizeof(LNode)); c.oBn = carve((size_t)cap * sizeof(BNode)); c.ov = carve(cap * 8ull); c.oV = carve(cap * 8ull);
+    c.oKA = carve((size_t)bigMax * kKeys * 8); c.oKB = carve((size_t)bigMax * (kKeys * 8 + kCnt * 4));
+    c.oScan = carve(c.scanBytes);
+    c.total = off;
+    return hipSuccess;
+}
+
 } // namespace
 
 #define SCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
-    return sfail(RT_E_DEVICE, "rt_build_bvh2_sah: %s failed: %s", #expr, hipGetErrorString(e_)); } while (0)
+    return sfail(RT_E_DEVICE, "%s: %s failed: %s", who, #expr, hipGetErrorString(e_)); } while (0)
 
 extern "C" int rt_debug_sah_phases(float* out)
 {
@@ -311,9 +337,119 @@ extern "C" int rt_debug_sah_phases(float* out)
     return RT_OK;
 }
 
+namespace sahdev {
+
+const char* check_args(int32_t nPrims, int32_t first, int32_t count, uint32_t nodeBase, uint32_t idxBase)
+{
+    static const RtPrimitive prim{}; static const RtBVHNode2 node{}; static const int32_t n = 0; static const uint32_t idx = 0;   // (only their presence is checked)
+    return sah::check_args(&prim, nPrims, first, count, nodeBase, idxBase, &node, count > 0 ? 2 * count - 1 : 0, &n, &idx);
+}
+
+int work_bytes(const char* who, uint32_t n, hipStream_t s, size_t* bytes)
+{
+    Carve c;
+    SCHK(carve_work(n, s, c));
+    *bytes = c.total;
+    return RT_OK;
+}
+
+// The build proper (build_cores.h): everything stays on the device; the host reads three words per level, then the root's record.
+int build(const char* who, hipStream_t stream, void* work, const RtPrimitive* dPrims, uint32_t n, uint32_t first, uint32_t nodeBase,
+          uint32_t idxBase, RtBVHNode2* dNodes, uint32_t* dIdx, hipEvent_t evBegin, hipEvent_t evEnd, Built* out)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint32_t cap = 2 * n - 1, bigMax = n / (kSmall + 1) + 1;
+    Carve c;
+    SCHK(carve_work(n, stream, c));
+    char* base = (char*)work;
+    auto at = [&](size_t o) { return (void*)(base + o); };
+    uint32_t* summary = (uint32_t*)at(c.oSum);
+    Prim* P = (Prim*)at(c.oP);
+    uint32_t *cur = (uint32_t*)at(c.oCur), *nxt = (uint32_t*)at(c.oNxt), *nid = (uint32_t*)at(c.oNid), *nidN = (uint32_t*)at(c.oNidN);
+    uint32_t *owner = (uint32_t*)at(c.oOwn), *f = (uint32_t*)at(c.of), *F = (uint32_t*)at(c.oF);
+    uint32_t *sA = (uint32_t*)at(c.oSA), *sB = (uint32_t*)at(c.oSB), *sout = (uint32_t*)at(c.oSout);
+    LNode* snodes = (LNode*)at(c.oSn);
+    BNode* bn = (BNode*)at(c.oBn);
+    uint64_t *v = (uint64_t*)at(c.ov), *V = (uint64_t*)at(c.oV), *keysA = (uint64_t*)at(c.oKA), *keysB = (uint64_t*)at(c.oKB);
+    size_t scanBytes = c.scanBytes;
+
+    const BNode root = open_node(0, n, 0);
+    SCHK(hipMemcpyAsync(bn, &root, sizeof root, hipMemcpyHostToDevice, stream));
+    SCHK(hipMemsetAsync(summary, 0, 4 * sizeof(uint32_t), stream));
+    if (evBegin) SCHK(hipEventRecord(evBegin, stream));
+    hipLaunchKernelGGL(k_sah_prims, grid(n), dim3(kBlock), 0, stream, dPrims, n, P, cur, nid, owner, summary + 2);
+    SCHK(hipGetLastError());
+    uint32_t hs[4] = { 0, 0, 0, 0 };
+    SCHK(hipMemcpyAsync(hs, summary, sizeof hs, hipMemcpyDeviceToHost, stream));
+    SCHK(hipStreamSynchronize(stream));   // (rt_build_bvh2_sah: nothing of the caller's host arrays is read after this point)
+    if (hs[2]) return sfail(RT_E_UNSUPPORTED, "%s: %s", who, status_text(hs[2]));
+    const double tPrims = ms_since(t0);
+
+    // level passes
+    std::vector<std::pair<uint32_t, uint32_t>> levels;
+    uint32_t lb = 0, le = 1, nBig = n > kSmall ? 1 : 0;
+    for (;;) {
+        levels.emplace_back(lb, le);
+        const uint32_t K = le - lb;
+        uint64_t *kmin = keysA, *bkmin = keysA + (size_t)nBig * 6, *kmax = keysB, *bkmax = keysB + (size_t)nBig * 6;
+        uint32_t* bcnt = (uint32_t*)(keysB + (size_t)nBig * kKeys);
+        if (nBig) {
+            SCHK(hipMemsetAsync(keysA, 0xff, (size_t)nBig * kKeys * 8, stream));
+            SCHK(hipMemsetAsync(keysB, 0, (size_t)nBig * (kKeys * 8 + kCnt * 4), stream));
+            hipLaunchKernelGGL(k_sah_reduce, grid(n), dim3(kBlock), 0, stream, P, cur, nid, bn, n, kmin, kmax, summary + 2);
+            hipLaunchKernelGGL(k_sah_bins, grid(n), dim3(kBlock), 0, stream, P, cur, nid, bn, n, kmin, kmax, bkmin, bkmax, bcnt, summary + 2);
+        }
+        hipLaunchKernelGGL(k_sah_decide, grid(K), dim3(kBlock), 0, stream, bn, lb, le, kmin, kmax, bkmin, bkmax, bcnt, summary + 2);
+        hipLaunchKernelGGL(k_sah_small, grid(K), dim3(kBlock), 0, stream, P, cur, bn, lb, le, sA, sB, sout, snodes, summary + 2);
+        hipLaunchKernelGGL(k_sah_flag, grid(n + 1), dim3(kBlock), 0, stream, P, cur, nid, bn, n, f);
+        SCHK(hipcub::DeviceScan::ExclusiveSum(at(c.oScan), scanBytes, f, F, (int)(n + 1), stream));
+        hipLaunchKernelGGL(k_sah_count, grid(K), dim3(kBlock), 0, stream, bn, lb, le, F, v);
+        SCHK(hipcub::DeviceScan::ExclusiveSum(at(c.oScan), scanBytes, v, V, (int)K, stream));
+        hipLaunchKernelGGL(k_sah_children, grid(K), dim3(kBlock), 0, stream, bn, lb, le, cap, v, V, summary);
+        hipLaunchKernelGGL(k_sah_scatter, grid(n), dim3(kBlock), 0, stream, cur, nid, bn, n, f, F, nxt, nidN, owner);
+        SCHK(hipGetLastError());
+        std::swap(cur, nxt);
+        std::swap(nid, nidN);
+        SCHK(hipMemcpyAsync(hs, summary, sizeof hs, hipMemcpyDeviceToHost, stream));
+        SCHK(hipStreamSynchronize(stream));
+        if (hs[2]) return sfail(RT_E_UNSUPPORTED, "%s: %s", who, status_text(hs[2]));
+        if (hs[0] == 0) break;
+        if ((uint64_t)le + 2ull * hs[0] > cap || hs[1] > bigMax)
+            return sfail(RT_E_DEVICE, "%s: inconsistent device result (%u splits, %u open nodes)", who, hs[0], hs[1]);
+        lb = le; le += 2 * hs[0]; nBig = hs[1];
+    }
+    const double tLevels = ms_since(t0) - tPrims;
+
+    // numbering and emit
+    for (size_t l = levels.size(); l-- > 0;)
+        hipLaunchKernelGGL(k_sah_up, grid(levels[l].second - levels[l].first), dim3(kBlock), 0, stream, bn, levels[l].first, levels[l].second);
+    for (const auto& L : levels)
+        hipLaunchKernelGGL(k_sah_down, grid(L.second - L.first), dim3(kBlock), 0, stream, bn, L.first, L.second);
+    const uint32_t total = levels.back().second;
+    hipLaunchKernelGGL(k_sah_emit, grid(total), dim3(kBlock), 0, stream, bn, total, snodes, nodeBase, idxBase, dNodes, cap, summary + 2);
+    hipLaunchKernelGGL(k_sah_emit_refs, grid(n), dim3(kBlock), 0, stream, bn, owner, cur, sout, n, first, dIdx, summary + 2);
+    SCHK(hipGetLastError());
+    if (evEnd) SCHK(hipEventRecord(evEnd, stream));
+    BNode top;
+    SCHK(hipMemcpyAsync(&top, bn, sizeof top, hipMemcpyDeviceToHost, stream));
+    SCHK(hipMemcpyAsync(hs, summary, sizeof hs, hipMemcpyDeviceToHost, stream));
+    SCHK(hipStreamSynchronize(stream));
+    const uint32_t outNodes = 2 * top.interiors + 1;
+    if (hs[2] || outNodes > cap)
+        return sfail(RT_E_DEVICE, "%s: inconsistent device result (%s, %u nodes)", who, status_text(hs[2]), outNodes);
+    out->nodes = outNodes; out->leaves = top.interiors + 1; out->depth = top.depth; out->cost = top.cost; out->mortonBits = 0;
+    out->levels = (uint32_t)levels.size();
+    out->ms[0] = (float)tPrims; out->ms[1] = (float)tLevels; out->ms[2] = (float)(ms_since(t0) - tPrims - tLevels);
+    return RT_OK;
+}
+
+} // namespace sahdev
+
+// The C-ABI entry: allocate, upload, build (sahdev::build), download.
 extern "C" int rt_build_bvh2_sah(int32_t device, const RtPrimitive* prims, int32_t nPrims, int32_t first, int32_t count, uint32_t nodeBase,
                                  uint32_t idxBase, RtBVHNode2* nodes, int32_t nodeCap, int32_t* nNodes, uint32_t* primIdx, RtBuildStats* stats)
 {
+    const char* who = "rt_build_bvh2_sah";
     const auto t0 = std::chrono::steady_clock::now();
     if (const char* msg = check_args(prims, nPrims, first, count, nodeBase, idxBase, nodes, nodeCap, nNodes, primIdx))
         return sfail(RT_E_INVALID, "rt_build_bvh2_sah: %s", msg);
@@ -327,115 +463,33 @@ extern "C" int rt_build_bvh2_sah(int32_t device, const RtPrimitive* prims, int32
     SCHK(hipEventCreate(&w.ev[0]));
     SCHK(hipEventCreate(&w.ev[1]));
 
-    const uint32_t n = (uint32_t)count, cap = 2 * n - 1, bigMax = n / (kSmall + 1) + 1;
-    size_t scan32 = 0, scan64 = 0;
-    SCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan32, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)(n + 1), w.stream));
-    SCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, scan64, (uint64_t*)nullptr, (uint64_t*)nullptr, (int)cap, w.stream));
-    size_t scanBytes = scan32 > scan64 ? scan32 : scan64;
-
-    // one allocation, carved
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { const size_t o = off; off += align_up(bytes); return o; };
-    const size_t oSum = carve(4 * sizeof(uint32_t)), oPrim = carve(n * sizeof(RtPrimitive)), oP = carve(n * sizeof(Prim));
-    const size_t oCur = carve(n * 4ull), oNxt = carve(n * 4ull), oNid = carve(n * 4ull), oNidN = carve(n * 4ull), oOwn = carve(n * 4ull);
-    const size_t of = carve((n + 1) * 4ull), oF = carve((n + 1) * 4ull), oSA = carve(n * 4ull), oSB = carve(n * 4ull), oSout = carve(n * 4ull);
-    const size_t oSn = carve(2ull * n * sizeof(LNode)), oBn = carve((size_t)cap * sizeof(BNode)), ov = carve(cap * 8ull), oV = carve(cap * 8ull);
-    const size_t oKA = carve((size_t)bigMax * kKeys * 8), oKB = carve((size_t)bigMax * (kKeys * 8 + kCnt * 4));
-    const size_t oNodes = carve((size_t)cap * sizeof(RtBVHNode2)), oIdx = carve(n * 4ull), oScan = carve(scanBytes);
-    if (hipMalloc(&w.mem, off) != hipSuccess) { w.mem = nullptr; return sfail(RT_E_NOMEM, "rt_build_bvh2_sah: %zu bytes of device memory", off); }
-    char* base = (char*)w.mem;
-    auto at = [&](size_t o) { return (void*)(base + o); };
-    uint32_t* summary = (uint32_t*)at(oSum);
-    RtPrimitive* dPrims = (RtPrimitive*)at(oPrim);
-    Prim* P = (Prim*)at(oP);
-    uint32_t *cur = (uint32_t*)at(oCur), *nxt = (uint32_t*)at(oNxt), *nid = (uint32_t*)at(oNid), *nidN = (uint32_t*)at(oNidN);
-    uint32_t *owner = (uint32_t*)at(oOwn), *f = (uint32_t*)at(of), *F = (uint32_t*)at(oF);
-    uint32_t *sA = (uint32_t*)at(oSA), *sB = (uint32_t*)at(oSB), *sout = (uint32_t*)at(oSout);
-    LNode* snodes = (LNode*)at(oSn);
-    BNode* bn = (BNode*)at(oBn);
-    uint64_t *v = (uint64_t*)at(ov), *V = (uint64_t*)at(oV), *keysA = (uint64_t*)at(oKA), *keysB = (uint64_t*)at(oKB);
-    RtBVHNode2* dNodes = (RtBVHNode2*)at(oNodes);
-    uint32_t* dIdx = (uint32_t*)at(oIdx);
+    const uint32_t n = (uint32_t)count, cap = 2 * n - 1;
+    size_t workBytes = 0;
+    if (const int rc = sahdev::work_bytes(who, n, w.stream, &workBytes)) return rc;
+    // one allocation: the core's workspace, then the primitives and the output arrays
+    const size_t oPrim = align_up(workBytes), oNodes = oPrim + align_up(n * sizeof(RtPrimitive)), oIdx = oNodes + align_up((size_t)cap * sizeof(RtBVHNode2));
+    const size_t bytes = oIdx + align_up(n * 4ull);
+    if (hipMalloc(&w.mem, bytes) != hipSuccess) { w.mem = nullptr; return sfail(RT_E_NOMEM, "rt_build_bvh2_sah: %zu bytes of device memory", bytes); }
+    RtPrimitive* dPrims = (RtPrimitive*)((char*)w.mem + oPrim);
+    RtBVHNode2* dNodes = (RtBVHNode2*)((char*)w.mem + oNodes);
+    uint32_t* dIdx = (uint32_t*)((char*)w.mem + oIdx);
+    SCHK(hipMemcpyAsync(dPrims, prims + first, n * sizeof(RtPrimitive), hipMemcpyHostToDevice, w.stream));
     const double tAlloc = ms_since(t0);
 
-    const BNode root = open_node(0, n, 0);
-    SCHK(hipMemcpyAsync(dPrims, prims + first, n * sizeof(RtPrimitive), hipMemcpyHostToDevice, w.stream));
-    SCHK(hipMemcpyAsync(bn, &root, sizeof root, hipMemcpyHostToDevice, w.stream));
-    SCHK(hipMemsetAsync(summary, 0, 4 * sizeof(uint32_t), w.stream));
-    SCHK(hipEventRecord(w.ev[0], w.stream));
-    hipLaunchKernelGGL(k_sah_prims, grid(n), dim3(kBlock), 0, w.stream, dPrims, n, P, cur, nid, owner, summary + 2);
-    SCHK(hipGetLastError());
-    uint32_t hs[4] = { 0, 0, 0, 0 };
-    SCHK(hipMemcpyAsync(hs, summary, sizeof hs, hipMemcpyDeviceToHost, w.stream));
-    SCHK(hipStreamSynchronize(w.stream));   // the host arrays are the caller's: nothing of them is read after this point
-    if (hs[2]) return sfail(RT_E_UNSUPPORTED, "rt_build_bvh2_sah: %s", status_text(hs[2]));
-    const double tUpload = ms_since(t0) - tAlloc;
-
-    // level passes
-    std::vector<std::pair<uint32_t, uint32_t>> levels;
-    uint32_t lb = 0, le = 1, nBig = n > kSmall ? 1 : 0;
-    for (;;) {
-        levels.emplace_back(lb, le);
-        const uint32_t K = le - lb;
-        uint64_t *kmin = keysA, *bkmin = keysA + (size_t)nBig * 6, *kmax = keysB, *bkmax = keysB + (size_t)nBig * 6;
-        uint32_t* bcnt = (uint32_t*)(keysB + (size_t)nBig * kKeys);
-        if (nBig) {
-            SCHK(hipMemsetAsync(keysA, 0xff, (size_t)nBig * kKeys * 8, w.stream));
-            SCHK(hipMemsetAsync(keysB, 0, (size_t)nBig * (kKeys * 8 + kCnt * 4), w.stream));
-            hipLaunchKernelGGL(k_sah_reduce, grid(n), dim3(kBlock), 0, w.stream, P, cur, nid, bn, n, kmin, kmax, summary + 2);
-            hipLaunchKernelGGL(k_sah_bins, grid(n), dim3(kBlock), 0, w.stream, P, cur, nid, bn, n, kmin, kmax, bkmin, bkmax, bcnt, summary + 2);
-        }
-        hipLaunchKernelGGL(k_sah_decide, grid(K), dim3(kBlock), 0, w.stream, bn, lb, le, kmin, kmax, bkmin, bkmax, bcnt, summary + 2);
-        hipLaunchKernelGGL(k_sah_small, grid(K), dim3(kBlock), 0, w.stream, P, cur, bn, lb, le, sA, sB, sout, snodes, summary + 2);
-        hipLaunchKernelGGL(k_sah_flag, grid(n + 1), dim3(kBlock), 0, w.stream, P, cur, nid, bn, n, f);
-        SCHK(hipcub::DeviceScan::ExclusiveSum(at(oScan), scanBytes, f, F, (int)(n + 1), w.stream));
-        hipLaunchKernelGGL(k_sah_count, grid(K), dim3(kBlock), 0, w.stream, bn, lb, le, F, v);
-        SCHK(hipcub::DeviceScan::ExclusiveSum(at(oScan), scanBytes, v, V, (int)K, w.stream));
-        hipLaunchKernelGGL(k_sah_children, grid(K), dim3(kBlock), 0, w.stream, bn, lb, le, cap, v, V, summary);
-        hipLaunchKernelGGL(k_sah_scatter, grid(n), dim3(kBlock), 0, w.stream, cur, nid, bn, n, f, F, nxt, nidN, owner);
-        SCHK(hipGetLastError());
-        std::swap(cur, nxt);
-        std::swap(nid, nidN);
-        SCHK(hipMemcpyAsync(hs, summary, sizeof hs, hipMemcpyDeviceToHost, w.stream));
-        SCHK(hipStreamSynchronize(w.stream));
-        if (hs[2]) return sfail(RT_E_UNSUPPORTED, "rt_build_bvh2_sah: %s", status_text(hs[2]));
-        if (hs[0] == 0) break;
-        if ((uint64_t)le + 2ull * hs[0] > cap || hs[1] > bigMax)
-            return sfail(RT_E_DEVICE, "rt_build_bvh2_sah: inconsistent device result (%u splits, %u open nodes)", hs[0], hs[1]);
-        lb = le; le += 2 * hs[0]; nBig = hs[1];
-    }
-    const double tLevels = ms_since(t0) - tAlloc - tUpload;
-
-    // numbering and emit
-    for (size_t l = levels.size(); l-- > 0;)
-        hipLaunchKernelGGL(k_sah_up, grid(levels[l].second - levels[l].first), dim3(kBlock), 0, w.stream, bn, levels[l].first, levels[l].second);
-    for (const auto& L : levels)
-        hipLaunchKernelGGL(k_sah_down, grid(L.second - L.first), dim3(kBlock), 0, w.stream, bn, L.first, L.second);
-    const uint32_t total = levels.back().second;
-    hipLaunchKernelGGL(k_sah_emit, grid(total), dim3(kBlock), 0, w.stream, bn, total, snodes, nodeBase, idxBase, dNodes, cap, summary + 2);
-    hipLaunchKernelGGL(k_sah_emit_refs, grid(n), dim3(kBlock), 0, w.stream, bn, owner, cur, sout, n, (uint32_t)first, dIdx, summary + 2);
-    SCHK(hipGetLastError());
-    SCHK(hipEventRecord(w.ev[1], w.stream));
-    BNode top;
-    SCHK(hipMemcpyAsync(&top, bn, sizeof top, hipMemcpyDeviceToHost, w.stream));
-    SCHK(hipMemcpyAsync(hs, summary, sizeof hs, hipMemcpyDeviceToHost, w.stream));
-    SCHK(hipStreamSynchronize(w.stream));
-    const uint32_t outNodes = 2 * top.interiors + 1;
-    if (hs[2] || outNodes > cap)
-        return sfail(RT_E_DEVICE, "rt_build_bvh2_sah: inconsistent device result (%s, %u nodes)", status_text(hs[2]), outNodes);
-    const double tNumber = ms_since(t0) - tAlloc - tUpload - tLevels;
-    SCHK(hipMemcpyAsync(nodes, dNodes, outNodes * sizeof(RtBVHNode2), hipMemcpyDeviceToHost, w.stream));
+    sahdev::Built b{};
+    if (const int rc = sahdev::build(who, w.stream, w.mem, dPrims, n, (uint32_t)first, nodeBase, idxBase, dNodes, dIdx, w.ev[0], w.ev[1], &b)) return rc;
+    const double tBuilt = ms_since(t0);
+    SCHK(hipMemcpyAsync(nodes, dNodes, b.nodes * sizeof(RtBVHNode2), hipMemcpyDeviceToHost, w.stream));
     SCHK(hipMemcpyAsync(primIdx, dIdx, n * sizeof(uint32_t), hipMemcpyDeviceToHost, w.stream));
     SCHK(hipStreamSynchronize(w.stream));
-    *nNodes = (int32_t)outNodes;
-    const double tDownload = ms_since(t0) - tAlloc - tUpload - tLevels - tNumber;
-    g_phases[0] = (float)(tAlloc + tUpload); g_phases[1] = (float)tLevels; g_phases[2] = (float)tNumber; g_phases[3] = (float)tDownload;
-    g_phases[4] = (float)levels.size();
+    *nNodes = (int32_t)b.nodes;
+    g_phases[0] = (float)tAlloc + b.ms[0]; g_phases[1] = b.ms[1]; g_phases[2] = b.ms[2]; g_phases[3] = (float)(ms_since(t0) - tBuilt);
+    g_phases[4] = (float)b.levels;
     if (stats) {
         float ms = 0;
         SCHK(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
-        stats->nodes = (int32_t)outNodes; stats->leaves = (int32_t)top.interiors + 1; stats->depth = (int32_t)top.depth;
-        stats->morton_bits = 0; stats->sah_cost = top.cost; stats->device_ms = ms;
+        stats->nodes = (int32_t)b.nodes; stats->leaves = (int32_t)b.leaves; stats->depth = (int32_t)b.depth;
+        stats->morton_bits = 0; stats->sah_cost = b.cost; stats->device_ms = ms;
         stats->wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
         stats->_reserved = 0;
     }

@@ -146,6 +146,20 @@ int rth_refit(RthScene* s)
     if (rc != RT_OK) g_herr = err;
     return rc;
 }
+int rth_rebuild(RthScene* s, int builder, const RtBuildOptions* opts)
+{
+    if (!s || !s->scene.bvh2) { g_herr = "rth_rebuild: null scene"; return RT_E_INVALID; }
+    try { s->scene.bvh2->Rebuild(builder, opts); return 0; }
+    catch (const LbvhError& e) { g_herr = e.what(); return e.code; }
+    catch (const std::exception& e) { g_herr = e.what(); return RT_E_NOMEM; }
+}
+int rth_blas_ranges(RthScene* s, int32_t* firstOut, int32_t* countOut)
+{
+    if (!s || !s->scene.bvh2) { g_herr = "rth_blas_ranges: null scene"; return RT_E_INVALID; }
+    const BVH2& b = *s->scene.bvh2;
+    return rt_blas_ranges(b.bvhNodes.data(), (int32_t)b.bvhNodes.size(), b.primIdx.data(), (int32_t)b.primIdx.size(), (int32_t)s->scene.primitives.size(),
+                          s->scene.blasNodes.data(), (int32_t)s->scene.blasNodes.size(), firstOut, countOut);
+}
 int rth_build_tlas(RthScene* s) { GUARD(delete s->tlas; s->tlas = new TLAS(*s->scene.bvh2); s->tlas->Build()) }
 int rth_set_instance_transform(RthScene* s, int blas, const float invT[16])
 {

@@ -72,6 +72,10 @@ public:
     // BuildBLAS(alpha = 1) appends.  device >= 0: rt_build_bvh2_sah on that GPU; -1: the host restatement.  Throws LbvhError and
     // leaves everything unchanged when the build is refused.
     void     BuildBLASSAHGPU(int startIdx, int device);
+    // Discards the trees and builds every BLAS again over the primitive range it covers, in increasing order of the ranges, with the
+    // host restatement of rt_rebuild_scene's builder (RT_REBUILD_SAH / RT_REBUILD_LBVH, opt for the latter); instance transforms stay,
+    // bvhIdx follows.  Throws LbvhError and leaves everything unchanged when refused (rebuild_host.cpp).
+    void     Rebuild(int builder, const RtBuildOptions* opt);
     int      buildThreads = 1;   // > 1: subtrees are built by parallel tasks, then numbered in the reference's LIFO order (same arrays)
     uint32_t Depth(uint32_t nodeIdx) const;
     uint32_t Count(uint32_t nodeIdx) const;

@@ -176,6 +176,25 @@ class Scene:
         rebuild the TLAS (and the BVH4) from the refit tree."""
         self._chk(self._lib.rth_refit(self._h))
 
+    def Rebuild(self, builder="sah", **lbvh_options):
+        """Discard the BVH2 and build every BLAS again over the primitive range it covers, as rt_rebuild_scene does on the GPU
+        (rth_rebuild): builder="sah" is the GPU SAH builder's host restatement (BuildBLAS with alpha 1), "lbvh" the linear builder's
+        (lbvh_options: max_leaf, cost_traverse, cost_intersect).  Instance transforms stay; arrays() / BuildTLAS() then rebuild the
+        TLAS (and the BVH4).  Raises BuildError (.code, an RT_E_* value) and changes nothing when refused."""
+        rc = self._lib.rth_rebuild(self._h, rebuild_builder(builder, lbvh_options), _lib.ptr(build_options(**lbvh_options)))
+        if rc != 0:
+            raise BuildError(rc, self._lib.rth_last_error().decode())
+
+    def blas_ranges(self):
+        """The primitive range (first, count) of every instance's BLAS (rt_blas_ranges); raises BuildError with RT_E_UNSUPPORTED when
+        the BLAS do not cover contiguous, disjoint ranges in the order of their roots (such a scene cannot be rebuilt in place)."""
+        n = len(_view(self._lib.rth_blas_nodes, self._h, _lib.BVHInstance))
+        first, count = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        rc = self._lib.rth_blas_ranges(self._h, _lib.ptr(first), _lib.ptr(count))
+        if rc != 0:
+            raise BuildError(rc, _lib.device_lib().rt_last_error().decode())
+        return [(int(a), int(b)) for a, b in zip(first[:n], count[:n])]
+
     def SetInstanceTransform(self, blas, invT):
         self._chk(self._lib.rth_set_instance_transform(self._h, int(blas), _lib.fvec(np.asarray(invT, dtype=np.float32).ravel())))
 
@@ -216,6 +235,28 @@ def build_options(max_leaf=None, cost_traverse=None, cost_intersect=None):
     o["cost_traverse"] = LBVH_DEFAULTS["cost_traverse"] if cost_traverse is None else float(cost_traverse)
     o["cost_intersect"] = LBVH_DEFAULTS["cost_intersect"] if cost_intersect is None else float(cost_intersect)
     return o
+
+
+def rebuild_builder(builder, lbvh_options=None):
+    """RT_REBUILD_* of a builder name; the linear builder's options apply to "lbvh" only."""
+    if builder not in ("sah", "lbvh"):
+        raise ValueError(f"unknown builder {builder!r} (expected 'sah' or 'lbvh')")
+    if builder == "sah" and lbvh_options:
+        raise ValueError(f"options {sorted(lbvh_options)} apply to builder='lbvh' only")
+    return _lib.REBUILD_SAH if builder == "sah" else _lib.REBUILD_LBVH
+
+
+def blas_ranges(sa):
+    """rt_blas_ranges of SceneArrays (or anything with bvh2 / primIdx / prims / blas): [(first, count)] per instance; raises BuildError
+    (RT_E_UNSUPPORTED) when rt_rebuild_scene would not take the scene."""
+    L = _lib.device_lib()
+    nodes, idx = np.ascontiguousarray(sa.bvh2, _lib.BVHNode2), np.ascontiguousarray(sa.primIdx, np.uint32)
+    inst = np.ascontiguousarray(sa.blas, _lib.BVHInstance)
+    first, count = np.zeros(max(len(inst), 1), np.int32), np.zeros(max(len(inst), 1), np.int32)
+    rc = L.rt_blas_ranges(_lib.ptr(nodes), len(nodes), _lib.ptr(idx), len(idx), len(sa.prims), _lib.ptr(inst), len(inst), _lib.ptr(first), _lib.ptr(count))
+    if rc != 0:
+        raise BuildError(rc, L.rt_last_error().decode())
+    return [(int(a), int(b)) for a, b in zip(first[:len(inst)], count[:len(inst)])]
 
 
 def _stats_dict(st):

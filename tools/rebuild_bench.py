@@ -1,0 +1,182 @@
+"""Cost of an in-place BLAS rebuild (rt_rebuild_scene) against the round trip it removes, on one GPU.
+
+    python tools/rebuild_bench.py [--reps 10] [--frames 20]
+
+For sponza-class (every vertex scrambled across the triangles) and config 5 (every vertex jittered), three ways to bring a bound scene
+up to date are timed in one process, alternating within each repetition (min / median / max of --reps after a warm-up):
+  A  Device.rebuild_scene(prims, builder="sah" | "lbvh"): wall ms, gpu_ms and its split (stage, builds, derive, TLAS, commit);
+  B  the way to the same arrays without it, minus the scene generator: rt_build_bvh2_sah (resp. rt_build_bvh2) per BLAS on caller
+     arrays, the TLAS on the host, rt_upload_scene into a second context (the first repetition checks that B's eleven device arrays
+     equal A's);
+  C  Device.update_scene(prims) of the same records, for scale.
+Then the trace rate (M samples/s over --frames frames) on sponza-class with the vertices scrambled among every 64 consecutive
+triangles (a deformation that leaves a tree something to cull): the scene as built, after the refit alone, after the rebuild.
+One JSON line per scene and builder."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from magr_ray_tracer_amd import _lib as W, scenes  # noqa: E402
+from magr_ray_tracer_amd.renderer import Device  # noqa: E402
+from magr_ray_tracer_amd.scene import SceneArrays, blas_ranges, build_lbvh, build_sah_gpu  # noqa: E402
+
+RW, RH = 1280, 720
+
+
+def mmm(xs):
+    return [round(min(xs), 3), round(statistics.median(xs), 3), round(max(xs), 3)]
+
+
+def scrambled(prims, seed):
+    rng = np.random.default_rng(seed)
+    p = prims.copy()
+    tri = np.where(p["objType"] == W.PRIM_TRIANGLE)[0]
+    v = np.stack([p["v0"][tri], p["v1"][tri], p["v2"][tri]], axis=1).reshape(-1, 4)
+    v = v[rng.permutation(len(v))].reshape(-1, 3, 4)
+    p["v0"][tri], p["v1"][tri], p["v2"][tri] = v[:, 0], v[:, 1], v[:, 2]
+    return p
+
+
+def scrambled_locally(prims, seed, block=64):
+    """Vertices scrambled among each run of `block` consecutive triangles: triangles several times their size that stay where they were,
+    which a refit follows badly and a tree can still cull."""
+    rng = np.random.default_rng(seed)
+    p = prims.copy()
+    tri = np.where(p["objType"] == W.PRIM_TRIANGLE)[0]
+    v = np.stack([p["v0"][tri], p["v1"][tri], p["v2"][tri]], axis=1)
+    for a in range(0, len(v), block):
+        w = v[a:a + block].reshape(-1, 4)
+        v[a:a + block] = w[rng.permutation(len(w))].reshape(-1, 3, 4)
+    p["v0"][tri], p["v1"][tri], p["v2"][tri] = v[:, 0], v[:, 1], v[:, 2]
+    return p
+
+
+def jittered(prims, seed):
+    rng = np.random.default_rng(seed)
+    p = prims.copy()
+    for f in ("v0", "v1", "v2"):
+        p[f][:, :3] += rng.normal(scale=1e-3, size=(len(p), 3)).astype(np.float32)
+    return p
+
+
+def small_tlas(nodes, inst):
+    """TLAS::Build for one or two identity instances (what the two scenes have): leaves at 1 + i, the join behind them, node 0 = root."""
+    n = len(inst)
+    assert n in (1, 2) and all(np.array_equal(i["invT"], np.eye(4, dtype=np.float32).ravel()) for i in inst)
+    t = np.zeros(2 * n, W.TLASNode)
+    for i in range(n):
+        r = nodes[int(inst["bvhIdx"][i])]
+        t["aabbMin"][1 + i], t["aabbMax"][1 + i], t["BLASidx"][1 + i] = r["aabbMin"], r["aabbMax"], i
+    if n == 2:
+        t["aabbMin"][3], t["aabbMax"][3] = np.minimum(t["aabbMin"][1], t["aabbMin"][2]), np.maximum(t["aabbMax"][1], t["aabbMax"][2])
+        t["leftRight"][3] = 1 + (2 << 16)
+    t[0] = t[2 * n - 1]
+    return t
+
+
+def round_trip(sa, prims, ranges, builder, d2):
+    """B: per-BLAS GPU builds on caller arrays, host TLAS, upload.  Returns (wall ms, sum of the builders' device_ms)."""
+    t0 = time.perf_counter()
+    nodes, idx, roots, dev = [], [], {}, 0.0
+    nb = ib = 0
+    for first, count in sorted(set(ranges)):
+        fn = build_sah_gpu if builder == "sah" else build_lbvh
+        n, i, st = fn(prims, first=first, count=count, device=0, node_base=nb, idx_base=ib)
+        roots[(first, count)] = nb
+        nodes.append(n)
+        idx.append(i)
+        nb += len(n)
+        ib += len(i)
+        dev += st["device_ms"]
+    nodes, idx = np.concatenate(nodes), np.concatenate(idx)
+    inst = sa.blas.copy()
+    inst["bvhIdx"] = [roots[r] for r in ranges]
+    new = SceneArrays(prims=prims, mats=sa.mats, tex=sa.tex, lights=sa.lights, bvh2=nodes, bvh4=sa.bvh4, primIdx=idx,
+                      tlas=small_tlas(nodes, inst), blas=inst)
+    d2.upload(new)
+    return (time.perf_counter() - t0) * 1e3, dev
+
+
+def trace_rate(d, cam, frames):
+    d.seed_default()
+    d.reset()
+    d.render(cam, 2)
+    d.synchronize()
+    t0 = time.perf_counter()
+    d.render(cam, frames)
+    d.synchronize()
+    return round(RW * RH * frames / (time.perf_counter() - t0) / 1e6, 3)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--frames", type=int, default=20)
+    a = ap.parse_args()
+    cases = {"sponza_class": (lambda: scenes.sponza_class(1.0), scrambled), "config5": (lambda: scenes.config5_scene(0.0), jittered)}
+    for name, (make, move) in cases.items():
+        s, view = make()
+        sa = s.arrays(bvh4=False)
+        ranges = blas_ranges(sa)
+        cam = scenes.camera_for(view, RW, RH)
+        dC = Device(RW, RH)
+        dC.upload(sa)
+        dC.update_scene(move(sa.prims, 0))            # warm-up: allocates the staging buffers
+        d2 = Device(320, 240)
+        for builder in ("sah", "lbvh"):
+            dA = Device(RW, RH)
+            dA.upload(sa)
+            for k in range(2):                        # warm-up: both sets of arrays and the builders' workspace
+                dA.rebuild_scene(move(sa.prims, 100 + k), builder=builder)
+            round_trip(sa, move(sa.prims, 100), ranges, builder, d2)
+            A, Ag, B, Bd, Cw, Cg = [], [], [], [], [], []
+            split = {k: [] for k in ("stage_ms", "build_ms", "derive_ms", "tlas_ms", "commit_ms")}
+            for r in range(a.reps):
+                p = move(sa.prims, r + 1)
+                t0 = time.perf_counter()
+                st = dA.rebuild_scene(p, builder=builder)
+                A.append((time.perf_counter() - t0) * 1e3)
+                Ag.append(st["gpu_ms"])
+                for k in split:
+                    split[k].append(st[k])
+                w, dev = round_trip(sa, p, ranges, builder, d2)
+                B.append(w)
+                Bd.append(dev)
+                if r == 0:
+                    for k in W.SCENE_ARRAYS:
+                        assert np.array_equal(dA.scene_array(k), d2.scene_array(k)), f"{name} / {builder}: B's {k} differs from A's"
+                t0 = time.perf_counter()
+                su = dC.update_scene(p)
+                Cw.append((time.perf_counter() - t0) * 1e3)
+                Cg.append(su["gpu_ms"])
+            mA, mB = statistics.median(A), statistics.median(B)
+            out = {"scene": name, "builder": builder, "prims": int(len(sa.prims)), "nodes": st["nodes"], "max_depth": st["max_depth"],
+                   "A_wall_ms": mmm(A), "A_gpu_ms": mmm(Ag), "A_split_ms": {k: round(statistics.median(v), 3) for k, v in split.items()},
+                   "B_wall_ms": mmm(B), "B_builders_device_ms": mmm(Bd), "C_wall_ms": mmm(Cw), "C_gpu_ms": mmm(Cg),
+                   "A_over_B": round(mA / mB, 3), "B_spread_ms": round(max(B) - min(B), 3), "A_below_B_by_ms": round(mB - mA, 3),
+                   "gpu_budget_ms": round(statistics.median(Bd) + statistics.median(Cg) + statistics.median(split["derive_ms"]), 3)}
+            if name == "sponza_class":   # the number that tells when to call which: the same locally scrambled scene, refit and rebuilt
+                dT = Device(RW, RH)
+                dT.upload(sa)
+                out["trace_built_Msps"] = trace_rate(dT, cam, a.frames)           # the scene as built, for scale
+                p = scrambled_locally(sa.prims, 7)
+                dT.update_scene(p)
+                out["trace_refit_only_Msps"] = trace_rate(dT, cam, a.frames)
+                dA.rebuild_scene(p, builder=builder)
+                out["trace_rebuilt_Msps"] = trace_rate(dA, cam, a.frames)
+                dT.close()
+            print(json.dumps(out), flush=True)
+            dA.close()
+        d2.close()
+        dC.close()
+        s.close()
+
+
+if __name__ == "__main__":
+    main()
