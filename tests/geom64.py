@@ -534,7 +534,7 @@ def rows_differ(a, b):
     """Per row of two float32 arrays (n, k): does any element differ bit for bit (+0 and -0 count as equal)?"""
     a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
     bad = (a.view(np.uint32) != b.view(np.uint32)) & ~((a == 0) & (b == 0))
-    return bad.reshape(len(a), -1).any(axis=1)
+    return bad.reshape(len(a), bad.size // max(len(a), 1)).any(axis=1)   # (no rows: -1 cannot be inferred)
 
 
 def mismatch_rows(a, b):
