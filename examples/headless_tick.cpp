@@ -3,7 +3,7 @@
 // the host code is the reference's call sequence (src/renderer.cpp:6-63, template main loop), the device work goes through
 // librt355.so.  There is no CPU path: without a HIP device Init() throws.
 //
-//   headless_tick [--obj model.obj] [--tex image.png] [--size W H] [--spp N] [--bvh4] [--kajiya] [--decorrelate] [--lanes N] [--out frame.png]
+//   headless_tick [--obj model.obj] [--tex image.png] [--size W H] [--spp N] [--bvh4] [--kajiya] [--decorrelate] [--lanes N] [--builtins ieee|reference] [--out frame.png]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -47,7 +47,7 @@ int main(int argc, char** argv)
     int W = 1280, H = 720, spp = 64;
     std::string obj, tex, out = "frame.png";
     bool bvh4 = false, kajiya = false, decorrelate = false;
-    int lanes = 1;
+    int lanes = 1, builtins = RT_BUILTINS_DEFAULT;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--obj" && i + 1 < argc) obj = argv[++i];
@@ -59,6 +59,12 @@ int main(int argc, char** argv)
         else if (a == "--kajiya") kajiya = true;
         else if (a == "--decorrelate") decorrelate = true;
         else if (a == "--lanes" && i + 1 < argc) lanes = std::max(1, atoi(argv[++i]));
+        else if (a == "--builtins" && i + 1 < argc) {
+            const std::string m = argv[++i];
+            if (m == "ieee") builtins = RT_BUILTINS_IEEE;
+            else if (m == "reference") builtins = RT_BUILTINS_REFERENCE;
+            else { fprintf(stderr, "--builtins takes ieee or reference, not %s\n", m.c_str()); return 2; }
+        }
         else { fprintf(stderr, "unknown argument %s\n", a.c_str()); return 2; }
     }
     try {
@@ -67,6 +73,7 @@ int main(int argc, char** argv)
         // overlap on the GPU.  The library says so on stderr when the process's hardware queues serialise them.
         Renderer r(W, H);
         r.lanes = lanes;
+        r.builtins = builtins;   // IEEE (default): reproducible on a CPU; REFERENCE: the reference's image from the reference's seeds
         Scene& s = r.scene;
         // materials the way the reference's Scene constructor sets them up (scene.cpp:14-43)
         { RtMaterial& mt = s.AddMaterial("white"); mt.color = RtFloat4{ 0.9f, 0.9f, 0.9f, 0 }; }

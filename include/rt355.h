@@ -60,8 +60,16 @@ typedef struct RtConfig {
     int32_t persist_blocks_per_cu; /* workgroups per CU of the persistent traversal grids: 0 = what the hardware admits (7 extend / 6 connect);
                                  * 4 is best when three contexts share the GPU (their workgroups then fit beside each other);
                                  * a group of several lanes picks 2 when four or more of its streams run side by side, else 3       */
-    int32_t reserved[1];
+    int32_t builtins;           /* RT_BUILTINS_*: how normalize / length / exp / sin / cos / acospi / atan2pi are evaluated (see below);
+                                 * any other value: RT_E_INVALID                                                             */
 } RtConfig;
+
+/* RtConfig.builtins.  IEEE: sequences of IEEE + - * / sqrt that a CPU reproduces bit for bit (what the oracle checks).  REFERENCE: the
+ * instruction sequences ROCm's OpenCL library gives the reference's own kernels (hardware rsq / sqrt, the ocml functions): the
+ * reference's image from the reference's seeds.  DEFAULT (what a zero-filled struct asks for) is IEEE. */
+#define RT_BUILTINS_DEFAULT    0
+#define RT_BUILTINS_IEEE       1
+#define RT_BUILTINS_REFERENCE  2
 
 /* Device-side work counters (per-kernel-family totals since the last rt_reset_counters).
  * They define the algorithmic bytes of SURVEY.md §8(d). */
@@ -101,6 +109,7 @@ typedef struct RtKernelInfo {
 const char* rt_last_error(void);
 int rt_device_count(void);
 int rt_kernel_info(RtCtx* ctx, RtKernelInfo* out);
+int rt_builtins(RtCtx* ctx);   /* the context's arithmetic, resolved: RT_BUILTINS_IEEE or RT_BUILTINS_REFERENCE */
 
 /* new Buffer(...) x11 + new Kernel(...) x6 (renderer.cpp:145-157, :218-223). */
 int rt_create(const RtConfig* cfg, RtCtx** out);
@@ -370,7 +379,8 @@ int rt_debug_get_steps(RtCtx* ctx, int32_t* out, int32_t capacity, int32_t* n);
  *   RT_MATH_SPHERE_TEXEL             N.x, N.y, N.z, N.w, texW, texH (int32) -> int32 x, y: texel column and row of a sphere hit
  *   RT_MATH_NORMALIZE4               v.x, v.y, v.z, v.w                 -> float4
  *   RT_MATH_LENGTH4                  v.x, v.y, v.z, v.w                 -> float
- * The library built with the reference's builtins (librt355_refb.so) evaluates its ocml functions; it has no ACOS, ATAN or ATAN2
+ * rt_debug_math / rt_debug_math_sweep evaluate the library's default arithmetic (RT_BUILTINS_DEFAULT), the _mode forms the one named
+ * (RT_BUILTINS_*; any other value: RT_E_INVALID).  RT_BUILTINS_REFERENCE evaluates the ocml functions; it has no ACOS, ATAN or ATAN2
  * (it calls acospi / atan2pi only inside the texel lookup) and returns RT_E_UNSUPPORTED for them. */
 #define RT_MATH_EXP           0
 #define RT_MATH_SIN           1
@@ -383,11 +393,13 @@ int rt_debug_get_steps(RtCtx* ctx, int32_t* out, int32_t capacity, int32_t* n);
 #define RT_MATH_NORMALIZE4    8
 #define RT_MATH_LENGTH4       9
 int rt_debug_math(int32_t fn, const void* in, void* out, int64_t n);
+int rt_debug_math_mode(int32_t builtins, int32_t fn, const void* in, void* out, int64_t n);
 /* Sweep of a one-argument function (EXP ... F2I) over every float32 bit pattern of blocks [firstBlock, firstBlock + nBlocks) of
  * 2^20 inputs each (block b: bits b<<20 ...; 4096 blocks in all).  hashes[k] = sum mod 2^64 over the block of
  * splitmix64((uint64_t)in_bits << 32 | out_bits), every NaN output counted as 0x7fc00000: independent of evaluation order. */
 #define RT_MATH_SWEEP_BLOCK_BITS 20
 int rt_debug_math_sweep(int32_t fn, int32_t firstBlock, int32_t nBlocks, uint64_t* hashes);
+int rt_debug_math_sweep_mode(int32_t builtins, int32_t fn, int32_t firstBlock, int32_t nBlocks, uint64_t* hashes);
 
 #ifdef __cplusplus
 }

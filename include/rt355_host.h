@@ -120,6 +120,8 @@ int  rth_renderer_camera_move(RthRenderer* r, int camdir /* 0 Forward 1 Backward
 int  rth_renderer_camera_mouse(RthRenderer* r, float xOffset, float yOffset);
 int  rth_renderer_camera_zoom(RthRenderer* r, float offset);
 int rth_renderer_set_lanes(RthRenderer* r, int lanes);   /* before rth_renderer_init: Renderer::lanes (Tick = `lanes` overlapping frames) */
+int rth_renderer_set_builtins(RthRenderer* r, int builtins);   /* before rth_renderer_init: Renderer::builtins = RtConfig.builtins of the lanes (RT_BUILTINS_*, rt355.h); other values: -1 */
+int rth_renderer_builtins(RthRenderer* r);                /* the stored setting (RT_BUILTINS_DEFAULT until set) */
 int  rth_renderer_frames(RthRenderer* r);                                 /* settings->frames */          /* Renderer::SaveFrame (renderer.cpp:303-308) */
 
 #ifdef __cplusplus

@@ -44,7 +44,7 @@ StageTimes = np.dtype([(n, "<f8") for n in ("generate_ms", "extend_ms", "shade_m
 Config = np.dtype([(n, "<i4") for n in ("width", "height", "y0", "y1", "max_bounces", "shading", "sampling", "accel",
                                          "russian_roulette", "filter_fireflies", "device", "extend_variant", "profile",
                                          "shade_blocks_per_cu", "persist_blocks_per_cu")] +
-                  [("reserved", "<i4", 1)])
+                  [("builtins", "<i4")])   # RT_BUILTINS_* (byte 60)
 
 BuildOptions = np.dtype([("max_leaf", "<i4"), ("cost_traverse", "<f4"), ("cost_intersect", "<f4"), ("_reserved", "<i4")])
 BuildStats = np.dtype([("nodes", "<i4"), ("leaves", "<i4"), ("depth", "<i4"), ("morton_bits", "<i4"), ("sah_cost", "<f4"),
@@ -68,6 +68,19 @@ MATH_WORDS = {MATH_EXP: (1, 1), MATH_SIN: (1, 1), MATH_COS: (1, 1), MATH_ACOS: (
               MATH_ATAN2: (2, 1), MATH_SPHERE_TEXEL: (6, 2), MATH_NORMALIZE4: (4, 4), MATH_LENGTH4: (4, 1)}
 MATH_SWEEP_BLOCK_BITS = 20
 MAX_BOUNCES = 7
+# RtConfig.builtins (include/rt355.h): how the kernels evaluate normalize / length / exp / sin / cos / acospi / atan2pi
+BUILTINS_DEFAULT, BUILTINS_IEEE, BUILTINS_REFERENCE = 0, 1, 2
+BUILTINS = {None: BUILTINS_DEFAULT, "ieee": BUILTINS_IEEE, "reference": BUILTINS_REFERENCE}
+
+
+def builtins_value(name):
+    """RT_BUILTINS_* of None / "ieee" / "reference"; anything else is a ValueError (raised before any library is loaded)."""
+    try:
+        return BUILTINS[name]
+    except (KeyError, TypeError):
+        raise ValueError(f"builtins must be None, 'ieee' or 'reference', not {name!r}") from None
+
+
 RT_OK, RT_E_INVALID, RT_E_DEVICE, RT_E_NOMEM, RT_E_UNSUPPORTED = 0, -1, -2, -3, -4
 # rt_debug_get_scene_array ids (include/rt355.h): name -> (id, record dtype)
 SCENE_ARRAYS = {"prims": 0, "bvh": 1, "tlas": 2, "instances": 3, "pairs": 4, "triRecs": 5, "shadeRecs": 6, "lightRecs": 7,
@@ -82,12 +95,12 @@ RebuildStats = np.dtype([(n, "<f8") for n in ("gpu_ms", "wall_ms", "stage_ms", "
 assert RebuildStats.itemsize == 96
 
 DEVICE_SYMBOLS = [
-    "rt_last_error", "rt_device_count", "rt_kernel_info", "rt_create", "rt_destroy", "rt_upload_scene", "rt_share_scene", "rt_set_seeds", "rt_seed_default",
+    "rt_last_error", "rt_device_count", "rt_kernel_info", "rt_builtins", "rt_create", "rt_destroy", "rt_upload_scene", "rt_share_scene", "rt_set_seeds", "rt_seed_default",
     "rt_get_seeds", "rt_bind_accum", "rt_accum_device_ptr", "rt_stream", "rt_reset", "rt_render", "rt_synchronize", "rt_focus",
     "rt_read_accum", "rt_write_accum", "rt_postproc", "rt_read_counters", "rt_reset_counters", "rt_read_stage_times", "rt_reset_stage_times", "rt_set_profile",
     "rt_stage_begin_frame", "rt_stage_generate", "rt_stage_extend", "rt_stage_shade", "rt_stage_connect",
     "rt_debug_get_rays", "rt_debug_set_rays", "rt_debug_get_shadow", "rt_debug_enable_steps", "rt_debug_get_steps", "rt_debug_math",
-    "rt_debug_math_sweep", "rt_validate_scene", "rt_build_bvh2", "rt_build_bvh2_sah", "rt_debug_sah_phases", "rt_update_scene", "rt_group_update_scene", "rt_debug_get_scene_array",
+    "rt_debug_math_sweep", "rt_debug_math_mode", "rt_debug_math_sweep_mode", "rt_validate_scene", "rt_build_bvh2", "rt_build_bvh2_sah", "rt_debug_sah_phases", "rt_update_scene", "rt_group_update_scene", "rt_debug_get_scene_array",
     "rt_rebuild_scene", "rt_group_rebuild_scene", "rt_blas_ranges",
     "rt_group_create", "rt_group_destroy", "rt_group_lanes", "rt_group_concurrency", "rt_group_lane", "rt_group_frames", "rt_group_upload_scene", "rt_group_share_scene",
     "rt_group_seed", "rt_group_reset", "rt_group_render", "rt_group_synchronize", "rt_group_sum", "rt_group_read_accum", "rt_group_focus",
@@ -99,7 +112,7 @@ HOST_SYMBOLS = [
     "rth_bvh2_nodes", "rth_bvh4_nodes", "rth_prim_idx", "rth_tlas_nodes", "rth_blas_nodes", "rth_bvh_stats", "rth_camera",
     "rth_renderer_create", "rth_renderer_destroy", "rth_renderer_init", "rth_renderer_set_camera", "rth_renderer_tick",
     "rth_renderer_read", "rth_renderer_camera", "rth_seed_stream", "rth_load_model", "rth_save_png",
-    "rth_set_build_threads", "rth_renderer_save_frame", "rth_renderer_camera_move", "rth_renderer_camera_mouse", "rth_renderer_camera_zoom", "rth_renderer_frames", "rth_renderer_set_lanes",
+    "rth_set_build_threads", "rth_renderer_save_frame", "rth_renderer_camera_move", "rth_renderer_camera_mouse", "rth_renderer_camera_zoom", "rth_renderer_frames", "rth_renderer_set_lanes", "rth_renderer_set_builtins", "rth_renderer_builtins",
     "rth_build_blas_lbvh", "rth_build_bvh2_lbvh", "rth_lbvh_stats", "rth_set_primitives", "rth_refit",
     "rth_build_blas_sah_gpu", "rth_build_bvh2_sah", "rth_rebuild", "rth_blas_ranges"]
 
@@ -146,6 +159,7 @@ def _bind_device(lib):
         lib.rt_last_error.restype = C.c_char_p
         lib.rt_create.argtypes = [vp, C.POINTER(vp)]
         lib.rt_kernel_info.argtypes = [vp, vp]
+        lib.rt_builtins.argtypes = [vp]
         lib.rt_destroy.argtypes = [vp]
         lib.rt_upload_scene.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32]
         lib.rt_share_scene.argtypes = [vp, vp]
@@ -181,6 +195,8 @@ def _bind_device(lib):
         lib.rt_debug_enable_steps.argtypes = [vp, i32]
         lib.rt_debug_math.argtypes = [i32, vp, vp, i64]
         lib.rt_debug_math_sweep.argtypes = [i32, i32, i32, vp]
+        lib.rt_debug_math_mode.argtypes = [i32, i32, vp, vp, i64]
+        lib.rt_debug_math_sweep_mode.argtypes = [i32, i32, i32, i32, vp]
         lib.rt_validate_scene.argtypes = [i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32]
         lib.rt_build_bvh2.argtypes = [i32, vp, vp, i32, i32, i32, C.c_uint32, C.c_uint32, vp, i32, C.POINTER(i32), vp, vp]
         lib.rt_build_bvh2_sah.argtypes = [i32, vp, i32, i32, i32, C.c_uint32, C.c_uint32, vp, i32, C.POINTER(i32), vp, vp]
@@ -270,6 +286,8 @@ def host_lib():
         lib.rth_renderer_camera_zoom.argtypes = [vp, C.c_float]
         lib.rth_renderer_frames.argtypes = [vp]
         lib.rth_renderer_set_lanes.argtypes = [vp, i32]
+        lib.rth_renderer_set_builtins.argtypes = [vp, i32]
+        lib.rth_renderer_builtins.argtypes = [vp]
         _host = lib
     return _host
 

@@ -4,7 +4,7 @@
 
 Outputs (git-ignored, shipped to the GPU box by gpurun):
     magr_ray_tracer_amd/librt355.so       device path: HIP kernels + C-ABI (include/rt355.h)
-    magr_ray_tracer_amd/librt355_refb.so  the same with the reference's OpenCL builtin sequences (tests only, -DRT355_REF_BUILTINS)
+    magr_ray_tracer_amd/librt355_refb.so  the same source with -DRT355_REF_BUILTINS: RT_BUILTINS_DEFAULT means REFERENCE there (a yardstick of the tests)
     magr_ray_tracer_amd/librt355_host.so  host side: Scene / BVH2 / BVH4 / TLAS / Renderer mirror
     oracle/liboracle.so                   CPU restatement (test infrastructure only)
 """
@@ -55,9 +55,10 @@ def build_device(force=False):
 
 
 def build_device_refb(force=False):
-    """librt355_refb.so: the same library with -DRT355_REF_BUILTINS (normalize / length / exp / sin / cos / acospi / atan2pi as ROCm's
-    OpenCL library evaluates them for the reference's kernels, rt355_kernels.h).  Test infrastructure for tests/test_gpu_reference.py
-    (uncurated whole-frame comparison with the reference's kernels); the shipped library is librt355.so."""
+    """librt355_refb.so: the same library with -DRT355_REF_BUILTINS, which makes RT_BUILTINS_DEFAULT resolve to RT_BUILTINS_REFERENCE
+    (normalize / length / exp / sin / cos / acospi / atan2pi as ROCm's OpenCL library evaluates them for the reference's kernels,
+    rt355_kernels.h) and changes nothing else: both sets of kernels are in both libraries.  A second build for the tests to compare the
+    shipped library's run-time mode with (tests/test_gpu_reference.py, tests/test_gpu_builtins.py); the shipped library is librt355.so."""
     src = os.path.join(PKG, "csrc", "rt355.hip")
     lbvh = os.path.join(PKG, "csrc", "lbvh.hip")      # same entry points as librt355.so (the ctypes binding declares them all)
     refit = os.path.join(PKG, "csrc", "refit.hip")

@@ -132,7 +132,37 @@ struct RtCtx {
     int32_t* dSteps = nullptr;   // per-ray `steps` buffer, only bound while rt_debug_enable_steps is on
     int shadeTile = kTile;  // k_shade tile = workgroup size: kTile (512), or 256 for contexts that share the GPU (RtConfig.shade_blocks_per_cu > 0)
     int shadeGrid = 1024;   // workgroups of k_shade (what the CUs hold at once; the kernel does not depend on it); set in rt_create
+    // The instantiations of the kernels that reach one of the seven builtins, for this context's arithmetic (cfg.builtins, resolved to
+    // RT_BUILTINS_IEEE or RT_BUILTINS_REFERENCE), shading, tile and accel: chosen once by choose_builtin_kernels (rt_create)
+    void (*kGenerate)(DevQueues, RtCamera, int, int) = nullptr;
+    void (*kShade)(DevScene, DevQueues, DevVariant, int) = nullptr;
+    void (*kFocus)(DevScene, RtCamera, int, int, int, int, float*) = nullptr;
 };
+// RT_BUILTINS_DEFAULT is IEEE in the shipped library; -DRT355_REF_BUILTINS (librt355_refb.so) changes that and nothing else
+#ifdef RT355_REF_BUILTINS
+static constexpr int32_t kDefaultBuiltins = RT_BUILTINS_REFERENCE;
+#else
+static constexpr int32_t kDefaultBuiltins = RT_BUILTINS_IEEE;
+#endif
+static bool resolve_builtins(int32_t word, int32_t* mode)
+{
+    if (word == RT_BUILTINS_DEFAULT) word = kDefaultBuiltins;
+    if (word != RT_BUILTINS_IEEE && word != RT_BUILTINS_REFERENCE) return false;
+    *mode = word;
+    return true;
+}
+template <bool REFB> static void choose_builtin_kernels_of(RtCtx* ctx)
+{
+    const bool nee = ctx->cfg.shading == RT_SHADING_NEE, small = ctx->shadeTile == 256;
+    ctx->kGenerate = k_generate<REFB>;
+    ctx->kShade = nee ? (small ? k_shade<true, 256, REFB> : k_shade<true, kTile, REFB>) : (small ? k_shade<false, 256, REFB> : k_shade<false, kTile, REFB>);
+    ctx->kFocus = ctx->cfg.accel == RT_ACCEL_BVH4 ? k_focus<RT_ACCEL_BVH4, REFB> : k_focus<RT_ACCEL_BVH2, REFB>;
+}
+static void choose_builtin_kernels(RtCtx* ctx)   // needs cfg (builtins resolved) and shadeTile
+{
+    if (ctx->cfg.builtins == RT_BUILTINS_REFERENCE) choose_builtin_kernels_of<true>(ctx);
+    else choose_builtin_kernels_of<false>(ctx);
+}
 enum { ST_GENERATE, ST_EXTEND, ST_SHADE, ST_COMPACT, ST_CONNECT, ST_ACCUM };
 // The traversal kernels of a context (layout 1 only; the first four values are RtKernelInfo.persist):
 enum Traversal {
@@ -148,6 +178,11 @@ static bool tlas_trav(const RtCtx* c) { return c->trav == TRAV_TLAS || c->trav =
 extern "C" const char* rt_last_error(void) { return g_err.c_str(); }
 extern "C" int rt_device_count(void) { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess) return 0; return n; }
 static int sync_scene_config(RtCtx* ctx);
+extern "C" int rt_builtins(RtCtx* ctx)
+{
+    if (!ctx) return fail(RT_E_INVALID, "rt_builtins: null context");
+    return ctx->cfg.builtins;
+}
 extern "C" int rt_kernel_info(RtCtx* ctx, RtKernelInfo* out)
 {
     if (!ctx || !out) return fail(RT_E_INVALID, "rt_kernel_info: null argument");
@@ -334,6 +369,8 @@ extern "C" int rt_create(const RtConfig* cfg, RtCtx** out)
     if ((c.shading != RT_SHADING_SIMPLE && c.shading != RT_SHADING_NEE) || (c.sampling != RT_SAMPLING_HEMISPHERE && c.sampling != RT_SAMPLING_COSINE) ||
         (c.accel != RT_ACCEL_BVH2 && c.accel != RT_ACCEL_BVH4))
         return fail(RT_E_INVALID, "rt_create: unknown kernel variant");
+    if (!resolve_builtins(c.builtins, &c.builtins))
+        return fail(RT_E_INVALID, "rt_create: RtConfig.builtins = %d is none of RT_BUILTINS_DEFAULT (0), RT_BUILTINS_IEEE (1), RT_BUILTINS_REFERENCE (2)", cfg->builtins);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(RT_E_DEVICE, "rt_create: no HIP device visible (this library has no CPU path)");
@@ -355,13 +392,8 @@ extern "C" int rt_create(const RtConfig* cfg, RtCtx** out)
         HIPCHK(hipGetDeviceProperties(&prop, c.device));
         ctx->shadeTile = c.shade_blocks_per_cu > 0 ? 256 : kTile;
         if (const char* t = getenv("RT355_SHADE_TILE")) { const int v = atoi(t); if (v == 256 || v == 512) ctx->shadeTile = v; }
-        if (c.shading == RT_SHADING_NEE) {
-            if (ctx->shadeTile == 256) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, (k_shade<true, 256>), 256, 0));
-            else HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, (k_shade<true, kTile>), kTile, 0));
-        } else {
-            if (ctx->shadeTile == 256) HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, (k_shade<false, 256>), 256, 0));
-            else HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, (k_shade<false, kTile>), kTile, 0));
-        }
+        choose_builtin_kernels(ctx);
+        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, ctx->kShade, ctx->shadeTile, 0));
         perCU = std::min(perCU, kAdmitAnySgpr);
         ctx->shadeGrid = prop.multiProcessorCount * std::max(1, perCU);
         if (c.shade_blocks_per_cu > 0 && c.shade_blocks_per_cu <= 16) ctx->shadeGrid = prop.multiProcessorCount * c.shade_blocks_per_cu;
@@ -1354,7 +1386,7 @@ static int generate(RtCtx* ctx, const RtCamera* cam, const RtSettings* s, int be
 {
     if (beginFrame) frame_state_reset(ctx);
     ctx->queued = true;
-    LAUNCH(ctx, ST_GENERATE, k_generate, grid_for(ctx->nPix), 0, ctx->q, *cam, s ? s->antiAliasing : 1, beginFrame);
+    LAUNCH(ctx, ST_GENERATE, ctx->kGenerate, grid_for(ctx->nPix), 0, ctx->q, *cam, s ? s->antiAliasing : 1, beginFrame);
     HIPCHK(hipGetLastError());
     ctx->primaryRays += (uint64_t)ctx->nPix;
     ctx->generated = true;
@@ -1398,13 +1430,7 @@ extern "C" int rt_stage_shade(RtCtx* ctx, int32_t bounce)
     }
     const int tileSz = ctx->shadeTile;
     const dim3 sg((unsigned)std::max(1, std::min(ctx->shadeGrid, (ctx->nPix + tileSz - 1) / tileSz)));
-    if (ctx->cfg.shading == RT_SHADING_NEE) {
-        if (tileSz == 256) LAUNCHB(ctx, ST_SHADE, (k_shade<true, 256>), sg, 256, 0, ctx->sc, ctx->q, ctx->var, bounce);
-        else LAUNCHB(ctx, ST_SHADE, (k_shade<true, kTile>), sg, kTile, 0, ctx->sc, ctx->q, ctx->var, bounce);
-    } else {
-        if (tileSz == 256) LAUNCHB(ctx, ST_SHADE, (k_shade<false, 256>), sg, 256, 0, ctx->sc, ctx->q, ctx->var, bounce);
-        else LAUNCHB(ctx, ST_SHADE, (k_shade<false, kTile>), sg, kTile, 0, ctx->sc, ctx->q, ctx->var, bounce);
-    }
+    LAUNCHB(ctx, ST_SHADE, ctx->kShade, sg, tileSz, 0, ctx->sc, ctx->q, ctx->var, bounce);
     ctx->shadeRun[bounce] = true;
     HIPCHK(hipGetLastError());
     return RT_OK;
@@ -1476,10 +1502,7 @@ extern "C" int rt_focus(RtCtx* ctx, int32_t x, int32_t y, const RtCamera* cam, f
     int rc = need_scene(ctx, "rt_focus"); if (rc) return rc;
     if (!cam || !t) return fail(RT_E_INVALID, "rt_focus: null argument");
     HIPCHK(hipSetDevice(ctx->cfg.device));
-    if (ctx->cfg.accel == RT_ACCEL_BVH4)
-        hipLaunchKernelGGL((k_focus<RT_ACCEL_BVH4>), dim3(1), dim3(kBlock), stack_bytes(ctx), ctx->stream, ctx->sc, *cam, x, y, ctx->cfg.width, ctx->cfg.height, ctx->dFocus);
-    else
-        hipLaunchKernelGGL((k_focus<RT_ACCEL_BVH2>), dim3(1), dim3(kBlock), stack_bytes(ctx), ctx->stream, ctx->sc, *cam, x, y, ctx->cfg.width, ctx->cfg.height, ctx->dFocus);
+    hipLaunchKernelGGL(ctx->kFocus, dim3(1), dim3(kBlock), stack_bytes(ctx), ctx->stream, ctx->sc, *cam, x, y, ctx->cfg.width, ctx->cfg.height, ctx->dFocus);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(t, ctx->dFocus, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -1661,57 +1684,51 @@ extern "C" int rt_debug_get_steps(RtCtx* ctx, int32_t* out, int32_t capacity, in
 
 // ---- the kernels' math functions on their own (rt_debug_math, tests/test_gpu_math.py) ---------------------------------
 // Each case calls the function the renderer calls; nothing here restates one.
-#ifdef RT355_REF_BUILTINS
-static constexpr bool kMathHasAcosAtan = false;
-#else
-static constexpr bool kMathHasAcosAtan = true;
-#endif
-static __device__ __forceinline__ uint32_t math_one(int fn, uint32_t bits)
+// REFB as in rt355_kernels.h; the REFERENCE set has no acos / atan of its own (it calls acospi / atan2pi inside the texel lookup only).
+template <bool REFB> static __device__ __forceinline__ uint32_t math_one(int fn, uint32_t bits)
 {
     const float x = __uint_as_float(bits);
     float r;
     switch (fn) {
-    case RT_MATH_EXP: r = rt_expf(x); break;
-    case RT_MATH_SIN: r = rt_sinf(x); break;
-    case RT_MATH_COS: r = rt_cosf(x); break;
-#ifndef RT355_REF_BUILTINS
-    case RT_MATH_ACOS: r = rt_acosf(x); break;
-    case RT_MATH_ATAN: r = rt_atan2f(x, 1.0f); break;
-#endif
+    case RT_MATH_EXP: r = rt_expf<REFB>(x); break;
+    case RT_MATH_SIN: r = rt_sinf<REFB>(x); break;
+    case RT_MATH_COS: r = rt_cosf<REFB>(x); break;
     case RT_MATH_F2I: return (uint32_t)f2i_gpu(x);
+    case RT_MATH_ACOS: if constexpr (!REFB) { r = rt_acosf(x); break; }   // REFB: not a function of that set (the host refuses it)
+    case RT_MATH_ATAN: if constexpr (!REFB) { r = rt_atan2f(x, 1.0f); break; }
     default: r = 0.0f; break;
     }
     return __float_as_uint(r);
 }
+template <bool REFB>
 __global__ __launch_bounds__(kBlock) void k_debug_math(int fn, const uint32_t* in, uint32_t* out, int64_t n)
 {
     for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
         const uint32_t* a = in;
         uint32_t* o = out;
         switch (fn) {
-#ifndef RT355_REF_BUILTINS
-        case RT_MATH_ATAN2: o[i] = __float_as_uint(rt_atan2f(__uint_as_float(a[2 * i]), __uint_as_float(a[2 * i + 1]))); break;
-#endif
         case RT_MATH_SPHERE_TEXEL: {
             const uint32_t* e = a + 6 * i;
             const float4 N = mk4(__uint_as_float(e[0]), __uint_as_float(e[1]), __uint_as_float(e[2]), __uint_as_float(e[3]));
             int x, y;
-            sphere_texel_xy(N, (int)e[4], (int)e[5], x, y);
+            sphere_texel_xy<REFB>(N, (int)e[4], (int)e[5], x, y);
             o[2 * i] = (uint32_t)x; o[2 * i + 1] = (uint32_t)y;
         } break;
         case RT_MATH_NORMALIZE4:
         case RT_MATH_LENGTH4: {
             const uint32_t* e = a + 4 * i;
             const float4 v = mk4(__uint_as_float(e[0]), __uint_as_float(e[1]), __uint_as_float(e[2]), __uint_as_float(e[3]));
-            if (fn == RT_MATH_LENGTH4) { o[i] = __float_as_uint(length4(v)); break; }
-            const float4 r = normalize4(v);
+            if (fn == RT_MATH_LENGTH4) { o[i] = __float_as_uint(length4<REFB>(v)); break; }
+            const float4 r = normalize4<REFB>(v);
             o[4 * i] = __float_as_uint(r.x); o[4 * i + 1] = __float_as_uint(r.y); o[4 * i + 2] = __float_as_uint(r.z); o[4 * i + 3] = __float_as_uint(r.w);
         } break;
-        default: o[i] = math_one(fn, a[i]); break;
+        case RT_MATH_ATAN2: if constexpr (!REFB) { o[i] = __float_as_uint(rt_atan2f(__uint_as_float(a[2 * i]), __uint_as_float(a[2 * i + 1]))); break; }   // REFB: as in math_one
+        default: o[i] = math_one<REFB>(fn, a[i]); break;
         }
     }
 }
 static constexpr int kSweepPerThread = 64;   // a workgroup hashes 256 x 64 = 2^14 inputs; a block of 2^20 takes 64 workgroups
+template <bool REFB>
 __global__ __launch_bounds__(kBlock) void k_debug_math_sweep(int fn, uint32_t firstBlock, unsigned long long* hashes)
 {
     __shared__ unsigned long long part[kBlock];
@@ -1721,7 +1738,7 @@ __global__ __launch_bounds__(kBlock) void k_debug_math_sweep(int fn, uint32_t fi
     unsigned long long h = 0;
     for (int k = 0; k < kSweepPerThread; k++) {
         const uint32_t bits = base + (uint32_t)k * kBlock + threadIdx.x;
-        uint32_t r = math_one(fn, bits);
+        uint32_t r = math_one<REFB>(fn, bits);
         if (fn != RT_MATH_F2I && (r & 0x7fffffffu) > 0x7f800000u) r = 0x7fc00000u;
         unsigned long long z = ((unsigned long long)bits << 32 | r) + 0x9e3779b97f4a7c15ull;   // splitmix64
         z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
@@ -1743,12 +1760,15 @@ static int math_device(const char* who)
     HIPCHK(hipSetDevice(0));
     return RT_OK;
 }
-extern "C" int rt_debug_math(int32_t fn, const void* in, void* out, int64_t n)
+extern "C" int rt_debug_math_mode(int32_t builtins, int32_t fn, const void* in, void* out, int64_t n)
 {
+    int32_t mode;
+    if (!resolve_builtins(builtins, &mode)) return fail(RT_E_INVALID, "rt_debug_math: builtins = %d is none of RT_BUILTINS_DEFAULT (0), RT_BUILTINS_IEEE (1), RT_BUILTINS_REFERENCE (2)", builtins);
+    const bool refb = mode == RT_BUILTINS_REFERENCE;
     static const int inWords[] = { 1, 1, 1, 1, 1, 1, 2, 6, 4, 4 }, outWords[] = { 1, 1, 1, 1, 1, 1, 1, 2, 4, 1 };
     if (fn < RT_MATH_EXP || fn > RT_MATH_LENGTH4 || n < 0 || (n > 0 && (!in || !out))) return fail(RT_E_INVALID, "rt_debug_math: bad argument");
-    if (!kMathHasAcosAtan && (fn == RT_MATH_ACOS || fn == RT_MATH_ATAN || fn == RT_MATH_ATAN2))
-        return fail(RT_E_UNSUPPORTED, "rt_debug_math: this build evaluates acos / atan2 only as acospi / atan2pi inside RT_MATH_SPHERE_TEXEL");
+    if (refb && (fn == RT_MATH_ACOS || fn == RT_MATH_ATAN || fn == RT_MATH_ATAN2))
+        return fail(RT_E_UNSUPPORTED, "rt_debug_math: RT_BUILTINS_REFERENCE evaluates acos / atan2 only as acospi / atan2pi inside RT_MATH_SPHERE_TEXEL");
     int rc = math_device("rt_debug_math"); if (rc) return rc;
     if (n == 0) return RT_OK;
     const size_t inB = sizeof(uint32_t) * inWords[fn] * (size_t)n, outB = sizeof(uint32_t) * outWords[fn] * (size_t)n;
@@ -1758,7 +1778,7 @@ extern "C" int rt_debug_math(int32_t fn, const void* in, void* out, int64_t n)
     if (e == hipSuccess) e = hipMemcpy(dIn, in, inB, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         const int grid = (int)std::min<int64_t>((n + kBlock - 1) / kBlock, 65536);
-        hipLaunchKernelGGL(k_debug_math, dim3(grid), dim3(kBlock), 0, 0, (int)fn, dIn, dOut, (int64_t)n);
+        hipLaunchKernelGGL(refb ? k_debug_math<true> : k_debug_math<false>, dim3(grid), dim3(kBlock), 0, 0, (int)fn, dIn, dOut, (int64_t)n);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy(out, dOut, outB, hipMemcpyDeviceToHost);
@@ -1766,13 +1786,17 @@ extern "C" int rt_debug_math(int32_t fn, const void* in, void* out, int64_t n)
     if (e != hipSuccess) return fail(RT_E_DEVICE, "rt_debug_math: %s", hipGetErrorString(e));
     return RT_OK;
 }
-extern "C" int rt_debug_math_sweep(int32_t fn, int32_t firstBlock, int32_t nBlocks, uint64_t* hashes)
+extern "C" int rt_debug_math(int32_t fn, const void* in, void* out, int64_t n) { return rt_debug_math_mode(RT_BUILTINS_DEFAULT, fn, in, out, n); }
+extern "C" int rt_debug_math_sweep_mode(int32_t builtins, int32_t fn, int32_t firstBlock, int32_t nBlocks, uint64_t* hashes)
 {
+    int32_t mode;
+    if (!resolve_builtins(builtins, &mode)) return fail(RT_E_INVALID, "rt_debug_math_sweep: builtins = %d is none of RT_BUILTINS_DEFAULT (0), RT_BUILTINS_IEEE (1), RT_BUILTINS_REFERENCE (2)", builtins);
+    const bool refb = mode == RT_BUILTINS_REFERENCE;
     constexpr int kBlocks = 1 << (32 - RT_MATH_SWEEP_BLOCK_BITS);
     if (fn < RT_MATH_EXP || fn > RT_MATH_F2I || firstBlock < 0 || nBlocks < 0 || firstBlock + nBlocks > kBlocks || (nBlocks > 0 && !hashes))
         return fail(RT_E_INVALID, "rt_debug_math_sweep: bad argument");
-    if (!kMathHasAcosAtan && (fn == RT_MATH_ACOS || fn == RT_MATH_ATAN))
-        return fail(RT_E_UNSUPPORTED, "rt_debug_math_sweep: this build has no acos / atan of its own");
+    if (refb && (fn == RT_MATH_ACOS || fn == RT_MATH_ATAN))
+        return fail(RT_E_UNSUPPORTED, "rt_debug_math_sweep: RT_BUILTINS_REFERENCE has no acos / atan of its own");
     int rc = math_device("rt_debug_math_sweep"); if (rc) return rc;
     if (nBlocks == 0) return RT_OK;
     unsigned long long* dH = nullptr;
@@ -1780,7 +1804,7 @@ extern "C" int rt_debug_math_sweep(int32_t fn, int32_t firstBlock, int32_t nBloc
     if (e == hipSuccess) e = hipMemset(dH, 0, sizeof(uint64_t) * nBlocks);
     if (e == hipSuccess) {
         const int groups = nBlocks * ((1 << RT_MATH_SWEEP_BLOCK_BITS) / (kBlock * kSweepPerThread));
-        hipLaunchKernelGGL(k_debug_math_sweep, dim3(groups), dim3(kBlock), 0, 0, (int)fn, (uint32_t)firstBlock, dH);
+        hipLaunchKernelGGL(refb ? k_debug_math_sweep<true> : k_debug_math_sweep<false>, dim3(groups), dim3(kBlock), 0, 0, (int)fn, (uint32_t)firstBlock, dH);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy(hashes, dH, sizeof(uint64_t) * nBlocks, hipMemcpyDeviceToHost);
@@ -1788,6 +1812,7 @@ extern "C" int rt_debug_math_sweep(int32_t fn, int32_t firstBlock, int32_t nBloc
     if (e != hipSuccess) return fail(RT_E_DEVICE, "rt_debug_math_sweep: %s", hipGetErrorString(e));
     return RT_OK;
 }
+extern "C" int rt_debug_math_sweep(int32_t fn, int32_t firstBlock, int32_t nBlocks, uint64_t* hashes) { return rt_debug_math_sweep_mode(RT_BUILTINS_DEFAULT, fn, firstBlock, nBlocks, hashes); }
 
 // ---- post-processing chain (renderer.cpp:95-124 PostProc, :303-308 SaveFrame) ----------------------------------------
 extern "C" int rt_postproc(RtCtx* ctx, int32_t frames, float vignette, float gamma, float chromatic, RtFloat4* outF32, uint8_t* outRGBA8)

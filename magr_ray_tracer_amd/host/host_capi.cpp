@@ -256,6 +256,17 @@ extern "C" int rth_renderer_camera_mouse(RthRenderer* r, float dx, float dy) { G
 extern "C" int rth_renderer_camera_zoom(RthRenderer* r, float offset) { GUARD(r->r->camera.Zoom(offset)) }
 // sample streams behind the Renderer (before Init): Tick() then renders `lanes` frames whose kernels overlap (include/rt355.h, rt_group_*)
 extern "C" int rth_renderer_set_lanes(RthRenderer* r, int lanes) { if (!r || lanes < 1 || lanes > 8) { g_herr = "rth_renderer_set_lanes: lanes must be 1..8"; return -1; } r->r->lanes = lanes; return 0; }
+// arithmetic of the contexts Init() creates (before Init): RT_BUILTINS_* of include/rt355.h; anything else is refused here
+extern "C" int rth_renderer_set_builtins(RthRenderer* r, int builtins)
+{
+    if (!r || (builtins != RT_BUILTINS_DEFAULT && builtins != RT_BUILTINS_IEEE && builtins != RT_BUILTINS_REFERENCE)) {
+        g_herr = "rth_renderer_set_builtins: builtins must be RT_BUILTINS_DEFAULT (0), RT_BUILTINS_IEEE (1) or RT_BUILTINS_REFERENCE (2)";
+        return -1;
+    }
+    r->r->builtins = builtins;
+    return 0;
+}
+extern "C" int rth_renderer_builtins(RthRenderer* r) { return r ? r->r->builtins : -1; }
 extern "C" int rth_renderer_frames(RthRenderer* r) { return r && r->r->settings ? r->r->settings->frames : -1; }
 extern "C" int rth_renderer_save_frame(RthRenderer* r, const char* file) { GUARD(r->r->SaveFrame(file)) }
 

@@ -242,6 +242,7 @@ public:
     RtGroup*       group = nullptr;    // the lanes behind this Renderer (include/rt355.h, rt_group_*)
     RtCtx*         ctx = nullptr;      // lane 0 (focus pick, counters, stage-level debugging)
     int            lanes = 1;          // set before Init(): sample streams whose frames overlap on the GPU; Tick() = `lanes` frames
+    int            builtins = 0;       // set before Init(): RtConfig.builtins of the lanes (RT_BUILTINS_DEFAULT / _IEEE / _REFERENCE, include/rt355.h)
     int width, height, device, y0, y1;
 };
 

@@ -47,14 +47,18 @@ def _rebuild_dict(st):
 class Device:
     def __init__(self, width, height, y0=0, y1=None, shading=_lib.SHADING_NEE, sampling=_lib.SAMPLING_COSINE,
                  accel=_lib.ACCEL_BVH2, russian_roulette=True, filter_fireflies=True, max_bounces=_lib.MAX_BOUNCES,
-                 device=0, profile=False, extend_variant=0, shade_blocks_per_cu=0, persist_blocks_per_cu=0, lib=None):
-        self._lib = _lib.device_lib(lib)      # lib="refb": the build with the reference's OpenCL builtin sequences (tests only)
+                 device=0, profile=False, extend_variant=0, shade_blocks_per_cu=0, persist_blocks_per_cu=0, lib=None, builtins=None):
+        # builtins: None (the library's default: IEEE) | "ieee" (reproducible on a CPU, what the oracle checks) | "reference" (the
+        # instruction sequences of the reference's own kernels: the reference's image from the reference's seeds)
+        mode = _lib.builtins_value(builtins)
+        self._lib = _lib.device_lib(lib)      # lib="refb": the build whose DEFAULT is "reference" (a yardstick of the tests)
         cfg = np.zeros((), dtype=_lib.Config)
         cfg["width"], cfg["height"], cfg["y0"], cfg["y1"] = width, height, y0, height if y1 is None else y1
         cfg["max_bounces"], cfg["shading"], cfg["sampling"], cfg["accel"] = max_bounces, shading, sampling, accel
         cfg["russian_roulette"], cfg["filter_fireflies"] = int(russian_roulette), int(filter_fireflies)
         cfg["device"], cfg["profile"], cfg["extend_variant"] = device, (2 if profile is True else int(profile)), extend_variant
         cfg["shade_blocks_per_cu"], cfg["persist_blocks_per_cu"] = shade_blocks_per_cu, persist_blocks_per_cu
+        cfg["builtins"] = mode
         self.cfg = cfg
         self.width, self.height = width, height
         self.y0, self.y1 = int(cfg["y0"]), int(cfg["y1"])
@@ -146,6 +150,14 @@ class Device:
         k = np.zeros((), dtype=_lib.KernelInfo)
         self._chk(self._lib.rt_kernel_info(self._h, k.ctypes.data_as(C.c_void_p)))
         return {n: int(k[n]) for n in k.dtype.names}
+
+    @property
+    def builtins(self):
+        """The context's arithmetic as resolved by the library (rt_builtins): _lib.BUILTINS_IEEE or _lib.BUILTINS_REFERENCE."""
+        rc = self._lib.rt_builtins(self._h)
+        if rc < 0:
+            self._chk(rc)
+        return int(rc)
 
     def extend_kernel_name(self):
         k = self.kernel_info()
@@ -299,7 +311,8 @@ class Group:
 
     def __init__(self, width, height, lanes=4, y0=0, y1=None, shading=_lib.SHADING_NEE, sampling=_lib.SAMPLING_COSINE,
                  accel=_lib.ACCEL_BVH2, russian_roulette=True, filter_fireflies=True, max_bounces=_lib.MAX_BOUNCES,
-                 device=0, profile=False, extend_variant=0, shade_blocks_per_cu=0, persist_blocks_per_cu=0):
+                 device=0, profile=False, extend_variant=0, shade_blocks_per_cu=0, persist_blocks_per_cu=0, builtins=None):
+        mode = _lib.builtins_value(builtins)   # as for Device; every lane gets it
         self._lib = _lib.device_lib()
         cfg = np.zeros((), dtype=_lib.Config)
         cfg["width"], cfg["height"], cfg["y0"], cfg["y1"] = width, height, y0, height if y1 is None else y1
@@ -307,6 +320,7 @@ class Group:
         cfg["russian_roulette"], cfg["filter_fireflies"] = int(russian_roulette), int(filter_fireflies)
         cfg["device"], cfg["profile"], cfg["extend_variant"] = device, (2 if profile is True else int(profile)), extend_variant
         cfg["shade_blocks_per_cu"], cfg["persist_blocks_per_cu"] = shade_blocks_per_cu, persist_blocks_per_cu
+        cfg["builtins"] = mode
         self.cfg, self.width, self.height, self.accel = cfg, width, height, accel
         self.y0, self.y1 = int(cfg["y0"]), int(cfg["y1"])
         h = C.c_void_p()
@@ -419,17 +433,24 @@ class Renderer:
     """The C++ Renderer mirror (host/renderer.cpp): Init(), Tick(), accumulator read-back, energy."""
 
     def __init__(self, scene, width, height, device=0, y0=0, y1=-1, shading=_lib.SHADING_NEE, sampling=_lib.SAMPLING_COSINE,
-                 bvh=_lib.ACCEL_BVH2, russian_roulette=True, filter_fireflies=True):
+                 bvh=_lib.ACCEL_BVH2, russian_roulette=True, filter_fireflies=True, builtins=None):
+        mode = _lib.builtins_value(builtins)   # as for Device
         self._lib = _lib.host_lib()
         self.width, self.height = width, height
         self._h = self._lib.rth_renderer_create(scene._h, width, height, device, y0, y1, shading, sampling, bvh,
                                                 int(russian_roulette), int(filter_fireflies))
         if not self._h:
             raise RtError(self._lib.rth_last_error().decode())
+        if mode != _lib.BUILTINS_DEFAULT:
+            self.SetBuiltins(mode)
 
     def _chk(self, rc):
         if rc < 0:
             raise RtError(self._lib.rth_last_error().decode())
+
+    def SetBuiltins(self, mode):
+        """Before Init(): the arithmetic of the context(s) Init() creates (_lib.BUILTINS_*)."""
+        self._chk(self._lib.rth_renderer_set_builtins(self._h, int(mode)))
 
     def SetCamera(self, origin, forward, fov=110.0, aperture=0.1):
         self._chk(self._lib.rth_renderer_set_camera(self._h, _lib.fvec(origin), _lib.fvec(forward), float(fov), float(aperture)))
