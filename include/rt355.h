@@ -129,7 +129,20 @@ int rt_upload_scene(RtCtx* ctx,
                     const RtBVHInstance* blas, int32_t nBlas);
 
 /* The host-side shape checks rt_upload_scene runs before it touches the device (index ranges, tree cycles and depths, stack needs,
- * the 32768-node / instance bound of the TLAS encodings), callable without a GPU.  `accel` says how bvhNodes is to be read. */
+ * the 32768-node / instance bound of the TLAS encodings), callable without a GPU.  `accel` says how bvhNodes is to be read.  What it
+ * accepts, every kernel and every derivation of rt_upload_scene can walk inside the arrays, within the stacks and in finite time, with
+ * the reference arrays and with the derived records alike; anything else is RT_E_INVALID or RT_E_UNSUPPORTED with a message.
+ *   BVH4 slots   slot k of a node is unused iff first[k] == -1 (RT_INVALID); a used slot needs count[k] >= 0 and first[k] >= 0:
+ *                count > 0 is a leaf with first + count <= nIdx, count == 0 a child with first < nNodes.  Every slot of every record
+ *                is held to this, reachable or not; a violation is RT_E_INVALID naming the node and the slot.  (The collapse writes
+ *                first = count = -1 into an unused slot and leaves absorbed nodes behind: both pass.)
+ *   sharing      instances may share a BLAS root.  A BVH2 subtree named by two parents is accepted as long as the walk over every
+ *                path from the root stays within 2 * nNodes + 2 node visits (each level of fully shared children doubles the visits:
+ *                a ladder of 3 such levels - 7 nodes, 15 visits - passes, one of 4 - 9 nodes, 31 visits - is refused as malformed),
+ *                a BVH4 one within nNodes + 1; such a scene renders but can neither be refit nor rebuilt in place.  A TLAS node
+ *                reachable twice is always refused.
+ *   unreachable  records no root leads to may hold zeros; their leaf ranges (BVH2) and slots (BVH4) are still checked.
+ * Counts below zero are RT_E_INVALID. */
 int rt_validate_scene(int32_t accel,
                       const RtPrimitive* prims, int32_t nPrims, const RtMaterial* mats, int32_t nMats,
                       const RtFloat4* textures, int32_t nTexels, const uint32_t* lights, int32_t nLights,
@@ -359,6 +372,10 @@ int rt_stage_shade(RtCtx* ctx, int32_t bounce);                                 
 int rt_stage_connect(RtCtx* ctx, int32_t firstBounce, int32_t lastBounce);      /* wavefront.cl:144-201 */
 /* Ray queue of `bounce` as reference-layout Ray structs (I and N as extend leaves them). */
 int rt_debug_get_rays(RtCtx* ctx, int32_t bounce, RtRay* out, int32_t capacity, int32_t* n);
+/* Replace the ray queue of `bounce` by n <= (y1 - y0) * width caller records.  The kernels index the accumulator by a record's
+ * pixelIdx and the primitive array by its primIdx (a ray that arrives already hit): a pixelIdx outside the context's band
+ * [y0 * width, y1 * width) or a primIdx outside [-1, nPrims) of the bound scene (-1 only, without one) is RT_E_INVALID, and the
+ * queue stays as it was. */
 int rt_debug_set_rays(RtCtx* ctx, int32_t bounce, const RtRay* in, int32_t n);
 /* Shadow rays appended by shade() of bounces [firstBounce,lastBounce], in queue order:
  * origin = I + L*EPSILON (xyz), tmax = dist - 2*EPSILON, dir = L (xyz), pixel index and the

@@ -59,6 +59,20 @@ LB_HD int stack_entries(int need)
     return e < RT_BVH4_STACK ? e : RT_BVH4_STACK;
 }
 
+// What one slot k of an RtBVHNode4 is - the one rule validate_scene, the stack-need replay and the layout-1 derivation go by.
+// traverse_bvh4 calls a slot used iff first != RT_INVALID, reads primIdx[first + j] for j < count when count > 0 and pushes `first`
+// as a node id otherwise, so a used slot must have count >= 0 and first >= 0: a leaf's range must lie in primIdx, a child in the node
+// array.  (The collapse only ever writes first = count = -1 into an unused slot.)
+enum Bvh4Slot { kSlotUnused = 0, kSlotLeaf = 1, kSlotChild = 2, kSlotBad = -1 };
+LB_HD int bvh4_slot(int32_t first, int32_t count, int32_t nNodes, int32_t nIdx)
+{
+    if (first == RT_INVALID) return kSlotUnused;
+    if (first < 0 || count < 0) return kSlotBad;
+    if (count > 0) return (int64_t)first + (int64_t)count <= (int64_t)nIdx ? kSlotLeaf : kSlotBad;
+    return first < nNodes ? kSlotChild : kSlotBad;
+}
+LB_HD int bvh4_slot(const RtBVHNode4& n, int k, int32_t nNodes, int32_t nIdx) { return bvh4_slot(n.first[k], n.count[k], nNodes, nIdx); }
+
 // ---- BLAS ranges (host only) ------------------------------------------------------------------------------------------------------
 // A scene can be rebuilt BLAS by BLAS when the primitives each distinct BLAS references form one contiguous range (a primitive may be
 // referenced several times, as SBVH leaves do), the ranges are disjoint and they come in the order of the roots - what appending BLAS

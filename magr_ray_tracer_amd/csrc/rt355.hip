@@ -485,19 +485,20 @@ static int bvh2_depth(const RtBVHNode2* n, int32_t nNodes, uint32_t root)
     }
     return best;
 }
-static int bvh4_stack_need(const RtBVHNode4* n, int32_t nNodes, uint32_t root)
+static int bvh4_stack_need(const RtBVHNode4* n, int32_t nNodes, int32_t nIdx, uint32_t root)
 {
-    // worst-case live stack entries of the unordered 4-wide traversal (push every interior child, pop one)
+    // worst-case live stack entries of the unordered 4-wide traversal (push every interior child, pop one); the slots have passed
+    // rebuild::bvh4_slot, so a child is what the kernel pushes
     std::vector<std::pair<uint32_t, int>> st; st.push_back({ root, 0 });
     int best = 0; size_t visited = 0;
     while (!st.empty()) {
         auto [i, base] = st.back(); st.pop_back();
-        if (i >= (uint32_t)nNodes || ++visited > (size_t)nNodes + 1) return -1;
+        if (++visited > (size_t)nNodes + 1) return -1;   // (in range: the root by the caller's check, a child by the slot rule)
         int kids = 0;
-        for (int k = 0; k < 4; k++) if (n[i].first[k] != RT_INVALID && n[i].count[k] == 0) kids++;
+        for (int k = 0; k < 4; k++) if (rebuild::bvh4_slot(n[i], k, nNodes, nIdx) == rebuild::kSlotChild) kids++;
         if (base + kids > best) best = base + kids;
         int pushed = 0;
-        for (int k = 0; k < 4; k++) if (n[i].first[k] != RT_INVALID && n[i].count[k] == 0) {
+        for (int k = 0; k < 4; k++) if (rebuild::bvh4_slot(n[i], k, nNodes, nIdx) == rebuild::kSlotChild) {
             // child k is popped when the (kids-1-pushed) later siblings are gone: entries below it = base + pushed
             st.push_back({ (uint32_t)n[i].first[k], base + pushed });
             pushed++;
@@ -517,6 +518,7 @@ static int validate_scene(int accel, const RtPrimitive* prims, int32_t nPrims, c
     if (accel != RT_ACCEL_BVH2 && accel != RT_ACCEL_BVH4) return fail(RT_E_INVALID, "rt_upload_scene: unknown accel %d", accel);
     if (!prims || nPrims <= 0 || !mats || nMats <= 0 || !bvhNodes || nNodes <= 0 || !primIdx || nIdx <= 0 || !tlas || nTlas <= 0 || !blas || nBlas <= 0)
         return fail(RT_E_INVALID, "rt_upload_scene: missing array (prims/materials/bvh/primIdx/tlas/blas are required)");
+    if (nLights < 0 || nTexels < 0) return fail(RT_E_INVALID, "rt_upload_scene: negative count (nLights %d, nTexels %d)", nLights, nTexels);
     if (nLights > 0 && !lights) return fail(RT_E_INVALID, "rt_upload_scene: nLights > 0 but lights == NULL");
     if (nTexels > 0 && !textures) return fail(RT_E_INVALID, "rt_upload_scene: nTexels > 0 but textures == NULL");
     // Child ids and instance ids of the TLAS travel as 15-bit values on the traversal stacks (bit 15 = leaf; the reference's own
@@ -558,9 +560,15 @@ static int validate_scene(int accel, const RtPrimitive* prims, int32_t nPrims, c
     // (SBVH trees at alpha = 0 do get deeper than 32); this library sizes the LDS stack to the tree, up to 64 entries.
     const int stackCap = RT_BVH4_STACK;
     int stackNeed = 1;
+    if (accel == RT_ACCEL_BVH4) {   // every slot of every node, before anything follows one (the rule: rebuild_common.h, bvh4_slot)
+        const RtBVHNode4* n4 = (const RtBVHNode4*)bvhNodes;
+        for (int32_t i = 0; i < nNodes; i++) for (int k = 0; k < 4; k++) if (rebuild::bvh4_slot(n4[i], k, nNodes, nIdx) == rebuild::kSlotBad)
+            return fail(RT_E_INVALID, "bvh4 node %d slot %d: first %d, count %d is neither unused (first = -1), a leaf range inside primIdx nor a child node", i, k,
+                        n4[i].first[k], n4[i].count[k]);
+    }
     for (int32_t b = 0; b < nBlas; b++) {
         if (blas[b].bvhIdx >= (uint32_t)nNodes) return fail(RT_E_INVALID, "instance %d: bvhIdx out of range", b);
-        int need = accel == RT_ACCEL_BVH4 ? bvh4_stack_need((const RtBVHNode4*)bvhNodes, nNodes, blas[b].bvhIdx)
+        int need = accel == RT_ACCEL_BVH4 ? bvh4_stack_need((const RtBVHNode4*)bvhNodes, nNodes, nIdx, blas[b].bvhIdx)
                                           : bvh2_depth((const RtBVHNode2*)bvhNodes, nNodes, blas[b].bvhIdx);
         if (need < 0) return fail(RT_E_INVALID, "instance %d: malformed BVH (child index out of range or cycle)", b);
         if (rebuild::exceeds_stack(need)) return fail(RT_E_UNSUPPORTED, "instance %d: traversal needs %d stack entries, at most %d are supported", b, need, stackCap);
@@ -570,10 +578,6 @@ static int validate_scene(int accel, const RtPrimitive* prims, int32_t nPrims, c
         const RtBVHNode2* n2 = (const RtBVHNode2*)bvhNodes;
         for (int32_t i = 0; i < nNodes; i++) if (n2[i].count > 0 && (uint64_t)n2[i].first + n2[i].count > (uint64_t)nIdx)
             return fail(RT_E_INVALID, "bvh node %d: leaf range exceeds primIdx", i);
-    } else {
-        const RtBVHNode4* n4 = (const RtBVHNode4*)bvhNodes;
-        for (int32_t i = 0; i < nNodes; i++) for (int k = 0; k < 4; k++) if (n4[i].first[k] != RT_INVALID && n4[i].count[k] > 0 &&
-            (int64_t)n4[i].first[k] + n4[i].count[k] > (int64_t)nIdx) return fail(RT_E_INVALID, "bvh4 node %d: leaf range exceeds primIdx", i);
     }
     if (stackEntriesOut) *stackEntriesOut = rebuild::stack_entries(stackNeed);   // (rebuild_common.h: rt_rebuild_scene sizes it the same way)
     if (texPadOut) *texPadOut = texPad;
@@ -719,7 +723,7 @@ extern "C" int rt_upload_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t nPr
     if (rc == RT_OK && ctx->cfg.accel == RT_ACCEL_BVH4 && ctx->cfg.extend_variant != 1 && nIdx < (1 << 24)) {
         const RtBVHNode4* n4 = (const RtBVHNode4*)bvhNodes;
         bool fits = true;
-        for (int32_t i = 0; i < nNodes && fits; i++) for (int k = 0; k < 4; k++) if (n4[i].first[k] != RT_INVALID && n4[i].count[k] > 127) fits = false;
+        for (int32_t i = 0; i < nNodes && fits; i++) for (int k = 0; k < 4; k++) if (n4[i].first[k] != RT_INVALID && n4[i].count[k] > (int32_t)rebuild::kMaxPackedLeaf) fits = false;
         if (fits) {
             auto f2u = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
             // The collapse (bvh.cpp:695-803) leaves the absorbed BVH2 nodes in the array: only the nodes still reachable from a BLAS
@@ -733,7 +737,7 @@ extern "C" int rt_upload_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t nPr
                 for (; head < order.size(); head++) {
                     const uint32_t i = order[head];
                     for (int k = 0; k < 4; k++) {
-                        if (n4[i].first[k] == RT_INVALID || n4[i].count[k] > 0) continue;
+                        if (rebuild::bvh4_slot(n4[i], k, nNodes, nIdx) != rebuild::kSlotChild) continue;
                         const uint32_t c = (uint32_t)n4[i].first[k];
                         if (newId[c] == 0xffffffffu) { newId[c] = (uint32_t)order.size(); order.push_back(c); }
                     }
@@ -746,8 +750,9 @@ extern "C" int rt_upload_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t nPr
                 for (int k = 0; k < 4; k++) {
                     const RtFloat4& mn = n4[i].aabbMin[k]; const RtFloat4& mx = n4[i].aabbMax[k];
                     b[k * 6 + 0] = mn.x; b[k * 6 + 1] = mn.y; b[k * 6 + 2] = mn.z; b[k * 6 + 3] = mx.x; b[k * 6 + 4] = mx.y; b[k * 6 + 5] = mx.z;
-                    if (n4[i].first[k] == RT_INVALID) e[k] = 0xffffffffu;
-                    else if (n4[i].count[k] > 0) e[k] = 0x80000000u | ((uint32_t)n4[i].count[k] << 24) | (uint32_t)n4[i].first[k];
+                    const int slot = rebuild::bvh4_slot(n4[i], k, nNodes, nIdx);
+                    if (slot == rebuild::kSlotUnused) e[k] = 0xffffffffu;
+                    else if (slot == rebuild::kSlotLeaf) e[k] = 0x80000000u | ((uint32_t)n4[i].count[k] << 24) | (uint32_t)n4[i].first[k];
                     else e[k] = newId[(uint32_t)n4[i].first[k]];
                 }
                 for (int v = 0; v < 6; v++) quads[q * 8 + v] = make_float4(b[v * 4], b[v * 4 + 1], b[v * 4 + 2], b[v * 4 + 3]);
@@ -1624,6 +1629,14 @@ extern "C" int rt_debug_get_rays(RtCtx* ctx, int32_t bounce, RtRay* out, int32_t
 extern "C" int rt_debug_set_rays(RtCtx* ctx, int32_t bounce, const RtRay* in, int32_t n)
 {
     if (!ctx || !in || n < 0 || n > ctx->nPix || bounce < 0 || bounce > ctx->cfg.max_bounces) return fail(RT_E_INVALID, "rt_debug_set_rays: bad argument");
+    // the kernels index the accumulator by pixelIdx and the primitives by primIdx: refuse what lies outside before anything is written
+    const int32_t nPrims = ctx->sceneLoaded ? ctx->sc.nPrims : 0;
+    for (int32_t i = 0; i < n; i++) {
+        if (in[i].pixelIdx < ctx->firstPixel || in[i].pixelIdx >= ctx->firstPixel + ctx->nPix)
+            return fail(RT_E_INVALID, "rt_debug_set_rays: ray %d: pixelIdx %d outside the context's band [%d, %d)", i, in[i].pixelIdx, ctx->firstPixel, ctx->firstPixel + ctx->nPix);
+        if (in[i].primIdx < -1 || in[i].primIdx >= nPrims)
+            return fail(RT_E_INVALID, "rt_debug_set_rays: ray %d: primIdx %d outside [-1, %d)", i, in[i].primIdx, nPrims);
+    }
     HIPCHK(hipSetDevice(ctx->cfg.device));
     int rc = ray_io(ctx); if (rc) return rc;
     HIPCHK(hipStreamSynchronize(ctx->stream));

@@ -118,6 +118,11 @@ int rth_bvh4_from_nodes(const RtBVHNode2* nodes, int n, RtBVHNode4* out)
             if (i >= (uint32_t)n || ++visited > (size_t)n) { g_herr = "rth_bvh4_from_nodes: child index out of range or a node reachable twice"; return -1; }
             if (nodes[i].count == 0) { st.push_back(nodes[i].first); st.push_back(nodes[i].first + 1); }
         }
+        // ... and Convert reads both children of EVERY interior record of the array, reachable from node 0 or not
+        for (int i = 0; i < n; i++) if (nodes[i].count == 0 && (uint64_t)nodes[i].first + 1 >= (uint64_t)n) {
+            g_herr = "rth_bvh4_from_nodes: node " + std::to_string(i) + ": child index out of range (an unreachable interior record is converted too)";
+            return -1;
+        }
     }
     try {
         std::vector<RtPrimitive> prims; std::vector<RtBVHInstance> blas(1);
