@@ -189,6 +189,28 @@ int rt_build_bvh2_sah(int32_t device, const RtPrimitive* prims, int32_t nPrims, 
 /* Wall-clock split of this process's last successful rt_build_bvh2_sah (measurement aid, tools/sah_gpu_bench.py): out[0] allocation
  * and upload, out[1] the level passes, out[2] numbering and emit, out[3] download (ms), out[4] the number of level passes. */
 int rt_debug_sah_phases(float* out);
+/* SBVH BLAS trees on the GPU: BVH2::BuildBLAS with bvh2->alpha = alpha in [0, 1] (binned SAH with spatial splits; 0 = full SBVH,
+ * 1 = rt_build_bvh2_sah's tree) over the primitives [first, first + count) of prims[nPrims], on `device`.  Nodes and primIdx equal,
+ * byte for byte, what BuildBLAS(startIdx = first) appends (see rt_build_bvh2_sah: root at nodeBase, LIFO numbering, leaves index
+ * primIdx from idxBase, ids global).  A spatial split duplicates refs, so neither array has a bound known beforehand: when nodeCap
+ * or idxCap is too small for the finished tree the call writes nothing to nodes / primIdx, stores the needed sizes in *nNodes /
+ * *nIdx and returns RT_E_INVALID with "capacity" in the message; a second call with those sizes succeeds.  The rules live in
+ * csrc/sbvh_common.h; the host restatement rth_build_bvh2_sbvh (rt355_host.h) gives the same arrays.  Any depth.  Synchronous, on a
+ * stream of its own; the caller's device is restored.  stats may be NULL.  The environment variable RT355_SBVH_INITIAL_REFS=k,
+ * read per call, sets the initial capacity of the ref arrays (they grow level by level; for tests and A/B runs).
+ * Refusals write nothing to the caller's arrays:
+ *   RT_E_INVALID      alpha not in [0, 1] (NaN included); rt_build_bvh2_sah's argument checks except the capacities; capacity (above);
+ *   RT_E_NOMEM        device memory (the ref arrays grow with the tree);
+ *   RT_E_UNSUPPORTED  what rt_build_bvh2_sah refuses, and a spatial bin index scale * (x - bmin) that is not finite, is <= -1 or is
+ *                     >= 2^31 where a spatial split is evaluated (a ref with an empty or inverted box: a plane inside the range, a
+ *                     sphere fragment whose clip came out inverted).  BuildBLAS indexes bins[] with it; it throws by the same rule. */
+int rt_build_bvh2_sbvh(int32_t device, float alpha, const RtPrimitive* prims, int32_t nPrims, int32_t first, int32_t count,
+                       uint32_t nodeBase, uint32_t idxBase, RtBVHNode2* nodes, int32_t nodeCap, int32_t* nNodes, uint32_t* primIdx,
+                       int32_t idxCap, int32_t* nIdx, RtSbvhStats* stats);
+/* Wall-clock split of this process's last successful rt_build_bvh2_sbvh (tools/sbvh_gpu_bench.py): out[0] allocation and upload,
+ * out[1] the level passes, out[2] numbering and emit, out[3] download (ms), out[4] the number of level passes, out[5] scratch bytes
+ * per work-item of the spatial-bin kernel, out[6] of the flag kernel, out[7] of the scatter kernel (the three that clip). */
+int rt_debug_sbvh_phases(float* out);
 
 /* ---- in-place scene updates (animation) ----------------------------------------------------------------------------------------
  * What Renderer::Tick's disabled animation hook (renderer.cpp:29-37: scene.Animate, tlas->Build, the node buffers' CopyToDevice) needs,

@@ -62,6 +62,14 @@ int rth_build_blas_sah_gpu(RthScene* s, int startIdx, int device);
 /* The host restatement on caller arrays: rt_build_bvh2_sah's contract without the device (stats->device_ms = 0). */
 int rth_build_bvh2_sah(const RtPrimitive* prims, int32_t nPrims, int32_t first, int32_t count, uint32_t nodeBase, uint32_t idxBase,
                        RtBVHNode2* nodes, int32_t nodeCap, int32_t* nNodes, uint32_t* primIdx, RtBuildStats* stats);
+/* SBVH trees by the GPU builder (rt_build_bvh2_sbvh, rt355.h) over primitives [startIdx, end), appended exactly as
+ * rth_build_blas(s, startIdx, alpha) appends them (instance record, nodes, primIdx, rth_bvh_stats including spatial splits and clipped
+ * primitives).  device >= 0: on that GPU; -1: the host restatement.  Returns RT_E_* and leaves the scene unchanged when refused. */
+int rth_build_blas_sbvh_gpu(RthScene* s, int startIdx, float alpha, int device);
+/* The host restatement on caller arrays: rt_build_bvh2_sbvh's contract without the device (stats->device_ms = 0). */
+int rth_build_bvh2_sbvh(float alpha, const RtPrimitive* prims, int32_t nPrims, int32_t first, int32_t count, uint32_t nodeBase,
+                        uint32_t idxBase, RtBVHNode2* nodes, int32_t nodeCap, int32_t* nNodes, uint32_t* primIdx, int32_t idxCap,
+                        int32_t* nIdx, RtSbvhStats* stats);
 /* The host restatement of rt_update_scene (rt355.h): rth_set_primitives replaces primitives [first, first + count), which must keep
  * their objType and matIdx; rth_refit refits every BLAS of the scene's BVH2 in place by the rules rt_update_scene runs on the device
  * (csrc/refit_common.h).  The caller then runs rth_build_tlas (and rth_build_bvh4 if it renders a BVH4).  Both return RT_E_* and

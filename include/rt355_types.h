@@ -147,6 +147,13 @@ typedef struct RtBuildStats {
     float   wall_ms;               /* the whole call, transfers and allocations included                                */
     int32_t _reserved;
 } RtBuildStats;
+typedef struct RtSbvhStats {         /* rt_build_bvh2_sbvh (rt355.h) */
+    int32_t nodes, leaves, n_idx, depth;       /* records, leaves, primIdx entries, BVH2::Depth */
+    int32_t spatial_splits, prims_clipped;     /* as BVH2::stat_* count them                    */
+    int32_t forced_leaves, levels;             /* BVH2::stat_forced_leaves; level passes        */
+    float   sah_cost, device_ms, wall_ms;      /* as in RtBuildStats                            */
+    int32_t peak_refs;                         /* most refs alive in one level                  */
+} RtSbvhStats;
 
 RT_STATIC_ASSERT(sizeof(RtRay) == 128 && offsetof(RtRay, t) == 96 && offsetof(RtRay, primIdx) == 100 &&
                  offsetof(RtRay, pixelIdx) == 108 && offsetof(RtRay, inside) == 112 &&
@@ -168,6 +175,7 @@ RT_STATIC_ASSERT(sizeof(RtBVHNode2) == 48 && offsetof(RtBVHNode2, first) == 32, 
 RT_STATIC_ASSERT(sizeof(RtBVHNode4) == 160 && offsetof(RtBVHNode4, first) == 128 && offsetof(RtBVHNode4, count) == 144, "BVHNode4 layout");
 RT_STATIC_ASSERT(sizeof(RtBVHInstance) == 68 && offsetof(RtBVHInstance, invT) == 4, "BVHInstance layout");
 RT_STATIC_ASSERT(sizeof(RtBuildOptions) == 16 && sizeof(RtBuildStats) == 32, "build options / stats layout");
+RT_STATIC_ASSERT(sizeof(RtSbvhStats) == 48, "SBVH build stats layout");
 RT_STATIC_ASSERT(sizeof(RtTLASNode) == 48 && offsetof(RtTLASNode, leftRight) == 32 && offsetof(RtTLASNode, BLASidx) == 36, "TLASNode layout");
 
 #ifdef __cplusplus

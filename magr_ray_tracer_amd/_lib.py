@@ -49,12 +49,14 @@ Config = np.dtype([(n, "<i4") for n in ("width", "height", "y0", "y1", "max_boun
 BuildOptions = np.dtype([("max_leaf", "<i4"), ("cost_traverse", "<f4"), ("cost_intersect", "<f4"), ("_reserved", "<i4")])
 BuildStats = np.dtype([("nodes", "<i4"), ("leaves", "<i4"), ("depth", "<i4"), ("morton_bits", "<i4"), ("sah_cost", "<f4"),
                        ("device_ms", "<f4"), ("wall_ms", "<f4"), ("_reserved", "<i4")])
+SbvhStats = np.dtype([(n, "<i4") for n in ("nodes", "leaves", "n_idx", "depth", "spatial_splits", "prims_clipped", "forced_leaves", "levels")] +
+                     [("sah_cost", "<f4"), ("device_ms", "<f4"), ("wall_ms", "<f4"), ("peak_refs", "<i4")])   # RtSbvhStats
 KernelInfo = np.dtype([(n, "<i4") for n in ("layout", "persist", "persist4", "stack_entries", "persist_grid", "persist_grid_connect",
                                              "shade_grid", "n_blas")])
 
 _SIZES = {"Ray": (Ray, 128), "ShadowRay": (ShadowRay, 96), "Material": (Material, 80), "Primitive": (Primitive, 128),
           "Camera": (Camera, 128), "Settings": (Settings, 40), "BVHNode2": (BVHNode2, 48), "BVHNode4": (BVHNode4, 160),
-          "BVHInstance": (BVHInstance, 68), "TLASNode": (TLASNode, 48), "BuildOptions": (BuildOptions, 16), "BuildStats": (BuildStats, 32), "ShadowRecord": (ShadowRecord, 48), "Config": (Config, 64)}
+          "BVHInstance": (BVHInstance, 68), "TLASNode": (TLASNode, 48), "BuildOptions": (BuildOptions, 16), "BuildStats": (BuildStats, 32), "SbvhStats": (SbvhStats, 48), "ShadowRecord": (ShadowRecord, 48), "Config": (Config, 64)}
 for _n, (_d, _s) in _SIZES.items():
     assert _d.itemsize == _s, (_n, _d.itemsize, _s)
 
@@ -100,7 +102,7 @@ DEVICE_SYMBOLS = [
     "rt_read_accum", "rt_write_accum", "rt_postproc", "rt_read_counters", "rt_reset_counters", "rt_read_stage_times", "rt_reset_stage_times", "rt_set_profile",
     "rt_stage_begin_frame", "rt_stage_generate", "rt_stage_extend", "rt_stage_shade", "rt_stage_connect",
     "rt_debug_get_rays", "rt_debug_set_rays", "rt_debug_get_shadow", "rt_debug_enable_steps", "rt_debug_get_steps", "rt_debug_math",
-    "rt_debug_math_sweep", "rt_debug_math_mode", "rt_debug_math_sweep_mode", "rt_validate_scene", "rt_build_bvh2", "rt_build_bvh2_sah", "rt_debug_sah_phases", "rt_update_scene", "rt_group_update_scene", "rt_debug_get_scene_array",
+    "rt_debug_math_sweep", "rt_debug_math_mode", "rt_debug_math_sweep_mode", "rt_validate_scene", "rt_build_bvh2", "rt_build_bvh2_sah", "rt_debug_sah_phases", "rt_build_bvh2_sbvh", "rt_debug_sbvh_phases", "rt_update_scene", "rt_group_update_scene", "rt_debug_get_scene_array",
     "rt_rebuild_scene", "rt_group_rebuild_scene", "rt_blas_ranges",
     "rt_group_create", "rt_group_destroy", "rt_group_lanes", "rt_group_concurrency", "rt_group_lane", "rt_group_frames", "rt_group_upload_scene", "rt_group_share_scene",
     "rt_group_seed", "rt_group_reset", "rt_group_render", "rt_group_synchronize", "rt_group_sum", "rt_group_read_accum", "rt_group_focus",
@@ -114,7 +116,7 @@ HOST_SYMBOLS = [
     "rth_renderer_read", "rth_renderer_camera", "rth_seed_stream", "rth_load_model", "rth_save_png",
     "rth_set_build_threads", "rth_renderer_save_frame", "rth_renderer_camera_move", "rth_renderer_camera_mouse", "rth_renderer_camera_zoom", "rth_renderer_frames", "rth_renderer_set_lanes", "rth_renderer_set_builtins", "rth_renderer_builtins",
     "rth_build_blas_lbvh", "rth_build_bvh2_lbvh", "rth_lbvh_stats", "rth_set_primitives", "rth_refit",
-    "rth_build_blas_sah_gpu", "rth_build_bvh2_sah", "rth_rebuild", "rth_blas_ranges"]
+    "rth_build_blas_sah_gpu", "rth_build_bvh2_sah", "rth_build_blas_sbvh_gpu", "rth_build_bvh2_sbvh", "rth_rebuild", "rth_blas_ranges"]
 
 _dev = None
 _host = None
@@ -201,6 +203,8 @@ def _bind_device(lib):
         lib.rt_build_bvh2.argtypes = [i32, vp, vp, i32, i32, i32, C.c_uint32, C.c_uint32, vp, i32, C.POINTER(i32), vp, vp]
         lib.rt_build_bvh2_sah.argtypes = [i32, vp, i32, i32, i32, C.c_uint32, C.c_uint32, vp, i32, C.POINTER(i32), vp, vp]
         lib.rt_debug_sah_phases.argtypes = [vp]
+        lib.rt_build_bvh2_sbvh.argtypes = [i32, C.c_float, vp, i32, i32, i32, C.c_uint32, C.c_uint32, vp, i32, C.POINTER(i32), vp, i32, C.POINTER(i32), vp]
+        lib.rt_debug_sbvh_phases.argtypes = [vp]
         lib.rt_update_scene.argtypes = [vp, vp, i32, i32, vp, i32, vp]
         lib.rt_group_update_scene.argtypes = [vp, vp, i32, i32, vp, i32, vp]
         lib.rt_debug_get_scene_array.argtypes = [vp, i32, vp, i64, C.POINTER(i64)]
@@ -255,6 +259,9 @@ def host_lib():
         lib.rth_build_blas_sah_gpu.argtypes = [vp, i32, i32]
         lib.rth_build_bvh2_sah.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, vp, C.c_int32,
                                            C.POINTER(C.c_int32), vp, vp]
+        lib.rth_build_blas_sbvh_gpu.argtypes = [vp, i32, C.c_float, i32]
+        lib.rth_build_bvh2_sbvh.argtypes = [C.c_float, vp, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, vp, C.c_int32,
+                                            C.POINTER(C.c_int32), vp, C.c_int32, C.POINTER(C.c_int32), vp]
         lib.rth_set_primitives.argtypes = [vp, i32, i32, vp]
         lib.rth_refit.argtypes = [vp]
         lib.rth_rebuild.argtypes = [vp, i32, vp]

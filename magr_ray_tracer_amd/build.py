@@ -45,12 +45,13 @@ def build_device(force=False):
     refit = os.path.join(PKG, "csrc", "refit.hip")    # rt_update_scene: BLAS refit, derived records and TLAS rebuild on the GPU
     sah = os.path.join(PKG, "csrc", "sah.hip")        # rt_build_bvh2_sah: the default SAH BLAS built on the GPU
     rebuild = os.path.join(PKG, "csrc", "rebuild.hip")  # rt_rebuild_scene: what upload derives from a BVH2, derived on the GPU
-    deps = [src, lbvh, refit, sah, rebuild, *REBUILD_HEADERS, os.path.join(PKG, "csrc", "rt355_kernels.h"), os.path.join(PKG, "csrc", "lbvh_common.h"),
+    sbvh = os.path.join(PKG, "csrc", "sbvh.hip")      # rt_build_bvh2_sbvh: SBVH BLAS trees (spatial splits) built on the GPU
+    deps = [src, lbvh, refit, sah, rebuild, sbvh, os.path.join(PKG, "csrc", "sbvh_common.h"), *REBUILD_HEADERS, os.path.join(PKG, "csrc", "rt355_kernels.h"), os.path.join(PKG, "csrc", "lbvh_common.h"),
             os.path.join(PKG, "csrc", "refit_common.h"), os.path.join(PKG, "csrc", "sah_common.h"), os.path.join(ROOT, "include", "rt355.h"),
             os.path.join(ROOT, "include", "rt355_types.h")]
     out = os.path.join(PKG, "librt355.so")
     if force or _stale(out, deps):
-        _run([HIPCC] + DEVICE_FLAGS + [src, lbvh, refit, sah, rebuild, "-o", out])
+        _run([HIPCC] + DEVICE_FLAGS + [src, lbvh, refit, sah, rebuild, sbvh, "-o", out])
     return out
 
 
@@ -64,7 +65,8 @@ def build_device_refb(force=False):
     refit = os.path.join(PKG, "csrc", "refit.hip")
     sah = os.path.join(PKG, "csrc", "sah.hip")
     rebuild = os.path.join(PKG, "csrc", "rebuild.hip")
-    deps = [src, lbvh, refit, sah, rebuild, *REBUILD_HEADERS, os.path.join(PKG, "csrc", "rt355_kernels.h"), os.path.join(PKG, "csrc", "lbvh_common.h"),
+    sbvh = os.path.join(PKG, "csrc", "sbvh.hip")
+    deps = [src, lbvh, refit, sah, rebuild, sbvh, os.path.join(PKG, "csrc", "sbvh_common.h"), *REBUILD_HEADERS, os.path.join(PKG, "csrc", "rt355_kernels.h"), os.path.join(PKG, "csrc", "lbvh_common.h"),
             os.path.join(PKG, "csrc", "refit_common.h"), os.path.join(PKG, "csrc", "sah_common.h"), os.path.join(ROOT, "include", "rt355.h"),
             os.path.join(ROOT, "include", "rt355_types.h")]
     out = os.path.join(PKG, "librt355_refb.so")
@@ -72,7 +74,7 @@ def build_device_refb(force=False):
         # -Bsymbolic: this library defines the same global symbols as librt355.so (C-ABI entry points, the kernels' host stubs).  Loaded
         # into a process that already holds librt355.so, its own references would otherwise bind to THAT library's definitions - and
         # launch the other build's kernels
-        _run([HIPCC] + DEVICE_FLAGS + ["-DRT355_REF_BUILTINS", "-Wl,-Bsymbolic", src, lbvh, refit, sah, rebuild, "-o", out])
+        _run([HIPCC] + DEVICE_FLAGS + ["-DRT355_REF_BUILTINS", "-Wl,-Bsymbolic", src, lbvh, refit, sah, rebuild, sbvh, "-o", out])
     return out
 
 
@@ -80,7 +82,7 @@ def build_host(force=False):
     hdir = os.path.join(PKG, "host")
     srcs = [os.path.join(hdir, f) for f in sorted(os.listdir(hdir)) if f.endswith(".cpp")]
     deps = srcs + [os.path.join(hdir, "rt_host.h"), os.path.join(PKG, "csrc", "lbvh_common.h"), os.path.join(PKG, "csrc", "refit_common.h"),
-                   os.path.join(PKG, "csrc", "sah_common.h"), os.path.join(PKG, "csrc", "rebuild_common.h"),
+                   os.path.join(PKG, "csrc", "sah_common.h"), os.path.join(PKG, "csrc", "sbvh_common.h"), os.path.join(PKG, "csrc", "rebuild_common.h"),
                    os.path.join(ROOT, "include", "rt355.h"),
                    os.path.join(ROOT, "include", "rt355_host.h"), os.path.join(ROOT, "include", "rt355_types.h")]
     out = os.path.join(PKG, "librt355_host.so")

@@ -1,4 +1,4 @@
-// build_cores.h — the two GPU BLAS builders as cores that work on device-resident arrays (sah.hip, lbvh.hip).  rt_build_bvh2_sah and
+// build_cores.h — the GPU BLAS builders as cores that work on device-resident arrays (sah.hip, lbvh.hip, sbvh.hip).  rt_build_bvh2_sah and
 // rt_build_bvh2 wrap them (allocate, upload, core, download); rt_rebuild_scene (rt355.hip) runs them BLAS by BLAS straight into a
 // scene's device arrays.
 //
@@ -36,4 +36,25 @@ const char* check_args(const RtBuildOptions* opts, int32_t nPrims, int32_t first
 int work_bytes(const char* who, uint32_t n, hipStream_t stream, size_t* bytes);
 int build(const char* who, hipStream_t stream, void* work, const lbvh::Params& P, const RtPrimitive* dPrims, uint32_t n, uint32_t first,
           uint32_t nodeBase, uint32_t idxBase, RtBVHNode2* dNodes, uint32_t* dIdx, hipEvent_t evBegin, hipEvent_t evEnd, Built* out);
+}
+
+// The SBVH builder (sbvh.hip, rules in sbvh_common.h).  A spatial split duplicates refs, so the size of the tree is known only after
+// it is built: build() leaves the numbered tree on the device (its own allocations, grown level by level; RT_E_NOMEM when one fails)
+// and reports the sizes, emit() then writes the records and primIdx into arrays of built.nodes / built.nIdx entries.  This is the
+// shape an in-place rebuild with an SBVH builder needs (size, then place); rt_rebuild_scene does not use it yet.  The caller has
+// checked the arguments (sbvh::check_args) and set the device; *tree is set whenever build() got that far and is destroyed by the
+// caller, after a failure too.  The stream is idle when either returns.
+struct SbvhBuilt {
+    uint32_t nodes, leaves, nIdx, depth;                     // records, leaves, primIdx entries, BVH2::Depth
+    uint32_t spatialSplits, primsClipped, forcedLeaves;      // as BVH2::stat_* count them
+    uint32_t levels, peakRefs;                               // level passes; most refs alive in one level
+    float cost;                                              // BVH2::TotalCost
+    float ms[3];                                             // wall-clock of the primitive pass, the level passes, the numbering
+};
+namespace sbvhdev {
+struct Tree;
+int build(const char* who, hipStream_t stream, float alpha, const RtPrimitive* dPrims, uint32_t n, uint32_t first, uint32_t nodeBase,
+          uint32_t idxBase, hipEvent_t evBegin, hipEvent_t evEnd, Tree** tree, SbvhBuilt* out);
+int emit(const char* who, hipStream_t stream, Tree* tree, RtBVHNode2* dNodes, uint32_t* dIdx);
+void destroy(Tree* tree);
 }

@@ -17,6 +17,7 @@
 #include <stdexcept>
 #include <cstring>
 #include <future>
+#include <memory>
 #include <mutex>
 #include <utility>
 #include "rt_host.h"
@@ -130,7 +131,25 @@ void BVH2::UpdateNodeBounds(uint32_t nodeIdx, const Refs& refs)
     }
 }
 
+// BuildBLAS proper.  It throws where a spatial bin index is undefined (FindBestSpatialSplitPlane); the scene is then put back as it was
+// before the call: node, primIdx and instance arrays, root index, statistics.
 void BVH2::BuildBLAS(bool statistics, int startIdx)
+{
+    const size_t nNodes = bvhNodes.size(), nIdx = primIdx.size(), nBlas = blasNodes.size();
+    const uint32_t root = rootNodeIdx_, used = nodesUsed_;
+    const uint32_t su[6] = { stat_depth, stat_node_count, stat_spatial_splits, stat_prims_clipped, stat_prim_count, stat_forced_leaves };
+    const float sf[2] = { stat_sah_cost, stat_build_time };
+    try {
+        BuildBLASUnguarded(statistics, startIdx);
+    } catch (...) {
+        bvhNodes.resize(nNodes); primIdx.resize(nIdx); blasNodes.resize(nBlas);
+        rootNodeIdx_ = root; nodesUsed_ = used;
+        stat_depth = su[0]; stat_node_count = su[1]; stat_spatial_splits = su[2]; stat_prims_clipped = su[3]; stat_prim_count = su[4];
+        stat_forced_leaves = su[5]; stat_sah_cost = sf[0]; stat_build_time = sf[1];
+        throw;
+    }
+}
+void BVH2::BuildBLASUnguarded(bool statistics, int startIdx)
 {
     auto t0 = std::chrono::steady_clock::now();
     RtBVHInstance inst;
@@ -228,7 +247,8 @@ struct BVH2::TNode {
 static std::mutex g_statMutex;
 BVH2::TNode* BVH2::BuildSubtree(Refs refs, float rootArea, int depth, int& budget)
 {
-    TNode* n = new TNode();
+    std::unique_ptr<TNode> owner(new TNode());   // (FindBestSpatialSplitPlane may throw, here or in a subtree)
+    TNode* n = owner.get();
     n->bmin[0] = n->bmin[1] = n->bmin[2] = RT_REALLYFAR; n->bmin[3] = 0;
     n->bmax[0] = n->bmax[1] = n->bmax[2] = -RT_REALLYFAR; n->bmax[3] = 0;
     for (const BVHPrimData& r : refs) {
@@ -242,7 +262,7 @@ BVH2::TNode* BVH2::BuildSubtree(Refs refs, float rootArea, int depth, int& budge
     float ex = n->bmax[0] - n->bmin[0], ey = n->bmax[1] - n->bmin[1], ez = n->bmax[2] - n->bmin[2];
     float leafCost = (float)(uint32_t)refs.size() * (ex * ey + ey * ez + ez * ex);
     if (overlap / rootArea > alpha) spatialCost = FindBestSpatialSplitPlane(spatialAxis, spatialPos, refs);
-    if (refs.size() <= RT_MIN_LEAF_PRIMS || (leafCost < objectCost && leafCost < spatialCost)) { n->refs = std::move(refs); return n; }
+    if (refs.size() <= RT_MIN_LEAF_PRIMS || (leafCost < objectCost && leafCost < spatialCost)) { n->refs = std::move(refs); return owner.release(); }
     Refs left, right;
     uint32_t clipped = 0;
     bool spatial = !(objectCost < spatialCost);
@@ -255,7 +275,7 @@ BVH2::TNode* BVH2::BuildSubtree(Refs refs, float rootArea, int depth, int& budge
     if (left.empty() || right.empty() || (left.size() >= refs.size() && right.size() >= refs.size())) {
         { std::lock_guard<std::mutex> lock(g_statMutex); stat_forced_leaves++; if (spatial) { /* the sequential build counts the split before it is discarded */ stat_spatial_splits++; } }
         n->refs = std::move(refs);
-        return n;
+        return owner.release();
     }
     if (spatial) { std::lock_guard<std::mutex> lock(g_statMutex); stat_spatial_splits++; }
     refs.clear(); refs.shrink_to_fit();
@@ -270,7 +290,7 @@ BVH2::TNode* BVH2::BuildSubtree(Refs refs, float rootArea, int depth, int& budge
         n->left = BuildSubtree(std::move(left), rootArea, depth + 1, budget);
         n->right = BuildSubtree(std::move(right), rootArea, depth + 1, budget);
     }
-    return n;
+    return owner.release();
 }
 void BVH2::FlattenLIFO(uint32_t root, TNode* tree)
 {
@@ -437,6 +457,11 @@ float BVH2::FindBestSpatialSplitPlane(int& axis, float& splitPos, const Refs& re
         }
         for (const BVHPrimData& r : refs) {
             const Aabb& box = r.box;
+            // The rule of csrc/sbvh_common.h (spatial_index): an index that is not finite, <= -1 or >= 2^31 has no defined conversion or
+            // indexes outside bins[] (a ref with an empty or inverted box).  The GPU builder refuses the same inputs.
+            const float fl = scale * (box.bmin[a] - bmin), fr = scale * (box.bmax[a] - bmin);
+            if (!std::isfinite(fl) || fl <= -1.0f || fl >= 2147483648.0f || !std::isfinite(fr) || fr <= -1.0f || fr >= 2147483648.0f)
+                throw std::runtime_error("BuildBLAS: a spatial bin index that is not finite, <= -1 or >= 2^31 (an inverted or empty ref box among the refs)");
             int lb = (int)(scale * (box.bmin[a] - bmin)); if (lb > NB - 1) lb = NB - 1;
             int rb = (int)(scale * (box.bmax[a] - bmin)); if (rb > NB - 1) rb = NB - 1;
             while (box.bmin[a] <= bins[lb].left && lb > 0) lb--;

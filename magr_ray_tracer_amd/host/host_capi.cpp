@@ -103,6 +103,21 @@ int rth_build_bvh2_sah(const RtPrimitive* prims, int32_t nPrims, int32_t first, 
     if (rc != RT_OK) g_herr = err;
     return rc;
 }
+int rth_build_blas_sbvh_gpu(RthScene* s, int startIdx, float alpha, int device)
+{
+    if (!s || startIdx < 0 || startIdx >= (int)s->scene.primitives.size()) { g_herr = "rth_build_blas_sbvh_gpu: bad start index"; return RT_E_INVALID; }
+    try { s->scene.bvh2->BuildBLASSBVHGPU(startIdx, alpha, device); return 0; }
+    catch (const LbvhError& e) { g_herr = e.what(); return e.code; }
+    catch (const std::exception& e) { g_herr = e.what(); return RT_E_NOMEM; }
+}
+int rth_build_bvh2_sbvh(float alpha, const RtPrimitive* prims, int32_t nPrims, int32_t first, int32_t count, uint32_t nodeBase, uint32_t idxBase,
+                        RtBVHNode2* nodes, int32_t nodeCap, int32_t* nNodes, uint32_t* primIdx, int32_t idxCap, int32_t* nIdx, RtSbvhStats* stats)
+{
+    std::string err;
+    const int rc = SbvhBuildHost(alpha, prims, nPrims, first, count, nodeBase, idxBase, nodes, nodeCap, nNodes, primIdx, idxCap, nIdx, stats, err);
+    if (rc != RT_OK) g_herr = err;
+    return rc;
+}
 int rth_set_build_threads(RthScene* s, int threads) { if (!s) return -1; s->scene.bvh2->buildThreads = threads < 1 ? 1 : threads; return 0; }
 int rth_build_bvh4(RthScene* s) { GUARD(s->scene.BuildBVH4()) }
 // BVH4::Convert + Collapse (bvh.cpp:695-787) on a caller-provided BVH2 node array with ONE BLAS rooted at node 0: how the tests feed

@@ -72,6 +72,10 @@ public:
     // BuildBLAS(alpha = 1) appends.  device >= 0: rt_build_bvh2_sah on that GPU; -1: the host restatement.  Throws LbvhError and
     // leaves everything unchanged when the build is refused.
     void     BuildBLASSAHGPU(int startIdx, int device);
+    // The GPU build of BuildBLAS for any alpha in [0, 1], spatial splits included (csrc/sbvh_common.h): appends exactly what BuildBLAS
+    // appends with bvh2->alpha = alpha, statistics included.  device >= 0: rt_build_bvh2_sbvh on that GPU; -1: the host restatement.
+    // Throws LbvhError and leaves everything unchanged when the build is refused.
+    void     BuildBLASSBVHGPU(int startIdx, float alpha, int device);
     // Discards the trees and builds every BLAS again over the primitive range it covers, in increasing order of the ranges, with the
     // host restatement of rt_rebuild_scene's builder (RT_REBUILD_SAH / RT_REBUILD_LBVH, opt for the latter); instance transforms stay,
     // bvhIdx follows.  Throws LbvhError and leaves everything unchanged when refused (rebuild_host.cpp).
@@ -88,6 +92,7 @@ public:
     std::vector<RtBVHInstance>& blasNodes;
 private:
     using Refs = std::vector<BVHPrimData>;
+    void  BuildBLASUnguarded(bool statistics, int startIdx);
     void  BuildBVH(uint32_t root, Refs data);
     struct TNode;                                       // temporary pointer tree of the parallel build
     TNode* BuildSubtree(Refs refs, float rootArea, int depth, int& budget);
@@ -114,6 +119,11 @@ int LbvhBuildHost(const RtBuildOptions* opt, const RtPrimitive* prims, int32_t n
 // The GPU SAH build's sequential host restatement (rth_build_bvh2_sah); err receives the message of a refused call.
 int SahBuildHost(const RtPrimitive* prims, int32_t nPrims, int32_t first, int32_t count, uint32_t nodeBase, uint32_t idxBase,
                  RtBVHNode2* nodes, int32_t nodeCap, int32_t* nNodes, uint32_t* primIdx, RtBuildStats* stats, std::string& err);
+
+// The GPU SBVH build's sequential host restatement (rth_build_bvh2_sbvh); err receives the message of a refused call.
+int SbvhBuildHost(float alpha, const RtPrimitive* prims, int32_t nPrims, int32_t first, int32_t count, uint32_t nodeBase, uint32_t idxBase,
+                  RtBVHNode2* nodes, int32_t nodeCap, int32_t* nNodes, uint32_t* primIdx, int32_t idxCap, int32_t* nIdx, RtSbvhStats* stats,
+                  std::string& err);
 
 // In-place updates (refit_host.cpp, the host restatement of rt_update_scene): replace primitives keeping objType / matIdx, then refit
 // every BLAS by the rules of csrc/refit_common.h; err receives why a call is refused (RT_E_* returned, nothing changed).

@@ -131,7 +131,10 @@ class Scene:
         builder="lbvh": the linear BVH builder (rt_build_bvh2) on HIP device `device`, or its host restatement when device is None
         (identical arrays); lbvh_options: max_leaf, cost_traverse, cost_intersect.  It has no spatial splits: alpha must stay 1.
         builder="sah_gpu": builder="sah" with alpha 1, built on HIP device `device` (rt_build_bvh2_sah) or by its host restatement
-        when device is None; the arrays equal builder="sah"'s byte for byte.  alpha and threads must stay 1."""
+        when device is None; the arrays equal builder="sah"'s byte for byte.  alpha and threads must stay 1.
+        builder="sbvh_gpu": builder="sah" with any alpha in [0, 1] (spatial splits), built on HIP device `device`
+        (rt_build_bvh2_sbvh) or by its host restatement when device is None; arrays and statistics equal builder="sah"'s with that
+        alpha byte for byte.  threads must stay 1."""
         if builder == "sah":
             if lbvh_options:
                 raise ValueError(f"options {sorted(lbvh_options)} apply to builder='lbvh' only")
@@ -150,8 +153,14 @@ class Scene:
             if threads != 1:
                 raise ValueError("builder='sah_gpu' takes no host threads: threads must be 1")
             self._chk(self._lib.rth_build_blas_sah_gpu(self._h, int(startIdx), -1 if device is None else int(device)))
+        elif builder == "sbvh_gpu":
+            if lbvh_options:
+                raise ValueError(f"options {sorted(lbvh_options)} apply to builder='lbvh' only")
+            if threads != 1:
+                raise ValueError("builder='sbvh_gpu' takes no host threads: threads must be 1")
+            self._chk(self._lib.rth_build_blas_sbvh_gpu(self._h, int(startIdx), float(alpha), -1 if device is None else int(device)))
         else:
-            raise ValueError(f"unknown builder {builder!r} (expected 'sah', 'lbvh' or 'sah_gpu')")
+            raise ValueError(f"unknown builder {builder!r} (expected 'sah', 'lbvh', 'sah_gpu' or 'sbvh_gpu')")
 
     def lbvh_stats(self):
         """Statistics of the last builder='lbvh' BuildBLAS (RtBuildStats)."""
@@ -324,6 +333,47 @@ def build_sah_gpu(prims, first=0, count=None, device=None, node_base=0, idx_base
     if rc != 0:
         raise BuildError(rc, msg().decode())
     return nodes[:written.value].copy(), idx[:n].copy(), _stats_dict(st)
+
+
+def _sbvh_stats_dict(st):
+    return {k: (float(st[k]) if k in ("sah_cost", "device_ms", "wall_ms") else int(st[k])) for k in _lib.SbvhStats.names}
+
+
+def build_sbvh_gpu(prims, alpha, first=0, count=None, device=None, node_base=0, idx_base=0, nodes=None, idx=None):
+    """BVH2::BuildBLAS with bvh2->alpha = alpha (spatial splits) on a primitive array: rt_build_bvh2_sbvh on HIP device `device`, or
+    its host restatement (rth_build_bvh2_sbvh) when device is None.  Returns (nodes, primIdx, stats); raises BuildError (with .code,
+    an RT_E_* value, and .needed = (nodes, primIdx entries) after a capacity refusal) when the call is refused.  Without nodes / idx
+    the call starts with 2 * count - 1 nodes and count indices and, told that the tree is larger, calls once more with the sizes it
+    was given.  nodes / idx: the caller's arrays to write into; their lengths are the capacities, and there is no second call."""
+    p = np.ascontiguousarray(prims, dtype=_lib.Primitive)
+    n = len(p) - int(first) if count is None else int(count)
+    own = nodes is None and idx is None
+    nodes = np.zeros(max(2 * n - 1, 1), _lib.BVHNode2) if nodes is None else nodes
+    idx = np.zeros(max(n, 1), np.uint32) if idx is None else idx
+    if nodes.dtype != _lib.BVHNode2 or idx.dtype != np.uint32:
+        raise ValueError("nodes / idx: BVHNode2 and uint32 arrays expected")
+    st = np.zeros((), _lib.SbvhStats)
+    for attempt in (0, 1):
+        nn, ni = C.c_int32(0), C.c_int32(0)
+        if device is None:
+            L = _lib.host_lib()
+            rc = L.rth_build_bvh2_sbvh(float(alpha), _lib.ptr(p), len(p), int(first), n, int(node_base), int(idx_base), _lib.ptr(nodes), len(nodes),
+                                       C.byref(nn), _lib.ptr(idx), len(idx), C.byref(ni), _lib.ptr(st))
+            msg = L.rth_last_error
+        else:
+            L = _lib.device_lib()
+            rc = L.rt_build_bvh2_sbvh(int(device), float(alpha), _lib.ptr(p), len(p), int(first), n, int(node_base), int(idx_base), _lib.ptr(nodes),
+                                      len(nodes), C.byref(nn), _lib.ptr(idx), len(idx), C.byref(ni), _lib.ptr(st))
+            msg = L.rt_last_error
+        if rc == 0:
+            return nodes[:nn.value].copy(), idx[:ni.value].copy(), _sbvh_stats_dict(st)
+        text = msg().decode()
+        if own and attempt == 0 and rc == _lib.RT_E_INVALID and "capacity" in text:
+            nodes, idx = np.zeros(nn.value, _lib.BVHNode2), np.zeros(ni.value, np.uint32)
+            continue
+        err = BuildError(rc, text)
+        err.needed = (nn.value, ni.value)
+        raise err
 
 
 def make_camera(width, height, origin, forward, fov=110.0, aperture=0.1, focalLength=1.0, type=0):

@@ -96,7 +96,8 @@ def sponza_class(detail=1.0, alpha=1.0, builder="sah", device=0):
     fluted columns carrying round arches along both long sides, ribbed walls, six hanging drapes.
     detail=1.0 gives ~262k triangles (Crytek Sponza has 262,267); the generator is RNG-free.
     builder="lbvh": the linear BVH builder on HIP device `device` (None: its host restatement) instead of the SAH builder;
-    builder="sah_gpu" (alpha 1): the SAH builder's tree built on HIP device `device` (None: its host restatement)."""
+    builder="sah_gpu" (alpha 1): the SAH builder's tree built on HIP device `device` (None: its host restatement);
+    builder="sbvh_gpu" (any alpha): the SAH / SBVH builder's tree, spatial splits included, built on `device` (None: host restatement)."""
     s = Scene()
     _std_materials(s)
     d = float(detail)
@@ -276,7 +277,8 @@ def config5_scene(alpha=0.0, decimate=1, builder="sah", device=0):
     alpha (0 = full spatial splits), glass on the terrarium dome.  Geometry: magr_ray_tracer_amd/assets/*.npz (converted
     from the glTF files that ship with the reference; CC-BY-4.0, see assets/ATTRIBUTION.md).
     builder="lbvh" (alpha is then ignored): both BLAS by the linear BVH builder on HIP device `device` (None: host restatement).
-    builder="sah_gpu" (alpha must be 1): both BLAS by the SAH builder's GPU build on `device` (None: host restatement)."""
+    builder="sah_gpu" (alpha must be 1): both BLAS by the SAH builder's GPU build on `device` (None: host restatement).
+    builder="sbvh_gpu": both BLAS with SBVH alpha by the GPU SBVH build on `device` (None: host restatement); same arrays as "sah"."""
     import os
     from . import gltf
     adir = os.path.join(os.path.dirname(os.path.abspath(__file__)), "assets")
@@ -301,6 +303,8 @@ def config5_scene(alpha=0.0, decimate=1, builder="sah", device=0):
     if builder == "sah_gpu" and alpha != 1.0:
         raise ValueError("builder='sah_gpu' has no spatial splits: alpha must be 1")
     blas = dict(builder=builder, device=device) if builder in ("lbvh", "sah_gpu") else dict(alpha=alpha)
+    if builder == "sbvh_gpu":
+        blas = dict(alpha=alpha, builder=builder, device=device)
     s.BuildBLAS(0, **blas)
     start = s.num_prims
     place("terrarium_bot.npz", 2.4, (1.7, 0.0, 0.0), {"glass": "white-glass", "ground": "sand", "inside": "sand", "pipes": "red"}, "white")
