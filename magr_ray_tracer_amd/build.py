@@ -24,7 +24,15 @@ HOST_FLAGS = ["-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wa
 ORACLE_FLAGS = ["-O2", "-std=c11", "-fPIC", "-shared", "-ffp-contract=off", "-mfma", "-fopenmp", "-Wall", "-D_GNU_SOURCE"]
 
 
-REBUILD_HEADERS = [os.path.join(PKG, "csrc", h) for h in ("rebuild_common.h", "rebuild_dev.h", "build_cores.h")]
+CSRC = os.path.join(PKG, "csrc")
+# The device libraries' translation units: the C-ABI and traversal kernels, then rt_build_bvh2 (linear BVH builder), rt_update_scene
+# (refit), rt_build_bvh2_sah (SAH builder), rt_rebuild_scene (what upload derives from a BVH2) and rt_build_bvh2_sbvh (SBVH builder)
+DEVICE_SRCS = [os.path.join(CSRC, f) for f in ("rt355.hip", "lbvh.hip", "refit.hip", "sah.hip", "rebuild.hip", "sbvh.hip")]
+
+
+def _headers(*dirs):
+    """Every header of the directories: a library is rebuilt when any header it could include has changed."""
+    return [os.path.join(d, f) for d in dirs for f in sorted(os.listdir(d)) if f.endswith(".h")]
 
 
 def _stale(out, srcs):
@@ -40,18 +48,9 @@ def _run(cmd):
 
 
 def build_device(force=False):
-    src = os.path.join(PKG, "csrc", "rt355.hip")
-    lbvh = os.path.join(PKG, "csrc", "lbvh.hip")      # rt_build_bvh2: the GPU linear BVH builder
-    refit = os.path.join(PKG, "csrc", "refit.hip")    # rt_update_scene: BLAS refit, derived records and TLAS rebuild on the GPU
-    sah = os.path.join(PKG, "csrc", "sah.hip")        # rt_build_bvh2_sah: the default SAH BLAS built on the GPU
-    rebuild = os.path.join(PKG, "csrc", "rebuild.hip")  # rt_rebuild_scene: what upload derives from a BVH2, derived on the GPU
-    sbvh = os.path.join(PKG, "csrc", "sbvh.hip")      # rt_build_bvh2_sbvh: SBVH BLAS trees (spatial splits) built on the GPU
-    deps = [src, lbvh, refit, sah, rebuild, sbvh, os.path.join(PKG, "csrc", "sbvh_common.h"), *REBUILD_HEADERS, os.path.join(PKG, "csrc", "rt355_kernels.h"), os.path.join(PKG, "csrc", "lbvh_common.h"),
-            os.path.join(PKG, "csrc", "refit_common.h"), os.path.join(PKG, "csrc", "sah_common.h"), os.path.join(ROOT, "include", "rt355.h"),
-            os.path.join(ROOT, "include", "rt355_types.h")]
     out = os.path.join(PKG, "librt355.so")
-    if force or _stale(out, deps):
-        _run([HIPCC] + DEVICE_FLAGS + [src, lbvh, refit, sah, rebuild, sbvh, "-o", out])
+    if force or _stale(out, DEVICE_SRCS + _headers(CSRC, os.path.join(ROOT, "include"))):
+        _run([HIPCC] + DEVICE_FLAGS + DEVICE_SRCS + ["-o", out])
     return out
 
 
@@ -60,31 +59,19 @@ def build_device_refb(force=False):
     (normalize / length / exp / sin / cos / acospi / atan2pi as ROCm's OpenCL library evaluates them for the reference's kernels,
     rt355_kernels.h) and changes nothing else: both sets of kernels are in both libraries.  A second build for the tests to compare the
     shipped library's run-time mode with (tests/test_gpu_reference.py, tests/test_gpu_builtins.py); the shipped library is librt355.so."""
-    src = os.path.join(PKG, "csrc", "rt355.hip")
-    lbvh = os.path.join(PKG, "csrc", "lbvh.hip")      # same entry points as librt355.so (the ctypes binding declares them all)
-    refit = os.path.join(PKG, "csrc", "refit.hip")
-    sah = os.path.join(PKG, "csrc", "sah.hip")
-    rebuild = os.path.join(PKG, "csrc", "rebuild.hip")
-    sbvh = os.path.join(PKG, "csrc", "sbvh.hip")
-    deps = [src, lbvh, refit, sah, rebuild, sbvh, os.path.join(PKG, "csrc", "sbvh_common.h"), *REBUILD_HEADERS, os.path.join(PKG, "csrc", "rt355_kernels.h"), os.path.join(PKG, "csrc", "lbvh_common.h"),
-            os.path.join(PKG, "csrc", "refit_common.h"), os.path.join(PKG, "csrc", "sah_common.h"), os.path.join(ROOT, "include", "rt355.h"),
-            os.path.join(ROOT, "include", "rt355_types.h")]
     out = os.path.join(PKG, "librt355_refb.so")
-    if force or _stale(out, deps):
+    if force or _stale(out, DEVICE_SRCS + _headers(CSRC, os.path.join(ROOT, "include"))):
         # -Bsymbolic: this library defines the same global symbols as librt355.so (C-ABI entry points, the kernels' host stubs).  Loaded
         # into a process that already holds librt355.so, its own references would otherwise bind to THAT library's definitions - and
         # launch the other build's kernels
-        _run([HIPCC] + DEVICE_FLAGS + ["-DRT355_REF_BUILTINS", "-Wl,-Bsymbolic", src, lbvh, refit, sah, rebuild, sbvh, "-o", out])
+        _run([HIPCC] + DEVICE_FLAGS + ["-DRT355_REF_BUILTINS", "-Wl,-Bsymbolic"] + DEVICE_SRCS + ["-o", out])
     return out
 
 
 def build_host(force=False):
     hdir = os.path.join(PKG, "host")
     srcs = [os.path.join(hdir, f) for f in sorted(os.listdir(hdir)) if f.endswith(".cpp")]
-    deps = srcs + [os.path.join(hdir, "rt_host.h"), os.path.join(PKG, "csrc", "lbvh_common.h"), os.path.join(PKG, "csrc", "refit_common.h"),
-                   os.path.join(PKG, "csrc", "sah_common.h"), os.path.join(PKG, "csrc", "sbvh_common.h"), os.path.join(PKG, "csrc", "rebuild_common.h"),
-                   os.path.join(ROOT, "include", "rt355.h"),
-                   os.path.join(ROOT, "include", "rt355_host.h"), os.path.join(ROOT, "include", "rt355_types.h")]
+    deps = srcs + _headers(hdir, CSRC, os.path.join(ROOT, "include"))
     out = os.path.join(PKG, "librt355_host.so")
     if force or _stale(out, deps):
         _run(["g++"] + HOST_FLAGS + srcs + ["-o", out, "-L" + PKG, "-lrt355", "-lz", "-Wl,-rpath,$ORIGIN"])

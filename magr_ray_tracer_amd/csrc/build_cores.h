@@ -1,6 +1,7 @@
 // build_cores.h — the GPU BLAS builders as cores that work on device-resident arrays (sah.hip, lbvh.hip, sbvh.hip).  rt_build_bvh2_sah and
 // rt_build_bvh2 wrap them (allocate, upload, core, download); rt_rebuild_scene (rt355.hip) runs them BLAS by BLAS straight into a
-// scene's device arrays.
+// scene's device arrays.  The driver side the three files share (error reporting, the per-call session, the wrappers' common tail)
+// is build_dev.h; the workgroup fold of the SAH and SBVH level kernels is fold_dev.h.
 //
 // A core builds the BLAS over dPrims[0, n) - the primitives [first, first + n) of the scene, `first` is added to the ids it writes to
 // dIdx[0, n) - with its root at node id nodeBase and its leaves indexing primIdx from idxBase; dNodes[0, 2n - 1) receives the records

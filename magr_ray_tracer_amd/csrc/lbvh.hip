@@ -11,16 +11,14 @@
 //   k_lbvh_emit      RtBVHNode2 records and primIdx
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
-#include <chrono>
-#include <cstdarg>
-#include <cstdio>
 #include "../../include/rt355.h"
 #include "lbvh_common.h"
-#include "build_cores.h"
+#include "build_dev.h"
 
 using namespace lbvh;
-
-int rt355_set_error(int code, const char* msg);   // rt355.hip: sets the text rt_last_error() returns
+using builddev::align_up;
+using builddev::build_fail;
+using builddev::grid;
 
 namespace {
 
@@ -115,31 +113,6 @@ __global__ void __launch_bounds__(kBlock) k_lbvh_emit(const NodeRec* rec, const 
     }
 }
 
-int lfail(int code, const char* fmt, ...)   // the message goes to rt_last_error()
-{
-    char buf[512];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-    return rt355_set_error(code, buf);
-}
-
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-
-// Everything one rt_build_bvh2 call allocates on the device; freed on every exit path.
-struct Work {
-    void* mem = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = { nullptr, nullptr };
-    int prevDevice = -1;                      // the caller's current device, restored on the way out
-    ~Work()
-    {
-        if (stream) (void)hipStreamSynchronize(stream);
-        if (mem) (void)hipFree(mem);
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        if (stream) (void)hipStreamDestroy(stream);
-        if (prevDevice >= 0) (void)hipSetDevice(prevDevice);
-    }
-};
-
 // The carved workspace of one build of n primitives (everything but the primitives and the output arrays):
 // [cb | tickets | parent] first (the words the memsets initialise), then the rest
 struct Carve { size_t oCb, oTick, oPar, oBox, oK0, oK1, oV0, oV1, oKids, oRec, oFlag, oRank, oSort, oScan, sortBytes, scanBytes, total; };
@@ -167,9 +140,6 @@ hipError_t carve_work(uint32_t n, hipStream_t s, Carve& c)
 
 } // namespace
 
-#define LCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
-    return lfail(RT_E_DEVICE, "%s: %s failed: %s", who, #expr, hipGetErrorString(e_)); } while (0)
-
 namespace lbvhdev {
 
 const char* check_args(const RtBuildOptions* opts, int32_t nPrims, int32_t first, int32_t count, uint32_t nodeBase, uint32_t idxBase, Params& P)
@@ -181,7 +151,7 @@ const char* check_args(const RtBuildOptions* opts, int32_t nPrims, int32_t first
 int work_bytes(const char* who, uint32_t n, hipStream_t s, size_t* bytes)
 {
     Carve c;
-    LCHK(carve_work(n, s, c));
+    BUILD_CHK(carve_work(n, s, c));
     *bytes = c.total;
     return RT_OK;
 }
@@ -194,7 +164,7 @@ int build(const char* who, hipStream_t stream, void* work, const Params& P, cons
     const int bIdx = index_bits(n), k = axis_bits(n), keyBits = 3 * k + bIdx;
     const size_t nI = nInt > 0 ? nInt : 1;
     Carve c;
-    LCHK(carve_work(n, stream, c));
+    BUILD_CHK(carve_work(n, stream, c));
     char* base = (char*)work;
     auto at = [&](size_t o) { return (void*)(base + o); };
     uint32_t* cb = (uint32_t*)at(c.oCb);
@@ -208,31 +178,31 @@ int build(const char* who, hipStream_t stream, void* work, const Params& P, cons
     uint32_t *flags = (uint32_t*)at(c.oFlag), *rank = (uint32_t*)at(c.oRank);
 
     const uint32_t cbInit[6] = { kKeyMinInit, kKeyMinInit, kKeyMinInit, kKeyMaxInit, kKeyMaxInit, kKeyMaxInit };
-    LCHK(hipMemcpyAsync(cb, cbInit, sizeof cbInit, hipMemcpyHostToDevice, stream));
-    LCHK(hipMemsetAsync(tickets, 0, nI * sizeof(uint32_t), stream));
-    LCHK(hipMemsetAsync(parent, 0xff, nTree * sizeof(uint32_t), stream));
-    LCHK(hipStreamSynchronize(stream));   // (rt_build_bvh2: nothing of the caller's host arrays is read after this point)
+    BUILD_CHK(hipMemcpyAsync(cb, cbInit, sizeof cbInit, hipMemcpyHostToDevice, stream));
+    BUILD_CHK(hipMemsetAsync(tickets, 0, nI * sizeof(uint32_t), stream));
+    BUILD_CHK(hipMemsetAsync(parent, 0xff, nTree * sizeof(uint32_t), stream));
+    BUILD_CHK(hipStreamSynchronize(stream));   // (rt_build_bvh2: nothing of the caller's host arrays is read after this point)
 
-    const dim3 blk(kBlock), gN((n + kBlock - 1) / kBlock), gI((nI + kBlock - 1) / kBlock);
-    if (evBegin) LCHK(hipEventRecord(evBegin, stream));
+    const dim3 blk(kBlock), gN = grid(n, kBlock), gI = grid((uint32_t)nI, kBlock);
+    if (evBegin) BUILD_CHK(hipEventRecord(evBegin, stream));
     hipLaunchKernelGGL(k_lbvh_boxes, gN, blk, 0, stream, dPrims, n, boxes, cb);
     hipLaunchKernelGGL(k_lbvh_keys, gN, blk, 0, stream, boxes, n, cb, k, bIdx, k0, v0);
-    LCHK(hipcub::DeviceRadixSort::SortPairs(at(c.oSort), c.sortBytes, k0, k1, v0, v1, (int)n, 0, keyBits, stream));
+    BUILD_CHK(hipcub::DeviceRadixSort::SortPairs(at(c.oSort), c.sortBytes, k0, k1, v0, v1, (int)n, 0, keyBits, stream));
     if (nInt > 0) hipLaunchKernelGGL(k_lbvh_karras, gI, blk, 0, stream, k1, n, kids, parent);
     hipLaunchKernelGGL(k_lbvh_bottomup, gN, blk, 0, stream, boxes, v1, n, rec, parent, kids, tickets, P);
     if (nInt > 0) {
         hipLaunchKernelGGL(k_lbvh_survive, gI, blk, 0, stream, rec, parent, nInt, P.maxLeaf, flags);
-        LCHK(hipcub::DeviceScan::ExclusiveSum(at(c.oScan), c.scanBytes, flags, rank, (int)nInt, stream));
+        BUILD_CHK(hipcub::DeviceScan::ExclusiveSum(at(c.oScan), c.scanBytes, flags, rank, (int)nInt, stream));
     }
     hipLaunchKernelGGL(k_lbvh_emit, gN, blk, 0, stream, rec, kids, flags, rank, v1, n, first, nodeBase, idxBase, dNodes, dIdx);
-    LCHK(hipGetLastError());
-    if (evEnd) LCHK(hipEventRecord(evEnd, stream));
+    BUILD_CHK(hipGetLastError());
+    if (evEnd) BUILD_CHK(hipEventRecord(evEnd, stream));
 
     NodeRec root;
-    LCHK(hipMemcpyAsync(&root, rec, sizeof root, hipMemcpyDeviceToHost, stream));
-    LCHK(hipStreamSynchronize(stream));
+    BUILD_CHK(hipMemcpyAsync(&root, rec, sizeof root, hipMemcpyDeviceToHost, stream));
+    BUILD_CHK(hipStreamSynchronize(stream));
     const uint32_t outNodes = 2 * root.leaves - 1;
-    if (root.leaves < 1 || outNodes > nTree) return lfail(RT_E_DEVICE, "%s: inconsistent device result (%u leaves)", who, root.leaves);
+    if (root.leaves < 1 || outNodes > nTree) return build_fail(RT_E_DEVICE, "%s: inconsistent device result (%u leaves)", who, root.leaves);
     *out = Built{};
     out->nodes = outNodes; out->leaves = root.leaves; out->depth = root.height; out->mortonBits = (uint32_t)k; out->cost = root.total;
     return RT_OK;
@@ -240,51 +210,21 @@ int build(const char* who, hipStream_t stream, void* work, const Params& P, cons
 
 } // namespace lbvhdev
 
-// The C-ABI entry: allocate, upload, build (lbvhdev::build), download.
+// The C-ABI entry: a session on the device, then builddev::build_flat around lbvhdev::build.
 extern "C" int rt_build_bvh2(int32_t device, const RtBuildOptions* opt, const RtPrimitive* prims, int32_t nPrims, int32_t first,
                              int32_t count, uint32_t nodeBase, uint32_t idxBase, RtBVHNode2* nodes, int32_t nodeCap, int32_t* nNodes,
                              uint32_t* primIdx, RtBuildStats* stats)
 {
     const char* who = "rt_build_bvh2";
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = builddev::Clock::now();
     Params P;
     if (const char* msg = check_args(opt, prims, nPrims, first, count, nodeBase, idxBase, nodes, nodeCap, nNodes, primIdx, P))
-        return lfail(RT_E_INVALID, "rt_build_bvh2: %s", msg);
-    int nDev = 0;
-    if (hipGetDeviceCount(&nDev) != hipSuccess || nDev <= 0) return lfail(RT_E_DEVICE, "rt_build_bvh2: no HIP device");
-    if (device < 0 || device >= nDev) return lfail(RT_E_INVALID, "rt_build_bvh2: device %d out of range (%d devices)", device, nDev);
-    Work w;
-    LCHK(hipGetDevice(&w.prevDevice));
-    LCHK(hipSetDevice(device));
-    LCHK(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
-    LCHK(hipEventCreate(&w.ev[0]));
-    LCHK(hipEventCreate(&w.ev[1]));
-
-    const uint32_t n = (uint32_t)count, nTree = 2 * n - 1;
-    size_t workBytes = 0;
-    if (const int rc = lbvhdev::work_bytes(who, n, w.stream, &workBytes)) return rc;
-    // one allocation: the core's workspace, then the primitives and the output arrays
-    const size_t oPrim = align_up(workBytes), oNodes = oPrim + align_up(n * sizeof(RtPrimitive)), oIdx = oNodes + align_up((size_t)nTree * sizeof(RtBVHNode2));
-    const size_t bytes = oIdx + align_up(n * 4ull);
-    if (hipMalloc(&w.mem, bytes) != hipSuccess) { w.mem = nullptr; return lfail(RT_E_NOMEM, "rt_build_bvh2: %zu bytes of device memory", bytes); }
-    RtPrimitive* dPrims = (RtPrimitive*)((char*)w.mem + oPrim);
-    RtBVHNode2* dNodes = (RtBVHNode2*)((char*)w.mem + oNodes);
-    uint32_t* dIdx = (uint32_t*)((char*)w.mem + oIdx);
-    LCHK(hipMemcpyAsync(dPrims, prims + first, n * sizeof(RtPrimitive), hipMemcpyHostToDevice, w.stream));
-
-    lbvhdev::Built b{};
-    if (const int rc = lbvhdev::build(who, w.stream, w.mem, P, dPrims, n, (uint32_t)first, nodeBase, idxBase, dNodes, dIdx, w.ev[0], w.ev[1], &b)) return rc;
-    LCHK(hipMemcpyAsync(nodes, dNodes, b.nodes * sizeof(RtBVHNode2), hipMemcpyDeviceToHost, w.stream));
-    LCHK(hipMemcpyAsync(primIdx, dIdx, n * sizeof(uint32_t), hipMemcpyDeviceToHost, w.stream));
-    LCHK(hipStreamSynchronize(w.stream));
-    *nNodes = (int32_t)b.nodes;
-    if (stats) {
-        float ms = 0;
-        LCHK(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
-        stats->nodes = (int32_t)b.nodes; stats->leaves = (int32_t)b.leaves; stats->depth = (int32_t)b.depth;
-        stats->morton_bits = (int32_t)b.mortonBits; stats->sah_cost = b.cost; stats->device_ms = ms;
-        stats->wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        stats->_reserved = 0;
-    }
-    return RT_OK;
+        return build_fail(RT_E_INVALID, "rt_build_bvh2: %s", msg);
+    builddev::Session w;
+    if (const int rc = builddev::open_session(who, device, w)) return rc;
+    const uint32_t n = (uint32_t)count;
+    return builddev::build_flat(who, w, t0, lbvhdev::work_bytes, prims, first, n, nodes, nNodes, primIdx, stats,
+        [&](void* work, const RtPrimitive* dPrims, RtBVHNode2* dNodes, uint32_t* dIdx, Built* b) {
+            return lbvhdev::build(who, w.stream, work, P, dPrims, n, (uint32_t)first, nodeBase, idxBase, dNodes, dIdx, w.ev[0], w.ev[1], b);
+        });
 }

@@ -15,18 +15,19 @@
 //   k_sah_emit      RtBVHNode2 records (level part and small subtrees); k_sah_emit_refs: primIdx
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
-#include <chrono>
-#include <cstdarg>
-#include <cstdio>
 #include <utility>
 #include <vector>
 #include "../../include/rt355.h"
 #include "sah_common.h"
-#include "build_cores.h"
+#include "build_dev.h"
+#include "fold_dev.h"
 
 using namespace sah;
-
-int rt355_set_error(int code, const char* msg);   // rt355.hip: sets the text rt_last_error() returns
+using namespace fold;
+using builddev::align_up;
+using builddev::build_fail;
+using builddev::grid;
+using builddev::ms_since;
 
 namespace {
 
@@ -38,11 +39,6 @@ constexpr int kKeys = 6 + kBinKeys;                 // 64-bit keys per open node
 
 // phases of the last build, for rt_debug_sah_phases: upload, level passes, numbering + emit, download (ms), levels
 float g_phases[5] = { 0, 0, 0, 0, 0 };
-
-__device__ inline void lds_min(uint64_t* p, uint64_t v) { __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ inline void lds_max(uint64_t* p, uint64_t v) { __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ inline void glb_min(uint64_t* p, uint64_t v) { __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline void glb_max(uint64_t* p, uint64_t v) { __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 __global__ void __launch_bounds__(kBlock) k_sah_prims(const RtPrimitive* prims, uint32_t n, Prim* P, uint32_t* cur, uint32_t* nid,
                                                       uint32_t* owner, uint32_t* status)
@@ -69,8 +65,8 @@ __global__ void __launch_bounds__(kBlock) k_sah_reduce(const Prim* P, const uint
 {
     __shared__ uint64_t smin[kSlots * 6], smax[kSlots * 6];
     __shared__ uint32_t sfirst;
-    for (int t = threadIdx.x; t < kSlots * 6; t += kBlock) { smin[t] = kKeyMinEmpty; smax[t] = kKeyMaxEmpty; }
-    if (threadIdx.x == 0) sfirst = kNone;
+    init_keys<kBlock, kSlots * 6>(smin, smax);
+    init_first(&sfirst);
     __syncthreads();
     const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
     const uint32_t br = open_rank(nid, bn, p, n);
@@ -88,10 +84,7 @@ __global__ void __launch_bounds__(kBlock) k_sah_reduce(const Prim* P, const uint
     }
     __syncthreads();
     if (sfirst == kNone) return;
-    for (int t = threadIdx.x; t < kSlots * 6; t += kBlock) {   // touched slots only: their ranks are < the level's open nodes
-        if (smin[t] != kKeyMinEmpty) glb_min(&kmin[sfirst * 6 + t], smin[t]);
-        if (smax[t] != kKeyMaxEmpty) glb_max(&kmax[sfirst * 6 + t], smax[t]);
-    }
+    flush_keys<kBlock, kSlots * 6>(smin, smax, kmin + sfirst * 6, kmax + sfirst * 6);   // their ranks are < the level's open nodes
 }
 
 __global__ void __launch_bounds__(kBlock) k_sah_bins(const Prim* P, const uint32_t* cur, const uint32_t* nid, const BNode* bn, uint32_t n,
@@ -101,9 +94,9 @@ __global__ void __launch_bounds__(kBlock) k_sah_bins(const Prim* P, const uint32
     __shared__ uint64_t smin[kSlots * kBinKeys], smax[kSlots * kBinKeys];
     __shared__ uint32_t scnt[kSlots * kCnt];
     __shared__ uint32_t sfirst;
-    for (int t = threadIdx.x; t < kSlots * kBinKeys; t += kBlock) { smin[t] = kKeyMinEmpty; smax[t] = kKeyMaxEmpty; }
-    for (int t = threadIdx.x; t < kSlots * kCnt; t += kBlock) scnt[t] = 0;
-    if (threadIdx.x == 0) sfirst = kNone;
+    init_keys<kBlock, kSlots * kBinKeys>(smin, smax);
+    init_counts<kBlock, kSlots * kCnt>(scnt);
+    init_first(&sfirst);
     __syncthreads();
     const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
     const uint32_t br = open_rank(nid, bn, p, n);
@@ -132,12 +125,8 @@ __global__ void __launch_bounds__(kBlock) k_sah_bins(const Prim* P, const uint32
     }
     __syncthreads();
     if (sfirst == kNone) return;
-    for (int t = threadIdx.x; t < kSlots * kBinKeys; t += kBlock) {
-        if (smin[t] != kKeyMinEmpty) glb_min(&bkmin[sfirst * kBinKeys + t], smin[t]);
-        if (smax[t] != kKeyMaxEmpty) glb_max(&bkmax[sfirst * kBinKeys + t], smax[t]);
-    }
-    for (int t = threadIdx.x; t < kSlots * kCnt; t += kBlock)
-        if (scnt[t]) atomicAdd(&bcnt[sfirst * kCnt + t], scnt[t]);
+    flush_keys<kBlock, kSlots * kBinKeys>(smin, smax, bkmin + sfirst * kBinKeys, bkmax + sfirst * kBinKeys);
+    flush_counts<kBlock, kSlots * kCnt>(scnt, bcnt + sfirst * kCnt);
 }
 
 __global__ void __launch_bounds__(kBlock) k_sah_decide(BNode* bn, uint32_t lb, uint32_t le, const uint64_t* kmin, const uint64_t* kmax,
@@ -273,33 +262,6 @@ __global__ void __launch_bounds__(kBlock) k_sah_emit_refs(const BNode* bn, const
     primIdx[dst] = first + (N.kind == kSmallRoot ? sout[p] : cur[p]);
 }
 
-int sfail(int code, const char* fmt, ...)   // the message goes to rt_last_error()
-{
-    char buf[512];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-    return rt355_set_error(code, buf);
-}
-
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-dim3 grid(uint32_t threads) { return dim3((threads + kBlock - 1) / kBlock); }
-double ms_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
-
-// Everything one rt_build_bvh2_sah call allocates on the device; freed on every exit path.
-struct Work {
-    void* mem = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = { nullptr, nullptr };
-    int prevDevice = -1;                      // the caller's current device, restored on the way out
-    ~Work()
-    {
-        if (stream) (void)hipStreamSynchronize(stream);
-        if (mem) (void)hipFree(mem);
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        if (stream) (void)hipStreamDestroy(stream);
-        if (prevDevice >= 0) (void)hipSetDevice(prevDevice);
-    }
-};
-
 // The carved workspace of one build of n primitives (everything but the primitives and the output arrays)
 struct Carve {
     size_t oSum, oP, oCur, oNxt, oNid, oNidN, oOwn, of, oF, oSA, oSB, oSout, oSn, oBn, ov, oV, oKA, oKB, oScan, scanBytes, total;
@@ -327,9 +289,6 @@ hipError_t carve_work(uint32_t n, hipStream_t s, Carve& c)
 
 } // namespace
 
-#define SCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
-    return sfail(RT_E_DEVICE, "%s: %s failed: %s", who, #expr, hipGetErrorString(e_)); } while (0)
-
 extern "C" int rt_debug_sah_phases(float* out)
 {
     if (!out) return RT_E_INVALID;
@@ -348,7 +307,7 @@ const char* check_args(int32_t nPrims, int32_t first, int32_t count, uint32_t no
 int work_bytes(const char* who, uint32_t n, hipStream_t s, size_t* bytes)
 {
     Carve c;
-    SCHK(carve_work(n, s, c));
+    BUILD_CHK(carve_work(n, s, c));
     *bytes = c.total;
     return RT_OK;
 }
@@ -357,10 +316,10 @@ int work_bytes(const char* who, uint32_t n, hipStream_t s, size_t* bytes)
 int build(const char* who, hipStream_t stream, void* work, const RtPrimitive* dPrims, uint32_t n, uint32_t first, uint32_t nodeBase,
           uint32_t idxBase, RtBVHNode2* dNodes, uint32_t* dIdx, hipEvent_t evBegin, hipEvent_t evEnd, Built* out)
 {
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = builddev::Clock::now();
     const uint32_t cap = 2 * n - 1, bigMax = n / (kSmall + 1) + 1;
     Carve c;
-    SCHK(carve_work(n, stream, c));
+    BUILD_CHK(carve_work(n, stream, c));
     char* base = (char*)work;
     auto at = [&](size_t o) { return (void*)(base + o); };
     uint32_t* summary = (uint32_t*)at(c.oSum);
@@ -374,15 +333,15 @@ int build(const char* who, hipStream_t stream, void* work, const RtPrimitive* dP
     size_t scanBytes = c.scanBytes;
 
     const BNode root = open_node(0, n, 0);
-    SCHK(hipMemcpyAsync(bn, &root, sizeof root, hipMemcpyHostToDevice, stream));
-    SCHK(hipMemsetAsync(summary, 0, 4 * sizeof(uint32_t), stream));
-    if (evBegin) SCHK(hipEventRecord(evBegin, stream));
-    hipLaunchKernelGGL(k_sah_prims, grid(n), dim3(kBlock), 0, stream, dPrims, n, P, cur, nid, owner, summary + 2);
-    SCHK(hipGetLastError());
+    BUILD_CHK(hipMemcpyAsync(bn, &root, sizeof root, hipMemcpyHostToDevice, stream));
+    BUILD_CHK(hipMemsetAsync(summary, 0, 4 * sizeof(uint32_t), stream));
+    if (evBegin) BUILD_CHK(hipEventRecord(evBegin, stream));
+    hipLaunchKernelGGL(k_sah_prims, grid(n, kBlock), dim3(kBlock), 0, stream, dPrims, n, P, cur, nid, owner, summary + 2);
+    BUILD_CHK(hipGetLastError());
     uint32_t hs[4] = { 0, 0, 0, 0 };
-    SCHK(hipMemcpyAsync(hs, summary, sizeof hs, hipMemcpyDeviceToHost, stream));
-    SCHK(hipStreamSynchronize(stream));   // (rt_build_bvh2_sah: nothing of the caller's host arrays is read after this point)
-    if (hs[2]) return sfail(RT_E_UNSUPPORTED, "%s: %s", who, status_text(hs[2]));
+    BUILD_CHK(hipMemcpyAsync(hs, summary, sizeof hs, hipMemcpyDeviceToHost, stream));
+    BUILD_CHK(hipStreamSynchronize(stream));   // (rt_build_bvh2_sah: nothing of the caller's host arrays is read after this point)
+    if (hs[2]) return build_fail(RT_E_UNSUPPORTED, "%s: %s", who, status_text(hs[2]));
     const double tPrims = ms_since(t0);
 
     // level passes
@@ -394,49 +353,49 @@ int build(const char* who, hipStream_t stream, void* work, const RtPrimitive* dP
         uint64_t *kmin = keysA, *bkmin = keysA + (size_t)nBig * 6, *kmax = keysB, *bkmax = keysB + (size_t)nBig * 6;
         uint32_t* bcnt = (uint32_t*)(keysB + (size_t)nBig * kKeys);
         if (nBig) {
-            SCHK(hipMemsetAsync(keysA, 0xff, (size_t)nBig * kKeys * 8, stream));
-            SCHK(hipMemsetAsync(keysB, 0, (size_t)nBig * (kKeys * 8 + kCnt * 4), stream));
-            hipLaunchKernelGGL(k_sah_reduce, grid(n), dim3(kBlock), 0, stream, P, cur, nid, bn, n, kmin, kmax, summary + 2);
-            hipLaunchKernelGGL(k_sah_bins, grid(n), dim3(kBlock), 0, stream, P, cur, nid, bn, n, kmin, kmax, bkmin, bkmax, bcnt, summary + 2);
+            BUILD_CHK(hipMemsetAsync(keysA, 0xff, (size_t)nBig * kKeys * 8, stream));
+            BUILD_CHK(hipMemsetAsync(keysB, 0, (size_t)nBig * (kKeys * 8 + kCnt * 4), stream));
+            hipLaunchKernelGGL(k_sah_reduce, grid(n, kBlock), dim3(kBlock), 0, stream, P, cur, nid, bn, n, kmin, kmax, summary + 2);
+            hipLaunchKernelGGL(k_sah_bins, grid(n, kBlock), dim3(kBlock), 0, stream, P, cur, nid, bn, n, kmin, kmax, bkmin, bkmax, bcnt, summary + 2);
         }
-        hipLaunchKernelGGL(k_sah_decide, grid(K), dim3(kBlock), 0, stream, bn, lb, le, kmin, kmax, bkmin, bkmax, bcnt, summary + 2);
-        hipLaunchKernelGGL(k_sah_small, grid(K), dim3(kBlock), 0, stream, P, cur, bn, lb, le, sA, sB, sout, snodes, summary + 2);
-        hipLaunchKernelGGL(k_sah_flag, grid(n + 1), dim3(kBlock), 0, stream, P, cur, nid, bn, n, f);
-        SCHK(hipcub::DeviceScan::ExclusiveSum(at(c.oScan), scanBytes, f, F, (int)(n + 1), stream));
-        hipLaunchKernelGGL(k_sah_count, grid(K), dim3(kBlock), 0, stream, bn, lb, le, F, v);
-        SCHK(hipcub::DeviceScan::ExclusiveSum(at(c.oScan), scanBytes, v, V, (int)K, stream));
-        hipLaunchKernelGGL(k_sah_children, grid(K), dim3(kBlock), 0, stream, bn, lb, le, cap, v, V, summary);
-        hipLaunchKernelGGL(k_sah_scatter, grid(n), dim3(kBlock), 0, stream, cur, nid, bn, n, f, F, nxt, nidN, owner);
-        SCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_sah_decide, grid(K, kBlock), dim3(kBlock), 0, stream, bn, lb, le, kmin, kmax, bkmin, bkmax, bcnt, summary + 2);
+        hipLaunchKernelGGL(k_sah_small, grid(K, kBlock), dim3(kBlock), 0, stream, P, cur, bn, lb, le, sA, sB, sout, snodes, summary + 2);
+        hipLaunchKernelGGL(k_sah_flag, grid(n + 1, kBlock), dim3(kBlock), 0, stream, P, cur, nid, bn, n, f);
+        BUILD_CHK(hipcub::DeviceScan::ExclusiveSum(at(c.oScan), scanBytes, f, F, (int)(n + 1), stream));
+        hipLaunchKernelGGL(k_sah_count, grid(K, kBlock), dim3(kBlock), 0, stream, bn, lb, le, F, v);
+        BUILD_CHK(hipcub::DeviceScan::ExclusiveSum(at(c.oScan), scanBytes, v, V, (int)K, stream));
+        hipLaunchKernelGGL(k_sah_children, grid(K, kBlock), dim3(kBlock), 0, stream, bn, lb, le, cap, v, V, summary);
+        hipLaunchKernelGGL(k_sah_scatter, grid(n, kBlock), dim3(kBlock), 0, stream, cur, nid, bn, n, f, F, nxt, nidN, owner);
+        BUILD_CHK(hipGetLastError());
         std::swap(cur, nxt);
         std::swap(nid, nidN);
-        SCHK(hipMemcpyAsync(hs, summary, sizeof hs, hipMemcpyDeviceToHost, stream));
-        SCHK(hipStreamSynchronize(stream));
-        if (hs[2]) return sfail(RT_E_UNSUPPORTED, "%s: %s", who, status_text(hs[2]));
+        BUILD_CHK(hipMemcpyAsync(hs, summary, sizeof hs, hipMemcpyDeviceToHost, stream));
+        BUILD_CHK(hipStreamSynchronize(stream));
+        if (hs[2]) return build_fail(RT_E_UNSUPPORTED, "%s: %s", who, status_text(hs[2]));
         if (hs[0] == 0) break;
         if ((uint64_t)le + 2ull * hs[0] > cap || hs[1] > bigMax)
-            return sfail(RT_E_DEVICE, "%s: inconsistent device result (%u splits, %u open nodes)", who, hs[0], hs[1]);
+            return build_fail(RT_E_DEVICE, "%s: inconsistent device result (%u splits, %u open nodes)", who, hs[0], hs[1]);
         lb = le; le += 2 * hs[0]; nBig = hs[1];
     }
     const double tLevels = ms_since(t0) - tPrims;
 
     // numbering and emit
     for (size_t l = levels.size(); l-- > 0;)
-        hipLaunchKernelGGL(k_sah_up, grid(levels[l].second - levels[l].first), dim3(kBlock), 0, stream, bn, levels[l].first, levels[l].second);
+        hipLaunchKernelGGL(k_sah_up, grid(levels[l].second - levels[l].first, kBlock), dim3(kBlock), 0, stream, bn, levels[l].first, levels[l].second);
     for (const auto& L : levels)
-        hipLaunchKernelGGL(k_sah_down, grid(L.second - L.first), dim3(kBlock), 0, stream, bn, L.first, L.second);
+        hipLaunchKernelGGL(k_sah_down, grid(L.second - L.first, kBlock), dim3(kBlock), 0, stream, bn, L.first, L.second);
     const uint32_t total = levels.back().second;
-    hipLaunchKernelGGL(k_sah_emit, grid(total), dim3(kBlock), 0, stream, bn, total, snodes, nodeBase, idxBase, dNodes, cap, summary + 2);
-    hipLaunchKernelGGL(k_sah_emit_refs, grid(n), dim3(kBlock), 0, stream, bn, owner, cur, sout, n, first, dIdx, summary + 2);
-    SCHK(hipGetLastError());
-    if (evEnd) SCHK(hipEventRecord(evEnd, stream));
+    hipLaunchKernelGGL(k_sah_emit, grid(total, kBlock), dim3(kBlock), 0, stream, bn, total, snodes, nodeBase, idxBase, dNodes, cap, summary + 2);
+    hipLaunchKernelGGL(k_sah_emit_refs, grid(n, kBlock), dim3(kBlock), 0, stream, bn, owner, cur, sout, n, first, dIdx, summary + 2);
+    BUILD_CHK(hipGetLastError());
+    if (evEnd) BUILD_CHK(hipEventRecord(evEnd, stream));
     BNode top;
-    SCHK(hipMemcpyAsync(&top, bn, sizeof top, hipMemcpyDeviceToHost, stream));
-    SCHK(hipMemcpyAsync(hs, summary, sizeof hs, hipMemcpyDeviceToHost, stream));
-    SCHK(hipStreamSynchronize(stream));
+    BUILD_CHK(hipMemcpyAsync(&top, bn, sizeof top, hipMemcpyDeviceToHost, stream));
+    BUILD_CHK(hipMemcpyAsync(hs, summary, sizeof hs, hipMemcpyDeviceToHost, stream));
+    BUILD_CHK(hipStreamSynchronize(stream));
     const uint32_t outNodes = 2 * top.interiors + 1;
     if (hs[2] || outNodes > cap)
-        return sfail(RT_E_DEVICE, "%s: inconsistent device result (%s, %u nodes)", who, status_text(hs[2]), outNodes);
+        return build_fail(RT_E_DEVICE, "%s: inconsistent device result (%s, %u nodes)", who, status_text(hs[2]), outNodes);
     out->nodes = outNodes; out->leaves = top.interiors + 1; out->depth = top.depth; out->cost = top.cost; out->mortonBits = 0;
     out->levels = (uint32_t)levels.size();
     out->ms[0] = (float)tPrims; out->ms[1] = (float)tLevels; out->ms[2] = (float)(ms_since(t0) - tPrims - tLevels);
@@ -445,53 +404,25 @@ int build(const char* who, hipStream_t stream, void* work, const RtPrimitive* dP
 
 } // namespace sahdev
 
-// The C-ABI entry: allocate, upload, build (sahdev::build), download.
+// The C-ABI entry: a session on the device, then builddev::build_flat around sahdev::build.
 extern "C" int rt_build_bvh2_sah(int32_t device, const RtPrimitive* prims, int32_t nPrims, int32_t first, int32_t count, uint32_t nodeBase,
                                  uint32_t idxBase, RtBVHNode2* nodes, int32_t nodeCap, int32_t* nNodes, uint32_t* primIdx, RtBuildStats* stats)
 {
     const char* who = "rt_build_bvh2_sah";
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = builddev::Clock::now();
     if (const char* msg = check_args(prims, nPrims, first, count, nodeBase, idxBase, nodes, nodeCap, nNodes, primIdx))
-        return sfail(RT_E_INVALID, "rt_build_bvh2_sah: %s", msg);
-    int nDev = 0;
-    if (hipGetDeviceCount(&nDev) != hipSuccess || nDev <= 0) return sfail(RT_E_DEVICE, "rt_build_bvh2_sah: no HIP device");
-    if (device < 0 || device >= nDev) return sfail(RT_E_INVALID, "rt_build_bvh2_sah: device %d out of range (%d devices)", device, nDev);
-    Work w;
-    SCHK(hipGetDevice(&w.prevDevice));
-    SCHK(hipSetDevice(device));
-    SCHK(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
-    SCHK(hipEventCreate(&w.ev[0]));
-    SCHK(hipEventCreate(&w.ev[1]));
-
-    const uint32_t n = (uint32_t)count, cap = 2 * n - 1;
-    size_t workBytes = 0;
-    if (const int rc = sahdev::work_bytes(who, n, w.stream, &workBytes)) return rc;
-    // one allocation: the core's workspace, then the primitives and the output arrays
-    const size_t oPrim = align_up(workBytes), oNodes = oPrim + align_up(n * sizeof(RtPrimitive)), oIdx = oNodes + align_up((size_t)cap * sizeof(RtBVHNode2));
-    const size_t bytes = oIdx + align_up(n * 4ull);
-    if (hipMalloc(&w.mem, bytes) != hipSuccess) { w.mem = nullptr; return sfail(RT_E_NOMEM, "rt_build_bvh2_sah: %zu bytes of device memory", bytes); }
-    RtPrimitive* dPrims = (RtPrimitive*)((char*)w.mem + oPrim);
-    RtBVHNode2* dNodes = (RtBVHNode2*)((char*)w.mem + oNodes);
-    uint32_t* dIdx = (uint32_t*)((char*)w.mem + oIdx);
-    SCHK(hipMemcpyAsync(dPrims, prims + first, n * sizeof(RtPrimitive), hipMemcpyHostToDevice, w.stream));
-    const double tAlloc = ms_since(t0);
-
-    sahdev::Built b{};
-    if (const int rc = sahdev::build(who, w.stream, w.mem, dPrims, n, (uint32_t)first, nodeBase, idxBase, dNodes, dIdx, w.ev[0], w.ev[1], &b)) return rc;
-    const double tBuilt = ms_since(t0);
-    SCHK(hipMemcpyAsync(nodes, dNodes, b.nodes * sizeof(RtBVHNode2), hipMemcpyDeviceToHost, w.stream));
-    SCHK(hipMemcpyAsync(primIdx, dIdx, n * sizeof(uint32_t), hipMemcpyDeviceToHost, w.stream));
-    SCHK(hipStreamSynchronize(w.stream));
-    *nNodes = (int32_t)b.nodes;
-    g_phases[0] = (float)tAlloc + b.ms[0]; g_phases[1] = b.ms[1]; g_phases[2] = b.ms[2]; g_phases[3] = (float)(ms_since(t0) - tBuilt);
+        return build_fail(RT_E_INVALID, "rt_build_bvh2_sah: %s", msg);
+    builddev::Session w;
+    if (const int rc = builddev::open_session(who, device, w)) return rc;
+    const uint32_t n = (uint32_t)count;
+    Built b{};
+    builddev::FlatTimes t{};
+    const int rc = builddev::build_flat(who, w, t0, sahdev::work_bytes, prims, first, n, nodes, nNodes, primIdx, stats,
+        [&](void* work, const RtPrimitive* dPrims, RtBVHNode2* dNodes, uint32_t* dIdx, Built* out) {
+            return sahdev::build(who, w.stream, work, dPrims, n, (uint32_t)first, nodeBase, idxBase, dNodes, dIdx, w.ev[0], w.ev[1], out);
+        }, &b, &t);
+    if (rc != RT_OK) return rc;
+    g_phases[0] = (float)t.alloc + b.ms[0]; g_phases[1] = b.ms[1]; g_phases[2] = b.ms[2]; g_phases[3] = (float)(t.done - t.built);
     g_phases[4] = (float)b.levels;
-    if (stats) {
-        float ms = 0;
-        SCHK(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
-        stats->nodes = (int32_t)b.nodes; stats->leaves = (int32_t)b.leaves; stats->depth = (int32_t)b.depth;
-        stats->morton_bits = 0; stats->sah_cost = b.cost; stats->device_ms = ms;
-        stats->wall_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        stats->_reserved = 0;
-    }
     return RT_OK;
 }

@@ -28,7 +28,8 @@
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define SAH_HD __host__ __device__ inline
-#define SAH_HD_CALL __host__ __device__ __attribute__((noinline))   // a real call on the device (decide: see there)
+// a real call on the device (decide: see there); inline for linkage only, so that every translation unit may include the rules
+#define SAH_HD_CALL __host__ __device__ inline __attribute__((noinline))
 #else
 #define SAH_HD inline
 #define SAH_HD_CALL inline

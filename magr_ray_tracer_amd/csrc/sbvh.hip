@@ -19,23 +19,20 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
-#include <chrono>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <utility>
 #include <vector>
 #include "../../include/rt355.h"
-// sah_common.h makes sah::decide a real (non-inline) function for hipcc, and sah.hip already gives the library its one external copy:
-// this file's copy of the rules gets internal linkage.  (The headers they include are included above and guarded.)
-namespace {
 #include "sbvh_common.h"
-}
-#include "build_cores.h"
+#include "build_dev.h"
+#include "fold_dev.h"
 
 using namespace sbvh;
-
-int rt355_set_error(int code, const char* msg);   // rt355.hip: sets the text rt_last_error() returns
+using namespace fold;
+using builddev::align_up;
+using builddev::build_fail;
+using builddev::grid;
+using builddev::ms_since;
 
 namespace {
 
@@ -46,11 +43,6 @@ constexpr int kCnt = 3 * kBins;
 constexpr int kSumWords = 8, kSumStatus = 2, kSumSpatial = 3, kSumClipped = 4, kSumForced = 5;
 
 float g_phases[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };   // rt_debug_sbvh_phases
-
-__device__ inline void lds_min(uint64_t* p, uint64_t v) { __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ inline void lds_max(uint64_t* p, uint64_t v) { __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ inline void glb_min(uint64_t* p, uint64_t v) { __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ inline void glb_max(uint64_t* p, uint64_t v) { __hip_atomic_fetch_max(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 __global__ void __launch_bounds__(kBlock) k_sbvh_prims(const RtPrimitive* prims, uint32_t n, Ref* refs, uint32_t* nid, uint32_t* prim,
                                                        uint32_t* status)
@@ -69,8 +61,8 @@ __global__ void __launch_bounds__(kBlock) k_sbvh_reduce(const Ref* refs, const u
 {
     __shared__ uint64_t smin[kSlots * kNodeKeys], smax[kSlots * kNodeKeys];
     __shared__ uint32_t sfirst;
-    for (int t = threadIdx.x; t < kSlots * kNodeKeys; t += kBlock) { smin[t] = kKeyMinEmpty; smax[t] = kKeyMaxEmpty; }
-    if (threadIdx.x == 0) sfirst = kNone;
+    init_keys<kBlock, kSlots * kNodeKeys>(smin, smax);
+    init_first(&sfirst);
     __syncthreads();
     const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
     uint32_t t = kNone;
@@ -91,10 +83,7 @@ __global__ void __launch_bounds__(kBlock) k_sbvh_reduce(const Ref* refs, const u
     }
     __syncthreads();
     if (sfirst == kNone) return;
-    for (int j = threadIdx.x; j < kSlots * kNodeKeys; j += kBlock) {   // touched slots only: their nodes are < K
-        if (smin[j] != kKeyMinEmpty) glb_min(&kmin[(size_t)sfirst * kNodeKeys + j], smin[j]);
-        if (smax[j] != kKeyMaxEmpty) glb_max(&kmax[(size_t)sfirst * kNodeKeys + j], smax[j]);
-    }
+    flush_keys<kBlock, kSlots * kNodeKeys>(smin, smax, kmin + (size_t)sfirst * kNodeKeys, kmax + (size_t)sfirst * kNodeKeys);   // their nodes are < K
 }
 
 __global__ void __launch_bounds__(kBlock) k_sbvh_obins(const Ref* refs, const uint32_t* nid, uint32_t m, uint32_t lb, uint32_t K,
@@ -104,9 +93,9 @@ __global__ void __launch_bounds__(kBlock) k_sbvh_obins(const Ref* refs, const ui
     __shared__ uint64_t smin[kSlots * kBinKeys], smax[kSlots * kBinKeys];
     __shared__ uint32_t scnt[kSlots * kCnt];
     __shared__ uint32_t sfirst;
-    for (int t = threadIdx.x; t < kSlots * kBinKeys; t += kBlock) { smin[t] = kKeyMinEmpty; smax[t] = kKeyMaxEmpty; }
-    for (int t = threadIdx.x; t < kSlots * kCnt; t += kBlock) scnt[t] = 0;
-    if (threadIdx.x == 0) sfirst = kNone;
+    init_keys<kBlock, kSlots * kBinKeys>(smin, smax);
+    init_counts<kBlock, kSlots * kCnt>(scnt);
+    init_first(&sfirst);
     __syncthreads();
     const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
     uint32_t t = kNone;
@@ -141,12 +130,8 @@ __global__ void __launch_bounds__(kBlock) k_sbvh_obins(const Ref* refs, const ui
     }
     __syncthreads();
     if (sfirst == kNone) return;
-    for (int j = threadIdx.x; j < kSlots * kBinKeys; j += kBlock) {
-        if (smin[j] != kKeyMinEmpty) glb_min(&bkmin[(size_t)sfirst * kBinKeys + j], smin[j]);
-        if (smax[j] != kKeyMaxEmpty) glb_max(&bkmax[(size_t)sfirst * kBinKeys + j], smax[j]);
-    }
-    for (int j = threadIdx.x; j < kSlots * kCnt; j += kBlock)
-        if (scnt[j]) atomicAdd(&bcnt[(size_t)sfirst * kCnt + j], scnt[j]);
+    flush_keys<kBlock, kSlots * kBinKeys>(smin, smax, bkmin + (size_t)sfirst * kBinKeys, bkmax + (size_t)sfirst * kBinKeys);
+    flush_counts<kBlock, kSlots * kCnt>(scnt, bcnt + (size_t)sfirst * kCnt);
 }
 
 __global__ void __launch_bounds__(kBlock) k_sbvh_decide1(SNode* bn, uint32_t lb, uint32_t le, float alpha, const uint64_t* kmin,
@@ -173,9 +158,10 @@ __global__ void __launch_bounds__(kBlock) k_sbvh_sbins(const Ref* refs, const ui
     __shared__ uint64_t smin[kSlots * kBinKeys], smax[kSlots * kBinKeys];
     __shared__ uint32_t sen[kSlots * kSpCnt], sex[kSlots * kSpCnt];
     __shared__ uint32_t sfirst;
-    for (int t = threadIdx.x; t < kSlots * kBinKeys; t += kBlock) { smin[t] = kKeyMinEmpty; smax[t] = kKeyMaxEmpty; }
-    for (int t = threadIdx.x; t < kSlots * kSpCnt; t += kBlock) { sen[t] = 0; sex[t] = 0; }
-    if (threadIdx.x == 0) sfirst = kNone;
+    init_keys<kBlock, kSlots * kBinKeys>(smin, smax);
+    init_counts<kBlock, kSlots * kSpCnt>(sen);
+    init_counts<kBlock, kSlots * kSpCnt>(sex);
+    init_first(&sfirst);
     __syncthreads();
     const uint32_t p = blockIdx.x * kBlock + threadIdx.x;
     uint32_t t = kNone;
@@ -216,14 +202,9 @@ __global__ void __launch_bounds__(kBlock) k_sbvh_sbins(const Ref* refs, const ui
     }
     __syncthreads();
     if (sfirst == kNone) return;
-    for (int j = threadIdx.x; j < kSlots * kBinKeys; j += kBlock) {
-        if (smin[j] != kKeyMinEmpty) glb_min(&skmin[(size_t)sfirst * kBinKeys + j], smin[j]);
-        if (smax[j] != kKeyMaxEmpty) glb_max(&skmax[(size_t)sfirst * kBinKeys + j], smax[j]);
-    }
-    for (int j = threadIdx.x; j < kSlots * kSpCnt; j += kBlock) {
-        if (sen[j]) atomicAdd(&sent[(size_t)sfirst * kSpCnt + j], sen[j]);
-        if (sex[j]) atomicAdd(&sext[(size_t)sfirst * kSpCnt + j], sex[j]);
-    }
+    flush_keys<kBlock, kSlots * kBinKeys>(smin, smax, skmin + (size_t)sfirst * kBinKeys, skmax + (size_t)sfirst * kBinKeys);
+    flush_counts<kBlock, kSlots * kSpCnt>(sen, sent + (size_t)sfirst * kSpCnt);
+    flush_counts<kBlock, kSlots * kSpCnt>(sex, sext + (size_t)sfirst * kSpCnt);
 }
 
 __global__ void __launch_bounds__(kBlock) k_sbvh_decide2(SNode* bn, uint32_t lb, uint32_t le, const uint64_t* kmin, const uint64_t* kmax,
@@ -357,17 +338,6 @@ __global__ void __launch_bounds__(kBlock) k_sbvh_emit_refs(const SNode* bn, uint
     primIdx[dst] = first + prim[p];
 }
 
-int sfail(int code, const char* fmt, ...)   // the message goes to rt_last_error()
-{
-    char buf[512];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-    return rt355_set_error(code, buf);
-}
-
-size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
-dim3 grid(uint32_t threads) { return dim3((threads + kBlock - 1) / kBlock); }
-double ms_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
-
 // A device array that grows: ensure() keeps the first `keep` bytes when it has to move
 struct DBuf {
     void* p = nullptr;
@@ -392,30 +362,15 @@ struct DBuf {
     }
 };
 
-// Everything one rt_build_bvh2_sbvh call owns on the device; freed on every exit path.
-struct Work {
-    void* prims = nullptr;
-    void* out = nullptr;
+// What one rt_build_bvh2_sbvh call owns on the device: the session's two allocations and the built tree, which goes while the stream
+// still exists and is idle
+struct SbvhSession : builddev::Session {
+    void *&prims = mem[0], *&out = mem[1];   // the uploaded primitives; the emitted arrays
     sbvhdev::Tree* tree = nullptr;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[2] = { nullptr, nullptr };
-    int prevDevice = -1;                      // the caller's current device, restored on the way out
-    ~Work()
-    {
-        if (stream) (void)hipStreamSynchronize(stream);
-        sbvhdev::destroy(tree);
-        if (prims) (void)hipFree(prims);
-        if (out) (void)hipFree(out);
-        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-        if (stream) (void)hipStreamDestroy(stream);
-        if (prevDevice >= 0) (void)hipSetDevice(prevDevice);
-    }
+    ~SbvhSession() { idle(); sbvhdev::destroy(tree); }
 };
 
 } // namespace
-
-#define SCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
-    return sfail(e_ == hipErrorOutOfMemory ? RT_E_NOMEM : RT_E_DEVICE, "%s: %s failed: %s", who, #expr, hipGetErrorString(e_)); } while (0)
 
 extern "C" int rt_debug_sbvh_phases(float* out)
 {
@@ -446,7 +401,7 @@ void destroy(Tree* t) { delete t; }
 int build(const char* who, hipStream_t stream, float alpha, const RtPrimitive* dPrims, uint32_t n, uint32_t first, uint32_t nodeBase,
           uint32_t idxBase, hipEvent_t evBegin, hipEvent_t evEnd, Tree** treeOut, SbvhBuilt* out)
 {
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = builddev::Clock::now();
     Tree* T = new Tree();
     *treeOut = T;                                             // the caller destroys it, on failure too
     T->first = first; T->nodeBase = nodeBase; T->idxBase = idxBase;
@@ -465,22 +420,22 @@ int build(const char* who, hipStream_t stream, float alpha, const RtPrimitive* d
         T->hist.push_back(h); T->histN.push_back(m);
         return hipSuccess;
     };
-    SCHK(T->summary.ensure(kSumWords * sizeof(uint32_t), 0, stream));
-    SCHK(T->bn.ensure(1024 * sizeof(SNode), 0, stream));
-    SCHK(refsA.ensure(refCap * sizeof(Ref), 0, stream));
-    SCHK(add_level(n));
+    BUILD_CHK(T->summary.ensure(kSumWords * sizeof(uint32_t), 0, stream));
+    BUILD_CHK(T->bn.ensure(1024 * sizeof(SNode), 0, stream));
+    BUILD_CHK(refsA.ensure(refCap * sizeof(Ref), 0, stream));
+    BUILD_CHK(add_level(n));
     uint32_t* summary = (uint32_t*)T->summary.p;
     const SNode root = open_snode(0, n);
-    SCHK(hipMemcpyAsync(T->bn.p, &root, sizeof root, hipMemcpyHostToDevice, stream));
-    SCHK(hipMemsetAsync(summary, 0, kSumWords * sizeof(uint32_t), stream));
-    if (evBegin) SCHK(hipEventRecord(evBegin, stream));
-    hipLaunchKernelGGL(k_sbvh_prims, grid(n), dim3(kBlock), 0, stream, dPrims, n, (Ref*)refsA.p, (uint32_t*)T->hist[0], (uint32_t*)T->hist[0] + n,
+    BUILD_CHK(hipMemcpyAsync(T->bn.p, &root, sizeof root, hipMemcpyHostToDevice, stream));
+    BUILD_CHK(hipMemsetAsync(summary, 0, kSumWords * sizeof(uint32_t), stream));
+    if (evBegin) BUILD_CHK(hipEventRecord(evBegin, stream));
+    hipLaunchKernelGGL(k_sbvh_prims, grid(n, kBlock), dim3(kBlock), 0, stream, dPrims, n, (Ref*)refsA.p, (uint32_t*)T->hist[0], (uint32_t*)T->hist[0] + n,
                        summary + kSumStatus);
-    SCHK(hipGetLastError());
+    BUILD_CHK(hipGetLastError());
     uint32_t hs[kSumWords] = {};
-    SCHK(hipMemcpyAsync(hs, summary, sizeof hs, hipMemcpyDeviceToHost, stream));
-    SCHK(hipStreamSynchronize(stream));   // (rt_build_bvh2_sbvh: nothing of the caller's host arrays is read after this point)
-    if (hs[kSumStatus]) return sfail(RT_E_UNSUPPORTED, "%s: %s", who, sstatus_text(hs[kSumStatus]));
+    BUILD_CHK(hipMemcpyAsync(hs, summary, sizeof hs, hipMemcpyDeviceToHost, stream));
+    BUILD_CHK(hipStreamSynchronize(stream));   // (rt_build_bvh2_sbvh: nothing of the caller's host arrays is read after this point)
+    if (hs[kSumStatus]) return build_fail(RT_E_UNSUPPORTED, "%s: %s", who, sstatus_text(hs[kSumStatus]));
     const double tPrims = ms_since(t0);
 
     // level passes
@@ -496,15 +451,15 @@ int build(const char* who, hipStream_t stream, float alpha, const RtPrimitive* d
         const size_t oBcnt = oSkmax + (size_t)K * kBinKeys * 8, oSent = oBcnt + (size_t)K * kCnt * 4, oSext = oSent + (size_t)K * kSpCnt * 4;
         const size_t zeroBytes = align_up(oSext + (size_t)K * kSpCnt * 4 - ffBytes);
         const size_t ov = ffBytes + zeroBytes, oV = ov + align_up((size_t)K * 8);
-        SCHK(lvl.ensure(oV + align_up((size_t)K * 8), 0, stream));
+        BUILD_CHK(lvl.ensure(oV + align_up((size_t)K * 8), 0, stream));
         size_t scanA = 0, scanB = 0;
-        SCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, scanA, (uint64_t*)nullptr, (uint64_t*)nullptr, (int)(m + 1), stream));
-        SCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, scanB, (uint64_t*)nullptr, (uint64_t*)nullptr, (int)K, stream));
+        BUILD_CHK(hipcub::DeviceScan::ExclusiveSum(nullptr, scanA, (uint64_t*)nullptr, (uint64_t*)nullptr, (int)(m + 1), stream));
+        BUILD_CHK(hipcub::DeviceScan::ExclusiveSum(nullptr, scanB, (uint64_t*)nullptr, (uint64_t*)nullptr, (int)K, stream));
         size_t scanBytes = scanA > scanB ? scanA : scanB;
-        SCHK(scan.ensure(scanBytes ? scanBytes : 256, 0, stream));
-        SCHK(fbuf.ensure(((size_t)m + 1) * 8, 0, stream));
-        SCHK(Fbuf.ensure(((size_t)m + 1) * 8, 0, stream));
-        SCHK(T->bn.ensure(((size_t)le + 2 * (size_t)K) * sizeof(SNode), (size_t)le * sizeof(SNode), stream));
+        BUILD_CHK(scan.ensure(scanBytes ? scanBytes : 256, 0, stream));
+        BUILD_CHK(fbuf.ensure(((size_t)m + 1) * 8, 0, stream));
+        BUILD_CHK(Fbuf.ensure(((size_t)m + 1) * 8, 0, stream));
+        BUILD_CHK(T->bn.ensure(((size_t)le + 2 * (size_t)K) * sizeof(SNode), (size_t)le * sizeof(SNode), stream));
         const uint32_t bnCap = (uint32_t)std::min<size_t>(T->bn.cap / sizeof(SNode), 0xffffffffu);
         char* base = (char*)lvl.p;
         uint64_t *kmin = (uint64_t*)(base + oKmin), *bkmin = (uint64_t*)(base + oBkmin), *skmin = (uint64_t*)(base + oSkmin);
@@ -515,37 +470,37 @@ int build(const char* who, hipStream_t stream, float alpha, const RtPrimitive* d
         SNode* bn = (SNode*)T->bn.p;
         const Ref* refs = (const Ref*)cur->p;
         const uint32_t* nid = (const uint32_t*)T->hist.back();
-        SCHK(hipMemsetAsync(base, 0xff, ffBytes, stream));
-        SCHK(hipMemsetAsync(base + ffBytes, 0, zeroBytes, stream));
-        hipLaunchKernelGGL(k_sbvh_reduce, grid(m), dim3(kBlock), 0, stream, refs, nid, m, lb, K, kmin, kmax, summary + kSumStatus);
-        hipLaunchKernelGGL(k_sbvh_obins, grid(m), dim3(kBlock), 0, stream, refs, nid, m, lb, K, kmin, kmax, bkmin, bkmax, bcnt, summary + kSumStatus);
-        hipLaunchKernelGGL(k_sbvh_decide1, grid(K), dim3(kBlock), 0, stream, bn, lb, le, alpha, kmin, kmax, bkmin, bkmax, bcnt);
-        hipLaunchKernelGGL(k_sbvh_sbins, grid(m), dim3(kBlock), 0, stream, refs, nid, dPrims, bn, m, lb, K, kmin, kmax, skmin, skmax, sent, sext,
+        BUILD_CHK(hipMemsetAsync(base, 0xff, ffBytes, stream));
+        BUILD_CHK(hipMemsetAsync(base + ffBytes, 0, zeroBytes, stream));
+        hipLaunchKernelGGL(k_sbvh_reduce, grid(m, kBlock), dim3(kBlock), 0, stream, refs, nid, m, lb, K, kmin, kmax, summary + kSumStatus);
+        hipLaunchKernelGGL(k_sbvh_obins, grid(m, kBlock), dim3(kBlock), 0, stream, refs, nid, m, lb, K, kmin, kmax, bkmin, bkmax, bcnt, summary + kSumStatus);
+        hipLaunchKernelGGL(k_sbvh_decide1, grid(K, kBlock), dim3(kBlock), 0, stream, bn, lb, le, alpha, kmin, kmax, bkmin, bkmax, bcnt);
+        hipLaunchKernelGGL(k_sbvh_sbins, grid(m, kBlock), dim3(kBlock), 0, stream, refs, nid, dPrims, bn, m, lb, K, kmin, kmax, skmin, skmax, sent, sext,
                            summary + kSumStatus);
-        hipLaunchKernelGGL(k_sbvh_decide2, grid(K), dim3(kBlock), 0, stream, bn, lb, le, kmin, kmax, skmin, skmax, sent, sext, summary + kSumStatus);
-        hipLaunchKernelGGL(k_sbvh_flag, grid(m + 1), dim3(kBlock), 0, stream, refs, nid, dPrims, bn, m, f, summary);
-        SCHK(hipcub::DeviceScan::ExclusiveSum(scan.p, scanBytes, f, F, (int)(m + 1), stream));
-        hipLaunchKernelGGL(k_sbvh_count, grid(K), dim3(kBlock), 0, stream, bn, lb, le, F, v, summary);
-        SCHK(hipcub::DeviceScan::ExclusiveSum(scan.p, scanBytes, v, V, (int)K, stream));
-        hipLaunchKernelGGL(k_sbvh_children, grid(K), dim3(kBlock), 0, stream, bn, lb, le, bnCap, v, V, summary);
-        SCHK(hipGetLastError());
-        SCHK(hipMemcpyAsync(hs, summary, sizeof hs, hipMemcpyDeviceToHost, stream));
-        SCHK(hipStreamSynchronize(stream));
-        if (hs[kSumStatus] & kInternal) return sfail(RT_E_DEVICE, "%s: %s", who, sstatus_text(hs[kSumStatus]));
-        if (hs[kSumStatus]) return sfail(RT_E_UNSUPPORTED, "%s: %s", who, sstatus_text(hs[kSumStatus]));
+        hipLaunchKernelGGL(k_sbvh_decide2, grid(K, kBlock), dim3(kBlock), 0, stream, bn, lb, le, kmin, kmax, skmin, skmax, sent, sext, summary + kSumStatus);
+        hipLaunchKernelGGL(k_sbvh_flag, grid(m + 1, kBlock), dim3(kBlock), 0, stream, refs, nid, dPrims, bn, m, f, summary);
+        BUILD_CHK(hipcub::DeviceScan::ExclusiveSum(scan.p, scanBytes, f, F, (int)(m + 1), stream));
+        hipLaunchKernelGGL(k_sbvh_count, grid(K, kBlock), dim3(kBlock), 0, stream, bn, lb, le, F, v, summary);
+        BUILD_CHK(hipcub::DeviceScan::ExclusiveSum(scan.p, scanBytes, v, V, (int)K, stream));
+        hipLaunchKernelGGL(k_sbvh_children, grid(K, kBlock), dim3(kBlock), 0, stream, bn, lb, le, bnCap, v, V, summary);
+        BUILD_CHK(hipGetLastError());
+        BUILD_CHK(hipMemcpyAsync(hs, summary, sizeof hs, hipMemcpyDeviceToHost, stream));
+        BUILD_CHK(hipStreamSynchronize(stream));
+        if (hs[kSumStatus] & kInternal) return build_fail(RT_E_DEVICE, "%s: %s", who, sstatus_text(hs[kSumStatus]));
+        if (hs[kSumStatus]) return build_fail(RT_E_UNSUPPORTED, "%s: %s", who, sstatus_text(hs[kSumStatus]));
         const uint32_t splits = hs[0], mNext = hs[1];
         if (splits == 0) break;
         if (splits > K || (uint64_t)mNext > 2ull * m || mNext == 0)
-            return sfail(RT_E_DEVICE, "%s: inconsistent device result (%u splits of %u nodes, %u refs from %u)", who, splits, K, mNext, m);
+            return build_fail(RT_E_DEVICE, "%s: inconsistent device result (%u splits of %u nodes, %u refs from %u)", who, splits, K, mNext, m);
         if (mNext > kMaxRefs - 1 || (uint64_t)le + 2ull * splits > kMaxRefs)
-            return sfail(RT_E_NOMEM, "%s: more than 2^31 refs or nodes", who);
+            return build_fail(RT_E_NOMEM, "%s: more than 2^31 refs or nodes", who);
         // the next level's arrays, sized from the scan
         if (nxt->ensure((size_t)mNext * sizeof(Ref), 0, stream) != hipSuccess || add_level(mNext) != hipSuccess)
-            return sfail(RT_E_NOMEM, "%s: device memory for %u refs", who, mNext);
+            return build_fail(RT_E_NOMEM, "%s: device memory for %u refs", who, mNext);
         uint32_t* nidN = (uint32_t*)T->hist.back();
-        hipLaunchKernelGGL(k_sbvh_scatter, grid(m), dim3(kBlock), 0, stream, refs, nid, dPrims, bn, m, bnCap, F, (Ref*)nxt->p, nidN, nidN + mNext, mNext,
+        hipLaunchKernelGGL(k_sbvh_scatter, grid(m, kBlock), dim3(kBlock), 0, stream, refs, nid, dPrims, bn, m, bnCap, F, (Ref*)nxt->p, nidN, nidN + mNext, mNext,
                            summary + kSumStatus);
-        SCHK(hipGetLastError());
+        BUILD_CHK(hipGetLastError());
         std::swap(cur, nxt);
         m = mNext;
         if (m > peak) peak = m;
@@ -556,19 +511,19 @@ int build(const char* who, hipStream_t stream, float alpha, const RtPrimitive* d
     // numbering
     SNode* bn = (SNode*)T->bn.p;
     for (size_t l = T->levels.size(); l-- > 0;)
-        hipLaunchKernelGGL(k_sbvh_up, grid(T->levels[l].second - T->levels[l].first), dim3(kBlock), 0, stream, bn, T->levels[l].first, T->levels[l].second);
+        hipLaunchKernelGGL(k_sbvh_up, grid(T->levels[l].second - T->levels[l].first, kBlock), dim3(kBlock), 0, stream, bn, T->levels[l].first, T->levels[l].second);
     for (const auto& L : T->levels)
-        hipLaunchKernelGGL(k_sbvh_down, grid(L.second - L.first), dim3(kBlock), 0, stream, bn, L.first, L.second);
-    SCHK(hipGetLastError());
-    if (evEnd) SCHK(hipEventRecord(evEnd, stream));
+        hipLaunchKernelGGL(k_sbvh_down, grid(L.second - L.first, kBlock), dim3(kBlock), 0, stream, bn, L.first, L.second);
+    BUILD_CHK(hipGetLastError());
+    if (evEnd) BUILD_CHK(hipEventRecord(evEnd, stream));
     SNode top;
-    SCHK(hipMemcpyAsync(&top, bn, sizeof top, hipMemcpyDeviceToHost, stream));
-    SCHK(hipMemcpyAsync(hs, summary, sizeof hs, hipMemcpyDeviceToHost, stream));
-    SCHK(hipStreamSynchronize(stream));
+    BUILD_CHK(hipMemcpyAsync(&top, bn, sizeof top, hipMemcpyDeviceToHost, stream));
+    BUILD_CHK(hipMemcpyAsync(hs, summary, sizeof hs, hipMemcpyDeviceToHost, stream));
+    BUILD_CHK(hipStreamSynchronize(stream));
     T->total = T->levels.back().second;
     const uint64_t outNodes = 2ull * top.b.interiors + 1;
     if (hs[kSumStatus] || outNodes != T->total)
-        return sfail(RT_E_DEVICE, "%s: inconsistent device result (%s, %llu nodes of %u)", who, sstatus_text(hs[kSumStatus]), (unsigned long long)outNodes, T->total);
+        return build_fail(RT_E_DEVICE, "%s: inconsistent device result (%s, %llu nodes of %u)", who, sstatus_text(hs[kSumStatus]), (unsigned long long)outNodes, T->total);
     SbvhBuilt& b = T->built;
     b.nodes = (uint32_t)outNodes; b.leaves = top.b.interiors + 1; b.nIdx = top.b.cnt; b.depth = top.b.depth; b.cost = top.b.cost;
     b.spatialSplits = hs[kSumSpatial]; b.primsClipped = hs[kSumClipped]; b.forcedLeaves = hs[kSumForced];
@@ -583,19 +538,19 @@ int emit(const char* who, hipStream_t stream, Tree* T, RtBVHNode2* dNodes, uint3
 {
     uint32_t* summary = (uint32_t*)T->summary.p;
     const SNode* bn = (const SNode*)T->bn.p;
-    hipLaunchKernelGGL(k_sbvh_emit, grid(T->total), dim3(kBlock), 0, stream, bn, T->total, T->nodeBase, T->idxBase, dNodes, T->built.nodes,
+    hipLaunchKernelGGL(k_sbvh_emit, grid(T->total, kBlock), dim3(kBlock), 0, stream, bn, T->total, T->nodeBase, T->idxBase, dNodes, T->built.nodes,
                        summary + kSumStatus);
     for (size_t l = 0; l < T->hist.size(); l++) {
         const uint32_t m = T->histN[l];
         const uint32_t* nid = (const uint32_t*)T->hist[l];
-        hipLaunchKernelGGL(k_sbvh_emit_refs, grid(m), dim3(kBlock), 0, stream, bn, T->total, nid, nid + m, m, T->first, dIdx, T->built.nIdx,
+        hipLaunchKernelGGL(k_sbvh_emit_refs, grid(m, kBlock), dim3(kBlock), 0, stream, bn, T->total, nid, nid + m, m, T->first, dIdx, T->built.nIdx,
                            summary + kSumStatus);
     }
-    SCHK(hipGetLastError());
+    BUILD_CHK(hipGetLastError());
     uint32_t st = 0;
-    SCHK(hipMemcpyAsync(&st, summary + kSumStatus, sizeof st, hipMemcpyDeviceToHost, stream));
-    SCHK(hipStreamSynchronize(stream));
-    if (st) return sfail(RT_E_DEVICE, "%s: inconsistent device result (%s)", who, sstatus_text(st));
+    BUILD_CHK(hipMemcpyAsync(&st, summary + kSumStatus, sizeof st, hipMemcpyDeviceToHost, stream));
+    BUILD_CHK(hipStreamSynchronize(stream));
+    if (st) return build_fail(RT_E_DEVICE, "%s: inconsistent device result (%s)", who, sstatus_text(st));
     return RT_OK;
 }
 
@@ -607,48 +562,41 @@ extern "C" int rt_build_bvh2_sbvh(int32_t device, float alpha, const RtPrimitive
                                   int32_t idxCap, int32_t* nIdx, RtSbvhStats* stats)
 {
     const char* who = "rt_build_bvh2_sbvh";
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = builddev::Clock::now();
     if (const char* msg = check_args(alpha, prims, nPrims, first, count, nodes, nodeCap, nNodes, primIdx, idxCap, nIdx))
-        return sfail(RT_E_INVALID, "rt_build_bvh2_sbvh: %s", msg);
-    int nDev = 0;
-    if (hipGetDeviceCount(&nDev) != hipSuccess || nDev <= 0) return sfail(RT_E_DEVICE, "rt_build_bvh2_sbvh: no HIP device");
-    if (device < 0 || device >= nDev) return sfail(RT_E_INVALID, "rt_build_bvh2_sbvh: device %d out of range (%d devices)", device, nDev);
-    Work w;
-    SCHK(hipGetDevice(&w.prevDevice));
-    SCHK(hipSetDevice(device));
-    SCHK(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
-    SCHK(hipEventCreate(&w.ev[0]));
-    SCHK(hipEventCreate(&w.ev[1]));
+        return build_fail(RT_E_INVALID, "rt_build_bvh2_sbvh: %s", msg);
+    SbvhSession w;
+    if (const int rc = builddev::open_session(who, device, w)) return rc;
     const uint32_t n = (uint32_t)count;
-    if (hipMalloc(&w.prims, n * sizeof(RtPrimitive)) != hipSuccess) { w.prims = nullptr; return sfail(RT_E_NOMEM, "rt_build_bvh2_sbvh: device memory for %u primitives", n); }
-    SCHK(hipMemcpyAsync(w.prims, prims + first, n * sizeof(RtPrimitive), hipMemcpyHostToDevice, w.stream));
+    if (hipMalloc(&w.prims, n * sizeof(RtPrimitive)) != hipSuccess) { w.prims = nullptr; return build_fail(RT_E_NOMEM, "rt_build_bvh2_sbvh: device memory for %u primitives", n); }
+    BUILD_CHK(hipMemcpyAsync(w.prims, prims + first, n * sizeof(RtPrimitive), hipMemcpyHostToDevice, w.stream));
     const double tAlloc = ms_since(t0);
 
     SbvhBuilt b{};
     if (const int rc = sbvhdev::build(who, w.stream, alpha, (const RtPrimitive*)w.prims, n, (uint32_t)first, nodeBase, idxBase, w.ev[0], nullptr, &w.tree, &b))
         return rc;
     if ((uint64_t)nodeBase + b.nodes > 0xffffffffull || (uint64_t)idxBase + b.nIdx > 0xffffffffull)
-        return sfail(RT_E_INVALID, "rt_build_bvh2_sbvh: nodeBase / idxBase + the tree overflow 32-bit ids");
+        return build_fail(RT_E_INVALID, "rt_build_bvh2_sbvh: nodeBase / idxBase + the tree overflow 32-bit ids");
     *nNodes = (int32_t)b.nodes; *nIdx = (int32_t)b.nIdx;
     if ((uint32_t)nodeCap < b.nodes || (uint32_t)idxCap < b.nIdx)
-        return sfail(RT_E_INVALID, "rt_build_bvh2_sbvh: capacity: the tree has %u nodes and %u primIdx entries (nodeCap %d, idxCap %d)", b.nodes, b.nIdx,
+        return build_fail(RT_E_INVALID, "rt_build_bvh2_sbvh: capacity: the tree has %u nodes and %u primIdx entries (nodeCap %d, idxCap %d)", b.nodes, b.nIdx,
                      nodeCap, idxCap);
     const double tEmit = ms_since(t0);
     const size_t oIdx = align_up((size_t)b.nodes * sizeof(RtBVHNode2));
-    if (hipMalloc(&w.out, oIdx + align_up((size_t)b.nIdx * 4)) != hipSuccess) { w.out = nullptr; return sfail(RT_E_NOMEM, "rt_build_bvh2_sbvh: device memory for the tree"); }
+    if (hipMalloc(&w.out, oIdx + align_up((size_t)b.nIdx * 4)) != hipSuccess) { w.out = nullptr; return build_fail(RT_E_NOMEM, "rt_build_bvh2_sbvh: device memory for the tree"); }
     RtBVHNode2* dNodes = (RtBVHNode2*)w.out;
     uint32_t* dIdx = (uint32_t*)((char*)w.out + oIdx);
     if (const int rc = sbvhdev::emit(who, w.stream, w.tree, dNodes, dIdx)) return rc;
-    SCHK(hipEventRecord(w.ev[1], w.stream));
+    BUILD_CHK(hipEventRecord(w.ev[1], w.stream));
     const double tBuilt = ms_since(t0);
-    SCHK(hipMemcpyAsync(nodes, dNodes, (size_t)b.nodes * sizeof(RtBVHNode2), hipMemcpyDeviceToHost, w.stream));
-    SCHK(hipMemcpyAsync(primIdx, dIdx, (size_t)b.nIdx * sizeof(uint32_t), hipMemcpyDeviceToHost, w.stream));
-    SCHK(hipStreamSynchronize(w.stream));
+    BUILD_CHK(hipMemcpyAsync(nodes, dNodes, (size_t)b.nodes * sizeof(RtBVHNode2), hipMemcpyDeviceToHost, w.stream));
+    BUILD_CHK(hipMemcpyAsync(primIdx, dIdx, (size_t)b.nIdx * sizeof(uint32_t), hipMemcpyDeviceToHost, w.stream));
+    BUILD_CHK(hipStreamSynchronize(w.stream));
     g_phases[0] = (float)tAlloc + b.ms[0]; g_phases[1] = b.ms[1]; g_phases[2] = b.ms[2] + (float)(tBuilt - tEmit);
     g_phases[3] = (float)(ms_since(t0) - tBuilt); g_phases[4] = (float)b.levels;
     if (stats) {
         float ms = 0;
-        SCHK(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
+        BUILD_CHK(hipEventElapsedTime(&ms, w.ev[0], w.ev[1]));
         stats->nodes = (int32_t)b.nodes; stats->leaves = (int32_t)b.leaves; stats->n_idx = (int32_t)b.nIdx; stats->depth = (int32_t)b.depth;
         stats->spatial_splits = (int32_t)b.spatialSplits; stats->prims_clipped = (int32_t)b.primsClipped;
         stats->forced_leaves = (int32_t)b.forcedLeaves; stats->levels = (int32_t)b.levels;

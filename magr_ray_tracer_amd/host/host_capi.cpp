@@ -16,6 +16,23 @@ struct RthRenderer { Renderer* r = nullptr; RthScene* adopted = nullptr; };
 static float3 f3(const float* p) { return float3(p[0], p[1], p[2]); }
 static float2 f2(const float* p) { float2 r; if (p) { r.x = p[0]; r.y = p[1]; } return r; }
 
+// rth_build_blas_<builder>: the start index checked, then the BVH2 method; an LbvhError carries its RT_E_* code
+template <class Build> static int build_blas(const char* who, RthScene* s, int startIdx, Build build)
+{
+    if (!s || startIdx < 0 || startIdx >= (int)s->scene.primitives.size()) { g_herr = std::string(who) + ": bad start index"; return RT_E_INVALID; }
+    try { build(); return 0; }
+    catch (const LbvhError& e) { g_herr = e.what(); return e.code; }
+    catch (const std::exception& e) { g_herr = e.what(); return RT_E_NOMEM; }
+}
+// rth_build_bvh2_<builder>: the host restatement's message goes to rth_last_error() when it refuses
+template <class Build> static int build_bvh2(Build build)
+{
+    std::string err;
+    const int rc = build(err);
+    if (rc != RT_OK) g_herr = err;
+    return rc;
+}
+
 extern "C" {
 
 const char* rth_last_error(void) { return g_herr.c_str(); }
@@ -74,49 +91,33 @@ int rth_build_blas(RthScene* s, int startIdx, float alpha)
 }
 int rth_build_blas_lbvh(RthScene* s, int startIdx, int device, const RtBuildOptions* opts)
 {
-    if (!s || startIdx < 0 || startIdx >= (int)s->scene.primitives.size()) { g_herr = "rth_build_blas_lbvh: bad start index"; return RT_E_INVALID; }
-    try { s->scene.bvh2->BuildBLASLBVH(startIdx, device, opts); return 0; }
-    catch (const LbvhError& e) { g_herr = e.what(); return e.code; }
-    catch (const std::exception& e) { g_herr = e.what(); return RT_E_NOMEM; }
+    return build_blas("rth_build_blas_lbvh", s, startIdx, [&] { s->scene.bvh2->BuildBLASLBVH(startIdx, device, opts); });
 }
 int rth_build_bvh2_lbvh(const RtBuildOptions* opts, const RtPrimitive* prims, int32_t nPrims, int32_t first, int32_t count, uint32_t nodeBase,
                         uint32_t idxBase, RtBVHNode2* nodes, int32_t nodeCap, int32_t* nNodes, uint32_t* primIdx, RtBuildStats* stats)
 {
-    std::string err;
-    const int rc = LbvhBuildHost(opts, prims, nPrims, first, count, nodeBase, idxBase, nodes, nodeCap, nNodes, primIdx, stats, err);
-    if (rc != RT_OK) g_herr = err;
-    return rc;
+    return build_bvh2([&](std::string& err) { return LbvhBuildHost(opts, prims, nPrims, first, count, nodeBase, idxBase, nodes, nodeCap, nNodes, primIdx, stats, err); });
 }
 int rth_lbvh_stats(RthScene* s, RtBuildStats* out) { if (!s || !out) return -1; *out = s->scene.bvh2->lastLbvh; return 0; }
 int rth_build_blas_sah_gpu(RthScene* s, int startIdx, int device)
 {
-    if (!s || startIdx < 0 || startIdx >= (int)s->scene.primitives.size()) { g_herr = "rth_build_blas_sah_gpu: bad start index"; return RT_E_INVALID; }
-    try { s->scene.bvh2->BuildBLASSAHGPU(startIdx, device); return 0; }
-    catch (const LbvhError& e) { g_herr = e.what(); return e.code; }
-    catch (const std::exception& e) { g_herr = e.what(); return RT_E_NOMEM; }
+    return build_blas("rth_build_blas_sah_gpu", s, startIdx, [&] { s->scene.bvh2->BuildBLASSAHGPU(startIdx, device); });
 }
 int rth_build_bvh2_sah(const RtPrimitive* prims, int32_t nPrims, int32_t first, int32_t count, uint32_t nodeBase, uint32_t idxBase,
                        RtBVHNode2* nodes, int32_t nodeCap, int32_t* nNodes, uint32_t* primIdx, RtBuildStats* stats)
 {
-    std::string err;
-    const int rc = SahBuildHost(prims, nPrims, first, count, nodeBase, idxBase, nodes, nodeCap, nNodes, primIdx, stats, err);
-    if (rc != RT_OK) g_herr = err;
-    return rc;
+    return build_bvh2([&](std::string& err) { return SahBuildHost(prims, nPrims, first, count, nodeBase, idxBase, nodes, nodeCap, nNodes, primIdx, stats, err); });
 }
 int rth_build_blas_sbvh_gpu(RthScene* s, int startIdx, float alpha, int device)
 {
-    if (!s || startIdx < 0 || startIdx >= (int)s->scene.primitives.size()) { g_herr = "rth_build_blas_sbvh_gpu: bad start index"; return RT_E_INVALID; }
-    try { s->scene.bvh2->BuildBLASSBVHGPU(startIdx, alpha, device); return 0; }
-    catch (const LbvhError& e) { g_herr = e.what(); return e.code; }
-    catch (const std::exception& e) { g_herr = e.what(); return RT_E_NOMEM; }
+    return build_blas("rth_build_blas_sbvh_gpu", s, startIdx, [&] { s->scene.bvh2->BuildBLASSBVHGPU(startIdx, alpha, device); });
 }
 int rth_build_bvh2_sbvh(float alpha, const RtPrimitive* prims, int32_t nPrims, int32_t first, int32_t count, uint32_t nodeBase, uint32_t idxBase,
                         RtBVHNode2* nodes, int32_t nodeCap, int32_t* nNodes, uint32_t* primIdx, int32_t idxCap, int32_t* nIdx, RtSbvhStats* stats)
 {
-    std::string err;
-    const int rc = SbvhBuildHost(alpha, prims, nPrims, first, count, nodeBase, idxBase, nodes, nodeCap, nNodes, primIdx, idxCap, nIdx, stats, err);
-    if (rc != RT_OK) g_herr = err;
-    return rc;
+    return build_bvh2([&](std::string& err) {
+        return SbvhBuildHost(alpha, prims, nPrims, first, count, nodeBase, idxBase, nodes, nodeCap, nNodes, primIdx, idxCap, nIdx, stats, err);
+    });
 }
 int rth_set_build_threads(RthScene* s, int threads) { if (!s) return -1; s->scene.bvh2->buildThreads = threads < 1 ? 1 : threads; return 0; }
 int rth_build_bvh4(RthScene* s) { GUARD(s->scene.BuildBVH4()) }

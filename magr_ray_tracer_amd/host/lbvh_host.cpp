@@ -89,8 +89,26 @@ int LbvhBuildHost(const RtBuildOptions* opt, const RtPrimitive* prims, int32_t n
     }
 }
 
-// BuildBLAS's bookkeeping (instance record, appended arrays, statistics) around the linear builder.  The scene is left unchanged
-// when the build is refused.
+// BuildBLAS's bookkeeping for a BLAS built elsewhere, rooted at nodeBase = bvhNodes.size(): instance record, appended arrays, statistics
+void BVH2::AppendBuiltBLAS(uint32_t nodeBase, const RtBVHNode2* nodes, size_t nN, const uint32_t* idx, size_t nI, float wall_ms, int32_t depth,
+                           float cost)
+{
+    RtBVHInstance inst;
+    memset(&inst, 0, sizeof inst);
+    inst.bvhIdx = nodeBase;
+    inst.invT[0] = inst.invT[5] = inst.invT[10] = inst.invT[15] = 1.0f;
+    blasNodes.push_back(inst);
+    bvhNodes.insert(bvhNodes.end(), nodes, nodes + nN);
+    primIdx.insert(primIdx.end(), idx, idx + nI);
+    nodesUsed_ = rootNodeIdx_ = (uint32_t)bvhNodes.size();
+    stat_build_time += wall_ms;
+    stat_node_count = nodesUsed_;
+    if ((uint32_t)depth > stat_depth) stat_depth = (uint32_t)depth;
+    stat_sah_cost += cost;
+    stat_prim_count = (uint32_t)primitives_.size();
+}
+
+// The linear builder, appended as BuildBLAS appends.  The scene is left unchanged when the build is refused.
 void BVH2::BuildBLASLBVH(int startIdx, int device, const RtBuildOptions* opt)
 {
     const int64_t n = (int64_t)primitives_.size() - startIdx;
@@ -108,19 +126,7 @@ void BVH2::BuildBLASLBVH(int startIdx, int device, const RtBuildOptions* opt)
         : rt_build_bvh2(device, opt, primitives_.data(), (int32_t)primitives_.size(), startIdx, (int32_t)n, nodeBase, idxBase, nodes.data(),
                         (int32_t)nodes.size(), &written, idx.data(), &st);
     if (rc != RT_OK) throw LbvhError(rc, device < 0 ? err : std::string(rt_last_error()));
-    RtBVHInstance inst;
-    memset(&inst, 0, sizeof inst);
-    inst.bvhIdx = nodeBase;
-    inst.invT[0] = inst.invT[5] = inst.invT[10] = inst.invT[15] = 1.0f;
-    blasNodes.push_back(inst);
-    bvhNodes.insert(bvhNodes.end(), nodes.begin(), nodes.begin() + written);
-    primIdx.insert(primIdx.end(), idx.begin(), idx.end());
-    nodesUsed_ = rootNodeIdx_ = (uint32_t)bvhNodes.size();
-    stat_build_time += st.wall_ms;
-    stat_node_count = nodesUsed_;
-    if ((uint32_t)st.depth > stat_depth) stat_depth = (uint32_t)st.depth;
-    stat_sah_cost += st.sah_cost;
-    stat_prim_count = (uint32_t)primitives_.size();
+    AppendBuiltBLAS(nodeBase, nodes.data(), (size_t)written, idx.data(), idx.size(), st.wall_ms, st.depth, st.sah_cost);
     lastLbvh = st;
 }
 

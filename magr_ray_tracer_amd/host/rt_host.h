@@ -93,6 +93,9 @@ public:
 private:
     using Refs = std::vector<BVHPrimData>;
     void  BuildBLASUnguarded(bool statistics, int startIdx);
+    // what BuildBLASLBVH / BuildBLASSAHGPU / BuildBLASSBVHGPU do once their build has succeeded (lbvh_host.cpp)
+    void  AppendBuiltBLAS(uint32_t nodeBase, const RtBVHNode2* nodes, size_t nN, const uint32_t* idx, size_t nI, float wall_ms, int32_t depth,
+                          float cost);
     void  BuildBVH(uint32_t root, Refs data);
     struct TNode;                                       // temporary pointer tree of the parallel build
     TNode* BuildSubtree(Refs refs, float rootArea, int depth, int& budget);

@@ -168,8 +168,7 @@ int SahBuildHost(const RtPrimitive* prims, int32_t nPrims, int32_t first, int32_
     }
 }
 
-// BuildBLAS's bookkeeping (instance record, appended arrays, statistics) around the GPU SAH build.  The scene is left unchanged
-// when the build is refused.
+// The GPU SAH build, appended as BuildBLAS appends (AppendBuiltBLAS).  The scene is left unchanged when the build is refused.
 void BVH2::BuildBLASSAHGPU(int startIdx, int device)
 {
     const int64_t n = (int64_t)primitives_.size() - startIdx;
@@ -187,19 +186,7 @@ void BVH2::BuildBLASSAHGPU(int startIdx, int device)
         : rt_build_bvh2_sah(device, primitives_.data(), (int32_t)primitives_.size(), startIdx, (int32_t)n, nodeBase, idxBase,
                             nodes.data(), (int32_t)nodes.size(), &written, idx.data(), &st);
     if (rc != RT_OK) throw LbvhError(rc, device < 0 ? err : std::string(rt_last_error()));
-    RtBVHInstance inst;
-    memset(&inst, 0, sizeof inst);
-    inst.bvhIdx = nodeBase;
-    inst.invT[0] = inst.invT[5] = inst.invT[10] = inst.invT[15] = 1.0f;
-    blasNodes.push_back(inst);
-    bvhNodes.insert(bvhNodes.end(), nodes.begin(), nodes.begin() + written);
-    primIdx.insert(primIdx.end(), idx.begin(), idx.end());
-    nodesUsed_ = rootNodeIdx_ = (uint32_t)bvhNodes.size();
-    stat_build_time += st.wall_ms;
-    stat_node_count = nodesUsed_;
-    if ((uint32_t)st.depth > stat_depth) stat_depth = (uint32_t)st.depth;
-    stat_sah_cost += st.sah_cost;
-    stat_prim_count = (uint32_t)primitives_.size();
+    AppendBuiltBLAS(nodeBase, nodes.data(), (size_t)written, idx.data(), idx.size(), st.wall_ms, st.depth, st.sah_cost);
 }
 
 } // namespace rt355

@@ -248,8 +248,7 @@ int SbvhBuildHost(float alpha, const RtPrimitive* prims, int32_t nPrims, int32_t
     return RT_OK;
 }
 
-// BuildBLAS's bookkeeping (instance record, appended arrays, statistics) around the GPU SBVH build.  The scene is left unchanged
-// when the build is refused.
+// The GPU SBVH build, appended as BuildBLAS appends (AppendBuiltBLAS).  The scene is left unchanged when the build is refused.
 void BVH2::BuildBLASSBVHGPU(int startIdx, float a, int device)
 {
     const int64_t n = (int64_t)primitives_.size() - startIdx;
@@ -279,20 +278,8 @@ void BVH2::BuildBLASSBVHGPU(int startIdx, float a, int device)
         }
     }
     if (rc != RT_OK) throw LbvhError(rc, device < 0 ? err : std::string(rt_last_error()));
-    RtBVHInstance inst;
-    memset(&inst, 0, sizeof inst);
-    inst.bvhIdx = nodeBase;
-    inst.invT[0] = inst.invT[5] = inst.invT[10] = inst.invT[15] = 1.0f;
-    blasNodes.push_back(inst);
-    bvhNodes.insert(bvhNodes.end(), nodes.begin(), nodes.begin() + nN);
-    primIdx.insert(primIdx.end(), idx.begin(), idx.begin() + nI);
-    nodesUsed_ = rootNodeIdx_ = (uint32_t)bvhNodes.size();
+    AppendBuiltBLAS(nodeBase, nodes.data(), (size_t)nN, idx.data(), (size_t)nI, st.wall_ms, st.depth, st.sah_cost);
     alpha = a;
-    stat_build_time += st.wall_ms;
-    stat_node_count = nodesUsed_;
-    if ((uint32_t)st.depth > stat_depth) stat_depth = (uint32_t)st.depth;
-    stat_sah_cost += st.sah_cost;
-    stat_prim_count = (uint32_t)primitives_.size();
     stat_spatial_splits += (uint32_t)st.spatial_splits;
     stat_prims_clipped += (uint32_t)st.prims_clipped;
     stat_forced_leaves += (uint32_t)st.forced_leaves;

@@ -279,30 +279,44 @@ class BuildError(RuntimeError):
         self.code = code
 
 
+def _build_args(prims, first, count, nodes, idx, node_cap=None, lengths=True):
+    """(primitive array, count, node_cap, nodes, idx) of a build_* call: nodes / idx are the caller's arrays, or new ones of node_cap
+    (default 2 * count - 1) and count records; their dtype, and with `lengths` their lengths, are checked."""
+    p = np.ascontiguousarray(prims, dtype=_lib.Primitive)
+    n = len(p) - int(first) if count is None else int(count)
+    cap = max(2 * n - 1, 1) if node_cap is None else int(node_cap)
+    nodes = np.zeros(max(cap, 1), _lib.BVHNode2) if nodes is None else nodes
+    idx = np.zeros(max(n, 1), np.uint32) if idx is None else idx
+    if nodes.dtype != _lib.BVHNode2 or idx.dtype != np.uint32 or (lengths and (len(nodes) < cap or len(idx) < max(n, 1))):
+        raise ValueError("nodes / idx: BVHNode2[node_cap] and uint32[count] arrays expected" if lengths else
+                         "nodes / idx: BVHNode2 and uint32 arrays expected")
+    return p, n, cap, nodes, idx
+
+
+def _build_call(host_fn, device_fn, device, *args):
+    """device_fn(device, *args) of the device library, or the host restatement host_fn(*args) of the host library when device is None.
+    Returns (rc, the message of the library that was called when it refused)."""
+    if device is None:
+        L = _lib.host_lib()
+        rc, msg = getattr(L, host_fn)(*args), L.rth_last_error
+    else:
+        L = _lib.device_lib()
+        rc, msg = getattr(L, device_fn)(int(device), *args), L.rt_last_error
+    return rc, (msg().decode() if rc != 0 else "")
+
+
 def build_lbvh(prims, first=0, count=None, device=None, node_base=0, idx_base=0, node_cap=None, **options):
     """The linear BVH builder on a primitive array (Primitive records): rt_build_bvh2 on HIP device `device`, or its host
     restatement (rth_build_bvh2_lbvh) when device is None.  Returns (nodes, primIdx, stats); raises BuildError (with .code, an RT_E_*
     value) when the call is refused.  node_cap defaults to what the call needs (2 * count - 1)."""
-    p = np.ascontiguousarray(prims, dtype=_lib.Primitive)
-    n = len(p) - int(first) if count is None else int(count)
-    cap = max(2 * n - 1, 1) if node_cap is None else int(node_cap)
-    nodes = np.zeros(max(cap, 1), _lib.BVHNode2)
-    idx = np.zeros(max(n, 1), np.uint32)
+    p, n, cap, nodes, idx = _build_args(prims, first, count, None, None, node_cap)
     st = np.zeros((), _lib.BuildStats)
     written = C.c_int32(0)
     opts = build_options(**options)
-    if device is None:
-        L = _lib.host_lib()
-        rc = L.rth_build_bvh2_lbvh(_lib.ptr(opts), _lib.ptr(p), len(p), int(first), n, int(node_base), int(idx_base), _lib.ptr(nodes), cap,
-                                   C.byref(written), _lib.ptr(idx), _lib.ptr(st))
-        msg = L.rth_last_error
-    else:
-        L = _lib.device_lib()
-        rc = L.rt_build_bvh2(int(device), _lib.ptr(opts), _lib.ptr(p), len(p), int(first), n, int(node_base), int(idx_base), _lib.ptr(nodes),
-                             cap, C.byref(written), _lib.ptr(idx), _lib.ptr(st))
-        msg = L.rt_last_error
+    rc, text = _build_call("rth_build_bvh2_lbvh", "rt_build_bvh2", device, _lib.ptr(opts), _lib.ptr(p), len(p), int(first), n, int(node_base),
+                           int(idx_base), _lib.ptr(nodes), cap, C.byref(written), _lib.ptr(idx), _lib.ptr(st))
     if rc != 0:
-        raise BuildError(rc, msg().decode())
+        raise BuildError(rc, text)
     return nodes[:written.value].copy(), idx[:n].copy(), _stats_dict(st)
 
 
@@ -311,27 +325,13 @@ def build_sah_gpu(prims, first=0, count=None, device=None, node_base=0, idx_base
     (rth_build_bvh2_sah) when device is None.  Returns (nodes, primIdx, stats); raises BuildError (with .code, an RT_E_* value) when
     the call is refused.  node_cap defaults to what the call needs (2 * count - 1).  nodes / idx: the caller's arrays to write into
     (at least node_cap / count records), e.g. pre-filled to see that a refused call leaves them alone."""
-    p = np.ascontiguousarray(prims, dtype=_lib.Primitive)
-    n = len(p) - int(first) if count is None else int(count)
-    cap = max(2 * n - 1, 1) if node_cap is None else int(node_cap)
-    nodes = np.zeros(max(cap, 1), _lib.BVHNode2) if nodes is None else nodes
-    idx = np.zeros(max(n, 1), np.uint32) if idx is None else idx
-    if nodes.dtype != _lib.BVHNode2 or len(nodes) < cap or idx.dtype != np.uint32 or len(idx) < max(n, 1):
-        raise ValueError("nodes / idx: BVHNode2[node_cap] and uint32[count] arrays expected")
+    p, n, cap, nodes, idx = _build_args(prims, first, count, nodes, idx, node_cap)
     st = np.zeros((), _lib.BuildStats)
     written = C.c_int32(0)
-    if device is None:
-        L = _lib.host_lib()
-        rc = L.rth_build_bvh2_sah(_lib.ptr(p), len(p), int(first), n, int(node_base), int(idx_base), _lib.ptr(nodes), cap,
-                                  C.byref(written), _lib.ptr(idx), _lib.ptr(st))
-        msg = L.rth_last_error
-    else:
-        L = _lib.device_lib()
-        rc = L.rt_build_bvh2_sah(int(device), _lib.ptr(p), len(p), int(first), n, int(node_base), int(idx_base), _lib.ptr(nodes), cap,
-                                 C.byref(written), _lib.ptr(idx), _lib.ptr(st))
-        msg = L.rt_last_error
+    rc, text = _build_call("rth_build_bvh2_sah", "rt_build_bvh2_sah", device, _lib.ptr(p), len(p), int(first), n, int(node_base), int(idx_base),
+                           _lib.ptr(nodes), cap, C.byref(written), _lib.ptr(idx), _lib.ptr(st))
     if rc != 0:
-        raise BuildError(rc, msg().decode())
+        raise BuildError(rc, text)
     return nodes[:written.value].copy(), idx[:n].copy(), _stats_dict(st)
 
 
@@ -345,29 +345,15 @@ def build_sbvh_gpu(prims, alpha, first=0, count=None, device=None, node_base=0, 
     an RT_E_* value, and .needed = (nodes, primIdx entries) after a capacity refusal) when the call is refused.  Without nodes / idx
     the call starts with 2 * count - 1 nodes and count indices and, told that the tree is larger, calls once more with the sizes it
     was given.  nodes / idx: the caller's arrays to write into; their lengths are the capacities, and there is no second call."""
-    p = np.ascontiguousarray(prims, dtype=_lib.Primitive)
-    n = len(p) - int(first) if count is None else int(count)
     own = nodes is None and idx is None
-    nodes = np.zeros(max(2 * n - 1, 1), _lib.BVHNode2) if nodes is None else nodes
-    idx = np.zeros(max(n, 1), np.uint32) if idx is None else idx
-    if nodes.dtype != _lib.BVHNode2 or idx.dtype != np.uint32:
-        raise ValueError("nodes / idx: BVHNode2 and uint32 arrays expected")
+    p, n, _, nodes, idx = _build_args(prims, first, count, nodes, idx, lengths=False)
     st = np.zeros((), _lib.SbvhStats)
     for attempt in (0, 1):
         nn, ni = C.c_int32(0), C.c_int32(0)
-        if device is None:
-            L = _lib.host_lib()
-            rc = L.rth_build_bvh2_sbvh(float(alpha), _lib.ptr(p), len(p), int(first), n, int(node_base), int(idx_base), _lib.ptr(nodes), len(nodes),
-                                       C.byref(nn), _lib.ptr(idx), len(idx), C.byref(ni), _lib.ptr(st))
-            msg = L.rth_last_error
-        else:
-            L = _lib.device_lib()
-            rc = L.rt_build_bvh2_sbvh(int(device), float(alpha), _lib.ptr(p), len(p), int(first), n, int(node_base), int(idx_base), _lib.ptr(nodes),
-                                      len(nodes), C.byref(nn), _lib.ptr(idx), len(idx), C.byref(ni), _lib.ptr(st))
-            msg = L.rt_last_error
+        rc, text = _build_call("rth_build_bvh2_sbvh", "rt_build_bvh2_sbvh", device, float(alpha), _lib.ptr(p), len(p), int(first), n, int(node_base),
+                               int(idx_base), _lib.ptr(nodes), len(nodes), C.byref(nn), _lib.ptr(idx), len(idx), C.byref(ni), _lib.ptr(st))
         if rc == 0:
             return nodes[:nn.value].copy(), idx[:ni.value].copy(), _sbvh_stats_dict(st)
-        text = msg().decode()
         if own and attempt == 0 and rc == _lib.RT_E_INVALID and "capacity" in text:
             nodes, idx = np.zeros(nn.value, _lib.BVHNode2), np.zeros(ni.value, np.uint32)
             continue
