@@ -245,7 +245,10 @@ int rt_update_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t first, int32_t
  * the device over its own primitive range, in increasing order of the ranges and numbered the way the host appends BLAS after BLAS
  * (nodeBase of BLAS k = the nodes of BLAS 0..k-1, idxBase likewise), with
  *   RT_REBUILD_SAH   rt_build_bvh2_sah's tree (BVH2::BuildBLAS, alpha 1; opts ignored), or
- *   RT_REBUILD_LBVH  rt_build_bvh2's tree (opts as there, NULL = defaults);
+ *   RT_REBUILD_LBVH  rt_build_bvh2's tree (opts as there, NULL = defaults), or
+ *   RT_REBUILD_SBVH  rt_build_bvh2_sbvh's tree (BVH2::BuildBLAS with bvh2->alpha = opts->alpha, spatial splits; opts NULL or
+ *                    zero-filled: alpha 0, the full SBVH; the other words of opts are ignored, as alpha is by the other builders):
+ *                    the way back to an SBVH for a scene bound as one, whose refits lose the clipped leaf boxes;
  * every instance's bvhIdx becomes its BLAS's new root, the TLAS is rebuilt by TLAS::Build's rules and every derived array is
  * produced on the device.  No node, index or record array crosses the bus; the host reads the few words per build step the builders
  * read anyway, plus counts, depths and status.  Afterwards the arrays rt_debug_get_scene_array returns, their sizes included, are
@@ -254,20 +257,34 @@ int rt_update_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t first, int32_t
  * waits for the streams of every context holding the scene (as rt_update_scene does); each holder takes the new arrays, stack size
  * and traversal kernels before its next launch.  rt_update_scene works on the rebuilt scene (instance records handed to later calls
  * carry the new bvhIdx: RT_SCENE_INSTANCES, or the host restatement's).  Synchronous; accumulators are not
- * reset.  The first two rebuilds of a scene copy allocate (two sets of the arrays at capacity, which later rebuilds alternate
- * between); the copy uploaded originally stays allocated beside them until the scene copy is freed.
+ * reset.  The first two rebuilds of a scene copy allocate two sets of the arrays, which later rebuilds alternate between; the copy
+ * uploaded originally stays allocated beside them until the scene copy is freed.  What scales with the trees (nodes, primIdx, pair
+ * and triangle records, the refit topology, the derivation's scratch) starts with room for nPrims index slots and 2 * nPrims nodes,
+ * which bounds every tree of the first two builders.  A spatial split duplicates refs, so an SBVH tree has no such bound: every BLAS
+ * is built in the builder's own memory first (one tree at a time), and when the running totals outgrow the set that is not live its
+ * arrays go to the need plus a quarter, device to device, what was emitted so far is kept and the arrays replaced are freed at once;
+ * the live set is never touched.  The builder's own memory is kept from rebuild to rebuild, so a scene whose tree sizes are stable is
+ * rebuilt without any device allocation once both sets have grown (rt_debug_rebuild_allocations counts them).  rt_update_scene's
+ * staging nodes grow the same way.  The environment variable RT355_REBUILD_INITIAL_CAP=k, read per call, makes what is allocated
+ * afterwards start at k index slots and 2 * k nodes (for tests and A/B runs: a small k runs every growth path).
  * Refusals change nothing (the work is staged in the set that is not live; the bound scene renders exactly as before):
- *   RT_E_INVALID      what rt_update_scene answers with it, an unknown builder, bad opts (the builder's own argument checks);
+ *   RT_E_INVALID      what rt_update_scene answers with it, an unknown builder, bad opts (the builder's own argument checks; for
+ *                     RT_REBUILD_SBVH an alpha outside [0, 1], NaN included), all before any device work;
+ *   RT_E_NOMEM        device memory, for the sets, a grown set or the SBVH builder's ref arrays (a later call takes the allocation
+ *                     up where it stopped);
  *   RT_E_UNSUPPORTED  a BVH4 context; a scene whose BLAS do not each cover one contiguous primitive range, ranges disjoint and in the
  *                     order of their roots (found at rt_upload_scene; rt_blas_ranges tells beforehand), more than 256 instances or
- *                     a TLAS not of TLAS::Build's shape; whatever the builder refuses on these primitives (rt_build_bvh2_sah);
+ *                     a TLAS not of TLAS::Build's shape; whatever the builder refuses on these primitives (rt_build_bvh2_sah,
+ *                     rt_build_bvh2_sbvh: a non-finite box, an undefined spatial bin index, ...);
  *                     a new BLAS that needs more than RT_BVH4_STACK stack entries (the SAH builder makes a tree 65 levels deep
  *                     out of thin triangles on a geometric ladder over 190 octaves; rth_rebuild refuses it by the same rule); a rebuilt TLAS deeper than RT_TLAS_STACK; and
  *                     new trees that would change the scene's derived layout (RtKernelInfo.layout: a leaf of more than 127
- *                     primitives - the SAH builder makes one out of 128 coincident triangles - takes layout 0 at upload).
+ *                     primitives - the SAH builder makes one out of 128 coincident triangles - takes layout 0 at upload, and so
+ *                     do 2^24 index slots or more, which an SBVH rebuild can reach with fewer primitives).
  *                     Not following a layout change is a deliberate limit: upload the rebuilt scene in that case. */
 #define RT_REBUILD_SAH   0
 #define RT_REBUILD_LBVH  1
+#define RT_REBUILD_SBVH  2
 typedef struct RtRebuildStats {
     double  gpu_ms;               /* from the first to the last GPU operation of the rebuild on its stream                     */
     double  wall_ms;              /* the whole call                                                                            */
@@ -280,10 +297,13 @@ typedef struct RtRebuildStats {
     int32_t max_depth;            /* height of the deepest new BLAS (edges)                                                    */
     int32_t tlas_nodes, tlas_depth;
     int32_t reconfigured;         /* 1: the stack size or the TLAS depth changed (the holders always take the new arrays)      */
-    int32_t reserved[2];
+    int32_t spatial_splits, prims_clipped;   /* RT_REBUILD_SBVH: BVH2::stat_* summed over the BLAS built (0 for the other builders) */
 } RtRebuildStats;
 int rt_rebuild_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
                      int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats);
+/* Device allocations (hipMalloc calls) that rt_update_scene and rt_rebuild_scene have made for the context's scene copy so far, the
+ * SBVH builder's included: a test can see that a repeated rebuild has stopped allocating. */
+int rt_debug_rebuild_allocations(RtCtx* ctx, int64_t* count);
 /* The primitive range [first, first + count) of every instance's BLAS in wire arrays, as rt_upload_scene finds them for
  * rt_rebuild_scene (csrc/rebuild_common.h); firstOut / countOut hold nBlas entries (either may be NULL).  RT_E_UNSUPPORTED with the
  * reason in rt_last_error() when the scene is not of the shape rt_rebuild_scene takes.  No device needed. */

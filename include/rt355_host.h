@@ -78,8 +78,10 @@ int rth_set_primitives(RthScene* s, int first, int count, const RtPrimitive* pri
 int rth_refit(RthScene* s);
 /* The host restatement of rt_rebuild_scene's BLAS rebuild (rt355.h): discards the scene's BVH2 and builds every distinct BLAS again
  * over the primitive range it covers (in increasing order of the ranges, appended as BuildBLAS appends BLAS after BLAS) with the host
- * restatement of the chosen builder: RT_REBUILD_SAH (rth_build_bvh2_sah; opts ignored) or RT_REBUILD_LBVH (rth_build_bvh2_lbvh, opts
- * NULL = defaults).  Instance transforms stay, every bvhIdx becomes its BLAS's new root.  The caller then runs rth_build_tlas (and
+ * restatement of the chosen builder: RT_REBUILD_SAH (rth_build_bvh2_sah; opts ignored), RT_REBUILD_LBVH (rth_build_bvh2_lbvh, opts
+ * NULL = defaults) or RT_REBUILD_SBVH (rth_build_bvh2_sbvh with opts->alpha, NULL or zero-filled = 0; alpha outside [0, 1] is
+ * RT_E_INVALID; every BLAS appends the nodes and indices its tree turned out to have, and the scene's spatial-split, clipped-primitive
+ * and forced-leaf statistics become the sums).  Instance transforms stay, every bvhIdx becomes its BLAS's new root.  The caller then runs rth_build_tlas (and
  * rth_build_bvh4).  Returns RT_E_* and changes nothing when refused (a scene whose BLAS do not cover contiguous, disjoint, ordered
  * ranges; whatever the builder refuses). */
 int rth_rebuild(RthScene* s, int builder, const RtBuildOptions* opts);

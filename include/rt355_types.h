@@ -132,12 +132,14 @@ typedef struct RtTLASNode {
 } RtTLASNode;
 
 /* Options and statistics of the linear BVH builder (rt_build_bvh2 in rt355.h, rth_build_bvh2_lbvh / rth_build_blas_lbvh in
- * rt355_host.h).  Not part of the reference's wire format. */
+ * rt355_host.h); rt_rebuild_scene / rth_rebuild take the same record for every builder, and read `alpha` for RT_REBUILD_SBVH only.
+ * Not part of the reference's wire format. */
 typedef struct RtBuildOptions {
     int32_t max_leaf;            /* largest leaf the SAH collapse may form: RT_MIN_LEAF_PRIMS..127 (default 8)           */
     float   cost_traverse;       /* C_t: cost of an interior node per unit of its area (default 1)                      */
     float   cost_intersect;      /* C_i: cost of one primitive test per unit of its leaf's area (default 1)             */
-    int32_t _reserved;
+    float   alpha;               /* RT_REBUILD_SBVH only: bvh2->alpha in [0, 1], 0 (a zero-filled record) = the full SBVH;   */
+                                 /* the other builders and rt_build_bvh2 ignore the word (it used to be reserved)            */
 } RtBuildOptions;
 typedef struct RtBuildStats {
     int32_t nodes, leaves, depth;  /* node records written (2 * leaves - 1), leaves, height in edges (BVH2::Depth)       */
@@ -174,7 +176,7 @@ RT_STATIC_ASSERT(sizeof(RtSettings) == 40 && offsetof(RtSettings, numInRays) == 
 RT_STATIC_ASSERT(sizeof(RtBVHNode2) == 48 && offsetof(RtBVHNode2, first) == 32, "BVHNode2 layout");
 RT_STATIC_ASSERT(sizeof(RtBVHNode4) == 160 && offsetof(RtBVHNode4, first) == 128 && offsetof(RtBVHNode4, count) == 144, "BVHNode4 layout");
 RT_STATIC_ASSERT(sizeof(RtBVHInstance) == 68 && offsetof(RtBVHInstance, invT) == 4, "BVHInstance layout");
-RT_STATIC_ASSERT(sizeof(RtBuildOptions) == 16 && sizeof(RtBuildStats) == 32, "build options / stats layout");
+RT_STATIC_ASSERT(sizeof(RtBuildOptions) == 16 && offsetof(RtBuildOptions, alpha) == 12 && sizeof(RtBuildStats) == 32, "build options / stats layout");
 RT_STATIC_ASSERT(sizeof(RtSbvhStats) == 48, "SBVH build stats layout");
 RT_STATIC_ASSERT(sizeof(RtTLASNode) == 48 && offsetof(RtTLASNode, leftRight) == 32 && offsetof(RtTLASNode, BLASidx) == 36, "TLASNode layout");
 

@@ -46,7 +46,7 @@ Config = np.dtype([(n, "<i4") for n in ("width", "height", "y0", "y1", "max_boun
                                          "shade_blocks_per_cu", "persist_blocks_per_cu")] +
                   [("builtins", "<i4")])   # RT_BUILTINS_* (byte 60)
 
-BuildOptions = np.dtype([("max_leaf", "<i4"), ("cost_traverse", "<f4"), ("cost_intersect", "<f4"), ("_reserved", "<i4")])
+BuildOptions = np.dtype([("max_leaf", "<i4"), ("cost_traverse", "<f4"), ("cost_intersect", "<f4"), ("alpha", "<f4")])   # alpha: RT_REBUILD_SBVH only
 BuildStats = np.dtype([("nodes", "<i4"), ("leaves", "<i4"), ("depth", "<i4"), ("morton_bits", "<i4"), ("sah_cost", "<f4"),
                        ("device_ms", "<f4"), ("wall_ms", "<f4"), ("_reserved", "<i4")])
 SbvhStats = np.dtype([(n, "<i4") for n in ("nodes", "leaves", "n_idx", "depth", "spatial_splits", "prims_clipped", "forced_leaves", "levels")] +
@@ -90,10 +90,10 @@ SCENE_ARRAYS = {"prims": 0, "bvh": 1, "tlas": 2, "instances": 3, "pairs": 4, "tr
 UpdateStats = np.dtype([("gpu_ms", "<f8"), ("prims", "<i4"), ("nodes", "<i4"), ("tlas_nodes", "<i4"), ("tlas_depth", "<i4"),
                         ("reconfigured", "<i4"), ("reserved", "<i4", 3)])
 assert UpdateStats.itemsize == 40
-REBUILD_SAH, REBUILD_LBVH = 0, 1   # rt_rebuild_scene builders
+REBUILD_SAH, REBUILD_LBVH, REBUILD_SBVH = 0, 1, 2   # rt_rebuild_scene builders
 RebuildStats = np.dtype([(n, "<f8") for n in ("gpu_ms", "wall_ms", "stage_ms", "build_ms", "derive_ms", "tlas_ms", "commit_ms")] +
                         [(n, "<i4") for n in ("prims", "blas_built", "nodes", "n_idx", "max_depth", "tlas_nodes", "tlas_depth", "reconfigured")] +
-                        [("reserved", "<i4", 2)])
+                        [("spatial_splits", "<i4"), ("prims_clipped", "<i4")])
 assert RebuildStats.itemsize == 96
 
 DEVICE_SYMBOLS = [
@@ -103,7 +103,7 @@ DEVICE_SYMBOLS = [
     "rt_stage_begin_frame", "rt_stage_generate", "rt_stage_extend", "rt_stage_shade", "rt_stage_connect",
     "rt_debug_get_rays", "rt_debug_set_rays", "rt_debug_get_shadow", "rt_debug_enable_steps", "rt_debug_get_steps", "rt_debug_math",
     "rt_debug_math_sweep", "rt_debug_math_mode", "rt_debug_math_sweep_mode", "rt_validate_scene", "rt_build_bvh2", "rt_build_bvh2_sah", "rt_debug_sah_phases", "rt_build_bvh2_sbvh", "rt_debug_sbvh_phases", "rt_update_scene", "rt_group_update_scene", "rt_debug_get_scene_array",
-    "rt_rebuild_scene", "rt_group_rebuild_scene", "rt_blas_ranges",
+    "rt_rebuild_scene", "rt_group_rebuild_scene", "rt_blas_ranges", "rt_debug_rebuild_allocations",
     "rt_group_create", "rt_group_destroy", "rt_group_lanes", "rt_group_concurrency", "rt_group_lane", "rt_group_frames", "rt_group_upload_scene", "rt_group_share_scene",
     "rt_group_seed", "rt_group_reset", "rt_group_render", "rt_group_synchronize", "rt_group_sum", "rt_group_read_accum", "rt_group_focus",
     "rt_group_postproc"]
@@ -210,6 +210,7 @@ def _bind_device(lib):
         lib.rt_debug_get_scene_array.argtypes = [vp, i32, vp, i64, C.POINTER(i64)]
         lib.rt_rebuild_scene.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp, vp]
         lib.rt_group_rebuild_scene.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp, vp]
+        lib.rt_debug_rebuild_allocations.argtypes = [vp, vp]
         lib.rt_blas_ranges.argtypes = [vp, i32, vp, i32, i32, vp, i32, vp, vp]
         lib.rt_group_create.argtypes = [vp, i32, C.POINTER(vp)]
         lib.rt_group_destroy.argtypes = [vp]

@@ -42,9 +42,11 @@ int build(const char* who, hipStream_t stream, void* work, const lbvh::Params& P
 // The SBVH builder (sbvh.hip, rules in sbvh_common.h).  A spatial split duplicates refs, so the size of the tree is known only after
 // it is built: build() leaves the numbered tree on the device (its own allocations, grown level by level; RT_E_NOMEM when one fails)
 // and reports the sizes, emit() then writes the records and primIdx into arrays of built.nodes / built.nIdx entries.  This is the
-// shape an in-place rebuild with an SBVH builder needs (size, then place); rt_rebuild_scene does not use it yet.  The caller has
-// checked the arguments (sbvh::check_args) and set the device; *tree is set whenever build() got that far and is destroyed by the
-// caller, after a failure too.  The stream is idle when either returns.
+// shape an in-place rebuild with an SBVH builder needs (size, then place): rt_rebuild_scene builds, grows the scene's arrays to the
+// sizes if it must, emits and destroys, BLAS by BLAS.  The caller has checked the arguments (sbvh::check_args) and set the device;
+// *tree is set whenever build() got that far and is destroyed by the caller, after a failure too.  The stream is idle when either
+// returns.  `pool` (may be NULL: hipMalloc / hipFree) keeps the device blocks of a build for the next one: a caller that builds the
+// same sizes again allocates nothing; one pool serves one stream, and outlives every tree built from it.
 struct SbvhBuilt {
     uint32_t nodes, leaves, nIdx, depth;                     // records, leaves, primIdx entries, BVH2::Depth
     uint32_t spatialSplits, primsClipped, forcedLeaves;      // as BVH2::stat_* count them
@@ -54,8 +56,12 @@ struct SbvhBuilt {
 };
 namespace sbvhdev {
 struct Tree;
+struct Pool;
+Pool* pool_create();
+void pool_destroy(Pool* pool);
+uint64_t pool_allocations(const Pool* pool);                 // hipMalloc calls so far
 int build(const char* who, hipStream_t stream, float alpha, const RtPrimitive* dPrims, uint32_t n, uint32_t first, uint32_t nodeBase,
-          uint32_t idxBase, hipEvent_t evBegin, hipEvent_t evEnd, Tree** tree, SbvhBuilt* out);
+          uint32_t idxBase, hipEvent_t evBegin, hipEvent_t evEnd, Pool* pool, Tree** tree, SbvhBuilt* out);
 int emit(const char* who, hipStream_t stream, Tree* tree, RtBVHNode2* dNodes, uint32_t* dIdx);
 void destroy(Tree* tree);
 }

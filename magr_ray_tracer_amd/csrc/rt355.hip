@@ -61,7 +61,7 @@ struct SceneBag {
     // staging of an update (allocated by the first one): nothing live is written before the new TLAS has passed
     RtPrimitive* sPrims = nullptr; RtBVHNode2* sNodes = nullptr; RtBVHInstance* sInst = nullptr; RtTLASNode* sTlas = nullptr;
     RtFloat4 *sTp = nullptr, *sTpP = nullptr, *sIr = nullptr; int32_t* sStatus = nullptr;
-    size_t sNodesCap = 0;                     // records sNodes holds (a rebuild changes the node count)
+    size_t sNodesCap = 0;                     // records sNodes holds (a rebuild changes the node count; grown by update_scene)
     hipStream_t stream = nullptr;             // where updates run
     hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };   // brackets of the staging and of the commit
     // rt_rebuild_scene: what it needs of the upload, and its device memory (allocated by the first rebuilds, then reused)
@@ -70,14 +70,24 @@ struct SceneBag {
     std::vector<int32_t> instBlas;            // instance -> its range
     bool variantLayout1 = false;              // the holders' extend_variant admits the derived layout 1
     int stackEntries = RT_BVH2_STACK, nInterior = 0;   // what the holders take over after a rebuild (sync_scene_config)
-    // Everything a rebuild changes, twice at capacity (2 * nPrims nodes, nPrims indices bound every tree of both builders): a rebuild
-    // writes the set that is not live and the commit swaps the pointers; the upload's own arrays stay behind until the copy is freed.
+    // Everything a rebuild changes, twice: a rebuild writes the set that is not live and the commit swaps the pointers; the upload's own
+    // arrays stay behind until the copy is freed.  The arrays that scale with the primitives are made once.  Those that scale with the
+    // trees (Grown) have capacities of their own: nPrims index slots and 2 * nPrims nodes at first, which bounds every tree of the SAH
+    // and the linear builder; an SBVH tree has no such bound, so the set that is not live grows to what the finished trees need plus a
+    // quarter (kRebuildHeadroomDiv, rebuild_reserve), what was emitted so far is kept and the arrays it replaces are freed at once.
+    template <class T> struct Grown { T* p = nullptr; size_t cap = 0; };
     struct RebuildSet {
         bool allocated = false;
-        RtPrimitive* prims = nullptr; RtBVHNode2* nodes = nullptr; uint32_t* primIdx = nullptr; RtBVHInstance* blas = nullptr; RtTLASNode* tlas = nullptr;
-        RtFloat4 *tp = nullptr, *tpP = nullptr, *ir = nullptr, *pairs = nullptr, *triRecs = nullptr, *shadeRecs = nullptr, *lightRecs = nullptr;
-        uint32_t *rootEntry = nullptr, *parent = nullptr, *leaves = nullptr, *tickets = nullptr, *pairNode = nullptr;
+        RtPrimitive* prims = nullptr; RtBVHInstance* blas = nullptr; RtTLASNode* tlas = nullptr;
+        RtFloat4 *tp = nullptr, *tpP = nullptr, *ir = nullptr, *shadeRecs = nullptr, *lightRecs = nullptr;
+        uint32_t* rootEntry = nullptr;
+        Grown<uint32_t> primIdx; Grown<RtFloat4> triRecs;                                    // index slots (triRecs: 3 per slot)
+        Grown<RtBVHNode2> nodes; Grown<uint32_t> parent, tickets;                            // nodes
+        Grown<RtFloat4> pairs; Grown<uint32_t> leaves, pairNode;                             // nodes / 2 (pairs: 4 per interior node)
     } rset[2];
+    Grown<uint32_t> dwFlags, dwRanks, dwNewId, dwFrontA, dwFrontB; Grown<char> dwScan;   // the derivation's scratch, grown likewise
+    sbvhdev::Pool* spool = nullptr;           // the SBVH builder's device blocks, kept from rebuild to rebuild
+    uint64_t rallocs = 0;                     // device allocations by updates and rebuilds of this copy (rt_debug_rebuild_allocations)
     int rnext = 0;                            // the set the next rebuild writes
     void* rwork = nullptr; size_t rworkBytes = 0;   // the builders' workspace (grown on demand)
     rebuilddev::Work dw{};                    // scratch of the derivation
@@ -90,6 +100,12 @@ struct SceneBag {
         for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : rev) if (e) (void)hipEventDestroy(e);
         if (rwork) (void)hipFree(rwork);
+        if (sNodes) (void)hipFree(sNodes);
+        sbvhdev::pool_destroy(spool);
+        for (RebuildSet& t : rset)
+            for (void* p : { (void*)t.primIdx.p, (void*)t.triRecs.p, (void*)t.nodes.p, (void*)t.parent.p, (void*)t.tickets.p, (void*)t.pairs.p,
+                             (void*)t.leaves.p, (void*)t.pairNode.p }) if (p) (void)hipFree(p);
+        for (void* p : { (void*)dwFlags.p, (void*)dwRanks.p, (void*)dwNewId.p, (void*)dwFrontA.p, (void*)dwFrontB.p, (void*)dwScan.p }) if (p) (void)hipFree(p);
         for (void* p : allocs) (void)hipFree(p);
     }
 };
@@ -956,6 +972,21 @@ static int sync_scene_config(RtCtx* ctx)
 
 template <class T> static T* mut(const T* p) { return const_cast<T*>(p); }   // the scene's own allocations, read-only for the renderers
 
+// Capacities of what scales with the trees (SceneBag::RebuildSet, the derivation's scratch, rt_update_scene's staging nodes): index
+// slots at first, twice as many nodes; RT355_REBUILD_INITIAL_CAP=k (read per call; tests, A/B runs) starts smaller or larger.  An array
+// that a finished tree outgrows goes to the need plus need / kRebuildHeadroomDiv: a quarter covers the frame-to-frame drift of an
+// animated SBVH scene (its slot count moved by a few percent between the deformations tried), so a per-frame rebuild stops allocating
+// once both sets have grown, and costs at most that much idle memory.
+constexpr size_t kRebuildHeadroomDiv = 4;
+static size_t rebuild_initial_cap(const SceneBag& b)
+{
+    if (const char* env = getenv("RT355_REBUILD_INITIAL_CAP")) {
+        const long long k = atoll(env);
+        if (k > 0) return (size_t)std::min<long long>(k, 1ll << 30);
+    }
+    return (size_t)std::max(b.nPrims, 1);
+}
+
 static int update_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
                         RtUpdateStats* stats)
 {
@@ -981,8 +1012,6 @@ static int update_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, in
     // ---- staging buffers (first update)
     if (!b.sPrims) {
         int rc = dalloc(b.allocs, &b.sPrims, (size_t)b.nPrims);
-        b.sNodesCap = (size_t)std::max(b.nNodes, 2 * b.nPrims);   // (room for every tree a rebuild can bind later)
-        if (rc == RT_OK) rc = dalloc(b.allocs, &b.sNodes, b.sNodesCap);
         if (rc == RT_OK) rc = dalloc(b.allocs, &b.sInst, (size_t)b.nBlas);
         if (rc == RT_OK) rc = dalloc(b.allocs, &b.sTlas, (size_t)b.nTlas);
         if (rc == RT_OK) rc = dalloc(b.allocs, &b.sTp, (size_t)b.nTlas * 4);
@@ -990,8 +1019,19 @@ static int update_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, in
         if (rc == RT_OK) rc = dalloc(b.allocs, &b.sIr, (size_t)b.nBlas * 4);
         if (rc == RT_OK) rc = dalloc(b.allocs, &b.sStatus, 2);
         if (rc != RT_OK) { b.sPrims = nullptr; return rc; }
+        b.rallocs += 7;
         if (!b.stream) HIPCHK(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));   // (a rebuild may have made it already)
         for (hipEvent_t& e : b.ev) if (!e) HIPCHK(hipEventCreate(&e));
+    }
+    if (!b.sNodes || (size_t)b.nNodes > b.sNodesCap) {
+        // the staging nodes: at first room for every tree the SAH and the linear builder can bind later; an SBVH rebuild may bind more
+        // nodes than that, then the array grows as the rebuild's sets do (nothing in it outlives a call)
+        const size_t n = (size_t)b.nNodes, cap = b.sNodes ? n + n / kRebuildHeadroomDiv : std::max(n, 2 * rebuild_initial_cap(b));
+        HIPCHK(hipStreamSynchronize(b.stream));
+        if (b.sNodes) (void)hipFree(b.sNodes);
+        b.sNodes = nullptr; b.sNodesCap = 0;
+        if (hipMalloc((void**)&b.sNodes, cap * sizeof(RtBVHNode2)) != hipSuccess) { b.sNodes = nullptr; return fail(RT_E_NOMEM, "rt_update_scene: %zu staging nodes", cap); }
+        b.sNodesCap = cap; b.rallocs++;
     }
     const DevScene& sc = b.sc;
     hipStream_t s = b.stream;
@@ -1057,26 +1097,80 @@ extern "C" int rt_group_update_scene(RtGroup* g, const RtPrimitive* prims, int32
     if (!g) return fail(RT_E_INVALID, "rt_group_update_scene: null group");
     return rt_update_scene(rt_group_lane(g, 0), prims, first, count, blas, nBlas, stats);   // every lane holds lane 0's copy
 }
-// ---- in-place rebuilds (rt_rebuild_scene; builders: sah.hip / lbvh.hip, derivation: rebuild.hip, rules: rebuild_common.h) ----------
+// ---- in-place rebuilds (rt_rebuild_scene; builders: sah.hip / lbvh.hip / sbvh.hip, derivation: rebuild.hip, rules: rebuild_common.h) ----
+// An array of a rebuild set or of the scratch to at least `count` records, keeping the first `keep`; the array it replaces is freed here
+template <class T> static int rebuild_grow(SceneBag& b, SceneBag::Grown<T>& a, size_t count, size_t keep, const char* what)
+{
+    if (count <= a.cap && a.p) return RT_OK;
+    count = std::max<size_t>(count, 1);
+    void* q = nullptr;
+    if (hipMalloc(&q, count * sizeof(T)) != hipSuccess) return fail(RT_E_NOMEM, "rt_rebuild_scene: %zu bytes of device memory for %s", count * sizeof(T), what);
+    b.rallocs++;
+    if (a.p) {
+        hipError_t e = keep ? hipMemcpyAsync(q, a.p, keep * sizeof(T), hipMemcpyDeviceToDevice, b.stream) : hipSuccess;
+        if (e == hipSuccess) e = hipStreamSynchronize(b.stream);
+        if (e != hipSuccess) { (void)hipFree(q); return fail(RT_E_DEVICE, "rt_rebuild_scene: moving %s failed: %s", what, hipGetErrorString(e)); }
+        (void)hipFree(a.p);
+    }
+    a.p = (T*)q; a.cap = count;
+    return RT_OK;
+}
+// Room in the set `t` (not live) for idxNeed index slots and nodeNeed nodes, keeping the keepIdx slots and keepNodes records emitted so
+// far.  An array that is too small goes to the need plus kRebuildHeadroomDiv-th of it; one that NOMEM stopped is taken up by a later call.
+static int rebuild_reserve(SceneBag& b, SceneBag::RebuildSet& t, size_t idxNeed, size_t nodeNeed, size_t keepIdx, size_t keepNodes)
+{
+    const bool have = t.nodes.p != nullptr;   // (the first allocation is exact: the initial capacity)
+    const size_t idxCap = idxNeed <= t.primIdx.cap ? t.primIdx.cap : idxNeed + (have ? idxNeed / kRebuildHeadroomDiv : 0);
+    size_t nodeCap = nodeNeed <= t.nodes.cap ? t.nodes.cap : nodeNeed + (have ? nodeNeed / kRebuildHeadroomDiv : 0);
+    nodeCap = (nodeCap + 1) & ~(size_t)1;
+    int rc = rebuild_grow(b, t.primIdx, idxCap, keepIdx, "primIdx");
+    if (rc == RT_OK) rc = rebuild_grow(b, t.nodes, nodeCap, keepNodes, "nodes");
+    if (rc == RT_OK) rc = rebuild_grow(b, t.triRecs, idxCap * 3, 0, "triangle records");
+    if (rc == RT_OK) rc = rebuild_grow(b, t.parent, nodeCap, 0, "parent links");
+    if (rc == RT_OK) rc = rebuild_grow(b, t.tickets, nodeCap, 0, "tickets");
+    if (rc == RT_OK) rc = rebuild_grow(b, t.pairs, std::max<size_t>(nodeCap / 2, 1) * 4, 0, "pair records");
+    if (rc == RT_OK) rc = rebuild_grow(b, t.leaves, nodeCap / 2, 0, "leaves");
+    if (rc == RT_OK) rc = rebuild_grow(b, t.pairNode, nodeCap / 2, 0, "pair nodes");
+    return rc;
+}
+// The derivation's scratch for trees of nodeNeed nodes in all (flags / ranks / newId: a word per node, the frontiers: per interior node)
+static int rebuild_scratch(SceneBag& b, size_t nodeNeed)
+{
+    const bool have = b.dwFlags.p != nullptr;
+    size_t cap = nodeNeed <= b.dwFlags.cap ? b.dwFlags.cap : nodeNeed + (have ? nodeNeed / kRebuildHeadroomDiv : 0);
+    cap = (cap + 1) & ~(size_t)1;
+    int rc = rebuild_grow(b, b.dwFlags, cap, 0, "scratch");
+    if (rc == RT_OK) rc = rebuild_grow(b, b.dwRanks, cap, 0, "scratch");
+    if (rc == RT_OK) rc = rebuild_grow(b, b.dwNewId, cap, 0, "scratch");
+    if (rc == RT_OK) rc = rebuild_grow(b, b.dwFrontA, cap / 2, 0, "scratch");
+    if (rc == RT_OK) rc = rebuild_grow(b, b.dwFrontB, cap / 2, 0, "scratch");
+    if (rc != RT_OK) return rc;
+    size_t scanBytes = 0;
+    HIPCHK(rebuilddev::scan_bytes((uint32_t)b.dwFlags.cap, b.stream, &scanBytes));
+    rc = rebuild_grow(b, b.dwScan, std::max<size_t>(scanBytes, 256), 0, "scan workspace");
+    if (rc != RT_OK) return rc;
+    b.dw.flags = b.dwFlags.p; b.dw.ranks = b.dwRanks.p; b.dw.newId = b.dwNewId.p; b.dw.frontA = b.dwFrontA.p; b.dw.frontB = b.dwFrontB.p;
+    b.dw.frontCap = (uint32_t)std::min(b.dwFrontA.cap, b.dwFrontB.cap);
+    b.dw.scan = b.dwScan.p; b.dw.scanBytes = b.dwScan.cap;
+    return RT_OK;
+}
 static int rebuild_alloc(SceneBag& b, SceneBag::RebuildSet& t)
 {
     const size_t nP = (size_t)b.nPrims, nB = (size_t)b.nBlas, nT = (size_t)b.nTlas, nL = std::max<size_t>((size_t)b.nLights, 1);
     int rc = RT_OK;
     // every piece is made once: a call that ran out of memory half way is taken up where it stopped
-    auto need = [&](auto** p, size_t count) { if (rc == RT_OK && !*p) rc = dalloc(b.allocs, p, count); };
+    auto need = [&](auto** p, size_t count) { if (rc == RT_OK && !*p) { rc = dalloc(b.allocs, p, count); if (rc == RT_OK) b.rallocs++; } };
     if (!b.stream) HIPCHK(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));
     for (hipEvent_t& e : b.rev) if (!e) HIPCHK(hipEventCreate(&e));
+    if (!b.spool) b.spool = sbvhdev::pool_create();
+    const size_t cap0 = rebuild_initial_cap(b);
     // the scratch both sets share
-    if (!b.dw.scanBytes) HIPCHK(rebuilddev::scan_bytes((uint32_t)(2 * nP), b.stream, &b.dw.scanBytes));
-    char* scan = (char*)b.dw.scan;
-    need(&b.dw.flags, 2 * nP); need(&b.dw.ranks, 2 * nP); need(&b.dw.newId, 2 * nP); need(&b.dw.frontA, nP); need(&b.dw.frontB, nP);
-    need(&scan, b.dw.scanBytes); need(&b.rStatus, 2); need(&b.dw.ctr, rebuilddev::kCtrWords);
-    b.dw.scan = scan; b.dw.frontCap = (uint32_t)nP;
+    need(&b.rStatus, 2); need(&b.dw.ctr, rebuilddev::kCtrWords);
+    if (rc == RT_OK && !b.dwScan.p) rc = rebuild_scratch(b, 2 * cap0);
     if (rc != RT_OK || t.allocated) return rc;
-    need(&t.prims, nP); need(&t.nodes, 2 * nP); need(&t.primIdx, nP); need(&t.blas, nB); need(&t.tlas, nT);
-    need(&t.tp, nT * 4); need(&t.tpP, nT * 4); need(&t.ir, nB * 4); need(&t.pairs, nP * 4); need(&t.triRecs, nP * 3);
-    need(&t.shadeRecs, nP); need(&t.lightRecs, nL * 8); need(&t.rootEntry, nB); need(&t.parent, 2 * nP); need(&t.leaves, nP);
-    need(&t.tickets, 2 * nP); need(&t.pairNode, nP);
+    need(&t.prims, nP); need(&t.blas, nB); need(&t.tlas, nT); need(&t.tp, nT * 4); need(&t.tpP, nT * 4); need(&t.ir, nB * 4);
+    need(&t.shadeRecs, nP); need(&t.lightRecs, nL * 8); need(&t.rootEntry, nB);
+    if (rc == RT_OK) rc = rebuild_reserve(b, t, std::max(cap0, t.primIdx.cap), std::max(2 * cap0, t.nodes.cap), 0, 0);
     if (rc != RT_OK) return rc;
     t.allocated = true;
     return RT_OK;
@@ -1096,7 +1190,10 @@ static int rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, i
     // ---- refusals that need no device work
     if (b.refitRefusal) return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: %s", b.refitRefusal);
     if (b.rebuildRefusal) return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: %s", b.rebuildRefusal);
-    if (builder != RT_REBUILD_SAH && builder != RT_REBUILD_LBVH) return fail(RT_E_INVALID, "rt_rebuild_scene: unknown builder %d", builder);
+    if (builder != RT_REBUILD_SAH && builder != RT_REBUILD_LBVH && builder != RT_REBUILD_SBVH) return fail(RT_E_INVALID, "rt_rebuild_scene: unknown builder %d", builder);
+    const bool sbvh = builder == RT_REBUILD_SBVH;
+    const float alpha = sbvh && opts ? opts->alpha : 0.0f;
+    if (!(alpha >= 0.0f && alpha <= 1.0f)) return fail(RT_E_INVALID, "rt_rebuild_scene: alpha must lie in [0, 1]");
     if (count < 0 || (count > 0 && !prims)) return fail(RT_E_INVALID, "rt_rebuild_scene: bad primitive count %d / NULL records", count);
     if (count > 0 && (first < 0 || (int64_t)first + count > (int64_t)b.nPrims))
         return fail(RT_E_INVALID, "rt_rebuild_scene: primitive range [%d, %lld) outside the %d uploaded", first, (long long)first + count, b.nPrims);
@@ -1113,13 +1210,11 @@ static int rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, i
             if (refit::singular(blas[k].invT)) return fail(RT_E_INVALID, "rt_rebuild_scene: instance %d: the transform is singular", k);
         }
     }
-    HIPCHK(hipSetDevice(b.device));
-    SceneBag::RebuildSet& t = b.rset[b.rnext];
-    if (const int rc = rebuild_alloc(b, t)) return rc;
-    hipStream_t s = b.stream;
-    // the builders' own argument checks, BLAS by BLAS (the arrays are the set's: node and index ids as the host appends BLAS after BLAS)
+    const size_t nR = b.ranges.size();
+    // the builders' own argument checks, BLAS by BLAS (node and index ids as the host appends BLAS after BLAS; the SBVH builder's ids
+    // are known only as the trees are built: its ranges are the upload's, at most 2^30 primitives each, and alpha is checked above)
     lbvh::Params P{};
-    {
+    if (!sbvh) {
         uint32_t nodeBase = 0, idxBase = 0;
         for (const rebuild::BlasRange& r : b.ranges) {
             const int32_t cap = 2 * (int32_t)r.count - 1;
@@ -1128,8 +1223,17 @@ static int rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, i
             if (msg) return fail(RT_E_INVALID, "rt_rebuild_scene: %s", msg);
             nodeBase += (uint32_t)cap; idxBase += r.count;
         }
+    } else {
+        for (const rebuild::BlasRange& r : b.ranges) if (r.count == 0 || r.count > (1u << 30)) return fail(RT_E_INVALID, "rt_rebuild_scene: a BLAS of %u primitives", r.count);
     }
-    {   // the builders' workspace
+    HIPCHK(hipSetDevice(b.device));
+    SceneBag::RebuildSet& t = b.rset[b.rnext];
+    if (const int rc = rebuild_alloc(b, t)) return rc;
+    hipStream_t s = b.stream;
+    if (!sbvh) {
+        // room for every tree these builders can make (a set or the scratch that started smaller, or has only held SBVH trees so far)
+        if (const int rc = rebuild_reserve(b, t, (size_t)b.nPrims, 2 * (size_t)b.nPrims, 0, 0)) return rc;
+        // the builders' workspace
         size_t need = 0;
         for (const rebuild::BlasRange& r : b.ranges) {
             size_t bytes = 0;
@@ -1142,7 +1246,7 @@ static int rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, i
             if (b.rwork) (void)hipFree(b.rwork);
             b.rwork = nullptr; b.rworkBytes = 0;
             if (hipMalloc(&b.rwork, need) != hipSuccess) { b.rwork = nullptr; return fail(RT_E_NOMEM, "rt_rebuild_scene: %zu bytes of builder workspace", need); }
-            b.rworkBytes = need;
+            b.rworkBytes = need; b.rallocs++;
         }
     }
     const DevScene& sc = b.sc;
@@ -1153,17 +1257,32 @@ static int rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, i
     HIPCHK(hipMemcpyAsync(t.lightRecs, sc.lightRecs, sizeof(float4) * 8 * std::max<size_t>((size_t)b.nLights, 1), hipMemcpyDeviceToDevice, s));   // (the emittance words stay)
     const auto t1 = clock::now();
     // ---- every BLAS anew, in the order of the ranges
-    const size_t nR = b.ranges.size();
     std::vector<uint32_t> rootOf(nR), interiors(nR), depth(nR);
     uint32_t nNodes = 0, nIdx = 0, maxDepth = 0;
+    uint64_t spatialSplits = 0, primsClipped = 0;
     for (size_t k = 0; k < nR; k++) {
         const rebuild::BlasRange& r = b.ranges[k];
         Built built{};
-        const int rc = builder == RT_REBUILD_SAH
-            ? sahdev::build(who, s, b.rwork, t.prims + r.first, r.count, r.first, nNodes, nIdx, t.nodes + nNodes, t.primIdx + nIdx, nullptr, nullptr, &built)
-            : lbvhdev::build(who, s, b.rwork, P, t.prims + r.first, r.count, r.first, nNodes, nIdx, t.nodes + nNodes, t.primIdx + nIdx, nullptr, nullptr, &built);
-        if (rc != RT_OK) return rc;
-        if (built.nodes == 0 || (built.nodes & 1u) == 0 || built.nodes > 2 * r.count - 1)
+        uint32_t slots = r.count;
+        if (sbvh) {
+            // size, then place: the tree stays in the builder's own memory until the set has room for it (one tree at a time)
+            struct TreeGuard { sbvhdev::Tree* p = nullptr; ~TreeGuard() { sbvhdev::destroy(p); } } tree;
+            SbvhBuilt sb{};
+            if (const int rc = sbvhdev::build(who, s, alpha, t.prims + r.first, r.count, r.first, nNodes, nIdx, nullptr, nullptr, b.spool, &tree.p, &sb)) return rc;
+            if (sb.nIdx == 0 || (uint64_t)nNodes + sb.nodes + nR > 0x7fffffffull || (uint64_t)nIdx + sb.nIdx > 0x7fffffffull)
+                return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: the new trees have 2^31 nodes or index slots, or more; the scene is unchanged");
+            // (nR spare nodes: the leaf and pair arrays hold half the node capacity, and k trees have k leaves more than interior nodes)
+            if (const int rc = rebuild_reserve(b, t, (size_t)nIdx + sb.nIdx, (size_t)nNodes + sb.nodes + nR, nIdx, nNodes)) return rc;
+            if (const int rc = sbvhdev::emit(who, s, tree.p, t.nodes.p + nNodes, t.primIdx.p + nIdx)) return rc;
+            built.nodes = sb.nodes; built.depth = sb.depth; slots = sb.nIdx;
+            spatialSplits += sb.spatialSplits; primsClipped += sb.primsClipped;
+        } else {
+            const int rc = builder == RT_REBUILD_SAH
+                ? sahdev::build(who, s, b.rwork, t.prims + r.first, r.count, r.first, nNodes, nIdx, t.nodes.p + nNodes, t.primIdx.p + nIdx, nullptr, nullptr, &built)
+                : lbvhdev::build(who, s, b.rwork, P, t.prims + r.first, r.count, r.first, nNodes, nIdx, t.nodes.p + nNodes, t.primIdx.p + nIdx, nullptr, nullptr, &built);
+            if (rc != RT_OK) return rc;
+        }
+        if (built.nodes == 0 || (built.nodes & 1u) == 0 || (!sbvh && built.nodes > 2 * r.count - 1))
             return fail(RT_E_DEVICE, "rt_rebuild_scene: inconsistent builder result (%u nodes for %u primitives)", built.nodes, r.count);
         if ((built.depth == 0) != (built.nodes == 1))
             return fail(RT_E_DEVICE, "rt_rebuild_scene: inconsistent builder result (height %u with %u nodes)", built.depth, built.nodes);
@@ -1172,8 +1291,9 @@ static int rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, i
                         built.depth, RT_BVH4_STACK);
         rootOf[k] = nNodes; interiors[k] = (built.nodes - 1) / 2; depth[k] = built.depth;
         maxDepth = std::max(maxDepth, built.depth);
-        nNodes += built.nodes; nIdx += r.count;
+        nNodes += built.nodes; nIdx += slots;
     }
+    if (const int rc = rebuild_scratch(b, (size_t)nNodes + nR)) return rc;
     const auto t2 = clock::now();
     // ---- the instances (host: at most 256 records), then everything upload derives
     std::vector<RtBVHInstance> inst = b.inst;
@@ -1181,7 +1301,7 @@ static int rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, i
     for (int32_t i = 0; i < b.nBlas; i++) inst[(size_t)i].bvhIdx = rootOf[(size_t)b.instBlas[(size_t)i]];
     HIPCHK(hipMemcpyAsync(t.blas, inst.data(), sizeof(RtBVHInstance) * (size_t)b.nBlas, hipMemcpyHostToDevice, s));
     HIPCHK(hipEventRecord(b.rev[1], s));
-    HIPCHK(rebuilddev::begin(s, b.dw, t.parent, nNodes));
+    HIPCHK(rebuilddev::begin(s, b.dw, t.parent.p, nNodes));
     uint32_t nPairs = 0;
     {   // pair ids: BLAS by BLAS in the order in which the instances first name them
         std::vector<uint8_t> done(nR, 0);
@@ -1189,17 +1309,17 @@ static int rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, i
             const size_t k = (size_t)b.instBlas[(size_t)i];
             if (done[k]) continue;
             done[k] = 1;
-            HIPCHK(rebuilddev::number_blas(s, b.dw, t.nodes, nNodes, rootOf[k], interiors[k], depth[k], nPairs, (uint32_t)b.nPrims, t.pairNode, t.parent));
+            HIPCHK(rebuilddev::number_blas(s, b.dw, t.nodes.p, nNodes, rootOf[k], interiors[k], depth[k], nPairs, (uint32_t)t.pairNode.cap, t.pairNode.p, t.parent.p));
             nPairs += interiors[k];
         }
     }
     const uint32_t nLeaves = nNodes - nPairs;
     const bool layout1 = b.layout == 1;
-    HIPCHK(rebuilddev::finish(s, b.dw, t.nodes, nNodes, nPairs, nLeaves, t.blas, (uint32_t)b.nBlas, t.pairNode, layout1 ? t.pairs : nullptr, t.rootEntry, t.leaves));
-    HIPCHK(refitdev::launch_records(s, t.prims, t.nodes, t.primIdx, nIdx, sc.lights, (uint32_t)b.nLights, 0u, (uint32_t)b.nPrims, nullptr, 0u, nullptr,
-                                    layout1 ? t.triRecs : nullptr, t.shadeRecs, t.lightRecs));
+    HIPCHK(rebuilddev::finish(s, b.dw, t.nodes.p, nNodes, nPairs, nLeaves, t.blas, (uint32_t)b.nBlas, t.pairNode.p, layout1 ? t.pairs.p : nullptr, t.rootEntry, t.leaves.p));
+    HIPCHK(refitdev::launch_records(s, t.prims, t.nodes.p, t.primIdx.p, nIdx, sc.lights, (uint32_t)b.nLights, 0u, (uint32_t)b.nPrims, nullptr, 0u, nullptr,
+                                    layout1 ? t.triRecs.p : nullptr, t.shadeRecs, t.lightRecs));
     HIPCHK(hipEventRecord(b.rev[2], s));
-    HIPCHK(refitdev::launch_tlas(s, t.nodes, t.blas, b.nBlas, layout1 ? t.rootEntry : nullptr, t.tlas, t.tp, t.tpP, t.ir, b.rStatus));
+    HIPCHK(refitdev::launch_tlas(s, t.nodes.p, t.blas, b.nBlas, layout1 ? t.rootEntry : nullptr, t.tlas, t.tp, t.tpP, t.ir, b.rStatus));
     HIPCHK(hipEventRecord(b.rev[3], s));
     int32_t status[2] = { 0, 0 };
     uint32_t walk[2] = { 0, 0 };
@@ -1221,13 +1341,13 @@ static int rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, i
         if (h->home != h->stream) HIPCHK(hipStreamSynchronize(h->home));
     }
     DevScene n = b.sc;
-    n.prims = t.prims; n.bvh2 = t.nodes; n.primIdx = t.primIdx; n.blas = t.blas; n.tlas = t.tlas;
+    n.prims = t.prims; n.bvh2 = t.nodes.p; n.primIdx = t.primIdx.p; n.blas = t.blas; n.tlas = t.tlas;
     n.tlasPairs = (const float4*)t.tp; n.tlasPairsP = (const float4*)t.tpP; n.instRecs = (const float4*)t.ir;
     n.shadeRecs = (const float4*)t.shadeRecs; n.lightRecs = (const float4*)t.lightRecs;
-    if (layout1 && nPairs == 0) HIPCHK(hipMemsetAsync(t.pairs, 0, sizeof(float4) * 4, s));   // no interior node: one zero record, as at upload
-    if (layout1) { n.pairs = (const float4*)t.pairs; n.triRecs = (const float4*)t.triRecs; n.rootEntry = t.rootEntry; }
+    if (layout1 && nPairs == 0) HIPCHK(hipMemsetAsync(t.pairs.p, 0, sizeof(float4) * 4, s));   // no interior node: one zero record, as at upload
+    if (layout1) { n.pairs = (const float4*)t.pairs.p; n.triRecs = (const float4*)t.triRecs.p; n.rootEntry = t.rootEntry; }
     b.sc = n;
-    b.dParent = t.parent; b.dLeaves = t.leaves; b.dTickets = t.tickets; b.dPairNode = t.pairNode;
+    b.dParent = t.parent.p; b.dLeaves = t.leaves.p; b.dTickets = t.tickets.p; b.dPairNode = t.pairNode.p;
     b.nNodes = (int32_t)nNodes; b.nIdx = (int32_t)nIdx; b.nPairs = layout1 ? (int32_t)nPairs : 0; b.nLeaves = nLeaves; b.nReach = nNodes;
     b.inst = inst;
     const bool reconfigure = status[1] != b.tlasDepth || rebuild::stack_entries((int)std::max(maxDepth, 1u)) != b.stackEntries;
@@ -1246,6 +1366,7 @@ static int rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, i
         stats->commit_ms = ms_between(t3, t4);
         stats->prims = count; stats->blas_built = (int32_t)nR; stats->nodes = (int32_t)nNodes; stats->n_idx = (int32_t)nIdx;
         stats->max_depth = (int32_t)maxDepth; stats->tlas_nodes = b.nTlas; stats->tlas_depth = status[1]; stats->reconfigured = reconfigure ? 1 : 0;
+        stats->spatial_splits = (int32_t)std::min<uint64_t>(spatialSplits, 0x7fffffffu); stats->prims_clipped = (int32_t)std::min<uint64_t>(primsClipped, 0x7fffffffu);
     }
     return RT_OK;
 }
@@ -1262,6 +1383,13 @@ extern "C" int rt_group_rebuild_scene(RtGroup* g, const RtPrimitive* prims, int3
 {
     if (!g) return fail(RT_E_INVALID, "rt_group_rebuild_scene: null group");
     return rt_rebuild_scene(rt_group_lane(g, 0), prims, first, count, blas, nBlas, builder, opts, stats);   // every lane holds lane 0's copy
+}
+extern "C" int rt_debug_rebuild_allocations(RtCtx* ctx, int64_t* count)
+{
+    if (!ctx || !count) return fail(RT_E_INVALID, "rt_debug_rebuild_allocations: null argument");
+    if (!ctx->sceneLoaded || !ctx->scene) return fail(RT_E_INVALID, "rt_debug_rebuild_allocations: no scene uploaded");
+    *count = (int64_t)(ctx->scene->rallocs + sbvhdev::pool_allocations(ctx->scene->spool));
+    return RT_OK;
 }
 // The primitive range of every instance's BLAS (rebuild_common.h), for callers that want to know beforehand whether rt_rebuild_scene
 // will take a scene; no device needed.

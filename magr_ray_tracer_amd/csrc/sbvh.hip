@@ -34,7 +34,52 @@ using builddev::build_fail;
 using builddev::grid;
 using builddev::ms_since;
 
+// Device blocks that outlive a build (build_cores.h): a caller that builds again and again (rt_rebuild_scene, every frame) hands the
+// same pool to every build, and the builds take their arrays from it.  Requests are rounded up to size classes (2^k and 3 * 2^(k-1)
+// bytes) and a request only ever takes a free block of its own class, so a build that asks for the same sizes in the same order as
+// an earlier one finds every block it needs: no hipMalloc, and no hipFree (which waits for the whole device) between frames.
+// Blocks are reused in stream order only (one stream per pool).
+namespace sbvhdev {
+struct Pool {
+    struct Block { void* p; size_t cap; bool used; };
+    std::vector<Block> blocks;
+    uint64_t allocations = 0;
+    ~Pool() { for (Block& b : blocks) (void)hipFree(b.p); }
+};
+Pool* pool_create() { return new Pool(); }
+void pool_destroy(Pool* p) { delete p; }
+uint64_t pool_allocations(const Pool* p) { return p ? p->allocations : 0; }
+}
+
 namespace {
+
+size_t size_class(size_t bytes)
+{
+    size_t c = 256;
+    while (c < bytes) {
+        if (c + c / 2 >= bytes) return c + c / 2;
+        c *= 2;
+    }
+    return c;
+}
+// *bytes in: what is needed; out: what the block holds
+hipError_t pool_alloc(sbvhdev::Pool* pool, void** out, size_t* bytes)
+{
+    if (!pool) return hipMalloc(out, *bytes);
+    const size_t c = size_class(*bytes);
+    *bytes = c;
+    for (sbvhdev::Pool::Block& b : pool->blocks) if (!b.used && b.cap == c) { b.used = true; *out = b.p; return hipSuccess; }
+    const hipError_t e = hipMalloc(out, c);
+    if (e != hipSuccess) return e;
+    pool->blocks.push_back({ *out, c, true });
+    pool->allocations++;
+    return hipSuccess;
+}
+void pool_free(sbvhdev::Pool* pool, void* p)
+{
+    if (!pool) { (void)hipFree(p); return; }
+    for (sbvhdev::Pool::Block& b : pool->blocks) if (b.p == p) { b.used = false; return; }
+}
 
 constexpr int kBlock = 256;
 constexpr int kSlots = 16;                          // nodes per workgroup that are folded in LDS; further ones go to global memory
@@ -338,25 +383,30 @@ __global__ void __launch_bounds__(kBlock) k_sbvh_emit_refs(const SNode* bn, uint
     primIdx[dst] = first + prim[p];
 }
 
-// A device array that grows: ensure() keeps the first `keep` bytes when it has to move
+// A device array that grows: ensure() keeps the first `keep` bytes when it has to move.  Its memory comes from the build's pool
+// (sbvhdev::Pool, below) when there is one, from hipMalloc / hipFree otherwise.
 struct DBuf {
     void* p = nullptr;
     size_t cap = 0;
-    ~DBuf() { if (p) (void)hipFree(p); }
+    sbvhdev::Pool* pool = nullptr;
+    explicit DBuf(sbvhdev::Pool* pl = nullptr) : pool(pl) {}
+    DBuf(const DBuf&) = delete;
+    DBuf& operator=(const DBuf&) = delete;
+    ~DBuf() { if (p) pool_free(pool, p); }
     hipError_t ensure(size_t bytes, size_t keep, hipStream_t s)
     {
         if (bytes <= cap) return hipSuccess;
         size_t want = cap + cap / 2;
         if (want < bytes) want = bytes;
         void* q = nullptr;
-        hipError_t e = hipMalloc(&q, want);
+        hipError_t e = pool_alloc(pool, &q, &want);
         if (e != hipSuccess) return e;
         if (keep && p) {
             e = hipMemcpyAsync(q, p, keep, hipMemcpyDeviceToDevice, s);
             if (e == hipSuccess) e = hipStreamSynchronize(s);
-            if (e != hipSuccess) { (void)hipFree(q); return e; }
+            if (e != hipSuccess) { pool_free(pool, q); return e; }
         }
-        if (p) (void)hipFree(p);
+        if (p) pool_free(pool, p);
         p = q; cap = want;
         return hipSuccess;
     }
@@ -387,22 +437,24 @@ namespace sbvhdev {
 
 // The device-side state of a finished build: the build nodes, numbered, and per level the (node, primitive) of every ref
 struct Tree {
+    Pool* pool;
     DBuf bn, summary;
     std::vector<void*> hist;                                  // per level: nid[m], then prim[m]
     std::vector<uint32_t> histN;
     std::vector<std::pair<uint32_t, uint32_t>> levels;
     uint32_t first = 0, nodeBase = 0, idxBase = 0, total = 0;
     SbvhBuilt built{};
-    ~Tree() { for (void* h : hist) if (h) (void)hipFree(h); }
+    explicit Tree(Pool* pl) : pool(pl), bn(pl), summary(pl) {}
+    ~Tree() { for (void* h : hist) if (h) pool_free(pool, h); }
 };
 
 void destroy(Tree* t) { delete t; }
 
 int build(const char* who, hipStream_t stream, float alpha, const RtPrimitive* dPrims, uint32_t n, uint32_t first, uint32_t nodeBase,
-          uint32_t idxBase, hipEvent_t evBegin, hipEvent_t evEnd, Tree** treeOut, SbvhBuilt* out)
+          uint32_t idxBase, hipEvent_t evBegin, hipEvent_t evEnd, Pool* pool, Tree** treeOut, SbvhBuilt* out)
 {
     const auto t0 = builddev::Clock::now();
-    Tree* T = new Tree();
+    Tree* T = new Tree(pool);
     *treeOut = T;                                             // the caller destroys it, on failure too
     T->first = first; T->nodeBase = nodeBase; T->idxBase = idxBase;
     // the initial capacity of the ref arrays (they grow from the scan of every level)
@@ -412,10 +464,11 @@ int build(const char* who, hipStream_t stream, float alpha, const RtPrimitive* d
         if (k > 0) refCap = (size_t)k;
     }
     if (refCap < n) refCap = n;
-    DBuf refsA, refsB, fbuf, Fbuf, scan, lvl;
+    DBuf refsA(pool), refsB(pool), fbuf(pool), Fbuf(pool), scan(pool), lvl(pool);
     auto add_level = [&](uint32_t m) -> hipError_t {
         void* h = nullptr;
-        const hipError_t e = hipMalloc(&h, (size_t)(m ? m : 1) * 8);
+        size_t bytes = (size_t)(m ? m : 1) * 8;
+        const hipError_t e = pool_alloc(pool, &h, &bytes);
         if (e != hipSuccess) return e;
         T->hist.push_back(h); T->histN.push_back(m);
         return hipSuccess;
@@ -573,7 +626,7 @@ extern "C" int rt_build_bvh2_sbvh(int32_t device, float alpha, const RtPrimitive
     const double tAlloc = ms_since(t0);
 
     SbvhBuilt b{};
-    if (const int rc = sbvhdev::build(who, w.stream, alpha, (const RtPrimitive*)w.prims, n, (uint32_t)first, nodeBase, idxBase, w.ev[0], nullptr, &w.tree, &b))
+    if (const int rc = sbvhdev::build(who, w.stream, alpha, (const RtPrimitive*)w.prims, n, (uint32_t)first, nodeBase, idxBase, w.ev[0], nullptr, nullptr, &w.tree, &b))
         return rc;
     if ((uint64_t)nodeBase + b.nodes > 0xffffffffull || (uint64_t)idxBase + b.nIdx > 0xffffffffull)
         return build_fail(RT_E_INVALID, "rt_build_bvh2_sbvh: nodeBase / idxBase + the tree overflow 32-bit ids");

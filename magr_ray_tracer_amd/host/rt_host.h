@@ -77,7 +77,7 @@ public:
     // Throws LbvhError and leaves everything unchanged when the build is refused.
     void     BuildBLASSBVHGPU(int startIdx, float alpha, int device);
     // Discards the trees and builds every BLAS again over the primitive range it covers, in increasing order of the ranges, with the
-    // host restatement of rt_rebuild_scene's builder (RT_REBUILD_SAH / RT_REBUILD_LBVH, opt for the latter); instance transforms stay,
+    // host restatement of rt_rebuild_scene's builder (RT_REBUILD_SAH / RT_REBUILD_LBVH / RT_REBUILD_SBVH, opt as there); instance transforms stay,
     // bvhIdx follows.  Throws LbvhError and leaves everything unchanged when refused (rebuild_host.cpp).
     void     Rebuild(int builder, const RtBuildOptions* opt);
     int      buildThreads = 1;   // > 1: subtrees are built by parallel tasks, then numbered in the reference's LIFO order (same arrays)
@@ -124,6 +124,9 @@ int SahBuildHost(const RtPrimitive* prims, int32_t nPrims, int32_t first, int32_
                  RtBVHNode2* nodes, int32_t nodeCap, int32_t* nNodes, uint32_t* primIdx, RtBuildStats* stats, std::string& err);
 
 // The GPU SBVH build's sequential host restatement (rth_build_bvh2_sbvh); err receives the message of a refused call.
+// the same build into vectors of the tree's own size, for callers that have checked the arguments (BVH2::Rebuild)
+int SbvhBuildVectors(float alpha, const RtPrimitive* prims, int32_t first, int32_t count, uint32_t nodeBase, uint32_t idxBase,
+                     std::vector<RtBVHNode2>& nodes, std::vector<uint32_t>& primIdx, RtSbvhStats* stats, std::string& err);
 int SbvhBuildHost(float alpha, const RtPrimitive* prims, int32_t nPrims, int32_t first, int32_t count, uint32_t nodeBase, uint32_t idxBase,
                   RtBVHNode2* nodes, int32_t nodeCap, int32_t* nNodes, uint32_t* primIdx, int32_t idxCap, int32_t* nIdx, RtSbvhStats* stats,
                   std::string& err);

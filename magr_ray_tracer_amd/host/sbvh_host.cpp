@@ -19,7 +19,7 @@ using namespace sbvh;
 namespace rt355 {
 
 // The build into vectors of the tree's own size (the arguments are checked by the callers)
-static int SbvhBuildVectors(float alpha, const RtPrimitive* prims, int32_t first, int32_t count, uint32_t nodeBase, uint32_t idxBase,
+int SbvhBuildVectors(float alpha, const RtPrimitive* prims, int32_t first, int32_t count, uint32_t nodeBase, uint32_t idxBase,
                             std::vector<RtBVHNode2>& nodes, std::vector<uint32_t>& primIdx, RtSbvhStats* stats, std::string& err)
 {
     const std::string who = "rth_build_bvh2_sbvh: ";

@@ -28,18 +28,19 @@ def _update_dict(st):
             "tlas_depth": int(st["tlas_depth"]), "reconfigured": bool(st["reconfigured"])}
 
 
-def _rebuild_args(prims, first, instances, builder, lbvh_options):
+def _rebuild_args(prims, first, instances, builder, lbvh_options, alpha=None):
     from .scene import build_options, rebuild_builder
-    which = rebuild_builder(builder, lbvh_options)
+    which = rebuild_builder(builder, lbvh_options, alpha)
     (p_, f_, n_, b_, nb_, _), keep, _ = _update_args(prims, first, instances)
-    opts = build_options(**lbvh_options)
+    opts = build_options(alpha=alpha, **lbvh_options)
     st = np.zeros((), dtype=_lib.RebuildStats)
     return (p_, f_, n_, b_, nb_, which, _lib.ptr(opts), _lib.ptr(st)), (keep, opts), st
 
 
 def _rebuild_dict(st):
     d = {n: float(st[n]) for n in ("gpu_ms", "wall_ms", "stage_ms", "build_ms", "derive_ms", "tlas_ms", "commit_ms")}
-    d.update({n: int(st[n]) for n in ("prims", "blas_built", "nodes", "n_idx", "max_depth", "tlas_nodes", "tlas_depth")})
+    d.update({n: int(st[n]) for n in ("prims", "blas_built", "nodes", "n_idx", "max_depth", "tlas_nodes", "tlas_depth", "spatial_splits",
+                                      "prims_clipped")})
     d["reconfigured"] = bool(st["reconfigured"])
     return d
 
@@ -121,19 +122,26 @@ class Device:
         self._chk(self._lib.rt_update_scene(self._h, *args))
         return _update_dict(st)
 
-    def rebuild_scene(self, prims=None, first=0, instances=None, builder="sah", **lbvh_options):
+    def rebuild_scene(self, prims=None, first=0, instances=None, builder="sah", alpha=None, **lbvh_options):
         """Rebuild the bound scene's BLAS in place on the GPU (rt_rebuild_scene): `prims` / `instances` as for update_scene; then every
-        BLAS is built anew over its primitive range with builder "sah" (BVH2::BuildBLAS, alpha 1) or "lbvh" (lbvh_options: max_leaf,
-        cost_traverse, cost_intersect), the TLAS is rebuilt and every derived array is produced on the device.  Use it when refits have
-        degraded the trees (topology-changing motion).  Every context holding the scene sees it.  Returns the stats; a refusal raises
-        RtError (.code) and leaves the scene as it was."""
-        args, keep, st = _rebuild_args(prims, first, instances, builder, lbvh_options)
+        BLAS is built anew over its primitive range with builder "sah" (BVH2::BuildBLAS, alpha 1), "lbvh" (lbvh_options: max_leaf,
+        cost_traverse, cost_intersect) or "sbvh_gpu" (BVH2::BuildBLAS with `alpha` in [0, 1], default 0: spatial splits, for scenes
+        bound as an SBVH), the TLAS is rebuilt and every derived array is produced on the device.  Use it when refits have degraded
+        the trees (topology-changing motion).  Every context holding the scene sees it.  Returns the stats; a refusal raises RtError
+        (.code) and leaves the scene as it was."""
+        args, keep, st = _rebuild_args(prims, first, instances, builder, lbvh_options, alpha)
         rc = self._lib.rt_rebuild_scene(self._h, *args)
         if rc != 0:
             e = RtError(self._lib.rt_last_error().decode())
             e.code = rc
             raise e
         return _rebuild_dict(st)
+
+    def rebuild_allocations(self):
+        """Device allocations that updates and rebuilds of the bound scene copy have made so far (rt_debug_rebuild_allocations)."""
+        n = C.c_int64(0)
+        self._chk(self._lib.rt_debug_rebuild_allocations(self._h, C.byref(n)))
+        return n.value
 
     def scene_array(self, name):
         """A device array of the bound scene as raw bytes (rt_debug_get_scene_array; names: _lib.SCENE_ARRAYS)."""
@@ -361,9 +369,9 @@ class Group:
         self._chk(self._lib.rt_group_update_scene(self._h, *args))
         return _update_dict(st)
 
-    def rebuild_scene(self, prims=None, first=0, instances=None, builder="sah", **lbvh_options):
+    def rebuild_scene(self, prims=None, first=0, instances=None, builder="sah", alpha=None, **lbvh_options):
         """Device.rebuild_scene for the group's scene copy (rt_group_rebuild_scene): every lane sees the rebuilt scene."""
-        args, keep, st = _rebuild_args(prims, first, instances, builder, lbvh_options)
+        args, keep, st = _rebuild_args(prims, first, instances, builder, lbvh_options, alpha)
         rc = self._lib.rt_group_rebuild_scene(self._h, *args)
         if rc != 0:
             e = RtError(self._lib.rt_last_error().decode())

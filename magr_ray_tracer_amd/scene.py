@@ -185,12 +185,15 @@ class Scene:
         rebuild the TLAS (and the BVH4) from the refit tree."""
         self._chk(self._lib.rth_refit(self._h))
 
-    def Rebuild(self, builder="sah", **lbvh_options):
+    def Rebuild(self, builder="sah", alpha=None, **lbvh_options):
         """Discard the BVH2 and build every BLAS again over the primitive range it covers, as rt_rebuild_scene does on the GPU
         (rth_rebuild): builder="sah" is the GPU SAH builder's host restatement (BuildBLAS with alpha 1), "lbvh" the linear builder's
-        (lbvh_options: max_leaf, cost_traverse, cost_intersect).  Instance transforms stay; arrays() / BuildTLAS() then rebuild the
-        TLAS (and the BVH4).  Raises BuildError (.code, an RT_E_* value) and changes nothing when refused."""
-        rc = self._lib.rth_rebuild(self._h, rebuild_builder(builder, lbvh_options), _lib.ptr(build_options(**lbvh_options)))
+        (lbvh_options: max_leaf, cost_traverse, cost_intersect), "sbvh_gpu" the GPU SBVH builder's (BuildBLAS with `alpha` in [0, 1],
+        default 0: spatial splits; stats() then reports the new trees' spatial_splits / prims_clipped).  Instance transforms stay;
+        arrays() / BuildTLAS() then rebuild the TLAS (and the BVH4).  Raises BuildError (.code, an RT_E_* value) and changes nothing
+        when refused."""
+        which = rebuild_builder(builder, lbvh_options, alpha)
+        rc = self._lib.rth_rebuild(self._h, which, _lib.ptr(build_options(alpha=alpha, **lbvh_options)))
         if rc != 0:
             raise BuildError(rc, self._lib.rth_last_error().decode())
 
@@ -237,22 +240,28 @@ class Scene:
 LBVH_DEFAULTS = dict(max_leaf=8, cost_traverse=1.0, cost_intersect=1.0)   # lbvh_common.h
 
 
-def build_options(max_leaf=None, cost_traverse=None, cost_intersect=None):
-    """RtBuildOptions of the linear builder; None = its default."""
+def build_options(max_leaf=None, cost_traverse=None, cost_intersect=None, alpha=None):
+    """RtBuildOptions: the linear builder's options (None = its default) and the SBVH rebuild's alpha (None = 0)."""
     o = np.zeros((), _lib.BuildOptions)
     o["max_leaf"] = LBVH_DEFAULTS["max_leaf"] if max_leaf is None else int(max_leaf)
     o["cost_traverse"] = LBVH_DEFAULTS["cost_traverse"] if cost_traverse is None else float(cost_traverse)
     o["cost_intersect"] = LBVH_DEFAULTS["cost_intersect"] if cost_intersect is None else float(cost_intersect)
+    o["alpha"] = 0.0 if alpha is None else float(alpha)
     return o
 
 
-def rebuild_builder(builder, lbvh_options=None):
-    """RT_REBUILD_* of a builder name; the linear builder's options apply to "lbvh" only."""
-    if builder not in ("sah", "lbvh"):
-        raise ValueError(f"unknown builder {builder!r} (expected 'sah' or 'lbvh')")
-    if builder == "sah" and lbvh_options:
+REBUILD_BUILDERS = {"sah": _lib.REBUILD_SAH, "lbvh": _lib.REBUILD_LBVH, "sbvh_gpu": _lib.REBUILD_SBVH}
+
+
+def rebuild_builder(builder, lbvh_options=None, alpha=None):
+    """RT_REBUILD_* of a builder name; the linear builder's options apply to "lbvh" only, alpha to "sbvh_gpu" only."""
+    if builder not in REBUILD_BUILDERS:
+        raise ValueError(f"unknown builder {builder!r} (expected 'sah', 'lbvh' or 'sbvh_gpu')")
+    if builder != "lbvh" and lbvh_options:
         raise ValueError(f"options {sorted(lbvh_options)} apply to builder='lbvh' only")
-    return _lib.REBUILD_SAH if builder == "sah" else _lib.REBUILD_LBVH
+    if builder != "sbvh_gpu" and alpha is not None:
+        raise ValueError("alpha applies to builder='sbvh_gpu' only")
+    return REBUILD_BUILDERS[builder]
 
 
 def blas_ranges(sa):

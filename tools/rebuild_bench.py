@@ -1,6 +1,6 @@
 """Cost of an in-place BLAS rebuild (rt_rebuild_scene) against the round trip it removes, on one GPU.
 
-    python tools/rebuild_bench.py [--reps 10] [--frames 20]
+    python tools/rebuild_bench.py [--reps 10] [--frames 20] [--builders sah,lbvh,sbvh] [--host-reps 1]
 
 For sponza-class (every vertex scrambled across the triangles) and config 5 (every vertex jittered), three ways to bring a bound scene
 up to date are timed in one process, alternating within each repetition (min / median / max of --reps after a warm-up):
@@ -11,7 +11,15 @@ up to date are timed in one process, alternating within each repetition (min / m
   C  Device.update_scene(prims) of the same records, for scale.
 Then the trace rate (M samples/s over --frames frames) on sponza-class with the vertices scrambled among every 64 consecutive
 triangles (a deformation that leaves a tree something to cull): the scene as built, after the refit alone, after the rebuild.
-One JSON line per scene and builder."""
+One JSON line per scene and builder.
+
+--builders sbvh: the SBVH rebuild (builder="sbvh_gpu"), sponza-class at alpha 0.5 and 0 and config 5 at alpha 0 (the alpha both its
+BLAS are built with), against the two ways to the same trees that exist without it, in the same run:
+  a  rt_build_bvh2_sbvh per BLAS (the tree comes back to the host), the TLAS on the host, rt_upload_scene into a second context (the
+     first repetition checks that its eleven device arrays equal the rebuild's);
+  b  the same triangles built from scratch on the host by BuildBLAS(alpha) at 16 threads, BuildTLAS, rt_upload_scene (--host-reps times).
+For config 5 also what the feature is for, the trace rate of the jittered scene in three states: refit alone (the SBVH leaves have
+lost their clipped boxes), rebuilt with "sah" (no spatial splits), rebuilt with "sbvh_gpu" at alpha 0."""
 import argparse
 import json
 import os
@@ -24,7 +32,8 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from magr_ray_tracer_amd import _lib as W, scenes  # noqa: E402
 from magr_ray_tracer_amd.renderer import Device  # noqa: E402
-from magr_ray_tracer_amd.scene import SceneArrays, blas_ranges, build_lbvh, build_sah_gpu  # noqa: E402
+from magr_ray_tracer_amd.scene import SceneArrays, blas_ranges, build_lbvh, build_sah_gpu, build_sbvh_gpu  # noqa: E402
+from magr_ray_tracer_amd.scenes import Scene, _std_materials  # noqa: E402
 
 RW, RH = 1280, 720
 
@@ -80,14 +89,17 @@ def small_tlas(nodes, inst):
     return t
 
 
-def round_trip(sa, prims, ranges, builder, d2):
+def round_trip(sa, prims, ranges, builder, d2, alpha=None):
     """B: per-BLAS GPU builds on caller arrays, host TLAS, upload.  Returns (wall ms, sum of the builders' device_ms)."""
     t0 = time.perf_counter()
     nodes, idx, roots, dev = [], [], {}, 0.0
     nb = ib = 0
     for first, count in sorted(set(ranges)):
-        fn = build_sah_gpu if builder == "sah" else build_lbvh
-        n, i, st = fn(prims, first=first, count=count, device=0, node_base=nb, idx_base=ib)
+        if builder == "sbvh":
+            n, i, st = build_sbvh_gpu(prims, alpha, first=first, count=count, device=0, node_base=nb, idx_base=ib)
+        else:
+            fn = build_sah_gpu if builder == "sah" else build_lbvh
+            n, i, st = fn(prims, first=first, count=count, device=0, node_base=nb, idx_base=ib)
         roots[(first, count)] = nb
         nodes.append(n)
         idx.append(i)
@@ -114,12 +126,104 @@ def trace_rate(d, cam, frames):
     return round(RW * RH * frames / (time.perf_counter() - t0) / 1e6, 3)
 
 
+def host_from_scratch(prims, ranges, alpha, d2):
+    """b: the triangles built from scratch on the host, BLAS after BLAS, by BuildBLAS(alpha) at 16 threads, BuildTLAS, upload.
+    Returns (wall ms of the builds, TLAS and upload; of the BuildBLAS calls alone)."""
+    assert np.all(prims["objType"] == W.PRIM_TRIANGLE)
+    s = Scene()
+    _std_materials(s)
+    wall = build = 0.0
+    for first, count in sorted(set(ranges)):
+        q = prims[first:first + count]
+        s.AddTriangles(np.stack([q["v0"][:, :3], q["v1"][:, :3], q["v2"][:, :3]], axis=1), "white")   # (not timed: the caller has its records)
+        t0 = time.perf_counter()
+        s.BuildBLAS(first, alpha=alpha, threads=16)
+        build += (time.perf_counter() - t0) * 1e3
+    t0 = time.perf_counter()
+    d2.upload(s.arrays(bvh4=False))
+    wall = build + (time.perf_counter() - t0) * 1e3
+    s.close()
+    return wall, build
+
+
+def sbvh_cases(a):
+    """The SBVH rebuild against routes a and b; config 5's trace rate refit / rebuilt without / rebuilt with spatial splits."""
+    # (the rebuild does not depend on how the scene was first built: sponza-class is bound as the plain SAH tree, which builds fast;
+    # config 5 as what the benchmark measures, both BLAS at alpha 0, built by the GPU builder - the same arrays as the host's)
+    cases = (("sponza_class", 0.5, lambda: scenes.sponza_class(1.0), scrambled), ("sponza_class", 0.0, lambda: scenes.sponza_class(1.0), scrambled),
+             ("config5", 0.0, lambda: scenes.config5_scene(0.0, builder="sbvh_gpu", device=0), jittered))
+    for name, alpha, make, move in cases:
+        s, view = make()
+        sa = s.arrays(bvh4=False)
+        ranges = blas_ranges(sa)
+        cam = scenes.camera_for(view, RW, RH)
+        d2 = Device(320, 240)
+        dA = Device(RW, RH)
+        dA.upload(sa)
+        allocs = []
+        for k in range(3):                            # warm-up: both sets grown, the builder's blocks pooled
+            dA.rebuild_scene(move(sa.prims, 100 + k), builder="sbvh_gpu", alpha=alpha)
+            allocs.append(dA.rebuild_allocations())
+        round_trip(sa, move(sa.prims, 100), ranges, "sbvh", d2, alpha)
+        A, Ag, Ra, Rad = [], [], [], []
+        split = {k: [] for k in ("stage_ms", "build_ms", "derive_ms", "tlas_ms", "commit_ms")}
+        for r in range(a.reps):
+            p = move(sa.prims, r + 1)
+            t0 = time.perf_counter()
+            st = dA.rebuild_scene(p, builder="sbvh_gpu", alpha=alpha)
+            A.append((time.perf_counter() - t0) * 1e3)
+            Ag.append(st["gpu_ms"])
+            for k in split:
+                split[k].append(st[k])
+            w, dev = round_trip(sa, p, ranges, "sbvh", d2, alpha)
+            Ra.append(w)
+            Rad.append(dev)
+            if r == 0:
+                for k in W.SCENE_ARRAYS:
+                    assert np.array_equal(dA.scene_array(k), d2.scene_array(k)), f"{name} / sbvh alpha {alpha}: route a's {k} differs from the rebuild's"
+        allocs.append(dA.rebuild_allocations())
+        Rb, Rbb = [], []
+        for r in range(a.host_reps):
+            w, bw = host_from_scratch(move(sa.prims, r + 1), ranges, alpha, d2)
+            Rb.append(w)
+            Rbb.append(bw)
+        mA = statistics.median(A)
+        out = {"scene": name, "builder": "sbvh_gpu", "alpha": alpha, "prims": int(len(sa.prims)), "nodes": st["nodes"], "n_idx": st["n_idx"],
+               "max_depth": st["max_depth"], "spatial_splits": st["spatial_splits"], "prims_clipped": st["prims_clipped"],
+               "A_wall_ms": mmm(A), "A_gpu_ms": mmm(Ag), "A_split_ms": {k: round(statistics.median(v), 3) for k, v in split.items()},
+               "a_wall_ms": mmm(Ra), "a_builders_device_ms": mmm(Rad), "A_over_a": round(mA / statistics.median(Ra), 3),
+               "allocations_after_warmups_and_reps": allocs}
+        if Rb:
+            out.update({"b_wall_ms": mmm(Rb), "b_buildblas_ms": mmm(Rbb), "A_over_b": round(mA / statistics.median(Rb), 4)})
+        if name == "config5":
+            dT = Device(RW, RH)
+            dT.upload(sa)
+            out["trace_built_Msps"] = trace_rate(dT, cam, a.frames)           # the scene as built, for scale
+            p = move(sa.prims, 7)
+            dT.update_scene(p)
+            out["trace_refit_only_Msps"] = trace_rate(dT, cam, a.frames)
+            dT.rebuild_scene(p, builder="sah")
+            out["trace_rebuilt_sah_Msps"] = trace_rate(dT, cam, a.frames)
+            dA.rebuild_scene(p, builder="sbvh_gpu", alpha=alpha)
+            out["trace_rebuilt_sbvh_Msps"] = trace_rate(dA, cam, a.frames)
+            dT.close()
+        print(json.dumps(out), flush=True)
+        dA.close()
+        d2.close()
+        s.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--frames", type=int, default=20)
+    ap.add_argument("--builders", default="sah,lbvh,sbvh")
+    ap.add_argument("--host-reps", type=int, default=1)
     a = ap.parse_args()
+    which = a.builders.split(",")
     cases = {"sponza_class": (lambda: scenes.sponza_class(1.0), scrambled), "config5": (lambda: scenes.config5_scene(0.0), jittered)}
+    if not [b for b in which if b in ("sah", "lbvh")]:
+        cases = {}
     for name, (make, move) in cases.items():
         s, view = make()
         sa = s.arrays(bvh4=False)
@@ -129,7 +233,7 @@ def main():
         dC.upload(sa)
         dC.update_scene(move(sa.prims, 0))            # warm-up: allocates the staging buffers
         d2 = Device(320, 240)
-        for builder in ("sah", "lbvh"):
+        for builder in [b for b in which if b in ("sah", "lbvh")]:
             dA = Device(RW, RH)
             dA.upload(sa)
             for k in range(2):                        # warm-up: both sets of arrays and the builders' workspace
@@ -176,6 +280,8 @@ def main():
         d2.close()
         dC.close()
         s.close()
+    if "sbvh" in which:
+        sbvh_cases(a)
 
 
 if __name__ == "__main__":
