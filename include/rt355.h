@@ -224,7 +224,8 @@ int rt_debug_sbvh_phases(float* out);
  * scene refit on the host (rth_set_primitives + rth_refit + rth_build_tlas, rt355_host.h).
  * Refusals return before anything is written: RT_E_INVALID for a changed objType / matIdx / bvhIdx, a range outside the upload, a
  * singular invT or a wrong instance count; RT_E_UNSUPPORTED for BVH4 contexts, scenes the update cannot handle (a TLAS not built by
- * TLAS::Build's rules, a node reachable twice) and a rebuilt TLAS deeper than RT_TLAS_STACK (the work is staged: the bound scene then
+ * TLAS::Build's rules, a node reachable twice), a rebuilt TLAS deeper than RT_TLAS_STACK and a clustering that finds no partner (no two
+ * instance boxes with a union area below RT_REALLYFAR; rth_build_tlas refuses it too) (the work is staged: the bound scene then
  * renders exactly as before).  The update waits for the streams of every context holding the scene (rt_share_scene partners, all
  * lanes and worker streams of a group), not for other device work; each of them re-derives its traversal kernels (rt_kernel_info)
  * before its next launch when the TLAS depth changed.  Synchronous; stats may be NULL.  Accumulators are not reset. */

@@ -89,7 +89,10 @@ int rth_rebuild(RthScene* s, int builder, const RtBuildOptions* opts);
  * the reason) when the scene is not of the shape a rebuild takes. */
 int rth_blas_ranges(RthScene* s, int32_t* firstOut, int32_t* countOut);
 int rth_build_bvh4(RthScene* s);            /* new BVH4(*bvh2) (scene.cpp:71)                    */
-int rth_build_tlas(RthScene* s);            /* new TLAS(*bvh2); Build() (renderer.cpp:12-13)     */
+/* new TLAS(*bvh2); Build() (renderer.cpp:12-13).  Refused (-1, the scene keeps the TLAS it had) for more than 256 instances, none, a
+ * singular transform, and where the clustering finds no partner: no two boxes with a union area below RT_REALLYFAR (instances 1e15
+ * apart, NaN boxes), which rt_update_scene / rt_rebuild_scene refuse as RT_E_UNSUPPORTED and the reference answers by reading slot[-1]. */
+int rth_build_tlas(RthScene* s);
 /* BVH4::Convert + Collapse (bvh.cpp:695-787) on a caller-provided BVH2 node array, one BLAS rooted at node 0; out[n] */
 int rth_bvh4_from_nodes(const RtBVHNode2* nodes, int n, RtBVHNode4* out);
 int rth_set_instance_transform(RthScene* s, int blas, const float invT[16]); /* scene.cpp:82 (commented out there) */

@@ -655,7 +655,14 @@ void TLAS::Build()
         leaf.BLASidx = (uint32_t)i; leaf.leftRight = 0;
         slot[i] = (int)nodesUsed_++;
     }
-    int A = 0, B = FindBestMatch(slot, live, A);
+    // No pair of boxes with a union area below RT_REALLYFAR (instances 1e15 apart, NaN boxes): FindBestMatch returns -1 and the
+    // reference reads slot[-1] (tlas.cpp:24-45).  k_tlas_build reports it (status 2, "no partner"); so does the mirror.
+    const auto partner = [&](int a) {
+        const int b = FindBestMatch(slot, live, a);
+        if (b < 0) throw std::runtime_error("TLAS::Build: the clustering found no partner (boxes of area >= RT_REALLYFAR or NaN)");
+        return b;
+    };
+    int A = 0, B = live > 1 ? partner(A) : -1;
     while (live > 1) {
         int C = FindBestMatch(slot, live, B);
         if (A == C) {
@@ -668,7 +675,7 @@ void TLAS::Build()
             tlasNodes[nodesUsed_] = joined;
             slot[A] = (int)nodesUsed_++;
             slot[B] = slot[live - 1];
-            B = FindBestMatch(slot, --live, A);
+            B = --live > 1 ? partner(A) : -1;
         } else { A = B; B = C; }
     }
     tlasNodes[0] = tlasNodes[slot[A]];

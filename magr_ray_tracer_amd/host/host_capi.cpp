@@ -1,6 +1,7 @@
 // host_capi.cpp — extern "C" wrappers (include/rt355_host.h) over the C++ host classes.
 #include <cstring>
 #include <exception>
+#include <memory>
 #include <string>
 #include "../../include/rt355.h"
 #include "../../include/rt355_host.h"
@@ -181,7 +182,8 @@ int rth_blas_ranges(RthScene* s, int32_t* firstOut, int32_t* countOut)
     return rt_blas_ranges(b.bvhNodes.data(), (int32_t)b.bvhNodes.size(), b.primIdx.data(), (int32_t)b.primIdx.size(), (int32_t)s->scene.primitives.size(),
                           s->scene.blasNodes.data(), (int32_t)s->scene.blasNodes.size(), firstOut, countOut);
 }
-int rth_build_tlas(RthScene* s) { GUARD(delete s->tlas; s->tlas = new TLAS(*s->scene.bvh2); s->tlas->Build()) }
+// (a refused build - too many instances, a singular transform, no partner - leaves the TLAS the scene had)
+int rth_build_tlas(RthScene* s) { GUARD(std::unique_ptr<TLAS> t(new TLAS(*s->scene.bvh2)); t->Build(); delete s->tlas; s->tlas = t.release()) }
 int rth_set_instance_transform(RthScene* s, int blas, const float invT[16])
 {
     if (!s || blas < 0 || blas >= (int)s->scene.blasNodes.size()) { g_herr = "rth_set_instance_transform: bad index"; return -1; }

@@ -271,6 +271,11 @@ def closest_hit(gt, O, D, tmax=None):
     out = {k: np.stack([g[k] for g in groups])[w, rows] for k in groups[0]}
     lower = np.stack([g["t"] - g["tol"] for g in groups])
     lower[w, rows] = np.inf
+    # (a group whose nearest hit is a duplicate of the winner - one class across BLAS, tlas_check.merge_duplicates - competes with
+    # its nearest hit of another class instead)
+    same = (np.stack([g["dup"] for g in groups]) == out["dup"][None]) & (out["dup"][None] >= 0)
+    same[w, rows] = False
+    lower = np.where(same, np.stack([g["t2"] for g in groups]), lower)
     out["t2"] = np.minimum(out["t2"], lower.min(axis=0))          # the other groups' nearest sure hits compete with the winner
     out["amb"] = np.stack([g["amb"] for g in groups]).min(axis=0)
     out["any_sure"] = np.stack([g["any_sure"] for g in groups]).any(axis=0)

@@ -497,6 +497,8 @@ def test_a_rebuilt_tlas_deeper_than_the_stack_is_refused_late_and_changes_nothin
             d.reset()
             d.render(cam, 1)
             ref = d.read_accum()
+            if rounds == 0:   # the frame every refusal is compared with is the oracle's frame of the grid, and shows the grid
+                assert_bits(ref, RF._oracle_frames(sa, cam, 1)[0], "the frame before the refusals")
             live = np.frombuffer(before["instances"].tobytes(), W.BVHInstance).copy()
             deep["bvhIdx"] = live["bvhIdx"]
             for builder in RB.BUILDERS:
@@ -509,8 +511,14 @@ def test_a_rebuilt_tlas_deeper_than_the_stack_is_refused_late_and_changes_nothin
                 assert_bits(b.read_accum(), ref, "the sharing partner's frame after the refusal")
             st = d.rebuild_scene(builder="sah")
             assert st["tlas_depth"] == RF._tlas_depth(sa.tlas)
-            _check(d, RB.host_rebuild(s, None, builder="sah"), f"a rebuild after the refusals (round {rounds})", **DEFAULT)
+            sa_new = RB.host_rebuild(s, None, builder="sah")
+            _check(d, sa_new, f"a rebuild after the refusals (round {rounds})", **DEFAULT)
             assert b.kernel_info() == d.kernel_info()
+            for dv in (d, b):
+                dv.seed_default()
+                dv.reset()
+                dv.render(cam, 1)
+                assert_bits(dv.read_accum(), RF._oracle_frames(sa_new, cam, 1)[0], f"the frame after the rebuild (round {rounds})")
     finally:
         b.close()
         d.close()

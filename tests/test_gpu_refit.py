@@ -8,6 +8,7 @@ import refit_check as R
 import test_gpu_groundtruth as GT
 import test_groundtruth_cpu as C
 from helpers import DEFAULT, assert_bits
+from tlas_check import assert_seen
 from magr_ray_tracer_amd import _lib as W, scenes
 from magr_ray_tracer_amd.renderer import Device, Group, RtError, _update_args
 from magr_ray_tracer_amd.scenes import Scene, _std_materials, box_tris
@@ -155,13 +156,16 @@ def _chain_scene(n):
     for b in range(n):
         s.AddTriangles(np.asarray(box_tris((-0.4, -0.4, -0.4), (0.4, 0.4, 0.4)), np.float32), ["sand", "green", "red", "white"][b % 4])
         s.AddTriangles(C._soup(rng, 6, -0.4, 0.4, 0.2), "grey")
-        s.BuildBLAS(s.num_prims - 18)
+        if b == 0:   # an emissive quad above the grid and a floor under it (in the coordinates of BLAS 0, which sits at (-2, -1.5, 0))
+            s.AddQuad((1.5, 5.5, -1), (3.5, 5.5, -1), (3.5, 5.5, 1), (1.5, 5.5, 1), "white-light")
+            s.AddQuad((-1, -1.0, -2), (-1, -1.0, 2), (6, -1.0, 2), (6, -1.0, -2), "grey")
+        s.BuildBLAS(s.num_prims - (22 if b == 0 else 18))
     grid = [C.invT(np.eye(3), (-(b % 4) * 1.5 + 2.0, -(b // 4) * 1.5 + 1.5, 0.0)) for b in range(n)]
     for b in range(n):
         s.SetInstanceTransform(b, grid[b])
     s.Refit()   # (the device refits on every update: equal values, and with this the same bits on +-0 too)
     sa = s.arrays(bvh4=False)
-    view = dict(origin=(0.0, 0.0, 12.0), forward=(0.0, 0.0, -1.0), fov=60.0, aperture=0.01)
+    view = dict(origin=(0.0, 0.0, 12.0), forward=(0.0, 0.0, 1.0), fov=60.0, aperture=0.01)   # (the camera looks along -forward)
     return s, sa, view
 
 
@@ -185,7 +189,10 @@ def _tlas_depth(t):
 
 
 def _oracle_frames(sa, cam, frames, acc=None, seeds=None):
-    return Oracle(sa, Wd, Hd, **DEFAULT).render(cam, frames, accum=acc, seeds=seeds)
+    """The oracle's frames, which must show the scene (tlas_check.assert_seen): a camera that faces away renders the sky bit-exactly."""
+    r = Oracle(sa, Wd, Hd, **DEFAULT).render(cam, frames, accum=acc, seeds=seeds)
+    print("inst_visits / rays", assert_seen(r[2], r[3], "the oracle's frame"))
+    return r
 
 
 def test_shared_contexts_and_group_lanes_see_the_update_and_reconfigure(monkeypatch):
@@ -247,6 +254,7 @@ def test_refusals_return_their_code_and_change_nothing():
         d.seed_default()
         d.render(cam, 1)
         ref = d.read_accum()
+        assert_bits(ref, _oracle_frames(sa, cam, 1)[0], "the frame before the refusals")
         L = W.device_lib()
         bad_type = sa.prims[:4].copy()
         bad_type["objType"][1] = W.PRIM_SPHERE
