@@ -1,5 +1,5 @@
 // build_cores.h — the GPU BLAS builders as cores that work on device-resident arrays (sah.hip, lbvh.hip, sbvh.hip).  rt_build_bvh2_sah and
-// rt_build_bvh2 wrap them (allocate, upload, core, download); rt_rebuild_scene (rt355.hip) runs them BLAS by BLAS straight into a
+// rt_build_bvh2 wrap them (allocate, upload, core, download); rt_rebuild_scene (scene.hip) runs them BLAS by BLAS straight into a
 // scene's device arrays.  The driver side the three files share (error reporting, the per-call session, the wrappers' common tail)
 // is build_dev.h; the workgroup fold of the SAH and SBVH level kernels is fold_dev.h.
 //

@@ -20,7 +20,7 @@
 //
 // Depth bound.  Distinct keys of L significant bits: the root's common prefix is >= 64 - L bits, an internal node's prefix is
 // strictly longer than its parent's, and two distinct keys share at most 63 bits.  So a root-to-leaf path passes at most L internal
-// nodes and the tree's height (edges, BVH2::Depth and rt355.hip's bvh2_depth, which counts the root as 0) is <= L <= 63: every
+// nodes and the tree's height (edges, BVH2::Depth and scene.hip's bvh2_depth, which counts the root as 0) is <= L <= 63: every
 // tree fits the 64-entry traversal stack rt_validate_scene checks.  The collapse only lowers it.
 //
 // Floating point: strict binary32 in source order on both sides (-ffp-contract=off everywhere, correctly rounded division on the
@@ -45,7 +45,7 @@ constexpr uint32_t kNone = 0xffffffffu;
 constexpr int   kDefaultMaxLeaf = 8;
 constexpr float kDefaultCostTraverse = 1.0f;
 constexpr float kDefaultCostIntersect = 1.0f;
-constexpr int   kMaxLeafLimit = 127;           // larger leaves would lose the derived traversal layout (rt355.hip, layout 1)
+constexpr int   kMaxLeafLimit = 127;           // larger leaves would lose the derived traversal layout (scene.hip, layout 1)
 
 struct Box { float mn[4], mx[4]; };
 

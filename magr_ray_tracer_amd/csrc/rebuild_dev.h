@@ -1,4 +1,4 @@
-// rebuild_dev.h — the interface between rt355.hip's rt_rebuild_scene and rebuild.hip's kernels.
+// rebuild_dev.h — the interface between scene.hip's rebuild_scene (rt_rebuild_scene) and rebuild.hip's kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,7 +11,7 @@ constexpr uint32_t kMaxLevels = RT_BVH4_STACK;     // a BLAS deeper than the tra
 constexpr uint32_t kCnt = 0, kBase = kMaxLevels + 2, kStatus = 2 * (kMaxLevels + 2), kLargestLeaf = kStatus + 1, kCtrWords = kStatus + 2;
 constexpr uint32_t kWalk = 1;                      // status bit: the walk did not end where the builder said (an inconsistent tree)
 
-// scratch of the derivation, sized for trees of N nodes in all (rt355.hip grows it with the trees): flags / ranks / newId N words,
+// scratch of the derivation, sized for trees of N nodes in all (scene.hip grows it with the trees): flags / ranks / newId N words,
 // frontA / frontB frontCap (>= the interior nodes, N / 2) words, ctr kCtrWords words, scan: scan_bytes(N)
 struct Work { uint32_t *flags, *ranks, *newId, *frontA, *frontB, *ctr; uint32_t frontCap; void* scan; size_t scanBytes; };
 

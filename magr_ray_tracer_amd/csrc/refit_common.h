@@ -1,5 +1,5 @@
 // refit_common.h — the scalar rules of an in-place scene update (rt_update_scene, include/rt355.h), compiled by hipcc for the device
-// path (rt355.hip's upload, refit.hip's kernels) and by g++ for the host restatement (host/refit_host.cpp, rth_refit) and the host
+// path (scene.hip's upload, refit.hip's kernels) and by g++ for the host restatement (host/refit_host.cpp, rth_refit) and the host
 // TLAS builder (accel_build.cpp).  Every value an update writes is computed by one of these functions on both sides, so that the
 // device arrays after an update are bit for bit those a fresh rt_upload_scene of the host-refit scene produces.
 //

@@ -1,0 +1,733 @@
+// scene.hip — the device copy of a scene (SceneBag, scene_dev.h) through its life: the host-side checks of the arrays, the upload and
+// what it derives, in-place updates and rebuilds, the debug views.  Host code only: the kernels it drives are refit.hip's, rebuild.hip's
+// and the builders'; of the contexts that render from a copy (rt355.hip) it knows SceneBag::wait_holders and nothing else.
+#include <chrono>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include "scene_dev.h"
+
+using namespace scenedev;
+
+static int bvh2_depth(const RtBVHNode2* n, int32_t nNodes, uint32_t root)
+{
+    // iterative depth of the subtree at `root`; also validates child indices
+    std::vector<std::pair<uint32_t, int>> st; st.push_back({ root, 0 });
+    int best = 0; size_t visited = 0;
+    while (!st.empty()) {
+        auto [i, d] = st.back(); st.pop_back();
+        if (i >= (uint32_t)nNodes || ++visited > (size_t)nNodes * 2 + 2) return -1;
+        if (d > best) best = d;
+        if (n[i].count == 0) { st.push_back({ n[i].first, d + 1 }); st.push_back({ n[i].first + 1, d + 1 }); }
+    }
+    return best;
+}
+static int bvh4_stack_need(const RtBVHNode4* n, int32_t nNodes, int32_t nIdx, uint32_t root)
+{
+    // worst-case live stack entries of the unordered 4-wide traversal (push every interior child, pop one); the slots have passed
+    // rebuild::bvh4_slot, so a child is what the kernel pushes
+    std::vector<std::pair<uint32_t, int>> st; st.push_back({ root, 0 });
+    int best = 0; size_t visited = 0;
+    while (!st.empty()) {
+        auto [i, base] = st.back(); st.pop_back();
+        if (++visited > (size_t)nNodes + 1) return -1;   // (in range: the root by the caller's check, a child by the slot rule)
+        int kids = 0;
+        for (int k = 0; k < 4; k++) if (rebuild::bvh4_slot(n[i], k, nNodes, nIdx) == rebuild::kSlotChild) kids++;
+        if (base + kids > best) best = base + kids;
+        int pushed = 0;
+        for (int k = 0; k < 4; k++) if (rebuild::bvh4_slot(n[i], k, nNodes, nIdx) == rebuild::kSlotChild) {
+            // child k is popped when the (kids-1-pushed) later siblings are gone: entries below it = base + pushed
+            st.push_back({ (uint32_t)n[i].first[k], base + pushed });
+            pushed++;
+        }
+    }
+    return best;
+}
+
+// Host-side shape checks of a scene (no device needed; rt_upload_scene runs them first): a kernel that walks a malformed tree can
+// fault the GPU.  Also sizes the LDS traversal stack and the texture padding.
+int scenedev::validate_scene(int accel, const HostScene& in, int* stackEntriesOut, int64_t* texPadOut, int* tlasDepthOut)
+{
+    const auto& [prims, nPrims, mats, nMats, textures, nTexels, lights, nLights, bvhNodes, nNodes, primIdx, nIdx, tlas, nTlas, blas, nBlas] = in;
+    if (accel != RT_ACCEL_BVH2 && accel != RT_ACCEL_BVH4) return fail(RT_E_INVALID, "rt_upload_scene: unknown accel %d", accel);
+    if (!prims || nPrims <= 0 || !mats || nMats <= 0 || !bvhNodes || nNodes <= 0 || !primIdx || nIdx <= 0 || !tlas || nTlas <= 0 || !blas || nBlas <= 0)
+        return fail(RT_E_INVALID, "rt_upload_scene: missing array (prims/materials/bvh/primIdx/tlas/blas are required)");
+    if (nLights < 0 || nTexels < 0) return fail(RT_E_INVALID, "rt_upload_scene: negative count (nLights %d, nTexels %d)", nLights, nTexels);
+    if (nLights > 0 && !lights) return fail(RT_E_INVALID, "rt_upload_scene: nLights > 0 but lights == NULL");
+    if (nTexels > 0 && !textures) return fail(RT_E_INVALID, "rt_upload_scene: nTexels > 0 but textures == NULL");
+    // Child ids and instance ids of the TLAS travel as 15-bit values on the traversal stacks (bit 15 = leaf; the reference's own
+    // TLASNode packs two 16-bit child ids into leftRight and TLAS::Build stops at 256 instances, tlas.cpp:11): larger trees are refused.
+    if (nTlas > 0x8000 || nBlas > 0x8000) return fail(RT_E_UNSUPPORTED, "rt_upload_scene: %d TLAS nodes / %d instances exceed the 32768 the traversal stacks encode", nTlas, nBlas);
+    for (int32_t i = 0; i < nPrims; i++) {
+        if (prims[i].matIdx < 0 || prims[i].matIdx >= nMats) return fail(RT_E_INVALID, "primitive %d: matIdx %d out of range", i, prims[i].matIdx);
+        if (prims[i].objType < 0 || prims[i].objType > 2) return fail(RT_E_INVALID, "primitive %d: objType %d", i, prims[i].objType);
+    }
+    for (int32_t i = 0; i < nIdx; i++) if (primIdx[i] >= (uint32_t)nPrims) return fail(RT_E_INVALID, "primIdx[%d] = %u out of range", i, primIdx[i]);
+    for (int32_t i = 0; i < nLights; i++) if (lights[i] >= (uint32_t)nPrims) return fail(RT_E_INVALID, "lights[%d] out of range", i);
+    int64_t texPad = 2; // the reference's lookup can land one row + one texel past a texture (uv == 1): pad the atlas
+    for (int32_t i = 0; i < nMats; i++) if (mats[i].texIdx != -1) {
+        if (mats[i].texIdx < 0 || mats[i].texW <= 0 || mats[i].texH <= 0 ||
+            (int64_t)mats[i].texIdx + (int64_t)mats[i].texW * mats[i].texH > (int64_t)nTexels)
+            return fail(RT_E_INVALID, "material %d: texture window exceeds the atlas", i);
+        texPad = std::max<int64_t>(texPad, (int64_t)mats[i].texW + 2);
+    }
+    for (int32_t i = 0; i < nTlas; i++) {
+        const uint32_t lr = tlas[i].leftRight;
+        if (lr == 0) { if (tlas[i].BLASidx >= (uint32_t)nBlas) return fail(RT_E_INVALID, "tlas node %d: BLASidx out of range", i); }
+        else if ((lr & 0xffffu) >= (uint32_t)nTlas || (lr >> 16) >= (uint32_t)nTlas) return fail(RT_E_INVALID, "tlas node %d: child out of range", i);
+    }
+    int tlasDepth = 0;
+    {   // walk the TLAS from node 0: a back reference would make traverse_tlas spin forever, and its private stack holds
+        // RT_TLAS_STACK entries (the ordered descent keeps at most one pending sibling per level, so depth bounds the stack)
+        std::vector<std::pair<uint32_t, int>> st; st.push_back({ 0u, 0 });
+        size_t visited = 0;
+        while (!st.empty()) {
+            auto [i, d] = st.back(); st.pop_back();
+            if (++visited > (size_t)nTlas) return fail(RT_E_INVALID, "tlas: a node is reachable twice (cycle or shared child)");
+            tlasDepth = std::max(tlasDepth, d);
+            const uint32_t lr = tlas[i].leftRight;
+            if (lr != 0) { st.push_back({ lr & 0xffffu, d + 1 }); st.push_back({ lr >> 16, d + 1 }); }
+        }
+        if (tlasDepth > RT_TLAS_STACK) return fail(RT_E_UNSUPPORTED, "tlas: depth %d exceeds the %d-entry traversal stack", tlasDepth, RT_TLAS_STACK);
+    }
+    // The reference kernels give BVH2 32 and BVH4 64 stack entries (bvh.cl:15,57) and overflow silently beyond that
+    // (SBVH trees at alpha = 0 do get deeper than 32); this library sizes the LDS stack to the tree, up to 64 entries.
+    const int stackCap = RT_BVH4_STACK;
+    int stackNeed = 1;
+    if (accel == RT_ACCEL_BVH4) {   // every slot of every node, before anything follows one (the rule: rebuild_common.h, bvh4_slot)
+        const RtBVHNode4* n4 = (const RtBVHNode4*)bvhNodes;
+        for (int32_t i = 0; i < nNodes; i++) for (int k = 0; k < 4; k++) if (rebuild::bvh4_slot(n4[i], k, nNodes, nIdx) == rebuild::kSlotBad)
+            return fail(RT_E_INVALID, "bvh4 node %d slot %d: first %d, count %d is neither unused (first = -1), a leaf range inside primIdx nor a child node", i, k,
+                        n4[i].first[k], n4[i].count[k]);
+    }
+    for (int32_t b = 0; b < nBlas; b++) {
+        if (blas[b].bvhIdx >= (uint32_t)nNodes) return fail(RT_E_INVALID, "instance %d: bvhIdx out of range", b);
+        int need = accel == RT_ACCEL_BVH4 ? bvh4_stack_need((const RtBVHNode4*)bvhNodes, nNodes, nIdx, blas[b].bvhIdx)
+                                          : bvh2_depth((const RtBVHNode2*)bvhNodes, nNodes, blas[b].bvhIdx);
+        if (need < 0) return fail(RT_E_INVALID, "instance %d: malformed BVH (child index out of range or cycle)", b);
+        if (rebuild::exceeds_stack(need)) return fail(RT_E_UNSUPPORTED, "instance %d: traversal needs %d stack entries, at most %d are supported", b, need, stackCap);
+        stackNeed = std::max(stackNeed, need);
+    }
+    if (accel == RT_ACCEL_BVH2) {
+        const RtBVHNode2* n2 = (const RtBVHNode2*)bvhNodes;
+        for (int32_t i = 0; i < nNodes; i++) if (n2[i].count > 0 && (uint64_t)n2[i].first + n2[i].count > (uint64_t)nIdx)
+            return fail(RT_E_INVALID, "bvh node %d: leaf range exceeds primIdx", i);
+    }
+    if (stackEntriesOut) *stackEntriesOut = rebuild::stack_entries(stackNeed);   // (rebuild_common.h: rt_rebuild_scene sizes it the same way)
+    if (texPadOut) *texPadOut = texPad;
+    if (tlasDepthOut) *tlasDepthOut = tlasDepth;
+    return RT_OK;
+}
+extern "C" int rt_validate_scene(int32_t accel, const RtPrimitive* prims, int32_t nPrims, const RtMaterial* mats, int32_t nMats,
+                                 const RtFloat4* textures, int32_t nTexels, const uint32_t* lights, int32_t nLights,
+                                 const void* bvhNodes, int32_t nNodes, const uint32_t* primIdx, int32_t nIdx,
+                                 const RtTLASNode* tlas, int32_t nTlas, const RtBVHInstance* blas, int32_t nBlas)
+{
+    return validate_scene(accel, HostScene{ prims, nPrims, mats, nMats, textures, nTexels, lights, nLights, bvhNodes, nNodes, primIdx, nIdx, tlas, nTlas, blas, nBlas },
+                          nullptr, nullptr, nullptr);
+}
+
+// What rt_update_scene needs of an upload: the counts, the host shadow of the fields an update must keep, and the refit topology on
+// the device (parents, reachable leaves, pair id -> node id).  A scene the update cannot handle records why (refitRefusal).
+static int prepare_update(SceneBag& b, int accel, int extendVariant, const HostScene& in, const std::vector<uint32_t>& pairNode)
+{
+    const auto& [prims, nPrims, mats, nMats, textures, nTexels, lights, nLights, bvhNodes, nNodes, primIdx, nIdx, tlas, nTlas, blas, nBlas] = in;
+    b.nPrims = nPrims; b.nNodes = nNodes; b.nIdx = nIdx; b.nLights = nLights; b.nTlas = nTlas; b.nBlas = nBlas;
+    b.nPairs = (int32_t)pairNode.size(); b.accel = accel;
+    if (accel != RT_ACCEL_BVH2) { b.refitRefusal = "BVH4 scenes cannot be refit"; return RT_OK; }
+    if (nBlas > refit::kMaxInstances) { b.refitRefusal = "more than 256 instances (TLAS::Build's limit)"; return RT_OK; }
+    if (nTlas != 2 * nBlas) { b.refitRefusal = "the TLAS does not have TLAS::Build's 2 x instances nodes"; return RT_OK; }
+    refit::Topology t;
+    if (const char* why = refit::build_topology((const RtBVHNode2*)bvhNodes, nNodes, blas, nBlas, t)) { b.refitRefusal = why; return RT_OK; }
+    b.primType.resize((size_t)nPrims); b.primMat.resize((size_t)nPrims);
+    for (int32_t i = 0; i < nPrims; i++) { b.primType[(size_t)i] = prims[i].objType; b.primMat[(size_t)i] = prims[i].matIdx; }
+    b.inst.assign(blas, blas + nBlas);
+    b.variantLayout1 = extendVariant != 1;
+    // rt_rebuild_scene: the primitive range of each BLAS (rebuild_common.h)
+    b.rebuildRefusal = rebuild::find_blas_ranges((const RtBVHNode2*)bvhNodes, nNodes, primIdx, nIdx, nPrims, blas, nBlas, b.ranges, b.instBlas);
+    b.nLeaves = (uint32_t)t.leaves.size(); b.nReach = (uint32_t)t.order.size();
+    int rc = dalloc(b.allocs, &b.dParent, t.parent.size());
+    if (rc == RT_OK) rc = dalloc(b.allocs, &b.dLeaves, t.leaves.size());
+    if (rc == RT_OK) rc = dalloc(b.allocs, &b.dTickets, (size_t)nNodes);
+    if (rc == RT_OK) rc = dalloc(b.allocs, &b.dPairNode, pairNode.size());
+    if (rc != RT_OK) return rc;
+    HIPCHK(hipMemcpy(b.dParent, t.parent.data(), sizeof(uint32_t) * t.parent.size(), hipMemcpyHostToDevice));
+    if (!t.leaves.empty()) HIPCHK(hipMemcpy(b.dLeaves, t.leaves.data(), sizeof(uint32_t) * t.leaves.size(), hipMemcpyHostToDevice));
+    if (!pairNode.empty()) HIPCHK(hipMemcpy(b.dPairNode, pairNode.data(), sizeof(uint32_t) * pairNode.size(), hipMemcpyHostToDevice));
+    return RT_OK;
+}
+
+// ---- scene upload: validate (above), derive, copy to device, bind.  What it derives, as functions of the host arrays; the record rules
+// are refit_common.h's and rebuild_common.h's (the kernels of an update or a rebuild write the same records) ---------------------------
+static std::vector<RtFloat4> shade_records(const RtPrimitive* prims, int32_t nPrims)   // k_shade: geometric normal + material id + type per primitive
+{
+    std::vector<RtFloat4> recs((size_t)nPrims);
+    for (int32_t i = 0; i < nPrims; i++) recs[(size_t)i] = refit::shade_rec(prims[i]);
+    return recs;
+}
+// k_shade, NEE: the first 64 bytes of the light's Primitive, {objType, area}, its material's emittance (k_light_recs rewrites words 0..4)
+static std::vector<RtFloat4> light_records(const RtPrimitive* prims, const RtMaterial* mats, const uint32_t* lights, int32_t nLights)
+{
+    std::vector<RtFloat4> lr(std::max<size_t>((size_t)nLights, 1) * 8, RtFloat4{ 0, 0, 0, 0 });
+    for (int32_t i = 0; i < nLights; i++) {
+        const RtPrimitive& p = prims[lights[i]];
+        refit::light_rec(p, &lr[(size_t)i * 8]);
+        lr[(size_t)i * 8 + 5] = mats[p.matIdx].emittance;
+    }
+    return lr;
+}
+static std::vector<RtFloat4> triangle_records(const RtPrimitive* prims, const uint32_t* primIdx, int32_t nIdx)   // leaf-ordered vertices + primitive id
+{
+    std::vector<RtFloat4> recs((size_t)nIdx * 3);
+    for (int32_t s = 0; s < nIdx; s++) refit::tri_rec(prims[primIdx[s]], primIdx[s], &recs[(size_t)s * 3]);
+    return recs;
+}
+// The nodes a derived table keeps, renumbered breadth-first, BLAS by BLAS, and stored densely: breadth-first puts the top levels of
+// the (first) tree, which every ray visits, into the first records.  kids(i, number) calls number(c) for every child c of node i that
+// gets a record; newId (all rebuild::kNone) receives node id -> record id.
+template <class Kids> static std::vector<uint32_t> breadth_first(const std::vector<uint32_t>& roots, std::vector<uint32_t>& newId, Kids kids)
+{
+    std::vector<uint32_t> order;
+    auto number = [&](uint32_t c) { if (newId[c] == rebuild::kNone) { newId[c] = (uint32_t)order.size(); order.push_back(c); } };
+    for (const uint32_t root : roots) {
+        size_t head = order.size();
+        number(root);
+        for (; head < order.size(); head++) kids(order[head], number);
+    }
+    return order;
+}
+// Layout 1 of a BVH2 (rt355_kernels.h, traverse_bvh2_packed): a record per interior node - the reference array interleaves leaves and
+// interior nodes (children are allocated in pairs), so a table indexed by the reference's node id would be half holes.  `order`
+// receives pair id -> node id (rt_update_scene rewrites the pairs' boxes), `roots` every instance's encoded root.
+static std::vector<RtFloat4> pair_records(const RtBVHNode2* n2, int32_t nNodes, const RtBVHInstance* blas, int32_t nBlas, std::vector<uint32_t>& order,
+                                          std::vector<uint32_t>& roots)
+{
+    std::vector<uint32_t> newId((size_t)nNodes, rebuild::kNone), interiorRoots;
+    for (int32_t b = 0; b < nBlas; b++) if (n2[blas[b].bvhIdx].count == 0) interiorRoots.push_back(blas[b].bvhIdx);
+    order = breadth_first(interiorRoots, newId, [&](uint32_t i, auto& number) {
+        for (uint32_t c = n2[i].first; c <= n2[i].first + 1; c++) if (n2[c].count == 0) number(c);
+    });
+    std::vector<RtFloat4> pairs(std::max<size_t>(order.size(), 1) * 4, RtFloat4{ 0, 0, 0, 0 });
+    for (size_t k = 0; k < order.size(); k++) rebuild::pair_record(n2, order[k], newId.data(), &pairs[k * 4]);   // (k_pair_boxes rewrites the boxes)
+    for (int32_t b = 0; b < nBlas; b++) roots[(size_t)b] = rebuild::child_entry(n2[blas[b].bvhIdx], newId[blas[b].bvhIdx]);
+    return pairs;
+}
+// Layout 1 of a BVH4: four child boxes + four encoded child entries per node.  The collapse (bvh.cpp:695-803) leaves the absorbed BVH2
+// nodes in the array: only the nodes still reachable from a BLAS root are kept (on the bench scene 1 node in 4 is alive).
+static std::vector<RtFloat4> quad_records(const RtBVHNode4* n4, int32_t nNodes, int32_t nIdx, const RtBVHInstance* blas, int32_t nBlas, std::vector<uint32_t>& roots)
+{
+    std::vector<uint32_t> newId((size_t)nNodes, rebuild::kNone), all((size_t)nBlas);
+    for (int32_t b = 0; b < nBlas; b++) all[(size_t)b] = blas[b].bvhIdx;
+    const std::vector<uint32_t> order = breadth_first(all, newId, [&](uint32_t i, auto& number) {
+        for (int k = 0; k < 4; k++) if (rebuild::bvh4_slot(n4[i], k, nNodes, nIdx) == rebuild::kSlotChild) number((uint32_t)n4[i].first[k]);
+    });
+    auto f2u = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
+    std::vector<RtFloat4> quads(std::max<size_t>(order.size(), 1) * 8, RtFloat4{ 0, 0, 0, 0 });
+    for (size_t q = 0; q < order.size(); q++) {
+        const uint32_t i = order[q];
+        float b[24]; uint32_t e[4];
+        for (int k = 0; k < 4; k++) {
+            const RtFloat4& mn = n4[i].aabbMin[k]; const RtFloat4& mx = n4[i].aabbMax[k];
+            b[k * 6 + 0] = mn.x; b[k * 6 + 1] = mn.y; b[k * 6 + 2] = mn.z; b[k * 6 + 3] = mx.x; b[k * 6 + 4] = mx.y; b[k * 6 + 5] = mx.z;
+            const int slot = rebuild::bvh4_slot(n4[i], k, nNodes, nIdx);
+            if (slot == rebuild::kSlotUnused) e[k] = 0xffffffffu;
+            else if (slot == rebuild::kSlotLeaf) e[k] = 0x80000000u | ((uint32_t)n4[i].count[k] << 24) | (uint32_t)n4[i].first[k];
+            else e[k] = newId[(uint32_t)n4[i].first[k]];
+        }
+        for (int v = 0; v < 6; v++) quads[q * 8 + v] = RtFloat4{ b[v * 4], b[v * 4 + 1], b[v * 4 + 2], b[v * 4 + 3] };
+        quads[q * 8 + 6] = RtFloat4{ f2u(e[0]), f2u(e[1]), f2u(e[2]), f2u(e[3]) };
+    }
+    for (int32_t b = 0; b < nBlas; b++) roots[(size_t)b] = newId[blas[b].bvhIdx];
+    return quads;
+}
+// TLAS interior records (traverse_tlas; tagged: the children in the encoding of k_trace_persist_tlas) and instance records (traverse_instance)
+static std::vector<RtFloat4> tlas_records(const RtTLASNode* tlas, int32_t nTlas, bool tagged)
+{
+    std::vector<RtFloat4> tp((size_t)nTlas * 4, RtFloat4{ 0, 0, 0, 0 });
+    for (int32_t i = 0; i < nTlas; i++) refit::tlas_pair(tlas, (uint32_t)i, tagged, &tp[(size_t)i * 4]);   // (k_tlas_build)
+    return tp;
+}
+static std::vector<RtFloat4> instance_records(const RtBVHInstance* blas, int32_t nBlas, const std::vector<uint32_t>& roots)
+{
+    std::vector<RtFloat4> ir((size_t)nBlas * 4);
+    for (int32_t b = 0; b < nBlas; b++) refit::inst_rec(blas[b], roots[(size_t)b], &ir[(size_t)b * 4]);
+    return ir;
+}
+
+template <class T> static int upload(SceneBag& b, T** dst, const T* src, size_t count)
+{
+    const int rc = dalloc(b.allocs, dst, count);
+    if (rc != RT_OK) return rc;
+    if (count) HIPCHK(hipMemcpy(*dst, src, count * sizeof(T), hipMemcpyHostToDevice));
+    return RT_OK;
+}
+template <class T> static int upload(SceneBag& b, T** dst, const std::vector<T>& v) { return upload(b, dst, v.data(), v.size()); }
+
+int scenedev::upload_scene(SceneBag& b, int accel, int extendVariant, const HostScene& in, int stackEntries, int64_t texPad, int tlasDepth)
+{
+    const auto& [prims, nPrims, mats, nMats, textures, nTexels, lights, nLights, bvhNodes, nNodes, primIdx, nIdx, tlas, nTlas, blas, nBlas] = in;
+    // ---- derive.  Layout 1 (pair or quad records, triangle records, encoded roots) only when the encodings fit (rebuild_common.h,
+    // shared with rt_rebuild_scene's kernels); in layout 0 the instance records carry root entry 0
+    const RtBVHNode2* n2 = (const RtBVHNode2*)bvhNodes; const RtBVHNode4* n4 = (const RtBVHNode4*)bvhNodes;
+    std::vector<uint32_t> pairNode, roots((size_t)nBlas, 0u);
+    std::vector<RtFloat4> pairs, quads;
+    int layout = 0;
+    if (accel == RT_ACCEL_BVH2) {
+        uint32_t largestLeaf = 0;
+        for (int32_t i = 0; i < nNodes; i++) largestLeaf = std::max(largestLeaf, n2[i].count);
+        if (rebuild::takes_layout1(extendVariant != 1, nIdx, largestLeaf)) { pairs = pair_records(n2, nNodes, blas, nBlas, pairNode, roots); layout = 1; }
+    } else if (extendVariant != 1 && nIdx < (1 << 24)) {
+        bool fits = true;
+        for (int32_t i = 0; i < nNodes && fits; i++) for (int k = 0; k < 4; k++) if (n4[i].first[k] != RT_INVALID && n4[i].count[k] > (int32_t)rebuild::kMaxPackedLeaf) fits = false;
+        if (fits) { quads = quad_records(n4, nNodes, nIdx, blas, nBlas, roots); layout = 1; }
+    }
+    // ---- copy to device
+    SceneArrays sc{};
+    int rc = upload(b, &sc.prims, prims, (size_t)nPrims);
+    if (rc == RT_OK) rc = upload(b, &sc.mats, mats, (size_t)nMats);
+    if (rc == RT_OK) rc = dalloc(b.allocs, &sc.tex, (size_t)nTexels + (size_t)texPad);   // zero-padded atlas (texPad: validate_scene)
+    if (rc == RT_OK) {
+        HIPCHK(hipMemset(sc.tex, 0, sizeof(RtFloat4) * ((size_t)nTexels + (size_t)texPad)));
+        if (nTexels) HIPCHK(hipMemcpy(sc.tex, textures, sizeof(RtFloat4) * (size_t)nTexels, hipMemcpyHostToDevice));
+    }
+    if (rc == RT_OK) rc = upload(b, &sc.lights, lights, (size_t)nLights);
+    if (rc == RT_OK) rc = accel == RT_ACCEL_BVH4 ? upload(b, &sc.bvh4, n4, (size_t)nNodes) : upload(b, &sc.bvh2, n2, (size_t)nNodes);
+    if (rc == RT_OK) rc = upload(b, &sc.primIdx, primIdx, (size_t)nIdx);
+    if (rc == RT_OK) rc = upload(b, &sc.tlas, tlas, (size_t)nTlas);
+    if (rc == RT_OK) rc = upload(b, &sc.blas, blas, (size_t)nBlas);
+    if (rc == RT_OK) rc = upload(b, &sc.shadeRecs, shade_records(prims, nPrims));
+    if (rc == RT_OK) rc = upload(b, &sc.lightRecs, light_records(prims, mats, lights, nLights));
+    if (rc == RT_OK && layout == 1) {
+        rc = accel == RT_ACCEL_BVH4 ? upload(b, &sc.quads, quads) : upload(b, &sc.pairs, pairs);
+        if (rc == RT_OK) rc = upload(b, &sc.triRecs, triangle_records(prims, primIdx, nIdx));
+        if (rc == RT_OK) rc = upload(b, &sc.rootEntry, roots);
+    }
+    if (rc == RT_OK) rc = upload(b, &sc.tlasPairs, tlas_records(tlas, nTlas, false));
+    if (rc == RT_OK) rc = upload(b, &sc.instRecs, instance_records(blas, nBlas, roots));
+    if (rc == RT_OK) rc = upload(b, &sc.tlasPairsP, tlas_records(tlas, nTlas, true));
+    if (rc != RT_OK) return rc;
+    const bool leafRoot = tlas[0].leftRight == 0;
+    sc.tlasRoot = leafRoot ? (refit::kLeafBit | tlas[0].BLASidx) : 0u;
+    sc.tlasRootP = leafRoot ? (refit::kTagInst | tlas[0].BLASidx) : refit::kTagTlas;
+    sc.nLights = nLights; sc.nPrims = nPrims; sc.nBlas = nBlas; sc.nTex = nTexels;
+    // ---- bind: the copy's facts, and what updates and rebuilds need of this upload
+    b.sc = sc;
+    b.layout = layout; b.stackEntries = stackEntries; b.tlasDepth = tlasDepth; b.nInterior = (int)pairNode.size(); b.singleBlas = leafRoot;
+    return prepare_update(b, accel, extendVariant, in, pairNode);
+}
+
+// ---- in-place scene updates (rt_update_scene; kernels: refit.hip, rules: refit_common.h) and what they share with a rebuild -----------
+namespace refitdev {
+hipError_t launch_refit(hipStream_t s, RtBVHNode2* nodes, uint32_t nNodes, const RtPrimitive* prims, const uint32_t* primIdx, const uint32_t* leaves,
+                        uint32_t nLeaves, const uint32_t* parent, uint32_t* tickets);
+hipError_t launch_tlas(hipStream_t s, const RtBVHNode2* nodes, const RtBVHInstance* inst, int n, const uint32_t* rootEntry, RtTLASNode* tlas, RtFloat4* tp,
+                       RtFloat4* tpP, RtFloat4* ir, int32_t* status);
+hipError_t launch_records(hipStream_t s, const RtPrimitive* prims, const RtBVHNode2* nodes, const uint32_t* primIdx, uint32_t nIdx, const uint32_t* lights,
+                          uint32_t nLights, uint32_t first, uint32_t count, const uint32_t* pairNode, uint32_t nPairs, RtFloat4* pairs, RtFloat4* triRecs,
+                          RtFloat4* shadeRecs, RtFloat4* lightRecs);
+}
+
+// Capacities of what scales with the trees (SceneBag::RebuildSet, the derivation's scratch, rt_update_scene's staging nodes): index
+// slots at first, twice as many nodes; RT355_REBUILD_INITIAL_CAP=k (read per call; tests, A/B runs) starts smaller or larger.  An array
+// that a finished tree outgrows goes to the need plus need / kRebuildHeadroomDiv: a quarter covers the frame-to-frame drift of an
+// animated SBVH scene (its slot count moved by a few percent between the deformations tried), so a per-frame rebuild stops allocating
+// once both sets have grown, and costs at most that much idle memory.
+constexpr size_t kRebuildHeadroomDiv = 4;
+static size_t rebuild_initial_cap(const SceneBag& b)
+{
+    if (const char* env = getenv("RT355_REBUILD_INITIAL_CAP")) {
+        const long long k = atoll(env);
+        if (k > 0) return (size_t)std::min<long long>(k, 1ll << 30);
+    }
+    return (size_t)std::max(b.nPrims, 1);
+}
+
+// What an update and a rebuild refuse alike, before anything is written: `prims` replaces the primitives [first, first + count), `blas`
+// (may be NULL) the instances.  typeSuffix ends the message about a changed objType / matIdx.
+static int check_change(const char* who, const SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
+                        const char* typeSuffix)
+{
+    if (count < 0 || (count > 0 && !prims)) return fail(RT_E_INVALID, "%s: bad primitive count %d / NULL records", who, count);
+    if (count > 0 && (first < 0 || (int64_t)first + count > (int64_t)b.nPrims))
+        return fail(RT_E_INVALID, "%s: primitive range [%d, %lld) outside the %d uploaded", who, first, (long long)first + count, b.nPrims);
+    for (int32_t i = 0; i < count; i++) {
+        const size_t g = (size_t)first + (size_t)i;
+        if (prims[i].objType != b.primType[g] || prims[i].matIdx != b.primMat[g])
+            return fail(RT_E_INVALID, "%s: primitive %zu changes its objType / matIdx (%d / %d -> %d / %d)%s", who, g,
+                        b.primType[g], b.primMat[g], prims[i].objType, prims[i].matIdx, typeSuffix);
+    }
+    if (blas) {
+        if (nBlas != b.nBlas) return fail(RT_E_INVALID, "%s: %d instances given, %d uploaded", who, nBlas, b.nBlas);
+        for (int32_t k = 0; k < nBlas; k++) {
+            if (blas[k].bvhIdx != b.inst[(size_t)k].bvhIdx) return fail(RT_E_INVALID, "%s: instance %d changes its bvhIdx", who, k);
+            if (refit::singular(blas[k].invT)) return fail(RT_E_INVALID, "%s: instance %d: the transform is singular", who, k);
+        }
+    }
+    return RT_OK;
+}
+// k_tlas_build's two status words (what went wrong, the height of the new TLAS) as the error of the call that ran it
+static int tlas_status_error(const char* who, const int32_t status[2])
+{
+    if (status[0] == 1) return fail(RT_E_INVALID, "%s: an instance transform is singular", who);
+    if (status[0] != 0) return fail(RT_E_UNSUPPORTED, "%s: the TLAS clustering found no partner (boxes of area >= RT_REALLYFAR or NaN)", who);
+    if (status[1] > RT_TLAS_STACK)
+        return fail(RT_E_UNSUPPORTED, "%s: the rebuilt TLAS is %d levels deep, the traversal stack holds %d; the scene is unchanged", who, status[1], RT_TLAS_STACK);
+    return RT_OK;
+}
+
+// A Grown array to at least `count` records, keeping the first `keep`: the one place that replaces (and frees) a buffer of a copy.
+// `nomem` (a format of `count`) replaces the message of a failed allocation.
+template <class T> static int rebuild_grow(SceneBag& b, SceneBag::Grown<T>& a, size_t count, size_t keep, const char* what, const char* nomem = nullptr)
+{
+    if (count <= a.cap && a.p) return RT_OK;
+    count = std::max<size_t>(count, 1);
+    void* q = nullptr;
+    if (hipMalloc(&q, count * sizeof(T)) != hipSuccess)
+        return nomem ? fail(RT_E_NOMEM, nomem, count) : fail(RT_E_NOMEM, "rt_rebuild_scene: %zu bytes of device memory for %s", count * sizeof(T), what);
+    b.rallocs++;
+    if (a.p) {
+        hipError_t e = keep ? hipMemcpyAsync(q, a.p, keep * sizeof(T), hipMemcpyDeviceToDevice, b.stream) : hipSuccess;
+        if (e == hipSuccess) e = hipStreamSynchronize(b.stream);
+        if (e != hipSuccess) { (void)hipFree(q); return fail(RT_E_DEVICE, "rt_rebuild_scene: moving %s failed: %s", what, hipGetErrorString(e)); }
+        (void)hipFree(a.p);
+    }
+    a.p = (T*)q; a.cap = count;
+    return RT_OK;
+}
+int scenedev::update_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas, RtUpdateStats* stats)
+{
+    const char* who = "rt_update_scene";
+    // ---- refusals: before anything is written
+    if (b.refitRefusal) return fail(RT_E_UNSUPPORTED, "rt_update_scene: %s", b.refitRefusal);
+    if (const int rc = check_change(who, b, prims, first, count, blas, nBlas, ": topology must not change")) return rc;
+    HIPCHK(hipSetDevice(b.device));
+    // ---- staging buffers (first update)
+    if (!b.sPrims) {
+        int rc = dalloc(b.allocs, &b.sPrims, (size_t)b.nPrims);
+        if (rc == RT_OK) rc = dalloc(b.allocs, &b.sInst, (size_t)b.nBlas);
+        if (rc == RT_OK) rc = dalloc(b.allocs, &b.sTlas, (size_t)b.nTlas);
+        if (rc == RT_OK) rc = dalloc(b.allocs, &b.sTp, (size_t)b.nTlas * 4);
+        if (rc == RT_OK) rc = dalloc(b.allocs, &b.sTpP, (size_t)b.nTlas * 4);
+        if (rc == RT_OK) rc = dalloc(b.allocs, &b.sIr, (size_t)b.nBlas * 4);
+        if (rc == RT_OK) rc = dalloc(b.allocs, &b.sStatus, 2);
+        if (rc != RT_OK) { b.sPrims = nullptr; return rc; }
+        b.rallocs += 7;
+        if (!b.stream) HIPCHK(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));   // (a rebuild may have made it already)
+        for (hipEvent_t& e : b.ev) if (!e) HIPCHK(hipEventCreate(&e));
+    }
+    if (!b.sNodes.p || (size_t)b.nNodes > b.sNodes.cap) {
+        // the staging nodes: at first room for every tree the SAH and the linear builder can bind later; an SBVH rebuild may bind more
+        // nodes than that, then the array grows as the rebuild's sets do (nothing in it outlives a call)
+        const size_t n = (size_t)b.nNodes, cap = b.sNodes.p ? n + n / kRebuildHeadroomDiv : std::max(n, 2 * rebuild_initial_cap(b));
+        if (const int rc = rebuild_grow(b, b.sNodes, cap, 0, "the staging nodes", "rt_update_scene: %zu staging nodes")) return rc;
+    }
+    const SceneArrays& sc = b.sc;
+    hipStream_t s = b.stream;
+    // ---- stage: the new primitives, the refit tree and the rebuilt TLAS in scratch
+    HIPCHK(hipEventRecord(b.ev[0], s));
+    HIPCHK(hipMemcpyAsync(b.sPrims, sc.prims, sizeof(RtPrimitive) * (size_t)b.nPrims, hipMemcpyDeviceToDevice, s));
+    if (count) HIPCHK(hipMemcpyAsync(b.sPrims + first, prims, sizeof(RtPrimitive) * (size_t)count, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(b.sNodes.p, sc.bvh2, sizeof(RtBVHNode2) * (size_t)b.nNodes, hipMemcpyDeviceToDevice, s));
+    if (blas) HIPCHK(hipMemcpyAsync(b.sInst, blas, sizeof(RtBVHInstance) * (size_t)b.nBlas, hipMemcpyHostToDevice, s));
+    else HIPCHK(hipMemcpyAsync(b.sInst, sc.blas, sizeof(RtBVHInstance) * (size_t)b.nBlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(refitdev::launch_refit(s, b.sNodes.p, (uint32_t)b.nNodes, b.sPrims, sc.primIdx, b.dLeaves, b.nLeaves, b.dParent, b.dTickets));
+    HIPCHK(refitdev::launch_tlas(s, b.sNodes.p, b.sInst, b.nBlas, b.layout == 1 ? sc.rootEntry : nullptr, b.sTlas, b.sTp, b.sTpP, b.sIr, b.sStatus));
+    int32_t status[2] = { 0, 0 };
+    HIPCHK(hipEventRecord(b.ev[1], s));
+    HIPCHK(hipMemcpyAsync(status, b.sStatus, sizeof status, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (const int rc = tlas_status_error(who, status)) return rc;
+    // ---- commit: no kernel of a context holding this copy may read the arrays while they are rewritten
+    if (const int rc = b.wait_holders()) return rc;
+    HIPCHK(hipEventRecord(b.ev[2], s));
+    if (count) HIPCHK(hipMemcpyAsync(sc.prims + first, b.sPrims + first, sizeof(RtPrimitive) * (size_t)count, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(sc.bvh2, b.sNodes.p, sizeof(RtBVHNode2) * (size_t)b.nNodes, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(sc.blas, b.sInst, sizeof(RtBVHInstance) * (size_t)b.nBlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(sc.tlas, b.sTlas, sizeof(RtTLASNode) * (size_t)b.nTlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(sc.tlasPairs, b.sTp, sizeof(RtFloat4) * 4 * (size_t)b.nTlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(sc.tlasPairsP, b.sTpP, sizeof(RtFloat4) * 4 * (size_t)b.nTlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(sc.instRecs, b.sIr, sizeof(RtFloat4) * 4 * (size_t)b.nBlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(refitdev::launch_records(s, sc.prims, sc.bvh2, sc.primIdx, (uint32_t)b.nIdx, sc.lights, (uint32_t)b.nLights, (uint32_t)std::max(first, 0),
+                                    (uint32_t)count, b.dPairNode, (uint32_t)b.nPairs, b.layout == 1 ? sc.pairs : nullptr,
+                                    b.layout == 1 ? sc.triRecs : nullptr, sc.shadeRecs, sc.lightRecs));
+    HIPCHK(hipEventRecord(b.ev[3], s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (blas) b.inst.assign(blas, blas + nBlas);
+    const bool reconfigure = status[1] != b.tlasDepth;
+    if (reconfigure) { b.tlasDepth = status[1]; b.generation++; }
+    if (stats) {
+        float ms = 0, ms2 = 0;   // GPU time of both phases (not the wait for the holders in between)
+        (void)hipEventElapsedTime(&ms, b.ev[0], b.ev[1]); (void)hipEventElapsedTime(&ms2, b.ev[2], b.ev[3]);
+        ms += ms2;
+        *stats = RtUpdateStats{};
+        stats->gpu_ms = ms; stats->prims = count; stats->nodes = (int32_t)b.nReach; stats->tlas_nodes = b.nTlas; stats->tlas_depth = status[1];
+        stats->reconfigured = reconfigure ? 1 : 0;
+    }
+    return RT_OK;
+}
+
+// ---- in-place rebuilds (rt_rebuild_scene; builders: sah.hip / lbvh.hip / sbvh.hip, derivation: rebuild.hip, rules: rebuild_common.h) ----
+// Room in the set `t` (not live) for idxNeed index slots and nodeNeed nodes, keeping the keepIdx slots and keepNodes records emitted so
+// far.  An array that is too small goes to the need plus kRebuildHeadroomDiv-th of it; one that NOMEM stopped is taken up by a later call.
+static int rebuild_reserve(SceneBag& b, SceneBag::RebuildSet& t, size_t idxNeed, size_t nodeNeed, size_t keepIdx, size_t keepNodes)
+{
+    const bool have = t.nodes.p != nullptr;   // (the first allocation is exact: the initial capacity)
+    const size_t idxCap = idxNeed <= t.primIdx.cap ? t.primIdx.cap : idxNeed + (have ? idxNeed / kRebuildHeadroomDiv : 0);
+    size_t nodeCap = nodeNeed <= t.nodes.cap ? t.nodes.cap : nodeNeed + (have ? nodeNeed / kRebuildHeadroomDiv : 0);
+    nodeCap = (nodeCap + 1) & ~(size_t)1;
+    int rc = rebuild_grow(b, t.primIdx, idxCap, keepIdx, "primIdx");
+    if (rc == RT_OK) rc = rebuild_grow(b, t.nodes, nodeCap, keepNodes, "nodes");
+    if (rc == RT_OK) rc = rebuild_grow(b, t.triRecs, idxCap * 3, 0, "triangle records");
+    if (rc == RT_OK) rc = rebuild_grow(b, t.parent, nodeCap, 0, "parent links");
+    if (rc == RT_OK) rc = rebuild_grow(b, t.tickets, nodeCap, 0, "tickets");
+    if (rc == RT_OK) rc = rebuild_grow(b, t.pairs, std::max<size_t>(nodeCap / 2, 1) * 4, 0, "pair records");
+    if (rc == RT_OK) rc = rebuild_grow(b, t.leaves, nodeCap / 2, 0, "leaves");
+    if (rc == RT_OK) rc = rebuild_grow(b, t.pairNode, nodeCap / 2, 0, "pair nodes");
+    return rc;
+}
+// The derivation's scratch for trees of nodeNeed nodes in all (flags / ranks / newId: a word per node, the frontiers: per interior node)
+static int rebuild_scratch(SceneBag& b, size_t nodeNeed)
+{
+    const bool have = b.dwFlags.p != nullptr;
+    size_t cap = nodeNeed <= b.dwFlags.cap ? b.dwFlags.cap : nodeNeed + (have ? nodeNeed / kRebuildHeadroomDiv : 0);
+    cap = (cap + 1) & ~(size_t)1;
+    int rc = rebuild_grow(b, b.dwFlags, cap, 0, "scratch");
+    if (rc == RT_OK) rc = rebuild_grow(b, b.dwRanks, cap, 0, "scratch");
+    if (rc == RT_OK) rc = rebuild_grow(b, b.dwNewId, cap, 0, "scratch");
+    if (rc == RT_OK) rc = rebuild_grow(b, b.dwFrontA, cap / 2, 0, "scratch");
+    if (rc == RT_OK) rc = rebuild_grow(b, b.dwFrontB, cap / 2, 0, "scratch");
+    if (rc != RT_OK) return rc;
+    size_t scanBytes = 0;
+    HIPCHK(rebuilddev::scan_bytes((uint32_t)b.dwFlags.cap, b.stream, &scanBytes));
+    rc = rebuild_grow(b, b.dwScan, std::max<size_t>(scanBytes, 256), 0, "scan workspace");
+    if (rc != RT_OK) return rc;
+    b.dw.flags = b.dwFlags.p; b.dw.ranks = b.dwRanks.p; b.dw.newId = b.dwNewId.p; b.dw.frontA = b.dwFrontA.p; b.dw.frontB = b.dwFrontB.p;
+    b.dw.frontCap = (uint32_t)std::min(b.dwFrontA.cap, b.dwFrontB.cap);
+    b.dw.scan = b.dwScan.p; b.dw.scanBytes = b.dwScan.cap;
+    return RT_OK;
+}
+static int rebuild_alloc(SceneBag& b, SceneBag::RebuildSet& t)
+{
+    const size_t nP = (size_t)b.nPrims, nB = (size_t)b.nBlas, nT = (size_t)b.nTlas, nL = std::max<size_t>((size_t)b.nLights, 1);
+    int rc = RT_OK;
+    // every piece is made once: a call that ran out of memory half way is taken up where it stopped
+    auto need = [&](auto** p, size_t count) { if (rc == RT_OK && !*p) { rc = dalloc(b.allocs, p, count); if (rc == RT_OK) b.rallocs++; } };
+    if (!b.stream) HIPCHK(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));
+    for (hipEvent_t& e : b.rev) if (!e) HIPCHK(hipEventCreate(&e));
+    if (!b.spool) b.spool = sbvhdev::pool_create();
+    const size_t cap0 = rebuild_initial_cap(b);
+    // the scratch both sets share
+    need(&b.rStatus, 2); need(&b.dw.ctr, rebuilddev::kCtrWords);
+    if (rc == RT_OK && !b.dwScan.p) rc = rebuild_scratch(b, 2 * cap0);
+    if (rc != RT_OK || t.allocated) return rc;
+    need(&t.prims, nP); need(&t.blas, nB); need(&t.tlas, nT); need(&t.tp, nT * 4); need(&t.tpP, nT * 4); need(&t.ir, nB * 4);
+    need(&t.shadeRecs, nP); need(&t.lightRecs, nL * 8); need(&t.rootEntry, nB);
+    if (rc == RT_OK) rc = rebuild_reserve(b, t, std::max(cap0, t.primIdx.cap), std::max(2 * cap0, t.nodes.cap), 0, 0);
+    if (rc != RT_OK) return rc;
+    t.allocated = true;
+    return RT_OK;
+}
+
+static double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b)
+{
+    return std::chrono::duration<double, std::milli>(b - a).count();
+}
+
+int scenedev::rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
+                            int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats)
+{
+    using clock = std::chrono::steady_clock;
+    const auto t0 = clock::now();
+    const char* who = "rt_rebuild_scene";
+    // ---- refusals that need no device work
+    if (b.refitRefusal) return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: %s", b.refitRefusal);
+    if (b.rebuildRefusal) return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: %s", b.rebuildRefusal);
+    if (builder != RT_REBUILD_SAH && builder != RT_REBUILD_LBVH && builder != RT_REBUILD_SBVH) return fail(RT_E_INVALID, "rt_rebuild_scene: unknown builder %d", builder);
+    const bool sbvh = builder == RT_REBUILD_SBVH;
+    const float alpha = sbvh && opts ? opts->alpha : 0.0f;
+    if (!(alpha >= 0.0f && alpha <= 1.0f)) return fail(RT_E_INVALID, "rt_rebuild_scene: alpha must lie in [0, 1]");
+    if (const int rc = check_change(who, b, prims, first, count, blas, nBlas, "")) return rc;
+    const size_t nR = b.ranges.size();
+    // the builders' own argument checks, BLAS by BLAS (node and index ids as the host appends BLAS after BLAS; the SBVH builder's ids
+    // are known only as the trees are built: its ranges are the upload's, at most 2^30 primitives each, and alpha is checked above)
+    lbvh::Params P{};
+    if (!sbvh) {
+        uint32_t nodeBase = 0, idxBase = 0;
+        for (const rebuild::BlasRange& r : b.ranges) {
+            const int32_t cap = 2 * (int32_t)r.count - 1;
+            const char* msg = builder == RT_REBUILD_SAH ? sahdev::check_args(b.nPrims, (int32_t)r.first, (int32_t)r.count, nodeBase, idxBase)
+                                                        : lbvhdev::check_args(opts, b.nPrims, (int32_t)r.first, (int32_t)r.count, nodeBase, idxBase, P);
+            if (msg) return fail(RT_E_INVALID, "rt_rebuild_scene: %s", msg);
+            nodeBase += (uint32_t)cap; idxBase += r.count;
+        }
+    } else {
+        for (const rebuild::BlasRange& r : b.ranges) if (r.count == 0 || r.count > (1u << 30)) return fail(RT_E_INVALID, "rt_rebuild_scene: a BLAS of %u primitives", r.count);
+    }
+    HIPCHK(hipSetDevice(b.device));
+    SceneBag::RebuildSet& t = b.rset[b.rnext];
+    if (const int rc = rebuild_alloc(b, t)) return rc;
+    hipStream_t s = b.stream;
+    if (!sbvh) {
+        // room for every tree these builders can make (a set or the scratch that started smaller, or has only held SBVH trees so far)
+        if (const int rc = rebuild_reserve(b, t, (size_t)b.nPrims, 2 * (size_t)b.nPrims, 0, 0)) return rc;
+        // the builders' workspace
+        size_t need = 0;
+        for (const rebuild::BlasRange& r : b.ranges) {
+            size_t bytes = 0;
+            const int rc = builder == RT_REBUILD_SAH ? sahdev::work_bytes(who, r.count, s, &bytes) : lbvhdev::work_bytes(who, r.count, s, &bytes);
+            if (rc != RT_OK) return rc;
+            need = std::max(need, bytes);
+        }
+        if (need > b.rwork.cap)
+            if (const int rc = rebuild_grow(b, b.rwork, need, 0, "the builders' workspace", "rt_rebuild_scene: %zu bytes of builder workspace")) return rc;
+    }
+    const SceneArrays& sc = b.sc;
+    // ---- stage: the new primitives into the set that is not live
+    HIPCHK(hipEventRecord(b.rev[0], s));
+    HIPCHK(hipMemcpyAsync(t.prims, sc.prims, sizeof(RtPrimitive) * (size_t)b.nPrims, hipMemcpyDeviceToDevice, s));
+    if (count) HIPCHK(hipMemcpyAsync(t.prims + first, prims, sizeof(RtPrimitive) * (size_t)count, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(t.lightRecs, sc.lightRecs, sizeof(RtFloat4) * 8 * std::max<size_t>((size_t)b.nLights, 1), hipMemcpyDeviceToDevice, s));   // (the emittance words stay)
+    const auto t1 = clock::now();
+    // ---- every BLAS anew, in the order of the ranges
+    std::vector<uint32_t> rootOf(nR), interiors(nR), depth(nR);
+    uint32_t nNodes = 0, nIdx = 0, maxDepth = 0;
+    uint64_t spatialSplits = 0, primsClipped = 0;
+    for (size_t k = 0; k < nR; k++) {
+        const rebuild::BlasRange& r = b.ranges[k];
+        Built built{};
+        uint32_t slots = r.count;
+        if (sbvh) {
+            // size, then place: the tree stays in the builder's own memory until the set has room for it (one tree at a time)
+            struct TreeGuard { sbvhdev::Tree* p = nullptr; ~TreeGuard() { sbvhdev::destroy(p); } } tree;
+            SbvhBuilt sb{};
+            if (const int rc = sbvhdev::build(who, s, alpha, t.prims + r.first, r.count, r.first, nNodes, nIdx, nullptr, nullptr, b.spool, &tree.p, &sb)) return rc;
+            if (sb.nIdx == 0 || (uint64_t)nNodes + sb.nodes + nR > 0x7fffffffull || (uint64_t)nIdx + sb.nIdx > 0x7fffffffull)
+                return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: the new trees have 2^31 nodes or index slots, or more; the scene is unchanged");
+            // (nR spare nodes: the leaf and pair arrays hold half the node capacity, and k trees have k leaves more than interior nodes)
+            if (const int rc = rebuild_reserve(b, t, (size_t)nIdx + sb.nIdx, (size_t)nNodes + sb.nodes + nR, nIdx, nNodes)) return rc;
+            if (const int rc = sbvhdev::emit(who, s, tree.p, t.nodes.p + nNodes, t.primIdx.p + nIdx)) return rc;
+            built.nodes = sb.nodes; built.depth = sb.depth; slots = sb.nIdx;
+            spatialSplits += sb.spatialSplits; primsClipped += sb.primsClipped;
+        } else {
+            const int rc = builder == RT_REBUILD_SAH
+                ? sahdev::build(who, s, b.rwork.p, t.prims + r.first, r.count, r.first, nNodes, nIdx, t.nodes.p + nNodes, t.primIdx.p + nIdx, nullptr, nullptr, &built)
+                : lbvhdev::build(who, s, b.rwork.p, P, t.prims + r.first, r.count, r.first, nNodes, nIdx, t.nodes.p + nNodes, t.primIdx.p + nIdx, nullptr, nullptr, &built);
+            if (rc != RT_OK) return rc;
+        }
+        if (built.nodes == 0 || (built.nodes & 1u) == 0 || (!sbvh && built.nodes > 2 * r.count - 1))
+            return fail(RT_E_DEVICE, "rt_rebuild_scene: inconsistent builder result (%u nodes for %u primitives)", built.nodes, r.count);
+        if ((built.depth == 0) != (built.nodes == 1))
+            return fail(RT_E_DEVICE, "rt_rebuild_scene: inconsistent builder result (height %u with %u nodes)", built.depth, built.nodes);
+        if (rebuild::exceeds_stack(built.depth))   // validate_scene's rule
+            return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: the new BLAS %zu needs %u stack entries, at most %d are supported; the scene is unchanged", k,
+                        built.depth, RT_BVH4_STACK);
+        rootOf[k] = nNodes; interiors[k] = (built.nodes - 1) / 2; depth[k] = built.depth;
+        maxDepth = std::max(maxDepth, built.depth);
+        nNodes += built.nodes; nIdx += slots;
+    }
+    if (const int rc = rebuild_scratch(b, (size_t)nNodes + nR)) return rc;
+    const auto t2 = clock::now();
+    // ---- the instances (host: at most 256 records), then everything upload derives
+    std::vector<RtBVHInstance> inst = b.inst;
+    if (blas) inst.assign(blas, blas + nBlas);
+    for (int32_t i = 0; i < b.nBlas; i++) inst[(size_t)i].bvhIdx = rootOf[(size_t)b.instBlas[(size_t)i]];
+    HIPCHK(hipMemcpyAsync(t.blas, inst.data(), sizeof(RtBVHInstance) * (size_t)b.nBlas, hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(b.rev[1], s));
+    HIPCHK(rebuilddev::begin(s, b.dw, t.parent.p, nNodes));
+    uint32_t nPairs = 0;
+    {   // pair ids: BLAS by BLAS in the order in which the instances first name them
+        std::vector<uint8_t> done(nR, 0);
+        for (int32_t i = 0; i < b.nBlas; i++) {
+            const size_t k = (size_t)b.instBlas[(size_t)i];
+            if (done[k]) continue;
+            done[k] = 1;
+            HIPCHK(rebuilddev::number_blas(s, b.dw, t.nodes.p, nNodes, rootOf[k], interiors[k], depth[k], nPairs, (uint32_t)t.pairNode.cap, t.pairNode.p, t.parent.p));
+            nPairs += interiors[k];
+        }
+    }
+    const uint32_t nLeaves = nNodes - nPairs;
+    const bool layout1 = b.layout == 1;
+    HIPCHK(rebuilddev::finish(s, b.dw, t.nodes.p, nNodes, nPairs, nLeaves, t.blas, (uint32_t)b.nBlas, t.pairNode.p, layout1 ? t.pairs.p : nullptr, t.rootEntry, t.leaves.p));
+    HIPCHK(refitdev::launch_records(s, t.prims, t.nodes.p, t.primIdx.p, nIdx, sc.lights, (uint32_t)b.nLights, 0u, (uint32_t)b.nPrims, nullptr, 0u, nullptr,
+                                    layout1 ? t.triRecs.p : nullptr, t.shadeRecs, t.lightRecs));
+    HIPCHK(hipEventRecord(b.rev[2], s));
+    HIPCHK(refitdev::launch_tlas(s, t.nodes.p, t.blas, b.nBlas, layout1 ? t.rootEntry : nullptr, t.tlas, t.tp, t.tpP, t.ir, b.rStatus));
+    HIPCHK(hipEventRecord(b.rev[3], s));
+    int32_t status[2] = { 0, 0 };
+    uint32_t walk[2] = { 0, 0 };
+    HIPCHK(hipMemcpyAsync(status, b.rStatus, sizeof status, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(walk, b.dw.ctr + rebuilddev::kStatus, sizeof walk, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (walk[0]) return fail(RT_E_DEVICE, "rt_rebuild_scene: the breadth-first walk does not match the builder's tree (inconsistent device result)");
+    if (const int rc = tlas_status_error(who, status)) return rc;
+    if (rebuild::takes_layout1(b.variantLayout1, (int32_t)nIdx, std::max(walk[1], 1u)) != layout1)
+        return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: the new trees would change the scene's derived layout (largest leaf %u primitives, %u index slots; "
+                    "layout %d is bound): upload the rebuilt scene instead; the scene is unchanged", walk[1], nIdx, b.layout);
+    const auto t3 = clock::now();
+    // ---- commit: swap the arrays once no kernel of a holder reads the old ones
+    if (const int rc = b.wait_holders()) return rc;
+    SceneArrays n = b.sc;
+    n.prims = t.prims; n.bvh2 = t.nodes.p; n.primIdx = t.primIdx.p; n.blas = t.blas; n.tlas = t.tlas;
+    n.tlasPairs = t.tp; n.tlasPairsP = t.tpP; n.instRecs = t.ir;
+    n.shadeRecs = t.shadeRecs; n.lightRecs = t.lightRecs;
+    if (layout1 && nPairs == 0) HIPCHK(hipMemsetAsync(t.pairs.p, 0, sizeof(RtFloat4) * 4, s));   // no interior node: one zero record, as at upload
+    if (layout1) { n.pairs = t.pairs.p; n.triRecs = t.triRecs.p; n.rootEntry = t.rootEntry; }
+    b.sc = n;
+    b.dParent = t.parent.p; b.dLeaves = t.leaves.p; b.dTickets = t.tickets.p; b.dPairNode = t.pairNode.p;
+    b.nNodes = (int32_t)nNodes; b.nIdx = (int32_t)nIdx; b.nPairs = layout1 ? (int32_t)nPairs : 0; b.nLeaves = nLeaves; b.nReach = nNodes;
+    b.inst = inst;
+    const bool reconfigure = status[1] != b.tlasDepth || rebuild::stack_entries((int)std::max(maxDepth, 1u)) != b.stackEntries;
+    b.tlasDepth = status[1];
+    b.stackEntries = rebuild::stack_entries((int)std::max(maxDepth, 1u));
+    b.nInterior = layout1 ? (int)nPairs : 0;
+    b.generation++;   // every holder takes the new arrays (and re-derives its traversal kernels) before its next launch
+    b.rnext ^= 1;
+    const auto t4 = clock::now();
+    if (stats) {
+        float ms = 0, derive = 0, tlas = 0;
+        (void)hipEventElapsedTime(&ms, b.rev[0], b.rev[3]); (void)hipEventElapsedTime(&derive, b.rev[1], b.rev[2]); (void)hipEventElapsedTime(&tlas, b.rev[2], b.rev[3]);
+        *stats = RtRebuildStats{};
+        stats->gpu_ms = ms; stats->wall_ms = ms_between(t0, t4);
+        stats->stage_ms = ms_between(t0, t1); stats->build_ms = ms_between(t1, t2); stats->derive_ms = derive; stats->tlas_ms = tlas;
+        stats->commit_ms = ms_between(t3, t4);
+        stats->prims = count; stats->blas_built = (int32_t)nR; stats->nodes = (int32_t)nNodes; stats->n_idx = (int32_t)nIdx;
+        stats->max_depth = (int32_t)maxDepth; stats->tlas_nodes = b.nTlas; stats->tlas_depth = status[1]; stats->reconfigured = reconfigure ? 1 : 0;
+        stats->spatial_splits = (int32_t)std::min<uint64_t>(spatialSplits, 0x7fffffffu); stats->prims_clipped = (int32_t)std::min<uint64_t>(primsClipped, 0x7fffffffu);
+    }
+    return RT_OK;
+}
+int64_t scenedev::rebuild_allocations(const SceneBag& b) { return (int64_t)(b.rallocs + sbvhdev::pool_allocations(b.spool)); }
+// The primitive range of every instance's BLAS (rebuild_common.h), for callers that want to know beforehand whether rt_rebuild_scene
+// will take a scene; no device needed.
+extern "C" int rt_blas_ranges(const RtBVHNode2* nodes, int32_t nNodes, const uint32_t* primIdx, int32_t nIdx, int32_t nPrims,
+                              const RtBVHInstance* blas, int32_t nBlas, int32_t* firstOut, int32_t* countOut)
+{
+    std::vector<rebuild::BlasRange> ranges; std::vector<int32_t> instBlas;
+    if (const char* why = rebuild::find_blas_ranges(nodes, nNodes, primIdx, nIdx, nPrims, blas, nBlas, ranges, instBlas))
+        return fail(why == std::string("missing array") ? RT_E_INVALID : RT_E_UNSUPPORTED, "rt_blas_ranges: %s", why);
+    for (int32_t i = 0; i < nBlas; i++) {
+        if (firstOut) firstOut[i] = (int32_t)ranges[(size_t)instBlas[(size_t)i]].first;
+        if (countOut) countOut[i] = (int32_t)ranges[(size_t)instBlas[(size_t)i]].count;
+    }
+    return RT_OK;
+}
+int scenedev::scene_array(const SceneBag& b, int32_t which, const void** src, size_t* n)
+{
+    const SceneArrays& sc = b.sc;
+    switch (which) {
+    case RT_SCENE_PRIMS:        *src = sc.prims; *n = sizeof(RtPrimitive) * (size_t)b.nPrims; break;
+    case RT_SCENE_BVH:          *src = b.accel == RT_ACCEL_BVH4 ? (const void*)sc.bvh4 : (const void*)sc.bvh2;
+                                *n = (b.accel == RT_ACCEL_BVH4 ? sizeof(RtBVHNode4) : sizeof(RtBVHNode2)) * (size_t)b.nNodes; break;
+    case RT_SCENE_TLAS:         *src = sc.tlas; *n = sizeof(RtTLASNode) * (size_t)b.nTlas; break;
+    case RT_SCENE_INSTANCES:    *src = sc.blas; *n = sizeof(RtBVHInstance) * (size_t)b.nBlas; break;
+    case RT_SCENE_PAIRS:        *src = sc.pairs; *n = sc.pairs ? sizeof(RtFloat4) * 4 * (size_t)b.nPairs : 0; break;
+    case RT_SCENE_TRI_RECS:     *src = sc.triRecs; *n = sc.triRecs ? sizeof(RtFloat4) * 3 * (size_t)b.nIdx : 0; break;
+    case RT_SCENE_SHADE_RECS:   *src = sc.shadeRecs; *n = sizeof(RtFloat4) * (size_t)b.nPrims; break;
+    case RT_SCENE_LIGHT_RECS:   *src = sc.lightRecs; *n = sizeof(RtFloat4) * 8 * (size_t)b.nLights; break;
+    case RT_SCENE_TLAS_PAIRS:   *src = sc.tlasPairs; *n = sizeof(RtFloat4) * 4 * (size_t)b.nTlas; break;
+    case RT_SCENE_TLAS_PAIRS_P: *src = sc.tlasPairsP; *n = sizeof(RtFloat4) * 4 * (size_t)b.nTlas; break;
+    case RT_SCENE_INST_RECS:    *src = sc.instRecs; *n = sizeof(RtFloat4) * 4 * (size_t)b.nBlas; break;
+    default: return fail(RT_E_INVALID, "rt_debug_get_scene_array: unknown array %d", which);
+    }
+    return RT_OK;
+}

@@ -1,0 +1,133 @@
+// scene_dev.h — the device copy of a scene (scene.hip) as the contexts of rt355.hip hold it, and what the two files share: error
+// reporting and the allocation helper.  scene.hip knows nothing of a context (RtCtx) but that the holders of a copy can be made to wait.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cstdarg>
+#include <cstdio>
+#include <vector>
+#include "../../include/rt355.h"
+#include "refit_common.h"
+#include "rebuild_common.h"
+#include "rebuild_dev.h"
+#include "build_cores.h"
+
+int rt355_set_error(int code, const char* msg);   // rt355.hip: sets the text rt_last_error() returns
+static int fail(int code, const char* fmt, ...)
+{
+    char buf[512];
+    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
+    return rt355_set_error(code, buf);
+}
+#define HIPCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
+    return fail(RT_E_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
+
+template <class T> static int dalloc(std::vector<void*>& bag, T** p, size_t count)
+{
+    void* v = nullptr;
+    size_t bytes = std::max<size_t>(count, 1) * sizeof(T);
+    hipError_t e = hipMalloc(&v, bytes);
+    if (e != hipSuccess) return fail(RT_E_NOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+    bag.push_back(v);
+    *p = (T*)v;
+    return RT_OK;
+}
+
+struct RtCtx;
+namespace scenedev __attribute__((visibility("hidden"))) {   // (nothing of this interface is exported from the library)
+
+// The arrays of a copy as their owner writes them: DevScene (rt355_kernels.h, which a file without kernels cannot include) field for
+// field and in its order; a context turns them into the kernels' read-only view when it takes the copy over (rt355.hip, adopt_scene).
+struct SceneArrays {
+    RtPrimitive* prims; RtMaterial* mats; RtFloat4* tex; uint32_t* lights; RtBVHNode2* bvh2; RtBVHNode4* bvh4; uint32_t* primIdx;
+    RtTLASNode* tlas; RtBVHInstance* blas;
+    RtFloat4 *pairs, *triRecs; uint32_t* rootEntry; RtFloat4 *shadeRecs, *tlasPairs, *instRecs; uint32_t tlasRoot;
+    RtFloat4* tlasPairsP; uint32_t tlasRootP; RtFloat4 *lightRecs, *quads;
+    int32_t nLights, nPrims, nBlas, nTex;
+};
+
+// The device copy of a scene (uploaded arrays + derived layouts).  Contexts that render the same scene - sample-stream lanes, the
+// row bands of one frame - can hold ONE copy (rt_share_scene): less HBM, and one working set in the L2s / Infinity Cache instead of one per context.
+struct SceneBag {
+    std::vector<void*> allocs;                // what is made once and lives as long as the copy
+    int device = 0;
+    // What a holder renders with, written by upload, update and rebuild only; a context takes these over in adopt_scene (rt355.hip)
+    SceneArrays sc{};                         // the device arrays (an update rewrites them in place, a rebuild swaps them)
+    int layout = 0;                           // 0 = traverse the reference arrays as uploaded, 1 = derived pair/triangle-record layout
+    int stackEntries = RT_BVH2_STACK, tlasDepth = 0, nInterior = 0;   // LDS stack entries the trees need; TLAS height; records of the dense pair table
+    bool singleBlas = false;                  // the TLAS root is a leaf
+    uint64_t generation = 0;                  // bumped when an update or a rebuild changes any of them
+    std::vector<RtCtx*> holders;              // the contexts rendering from this copy
+    int wait_holders() const;                 // rt355.hip: until `stream` and `home` of every holder are idle (before a commit)
+    // rt_update_scene: what an in-place update needs of the upload, kept beside the device copy
+    const char* refitRefusal = nullptr;       // why this scene cannot be updated in place (NULL: it can)
+    int32_t nPrims = 0, nNodes = 0, nIdx = 0, nLights = 0, nTlas = 0, nBlas = 0, nPairs = 0, accel = 0;
+    std::vector<int32_t> primType, primMat;   // host shadow of every primitive's objType / matIdx (the light list and materials depend on them)
+    std::vector<RtBVHInstance> inst;          // the instances as last uploaded or updated
+    uint32_t *dParent = nullptr, *dLeaves = nullptr, *dPairNode = nullptr, *dTickets = nullptr;   // refit topology (walked from the BLAS roots)
+    uint32_t nLeaves = 0, nReach = 0;
+    // A device array that is replaced during the copy's life (scene.hip, rebuild_grow, is the one place that does) and freed with it
+    template <class T> struct Grown {
+        T* p = nullptr; size_t cap = 0;
+        Grown() = default; Grown(const Grown&) = delete; Grown& operator=(const Grown&) = delete;
+        ~Grown() { if (p) (void)hipFree(p); }
+    };
+    // staging of an update (allocated by the first one): nothing live is written before the new TLAS has passed
+    RtPrimitive* sPrims = nullptr; RtBVHInstance* sInst = nullptr; RtTLASNode* sTlas = nullptr;
+    RtFloat4 *sTp = nullptr, *sTpP = nullptr, *sIr = nullptr; int32_t* sStatus = nullptr;
+    Grown<RtBVHNode2> sNodes;                 // (a rebuild changes the node count)
+    hipStream_t stream = nullptr;             // where updates run
+    hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };   // brackets of the staging and of the commit
+    // rt_rebuild_scene: what it needs of the upload, and its device memory (allocated by the first rebuilds, then reused)
+    const char* rebuildRefusal = nullptr;     // why this scene cannot be rebuilt in place (NULL: it can)
+    std::vector<rebuild::BlasRange> ranges;   // the primitive range of every distinct BLAS, in increasing order
+    std::vector<int32_t> instBlas;            // instance -> its range
+    bool variantLayout1 = false;              // the holders' extend_variant admits the derived layout 1
+    // Everything a rebuild changes, twice: a rebuild writes the set that is not live and the commit swaps the pointers; the upload's own
+    // arrays stay behind until the copy is freed.  The arrays that scale with the primitives are made once.  Those that scale with the
+    // trees (Grown) have capacities of their own: nPrims index slots and 2 * nPrims nodes at first, which bounds every tree of the SAH
+    // and the linear builder; an SBVH tree has no such bound, so the set that is not live grows to what the finished trees need plus a
+    // quarter (kRebuildHeadroomDiv, rebuild_reserve), what was emitted so far is kept and the arrays it replaces are freed at once.
+    struct RebuildSet {
+        bool allocated = false;
+        RtPrimitive* prims = nullptr; RtBVHInstance* blas = nullptr; RtTLASNode* tlas = nullptr;
+        RtFloat4 *tp = nullptr, *tpP = nullptr, *ir = nullptr, *shadeRecs = nullptr, *lightRecs = nullptr;
+        uint32_t* rootEntry = nullptr;
+        Grown<uint32_t> primIdx; Grown<RtFloat4> triRecs;                                    // index slots (triRecs: 3 per slot)
+        Grown<RtBVHNode2> nodes; Grown<uint32_t> parent, tickets;                            // nodes
+        Grown<RtFloat4> pairs; Grown<uint32_t> leaves, pairNode;                             // nodes / 2 (pairs: 4 per interior node)
+    } rset[2];
+    Grown<uint32_t> dwFlags, dwRanks, dwNewId, dwFrontA, dwFrontB; Grown<char> dwScan;   // the derivation's scratch, grown likewise
+    sbvhdev::Pool* spool = nullptr;           // the SBVH builder's device blocks, kept from rebuild to rebuild
+    uint64_t rallocs = 0;                     // device allocations by updates and rebuilds of this copy (rt_debug_rebuild_allocations)
+    int rnext = 0;                            // the set the next rebuild writes
+    Grown<char> rwork;                        // the builders' workspace (bytes)
+    rebuilddev::Work dw{};                    // scratch of the derivation
+    int32_t* rStatus = nullptr;               // k_tlas_build's status words
+    hipEvent_t rev[4] = { nullptr, nullptr, nullptr, nullptr };
+    ~SceneBag()
+    {
+        (void)hipSetDevice(device);
+        if (stream) (void)hipStreamDestroy(stream);
+        for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : rev) if (e) (void)hipEventDestroy(e);
+        sbvhdev::pool_destroy(spool);
+        for (void* p : allocs) (void)hipFree(p);
+    }
+};
+
+// scene.hip; messages go to rt_last_error()
+struct HostScene {   // the host arrays of rt_upload_scene (include/rt355.h), in its order
+    const RtPrimitive* prims; int32_t nPrims; const RtMaterial* mats; int32_t nMats; const RtFloat4* textures; int32_t nTexels; const uint32_t* lights; int32_t nLights;
+    const void* bvhNodes; int32_t nNodes; const uint32_t* primIdx; int32_t nIdx; const RtTLASNode* tlas; int32_t nTlas; const RtBVHInstance* blas; int32_t nBlas;
+};
+int validate_scene(int accel, const HostScene& in, int* stackEntriesOut, int64_t* texPadOut, int* tlasDepthOut);
+// fills a fresh copy on the current device from arrays that have passed validate_scene, which gave the last three arguments
+int upload_scene(SceneBag& b, int accel, int extendVariant, const HostScene& in, int stackEntries, int64_t texPad, int tlasDepth);
+int update_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas, RtUpdateStats* stats);
+int rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
+                  int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats);
+int64_t rebuild_allocations(const SceneBag& b);
+int scene_array(const SceneBag& b, int32_t which, const void** src, size_t* bytes);   // where RT_SCENE_* lies on the device and how long it is
+
+} // namespace scenedev
