@@ -128,6 +128,19 @@ int rt_upload_scene(RtCtx* ctx,
                     const RtTLASNode* tlas, int32_t nTlas,
                     const RtBVHInstance* blas, int32_t nBlas);
 
+/* rt_upload_scene with bvhNodes always RtBVHNode2[nNodes].  On a BVH2 context it is rt_upload_scene.  On a BVH4 context the BVH2 is
+ * validated by the BVH2 rules (plus rt_build_bvh4's check of every interior record), uploaded and collapsed on the device
+ * (rt_build_bvh4's kernels); quad records, triangle records and root entries are derived there too.  Afterwards every device array
+ * and rt_kernel_info equal those of rt_upload_scene of the same scene collapsed on the host.  The copy keeps the BVH2 on the device
+ * (RT_SCENE_BVH2_KEPT) and the primitive range of every BLAS, so rt_rebuild_scene works on it (a copy bound through rt_upload_scene
+ * on a BVH4 context has lost the BVH2 and refuses).  A refusal - the checks, a collapsed BLAS that needs more than RT_BVH4_STACK
+ * stack entries (RT_E_UNSUPPORTED) - leaves the bound scene and its stack size untouched. */
+int rt_upload_scene_bvh2(RtCtx* ctx,
+                         const RtPrimitive* prims, int32_t nPrims, const RtMaterial* mats, int32_t nMats,
+                         const RtFloat4* textures, int32_t nTexels, const uint32_t* lights, int32_t nLights,
+                         const RtBVHNode2* bvhNodes, int32_t nNodes, const uint32_t* primIdx, int32_t nIdx,
+                         const RtTLASNode* tlas, int32_t nTlas, const RtBVHInstance* blas, int32_t nBlas);
+
 /* The host-side shape checks rt_upload_scene runs before it touches the device (index ranges, tree cycles and depths, stack needs,
  * the 32768-node / instance bound of the TLAS encodings), callable without a GPU.  `accel` says how bvhNodes is to be read.  What it
  * accepts, every kernel and every derivation of rt_upload_scene can walk inside the arrays, within the stacks and in finite time, with
@@ -211,6 +224,21 @@ int rt_build_bvh2_sbvh(int32_t device, float alpha, const RtPrimitive* prims, in
  * out[1] the level passes, out[2] numbering and emit, out[3] download (ms), out[4] the number of level passes, out[5] scratch bytes
  * per work-item of the spatial-bin kernel, out[6] of the flag kernel, out[7] of the scatter kernel (the three that clip). */
 int rt_debug_sbvh_phases(float* out);
+/* The BVH2 -> BVH4 collapse on the GPU: BVH4::Convert + Collapse (rt355_host.h rth_build_bvh4) of the BVH2 nodes2[nNodes] whose BLAS
+ * roots are roots[nRoots] (the instances' bvhIdx in instance order; a root named before is the same BLAS), on `device`.  out4[nNodes]
+ * receives the RtBVHNode4 array byte for byte as BuildBVH4 leaves it: the collapsed records of the surviving nodes, Convert's two-slot
+ * records of the absorbed and the unreachable interior nodes, zeros for BVH2 leaves, the one-slot record of a BLAS root that is a
+ * leaf.  A surviving node's record is a function of the BVH2 below it alone (csrc/collapse_common.h), so the survivors of one level
+ * are collapsed side by side, level by level; the host restatement rth_build_bvh4_levels (rt355_host.h) gives the same arrays.
+ * nIdx: the primIdx slots the leaves index.  Synchronous, on a stream of its own; the caller's device is restored.  stats may be NULL.
+ * Refusals write nothing to out4:
+ *   RT_E_INVALID      a missing array or a count <= 0; a root out of range; any record with count == 0 whose first + 1 is not inside
+ *                     the array (every interior record is converted, reachable or not); a leaf range outside nIdx; a node reachable
+ *                     twice from the roots; a bad device;
+ *   RT_E_UNSUPPORTED  a BLAS whose BVH2 is deeper than RT_BVH4_STACK levels.
+ * A result whose stack_need exceeds RT_BVH4_STACK is returned with the figure: it is the upload that refuses it. */
+int rt_build_bvh4(int32_t device, const RtBVHNode2* nodes2, int32_t nNodes, int32_t nIdx, const uint32_t* roots, int32_t nRoots,
+                  RtBVHNode4* out4, RtBvh4Stats* stats);
 
 /* ---- in-place scene updates (animation) ----------------------------------------------------------------------------------------
  * What Renderer::Tick's disabled animation hook (renderer.cpp:29-37: scene.Animate, tlas->Build, the node buffers' CopyToDevice) needs,
@@ -323,6 +351,9 @@ int rt_blas_ranges(const RtBVHNode2* nodes, int32_t nNodes, const uint32_t* prim
 #define RT_SCENE_TLAS_PAIRS    8
 #define RT_SCENE_TLAS_PAIRS_P  9
 #define RT_SCENE_INST_RECS    10
+#define RT_SCENE_QUADS        11   /* layout-1 quad records of a BVH4 (empty otherwise)     */
+#define RT_SCENE_ROOT_ENTRY   12   /* layout-1 root entry per instance                      */
+#define RT_SCENE_BVH2_KEPT    13   /* the BVH2 a BVH4 copy keeps (rt_upload_scene_bvh2); 0 bytes when the copy holds none */
 int rt_debug_get_scene_array(RtCtx* ctx, int32_t which, void* out, int64_t capacityBytes, int64_t* bytes);
 
 /* ---- lanes: one accumulation as several interleaved sample streams behind one handle -------------------------------------------
@@ -350,6 +381,11 @@ int rt_group_upload_scene(RtGroup* g,
                           const RtFloat4* textures, int32_t nTexels, const uint32_t* lights, int32_t nLights,
                           const void* bvhNodes, int32_t nNodes, const uint32_t* primIdx, int32_t nIdx,
                           const RtTLASNode* tlas, int32_t nTlas, const RtBVHInstance* blas, int32_t nBlas);
+int rt_group_upload_scene_bvh2(RtGroup* g,
+                               const RtPrimitive* prims, int32_t nPrims, const RtMaterial* mats, int32_t nMats,
+                               const RtFloat4* textures, int32_t nTexels, const uint32_t* lights, int32_t nLights,
+                               const RtBVHNode2* bvhNodes, int32_t nNodes, const uint32_t* primIdx, int32_t nIdx,
+                               const RtTLASNode* tlas, int32_t nTlas, const RtBVHInstance* blas, int32_t nBlas);   /* rt_upload_scene_bvh2 */
 int rt_group_share_scene(RtGroup* g, RtGroup* from);                         /* e.g. the row bands of one frame: one device copy        */
 int rt_group_update_scene(RtGroup* g, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
                           RtUpdateStats* stats);                             /* rt_update_scene for the group's copy (all lanes)        */

@@ -95,6 +95,15 @@ int rth_build_bvh4(RthScene* s);            /* new BVH4(*bvh2) (scene.cpp:71)   
 int rth_build_tlas(RthScene* s);
 /* BVH4::Convert + Collapse (bvh.cpp:695-787) on a caller-provided BVH2 node array, one BLAS rooted at node 0; out[n] */
 int rth_bvh4_from_nodes(const RtBVHNode2* nodes, int n, RtBVHNode4* out);
+/* rth_build_bvh4's arrays by the level-wise collapse (rt_build_bvh4, rt355.h): device >= 0: on that GPU; -1: the host restatement.
+ * Returns RT_E_* and leaves the scene's BVH4 as it was when refused. */
+int rth_build_bvh4_gpu(RthScene* s, int device);
+/* The host restatement of rt_build_bvh4 (rt355.h): the same level loop over csrc/collapse_common.h, written sequentially, with the
+ * same checks and messages (in rth_last_error()); stats->device_ms = 0.  Optional outputs (NULL: not wanted) of what the upload
+ * derives from the collapsed tree: quads (8 RtFloat4 per live node, room for nNodes records), rootEntry[nRoots] (the live id of every
+ * root), quadNode (live id -> node id, room for nNodes). */
+int rth_build_bvh4_levels(const RtBVHNode2* nodes2, int32_t nNodes, int32_t nIdx, const uint32_t* roots, int32_t nRoots, RtBVHNode4* out4,
+                          RtBvh4Stats* stats, RtFloat4* quads, uint32_t* rootEntry, uint32_t* quadNode);
 int rth_set_instance_transform(RthScene* s, int blas, const float invT[16]); /* scene.cpp:82 (commented out there) */
 
 /* Borrowed views of the arrays (valid until the scene changes). */

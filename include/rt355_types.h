@@ -156,6 +156,11 @@ typedef struct RtSbvhStats {         /* rt_build_bvh2_sbvh (rt355.h) */
     float   sah_cost, device_ms, wall_ms;      /* as in RtBuildStats                            */
     int32_t peak_refs;                         /* most refs alive in one level                  */
 } RtSbvhStats;
+typedef struct RtBvh4Stats {         /* rt_build_bvh4 (rt355.h) */
+    int32_t live_nodes, levels;                /* surviving nodes (= quad records); BVH4 levels of the deepest BLAS          */
+    int32_t stack_need, largest_leaf;          /* entries the 4-wide traversal needs at most; primitives of the largest leaf */
+    float   device_ms, wall_ms;                /* as in RtBuildStats                                                         */
+} RtBvh4Stats;
 
 RT_STATIC_ASSERT(sizeof(RtRay) == 128 && offsetof(RtRay, t) == 96 && offsetof(RtRay, primIdx) == 100 &&
                  offsetof(RtRay, pixelIdx) == 108 && offsetof(RtRay, inside) == 112 &&
@@ -178,6 +183,7 @@ RT_STATIC_ASSERT(sizeof(RtBVHNode4) == 160 && offsetof(RtBVHNode4, first) == 128
 RT_STATIC_ASSERT(sizeof(RtBVHInstance) == 68 && offsetof(RtBVHInstance, invT) == 4, "BVHInstance layout");
 RT_STATIC_ASSERT(sizeof(RtBuildOptions) == 16 && offsetof(RtBuildOptions, alpha) == 12 && sizeof(RtBuildStats) == 32, "build options / stats layout");
 RT_STATIC_ASSERT(sizeof(RtSbvhStats) == 48, "SBVH build stats layout");
+RT_STATIC_ASSERT(sizeof(RtBvh4Stats) == 24, "BVH4 collapse stats layout");
 RT_STATIC_ASSERT(sizeof(RtTLASNode) == 48 && offsetof(RtTLASNode, leftRight) == 32 && offsetof(RtTLASNode, BLASidx) == 36, "TLASNode layout");
 
 #ifdef __cplusplus

@@ -51,12 +51,13 @@ BuildStats = np.dtype([("nodes", "<i4"), ("leaves", "<i4"), ("depth", "<i4"), ("
                        ("device_ms", "<f4"), ("wall_ms", "<f4"), ("_reserved", "<i4")])
 SbvhStats = np.dtype([(n, "<i4") for n in ("nodes", "leaves", "n_idx", "depth", "spatial_splits", "prims_clipped", "forced_leaves", "levels")] +
                      [("sah_cost", "<f4"), ("device_ms", "<f4"), ("wall_ms", "<f4"), ("peak_refs", "<i4")])   # RtSbvhStats
+Bvh4Stats = np.dtype([(n, "<i4") for n in ("live_nodes", "levels", "stack_need", "largest_leaf")] + [("device_ms", "<f4"), ("wall_ms", "<f4")])   # RtBvh4Stats
 KernelInfo = np.dtype([(n, "<i4") for n in ("layout", "persist", "persist4", "stack_entries", "persist_grid", "persist_grid_connect",
                                              "shade_grid", "n_blas")])
 
 _SIZES = {"Ray": (Ray, 128), "ShadowRay": (ShadowRay, 96), "Material": (Material, 80), "Primitive": (Primitive, 128),
           "Camera": (Camera, 128), "Settings": (Settings, 40), "BVHNode2": (BVHNode2, 48), "BVHNode4": (BVHNode4, 160),
-          "BVHInstance": (BVHInstance, 68), "TLASNode": (TLASNode, 48), "BuildOptions": (BuildOptions, 16), "BuildStats": (BuildStats, 32), "SbvhStats": (SbvhStats, 48), "ShadowRecord": (ShadowRecord, 48), "Config": (Config, 64)}
+          "BVHInstance": (BVHInstance, 68), "TLASNode": (TLASNode, 48), "BuildOptions": (BuildOptions, 16), "BuildStats": (BuildStats, 32), "SbvhStats": (SbvhStats, 48), "Bvh4Stats": (Bvh4Stats, 24), "ShadowRecord": (ShadowRecord, 48), "Config": (Config, 64)}
 for _n, (_d, _s) in _SIZES.items():
     assert _d.itemsize == _s, (_n, _d.itemsize, _s)
 
@@ -87,6 +88,8 @@ RT_OK, RT_E_INVALID, RT_E_DEVICE, RT_E_NOMEM, RT_E_UNSUPPORTED = 0, -1, -2, -3, 
 # rt_debug_get_scene_array ids (include/rt355.h): name -> (id, record dtype)
 SCENE_ARRAYS = {"prims": 0, "bvh": 1, "tlas": 2, "instances": 3, "pairs": 4, "triRecs": 5, "shadeRecs": 6, "lightRecs": 7,
                 "tlasPairs": 8, "tlasPairsP": 9, "instRecs": 10}
+# ... and those only a BVH4 copy fills (bvh2Kept: 0 bytes unless the copy was bound with its BVH2, rt_upload_scene_bvh2)
+SCENE_ARRAYS_BVH4 = {"quads": 11, "rootEntry": 12, "bvh2Kept": 13}
 UpdateStats = np.dtype([("gpu_ms", "<f8"), ("prims", "<i4"), ("nodes", "<i4"), ("tlas_nodes", "<i4"), ("tlas_depth", "<i4"),
                         ("reconfigured", "<i4"), ("reserved", "<i4", 3)])
 assert UpdateStats.itemsize == 40
@@ -104,6 +107,7 @@ DEVICE_SYMBOLS = [
     "rt_debug_get_rays", "rt_debug_set_rays", "rt_debug_get_shadow", "rt_debug_enable_steps", "rt_debug_get_steps", "rt_debug_math",
     "rt_debug_math_sweep", "rt_debug_math_mode", "rt_debug_math_sweep_mode", "rt_validate_scene", "rt_build_bvh2", "rt_build_bvh2_sah", "rt_debug_sah_phases", "rt_build_bvh2_sbvh", "rt_debug_sbvh_phases", "rt_update_scene", "rt_group_update_scene", "rt_debug_get_scene_array",
     "rt_rebuild_scene", "rt_group_rebuild_scene", "rt_blas_ranges", "rt_debug_rebuild_allocations",
+    "rt_build_bvh4", "rt_upload_scene_bvh2", "rt_group_upload_scene_bvh2",
     "rt_group_create", "rt_group_destroy", "rt_group_lanes", "rt_group_concurrency", "rt_group_lane", "rt_group_frames", "rt_group_upload_scene", "rt_group_share_scene",
     "rt_group_seed", "rt_group_reset", "rt_group_render", "rt_group_synchronize", "rt_group_sum", "rt_group_read_accum", "rt_group_focus",
     "rt_group_postproc"]
@@ -116,7 +120,8 @@ HOST_SYMBOLS = [
     "rth_renderer_read", "rth_renderer_camera", "rth_seed_stream", "rth_load_model", "rth_save_png",
     "rth_set_build_threads", "rth_renderer_save_frame", "rth_renderer_camera_move", "rth_renderer_camera_mouse", "rth_renderer_camera_zoom", "rth_renderer_frames", "rth_renderer_set_lanes", "rth_renderer_set_builtins", "rth_renderer_builtins",
     "rth_build_blas_lbvh", "rth_build_bvh2_lbvh", "rth_lbvh_stats", "rth_set_primitives", "rth_refit",
-    "rth_build_blas_sah_gpu", "rth_build_bvh2_sah", "rth_build_blas_sbvh_gpu", "rth_build_bvh2_sbvh", "rth_rebuild", "rth_blas_ranges"]
+    "rth_build_blas_sah_gpu", "rth_build_bvh2_sah", "rth_build_blas_sbvh_gpu", "rth_build_bvh2_sbvh", "rth_rebuild", "rth_blas_ranges",
+    "rth_build_bvh4_gpu", "rth_build_bvh4_levels"]
 
 _dev = None
 _host = None
@@ -164,6 +169,9 @@ def _bind_device(lib):
         lib.rt_builtins.argtypes = [vp]
         lib.rt_destroy.argtypes = [vp]
         lib.rt_upload_scene.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32]
+        lib.rt_upload_scene_bvh2.argtypes = lib.rt_upload_scene.argtypes
+        lib.rt_group_upload_scene_bvh2.argtypes = lib.rt_upload_scene.argtypes
+        lib.rt_build_bvh4.argtypes = [i32, vp, i32, i32, vp, i32, vp, vp]
         lib.rt_share_scene.argtypes = [vp, vp]
         lib.rt_set_seeds.argtypes = [vp, vp, i64]
         lib.rt_seed_default.argtypes = [vp]
@@ -253,6 +261,8 @@ def host_lib():
         lib.rth_add_triangles.argtypes = [vp, vp, vp, i32, cp, i32]
         lib.rth_build_blas.argtypes = [vp, i32, C.c_float]
         lib.rth_build_bvh4.argtypes = [vp]
+        lib.rth_build_bvh4_gpu.argtypes = [vp, i32]
+        lib.rth_build_bvh4_levels.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp]
         lib.rth_build_blas_lbvh.argtypes = [vp, i32, i32, vp]
         lib.rth_build_bvh2_lbvh.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, vp, C.c_int32,
                                             C.POINTER(C.c_int32), vp, vp]

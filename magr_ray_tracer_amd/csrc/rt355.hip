@@ -546,6 +546,38 @@ extern "C" int rt_upload_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t nPr
     return RT_OK;
 }
 
+// rt_upload_scene with the BVH2 given for any context.  A BVH4 context collapses it on the device (scene.hip, collapse.hip) and keeps it,
+// so the copy can be rebuilt in place.  The new copy is made beside the bound one, which stays in use when the call is refused.
+extern "C" int rt_upload_scene_bvh2(RtCtx* ctx, const RtPrimitive* prims, int32_t nPrims, const RtMaterial* mats, int32_t nMats,
+                                    const RtFloat4* textures, int32_t nTexels, const uint32_t* lights, int32_t nLights,
+                                    const RtBVHNode2* bvhNodes, int32_t nNodes, const uint32_t* primIdx, int32_t nIdx,
+                                    const RtTLASNode* tlas, int32_t nTlas, const RtBVHInstance* blas, int32_t nBlas)
+{
+    if (!ctx) return fail(RT_E_INVALID, "rt_upload_scene_bvh2: null context");
+    if (ctx->cfg.accel == RT_ACCEL_BVH2)
+        return rt_upload_scene(ctx, prims, nPrims, mats, nMats, textures, nTexels, lights, nLights, bvhNodes, nNodes, primIdx, nIdx, tlas, nTlas, blas, nBlas);
+    const HostScene in{ prims, nPrims, mats, nMats, textures, nTexels, lights, nLights, bvhNodes, nNodes, primIdx, nIdx, tlas, nTlas, blas, nBlas };
+    int stackEntries = RT_BVH2_STACK, tlasDepth = 0; int64_t texPad = 2;
+    if (const int rc = validate_scene(RT_ACCEL_BVH2, in, &stackEntries, &texPad, &tlasDepth)) return rc;   // the BVH2 rules ...
+    std::vector<uint32_t> roots((size_t)nBlas);
+    for (int32_t b = 0; b < nBlas; b++) roots[(size_t)b] = blas[b].bvhIdx;
+    std::vector<collapse::Blas> blas4;
+    std::string why;
+    if (const int rc = collapse::check_args(bvhNodes, nNodes, nIdx, roots.data(), nBlas, blas4, why))   // ... and every record the collapse reads
+        return fail(rc, "rt_upload_scene_bvh2: %s", why.c_str());
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    auto bag = std::make_shared<SceneBag>();
+    bag->device = ctx->cfg.device;
+    if (const int rc = upload_scene(*bag, ctx->cfg.accel, ctx->cfg.extend_variant, in, stackEntries, texPad, tlasDepth, &blas4)) return rc;
+    scene_hold(ctx, bag);
+    ctx->sceneLoaded = false; ctx->trav = TRAV_NESTED;
+    const int rc = adopt_scene(ctx);
+    if (rc != RT_OK) { scene_release(ctx); return rc; }
+    ctx->sceneLoaded = true;
+    return RT_OK;
+}
+
 // A second context on the same device renders the scene `from` holds: it takes the device copy (uploaded arrays and derived layouts)
 // instead of uploading its own.  Both contexts must agree on what the derived layout depends on (accel, extend_variant).
 extern "C" int rt_share_scene(RtCtx* ctx, RtCtx* from)
@@ -573,7 +605,8 @@ extern "C" int rt_update_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t fir
 {
     if (!ctx) return fail(RT_E_INVALID, "rt_update_scene: null context");
     if (!ctx->sceneLoaded || !ctx->scene) return fail(RT_E_INVALID, "rt_update_scene: no scene uploaded");
-    if (ctx->cfg.accel != RT_ACCEL_BVH2) return fail(RT_E_UNSUPPORTED, "rt_update_scene: BVH4 contexts cannot refit (rebuild and upload instead)");
+    if (ctx->cfg.accel != RT_ACCEL_BVH2)
+        return fail(RT_E_UNSUPPORTED, "rt_update_scene: BVH4 contexts cannot refit (rt_rebuild_scene a copy bound with rt_upload_scene_bvh2, or rebuild and upload)");
     return update_scene(*ctx->scene, prims, first, count, blas, nBlas, stats);
 }
 extern "C" int rt_group_update_scene(RtGroup* g, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
@@ -587,7 +620,9 @@ extern "C" int rt_rebuild_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t fi
 {
     if (!ctx) return fail(RT_E_INVALID, "rt_rebuild_scene: null context");
     if (!ctx->sceneLoaded || !ctx->scene) return fail(RT_E_INVALID, "rt_rebuild_scene: no scene uploaded");
-    if (ctx->cfg.accel != RT_ACCEL_BVH2) return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: BVH4 contexts cannot rebuild in place (build on the host and upload instead)");
+    if (ctx->cfg.accel != RT_ACCEL_BVH2 && !ctx->scene->keepsBvh2)
+        return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: a BVH4 copy bound through rt_upload_scene has lost its BVH2 and cannot rebuild in place "
+                    "(bind the BVH2 with rt_upload_scene_bvh2, or build on the host and upload)");
     return rebuild_scene(*ctx->scene, prims, first, count, blas, nBlas, builder, opts, stats);
 }
 extern "C" int rt_group_rebuild_scene(RtGroup* g, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
@@ -1309,6 +1344,16 @@ extern "C" int rt_group_upload_scene(RtGroup* g, const RtPrimitive* prims, int32
 {
     if (!g) return fail(RT_E_INVALID, "rt_group_upload_scene: null group");
     int rc = rt_upload_scene(g->lane[0], prims, nPrims, mats, nMats, textures, nTexels, lights, nLights, bvhNodes, nNodes, primIdx, nIdx, tlas, nTlas, blas, nBlas);
+    for (size_t m = 1; m < g->lane.size() && rc == RT_OK; m++) rc = rt_share_scene(g->lane[m], g->lane[0]);   // ONE device copy
+    return rc;
+}
+extern "C" int rt_group_upload_scene_bvh2(RtGroup* g, const RtPrimitive* prims, int32_t nPrims, const RtMaterial* mats, int32_t nMats,
+                                          const RtFloat4* textures, int32_t nTexels, const uint32_t* lights, int32_t nLights,
+                                          const RtBVHNode2* bvhNodes, int32_t nNodes, const uint32_t* primIdx, int32_t nIdx,
+                                          const RtTLASNode* tlas, int32_t nTlas, const RtBVHInstance* blas, int32_t nBlas)
+{
+    if (!g) return fail(RT_E_INVALID, "rt_group_upload_scene_bvh2: null group");
+    int rc = rt_upload_scene_bvh2(g->lane[0], prims, nPrims, mats, nMats, textures, nTexels, lights, nLights, bvhNodes, nNodes, primIdx, nIdx, tlas, nTlas, blas, nBlas);
     for (size_t m = 1; m < g->lane.size() && rc == RT_OK; m++) rc = rt_share_scene(g->lane[m], g->lane[0]);   // ONE device copy
     return rc;
 }

@@ -129,12 +129,14 @@ extern "C" int rt_validate_scene(int32_t accel, const RtPrimitive* prims, int32_
 
 // What rt_update_scene needs of an upload: the counts, the host shadow of the fields an update must keep, and the refit topology on
 // the device (parents, reachable leaves, pair id -> node id).  A scene the update cannot handle records why (refitRefusal).
+// (a BVH4 copy that keeps its BVH2 - in.bvhNodes is the BVH2 - is prepared like a BVH2 copy: it can be rebuilt; rt_update_scene refuses
+// every BVH4 context before it comes here)
 static int prepare_update(SceneBag& b, int accel, int extendVariant, const HostScene& in, const std::vector<uint32_t>& pairNode)
 {
     const auto& [prims, nPrims, mats, nMats, textures, nTexels, lights, nLights, bvhNodes, nNodes, primIdx, nIdx, tlas, nTlas, blas, nBlas] = in;
     b.nPrims = nPrims; b.nNodes = nNodes; b.nIdx = nIdx; b.nLights = nLights; b.nTlas = nTlas; b.nBlas = nBlas;
     b.nPairs = (int32_t)pairNode.size(); b.accel = accel;
-    if (accel != RT_ACCEL_BVH2) { b.refitRefusal = "BVH4 scenes cannot be refit"; return RT_OK; }
+    if (accel != RT_ACCEL_BVH2 && !b.keepsBvh2) { b.refitRefusal = "BVH4 scenes cannot be refit"; return RT_OK; }
     if (nBlas > refit::kMaxInstances) { b.refitRefusal = "more than 256 instances (TLAS::Build's limit)"; return RT_OK; }
     if (nTlas != 2 * nBlas) { b.refitRefusal = "the TLAS does not have TLAS::Build's 2 x instances nodes"; return RT_OK; }
     refit::Topology t;
@@ -221,22 +223,8 @@ static std::vector<RtFloat4> quad_records(const RtBVHNode4* n4, int32_t nNodes, 
     const std::vector<uint32_t> order = breadth_first(all, newId, [&](uint32_t i, auto& number) {
         for (int k = 0; k < 4; k++) if (rebuild::bvh4_slot(n4[i], k, nNodes, nIdx) == rebuild::kSlotChild) number((uint32_t)n4[i].first[k]);
     });
-    auto f2u = [](uint32_t u) { float f; memcpy(&f, &u, 4); return f; };
     std::vector<RtFloat4> quads(std::max<size_t>(order.size(), 1) * 8, RtFloat4{ 0, 0, 0, 0 });
-    for (size_t q = 0; q < order.size(); q++) {
-        const uint32_t i = order[q];
-        float b[24]; uint32_t e[4];
-        for (int k = 0; k < 4; k++) {
-            const RtFloat4& mn = n4[i].aabbMin[k]; const RtFloat4& mx = n4[i].aabbMax[k];
-            b[k * 6 + 0] = mn.x; b[k * 6 + 1] = mn.y; b[k * 6 + 2] = mn.z; b[k * 6 + 3] = mx.x; b[k * 6 + 4] = mx.y; b[k * 6 + 5] = mx.z;
-            const int slot = rebuild::bvh4_slot(n4[i], k, nNodes, nIdx);
-            if (slot == rebuild::kSlotUnused) e[k] = 0xffffffffu;
-            else if (slot == rebuild::kSlotLeaf) e[k] = 0x80000000u | ((uint32_t)n4[i].count[k] << 24) | (uint32_t)n4[i].first[k];
-            else e[k] = newId[(uint32_t)n4[i].first[k]];
-        }
-        for (int v = 0; v < 6; v++) quads[q * 8 + v] = RtFloat4{ b[v * 4], b[v * 4 + 1], b[v * 4 + 2], b[v * 4 + 3] };
-        quads[q * 8 + 6] = RtFloat4{ f2u(e[0]), f2u(e[1]), f2u(e[2]), f2u(e[3]) };
-    }
+    for (size_t q = 0; q < order.size(); q++) collapse::quad_record(n4[order[q]], nNodes, nIdx, newId.data(), &quads[q * 8]);   // (k_c4_quads writes the same)
     for (int32_t b = 0; b < nBlas; b++) roots[(size_t)b] = newId[blas[b].bvhIdx];
     return quads;
 }
@@ -263,7 +251,11 @@ template <class T> static int upload(SceneBag& b, T** dst, const T* src, size_t 
 }
 template <class T> static int upload(SceneBag& b, T** dst, const std::vector<T>& v) { return upload(b, dst, v.data(), v.size()); }
 
-int scenedev::upload_scene(SceneBag& b, int accel, int extendVariant, const HostScene& in, int stackEntries, int64_t texPad, int tlasDepth)
+static int collapse_uploaded(SceneBag& b, SceneArrays& sc, int extendVariant, const HostScene& in, const std::vector<collapse::Blas>& blas4, int& layout,
+                             int& stackEntries, std::vector<uint32_t>& roots);   // (below, with the rebuild's helpers it shares)
+
+int scenedev::upload_scene(SceneBag& b, int accel, int extendVariant, const HostScene& in, int stackEntries, int64_t texPad, int tlasDepth,
+                           const std::vector<collapse::Blas>* blas4)
 {
     const auto& [prims, nPrims, mats, nMats, textures, nTexels, lights, nLights, bvhNodes, nNodes, primIdx, nIdx, tlas, nTlas, blas, nBlas] = in;
     // ---- derive.  Layout 1 (pair or quad records, triangle records, encoded roots) only when the encodings fit (rebuild_common.h,
@@ -276,6 +268,8 @@ int scenedev::upload_scene(SceneBag& b, int accel, int extendVariant, const Host
         uint32_t largestLeaf = 0;
         for (int32_t i = 0; i < nNodes; i++) largestLeaf = std::max(largestLeaf, n2[i].count);
         if (rebuild::takes_layout1(extendVariant != 1, nIdx, largestLeaf)) { pairs = pair_records(n2, nNodes, blas, nBlas, pairNode, roots); layout = 1; }
+    } else if (blas4) {
+        // (the layout follows from the collapse on the device, below)
     } else if (extendVariant != 1 && nIdx < (1 << 24)) {
         bool fits = true;
         for (int32_t i = 0; i < nNodes && fits; i++) for (int k = 0; k < 4; k++) if (n4[i].first[k] != RT_INVALID && n4[i].count[k] > (int32_t)rebuild::kMaxPackedLeaf) fits = false;
@@ -291,13 +285,14 @@ int scenedev::upload_scene(SceneBag& b, int accel, int extendVariant, const Host
         if (nTexels) HIPCHK(hipMemcpy(sc.tex, textures, sizeof(RtFloat4) * (size_t)nTexels, hipMemcpyHostToDevice));
     }
     if (rc == RT_OK) rc = upload(b, &sc.lights, lights, (size_t)nLights);
-    if (rc == RT_OK) rc = accel == RT_ACCEL_BVH4 ? upload(b, &sc.bvh4, n4, (size_t)nNodes) : upload(b, &sc.bvh2, n2, (size_t)nNodes);
+    if (rc == RT_OK) rc = accel == RT_ACCEL_BVH4 && !blas4 ? upload(b, &sc.bvh4, n4, (size_t)nNodes) : upload(b, &sc.bvh2, n2, (size_t)nNodes);
     if (rc == RT_OK) rc = upload(b, &sc.primIdx, primIdx, (size_t)nIdx);
     if (rc == RT_OK) rc = upload(b, &sc.tlas, tlas, (size_t)nTlas);
     if (rc == RT_OK) rc = upload(b, &sc.blas, blas, (size_t)nBlas);
     if (rc == RT_OK) rc = upload(b, &sc.shadeRecs, shade_records(prims, nPrims));
     if (rc == RT_OK) rc = upload(b, &sc.lightRecs, light_records(prims, mats, lights, nLights));
-    if (rc == RT_OK && layout == 1) {
+    if (rc == RT_OK && blas4) rc = collapse_uploaded(b, sc, extendVariant, in, *blas4, layout, stackEntries, roots);
+    else if (rc == RT_OK && layout == 1) {
         rc = accel == RT_ACCEL_BVH4 ? upload(b, &sc.quads, quads) : upload(b, &sc.pairs, pairs);
         if (rc == RT_OK) rc = upload(b, &sc.triRecs, triangle_records(prims, primIdx, nIdx));
         if (rc == RT_OK) rc = upload(b, &sc.rootEntry, roots);
@@ -313,6 +308,7 @@ int scenedev::upload_scene(SceneBag& b, int accel, int extendVariant, const Host
     // ---- bind: the copy's facts, and what updates and rebuilds need of this upload
     b.sc = sc;
     b.layout = layout; b.stackEntries = stackEntries; b.tlasDepth = tlasDepth; b.nInterior = (int)pairNode.size(); b.singleBlas = leafRoot;
+    if (!blas4) b.nQuads = (int32_t)(quads.size() / 8);
     return prepare_update(b, accel, extendVariant, in, pairNode);
 }
 
@@ -394,6 +390,86 @@ template <class T> static int rebuild_grow(SceneBag& b, SceneBag::Grown<T>& a, s
     a.p = (T*)q; a.cap = count;
     return RT_OK;
 }
+
+// ---- the BVH2 -> BVH4 collapse of a copy that keeps its BVH2 (kernels: collapse.hip, rules: collapse_common.h) --------------------------
+// The collapse's scratch for trees of nodeNeed nodes in all and nR BLAS; grows as the derivation's scratch does (rebuild_scratch)
+static int collapse_scratch(SceneBag& b, size_t nodeNeed, size_t nR)
+{
+    const bool have = b.c4NewId.p != nullptr;
+    size_t cap = nodeNeed <= b.c4NewId.cap ? b.c4NewId.cap : nodeNeed + (have ? nodeNeed / kRebuildHeadroomDiv : 0);
+    cap = (cap + 1) & ~(size_t)1;
+    const size_t front = cap / 2 + 1, quad = cap / 2 + nR;
+    if (4 * front > (size_t)0x7fffffff) return fail(RT_E_UNSUPPORTED, "the BVH4 collapse takes at most 2^30 nodes (%zu given)", nodeNeed);
+    int rc = rebuild_grow(b, b.c4NewId, cap, 0, "collapse scratch");
+    if (rc == RT_OK) rc = rebuild_grow(b, b.c4FrontA, front, 0, "collapse scratch");
+    if (rc == RT_OK) rc = rebuild_grow(b, b.c4FrontB, front, 0, "collapse scratch");
+    if (rc == RT_OK) rc = rebuild_grow(b, b.c4Flags, 4 * front, 0, "collapse scratch");
+    if (rc == RT_OK) rc = rebuild_grow(b, b.c4Ranks, 4 * front, 0, "collapse scratch");
+    if (rc == RT_OK) rc = rebuild_grow(b, b.c4Kids, 4 * front, 0, "collapse scratch");
+    if (rc == RT_OK) rc = rebuild_grow(b, b.c4QuadNode, quad, 0, "collapse scratch");
+    if (rc == RT_OK) rc = rebuild_grow(b, b.c4Ctr, collapsedev::kCtrWords, 0, "collapse scratch");
+    if (rc != RT_OK) return rc;
+    const size_t frontCap = std::min(std::min(b.c4FrontA.cap, b.c4FrontB.cap), std::min(std::min(b.c4Flags.cap, b.c4Ranks.cap), b.c4Kids.cap) / 4);
+    size_t scanBytes = 0;
+    HIPCHK(collapsedev::scan_bytes((uint32_t)(4 * frontCap), b.stream, &scanBytes));
+    rc = rebuild_grow(b, b.c4Scan, std::max<size_t>(scanBytes, 256), 0, "scan workspace");
+    if (rc != RT_OK) return rc;
+    b.c4 = collapsedev::Work{ b.c4FrontA.p, b.c4FrontB.p, (uint32_t)frontCap, b.c4Flags.p, b.c4Ranks.p, b.c4Kids.p, b.c4NewId.p, b.c4QuadNode.p,
+                              (uint32_t)b.c4QuadNode.cap, b.c4Ctr.p, b.c4Scan.p, b.c4Scan.cap };
+    return RT_OK;
+}
+// What a collapse left in its status words: a failed walk, a BLAS that needs more stack than there is.  `tail` ends the stack message.
+static int collapse_status_error(const char* who, const uint32_t st[collapsedev::kStatusWords], const char* tail)
+{
+    using namespace collapsedev;
+    if (st[kWalkWord - kStatus]) return fail(RT_E_DEVICE, "%s: the BVH4 level walk does not match the BVH2 (inconsistent device result)", who);
+    if (rebuild::exceeds_stack(st[kNeed - kStatus]))   // validate_scene's rule for a BVH4
+        return fail(RT_E_UNSUPPORTED, "%s: a collapsed BLAS: traversal needs %u stack entries, at most %d are supported%s", who, st[kNeed - kStatus], RT_BVH4_STACK, tail);
+    return RT_OK;
+}
+static uint32_t collapse_largest_leaf(const uint32_t st[collapsedev::kStatusWords])
+{
+    return std::max(std::max(st[collapsedev::kLeaf - collapsedev::kStatus], st[collapsedev::kLeafAny - collapsedev::kStatus]), 1u);
+}
+// rt_upload_scene_bvh2 on a BVH4 context, after the wire arrays are on the device: the collapse into sc.bvh4, then the layout, the stack
+// size and the layout-1 records (quads, root entries, triangle records) as rt_upload_scene derives them from the host's collapse
+static int collapse_uploaded(SceneBag& b, SceneArrays& sc, int extendVariant, const HostScene& in, const std::vector<collapse::Blas>& blas4, int& layout,
+                             int& stackEntries, std::vector<uint32_t>& roots)
+{
+    using namespace collapsedev;
+    const char* who = "rt_upload_scene_bvh2";
+    const int32_t nNodes = in.nNodes, nIdx = in.nIdx, nBlas = in.nBlas;
+    if (!b.stream) HIPCHK(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));
+    hipStream_t s = b.stream;
+    int rc = dalloc(b.allocs, &sc.bvh4, (size_t)nNodes);
+    if (rc == RT_OK) rc = collapse_scratch(b, (size_t)nNodes, blas4.size());
+    if (rc != RT_OK) return rc;
+    HIPCHK(begin(s, b.c4, sc.bvh2, (uint32_t)nNodes, sc.bvh4));
+    for (const collapse::Blas& k : blas4) HIPCHK(collapse_blas(s, b.c4, sc.bvh2, (uint32_t)nNodes, k.root, k.interiors, k.height, sc.bvh4));
+    uint32_t st[kStatusWords] = { 0 };
+    HIPCHK(hipMemcpyAsync(st, b.c4.ctr + kStatus, sizeof st, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if ((rc = collapse_status_error(who, st, "")) != RT_OK) return rc;
+    const uint32_t live = st[kLive - kStatus];
+    layout = rebuild::takes_layout1(extendVariant != 1, nIdx, collapse_largest_leaf(st)) ? 1 : 0;
+    stackEntries = rebuild::stack_entries((int)std::max(st[kNeed - kStatus], 1u));
+    b.nQuads = layout == 1 ? (int32_t)live : 0;
+    b.keepsBvh2 = true;
+    if (layout != 1) return RT_OK;
+    rc = dalloc(b.allocs, &sc.quads, (size_t)std::max(live, 1u) * 8);
+    if (rc == RT_OK) rc = dalloc(b.allocs, &sc.rootEntry, (size_t)nBlas);
+    if (rc == RT_OK) rc = dalloc(b.allocs, &sc.triRecs, (size_t)nIdx * 3);
+    if (rc != RT_OK) return rc;
+    Work w = b.c4;
+    w.quadCap = std::min(w.quadCap, std::max(live, 1u));   // what sc.quads holds
+    HIPCHK(finish(s, w, sc.bvh4, (uint32_t)nNodes, (uint32_t)nIdx, (const uint32_t*)sc.blas, (uint32_t)(sizeof(RtBVHInstance) / 4), (uint32_t)nBlas, sc.quads, sc.rootEntry));
+    HIPCHK(refitdev::launch_records(s, sc.prims, sc.bvh2, sc.primIdx, (uint32_t)nIdx, sc.lights, (uint32_t)in.nLights, 0u, (uint32_t)in.nPrims, nullptr, 0u, nullptr,
+                                    sc.triRecs, sc.shadeRecs, sc.lightRecs));
+    HIPCHK(hipMemcpyAsync(roots.data(), sc.rootEntry, sizeof(uint32_t) * (size_t)nBlas, hipMemcpyDeviceToHost, s));   // (the instance records carry them)
+    HIPCHK(hipStreamSynchronize(s));
+    return RT_OK;
+}
+
 int scenedev::update_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas, RtUpdateStats* stats)
 {
     const char* who = "rt_update_scene";
@@ -483,6 +559,10 @@ static int rebuild_reserve(SceneBag& b, SceneBag::RebuildSet& t, size_t idxNeed,
     if (rc == RT_OK) rc = rebuild_grow(b, t.pairs, std::max<size_t>(nodeCap / 2, 1) * 4, 0, "pair records");
     if (rc == RT_OK) rc = rebuild_grow(b, t.leaves, nodeCap / 2, 0, "leaves");
     if (rc == RT_OK) rc = rebuild_grow(b, t.pairNode, nodeCap / 2, 0, "pair nodes");
+    if (b.accel == RT_ACCEL_BVH4) {   // (a copy that keeps its BVH2: the collapsed records, and a quad record per interior node and leaf root at most)
+        if (rc == RT_OK) rc = rebuild_grow(b, t.bvh4, nodeCap, 0, "BVH4 nodes");
+        if (rc == RT_OK) rc = rebuild_grow(b, t.quads, (nodeCap / 2 + b.ranges.size()) * 8, 0, "quad records");
+    }
     return rc;
 }
 // The derivation's scratch for trees of nodeNeed nodes in all (flags / ranks / newId: a word per node, the frontiers: per interior node)
@@ -626,6 +706,8 @@ int scenedev::rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first
         nNodes += built.nodes; nIdx += slots;
     }
     if (const int rc = rebuild_scratch(b, (size_t)nNodes + nR)) return rc;
+    const bool bvh4 = b.accel == RT_ACCEL_BVH4;
+    if (bvh4) if (const int rc = collapse_scratch(b, (size_t)nNodes + nR, nR)) return rc;
     const auto t2 = clock::now();
     // ---- the instances (host: at most 256 records), then everything upload derives
     std::vector<RtBVHInstance> inst = b.inst;
@@ -647,7 +729,22 @@ int scenedev::rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first
     }
     const uint32_t nLeaves = nNodes - nPairs;
     const bool layout1 = b.layout == 1;
-    HIPCHK(rebuilddev::finish(s, b.dw, t.nodes.p, nNodes, nPairs, nLeaves, t.blas, (uint32_t)b.nBlas, t.pairNode.p, layout1 ? t.pairs.p : nullptr, t.rootEntry, t.leaves.p));
+    HIPCHK(rebuilddev::finish(s, b.dw, t.nodes.p, nNodes, nPairs, nLeaves, t.blas, (uint32_t)b.nBlas, t.pairNode.p, layout1 && !bvh4 ? t.pairs.p : nullptr, t.rootEntry,
+                              t.leaves.p));
+    if (bvh4) {   // the collapse into the set's bvh4, BLAS by BLAS in the same order; quad records and root entries (layout 1)
+        collapsedev::Work w = b.c4;
+        w.quadCap = (uint32_t)std::min<size_t>(w.quadCap, t.quads.cap / 8);
+        HIPCHK(collapsedev::begin(s, w, t.nodes.p, nNodes, t.bvh4.p));
+        std::vector<uint8_t> done(nR, 0);
+        for (int32_t i = 0; i < b.nBlas; i++) {
+            const size_t k = (size_t)b.instBlas[(size_t)i];
+            if (done[k]) continue;
+            done[k] = 1;
+            HIPCHK(collapsedev::collapse_blas(s, w, t.nodes.p, nNodes, rootOf[k], interiors[k], depth[k], t.bvh4.p));
+        }
+        HIPCHK(collapsedev::finish(s, w, t.bvh4.p, nNodes, nIdx, (const uint32_t*)t.blas, (uint32_t)(sizeof(RtBVHInstance) / 4), (uint32_t)b.nBlas,
+                                   layout1 ? t.quads.p : nullptr, t.rootEntry));
+    }
     HIPCHK(refitdev::launch_records(s, t.prims, t.nodes.p, t.primIdx.p, nIdx, sc.lights, (uint32_t)b.nLights, 0u, (uint32_t)b.nPrims, nullptr, 0u, nullptr,
                                     layout1 ? t.triRecs.p : nullptr, t.shadeRecs, t.lightRecs));
     HIPCHK(hipEventRecord(b.rev[2], s));
@@ -657,9 +754,16 @@ int scenedev::rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first
     uint32_t walk[2] = { 0, 0 };
     HIPCHK(hipMemcpyAsync(status, b.rStatus, sizeof status, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(walk, b.dw.ctr + rebuilddev::kStatus, sizeof walk, hipMemcpyDeviceToHost, s));
+    uint32_t c4st[collapsedev::kStatusWords] = { 0 };
+    if (bvh4) HIPCHK(hipMemcpyAsync(c4st, b.c4.ctr + collapsedev::kStatus, sizeof c4st, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (walk[0]) return fail(RT_E_DEVICE, "rt_rebuild_scene: the breadth-first walk does not match the builder's tree (inconsistent device result)");
+    if (bvh4) {
+        if (const int rc = collapse_status_error(who, c4st, "; the scene is unchanged")) return rc;
+        walk[1] = collapse_largest_leaf(c4st);   // the layout rule of a BVH4 looks at the collapsed records
+    }
     if (const int rc = tlas_status_error(who, status)) return rc;
+    const int stackNeed = bvh4 ? (int)c4st[collapsedev::kNeed - collapsedev::kStatus] : (int)maxDepth;
     if (rebuild::takes_layout1(b.variantLayout1, (int32_t)nIdx, std::max(walk[1], 1u)) != layout1)
         return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: the new trees would change the scene's derived layout (largest leaf %u primitives, %u index slots; "
                     "layout %d is bound): upload the rebuilt scene instead; the scene is unchanged", walk[1], nIdx, b.layout);
@@ -670,16 +774,19 @@ int scenedev::rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first
     n.prims = t.prims; n.bvh2 = t.nodes.p; n.primIdx = t.primIdx.p; n.blas = t.blas; n.tlas = t.tlas;
     n.tlasPairs = t.tp; n.tlasPairsP = t.tpP; n.instRecs = t.ir;
     n.shadeRecs = t.shadeRecs; n.lightRecs = t.lightRecs;
-    if (layout1 && nPairs == 0) HIPCHK(hipMemsetAsync(t.pairs.p, 0, sizeof(RtFloat4) * 4, s));   // no interior node: one zero record, as at upload
-    if (layout1) { n.pairs = t.pairs.p; n.triRecs = t.triRecs.p; n.rootEntry = t.rootEntry; }
+    if (layout1 && !bvh4 && nPairs == 0) HIPCHK(hipMemsetAsync(t.pairs.p, 0, sizeof(RtFloat4) * 4, s));   // no interior node: one zero record, as at upload
+    if (layout1 && !bvh4) n.pairs = t.pairs.p;
+    if (layout1) { n.triRecs = t.triRecs.p; n.rootEntry = t.rootEntry; }
+    if (bvh4) { n.bvh4 = t.bvh4.p; if (layout1) n.quads = t.quads.p; }
     b.sc = n;
     b.dParent = t.parent.p; b.dLeaves = t.leaves.p; b.dTickets = t.tickets.p; b.dPairNode = t.pairNode.p;
-    b.nNodes = (int32_t)nNodes; b.nIdx = (int32_t)nIdx; b.nPairs = layout1 ? (int32_t)nPairs : 0; b.nLeaves = nLeaves; b.nReach = nNodes;
+    b.nNodes = (int32_t)nNodes; b.nIdx = (int32_t)nIdx; b.nPairs = layout1 && !bvh4 ? (int32_t)nPairs : 0; b.nLeaves = nLeaves; b.nReach = nNodes;
+    b.nQuads = layout1 && bvh4 ? (int32_t)c4st[collapsedev::kLive - collapsedev::kStatus] : 0;
     b.inst = inst;
-    const bool reconfigure = status[1] != b.tlasDepth || rebuild::stack_entries((int)std::max(maxDepth, 1u)) != b.stackEntries;
+    const bool reconfigure = status[1] != b.tlasDepth || rebuild::stack_entries(std::max(stackNeed, 1)) != b.stackEntries;
     b.tlasDepth = status[1];
-    b.stackEntries = rebuild::stack_entries((int)std::max(maxDepth, 1u));
-    b.nInterior = layout1 ? (int)nPairs : 0;
+    b.stackEntries = rebuild::stack_entries(std::max(stackNeed, 1));   // (a BVH4: the collapsed trees' need, as validate_scene replays it)
+    b.nInterior = layout1 && !bvh4 ? (int)nPairs : 0;
     b.generation++;   // every holder takes the new arrays (and re-derives its traversal kernels) before its next launch
     b.rnext ^= 1;
     const auto t4 = clock::now();
@@ -727,6 +834,9 @@ int scenedev::scene_array(const SceneBag& b, int32_t which, const void** src, si
     case RT_SCENE_TLAS_PAIRS:   *src = sc.tlasPairs; *n = sizeof(RtFloat4) * 4 * (size_t)b.nTlas; break;
     case RT_SCENE_TLAS_PAIRS_P: *src = sc.tlasPairsP; *n = sizeof(RtFloat4) * 4 * (size_t)b.nTlas; break;
     case RT_SCENE_INST_RECS:    *src = sc.instRecs; *n = sizeof(RtFloat4) * 4 * (size_t)b.nBlas; break;
+    case RT_SCENE_QUADS:        *src = sc.quads; *n = sc.quads ? sizeof(RtFloat4) * 8 * (size_t)std::max(b.nQuads, 1) : 0; break;
+    case RT_SCENE_ROOT_ENTRY:   *src = sc.rootEntry; *n = sc.rootEntry ? sizeof(uint32_t) * (size_t)b.nBlas : 0; break;
+    case RT_SCENE_BVH2_KEPT:    *src = sc.bvh2; *n = b.keepsBvh2 ? sizeof(RtBVHNode2) * (size_t)b.nNodes : 0; break;
     default: return fail(RT_E_INVALID, "rt_debug_get_scene_array: unknown array %d", which);
     }
     return RT_OK;

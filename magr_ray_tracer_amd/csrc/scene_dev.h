@@ -10,6 +10,7 @@
 #include "refit_common.h"
 #include "rebuild_common.h"
 #include "rebuild_dev.h"
+#include "collapse_dev.h"
 #include "build_cores.h"
 
 int rt355_set_error(int code, const char* msg);   // rt355.hip: sets the text rt_last_error() returns
@@ -62,6 +63,8 @@ struct SceneBag {
     // rt_update_scene: what an in-place update needs of the upload, kept beside the device copy
     const char* refitRefusal = nullptr;       // why this scene cannot be updated in place (NULL: it can)
     int32_t nPrims = 0, nNodes = 0, nIdx = 0, nLights = 0, nTlas = 0, nBlas = 0, nPairs = 0, accel = 0;
+    int32_t nQuads = 0;                       // quad records (the surviving nodes of a BVH4 in layout 1)
+    bool keepsBvh2 = false;                   // a BVH4 copy bound with its BVH2 (rt_upload_scene_bvh2): sc.bvh2 is kept, the copy can be rebuilt
     std::vector<int32_t> primType, primMat;   // host shadow of every primitive's objType / matIdx (the light list and materials depend on them)
     std::vector<RtBVHInstance> inst;          // the instances as last uploaded or updated
     uint32_t *dParent = nullptr, *dLeaves = nullptr, *dPairNode = nullptr, *dTickets = nullptr;   // refit topology (walked from the BLAS roots)
@@ -96,8 +99,12 @@ struct SceneBag {
         Grown<uint32_t> primIdx; Grown<RtFloat4> triRecs;                                    // index slots (triRecs: 3 per slot)
         Grown<RtBVHNode2> nodes; Grown<uint32_t> parent, tickets;                            // nodes
         Grown<RtFloat4> pairs; Grown<uint32_t> leaves, pairNode;                             // nodes / 2 (pairs: 4 per interior node)
+        Grown<RtBVHNode4> bvh4; Grown<RtFloat4> quads;                                       // a BVH4 copy: nodes; nodes / 2 + one per BLAS (8 per live node)
     } rset[2];
     Grown<uint32_t> dwFlags, dwRanks, dwNewId, dwFrontA, dwFrontB; Grown<char> dwScan;   // the derivation's scratch, grown likewise
+    // the collapse's scratch (a BVH4 copy that keeps its BVH2), grown likewise: frontiers, flags / ranks / kids, newId, quadNode, scan, counters
+    Grown<uint2> c4FrontA, c4FrontB; Grown<uint32_t> c4Flags, c4Ranks, c4Kids, c4NewId, c4QuadNode, c4Ctr; Grown<char> c4Scan;
+    collapsedev::Work c4{};
     sbvhdev::Pool* spool = nullptr;           // the SBVH builder's device blocks, kept from rebuild to rebuild
     uint64_t rallocs = 0;                     // device allocations by updates and rebuilds of this copy (rt_debug_rebuild_allocations)
     int rnext = 0;                            // the set the next rebuild writes
@@ -123,7 +130,9 @@ struct HostScene {   // the host arrays of rt_upload_scene (include/rt355.h), in
 };
 int validate_scene(int accel, const HostScene& in, int* stackEntriesOut, int64_t* texPadOut, int* tlasDepthOut);
 // fills a fresh copy on the current device from arrays that have passed validate_scene, which gave the last three arguments
-int upload_scene(SceneBag& b, int accel, int extendVariant, const HostScene& in, int stackEntries, int64_t texPad, int tlasDepth);
+// blas4 != NULL (a BVH4 context, in.bvhNodes is the BVH2; collapse::check_args gave the BLAS): the BVH2 is kept and collapsed on the device
+int upload_scene(SceneBag& b, int accel, int extendVariant, const HostScene& in, int stackEntries, int64_t texPad, int tlasDepth,
+                 const std::vector<collapse::Blas>* blas4 = nullptr);
 int update_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas, RtUpdateStats* stats);
 int rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
                   int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats);

@@ -122,6 +122,30 @@ int rth_build_bvh2_sbvh(float alpha, const RtPrimitive* prims, int32_t nPrims, i
 }
 int rth_set_build_threads(RthScene* s, int threads) { if (!s) return -1; s->scene.bvh2->buildThreads = threads < 1 ? 1 : threads; return 0; }
 int rth_build_bvh4(RthScene* s) { GUARD(s->scene.BuildBVH4()) }
+int rth_build_bvh4_gpu(RthScene* s, int device)
+{
+    if (!s || !s->scene.bvh2) { g_herr = "rth_build_bvh4_gpu: null scene"; return RT_E_INVALID; }
+    try {
+        Scene& sc = s->scene;
+        const std::vector<RtBVHNode2>& n2 = sc.bvh2->bvhNodes;
+        std::vector<RtBVHNode4> out(n2.size());
+        std::vector<uint32_t> roots;
+        for (const RtBVHInstance& inst : sc.blasNodes) roots.push_back(inst.bvhIdx);
+        std::string err;
+        const int rc = device < 0
+            ? Bvh4LevelsHost(n2.data(), (int32_t)n2.size(), (int32_t)sc.bvh2->primIdx.size(), roots.data(), (int32_t)roots.size(), out.data(), nullptr, nullptr,
+                             nullptr, nullptr, err)
+            : rt_build_bvh4(device, n2.data(), (int32_t)n2.size(), (int32_t)sc.bvh2->primIdx.size(), roots.data(), (int32_t)roots.size(), out.data(), nullptr);
+        if (rc != RT_OK) { g_herr = device < 0 ? err : std::string(rt_last_error()); return rc; }   // (the scene keeps the BVH4 it had)
+        delete sc.bvh4; sc.bvh4 = new BVH4(*sc.bvh2, std::move(out));
+        return 0;
+    } catch (const std::exception& e) { g_herr = e.what(); return RT_E_NOMEM; }
+}
+int rth_build_bvh4_levels(const RtBVHNode2* nodes2, int32_t nNodes, int32_t nIdx, const uint32_t* roots, int32_t nRoots, RtBVHNode4* out4,
+                          RtBvh4Stats* stats, RtFloat4* quads, uint32_t* rootEntry, uint32_t* quadNode)
+{
+    return build_bvh2([&](std::string& err) { return Bvh4LevelsHost(nodes2, nNodes, nIdx, roots, nRoots, out4, stats, quads, rootEntry, quadNode, err); });
+}
 // BVH4::Convert + Collapse (bvh.cpp:695-787) on a caller-provided BVH2 node array with ONE BLAS rooted at node 0: how the tests feed
 // the reference's own hand-built 13-node tree (bvh.cpp:615-674) through the collapse.
 int rth_bvh4_from_nodes(const RtBVHNode2* nodes, int n, RtBVHNode4* out)

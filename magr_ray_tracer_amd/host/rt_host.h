@@ -131,6 +131,11 @@ int SbvhBuildHost(float alpha, const RtPrimitive* prims, int32_t nPrims, int32_t
                   RtBVHNode2* nodes, int32_t nodeCap, int32_t* nNodes, uint32_t* primIdx, int32_t idxCap, int32_t* nIdx, RtSbvhStats* stats,
                   std::string& err);
 
+// The GPU BVH2 -> BVH4 collapse's sequential host restatement (rth_build_bvh4_levels, collapse_host.cpp); err receives the message of a
+// refused call, which writes nothing.
+int Bvh4LevelsHost(const RtBVHNode2* nodes2, int32_t nNodes, int32_t nIdx, const uint32_t* roots, int32_t nRoots, RtBVHNode4* out4, RtBvh4Stats* stats,
+                   RtFloat4* quads, uint32_t* rootEntry, uint32_t* quadNode, std::string& err);
+
 // In-place updates (refit_host.cpp, the host restatement of rt_update_scene): replace primitives keeping objType / matIdx, then refit
 // every BLAS by the rules of csrc/refit_common.h; err receives why a call is refused (RT_E_* returned, nothing changed).
 int SetPrimitivesHost(std::vector<RtPrimitive>& prims, int32_t first, int32_t count, const RtPrimitive* in, std::string& err);
@@ -141,6 +146,7 @@ int RefitHost(std::vector<RtBVHNode2>& nodes, const std::vector<uint32_t>& primI
 class BVH4 {
 public:
     explicit BVH4(BVH2& bvh2);
+    BVH4(BVH2& bvh2, std::vector<RtBVHNode4>&& collapsed) : bvh2(bvh2), bvhNodes(std::move(collapsed)) {}   // nodes collapsed elsewhere (rt_build_bvh4)
     std::vector<RtBVHNode4>& Nodes() { return bvhNodes; }
     std::vector<uint32_t>&   Idx() { return bvh2.primIdx; }
     uint32_t Depth(uint32_t nodeIdx) const;

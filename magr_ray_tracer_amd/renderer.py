@@ -102,13 +102,22 @@ class Device:
             pass
 
     # ---- uploads (renderer.cpp:160-208)
-    def upload(self, sa):
-        nodes = sa.nodes(self.accel)
+    def upload(self, sa, from_bvh2=False):
+        """Bind the scene arrays (rt_upload_scene).  from_bvh2=True hands over the BVH2 whatever the context's accel
+        (rt_upload_scene_bvh2): a BVH4 context collapses it on the GPU and keeps it, so rebuild_scene works on the copy.  A refusal
+        raises RtError (.code)."""
+        nodes = sa.bvh2 if from_bvh2 else sa.nodes(self.accel)
         P = _lib.ptr
-        self._chk(self._lib.rt_upload_scene(
+        self._chk_code((self._lib.rt_upload_scene_bvh2 if from_bvh2 else self._lib.rt_upload_scene)(
             self._h, P(sa.prims), len(sa.prims), P(sa.mats), len(sa.mats), P(sa.tex) if len(sa.tex) else None, len(sa.tex),
             P(sa.lights) if len(sa.lights) else None, len(sa.lights), P(nodes), len(nodes), P(sa.primIdx), len(sa.primIdx),
             P(sa.tlas), len(sa.tlas), P(sa.blas), len(sa.blas)))
+
+    def _chk_code(self, rc):
+        if rc != 0:
+            e = RtError(self._lib.rt_last_error().decode())
+            e.code = rc
+            raise e
 
     def share_scene(self, other):
         """Render the scene `other` (a Device on the same GPU, same accel) holds, from ITS device copy (rt_share_scene)."""
@@ -144,8 +153,8 @@ class Device:
         return n.value
 
     def scene_array(self, name):
-        """A device array of the bound scene as raw bytes (rt_debug_get_scene_array; names: _lib.SCENE_ARRAYS)."""
-        which = _lib.SCENE_ARRAYS[name]
+        """A device array of the bound scene as raw bytes (rt_debug_get_scene_array; names: _lib.SCENE_ARRAYS, _lib.SCENE_ARRAYS_BVH4)."""
+        which = _lib.SCENE_ARRAYS[name] if name in _lib.SCENE_ARRAYS else _lib.SCENE_ARRAYS_BVH4[name]
         n = C.c_int64(0)
         self._chk(self._lib.rt_debug_get_scene_array(self._h, which, None, 0, C.byref(n)))
         out = np.zeros(n.value, dtype=np.uint8)
@@ -351,10 +360,11 @@ class Group:
     def frames(self):
         return int(self._lib.rt_group_frames(self._h))
 
-    def upload(self, sa):
-        nodes = sa.nodes(self.accel)
+    def upload(self, sa, from_bvh2=False):
+        """Device.upload for the group: one device copy that every lane holds (rt_group_upload_scene / rt_group_upload_scene_bvh2)."""
+        nodes = sa.bvh2 if from_bvh2 else sa.nodes(self.accel)
         P = _lib.ptr
-        self._chk(self._lib.rt_group_upload_scene(
+        self._chk((self._lib.rt_group_upload_scene_bvh2 if from_bvh2 else self._lib.rt_group_upload_scene)(
             self._h, P(sa.prims), len(sa.prims), P(sa.mats), len(sa.mats), P(sa.tex) if len(sa.tex) else None, len(sa.tex),
             P(sa.lights) if len(sa.lights) else None, len(sa.lights), P(nodes), len(nodes), P(sa.primIdx), len(sa.primIdx),
             P(sa.tlas), len(sa.tlas), P(sa.blas), len(sa.blas)))

@@ -168,8 +168,18 @@ class Scene:
         self._chk(self._lib.rth_lbvh_stats(self._h, _lib.ptr(st)))
         return _stats_dict(st)
 
-    def BuildBVH4(self):
-        self._chk(self._lib.rth_build_bvh4(self._h))
+    def BuildBVH4(self, builder="host", device=0):
+        """The BVH4 of the scene's BVH2 (reference: new BVH4(*bvh2)).  builder="host": BVH4::Convert / Collapse, sequential.
+        builder="gpu": the level-wise collapse (rt_build_bvh4) on HIP device `device`, or its host restatement when device is None; the
+        arrays are the same byte for byte.  A refused "gpu" build raises BuildError and keeps the BVH4 the scene had."""
+        if builder == "host":
+            self._chk(self._lib.rth_build_bvh4(self._h))
+        elif builder == "gpu":
+            rc = self._lib.rth_build_bvh4_gpu(self._h, -1 if device is None else int(device))
+            if rc != 0:
+                raise BuildError(rc, self._lib.rth_last_error().decode())
+        else:
+            raise ValueError(f"unknown builder {builder!r} (expected 'host' or 'gpu')")
 
     def BuildTLAS(self):
         self._chk(self._lib.rth_build_tlas(self._h))
@@ -369,6 +379,35 @@ def build_sbvh_gpu(prims, alpha, first=0, count=None, device=None, node_base=0, 
         err = BuildError(rc, text)
         err.needed = (nn.value, ni.value)
         raise err
+
+
+def build_bvh4_gpu(nodes2, roots, n_idx, device=None, out=None, derived=False):
+    """The BVH2 -> BVH4 collapse of BVHNode2 records whose BLAS roots are `roots` (the instances' bvhIdx, in instance order) and whose
+    leaves index n_idx primIdx slots: rt_build_bvh4 on HIP device `device`, or its host restatement (rth_build_bvh4_levels) when device
+    is None.  Returns (BVHNode4 array, stats); raises BuildError (.code) when refused.  out: the caller's BVHNode4 array to write into
+    (e.g. pre-filled to see that a refused call leaves it alone).  derived=True (host restatement only): also returns what the upload
+    derives, (nodes4, stats, quads (live, 8, 4) float32, rootEntry, quadNode)."""
+    n2 = np.ascontiguousarray(nodes2, dtype=_lib.BVHNode2)
+    r = np.ascontiguousarray(roots, dtype=np.uint32)
+    out = np.zeros(max(len(n2), 1), _lib.BVHNode4) if out is None else out
+    if out.dtype != _lib.BVHNode4 or len(out) < len(n2):
+        raise ValueError("out: a BVHNode4 array of len(nodes2) records expected")
+    if derived and device is not None:
+        raise ValueError("derived=True is the host restatement's (device=None)")
+    st = np.zeros((), _lib.Bvh4Stats)
+    args = [_lib.ptr(n2) if len(n2) else None, len(n2), int(n_idx), _lib.ptr(r) if len(r) else None, len(r), _lib.ptr(out), _lib.ptr(st)]
+    if device is None:
+        quads = np.zeros((max(len(n2), 1), 8, 4), np.float32) if derived else None
+        entry, qnode = (np.zeros(max(len(r), 1), np.uint32), np.zeros(max(len(n2), 1), np.uint32)) if derived else (None, None)
+        args += [_lib.ptr(quads), _lib.ptr(entry), _lib.ptr(qnode)]
+    rc, text = _build_call("rth_build_bvh4_levels", "rt_build_bvh4", device, *args)
+    if rc != 0:
+        raise BuildError(rc, text)
+    stats = {k: (float(st[k]) if k in ("device_ms", "wall_ms") else int(st[k])) for k in _lib.Bvh4Stats.names}
+    if derived:
+        live = stats["live_nodes"]
+        return out[:len(n2)], stats, quads[:live].copy(), entry[:len(r)].copy(), qnode[:live].copy()
+    return out[:len(n2)], stats
 
 
 def make_camera(width, height, origin, forward, fov=110.0, aperture=0.1, focalLength=1.0, type=0):

@@ -1,6 +1,6 @@
 """Cost of an in-place BLAS rebuild (rt_rebuild_scene) against the round trip it removes, on one GPU.
 
-    python tools/rebuild_bench.py [--reps 10] [--frames 20] [--builders sah,lbvh,sbvh] [--host-reps 1]
+    python tools/rebuild_bench.py [--reps 10] [--frames 20] [--builders sah,lbvh,sbvh] [--host-reps 1] [--accel bvh2|bvh4]
 
 For sponza-class (every vertex scrambled across the triangles) and config 5 (every vertex jittered), three ways to bring a bound scene
 up to date are timed in one process, alternating within each repetition (min / median / max of --reps after a warm-up):
@@ -19,7 +19,16 @@ BLAS are built with), against the two ways to the same trees that exist without 
      first repetition checks that its eleven device arrays equal the rebuild's);
   b  the same triangles built from scratch on the host by BuildBLAS(alpha) at 16 threads, BuildTLAS, rt_upload_scene (--host-reps times).
 For config 5 also what the feature is for, the trace rate of the jittered scene in three states: refit alone (the SBVH leaves have
-lost their clipped boxes), rebuilt with "sah" (no spatial splits), rebuilt with "sbvh_gpu" at alpha 0."""
+lost their clipped boxes), rebuilt with "sah" (no spatial splits), rebuilt with "sbvh_gpu" at alpha 0.
+
+--accel bvh4: a BVH4 context bound with its BVH2 (Device.upload(sa, from_bvh2=True)), builders "sah" and "lbvh" of --builders, on the
+same two scenes and deformations, alternating within each repetition:
+  A  Device.rebuild_scene(prims, builder) in place: the BLAS builds, the BVH2 -> BVH4 collapse, quad records and TLAS on the device;
+  H  the only way there was: Scene.SetPrimitives + Scene.Rebuild (the builder's host restatement, rth_rebuild), Scene.BuildBVH4
+     (BVH4::Convert / Collapse, sequential), BuildTLAS and rt_upload_scene of everything into a second context, each part timed (the
+     first repetition checks that H's thirteen device arrays equal A's);
+and the collapse alone on the rebuilt BVH2 of the last repetition: rt_build_bvh4 (wall with both transfers, and its device_ms)
+against Scene.BuildBVH4.  One JSON line per scene and builder."""
 import argparse
 import json
 import os
@@ -213,14 +222,87 @@ def sbvh_cases(a):
         s.close()
 
 
+def bvh4_cases(a, which):
+    """--accel bvh4: the in-place rebuild of a BVH4 copy against rebuild + collapse on the host + upload; the collapse alone."""
+    from magr_ray_tracer_amd.scene import build_bvh4_gpu
+    b4 = dict(accel=W.ACCEL_BVH4)
+    arrays = [k for k in list(W.SCENE_ARRAYS) + list(W.SCENE_ARRAYS_BVH4) if k != "bvh2Kept"]
+    cases = {"sponza_class": (lambda: scenes.sponza_class(1.0), scrambled), "config5": (lambda: scenes.config5_scene(0.0), jittered)}
+    for name, (make, move) in cases.items():
+        s, view = make()
+        sa = s.arrays()
+        d2 = Device(320, 240, **b4)
+        for builder in [b for b in which if b in ("sah", "lbvh")]:
+            dA = Device(RW, RH, **b4)
+            dA.upload(sa, from_bvh2=True)
+            for k in range(2):                        # warm-up: both sets of arrays, the builders' workspace, the collapse's scratch
+                dA.rebuild_scene(move(sa.prims, 100 + k), builder=builder)
+            A, Ag, H = [], [], {k: [] for k in ("wall", "rebuild", "collapse", "tlas_and_views", "upload")}
+            split = {k: [] for k in ("stage_ms", "build_ms", "derive_ms", "tlas_ms", "commit_ms")}
+            for r in range(a.reps):
+                p = move(sa.prims, r + 1)
+                t0 = time.perf_counter()
+                st = dA.rebuild_scene(p, builder=builder)
+                A.append((time.perf_counter() - t0) * 1e3)
+                Ag.append(st["gpu_ms"])
+                for k in split:
+                    split[k].append(st[k])
+                t0 = time.perf_counter()
+                s.SetPrimitives(0, p)
+                s.Rebuild(builder)
+                t1 = time.perf_counter()
+                s.BuildBVH4()
+                t2 = time.perf_counter()
+                new = s.arrays(bvh4=False)            # BuildTLAS and the copies out of the host library
+                new.bvh4 = K_view(s)
+                t3 = time.perf_counter()
+                d2.upload(new)
+                t4 = time.perf_counter()
+                for k, v in zip(H, (t4 - t0, t1 - t0, t2 - t1, t3 - t2, t4 - t3)):
+                    H[k].append(v * 1e3)
+                if r == 0:
+                    for k in arrays:
+                        assert np.array_equal(dA.scene_array(k), d2.scene_array(k)), f"{name} / {builder}: H's {k} differs from A's"
+            roots = new.blas["bvhIdx"].astype(np.uint32)
+            Cw, Cd, Ch = [], [], []
+            for r in range(a.reps):
+                t0 = time.perf_counter()
+                n4, cs = build_bvh4_gpu(new.bvh2, roots, len(new.primIdx), device=0)
+                Cw.append((time.perf_counter() - t0) * 1e3)
+                Cd.append(cs["device_ms"])
+                t0 = time.perf_counter()
+                s.BuildBVH4()
+                Ch.append((time.perf_counter() - t0) * 1e3)
+            assert np.array_equal(n4.view(np.uint8), K_view(s).view(np.uint8)), f"{name} / {builder}: rt_build_bvh4 differs from BuildBVH4"
+            out = {"scene": name, "accel": "bvh4", "builder": builder, "prims": int(len(sa.prims)), "nodes": st["nodes"], "max_depth": st["max_depth"],
+                   "live_nodes": cs["live_nodes"], "bvh4_levels": cs["levels"], "stack_need": cs["stack_need"],
+                   "A_wall_ms": mmm(A), "A_gpu_ms": mmm(Ag), "A_split_ms": {k: round(statistics.median(v), 3) for k, v in split.items()},
+                   "H_wall_ms": mmm(H["wall"]), "H_split_ms": {k: round(statistics.median(v), 3) for k, v in H.items() if k != "wall"},
+                   "A_over_H": round(statistics.median(A) / statistics.median(H["wall"]), 4),
+                   "collapse_gpu_wall_ms": mmm(Cw), "collapse_gpu_device_ms": mmm(Cd), "collapse_host_ms": mmm(Ch)}
+            print(json.dumps(out), flush=True)
+            dA.close()
+        d2.close()
+        s.close()
+
+
+def K_view(s):
+    """The Scene's BVH4 array as a copy."""
+    from magr_ray_tracer_amd.scene import _view
+    return _view(s._lib.rth_bvh4_nodes, s._h, W.BVHNode4)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--frames", type=int, default=20)
     ap.add_argument("--builders", default="sah,lbvh,sbvh")
     ap.add_argument("--host-reps", type=int, default=1)
+    ap.add_argument("--accel", default="bvh2", choices=["bvh2", "bvh4"])
     a = ap.parse_args()
     which = a.builders.split(",")
+    if a.accel == "bvh4":
+        return bvh4_cases(a, which)
     cases = {"sponza_class": (lambda: scenes.sponza_class(1.0), scrambled), "config5": (lambda: scenes.config5_scene(0.0), jittered)}
     if not [b for b in which if b in ("sah", "lbvh")]:
         cases = {}
