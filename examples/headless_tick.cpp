@@ -3,7 +3,7 @@
 // the host code is the reference's call sequence (src/renderer.cpp:6-63, template main loop), the device work goes through
 // librt355.so.  There is no CPU path: without a HIP device Init() throws.
 //
-//   headless_tick [--obj model.obj] [--tex image.png] [--size W H] [--spp N] [--bvh4] [--kajiya] [--decorrelate] [--lanes N] [--builtins ieee|reference] [--out frame.png]
+//   headless_tick [--obj model.obj] [--tex image.png] [--size W H] [--spp N] [--bvh4] [--kajiya] [--decorrelate] [--lanes N] [--builtins ieee|reference] [--extend-variant N] [--out frame.png]
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -47,7 +47,7 @@ int main(int argc, char** argv)
     int W = 1280, H = 720, spp = 64;
     std::string obj, tex, out = "frame.png";
     bool bvh4 = false, kajiya = false, decorrelate = false;
-    int lanes = 1, builtins = RT_BUILTINS_DEFAULT;
+    int lanes = 1, builtins = RT_BUILTINS_DEFAULT, extendVariant = 0;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         if (a == "--obj" && i + 1 < argc) obj = argv[++i];
@@ -59,6 +59,7 @@ int main(int argc, char** argv)
         else if (a == "--kajiya") kajiya = true;
         else if (a == "--decorrelate") decorrelate = true;
         else if (a == "--lanes" && i + 1 < argc) lanes = std::max(1, atoi(argv[++i]));
+        else if (a == "--extend-variant" && i + 1 < argc) extendVariant = atoi(argv[++i]);
         else if (a == "--builtins" && i + 1 < argc) {
             const std::string m = argv[++i];
             if (m == "ieee") builtins = RT_BUILTINS_IEEE;
@@ -73,6 +74,7 @@ int main(int argc, char** argv)
         // overlap on the GPU.  The library says so on stderr when the process's hardware queues serialise them.
         Renderer r(W, H);
         r.lanes = lanes;
+        r.extend_variant = extendVariant;   // RtConfig.extend_variant (0: best available; 6: multi-BLAS BVH4 scenes through k_trace_persist4_tlas)
         r.builtins = builtins;   // IEEE (default): reproducible on a CPU; REFERENCE: the reference's image from the reference's seeds
         Scene& s = r.scene;
         // materials the way the reference's Scene constructor sets them up (scene.cpp:14-43)

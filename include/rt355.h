@@ -51,7 +51,10 @@ typedef struct RtConfig {
     int32_t extend_variant;     /* traversal kernels: 0 = best available (derived node/triangle layout + persistent
                                  * wavefronts when the TLAS has one BLAS), 1 = traverse the reference arrays as uploaded,
                                  * one ray per lane, 2 = derived layout, one ray per lane, 4 = as 0 but multi-BLAS scenes keep the
-                                 * one-ray-per-lane nested TLAS loops instead of k_trace_persist_tlas (A/B runs)      */
+                                 * one-ray-per-lane nested TLAS loops instead of k_trace_persist_tlas (A/B runs),
+                                 * 6 = as 0, and a BVH4 context whose scene has several BLAS (layout 1, a TLAS of at most 8
+                                 * levels, fewer than 2^29 quad records) traces through k_trace_persist4_tlas instead of the
+                                 * one-ray-per-lane nested loops (opt-in until it has been measured as the default)   */
     int32_t profile;            /* HIP-event brackets on the context's stream: 0 none, 1 extend launches only
                                  * (what the roofline needs; ~1 % overhead), 2 every stage launch (~3.5 %)        */
     int32_t shade_blocks_per_cu;/* k_shade workgroups per CU: 0 = what the CUs hold (2, best for one context with the GPU to itself);
@@ -100,8 +103,10 @@ typedef struct RtKernelInfo {
     int32_t layout;               /* 0 = the reference arrays as uploaded, 1 = derived pair / quad / triangle records */
     int32_t persist, persist4;    /* persistent-wavefront traversal over the BVH2 (1: one BLAS, 2: through a multi-BLAS
                                    * TLAS, k_trace_persist_tlas, 3: the same with the deep end of the traversal stacks
-                                   * spilled to global memory) / over the BVH4 (one BLAS)                             */
-    int32_t stack_entries;        /* LDS traversal stack entries per lane                                             */
+                                   * spilled to global memory) / over the BVH4 (1: one BLAS, k_trace_persist4; with
+                                   * extend_variant 6 also 2: through a multi-BLAS TLAS, k_trace_persist4_tlas, 3: the
+                                   * same with the deep end of the stacks in global memory).  At most one is non-zero  */
+    int32_t stack_entries;        /* LDS traversal stack entries per lane (a spilling kernel: the part kept in LDS)   */
     int32_t persist_grid, persist_grid_connect, shade_grid;   /* workgroups of the persistent launches                */
     int32_t n_blas;
 } RtKernelInfo;

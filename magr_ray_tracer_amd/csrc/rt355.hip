@@ -106,9 +106,13 @@ enum Traversal {
     TRAV_TLAS,          // ... through a multi-BLAS TLAS (k_trace_persist_tlas)
     TRAV_TLAS_SPILL,    // ... with the deep end of the traversal stacks in global memory (trees deeper than the LDS share of 7 workgroups per CU)
     TRAV_BVH4,          // ... over the BVH4 of a single BLAS (k_trace_persist4)
+    TRAV_BVH4_TLAS,     // ... through a multi-BLAS TLAS over BVH4 instances (k_trace_persist4_tlas; extend_variant 6 only)
+    TRAV_BVH4_TLAS_SPILL,   // ... with the deep end of the traversal stacks in global memory
 };
 static bool persistent(const RtCtx* c) { return c->trav != TRAV_NESTED; }
-static bool tlas_trav(const RtCtx* c) { return c->trav == TRAV_TLAS || c->trav == TRAV_TLAS_SPILL; }
+static bool spill_trav(const RtCtx* c) { return c->trav == TRAV_TLAS_SPILL || c->trav == TRAV_BVH4_TLAS_SPILL; }
+static bool bvh4_tlas_trav(const RtCtx* c) { return c->trav == TRAV_BVH4_TLAS || c->trav == TRAV_BVH4_TLAS_SPILL; }
+static bool tlas_trav(const RtCtx* c) { return c->trav == TRAV_TLAS || c->trav == TRAV_TLAS_SPILL || bvh4_tlas_trav(c); }   // one tagged column per lane, world-ray backup behind it
 
 extern "C" const char* rt_last_error(void) { return g_err.c_str(); }
 extern "C" int rt_device_count(void) { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess) return 0; return n; }
@@ -123,7 +127,9 @@ extern "C" int rt_kernel_info(RtCtx* ctx, RtKernelInfo* out)
     if (!ctx || !out) return fail(RT_E_INVALID, "rt_kernel_info: null argument");
     if (!ctx->sceneLoaded) return fail(RT_E_INVALID, "rt_kernel_info: no scene uploaded");
     if (const int rc = sync_scene_config(ctx)) return rc;
-    *out = RtKernelInfo{ ctx->layout, ctx->trav == TRAV_BVH4 ? 0 : ctx->trav, ctx->trav == TRAV_BVH4 ? 1 : 0, ctx->trav == TRAV_TLAS_SPILL ? ctx->spillCap : ctx->stackEntries, ctx->persistGrid, ctx->persistGridConnect,
+    const int persist = ctx->trav <= TRAV_TLAS_SPILL ? ctx->trav : 0;
+    const int persist4 = ctx->trav == TRAV_BVH4 ? 1 : (ctx->trav == TRAV_BVH4_TLAS ? 2 : (ctx->trav == TRAV_BVH4_TLAS_SPILL ? 3 : 0));
+    *out = RtKernelInfo{ ctx->layout, persist, persist4, spill_trav(ctx) ? ctx->spillCap : ctx->stackEntries, ctx->persistGrid, ctx->persistGridConnect,
                          ctx->shadeGrid, ctx->sc.nBlas };
     return RT_OK;
 }
@@ -160,8 +166,9 @@ static size_t stack_bytes(const RtCtx* c) { return (size_t)c->stackEntries * kBl
 // k_trace_persist_tlas keeps its pending TLAS siblings (<= one per level) on the same column; with TRAV_TLAS_SPILL only the first spillCap
 // entries of a column live in LDS.  The world-ray backup sits behind them.
 static int tlas_stack_entries(const RtCtx* c) { return c->stackEntries + c->tlasDepth + 1; }
-static int tlas_lds_entries(const RtCtx* c) { return c->trav == TRAV_TLAS_SPILL ? c->spillCap : tlas_stack_entries(c); }
-static size_t tlas_stack_bytes(const RtCtx* c) { return (size_t)(tlas_lds_entries(c) + kBackupWords) * kBlock * sizeof(uint32_t); }
+static int tlas_lds_entries(const RtCtx* c) { return spill_trav(c) ? c->spillCap : tlas_stack_entries(c); }
+static size_t tlas_column_bytes(int entries) { return (size_t)(entries + kBackupWords) * kBlock * sizeof(uint32_t); }
+static size_t tlas_stack_bytes(const RtCtx* c) { return tlas_column_bytes(tlas_lds_entries(c)); }
 static inline dim3 grid_for(int n) { return dim3((unsigned)std::max(1, (n + kBlock - 1) / kBlock)); }
 
 // The traversal launch of a stage: the one place that maps (stage, bounce, steps wanted) to a kernel instantiation, its grid, its dynamic
@@ -220,6 +227,22 @@ static TraceLaunch trace_launch(const RtCtx* c, int stage, int bounce, bool step
         if (steps) L.persist = spill ? k_trace_persist_tlas<false, true, true> : k_trace_persist_tlas<false, true>;
         else if (coh) L.persist = spill ? k_trace_persist_tlas<false, false, true, true> : k_trace_persist_tlas<false, false, false, true>;
         else L.persist = spill ? k_trace_persist_tlas<false, false, true> : k_trace_persist_tlas<false>;
+        break;
+    }
+    case TRAV_BVH4_TLAS:
+    case TRAV_BVH4_TLAS_SPILL: {
+        const bool spill = c->trav == TRAV_BVH4_TLAS_SPILL;
+        L.lds = tlas_stack_bytes(c);
+        if (connect) {
+            L.tune = c->tuneConnect;
+            L.persist = spill ? k_trace_persist4_tlas<true, false, true> : k_trace_persist4_tlas<true>;
+            L.grid = dim3(c->persistGridConnect);
+            break;
+        }
+        L.tune = c->tune4;
+        if (bounce > 0 || spill) L.grid = dim3(c->persistGrid);   // (as TRAV_TLAS*: every SPILL launch on the persistent grid)
+        if (steps) L.persist = spill ? k_trace_persist4_tlas<false, true, true> : k_trace_persist4_tlas<false, true>;
+        else L.persist = spill ? k_trace_persist4_tlas<false, false, true> : k_trace_persist4_tlas<false>;
         break;
     }
     }
@@ -408,6 +431,11 @@ static int configure_traversal(RtCtx* ctx)
         if (ctx->singleBlas) ctx->trav = ctx->cfg.accel == RT_ACCEL_BVH2 ? TRAV_BVH2 : (ctx->cfg.accel == RT_ACCEL_BVH4 ? TRAV_BVH4 : TRAV_NESTED);
         else if (ctx->cfg.accel == RT_ACCEL_BVH2 && ctx->cfg.extend_variant != 4 && ctx->tlasDepth <= 8 && ctx->nInterior < (1 << 29)) ctx->trav = TRAV_TLAS;
     }
+    // extend_variant 6 (opt-in): a multi-BLAS BVH4 scene through k_trace_persist4_tlas, under the TLAS kernel's conditions - quad ids ride on
+    // the tagged column, so the copy must hold fewer than 2^29 quad records; everything else under variant 6 is variant 0
+    const bool bvh4Tlas = ctx->layout == 1 && ctx->cfg.extend_variant == 6 && ctx->cfg.accel == RT_ACCEL_BVH4 && !ctx->singleBlas && ctx->tlasDepth <= 8 &&
+                          ctx->scene && ctx->scene->nQuads < (1 << 29);
+    if (bvh4Tlas) ctx->trav = TRAV_BVH4_TLAS;
     // deep trees (an SBVH at alpha = 0: config 5's second BLAS has 63 levels): a full LDS column per lane would leave two workgroups per
     // CU, so the column is capped and its deep end spills to global memory (rt355_kernels.h, stk_push / stk_pop)
     ctx->spillCap = kSpillCap;
@@ -419,6 +447,18 @@ static int configure_traversal(RtCtx* ctx)
         !(getenv("RT355_NO_SPILL") && atoi(getenv("RT355_NO_SPILL"))))
         ctx->trav = TRAV_TLAS_SPILL;
     if (ctx->trav == TRAV_TLAS && tlas_stack_entries(ctx) > RT_BVH4_STACK + 9) ctx->trav = TRAV_NESTED;
+    if (ctx->trav == TRAV_BVH4_TLAS) {
+        // the BVH2 rule with the BVH2 numbers (kFitSeven was measured on pair records, not on quad records).  A push-all BVH4 needs many
+        // more entries than a BVH2 of its depth: a column that, with its backup words, exceeds the LDS a workgroup may ask for takes the
+        // spill instantiation too, and the nested loops where RT355_NO_SPILL forbids that - no launch the runtime would reject
+        hipDeviceProp_t prop;
+        HIPCHK(hipGetDeviceProperties(&prop, ctx->cfg.device));
+        const bool noSpill = getenv("RT355_NO_SPILL") && atoi(getenv("RT355_NO_SPILL"));
+        const bool fits = tlas_column_bytes(tlas_stack_entries(ctx)) <= prop.sharedMemPerBlock;
+        const bool canSpill = !noSpill && tlas_stack_entries(ctx) > ctx->spillCap && tlas_column_bytes(ctx->spillCap) <= prop.sharedMemPerBlock;
+        if ((tlas_stack_entries(ctx) > kFitSeven || forceSpill || !fits) && canSpill) ctx->trav = TRAV_BVH4_TLAS_SPILL;
+        else if (!fits) ctx->trav = TRAV_NESTED;
+    }
     // bounce 0 (RT355_COHERENT=2: every bounce of k_trace_persist_tlas, lab; 0: off for A/B runs): wave-uniform node records come through
     // the scalar cache (traverse_bvh2_packed_coherent, k_trace_persist_tlas<COH>)
     ctx->coherent = getenv("RT355_COHERENT") ? atoi(getenv("RT355_COHERENT")) : 1;
@@ -450,8 +490,9 @@ static int configure_traversal(RtCtx* ctx)
         // 522 / 446 / 198 us against 654 / 562 / 194 through the event loop and 730 / 643 / 237 through the nested loops at two
         // workgroups per CU), connect - unoccluded shadow rays cross the whole scene - the event loop (646 against 690 / 1,418 us).
         // RT355_TLAS_FLAT="e,c" overrides (A/B runs).  profiles/r03_config5_per_bounce.txt
-        ctx->tune.flat = 1; ctx->tuneConnect.flat = 0;
-        if (const char* t = getenv("RT355_TLAS_FLAT")) { int a = 0, b = 0; if (sscanf(t, "%d,%d", &a, &b) == 2) { ctx->tune.flat = a; ctx->tuneConnect.flat = b; } }
+        // (k_trace_persist4_tlas takes its extend tune from tune4; the flat default was measured on BVH2 instances only)
+        ctx->tune.flat = ctx->tune4.flat = 1; ctx->tuneConnect.flat = 0;
+        if (const char* t = getenv("RT355_TLAS_FLAT")) { int a = 0, b = 0; if (sscanf(t, "%d,%d", &a, &b) == 2) { ctx->tune.flat = ctx->tune4.flat = a; ctx->tuneConnect.flat = b; } }
     }
     // sparse queues (the one-ray-per-lane branches) stay on as few XCDs as hold them at 1,024 rays each, so that their rays share an L2
     // (EXPERIMENTS.md (54): 16,384 before the thinning below made spreading the better default); contexts start on different XCDs
@@ -476,19 +517,28 @@ static int configure_traversal(RtCtx* ctx)
         // the closest-hit instantiations use ~90 SGPRs, the any-hit ones ~100: the hardware admits 7 resp. 6 workgroups per CU where
         // the occupancy query may say more (see rt_create); a surplus workgroup would strand its static first chunk until another exits
         const int mp = prop.multiProcessorCount;
-        ctx->persistGrid = std::min(ctx->gridMax, std::max(1, std::min(perCU, kAdmit96Sgpr)) * mp);
-        ctx->persistGridConnect = std::min(ctx->gridMax, std::max(1, std::min(perCU, kAdmitAnySgpr)) * mp);
-        if (ctx->cfg.persist_blocks_per_cu > 0) {
-            const int d = std::min(ctx->cfg.persist_blocks_per_cu, std::max(1, perCU));
-            ctx->persistGrid = std::min(ctx->persistGrid, std::min(ctx->gridMax, d * mp));
-            ctx->persistGridConnect = std::min(ctx->persistGridConnect, std::min(ctx->gridMax, d * mp));
+        // (k_trace_persist4_tlas: its any-hit instantiations need more registers than its closest-hit ones and admit a workgroup fewer, so
+        // connect's grid goes by connect's own kernel)
+        int perCUc = perCU;
+        if (bvh4_tlas_trav(ctx)) {
+            const TraceLaunch C = trace_launch(ctx, ST_CONNECT, 0, false, ctx->nPix);
+            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCUc, C.persist, kBlock, C.lds));
         }
-        if (tuneBlocks > 0) ctx->persistGrid = ctx->persistGridConnect = std::min(ctx->gridMax, std::min(tuneBlocks, std::max(1, perCU)) * mp);
-        if (const char* t = getenv("RT355_CONNECT_BLOCKS")) { const int d = atoi(t); if (d > 0) ctx->persistGridConnect = std::min(ctx->gridMax, std::min(d, std::max(1, perCU)) * mp); }   // (lab)
+        ctx->persistGrid = std::min(ctx->gridMax, std::max(1, std::min(perCU, kAdmit96Sgpr)) * mp);
+        ctx->persistGridConnect = std::min(ctx->gridMax, std::max(1, std::min(perCUc, kAdmitAnySgpr)) * mp);
+        if (ctx->cfg.persist_blocks_per_cu > 0) {
+            ctx->persistGrid = std::min(ctx->persistGrid, std::min(ctx->gridMax, std::min(ctx->cfg.persist_blocks_per_cu, std::max(1, perCU)) * mp));
+            ctx->persistGridConnect = std::min(ctx->persistGridConnect, std::min(ctx->gridMax, std::min(ctx->cfg.persist_blocks_per_cu, std::max(1, perCUc)) * mp));
+        }
+        if (tuneBlocks > 0) {
+            ctx->persistGrid = std::min(ctx->gridMax, std::min(tuneBlocks, std::max(1, perCU)) * mp);
+            ctx->persistGridConnect = std::min(ctx->gridMax, std::min(tuneBlocks, std::max(1, perCUc)) * mp);
+        }
+        if (const char* t = getenv("RT355_CONNECT_BLOCKS")) { const int d = atoi(t); if (d > 0) ctx->persistGridConnect = std::min(ctx->gridMax, std::min(d, std::max(1, perCUc)) * mp); }   // (lab)
     }
     ctx->q.spill = nullptr; ctx->q.spillStride = 0; ctx->q.stackCap = 0;
     ctx->q.tlasLdsEntries = tlas_trav(ctx) ? (uint32_t)tlas_lds_entries(ctx) : 0u;
-    if (ctx->trav == TRAV_TLAS_SPILL) {   // every SPILL launch runs on a persistent grid (bounce 0 too), so the global columns are bounded by the grids
+    if (spill_trav(ctx)) {   // every SPILL launch runs on a persistent grid (bounce 0 too), so the global columns are bounded by the grids
         const size_t stride = (size_t)std::max(ctx->persistGrid, ctx->persistGridConnect) * kBlock;
         const size_t words = stride * (size_t)(tlas_stack_entries(ctx) - ctx->spillCap);
         if (words > ctx->spillWords) {

@@ -1471,6 +1471,176 @@ __global__ __launch_bounds__(kBlock) void k_trace_persist4(DevScene sc, DevQueue
     flush_counters(OCC ? q.ctrConnect : q.ctrExtend, rays, wc, stk);
 }
 
+// ------------------------------------------------------------------ k_trace_persist4_tlas: persistent wavefronts through a multi-BLAS TLAS over BVH4 instances (layout 1)
+// The state machine of k_trace_persist_tlas with the instances of k_trace_persist4.  One stack column per lane (LDS; SPILL: its deep end
+// in q.spill) holds
+//     bits 31..29 = 000               BVH4 interior    id in the dense quad table
+//     bits 31..29 = 010  (kTagTlas)   TLAS interior    id in tlasPairsP
+//     bits 31..29 = 011  (kTagInst)   TLAS leaf        instance id
+// BVH4 leaf children never reach the column: the ones a quad visit hit wait in e0..e3 under leafMask, as in k_trace_persist4, so an
+// instance is exhausted when leafMask == 0 && sp == spBase.  Instance entry and exit are inst_enter / inst_exit (ray transformed once,
+// world ray + TLAS-level tLight in the 10 backup words, cur = the instance record's quad root, tLight = r.t on entry); TLAS interior
+// nodes are tlas_node's rule (near child first, for connect too; wc.tlas, no `steps`); quad nodes are k_trace_persist4's (seven loads in
+// one round trip, four distances against the tLight of entry, hit interior children pushed in slot order, steps++ and wc.node++ per
+// visit); a leaf event tests one triangle of the lowest pending leaf child, and connect stops at the first r.t < tLight.  Hits, `steps`
+// and every counter are those of traverse_tlas over traverse_bvh4_packed.
+// Event loop: instance entries are issued first and alone; TLAS-node and quad-node events share ONE issue (a lane on a TLAS node runs
+// tlas_node, a lane on a quad its visit, the TLAS side skipped wave-uniformly when no lane is on one) and leaf events the other, chosen
+// by the leafK rule of k_trace_persist4.  A TLAS visit is one event per ray and level: an issue of its own would hold every quad lane of
+// the wave back for a whole iteration whenever a fresh ray starts.
+// One quad-node event: pushes the interior children that were hit, leaves the record's entries in e0..e3 and returns the mask of the
+// leaf children that were hit.
+template <bool SPILL>
+RT_FORCEINLINE uint32_t quad_node(const DevScene& sc, const DevQueues& q, uint32_t* stk, uint32_t gl, const TRay& r, uint32_t cur, uint32_t& sp, float tLight,
+                                  uint32_t& e0, uint32_t& e1, uint32_t& e2, uint32_t& e3)
+{
+    const float4* p = sc.quads + (size_t)cur * 8;
+    const float4 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3], q4 = p[4], q5 = p[5], q6 = p[6];
+    asm volatile("" : : "v"(q0.x), "v"(q1.x), "v"(q2.x), "v"(q3.x), "v"(q4.x), "v"(q5.x), "v"(q6.x));   // one round trip (see test_tri_packed)
+    e0 = __float_as_uint(q6.x); e1 = __float_as_uint(q6.y); e2 = __float_as_uint(q6.z); e3 = __float_as_uint(q6.w);
+    const float d0 = e0 != kNoChild ? slab(r, mk4(q0.x, q0.y, q0.z, 0.0f), mk4(q0.w, q1.x, q1.y, 0.0f)) : kFar;
+    const float d1 = e1 != kNoChild ? slab(r, mk4(q1.z, q1.w, q2.x, 0.0f), mk4(q2.y, q2.z, q2.w, 0.0f)) : kFar;
+    const float d2 = e2 != kNoChild ? slab(r, mk4(q3.x, q3.y, q3.z, 0.0f), mk4(q3.w, q4.x, q4.y, 0.0f)) : kFar;
+    const float d3 = e3 != kNoChild ? slab(r, mk4(q4.z, q4.w, q5.x, 0.0f), mk4(q5.y, q5.z, q5.w, 0.0f)) : kFar;
+    uint32_t m = 0;
+    if (e0 != kNoChild && d0 < tLight) { if (e0 & kLeafBit) m |= 1u; else stk_push<SPILL>(stk, q, gl, sp, e0); }
+    if (e1 != kNoChild && d1 < tLight) { if (e1 & kLeafBit) m |= 2u; else stk_push<SPILL>(stk, q, gl, sp, e1); }
+    if (e2 != kNoChild && d2 < tLight) { if (e2 & kLeafBit) m |= 4u; else stk_push<SPILL>(stk, q, gl, sp, e2); }
+    if (e3 != kNoChild && d3 < tLight) { if (e3 & kLeafBit) m |= 8u; else stk_push<SPILL>(stk, q, gl, sp, e3); }
+    return m;
+}
+template <bool OCC, bool STEPS = false, bool SPILL = false>
+__global__ __launch_bounds__(kBlock) void k_trace_persist4_tlas(DevScene sc, DevQueues q, int b0, int b1, int renderBVH, PersistTune tune)
+{
+    const int kInner = tune.inner, kLeafK = tune.leafK;
+    extern __shared__ uint32_t stk[];
+    const int lane = threadIdx.x & 63;
+    const QueueWindow w = queue_window<OCC>(q, b0, b1);
+    const int nWaves = gridDim.x * (kBlock / 64), waveId = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    const uint32_t gl = blockIdx.x * kBlock + threadIdx.x;    // this lane's column of the spill stack
+
+    if (w.n <= nWaves * 64 || tune.flat) {
+        // one ray per lane (see k_trace_persist_tlas): the same states and the same single column, a whole leaf child per step
+        WorkCtr wc = { 0, 0, 0, 0 };
+        uint32_t rays = 0;
+        const bool tiled = primary_tiles<OCC>(q, b0, w.n);
+        const SparseMap m = tiled ? SparseMap{ waveId, nWaves, 64 } : sparse_map(w.n, tune, waveId);
+        for (int item = m.first < 0 ? w.n : m.first; (long long)item * m.per < (long long)w.n; item += m.stride) {
+            const int idx = tiled ? tile_slot(q, item, lane) : item * m.per + lane;
+            if (lane >= m.per || idx >= w.n) continue;
+            TRay r;
+            queue_ray<OCC>(r, q, b0, w.first, idx);
+            rays++;
+            uint32_t cur = sc.tlasRootP, sp = 0, spBase = 0, e0 = 0, e1 = 0, e2 = 0, e3 = 0;
+            bool inInst = false, occluded = false;
+            float tLight = r.t;
+            int steps = 0;
+            for (;;) {
+                bool needPop = false;
+                if ((cur & kTagMask) == kTagInst) {
+                    wc.inst++;
+                    inst_enter(sc, q, stk, r, cur, sp, spBase, inInst, tLight);
+                    continue;
+                } else if ((cur & kTagTlas) != 0u) {
+                    wc.tlas++;
+                    needPop = tlas_node<OCC, SPILL, false, true>(sc, q, stk, gl, r, cur, sp, tLight, steps);
+                } else {
+                    steps++; wc.node++;
+                    uint32_t lm = quad_node<SPILL>(sc, q, stk, gl, r, cur, sp, tLight, e0, e1, e2, e3);
+                    while (lm != 0u) {   // the leaf children that were hit, in slot order
+                        const int k = __ffs((int)lm) - 1;
+                        const uint32_t ek = k == 0 ? e0 : (k == 1 ? e1 : (k == 2 ? e2 : e3));
+                        const uint32_t first = ek & 0x00ffffffu, count = (ek >> 24) & 0x7fu;
+                        for (uint32_t i = 0; i < count; i++) {
+                            wc.prim++;
+                            test_tri_packed(sc, first + i, r);
+                            if (OCC && r.t < tLight) { occluded = true; break; }
+                        }
+                        if (OCC && occluded) break;
+                        lm &= lm - 1u;
+                    }
+                    if (OCC && occluded) break;
+                    needPop = true;
+                }
+                if (needPop) {
+                    if (inInst && sp == spBase) inst_exit(q, stk, r, spBase, inInst, tLight);
+                    if (sp == 0) break;
+                    cur = stk_pop<SPILL>(stk, q, gl, sp);
+                }
+            }
+            store_result<OCC, true>(q, w.first, idx, r, steps, occluded, renderBVH);
+        }
+        flush_counters(OCC ? q.ctrConnect : q.ctrExtend, rays, wc, stk);
+        return;
+    }
+
+    uint32_t wRays = 0, wNode = 0, wPrim = 0, wTlas = 0, wInst = 0, wNodeIss = 0, wLeafIss = 0;    // this wave's work (wave-uniform)
+    TRay r; r.t = 0; r.prim = -1; r.u = r.v = 0; r.ox = r.oy = r.oz = r.dx = r.dy = r.dz = r.rx = r.ry = r.rz = 0;
+    uint32_t cur = 0, sp = 0, spBase = 0, leafMask = 0, e0 = 0, e1 = 0, e2 = 0, e3 = 0;
+    bool inInst = false;
+    int slot = -1, steps = 0;
+    float tLight = 0;
+    ChunkDealer deal(waveId, tune.chunk, w.n);
+    for (;;) {
+        int idx;
+        if (!deal.refill(slot < 0, idx, wRays, w, tune, nWaves, waveId, lane)) break;
+        if (idx >= 0) { queue_ray<OCC>(r, q, b0, w.first, idx); tLight = r.t; cur = sc.tlasRootP; sp = 0; spBase = 0; inInst = false; steps = 0; leafMask = 0; slot = idx; }
+#pragma unroll 1
+        for (int it = 0; it < kInner; it++) {
+            const bool act = slot >= 0, atLeaf = act && leafMask != 0u;
+            const bool atInst = act && !atLeaf && (cur & kTagMask) == kTagInst;
+            const bool atNode = act && !atLeaf && !atInst;
+            const unsigned long long lm = __ballot(atLeaf), im = __ballot(atNode), xm = __ballot(atInst);
+            if ((lm | im | xm) == 0ull) break;
+            if (xm != 0ull) {   // entering an instance is rare (<= nBlas per ray) and short, so it goes first and alone
+                wInst += (uint32_t)__popcll(xm);
+                if (atInst) inst_enter(sc, q, stk, r, cur, sp, spBase, inInst, tLight);
+                continue;
+            }
+            const bool doLeaf = im == 0ull || __popcll(lm) >= kLeafK;
+            bool done = false, occluded = false, needPop = false;
+            if (doLeaf) {
+                wPrim += (uint32_t)__popcll(lm); if (STEPS) wLeafIss++;
+                if (atLeaf) {
+                    const int k = __ffs((int)leafMask) - 1;
+                    uint32_t ek = k == 0 ? e0 : (k == 1 ? e1 : (k == 2 ? e2 : e3));
+                    const uint32_t first = ek & 0x00ffffffu, count = (ek >> 24) & 0x7fu;
+                    test_tri_packed(sc, first, r);
+                    if (OCC && r.t < tLight) { done = true; occluded = true; }
+                    else if (count > 1) {
+                        ek = kLeafBit | ((count - 1) << 24) | (first + 1);
+                        if (k == 0) e0 = ek; else if (k == 1) e1 = ek; else if (k == 2) e2 = ek; else e3 = ek;
+                    } else {
+                        leafMask &= leafMask - 1u;
+                        needPop = leafMask == 0u;
+                    }
+                }
+            } else {
+                if (STEPS) wNodeIss++;
+                const bool atTlas = atNode && (cur & kTagTlas) != 0u;
+                const unsigned long long tm = __ballot(atTlas);
+                wTlas += (uint32_t)__popcll(tm); wNode += (uint32_t)(__popcll(im) - __popcll(tm));
+                if (tm != 0ull) { if (atTlas) needPop = tlas_node<OCC, SPILL, false, STEPS>(sc, q, stk, gl, r, cur, sp, tLight, steps); }
+                if (atNode && !atTlas) {
+                    if (STEPS) steps++;
+                    leafMask = quad_node<SPILL>(sc, q, stk, gl, r, cur, sp, tLight, e0, e1, e2, e3);
+                    needPop = leafMask == 0u;
+                }
+            }
+            if (needPop) {
+                if (inInst && sp == spBase) inst_exit(q, stk, r, spBase, inInst, tLight);
+                if (sp == 0) done = true;
+                else cur = stk_pop<SPILL>(stk, q, gl, sp);
+            }
+            if (done) { store_result<OCC, STEPS>(q, w.first, slot, r, steps, occluded, renderBVH); slot = -1; leafMask = 0; }
+        }
+    }
+    WorkCtr wc = { 0, 0, 0, 0 };
+    uint32_t rays = 0;
+    if (lane == 0) { rays = wRays; wc.tlas = wTlas; wc.inst = wInst; wc.node = wNode; wc.prim = wPrim; if (STEPS) { wc.nodeIss = wNodeIss; wc.leafIss = wLeafIss; wc.evNode = wNode + wTlas; wc.evPrim = wPrim; } }
+    flush_counters(OCC ? q.ctrConnect : q.ctrExtend, rays, wc, stk);
+}
+
 // ------------------------------------------------------------------ shading helpers
 struct SRay { // the reference Ray fields shade() reads and writes
     float4 O, D, N, I, inten;

@@ -51,6 +51,7 @@ void Renderer::Init() // renderer.cpp:6-21 (+ InitBuffers :142-209, InitWavefron
     cfg.shading = imgui.shading; cfg.sampling = imgui.sampling; cfg.accel = imgui.bvh;
     cfg.russian_roulette = imgui.use_russian_roulette; cfg.filter_fireflies = imgui.filter_fireflies;
     cfg.device = device;
+    cfg.extend_variant = extend_variant;
     cfg.builtins = builtins;   // the arithmetic of every lane: IEEE (default; reproducible on a CPU) or the reference's own builtin sequences
     // `lanes` sample streams behind this one Renderer (rt_group_*, include/rt355.h): 1 = the reference's single in-order queue, bit for
     // bit; more keep the GPU full (the lanes' frames overlap) and turn one Tick() into `lanes` frames of the same accumulation

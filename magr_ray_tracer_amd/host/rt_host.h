@@ -265,6 +265,7 @@ public:
     RtCtx*         ctx = nullptr;      // lane 0 (focus pick, counters, stage-level debugging)
     int            lanes = 1;          // set before Init(): sample streams whose frames overlap on the GPU; Tick() = `lanes` frames
     int            builtins = 0;       // set before Init(): RtConfig.builtins of the lanes (RT_BUILTINS_DEFAULT / _IEEE / _REFERENCE, include/rt355.h)
+    int            extend_variant = 0; // set before Init(): RtConfig.extend_variant of the lanes (0 = best available; 6 also takes k_trace_persist4_tlas, include/rt355.h)
     int width, height, device, y0, y1;
 };
 

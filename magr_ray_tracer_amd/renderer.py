@@ -178,6 +178,10 @@ class Device:
 
     def extend_kernel_name(self):
         k = self.kernel_info()
+        if k["persist4"] == 3:
+            return "k_trace_persist4_tlas<false, false, true> (LDS stack of %d entries per lane, deeper entries in global memory)" % k["stack_entries"]
+        if k["persist4"] == 2:
+            return "k_trace_persist4_tlas<false> (bounce 0: its one-ray-per-lane branch)"
         if k["persist4"]:
             return "k_trace_persist4<false>"
         if k["persist"] == 3:
