@@ -86,7 +86,8 @@ typedef struct RtCounters {
      * loop_node_events / (64 * node_issues) is the share of the lanes that had a box pair to test when the node path ran,
      * loop_leaf_events / (64 * leaf_issues) the same for the triangle path.  Counted by the extend instantiation that also keeps the
      * per-ray `steps` (rt_debug_enable_steps(ctx, 1) or renderBVH): the production kernel does not pay for them; launches that ran one
-     * ray per lane count nothing here */
+     * ray per lane count nothing here.  An iteration of the top descent (a node event whose record comes from the LDS top table,
+     * rt_top_levels) is an issue of the node path and its events are node events */
     uint64_t extend_node_issues, extend_leaf_issues, connect_node_issues, connect_leaf_issues;
     uint64_t extend_loop_node_events, extend_loop_leaf_events, connect_loop_node_events, connect_loop_leaf_events;   /* the events those issues carried */
 } RtCounters;
@@ -115,6 +116,9 @@ const char* rt_last_error(void);
 int rt_device_count(void);
 int rt_kernel_info(RtCtx* ctx, RtKernelInfo* out);
 int rt_builtins(RtCtx* ctx);   /* the context's arithmetic, resolved: RT_BUILTINS_IEEE or RT_BUILTINS_REFERENCE */
+/* Levels of the BLAS that the event loops of extend and of connect descend from a table in LDS when a lane takes a new ray (0..6; 0: no
+ * table.  Single-BLAS BVH2 scenes under persistent wavefronts only, else 0; RT355_TOP_LEVELS overrides the defaults) */
+int rt_top_levels(RtCtx* ctx, int32_t* extend, int32_t* connect);
 
 /* new Buffer(...) x11 + new Kernel(...) x6 (renderer.cpp:145-157, :218-223). */
 int rt_create(const RtConfig* cfg, RtCtx** out);

@@ -25,6 +25,9 @@ static constexpr int kAdmitAnySgpr = 6, kAdmit96Sgpr = 7;
 // LDS words per lane of k_trace_persist_tlas: 22 x 1 KB per workgroup is the most with which seven workgroups share a CU's 160 KB; the
 // world ray (O, D, 1/D) and the TLAS level's pruning distance wait in 10 of them while a lane is inside an instance, so a spilling
 // kernel keeps 12 stack entries in LDS
+// levels of the LDS top table of k_trace_persist's event loops, extend and connect, at most: a context takes the deepest table that does
+// not cost its persistent grid a resident workgroup (configure_traversal; EXPERIMENTS.md (59)).  0 = the instantiations without it
+static constexpr int kTopLevelsExtend = 6, kTopLevelsConnect = 6;
 static constexpr int kFitSeven = 22, kBackupWords = 10, kSpillCap = kFitSeven - kBackupWords;
 static thread_local std::string g_err;
 int rt355_set_error(int code, const char* msg) { g_err = msg; return code; }   // for every source file of this library (fail, build_fail)
@@ -134,6 +137,15 @@ extern "C" int rt_kernel_info(RtCtx* ctx, RtKernelInfo* out)
     return RT_OK;
 }
 
+extern "C" int rt_top_levels(RtCtx* ctx, int32_t* extend, int32_t* connect)
+{
+    if (!ctx || !extend || !connect) return fail(RT_E_INVALID, "rt_top_levels: null argument");
+    if (!ctx->sceneLoaded) return fail(RT_E_INVALID, "rt_top_levels: no scene uploaded");
+    if (const int rc = sync_scene_config(ctx)) return rc;
+    *extend = ctx->tune.topLevels; *connect = ctx->tuneConnect.topLevels;
+    return RT_OK;
+}
+
 static void free_bag(std::vector<void*>& bag) { for (void* p : bag) (void)hipFree(p); bag.clear(); }
 
 // A context holds at most one device copy of a scene; the copy knows its holders (rt_update_scene waits for them and reconfigures them).
@@ -163,6 +175,8 @@ int SceneBag::wait_holders() const
 // LDS traversal stack: one column per lane; sized at upload to what this scene's trees can need
 // (never more than the reference kernels' 32 / 64 entries).
 static size_t stack_bytes(const RtCtx* c) { return (size_t)c->stackEntries * kBlock * sizeof(uint32_t); }
+// the top table of k_trace_persist<.., TOP> behind them: 2^levels - 1 pair records of 64 bytes
+static size_t top_bytes(int levels) { return levels > 0 ? (((size_t)1 << levels) - 1) * 4 * sizeof(float4) : 0; }
 // k_trace_persist_tlas keeps its pending TLAS siblings (<= one per level) on the same column; with TRAV_TLAS_SPILL only the first spillCap
 // entries of a column live in LDS.  The world-ray backup sits behind them.
 static int tlas_stack_entries(const RtCtx* c) { return c->stackEntries + c->tlasDepth + 1; }
@@ -183,13 +197,14 @@ struct TraceLaunch {
     size_t lds = 0;
     PersistTune tune{};
 };
-static TraceLaunch trace_launch(const RtCtx* c, int stage, int bounce, bool steps, int rays)
+static TraceLaunch trace_launch(const RtCtx* c, int stage, int bounce, bool steps, int rays, int topLevels = -1 /* >= 0: as if the stage's PersistTune.topLevels were this */)
 {
     TraceLaunch L;
     L.grid = grid_for(rays);
     L.lds = stack_bytes(c);
     const bool connect = stage == ST_CONNECT;
     const bool bvh4 = c->cfg.accel == RT_ACCEL_BVH4, l1 = c->layout == 1;
+    bool top = false;
     switch (c->trav) {
     case TRAV_NESTED:
         if (connect) L.nested = bvh4 ? (l1 ? k_connect<RT_ACCEL_BVH4, 1> : k_connect<RT_ACCEL_BVH4, 0>) : (l1 ? k_connect<RT_ACCEL_BVH2, 1> : k_connect<RT_ACCEL_BVH2, 0>);
@@ -197,12 +212,20 @@ static TraceLaunch trace_launch(const RtCtx* c, int stage, int bounce, bool step
         break;
     case TRAV_BVH2:
         L.tune = connect ? c->tuneConnect : c->tune;
-        if (connect) { L.persist = k_trace_persist<true>; L.grid = dim3(c->persistGridConnect); }
-        else if (bounce > 0 || c->cfg.extend_variant == 3) { L.persist = steps ? k_trace_persist<false, false, true> : k_trace_persist<false>; L.grid = dim3(c->persistGrid); }
+        if (topLevels >= 0) L.tune.topLevels = topLevels;
+        // (topLevels > 0: the TOP instantiations of the launches whose long queues run the event loop; the table lies behind the stack columns)
+        if (connect) { top = L.tune.topLevels > 0; L.persist = top ? k_trace_persist<true, false, false, true> : k_trace_persist<true>; L.grid = dim3(c->persistGridConnect); }
+        else if (bounce > 0 || c->cfg.extend_variant == 3) {
+            top = L.tune.topLevels > 0;
+            if (top) L.persist = steps ? k_trace_persist<false, false, true, true> : k_trace_persist<false, false, false, true>;
+            else L.persist = steps ? k_trace_persist<false, false, true> : k_trace_persist<false>;
+            L.grid = dim3(c->persistGrid);
+        }
         else if (c->cfg.extend_variant == 5) L.nested = k_extend<RT_ACCEL_BVH2, 1>;
         // bounce 0 through the same kernel with one workgroup per 256 rays: its "queue not longer than the grid" branch is the plain
         // one-ray-per-lane loop without the TLAS code of k_extend (60 instead of 86 VGPRs: 8 instead of 5 waves per SIMD)
         else L.persist = c->coherent ? k_trace_persist<false, true> : (steps ? k_trace_persist<false, false, true> : k_trace_persist<false>);
+        if (top) { L.tune.topBase = c->stackEntries * kBlock; L.lds += top_bytes(L.tune.topLevels); }
         break;
     case TRAV_BVH4:
         L.tune = connect ? c->tuneConnect : c->tune4;
@@ -247,6 +270,29 @@ static TraceLaunch trace_launch(const RtCtx* c, int stage, int bounce, bool step
     }
     }
     return L;
+}
+
+// What the occupancy query says of the kernel a stage runs on its persistent grid (workgroups per CU by VGPRs, LDS and wave slots);
+// topLevels >= 0: with a top table of that many levels instead of the stage's own
+static int persist_query(const RtCtx* c, int stage, int topLevels, int* perCU)
+{
+    const TraceLaunch L = trace_launch(c, stage, stage == ST_CONNECT ? 0 : 1, false, c->nPix, topLevels);
+    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(perCU, L.persist, kBlock, L.lds));
+    return RT_OK;
+}
+// Workgroups per CU of a stage's persistent grid, given that answer.  The closest-hit instantiations use ~90 SGPRs, the any-hit ones ~100:
+// the hardware admits 7 resp. 6 workgroups per CU where the query may say more (see rt_create); a surplus workgroup would strand its static
+// first chunk until another exits.  Contexts that share the GPU take RtConfig.persist_blocks_per_cu at most; RT355_TUNE's fifth field and,
+// for connect, RT355_CONNECT_BLOCKS (lab) override both.
+static int persist_blocks(const RtCtx* c, int stage, int perCU, int tuneBlocks)
+{
+    const bool connect = stage == ST_CONNECT;
+    const int fit = std::max(1, perCU);
+    int g = std::max(1, std::min(perCU, connect ? kAdmitAnySgpr : kAdmit96Sgpr));
+    if (c->cfg.persist_blocks_per_cu > 0) g = std::min(g, std::min(c->cfg.persist_blocks_per_cu, fit));
+    if (tuneBlocks > 0) g = std::min(tuneBlocks, fit);
+    if (connect) if (const char* t = getenv("RT355_CONNECT_BLOCKS")) { const int d = atoi(t); if (d > 0) g = std::min(d, fit); }
+    return g;
 }
 
 // ---- profiling brackets --------------------------------------------------------------
@@ -484,6 +530,21 @@ static int configure_traversal(RtCtx* ctx)
         int a = 0, b = 0, c = 0, l = 0;
         if (sscanf(t, "%d,%d,%d,%d", &a, &b, &c, &l) == 4 && a > 0 && b > 0 && b <= 64 && c > 0 && l > 0 && l <= 64) ctx->tuneConnect = PersistTune{ a, b, c, l, 0 };
     }
+    // RT355_TOP_LEVELS="e[,c]" (0..6; one number: both): levels of the BLAS that the event loops of k_trace_persist descend from a table in
+    // LDS when a lane takes a new ray (rt355_kernels.h, top_descent), extend and connect.  0: the instantiation without the table.
+    // Without the knob: the deepest table up to kTopLevels* that leaves the stage's persistent grid as it is (below)
+    ctx->tune.topLevels = ctx->tuneConnect.topLevels = 0;
+    bool topAuto = false;
+    if (ctx->trav == TRAV_BVH2) {
+        ctx->tune.topLevels = kTopLevelsExtend; ctx->tuneConnect.topLevels = kTopLevelsConnect;
+        topAuto = true;
+        if (const char* t = getenv("RT355_TOP_LEVELS")) {
+            int a = 0, b = 0;
+            const int k = sscanf(t, "%d,%d", &a, &b);
+            if (k == 1) b = a;
+            if (k >= 1 && a >= 0 && a <= kTopMaxLevels && b >= 0 && b <= kTopMaxLevels) { ctx->tune.topLevels = a; ctx->tuneConnect.topLevels = b; topAuto = false; }
+        }
+    }
     if (tlas_trav(ctx)) {
         // Multi-BLAS scenes so far are open scenes whose rays take a dozen events (config 5: 1 TLAS visit, 1.5 instance entries, 7.7 box
         // pairs, 1.9 triangles per ray): extend runs the kernel's one-ray-per-lane branch over every queue (measured per bounce at 4K:
@@ -512,29 +573,30 @@ static int configure_traversal(RtCtx* ctx)
     if (persistent(ctx)) {
         int perCU = 0; hipDeviceProp_t prop;
         HIPCHK(hipGetDeviceProperties(&prop, ctx->cfg.device));
-        const TraceLaunch L = trace_launch(ctx, ST_EXTEND, 1, false, ctx->nPix);   // what extend runs on the persistent grid
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, L.persist, kBlock, L.lds));
-        // the closest-hit instantiations use ~90 SGPRs, the any-hit ones ~100: the hardware admits 7 resp. 6 workgroups per CU where
-        // the occupancy query may say more (see rt_create); a surplus workgroup would strand its static first chunk until another exits
-        const int mp = prop.multiProcessorCount;
+        // (a top table that would not fit behind the stack columns of a very deep tree is left out: no launch the runtime would reject)
+        for (PersistTune* t : { &ctx->tune, &ctx->tuneConnect }) if (stack_bytes(ctx) + top_bytes(t->topLevels) > prop.sharedMemPerBlock) t->topLevels = 0;
+        // The table's LDS can cost a resident workgroup, and on the one scene this was measured on (the bench scene, EXPERIMENTS.md (59):
+        // alone, 22 KB of stack columns x 7 workgroups leave room for three levels) that costs more than the deeper levels give, while
+        // contexts that share the GPU run fewer workgroups per CU and lose none with six.  So without the knob each stage gets the
+        // deepest table with which it keeps the workgroups per CU it has without one.
+        if (topAuto) for (int stage : { ST_EXTEND, ST_CONNECT }) {
+            PersistTune& t = stage == ST_CONNECT ? ctx->tuneConnect : ctx->tune;
+            int q = 0, lv = t.topLevels;
+            if (const int rc = persist_query(ctx, stage, 0, &q)) return rc;
+            const int base = persist_blocks(ctx, stage, q, tuneBlocks);
+            for (; lv > 0; lv--) {
+                if (const int rc = persist_query(ctx, stage, lv, &q)) return rc;
+                if (persist_blocks(ctx, stage, q, tuneBlocks) == base) break;
+            }
+            t.topLevels = lv;
+        }
+        if (const int rc = persist_query(ctx, ST_EXTEND, -1, &perCU)) return rc;   // what extend runs on the persistent grid
         // (k_trace_persist4_tlas: its any-hit instantiations need more registers than its closest-hit ones and admit a workgroup fewer, so
-        // connect's grid goes by connect's own kernel)
+        // connect's grid goes by connect's own kernel; so does k_trace_persist's with a top table for connect: its own LDS size)
         int perCUc = perCU;
-        if (bvh4_tlas_trav(ctx)) {
-            const TraceLaunch C = trace_launch(ctx, ST_CONNECT, 0, false, ctx->nPix);
-            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCUc, C.persist, kBlock, C.lds));
-        }
-        ctx->persistGrid = std::min(ctx->gridMax, std::max(1, std::min(perCU, kAdmit96Sgpr)) * mp);
-        ctx->persistGridConnect = std::min(ctx->gridMax, std::max(1, std::min(perCUc, kAdmitAnySgpr)) * mp);
-        if (ctx->cfg.persist_blocks_per_cu > 0) {
-            ctx->persistGrid = std::min(ctx->persistGrid, std::min(ctx->gridMax, std::min(ctx->cfg.persist_blocks_per_cu, std::max(1, perCU)) * mp));
-            ctx->persistGridConnect = std::min(ctx->persistGridConnect, std::min(ctx->gridMax, std::min(ctx->cfg.persist_blocks_per_cu, std::max(1, perCUc)) * mp));
-        }
-        if (tuneBlocks > 0) {
-            ctx->persistGrid = std::min(ctx->gridMax, std::min(tuneBlocks, std::max(1, perCU)) * mp);
-            ctx->persistGridConnect = std::min(ctx->gridMax, std::min(tuneBlocks, std::max(1, perCUc)) * mp);
-        }
-        if (const char* t = getenv("RT355_CONNECT_BLOCKS")) { const int d = atoi(t); if (d > 0) ctx->persistGridConnect = std::min(ctx->gridMax, std::min(d, std::max(1, perCUc)) * mp); }   // (lab)
+        if (bvh4_tlas_trav(ctx) || ctx->tuneConnect.topLevels > 0) { if (const int rc = persist_query(ctx, ST_CONNECT, -1, &perCUc)) return rc; }
+        ctx->persistGrid = std::min(ctx->gridMax, persist_blocks(ctx, ST_EXTEND, perCU, tuneBlocks) * prop.multiProcessorCount);
+        ctx->persistGridConnect = std::min(ctx->gridMax, persist_blocks(ctx, ST_CONNECT, perCUc, tuneBlocks) * prop.multiProcessorCount);
     }
     ctx->q.spill = nullptr; ctx->q.spillStride = 0; ctx->q.stackCap = 0;
     ctx->q.tlasLdsEntries = tlas_trav(ctx) ? (uint32_t)tlas_lds_entries(ctx) : 0u;

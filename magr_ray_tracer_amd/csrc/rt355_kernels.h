@@ -843,6 +843,7 @@ struct PersistTune {
     int flat = 0;                      // k_trace_persist_tlas runs every queue through its one-ray-per-lane branch, 64 rays per wave and round (short traversals: config 5's open scene)
     int xcdRays = 0, xcdFirst = 0;     // a sparse queue's rays are kept on as few XCDs as hold them at this many rays each (one-ray-per-lane branches; 0 = spread over all eight)
     int thin = 0;                      // a queue of at most `thin` rays per participating wave is spread evenly over the waves (few lanes of each) instead of filling the first waves
+    int topLevels = 0, topBase = 0;    // k_trace_persist<.., TOP>: levels of the tree in the LDS top table (1..6) and the table's first word in dynamic LDS (behind the stack columns)
 };
 
 // A sparse queue on few XCDs: workgroup ids go to the eight XCDs round-robin and every XCD has its own L2, so the few thousand rays of a late
@@ -1002,6 +1003,93 @@ struct ChunkDealer {
     }
 };
 
+// One NODE event of k_trace_persist: the lane's ray against the pair record q0..q3 (wherever the four float4 came from), then descend,
+// push and pop exactly as traverse_bvh2_packed does.  Sets `done` when the ray is finished (nothing hit, stack empty).  Returns which child
+// of the record `cur` now is (1 / 2), or 0 after a pop or with `done` - only the top descent reads that, in the event loop it folds away.
+template <bool OCC, bool STEPS>
+RT_FORCEINLINE int node_event(const TRay& r, float tLight, float4 q0, float4 q1, float4 q2, float4 q3, uint32_t* stk, uint32_t& cur, uint32_t& sp, int& steps, bool& done)
+{
+    uint32_t e1 = __float_as_uint(q3.x), e2 = __float_as_uint(q3.y);
+    int child = 0;
+    if (OCC) {   // any-hit: the child the ray leaves later first (see slab_any); no `steps`, no near / far sort
+        float x1, x2;
+        const bool h1 = slab_any(r, mk4(q0.x, q0.y, q0.z, 0.0f), mk4(q0.w, q1.x, q1.y, 0.0f), x1);
+        const bool h2 = slab_any(r, mk4(q1.z, q1.w, q2.x, 0.0f), mk4(q2.y, q2.z, q2.w, 0.0f), x2);
+        if (h1 && h2) { const bool firstIs2 = x2 > x1; cur = firstIs2 ? e2 : e1; STK(sp) = firstIs2 ? e1 : e2; sp++; child = firstIs2 ? 2 : 1; }
+        else if (h1 || h2) { cur = h1 ? e1 : e2; child = h1 ? 1 : 2; }
+        else if (sp == 0) done = true;
+        else cur = STK(--sp);
+    } else {
+        float d1 = slab(r, mk4(q0.x, q0.y, q0.z, 0.0f), mk4(q0.w, q1.x, q1.y, 0.0f));
+        float d2 = slab(r, mk4(q1.z, q1.w, q2.x, 0.0f), mk4(q2.y, q2.z, q2.w, 0.0f));
+        const bool swap = d1 > d2;
+        if (swap) { float d = d1; d1 = d2; d2 = d; uint32_t e = e1; e1 = e2; e2 = e; }
+        if (d1 >= tLight) {
+            if (sp == 0) done = true;
+            else cur = STK(--sp);
+        } else {
+            if (STEPS) steps++;
+            cur = e1; child = swap ? 2 : 1;
+            if (d2 < tLight) { STK(sp) = e2; sp++; if (STEPS) steps++; }
+        }
+    }
+    return child;
+}
+
+// The top table of k_trace_persist<.., TOP>: the pair records of the first `levels` (1..6) levels of the BLAS in dynamic LDS behind the
+// stack columns, in heap order - slot 0 is the root's record, the children of slot s are slots 2s + 1 and 2s + 2.  A slot is PRESENT if its
+// node is an interior node and its parent's slot is present; an absent slot holds a record whose two child entries carry the leaf bit, so
+// that everything below it is absent too.  No separate presence mask is kept: a lane that descends in the table holds the child's entry in
+// `cur`, and the child's slot is present exactly if that entry is an interior one (top_descent).  The workgroup fills the table itself,
+// level by level - 2^l threads load a record each from sc.pairs and write it to LDS, one barrier per level - so the table is as fresh
+// as sc.pairs is, whatever upload, refit or rebuild last wrote it.  EVERY thread of the workgroup must call this (barriers).
+static constexpr int kTopMaxLevels = 6;
+RT_FORCEINLINE void fill_top(const DevScene& sc, uint32_t root, float4* top, int levels)
+{
+    const float4 absent = mk4(__uint_as_float(kLeafBit), __uint_as_float(kLeafBit), 0.0f, 0.0f);
+    for (int l = 0; l < levels; l++) {
+        const int n = 1 << l, t = (int)threadIdx.x;
+        if (t < n) {
+            const int s = n - 1 + t;
+            uint32_t e = root;
+            if (l > 0) { const float4 up = top[((s - 1) >> 1) * 4 + 3]; e = __float_as_uint((s & 1) ? up.x : up.y); }
+            float4 q0 = splat(0.0f), q1 = q0, q2 = q0, q3 = absent;
+            if (!(e & kLeafBit)) { const float4* p = sc.pairs + (size_t)e * 4; q0 = p[0]; q1 = p[1]; q2 = p[2]; q3 = p[3]; }
+            float4* o = top + s * 4;
+            o[0] = q0; o[1] = q1; o[2] = q2; o[3] = q3;
+        }
+        __syncthreads();
+    }
+}
+
+// Top descent: the lanes that have just taken a new ray (`fresh`; cur = root, sp = 0) take their first node events from the top table
+// instead of sc.pairs - LDS reads instead of four vector-memory requests and a round trip each - while any such lane is on a present
+// slot: at most `levels` iterations.  An iteration is a node issue of the event loop in every respect (same node_event, `wNode` and
+// `wNodeIss` counted the same way).  A lane leaves the phase with an ordinary entry in `cur` when its child is a leaf or lies below the
+// table, when it pops, or when its ray is finished; far children are pushed as ordinary entries, so the event loop never sees a slot.
+template <bool OCC, bool STEPS>
+RT_FORCEINLINE void top_descent(const DevQueues& q, const QueueWindow& w, int renderBVH, const float4* top, int levels, bool fresh, const TRay& r, float tLight,
+                                uint32_t* stk, uint32_t& cur, uint32_t& sp, int& steps, int& slot, uint32_t& wNode, uint32_t& wNodeIss)
+{
+    const uint32_t nSlots = (1u << levels) - 1u;
+    uint32_t ts = 0;
+    bool in = fresh && nSlots != 0u && !(cur & kLeafBit);
+    for (;;) {
+        const unsigned long long m = __ballot(in);
+        if (m == 0ull) break;
+        wNode += (uint32_t)__popcll(m); if (STEPS) wNodeIss++;
+        if (in) {
+            const float4* p = top + ts * 4;
+            const float4 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
+            bool done = false;
+            const int child = node_event<OCC, STEPS>(r, tLight, q0, q1, q2, q3, stk, cur, sp, steps, done);
+            if (done) { store_result<OCC, STEPS>(q, w.first, slot, r, steps, false, renderBVH); slot = -1; }
+            ts = 2u * ts + (uint32_t)child;
+            in = child != 0 && ts < nSlots && !(cur & kLeafBit);
+        }
+    }
+}
+
 // Short queue (late bounces, and bounce 0 when it is launched with one workgroup per 256 rays): every wave gets at most one 64-ray chunk
 // and nothing is left to refill from, so run the plain one-ray-per-lane loop, which has less per-step overhead than the refill machine.
 template <bool OCC, bool COH, bool BVH4 = false>
@@ -1026,7 +1114,9 @@ RT_FORCEINLINE void trace_short_queue(const DevScene& sc, const DevQueues& q, in
 // STEPS: the per-ray `steps` value of the heat map (wavefront.cl:66-67) is kept only by the instantiation that has a reader for it
 // (renderBVH or rt_debug_enable_steps); the work counters of a wave are kept in scalar registers (population counts of the masks the
 // event loop forms anyway), not per lane.
-template <bool OCC, bool COH = false, bool STEPS = false>
+// TOP: the first node events of every ray the event loop takes up come from a table of the tree's top levels in LDS (fill_top,
+// top_descent; tune.topLevels levels at word tune.topBase of the dynamic LDS).  Without TOP none of that is compiled in.
+template <bool OCC, bool COH = false, bool STEPS = false, bool TOP = false>
 __global__ __launch_bounds__(kBlock) void k_trace_persist(DevScene sc, DevQueues q, int b0, int b1, int renderBVH, PersistTune tune)
 {
     const int kInner = tune.inner, kLeafK = tune.leafK;
@@ -1054,11 +1144,16 @@ __global__ __launch_bounds__(kBlock) void k_trace_persist(DevScene sc, DevQueues
 #endif
         return;
     }
+    // (the branch above is taken by every workgroup of a launch or by none - the queue length and the grid are the launch's - so the
+    // barriers of the fill are reached by whole workgroups)
+    float4* const top = reinterpret_cast<float4*>(stk + tune.topBase);
+    if (TOP) fill_top(sc, one.root, top, tune.topLevels);
     ChunkDealer deal(waveId, tune.chunk, w.n);
     for (;;) {
         int idx;
         if (!deal.refill(slot < 0, idx, wRays, w, tune, nWaves, waveId, lane)) break;
         if (idx >= 0) { queue_ray<OCC>(r, q, b0, w.first, idx, &one); tLight = r.t; cur = one.root; sp = 0; steps = 0; slot = idx; }
+        if (TOP) top_descent<OCC, STEPS>(q, w, renderBVH, top, tune.topLevels, idx >= 0, r, tLight, stk, cur, sp, steps, slot, wNode, wNodeIss);
 #pragma unroll 1
         for (int it = 0; it < kInner; it++) {
             // One event per lane and iteration, but the wave issues only ONE of the two code paths: triangle tests
@@ -1085,28 +1180,7 @@ __global__ __launch_bounds__(kBlock) void k_trace_persist(DevScene sc, DevQueues
             } else if (act && !atLeaf) {
                 const float4* p = sc.pairs + (size_t)cur * 4;
                 const float4 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
-                uint32_t e1 = __float_as_uint(q3.x), e2 = __float_as_uint(q3.y);
-                if (OCC) {   // any-hit: the child the ray leaves later first (see slab_any); no `steps`, no near / far sort
-                    float x1, x2;
-                    const bool h1 = slab_any(r, mk4(q0.x, q0.y, q0.z, 0.0f), mk4(q0.w, q1.x, q1.y, 0.0f), x1);
-                    const bool h2 = slab_any(r, mk4(q1.z, q1.w, q2.x, 0.0f), mk4(q2.y, q2.z, q2.w, 0.0f), x2);
-                    if (h1 && h2) { const bool firstIs2 = x2 > x1; cur = firstIs2 ? e2 : e1; STK(sp) = firstIs2 ? e1 : e2; sp++; }
-                    else if (h1 || h2) cur = h1 ? e1 : e2;
-                    else if (sp == 0) done = true;
-                    else cur = STK(--sp);
-                } else {
-                    float d1 = slab(r, mk4(q0.x, q0.y, q0.z, 0.0f), mk4(q0.w, q1.x, q1.y, 0.0f));
-                    float d2 = slab(r, mk4(q1.z, q1.w, q2.x, 0.0f), mk4(q2.y, q2.z, q2.w, 0.0f));
-                    if (d1 > d2) { float d = d1; d1 = d2; d2 = d; uint32_t e = e1; e1 = e2; e2 = e; }
-                    if (d1 >= tLight) {
-                        if (sp == 0) done = true;
-                        else cur = STK(--sp);
-                    } else {
-                        if (STEPS) steps++;
-                        cur = e1;
-                        if (d2 < tLight) { STK(sp) = e2; sp++; if (STEPS) steps++; }
-                    }
-                }
+                node_event<OCC, STEPS>(r, tLight, q0, q1, q2, q3, stk, cur, sp, steps, done);
             }
             if (done) { store_result<OCC, STEPS>(q, w.first, slot, r, steps, occluded, renderBVH); slot = -1; }
         }

@@ -168,6 +168,12 @@ class Device:
         self._chk(self._lib.rt_kernel_info(self._h, k.ctypes.data_as(C.c_void_p)))
         return {n: int(k[n]) for n in k.dtype.names}
 
+    def top_levels(self):
+        """(extend, connect): levels of the BLAS the event loops descend from their LDS top table (rt_top_levels; 0 = no table)."""
+        e, c = C.c_int32(0), C.c_int32(0)
+        self._chk(self._lib.rt_top_levels(self._h, C.byref(e), C.byref(c)))
+        return int(e.value), int(c.value)
+
     @property
     def builtins(self):
         """The context's arithmetic as resolved by the library (rt_builtins): _lib.BUILTINS_IEEE or _lib.BUILTINS_REFERENCE."""
