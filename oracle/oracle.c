@@ -490,6 +490,61 @@ static int traverse_bvh2(RtRay* ray, const OrcScene* sc, uint32_t root, int occl
     }
     return steps;
 }
+/* The slab test of isect_aabb with both distances kept: the same six float32 products and minNum / maxNum chain, `hit` its visit
+ * condition against the pruning distance t_light, *exitT the distance at which the ray leaves the box. */
+static inline int slab_exit(const RtRay* ray, f4 bmin, f4 bmax, float t_light, float* exitT)
+{
+    float tx1 = (bmin.x - ray->O.x) * ray->rD.x, tx2 = (bmax.x - ray->O.x) * ray->rD.x;
+    float tmin = fminf(tx1, tx2), tmax = fmaxf(tx1, tx2);
+    float ty1 = (bmin.y - ray->O.y) * ray->rD.y, ty2 = (bmax.y - ray->O.y) * ray->rD.y;
+    tmin = fmaxf(tmin, fminf(ty1, ty2)); tmax = fminf(tmax, fmaxf(ty1, ty2));
+    float tz1 = (bmin.z - ray->O.z) * ray->rD.z, tz2 = (bmax.z - ray->O.z) * ray->rD.z;
+    tmin = fmaxf(tmin, fminf(tz1, tz2)); tmax = fminf(tmax, fmaxf(tz1, tz2));
+    *exitT = tmax;
+    return tmax >= tmin && tmin < t_light && tmax > 0;
+}
+/* OrcConfig.connect_order == 1: the occlusion traversal of a BVH2 BLAS in the order the HIP path's connect uses (NOT the reference's).
+ * Of the two children that pass the visit test the one the ray leaves LATER goes first - child 2 iff its exit distance is greater,
+ * ties go to child 1 - and the other is pushed; with one passing child descend into it, with none pop.  Which nodes are reached at all
+ * does not depend on the order, so neither does the verdict; the counts do.  Returns -1 for an occluded ray, else 0 (`steps` has no
+ * reader in connect). */
+static int traverse_bvh2_later_exit(RtRay* ray, const OrcScene* sc, uint32_t root, OrcCounters* c)
+{
+    const RtBVHNode2* nodes = sc->bvh2;
+    const RtBVHNode2* stack[RT_BVH4_STACK];
+    const RtBVHNode2* node = nodes + root;
+    uint32_t sp = 0;
+    const float t_light = ray->t;
+    for (;;) {
+        if (node->count > 0) {
+            for (uint32_t i = 0; i < node->count; i++) {
+                int index = (int)sc->primIdx[node->first + i];
+                c->prim_tests++;
+                isect_prim(index, &sc->prims[index], ray);
+                if (ray->t < t_light) return -1;
+            }
+            if (sp == 0) break;
+            node = stack[--sp];
+            continue;
+        }
+        c->node_visits++;
+        const RtBVHNode2* c1 = &nodes[node->first];
+        const RtBVHNode2* c2 = &nodes[node->first + 1];
+        float x1, x2;
+        const int h1 = slab_exit(ray, c1->aabbMin, c1->aabbMax, t_light, &x1);
+        const int h2 = slab_exit(ray, c2->aabbMin, c2->aabbMax, t_light, &x2);
+        if (h1 && h2) {
+            if (x2 > x1) { node = c2; stack[sp++] = c1; }
+            else { node = c1; stack[sp++] = c2; }
+        } else if (h1 || h2) {
+            node = h1 ? c1 : c2;
+        } else {
+            if (sp == 0) break;
+            node = stack[--sp];
+        }
+    }
+    return 0;
+}
 static int traverse_bvh4(RtRay* ray, const OrcScene* sc, uint32_t root, int occlusion, OrcCounters* c) /* bvh.cl:55-96 */
 {
     const RtBVHNode4* nodes = sc->bvh4;
@@ -539,6 +594,7 @@ static int traverse_instance(RtRay* ray, const OrcScene* sc, const OrcConfig* cf
     ray->rD = v4(1.0f / ray->D.x, 1.0f / ray->D.y, 1.0f / ray->D.z, 1.0f);
     c->inst_visits++;
     int steps = cfg->accel == ORC_ACCEL_BVH4 ? traverse_bvh4(ray, sc, inst->bvhIdx, occlusion, c)
+              : occlusion && cfg->connect_order == ORC_CONNECT_LATER_EXIT ? traverse_bvh2_later_exit(ray, sc, inst->bvhIdx, c)
                                              : traverse_bvh2(ray, sc, inst->bvhIdx, occlusion, c);
     ray->D = bD; ray->O = bO; ray->rD = brD;
     return steps;
@@ -776,6 +832,22 @@ void orc_connect(const RtShadowRay* shadow, int32_t n, const OrcScene* sc, const
     }
     if (ctr) { ctr->rays += local.rays; ctr->tlas_visits += local.tlas_visits; ctr->inst_visits += local.inst_visits;
                ctr->node_visits += local.node_visits; ctr->prim_tests += local.prim_tests; }
+}
+/* The traversal work of orc_connect ray by ray, nothing accumulated: work[i] belongs to shadow[i] whatever the schedule, and the sums
+ * over i are what orc_connect adds to its counters for the same queue and config (connect_order included). */
+void orc_connect_work(const RtShadowRay* shadow, int32_t n, const OrcScene* sc, const OrcConfig* cfg, OrcRayWork* work)
+{
+    for (int32_t i = 0; i < n; i++) {
+        const RtShadowRay* s = &shadow[i];
+        OrcCounters c; memset(&c, 0, sizeof c);
+        RtRay ray = zero_ray();
+        init_ray(&ray, add4(s->I, muls(s->L, RT_EPSILON)), s->L);
+        ray.t = s->dist - 2 * RT_EPSILON;
+        const int occluded = traverse_tlas(&ray, sc, cfg, 1, &c) == -1;
+        work[i].node_visits = (uint32_t)c.node_visits; work[i].prim_tests = (uint32_t)c.prim_tests;
+        work[i].tlas_visits = (uint32_t)c.tlas_visits; work[i].inst_visits = (uint32_t)c.inst_visits;
+        work[i].occluded = (uint32_t)occluded;
+    }
 }
 float orc_focus(int32_t x, int32_t y, const OrcScene* sc, const OrcConfig* cfg, const RtCamera* cam) /* wavefront.cl:203-224 */
 {

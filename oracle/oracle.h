@@ -31,6 +31,12 @@ enum { ORC_ACCEL_BVH2 = 0, ORC_ACCEL_BVH4 = 1 };            /* renderer.h:15-16 
  *     in processing order.  This is what the reference kernels do when launched
  *     with a global size of 1, and is used to pin shade() against them. */
 enum { ORC_SCHED_S1 = 1, ORC_SCHED_S0 = 0 };
+/* Order in which an OCCLUSION traversal (connect) visits the two children of a BVH2 BLAS node when the ray hits both:
+ * REFERENCE: near child first (bvh.cl:41-52), what a zero-filled config gives.
+ * LATER_EXIT: the child with the greater slab exit distance first, ties to child 1 - the order of the HIP path's connect
+ *     (rt355_kernels.h slab_any).  Changes nothing else: TLAS nodes, instance entry, BVH4 and every extend / focus traversal keep
+ *     the reference's order, and a shadow ray's verdict does not depend on it - only connect's node_visits and prim_tests do. */
+enum { ORC_CONNECT_REFERENCE = 0, ORC_CONNECT_LATER_EXIT = 1 };
 
 typedef struct OrcScene {
     const RtPrimitive*   prims;     int32_t nPrims;
@@ -51,6 +57,7 @@ typedef struct OrcConfig {
     int32_t shading, sampling, accel;
     int32_t russian_roulette, filter_fireflies;
     int32_t schedule;               /* ORC_SCHED_S1 / ORC_SCHED_S0 */
+    int32_t connect_order;          /* ORC_CONNECT_REFERENCE / ORC_CONNECT_LATER_EXIT */
 } OrcConfig;
 
 /* Work counters behind the roofline formula of SURVEY.md §8(d). */
@@ -74,6 +81,10 @@ void orc_shade(RtRay* in, int32_t nIn, RtRay* out, int32_t* nOut,
                const OrcConfig* cfg, RtFloat4* accum, uint32_t* seeds);
 void orc_connect(const RtShadowRay* shadow, int32_t n, const OrcScene* sc,
                  const OrcConfig* cfg, RtFloat4* accum, OrcCounters* ctr);
+/* orc_connect's traversal work per shadow ray (work[i] for shadow[i]); accumulates nothing.  Summed, the four counts are what
+ * orc_connect adds to its counters for the same queue. */
+typedef struct OrcRayWork { uint32_t node_visits, prim_tests, tlas_visits, inst_visits, occluded; } OrcRayWork;
+void orc_connect_work(const RtShadowRay* shadow, int32_t n, const OrcScene* sc, const OrcConfig* cfg, OrcRayWork* work);
 float orc_focus(int32_t x, int32_t y, const OrcScene* sc, const OrcConfig* cfg, const RtCamera* cam);
 
 /* One Renderer::RayTrace() (renderer.cpp:64-94) over pixels [firstPixel, firstPixel+n).

@@ -12,8 +12,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 S1, S0 = 1, 0
 
 OrcConfig = np.dtype([(n, "<i4") for n in ("width", "height", "max_bounces", "shading", "sampling", "accel",
-                                            "russian_roulette", "filter_fireflies", "schedule")])
+                                            "russian_roulette", "filter_fireflies", "schedule", "connect_order")])
 OrcCounters = np.dtype([(n, "<u8") for n in ("rays", "tlas_visits", "inst_visits", "node_visits", "prim_tests")])
+OrcRayWork = np.dtype([(n, "<u4") for n in ("node_visits", "prim_tests", "tlas_visits", "inst_visits", "occluded")])
+REFERENCE_ORDER, LATER_EXIT = 0, 1      # OrcConfig.connect_order
 
 
 class _Scene(C.Structure):
@@ -39,6 +41,7 @@ def lib():
         L.orc_extend.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp]
         L.orc_shade.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
         L.orc_connect.argtypes = [vp, i32, vp, vp, vp, vp]
+        L.orc_connect_work.argtypes = [vp, i32, vp, vp, vp]
         L.orc_focus.argtypes = [i32, i32, vp, vp, vp]
         L.orc_focus.restype = C.c_float
         L.orc_frame_work_bytes.argtypes = [i32, vp]
@@ -115,13 +118,16 @@ class Oracle:
     """Holds one scene (SceneArrays-like object with numpy arrays) + variant config."""
 
     def __init__(self, sa, width, height, shading=1, sampling=1, accel=0, russian_roulette=True, filter_fireflies=True,
-                 max_bounces=7, schedule=S1):
+                 max_bounces=7, schedule=S1, connect_order=REFERENCE_ORDER):
+        """connect_order LATER_EXIT: shadow rays walk a BVH2 BLAS in the HIP path's any-hit order (oracle.h); only connect's node and
+        primitive counts depend on it."""
         self.sa = sa
         self.cfg = np.zeros((), dtype=OrcConfig)
         c = self.cfg
         c["width"], c["height"], c["max_bounces"] = width, height, max_bounces
         c["shading"], c["sampling"], c["accel"] = shading, sampling, accel
         c["russian_roulette"], c["filter_fireflies"], c["schedule"] = int(russian_roulette), int(filter_fireflies), schedule
+        c["connect_order"] = connect_order
         self.width, self.height = width, height
         s = _Scene()
         s.prims, s.nPrims = _p(sa.prims), len(sa.prims)
@@ -171,6 +177,14 @@ class Oracle:
         if len(shadow):
             lib().orc_connect(_p(shadow), len(shadow), self._sc, self._cfg, _p(accum), ctr.ctypes.data_as(C.c_void_p))
         return {k: int(ctr[k]) for k in ctr.dtype.names}
+
+    def connect_work(self, shadow):
+        """Per shadow ray (OrcRayWork): node visits, primitive tests, TLAS and instance visits, occluded.  Accumulates nothing."""
+        work = np.zeros(len(shadow), dtype=OrcRayWork)
+        shadow = np.ascontiguousarray(shadow)
+        if len(shadow):
+            lib().orc_connect_work(_p(shadow), len(shadow), self._sc, self._cfg, _p(work))
+        return work
 
     def focus(self, x, y, cam):
         c = np.ascontiguousarray(cam)

@@ -69,10 +69,10 @@ def assert_same_bytes(a, b, what):
 
 
 def ctr_equal(dev, e, c):
-    """The extend counters (and connect's rays / TLAS / instance visits) equal the oracle's: tests/test_gpu_parity.py _ctr_equal."""
+    """The extend and the connect counters equal the oracle's (e, c of helpers.oracle_for): tests/test_gpu_parity.py _ctr_equal."""
     for k in ("rays", "tlas_visits", "inst_visits", "node_visits", "prim_tests"):
         assert dev["extend_" + k] == e[k], ("extend_" + k, dev["extend_" + k], e[k])
-    for k in ("rays", "tlas_visits", "inst_visits"):
+    for k in ("rays", "tlas_visits", "inst_visits", "node_visits", "prim_tests"):
         assert dev["connect_" + k] == c[k], ("connect_" + k, dev["connect_" + k], c[k])
 
 

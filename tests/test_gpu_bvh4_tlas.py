@@ -18,10 +18,10 @@ import test_gpu_groundtruth as T
 import test_gpu_validate as VAL
 import test_groundtruth_cpu as C
 import validate_catalogue as K
-from helpers import DEFAULT, assert_bits
+from helpers import DEFAULT, assert_bits, oracle_for
 from magr_ray_tracer_amd import _lib as W, scenes
 from magr_ray_tracer_amd.renderer import Device, Group
-from oracle.oracle_py import Oracle, seed_stream
+from oracle.oracle_py import seed_stream
 from test_gpu_parity import _ctr_equal
 
 pytestmark = pytest.mark.gpu
@@ -81,7 +81,7 @@ def test_variant_6_selects_the_kernel_only_for_multi_blas_bvh4_layout_1(monkeypa
 # ---- 2. bit for bit against the nested loops and the oracle ------------------------------------------------------------------------------
 def _oracle_frames(key, sa, view, accel=B4, frames=2):
     if key not in _ORACLE:
-        _ORACLE[key] = Oracle(sa, WD, HD, accel=accel, **FRAME).render(scenes.camera_for(view, WD, HD), frames)
+        _ORACLE[key] = oracle_for(sa, WD, HD, accel=accel, **FRAME).render(scenes.camera_for(view, WD, HD), frames)
     return _ORACLE[key]
 
 

@@ -10,8 +10,8 @@ import pytest
 from magr_ray_tracer_amd import scenes
 from magr_ray_tracer_amd import dist as rdist
 from magr_ray_tracer_amd.renderer import Group
-from oracle.oracle_py import Oracle, seed_stream
-from helpers import DEFAULT, assert_bits
+from oracle.oracle_py import seed_stream
+from helpers import DEFAULT, assert_bits, oracle_for
 
 Wd, Hd, FIRST = 160, 90, 1
 CALLS_A, CALLS_B = (4, 3), (5,)      # render(4), render(3); reset; render(5)
@@ -25,7 +25,7 @@ def _scene():
 
 def _oracle(sa, cam, lanes):
     """Per lane: accumulator and seeds after CALLS_A, then after the reset and CALLS_B, and the work counters of both."""
-    o = Oracle(sa, Wd, Hd, **DEFAULT)
+    o = oracle_for(sa, Wd, Hd, **DEFAULT)
     na, nb = rdist.lane_frames(sum(CALLS_A), lanes), rdist.lane_frames(sum(CALLS_B), lanes)
     out = []
     for m in range(lanes):
@@ -72,10 +72,10 @@ def _render(sa, cam, lanes, streams, monkeypatch):
 
 
 def _ctr_vs_oracle(dev, e, c, what):
-    """As test_gpu_parity._ctr_equal: extend counters are the reference's; connect's node / triangle counts follow its own order."""
+    """As test_gpu_parity._ctr_equal: extend's counters are the reference's, connect's the oracle's in connect's own order."""
     for k in ("rays", "tlas_visits", "inst_visits", "node_visits", "prim_tests"):
         assert dev["extend_" + k] == e.get(k, 0), (what, "extend_" + k, dev["extend_" + k], e.get(k, 0))
-    for k in ("rays", "tlas_visits", "inst_visits"):
+    for k in ("rays", "tlas_visits", "inst_visits", "node_visits", "prim_tests"):
         assert dev["connect_" + k] == c.get(k, 0), (what, "connect_" + k, dev["connect_" + k], c.get(k, 0))
 
 

@@ -14,7 +14,7 @@ import test_gpu_refit as RF
 import test_groundtruth_cpu as C
 import test_tlas_cpu as TC
 import tlas_check as T
-from helpers import DEFAULT, assert_bits
+from helpers import DEFAULT, assert_bits, oracle_for
 from magr_ray_tracer_amd import _lib as W, scenes
 from magr_ray_tracer_amd.renderer import Device, RtError, _rebuild_args, _update_args
 from oracle.oracle_py import Oracle, seed_stream
@@ -178,7 +178,7 @@ def _traverse(d, gt, sa, view, accel, what):
     through stage_extend meet the float64 closest hit."""
     cam = scenes.camera_for(view, Wd, Hd)
     v = dict(DEFAULT, accel=accel)
-    acc, seeds, e, c = Oracle(sa, Wd, Hd, **v).render(cam, 2)
+    acc, seeds, e, c = oracle_for(sa, Wd, Hd, **v).render(cam, 2)
     T.assert_seen(e, c, what)
     d.seed_default()
     d.reset()

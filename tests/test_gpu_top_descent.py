@@ -7,23 +7,18 @@ rt_rebuild_scene have changed the records the table is filled from.
 Set up as test_gpu_groundtruth.py: 320x240 frames and one workgroup per CU (RT355_TUNE), so that queues of more than 65,536 rays run
 the event loop.  Every comparison is with the oracle (oracle.oracle_py); none with another setting of the code under test.
 
-Connect is an any-hit traversal with its own visit order inside a BLAS (slab_any), so its node and triangle counts are not the
-reference's by design (as in test_gpu_parity._ctr_equal): of connect's counters the rays, TLAS and instance visits are compared, and -
-what the visit order cannot change - the accumulator.  The oracle therefore has no figure to hold connect's node and triangle counts
-to: a top descent of connect that counted its node events wrongly (`wNode`) while tracing them rightly would pass this module.  Extend's
-counts, which the same code forms in the same way, are held to the oracle's exactly."""
-import dataclasses
-
+Connect is an any-hit traversal with its own visit order inside a BLAS (slab_any): its counts are held to the oracle in connect's own
+order (helpers.oracle_for, as in test_gpu_parity._ctr_equal), all five of them exactly, like extend's."""
 import numpy as np
 import pytest
 
-import geom64 as G
 import test_groundtruth_cpu as C
-from helpers import assert_bits
+from hand_trees import floor_rays as _floor_rays, hand_rays as _hand_rays, hand_scene as _hand_scene, tree as _tree
+from helpers import assert_bits, oracle_for
 from magr_ray_tracer_amd import _lib as W, scenes
 from magr_ray_tracer_amd.renderer import Device
 from magr_ray_tracer_amd.scenes import Scene, _std_materials, box_tris
-from oracle.oracle_py import Oracle, seed_stream
+from oracle.oracle_py import seed_stream
 
 pytestmark = pytest.mark.gpu
 
@@ -40,9 +35,8 @@ def _ctr_extend(dev, e, what):
 
 
 def _ctr_connect(dev, c, what):
-    for k in ("rays", "tlas_visits", "inst_visits"):
+    for k in ("rays", "tlas_visits", "inst_visits", "node_visits", "prim_tests"):
         assert dev["connect_" + k] == c[k], (what, "connect_" + k, dev["connect_" + k], c[k])
-    assert (dev["connect_node_visits"] > 0) == (c["node_visits"] > 0), what
 
 
 def _add(tot, c):
@@ -82,7 +76,7 @@ def _frame_reference():
         gt, sa, view = C.soup_scene(0.0, room=True)
         cam = scenes.camera_for(view, WD, HD)
         n = WD * HD
-        o = Oracle(sa, WD, HD, **FRAME)
+        o = oracle_for(sa, WD, HD, **FRAME)
         seeds = seed_stream(0, n)
         acc = np.zeros((n, 4), np.float32)
         rays = o.generate(cam, 0, n, seeds)
@@ -149,117 +143,8 @@ def test_the_accessor_reports_each_stage_and_refuses_nonsense(monkeypatch):
             d.close()
 
 
-# ---- trees built by hand ----------------------------------------------------------------------------------------------------------------
-# Primitive 0 is a floor triangle in the plane y = 0, primitive 1 a light in the plane y = 2 above it, the others stand in a row along x
-# at y in [2, 3].  A shadow ray from the floor to the light starts above the floor's (flat) box and ends below the plane y = 2 that
-# bounds every other box from below: where the root's two children are the floor and everything else it misses both - a ray finished
-# inside the phase with tmax shorter than the entry distance.
-def _prims(n):
-    t = [[(-4, 0, -4), (4, 0, 4), (4, 0, -4)], [(-0.5, 2, -0.5), (0.5, 2, -0.5), (0.5, 2, 0.5)]]
-    for k in range(n - 2):
-        x = 6.0 + 1.5 * k
-        t.append([(x, 2, -1), (x + 0.25, 3, 0), (x, 2, 1)])
-    return np.array(t[:n], np.float32)
-
-
-def _hand_scene(n, tree):
-    """n primitives under the BVH2 `tree`: a list of primitive ids is a leaf, a pair (left, right) an interior node.  Nodes as BVH2's
-    builders lay them out (root 0, node 1 unused, the two children of a node side by side), boxes from the vertices."""
-    tris = _prims(n)
-    s = Scene()
-    _std_materials(s)
-    s.AddTriangles(tris[:1], "sand")
-    if n > 1:
-        s.AddTriangles(tris[1:2], "white-light")
-    if n > 2:
-        s.AddTriangles(tris[2:], "green")
-    s.BuildBLAS(0)
-    sa = s.arrays()
-    nodes, idx = [None, None], []
-
-    def fill(at, t):
-        nd = np.zeros((), W.BVHNode2)
-        if isinstance(t, list):
-            nd["first"], nd["count"] = len(idx), len(t)
-            idx.extend(t)
-            v = tris[t].reshape(-1, 3)
-        else:
-            k = len(nodes)
-            nodes.extend([None, None])
-            nd["first"], nd["count"] = k, 0
-            v = np.concatenate([fill(k, t[0]), fill(k + 1, t[1])])
-        nd["aabbMin"][:3], nd["aabbMax"][:3] = v.min(0), v.max(0)
-        nodes[at] = nd
-        return v
-
-    fill(0, tree)
-    nodes[1] = np.zeros((), W.BVHNode2)
-    bvh2 = np.array(nodes, dtype=W.BVHNode2)
-    assert int(sa.blas["bvhIdx"][0]) == 0 and len(sa.blas) == 1
-    assert np.array_equal(bvh2["aabbMin"][0], sa.bvh2["aabbMin"][0]) and np.array_equal(bvh2["aabbMax"][0], sa.bvh2["aabbMax"][0])
-    return dataclasses.replace(sa, bvh2=bvh2, primIdx=np.array(idx, np.uint32))
-
-
-def _ladder(ids):
-    """Every interior node has one leaf child and one interior child, the leaf on alternating sides; the last one two leaves."""
-    t = ([ids[-2]], [ids[-1]])
-    for k, i in enumerate(reversed(ids[:-2])):
-        t = ([i], t) if k % 2 else (t, [i])
-    return t
-
-
-def _balanced(ids):
-    return list(ids) if len(ids) == 1 else (_balanced(ids[:len(ids) // 2]), _balanced(ids[len(ids) // 2:]))
-
-
-def _tree(name, L):
-    if name == "one-triangle":
-        return 1, [0]
-    if name == "two-triangles":
-        return 2, ([0], [1])
-    if name == "ladder-8":                     # eight interior nodes, one per level; root = (floor, everything else)
-        return 9, ([0], _ladder(list(range(1, 9))))
-    d = L + {"depth-L-1": -1, "depth-L": 0, "depth-L+1": 1}[name]
-    return 1 << d, _balanced(list(range(1 << d)))      # complete: d levels of interior nodes over 2^d single-triangle leaves
-
-
+# ---- trees built by hand (hand_trees.py: row_prims, whose floor-to-light shadow rays finish at the root, missing both children) -------
 TREES = ["one-triangle", "two-triangles", "ladder-8", "depth-L-1", "depth-L", "depth-L+1"]
-
-
-def _hand_rays(n):
-    """Rays against the hand-built scenes: away from everything (both root children missed), down at the floor (one child; their shadow
-    rays run to the light), along the row from either end and across it (both children, far child pushed and popped later), random."""
-    rng = np.random.default_rng(17)
-    xmax = 6.0 + 1.5 * max(n - 2, 1)
-    O, D = [], []
-    k = 160
-    O.append(np.c_[rng.uniform(-4, xmax, k), np.full(k, 5.0), rng.uniform(-1, 1, k)]); D.append(np.tile([0.0, 1.0, 0.0], (k, 1)) + rng.normal(scale=0.2, size=(k, 3)))
-    P = np.c_[rng.uniform(-3.5, 3.5, 3 * k), np.zeros(3 * k), rng.uniform(-3.5, 3.5, 3 * k)]
-    o = np.c_[rng.uniform(-3, 3, 3 * k), np.full(3 * k, 6.0), rng.uniform(-3, 3, 3 * k)]
-    O.append(o); D.append(P - o)
-    for x0, sx in ((-5.0, 1.0), (xmax + 3.0, -1.0)):
-        o = np.c_[np.full(k, x0), rng.uniform(2.0, 3.0, k), rng.uniform(-1, 1, k)]
-        O.append(o); D.append(np.c_[np.full(k, sx), rng.normal(scale=0.03, size=k), rng.normal(scale=0.03, size=k)])
-    o = np.c_[rng.uniform(-4, xmax, 2 * k), rng.uniform(3.5, 6, 2 * k), rng.uniform(-3, 3, 2 * k)]
-    t = np.c_[rng.uniform(-4, xmax, 2 * k), rng.uniform(0, 3, 2 * k), rng.uniform(-1, 1, 2 * k)]
-    O.append(o); D.append(t - o)
-    o = rng.uniform([-6, -1, -5], [xmax + 2, 7, 5], (4 * k, 3))
-    O.append(o); D.append(rng.normal(size=(4 * k, 3)))
-    O, D = np.concatenate(O), np.concatenate(D)
-    return G.make_rays(O, D / np.linalg.norm(D, axis=1)[:, None])
-
-
-def _floor_rays(n):
-    """n rays from above to points inside the floor triangle: nearly every one of them sends a shadow ray to the light."""
-    rng = np.random.default_rng(29)
-    u, v = rng.uniform(0.03, 0.94, n), rng.uniform(0.03, 0.94, n)
-    over = u + v > 0.97
-    u[over], v[over] = 0.97 - v[over], 0.97 - u[over]
-    A, B, Cc = np.array([-4.0, 0, -4]), np.array([4.0, 0, 4]), np.array([4.0, 0, -4])
-    P = A + u[:, None] * (B - A) + v[:, None] * (Cc - A)
-    o = P + np.c_[rng.uniform(-1, 1, n), np.full(n, 6.0), rng.uniform(-1, 1, n)]
-    D = P - o
-    return G.make_rays(o, D / np.linalg.norm(D, axis=1)[:, None])
 
 
 def _trace_queue(d, o, sa, rays, what, steps_kept=True):
@@ -303,7 +188,7 @@ def test_hand_built_trees(name, levels, monkeypatch):
         sa = _hand_scene(n, tree)
         d.upload(sa)
         assert d.kernel_info()["persist"] == 1
-        o = Oracle(sa, WD, HD, **FRAME)
+        o = oracle_for(sa, WD, HD, **FRAME)
         rays = _hand_rays(n)
         m = len(rays)
         assert m <= 4096
@@ -367,7 +252,7 @@ def test_the_table_follows_an_update_and_a_rebuild(how, monkeypatch):
     sa0 = s0.arrays()
     prims = _room(True).arrays().prims
     cam = scenes.camera_for(VIEW, WD, HD)
-    o0 = Oracle(sa0, WD, HD, **FRAME)
+    o0 = oracle_for(sa0, WD, HD, **FRAME)
     acc, seeds, _, _ = o0.render(cam, 2)
     s0.SetPrimitives(0, prims)
     if how == "update":
@@ -376,7 +261,7 @@ def test_the_table_follows_an_update_and_a_rebuild(how, monkeypatch):
         s0.Rebuild("sah")
     saR = s0.arrays()
     assert not np.array_equal(saR.bvh2["aabbMin"][:8], sa0.bvh2["aabbMin"][:8])
-    acc, seeds, e, c = Oracle(saR, WD, HD, **FRAME).render(cam, 2, accum=acc, seeds=seeds)
+    acc, seeds, e, c = oracle_for(saR, WD, HD, **FRAME).render(cam, 2, accum=acc, seeds=seeds)
     d = _device(None, monkeypatch)
     try:
         d.upload(sa0)

@@ -17,10 +17,10 @@ import test_gpu_groundtruth as T
 import validate_catalogue as K
 import validate_sweep as S
 import wire_audit as A
-from helpers import assert_bits
+from helpers import assert_bits, oracle_for
 from magr_ray_tracer_amd import _lib as W, scenes
 from magr_ray_tracer_amd.renderer import Device, RtError
-from oracle.oracle_py import Oracle, seed_stream
+from oracle.oracle_py import seed_stream
 from test_gpu_parity import _ctr_equal
 
 pytestmark = pytest.mark.gpu
@@ -51,7 +51,7 @@ def _oracle_frames(name, accel):
     key = (name, accel, "frames")
     if key not in _ORACLE:
         e = K.entry(name)
-        _ORACLE[key] = Oracle(e.sa, WD, HD, accel=accel, **FRAME).render(scenes.camera_for(e.view, WD, HD), 2)
+        _ORACLE[key] = oracle_for(e.sa, WD, HD, accel=accel, **FRAME).render(scenes.camera_for(e.view, WD, HD), 2)
     return _ORACLE[key]
 
 
@@ -59,7 +59,7 @@ def _oracle_extend(name, accel, q, tag):
     key = (name, accel, tag)
     if key not in _ORACLE:
         r = q.copy()
-        _, ctr = Oracle(K.entry(name).sa, 64, 48, accel=accel, **FRAME).extend(r, want_steps=True)
+        _, ctr = oracle_for(K.entry(name).sa, 64, 48, accel=accel, **FRAME).extend(r, want_steps=True)
         _ORACLE[key] = (r, ctr)
     return _ORACLE[key]
 
