@@ -58,7 +58,7 @@ typedef struct RtConfig {
     int32_t profile;            /* HIP-event brackets on the context's stream: 0 none, 1 extend launches only
                                  * (what the roofline needs; ~1 % overhead), 2 every stage launch (~3.5 %)        */
     int32_t shade_blocks_per_cu;/* k_shade workgroups per CU: 0 = what the CUs hold (2, best for one context with the GPU to itself);
-                                 * > 0 also selects 256-slot tiles (39 KB of LDS instead of 78): 1 leaves room for the kernels of
+                                 * > 0 also selects 256-slot tiles (24.9 KB of LDS instead of 49.8; rt_shade_footprint): 1 leaves room for the kernels of
                                  * other contexts (best when several sample streams share the GPU)                               */
     int32_t persist_blocks_per_cu; /* workgroups per CU of the persistent traversal grids: 0 = what the hardware admits (7 extend / 6 connect);
                                  * 4 is best when three contexts share the GPU (their workgroups then fit beside each other);
@@ -119,6 +119,12 @@ int rt_builtins(RtCtx* ctx);   /* the context's arithmetic, resolved: RT_BUILTIN
 /* Levels of the BLAS that the event loops of extend and of connect descend from a table in LDS when a lane takes a new ray (0..6; 0: no
  * table.  Single-BLAS BVH2 scenes under persistent wavefronts only, else 0; RT355_TOP_LEVELS overrides the defaults) */
 int rt_top_levels(RtCtx* ctx, int32_t* extend, int32_t* connect);
+/* What shares a CU when contexts run side by side.  *ldsBytes: the static LDS of a workgroup of this context's k_shade instantiation
+ * (256 slots for the lanes of a group, 512 for a context alone).  *traversalBeside: how many workgroups of the context's persistent
+ * extend kernel, without a top table, fit a CU beside one such workgroup - by LDS, VGPRs and wave slots, from the kernels' own
+ * attributes (0 where no persistent kernel runs).  For a context that shares the GPU (RtConfig.persist_blocks_per_cu > 0) the automatic
+ * rt_top_levels are the deepest tables that keep this number. */
+int rt_shade_footprint(RtCtx* ctx, int32_t* ldsBytes, int32_t* traversalBeside);
 
 /* new Buffer(...) x11 + new Kernel(...) x6 (renderer.cpp:145-157, :218-223). */
 int rt_create(const RtConfig* cfg, RtCtx** out);

@@ -146,6 +146,25 @@ extern "C" int rt_top_levels(RtCtx* ctx, int32_t* extend, int32_t* connect)
     return RT_OK;
 }
 
+static int beside_shade(const RtCtx* c, int stage, int topLevels, int* perCU, int* shadeLds);
+extern "C" int rt_shade_footprint(RtCtx* ctx, int32_t* ldsBytes, int32_t* traversalBeside)
+{
+    if (!ctx || !ldsBytes || !traversalBeside) return fail(RT_E_INVALID, "rt_shade_footprint: null argument");
+    if (!ctx->sceneLoaded) return fail(RT_E_INVALID, "rt_shade_footprint: no scene uploaded");
+    if (const int rc = sync_scene_config(ctx)) return rc;
+    *ldsBytes = 0; *traversalBeside = 0;
+    if (!persistent(ctx)) {   // no persistent grid to count: the footprint alone
+        hipFuncAttributes a{};
+        HIPCHK(hipFuncGetAttributes(&a, (const void*)ctx->kShade));
+        *ldsBytes = (int32_t)a.sharedSizeBytes;
+        return RT_OK;
+    }
+    int lds = 0, beside = 0;
+    if (const int rc = beside_shade(ctx, ST_EXTEND, 0, &beside, &lds)) return rc;
+    *ldsBytes = lds; *traversalBeside = beside;
+    return RT_OK;
+}
+
 static void free_bag(std::vector<void*>& bag) { for (void* p : bag) (void)hipFree(p); bag.clear(); }
 
 // A context holds at most one device copy of a scene; the copy knows its holders (rt_update_scene waits for them and reconfigures them).
@@ -295,6 +314,35 @@ static int persist_blocks(const RtCtx* c, int stage, int perCU, int tuneBlocks)
     return g;
 }
 
+// What shares a CU when the lanes of a group run side by side: the traversal grids of some lanes with a k_shade workgroup of another
+// (its grid is one workgroup per CU; a lane spends about a quarter of its time there, so with three lanes in flight one is resident about
+// half the time).  *perCU: the workgroups of the stage's persistent kernel, with a top table of `topLevels` levels, that fit a CU beside ONE
+// k_shade workgroup of this context's instantiation - by LDS, by the VGPR file (512 per lane and SIMD, allocated in eights; a workgroup of
+// 256 threads puts one wave on each SIMD) and by the eight wave slots of a SIMD, capped at what the hardware admits of the kernel anyway.
+// *shadeLds: k_shade's static LDS.  Footprints come from the code objects, not from constants; a CU hands its LDS out in blocks of 320
+// dwords, which decides at these sizes (measured, tools/lab/lds_census.hip: beside 26,688 B five workgroups of 22,528 B, beside 24,908 B six).
+static constexpr size_t kLdsBlock = 1280;
+static int beside_shade(const RtCtx* c, int stage, int topLevels, int* perCU, int* shadeLds)
+{
+    const TraceLaunch L = trace_launch(c, stage, stage == ST_CONNECT ? 0 : 1, false, c->nPix, topLevels);
+    hipFuncAttributes shade{}, trav{};
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, c->cfg.device));
+    HIPCHK(hipFuncGetAttributes(&shade, (const void*)c->kShade));
+    HIPCHK(hipFuncGetAttributes(&trav, (const void*)L.persist));
+    auto alloc = [](int regs) { return std::max(8, (regs + 7) / 8 * 8); };
+    const size_t ldsCU = std::max(prop.maxSharedMemoryPerMultiProcessor, prop.sharedMemPerBlock);
+    auto blocks = [](size_t bytes) { return (bytes + kLdsBlock - 1) / kLdsBlock * kLdsBlock; };
+    const size_t travLds = blocks(trav.sharedSizeBytes + L.lds), shadeLdsCU = blocks(shade.sharedSizeBytes);
+    const int shadeWaves = std::max(1, c->shadeTile / kBlock);   // per SIMD
+    const int byLds = ldsCU > shadeLdsCU && travLds > 0 ? (int)((ldsCU - shadeLdsCU) / travLds) : 0;
+    const int byVgpr = (512 - shadeWaves * alloc(shade.numRegs)) / alloc(trav.numRegs);
+    const int bySlots = 8 - shadeWaves;
+    *perCU = std::max(0, std::min(std::min(byLds, byVgpr), std::min(bySlots, stage == ST_CONNECT ? kAdmitAnySgpr : kAdmit96Sgpr)));
+    *shadeLds = (int)shade.sharedSizeBytes;
+    return RT_OK;
+}
+
 // ---- profiling brackets --------------------------------------------------------------
 // Stage timing: a fixed ring of HIP event pairs on the context's stream.  Recording never forces a device sync: when the ring
 // wraps, the oldest pair is harvested (it completed thousands of launches ago; if not, the HOST waits on that one event while the
@@ -389,7 +437,7 @@ extern "C" int rt_create(const RtConfig* cfg, RtCtx** out)
     {   // k_shade: as many workgroups as the CUs hold at once.  Its ordered scan does not depend on that (tiles go by ticket to
         // running workgroups), so the size only matters for speed.  The occupancy query knows the VGPR, LDS and wave-slot limits
         // but not the SGPR file: 256-thread workgroups are admitted up to min(query, 8, 800 / (ceil16(sgprs) + 16)) per CU
-        // (MI355X_MICROARCH.md, residency) = 6 for any kernel (<= 112 SGPRs), 7 up to 96 SGPRs.  k_shade: 2 workgroups of 512 threads (registers, 78 KB LDS).
+        // (MI355X_MICROARCH.md, residency) = 6 for any kernel (<= 112 SGPRs), 7 up to 96 SGPRs.  k_shade: 2 workgroups of 512 threads (registers; 49.8 KB of LDS each).
         hipDeviceProp_t prop; int perCU = 0;
         HIPCHK(hipGetDeviceProperties(&prop, c.device));
         ctx->shadeTile = c.shade_blocks_per_cu > 0 ? 256 : kTile;
@@ -579,14 +627,23 @@ static int configure_traversal(RtCtx* ctx)
         // alone, 22 KB of stack columns x 7 workgroups leave room for three levels) that costs more than the deeper levels give, while
         // contexts that share the GPU run fewer workgroups per CU and lose none with six.  So without the knob each stage gets the
         // deepest table with which it keeps the workgroups per CU it has without one.
+        // The lanes of a group (persist_blocks_per_cu > 0) do not have the CU to themselves: their few workgroups sit there with those of
+        // the other lanes and, about half the time, with a k_shade workgroup.  What the table must not cost them is a place beside that
+        // workgroup (beside_shade; EXPERIMENTS.md (60)): the deepest table with which as many fit there as with none.
         if (topAuto) for (int stage : { ST_EXTEND, ST_CONNECT }) {
             PersistTune& t = stage == ST_CONNECT ? ctx->tuneConnect : ctx->tune;
-            int q = 0, lv = t.topLevels;
+            int q = 0, lv = t.topLevels, beside = 0, shadeLds = 0;
+            const bool shared = ctx->cfg.persist_blocks_per_cu > 0;
             if (const int rc = persist_query(ctx, stage, 0, &q)) return rc;
             const int base = persist_blocks(ctx, stage, q, tuneBlocks);
+            if (shared) { if (const int rc = beside_shade(ctx, stage, 0, &beside, &shadeLds)) return rc; }
             for (; lv > 0; lv--) {
                 if (const int rc = persist_query(ctx, stage, lv, &q)) return rc;
-                if (persist_blocks(ctx, stage, q, tuneBlocks) == base) break;
+                if (persist_blocks(ctx, stage, q, tuneBlocks) != base) continue;
+                if (!shared) break;
+                int fit = 0;
+                if (const int rc = beside_shade(ctx, stage, lv, &fit, &shadeLds)) return rc;
+                if (fit >= beside) break;
             }
             t.topLevels = lv;
         }

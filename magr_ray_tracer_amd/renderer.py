@@ -174,6 +174,13 @@ class Device:
         self._chk(self._lib.rt_top_levels(self._h, C.byref(e), C.byref(c)))
         return int(e.value), int(c.value)
 
+    def shade_footprint(self):
+        """(lds_bytes, traversal_beside): the static LDS of a k_shade workgroup of this context, and how many workgroups of its
+        persistent extend kernel (no top table) fit a CU beside one (rt_shade_footprint)."""
+        b, t = C.c_int32(0), C.c_int32(0)
+        self._chk(self._lib.rt_shade_footprint(self._h, C.byref(b), C.byref(t)))
+        return int(b.value), int(t.value)
+
     @property
     def builtins(self):
         """The context's arithmetic as resolved by the library (rt_builtins): _lib.BUILTINS_IEEE or _lib.BUILTINS_REFERENCE."""
