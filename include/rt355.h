@@ -125,6 +125,10 @@ int rt_top_levels(RtCtx* ctx, int32_t* extend, int32_t* connect);
  * attributes (0 where no persistent kernel runs).  For a context that shares the GPU (RtConfig.persist_blocks_per_cu > 0) the automatic
  * rt_top_levels are the deepest tables that keep this number. */
 int rt_shade_footprint(RtCtx* ctx, int32_t* ldsBytes, int32_t* traversalBeside);
+/* k_shade's staged tables.  *capacityRows: the 16-byte LDS rows reserved for them; a light takes six, a material three.  *staged: 1 if
+ * this context's k_shade launches read the uploaded scene's light records and materials from LDS - all of both fit the rows - and 0 if
+ * they read them from global memory (the scene needs more rows, or RT355_SHADE_TABLES=0).  The results are the same bits either way. */
+int rt_shade_tables(RtCtx* ctx, int32_t* capacityRows, int32_t* staged);
 
 /* new Buffer(...) x11 + new Kernel(...) x6 (renderer.cpp:145-157, :218-223). */
 int rt_create(const RtConfig* cfg, RtCtx** out);

@@ -165,6 +165,16 @@ extern "C" int rt_shade_footprint(RtCtx* ctx, int32_t* ldsBytes, int32_t* traver
     return RT_OK;
 }
 
+extern "C" int rt_shade_tables(RtCtx* ctx, int32_t* capacityRows, int32_t* staged)
+{
+    if (!ctx || !capacityRows || !staged) return fail(RT_E_INVALID, "rt_shade_tables: null argument");
+    if (!ctx->sceneLoaded) return fail(RT_E_INVALID, "rt_shade_tables: no scene uploaded");
+    if (const int rc = sync_scene_config(ctx)) return rc;
+    *capacityRows = kShadeTableRows;
+    *staged = ctx->var.shadeTables != 0 && shade_tables_fit(ctx->sc.nLights, ctx->sc.nMats);   // k_shade's own rule, from the arguments it is launched with
+    return RT_OK;
+}
+
 static void free_bag(std::vector<void*>& bag) { for (void* p : bag) (void)hipFree(p); bag.clear(); }
 
 // A context holds at most one device copy of a scene; the copy knows its holders (rt_update_scene waits for them and reconfigures them).
@@ -433,7 +443,8 @@ extern "C" int rt_create(const RtConfig* cfg, RtCtx** out)
     ctx->firstPixel = c.y0 * c.width;
     ctx->gridMax = (ctx->nPix * std::max(1, c.max_bounces) + kBlock - 1) / kBlock; // connect may cover max_bounces*nPix shadow rays
     ctx->gridMax = std::max(ctx->gridMax, 4096);                                    // and the persistent grid (<= 256 CUs x 8 blocks)
-    ctx->var = DevVariant{ c.shading, c.sampling, c.accel, c.russian_roulette ? 1 : 0, c.filter_fireflies ? 1 : 0, c.max_bounces };
+    ctx->var = DevVariant{ c.shading, c.sampling, c.accel, c.russian_roulette ? 1 : 0, c.filter_fireflies ? 1 : 0, c.max_bounces, 1 };
+    if (const char* t = getenv("RT355_SHADE_TABLES")) ctx->var.shadeTables = atoi(t) != 0;   // 0: k_shade reads lights and materials from global memory (A/B runs)
     {   // k_shade: as many workgroups as the CUs hold at once.  Its ordered scan does not depend on that (tiles go by ticket to
         // running workgroups), so the size only matters for speed.  The occupancy query knows the VGPR, LDS and wave-slot limits
         // but not the SGPR file: 256-thread workgroups are admitted up to min(query, 8, 800 / (ceil16(sgprs) + 16)) per CU
@@ -680,7 +691,7 @@ static int adopt_scene(RtCtx* ctx)
     const SceneArrays& a = b.sc;
     auto f4 = [](const RtFloat4* p) { return (const float4*)p; };
     ctx->sc = DevScene{ a.prims, a.mats, f4(a.tex), a.lights, a.bvh2, a.bvh4, a.primIdx, a.tlas, a.blas, f4(a.pairs), f4(a.triRecs), a.rootEntry, f4(a.shadeRecs),
-                        f4(a.tlasPairs), f4(a.instRecs), a.tlasRoot, f4(a.tlasPairsP), a.tlasRootP, f4(a.lightRecs), f4(a.quads), a.nLights, a.nPrims, a.nBlas, a.nTex };
+                        f4(a.tlasPairs), f4(a.instRecs), a.tlasRoot, f4(a.tlasPairsP), a.tlasRootP, f4(a.lightRecs), f4(a.quads), a.nLights, a.nPrims, a.nBlas, a.nTex, a.nMats };
     ctx->layout = b.layout; ctx->stackEntries = b.stackEntries; ctx->tlasDepth = b.tlasDepth; ctx->nInterior = b.nInterior; ctx->singleBlas = b.singleBlas;
     const int rc = configure_traversal(ctx);
     if (rc == RT_OK) ctx->sceneGen = b.generation;

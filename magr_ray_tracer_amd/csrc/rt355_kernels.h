@@ -60,6 +60,7 @@ struct DevScene {
     const float4*        lightRecs;  // [nLights][8]  what NEE needs of light li in one place: objData[0..63], {objType, area}, emittance of its material
     const float4*        quads;      // [nNodes][8]  layout 1 of the BVH4: four child boxes + four encoded child entries (128 B)
     int32_t nLights, nPrims, nBlas, nTex;
+    int32_t nMats;                   // records of `mats` (k_shade stages the whole table or none of it)
 };
 struct DevQueues {
     // ray queues (compacted), capacity nPix each; bounce b lives in set b & 1 (shade reads one, writes the other)
@@ -92,7 +93,7 @@ struct DevQueues {
 // round-robin, so an XCD then serves only 4 of the 32 classes, and two processes with two contexts each dead-locked within a few
 // frames: four partially resident k_shade grids, each holding the XCD another one needed.  tests: test_two_processes_with_two_lanes_...)
 static constexpr int kTicketClasses = 1, kTicketStride = 1024, kCursorWords = 2 * (RT_MAX_BOUNCES + 2);
-struct DevVariant { int32_t shading, sampling, accel, rr, fireflies, maxBounces; };
+struct DevVariant { int32_t shading, sampling, accel, rr, fireflies, maxBounces, shadeTables /* k_shade may stage its tables (RT355_SHADE_TABLES) */; };
 
 // meta.y bit layout
 static constexpr uint32_t kMetaBounceMask = 0xffu, kMetaInside = 0x100u, kMetaLastSpec = 0x200u;
@@ -1756,19 +1757,45 @@ RT_FORCEINLINE float4 texel(const DevScene& sc, long long i) { return i >= 0 && 
 // The scalar fields of a Material (bytes 32..63: specular, n1, n2, isDielectric | texIdx, texW, texH, isLight) fetched as two 16-byte
 // loads kept together; read field by field where they are used, the compiler turns them into a chain of up to eight dependent fetches.
 struct MatCtl { float specular, n1, n2; uint32_t isDielectric; int32_t texIdx, texW, texH; uint32_t isLight; };
-RT_FORCEINLINE MatCtl load_mat_ctl(const RtMaterial* mat)
+// k_shade's staged tables.  Every hit reads its Material's scalar fields, a diffuse hit its colour and, under NEE, six words of a light
+// record: three dependent round trips through the vector memory pipeline to two tables of a few hundred bytes.  A workgroup copies both
+// into LDS once per launch, from the arrays the launch is given (so upload, update and rebuild keep nothing fresh), when ALL of both fit
+// kShadeTableRows 16-byte rows; otherwise the launch reads them from global memory as before.  The rows are the same bits:
+//   [0, 6 L)             rows 0..5 of lightRecs[li] (k_light_recs; rows 6 and 7 are unused)
+//   [6 L, 6 L + 3 M)     bytes 0..15 (color) and 32..63 (what load_mat_ctl reads) of mats[m]
+// absorption (a ray inside glass) and emittance (a light is hit) stay global loads on their rare branches.  The capacity is what the
+// 256-slot NEE instantiation has left to the 25,600 B (twenty 1,280-B blocks) at which six traversal workgroups fit a CU beside it.
+static constexpr int kShadeTableRows = 42, kShadeLightRows = 6, kShadeMatRows = 3;
+__host__ __device__ inline bool shade_tables_fit(int32_t nLights, int32_t nMats)
 {
-    const uint4* p = reinterpret_cast<const uint4*>(mat);
-    const uint4 a = p[2], b = p[3];
+    return nLights >= 0 && nMats > 0 && (long long)kShadeLightRows * nLights + (long long)kShadeMatRows * nMats <= (long long)kShadeTableRows;
+}
+// (the rows are typed as LDS: with a plain pointer the compiler merges the two sides of `on` into one flat load of a selected address)
+typedef const __attribute__((address_space(3))) nt_v4f* lds_rows;
+struct ShadeTab { lds_rows rows; uint32_t mat0; bool on; };   // rows: the table in LDS; mat0: row of material 0; on: wave-uniform, fixed for the launch
+RT_FORCEINLINE float4 tab_row(const ShadeTab& tab, uint32_t i) { nt_v4f t = tab.rows[i]; return *(float4*)&t; }
+RT_FORCEINLINE MatCtl load_mat_ctl(const ShadeTab& tab, const RtMaterial* mat, int matIdx)
+{
+    uint4 a, b;
+    if (tab.on) {
+        const uint32_t r = tab.mat0 + (uint32_t)matIdx * kShadeMatRows;
+        const float4 fa = tab_row(tab, r + 1), fb = tab_row(tab, r + 2);
+        a = *(const uint4*)&fa; b = *(const uint4*)&fb;
+    } else {
+        const uint4* p = reinterpret_cast<const uint4*>(mat);
+        a = p[2]; b = p[3];
+    }
     asm volatile("" : : "v"(a.x), "v"(b.x));
     MatCtl m;
     m.specular = __uint_as_float(a.x); m.n1 = __uint_as_float(a.y); m.n2 = __uint_as_float(a.z); m.isDielectric = a.w & 0xffu;
     m.texIdx = (int32_t)b.x; m.texW = (int32_t)b.y; m.texH = (int32_t)b.z; m.isLight = b.w & 0xffu;
     return m;
 }
-template <bool REFB> RT_FORCEINLINE float4 albedo_of(const DevScene& sc, const RtPrimitive* prim, const RtMaterial* mat, const MatCtl& mc, const SRay& ray) // primitives.cl:107-148
+template <bool REFB> RT_FORCEINLINE float4 albedo_of(const DevScene& sc, const ShadeTab& tab, const RtPrimitive* prim, const RtMaterial* mat, const MatCtl& mc, const SRay& ray) // primitives.cl:107-148
 {
-    float4 albedo = ld4(mat->color);
+    float4 albedo;
+    if (tab.on) albedo = tab_row(tab, tab.mat0 + (uint32_t)ray.matIdx * kShadeMatRows);
+    else albedo = ld4(mat->color);
     const int texIdx = mc.texIdx;
     if (texIdx != -1) {
         const int texW = mc.texW, texH = mc.texH, type = prim->objType;
@@ -1871,11 +1898,11 @@ struct ShadowOut { float4 a, b, c; bool valid; };   // the record as q.sA/sB/sC 
 // neeShading (shading.cl:72-169) and kajiyaShading (:7-70) in one body; NEE selects the
 // light-sampling block and the lastSpecular rules.
 template <bool NEE, bool REFB>
-RT_FORCEINLINE float4 shade_hit(const DevScene& sc, const DevVariant& var, SRay& ray, uint32_t& seed, ExtRay& ext, ShadowOut& sh)
+RT_FORCEINLINE float4 shade_hit(const DevScene& sc, const ShadeTab& tab, const DevVariant& var, SRay& ray, uint32_t& seed, ExtRay& ext, ShadowOut& sh)
 {
     const RtPrimitive* prim = sc.prims + ray.prim;
     const RtMaterial* mat = sc.mats + ray.matIdx;
-    const MatCtl mc = load_mat_ctl(mat);
+    const MatCtl mc = load_mat_ctl(tab, mat, ray.matIdx);
     if (mc.isLight) {
         if (NEE && !ray.lastSpec) return splat(0.0f);
         return mul4(ray.inten, ld4(mat->emittance));
@@ -1890,15 +1917,17 @@ RT_FORCEINLINE float4 shade_hit(const DevScene& sc, const DevVariant& var, SRay&
         ext = reflect_ray(ray);
         if (NEE) ext.lastSpec = true;
     } else {
-        const float4 albedo = albedo_of<REFB>(sc, prim, mat, mc, ray);
+        const float4 albedo = albedo_of<REFB>(sc, tab, prim, mat, mc, ray);
         const float4 BRDF = muls(albedo, kInvPi);
         if (NEE && sc.nLights > 0) {
             uint32_t li = f2u_gpu(floorf(rnd_abs(seed) * (float)sc.nLights));
             if (li >= (uint32_t)sc.nLights) li = (uint32_t)sc.nLights - 1; // reference reads out of bounds here (draw == 1.0)
             // One round trip for everything NEE reads of the light (round 1 walked lights[li] -> Primitive.objType -> vertices -> normal ->
             // matIdx / area -> Material.emittance: six dependent fetches); same arithmetic as getRandomPoint / getNormal (primitives.cl:91-189).
-            const float4* LR = sc.lightRecs + (size_t)li * 8;
-            const float4 l0 = LR[0], l1 = LR[1], l2 = LR[2], l3 = LR[3], l4 = LR[4], l5 = LR[5];
+            // (from the staged table where the launch has one: the same six rows, an LDS read instead of the third dependent round trip)
+            float4 l0, l1, l2, l3, l4, l5;
+            if (tab.on) { const uint32_t r = li * (uint32_t)kShadeLightRows; l0 = tab_row(tab, r); l1 = tab_row(tab, r + 1); l2 = tab_row(tab, r + 2); l3 = tab_row(tab, r + 3); l4 = tab_row(tab, r + 4); l5 = tab_row(tab, r + 5); }
+            else { const float4* LR = sc.lightRecs + (size_t)li * 8; l0 = LR[0]; l1 = LR[1]; l2 = LR[2]; l3 = LR[3]; l4 = LR[4]; l5 = LR[5]; }
             asm volatile("" : : "v"(l0.x), "v"(l1.x), "v"(l2.x), "v"(l3.x), "v"(l4.x), "v"(l5.x));
             const int ltype = __float_as_int(l4.x);
             const float larea = l4.y;
@@ -2003,7 +2032,7 @@ __global__ __launch_bounds__(TILE, 4) void k_shade(DevScene sc, DevQueues q, Dev
     // (one array per width, rows at constant offsets from the lane's slot, and the slot made opaque where it is used: a row's address is
     // then an immediate of the LDS instruction instead of a loop-invariant VGPR per row, of which the kernel has none to spare)
     enum { P_EXT_O, P_EXT_D, P_EXT_I, P_SH_A, P_SH_C, P_ROWS4 = NEE ? 5 : 3 };   // (only NEE emits shadow rays)
-    __shared__ float4 sPark4[P_ROWS4 * TILE];
+    __shared__ float4 sPark4[P_ROWS4 * TILE + kShadeTableRows];   // behind the parking rows: the staged light and material tables (ShadeTab)
     __shared__ float2 sShB[NEE ? TILE : 1];      // sB.xy
     __shared__ uint2 sPixZ[TILE];      // { pixel = meta.x = bits of sB.w, bits of sB.z }
     __shared__ uint8_t sExtM[TILE];    // park_meta(meta.y)
@@ -2091,12 +2120,24 @@ __global__ __launch_bounds__(TILE, 4) void k_shade(DevScene sc, DevQueues q, Dev
     const uint32_t cls = blockIdx.x % (uint32_t)kTicketClasses;
     int32_t* ticket = q.shadeTicket + ((size_t)bounce * kTicketClasses + cls) * kTicketStride;
     uint32_t tkNext = 0;                                   // thread 0: ticket of the next tile (drawn while this one is shaded)
+    // The staged tables: one thread per row takes its row now and puts it into LDS behind the first tile's fetch, so the copy costs no
+    // round trip of its own and no barrier but the one the ticket needs anyway.  Whether the launch stages is decided here, once, from
+    // kernel arguments: all lights and all materials fit, or nothing is staged.
+    const ShadeTab tab = { (lds_rows)(sPark4 + P_ROWS4 * TILE), (uint32_t)kShadeLightRows * (uint32_t)sc.nLights, var.shadeTables != 0 && shade_tables_fit(sc.nLights, sc.nMats) };
+    const uint32_t tabRows = tab.on ? tab.mat0 + (uint32_t)kShadeMatRows * (uint32_t)sc.nMats : 0u;   // <= kShadeTableRows < TILE
+    float4 tabRow = splat(0.0f);
+    if (threadIdx.x < tabRows) {
+        const uint32_t r = threadIdx.x, m = r - tab.mat0;
+        if (r < tab.mat0) tabRow = sc.lightRecs[(size_t)(r / kShadeLightRows) * 8 + r % kShadeLightRows];
+        else tabRow = reinterpret_cast<const float4*>(sc.mats + m / kShadeMatRows)[m % kShadeMatRows ? m % kShadeMatRows + 1 : 0];   // words 0, 2, 3 of the 80 bytes
+    }
     if (threadIdx.x == 0) sTicket = (uint32_t)atomicAdd(ticket, 1);
     __syncthreads();
     uint32_t tile = sTicket * (uint32_t)kTicketClasses + cls;
-    __syncthreads();                                       // sTicket is rewritten inside the loop
     TileIn in;
     fetch(tile, in);
+    if (threadIdx.x < tabRows) sPark4[P_ROWS4 * TILE + threadIdx.x] = tabRow;
+    __syncthreads();                                       // sTicket is rewritten inside the loop; the tables are complete
     for (; tile < numTiles; par ^= 1) {
         const int i = (int)tile * TILE + threadIdx.x;
         if (threadIdx.x == 0) {
@@ -2135,7 +2176,7 @@ __global__ __launch_bounds__(TILE, 4) void k_shade(DevScene sc, DevQueues q, Dev
                                                       : mk4(rec.x, rec.y, rec.z, (tag & 0x08000000u) ? -0.0f : 0.0f);   // flipped normals carry w = -0
                 if (dot4(ray.N, neg4(ray.D)) < 0) ray.N = muls(ray.N, -1.0f);
                 uint32_t seed = in.seed;
-                float4 color = shade_hit<NEE, REFB>(sc, var, ray, seed, ext, sh);
+                float4 color = shade_hit<NEE, REFB>(sc, tab, var, ray, seed, ext, sh);
                 q.seeds[i] = seed;
                 color = firefly<REFB>(var.fireflies, color);
                 // one path per pixel and launch: the add is race-free; adding an exact zero is skipped

@@ -304,7 +304,7 @@ int scenedev::upload_scene(SceneBag& b, int accel, int extendVariant, const Host
     const bool leafRoot = tlas[0].leftRight == 0;
     sc.tlasRoot = leafRoot ? (refit::kLeafBit | tlas[0].BLASidx) : 0u;
     sc.tlasRootP = leafRoot ? (refit::kTagInst | tlas[0].BLASidx) : refit::kTagTlas;
-    sc.nLights = nLights; sc.nPrims = nPrims; sc.nBlas = nBlas; sc.nTex = nTexels;
+    sc.nLights = nLights; sc.nPrims = nPrims; sc.nBlas = nBlas; sc.nTex = nTexels; sc.nMats = nMats;
     // ---- bind: the copy's facts, and what updates and rebuilds need of this upload
     b.sc = sc;
     b.layout = layout; b.stackEntries = stackEntries; b.tlasDepth = tlasDepth; b.nInterior = (int)pairNode.size(); b.singleBlas = leafRoot;

@@ -44,7 +44,7 @@ struct SceneArrays {
     RtTLASNode* tlas; RtBVHInstance* blas;
     RtFloat4 *pairs, *triRecs; uint32_t* rootEntry; RtFloat4 *shadeRecs, *tlasPairs, *instRecs; uint32_t tlasRoot;
     RtFloat4* tlasPairsP; uint32_t tlasRootP; RtFloat4 *lightRecs, *quads;
-    int32_t nLights, nPrims, nBlas, nTex;
+    int32_t nLights, nPrims, nBlas, nTex, nMats;
 };
 
 // The device copy of a scene (uploaded arrays + derived layouts).  Contexts that render the same scene - sample-stream lanes, the

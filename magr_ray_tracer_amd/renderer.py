@@ -181,6 +181,13 @@ class Device:
         self._chk(self._lib.rt_shade_footprint(self._h, C.byref(b), C.byref(t)))
         return int(b.value), int(t.value)
 
+    def shade_tables(self):
+        """(capacity_rows, staged): the 16-byte LDS rows k_shade reserves for the light records (six each) and materials (three each),
+        and whether this context's launches read the uploaded scene's from there (rt_shade_tables)."""
+        r, s = C.c_int32(0), C.c_int32(0)
+        self._chk(self._lib.rt_shade_tables(self._h, C.byref(r), C.byref(s)))
+        return int(r.value), bool(s.value)
+
     @property
     def builtins(self):
         """The context's arithmetic as resolved by the library (rt_builtins): _lib.BUILTINS_IEEE or _lib.BUILTINS_REFERENCE."""
