@@ -382,9 +382,14 @@ int rt_debug_get_scene_array(RtCtx* ctx, int32_t which, void* out, int64_t capac
  * sample stream firstStream + m (seeds = that slice of the reference's host xorshift32 stream, renderer.cpp:195-196); the group's
  * accumulator is the sum of the lanes' accumulators in lane order and, after k frames in all, holds k samples per pixel - prep()
  * divides by k exactly as with one stream (postproc.cl:71).  A group of ONE lane is the reference's single Renderer bit for bit.
- * HIP runs kernels of streams that share a hardware queue one after the other (GPU_MAX_HW_QUEUES, the process's own setting):
- * rt_group_create measures which of the group's streams really run side by side (S of them: rt_group_concurrency) and writes one
- * line to stderr when S is fewer than `lanes`.  Frame j of the group is lane (j mod lanes)'s sample, issued on worker stream j mod S:
+ * HIP runs kernels of streams that share a hardware queue one after the other, and keeps one pool of up to GPU_MAX_HW_QUEUES queues
+ * (the process's own setting, default 4) per stream PRIORITY; the process's other streams - the null stream, a framework's - sit in the
+ * normal pool.  rt_group_create measures which of the lanes' streams really run side by side (S of them: rt_group_concurrency), in the
+ * normal class first and, when some lanes share a queue there, with the lanes' streams replaced by streams of the lowest and of the
+ * highest priority; it keeps the class with the most (normal at a tie, then the lowest: rt_group_stream_class) and writes one line to
+ * stderr when S is still fewer than `lanes`.  All lanes of a group have equal priority among themselves; a single context (rt_create)
+ * always has a normal stream.  RT355_GROUP_PRIORITY=normal|low|high forces a class, =mixed lets the lanes left over by the best class
+ * take streams of the others (rt_group_stream_class: 2), =auto or unset is the above.  Frame j of the group is lane (j mod lanes)'s sample, issued on worker stream j mod S:
  * with S < lanes a lane's frames move between those S streams, strictly in order (each waits on an event recorded behind the lane's
  * last work), so that no queue renders more frames than another.  rt_stream of a lane is the stream its last frame ran on; work the
  * caller queues there lands behind it.  The environment variable RT355_GROUP_STREAMS=k caps S at k (tests, A/B runs). */
@@ -393,6 +398,10 @@ int rt_group_create(const RtConfig* cfg, int32_t lanes, RtGroup** out);      /* 
 int rt_group_destroy(RtGroup* g);
 int rt_group_lanes(RtGroup* g);
 int rt_group_concurrency(RtGroup* g);                                        /* S: streams measured to run concurrently at creation     */
+int rt_group_stream_class(RtGroup* g);                                       /* priority class of the lanes' streams: -1 low, 0 normal,
+                                                                              * 1 high, 2 mixed                                         */
+int rt_group_class_concurrency(RtGroup* g, int32_t cls);                     /* S as measured in class -1, 0 or 1 at creation; -1 when
+                                                                              * that class was not tried                                */
 RtCtx* rt_group_lane(RtGroup* g, int32_t m);                                 /* lane m's context (counters, stage times, debug stages)  */
 uint64_t rt_group_frames(RtGroup* g);                                        /* frames rendered by all lanes since the last reset       */
 int rt_group_upload_scene(RtGroup* g,

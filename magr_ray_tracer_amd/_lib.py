@@ -108,7 +108,7 @@ DEVICE_SYMBOLS = [
     "rt_debug_math_sweep", "rt_debug_math_mode", "rt_debug_math_sweep_mode", "rt_validate_scene", "rt_build_bvh2", "rt_build_bvh2_sah", "rt_debug_sah_phases", "rt_build_bvh2_sbvh", "rt_debug_sbvh_phases", "rt_update_scene", "rt_group_update_scene", "rt_debug_get_scene_array",
     "rt_rebuild_scene", "rt_group_rebuild_scene", "rt_blas_ranges", "rt_debug_rebuild_allocations",
     "rt_build_bvh4", "rt_upload_scene_bvh2", "rt_group_upload_scene_bvh2",
-    "rt_group_create", "rt_group_destroy", "rt_group_lanes", "rt_group_concurrency", "rt_group_lane", "rt_group_frames", "rt_group_upload_scene", "rt_group_share_scene",
+    "rt_group_create", "rt_group_destroy", "rt_group_lanes", "rt_group_concurrency", "rt_group_stream_class", "rt_group_class_concurrency", "rt_group_lane", "rt_group_frames", "rt_group_upload_scene", "rt_group_share_scene",
     "rt_group_seed", "rt_group_reset", "rt_group_render", "rt_group_synchronize", "rt_group_sum", "rt_group_read_accum", "rt_group_focus",
     "rt_group_postproc"]
 HOST_SYMBOLS = [
@@ -227,6 +227,8 @@ def _bind_device(lib):
         lib.rt_group_destroy.argtypes = [vp]
         lib.rt_group_lanes.argtypes = [vp]
         lib.rt_group_concurrency.argtypes = [vp]
+        lib.rt_group_stream_class.argtypes = [vp]
+        lib.rt_group_class_concurrency.argtypes = [vp, i32]
         lib.rt_group_lane.argtypes = [vp, i32]
         lib.rt_group_lane.restype = vp
         lib.rt_group_frames.argtypes = [vp]

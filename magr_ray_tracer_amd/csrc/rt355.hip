@@ -1377,9 +1377,10 @@ extern "C" int rt_postproc(RtCtx* ctx, int32_t frames, float vignette, float gam
 // tails of one lane's launches are filled by the others' kernels.  The group's accumulator is the sum of its lanes' accumulators in
 // lane order.  (Reference: one Renderer, one in-order queue, renderer.cpp:26-94; the group is what stands behind Renderer::Tick here.)
 //
-// HIP maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4, the null stream included) and runs kernels of streams
-// that share one after the other.  The library leaves that setting to the process that loads it; rt_group_create MEASURES how many of
-// its streams really run side by side, so a caller is told instead of silently serialised.
+// HIP maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues per stream priority (default 4; the normal pool holds the null
+// stream too) and runs kernels of streams that share one after the other.  The library leaves that setting to the process that loads
+// it; rt_group_create MEASURES how many of its streams really run side by side - per priority class, choose_streams - so a caller is
+// told instead of silently serialised.
 //
 // Fewer concurrent streams than lanes must not leave a lane's frames queued behind another's: two lanes on one queue render twice
 // as many frames in series as the rest, which finish at half-time and leave the chip to one context (4 lanes on 3 queues: 41 % of
@@ -1408,8 +1409,19 @@ __global__ __launch_bounds__(kBlock) void k_sum_lanes(float4* out, const float4*
     out[i] = s;
 }
 
+// The stream classes of a group: HIP's stream priorities.  rt_group_stream_class reports one of these, or kClassMixed.
+enum { kClassLow = -1, kClassNormal = 0, kClassHigh = 1, kClassMixed = 2 };
+// Between the two classes beside normal, at equal S: the lower one, so that a renderer embedded in an application yields to that
+// application's other GPU work (the bench tells them apart by no more than its spread, EXPERIMENTS.md (62))
+static constexpr int kPreferClass = kClassLow;
+// Lanes that no single class runs side by side take streams of the other classes only on request (RT355_GROUP_PRIORITY=mixed): workers
+// of unequal priority finish their equal shares of frames at different times
+static constexpr bool kMixedByDefault = false;
+
 struct RtGroup {
     std::vector<RtCtx*> lane;
+    std::vector<int> laneClass;         // one per lane: the class of its home stream
+    int seen[3] = { -1, -1, -1 };       // S as measured per class (low, normal, high) at creation; -1: not measured
     float4* sum = nullptr;              // lane-ordered sum of the lanes' accumulators (own buffer)
     std::vector<hipEvent_t> done;       // one per lane: "this lane's queued frames are finished", for the sum on lane 0's stream
     uint64_t frames = 0;                // frames rendered by all lanes since the last reset (= the divisor of prep())
@@ -1431,43 +1443,136 @@ static void group_free(RtGroup* g)
     if (g->sum) (void)hipFree(g->sum);
     delete g;
 }
-// Which of the group's streams execute concurrently: one single-wave kernel that naps for ~1 ms, on one stream alone and then on
-// every stream of a candidate set at once, both timed on the host.  Streams that share a hardware queue run their naps one after
-// the other, so a set whose naps take about as long as one nap runs side by side.  Greedy in lane order: lane 0, then each lane
-// whose stream keeps the set concurrent.  Measured, not predicted: which queue a stream lands on is the runtime's business.
-static std::vector<int> measure_workers(RtGroup* g)
+// Which streams execute concurrently: one single-wave kernel that naps for ~1 ms, on one stream alone and then on every stream of a
+// candidate set at once, both timed on the host.  Streams that share a hardware queue run their naps one after the other, so a set
+// whose naps take about as long as one nap runs side by side.  Greedy: `set` (its first stream, when empty: the first candidate) grows
+// by each candidate that keeps it concurrent; returns which candidates were taken.  Measured, not predicted: which queue a stream
+// lands on is the runtime's business.
+static std::vector<int> grow_concurrent(RtGroup* g, std::vector<hipStream_t>& set, const std::vector<hipStream_t>& cand)
 {
-    const int n = (int)g->lane.size();
-    std::vector<int> set{ 0 };
-    if (n <= 1) return set;
+    std::vector<int> taken;
+    size_t first = 0;
+    if (set.empty() && !cand.empty()) { set.push_back(cand[0]); taken.push_back(0); first = 1; }
+    if (first >= cand.size()) return taken;
     int rate = 0;
     if (hipDeviceGetAttribute(&rate, hipDeviceAttributeWallClockRate, g->lane[0]->cfg.device) != hipSuccess || rate <= 0) rate = 100000;   // kHz
     const long long ticks = (long long)rate;        // 1 ms
     int* sink = (int*)g->lane[0]->q.fault;          // never written (ticks >= 0)
-    auto run = [&](const std::vector<int>& lanes) {
+    auto run = [&](const std::vector<hipStream_t>& on) {
         const auto t0 = std::chrono::steady_clock::now();
-        for (int m : lanes) hipLaunchKernelGGL(k_spin, dim3(1), dim3(64), 0, g->lane[(size_t)m]->home, ticks, sink);
-        for (int m : lanes) (void)hipStreamSynchronize(g->lane[(size_t)m]->home);
+        for (hipStream_t s : on) hipLaunchKernelGGL(k_spin, dim3(1), dim3(64), 0, s, ticks, sink);
+        for (hipStream_t s : on) (void)hipStreamSynchronize(s);
         return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     };
     // the best of three each: a host thread that is descheduled for a millisecond must not read as a serialised stream
-    auto best = [&](const std::vector<int>& lanes) { float t = run(lanes); for (int k = 0; k < 2; k++) t = std::min(t, run(lanes)); return t; };
-    std::vector<int> all(n);
-    for (int m = 0; m < n; m++) all[(size_t)m] = m;
+    auto best = [&](const std::vector<hipStream_t>& on) { float t = run(on); for (int k = 0; k < 2; k++) t = std::min(t, run(on)); return t; };
+    std::vector<hipStream_t> all = set;
+    all.insert(all.end(), cand.begin() + (ptrdiff_t)first, cand.end());
     (void)run(all);                                  // warms the code object up on every stream
-    const float one = best(set);
-    if (one <= 0) return set;
-    for (int m = 1; m < n; m++) {
-        std::vector<int> cand = set; cand.push_back(m);
-        if (best(cand) < 1.5f * one) set = cand;     // serialised: >= 2 naps
+    const float one = best({ set[0] });
+    if (one <= 0) return taken;
+    for (size_t k = first; k < cand.size(); k++) {
+        std::vector<hipStream_t> with = set; with.push_back(cand[k]);
+        if (best(with) < 1.5f * one) { set = with; taken.push_back((int)k); }   // serialised: >= 2 naps
     }
-    return set;
+    return taken;
+}
+
+// Which streams the lanes' frames are issued on.  HIP keeps one pool of hardware queues PER STREAM PRIORITY, each up to the process's
+// limit, and the process's other streams (the null stream, a framework's) sit in the normal pool: lane streams of another priority
+// class can have that class's queues to themselves.  All lanes of a class have equal priority among themselves, and nothing
+// process-wide changes.  Which class gives the most concurrent workers is measured like everything else here:
+//   normal   the streams of rt_create, as for a single context
+//   low/high every lane's stream replaced by one of that priority
+//   auto     (unset) normal when every lane runs side by side there - no other stream is ever created then - or when no other class
+//            holds more workers; else the class with the most, kPreferClass at a tie
+//   mixed    auto, then the lanes left over try a stream of each other class (kMixedByDefault: auto does the same)
+// A lane's stream is replaced before anything but its creation work was queued: rt_create has synchronised that, and nothing else of
+// a context is bound to its stream (the stage events are recorded on ctx->stream at use).
+static int choose_streams(RtGroup* g, int want, bool mixed)
+{
+    const int n = (int)g->lane.size();
+    int least = 0, greatest = 0;
+    HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    const bool classes = least != greatest;   // (numerically, a lower value is a higher priority)
+    if (!classes && (want == kClassLow || want == kClassHigh)) return fail(RT_E_INVALID, "rt_group_create: RT355_GROUP_PRIORITY asks for a priority class, but this device has one stream priority only");
+    std::vector<hipStream_t> cls[3];           // [class + 1][lane]; normal: the lanes' own
+    for (RtCtx* c : g->lane) cls[1].push_back(c->home);
+    auto drop = [&](int k) { for (hipStream_t s : cls[k + 1]) if (s) (void)hipStreamDestroy(s); cls[k + 1].clear(); };
+    auto make = [&](int k) {
+        for (int m = 0; m < n; m++) {
+            hipStream_t s = nullptr;
+            const hipError_t e = hipStreamCreateWithPriority(&s, hipStreamNonBlocking, k == kClassLow ? least : greatest);
+            if (e != hipSuccess) { drop(k); return fail(RT_E_DEVICE, "rt_group_create: hipStreamCreateWithPriority failed: %s", hipGetErrorString(e)); }
+            cls[k + 1].push_back(s);
+        }
+        return (int)RT_OK;
+    };
+    std::vector<hipStream_t> set;              // the concurrent streams
+    std::vector<int> worker;                   // and whose they are
+    int bestClass = kClassNormal;
+    auto measure = [&](int k) {
+        std::vector<hipStream_t> s;
+        std::vector<int> w = grow_concurrent(g, s, cls[k + 1]);
+        g->seen[k + 1] = (int)w.size();
+        // a tie with normal keeps normal; between the other two, kPreferClass
+        if (set.empty() || w.size() > set.size() || (w.size() == set.size() && bestClass != kClassNormal && k == kPreferClass)) { set = s; worker = w; bestClass = k; }
+    };
+    if (want == kClassLow || want == kClassHigh) {
+        const int rc = make(want); if (rc != RT_OK) return rc;
+        measure(want);
+    } else {
+        measure(kClassNormal);
+        if (want != kClassNormal && classes && (int)set.size() < n)
+            for (int k : { kClassLow, kClassHigh }) {
+                const int rc = make(k); if (rc != RT_OK) { drop(kClassLow); return rc; }
+                measure(k);
+            }
+    }
+    std::vector<hipStream_t> home = cls[bestClass + 1];
+    g->laneClass.assign((size_t)n, bestClass);
+    if (mixed && classes && (int)set.size() < n) {   // (only the measured choice is extended, and it has tried every class by now)
+        for (int m = 0; m < n; m++) {
+            if (std::find(worker.begin(), worker.end(), m) != worker.end()) continue;
+            for (int k : { kClassNormal, kClassLow, kClassHigh }) {
+                if (k == bestClass) continue;
+                if (grow_concurrent(g, set, { cls[k + 1][(size_t)m] }).empty()) continue;
+                worker.push_back(m); home[(size_t)m] = cls[k + 1][(size_t)m]; g->laneClass[(size_t)m] = k;
+                break;
+            }
+        }
+    }
+    // every lane its stream; the streams of the classes not kept go, so that their hardware queues are released
+    for (int m = 0; m < n; m++) {
+        RtCtx* c = g->lane[(size_t)m];
+        for (int k = 0; k < 3; k++) if (!cls[k].empty() && cls[k][(size_t)m] == home[(size_t)m]) cls[k][(size_t)m] = nullptr;
+        if (c->home == home[(size_t)m]) continue;
+        cls[1][(size_t)m] = nullptr;
+        HIPCHK(hipStreamSynchronize(c->home));   // the naps
+        HIPCHK(hipStreamDestroy(c->home));
+        c->home = c->stream = home[(size_t)m];
+    }
+    cls[1].clear();                            // (what is left there is some lane's home)
+    drop(kClassLow); drop(kClassHigh);
+    g->worker = worker;
+    return RT_OK;
 }
 
 extern "C" int rt_group_create(const RtConfig* cfg, int32_t lanes, RtGroup** out)
 {
     if (!cfg || !out) return fail(RT_E_INVALID, "rt_group_create: null argument");
     if (lanes < 1 || lanes > kMaxLanes) return fail(RT_E_INVALID, "rt_group_create: lanes must be 1..%d", kMaxLanes);
+    int want = kClassNormal;
+    bool any = true, mixed = kMixedByDefault;   // any: the class is the measurement's choice
+    if (const char* t = getenv("RT355_GROUP_PRIORITY")) {   // forces a class (tests, A/B runs)
+        const std::string v(t);
+        if (v == "normal") any = false;
+        else if (v == "low") { any = false; want = kClassLow; }
+        else if (v == "high") { any = false; want = kClassHigh; }
+        else if (v == "mixed") mixed = true;
+        else if (v != "auto" && !v.empty()) return fail(RT_E_INVALID, "rt_group_create: RT355_GROUP_PRIORITY=%s is none of normal, low, high, auto, mixed", t);
+    }
+    if (!any) mixed = false;
     std::unique_ptr<RtGroup, void (*)(RtGroup*)> guard(new RtGroup(), group_free);
     RtGroup* g = guard.get();
     for (int m = 0; m < lanes; m++) {
@@ -1489,23 +1594,29 @@ extern "C" int rt_group_create(const RtConfig* cfg, int32_t lanes, RtGroup** out
     const size_t px = (size_t)cfg->width * cfg->height;
     if (hipMalloc((void**)&g->sum, px * sizeof(float4)) != hipSuccess) return fail(RT_E_NOMEM, "rt_group_create: hipMalloc of the group accumulator failed");
     HIPCHK(hipMemset(g->sum, 0, px * sizeof(float4)));
-    g->worker = measure_workers(g);
+    {
+        const int rc = choose_streams(g, any ? kClassMixed : want, mixed);
+        if (rc != RT_OK) return rc;
+    }
     if (const char* t = getenv("RT355_GROUP_STREAMS")) {   // at most this many workers (tests of the routing; A/B runs)
         const int k = atoi(t);
         if (k >= 1 && k < (int)g->worker.size()) g->worker.resize((size_t)k);
     }
     g->concurrent = (int)g->worker.size();
     // the persistent traversal grids (sized at scene upload) of S concurrent lanes: S grids beside each other.  2 per CU was tuned
-    // for four; 3 for three or fewer (profiles/r04_group_streams.txt)
+    // for four; 3 for three or fewer (profiles/r04_group_streams.txt; at S = 4 on today's kernels 2 and 3 are equal, r08_group_priority.txt)
     if (lanes > 1 && cfg->persist_blocks_per_cu == 0)
         for (RtCtx* c : g->lane) c->cfg.persist_blocks_per_cu = g->concurrent >= 4 ? 2 : 3;
     if (g->concurrent < lanes) {
         static bool warned = false;
         if (!warned) {
             warned = true;
-            fprintf(stderr, "librt355: %d lanes requested but only %d of their HIP streams run concurrently (GPU_MAX_HW_QUEUES=%s; HIP serialises streams that "
-                            "share a hardware queue)\n",
-                    lanes, g->concurrent, getenv("GPU_MAX_HW_QUEUES") ? getenv("GPU_MAX_HW_QUEUES") : "unset");
+            static const char* const name[] = { "low", "normal", "high", "mixed" };
+            const char* q = getenv("GPU_MAX_HW_QUEUES");
+            fprintf(stderr, "librt355: %d lanes requested but only %d of their HIP streams run concurrently (stream priority class: %s; measured per class: "
+                            "low %d, normal %d, high %d, -1 = not tried; HIP serialises streams that share a hardware queue and keeps up to "
+                            "GPU_MAX_HW_QUEUES=%s of them per priority class, the normal class's shared with the process's other streams)\n",
+                    lanes, g->concurrent, name[rt_group_stream_class(g) + 1], g->seen[0], g->seen[1], g->seen[2], q ? q : "4 (unset)");
         }
     }
     *out = guard.release();
@@ -1514,6 +1625,13 @@ extern "C" int rt_group_create(const RtConfig* cfg, int32_t lanes, RtGroup** out
 extern "C" int rt_group_destroy(RtGroup* g) { group_free(g); return RT_OK; }
 extern "C" int rt_group_lanes(RtGroup* g) { return g ? (int)g->lane.size() : 0; }
 extern "C" int rt_group_concurrency(RtGroup* g) { return g ? g->concurrent : 0; }
+extern "C" int rt_group_stream_class(RtGroup* g)
+{
+    if (!g || g->laneClass.empty()) return kClassNormal;
+    for (int k : g->laneClass) if (k != g->laneClass[0]) return kClassMixed;
+    return g->laneClass[0];
+}
+extern "C" int rt_group_class_concurrency(RtGroup* g, int32_t cls) { return g && cls >= kClassLow && cls <= kClassHigh ? g->seen[cls + 1] : -1; }
 extern "C" RtCtx* rt_group_lane(RtGroup* g, int32_t m) { return g && m >= 0 && m < (int)g->lane.size() ? g->lane[(size_t)m] : nullptr; }
 extern "C" uint64_t rt_group_frames(RtGroup* g) { return g ? g->frames : 0; }
 

@@ -381,6 +381,15 @@ class Group:
         """How many of the lanes' HIP streams were measured to run side by side when the group was created."""
         return int(self._lib.rt_group_concurrency(self._h))
 
+    def stream_class(self):
+        """The HIP stream priority class of the lanes' streams: "low", "normal", "high", or "mixed" (rt_group_stream_class)."""
+        return {-1: "low", 0: "normal", 1: "high", 2: "mixed"}[int(self._lib.rt_group_stream_class(self._h))]
+
+    def class_concurrency(self):
+        """{class: S as measured in it when the group was created}, for the classes that were tried (rt_group_class_concurrency)."""
+        seen = {name: int(self._lib.rt_group_class_concurrency(self._h, k)) for k, name in ((-1, "low"), (0, "normal"), (1, "high"))}
+        return {name: s for name, s in seen.items() if s >= 0}
+
     def frames(self):
         return int(self._lib.rt_group_frames(self._h))
 
