@@ -477,6 +477,55 @@ int rt_stage_generate(RtCtx* ctx, const RtCamera* cam, const RtSettings* s);    
 int rt_stage_extend(RtCtx* ctx, int32_t bounce, int32_t renderBVH);             /* wavefront.cl:35-75   */
 int rt_stage_shade(RtCtx* ctx, int32_t bounce);                                 /* wavefront.cl:76-142  */
 int rt_stage_connect(RtCtx* ctx, int32_t firstBounce, int32_t lastBounce);      /* wavefront.cl:144-201 */
+/* ---- queries: the caller's own rays against the bound scene ------------------------------------------------------------------------
+ * rt_trace intersects rays->n rays, read from DEVICE memory, with the scene the context holds, through the traversal kernels the
+ * context runs for that scene (rt_kernel_info), and writes the results to DEVICE memory.  The reference has no such call: its rays are
+ * born in generate and die in shade (wavefront.cl).  Ray i is origin (x, y, z) at rays->origin + i * originStride and direction at
+ * rays->dir + i * dirStride (bytes; 12: packed float3, 16: float4 whose w is ignored, 32: every second float4, ...).  Directions are
+ * used as given - not normalised, not validated; the sphere test assumes a unit D, as it does in the renderer.
+ *   RT_TRACE_CLOSEST, tmax NULL   hit[i] is, bit for bit, what rt_stage_extend leaves in its hit queue for a slot holding
+ *                      O = (x, y, z, 0), D = (x, y, z, 0): t, primIdx, u, v of the closest hit, the same on every traversal path
+ *                      (the nested loops, k_trace_persist, k_trace_persist_tlas with or without spill, k_trace_persist4,
+ *                      k_trace_persist4_tlas); a miss is {RT_REALLYFAR, -1, 0, 0}.  point[i] / normal[i] (optional) are I = O + t * D
+ *                      and the primitive's N at I flipped against D, as rt_debug_get_rays reports them - one device function computes
+ *                      both; zeros on a miss.
+ *   RT_TRACE_CLOSEST, tmax given   a pure function of the above: ray i reports the unbounded hit when its t < tmax[i], else a miss
+ *                      (the traversal is NOT started at tmax: at knife edges that would be another float32 function).
+ *   RT_TRACE_ANY       occluded[i] = 1 iff the context's connect traversal, given the shadow record {origin, tmax[i]} / {dir},
+ *                      accepts a primitive with t < tmax[i] (tmax NULL: RT_REALLYFAR), else 0.  Connect's visit order; the result does
+ *                      not depend on it.
+ * With 16-byte strides on 16-byte boundaries, CLOSEST, no tmax and nothing but `hit` wanted, the kernels read and write the caller's
+ * arrays directly; every other form passes through a load and a store kernel that stream the batch once each.
+ * A batch runs in passes of at most rt_trace_window(ctx) rays: min(2^22, what the context's per-workgroup tables hold - at least
+ * 2^20); the environment variable RT355_TRACE_WINDOW=k, read per call, lowers it (tests).  Only a pass, never n, must fit 32 bits.
+ * The call is asynchronous on the context's stream, in order with its renders and stage calls (a lane of a group: as the stage entry
+ * points); rt_synchronize waits for it, and the caller's arrays must stay valid until then.  It follows rt_update_scene /
+ * rt_rebuild_scene like a render does.  It leaves the frame alone: counters, stage times, accumulator, seeds, the queues behind
+ * rt_debug_get_rays / rt_debug_get_shadow and the next rt_render are what they would be without it (the query has count words, dequeue
+ * heads, counter rows and ray arrays of its own, allocated on first use - 48 bytes per ray of the largest pass that is not traced in
+ * place - and freed with the context).  n == 0 succeeds and touches nothing.
+ * RT_E_INVALID, before anything is launched or written: a null ctx / rays / out; no scene bound; an unknown mode; n < 0; a stride below
+ * 12 or not a multiple of 4; a missing required output (CLOSEST: hit, ANY: occluded) or origin / dir; an output the mode does not
+ * produce; origin / dir / tmax not on a 4-byte, hit / point / normal not on a 16-byte boundary; any pointer that
+ * hipPointerGetAttributes does not report as memory accessible from the context's device (device memory of that GPU, managed or
+ * pinned host memory), or whose allocation, where the runtime knows it, ends before the n-th element.  The message names the argument. */
+#define RT_TRACE_CLOSEST 0      /* the context's extend traversal  */
+#define RT_TRACE_ANY     1      /* the context's connect traversal */
+typedef struct RtHit { float t; int32_t primIdx; float u, v; } RtHit;   /* the queue's own 16-byte hit record */
+typedef struct RtRayBatch {
+    const void* origin; const void* dir;   /* DEVICE pointers; ray i's x,y,z at base + i * stride                    */
+    int64_t originStride, dirStride;       /* bytes; >= 12 and a multiple of 4 (12: packed float3, 16: float4, ...)   */
+    const float* tmax;                     /* DEVICE, n floats; NULL: RT_REALLYFAR for every ray                      */
+    int64_t n;
+} RtRayBatch;
+typedef struct RtTraceOut {                /* DEVICE pointers, n elements each; unused ones NULL                      */
+    RtHit*    hit;        /* CLOSEST (required there) */
+    RtFloat4* point;      /* CLOSEST, optional: I = O + t * D as extend leaves it in the reference's Ray              */
+    RtFloat4* normal;     /* CLOSEST, optional: N of the primitive at I, flipped against D, as extend leaves it       */
+    uint8_t*  occluded;   /* ANY (required there): 1 / 0                                                              */
+} RtTraceOut;
+int     rt_trace(RtCtx* ctx, int32_t mode, const RtRayBatch* rays, const RtTraceOut* out);
+int64_t rt_trace_window(RtCtx* ctx);   /* rays one pass takes; never 0 here (0 would mean: any n in one pass) */
 /* Ray queue of `bounce` as reference-layout Ray structs (I and N as extend leaves them). */
 int rt_debug_get_rays(RtCtx* ctx, int32_t bounce, RtRay* out, int32_t capacity, int32_t* n);
 /* Replace the ray queue of `bounce` by n <= (y1 - y0) * width caller records.  The kernels index the accumulator by a record's

@@ -52,12 +52,18 @@ BuildStats = np.dtype([("nodes", "<i4"), ("leaves", "<i4"), ("depth", "<i4"), ("
 SbvhStats = np.dtype([(n, "<i4") for n in ("nodes", "leaves", "n_idx", "depth", "spatial_splits", "prims_clipped", "forced_leaves", "levels")] +
                      [("sah_cost", "<f4"), ("device_ms", "<f4"), ("wall_ms", "<f4"), ("peak_refs", "<i4")])   # RtSbvhStats
 Bvh4Stats = np.dtype([(n, "<i4") for n in ("live_nodes", "levels", "stack_need", "largest_leaf")] + [("device_ms", "<f4"), ("wall_ms", "<f4")])   # RtBvh4Stats
+Hit = np.dtype([("t", "<f4"), ("primIdx", "<i4"), ("u", "<f4"), ("v", "<f4")])   # RtHit
+RayBatch = np.dtype([("origin", "<u8"), ("dir", "<u8"), ("originStride", "<i8"), ("dirStride", "<i8"), ("tmax", "<u8"), ("n", "<i8")])   # RtRayBatch
+TraceOut = np.dtype([("hit", "<u8"), ("point", "<u8"), ("normal", "<u8"), ("occluded", "<u8")])   # RtTraceOut
+TRACE_CLOSEST, TRACE_ANY = 0, 1
+REALLYFAR = np.float32(1e30)
 KernelInfo = np.dtype([(n, "<i4") for n in ("layout", "persist", "persist4", "stack_entries", "persist_grid", "persist_grid_connect",
                                              "shade_grid", "n_blas")])
 
 _SIZES = {"Ray": (Ray, 128), "ShadowRay": (ShadowRay, 96), "Material": (Material, 80), "Primitive": (Primitive, 128),
           "Camera": (Camera, 128), "Settings": (Settings, 40), "BVHNode2": (BVHNode2, 48), "BVHNode4": (BVHNode4, 160),
-          "BVHInstance": (BVHInstance, 68), "TLASNode": (TLASNode, 48), "BuildOptions": (BuildOptions, 16), "BuildStats": (BuildStats, 32), "SbvhStats": (SbvhStats, 48), "Bvh4Stats": (Bvh4Stats, 24), "ShadowRecord": (ShadowRecord, 48), "Config": (Config, 64)}
+          "BVHInstance": (BVHInstance, 68), "TLASNode": (TLASNode, 48), "BuildOptions": (BuildOptions, 16), "BuildStats": (BuildStats, 32), "SbvhStats": (SbvhStats, 48), "Bvh4Stats": (Bvh4Stats, 24), "ShadowRecord": (ShadowRecord, 48), "Config": (Config, 64),
+          "Hit": (Hit, 16), "RayBatch": (RayBatch, 48), "TraceOut": (TraceOut, 32)}
 for _n, (_d, _s) in _SIZES.items():
     assert _d.itemsize == _s, (_n, _d.itemsize, _s)
 
@@ -110,7 +116,7 @@ DEVICE_SYMBOLS = [
     "rt_build_bvh4", "rt_upload_scene_bvh2", "rt_group_upload_scene_bvh2",
     "rt_group_create", "rt_group_destroy", "rt_group_lanes", "rt_group_concurrency", "rt_group_stream_class", "rt_group_class_concurrency", "rt_group_lane", "rt_group_frames", "rt_group_upload_scene", "rt_group_share_scene",
     "rt_group_seed", "rt_group_reset", "rt_group_render", "rt_group_synchronize", "rt_group_sum", "rt_group_read_accum", "rt_group_focus",
-    "rt_group_postproc"]
+    "rt_group_postproc", "rt_trace", "rt_trace_window"]
 HOST_SYMBOLS = [
     "rth_last_error", "rth_scene_create", "rth_scene_destroy", "rth_add_material", "rth_add_texture", "rth_load_texture", "rth_add_sphere",
     "rth_add_plane", "rth_add_triangle", "rth_add_quad", "rth_add_triangles", "rth_build_blas", "rth_build_bvh4",
@@ -203,6 +209,9 @@ def _bind_device(lib):
         lib.rt_stage_connect.argtypes = [vp, i32, i32]
         lib.rt_debug_get_rays.argtypes = [vp, i32, vp, i32, C.POINTER(i32)]
         lib.rt_debug_set_rays.argtypes = [vp, i32, vp, i32]
+        lib.rt_trace.argtypes = [vp, i32, vp, vp]
+        lib.rt_trace_window.argtypes = [vp]
+        lib.rt_trace_window.restype = i64
         lib.rt_debug_get_shadow.argtypes = [vp, i32, i32, vp, i32, C.POINTER(i32)]
         lib.rt_debug_get_steps.argtypes = [vp, vp, i32, C.POINTER(i32)]
         lib.rt_debug_enable_steps.argtypes = [vp, i32]

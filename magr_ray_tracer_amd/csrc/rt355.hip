@@ -68,6 +68,9 @@ struct RtCtx {
     PersistTune tune{}, tuneConnect{}, tune4{};   // extend (BVH2), connect, extend (BVH4): set by configure_traversal
     float4* dPostF = nullptr; uchar4* dPostB = nullptr;   // post-processing outputs (lazy)
     int32_t* dSteps = nullptr;   // per-ray `steps` buffer, only bound while rt_debug_enable_steps is on
+    // rt_trace's own DevQueues view (lazy): count, cursor and fault words and a counter table that no frame reads or writes, and queue
+    // arrays for the batches that are not traced in the caller's arrays, grown to the largest pass so far
+    struct TraceView { DevQueues q{}; bool ready = false; std::vector<void*> words; float4* rays[3] = {}; size_t cap = 0; } tv;
     int shadeTile = kTile;  // k_shade tile = workgroup size: kTile (512), or 256 for contexts that share the GPU (RtConfig.shade_blocks_per_cu > 0)
     int shadeGrid = 1024;   // workgroups of k_shade (what the CUs hold at once; the kernel does not depend on it); set in rt_create
     // The instantiations of the kernels that reach one of the seven builtins, for this context's arithmetic (cfg.builtins, resolved to
@@ -509,6 +512,8 @@ static void ctx_free(RtCtx* ctx)   // every owned resource; safe on a partially 
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     scene_release(ctx); free_bag(ctx->queueAllocs);
     if (ctx->dRayIO) (void)hipFree(ctx->dRayIO);
+    free_bag(ctx->tv.words);
+    for (float4* p : ctx->tv.rays) if (p) (void)hipFree(p);
     if (ctx->dSpill) (void)hipFree(ctx->dSpill);
     if (ctx->dPostF) (void)hipFree(ctx->dPostF);
     if (ctx->dPostB) (void)hipFree(ctx->dPostB);
@@ -983,6 +988,137 @@ extern "C" int rt_stage_connect(RtCtx* ctx, int32_t b0, int32_t b1)
         hipLaunchKernelGGL(k_accumulate, dim3(std::min(grid_for(ctx->nPix).x, 2048u)), dim3(kBlock), 0, ctx->stream, ctx->q, b);
     ev_end(ctx, ST_ACCUM);
     HIPCHK(hipGetLastError());
+    return RT_OK;
+}
+
+// ---- rt_trace: the caller's rays through the context's traversal kernels ------------------------------------------------------------
+// The kernels take DevQueues by value, so a query hands them a view of its own: the caller's arrays where their layout is the queue's
+// (in place: the batch costs the traversal launches and a one-thread arming launch per pass), else the view's arrays between
+// k_trace_load and k_trace_store.  Nothing the frame owns is written: counts, cursors, the fault word and the counter rows are the
+// view's; the spill columns are the context's - scratch that no launch expects to survive the one before it, and every SPILL launch
+// runs on a persistent grid, which is what they are sized for.  The launches carry no profiling events: stage times stay the frame's.
+// A pass takes at most trace_window() rays: the counter rows (gridMax, one per workgroup of the nested kernels' 256-ray grid) bound it,
+// and 2^22 rays caps what the view's arrays can grow to (48 bytes per ray: 192 MB) while a 1080p queue still goes in one pass.
+static constexpr int64_t kTraceWindowMax = (int64_t)1 << 22;
+static int64_t trace_window(const RtCtx* ctx)
+{
+    int64_t w = std::min<int64_t>((int64_t)ctx->gridMax * kBlock, kTraceWindowMax);
+    if (const char* t = getenv("RT355_TRACE_WINDOW")) { const long long k = atoll(t); if (k > 0) w = std::min<int64_t>(w, k); }
+    return w;
+}
+extern "C" int64_t rt_trace_window(RtCtx* ctx)
+{
+    if (!ctx) return fail(RT_E_INVALID, "rt_trace_window: null context");
+    return trace_window(ctx);
+}
+// A pointer the kernels will follow for `bytes` bytes: it must be memory the context's device can reach (a host pointer passed by
+// mistake is an error message here, not a fault there), aligned for the accesses, and - where the runtime knows the allocation - inside it
+static int trace_pointer(const RtCtx* ctx, const char* name, const void* p, int64_t bytes, int align)
+{
+    if ((uintptr_t)p % (uintptr_t)align) return fail(RT_E_INVALID, "rt_trace: %s (%p) is not aligned to %d bytes", name, p, align);
+    hipPointerAttribute_t a{};
+    const hipError_t e = hipPointerGetAttributes(&a, p);
+    if (e != hipSuccess) (void)hipGetLastError();
+    const bool device = e == hipSuccess && a.type == hipMemoryTypeDevice && a.device == ctx->cfg.device;
+    const bool shared = e == hipSuccess && (a.type == hipMemoryTypeManaged || (a.type == hipMemoryTypeHost && a.devicePointer == p));
+    if (!device && !shared)
+        return fail(RT_E_INVALID, "rt_trace: %s (%p) is not memory accessible from device %d (a host pointer? memory of another GPU?)", name, p, ctx->cfg.device);
+    if (device) {
+        hipDeviceptr_t base = nullptr; size_t size = 0;
+        if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) (void)hipGetLastError();   // (not every allocator's memory has one)
+        else if ((const char*)p + bytes > (const char*)base + size)
+            return fail(RT_E_INVALID, "rt_trace: %s needs %lld bytes from %p, its allocation ends %lld bytes earlier", name, (long long)bytes, p,
+                        (long long)(((const char*)p + bytes) - ((const char*)base + size)));
+    }
+    return RT_OK;
+}
+static int trace_view(RtCtx* ctx, size_t ownRays)
+{
+    RtCtx::TraceView& v = ctx->tv;
+    if (!v.ready) {
+        DevQueues q{};
+        unsigned long long* ctr = nullptr;
+        int rc = dalloc(v.words, &q.nRays, RT_MAX_BOUNCES + 2);
+        if (rc == RT_OK) rc = dalloc(v.words, &q.nShadow, RT_MAX_BOUNCES + 2);
+        if (rc == RT_OK) rc = dalloc(v.words, &q.cursor, kCursorWords);
+        if (rc == RT_OK) rc = dalloc(v.words, &q.fault, 1);
+        if (rc == RT_OK) rc = dalloc(v.words, &ctr, (size_t)ctx->gridMax * kCtrCols);   // nobody sums a query's work: one table takes both stages' rows
+        if (rc != RT_OK) { free_bag(v.words); return rc; }
+        HIPCHK(hipMemsetAsync(q.nRays, 0, sizeof(int32_t) * (RT_MAX_BOUNCES + 2), ctx->stream));
+        HIPCHK(hipMemsetAsync(q.nShadow, 0, sizeof(int32_t) * (RT_MAX_BOUNCES + 2), ctx->stream));
+        HIPCHK(hipMemsetAsync(q.cursor, 0, sizeof(int32_t) * kCursorWords, ctx->stream));
+        HIPCHK(hipMemsetAsync(q.fault, 0, sizeof(int32_t), ctx->stream));
+        HIPCHK(hipMemsetAsync(ctr, 0, sizeof(unsigned long long) * (size_t)ctx->gridMax * kCtrCols, ctx->stream));
+        q.ctrExtend = q.ctrConnect = ctr;
+        q.nPix = ctx->nPix; q.firstPixel = ctx->firstPixel; q.width = ctx->cfg.width; q.height = ctx->cfg.height;
+        v.q = q; v.ready = true;
+    }
+    if (ownRays > v.cap) {
+        HIPCHK(hipStreamSynchronize(ctx->stream));   // an earlier query may still be reading the arrays this one replaces
+        for (float4*& p : v.rays) { if (p) (void)hipFree(p); p = nullptr; }
+        v.cap = 0;
+        for (float4*& p : v.rays)
+            if (hipMalloc((void**)&p, ownRays * sizeof(float4)) != hipSuccess) {
+                (void)hipGetLastError();
+                for (float4*& r : v.rays) { if (r) (void)hipFree(r); r = nullptr; }
+                return fail(RT_E_NOMEM, "rt_trace: hipMalloc of the query's ray arrays (3 x %zu bytes) failed", ownRays * sizeof(float4));
+            }
+        v.cap = ownRays;
+    }
+    return RT_OK;
+}
+extern "C" int rt_trace(RtCtx* ctx, int32_t mode, const RtRayBatch* rays, const RtTraceOut* out)
+{
+    if (!ctx) return fail(RT_E_INVALID, "rt_trace: null ctx");
+    if (!rays) return fail(RT_E_INVALID, "rt_trace: null rays");
+    if (!out) return fail(RT_E_INVALID, "rt_trace: null out");
+    int rc = need_scene(ctx, "rt_trace"); if (rc) return rc;
+    if (mode != RT_TRACE_CLOSEST && mode != RT_TRACE_ANY) return fail(RT_E_INVALID, "rt_trace: mode %d is neither RT_TRACE_CLOSEST (0) nor RT_TRACE_ANY (1)", mode);
+    const bool any = mode == RT_TRACE_ANY;
+    const int64_t n = rays->n;
+    if (n < 0) return fail(RT_E_INVALID, "rt_trace: rays->n = %lld is negative", (long long)n);
+    if (rays->originStride < 12 || rays->originStride % 4) return fail(RT_E_INVALID, "rt_trace: rays->originStride = %lld must be >= 12 and a multiple of 4", (long long)rays->originStride);
+    if (rays->dirStride < 12 || rays->dirStride % 4) return fail(RT_E_INVALID, "rt_trace: rays->dirStride = %lld must be >= 12 and a multiple of 4", (long long)rays->dirStride);
+    if (any) {
+        if (out->hit || out->point || out->normal) return fail(RT_E_INVALID, "rt_trace: out->%s is not produced by RT_TRACE_ANY", out->hit ? "hit" : (out->point ? "point" : "normal"));
+    } else if (out->occluded) return fail(RT_E_INVALID, "rt_trace: out->occluded is not produced by RT_TRACE_CLOSEST");
+    if (n == 0) return RT_OK;
+    if (any ? !out->occluded : !out->hit) return fail(RT_E_INVALID, "rt_trace: out->%s is required by %s", any ? "occluded" : "hit", any ? "RT_TRACE_ANY" : "RT_TRACE_CLOSEST");
+    if (!rays->origin) return fail(RT_E_INVALID, "rt_trace: null rays->origin");
+    if (!rays->dir) return fail(RT_E_INVALID, "rt_trace: null rays->dir");
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    if ((rc = trace_pointer(ctx, "rays->origin", rays->origin, (n - 1) * rays->originStride + 12, 4))) return rc;
+    if ((rc = trace_pointer(ctx, "rays->dir", rays->dir, (n - 1) * rays->dirStride + 12, 4))) return rc;
+    if (rays->tmax) if ((rc = trace_pointer(ctx, "rays->tmax", rays->tmax, n * 4, 4))) return rc;
+    if (out->hit) if ((rc = trace_pointer(ctx, "out->hit", out->hit, n * 16, 16))) return rc;
+    if (out->point) if ((rc = trace_pointer(ctx, "out->point", out->point, n * 16, 16))) return rc;
+    if (out->normal) if ((rc = trace_pointer(ctx, "out->normal", out->normal, n * 16, 16))) return rc;
+    if (out->occluded) if ((rc = trace_pointer(ctx, "out->occluded", out->occluded, n, 1))) return rc;
+    const bool vecO = rays->originStride == 16 && (uintptr_t)rays->origin % 16 == 0, vecD = rays->dirStride == 16 && (uintptr_t)rays->dir % 16 == 0;
+    const bool inPlace = !any && vecO && vecD && !rays->tmax && !out->point && !out->normal;   // the queue's own layout, nothing but the hit record wanted
+    const int64_t window = trace_window(ctx);
+    if ((rc = trace_view(ctx, inPlace ? 0 : (size_t)std::min(n, window)))) return rc;
+    ctx->queued = true;
+    DevQueues q = ctx->tv.q;
+    q.spill = ctx->q.spill; q.spillStride = ctx->q.spillStride; q.stackCap = ctx->q.stackCap; q.tlasLdsEntries = ctx->q.tlasLdsEntries;
+    for (int64_t off = 0; off < n; off += window) {
+        const int m = (int)std::min(window, n - off);
+        TraceIO io{ (const char*)rays->origin + off * rays->originStride, (const char*)rays->dir + off * rays->dirStride, rays->originStride, rays->dirStride,
+                    rays->tmax ? rays->tmax + off : nullptr, out->hit ? (float4*)out->hit + off : nullptr, out->point ? (float4*)out->point + off : nullptr,
+                    out->normal ? (float4*)out->normal + off : nullptr, out->occluded ? out->occluded + off : nullptr };
+        float4* const* own = ctx->tv.rays;
+        q.O[kTraceBounce & 1] = q.sA = inPlace ? (float4*)io.origin : own[0];
+        q.D[kTraceBounce & 1] = q.sB = inPlace ? (float4*)io.dir : own[1];
+        q.hit = q.sC = inPlace ? io.hit : own[2];
+        hipLaunchKernelGGL(k_trace_arm, dim3(1), dim3(1), 0, ctx->stream, q, m, (int)any);
+        if (!inPlace) hipLaunchKernelGGL(k_trace_load, grid_for(m), dim3(kBlock), 0, ctx->stream, q, io, m, (int)any, (int)vecO, (int)vecD);
+        const TraceLaunch L = trace_launch(ctx, any ? ST_CONNECT : ST_EXTEND, kTraceBounce, false, m);
+        if (L.persist) hipLaunchKernelGGL(L.persist, L.grid, dim3(kBlock), L.lds, ctx->stream, ctx->sc, q, kTraceBounce, kTraceBounce, 0, L.tune);
+        else if (any) hipLaunchKernelGGL(L.nested, L.grid, dim3(kBlock), L.lds, ctx->stream, ctx->sc, q, kTraceBounce, kTraceBounce);
+        else hipLaunchKernelGGL(L.nested, L.grid, dim3(kBlock), L.lds, ctx->stream, ctx->sc, q, kTraceBounce, 0);
+        if (!inPlace) hipLaunchKernelGGL(k_trace_store, grid_for(m), dim3(kBlock), 0, ctx->stream, ctx->sc, q, io, m, (int)any);
+        HIPCHK(hipGetLastError());
+    }
     return RT_OK;
 }
 

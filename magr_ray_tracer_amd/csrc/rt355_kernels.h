@@ -2367,6 +2367,18 @@ __global__ __launch_bounds__(kBlock) void k_postproc(const float4* accum, float4
 }
 
 // ------------------------------------------------------------------ debug import/export (parity tests)
+// I and N as extend leaves them in the reference's Ray (wavefront.cl:56-63): the hit point O + t * D and the primitive's normal there,
+// flipped against D; zeros on a miss.  The one statement of that arithmetic: k_export_rays and k_trace_store both call it.
+RT_FORCEINLINE void hit_point_normal(const DevScene& sc, float4 O, float4 D, float4 hit, float4& I, float4& N)
+{
+    I = splat(0.0f); N = splat(0.0f);
+    const int prim = __float_as_int(hit.y);
+    if (prim != -1) {
+        I = add4(O, muls(D, hit.x));
+        N = prim_normal(sc.prims + prim, I);
+        if (dot4(N, neg4(D)) < 0) N = muls(N, -1.0f);
+    }
+}
 __global__ void k_export_rays(DevScene sc, DevQueues q, int bounce, RtRay* out)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2376,13 +2388,9 @@ __global__ void k_export_rays(DevScene sc, DevQueues q, int bounce, RtRay* out)
     const float4 O = q.O[set][i], D = q.D[set][i], hit = q.hit[i], inten = q.inten[set][i];
     const uint2 meta = q.meta[set][i];
     float4 rD = mk4(1.0f / D.x, 1.0f / D.y, 1.0f / D.z, 1.0f / D.w);
-    float4 I = splat(0.0f), N = splat(0.0f);
+    float4 I, N;
     const int prim = __float_as_int(hit.y);
-    if (prim != -1) {
-        I = add4(O, muls(D, hit.x));
-        N = prim_normal(sc.prims + prim, I);
-        if (dot4(N, neg4(D)) < 0) N = muls(N, -1.0f);
-    }
+    hit_point_normal(sc, O, D, hit, I, N);
     *reinterpret_cast<float4*>(&r.O) = O; *reinterpret_cast<float4*>(&r.D) = D; *reinterpret_cast<float4*>(&r.rD) = rD;
     *reinterpret_cast<float4*>(&r.N) = N; *reinterpret_cast<float4*>(&r.I) = I; *reinterpret_cast<float4*>(&r.intensity) = inten;
     r.t = hit.x; r.primIdx = prim; r.bounces = (int)(meta.y & kMetaBounceMask); r.pixelIdx = (int)meta.x;
@@ -2400,5 +2408,61 @@ __global__ void k_import_rays(DevQueues q, const RtRay* in, int n, int set)
     q.meta[set][i] = make_uint2((uint32_t)r.pixelIdx, (uint32_t)r.bounces | (r.inside ? kMetaInside : 0u) | (r.lastSpecular ? kMetaLastSpec : 0u));
 }
 __global__ void k_set_count(int32_t* p, int32_t v) { *p = v; }
+
+// ------------------------------------------------------------------ rt_trace: caller-supplied rays through a DevQueues view of their own
+// A query runs the context's traversal kernels over a view whose queue arrays are the caller's (16-byte rays, hit records wanted: no
+// pass besides the traversal) or the view's own, filled by k_trace_load and read back by k_trace_store.  Both stream: one ray per lane,
+// every byte touched once.  The view keeps its rays in bounce slot kTraceBounce: not slot 0, whose launches may map a wave to an 8x8
+// pixel tile (primary_tiles) and read wave-uniform node records through the scalar cache - caller rays are no pixel grid.
+static constexpr int kTraceBounce = 1;
+struct TraceIO {
+    const char* origin; const char* dir;   // ray i's x, y, z at base + i * stride
+    long long originStride, dirStride;
+    const float* tmax;                     // may be null
+    float4* hit; float4* point; float4* normal; uint8_t* occluded;   // outputs, null where not wanted
+};
+// One pass's queue state: the count words the kernels read, the dequeue heads they advance
+__global__ void k_trace_arm(DevQueues q, int n, int any)
+{
+    if (any) { q.nShadow[kTraceBounce] = 0; q.nShadow[kTraceBounce + 1] = n; q.cursor[(RT_MAX_BOUNCES + 2) + kTraceBounce] = 0; }
+    else { q.nRays[kTraceBounce] = n; q.cursor[kTraceBounce] = 0; }
+}
+// x, y, z of a strided record as (x, y, z, 0): one 16-byte load where the record is a float4 on a 16-byte boundary, else three words
+RT_FORCEINLINE float4 trace_xyz(const char* base, long long stride, int i, bool vec)
+{
+    const char* p = base + (long long)i * stride;
+    if (vec) { const float4 v = ldnt4(reinterpret_cast<const float4*>(p)); return mk4(v.x, v.y, v.z, 0.0f); }
+    const float* f = reinterpret_cast<const float*>(p);
+    return mk4(__builtin_nontemporal_load(f), __builtin_nontemporal_load(f + 1), __builtin_nontemporal_load(f + 2), 0.0f);
+}
+// Gather: closest -> O, D of the view's slot; any -> the shadow record {origin, tmax} / {dir}, radiance 1 (connect zeroes it when occluded)
+__global__ __launch_bounds__(kBlock) void k_trace_load(DevQueues q, TraceIO io, int n, int any, int vecO, int vecD)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    float4 O = trace_xyz(io.origin, io.originStride, i, vecO != 0);
+    const float4 D = trace_xyz(io.dir, io.dirStride, i, vecD != 0);
+    if (any) {
+        O.w = io.tmax ? __builtin_nontemporal_load(io.tmax + i) : kFar;
+        q.sA[i] = O; q.sB[i] = D; q.sC[i] = splat(1.0f);
+    } else { q.O[kTraceBounce & 1][i] = O; q.D[kTraceBounce & 1][i] = D; }
+}
+// Scatter: closest -> the hit record, a miss where t is not below the ray's tmax, and I, N of what is reported; any -> 1 / 0.
+// The view's own arrays are read for the last time here.
+__global__ __launch_bounds__(kBlock) void k_trace_store(DevScene sc, DevQueues q, TraceIO io, int n, int any)
+{
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    if (any) { io.occluded[i] = ldnt4(&q.sC[i]).x == 0.0f ? 1 : 0; return; }
+    float4 h = ldnt4(&q.hit[i]);
+    if (io.tmax && !(h.x < __builtin_nontemporal_load(io.tmax + i))) h = mk4(kFar, __int_as_float(-1), 0.0f, 0.0f);
+    stnt4(&io.hit[i], h);
+    if (io.point || io.normal) {
+        float4 I, N;
+        hit_point_normal(sc, ldnt4(&q.O[kTraceBounce & 1][i]), ldnt4(&q.D[kTraceBounce & 1][i]), h, I, N);
+        if (io.point) stnt4(&io.point[i], I);
+        if (io.normal) stnt4(&io.normal[i], N);
+    }
+}
 
 } // namespace rt355dev

@@ -336,6 +336,79 @@ class Device:
             self._chk(self._lib.rt_debug_get_shadow(self._h, b0, b1, _lib.ptr(out), n.value, C.byref(n)))
         return out
 
+    # ---- queries (rt_trace)
+    def trace_window(self):
+        """Rays one pass of trace() takes (rt_trace_window); a longer batch runs as several passes."""
+        w = int(self._lib.rt_trace_window(self._h))
+        if w < 0:
+            self._chk_code(w)
+        return w
+
+    def trace_raw(self, mode, origin=0, dir=0, origin_stride=16, dir_stride=16, tmax=0, n=0, hit=0, point=0, normal=0, occluded=0):
+        """rt_trace with the two structs filled from device addresses (integers; 0 = NULL).  Asynchronous; a refusal raises RtError (.code)."""
+        b = np.zeros((), dtype=_lib.RayBatch)
+        b["origin"], b["dir"], b["originStride"], b["dirStride"], b["tmax"], b["n"] = origin, dir, origin_stride, dir_stride, tmax, n
+        o = np.zeros((), dtype=_lib.TraceOut)
+        o["hit"], o["point"], o["normal"], o["occluded"] = hit, point, normal, occluded
+        self._chk_code(self._lib.rt_trace(self._h, int(mode), b.ctypes.data_as(C.c_void_p), o.ctypes.data_as(C.c_void_p)))
+
+    def trace(self, origins, dirs, tmax=None, mode="closest", point=False, normal=False):
+        """Intersect caller rays with the bound scene (rt_trace).  origins, dirs: (n, 3) or (n, 4) float32, either torch tensors on the
+        context's GPU - used in place through their row stride, which may be any multiple of 4 bytes from 12 up (a view of every second
+        row of a wider tensor is fine) - or numpy arrays, which are copied over.  tmax: None or n float32.
+        mode "closest" returns a dict: "hit" (n records of _lib.Hit: t, primIdx, u, v; a miss is (1e30, -1, 0, 0); with tmax, hits at
+        t >= tmax are misses) and, on request, "point" and "normal" ((n, 4) float32: O + t * D and the surface normal facing the ray).
+        mode "any" returns n uint8: 1 where something lies in front of tmax.  Results are torch tensors for torch input (hit as an
+        (n, 4) float32 tensor whose column 1 holds primIdx's bits: .view(torch.int32)), numpy arrays for numpy input.  The tensor path
+        waits for torch's current stream on entry; the call returns after rt_synchronize."""
+        import torch
+        which = {"closest": _lib.TRACE_CLOSEST, "any": _lib.TRACE_ANY}.get(mode)
+        if which is None:
+            raise ValueError(f"mode must be 'closest' or 'any', not {mode!r}")
+        if which == _lib.TRACE_ANY and (point or normal):
+            raise ValueError("point / normal are results of mode 'closest'")
+        as_torch = isinstance(origins, torch.Tensor)
+        dev = torch.device("cuda", int(self.cfg["device"]))
+
+        def rows(a, name):
+            if not as_torch:
+                a = torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+            if not (isinstance(a, torch.Tensor) and a.is_cuda and a.device == dev and a.dtype == torch.float32 and a.dim() == 2 and a.shape[1] in (3, 4)):
+                raise ValueError(f"{name} must be an (n, 3) or (n, 4) float32 array, or such a tensor on {dev}")
+            if a.shape[0] > 1 and (a.stride(1) != 1 or a.stride(0) < 3):
+                a = a.contiguous()
+            return a, (a.stride(0) if a.shape[0] > 1 else 4) * 4
+
+        o, o_stride = rows(origins, "origins")
+        d, d_stride = rows(dirs, "dirs")
+        n = o.shape[0]
+        if d.shape[0] != n:
+            raise ValueError("origins and dirs differ in length")
+        t = None
+        if tmax is not None:
+            t = tmax if isinstance(tmax, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(tmax, dtype=np.float32))
+            t = t.to(device=dev, dtype=torch.float32).contiguous().reshape(-1)
+            if t.shape[0] != n:
+                raise ValueError("tmax must hold one value per ray")
+        new = lambda *shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=dev)   # noqa: E731
+        hit = new(n, 4) if which == _lib.TRACE_CLOSEST else None
+        pt = new(n, 4) if point else None
+        nm = new(n, 4) if normal else None
+        occ = new(n, dtype=torch.uint8) if which == _lib.TRACE_ANY else None
+        P = lambda x: 0 if x is None or x.numel() == 0 else x.data_ptr()   # noqa: E731
+        torch.cuda.current_stream(dev).synchronize()   # what produced the inputs has finished; the context's stream is not torch's
+        self.trace_raw(which, P(o), P(d), o_stride, d_stride, P(t), n, P(hit), P(pt), P(nm), P(occ))
+        self.synchronize()
+        back = (lambda x: x) if as_torch else (lambda x: x.cpu().numpy())
+        if which == _lib.TRACE_ANY:
+            return back(occ)
+        res = {"hit": hit if as_torch else hit.cpu().numpy().view(_lib.Hit).reshape(-1)}
+        if point:
+            res["point"] = back(pt)
+        if normal:
+            res["normal"] = back(nm)
+        return res
+
     def enable_steps(self, on=True):
         self._chk(self._lib.rt_debug_enable_steps(self._h, int(on)))
 
