@@ -419,7 +419,8 @@ int rt_group_update_scene(RtGroup* g, const RtPrimitive* prims, int32_t first, i
                           RtUpdateStats* stats);                             /* rt_update_scene for the group's copy (all lanes)        */
 int rt_group_rebuild_scene(RtGroup* g, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
                            int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats);   /* rt_rebuild_scene for the group's copy */
-int rt_group_seed(RtGroup* g, uint64_t firstStream);                         /* a single Renderer: 0; rank r of a sample split: r*lanes */
+int rt_group_seed(RtGroup* g, uint64_t firstStream);                         /* a single Renderer: 0 (what rt_group_create leaves);
+                                                                              * rank r of a sample split: r*lanes                       */
 int rt_group_reset(RtGroup* g);                                              /* resetKernel on every lane; frames = 0                   */
 int rt_group_render(RtGroup* g, const RtCamera* cam, const RtSettings* settings, int32_t frames);   /* `frames` in all, round-robin   */
 int rt_group_synchronize(RtGroup* g);
@@ -431,7 +432,14 @@ int rt_group_postproc(RtGroup* g, int32_t frames, float vignette, float gamma, f
 
 /* seedBuffer (renderer.cpp:195-196,200).  rt_set_seeds takes the band's slice
  * (one uint per band pixel); rt_seed_default fills seeds[i] with the (firstPixel+i+1)-th
- * xorshift32 output from 0x12345678 like the reference's host loop. */
+ * xorshift32 output from 0x12345678 like the reference's host loop.
+ * A context is never unseeded: rt_create leaves it as rt_seed_default would, and rt_group_create leaves lane m as
+ * rt_group_seed(g, 0) would.  Every seed must be nonzero: rt_set_seeds returns RT_E_INVALID for a 0 (the message names the first
+ * such index) before it copies anything, so the seeds on the device stay what they were; rt_group_seed and a checkpoint restore
+ * go through it.  State 0 is the fixed point of the RNG step - every draw from it is 0.0f, and the rejection loop that samples a
+ * direction at a diffuse hit would never end.  The host check suffices: the step is a bijection of the 32-bit states that fixes
+ * only 0, so a nonzero state never becomes 0 on the device, and from a nonzero state that loop makes at most 28 attempts (DESIGN.md
+ * section 2). */
 int rt_set_seeds(RtCtx* ctx, const uint32_t* seeds, int64_t n);
 int rt_seed_default(RtCtx* ctx);
 int rt_get_seeds(RtCtx* ctx, uint32_t* out, int64_t n);
@@ -483,6 +491,12 @@ int rt_stage_connect(RtCtx* ctx, int32_t firstBounce, int32_t lastBounce);      
  * born in generate and die in shade (wavefront.cl).  Ray i is origin (x, y, z) at rays->origin + i * originStride and direction at
  * rays->dir + i * dirStride (bytes; 12: packed float3, 16: float4 whose w is ignored, 32: every second float4, ...).  Directions are
  * used as given - not normalised, not validated; the sphere test assumes a unit D, as it does in the renderer.
+ * A ray with a NaN or infinite component in its origin or direction misses, on every path: CLOSEST reports {RT_REALLYFAR, -1, 0, 0}
+ * with zero point and normal, ANY reports 0 whatever tmax (a ray enters an instance before it meets a primitive, in single-BLAS scenes
+ * too, and the instance transform - every component times every row, as in the reference - turns one non-finite component into an
+ * all-NaN ray, which no box or primitive test accepts).  A zero
+ * direction, like a subnormal or a FLT_MAX component, is traced as given: the result is what rt_stage_extend / connect compute for
+ * that ray, and a ray with D = 0 can report a sphere it starts inside.
  *   RT_TRACE_CLOSEST, tmax NULL   hit[i] is, bit for bit, what rt_stage_extend leaves in its hit queue for a slot holding
  *                      O = (x, y, z, 0), D = (x, y, z, 0): t, primIdx, u, v of the closest hit, the same on every traversal path
  *                      (the nested loops, k_trace_persist, k_trace_persist_tlas with or without spill, k_trace_persist4,
@@ -493,7 +507,13 @@ int rt_stage_connect(RtCtx* ctx, int32_t firstBounce, int32_t lastBounce);      
  *                      (the traversal is NOT started at tmax: at knife edges that would be another float32 function).
  *   RT_TRACE_ANY       occluded[i] = 1 iff the context's connect traversal, given the shadow record {origin, tmax[i]} / {dir},
  *                      accepts a primitive with t < tmax[i] (tmax NULL: RT_REALLYFAR), else 0.  Connect's visit order; the result does
- *                      not depend on it.
+ *                      not depend on it - except for a ray with a direction component so large that the float32 triangle test
+ *                      overflows (|D| of the order of FLT_MAX: 1 / det is 0 or the products are infinite, every visited triangle
+ *                      then "hits" at t = 0 or NaN).  The verdict for such a ray is what the context's own traversal computes: it
+ *                      may differ between a BVH2 and a BVH4 context, and at tmax > RT_REALLYFAR (+inf) a BVH2 context prunes the
+ *                      boxes the ray misses, where the reference's loop and a BVH4 context descend into them (their miss value
+ *                      1e30 is below such a tmax) and report such a ray occluded.  Every other ray, at every tmax, gets the one
+ *                      verdict of the reference's loop ("Non-finite rays").
  * With 16-byte strides on 16-byte boundaries, CLOSEST, no tmax and nothing but `hit` wanted, the kernels read and write the caller's
  * arrays directly; every other form passes through a load and a store kernel that stream the batch once each.
  * A batch runs in passes of at most rt_trace_window(ctx) rays: min(2^22, what the context's per-workgroup tables hold - at least

@@ -492,7 +492,6 @@ extern "C" int rt_create(const RtConfig* cfg, RtCtx** out)
     (void)hipMemsetAsync(q.fault, 0, sizeof(int32_t), ctx->stream);
     (void)hipMemsetAsync(q.ctrExtend, 0, sizeof(unsigned long long) * (size_t)ctx->gridMax * kCtrCols, ctx->stream);
     (void)hipMemsetAsync(q.ctrConnect, 0, sizeof(unsigned long long) * (size_t)ctx->gridMax * kCtrCols, ctx->stream);
-    (void)hipMemsetAsync(q.seeds, 0, sizeof(uint32_t) * n, ctx->stream);
     for (int k = 0; k < 2; k++) {
         (void)hipMemsetAsync(q.tile[k], 0, sizeof(unsigned long long) * (nTiles + 2), ctx->stream);
         (void)hipMemsetAsync(q.super[k], 0, sizeof(unsigned long long) * (nTiles / 64 + 2), ctx->stream);
@@ -500,6 +499,9 @@ extern "C" int rt_create(const RtConfig* cfg, RtCtx** out)
     }
     (void)hipMemsetAsync(q.hit, 0, sizeof(float4) * n, ctx->stream);
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    // never an unseeded context: state 0 is the RNG's fixed point, and k_shade's sample_ball would not return from it (rt_set_seeds)
+    rc = rt_seed_default(ctx);
+    if (rc != RT_OK) return rc;
     ev_init(ctx);
     *out = guard.release();
     return RT_OK;
@@ -843,6 +845,10 @@ extern "C" int rt_set_seeds(RtCtx* ctx, const uint32_t* seeds, int64_t n)
 {
     if (!ctx || !seeds) return fail(RT_E_INVALID, "rt_set_seeds: null argument");
     if (n != ctx->nPix) return fail(RT_E_INVALID, "rt_set_seeds: expected %d seeds (band pixels), got %lld", ctx->nPix, (long long)n);
+    // The RNG step is a bijection of the 32-bit states that fixes only 0: a nonzero state never becomes 0, and from 0
+    // every draw is 0.0f, with which sample_ball's rejection loop never ends.  So 0 is refused here, before anything is copied.
+    for (int64_t i = 0; i < n; i++)
+        if (seeds[i] == 0) return fail(RT_E_INVALID, "rt_set_seeds: seeds[%lld] is 0, the fixed point of the RNG: every seed must be nonzero", (long long)i);
     HIPCHK(hipSetDevice(ctx->cfg.device));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     HIPCHK(hipMemcpy(ctx->q.seeds, seeds, sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice));
@@ -1754,6 +1760,10 @@ extern "C" int rt_group_create(const RtConfig* cfg, int32_t lanes, RtGroup** out
                             "GPU_MAX_HW_QUEUES=%s of them per priority class, the normal class's shared with the process's other streams)\n",
                     lanes, g->concurrent, name[rt_group_stream_class(g) + 1], g->seen[0], g->seen[1], g->seen[2], q ? q : "4 (unset)");
         }
+    }
+    {   // lane m starts on sample stream m, as rt_group_seed(g, 0) leaves it
+        const int rc = rt_group_seed(g, 0);
+        if (rc != RT_OK) return rc;
     }
     *out = guard.release();
     return RT_OK;

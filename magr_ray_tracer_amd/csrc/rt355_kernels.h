@@ -321,7 +321,12 @@ RT_FORCEINLINE float slab(const TRay& r, float4 bmin, float4 bmax) // bvh.cl:3-1
 // occlusion traversal ray.t stays t_light until the first accepted primitive ends it, bvh.cl:25,40), and the exit distance comes
 // for free.  Whether a shadow ray is occluded does not depend on the ORDER in which the children that pass this test are visited
 // (a node is reached iff all its ancestors pass, whatever the order; the first accepted primitive returns), so connect is free to
-// pick its own: the child the ray leaves LATER first - nearer the light, where most occluders of this kind of scene sit - finds
+// pick its own.  Two exceptions, both outside rendering and both confined to rays whose primitive tests are float32 garbage - a
+// direction component near FLT_MAX, whose triangle determinant overflows ("Non-finite rays"): a primitive
+// accepted with a NaN t does not return and leaves r.t = NaN, after which no box passes, so the verdict depends on which garbage
+// primitive comes first; and for t_light > RT_REALLYFAR (rt_trace with tmax = +inf) the reference's loop descends into a box that
+// FAILED this test - its miss value 1e30 is below such a t_light - where this one does not.  rt_trace documents both (include/rt355.h);
+// tests/test_edge_rays_cpu.py pins the rays.  The order chosen: the child the ray leaves LATER first - nearer the light, where most occluders of this kind of scene sit - finds
 // an occluder after 27.6 instead of 34.9 node visits per shadow ray on the bench scene (tools/lab/anyhit_lab.c; 85 % of its
 // shadow rays are occluded), with the accumulator unchanged bit for bit.
 RT_FORCEINLINE bool slab_any(const TRay& r, float4 bmin, float4 bmax, float& exitT)

@@ -213,8 +213,10 @@ class Device:
         return "k_extend<%s, %d>" % ("RT_ACCEL_BVH4" if self.accel == _lib.ACCEL_BVH4 else "RT_ACCEL_BVH2", k["layout"])
 
     def set_seeds(self, seeds):
+        """One nonzero uint32 per band pixel (rt_set_seeds).  A zero seed raises RtError (.code RT_E_INVALID, the message names its
+        index) and leaves the context's seeds as they were; a fresh context already holds seed_default()'s."""
         s = np.ascontiguousarray(seeds, dtype=np.uint32)
-        self._chk(self._lib.rt_set_seeds(self._h, _lib.ptr(s), s.size))
+        self._chk_code(self._lib.rt_set_seeds(self._h, _lib.ptr(s), s.size))
 
     def seed_default(self):
         self._chk(self._lib.rt_seed_default(self._h))
@@ -267,8 +269,10 @@ class Device:
     def load_checkpoint(self, path):
         g = np.load(path)
         assert tuple(g["dims"]) == (self.width, self.height, self.y0, self.y1), "checkpoint was taken with another frame/band"
-        self.write_accum(g["accum"])
-        self.set_seeds(g["seeds"])
+        accum = g["accum"]
+        assert accum.shape == (self.height, self.width, 4)
+        self.set_seeds(g["seeds"])       # first: a checkpoint with a zero seed is refused whole (RtError), accumulator untouched
+        self.write_accum(accum)
         return int(g["frames"])
 
     def postproc(self, frames, vignette=0.0, gamma=0.9, chromatic=0.0):

@@ -491,8 +491,11 @@ static int traverse_bvh2(RtRay* ray, const OrcScene* sc, uint32_t root, int occl
     return steps;
 }
 /* The slab test of isect_aabb with both distances kept: the same six float32 products and minNum / maxNum chain, `hit` its visit
- * condition against the pruning distance t_light, *exitT the distance at which the ray leaves the box. */
-static inline int slab_exit(const RtRay* ray, f4 bmin, f4 bmax, float t_light, float* exitT)
+ * condition, *exitT the distance at which the ray leaves the box.  The pruning distance is ray->t, as in isect_aabb (bvh.cl:3-12) and in
+ * the kernels' slab_any: in an occlusion traversal it is t_light until a primitive is accepted, and an accepted primitive ends the
+ * traversal unless its t is not below t_light - equal to it, or a NaN (the triangle test rejects by comparisons, which a NaN passes).
+ * After a NaN no box passes any more, here as in the reference's loop, whose failed box reports 1e30 >= t_light. */
+static inline int slab_exit(const RtRay* ray, f4 bmin, f4 bmax, float* exitT)
 {
     float tx1 = (bmin.x - ray->O.x) * ray->rD.x, tx2 = (bmax.x - ray->O.x) * ray->rD.x;
     float tmin = fminf(tx1, tx2), tmax = fmaxf(tx1, tx2);
@@ -501,12 +504,15 @@ static inline int slab_exit(const RtRay* ray, f4 bmin, f4 bmax, float t_light, f
     float tz1 = (bmin.z - ray->O.z) * ray->rD.z, tz2 = (bmax.z - ray->O.z) * ray->rD.z;
     tmin = fmaxf(tmin, fminf(tz1, tz2)); tmax = fminf(tmax, fmaxf(tz1, tz2));
     *exitT = tmax;
-    return tmax >= tmin && tmin < t_light && tmax > 0;
+    return tmax >= tmin && tmin < ray->t && tmax > 0;
 }
 /* OrcConfig.connect_order == 1: the occlusion traversal of a BVH2 BLAS in the order the HIP path's connect uses (NOT the reference's).
  * Of the two children that pass the visit test the one the ray leaves LATER goes first - child 2 iff its exit distance is greater,
  * ties go to child 1 - and the other is pushed; with one passing child descend into it, with none pop.  Which nodes are reached at all
- * does not depend on the order, so neither does the verdict; the counts do.  Returns -1 for an occluded ray, else 0 (`steps` has no
+ * does not depend on the order, so neither does the verdict; the counts do.  (Two exceptions, on rays whose primitive tests are
+ * float32 garbage - a direction component near FLT_MAX: a primitive accepted with a NaN t kills every later box, so the verdict depends
+ * on which garbage primitive comes first; and for t_light > 1e30 the reference's loop above descends into boxes that failed - their 1e30
+ * is below such a t_light - where this one, like the kernels' slab_any, does not.  tests/test_edge_rays_cpu.py pins the rays.)  Returns -1 for an occluded ray, else 0 (`steps` has no
  * reader in connect). */
 static int traverse_bvh2_later_exit(RtRay* ray, const OrcScene* sc, uint32_t root, OrcCounters* c)
 {
@@ -531,8 +537,8 @@ static int traverse_bvh2_later_exit(RtRay* ray, const OrcScene* sc, uint32_t roo
         const RtBVHNode2* c1 = &nodes[node->first];
         const RtBVHNode2* c2 = &nodes[node->first + 1];
         float x1, x2;
-        const int h1 = slab_exit(ray, c1->aabbMin, c1->aabbMax, t_light, &x1);
-        const int h2 = slab_exit(ray, c2->aabbMin, c2->aabbMax, t_light, &x2);
+        const int h1 = slab_exit(ray, c1->aabbMin, c1->aabbMax, &x1);
+        const int h2 = slab_exit(ray, c2->aabbMin, c2->aabbMax, &x2);
         if (h1 && h2) {
             if (x2 > x1) { node = c2; stack[sp++] = c1; }
             else { node = c1; stack[sp++] = c2; }
@@ -849,6 +855,19 @@ void orc_connect_work(const RtShadowRay* shadow, int32_t n, const OrcScene* sc, 
         work[i].occluded = (uint32_t)occluded;
     }
 }
+/* orc_connect's traversal on rays given as they are traced: origin[i], dir[i] (xyz; the w lanes are taken as 0) with reach tmax[i]
+ * (NULL: RT_REALLYFAR).  occluded[i] = 1 iff a primitive is accepted with t < tmax[i].  A record {I, L, dist} of orc_connect is the ray
+ * I + L * eps, L with tmax = dist - 2 eps. */
+void orc_occluded(const RtFloat4* origin, const RtFloat4* dir, const float* tmax, int32_t n, const OrcScene* sc, const OrcConfig* cfg, uint8_t* occluded)
+{
+    for (int32_t i = 0; i < n; i++) {
+        OrcCounters c; memset(&c, 0, sizeof c);
+        RtRay ray = zero_ray();
+        init_ray(&ray, v4(origin[i].x, origin[i].y, origin[i].z, 0.0f), v4(dir[i].x, dir[i].y, dir[i].z, 0.0f));
+        ray.t = tmax ? tmax[i] : RT_REALLYFAR;
+        occluded[i] = traverse_tlas(&ray, sc, cfg, 1, &c) == -1;
+    }
+}
 float orc_focus(int32_t x, int32_t y, const OrcScene* sc, const OrcConfig* cfg, const RtCamera* cam) /* wavefront.cl:203-224 */
 {
     RtRay r = zero_ray(); OrcCounters c; memset(&c, 0, sizeof c);
@@ -1106,5 +1125,114 @@ int orc_math_error(int32_t fn, float lo, float hi, int32_t absolute, double boun
         }
     }
     *out = r;
+    return 0;
+}
+
+/* ---------------------------------------------------------------- the RNG as a linear map, and sample_ball's rejection loop over its whole cycle */
+/* xorshift32 is linear over GF(2): column b of the 32x32 matrix is the image of state 1 << b. */
+static void xs_matrix(uint32_t col[32]) { for (int b = 0; b < 32; b++) { uint32_t s = 1u << b; orc_xorshift32(&s); col[b] = s; } }
+static inline uint32_t xs_apply(const uint32_t col[32], uint32_t s) { uint32_t r = 0; for (int b = 0; b < 32; b++) if (s >> b & 1) r ^= col[b]; return r; }
+static void xs_power(uint32_t out[32], uint64_t e)   /* the matrix of e steps, by squaring */
+{
+    uint32_t sq[32], t[32];
+    xs_matrix(sq);
+    for (int b = 0; b < 32; b++) out[b] = 1u << b;
+    for (; e; e >>= 1) {
+        if (e & 1) { for (int b = 0; b < 32; b++) t[b] = xs_apply(sq, out[b]); memcpy(out, t, sizeof t); }
+        for (int b = 0; b < 32; b++) t[b] = xs_apply(sq, sq[b]);
+        memcpy(sq, t, sizeof t);
+    }
+}
+uint32_t orc_xorshift32_jump(uint32_t state, uint64_t steps) { uint32_t m[32]; xs_power(m, steps); return xs_apply(m, state); }
+
+/* one coordinate of sample_ball's candidate, from one draw: rnd_float * 2 - 1 (ray.cl:49 / :62) */
+static inline float ball_coord(uint32_t u) { return (float)u * 2.3283064365387e-10f * 2.0f - 1.0f; }
+
+static inline uint32_t xs_step(uint32_t x) { x ^= x << 13; x ^= x >> 17; x ^= x << 5; return x; }   /* orc_xorshift32, inlined */
+
+enum { REJ_SEGMENTS = 4096 };
+typedef struct RejRun { uint32_t len, state, index; } RejRun;   /* rejected attempts in a row; the state and attempt index the run starts from */
+typedef struct RejSeg {                 /* one residue (attempt index mod 3) of one segment of the cycle */
+    RejRun head, tail, best;            /* the run before the first accepted attempt; after the last; the longest between two accepted ones */
+    int32_t accepted;                   /* some attempt of the residue was accepted (else head = tail = all of them) */
+} RejSeg;
+
+static void rej_count(OrcRejection* o, RejRun r)   /* a whole run: the longest so far, the first met from state 1 among equals */
+{
+    if (r.len > o->longest || (r.len == o->longest && r.len && r.index < o->index)) { o->longest = r.len; o->state = r.state; o->index = r.index; }
+}
+
+int orc_rejection_cycle(int32_t threads, OrcRejection* out)
+{
+    if (!out) return -1;
+    /* Attempt i starts from state s_i (s_0 = 1) and consumes draws s_{i+1}, s_{i+2}, s_{i+3}; the attempt that follows a rejected
+     * attempt i is i + 3.  The period 2^32 - 1 is a multiple of 3, so the three residues close on themselves. */
+    const uint64_t P = 0xffffffffull;
+    const uint64_t L = (P / REJ_SEGMENTS / 3 + 1) * 3;
+    const int S = (int)((P + L - 1) / L);
+    uint32_t* start = (uint32_t*)malloc(sizeof(uint32_t) * (size_t)(2 * S + 1));
+    RejSeg* seg = (RejSeg*)calloc((size_t)S * 3, sizeof(RejSeg));
+    uint64_t* rejected = (uint64_t*)calloc((size_t)S, sizeof(uint64_t));
+    if (!start || !seg || !rejected) { free(start); free(seg); free(rejected); return -1; }
+    uint32_t* end = start + S + 1;
+    uint32_t jump[32];
+    xs_power(jump, L);
+    start[0] = 1;
+    for (int s = 0; s < S; s++) start[s + 1] = xs_apply(jump, start[s]);
+    #pragma omp parallel for schedule(dynamic, 8) num_threads(clamp_threads(threads))
+    for (int s = 0; s < S; s++) {
+        const uint64_t first = (uint64_t)s * L, n = first + L <= P ? L : P - first;
+        RejSeg* r = &seg[3 * s];
+        RejRun run[3];
+        memset(run, 0, sizeof run);
+        uint32_t prev = start[s], a = xs_step(prev), b = xs_step(a), c = xs_step(b);
+        float x = ball_coord(a), y = ball_coord(b), z = ball_coord(c);
+        uint64_t rej = 0;
+        int k = 0;
+        for (uint64_t i = 0; i < n; i++) {
+            if (x * x + y * y + z * z > 1.0f) {
+                if (run[k].len++ == 0) { run[k].state = prev; run[k].index = (uint32_t)(first + i); }
+                rej++;
+            } else {
+                if (!r[k].accepted) { r[k].accepted = 1; r[k].head = run[k]; }
+                else if (run[k].len > r[k].best.len) r[k].best = run[k];
+                run[k].len = 0;
+            }
+            prev = a; a = b; b = c; c = xs_step(c);
+            x = y; y = z; z = ball_coord(c);
+            k = k == 2 ? 0 : k + 1;
+        }
+        for (k = 0; k < 3; k++) {
+            r[k].tail = run[k];
+            if (!r[k].accepted) r[k].head = run[k];
+        }
+        rejected[s] = rej;
+        end[s] = prev;
+    }
+    OrcRejection o;
+    memset(&o, 0, sizeof o);
+    o.states = P;
+    o.closed = 1;
+    for (int s = 0; s < S; s++) {           /* the walks join up (which checks the jump-ahead too) and return to state 1 after 2^32 - 1 steps */
+        if (end[s] != (s + 1 < S ? start[s + 1] : 1u)) o.closed = 0;
+        o.rejected += rejected[s];
+    }
+    for (int k = 0; k < 3; k++) {
+        RejRun carry = { 0, 0, 0 };
+        int open = 0;                       /* a run is being carried (it may have length 0: an accepted attempt ended the segment) */
+        for (int s = 0; s < 2 * S; s++) {   /* second lap: the run open at the end of the cycle joins the first segments' */
+            const RejSeg* g = &seg[3 * (s % S) + k];
+            if (s >= S && !open) break;
+            if (s < S) rej_count(&o, g->best);
+            RejRun joined = carry.len ? carry : g->head;
+            joined.len = carry.len + g->head.len;
+            if (!g->accepted) { carry = joined; continue; }   /* no accepted attempt in the whole segment */
+            if (open) rej_count(&o, joined);     /* (the run before the cycle's first accepted attempt waits for the second lap) */
+            if (s >= S) break;
+            carry = g->tail; open = 1;
+        }
+    }
+    free(start); free(seg); free(rejected);
+    *out = o;
     return 0;
 }

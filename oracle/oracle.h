@@ -35,7 +35,8 @@ enum { ORC_SCHED_S1 = 1, ORC_SCHED_S0 = 0 };
  * REFERENCE: near child first (bvh.cl:41-52), what a zero-filled config gives.
  * LATER_EXIT: the child with the greater slab exit distance first, ties to child 1 - the order of the HIP path's connect
  *     (rt355_kernels.h slab_any).  Changes nothing else: TLAS nodes, instance entry, BVH4 and every extend / focus traversal keep
- *     the reference's order, and a shadow ray's verdict does not depend on it - only connect's node_visits and prim_tests do. */
+ *     the reference's order, and a shadow ray's verdict does not depend on it - only connect's node_visits and prim_tests do.  (The
+ *     verdict of a ray whose direction has a component near FLT_MAX can: its primitive tests overflow, see traverse_bvh2_later_exit.) */
 enum { ORC_CONNECT_REFERENCE = 0, ORC_CONNECT_LATER_EXIT = 1 };
 
 typedef struct OrcScene {
@@ -85,6 +86,9 @@ void orc_connect(const RtShadowRay* shadow, int32_t n, const OrcScene* sc,
  * orc_connect adds to its counters for the same queue. */
 typedef struct OrcRayWork { uint32_t node_visits, prim_tests, tlas_visits, inst_visits, occluded; } OrcRayWork;
 void orc_connect_work(const RtShadowRay* shadow, int32_t n, const OrcScene* sc, const OrcConfig* cfg, OrcRayWork* work);
+/* orc_connect's traversal on rays given as they are traced: origin[i], dir[i] (xyz; w is taken as 0), reach tmax[i] (NULL: RT_REALLYFAR);
+ * occluded[i] = 1 iff a primitive is accepted with t < tmax[i].  orc_connect's record {I, L, dist} is the ray I + L * eps, L, dist - 2 eps. */
+void orc_occluded(const RtFloat4* origin, const RtFloat4* dir, const float* tmax, int32_t n, const OrcScene* sc, const OrcConfig* cfg, uint8_t* occluded);
 float orc_focus(int32_t x, int32_t y, const OrcScene* sc, const OrcConfig* cfg, const RtCamera* cam);
 
 /* One Renderer::RayTrace() (renderer.cpp:64-94) over pixels [firstPixel, firstPixel+n).
@@ -128,6 +132,19 @@ int orc_math_sweep(int32_t fn, int32_t firstBlock, int32_t nBlocks, uint64_t* ha
  * largest error (the smallest in magnitude among ties). */
 typedef struct OrcMathError { double max_err; float arg; uint64_t above; uint64_t count; } OrcMathError;
 int orc_math_error(int32_t fn, float lo, float hi, int32_t absolute, double bound, int32_t threads, OrcMathError* out);
+
+/* The RNG step is linear over GF(2): `steps` steps from `state` through a power of its 32x32 matrix (a jump-ahead). */
+uint32_t orc_xorshift32_jump(uint32_t state, uint64_t steps);
+/* sample_ball's rejection loop (ray.cl:49-53 / 62-69) over the RNG's whole cycle, walked once from state 1 in segments reached by
+ * jump-ahead (OpenMP; threads is capped at 16).  An attempt takes three draws, each mapped as the kernels map it -
+ * (float)u * 2.3283064365387e-10f * 2 - 1 - and is rejected when x*x + y*y + z*z > 1.0f (summed left to right, no contraction).  The
+ * loop entered with state s makes the attempts at s, s + 3 draws, s + 6 draws, ...: `longest` is the longest run of consecutively
+ * rejected attempts at that stride over every nonzero s; `state` the state the first run of that length on
+ * the walk from state 1 starts from, `index` steps after state 1 (the loop entered there makes longest + 1 attempts: 3 * (longest + 1)
+ * draws).  `states` is the number of states walked, `rejected` how many of the attempts starting from them are rejected, `closed`
+ * whether the segments joined up and the walk returned to state 1 after `states` steps. */
+typedef struct OrcRejection { uint64_t states, rejected; uint32_t longest, state, index; int32_t closed; } OrcRejection;
+int orc_rejection_cycle(int32_t threads, OrcRejection* out);
 
 #ifdef __cplusplus
 }

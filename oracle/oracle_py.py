@@ -42,6 +42,7 @@ def lib():
         L.orc_shade.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
         L.orc_connect.argtypes = [vp, i32, vp, vp, vp, vp]
         L.orc_connect_work.argtypes = [vp, i32, vp, vp, vp]
+        L.orc_occluded.argtypes = [vp, vp, vp, i32, vp, vp, vp]
         L.orc_focus.argtypes = [i32, i32, vp, vp, vp]
         L.orc_focus.restype = C.c_float
         L.orc_frame_work_bytes.argtypes = [i32, vp]
@@ -53,6 +54,11 @@ def lib():
         L.orc_math.argtypes = [i32, vp, vp, C.c_int64]
         L.orc_math_sweep.argtypes = [i32, i32, i32, vp, i32]
         L.orc_math_error.argtypes = [i32, C.c_float, C.c_float, i32, C.c_double, i32, vp]
+        L.orc_xorshift32.argtypes = [vp]
+        L.orc_xorshift32.restype = C.c_uint32
+        L.orc_xorshift32_jump.argtypes = [C.c_uint32, C.c_uint64]
+        L.orc_xorshift32_jump.restype = C.c_uint32
+        L.orc_rejection_cycle.argtypes = [i32, vp]
         _lib = L
     return _lib
 
@@ -65,6 +71,37 @@ def seed_stream(first, n):
     s = np.zeros(n, dtype=np.uint32)
     lib().orc_seed_stream(_p(s), first, n)
     return s
+
+
+def nonzero_seeds(seeds, what):
+    """State 0 is the RNG's fixed point: every draw from it is 0.0f and sample_ball's rejection loop never ends.
+    The oracle has the same loop, so a zero seed is refused here, as rt_set_seeds refuses it, instead of spinning."""
+    if seeds is not None:
+        z = np.flatnonzero(np.asarray(seeds) == 0)
+        if len(z):
+            raise ValueError(f"{what}: seeds[{int(z[0])}] is 0, the fixed point of the RNG ({len(z)} of {np.size(seeds)} seeds are 0)")
+    return seeds
+
+
+def xorshift32(state, steps=1):
+    """The state after `steps` RNG steps from `state` (orc_xorshift32; more than a few steps go through orc_xorshift32_jump)."""
+    if steps > 64:
+        return int(lib().orc_xorshift32_jump(int(state), int(steps)))
+    s = C.c_uint32(int(state))
+    for _ in range(steps):
+        lib().orc_xorshift32(C.addressof(s))
+    return int(s.value)
+
+
+OrcRejection = np.dtype([("states", "<u8"), ("rejected", "<u8"), ("longest", "<u4"), ("state", "<u4"), ("index", "<u4"), ("closed", "<i4")], align=True)
+
+
+def rejection_cycle():
+    """orc_rejection_cycle: sample_ball's rejection loop over the RNG's whole cycle; dict states, rejected, longest, state, index, closed."""
+    r = np.zeros((), OrcRejection)
+    if lib().orc_rejection_cycle(math_threads(), r.ctypes.data_as(C.c_void_p)) != 0:
+        raise ValueError("orc_rejection_cycle: bad argument")
+    return {k: int(r[k]) for k in r.dtype.names}
 
 
 def postproc(accum, frames, vignette=0.0, gamma=0.9, chromatic=0.0):
@@ -152,6 +189,7 @@ class Oracle:
     def generate(self, cam, first_pixel, n, seeds, antiAliasing=1):
         from magr_ray_tracer_amd import _lib as W
         rays = np.zeros(n, dtype=W.Ray)
+        nonzero_seeds(seeds, "Oracle.generate")
         c = np.ascontiguousarray(cam)
         lib().orc_generate(_p(rays), n, first_pixel, self._cfg, c.ctypes.data_as(C.c_void_p), antiAliasing, _p(seeds))
         return rays
@@ -166,6 +204,7 @@ class Oracle:
     def shade(self, rays, accum, seeds, shadow_capacity=None):
         from magr_ray_tracer_amd import _lib as W
         n = len(rays)
+        nonzero_seeds(seeds, "Oracle.shade")
         out = np.zeros(max(n, 1), dtype=W.Ray)
         sh = np.zeros(max(shadow_capacity or n, 1), dtype=W.ShadowRay)
         nOut, nSh = C.c_int32(0), C.c_int32(0)
@@ -186,6 +225,17 @@ class Oracle:
             lib().orc_connect_work(_p(shadow), len(shadow), self._sc, self._cfg, _p(work))
         return work
 
+    def occluded(self, origins, dirs, tmax=None):
+        """orc_occluded: connect's traversal on rays (n, 3) or (n, 4) float32 with reach tmax (None: RT_REALLYFAR); n bools."""
+        n = len(origins)
+        o4, d4 = np.zeros((n, 4), np.float32), np.zeros((n, 4), np.float32)
+        o4[:, :3], d4[:, :3] = np.asarray(origins, np.float32)[:, :3], np.asarray(dirs, np.float32)[:, :3]
+        t = None if tmax is None else np.ascontiguousarray(np.broadcast_to(np.asarray(tmax, np.float32), (n,)))
+        out = np.zeros(n, np.uint8)
+        if n:
+            lib().orc_occluded(_p(o4), _p(d4), None if t is None else _p(t), n, self._sc, self._cfg, _p(out))
+        return out.astype(bool)
+
     def focus(self, x, y, cam):
         c = np.ascontiguousarray(cam)
         return np.float32(lib().orc_focus(x, y, self._sc, self._cfg, c.ctypes.data_as(C.c_void_p)))
@@ -198,6 +248,7 @@ class Oracle:
             accum = np.zeros((self.height, self.width, 4), dtype=np.float32)
         if seeds is None:
             seeds = seed_stream(y0 * self.width, n)
+        nonzero_seeds(seeds, "Oracle.render")
         e, c = np.zeros((), dtype=OrcCounters), np.zeros((), dtype=OrcCounters)
         cm = np.ascontiguousarray(cam)
         lib().orc_render_bands(self._sc, self._cfg, cm.ctypes.data_as(C.c_void_p), antiAliasing, y0, y1, frames, threads,

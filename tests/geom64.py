@@ -39,6 +39,13 @@ GRAZE_MIN = 1e-3
 SPHERE_TANGENT = 1e-5
 # |D|^2 farther than this from 1: the kernel's sphere test (written for a unit D) does not measure t in ray-parameter units
 NONUNIT_D = 1e-3
+# A direction so long that its product with two lengths of the scene leaves float32's normal range: the triangle test's det = e1 . (D x e2)
+# overflows, or its reciprocal is subnormal or zero - then u = v = t = 0 whatever the triangle, and a dot product that reached infinity
+# gives a NaN, which no comparison of the acceptance rules rejects.  Float32 decides nothing for such a ray (6: a dot of three cross
+# product components of two terms each; the lengths: the largest vertex coordinate or sphere extent of the instance, which also bounds
+# O - v0 for an origin inside the scene.  An origin far outside does not enter: that ray is decided by the slab tests, whose
+# arithmetic stays ordered up to infinity).
+PRODUCT_CEIL = 2.0 ** 126
 FAR = np.float32(1e30)      # RT_REALLYFAR: ray.t of an extension ray before traversal
 
 # minimum decidable fraction of a ray set: a set must not pass by being all ambiguous
@@ -253,8 +260,13 @@ def closest_hit(gt, O, D, tmax=None):
     if key in cache:
         return cache[key]
     groups = []
+    lost = np.zeros(n, bool)
     for st, (A, tr, _) in zip(gt.sets, instance_maps(gt.sa)):
         Oi, Di = O @ A.T + tr, D @ A.T
+        size = float(np.abs(st["tri"]).max()) if len(st["tri"]) else 0.0
+        if len(st["sph_r"]):
+            size = max(size, float((np.abs(st["sph_c"]).max(axis=1) + st["sph_r"]).max()))
+        lost |= 6.0 * np.abs(Di).max(axis=1) * size * size >= PRODUCT_CEIL
         # the instance transform rounds the origin to eps * (|A| |O| + |t|): carried as an extra origin magnitude
         ident = np.array_equal(A, np.eye(3)) and not tr.any()
         extra = np.zeros(n) if ident else np.abs(A).sum(1).max() * _norm(O) + _norm(tr)
@@ -282,7 +294,7 @@ def closest_hit(gt, O, D, tmax=None):
     hit = np.isfinite(out["t"])
     # decidable: no ambiguous contact and no competitor within the error bounds of the winner (miss: none anywhere before tmax)
     lim = np.where(hit, out["t"] + out["tol"], np.inf)
-    dec = np.where(hit, (out["amb"] > lim) & (out["t2"] > lim), out["amb"] == np.inf)
+    dec = np.where(hit, (out["amb"] > lim) & (out["t2"] > lim), out["amb"] == np.inf) & ~lost
     out.update(hit=hit, decidable=dec)
     cache[key] = out
     return out

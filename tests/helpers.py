@@ -52,7 +52,9 @@ def oracle_for(sa, W, H, **variant):
     """The oracle a device context of this configuration is held to, connect's node and triangle counts included.  A `variant` is what
     Device takes; of it the oracle reads the reference's settings and `accel`.  Over a BVH2 the kernels' connect walks a BLAS in its
     own any-hit order (rt355_kernels.h slab_any), which the oracle restates as connect_order LATER_EXIT; over a BVH4 it keeps the
-    reference's slot order.  Nothing but connect's node_visits and prim_tests depends on the choice (tests/test_anyhit_cpu.py)."""
+    reference's slot order.  Nothing but connect's node_visits and prim_tests depends on the choice (tests/test_anyhit_cpu.py) - for
+    rays whose primitive tests float32 can compute: the verdict of a ray with a direction component near FLT_MAX may depend on it, and
+    does at tmax = +inf (tests/test_edge_rays_cpu.py pins those rays)."""
     from oracle.oracle_py import LATER_EXIT, REFERENCE_ORDER, Oracle
     v = {k: x for k, x in variant.items() if k in ("shading", "sampling", "accel", "russian_roulette", "filter_fireflies", "max_bounces", "schedule")}
     return Oracle(sa, W, H, connect_order=REFERENCE_ORDER if v.get("accel", 0) == 1 else LATER_EXIT, **v)
