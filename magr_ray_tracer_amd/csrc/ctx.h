@@ -1,0 +1,64 @@
+// ctx.h — a rendering context (RtCtx, include/rt355.h) as rt355.hip, which owns it, and group.hip, which runs several of them as the
+// lanes of a group, both see it.  group.hip goes through the public rt_* calls; of the struct it reads and writes `stream`, `home`,
+// `queued`, `cfg`, `nPix`, `firstPixel` and `q.accum`, and of rt355.hip's internals it calls what is declared at the end of this file.
+#pragma once
+#include <algorithm>
+#include <memory>
+#include <vector>
+#include "rt355_dev.h"
+#include "scene_dev.h"
+
+struct RtCtx {
+    RtConfig cfg{};
+    hipStream_t stream = nullptr;         // where this context's work is queued: `home`, unless a group has moved its frames (rt_group_render)
+    hipStream_t home = nullptr;           // the context's own stream
+    bool queued = true;                   // asynchronous work queued since a group marked the end of this context's last frame
+    rt355dev::DevScene sc{};
+    rt355dev::DevQueues q{};
+    rt355dev::DevVariant var{};
+    int nPix = 0, firstPixel = 0, gridMax = 0;
+    bool sceneLoaded = false, ownAccum = true;
+    std::shared_ptr<scenedev::SceneBag> scene;   // shared by the contexts of rt_share_scene, freed with the last of them
+    uint64_t sceneGen = 0;                // the SceneBag generation this context's traversal configuration was derived for
+    bool singleBlas = false;              // the TLAS root is a leaf (this, sc, layout, stackEntries, tlasDepth, nInterior: the copy's facts, assigned by adopt_scene only)
+    std::vector<void*> queueAllocs;
+    float* dFocus = nullptr;
+    RtRay* dRayIO = nullptr; // debug import/export staging (lazy)
+    uint64_t frames = 0, primaryRays = 0;
+    // profiling
+    struct Ev { hipEvent_t a, b; int stage; };
+    std::vector<Ev> evPool; size_t evUsed = 0;
+    RtStageTimes times{};
+    int tlasDepth = 0;
+    int layout = 0;   // 0 = traverse the reference arrays as uploaded, 1 = derived pair/triangle-record layout
+    int trav = 0;           // the traversal kernels (Traversal, set by configure_traversal)
+    int coherent = 1;       // RT355_COHERENT: wave-uniform node records through the scalar cache on bounce 0 (1), every bounce of the TLAS kernel (2, lab), off (0)
+    uint32_t* dSpill = nullptr; size_t spillWords = 0;
+    int xcdFirst = -1;      // the XCD this context's sparse queues start on (PersistTune.xcdFirst)
+    int spillCap = 0;       // LDS stack entries per lane of a spilling kernel, set by configure_traversal (RT355_SPILL_CAP: tests force the spill path with a tiny cap, >= 6)
+    int nInterior = 0;          // records of the dense pair table (their ids must fit the 29-bit field of the tagged stack entries)
+    bool cursorUsed[2 * (RT_MAX_BOUNCES + 2)] = {};   // work-queue heads consumed since the last k_begin_frame
+    bool shadeRun[RT_MAX_BOUNCES + 1] = {};           // shade(b) launched since the last k_begin_frame
+    bool generated = false;                           // generate launched since the last k_begin_frame
+    int stackEntries = RT_BVH2_STACK, persistGrid = 0, persistGridConnect = 0;
+    rt355dev::PersistTune tune{}, tuneConnect{}, tune4{};   // extend (BVH2), connect, extend (BVH4): set by configure_traversal
+    float4* dPostF = nullptr; uchar4* dPostB = nullptr;   // post-processing outputs (lazy)
+    int32_t* dSteps = nullptr;   // per-ray `steps` buffer, only bound while rt_debug_enable_steps is on
+    // rt_trace's own DevQueues view (lazy): count, cursor and fault words and a counter table that no frame reads or writes, and queue
+    // arrays for the batches that are not traced in the caller's arrays, grown to the largest pass so far
+    struct TraceView { rt355dev::DevQueues q{}; bool ready = false; std::vector<void*> words; float4* rays[3] = {}; size_t cap = 0; } tv;
+    int shadeTile = rt355dev::kTile;   // k_shade tile = workgroup size: kTile (512), or 256 for contexts that share the GPU (RtConfig.shade_blocks_per_cu > 0)
+    int shadeGrid = 1024;   // workgroups of k_shade (what the CUs hold at once; the kernel does not depend on it); set in rt_create
+    // The instantiations of the kernels that reach one of the seven builtins, for this context's arithmetic (cfg.builtins, resolved to
+    // RT_BUILTINS_IEEE or RT_BUILTINS_REFERENCE), shading, tile and accel: chosen once by choose_builtin_kernels (rt_create)
+    void (*kGenerate)(rt355dev::DevQueues, RtCamera, int, int) = nullptr;
+    void (*kShade)(rt355dev::DevScene, rt355dev::DevQueues, rt355dev::DevVariant, int) = nullptr;
+    void (*kFocus)(rt355dev::DevScene, RtCamera, int, int, int, int, float*) = nullptr;
+};
+
+static inline dim3 grid_for(int n) { return dim3((unsigned)std::max(1, (n + rt355dev::kBlock - 1) / rt355dev::kBlock)); }
+// rt355.hip, for group.hip (hidden: neither is exported from the library)
+__attribute__((visibility("hidden"))) void ctx_free(RtCtx* ctx);   // every owned resource; safe on a partially constructed context
+// rt_postproc's work on the accumulator it is handed: the context's own, or a group's sum of its lanes'
+__attribute__((visibility("hidden"))) int postproc(RtCtx* ctx, const float4* accum, int32_t frames, float vignette, float gamma, float chromatic,
+                                                    RtFloat4* outF32, uint8_t* outRGBA8);

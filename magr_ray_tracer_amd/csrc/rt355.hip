@@ -1,10 +1,11 @@
-// rt355.hip — C-ABI implementation (include/rt355.h): device memory, streams, launch
-// sequence.  This is the replacement for the reference's OpenCL Kernel/Buffer dispatch in
-// Renderer (src/renderer.cpp:64-94,142-263,289-301).  No CPU fallback exists here.
+// rt355.hip — the rendering context of the C-ABI (include/rt355.h; RtCtx, ctx.h): its device memory and stream, the traversal
+// configuration it derives from the scene copy it holds (scene.hip) and trace_launch, which maps a stage to a kernel launch; the stages
+// and rt_render, rt_trace, the read-backs and debug exports, post-processing.  Every kernel of a frame is compiled here
+// (rt355_kernels.h).  This is the replacement for the reference's OpenCL Kernel/Buffer dispatch in Renderer
+// (src/renderer.cpp:64-94,142-263,289-301).  No CPU fallback exists here.  Lane groups live in group.hip, the math probes in math_debug.hip.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <cmath>
 #include <cstdlib>
@@ -15,7 +16,7 @@
 #include <vector>
 #include "../../include/rt355.h"
 #include "rt355_kernels.h"
-#include "scene_dev.h"
+#include "ctx.h"
 
 using namespace rt355dev;
 using namespace scenedev;
@@ -32,66 +33,6 @@ static constexpr int kFitSeven = 22, kBackupWords = 10, kSpillCap = kFitSeven - 
 static thread_local std::string g_err;
 int rt355_set_error(int code, const char* msg) { g_err = msg; return code; }   // for every source file of this library (fail, build_fail)
 
-struct RtCtx {
-    RtConfig cfg{};
-    hipStream_t stream = nullptr;         // where this context's work is queued: `home`, unless a group has moved its frames (rt_group_render)
-    hipStream_t home = nullptr;           // the context's own stream
-    bool queued = true;                   // asynchronous work queued since a group marked the end of this context's last frame
-    DevScene sc{};
-    DevQueues q{};
-    DevVariant var{};
-    int nPix = 0, firstPixel = 0, gridMax = 0;
-    bool sceneLoaded = false, ownAccum = true;
-    std::shared_ptr<SceneBag> scene;      // shared by the contexts of rt_share_scene, freed with the last of them
-    uint64_t sceneGen = 0;                // the SceneBag generation this context's traversal configuration was derived for
-    bool singleBlas = false;              // the TLAS root is a leaf (this, sc, layout, stackEntries, tlasDepth, nInterior: the copy's facts, assigned by adopt_scene only)
-    std::vector<void*> queueAllocs;
-    float* dFocus = nullptr;
-    RtRay* dRayIO = nullptr; // debug import/export staging (lazy)
-    uint64_t frames = 0, primaryRays = 0;
-    // profiling
-    struct Ev { hipEvent_t a, b; int stage; };
-    std::vector<Ev> evPool; size_t evUsed = 0;
-    RtStageTimes times{};
-    int tlasDepth = 0;
-    int layout = 0;   // 0 = traverse the reference arrays as uploaded, 1 = derived pair/triangle-record layout
-    int trav = 0;           // the traversal kernels (Traversal, set by configure_traversal)
-    int coherent = 1;       // RT355_COHERENT: wave-uniform node records through the scalar cache on bounce 0 (1), every bounce of the TLAS kernel (2, lab), off (0)
-    uint32_t* dSpill = nullptr; size_t spillWords = 0;
-    int xcdFirst = -1;      // the XCD this context's sparse queues start on (PersistTune.xcdFirst)
-    int spillCap = kSpillCap;   // LDS stack entries per lane of a spilling kernel (RT355_SPILL_CAP: tests force the spill path with a tiny cap, >= 6)
-    int nInterior = 0;          // records of the dense pair table (their ids must fit the 29-bit field of the tagged stack entries)
-    bool cursorUsed[2 * (RT_MAX_BOUNCES + 2)] = {};   // work-queue heads consumed since the last k_begin_frame
-    bool shadeRun[RT_MAX_BOUNCES + 1] = {};           // shade(b) launched since the last k_begin_frame
-    bool generated = false;                           // generate launched since the last k_begin_frame
-    int stackEntries = RT_BVH2_STACK, persistGrid = 0, persistGridConnect = 0;
-    PersistTune tune{}, tuneConnect{}, tune4{};   // extend (BVH2), connect, extend (BVH4): set by configure_traversal
-    float4* dPostF = nullptr; uchar4* dPostB = nullptr;   // post-processing outputs (lazy)
-    int32_t* dSteps = nullptr;   // per-ray `steps` buffer, only bound while rt_debug_enable_steps is on
-    // rt_trace's own DevQueues view (lazy): count, cursor and fault words and a counter table that no frame reads or writes, and queue
-    // arrays for the batches that are not traced in the caller's arrays, grown to the largest pass so far
-    struct TraceView { DevQueues q{}; bool ready = false; std::vector<void*> words; float4* rays[3] = {}; size_t cap = 0; } tv;
-    int shadeTile = kTile;  // k_shade tile = workgroup size: kTile (512), or 256 for contexts that share the GPU (RtConfig.shade_blocks_per_cu > 0)
-    int shadeGrid = 1024;   // workgroups of k_shade (what the CUs hold at once; the kernel does not depend on it); set in rt_create
-    // The instantiations of the kernels that reach one of the seven builtins, for this context's arithmetic (cfg.builtins, resolved to
-    // RT_BUILTINS_IEEE or RT_BUILTINS_REFERENCE), shading, tile and accel: chosen once by choose_builtin_kernels (rt_create)
-    void (*kGenerate)(DevQueues, RtCamera, int, int) = nullptr;
-    void (*kShade)(DevScene, DevQueues, DevVariant, int) = nullptr;
-    void (*kFocus)(DevScene, RtCamera, int, int, int, int, float*) = nullptr;
-};
-// RT_BUILTINS_DEFAULT is IEEE in the shipped library; -DRT355_REF_BUILTINS (librt355_refb.so) changes that and nothing else
-#ifdef RT355_REF_BUILTINS
-static constexpr int32_t kDefaultBuiltins = RT_BUILTINS_REFERENCE;
-#else
-static constexpr int32_t kDefaultBuiltins = RT_BUILTINS_IEEE;
-#endif
-static bool resolve_builtins(int32_t word, int32_t* mode)
-{
-    if (word == RT_BUILTINS_DEFAULT) word = kDefaultBuiltins;
-    if (word != RT_BUILTINS_IEEE && word != RT_BUILTINS_REFERENCE) return false;
-    *mode = word;
-    return true;
-}
 template <bool REFB> static void choose_builtin_kernels_of(RtCtx* ctx)
 {
     const bool nee = ctx->cfg.shading == RT_SHADING_NEE, small = ctx->shadeTile == 256;
@@ -215,7 +156,6 @@ static int tlas_stack_entries(const RtCtx* c) { return c->stackEntries + c->tlas
 static int tlas_lds_entries(const RtCtx* c) { return spill_trav(c) ? c->spillCap : tlas_stack_entries(c); }
 static size_t tlas_column_bytes(int entries) { return (size_t)(entries + kBackupWords) * kBlock * sizeof(uint32_t); }
 static size_t tlas_stack_bytes(const RtCtx* c) { return tlas_column_bytes(tlas_lds_entries(c)); }
-static inline dim3 grid_for(int n) { return dim3((unsigned)std::max(1, (n + kBlock - 1) / kBlock)); }
 
 // The traversal launch of a stage: the one place that maps (stage, bounce, steps wanted) to a kernel instantiation, its grid, its dynamic
 // LDS and its PersistTune.  A persistent kernel takes (scene, queues, b0, b1, renderBVH, tune); where none runs, the nested one-ray-per-lane
@@ -419,7 +359,6 @@ static void ev_collect(RtCtx* c) // call after a stream sync
 }
 
 // ---- create / destroy ----------------------------------------------------------------
-static void ctx_free(RtCtx* ctx);
 extern "C" int rt_create(const RtConfig* cfg, RtCtx** out)
 {
     if (!cfg || !out) return fail(RT_E_INVALID, "rt_create: null argument");
@@ -507,7 +446,7 @@ extern "C" int rt_create(const RtConfig* cfg, RtCtx** out)
     return RT_OK;
 }
 
-static void ctx_free(RtCtx* ctx)   // every owned resource; safe on a partially constructed context
+void ctx_free(RtCtx* ctx)   // every owned resource; safe on a partially constructed context (ctx.h: group.hip frees its lanes with it)
 {
     if (!ctx) return;
     (void)hipSetDevice(ctx->cfg.device);
@@ -555,8 +494,8 @@ static int configure_traversal(RtCtx* ctx)
     if (const char* t = getenv("RT355_SPILL_CAP")) { const int v = atoi(t); if (v >= 6 && v <= 64) { ctx->spillCap = v; forceSpill = true; } }
     // (columns of up to 22 entries stay whole in LDS, backup beside them: 5-6 workgroups per CU without the spill branches beat 7 with them,
     // 1,923 against 1,849 and 1,327 against 1,310 M samples/s on two-BLAS scenes of 16 and 22 entries - tools/middepth_tlas.py)
-    if (ctx->trav == TRAV_TLAS && (tlas_stack_entries(ctx) > kFitSeven || forceSpill) && tlas_stack_entries(ctx) > ctx->spillCap &&
-        !(getenv("RT355_NO_SPILL") && atoi(getenv("RT355_NO_SPILL"))))
+    const bool noSpill = getenv("RT355_NO_SPILL") && atoi(getenv("RT355_NO_SPILL"));
+    if (ctx->trav == TRAV_TLAS && (tlas_stack_entries(ctx) > kFitSeven || forceSpill) && tlas_stack_entries(ctx) > ctx->spillCap && !noSpill)
         ctx->trav = TRAV_TLAS_SPILL;
     if (ctx->trav == TRAV_TLAS && tlas_stack_entries(ctx) > RT_BVH4_STACK + 9) ctx->trav = TRAV_NESTED;
     if (ctx->trav == TRAV_BVH4_TLAS) {
@@ -565,7 +504,6 @@ static int configure_traversal(RtCtx* ctx)
         // spill instantiation too, and the nested loops where RT355_NO_SPILL forbids that - no launch the runtime would reject
         hipDeviceProp_t prop;
         HIPCHK(hipGetDeviceProperties(&prop, ctx->cfg.device));
-        const bool noSpill = getenv("RT355_NO_SPILL") && atoi(getenv("RT355_NO_SPILL"));
         const bool fits = tlas_column_bytes(tlas_stack_entries(ctx)) <= prop.sharedMemPerBlock;
         const bool canSpill = !noSpill && tlas_stack_entries(ctx) > ctx->spillCap && tlas_column_bytes(ctx->spillCap) <= prop.sharedMemPerBlock;
         if ((tlas_stack_entries(ctx) > kFitSeven || forceSpill || !fits) && canSpill) ctx->trav = TRAV_BVH4_TLAS_SPILL;
@@ -710,6 +648,16 @@ static int sync_scene_config(RtCtx* ctx)
     if (!ctx->scene || ctx->sceneGen == ctx->scene->generation) return RT_OK;
     return adopt_scene(ctx);
 }
+// The last step of every way to a scene: the context holds `bag` and is usable again once it has taken the copy over
+static int bind_scene(RtCtx* ctx, const std::shared_ptr<SceneBag>& bag)
+{
+    scene_hold(ctx, bag);
+    ctx->sceneLoaded = false; ctx->trav = TRAV_NESTED;
+    const int rc = adopt_scene(ctx);
+    if (rc != RT_OK) { scene_release(ctx); return rc; }
+    ctx->sceneLoaded = true;
+    return RT_OK;
+}
 
 extern "C" int rt_upload_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t nPrims, const RtMaterial* mats, int32_t nMats,
                                const RtFloat4* textures, int32_t nTexels, const uint32_t* lights, int32_t nLights,
@@ -723,14 +671,12 @@ extern "C" int rt_upload_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t nPr
     if (const int rc = validate_scene(ctx->cfg.accel, in, &stackEntries, &texPad, &tlasDepth)) return rc;
     HIPCHK(hipSetDevice(ctx->cfg.device));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    scene_hold(ctx, std::make_shared<SceneBag>());   // (a copy shared with other contexts lives on with them)
-    ctx->scene->device = ctx->cfg.device;
+    scene_release(ctx);   // the bound copy goes before the new one is made (one shared with other contexts lives on with them)
     ctx->sceneLoaded = false; ctx->trav = TRAV_NESTED;   // nothing usable until this upload has succeeded
-    int rc = upload_scene(*ctx->scene, ctx->cfg.accel, ctx->cfg.extend_variant, in, stackEntries, texPad, tlasDepth);
-    if (rc == RT_OK) rc = adopt_scene(ctx);
-    if (rc != RT_OK) { scene_release(ctx); return rc; }
-    ctx->sceneLoaded = true;
-    return RT_OK;
+    auto bag = std::make_shared<SceneBag>();
+    bag->device = ctx->cfg.device;
+    if (const int rc = upload_scene(*bag, ctx->cfg.accel, ctx->cfg.extend_variant, in, stackEntries, texPad, tlasDepth)) return rc;
+    return bind_scene(ctx, bag);
 }
 
 // rt_upload_scene with the BVH2 given for any context.  A BVH4 context collapses it on the device (scene.hip, collapse.hip) and keeps it,
@@ -757,12 +703,7 @@ extern "C" int rt_upload_scene_bvh2(RtCtx* ctx, const RtPrimitive* prims, int32_
     auto bag = std::make_shared<SceneBag>();
     bag->device = ctx->cfg.device;
     if (const int rc = upload_scene(*bag, ctx->cfg.accel, ctx->cfg.extend_variant, in, stackEntries, texPad, tlasDepth, &blas4)) return rc;
-    scene_hold(ctx, bag);
-    ctx->sceneLoaded = false; ctx->trav = TRAV_NESTED;
-    const int rc = adopt_scene(ctx);
-    if (rc != RT_OK) { scene_release(ctx); return rc; }
-    ctx->sceneLoaded = true;
-    return RT_OK;
+    return bind_scene(ctx, bag);
 }
 
 // A second context on the same device renders the scene `from` holds: it takes the device copy (uploaded arrays and derived layouts)
@@ -778,12 +719,7 @@ extern "C" int rt_share_scene(RtCtx* ctx, RtCtx* from)
         return fail(RT_E_INVALID, "rt_share_scene: the contexts differ in accel / extend_variant, which the derived layout depends on");
     HIPCHK(hipSetDevice(ctx->cfg.device));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    ctx->sceneLoaded = false;
-    scene_hold(ctx, from->scene);
-    const int rc = adopt_scene(ctx);
-    if (rc != RT_OK) { scene_release(ctx); return rc; }
-    ctx->sceneLoaded = true;
-    return RT_OK;
+    return bind_scene(ctx, from->scene);
 }
 
 // ---- in-place updates and rebuilds of the copy a context holds (scene.hip) ---------------------------------------------------------
@@ -796,12 +732,6 @@ extern "C" int rt_update_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t fir
         return fail(RT_E_UNSUPPORTED, "rt_update_scene: BVH4 contexts cannot refit (rt_rebuild_scene a copy bound with rt_upload_scene_bvh2, or rebuild and upload)");
     return update_scene(*ctx->scene, prims, first, count, blas, nBlas, stats);
 }
-extern "C" int rt_group_update_scene(RtGroup* g, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
-                                     RtUpdateStats* stats)
-{
-    if (!g) return fail(RT_E_INVALID, "rt_group_update_scene: null group");
-    return rt_update_scene(rt_group_lane(g, 0), prims, first, count, blas, nBlas, stats);   // every lane holds lane 0's copy
-}
 extern "C" int rt_rebuild_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
                                 int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats)
 {
@@ -811,12 +741,6 @@ extern "C" int rt_rebuild_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t fi
         return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: a BVH4 copy bound through rt_upload_scene has lost its BVH2 and cannot rebuild in place "
                     "(bind the BVH2 with rt_upload_scene_bvh2, or build on the host and upload)");
     return rebuild_scene(*ctx->scene, prims, first, count, blas, nBlas, builder, opts, stats);
-}
-extern "C" int rt_group_rebuild_scene(RtGroup* g, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
-                                      int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats)
-{
-    if (!g) return fail(RT_E_INVALID, "rt_group_rebuild_scene: null group");
-    return rt_rebuild_scene(rt_group_lane(g, 0), prims, first, count, blas, nBlas, builder, opts, stats);   // every lane holds lane 0's copy
 }
 extern "C" int rt_debug_rebuild_allocations(RtCtx* ctx, int64_t* count)
 {
@@ -1362,564 +1286,26 @@ extern "C" int rt_debug_get_steps(RtCtx* ctx, int32_t* out, int32_t capacity, in
     return RT_OK;
 }
 
-// ---- the kernels' math functions on their own (rt_debug_math, tests/test_gpu_math.py) ---------------------------------
-// Each case calls the function the renderer calls; nothing here restates one.
-// REFB as in rt355_kernels.h; the REFERENCE set has no acos / atan of its own (it calls acospi / atan2pi inside the texel lookup only).
-template <bool REFB> static __device__ __forceinline__ uint32_t math_one(int fn, uint32_t bits)
-{
-    const float x = __uint_as_float(bits);
-    float r;
-    switch (fn) {
-    case RT_MATH_EXP: r = rt_expf<REFB>(x); break;
-    case RT_MATH_SIN: r = rt_sinf<REFB>(x); break;
-    case RT_MATH_COS: r = rt_cosf<REFB>(x); break;
-    case RT_MATH_F2I: return (uint32_t)f2i_gpu(x);
-    case RT_MATH_ACOS: if constexpr (!REFB) { r = rt_acosf(x); break; }   // REFB: not a function of that set (the host refuses it)
-    case RT_MATH_ATAN: if constexpr (!REFB) { r = rt_atan2f(x, 1.0f); break; }
-    default: r = 0.0f; break;
-    }
-    return __float_as_uint(r);
-}
-template <bool REFB>
-__global__ __launch_bounds__(kBlock) void k_debug_math(int fn, const uint32_t* in, uint32_t* out, int64_t n)
-{
-    for (int64_t i = blockIdx.x * (int64_t)kBlock + threadIdx.x; i < n; i += (int64_t)gridDim.x * kBlock) {
-        const uint32_t* a = in;
-        uint32_t* o = out;
-        switch (fn) {
-        case RT_MATH_SPHERE_TEXEL: {
-            const uint32_t* e = a + 6 * i;
-            const float4 N = mk4(__uint_as_float(e[0]), __uint_as_float(e[1]), __uint_as_float(e[2]), __uint_as_float(e[3]));
-            int x, y;
-            sphere_texel_xy<REFB>(N, (int)e[4], (int)e[5], x, y);
-            o[2 * i] = (uint32_t)x; o[2 * i + 1] = (uint32_t)y;
-        } break;
-        case RT_MATH_NORMALIZE4:
-        case RT_MATH_LENGTH4: {
-            const uint32_t* e = a + 4 * i;
-            const float4 v = mk4(__uint_as_float(e[0]), __uint_as_float(e[1]), __uint_as_float(e[2]), __uint_as_float(e[3]));
-            if (fn == RT_MATH_LENGTH4) { o[i] = __float_as_uint(length4<REFB>(v)); break; }
-            const float4 r = normalize4<REFB>(v);
-            o[4 * i] = __float_as_uint(r.x); o[4 * i + 1] = __float_as_uint(r.y); o[4 * i + 2] = __float_as_uint(r.z); o[4 * i + 3] = __float_as_uint(r.w);
-        } break;
-        case RT_MATH_ATAN2: if constexpr (!REFB) { o[i] = __float_as_uint(rt_atan2f(__uint_as_float(a[2 * i]), __uint_as_float(a[2 * i + 1]))); break; }   // REFB: as in math_one
-        default: o[i] = math_one<REFB>(fn, a[i]); break;
-        }
-    }
-}
-static constexpr int kSweepPerThread = 64;   // a workgroup hashes 256 x 64 = 2^14 inputs; a block of 2^20 takes 64 workgroups
-template <bool REFB>
-__global__ __launch_bounds__(kBlock) void k_debug_math_sweep(int fn, uint32_t firstBlock, unsigned long long* hashes)
-{
-    __shared__ unsigned long long part[kBlock];
-    constexpr uint32_t perGroup = kBlock * kSweepPerThread, groupsPerBlock = (1u << RT_MATH_SWEEP_BLOCK_BITS) / perGroup;
-    const uint32_t blk = blockIdx.x / groupsPerBlock;
-    const uint32_t base = ((firstBlock + blk) << RT_MATH_SWEEP_BLOCK_BITS) + (blockIdx.x % groupsPerBlock) * perGroup;
-    unsigned long long h = 0;
-    for (int k = 0; k < kSweepPerThread; k++) {
-        const uint32_t bits = base + (uint32_t)k * kBlock + threadIdx.x;
-        uint32_t r = math_one<REFB>(fn, bits);
-        if (fn != RT_MATH_F2I && (r & 0x7fffffffu) > 0x7f800000u) r = 0x7fc00000u;
-        unsigned long long z = ((unsigned long long)bits << 32 | r) + 0x9e3779b97f4a7c15ull;   // splitmix64
-        z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-        z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-        h += z ^ (z >> 31);
-    }
-    part[threadIdx.x] = h;
-    __syncthreads();
-    for (int s = kBlock / 2; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) part[threadIdx.x] += part[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) atomicAdd(&hashes[blk], part[0]);
-}
-static int math_device(const char* who)
-{
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(RT_E_DEVICE, "%s: no HIP device visible (this library has no CPU path)", who);
-    HIPCHK(hipSetDevice(0));
-    return RT_OK;
-}
-extern "C" int rt_debug_math_mode(int32_t builtins, int32_t fn, const void* in, void* out, int64_t n)
-{
-    int32_t mode;
-    if (!resolve_builtins(builtins, &mode)) return fail(RT_E_INVALID, "rt_debug_math: builtins = %d is none of RT_BUILTINS_DEFAULT (0), RT_BUILTINS_IEEE (1), RT_BUILTINS_REFERENCE (2)", builtins);
-    const bool refb = mode == RT_BUILTINS_REFERENCE;
-    static const int inWords[] = { 1, 1, 1, 1, 1, 1, 2, 6, 4, 4 }, outWords[] = { 1, 1, 1, 1, 1, 1, 1, 2, 4, 1 };
-    if (fn < RT_MATH_EXP || fn > RT_MATH_LENGTH4 || n < 0 || (n > 0 && (!in || !out))) return fail(RT_E_INVALID, "rt_debug_math: bad argument");
-    if (refb && (fn == RT_MATH_ACOS || fn == RT_MATH_ATAN || fn == RT_MATH_ATAN2))
-        return fail(RT_E_UNSUPPORTED, "rt_debug_math: RT_BUILTINS_REFERENCE evaluates acos / atan2 only as acospi / atan2pi inside RT_MATH_SPHERE_TEXEL");
-    int rc = math_device("rt_debug_math"); if (rc) return rc;
-    if (n == 0) return RT_OK;
-    const size_t inB = sizeof(uint32_t) * inWords[fn] * (size_t)n, outB = sizeof(uint32_t) * outWords[fn] * (size_t)n;
-    uint32_t *dIn = nullptr, *dOut = nullptr;
-    hipError_t e = hipMalloc((void**)&dIn, inB);
-    if (e == hipSuccess) e = hipMalloc((void**)&dOut, outB);
-    if (e == hipSuccess) e = hipMemcpy(dIn, in, inB, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        const int grid = (int)std::min<int64_t>((n + kBlock - 1) / kBlock, 65536);
-        hipLaunchKernelGGL(refb ? k_debug_math<true> : k_debug_math<false>, dim3(grid), dim3(kBlock), 0, 0, (int)fn, dIn, dOut, (int64_t)n);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(out, dOut, outB, hipMemcpyDeviceToHost);
-    (void)hipFree(dIn); (void)hipFree(dOut);
-    if (e != hipSuccess) return fail(RT_E_DEVICE, "rt_debug_math: %s", hipGetErrorString(e));
-    return RT_OK;
-}
-extern "C" int rt_debug_math(int32_t fn, const void* in, void* out, int64_t n) { return rt_debug_math_mode(RT_BUILTINS_DEFAULT, fn, in, out, n); }
-extern "C" int rt_debug_math_sweep_mode(int32_t builtins, int32_t fn, int32_t firstBlock, int32_t nBlocks, uint64_t* hashes)
-{
-    int32_t mode;
-    if (!resolve_builtins(builtins, &mode)) return fail(RT_E_INVALID, "rt_debug_math_sweep: builtins = %d is none of RT_BUILTINS_DEFAULT (0), RT_BUILTINS_IEEE (1), RT_BUILTINS_REFERENCE (2)", builtins);
-    const bool refb = mode == RT_BUILTINS_REFERENCE;
-    constexpr int kBlocks = 1 << (32 - RT_MATH_SWEEP_BLOCK_BITS);
-    if (fn < RT_MATH_EXP || fn > RT_MATH_F2I || firstBlock < 0 || nBlocks < 0 || firstBlock + nBlocks > kBlocks || (nBlocks > 0 && !hashes))
-        return fail(RT_E_INVALID, "rt_debug_math_sweep: bad argument");
-    if (refb && (fn == RT_MATH_ACOS || fn == RT_MATH_ATAN))
-        return fail(RT_E_UNSUPPORTED, "rt_debug_math_sweep: RT_BUILTINS_REFERENCE has no acos / atan of its own");
-    int rc = math_device("rt_debug_math_sweep"); if (rc) return rc;
-    if (nBlocks == 0) return RT_OK;
-    unsigned long long* dH = nullptr;
-    hipError_t e = hipMalloc((void**)&dH, sizeof(uint64_t) * nBlocks);
-    if (e == hipSuccess) e = hipMemset(dH, 0, sizeof(uint64_t) * nBlocks);
-    if (e == hipSuccess) {
-        const int groups = nBlocks * ((1 << RT_MATH_SWEEP_BLOCK_BITS) / (kBlock * kSweepPerThread));
-        hipLaunchKernelGGL(refb ? k_debug_math_sweep<true> : k_debug_math_sweep<false>, dim3(groups), dim3(kBlock), 0, 0, (int)fn, (uint32_t)firstBlock, dH);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(hashes, dH, sizeof(uint64_t) * nBlocks, hipMemcpyDeviceToHost);
-    (void)hipFree(dH);
-    if (e != hipSuccess) return fail(RT_E_DEVICE, "rt_debug_math_sweep: %s", hipGetErrorString(e));
-    return RT_OK;
-}
-extern "C" int rt_debug_math_sweep(int32_t fn, int32_t firstBlock, int32_t nBlocks, uint64_t* hashes) { return rt_debug_math_sweep_mode(RT_BUILTINS_DEFAULT, fn, firstBlock, nBlocks, hashes); }
-
 // ---- post-processing chain (renderer.cpp:95-124 PostProc, :303-308 SaveFrame) ----------------------------------------
 extern "C" int rt_postproc(RtCtx* ctx, int32_t frames, float vignette, float gamma, float chromatic, RtFloat4* outF32, uint8_t* outRGBA8)
 {
     if (!ctx) return fail(RT_E_INVALID, "rt_postproc: null context");
     if (frames <= 0) return fail(RT_E_INVALID, "rt_postproc: frames must be > 0 (it is the divisor of prep())");
+    return postproc(ctx, ctx->q.accum, frames, vignette, gamma, chromatic, outF32, outRGBA8);
+}
+int postproc(RtCtx* ctx, const float4* accum, int32_t frames, float vignette, float gamma, float chromatic, RtFloat4* outF32, uint8_t* outRGBA8)
+{
     HIPCHK(hipSetDevice(ctx->cfg.device));
     const size_t px = (size_t)ctx->cfg.width * ctx->cfg.height;
     if (!ctx->dPostF) { HIPCHK(hipMalloc((void**)&ctx->dPostF, px * sizeof(float4))); HIPCHK(hipMalloc((void**)&ctx->dPostB, px * 4)); }
     PostParams pp{ 1 / (float)frames, vignette, gamma, chromatic, ctx->cfg.width, ctx->cfg.height };
-    hipLaunchKernelGGL(k_postproc, grid_for((int)px), dim3(kBlock), 0, ctx->stream, (const float4*)ctx->q.accum, ctx->dPostF, ctx->dPostB, pp);
+    hipLaunchKernelGGL(k_postproc, grid_for((int)px), dim3(kBlock), 0, ctx->stream, accum, ctx->dPostF, ctx->dPostB, pp);
     HIPCHK(hipGetLastError());
     if (outF32) HIPCHK(hipMemcpyAsync(outF32, ctx->dPostF, px * sizeof(float4), hipMemcpyDeviceToHost, ctx->stream));
     if (outRGBA8) HIPCHK(hipMemcpyAsync(outRGBA8, ctx->dPostB, px * 4, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     ev_collect(ctx);
     return RT_OK;
-}
-
-// ---- lanes: several sample streams of one accumulation behind ONE handle -------------------------------------------------------
-// Every launch of a frame ends in a tail of a few long rays during which most of the chip idles, and the frames of ONE seed stream cannot
-// overlap (each continues the RNG state of the one before).  A group renders the accumulation as `lanes` independent sample streams
-// instead - own context, HIP stream, queues and seed slice each, ONE device copy of the scene - and interleaves their frames, so the
-// tails of one lane's launches are filled by the others' kernels.  The group's accumulator is the sum of its lanes' accumulators in
-// lane order.  (Reference: one Renderer, one in-order queue, renderer.cpp:26-94; the group is what stands behind Renderer::Tick here.)
-//
-// HIP maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues per stream priority (default 4; the normal pool holds the null
-// stream too) and runs kernels of streams that share one after the other.  The library leaves that setting to the process that loads
-// it; rt_group_create MEASURES how many of its streams really run side by side - per priority class, choose_streams - so a caller is
-// told instead of silently serialised.
-//
-// Fewer concurrent streams than lanes must not leave a lane's frames queued behind another's: two lanes on one queue render twice
-// as many frames in series as the rest, which finish at half-time and leave the chip to one context (4 lanes on 3 queues: 41 % of
-// the bench's timed region, profiles/r04_group_streams.txt).  So the group keeps a lane's SAMPLES where they are (frame j is
-// lane j mod L's, with its seeds, accumulator and counters) but issues frame j on worker stream j mod S, the S lane streams found to
-// run side by side.  A lane's `stream` is then the worker that ran its last frame, and everything else it queues (reset, seeds, sum,
-// reads, synchronize, stage events) lands behind that frame.  A move to another worker waits on an event recorded right after the
-// lane's last frame - not on the other lanes' frames queued behind it there - or, when the lane has queued more work since, after that.
-
-__global__ void k_spin(long long ticks, int* sink)
-{
-    const long long t0 = wall_clock64();
-    while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(8);
-    if (ticks < 0) *sink = 1;
-}
-__global__ __launch_bounds__(kBlock) void k_sum_lanes(float4* out, const float4* a0, const float4* a1, const float4* a2, const float4* a3,
-                                                       const float4* a4, const float4* a5, const float4* a6, const float4* a7, int lanes, int first, int n)
-{
-    // only the group's own rows [first, first + n): the bands of one frame can be summed into one buffer without touching each other
-    int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    i += first;
-    const float4* a[8] = { a0, a1, a2, a3, a4, a5, a6, a7 };
-    float4 s = a[0][i];
-    for (int m = 1; m < lanes; m++) s = add4(s, a[m][i]);   // lane order, left to right
-    out[i] = s;
-}
-
-// The stream classes of a group: HIP's stream priorities.  rt_group_stream_class reports one of these, or kClassMixed.
-enum { kClassLow = -1, kClassNormal = 0, kClassHigh = 1, kClassMixed = 2 };
-// Between the two classes beside normal, at equal S: the lower one, so that a renderer embedded in an application yields to that
-// application's other GPU work (the bench tells them apart by no more than its spread, EXPERIMENTS.md (62))
-static constexpr int kPreferClass = kClassLow;
-// Lanes that no single class runs side by side take streams of the other classes only on request (RT355_GROUP_PRIORITY=mixed): workers
-// of unequal priority finish their equal shares of frames at different times
-static constexpr bool kMixedByDefault = false;
-
-struct RtGroup {
-    std::vector<RtCtx*> lane;
-    std::vector<int> laneClass;         // one per lane: the class of its home stream
-    int seen[3] = { -1, -1, -1 };       // S as measured per class (low, normal, high) at creation; -1: not measured
-    float4* sum = nullptr;              // lane-ordered sum of the lanes' accumulators (own buffer)
-    std::vector<hipEvent_t> done;       // one per lane: "this lane's queued frames are finished", for the sum on lane 0's stream
-    uint64_t frames = 0;                // frames rendered by all lanes since the last reset (= the divisor of prep())
-    int concurrent = 0;                 // S = worker.size(): streams measured to run side by side at creation
-    std::vector<int> worker;            // the lanes whose home streams run side by side: frames are issued on these
-    std::vector<hipEvent_t> moved;      // one per lane: the end of its last frame (or of work queued since), waited on by the worker it moves to
-    int nextLane = 0;                   // round-robin position, so that successive one-frame calls visit all lanes
-    int nextWorker = 0;                 // the same over the workers
-};
-static constexpr int kMaxLanes = 8;
-
-static void group_free(RtGroup* g)
-{
-    if (!g) return;
-    for (RtCtx* c : g->lane) { (void)hipStreamSynchronize(c->stream); c->stream = c->home; }   // a lane may sit on another's stream
-    for (RtCtx* c : g->lane) ctx_free(c);
-    for (hipEvent_t e : g->done) (void)hipEventDestroy(e);
-    for (hipEvent_t e : g->moved) (void)hipEventDestroy(e);
-    if (g->sum) (void)hipFree(g->sum);
-    delete g;
-}
-// Which streams execute concurrently: one single-wave kernel that naps for ~1 ms, on one stream alone and then on every stream of a
-// candidate set at once, both timed on the host.  Streams that share a hardware queue run their naps one after the other, so a set
-// whose naps take about as long as one nap runs side by side.  Greedy: `set` (its first stream, when empty: the first candidate) grows
-// by each candidate that keeps it concurrent; returns which candidates were taken.  Measured, not predicted: which queue a stream
-// lands on is the runtime's business.
-static std::vector<int> grow_concurrent(RtGroup* g, std::vector<hipStream_t>& set, const std::vector<hipStream_t>& cand)
-{
-    std::vector<int> taken;
-    size_t first = 0;
-    if (set.empty() && !cand.empty()) { set.push_back(cand[0]); taken.push_back(0); first = 1; }
-    if (first >= cand.size()) return taken;
-    int rate = 0;
-    if (hipDeviceGetAttribute(&rate, hipDeviceAttributeWallClockRate, g->lane[0]->cfg.device) != hipSuccess || rate <= 0) rate = 100000;   // kHz
-    const long long ticks = (long long)rate;        // 1 ms
-    int* sink = (int*)g->lane[0]->q.fault;          // never written (ticks >= 0)
-    auto run = [&](const std::vector<hipStream_t>& on) {
-        const auto t0 = std::chrono::steady_clock::now();
-        for (hipStream_t s : on) hipLaunchKernelGGL(k_spin, dim3(1), dim3(64), 0, s, ticks, sink);
-        for (hipStream_t s : on) (void)hipStreamSynchronize(s);
-        return std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    };
-    // the best of three each: a host thread that is descheduled for a millisecond must not read as a serialised stream
-    auto best = [&](const std::vector<hipStream_t>& on) { float t = run(on); for (int k = 0; k < 2; k++) t = std::min(t, run(on)); return t; };
-    std::vector<hipStream_t> all = set;
-    all.insert(all.end(), cand.begin() + (ptrdiff_t)first, cand.end());
-    (void)run(all);                                  // warms the code object up on every stream
-    const float one = best({ set[0] });
-    if (one <= 0) return taken;
-    for (size_t k = first; k < cand.size(); k++) {
-        std::vector<hipStream_t> with = set; with.push_back(cand[k]);
-        if (best(with) < 1.5f * one) { set = with; taken.push_back((int)k); }   // serialised: >= 2 naps
-    }
-    return taken;
-}
-
-// Which streams the lanes' frames are issued on.  HIP keeps one pool of hardware queues PER STREAM PRIORITY, each up to the process's
-// limit, and the process's other streams (the null stream, a framework's) sit in the normal pool: lane streams of another priority
-// class can have that class's queues to themselves.  All lanes of a class have equal priority among themselves, and nothing
-// process-wide changes.  Which class gives the most concurrent workers is measured like everything else here:
-//   normal   the streams of rt_create, as for a single context
-//   low/high every lane's stream replaced by one of that priority
-//   auto     (unset) normal when every lane runs side by side there - no other stream is ever created then - or when no other class
-//            holds more workers; else the class with the most, kPreferClass at a tie
-//   mixed    auto, then the lanes left over try a stream of each other class (kMixedByDefault: auto does the same)
-// A lane's stream is replaced before anything but its creation work was queued: rt_create has synchronised that, and nothing else of
-// a context is bound to its stream (the stage events are recorded on ctx->stream at use).
-static int choose_streams(RtGroup* g, int want, bool mixed)
-{
-    const int n = (int)g->lane.size();
-    int least = 0, greatest = 0;
-    HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    const bool classes = least != greatest;   // (numerically, a lower value is a higher priority)
-    if (!classes && (want == kClassLow || want == kClassHigh)) return fail(RT_E_INVALID, "rt_group_create: RT355_GROUP_PRIORITY asks for a priority class, but this device has one stream priority only");
-    std::vector<hipStream_t> cls[3];           // [class + 1][lane]; normal: the lanes' own
-    for (RtCtx* c : g->lane) cls[1].push_back(c->home);
-    auto drop = [&](int k) { for (hipStream_t s : cls[k + 1]) if (s) (void)hipStreamDestroy(s); cls[k + 1].clear(); };
-    auto make = [&](int k) {
-        for (int m = 0; m < n; m++) {
-            hipStream_t s = nullptr;
-            const hipError_t e = hipStreamCreateWithPriority(&s, hipStreamNonBlocking, k == kClassLow ? least : greatest);
-            if (e != hipSuccess) { drop(k); return fail(RT_E_DEVICE, "rt_group_create: hipStreamCreateWithPriority failed: %s", hipGetErrorString(e)); }
-            cls[k + 1].push_back(s);
-        }
-        return (int)RT_OK;
-    };
-    std::vector<hipStream_t> set;              // the concurrent streams
-    std::vector<int> worker;                   // and whose they are
-    int bestClass = kClassNormal;
-    auto measure = [&](int k) {
-        std::vector<hipStream_t> s;
-        std::vector<int> w = grow_concurrent(g, s, cls[k + 1]);
-        g->seen[k + 1] = (int)w.size();
-        // a tie with normal keeps normal; between the other two, kPreferClass
-        if (set.empty() || w.size() > set.size() || (w.size() == set.size() && bestClass != kClassNormal && k == kPreferClass)) { set = s; worker = w; bestClass = k; }
-    };
-    if (want == kClassLow || want == kClassHigh) {
-        const int rc = make(want); if (rc != RT_OK) return rc;
-        measure(want);
-    } else {
-        measure(kClassNormal);
-        if (want != kClassNormal && classes && (int)set.size() < n)
-            for (int k : { kClassLow, kClassHigh }) {
-                const int rc = make(k); if (rc != RT_OK) { drop(kClassLow); return rc; }
-                measure(k);
-            }
-    }
-    std::vector<hipStream_t> home = cls[bestClass + 1];
-    g->laneClass.assign((size_t)n, bestClass);
-    if (mixed && classes && (int)set.size() < n) {   // (only the measured choice is extended, and it has tried every class by now)
-        for (int m = 0; m < n; m++) {
-            if (std::find(worker.begin(), worker.end(), m) != worker.end()) continue;
-            for (int k : { kClassNormal, kClassLow, kClassHigh }) {
-                if (k == bestClass) continue;
-                if (grow_concurrent(g, set, { cls[k + 1][(size_t)m] }).empty()) continue;
-                worker.push_back(m); home[(size_t)m] = cls[k + 1][(size_t)m]; g->laneClass[(size_t)m] = k;
-                break;
-            }
-        }
-    }
-    // every lane its stream; the streams of the classes not kept go, so that their hardware queues are released
-    for (int m = 0; m < n; m++) {
-        RtCtx* c = g->lane[(size_t)m];
-        for (int k = 0; k < 3; k++) if (!cls[k].empty() && cls[k][(size_t)m] == home[(size_t)m]) cls[k][(size_t)m] = nullptr;
-        if (c->home == home[(size_t)m]) continue;
-        cls[1][(size_t)m] = nullptr;
-        HIPCHK(hipStreamSynchronize(c->home));   // the naps
-        HIPCHK(hipStreamDestroy(c->home));
-        c->home = c->stream = home[(size_t)m];
-    }
-    cls[1].clear();                            // (what is left there is some lane's home)
-    drop(kClassLow); drop(kClassHigh);
-    g->worker = worker;
-    return RT_OK;
-}
-
-extern "C" int rt_group_create(const RtConfig* cfg, int32_t lanes, RtGroup** out)
-{
-    if (!cfg || !out) return fail(RT_E_INVALID, "rt_group_create: null argument");
-    if (lanes < 1 || lanes > kMaxLanes) return fail(RT_E_INVALID, "rt_group_create: lanes must be 1..%d", kMaxLanes);
-    int want = kClassNormal;
-    bool any = true, mixed = kMixedByDefault;   // any: the class is the measurement's choice
-    if (const char* t = getenv("RT355_GROUP_PRIORITY")) {   // forces a class (tests, A/B runs)
-        const std::string v(t);
-        if (v == "normal") any = false;
-        else if (v == "low") { any = false; want = kClassLow; }
-        else if (v == "high") { any = false; want = kClassHigh; }
-        else if (v == "mixed") mixed = true;
-        else if (v != "auto" && !v.empty()) return fail(RT_E_INVALID, "rt_group_create: RT355_GROUP_PRIORITY=%s is none of normal, low, high, auto, mixed", t);
-    }
-    if (!any) mixed = false;
-    std::unique_ptr<RtGroup, void (*)(RtGroup*)> guard(new RtGroup(), group_free);
-    RtGroup* g = guard.get();
-    for (int m = 0; m < lanes; m++) {
-        RtConfig c = *cfg;
-        if (lanes > 1) {   // contexts that share the GPU get the footprints that fit BESIDE each other
-            if (c.shade_blocks_per_cu == 0) c.shade_blocks_per_cu = 1;
-        }
-        if (m > 0) c.profile = 0;   // HIP-event brackets on the first lane only
-        RtCtx* ctx = nullptr;
-        const int rc = rt_create(&c, &ctx);
-        if (rc != RT_OK) return rc;
-        g->lane.push_back(ctx);
-        for (auto* ev : { &g->done, &g->moved }) {
-            hipEvent_t e;
-            if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return fail(RT_E_DEVICE, "rt_group_create: hipEventCreate failed");
-            ev->push_back(e);
-        }
-    }
-    const size_t px = (size_t)cfg->width * cfg->height;
-    if (hipMalloc((void**)&g->sum, px * sizeof(float4)) != hipSuccess) return fail(RT_E_NOMEM, "rt_group_create: hipMalloc of the group accumulator failed");
-    HIPCHK(hipMemset(g->sum, 0, px * sizeof(float4)));
-    {
-        const int rc = choose_streams(g, any ? kClassMixed : want, mixed);
-        if (rc != RT_OK) return rc;
-    }
-    if (const char* t = getenv("RT355_GROUP_STREAMS")) {   // at most this many workers (tests of the routing; A/B runs)
-        const int k = atoi(t);
-        if (k >= 1 && k < (int)g->worker.size()) g->worker.resize((size_t)k);
-    }
-    g->concurrent = (int)g->worker.size();
-    // the persistent traversal grids (sized at scene upload) of S concurrent lanes: S grids beside each other.  2 per CU was tuned
-    // for four; 3 for three or fewer (profiles/r04_group_streams.txt; at S = 4 on today's kernels 2 and 3 are equal, r08_group_priority.txt)
-    if (lanes > 1 && cfg->persist_blocks_per_cu == 0)
-        for (RtCtx* c : g->lane) c->cfg.persist_blocks_per_cu = g->concurrent >= 4 ? 2 : 3;
-    if (g->concurrent < lanes) {
-        static bool warned = false;
-        if (!warned) {
-            warned = true;
-            static const char* const name[] = { "low", "normal", "high", "mixed" };
-            const char* q = getenv("GPU_MAX_HW_QUEUES");
-            fprintf(stderr, "librt355: %d lanes requested but only %d of their HIP streams run concurrently (stream priority class: %s; measured per class: "
-                            "low %d, normal %d, high %d, -1 = not tried; HIP serialises streams that share a hardware queue and keeps up to "
-                            "GPU_MAX_HW_QUEUES=%s of them per priority class, the normal class's shared with the process's other streams)\n",
-                    lanes, g->concurrent, name[rt_group_stream_class(g) + 1], g->seen[0], g->seen[1], g->seen[2], q ? q : "4 (unset)");
-        }
-    }
-    {   // lane m starts on sample stream m, as rt_group_seed(g, 0) leaves it
-        const int rc = rt_group_seed(g, 0);
-        if (rc != RT_OK) return rc;
-    }
-    *out = guard.release();
-    return RT_OK;
-}
-extern "C" int rt_group_destroy(RtGroup* g) { group_free(g); return RT_OK; }
-extern "C" int rt_group_lanes(RtGroup* g) { return g ? (int)g->lane.size() : 0; }
-extern "C" int rt_group_concurrency(RtGroup* g) { return g ? g->concurrent : 0; }
-extern "C" int rt_group_stream_class(RtGroup* g)
-{
-    if (!g || g->laneClass.empty()) return kClassNormal;
-    for (int k : g->laneClass) if (k != g->laneClass[0]) return kClassMixed;
-    return g->laneClass[0];
-}
-extern "C" int rt_group_class_concurrency(RtGroup* g, int32_t cls) { return g && cls >= kClassLow && cls <= kClassHigh ? g->seen[cls + 1] : -1; }
-extern "C" RtCtx* rt_group_lane(RtGroup* g, int32_t m) { return g && m >= 0 && m < (int)g->lane.size() ? g->lane[(size_t)m] : nullptr; }
-extern "C" uint64_t rt_group_frames(RtGroup* g) { return g ? g->frames : 0; }
-
-extern "C" int rt_group_upload_scene(RtGroup* g, const RtPrimitive* prims, int32_t nPrims, const RtMaterial* mats, int32_t nMats,
-                                     const RtFloat4* textures, int32_t nTexels, const uint32_t* lights, int32_t nLights,
-                                     const void* bvhNodes, int32_t nNodes, const uint32_t* primIdx, int32_t nIdx,
-                                     const RtTLASNode* tlas, int32_t nTlas, const RtBVHInstance* blas, int32_t nBlas)
-{
-    if (!g) return fail(RT_E_INVALID, "rt_group_upload_scene: null group");
-    int rc = rt_upload_scene(g->lane[0], prims, nPrims, mats, nMats, textures, nTexels, lights, nLights, bvhNodes, nNodes, primIdx, nIdx, tlas, nTlas, blas, nBlas);
-    for (size_t m = 1; m < g->lane.size() && rc == RT_OK; m++) rc = rt_share_scene(g->lane[m], g->lane[0]);   // ONE device copy
-    return rc;
-}
-extern "C" int rt_group_upload_scene_bvh2(RtGroup* g, const RtPrimitive* prims, int32_t nPrims, const RtMaterial* mats, int32_t nMats,
-                                          const RtFloat4* textures, int32_t nTexels, const uint32_t* lights, int32_t nLights,
-                                          const RtBVHNode2* bvhNodes, int32_t nNodes, const uint32_t* primIdx, int32_t nIdx,
-                                          const RtTLASNode* tlas, int32_t nTlas, const RtBVHInstance* blas, int32_t nBlas)
-{
-    if (!g) return fail(RT_E_INVALID, "rt_group_upload_scene_bvh2: null group");
-    int rc = rt_upload_scene_bvh2(g->lane[0], prims, nPrims, mats, nMats, textures, nTexels, lights, nLights, bvhNodes, nNodes, primIdx, nIdx, tlas, nTlas, blas, nBlas);
-    for (size_t m = 1; m < g->lane.size() && rc == RT_OK; m++) rc = rt_share_scene(g->lane[m], g->lane[0]);   // ONE device copy
-    return rc;
-}
-// Another group on the same device (e.g. another row band of the frame) renders from the device copy `from` holds.
-extern "C" int rt_group_share_scene(RtGroup* g, RtGroup* from)
-{
-    if (!g || !from) return fail(RT_E_INVALID, "rt_group_share_scene: null group");
-    for (RtCtx* c : g->lane) { const int rc = rt_share_scene(c, from->lane[0]); if (rc != RT_OK) return rc; }
-    return RT_OK;
-}
-// Lane m renders sample stream `firstStream + m`: its seeds are outputs (firstStream + m) * W*H + firstPixel + i + 1 of the reference's
-// host xorshift32 stream (renderer.cpp:195-196).  A single Renderer has firstStream 0; rank r of a sample-partitioned job r * lanes.
-extern "C" int rt_group_seed(RtGroup* g, uint64_t firstStream)
-{
-    if (!g) return fail(RT_E_INVALID, "rt_group_seed: null group");
-    const RtCtx* c0 = g->lane[0];
-    const uint64_t P = (uint64_t)c0->cfg.width * (uint64_t)c0->cfg.height;
-    uint32_t x = 0x12345678u; // template/template.cpp:711
-    auto next = [&x]() { x ^= x << 13; x ^= x >> 17; x ^= x << 5; return x; };
-    uint64_t pos = 0;
-    std::vector<uint32_t> s((size_t)c0->nPix);
-    for (size_t m = 0; m < g->lane.size(); m++) {
-        const uint64_t first = (firstStream + m) * P + (uint64_t)c0->firstPixel;
-        for (; pos < first; pos++) next();
-        for (auto& v : s) v = next();
-        pos += s.size();
-        const int rc = rt_set_seeds(g->lane[m], s.data(), (int64_t)s.size());
-        if (rc != RT_OK) return rc;
-    }
-    return RT_OK;
-}
-extern "C" int rt_group_reset(RtGroup* g)
-{
-    if (!g) return fail(RT_E_INVALID, "rt_group_reset: null group");
-    for (RtCtx* c : g->lane) { const int rc = rt_reset(c); if (rc != RT_OK) return rc; }
-    g->frames = 0; g->nextLane = 0; g->nextWorker = 0;
-    return RT_OK;
-}
-// `frames` frames in all, dealt to the lanes round-robin (continuing where the last call stopped) and queued interleaved, so that the
-// lanes' kernels overlap on the GPU.  Asynchronous.  After k frames in total the group accumulator holds the sum of k samples per
-// pixel: prep() divides by k (postproc.cl:71), exactly as with one stream.
-extern "C" int rt_group_render(RtGroup* g, const RtCamera* cam, const RtSettings* settings, int32_t frames)
-{
-    if (!g || !cam) return fail(RT_E_INVALID, "rt_group_render: null argument");
-    if (frames <= 0) return fail(RT_E_INVALID, "rt_group_render: frames must be > 0");
-    const int n = (int)g->lane.size(), S = (int)g->worker.size();
-    HIPCHK(hipSetDevice(g->lane[0]->cfg.device));
-    for (int f = 0; f < frames; f++) {
-        RtCtx* c = g->lane[(size_t)g->nextLane];
-        hipEvent_t moved = g->moved[(size_t)g->nextLane];
-        const hipStream_t w = g->lane[(size_t)g->worker[(size_t)g->nextWorker]]->home;
-        if (S == n) {   // frame j's worker is lane j's own stream
-            const int rc = rt_render(c, cam, settings, 1);
-            if (rc != RT_OK) return rc;
-        } else {
-            if (c->stream != w) {
-                // `moved` marks the end of the lane's last frame; the frames of other lanes queued behind it on that stream must not
-                // be waited for.  Work the lane queued after its frame (a reset, the group sum) sits behind them and must be.
-                if (c->queued) HIPCHK(hipEventRecord(moved, c->stream));
-                HIPCHK(hipStreamWaitEvent(w, moved, 0));
-                c->stream = w;
-            }
-            const int rc = rt_render(c, cam, settings, 1);
-            if (rc != RT_OK) return rc;
-            HIPCHK(hipEventRecord(moved, w));
-            c->queued = false;
-        }
-        g->nextLane = (g->nextLane + 1) % n;
-        g->nextWorker = (g->nextWorker + 1) % S;
-    }
-    g->frames += (uint64_t)frames;
-    return RT_OK;
-}
-extern "C" int rt_group_synchronize(RtGroup* g)
-{
-    if (!g) return fail(RT_E_INVALID, "rt_group_synchronize: null group");
-    for (RtCtx* c : g->lane) { const int rc = rt_synchronize(c); if (rc != RT_OK) return rc; }
-    return RT_OK;
-}
-// The lane-ordered sum of the lanes' accumulators, on the device: into `devicePtr` (float4[width*height], e.g. the tensor a
-// torch.distributed all_reduce then works on) or, when NULL, into the group's own buffer.  Queued on lane 0's stream behind every
-// lane's pending frames; rt_group_synchronize (or rt_group_read_accum) waits for it.
-extern "C" int rt_group_sum(RtGroup* g, void* devicePtr)
-{
-    if (!g) return fail(RT_E_INVALID, "rt_group_sum: null group");
-    RtCtx* c0 = g->lane[0];
-    HIPCHK(hipSetDevice(c0->cfg.device));
-    const int n = (int)g->lane.size();
-    for (int m = 1; m < n; m++) { HIPCHK(hipEventRecord(g->done[(size_t)m], g->lane[(size_t)m]->stream)); HIPCHK(hipStreamWaitEvent(c0->stream, g->done[(size_t)m], 0)); }
-    const float4* a[kMaxLanes];
-    for (int m = 0; m < kMaxLanes; m++) a[m] = g->lane[(size_t)std::min(m, n - 1)]->q.accum;
-    hipLaunchKernelGGL(k_sum_lanes, grid_for(c0->nPix), dim3(kBlock), 0, c0->stream, devicePtr ? (float4*)devicePtr : g->sum,
-                       a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], n, c0->firstPixel, c0->nPix);
-    HIPCHK(hipGetLastError());
-    // the lanes must not start overwriting their accumulators before the sum has read them
-    HIPCHK(hipEventRecord(g->done[0], c0->stream));
-    for (int m = 1; m < n; m++) HIPCHK(hipStreamWaitEvent(g->lane[(size_t)m]->stream, g->done[0], 0));
-    for (RtCtx* c : g->lane) c->queued = true;
-    return RT_OK;
-}
-extern "C" int rt_group_read_accum(RtGroup* g, RtFloat4* out)
-{
-    if (!g || !out) return fail(RT_E_INVALID, "rt_group_read_accum: null argument");
-    int rc = rt_group_sum(g, nullptr); if (rc != RT_OK) return rc;
-    rc = rt_group_synchronize(g); if (rc != RT_OK) return rc;
-    const RtCtx* c0 = g->lane[0];
-    HIPCHK(hipMemcpy(out, g->sum, sizeof(float4) * (size_t)c0->cfg.width * c0->cfg.height, hipMemcpyDeviceToHost));
-    return RT_OK;
-}
-extern "C" int rt_group_focus(RtGroup* g, int32_t x, int32_t y, const RtCamera* cam, float* t) { return g ? rt_focus(g->lane[0], x, y, cam, t) : fail(RT_E_INVALID, "rt_group_focus: null group"); }
-// Renderer::PostProc + SaveFrame over the group's accumulator; `frames` is the group's frame count (rt_group_frames) unless > 0.
-extern "C" int rt_group_postproc(RtGroup* g, int32_t frames, float vignette, float gamma, float chromatic, RtFloat4* outF32, uint8_t* outRGBA8)
-{
-    if (!g) return fail(RT_E_INVALID, "rt_group_postproc: null group");
-    RtCtx* c0 = g->lane[0];
-    if (g->lane.size() == 1) return rt_postproc(c0, frames > 0 ? frames : (int32_t)std::max<uint64_t>(g->frames, 1), vignette, gamma, chromatic, outF32, outRGBA8);
-    int rc = rt_group_sum(g, nullptr); if (rc != RT_OK) return rc;
-    float4* own = c0->q.accum;
-    c0->q.accum = g->sum;                  // k_postproc reads the accumulator it is handed: the summed one
-    rc = rt_postproc(c0, frames > 0 ? frames : (int32_t)std::max<uint64_t>(g->frames, 1), vignette, gamma, chromatic, outF32, outRGBA8);
-    c0->q.accum = own;
-    return rc;
 }
 
 #ifdef RT355_TAIL_PROBE

@@ -26,269 +26,18 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/rt355_types.h"
+#include "rt355_dev.h"    // the structs and constants shared with the host code
+#include "rt355_math.h"   // the arithmetic: float4 helpers, the two sets of builtins, the texel lookup
 
 namespace rt355dev {
 
-#define RT_FORCEINLINE __device__ __forceinline__
-static constexpr int   kBlock = 256;           // threads per workgroup = 4 wave64
 static constexpr float kEps = RT_EPSILON;
 static constexpr float kFar = RT_REALLYFAR;
 static constexpr float kPi = 3.14159274101257f;     // M_PI_F
 static constexpr float kInvPi = 0.31830987334251f;  // M_1_PI_F
 
-// ------------------------------------------------------------------ device views
-struct DevScene {
-    const RtPrimitive*   prims;
-    const RtMaterial*    mats;
-    const float4*        tex;
-    const uint32_t*      lights;
-    const RtBVHNode2*    bvh2;
-    const RtBVHNode4*    bvh4;
-    const uint32_t*      primIdx;
-    const RtTLASNode*    tlas;
-    const RtBVHInstance* blas;
-    // derived at upload from the unchanged BVH2 arrays (layout 1, see traverse_bvh2_packed)
-    const float4*        pairs;      // [nNodes][4]  both child boxes + encoded child entries of interior node i
-    const float4*        triRecs;    // [nIdx][3]    leaf-ordered triangle vertices + primitive id
-    const uint32_t*      rootEntry;  // [nBlas]      encoded root of every instance
-    const float4*        shadeRecs;  // [nPrims]     {N.xyz, bits(matIdx | (N.w is -0) << 27 | objType << 28)}: what shade() needs of a 128-B Primitive, in 16 B
-    const float4*        tlasPairs;  // [nTlas][4]    TLAS interior node i: both child boxes + encoded children (leaf: kLeafBit | BLASidx), one 64-B fetch
-    const float4*        instRecs;   // [nBlas][4]    rows 0..2 of invT + {encoded BLAS root (layout 1), bvhIdx}: one 64-B fetch per instance visit
-    uint32_t             tlasRoot;   // encoded TLAS root (a leaf when the scene has one BLAS)
-    const float4*        tlasPairsP; // [nTlas][4]    the same records with the children in the tagged encoding of k_trace_persist_tlas (kTagTlas / kTagInst)
-    uint32_t             tlasRootP;  // TLAS root in that encoding
-    const float4*        lightRecs;  // [nLights][8]  what NEE needs of light li in one place: objData[0..63], {objType, area}, emittance of its material
-    const float4*        quads;      // [nNodes][8]  layout 1 of the BVH4: four child boxes + four encoded child entries (128 B)
-    int32_t nLights, nPrims, nBlas, nTex;
-    int32_t nMats;                   // records of `mats` (k_shade stages the whole table or none of it)
-};
-struct DevQueues {
-    // ray queues (compacted), capacity nPix each; bounce b lives in set b & 1 (shade reads one, writes the other)
-    float4* O[2]; float4* D[2]; float4* inten[2]; uint2* meta[2];
-    float4* hit;       // {t, primIdx, u, v} of the queue extend() just traced
-    // shadow queue (compacted), capacity max_bounces * nPix
-    float4* sA; float4* sB; float4* sC;
-    // single-pass scan state of k_shade, one set per bounce parity: [1 + t] = status of tile t
-    unsigned long long* tile[2];
-    unsigned long long* super[2];   // [s] = status of super-tile s (64 consecutive tiles), same encoding
-    unsigned long long* supAcc[2];  // [s] = running total of super-tile s: [63:40] tiles arrived, [39:20] extension rays, [19:0] shadow rays
-    int32_t* nRays;    // [RT_MAX_BOUNCES+2]  rays entering bounce b
-    int32_t* nShadow;  // [RT_MAX_BOUNCES+2]  shadow rays of bounce b occupy [nShadow[b], nShadow[b+1])
-    int32_t* fault;    // [1] set to 1 by a kernel whose bounded wait expired (host turns it into RT_E_DEVICE)
-    int32_t* cursor;   // [2*(RT_MAX_BOUNCES+2)] work-queue heads of the persistent kernels (extend: [b], connect: [9+b])
-    int32_t* shadeTicket; // [(RT_MAX_BOUNCES+1) * kTicketClasses * kTicketStride] k_shade's tile tickets, one counter per bounce and class
-    uint32_t* seeds;   // one RNG stream per band slot
-    float4* accum;     // full frame, indexed by global pixel index
-    int32_t* steps;    // per-ray steps of the last extend (debug / heat map), may be null
-    unsigned long long* ctrExtend;  // [gridMax][kCtrCols] per-block partial work counters
-    unsigned long long* ctrConnect; // [gridMax][kCtrCols]
-    uint32_t* spill;   // [spillEntries][spillStride] deep ends of the traversal stacks (SPILL instantiations), may be null
-    uint32_t spillStride, stackCap;   // lanes of the largest SPILL launch; LDS entries per lane of those launches
-    uint32_t tlasLdsEntries;          // LDS stack entries per lane of k_trace_persist_tlas (the world-ray backup sits behind them)
-    int32_t nPix, firstPixel, width, height;
-};
-// k_shade hands its tiles out by ticket.  ONE counter: any running workgroup draws the smallest tile not drawn yet, so the ordered scan
-// depends on nothing but "some workgroup of the launch is running".  (A counter per class of workgroups - class = blockIdx mod 32,
-// tiles c, c + 32, ... - takes the tickets off one memory channel and was 5 % faster for k_shade, but workgroups go to the XCDs
-// round-robin, so an XCD then serves only 4 of the 32 classes, and two processes with two contexts each dead-locked within a few
-// frames: four partially resident k_shade grids, each holding the XCD another one needed.  tests: test_two_processes_with_two_lanes_...)
-static constexpr int kTicketClasses = 1, kTicketStride = 1024, kCursorWords = 2 * (RT_MAX_BOUNCES + 2);
-struct DevVariant { int32_t shading, sampling, accel, rr, fireflies, maxBounces, shadeTables /* k_shade may stage its tables (RT355_SHADE_TABLES) */; };
-
 // meta.y bit layout
 static constexpr uint32_t kMetaBounceMask = 0xffu, kMetaInside = 0x100u, kMetaLastSpec = 0x200u;
-
-// ------------------------------------------------------------------ float4 helpers
-// Non-temporal accesses for queue data at its LAST use (k_shade's input entries and hit records, k_accumulate's shadow records) and for
-// k_generate's primary rays: what streams through once does not push node and triangle records out of the L2s.  Measured with the
-// accesses switched one group at a time (profiles/r02_nt_streams.txt): +1.0 % with three lanes, +1.4 % for one context; the same hint on
-// k_shade's STORES costs a context alone 1 % (the next extend reads them back soon), on the traversal kernels' ray loads and hit stores nothing.
-typedef float nt_v4f __attribute__((ext_vector_type(4)));
-typedef unsigned nt_v2u __attribute__((ext_vector_type(2)));
-RT_FORCEINLINE float4 ldnt4(const float4* p) { nt_v4f t = __builtin_nontemporal_load((const nt_v4f*)p); return *(float4*)&t; }
-RT_FORCEINLINE uint2 ldnt2(const uint2* p) { nt_v2u t = __builtin_nontemporal_load((const nt_v2u*)p); return *(uint2*)&t; }
-RT_FORCEINLINE void stnt4(float4* p, float4 v) { __builtin_nontemporal_store(*(nt_v4f*)&v, (nt_v4f*)p); }
-RT_FORCEINLINE void stnt2(uint2* p, uint2 v) { __builtin_nontemporal_store(*(nt_v2u*)&v, (nt_v2u*)p); }
-RT_FORCEINLINE float4 mk4(float x, float y, float z, float w) { return make_float4(x, y, z, w); }
-RT_FORCEINLINE float4 splat(float s) { return make_float4(s, s, s, s); }
-RT_FORCEINLINE float4 add4(float4 a, float4 b) { return mk4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
-RT_FORCEINLINE float4 sub4(float4 a, float4 b) { return mk4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
-RT_FORCEINLINE float4 mul4(float4 a, float4 b) { return mk4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
-RT_FORCEINLINE float4 muls(float4 a, float s) { return mk4(a.x * s, a.y * s, a.z * s, a.w * s); }
-RT_FORCEINLINE float4 neg4(float4 a) { return mk4(-a.x, -a.y, -a.z, -a.w); }
-RT_FORCEINLINE float4 ld4(const RtFloat4& v) { return *reinterpret_cast<const float4*>(&v); }
-RT_FORCEINLINE float dot3(float4 a, float4 b) { return __fmaf_rn(a.z, b.z, __fmaf_rn(a.y, b.y, a.x * b.x)); }
-RT_FORCEINLINE float dot4(float4 a, float4 b) { return __fmaf_rn(a.w, b.w, __fmaf_rn(a.z, b.z, __fmaf_rn(a.y, b.y, a.x * b.x))); }
-RT_FORCEINLINE float4 cross4(float4 a, float4 b)
-{
-    return mk4(__fmaf_rn(a.y, b.z, b.y * (-a.z)), __fmaf_rn(a.z, b.x, b.z * (-a.x)), __fmaf_rn(a.x, b.y, b.x * (-a.y)), 0.0f);
-}
-// Two arithmetics, chosen per context (RtConfig.builtins) and carried down to here as the template parameter REFB of every function
-// that reaches one of the seven builtins; each kernel that does exists in both instantiations, and the host picks one per launch.
-// REFB = false (RT_BUILTINS_IEEE, the default): IEEE 1/sqrt and the Cephes sequences, what a CPU (the oracle) reproduces bit for bit.
-// REFB = true (RT_BUILTINS_REFERENCE; what RT_BUILTINS_DEFAULT means in librt355_refb.so, -DRT355_REF_BUILTINS): the builtins evaluate the
-// very instruction sequences ROCm's OpenCL library gives the reference's kernels - normalize() = v * rsqrt(dot) with the hardware
-// v_rsq_f32 (opencl.bc _Z9normalizeDv4_f -> __ocml_rsqrt_f32), length() = the hardware v_sqrt_f32 (llvm.sqrt with !fpmath 3 ulp in
-// _Z6lengthDv4_f), exp / sin / cos / acospi / atan2pi = the same ocml bitcode functions the OpenCL builtins resolve to (HIP links the same
-// ocml.bc with the same control constants: correctly rounded sqrt on, denormals on, no unsafe math).  With them the HIP path is held to
-// the reference's own kernels WITHOUT the few-ulp allowance of DESIGN.md section 2, on uncurated frames (tests/test_gpu_builtins.py).
-extern "C" __device__ float __ocml_acospi_f32(float);
-extern "C" __device__ float __ocml_atan2pi_f32(float, float);
-template <bool REFB> RT_FORCEINLINE float rt_len_sqrt(float d) { if constexpr (REFB) return __builtin_amdgcn_sqrtf(d); else return sqrtf(d); }
-template <bool REFB> RT_FORCEINLINE float rt_rsqrt(float d) { if constexpr (REFB) return __ocml_rsqrt_f32(d); else return 1.0f / sqrtf(d); }
-template <bool REFB> RT_FORCEINLINE float length4(float4 v)
-{
-    float d = dot4(v, v);
-    if (d < 1.17549435e-38f) { float4 s = muls(v, 0x1p+86f); return rt_len_sqrt<REFB>(dot4(s, s)) * 0x1p-86f; }
-    if (d == INFINITY) { float4 s = muls(v, 0x1p-66f); return rt_len_sqrt<REFB>(dot4(s, s)) * 0x1p+66f; }
-    return rt_len_sqrt<REFB>(d);
-}
-RT_FORCEINLINE float sel_inf(float x) { return copysignf(isinf(x) ? 1.0f : 0.0f, x); }
-template <bool REFB> RT_FORCEINLINE float4 normalize4(float4 v)
-{
-    if (v.x == 0.0f && v.y == 0.0f && v.z == 0.0f && v.w == 0.0f) return v;
-    float d = dot4(v, v);
-    if (d < 1.17549435e-38f) { v = muls(v, 0x1p+86f); d = dot4(v, v); }
-    else if (d == INFINITY) {
-        v = muls(v, 0x1p-66f); d = dot4(v, v);
-        if (d == INFINITY) { v = mk4(sel_inf(v.x), sel_inf(v.y), sel_inf(v.z), sel_inf(v.w)); d = dot4(v, v); }
-    }
-    float r = rt_rsqrt<REFB>(d);
-    return muls(v, r);
-}
-
-// ------------------------------------------------------------------ transcendentals
-// exp (Beer's law, glass.cl:4-9), sin / cos (fisheye camera, sphere-light sampling), acos / atan2 (sphere texture lookup).  The
-// device library's versions lean on hardware approximations (v_exp_f32, v_sin_f32 ...) that no CPU reproduces, and one last-bit
-// difference in a Fresnel draw or a texel index flips a whole path; so this path and the CPU oracle both evaluate the single-precision
-// Cephes algorithms (S. Moshier: expf.c, sinf.c, asinf.c, atanf.c) as plain sequences of IEEE + - * / sqrt - transcribed separately
-// here and in oracle/oracle.c - and agree bit for bit on every input (tests/test_gpu_math.py).  Error against float64 (DESIGN.md section
-// 2, asserted by tests/test_math_cpu.py): exp <= 1 ulp, acos <= 1.3 ulp, atan <= 2.9 ulp, atan2 <= 3.4 ulp, sin / cos <= 1.32 * 2^-24
-// absolute for |x| <= 8192 (0 beyond).  These are the *_ieee functions; rt_expf / rt_sinf / rt_cosf<REFB> behind them choose between
-// them and the ocml functions (REFB, see above).  acos / atan2 are called by the IEEE texel lookup only (sphere_texel_xy<false>).
-RT_FORCEINLINE float rt_expf_ieee(float x)
-{
-    if (x != x) return x;
-    if (x > 88.7228394f) return INFINITY;
-    if (x < -103.972076f) return 0.0f;
-    const float n = floorf(x * 1.44269504088896341f + 0.5f);
-    float r = x - n * 0.693359375f;
-    r = r - n * -2.12194440e-4f;
-    const float z = r * r;
-    float p = 1.9875691500E-4f;
-    p = p * r + 1.3981999507E-3f;
-    p = p * r + 8.3334519073E-3f;
-    p = p * r + 4.1665795894E-2f;
-    p = p * r + 1.6666665459E-1f;
-    p = p * r + 5.0000001201E-1f;
-    float e = p * z;
-    e = e + r;
-    e = e + 1.0f;
-    int k = (int)n;
-    if (k > 127) { e = e * 0x1p127f; k -= 127; }
-    else if (k < -126) { e = e * 0x1p-126f; k += 126; }
-    return e * __uint_as_float((uint32_t)(k + 127) << 23);
-}
-RT_FORCEINLINE float rt_trig_reduce(float ax, int& j)   // octant (made even-up) and remainder in [-pi/4, pi/4], three-term Cody-Waite
-{
-    j = (int)(1.27323954473516f * ax);
-    float y = (float)j;
-    if (j & 1) { j += 1; y = y + 1.0f; }
-    j &= 7;
-    float r = ax - y * 0.78515625f;
-    r = r - y * 2.4187564849853515625e-4f;
-    r = r - y * 3.77489497744594108e-8f;
-    return r;
-}
-RT_FORCEINLINE float rt_sin_kernel(float x, float z) { float p = -1.9515295891E-4f * z + 8.3321608736E-3f; p = p * z - 1.6666654611E-1f; p = p * z; p = p * x; return p + x; }
-RT_FORCEINLINE float rt_cos_kernel(float z) { float p = 2.443315711809948E-005f * z - 1.388731625493765E-003f; p = p * z + 4.166664568298827E-002f; p = p * z; p = p * z; p = p - 0.5f * z; return p + 1.0f; }
-RT_FORCEINLINE float rt_sinf_ieee(float x)
-{
-    if (x != x) return x;
-    bool neg = x < 0.0f;
-    const float ax = neg ? -x : x;
-    if (x == 0.0f) return x;   // sin(-0) = -0
-    if (ax == INFINITY) return x - x;   // NaN
-    if (ax > 8192.0f) return 0.0f;
-    int j; const float r = rt_trig_reduce(ax, j);
-    if (j > 3) { neg = !neg; j -= 4; }
-    const float z = r * r;
-    const float y = (j == 1 || j == 2) ? rt_cos_kernel(z) : rt_sin_kernel(r, z);
-    return neg ? -y : y;
-}
-RT_FORCEINLINE float rt_cosf_ieee(float x)
-{
-    if (x != x) return x;
-    const float ax = x < 0.0f ? -x : x;
-    if (ax == INFINITY) return x - x;   // NaN
-    if (ax > 8192.0f) return 0.0f;
-    int j; const float r = rt_trig_reduce(ax, j);
-    bool neg = false;
-    if (j > 3) { neg = !neg; j -= 4; }
-    if (j > 1) neg = !neg;
-    const float z = r * r;
-    const float y = (j == 1 || j == 2) ? rt_sin_kernel(r, z) : rt_cos_kernel(z);
-    return neg ? -y : y;
-}
-RT_FORCEINLINE float rt_asinf(float x)
-{
-    const bool neg = x < 0.0f;
-    const float a = neg ? -x : x;
-    if (a > 1.0f) return (x - x) / (x - x);
-    if (a < 1.0e-4f) return x;
-    float z, w; bool flag = false;
-    if (a > 0.5f) { z = 0.5f * (1.0f - a); w = sqrtf(z); flag = true; }
-    else { w = a; z = w * w; }
-    float p = 4.2163199048E-2f * z + 2.4181311049E-2f;
-    p = p * z + 4.5470025998E-2f;
-    p = p * z + 7.4953002686E-2f;
-    p = p * z + 1.6666752422E-1f;
-    p = p * z;
-    p = p * w;
-    p = p + w;
-    if (flag) { p = p + p; p = 1.5707963267948966192f - p; }
-    return neg ? -p : p;
-}
-RT_FORCEINLINE float rt_acosf(float x)
-{
-    if (x != x) return x;
-    if (x < -1.0f || x > 1.0f) return (x - x) / (x - x);   // NaN: a non-unit sphere normal (w-lane pollution) gets here; f2i_gpu then reads texel row 0
-    if (x < -0.5f) return 3.14159265358979323846f - 2.0f * rt_asinf(sqrtf(0.5f * (1.0f + x)));
-    if (x > 0.5f) return 2.0f * rt_asinf(sqrtf(0.5f * (1.0f - x)));
-    return 1.5707963267948966192f - rt_asinf(x);
-}
-RT_FORCEINLINE float rt_atanf(float x)
-{
-    const bool neg = signbit(x);   // atan(-0) = -0
-    float a = neg ? -x : x, y;
-    if (a > 2.414213562373095f) { y = 1.5707963267948966192f; a = -(1.0f / a); }
-    else if (a > 0.4142135623730950f) { y = 0.7853981633974483096f; a = (a - 1.0f) / (a + 1.0f); }
-    else y = 0.0f;
-    const float z = a * a;
-    float p = 8.05374449538e-2f * z - 1.38776856032E-1f;
-    p = p * z + 1.99777106478E-1f;
-    p = p * z - 3.33329491539E-1f;
-    p = p * z;
-    p = p * a;
-    p = p + a;
-    y = y + p;
-    return neg ? -y : y;
-}
-RT_FORCEINLINE float rt_atan2f(float y, float x)
-{
-    if (x != x || y != y) return x + y;
-    if (x == 0.0f) {
-        if (y == 0.0f) return signbit(x) ? copysignf(3.14159265358979323846f, y) : y;
-        return y > 0.0f ? 1.5707963267948966192f : -1.5707963267948966192f;
-    }
-    if (isinf(x) && isinf(y)) return copysignf(x > 0.0f ? 0.7853981633974483096f : 2.3561944901923449288f, y);
-    float z = rt_atanf(y / x);
-    if (x < 0.0f) z = signbit(y) ? z - 3.14159265358979323846f : z + 3.14159265358979323846f;
-    return z;
-}
-template <bool REFB> RT_FORCEINLINE float rt_expf(float x) { if constexpr (REFB) return __ocml_exp_f32(x); else return rt_expf_ieee(x); }
-template <bool REFB> RT_FORCEINLINE float rt_sinf(float x) { if constexpr (REFB) return __ocml_sin_f32(x); else return rt_sinf_ieee(x); }
-template <bool REFB> RT_FORCEINLINE float rt_cosf(float x) { if constexpr (REFB) return __ocml_cos_f32(x); else return rt_cosf_ieee(x); }
 
 // ------------------------------------------------------------------ RNG (util.cl:50-59)
 RT_FORCEINLINE uint32_t rng_next(uint32_t& s) { s ^= s << 13; s ^= s >> 17; s ^= s << 5; return s; }
@@ -304,7 +53,6 @@ struct TRay {
     float t; int prim; float u, v;
 };
 struct WorkCtr { uint32_t tlas, inst, node, prim, nodeIss = 0, leafIss = 0, evNode = 0, evPrim = 0; };   // nodeIss / leafIss: wave-level issues of the node path / the triangle path by the event loops (x 64 lanes = the slots those events had); evNode / evPrim: the events they carried
-static constexpr int kCtrCols = 9;
 
 RT_FORCEINLINE float slab(const TRay& r, float4 bmin, float4 bmax) // bvh.cl:3-12
 {
@@ -843,14 +591,6 @@ __global__ __launch_bounds__(kBlock) void k_extend(DevScene sc, DevQueues q, int
 static constexpr int kTpWaves = 8192;
 __device__ unsigned long long g_tp[9][kTpWaves][4];
 #endif
-struct PersistTune {
-    int chunk, refill, inner, leafK;   // rays per dequeue, idle lanes that trigger a top-up, events between checks, lanes on a leaf that trigger the triangle path
-    int fixedChunks;                   // chunks dealt round-robin instead of dequeued
-    int flat = 0;                      // k_trace_persist_tlas runs every queue through its one-ray-per-lane branch, 64 rays per wave and round (short traversals: config 5's open scene)
-    int xcdRays = 0, xcdFirst = 0;     // a sparse queue's rays are kept on as few XCDs as hold them at this many rays each (one-ray-per-lane branches; 0 = spread over all eight)
-    int thin = 0;                      // a queue of at most `thin` rays per participating wave is spread evenly over the waves (few lanes of each) instead of filling the first waves
-    int topLevels = 0, topBase = 0;    // k_trace_persist<.., TOP>: levels of the tree in the LDS top table (1..6) and the table's first word in dynamic LDS (behind the stack columns)
-};
 
 // A sparse queue on few XCDs: workgroup ids go to the eight XCDs round-robin and every XCD has its own L2, so the few thousand rays of a late
 // bounce spread over all of them fetch every node record from the Infinity Cache once PER XCD.  With `xcdRays` > 0 only the workgroups of
@@ -1738,25 +1478,6 @@ RT_FORCEINLINE float4 prim_normal(const RtPrimitive* p, float4 I) // primitives.
 // Texel `i` of the atlas.  The reference indexes `textures` unchecked (primitives.cl:124,134,145): uv == 1 lands one texel or one row
 // past a texture and a plane with negative u or v up to a whole texture past it - inside the atlas that reads a neighbouring
 // texture's texel (reproduced), past its end it is undefined behaviour.  Here, and in the oracle, texels outside the atlas are zero.
-// float -> int with the hardware's own rule (v_cvt_i32_f32 / v_cvt_u32_f32: NaN -> 0, out of range saturates), spelled out so that it
-// is defined C++ rather than a poison fptosi.  It matters: a sphere hit found with w-lane-polluted dots has a non-unit normal,
-// acos(N.y) is then NaN and the reference's kernels read texel row 0 (tests/test_gpu_reference.py, whole-frame comparison).
-RT_FORCEINLINE int f2i_gpu(float x) { return x != x ? 0 : (x >= 2147483648.0f ? 2147483647 : (x <= -2147483648.0f ? (int)(-2147483647 - 1) : (int)x)); }
-// Texel column / row of a sphere hit with normal N (primitives.cl:130-133).  The seam N.z = +-0, N.x < 0 gives ux = 1 or 0 by the
-// sign of N.z, and the pole N.y = -1 gives uy = 1: x = texW and y = texH are the reference's indices there (tests/test_gpu_math.py).
-template <bool REFB> RT_FORCEINLINE void sphere_texel_xy(float4 N, int texW, int texH, int& x, int& y)
-{
-    float ux, uy;
-    if constexpr (REFB) {
-        ux = (1.0f + __ocml_atan2pi_f32(N.z, N.x)) * 0.5f;   // primitives.cl:130 (int + float is a float add; * 0.5 is exact in any precision)
-        uy = __ocml_acospi_f32(N.y);                         // :131
-    } else {
-        ux = (float)((1 + rt_atan2f(N.z, N.x) / 3.14159265358979323846) * 0.5);
-        uy = rt_acosf(N.y) / 3.14159265358979323846f;
-    }
-    x = f2i_gpu(ux * (float)texW);
-    y = f2i_gpu(uy * (float)texH);
-}
 RT_FORCEINLINE uint32_t f2u_gpu(float x) { return !(x > 0.0f) ? 0u : (x >= 4294967296.0f ? 0xffffffffu : (uint32_t)x); }
 RT_FORCEINLINE float4 texel(const DevScene& sc, long long i) { return i >= 0 && i < (long long)sc.nTex ? sc.tex[i] : splat(0.0f); }
 // The scalar fields of a Material (bytes 32..63: specular, n1, n2, isDielectric | texIdx, texW, texH, isLight) fetched as two 16-byte
@@ -1991,7 +1712,6 @@ RT_FORCEINLINE float4 shade_hit(const DevScene& sc, const ShadeTab& tab, const D
 // Tile status word of the decoupled look-back scan: [63:62] flag (0 empty, 1 aggregate, 2 inclusive
 // prefix), [61:31] extension-ray count, [30:0] shadow-ray count.  Flag and payload travel in ONE 8-byte
 // word written/read with agent-scope atomics (L2-coherent across XCDs), so no separate fence is needed.
-static constexpr int kTile = 512;   // queue slots per tile = threads of a k_shade workgroup (a multiple of the 256 slots k_generate arms per workgroup)
 static constexpr unsigned long long kTileAgg = 1ull << 62, kTilePrefix = 2ull << 62, kTilePrefixZero = 2ull << 62;
 RT_FORCEINLINE unsigned long long tile_pack(unsigned long long flag, uint32_t e, uint32_t s) { return flag | ((unsigned long long)e << 31) | (unsigned long long)s; }
 RT_FORCEINLINE uint32_t tile_ext(unsigned long long v) { return (uint32_t)((v >> 31) & 0x7fffffffull); }

@@ -1,4 +1,4 @@
-// scene_dev.h — the device copy of a scene (scene.hip) as the contexts of rt355.hip hold it, and what the two files share: error
+// scene_dev.h — the device copy of a scene (scene.hip) as the contexts of rt355.hip hold it, and what the files of the C-ABI share: error
 // reporting and the allocation helper.  scene.hip knows nothing of a context (RtCtx) but that the holders of a copy can be made to wait.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -37,8 +37,8 @@ template <class T> static int dalloc(std::vector<void*>& bag, T** p, size_t coun
 struct RtCtx;
 namespace scenedev __attribute__((visibility("hidden"))) {   // (nothing of this interface is exported from the library)
 
-// The arrays of a copy as their owner writes them: DevScene (rt355_kernels.h, which a file without kernels cannot include) field for
-// field and in its order; a context turns them into the kernels' read-only view when it takes the copy over (rt355.hip, adopt_scene).
+// The arrays of a copy as their owner writes them: DevScene (rt355_dev.h, a header without kernels that this file could include: the
+// twin is not needed for that any more) field for field and in its order, writable and in the wire types; a context turns them into the kernels' read-only view when it takes the copy over (rt355.hip, adopt_scene).
 struct SceneArrays {
     RtPrimitive* prims; RtMaterial* mats; RtFloat4* tex; uint32_t* lights; RtBVHNode2* bvh2; RtBVHNode4* bvh4; uint32_t* primIdx;
     RtTLASNode* tlas; RtBVHInstance* blas;
