@@ -273,7 +273,8 @@ int rt_build_bvh4(int32_t device, const RtBVHNode2* nodes2, int32_t nNodes, int3
  * singular invT or a wrong instance count; RT_E_UNSUPPORTED for BVH4 contexts, scenes the update cannot handle (a TLAS not built by
  * TLAS::Build's rules, a node reachable twice), a rebuilt TLAS deeper than RT_TLAS_STACK and a clustering that finds no partner (no two
  * instance boxes with a union area below RT_REALLYFAR; rth_build_tlas refuses it too) (the work is staged: the bound scene then
- * renders exactly as before).  The update waits for the streams of every context holding the scene (rt_share_scene partners, all
+ * renders exactly as before; a BVH4 context refits through rt_rebuild_scene with RT_REBUILD_REFIT, below, which takes every context).
+ * The update waits for the streams of every context holding the scene (rt_share_scene partners, all
  * lanes and worker streams of a group), not for other device work; each of them re-derives its traversal kernels (rt_kernel_info)
  * before its next launch when the TLAS depth changed.  Synchronous; stats may be NULL.  Accumulators are not reset. */
 typedef struct RtUpdateStats {
@@ -297,6 +298,22 @@ int rt_update_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t first, int32_t
  *   RT_REBUILD_SBVH  rt_build_bvh2_sbvh's tree (BVH2::BuildBLAS with bvh2->alpha = opts->alpha, spatial splits; opts NULL or
  *                    zero-filled: alpha 0, the full SBVH; the other words of opts are ignored, as alpha is by the other builders):
  *                    the way back to an SBVH for a scene bound as one, whose refits lose the clipped leaf boxes;
+ *   RT_REBUILD_REFIT no new tree at all: the bound BVH2 is copied into the set that is not live and refit there as rt_update_scene
+ *                    refits it (opts ignored); bvhIdx, node count, primIdx, leaf ranges and pair ids stay, only boxes change.  This
+ *                    is the refit of a BVH4 copy that keeps its BVH2 (rt_update_scene refuses every BVH4 context), and one call
+ *                    that works on every context: on a BVH2 context the arrays afterwards equal, bit for bit, what
+ *                    rt_update_scene leaves for the same arguments; on a BVH4 copy they equal a fresh rt_upload_scene_bvh2 of the
+ *                    scene refit on the host (rth_set_primitives + rth_refit + rth_build_tlas), which equals rt_upload_scene of
+ *                    that scene collapsed by rth_build_bvh4.  The greedy collapse goes by box areas, so moved boxes can change
+ *                    which children a node absorbs.  One flat kernel therefore recomputes the record of every live node from the
+ *                    refit BVH2 and counts those whose slots (first, count) differ from the bound record.  None: the bound live
+ *                    ids, quad topology and stack need still hold, the records are final and only quad records are rewritten
+ *                    (in place).  Otherwise the rebuild's level-by-level collapse runs (the fallback); RT355_REFIT_RECOLLAPSE=1
+ *                    in the environment, read per call, forces it (tests, A/B runs).  Both ways end in the same bytes;
+ *                    rt_refit_info tells which one ran.  A refit cannot change the derived layout (leaf sizes do not move), and
+ *                    the stack need can only change through the fallback, which then sets `reconfigured`.  The stats of a
+ *                    refit: blas_built 0, build_ms the GPU time of the staging copies and the refit, nodes / n_idx / max_depth
+ *                    those of the bound trees, spatial_splits and prims_clipped 0;
  * every instance's bvhIdx becomes its BLAS's new root, the TLAS is rebuilt by TLAS::Build's rules and every derived array is
  * produced on the device.  No node, index or record array crosses the bus; the host reads the few words per build step the builders
  * read anyway, plus counts, depths and status.  Afterwards the arrays rt_debug_get_scene_array returns, their sizes included, are
@@ -333,6 +350,7 @@ int rt_update_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t first, int32_t
 #define RT_REBUILD_SAH   0
 #define RT_REBUILD_LBVH  1
 #define RT_REBUILD_SBVH  2
+#define RT_REBUILD_REFIT 3
 typedef struct RtRebuildStats {
     double  gpu_ms;               /* from the first to the last GPU operation of the rebuild on its stream                     */
     double  wall_ms;              /* the whole call                                                                            */
@@ -349,6 +367,13 @@ typedef struct RtRebuildStats {
 } RtRebuildStats;
 int rt_rebuild_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
                      int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats);
+/* The last successful RT_REBUILD_REFIT of the context's scene copy.  path: 0 no such call yet; 1 the records were rewritten in place
+ * (a BVH2 context always reports 1, with live_quads 0); 2 re-collapsed because changed_nodes live records changed a slot; 3
+ * re-collapsed because RT355_REFIT_RECOLLAPSE=1 forced it.  live_quads: the live BVH4 nodes afterwards; stack_need: the traversal's
+ * stack entries as the collapse counts them (a BVH2 context: the height of the deepest BLAS).  RT_E_INVALID for a null argument or
+ * when no scene is bound. */
+typedef struct RtRefitInfo { int32_t path, live_quads, changed_nodes, stack_need; } RtRefitInfo;
+int rt_refit_info(RtCtx* ctx, RtRefitInfo* out);
 /* Device allocations (hipMalloc calls) that rt_update_scene and rt_rebuild_scene have made for the context's scene copy so far, the
  * SBVH builder's included: a test can see that a repeated rebuild has stopped allocating. */
 int rt_debug_rebuild_allocations(RtCtx* ctx, int64_t* count);

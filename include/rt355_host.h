@@ -104,6 +104,16 @@ int rth_build_bvh4_gpu(RthScene* s, int device);
  * root), quadNode (live id -> node id, room for nNodes). */
 int rth_build_bvh4_levels(const RtBVHNode2* nodes2, int32_t nNodes, int32_t nIdx, const uint32_t* roots, int32_t nRoots, RtBVHNode4* out4,
                           RtBvh4Stats* stats, RtFloat4* quads, uint32_t* rootEntry, uint32_t* quadNode);
+/* The host restatement of RT_REBUILD_REFIT's collapse (rt355.h), sequential over csrc/collapse_common.h.  refit2: the BVH2 after the
+ * refit (same topology as before it); inout4: the collapse of the BVH2 before the refit; quadNode[nLive]: its live nodes by live id
+ * (rth_build_bvh4_levels' quadNode).  Writes Convert's record of every node plus the recomputed records of the live nodes and counts
+ * in *changedNodes (may be NULL) the live records that differ from inout4's in a slot's (first, count); when that count is not zero it
+ * collapses level by level instead.  Either way inout4 ends up as rth_build_bvh4_levels(refit2, ...) writes it, byte for byte; a
+ * refused call (RT_E_*, rth_last_error()) leaves it alone. */
+int rth_bvh4_refit(const RtBVHNode2* refit2, int32_t nNodes, int32_t nIdx, const uint32_t* roots, int32_t nRoots, RtBVHNode4* inout4,
+                   const uint32_t* quadNode, int32_t nLive, int32_t* changedNodes);
+/* rth_bvh4_refit on the scene's own arrays, after rth_refit: the scene's BVH4 must be the collapse of its BVH2 as it was before. */
+int rth_refit_bvh4(RthScene* s, int32_t* changedNodes);
 int rth_set_instance_transform(RthScene* s, int blas, const float invT[16]); /* scene.cpp:82 (commented out there) */
 
 /* Borrowed views of the arrays (valid until the scene changes). */

@@ -100,6 +100,10 @@ UpdateStats = np.dtype([("gpu_ms", "<f8"), ("prims", "<i4"), ("nodes", "<i4"), (
                         ("reconfigured", "<i4"), ("reserved", "<i4", 3)])
 assert UpdateStats.itemsize == 40
 REBUILD_SAH, REBUILD_LBVH, REBUILD_SBVH = 0, 1, 2   # rt_rebuild_scene builders
+REBUILD_REFIT = 3                                   # ... and its refit: no builder runs (the device library only: rth_rebuild refuses it)
+RefitInfo = np.dtype([(n, "<i4") for n in ("path", "live_quads", "changed_nodes", "stack_need")])   # RtRefitInfo
+assert RefitInfo.itemsize == 16
+REFIT_NONE, REFIT_IN_PLACE, REFIT_RECOLLAPSED, REFIT_FORCED = 0, 1, 2, 3   # RtRefitInfo.path
 RebuildStats = np.dtype([(n, "<f8") for n in ("gpu_ms", "wall_ms", "stage_ms", "build_ms", "derive_ms", "tlas_ms", "commit_ms")] +
                         [(n, "<i4") for n in ("prims", "blas_built", "nodes", "n_idx", "max_depth", "tlas_nodes", "tlas_depth", "reconfigured")] +
                         [("spatial_splits", "<i4"), ("prims_clipped", "<i4")])
@@ -112,7 +116,7 @@ DEVICE_SYMBOLS = [
     "rt_stage_begin_frame", "rt_stage_generate", "rt_stage_extend", "rt_stage_shade", "rt_stage_connect",
     "rt_debug_get_rays", "rt_debug_set_rays", "rt_debug_get_shadow", "rt_debug_enable_steps", "rt_debug_get_steps", "rt_debug_math",
     "rt_debug_math_sweep", "rt_debug_math_mode", "rt_debug_math_sweep_mode", "rt_validate_scene", "rt_build_bvh2", "rt_build_bvh2_sah", "rt_debug_sah_phases", "rt_build_bvh2_sbvh", "rt_debug_sbvh_phases", "rt_update_scene", "rt_group_update_scene", "rt_debug_get_scene_array",
-    "rt_rebuild_scene", "rt_group_rebuild_scene", "rt_blas_ranges", "rt_debug_rebuild_allocations",
+    "rt_rebuild_scene", "rt_group_rebuild_scene", "rt_blas_ranges", "rt_debug_rebuild_allocations", "rt_refit_info",
     "rt_build_bvh4", "rt_upload_scene_bvh2", "rt_group_upload_scene_bvh2",
     "rt_group_create", "rt_group_destroy", "rt_group_lanes", "rt_group_concurrency", "rt_group_stream_class", "rt_group_class_concurrency", "rt_group_lane", "rt_group_frames", "rt_group_upload_scene", "rt_group_share_scene",
     "rt_group_seed", "rt_group_reset", "rt_group_render", "rt_group_synchronize", "rt_group_sum", "rt_group_read_accum", "rt_group_focus",
@@ -127,7 +131,7 @@ HOST_SYMBOLS = [
     "rth_set_build_threads", "rth_renderer_save_frame", "rth_renderer_camera_move", "rth_renderer_camera_mouse", "rth_renderer_camera_zoom", "rth_renderer_frames", "rth_renderer_set_lanes", "rth_renderer_set_builtins", "rth_renderer_builtins",
     "rth_build_blas_lbvh", "rth_build_bvh2_lbvh", "rth_lbvh_stats", "rth_set_primitives", "rth_refit",
     "rth_build_blas_sah_gpu", "rth_build_bvh2_sah", "rth_build_blas_sbvh_gpu", "rth_build_bvh2_sbvh", "rth_rebuild", "rth_blas_ranges",
-    "rth_build_bvh4_gpu", "rth_build_bvh4_levels"]
+    "rth_build_bvh4_gpu", "rth_build_bvh4_levels", "rth_bvh4_refit", "rth_refit_bvh4"]
 
 _dev = None
 _host = None
@@ -231,6 +235,7 @@ def _bind_device(lib):
         lib.rt_rebuild_scene.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp, vp]
         lib.rt_group_rebuild_scene.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp, vp]
         lib.rt_debug_rebuild_allocations.argtypes = [vp, vp]
+        lib.rt_refit_info.argtypes = [vp, vp]
         lib.rt_blas_ranges.argtypes = [vp, i32, vp, i32, i32, vp, i32, vp, vp]
         lib.rt_group_create.argtypes = [vp, i32, C.POINTER(vp)]
         lib.rt_group_destroy.argtypes = [vp]
@@ -277,6 +282,8 @@ def host_lib():
         lib.rth_build_bvh4.argtypes = [vp]
         lib.rth_build_bvh4_gpu.argtypes = [vp, i32]
         lib.rth_build_bvh4_levels.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, vp, vp, vp, vp, vp]
+        lib.rth_bvh4_refit.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, vp, vp, C.c_int32, C.POINTER(C.c_int32)]
+        lib.rth_refit_bvh4.argtypes = [vp, C.POINTER(C.c_int32)]
         lib.rth_build_blas_lbvh.argtypes = [vp, i32, i32, vp]
         lib.rth_build_bvh2_lbvh.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, vp, C.c_int32,
                                             C.POINTER(C.c_int32), vp, vp]

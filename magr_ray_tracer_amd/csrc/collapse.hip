@@ -12,6 +12,9 @@
 // A BVH4 level descends at least one BVH2 level, so the host launches as many levels as the BVH2 is high (one for a leaf root) with
 // frontiers bounded by min(4^l, interior nodes), and reads nothing back; empty levels do nothing.  Every position comes from a scan: no
 // atomic decides where anything is written, two runs give the same bytes.  Then, over all BLAS:
+//   k_c4_refit      (a refit BVH2 under a bound collapse, RT_REBUILD_REFIT) one thread per bound live id: the final record from the refit
+//                   BVH2, and a count of the records whose slots differ from the bound ones; zero: the bound live ids still hold and
+//                   the level loop above is skipped
 //   k_c4_quads      one thread per live id: the quad record (collapse::quad_record)
 //   k_c4_roots      one thread per instance: rootEntry[b] = newId[root of b]
 // Flat kernels of 256 threads; nothing here depends on the wave size.
@@ -101,6 +104,25 @@ __global__ void __launch_bounds__(kBlock) k_c4_next(const uint2* front, uint32_t
         }
 }
 
+// One thread per live id of the bound collapse.  Reads the BVH2 and the bound records only: nothing another thread writes.
+__global__ void __launch_bounds__(kBlock) k_c4_refit(const RtBVHNode2* nodes, uint32_t nNodes, const RtBVHNode4* bound4, const uint32_t* quadNode,
+                                                     uint32_t nLive, RtBVHNode4* bvh4, uint32_t* ctr)
+{
+    const uint32_t q = blockIdx.x * kBlock + threadIdx.x;
+    if (q >= nLive) return;
+    if (q == 0) ctr[kLive] = nLive;
+    const uint32_t node = quadNode[q];
+    RtBVHNode4 rec;
+    if (!final_record(nodes, nNodes, node, rec)) { atomicOr(&ctr[kWalkWord], kWalk); return; }   // (node < nNodes: final_record's first check)
+    bvh4[node] = rec;
+    const RtBVHNode4& old = bound4[node];
+    bool same = true;
+    for (int k = 0; k < 4; k++) same = same && rec.first[k] == old.first[k] && rec.count[k] == old.count[k];
+    if (!same) atomicAdd(&ctr[kChanged], 1u);
+    const uint32_t leaf = largest_leaf(rec);
+    if (leaf) atomicMax(&ctr[kLeaf], leaf);
+}
+
 __global__ void __launch_bounds__(kBlock) k_c4_quads(const RtBVHNode4* bvh4, uint32_t nNodes, uint32_t nIdx, const uint32_t* quadNode, const uint32_t* newId,
                                                      uint32_t quadCap, const uint32_t* ctr, RtFloat4* quads)
 {
@@ -153,6 +175,14 @@ hipError_t collapse_blas(hipStream_t s, const Work& w, const RtBVHNode2* nodes, 
         hipLaunchKernelGGL(k_c4_next, grid(ub), dim3(kBlock), 0, s, front, ub, l, w.flags, w.ranks, w.kids, next, w.frontCap, l + 1 == levels ? 1u : 0u, w.ctr);
         uint2* t = front; front = next; next = t;
     }
+    return hipGetLastError();
+}
+
+hipError_t refit_records(hipStream_t s, const Work& w, const RtBVHNode2* nodes, uint32_t nNodes, const RtBVHNode4* bound4, const uint32_t* quadNode,
+                         uint32_t nLive, RtBVHNode4* bvh4)
+{
+    if (nLive == 0 || nLive > w.quadCap) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_c4_refit, grid(nLive), dim3(kBlock), 0, s, nodes, nNodes, bound4, quadNode, nLive, bvh4, w.ctr);
     return hipGetLastError();
 }
 

@@ -742,6 +742,13 @@ extern "C" int rt_rebuild_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t fi
                     "(bind the BVH2 with rt_upload_scene_bvh2, or build on the host and upload)");
     return rebuild_scene(*ctx->scene, prims, first, count, blas, nBlas, builder, opts, stats);
 }
+extern "C" int rt_refit_info(RtCtx* ctx, RtRefitInfo* out)
+{
+    if (!ctx || !out) return fail(RT_E_INVALID, "rt_refit_info: null argument");
+    if (!ctx->sceneLoaded || !ctx->scene) return fail(RT_E_INVALID, "rt_refit_info: no scene uploaded");
+    *out = ctx->scene->refitInfo;
+    return RT_OK;
+}
 extern "C" int rt_debug_rebuild_allocations(RtCtx* ctx, int64_t* count)
 {
     if (!ctx || !count) return fail(RT_E_INVALID, "rt_debug_rebuild_allocations: null argument");

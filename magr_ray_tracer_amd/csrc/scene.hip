@@ -147,6 +147,26 @@ static int prepare_update(SceneBag& b, int accel, int extendVariant, const HostS
     b.variantLayout1 = extendVariant != 1;
     // rt_rebuild_scene: the primitive range of each BLAS (rebuild_common.h)
     b.rebuildRefusal = rebuild::find_blas_ranges((const RtBVHNode2*)bvhNodes, nNodes, primIdx, nIdx, nPrims, blas, nBlas, b.ranges, b.instBlas);
+    if (!b.rebuildRefusal) {   // RT_REBUILD_REFIT: root, interior nodes and height of every BLAS (build_topology has walked the trees: no cycle)
+        const RtBVHNode2* n2 = (const RtBVHNode2*)bvhNodes;
+        const size_t nR = b.ranges.size();
+        b.blasRoot.assign(nR, 0u); b.blasInteriors.assign(nR, 0u); b.blasHeight.assign(nR, 0u);
+        std::vector<uint8_t> done(nR, 0);
+        std::vector<std::pair<uint32_t, uint32_t>> st;
+        for (int32_t i = 0; i < nBlas; i++) {
+            const size_t k = (size_t)b.instBlas[(size_t)i];
+            if (done[k]) continue;
+            done[k] = 1; b.blasRoot[k] = blas[i].bvhIdx;
+            st.assign(1, { blas[i].bvhIdx, 0u });
+            while (!st.empty()) {
+                const auto [node, d] = st.back(); st.pop_back();
+                b.blasHeight[k] = std::max(b.blasHeight[k], d);
+                if (n2[node].count > 0) continue;
+                b.blasInteriors[k]++;
+                st.push_back({ n2[node].first, d + 1 }); st.push_back({ n2[node].first + 1, d + 1 });
+            }
+        }
+    }
     b.nLeaves = (uint32_t)t.leaves.size(); b.nReach = (uint32_t)t.order.size();
     int rc = dalloc(b.allocs, &b.dParent, t.parent.size());
     if (rc == RT_OK) rc = dalloc(b.allocs, &b.dLeaves, t.leaves.size());
@@ -392,30 +412,36 @@ template <class T> static int rebuild_grow(SceneBag& b, SceneBag::Grown<T>& a, s
 }
 
 // ---- the BVH2 -> BVH4 collapse of a copy that keeps its BVH2 (kernels: collapse.hip, rules: collapse_common.h) --------------------------
-// The collapse's scratch for trees of nodeNeed nodes in all and nR BLAS; grows as the derivation's scratch does (rebuild_scratch)
-static int collapse_scratch(SceneBag& b, size_t nodeNeed, size_t nR)
+// The collapse's scratch for trees of nodeNeed nodes in all; grows as the derivation's scratch does (rebuild_scratch).  b.c4 lacks the
+// tables the collapse leaves behind (newId, quadNode and their capacity): collapse_work adds those of the arrays that are collapsed.
+static collapsedev::Work collapse_work(const SceneBag& b, uint32_t* newId, uint32_t* quadNode, size_t quadCap)
 {
-    const bool have = b.c4NewId.p != nullptr;
-    size_t cap = nodeNeed <= b.c4NewId.cap ? b.c4NewId.cap : nodeNeed + (have ? nodeNeed / kRebuildHeadroomDiv : 0);
+    collapsedev::Work w = b.c4;
+    w.newId = newId; w.quadNode = quadNode; w.quadCap = (uint32_t)std::min<size_t>(quadCap, 0x7fffffffu);
+    return w;
+}
+static int collapse_scratch(SceneBag& b, size_t nodeNeed)
+{
+    const bool have = b.c4Cap != 0;
+    size_t cap = nodeNeed <= b.c4Cap ? b.c4Cap : nodeNeed + (have ? nodeNeed / kRebuildHeadroomDiv : 0);
     cap = (cap + 1) & ~(size_t)1;
-    const size_t front = cap / 2 + 1, quad = cap / 2 + nR;
+    const size_t front = cap / 2 + 1;
     if (4 * front > (size_t)0x7fffffff) return fail(RT_E_UNSUPPORTED, "the BVH4 collapse takes at most 2^30 nodes (%zu given)", nodeNeed);
-    int rc = rebuild_grow(b, b.c4NewId, cap, 0, "collapse scratch");
-    if (rc == RT_OK) rc = rebuild_grow(b, b.c4FrontA, front, 0, "collapse scratch");
+    int rc = rebuild_grow(b, b.c4FrontA, front, 0, "collapse scratch");
     if (rc == RT_OK) rc = rebuild_grow(b, b.c4FrontB, front, 0, "collapse scratch");
     if (rc == RT_OK) rc = rebuild_grow(b, b.c4Flags, 4 * front, 0, "collapse scratch");
     if (rc == RT_OK) rc = rebuild_grow(b, b.c4Ranks, 4 * front, 0, "collapse scratch");
     if (rc == RT_OK) rc = rebuild_grow(b, b.c4Kids, 4 * front, 0, "collapse scratch");
-    if (rc == RT_OK) rc = rebuild_grow(b, b.c4QuadNode, quad, 0, "collapse scratch");
     if (rc == RT_OK) rc = rebuild_grow(b, b.c4Ctr, collapsedev::kCtrWords, 0, "collapse scratch");
     if (rc != RT_OK) return rc;
+    b.c4Cap = cap;
     const size_t frontCap = std::min(std::min(b.c4FrontA.cap, b.c4FrontB.cap), std::min(std::min(b.c4Flags.cap, b.c4Ranks.cap), b.c4Kids.cap) / 4);
     size_t scanBytes = 0;
     HIPCHK(collapsedev::scan_bytes((uint32_t)(4 * frontCap), b.stream, &scanBytes));
     rc = rebuild_grow(b, b.c4Scan, std::max<size_t>(scanBytes, 256), 0, "scan workspace");
     if (rc != RT_OK) return rc;
-    b.c4 = collapsedev::Work{ b.c4FrontA.p, b.c4FrontB.p, (uint32_t)frontCap, b.c4Flags.p, b.c4Ranks.p, b.c4Kids.p, b.c4NewId.p, b.c4QuadNode.p,
-                              (uint32_t)b.c4QuadNode.cap, b.c4Ctr.p, b.c4Scan.p, b.c4Scan.cap };
+    b.c4 = collapsedev::Work{ b.c4FrontA.p, b.c4FrontB.p, (uint32_t)frontCap, b.c4Flags.p, b.c4Ranks.p, b.c4Kids.p, nullptr, nullptr, 0u, b.c4Ctr.p,
+                              b.c4Scan.p, b.c4Scan.cap };
     return RT_OK;
 }
 // What a collapse left in its status words: a failed walk, a BLAS that needs more stack than there is.  `tail` ends the stack message.
@@ -441,16 +467,22 @@ static int collapse_uploaded(SceneBag& b, SceneArrays& sc, int extendVariant, co
     const int32_t nNodes = in.nNodes, nIdx = in.nIdx, nBlas = in.nBlas;
     if (!b.stream) HIPCHK(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));
     hipStream_t s = b.stream;
+    size_t quadCap = 0;   // a live node per interior node and leaf root at most
+    for (const collapse::Blas& k : blas4) quadCap += std::max(k.interiors, 1u);
     int rc = dalloc(b.allocs, &sc.bvh4, (size_t)nNodes);
-    if (rc == RT_OK) rc = collapse_scratch(b, (size_t)nNodes, blas4.size());
+    if (rc == RT_OK) rc = dalloc(b.allocs, &b.liveNewId, (size_t)nNodes);   // the copy's own: RT_REBUILD_REFIT reads them
+    if (rc == RT_OK) rc = dalloc(b.allocs, &b.liveQuadNode, quadCap);
+    if (rc == RT_OK) rc = collapse_scratch(b, (size_t)nNodes);
     if (rc != RT_OK) return rc;
-    HIPCHK(begin(s, b.c4, sc.bvh2, (uint32_t)nNodes, sc.bvh4));
-    for (const collapse::Blas& k : blas4) HIPCHK(collapse_blas(s, b.c4, sc.bvh2, (uint32_t)nNodes, k.root, k.interiors, k.height, sc.bvh4));
+    Work w = collapse_work(b, b.liveNewId, b.liveQuadNode, quadCap);
+    HIPCHK(begin(s, w, sc.bvh2, (uint32_t)nNodes, sc.bvh4));
+    for (const collapse::Blas& k : blas4) HIPCHK(collapse_blas(s, w, sc.bvh2, (uint32_t)nNodes, k.root, k.interiors, k.height, sc.bvh4));
     uint32_t st[kStatusWords] = { 0 };
     HIPCHK(hipMemcpyAsync(st, b.c4.ctr + kStatus, sizeof st, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if ((rc = collapse_status_error(who, st, "")) != RT_OK) return rc;
     const uint32_t live = st[kLive - kStatus];
+    b.nLive = live; b.c4Need = st[kNeed - kStatus];
     layout = rebuild::takes_layout1(extendVariant != 1, nIdx, collapse_largest_leaf(st)) ? 1 : 0;
     stackEntries = rebuild::stack_entries((int)std::max(st[kNeed - kStatus], 1u));
     b.nQuads = layout == 1 ? (int32_t)live : 0;
@@ -460,7 +492,6 @@ static int collapse_uploaded(SceneBag& b, SceneArrays& sc, int extendVariant, co
     if (rc == RT_OK) rc = dalloc(b.allocs, &sc.rootEntry, (size_t)nBlas);
     if (rc == RT_OK) rc = dalloc(b.allocs, &sc.triRecs, (size_t)nIdx * 3);
     if (rc != RT_OK) return rc;
-    Work w = b.c4;
     w.quadCap = std::min(w.quadCap, std::max(live, 1u));   // what sc.quads holds
     HIPCHK(finish(s, w, sc.bvh4, (uint32_t)nNodes, (uint32_t)nIdx, (const uint32_t*)sc.blas, (uint32_t)(sizeof(RtBVHInstance) / 4), (uint32_t)nBlas, sc.quads, sc.rootEntry));
     HIPCHK(refitdev::launch_records(s, sc.prims, sc.bvh2, sc.primIdx, (uint32_t)nIdx, sc.lights, (uint32_t)in.nLights, 0u, (uint32_t)in.nPrims, nullptr, 0u, nullptr,
@@ -562,6 +593,8 @@ static int rebuild_reserve(SceneBag& b, SceneBag::RebuildSet& t, size_t idxNeed,
     if (b.accel == RT_ACCEL_BVH4) {   // (a copy that keeps its BVH2: the collapsed records, and a quad record per interior node and leaf root at most)
         if (rc == RT_OK) rc = rebuild_grow(b, t.bvh4, nodeCap, 0, "BVH4 nodes");
         if (rc == RT_OK) rc = rebuild_grow(b, t.quads, (nodeCap / 2 + b.ranges.size()) * 8, 0, "quad records");
+        if (rc == RT_OK) rc = rebuild_grow(b, t.newId, nodeCap, 0, "live ids");
+        if (rc == RT_OK) rc = rebuild_grow(b, t.quadNode, nodeCap / 2 + b.ranges.size(), 0, "live nodes");
     }
     return rc;
 }
@@ -622,8 +655,9 @@ int scenedev::rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first
     // ---- refusals that need no device work
     if (b.refitRefusal) return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: %s", b.refitRefusal);
     if (b.rebuildRefusal) return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: %s", b.rebuildRefusal);
-    if (builder != RT_REBUILD_SAH && builder != RT_REBUILD_LBVH && builder != RT_REBUILD_SBVH) return fail(RT_E_INVALID, "rt_rebuild_scene: unknown builder %d", builder);
-    const bool sbvh = builder == RT_REBUILD_SBVH;
+    if (builder != RT_REBUILD_SAH && builder != RT_REBUILD_LBVH && builder != RT_REBUILD_SBVH && builder != RT_REBUILD_REFIT)
+        return fail(RT_E_INVALID, "rt_rebuild_scene: unknown builder %d", builder);
+    const bool sbvh = builder == RT_REBUILD_SBVH, refit = builder == RT_REBUILD_REFIT;   // (refit: no builder runs, opts is ignored)
     const float alpha = sbvh && opts ? opts->alpha : 0.0f;
     if (!(alpha >= 0.0f && alpha <= 1.0f)) return fail(RT_E_INVALID, "rt_rebuild_scene: alpha must lie in [0, 1]");
     if (const int rc = check_change(who, b, prims, first, count, blas, nBlas, "")) return rc;
@@ -631,7 +665,7 @@ int scenedev::rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first
     // the builders' own argument checks, BLAS by BLAS (node and index ids as the host appends BLAS after BLAS; the SBVH builder's ids
     // are known only as the trees are built: its ranges are the upload's, at most 2^30 primitives each, and alpha is checked above)
     lbvh::Params P{};
-    if (!sbvh) {
+    if (!sbvh && !refit) {
         uint32_t nodeBase = 0, idxBase = 0;
         for (const rebuild::BlasRange& r : b.ranges) {
             const int32_t cap = 2 * (int32_t)r.count - 1;
@@ -640,14 +674,16 @@ int scenedev::rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first
             if (msg) return fail(RT_E_INVALID, "rt_rebuild_scene: %s", msg);
             nodeBase += (uint32_t)cap; idxBase += r.count;
         }
-    } else {
+    } else if (sbvh) {
         for (const rebuild::BlasRange& r : b.ranges) if (r.count == 0 || r.count > (1u << 30)) return fail(RT_E_INVALID, "rt_rebuild_scene: a BLAS of %u primitives", r.count);
     }
     HIPCHK(hipSetDevice(b.device));
     SceneBag::RebuildSet& t = b.rset[b.rnext];
     if (const int rc = rebuild_alloc(b, t)) return rc;
     hipStream_t s = b.stream;
-    if (!sbvh) {
+    if (refit) {   // room for the bound trees (nR spare nodes: see the SBVH builder below)
+        if (const int rc = rebuild_reserve(b, t, (size_t)b.nIdx, (size_t)b.nNodes + nR, 0, 0)) return rc;
+    } else if (!sbvh) {
         // room for every tree these builders can make (a set or the scratch that started smaller, or has only held SBVH trees so far)
         if (const int rc = rebuild_reserve(b, t, (size_t)b.nPrims, 2 * (size_t)b.nPrims, 0, 0)) return rc;
         // the builders' workspace
@@ -668,11 +704,24 @@ int scenedev::rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first
     if (count) HIPCHK(hipMemcpyAsync(t.prims + first, prims, sizeof(RtPrimitive) * (size_t)count, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(t.lightRecs, sc.lightRecs, sizeof(RtFloat4) * 8 * std::max<size_t>((size_t)b.nLights, 1), hipMemcpyDeviceToDevice, s));   // (the emittance words stay)
     const auto t1 = clock::now();
-    // ---- every BLAS anew, in the order of the ranges
+    // ---- every BLAS anew, in the order of the ranges (a refit: the bound trees, their boxes anew)
     std::vector<uint32_t> rootOf(nR), interiors(nR), depth(nR);
     uint32_t nNodes = 0, nIdx = 0, maxDepth = 0;
     uint64_t spatialSplits = 0, primsClipped = 0;
-    for (size_t k = 0; k < nR; k++) {
+    if (refit) {
+        // the bound trees and their refit topology into the set, then the boxes anew: no BLAS is built, so node ids, leaf ranges,
+        // primIdx and pair ids stay
+        nNodes = (uint32_t)b.nNodes; nIdx = (uint32_t)b.nIdx;
+        HIPCHK(hipMemcpyAsync(t.nodes.p, sc.bvh2, sizeof(RtBVHNode2) * (size_t)nNodes, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(t.primIdx.p, sc.primIdx, sizeof(uint32_t) * (size_t)nIdx, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemcpyAsync(t.parent.p, b.dParent, sizeof(uint32_t) * (size_t)nNodes, hipMemcpyDeviceToDevice, s));
+        if (b.nLeaves) HIPCHK(hipMemcpyAsync(t.leaves.p, b.dLeaves, sizeof(uint32_t) * (size_t)b.nLeaves, hipMemcpyDeviceToDevice, s));
+        if (b.nPairs) HIPCHK(hipMemcpyAsync(t.pairNode.p, b.dPairNode, sizeof(uint32_t) * (size_t)b.nPairs, hipMemcpyDeviceToDevice, s));
+        HIPCHK(refitdev::launch_refit(s, t.nodes.p, nNodes, t.prims, t.primIdx.p, t.leaves.p, b.nLeaves, t.parent.p, t.tickets.p));
+        rootOf = b.blasRoot; interiors = b.blasInteriors; depth = b.blasHeight;
+        for (size_t k = 0; k < nR; k++) maxDepth = std::max(maxDepth, depth[k]);
+    }
+    for (size_t k = 0; k < nR && !refit; k++) {
         const rebuild::BlasRange& r = b.ranges[k];
         Built built{};
         uint32_t slots = r.count;
@@ -705,9 +754,9 @@ int scenedev::rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first
         maxDepth = std::max(maxDepth, built.depth);
         nNodes += built.nodes; nIdx += slots;
     }
-    if (const int rc = rebuild_scratch(b, (size_t)nNodes + nR)) return rc;
+    if (!refit) if (const int rc = rebuild_scratch(b, (size_t)nNodes + nR)) return rc;
     const bool bvh4 = b.accel == RT_ACCEL_BVH4;
-    if (bvh4) if (const int rc = collapse_scratch(b, (size_t)nNodes + nR, nR)) return rc;
+    if (bvh4) if (const int rc = collapse_scratch(b, (size_t)nNodes + nR)) return rc;
     const auto t2 = clock::now();
     // ---- the instances (host: at most 256 records), then everything upload derives
     std::vector<RtBVHInstance> inst = b.inst;
@@ -715,27 +764,49 @@ int scenedev::rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first
     for (int32_t i = 0; i < b.nBlas; i++) inst[(size_t)i].bvhIdx = rootOf[(size_t)b.instBlas[(size_t)i]];
     HIPCHK(hipMemcpyAsync(t.blas, inst.data(), sizeof(RtBVHInstance) * (size_t)b.nBlas, hipMemcpyHostToDevice, s));
     HIPCHK(hipEventRecord(b.rev[1], s));
-    HIPCHK(rebuilddev::begin(s, b.dw, t.parent.p, nNodes));
     uint32_t nPairs = 0;
-    {   // pair ids: BLAS by BLAS in the order in which the instances first name them
-        std::vector<uint8_t> done(nR, 0);
-        for (int32_t i = 0; i < b.nBlas; i++) {
-            const size_t k = (size_t)b.instBlas[(size_t)i];
-            if (done[k]) continue;
-            done[k] = 1;
-            HIPCHK(rebuilddev::number_blas(s, b.dw, t.nodes.p, nNodes, rootOf[k], interiors[k], depth[k], nPairs, (uint32_t)t.pairNode.cap, t.pairNode.p, t.parent.p));
-            nPairs += interiors[k];
-        }
-    }
-    const uint32_t nLeaves = nNodes - nPairs;
     const bool layout1 = b.layout == 1;
-    HIPCHK(rebuilddev::finish(s, b.dw, t.nodes.p, nNodes, nPairs, nLeaves, t.blas, (uint32_t)b.nBlas, t.pairNode.p, layout1 && !bvh4 ? t.pairs.p : nullptr, t.rootEntry,
-                              t.leaves.p));
+    if (refit) {   // the pair records (launch_records rewrites their boxes) and the root entries as they are bound
+        nPairs = (uint32_t)b.nPairs;
+        if (layout1 && !bvh4) {
+            HIPCHK(hipMemcpyAsync(t.pairs.p, sc.pairs, sizeof(RtFloat4) * 4 * std::max<size_t>(nPairs, 1), hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(t.rootEntry, sc.rootEntry, sizeof(uint32_t) * (size_t)b.nBlas, hipMemcpyDeviceToDevice, s));
+        }
+    } else {
+        HIPCHK(rebuilddev::begin(s, b.dw, t.parent.p, nNodes));
+        {   // pair ids: BLAS by BLAS in the order in which the instances first name them
+            std::vector<uint8_t> done(nR, 0);
+            for (int32_t i = 0; i < b.nBlas; i++) {
+                const size_t k = (size_t)b.instBlas[(size_t)i];
+                if (done[k]) continue;
+                done[k] = 1;
+                HIPCHK(rebuilddev::number_blas(s, b.dw, t.nodes.p, nNodes, rootOf[k], interiors[k], depth[k], nPairs, (uint32_t)t.pairNode.cap, t.pairNode.p, t.parent.p));
+                nPairs += interiors[k];
+            }
+        }
+        HIPCHK(rebuilddev::finish(s, b.dw, t.nodes.p, nNodes, nPairs, nNodes - nPairs, t.blas, (uint32_t)b.nBlas, t.pairNode.p, layout1 && !bvh4 ? t.pairs.p : nullptr,
+                                  t.rootEntry, t.leaves.p));
+    }
+    const uint32_t nLeaves = refit ? b.nLeaves : nNodes - nPairs;
+    uint32_t c4st[collapsedev::kStatusWords] = { 0 };
+    int32_t refitPath = refit ? 1 : 0;
     if (bvh4) {   // the collapse into the set's bvh4, BLAS by BLAS in the same order; quad records and root entries (layout 1)
-        collapsedev::Work w = b.c4;
-        w.quadCap = (uint32_t)std::min<size_t>(w.quadCap, t.quads.cap / 8);
+        const collapsedev::Work w = collapse_work(b, t.newId.p, t.quadNode.p, std::min(t.quadNode.cap, t.quads.cap / 8));
         HIPCHK(collapsedev::begin(s, w, t.nodes.p, nNodes, t.bvh4.p));
-        std::vector<uint8_t> done(nR, 0);
+        if (refit) {
+            // in place: the live records anew under the bound live ids (the set takes the bound tables over); if no slot of any of
+            // them changed, they are the collapse of the refit trees and the level loop is skipped
+            HIPCHK(hipMemcpyAsync(t.newId.p, b.liveNewId, sizeof(uint32_t) * (size_t)nNodes, hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(t.quadNode.p, b.liveQuadNode, sizeof(uint32_t) * (size_t)b.nLive, hipMemcpyDeviceToDevice, s));
+            HIPCHK(collapsedev::refit_records(s, w, t.nodes.p, nNodes, sc.bvh4, t.quadNode.p, b.nLive, t.bvh4.p));
+            HIPCHK(hipMemcpyAsync(c4st, w.ctr + collapsedev::kStatus, sizeof c4st, hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            if (const int rc = collapse_status_error(who, c4st, "; the scene is unchanged")) return rc;
+            const char* env = getenv("RT355_REFIT_RECOLLAPSE");
+            refitPath = env && atoi(env) == 1 ? 3 : c4st[collapsedev::kChanged - collapsedev::kStatus] ? 2 : 1;
+            if (refitPath != 1) HIPCHK(collapsedev::begin(s, w, t.nodes.p, nNodes, t.bvh4.p));   // the fallback: the rebuild's collapse
+        }
+        std::vector<uint8_t> done(nR, refitPath == 1 ? 1 : 0);
         for (int32_t i = 0; i < b.nBlas; i++) {
             const size_t k = (size_t)b.instBlas[(size_t)i];
             if (done[k]) continue;
@@ -745,18 +816,21 @@ int scenedev::rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first
         HIPCHK(collapsedev::finish(s, w, t.bvh4.p, nNodes, nIdx, (const uint32_t*)t.blas, (uint32_t)(sizeof(RtBVHInstance) / 4), (uint32_t)b.nBlas,
                                    layout1 ? t.quads.p : nullptr, t.rootEntry));
     }
-    HIPCHK(refitdev::launch_records(s, t.prims, t.nodes.p, t.primIdx.p, nIdx, sc.lights, (uint32_t)b.nLights, 0u, (uint32_t)b.nPrims, nullptr, 0u, nullptr,
-                                    layout1 ? t.triRecs.p : nullptr, t.shadeRecs, t.lightRecs));
+    const bool boxes = refit && layout1 && !bvh4;
+    HIPCHK(refitdev::launch_records(s, t.prims, t.nodes.p, t.primIdx.p, nIdx, sc.lights, (uint32_t)b.nLights, 0u, (uint32_t)b.nPrims,
+                                    boxes ? t.pairNode.p : nullptr, boxes ? nPairs : 0u, boxes ? t.pairs.p : nullptr, layout1 ? t.triRecs.p : nullptr,
+                                    t.shadeRecs, t.lightRecs));
     HIPCHK(hipEventRecord(b.rev[2], s));
     HIPCHK(refitdev::launch_tlas(s, t.nodes.p, t.blas, b.nBlas, layout1 ? t.rootEntry : nullptr, t.tlas, t.tp, t.tpP, t.ir, b.rStatus));
     HIPCHK(hipEventRecord(b.rev[3], s));
     int32_t status[2] = { 0, 0 };
     uint32_t walk[2] = { 0, 0 };
     HIPCHK(hipMemcpyAsync(status, b.rStatus, sizeof status, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(walk, b.dw.ctr + rebuilddev::kStatus, sizeof walk, hipMemcpyDeviceToHost, s));
-    uint32_t c4st[collapsedev::kStatusWords] = { 0 };
-    if (bvh4) HIPCHK(hipMemcpyAsync(c4st, b.c4.ctr + collapsedev::kStatus, sizeof c4st, hipMemcpyDeviceToHost, s));
+    if (!refit) HIPCHK(hipMemcpyAsync(walk, b.dw.ctr + rebuilddev::kStatus, sizeof walk, hipMemcpyDeviceToHost, s));
+    const uint32_t changed = c4st[collapsedev::kChanged - collapsedev::kStatus];
+    if (bvh4 && refitPath != 1) HIPCHK(hipMemcpyAsync(c4st, b.c4.ctr + collapsedev::kStatus, sizeof c4st, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
+    if (bvh4 && refitPath == 1) c4st[collapsedev::kNeed - collapsedev::kStatus] = b.c4Need;   // (a top-down figure: carried over with the live ids)
     if (walk[0]) return fail(RT_E_DEVICE, "rt_rebuild_scene: the breadth-first walk does not match the builder's tree (inconsistent device result)");
     if (bvh4) {
         if (const int rc = collapse_status_error(who, c4st, "; the scene is unchanged")) return rc;
@@ -764,7 +838,8 @@ int scenedev::rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first
     }
     if (const int rc = tlas_status_error(who, status)) return rc;
     const int stackNeed = bvh4 ? (int)c4st[collapsedev::kNeed - collapsedev::kStatus] : (int)maxDepth;
-    if (rebuild::takes_layout1(b.variantLayout1, (int32_t)nIdx, std::max(walk[1], 1u)) != layout1)
+    // (a refit moves no leaf size: a BVH2 copy keeps its layout, a BVH4 copy's check cannot fail)
+    if (!(refit && !bvh4) && rebuild::takes_layout1(b.variantLayout1, (int32_t)nIdx, std::max(walk[1], 1u)) != layout1)
         return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: the new trees would change the scene's derived layout (largest leaf %u primitives, %u index slots; "
                     "layout %d is bound): upload the rebuilt scene instead; the scene is unchanged", walk[1], nIdx, b.layout);
     const auto t3 = clock::now();
@@ -780,8 +855,15 @@ int scenedev::rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first
     if (bvh4) { n.bvh4 = t.bvh4.p; if (layout1) n.quads = t.quads.p; }
     b.sc = n;
     b.dParent = t.parent.p; b.dLeaves = t.leaves.p; b.dTickets = t.tickets.p; b.dPairNode = t.pairNode.p;
-    b.nNodes = (int32_t)nNodes; b.nIdx = (int32_t)nIdx; b.nPairs = layout1 && !bvh4 ? (int32_t)nPairs : 0; b.nLeaves = nLeaves; b.nReach = nNodes;
+    b.nNodes = (int32_t)nNodes; b.nIdx = (int32_t)nIdx; b.nPairs = layout1 && !bvh4 ? (int32_t)nPairs : 0; b.nLeaves = nLeaves;
+    if (!refit) b.nReach = nNodes;
     b.nQuads = layout1 && bvh4 ? (int32_t)c4st[collapsedev::kLive - collapsedev::kStatus] : 0;
+    b.blasRoot = rootOf; b.blasInteriors = interiors; b.blasHeight = depth;
+    if (bvh4) {   // the live collapse's tables follow the sets
+        b.liveNewId = t.newId.p; b.liveQuadNode = t.quadNode.p;
+        b.nLive = c4st[collapsedev::kLive - collapsedev::kStatus]; b.c4Need = c4st[collapsedev::kNeed - collapsedev::kStatus];
+    }
+    if (refit) b.refitInfo = RtRefitInfo{ refitPath, bvh4 ? (int32_t)b.nLive : 0, (int32_t)changed, stackNeed };
     b.inst = inst;
     const bool reconfigure = status[1] != b.tlasDepth || rebuild::stack_entries(std::max(stackNeed, 1)) != b.stackEntries;
     b.tlasDepth = status[1];
@@ -796,8 +878,9 @@ int scenedev::rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first
         *stats = RtRebuildStats{};
         stats->gpu_ms = ms; stats->wall_ms = ms_between(t0, t4);
         stats->stage_ms = ms_between(t0, t1); stats->build_ms = ms_between(t1, t2); stats->derive_ms = derive; stats->tlas_ms = tlas;
+        if (refit) { float fit = 0; (void)hipEventElapsedTime(&fit, b.rev[0], b.rev[1]); stats->build_ms = fit; }   // (GPU: the staging copies and the refit)
         stats->commit_ms = ms_between(t3, t4);
-        stats->prims = count; stats->blas_built = (int32_t)nR; stats->nodes = (int32_t)nNodes; stats->n_idx = (int32_t)nIdx;
+        stats->prims = count; stats->blas_built = refit ? 0 : (int32_t)nR; stats->nodes = (int32_t)nNodes; stats->n_idx = (int32_t)nIdx;
         stats->max_depth = (int32_t)maxDepth; stats->tlas_nodes = b.nTlas; stats->tlas_depth = status[1]; stats->reconfigured = reconfigure ? 1 : 0;
         stats->spatial_splits = (int32_t)std::min<uint64_t>(spatialSplits, 0x7fffffffu); stats->prims_clipped = (int32_t)std::min<uint64_t>(primsClipped, 0x7fffffffu);
     }

@@ -86,6 +86,13 @@ struct SceneBag {
     std::vector<rebuild::BlasRange> ranges;   // the primitive range of every distinct BLAS, in increasing order
     std::vector<int32_t> instBlas;            // instance -> its range
     bool variantLayout1 = false;              // the holders' extend_variant admits the derived layout 1
+    // What RT_REBUILD_REFIT needs of the live trees, per range (found at upload, reported by the builders at a rebuild), and of the live
+    // collapse of a BVH4 copy that keeps its BVH2: node -> live id and live id -> node (the upload's own arrays or the live set's, never
+    // scratch: a refused call in between must leave them), the live nodes and the stack need as the collapse counted it
+    std::vector<uint32_t> blasRoot, blasInteriors, blasHeight;
+    uint32_t *liveNewId = nullptr, *liveQuadNode = nullptr;
+    uint32_t nLive = 0, c4Need = 0;
+    RtRefitInfo refitInfo{};                  // the last successful RT_REBUILD_REFIT (rt_refit_info)
     // Everything a rebuild changes, twice: a rebuild writes the set that is not live and the commit swaps the pointers; the upload's own
     // arrays stay behind until the copy is freed.  The arrays that scale with the primitives are made once.  Those that scale with the
     // trees (Grown) have capacities of their own: nPrims index slots and 2 * nPrims nodes at first, which bounds every tree of the SAH
@@ -100,11 +107,14 @@ struct SceneBag {
         Grown<RtBVHNode2> nodes; Grown<uint32_t> parent, tickets;                            // nodes
         Grown<RtFloat4> pairs; Grown<uint32_t> leaves, pairNode;                             // nodes / 2 (pairs: 4 per interior node)
         Grown<RtBVHNode4> bvh4; Grown<RtFloat4> quads;                                       // a BVH4 copy: nodes; nodes / 2 + one per BLAS (8 per live node)
+        Grown<uint32_t> newId, quadNode;                                                     // a BVH4 copy: the collapse's tables (nodes; nodes / 2 + one per BLAS)
     } rset[2];
     Grown<uint32_t> dwFlags, dwRanks, dwNewId, dwFrontA, dwFrontB; Grown<char> dwScan;   // the derivation's scratch, grown likewise
-    // the collapse's scratch (a BVH4 copy that keeps its BVH2), grown likewise: frontiers, flags / ranks / kids, newId, quadNode, scan, counters
-    Grown<uint2> c4FrontA, c4FrontB; Grown<uint32_t> c4Flags, c4Ranks, c4Kids, c4NewId, c4QuadNode, c4Ctr; Grown<char> c4Scan;
-    collapsedev::Work c4{};
+    // the collapse's scratch (a BVH4 copy that keeps its BVH2), grown likewise: frontiers, flags / ranks / kids, scan, counters.  The
+    // tables a collapse leaves (newId, quadNode) are not scratch: they belong to the arrays collapsed (the upload's, a set's)
+    Grown<uint2> c4FrontA, c4FrontB; Grown<uint32_t> c4Flags, c4Ranks, c4Kids, c4Ctr; Grown<char> c4Scan;
+    size_t c4Cap = 0;                         // the nodes the scratch was sized for
+    collapsedev::Work c4{};                   // (newId / quadNode / quadCap: filled in by the caller)
     sbvhdev::Pool* spool = nullptr;           // the SBVH builder's device blocks, kept from rebuild to rebuild
     uint64_t rallocs = 0;                     // device allocations by updates and rebuilds of this copy (rt_debug_rebuild_allocations)
     int rnext = 0;                            // the set the next rebuild writes

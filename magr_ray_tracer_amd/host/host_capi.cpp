@@ -5,6 +5,7 @@
 #include <string>
 #include "../../include/rt355.h"
 #include "../../include/rt355_host.h"
+#include "../csrc/collapse_common.h"
 #include "rt_host.h"
 
 using namespace rt355;
@@ -145,6 +146,43 @@ int rth_build_bvh4_levels(const RtBVHNode2* nodes2, int32_t nNodes, int32_t nIdx
                           RtBvh4Stats* stats, RtFloat4* quads, uint32_t* rootEntry, uint32_t* quadNode)
 {
     return build_bvh2([&](std::string& err) { return Bvh4LevelsHost(nodes2, nNodes, nIdx, roots, nRoots, out4, stats, quads, rootEntry, quadNode, err); });
+}
+int rth_bvh4_refit(const RtBVHNode2* refit2, int32_t nNodes, int32_t nIdx, const uint32_t* roots, int32_t nRoots, RtBVHNode4* inout4,
+                   const uint32_t* quadNode, int32_t nLive, int32_t* changedNodes)
+{
+    return build_bvh2([&](std::string& err) { return Bvh4RefitHost(refit2, nNodes, nIdx, roots, nRoots, inout4, quadNode, nLive, changedNodes, err); });
+}
+// rth_bvh4_refit on the scene's own arrays: its BVH4 is the collapse of the BVH2 as it was before rth_refit.  The live nodes of that
+// collapse are numbered as the upload numbers them: breadth-first, BLAS by BLAS in the order in which the instances first name them.
+int rth_refit_bvh4(RthScene* s, int32_t* changedNodes)
+{
+    if (!s || !s->scene.bvh2 || !s->scene.bvh4) { g_herr = "rth_refit_bvh4: a scene with a BVH2 and the BVH4 collapsed from it is required"; return RT_E_INVALID; }
+    try {
+        Scene& sc = s->scene;
+        const std::vector<RtBVHNode2>& n2 = sc.bvh2->bvhNodes;
+        std::vector<RtBVHNode4>& n4 = sc.bvh4->Nodes();
+        if (n4.size() != n2.size() || n2.empty()) { g_herr = "rth_refit_bvh4: the BVH4 is not the collapse of the scene's BVH2"; return RT_E_INVALID; }
+        std::vector<uint32_t> roots, order;
+        std::vector<uint8_t> seen(n2.size(), 0);
+        for (const RtBVHInstance& inst : sc.blasNodes) roots.push_back(inst.bvhIdx);
+        for (const uint32_t root : roots) {
+            if (root >= n4.size()) { g_herr = "rth_refit_bvh4: an instance's bvhIdx is out of range"; return RT_E_INVALID; }
+            if (seen[root]) continue;
+            size_t head = order.size();
+            seen[root] = 1; order.push_back(root);
+            for (; head < order.size(); head++)
+                for (int k = 0; k < 4; k++) if (collapse::is_child(n4[order[head]], k)) {
+                    const uint32_t c = (uint32_t)n4[order[head]].first[k];
+                    if (c >= n4.size() || seen[c]) { g_herr = "rth_refit_bvh4: the BVH4 is malformed (a child out of range or reachable twice)"; return RT_E_INVALID; }
+                    seen[c] = 1; order.push_back(c);
+                }
+        }
+        std::string err;
+        const int rc = Bvh4RefitHost(n2.data(), (int32_t)n2.size(), (int32_t)sc.bvh2->primIdx.size(), roots.data(), (int32_t)roots.size(), n4.data(), order.data(),
+                                     (int32_t)order.size(), changedNodes, err);
+        if (rc != RT_OK) g_herr = err;
+        return rc;
+    } catch (const std::exception& e) { g_herr = e.what(); return RT_E_NOMEM; }
 }
 // BVH4::Convert + Collapse (bvh.cpp:695-787) on a caller-provided BVH2 node array with ONE BLAS rooted at node 0: how the tests feed
 // the reference's own hand-built 13-node tree (bvh.cpp:615-674) through the collapse.

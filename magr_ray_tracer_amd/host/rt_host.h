@@ -135,6 +135,9 @@ int SbvhBuildHost(float alpha, const RtPrimitive* prims, int32_t nPrims, int32_t
 // refused call, which writes nothing.
 int Bvh4LevelsHost(const RtBVHNode2* nodes2, int32_t nNodes, int32_t nIdx, const uint32_t* roots, int32_t nRoots, RtBVHNode4* out4, RtBvh4Stats* stats,
                    RtFloat4* quads, uint32_t* rootEntry, uint32_t* quadNode, std::string& err);
+// rth_bvh4_refit: the collapse of a refit BVH2 under the live ids of the collapse in inout4 (collapse_host.cpp)
+int Bvh4RefitHost(const RtBVHNode2* refit2, int32_t nNodes, int32_t nIdx, const uint32_t* roots, int32_t nRoots, RtBVHNode4* inout4, const uint32_t* quadNode,
+                  int32_t nLive, int32_t* changedNodes, std::string& err);
 
 // In-place updates (refit_host.cpp, the host restatement of rt_update_scene): replace primitives keeping objType / matIdx, then refit
 // every BLAS by the rules of csrc/refit_common.h; err receives why a call is refused (RT_E_* returned, nothing changed).

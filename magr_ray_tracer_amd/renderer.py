@@ -136,8 +136,10 @@ class Device:
         BLAS is built anew over its primitive range with builder "sah" (BVH2::BuildBLAS, alpha 1), "lbvh" (lbvh_options: max_leaf,
         cost_traverse, cost_intersect) or "sbvh_gpu" (BVH2::BuildBLAS with `alpha` in [0, 1], default 0: spatial splits, for scenes
         bound as an SBVH), the TLAS is rebuilt and every derived array is produced on the device.  Use it when refits have degraded
-        the trees (topology-changing motion).  Every context holding the scene sees it.  Returns the stats; a refusal raises RtError
-        (.code) and leaves the scene as it was."""
+        the trees (topology-changing motion).  builder="refit" (RT_REBUILD_REFIT) builds nothing: the bound trees are refit as
+        update_scene refits them, which is also how a BVH4 context bound with from_bvh2=True follows a deformation (refit_info() tells
+        whether its BVH4 records were rewritten in place).  Every context holding the scene sees it.  Returns the stats; a refusal
+        raises RtError (.code) and leaves the scene as it was."""
         args, keep, st = _rebuild_args(prims, first, instances, builder, lbvh_options, alpha)
         rc = self._lib.rt_rebuild_scene(self._h, *args)
         if rc != 0:
@@ -145,6 +147,14 @@ class Device:
             e.code = rc
             raise e
         return _rebuild_dict(st)
+
+    def refit_info(self):
+        """The last successful rebuild_scene(builder="refit") of the bound scene copy (rt_refit_info): path (0 none yet, 1 in place,
+        2 re-collapsed because changed_nodes > 0, 3 re-collapsed because RT355_REFIT_RECOLLAPSE=1 forced it), live_quads,
+        changed_nodes, stack_need."""
+        r = np.zeros((), _lib.RefitInfo)
+        self._chk(self._lib.rt_refit_info(self._h, _lib.ptr(r)))
+        return {n: int(r[n]) for n in r.dtype.names}
 
     def rebuild_allocations(self):
         """Device allocations that updates and rebuilds of the bound scene copy have made so far (rt_debug_rebuild_allocations)."""

@@ -195,6 +195,17 @@ class Scene:
         rebuild the TLAS (and the BVH4) from the refit tree."""
         self._chk(self._lib.rth_refit(self._h))
 
+    def RefitBVH4(self):
+        """After Refit(): bring the scene's BVH4 (the collapse of the BVH2 as it was before the refit) up to the refit BVH2 the way
+        rt_rebuild_scene's RT_REBUILD_REFIT does on the GPU (rth_bvh4_refit): the live records are recomputed, and only if one of
+        them changed a slot is the tree collapsed level by level again.  Returns True when the records were rewritten in place.
+        Either way the BVH4 equals BuildBVH4()'s of the refit BVH2 byte for byte.  Raises BuildError when refused."""
+        changed = C.c_int32(0)
+        rc = self._lib.rth_refit_bvh4(self._h, C.byref(changed))
+        if rc != 0:
+            raise BuildError(rc, self._lib.rth_last_error().decode())
+        return changed.value == 0
+
     def Rebuild(self, builder="sah", alpha=None, **lbvh_options):
         """Discard the BVH2 and build every BLAS again over the primitive range it covers, as rt_rebuild_scene does on the GPU
         (rth_rebuild): builder="sah" is the GPU SAH builder's host restatement (BuildBLAS with alpha 1), "lbvh" the linear builder's
@@ -202,6 +213,8 @@ class Scene:
         default 0: spatial splits; stats() then reports the new trees' spatial_splits / prims_clipped).  Instance transforms stay;
         arrays() / BuildTLAS() then rebuild the TLAS (and the BVH4).  Raises BuildError (.code, an RT_E_* value) and changes nothing
         when refused."""
+        if builder == "refit":
+            raise ValueError("builder='refit' is a device-side name (Device.rebuild_scene): on the host, Scene.Refit() refits the trees")
         which = rebuild_builder(builder, lbvh_options, alpha)
         rc = self._lib.rth_rebuild(self._h, which, _lib.ptr(build_options(alpha=alpha, **lbvh_options)))
         if rc != 0:
@@ -260,13 +273,14 @@ def build_options(max_leaf=None, cost_traverse=None, cost_intersect=None, alpha=
     return o
 
 
-REBUILD_BUILDERS = {"sah": _lib.REBUILD_SAH, "lbvh": _lib.REBUILD_LBVH, "sbvh_gpu": _lib.REBUILD_SBVH}
+REBUILD_BUILDERS = {"sah": _lib.REBUILD_SAH, "lbvh": _lib.REBUILD_LBVH, "sbvh_gpu": _lib.REBUILD_SBVH, "refit": _lib.REBUILD_REFIT}
 
 
 def rebuild_builder(builder, lbvh_options=None, alpha=None):
-    """RT_REBUILD_* of a builder name; the linear builder's options apply to "lbvh" only, alpha to "sbvh_gpu" only."""
+    """RT_REBUILD_* of a builder name; the linear builder's options apply to "lbvh" only, alpha to "sbvh_gpu" only ("refit", which
+    builds nothing, takes neither)."""
     if builder not in REBUILD_BUILDERS:
-        raise ValueError(f"unknown builder {builder!r} (expected 'sah', 'lbvh' or 'sbvh_gpu')")
+        raise ValueError(f"unknown builder {builder!r} (expected 'sah', 'lbvh', 'sbvh_gpu' or 'refit')")
     if builder != "lbvh" and lbvh_options:
         raise ValueError(f"options {sorted(lbvh_options)} apply to builder='lbvh' only")
     if builder != "sbvh_gpu" and alpha is not None:

@@ -1,6 +1,6 @@
 """Cost of an in-place BLAS rebuild (rt_rebuild_scene) against the round trip it removes, on one GPU.
 
-    python tools/rebuild_bench.py [--reps 10] [--frames 20] [--builders sah,lbvh,sbvh] [--host-reps 1] [--accel bvh2|bvh4]
+    python tools/rebuild_bench.py [--reps 10] [--frames 20] [--builders sah,lbvh,sbvh,refit] [--host-reps 1] [--accel bvh2|bvh4]
 
 For sponza-class (every vertex scrambled across the triangles) and config 5 (every vertex jittered), three ways to bring a bound scene
 up to date are timed in one process, alternating within each repetition (min / median / max of --reps after a warm-up):
@@ -28,7 +28,19 @@ same two scenes and deformations, alternating within each repetition:
      (BVH4::Convert / Collapse, sequential), BuildTLAS and rt_upload_scene of everything into a second context, each part timed (the
      first repetition checks that H's thirteen device arrays equal A's);
 and the collapse alone on the rebuilt BVH2 of the last repetition: rt_build_bvh4 (wall with both transfers, and its device_ms)
-against Scene.BuildBVH4.  One JSON line per scene and builder."""
+against Scene.BuildBVH4.  One JSON line per scene and builder.
+
+--builders refit (with either --accel; name it alone or with "sah" / "lbvh", which then only serve as yardsticks): the refit of every
+primitive, rebuild_scene(prims, builder="refit"), on both scenes with every vertex jittered, alternating within each repetition with
+  a  what a BVH4 copy had before: rebuild_scene(prims, builder) with the "lbvh" and "sah" of --builders, on contexts of their own;
+  b  Device.update_scene(prims) of the same records on a BVH2 context (--accel bvh2: the first repetition checks that its eleven
+     device arrays equal the refit's);
+  c  --accel bvh4: the refit itself with RT355_REFIT_RECOLLAPSE=1, the level-by-level collapse forced, on a context of its own (the
+     first repetition checks that its thirteen device arrays equal the in-place ones);
+and how many of the repetitions, each a new jitter of the scene as built and so two jitters away from the frame before, stayed in
+place (refit_info path 1) and how many re-collapsed, with the changed nodes of those; --accel bvh4: then the last records handed over
+again --reps times, which is in place by construction (identical boxes): what the in-place path costs when it applies.  One JSON line
+per scene."""
 import argparse
 import json
 import os
@@ -286,6 +298,100 @@ def bvh4_cases(a, which):
         s.close()
 
 
+def refit_cases(a, which):
+    """--builders refit: the refit against the rebuilds, rt_update_scene and its own forced fallback; how often it stays in place."""
+    bvh4 = a.accel == "bvh4"
+    kw = dict(accel=W.ACCEL_BVH4) if bvh4 else {}
+    arrays = list(W.SCENE_ARRAYS) + ([k for k in W.SCENE_ARRAYS_BVH4 if k != "bvh2Kept"] if bvh4 else [])
+    split_keys = ("stage_ms", "build_ms", "derive_ms", "tlas_ms", "commit_ms")
+
+    def timed(fn):
+        t0 = time.perf_counter()
+        st = fn()
+        return (time.perf_counter() - t0) * 1e3, st
+
+    def forced(dev, p):
+        os.environ["RT355_REFIT_RECOLLAPSE"] = "1"                  # (read per call)
+        try:
+            return dev.rebuild_scene(p, builder="refit")
+        finally:
+            del os.environ["RT355_REFIT_RECOLLAPSE"]
+
+    for name, make in (("sponza_class", lambda: scenes.sponza_class(1.0)), ("config5", lambda: scenes.config5_scene(0.0))):
+        s, view = make()
+        sa = s.arrays()
+        dR, dC = Device(RW, RH, **kw), Device(RW, RH)
+        dR.upload(sa, from_bvh2=True)
+        dC.upload(sa)
+        dF = Device(RW, RH, **kw) if bvh4 else None
+        if dF:
+            dF.upload(sa, from_bvh2=True)
+        others = {b: Device(RW, RH, **kw) for b in which if b in ("sah", "lbvh")}
+        for dv in others.values():
+            dv.upload(sa, from_bvh2=True)
+        for k in range(3):                                            # warm-up: both sets, the staging buffers, the workspaces
+            p = jittered(sa.prims, 100 + k)
+            dR.rebuild_scene(p, builder="refit")
+            dC.update_scene(p)
+            if dF:
+                forced(dF, p)
+            for b, dv in others.items():
+                dv.rebuild_scene(p, builder=b)
+        allocs = dR.rebuild_allocations()
+        R, Rg, F, Fg, U, Ug, paths, changed = [], [], [], [], [], [], [], []
+        O = {b: ([], []) for b in others}
+        split = {k: [] for k in split_keys}
+        for r in range(a.reps):
+            p = jittered(sa.prims, r + 1)
+            w, st = timed(lambda: dR.rebuild_scene(p, builder="refit"))
+            R.append(w)
+            Rg.append(st["gpu_ms"])
+            for k in split:
+                split[k].append(st[k])
+            info = dR.refit_info()
+            paths.append(info["path"])
+            changed.append(info["changed_nodes"])
+            if dF:
+                w, st = timed(lambda: forced(dF, p))
+                F.append(w)
+                Fg.append(st["gpu_ms"])
+                assert dF.refit_info()["path"] == 3
+            w, su = timed(lambda: dC.update_scene(p))
+            U.append(w)
+            Ug.append(su["gpu_ms"])
+            for b, dv in others.items():
+                w, so = timed(lambda: dv.rebuild_scene(p, builder=b))
+                O[b][0].append(w)
+                O[b][1].append(so["gpu_ms"])
+            if r == 0:
+                for k in arrays:
+                    other = dF if bvh4 else dC
+                    assert np.array_equal(dR.scene_array(k), other.scene_array(k)), f"{name}: {k} differs between the refit and its yardstick"
+        S, Sg = [], []                                                # the last records again: identical boxes, in place by construction
+        for r in range(a.reps if bvh4 else 0):
+            w, ss = timed(lambda: dR.rebuild_scene(p, builder="refit"))
+            S.append(w)
+            Sg.append(ss["gpu_ms"])
+            assert dR.refit_info()["path"] == 1
+        assert dR.rebuild_allocations() == allocs, "a refit of a stable scene allocated"
+        mR = statistics.median(R)
+        out = {"scene": name, "accel": a.accel, "builder": "refit", "prims": int(len(sa.prims)), "nodes": st["nodes"], "live_quads": info["live_quads"],
+               "stack_need": info["stack_need"], "refit_wall_ms": mmm(R), "refit_gpu_ms": mmm(Rg),
+               "refit_split_ms": {k: round(statistics.median(v), 3) for k, v in split.items()},
+               "in_place": paths.count(1), "recollapsed": paths.count(2), "changed_nodes_when_recollapsed": [c for c in changed if c],
+               "update_bvh2_wall_ms": mmm(U), "update_bvh2_gpu_ms": mmm(Ug), "refit_over_update": round(mR / statistics.median(U), 3)}
+        if dF:
+            out.update({"forced_wall_ms": mmm(F), "forced_gpu_ms": mmm(Fg), "refit_over_forced": round(mR / statistics.median(F), 3),
+                        "same_records_in_place_wall_ms": mmm(S), "same_records_in_place_gpu_ms": mmm(Sg),
+                        "in_place_over_forced": round(statistics.median(S) / statistics.median(F), 3)})
+        for b, (w, g) in O.items():
+            out.update({f"{b}_wall_ms": mmm(w), f"{b}_gpu_ms": mmm(g), f"refit_over_{b}": round(mR / statistics.median(w), 4)})
+        print(json.dumps(out), flush=True)
+        for dv in [dR, dC] + ([dF] if dF else []) + list(others.values()):
+            dv.close()
+        s.close()
+
+
 def K_view(s):
     """The Scene's BVH4 array as a copy."""
     from magr_ray_tracer_amd.scene import _view
@@ -301,6 +407,8 @@ def main():
     ap.add_argument("--accel", default="bvh2", choices=["bvh2", "bvh4"])
     a = ap.parse_args()
     which = a.builders.split(",")
+    if "refit" in which:
+        return refit_cases(a, which)
     if a.accel == "bvh4":
         return bvh4_cases(a, which)
     cases = {"sponza_class": (lambda: scenes.sponza_class(1.0), scrambled), "config5": (lambda: scenes.config5_scene(0.0), jittered)}
