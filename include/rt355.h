@@ -367,6 +367,62 @@ typedef struct RtRebuildStats {
 } RtRebuildStats;
 int rt_rebuild_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
                      int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats);
+/* ---- in-place resizes (a bound scene changes its shape without leaving the device) ----------------------------------------------------
+ * rt_update_scene and rt_rebuild_scene keep the scene's shape: the primitive count, every primitive's objType and matIdx, the number of
+ * BLAS and of instances, the light list.  rt_resize_scene replaces all of it but the materials and textures, which stay as bound:
+ *   prims   the whole new primitive array, RtPrimitive[nPrims], in host memory or in memory the context's GPU reaches (device memory of
+ *           that GPU, managed or pinned host memory: rt_trace's pointer rule - hipPointerGetAttributes decides, and an allocation the
+ *           runtime knows must not end before the nPrims-th record), so a simulation that writes primitives on the GPU never crosses the
+ *           bus.  The copy runs on the scene copy's own stream, which waits for no other: device work that produces prims must be
+ *           complete, or ordered before the call by the caller (Device.resize_scene waits for torch's current stream).  objType and matIdx are free: objType one of RT_PRIM_*, matIdx in [0, nMats) of the bound materials;
+ *   shape   nRanges BLAS that cover the new array back to back (rangeCount), and nBlas instances (1..256) that name them (instRange;
+ *           every range at least once) under blas[i].invT (blas NULL: identity; bvhIdx is ignored and assigned by the call).
+ * The new primitives are copied into the array set that is not live (host to device or device to device: one path from there on).
+ * k_resize_check, one thread per primitive, range-checks objType and matIdx, writes the light flag (the material's isLight != 0) and the
+ * packed (objType, matIdx) pair - 8 bytes per primitive, the only per-primitive data that returns to the host, which keeps it for the
+ * checks of later updates; a scan ranks the flags and k_light_emit writes the light list by the Scene rule (the lights' indices in
+ * increasing order) and the complete light records.  Then rt_rebuild_scene's own pipeline runs over the new ranges: every BLAS with
+ * RT_REBUILD_SAH, RT_REBUILD_LBVH or RT_REBUILD_SBVH (opts as there; RT_REBUILD_REFIT is RT_E_INVALID: there is no tree to refit), the
+ * collapse of a BVH4 copy that keeps its BVH2, the derived records and TLAS::Build, all on the device, and the same commit by pointer
+ * swap once the holders' streams are idle.  Afterwards every array rt_debug_get_scene_array returns (RT_SCENE_LIGHTS included), sizes
+ * too, is bit for bit that of a fresh rt_upload_scene (a BVH4 copy: rt_upload_scene_bvh2) of the scene made of the new primitives,
+ * the bound materials and textures, that light list, each BLAS built on the host over its range with the same builder and appended BLAS
+ * after BLAS, instance i carrying invT[i] and the root of BLAS instRange[i], and the TLAS of TLAS::Build; rt_kernel_info and
+ * rt_shade_tables of every holder equal the fresh context's (a resize from several instances to one, or back, changes the traversal
+ * kernels).  rt_update_scene, rt_rebuild_scene with all four builders, rt_trace, rt_share_scene and further resizes work on the result.
+ * Accumulators and seeds are not touched.  A holder whose primitive count changed empties its ray, hit and shadow queues on its own
+ * stream before its next launch, to what a new context has: every count, dequeue head and ticket zero, every hit record zero (a queued
+ * primIdx may lie outside the new array; rt_debug_get_rays then reports no rays until a stage has made some; rt_render never spans the
+ * call), and rt_debug_set_rays checks against the new count.  stats as for a rebuild; prims is nPrims.
+ * The arrays of a set that scale with the primitives, the instances and the lights grow like those that scale with the trees: to the
+ * need plus a quarter, the replaced array freed at once, the live set never touched, every allocation counted by
+ * rt_debug_rebuild_allocations; rt_update_scene's staging arrays likewise.  A scene that alternates between two shapes stops allocating
+ * by the third visit to each.
+ * Refusals change nothing (everything is staged; the bound scene, its arrays and its next frame are what they were):
+ *   RT_E_INVALID      before any device work: a null argument or no scene bound; nPrims <= 0; a range count below 1 or counts that do not
+ *                     sum to nPrims; an instRange outside [0, nRanges) or a range no instance names; nBlas outside 1..256; a singular
+ *                     invT; an unknown builder or RT_REBUILD_REFIT; bad opts; a prims pointer that is neither host memory nor reachable
+ *                     from the context's device for nPrims records.  (rt_resize_check runs the checks of the shape without a device.)
+ *                     Found on the device: the first primitive, by lowest index, whose objType or matIdx is out of range;
+ *   RT_E_UNSUPPORTED  what rt_rebuild_scene refuses (a BVH4 copy without its BVH2, a bound scene that cannot be rebuilt in place,
+ *                     whatever the builder refuses, a tree deeper than RT_BVH4_STACK, a TLAS deeper than RT_TLAS_STACK or one that
+ *                     finds no partner, new trees that would change the derived layout), and a bound scene whose BLAS ranges do not
+ *                     tile [0, nPrims) without gaps;
+ *   RT_E_NOMEM        as for rebuilds (a later call takes the allocation up where it stopped).
+ * Deliberately not followed: materials and textures, more than 256 instances, a change of the derived layout, copies without a BVH2. */
+typedef struct RtSceneShape {
+    int32_t nRanges;              /* distinct BLAS, >= 1 */
+    const int32_t* rangeCount;    /* HOST, nRanges entries, each >= 1, sum == nPrims: BLAS k covers primitives
+                                     [rangeCount[0] + .. + rangeCount[k-1], + rangeCount[k]) of the new array */
+    int32_t nBlas;                /* instances, 1..256 */
+    const int32_t* instRange;     /* HOST, nBlas entries in [0, nRanges): the BLAS instance i renders; every range named at least once */
+    const RtBVHInstance* blas;    /* HOST, nBlas records of which only invT is read (NULL: identity); bvhIdx is assigned by the call */
+} RtSceneShape;
+int rt_resize_scene(RtCtx* ctx, const void* prims, int32_t nPrims, const RtSceneShape* shape, int32_t builder, const RtBuildOptions* opts,
+                    RtRebuildStats* stats);
+/* The checks of rt_resize_scene that need neither a device nor a bound scene: nPrims, the shape, the builder and opts.  RT_OK, or
+ * RT_E_INVALID with the message rt_resize_scene would give. */
+int rt_resize_check(int32_t nPrims, const RtSceneShape* shape, int32_t builder, const RtBuildOptions* opts);
 /* The last successful RT_REBUILD_REFIT of the context's scene copy.  path: 0 no such call yet; 1 the records were rewritten in place
  * (a BVH2 context always reports 1, with live_quads 0); 2 re-collapsed because changed_nodes live records changed a slot; 3
  * re-collapsed because RT355_REFIT_RECOLLAPSE=1 forced it.  live_quads: the live BVH4 nodes afterwards; stack_need: the traversal's
@@ -398,6 +454,7 @@ int rt_blas_ranges(const RtBVHNode2* nodes, int32_t nNodes, const uint32_t* prim
 #define RT_SCENE_QUADS        11   /* layout-1 quad records of a BVH4 (empty otherwise)     */
 #define RT_SCENE_ROOT_ENTRY   12   /* layout-1 root entry per instance                      */
 #define RT_SCENE_BVH2_KEPT    13   /* the BVH2 a BVH4 copy keeps (rt_upload_scene_bvh2); 0 bytes when the copy holds none */
+#define RT_SCENE_LIGHTS       14   /* the light list: uint32 indices of the light primitives, increasing   */
 int rt_debug_get_scene_array(RtCtx* ctx, int32_t which, void* out, int64_t capacityBytes, int64_t* bytes);
 
 /* ---- lanes: one accumulation as several interleaved sample streams behind one handle -------------------------------------------
@@ -444,6 +501,8 @@ int rt_group_update_scene(RtGroup* g, const RtPrimitive* prims, int32_t first, i
                           RtUpdateStats* stats);                             /* rt_update_scene for the group's copy (all lanes)        */
 int rt_group_rebuild_scene(RtGroup* g, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
                            int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats);   /* rt_rebuild_scene for the group's copy */
+int rt_group_resize_scene(RtGroup* g, const void* prims, int32_t nPrims, const RtSceneShape* shape, int32_t builder, const RtBuildOptions* opts,
+                          RtRebuildStats* stats);                            /* rt_resize_scene for the group's copy (all lanes)        */
 int rt_group_seed(RtGroup* g, uint64_t firstStream);                         /* a single Renderer: 0 (what rt_group_create leaves);
                                                                               * rank r of a sample split: r*lanes                       */
 int rt_group_reset(RtGroup* g);                                              /* resetKernel on every lane; frames = 0                   */

@@ -115,6 +115,15 @@ int rth_bvh4_refit(const RtBVHNode2* refit2, int32_t nNodes, int32_t nIdx, const
 /* rth_bvh4_refit on the scene's own arrays, after rth_refit: the scene's BVH4 must be the collapse of its BVH2 as it was before. */
 int rth_refit_bvh4(RthScene* s, int32_t* changedNodes);
 int rth_set_instance_transform(RthScene* s, int blas, const float invT[16]); /* scene.cpp:82 (commented out there) */
+/* A further instance of the BLAS that instance `blas` renders: the new record (appended) carries that BLAS's root and invT (NULL: the
+ * identity); its TLAS leaf gets its bounds from the next rth_build_tlas by the rule every instance's does (the root's box, mapped by
+ * inverse(invT) unless invT is the identity).  What the host needs to state a scene with more instances than BLAS (rt_resize_scene's
+ * ground truth).  Returns the new instance's index, or -1: a bad index, a singular invT, 256 instances already. */
+int rth_add_instance(RthScene* s, int blas, const float invT[16]);
+/* The light list of prims[nPrims] under mats[nMats] by the Scene rule, as rt_resize_scene derives it (csrc/resize_common.h): the
+ * indices, in increasing order, of the primitives whose material has isLight != 0.  out needs room for nPrims entries; returns the
+ * count, or RT_E_INVALID for a missing array or the first primitive whose objType / matIdx is out of range (rth_last_error() names it). */
+int rth_light_list(const RtPrimitive* prims, int32_t nPrims, const RtMaterial* mats, int32_t nMats, uint32_t* out);
 
 /* Borrowed views of the arrays (valid until the scene changes). */
 const RtPrimitive*   rth_primitives(RthScene* s, int* n);

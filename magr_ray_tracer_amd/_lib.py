@@ -96,6 +96,11 @@ SCENE_ARRAYS = {"prims": 0, "bvh": 1, "tlas": 2, "instances": 3, "pairs": 4, "tr
                 "tlasPairs": 8, "tlasPairsP": 9, "instRecs": 10}
 # ... and those only a BVH4 copy fills (bvh2Kept: 0 bytes unless the copy was bound with its BVH2, rt_upload_scene_bvh2)
 SCENE_ARRAYS_BVH4 = {"quads": 11, "rootEntry": 12, "bvh2Kept": 13}
+# ... and the light list (uint32 primitive indices), which rt_resize_scene derives on the device
+SCENE_ARRAYS_RESIZE = {"lights": 14}
+SceneShape = np.dtype([("nRanges", "<i4"), ("_pad0", "<i4"), ("rangeCount", "<u8"), ("nBlas", "<i4"), ("_pad1", "<i4"), ("instRange", "<u8"),
+                       ("blas", "<u8")])   # RtSceneShape
+assert SceneShape.itemsize == 40
 UpdateStats = np.dtype([("gpu_ms", "<f8"), ("prims", "<i4"), ("nodes", "<i4"), ("tlas_nodes", "<i4"), ("tlas_depth", "<i4"),
                         ("reconfigured", "<i4"), ("reserved", "<i4", 3)])
 assert UpdateStats.itemsize == 40
@@ -120,7 +125,7 @@ DEVICE_SYMBOLS = [
     "rt_build_bvh4", "rt_upload_scene_bvh2", "rt_group_upload_scene_bvh2",
     "rt_group_create", "rt_group_destroy", "rt_group_lanes", "rt_group_concurrency", "rt_group_stream_class", "rt_group_class_concurrency", "rt_group_lane", "rt_group_frames", "rt_group_upload_scene", "rt_group_share_scene",
     "rt_group_seed", "rt_group_reset", "rt_group_render", "rt_group_synchronize", "rt_group_sum", "rt_group_read_accum", "rt_group_focus",
-    "rt_group_postproc", "rt_trace", "rt_trace_window"]
+    "rt_group_postproc", "rt_trace", "rt_trace_window", "rt_resize_scene", "rt_group_resize_scene", "rt_resize_check"]
 HOST_SYMBOLS = [
     "rth_last_error", "rth_scene_create", "rth_scene_destroy", "rth_add_material", "rth_add_texture", "rth_load_texture", "rth_add_sphere",
     "rth_add_plane", "rth_add_triangle", "rth_add_quad", "rth_add_triangles", "rth_build_blas", "rth_build_bvh4",
@@ -131,7 +136,7 @@ HOST_SYMBOLS = [
     "rth_set_build_threads", "rth_renderer_save_frame", "rth_renderer_camera_move", "rth_renderer_camera_mouse", "rth_renderer_camera_zoom", "rth_renderer_frames", "rth_renderer_set_lanes", "rth_renderer_set_builtins", "rth_renderer_builtins",
     "rth_build_blas_lbvh", "rth_build_bvh2_lbvh", "rth_lbvh_stats", "rth_set_primitives", "rth_refit",
     "rth_build_blas_sah_gpu", "rth_build_bvh2_sah", "rth_build_blas_sbvh_gpu", "rth_build_bvh2_sbvh", "rth_rebuild", "rth_blas_ranges",
-    "rth_build_bvh4_gpu", "rth_build_bvh4_levels", "rth_bvh4_refit", "rth_refit_bvh4"]
+    "rth_build_bvh4_gpu", "rth_build_bvh4_levels", "rth_bvh4_refit", "rth_refit_bvh4", "rth_add_instance", "rth_light_list"]
 
 _dev = None
 _host = None
@@ -235,6 +240,9 @@ def _bind_device(lib):
         lib.rt_rebuild_scene.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp, vp]
         lib.rt_group_rebuild_scene.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp, vp]
         lib.rt_debug_rebuild_allocations.argtypes = [vp, vp]
+        lib.rt_resize_scene.argtypes = [vp, vp, i32, vp, i32, vp, vp]
+        lib.rt_group_resize_scene.argtypes = [vp, vp, i32, vp, i32, vp, vp]
+        lib.rt_resize_check.argtypes = [i32, vp, i32, vp]
         lib.rt_refit_info.argtypes = [vp, vp]
         lib.rt_blas_ranges.argtypes = [vp, i32, vp, i32, i32, vp, i32, vp, vp]
         lib.rt_group_create.argtypes = [vp, i32, C.POINTER(vp)]
@@ -302,6 +310,8 @@ def host_lib():
         lib.rth_build_tlas.argtypes = [vp]
         lib.rth_bvh4_from_nodes.argtypes = [vp, i32, vp]
         lib.rth_set_instance_transform.argtypes = [vp, i32, fp]
+        lib.rth_add_instance.argtypes = [vp, i32, fp]
+        lib.rth_light_list.argtypes = [vp, C.c_int32, vp, C.c_int32, vp]
         for n in ("rth_primitives", "rth_materials", "rth_textures", "rth_lights", "rth_bvh2_nodes", "rth_bvh4_nodes",
                   "rth_prim_idx", "rth_tlas_nodes", "rth_blas_nodes"):
             getattr(lib, n).argtypes = [vp, C.POINTER(i32)]

@@ -324,6 +324,12 @@ extern "C" int rt_group_rebuild_scene(RtGroup* g, const RtPrimitive* prims, int3
     if (!g) return fail(RT_E_INVALID, "rt_group_rebuild_scene: null group");
     return rt_rebuild_scene(rt_group_lane(g, 0), prims, first, count, blas, nBlas, builder, opts, stats);   // every lane holds lane 0's copy
 }
+extern "C" int rt_group_resize_scene(RtGroup* g, const void* prims, int32_t nPrims, const RtSceneShape* shape, int32_t builder, const RtBuildOptions* opts,
+                                     RtRebuildStats* stats)
+{
+    if (!g) return fail(RT_E_INVALID, "rt_group_resize_scene: null group");
+    return rt_resize_scene(rt_group_lane(g, 0), prims, nPrims, shape, builder, opts, stats);   // every lane holds lane 0's copy
+}
 
 // Lane m renders sample stream `firstStream + m`: its seeds are outputs (firstStream + m) * W*H + firstPixel + i + 1 of the reference's
 // host xorshift32 stream (renderer.cpp:195-196).  A single Renderer has firstStream 0; rank r of a sample-partitioned job r * lanes.

@@ -12,11 +12,16 @@
 //   k_rb_pairs      one thread per pair id: the pair record (refit::pair_boxes + rebuild::pair_entries, what rebuild::pair_record packs)
 //   k_rb_leaf_flag / k_rb_leaf_list   the leaves (refit topology) in node order, by a scan; the largest leaf (status)
 //   k_rb_roots      one thread per instance: the packed entry of its BLAS root
+// rt_resize_scene adds, over the new primitive array (rules: resize_common.h):
+//   k_resize_check  one thread per primitive: objType / matIdx in range (the lowest refused index through atomicMin), the packed pair the
+//                   host keeps as its shadow, the light flag; a scan ranks the flags
+//   k_light_emit    one thread per primitive: a light writes its index and its complete light record at its rank
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include "../../include/rt355.h"
 #include "rebuild_common.h"
 #include "rebuild_dev.h"
+#include "resize_common.h"
 
 namespace rebuilddev {
 
@@ -161,6 +166,47 @@ hipError_t finish(hipStream_t s, const Work& w, const RtBVHNode2* nodes, uint32_
         if (nPairs) hipLaunchKernelGGL(k_rb_pairs, grid(nPairs), dim3(kBlock), 0, s, nodes, pairNode, w.newId, nPairs, pairs);
         hipLaunchKernelGGL(k_rb_roots, grid(nInst), dim3(kBlock), 0, s, nodes, inst, nInst, w.newId, rootEntry);
     }
+    return hipGetLastError();
+}
+
+// ---- rt_resize_scene: the new primitives' checks, the light list and the light records (rules: resize_common.h) -------------------------
+__global__ void __launch_bounds__(kBlock) k_resize_check(const RtPrimitive* prims, uint32_t nPrims, const RtMaterial* mats, int32_t nMats, int2* packed,
+                                                         uint32_t* flags, uint32_t* bad)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= nPrims) return;
+    const int32_t type = prims[i].objType, mat = prims[i].matIdx;
+    const bool ok = resize::prim_ok(type, mat, nMats);
+    packed[i] = make_int2(type, mat);
+    flags[i] = ok ? resize::light_flag(mats, mat) : 0u;   // (a refused record's material is never read)
+    if (!ok) atomicMin(bad, i);   // a value, not a position
+}
+__global__ void __launch_bounds__(kBlock) k_light_emit(const RtPrimitive* prims, uint32_t nPrims, const RtMaterial* mats, const uint32_t* flags,
+                                                       const uint32_t* ranks, uint32_t nLights, uint32_t* lights, RtFloat4* lightRecs)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= nPrims || !flags[i]) return;
+    const uint32_t r = ranks[i];
+    if (r >= nLights) return;   // (the host sized both arrays from this scan: never taken)
+    lights[r] = i;
+    resize::light_record(prims[i], mats, lightRecs + (size_t)r * 8);   // (straight into the record: no private copy of 128 bytes)
+}
+
+hipError_t resize_check(hipStream_t s, const Work& w, const RtPrimitive* prims, uint32_t nPrims, const RtMaterial* mats, int32_t nMats, int2* packed,
+                        uint32_t* bad)
+{
+    hipError_t e = hipMemsetAsync(bad, 0xff, sizeof(uint32_t), s);   // resize::kNoBad
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_resize_check, grid(nPrims), dim3(kBlock), 0, s, prims, nPrims, mats, nMats, packed, w.flags, bad);
+    size_t scanBytes = w.scanBytes;
+    e = hipcub::DeviceScan::ExclusiveSum(w.scan, scanBytes, w.flags, w.ranks, (int)nPrims, s);
+    return e != hipSuccess ? e : hipGetLastError();
+}
+hipError_t light_emit(hipStream_t s, const Work& w, const RtPrimitive* prims, uint32_t nPrims, const RtMaterial* mats, uint32_t nLights, uint32_t* lights,
+                      RtFloat4* lightRecs)
+{
+    if (nLights == 0) return hipMemsetAsync(lightRecs, 0, sizeof(RtFloat4) * 8, s);   // one zero record, as at upload
+    hipLaunchKernelGGL(k_light_emit, grid(nPrims), dim3(kBlock), 0, s, prims, nPrims, mats, w.flags, w.ranks, nLights, lights, lightRecs);
     return hipGetLastError();
 }
 

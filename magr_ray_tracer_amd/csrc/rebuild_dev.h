@@ -26,4 +26,15 @@ hipError_t number_blas(hipStream_t s, const Work& w, const RtBVHNode2* nodes, ui
 hipError_t finish(hipStream_t s, const Work& w, const RtBVHNode2* nodes, uint32_t nNodes, uint32_t nPairs, uint32_t nLeaves, const RtBVHInstance* inst,
                   uint32_t nInst, const uint32_t* pairNode, RtFloat4* pairs, uint32_t* rootEntry, uint32_t* leaves);
 
+// rt_resize_scene (rules: resize_common.h), over the nPrims new primitives already copied into a set that is not live:
+// resize_check: k_resize_check writes per primitive the packed (objType, matIdx) pair the host keeps as its shadow and the light flag
+//   (w.flags), puts the lowest index whose objType / matIdx is out of range into *bad (atomicMin: a value, never a position; kNoBad when
+//   none), and the flags are ranked by an exclusive scan (w.ranks); w.flags / w.ranks must hold nPrims words
+// light_emit: k_light_emit scatters lights[rank] = i and writes the complete 8-row light record at that rank; positions come from the
+//   scan alone
+hipError_t resize_check(hipStream_t s, const Work& w, const RtPrimitive* prims, uint32_t nPrims, const RtMaterial* mats, int32_t nMats, int2* packed,
+                        uint32_t* bad);
+hipError_t light_emit(hipStream_t s, const Work& w, const RtPrimitive* prims, uint32_t nPrims, const RtMaterial* mats, uint32_t nLights, uint32_t* lights,
+                      RtFloat4* lightRecs);
+
 } // namespace rebuilddev

@@ -630,10 +630,26 @@ static int configure_traversal(RtCtx* ctx)
 // A context takes over the facts of the copy it holds - the arrays, the layout, the stack sizes - and derives its traversal
 // configuration from them: after an upload, on sharing, and before the first launch after an update or a rebuild (sync_scene_config).
 // Nothing else assigns them.
+static void frame_state_reset(RtCtx* ctx);
 static int adopt_scene(RtCtx* ctx)
 {
     const SceneBag& b = *ctx->scene;
     const SceneArrays& a = b.sc;
+    // A resize changed the primitive count under a holder: its hit queue may name primitives the new array lacks, and k_shade and
+    // k_export_rays index the primitives by it.  So the queues are emptied on the holder's stream before its next launch, to what a
+    // new context has: every ray and shadow count, dequeue head and ticket zero and every hit record zero (primitive 0, which every
+    // scene has).  rt_stage_begin_frame's own state would not do: it sets the count of bounce 0 to the band's pixels, which hands the
+    // old hit records to rt_debug_get_rays.  (A frame of rt_render never spans the resize: the commit waited for this stream.)
+    if (ctx->sceneLoaded && ctx->sc.nPrims != a.nPrims) {
+        const DevQueues& q = ctx->q;
+        HIPCHK(hipMemsetAsync(q.nRays, 0, sizeof(int32_t) * (RT_MAX_BOUNCES + 2), ctx->stream));
+        HIPCHK(hipMemsetAsync(q.nShadow, 0, sizeof(int32_t) * (RT_MAX_BOUNCES + 2), ctx->stream));
+        HIPCHK(hipMemsetAsync(q.cursor, 0, sizeof(int32_t) * kCursorWords, ctx->stream));
+        HIPCHK(hipMemsetAsync(q.shadeTicket, 0, sizeof(int32_t) * (size_t)(RT_MAX_BOUNCES + 1) * kTicketClasses * kTicketStride, ctx->stream));
+        HIPCHK(hipMemsetAsync(q.hit, 0, sizeof(float4) * (size_t)ctx->nPix, ctx->stream));
+        ctx->queued = true;
+        frame_state_reset(ctx);
+    }
     auto f4 = [](const RtFloat4* p) { return (const float4*)p; };
     ctx->sc = DevScene{ a.prims, a.mats, f4(a.tex), a.lights, a.bvh2, a.bvh4, a.primIdx, a.tlas, a.blas, f4(a.pairs), f4(a.triRecs), a.rootEntry, f4(a.shadeRecs),
                         f4(a.tlasPairs), f4(a.instRecs), a.tlasRoot, f4(a.tlasPairsP), a.tlasRootP, f4(a.lightRecs), f4(a.quads), a.nLights, a.nPrims, a.nBlas, a.nTex, a.nMats };
@@ -741,6 +757,21 @@ extern "C" int rt_rebuild_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t fi
         return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: a BVH4 copy bound through rt_upload_scene has lost its BVH2 and cannot rebuild in place "
                     "(bind the BVH2 with rt_upload_scene_bvh2, or build on the host and upload)");
     return rebuild_scene(*ctx->scene, prims, first, count, blas, nBlas, builder, opts, stats);
+}
+static int device_pointer(const RtCtx* ctx, const char* who, const char* name, const void* p, int64_t bytes, int align, bool hostAllowed);   // (below, with rt_trace)
+extern "C" int rt_resize_scene(RtCtx* ctx, const void* prims, int32_t nPrims, const RtSceneShape* shape, int32_t builder, const RtBuildOptions* opts,
+                               RtRebuildStats* stats)
+{
+    if (!ctx || !prims || !shape) return fail(RT_E_INVALID, "rt_resize_scene: null argument (context, prims and shape are required)");
+    if (!ctx->sceneLoaded || !ctx->scene) return fail(RT_E_INVALID, "rt_resize_scene: no scene uploaded");
+    if (nPrims <= 0) return fail(RT_E_INVALID, "rt_resize_scene: nPrims must be positive (%d given)", nPrims);
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    // rt_trace's pointer rule, with host memory allowed: the records are copied, not followed by a kernel
+    if (const int rc = device_pointer(ctx, "rt_resize_scene", "prims", prims, (int64_t)sizeof(RtPrimitive) * nPrims, 4, true)) return rc;
+    if (ctx->cfg.accel != RT_ACCEL_BVH2 && !ctx->scene->keepsBvh2)
+        return fail(RT_E_UNSUPPORTED, "rt_resize_scene: a BVH4 copy bound through rt_upload_scene has lost its BVH2 and cannot be rebuilt in place "
+                    "(bind the BVH2 with rt_upload_scene_bvh2, or build on the host and upload)");
+    return resize_scene(*ctx->scene, prims, nPrims, shape, builder, opts, stats);
 }
 extern "C" int rt_refit_info(RtCtx* ctx, RtRefitInfo* out)
 {
@@ -949,26 +980,29 @@ extern "C" int64_t rt_trace_window(RtCtx* ctx)
     return trace_window(ctx);
 }
 // A pointer the kernels will follow for `bytes` bytes: it must be memory the context's device can reach (a host pointer passed by
-// mistake is an error message here, not a fault there), aligned for the accesses, and - where the runtime knows the allocation - inside it
-static int trace_pointer(const RtCtx* ctx, const char* name, const void* p, int64_t bytes, int align)
+// mistake is an error message here, not a fault there), aligned for the accesses, and - where the runtime knows the allocation - inside it.
+// hostAllowed (rt_resize_scene, which copies from it): memory the runtime does not know, or knows as host memory, passes as well.
+static int device_pointer(const RtCtx* ctx, const char* who, const char* name, const void* p, int64_t bytes, int align, bool hostAllowed)
 {
-    if ((uintptr_t)p % (uintptr_t)align) return fail(RT_E_INVALID, "rt_trace: %s (%p) is not aligned to %d bytes", name, p, align);
+    if ((uintptr_t)p % (uintptr_t)align) return fail(RT_E_INVALID, "%s: %s (%p) is not aligned to %d bytes", who, name, p, align);
     hipPointerAttribute_t a{};
     const hipError_t e = hipPointerGetAttributes(&a, p);
     if (e != hipSuccess) (void)hipGetLastError();
     const bool device = e == hipSuccess && a.type == hipMemoryTypeDevice && a.device == ctx->cfg.device;
     const bool shared = e == hipSuccess && (a.type == hipMemoryTypeManaged || (a.type == hipMemoryTypeHost && a.devicePointer == p));
-    if (!device && !shared)
-        return fail(RT_E_INVALID, "rt_trace: %s (%p) is not memory accessible from device %d (a host pointer? memory of another GPU?)", name, p, ctx->cfg.device);
+    const bool host = e != hipSuccess || a.type == hipMemoryTypeUnregistered || a.type == hipMemoryTypeHost;
+    if (!device && !shared && !(hostAllowed && host))
+        return fail(RT_E_INVALID, "%s: %s (%p) is not memory accessible from device %d (a host pointer? memory of another GPU?)", who, name, p, ctx->cfg.device);
     if (device) {
         hipDeviceptr_t base = nullptr; size_t size = 0;
         if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) (void)hipGetLastError();   // (not every allocator's memory has one)
         else if ((const char*)p + bytes > (const char*)base + size)
-            return fail(RT_E_INVALID, "rt_trace: %s needs %lld bytes from %p, its allocation ends %lld bytes earlier", name, (long long)bytes, p,
+            return fail(RT_E_INVALID, "%s: %s needs %lld bytes from %p, its allocation ends %lld bytes earlier", who, name, (long long)bytes, p,
                         (long long)(((const char*)p + bytes) - ((const char*)base + size)));
     }
     return RT_OK;
 }
+static int trace_pointer(const RtCtx* ctx, const char* name, const void* p, int64_t bytes, int align) { return device_pointer(ctx, "rt_trace", name, p, bytes, align, false); }
 static int trace_view(RtCtx* ctx, size_t ownRays)
 {
     RtCtx::TraceView& v = ctx->tv;
@@ -1228,6 +1262,9 @@ extern "C" int rt_debug_set_rays(RtCtx* ctx, int32_t bounce, const RtRay* in, in
 {
     if (!ctx || !in || n < 0 || n > ctx->nPix || bounce < 0 || bounce > ctx->cfg.max_bounces) return fail(RT_E_INVALID, "rt_debug_set_rays: bad argument");
     // the kernels index the accumulator by pixelIdx and the primitives by primIdx: refuse what lies outside before anything is written
+    // (a resize may have changed the copy since this holder's last launch: it is taken over first - its queues are emptied then, not
+    // after the injection - and the count is the new one)
+    if (ctx->sceneLoaded) if (const int rc = sync_scene_config(ctx)) return rc;
     const int32_t nPrims = ctx->sceneLoaded ? ctx->sc.nPrims : 0;
     for (int32_t i = 0; i < n; i++) {
         if (in[i].pixelIdx < ctx->firstPixel || in[i].pixelIdx >= ctx->firstPixel + ctx->nPix)
@@ -1251,6 +1288,7 @@ extern "C" int rt_debug_set_rays(RtCtx* ctx, int32_t bounce, const RtRay* in, in
 extern "C" int rt_debug_get_shadow(RtCtx* ctx, int32_t b0, int32_t b1, RtShadowRecord* out, int32_t capacity, int32_t* n)
 {
     if (!ctx || !n || b0 < 0 || b1 < b0 || b1 >= ctx->cfg.max_bounces) return fail(RT_E_INVALID, "rt_debug_get_shadow: bad argument");
+    if (ctx->sceneLoaded) if (const int rc = sync_scene_config(ctx)) return rc;   // (a holder of a resized copy: its queues are emptied first)
     HIPCHK(hipSetDevice(ctx->cfg.device));
     int32_t lo = 0, hi = 0, rc;
     if ((rc = read_count(ctx, ctx->q.nShadow + b0, &lo))) return rc;

@@ -6,6 +6,7 @@
 #include <cstring>
 #include <string>
 #include "scene_dev.h"
+#include "resize_common.h"
 
 using namespace scenedev;
 
@@ -399,16 +400,24 @@ template <class T> static int rebuild_grow(SceneBag& b, SceneBag::Grown<T>& a, s
     count = std::max<size_t>(count, 1);
     void* q = nullptr;
     if (hipMalloc(&q, count * sizeof(T)) != hipSuccess)
-        return nomem ? fail(RT_E_NOMEM, nomem, count) : fail(RT_E_NOMEM, "rt_rebuild_scene: %zu bytes of device memory for %s", count * sizeof(T), what);
+        return nomem ? fail(RT_E_NOMEM, nomem, count) : fail(RT_E_NOMEM, "in-place scene change: %zu bytes of device memory for %s", count * sizeof(T), what);
     b.rallocs++;
     if (a.p) {
         hipError_t e = keep ? hipMemcpyAsync(q, a.p, keep * sizeof(T), hipMemcpyDeviceToDevice, b.stream) : hipSuccess;
         if (e == hipSuccess) e = hipStreamSynchronize(b.stream);
-        if (e != hipSuccess) { (void)hipFree(q); return fail(RT_E_DEVICE, "rt_rebuild_scene: moving %s failed: %s", what, hipGetErrorString(e)); }
+        if (e != hipSuccess) { (void)hipFree(q); return fail(RT_E_DEVICE, "in-place scene change: moving %s failed: %s", what, hipGetErrorString(e)); }
         (void)hipFree(a.p);
     }
     a.p = (T*)q; a.cap = count;
     return RT_OK;
+}
+// An array that scales with the primitives, the instances or the lights (a RebuildSet's, the update's staging): made to fit exactly, and
+// once a resize outgrows it replaced by one of the need plus a kRebuildHeadroomDiv-th.  Nothing in it is kept.
+template <class T> static int rebuild_fit(SceneBag& b, SceneBag::Grown<T>& a, size_t need, const char* what)
+{
+    need = std::max<size_t>(need, 1);
+    if (a.p && need <= a.cap) return RT_OK;
+    return rebuild_grow(b, a, a.p ? need + need / kRebuildHeadroomDiv : need, 0, what);
 }
 
 // ---- the BVH2 -> BVH4 collapse of a copy that keeps its BVH2 (kernels: collapse.hip, rules: collapse_common.h) --------------------------
@@ -508,19 +517,18 @@ int scenedev::update_scene(SceneBag& b, const RtPrimitive* prims, int32_t first,
     if (b.refitRefusal) return fail(RT_E_UNSUPPORTED, "rt_update_scene: %s", b.refitRefusal);
     if (const int rc = check_change(who, b, prims, first, count, blas, nBlas, ": topology must not change")) return rc;
     HIPCHK(hipSetDevice(b.device));
-    // ---- staging buffers (first update)
-    if (!b.sPrims) {
-        int rc = dalloc(b.allocs, &b.sPrims, (size_t)b.nPrims);
-        if (rc == RT_OK) rc = dalloc(b.allocs, &b.sInst, (size_t)b.nBlas);
-        if (rc == RT_OK) rc = dalloc(b.allocs, &b.sTlas, (size_t)b.nTlas);
-        if (rc == RT_OK) rc = dalloc(b.allocs, &b.sTp, (size_t)b.nTlas * 4);
-        if (rc == RT_OK) rc = dalloc(b.allocs, &b.sTpP, (size_t)b.nTlas * 4);
-        if (rc == RT_OK) rc = dalloc(b.allocs, &b.sIr, (size_t)b.nBlas * 4);
-        if (rc == RT_OK) rc = dalloc(b.allocs, &b.sStatus, 2);
-        if (rc != RT_OK) { b.sPrims = nullptr; return rc; }
-        b.rallocs += 7;
-        if (!b.stream) HIPCHK(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));   // (a rebuild may have made it already)
-        for (hipEvent_t& e : b.ev) if (!e) HIPCHK(hipEventCreate(&e));
+    // ---- staging buffers (the first update makes them; one after a resize that outgrew them replaces them)
+    if (!b.stream) HIPCHK(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));   // (a rebuild may have made it already)
+    for (hipEvent_t& e : b.ev) if (!e) HIPCHK(hipEventCreate(&e));
+    {
+        int rc = rebuild_fit(b, b.sPrims, (size_t)b.nPrims, "the staging primitives");
+        if (rc == RT_OK) rc = rebuild_fit(b, b.sInst, (size_t)b.nBlas, "the staging instances");
+        if (rc == RT_OK) rc = rebuild_fit(b, b.sTlas, (size_t)b.nTlas, "the staging TLAS");
+        if (rc == RT_OK) rc = rebuild_fit(b, b.sTp, (size_t)b.nTlas * 4, "the staging TLAS records");
+        if (rc == RT_OK) rc = rebuild_fit(b, b.sTpP, (size_t)b.nTlas * 4, "the staging TLAS records");
+        if (rc == RT_OK) rc = rebuild_fit(b, b.sIr, (size_t)b.nBlas * 4, "the staging instance records");
+        if (rc == RT_OK && !b.sStatus) { rc = dalloc(b.allocs, &b.sStatus, 2); if (rc == RT_OK) b.rallocs++; }
+        if (rc != RT_OK) return rc;
     }
     if (!b.sNodes.p || (size_t)b.nNodes > b.sNodes.cap) {
         // the staging nodes: at first room for every tree the SAH and the linear builder can bind later; an SBVH rebuild may bind more
@@ -532,13 +540,13 @@ int scenedev::update_scene(SceneBag& b, const RtPrimitive* prims, int32_t first,
     hipStream_t s = b.stream;
     // ---- stage: the new primitives, the refit tree and the rebuilt TLAS in scratch
     HIPCHK(hipEventRecord(b.ev[0], s));
-    HIPCHK(hipMemcpyAsync(b.sPrims, sc.prims, sizeof(RtPrimitive) * (size_t)b.nPrims, hipMemcpyDeviceToDevice, s));
-    if (count) HIPCHK(hipMemcpyAsync(b.sPrims + first, prims, sizeof(RtPrimitive) * (size_t)count, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(b.sPrims.p, sc.prims, sizeof(RtPrimitive) * (size_t)b.nPrims, hipMemcpyDeviceToDevice, s));
+    if (count) HIPCHK(hipMemcpyAsync(b.sPrims.p + first, prims, sizeof(RtPrimitive) * (size_t)count, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(b.sNodes.p, sc.bvh2, sizeof(RtBVHNode2) * (size_t)b.nNodes, hipMemcpyDeviceToDevice, s));
-    if (blas) HIPCHK(hipMemcpyAsync(b.sInst, blas, sizeof(RtBVHInstance) * (size_t)b.nBlas, hipMemcpyHostToDevice, s));
-    else HIPCHK(hipMemcpyAsync(b.sInst, sc.blas, sizeof(RtBVHInstance) * (size_t)b.nBlas, hipMemcpyDeviceToDevice, s));
-    HIPCHK(refitdev::launch_refit(s, b.sNodes.p, (uint32_t)b.nNodes, b.sPrims, sc.primIdx, b.dLeaves, b.nLeaves, b.dParent, b.dTickets));
-    HIPCHK(refitdev::launch_tlas(s, b.sNodes.p, b.sInst, b.nBlas, b.layout == 1 ? sc.rootEntry : nullptr, b.sTlas, b.sTp, b.sTpP, b.sIr, b.sStatus));
+    if (blas) HIPCHK(hipMemcpyAsync(b.sInst.p, blas, sizeof(RtBVHInstance) * (size_t)b.nBlas, hipMemcpyHostToDevice, s));
+    else HIPCHK(hipMemcpyAsync(b.sInst.p, sc.blas, sizeof(RtBVHInstance) * (size_t)b.nBlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(refitdev::launch_refit(s, b.sNodes.p, (uint32_t)b.nNodes, b.sPrims.p, sc.primIdx, b.dLeaves, b.nLeaves, b.dParent, b.dTickets));
+    HIPCHK(refitdev::launch_tlas(s, b.sNodes.p, b.sInst.p, b.nBlas, b.layout == 1 ? sc.rootEntry : nullptr, b.sTlas.p, b.sTp.p, b.sTpP.p, b.sIr.p, b.sStatus));
     int32_t status[2] = { 0, 0 };
     HIPCHK(hipEventRecord(b.ev[1], s));
     HIPCHK(hipMemcpyAsync(status, b.sStatus, sizeof status, hipMemcpyDeviceToHost, s));
@@ -547,13 +555,13 @@ int scenedev::update_scene(SceneBag& b, const RtPrimitive* prims, int32_t first,
     // ---- commit: no kernel of a context holding this copy may read the arrays while they are rewritten
     if (const int rc = b.wait_holders()) return rc;
     HIPCHK(hipEventRecord(b.ev[2], s));
-    if (count) HIPCHK(hipMemcpyAsync(sc.prims + first, b.sPrims + first, sizeof(RtPrimitive) * (size_t)count, hipMemcpyDeviceToDevice, s));
+    if (count) HIPCHK(hipMemcpyAsync(sc.prims + first, b.sPrims.p + first, sizeof(RtPrimitive) * (size_t)count, hipMemcpyDeviceToDevice, s));
     HIPCHK(hipMemcpyAsync(sc.bvh2, b.sNodes.p, sizeof(RtBVHNode2) * (size_t)b.nNodes, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(sc.blas, b.sInst, sizeof(RtBVHInstance) * (size_t)b.nBlas, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(sc.tlas, b.sTlas, sizeof(RtTLASNode) * (size_t)b.nTlas, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(sc.tlasPairs, b.sTp, sizeof(RtFloat4) * 4 * (size_t)b.nTlas, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(sc.tlasPairsP, b.sTpP, sizeof(RtFloat4) * 4 * (size_t)b.nTlas, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(sc.instRecs, b.sIr, sizeof(RtFloat4) * 4 * (size_t)b.nBlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(sc.blas, b.sInst.p, sizeof(RtBVHInstance) * (size_t)b.nBlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(sc.tlas, b.sTlas.p, sizeof(RtTLASNode) * (size_t)b.nTlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(sc.tlasPairs, b.sTp.p, sizeof(RtFloat4) * 4 * (size_t)b.nTlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(sc.tlasPairsP, b.sTpP.p, sizeof(RtFloat4) * 4 * (size_t)b.nTlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(sc.instRecs, b.sIr.p, sizeof(RtFloat4) * 4 * (size_t)b.nBlas, hipMemcpyDeviceToDevice, s));
     HIPCHK(refitdev::launch_records(s, sc.prims, sc.bvh2, sc.primIdx, (uint32_t)b.nIdx, sc.lights, (uint32_t)b.nLights, (uint32_t)std::max(first, 0),
                                     (uint32_t)count, b.dPairNode, (uint32_t)b.nPairs, b.layout == 1 ? sc.pairs : nullptr,
                                     b.layout == 1 ? sc.triRecs : nullptr, sc.shadeRecs, sc.lightRecs));
@@ -575,8 +583,9 @@ int scenedev::update_scene(SceneBag& b, const RtPrimitive* prims, int32_t first,
 
 // ---- in-place rebuilds (rt_rebuild_scene; builders: sah.hip / lbvh.hip / sbvh.hip, derivation: rebuild.hip, rules: rebuild_common.h) ----
 // Room in the set `t` (not live) for idxNeed index slots and nodeNeed nodes, keeping the keepIdx slots and keepNodes records emitted so
-// far.  An array that is too small goes to the need plus kRebuildHeadroomDiv-th of it; one that NOMEM stopped is taken up by a later call.
-static int rebuild_reserve(SceneBag& b, SceneBag::RebuildSet& t, size_t idxNeed, size_t nodeNeed, size_t keepIdx, size_t keepNodes)
+// far; nR: the BLAS the trees belong to.  An array that is too small goes to the need plus kRebuildHeadroomDiv-th of it; one that NOMEM
+// stopped is taken up by a later call.
+static int rebuild_reserve(SceneBag& b, SceneBag::RebuildSet& t, size_t nR, size_t idxNeed, size_t nodeNeed, size_t keepIdx, size_t keepNodes)
 {
     const bool have = t.nodes.p != nullptr;   // (the first allocation is exact: the initial capacity)
     const size_t idxCap = idxNeed <= t.primIdx.cap ? t.primIdx.cap : idxNeed + (have ? idxNeed / kRebuildHeadroomDiv : 0);
@@ -592,9 +601,9 @@ static int rebuild_reserve(SceneBag& b, SceneBag::RebuildSet& t, size_t idxNeed,
     if (rc == RT_OK) rc = rebuild_grow(b, t.pairNode, nodeCap / 2, 0, "pair nodes");
     if (b.accel == RT_ACCEL_BVH4) {   // (a copy that keeps its BVH2: the collapsed records, and a quad record per interior node and leaf root at most)
         if (rc == RT_OK) rc = rebuild_grow(b, t.bvh4, nodeCap, 0, "BVH4 nodes");
-        if (rc == RT_OK) rc = rebuild_grow(b, t.quads, (nodeCap / 2 + b.ranges.size()) * 8, 0, "quad records");
+        if (rc == RT_OK) rc = rebuild_grow(b, t.quads, (nodeCap / 2 + nR) * 8, 0, "quad records");
         if (rc == RT_OK) rc = rebuild_grow(b, t.newId, nodeCap, 0, "live ids");
-        if (rc == RT_OK) rc = rebuild_grow(b, t.quadNode, nodeCap / 2 + b.ranges.size(), 0, "live nodes");
+        if (rc == RT_OK) rc = rebuild_grow(b, t.quadNode, nodeCap / 2 + nR, 0, "live nodes");
     }
     return rc;
 }
@@ -619,11 +628,24 @@ static int rebuild_scratch(SceneBag& b, size_t nodeNeed)
     b.dw.scan = b.dwScan.p; b.dw.scanBytes = b.dwScan.cap;
     return RT_OK;
 }
-static int rebuild_alloc(SceneBag& b, SceneBag::RebuildSet& t)
+// What the trees of a call are built over: the bound scene's own shape (a rebuild) or the caller's (a resize)
+struct Shape {
+    int32_t nPrims, nBlas, nLights;                  // (a resize learns nLights on the device: reserve_lights follows)
+    const std::vector<rebuild::BlasRange>* ranges;   // the primitive range of every distinct BLAS, in increasing order (root: not read)
+    const std::vector<int32_t>* instBlas;            // instance -> its range
+    int32_t nTlas() const { return 2 * nBlas; }      // TLAS::Build's node count
+};
+// The lights' arrays of the set `t` (not live): one record at least, as at upload
+static int reserve_lights(SceneBag& b, SceneBag::RebuildSet& t, size_t nLights)
 {
-    const size_t nP = (size_t)b.nPrims, nB = (size_t)b.nBlas, nT = (size_t)b.nTlas, nL = std::max<size_t>((size_t)b.nLights, 1);
+    const int rc = rebuild_fit(b, t.lights, nLights, "the light list");
+    return rc != RT_OK ? rc : rebuild_fit(b, t.lightRecs, std::max<size_t>(nLights, 1) * 8, "light records");
+}
+static int rebuild_alloc(SceneBag& b, SceneBag::RebuildSet& t, const Shape& sh, bool resize)
+{
+    const size_t nP = (size_t)sh.nPrims, nB = (size_t)sh.nBlas, nT = (size_t)sh.nTlas();
     int rc = RT_OK;
-    // every piece is made once: a call that ran out of memory half way is taken up where it stopped
+    // every piece is made on its own: a call that ran out of memory half way is taken up where it stopped
     auto need = [&](auto** p, size_t count) { if (rc == RT_OK && !*p) { rc = dalloc(b.allocs, p, count); if (rc == RT_OK) b.rallocs++; } };
     if (!b.stream) HIPCHK(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));
     for (hipEvent_t& e : b.rev) if (!e) HIPCHK(hipEventCreate(&e));
@@ -632,13 +654,23 @@ static int rebuild_alloc(SceneBag& b, SceneBag::RebuildSet& t)
     // the scratch both sets share
     need(&b.rStatus, 2); need(&b.dw.ctr, rebuilddev::kCtrWords);
     if (rc == RT_OK && !b.dwScan.p) rc = rebuild_scratch(b, 2 * cap0);
-    if (rc != RT_OK || t.allocated) return rc;
-    need(&t.prims, nP); need(&t.blas, nB); need(&t.tlas, nT); need(&t.tp, nT * 4); need(&t.tpP, nT * 4); need(&t.ir, nB * 4);
-    need(&t.shadeRecs, nP); need(&t.lightRecs, nL * 8); need(&t.rootEntry, nB);
-    if (rc == RT_OK) rc = rebuild_reserve(b, t, std::max(cap0, t.primIdx.cap), std::max(2 * cap0, t.nodes.cap), 0, 0);
     if (rc != RT_OK) return rc;
-    t.allocated = true;
-    return RT_OK;
+    // what scales with the shape
+    rc = rebuild_fit(b, t.prims, nP, "primitives");
+    if (rc == RT_OK) rc = rebuild_fit(b, t.shadeRecs, nP, "shade records");
+    if (rc == RT_OK) rc = rebuild_fit(b, t.blas, nB, "instances");
+    if (rc == RT_OK) rc = rebuild_fit(b, t.tlas, nT, "TLAS nodes");
+    if (rc == RT_OK) rc = rebuild_fit(b, t.tp, nT * 4, "TLAS records");
+    if (rc == RT_OK) rc = rebuild_fit(b, t.tpP, nT * 4, "TLAS records");
+    if (rc == RT_OK) rc = rebuild_fit(b, t.ir, nB * 4, "instance records");
+    if (rc == RT_OK) rc = rebuild_fit(b, t.rootEntry, nB, "root entries");
+    // (a rebuild carries the bound light records, and the light list only once a resize has put it into a set; a resize sizes both
+    // when its scan has counted the lights)
+    if (rc == RT_OK && !resize) rc = rebuild_fit(b, t.lightRecs, std::max<size_t>((size_t)sh.nLights, 1) * 8, "light records");
+    if (rc == RT_OK && !resize && b.lightsInSet) rc = rebuild_fit(b, t.lights, (size_t)sh.nLights, "the light list");
+    // ... and with the trees (the first allocation: the initial capacity)
+    if (rc == RT_OK && !t.nodes.p) rc = rebuild_reserve(b, t, sh.ranges->size(), std::max(cap0, t.primIdx.cap), std::max(2 * cap0, t.nodes.cap), 0, 0);
+    return rc;
 }
 
 static double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b)
@@ -646,63 +678,106 @@ static double ms_between(std::chrono::steady_clock::time_point a, std::chrono::s
     return std::chrono::duration<double, std::milli>(b - a).count();
 }
 
-int scenedev::rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
-                            int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats)
+// The checks of the builder and its options that need no scene: an unknown builder, a refit where there is no tree, alpha
+static int check_builder(const char* who, int32_t builder, const RtBuildOptions* opts, bool refitAllowed)
+{
+    if (builder != RT_REBUILD_SAH && builder != RT_REBUILD_LBVH && builder != RT_REBUILD_SBVH && builder != RT_REBUILD_REFIT)
+        return fail(RT_E_INVALID, "%s: unknown builder %d", who, builder);
+    if (builder == RT_REBUILD_REFIT && !refitAllowed) return fail(RT_E_INVALID, "%s: RT_REBUILD_REFIT: a resized scene has no tree to refit", who);
+    const float alpha = builder == RT_REBUILD_SBVH && opts ? opts->alpha : 0.0f;
+    if (!(alpha >= 0.0f && alpha <= 1.0f)) return fail(RT_E_INVALID, "%s: alpha must lie in [0, 1]", who);
+    return RT_OK;
+}
+// The builders' own argument checks, BLAS by BLAS (node and index ids as the host appends BLAS after BLAS; the SBVH builder's ids
+// are known only as the trees are built: its ranges hold at most 2^30 primitives each, and alpha is checked by check_builder)
+static int check_ranges(const char* who, int32_t builder, const RtBuildOptions* opts, int32_t nPrims, const std::vector<rebuild::BlasRange>& ranges, lbvh::Params& P)
+{
+    if (builder == RT_REBUILD_SAH || builder == RT_REBUILD_LBVH) {
+        uint32_t nodeBase = 0, idxBase = 0;
+        for (const rebuild::BlasRange& r : ranges) {
+            const int32_t cap = 2 * (int32_t)r.count - 1;
+            const char* msg = builder == RT_REBUILD_SAH ? sahdev::check_args(nPrims, (int32_t)r.first, (int32_t)r.count, nodeBase, idxBase)
+                                                        : lbvhdev::check_args(opts, nPrims, (int32_t)r.first, (int32_t)r.count, nodeBase, idxBase, P);
+            if (msg) return fail(RT_E_INVALID, "%s: %s", who, msg);
+            nodeBase += (uint32_t)cap; idxBase += r.count;
+        }
+    } else if (builder == RT_REBUILD_SBVH) {
+        for (const rebuild::BlasRange& r : ranges) if (r.count == 0 || r.count > (1u << 30)) return fail(RT_E_INVALID, "%s: a BLAS of %u primitives", who, r.count);
+    }
+    return RT_OK;
+}
+
+// The one body of rt_rebuild_scene and rt_resize_scene.  A rebuild (newPrims NULL) keeps the bound shape `sh` and takes the replacement
+// records prims / first / count and blas as rt_update_scene does; a resize builds the caller's shape over newPrims (host or device memory,
+// sh.nPrims records), blas (NULL: identity) carrying the transforms.  The arguments have passed the checks that need no device.
+static int rebuild_body(SceneBag& b, const char* who, const Shape& sh, const void* newPrims, const RtPrimitive* prims, int32_t first, int32_t count,
+                        const RtBVHInstance* blas, int32_t builder, const RtBuildOptions* opts, const lbvh::Params& P, RtRebuildStats* stats)
 {
     using clock = std::chrono::steady_clock;
     const auto t0 = clock::now();
-    const char* who = "rt_rebuild_scene";
-    // ---- refusals that need no device work
-    if (b.refitRefusal) return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: %s", b.refitRefusal);
-    if (b.rebuildRefusal) return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: %s", b.rebuildRefusal);
-    if (builder != RT_REBUILD_SAH && builder != RT_REBUILD_LBVH && builder != RT_REBUILD_SBVH && builder != RT_REBUILD_REFIT)
-        return fail(RT_E_INVALID, "rt_rebuild_scene: unknown builder %d", builder);
+    const bool resize = newPrims != nullptr;
     const bool sbvh = builder == RT_REBUILD_SBVH, refit = builder == RT_REBUILD_REFIT;   // (refit: no builder runs, opts is ignored)
     const float alpha = sbvh && opts ? opts->alpha : 0.0f;
-    if (!(alpha >= 0.0f && alpha <= 1.0f)) return fail(RT_E_INVALID, "rt_rebuild_scene: alpha must lie in [0, 1]");
-    if (const int rc = check_change(who, b, prims, first, count, blas, nBlas, "")) return rc;
-    const size_t nR = b.ranges.size();
-    // the builders' own argument checks, BLAS by BLAS (node and index ids as the host appends BLAS after BLAS; the SBVH builder's ids
-    // are known only as the trees are built: its ranges are the upload's, at most 2^30 primitives each, and alpha is checked above)
-    lbvh::Params P{};
-    if (!sbvh && !refit) {
-        uint32_t nodeBase = 0, idxBase = 0;
-        for (const rebuild::BlasRange& r : b.ranges) {
-            const int32_t cap = 2 * (int32_t)r.count - 1;
-            const char* msg = builder == RT_REBUILD_SAH ? sahdev::check_args(b.nPrims, (int32_t)r.first, (int32_t)r.count, nodeBase, idxBase)
-                                                        : lbvhdev::check_args(opts, b.nPrims, (int32_t)r.first, (int32_t)r.count, nodeBase, idxBase, P);
-            if (msg) return fail(RT_E_INVALID, "rt_rebuild_scene: %s", msg);
-            nodeBase += (uint32_t)cap; idxBase += r.count;
-        }
-    } else if (sbvh) {
-        for (const rebuild::BlasRange& r : b.ranges) if (r.count == 0 || r.count > (1u << 30)) return fail(RT_E_INVALID, "rt_rebuild_scene: a BLAS of %u primitives", r.count);
-    }
+    const std::vector<rebuild::BlasRange>& ranges = *sh.ranges;
+    const std::vector<int32_t>& instBlas = *sh.instBlas;
+    const size_t nR = ranges.size();
     HIPCHK(hipSetDevice(b.device));
     SceneBag::RebuildSet& t = b.rset[b.rnext];
-    if (const int rc = rebuild_alloc(b, t)) return rc;
+    if (const int rc = rebuild_alloc(b, t, sh, resize)) return rc;
     hipStream_t s = b.stream;
     if (refit) {   // room for the bound trees (nR spare nodes: see the SBVH builder below)
-        if (const int rc = rebuild_reserve(b, t, (size_t)b.nIdx, (size_t)b.nNodes + nR, 0, 0)) return rc;
+        if (const int rc = rebuild_reserve(b, t, nR, (size_t)b.nIdx, (size_t)b.nNodes + nR, 0, 0)) return rc;
     } else if (!sbvh) {
         // room for every tree these builders can make (a set or the scratch that started smaller, or has only held SBVH trees so far)
-        if (const int rc = rebuild_reserve(b, t, (size_t)b.nPrims, 2 * (size_t)b.nPrims, 0, 0)) return rc;
+        if (const int rc = rebuild_reserve(b, t, nR, (size_t)sh.nPrims, 2 * (size_t)sh.nPrims, 0, 0)) return rc;
         // the builders' workspace
         size_t need = 0;
-        for (const rebuild::BlasRange& r : b.ranges) {
+        for (const rebuild::BlasRange& r : ranges) {
             size_t bytes = 0;
             const int rc = builder == RT_REBUILD_SAH ? sahdev::work_bytes(who, r.count, s, &bytes) : lbvhdev::work_bytes(who, r.count, s, &bytes);
             if (rc != RT_OK) return rc;
             need = std::max(need, bytes);
         }
         if (need > b.rwork.cap)
-            if (const int rc = rebuild_grow(b, b.rwork, need, 0, "the builders' workspace", "rt_rebuild_scene: %zu bytes of builder workspace")) return rc;
+            if (const int rc = rebuild_grow(b, b.rwork, need, 0, "the builders' workspace", "in-place scene change: %zu bytes of builder workspace")) return rc;
     }
     const SceneArrays& sc = b.sc;
+    int32_t nLights = sh.nLights;
+    const uint32_t* lights = sc.lights;
     // ---- stage: the new primitives into the set that is not live
     HIPCHK(hipEventRecord(b.rev[0], s));
-    HIPCHK(hipMemcpyAsync(t.prims, sc.prims, sizeof(RtPrimitive) * (size_t)b.nPrims, hipMemcpyDeviceToDevice, s));
-    if (count) HIPCHK(hipMemcpyAsync(t.prims + first, prims, sizeof(RtPrimitive) * (size_t)count, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(t.lightRecs, sc.lightRecs, sizeof(RtFloat4) * 8 * std::max<size_t>((size_t)b.nLights, 1), hipMemcpyDeviceToDevice, s));   // (the emittance words stay)
+    if (resize) {
+        // one path for host and device input: copied first (the set is not live, so checking after the copy is safe), then checked
+        // where it lies; the light list and the light records come from the same pass
+        if (const int rc = rebuild_scratch(b, (size_t)sh.nPrims)) return rc;   // (flags and ranks: a word per primitive)
+        if (const int rc = rebuild_fit(b, b.rPacked, (size_t)sh.nPrims, "the packed objType / matIdx pairs")) return rc;
+        uint32_t* bad = (uint32_t*)b.rStatus;
+        HIPCHK(hipMemcpyAsync(t.prims.p, newPrims, sizeof(RtPrimitive) * (size_t)sh.nPrims, hipMemcpyDefault, s));
+        HIPCHK(rebuilddev::resize_check(s, b.dw, t.prims.p, (uint32_t)sh.nPrims, sc.mats, sc.nMats, b.rPacked.p, bad));
+        uint32_t firstBad = resize::kNoBad, lastRank = 0, lastFlag = 0;
+        HIPCHK(hipMemcpyAsync(&firstBad, bad, sizeof firstBad, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&lastRank, b.dw.ranks + (sh.nPrims - 1), sizeof lastRank, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&lastFlag, b.dw.flags + (sh.nPrims - 1), sizeof lastFlag, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (firstBad != resize::kNoBad) {
+            int2 pm{ 0, 0 };
+            HIPCHK(hipMemcpy(&pm, b.rPacked.p + firstBad, sizeof pm, hipMemcpyDeviceToHost));
+            return fail(RT_E_INVALID, "%s: primitive %u: objType %d / matIdx %d out of range (objType: one of RT_PRIM_*, matIdx: [0, %d)); the scene is unchanged", who,
+                        firstBad, pm.x, pm.y, sc.nMats);
+        }
+        nLights = (int32_t)(lastRank + lastFlag);
+        if (const int rc = reserve_lights(b, t, (size_t)nLights)) return rc;
+        HIPCHK(rebuilddev::light_emit(s, b.dw, t.prims.p, (uint32_t)sh.nPrims, sc.mats, (uint32_t)nLights, t.lights.p, t.lightRecs.p));
+        lights = t.lights.p;
+    } else {
+        HIPCHK(hipMemcpyAsync(t.prims.p, sc.prims, sizeof(RtPrimitive) * (size_t)b.nPrims, hipMemcpyDeviceToDevice, s));
+        if (count) HIPCHK(hipMemcpyAsync(t.prims.p + first, prims, sizeof(RtPrimitive) * (size_t)count, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(t.lightRecs.p, sc.lightRecs, sizeof(RtFloat4) * 8 * std::max<size_t>((size_t)b.nLights, 1), hipMemcpyDeviceToDevice, s));   // (the emittance words stay)
+        if (b.lightsInSet) {   // the light list lives in a set since a resize: it moves on with the arrays
+            if (nLights) HIPCHK(hipMemcpyAsync(t.lights.p, sc.lights, sizeof(uint32_t) * (size_t)nLights, hipMemcpyDeviceToDevice, s));
+            lights = t.lights.p;
+        }
+    }
     const auto t1 = clock::now();
     // ---- every BLAS anew, in the order of the ranges (a refit: the bound trees, their boxes anew)
     std::vector<uint32_t> rootOf(nR), interiors(nR), depth(nR);
@@ -717,38 +792,38 @@ int scenedev::rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first
         HIPCHK(hipMemcpyAsync(t.parent.p, b.dParent, sizeof(uint32_t) * (size_t)nNodes, hipMemcpyDeviceToDevice, s));
         if (b.nLeaves) HIPCHK(hipMemcpyAsync(t.leaves.p, b.dLeaves, sizeof(uint32_t) * (size_t)b.nLeaves, hipMemcpyDeviceToDevice, s));
         if (b.nPairs) HIPCHK(hipMemcpyAsync(t.pairNode.p, b.dPairNode, sizeof(uint32_t) * (size_t)b.nPairs, hipMemcpyDeviceToDevice, s));
-        HIPCHK(refitdev::launch_refit(s, t.nodes.p, nNodes, t.prims, t.primIdx.p, t.leaves.p, b.nLeaves, t.parent.p, t.tickets.p));
+        HIPCHK(refitdev::launch_refit(s, t.nodes.p, nNodes, t.prims.p, t.primIdx.p, t.leaves.p, b.nLeaves, t.parent.p, t.tickets.p));
         rootOf = b.blasRoot; interiors = b.blasInteriors; depth = b.blasHeight;
         for (size_t k = 0; k < nR; k++) maxDepth = std::max(maxDepth, depth[k]);
     }
     for (size_t k = 0; k < nR && !refit; k++) {
-        const rebuild::BlasRange& r = b.ranges[k];
+        const rebuild::BlasRange& r = ranges[k];
         Built built{};
         uint32_t slots = r.count;
         if (sbvh) {
             // size, then place: the tree stays in the builder's own memory until the set has room for it (one tree at a time)
             struct TreeGuard { sbvhdev::Tree* p = nullptr; ~TreeGuard() { sbvhdev::destroy(p); } } tree;
             SbvhBuilt sb{};
-            if (const int rc = sbvhdev::build(who, s, alpha, t.prims + r.first, r.count, r.first, nNodes, nIdx, nullptr, nullptr, b.spool, &tree.p, &sb)) return rc;
+            if (const int rc = sbvhdev::build(who, s, alpha, t.prims.p + r.first, r.count, r.first, nNodes, nIdx, nullptr, nullptr, b.spool, &tree.p, &sb)) return rc;
             if (sb.nIdx == 0 || (uint64_t)nNodes + sb.nodes + nR > 0x7fffffffull || (uint64_t)nIdx + sb.nIdx > 0x7fffffffull)
-                return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: the new trees have 2^31 nodes or index slots, or more; the scene is unchanged");
+                return fail(RT_E_UNSUPPORTED, "%s: the new trees have 2^31 nodes or index slots, or more; the scene is unchanged", who);
             // (nR spare nodes: the leaf and pair arrays hold half the node capacity, and k trees have k leaves more than interior nodes)
-            if (const int rc = rebuild_reserve(b, t, (size_t)nIdx + sb.nIdx, (size_t)nNodes + sb.nodes + nR, nIdx, nNodes)) return rc;
+            if (const int rc = rebuild_reserve(b, t, nR, (size_t)nIdx + sb.nIdx, (size_t)nNodes + sb.nodes + nR, nIdx, nNodes)) return rc;
             if (const int rc = sbvhdev::emit(who, s, tree.p, t.nodes.p + nNodes, t.primIdx.p + nIdx)) return rc;
             built.nodes = sb.nodes; built.depth = sb.depth; slots = sb.nIdx;
             spatialSplits += sb.spatialSplits; primsClipped += sb.primsClipped;
         } else {
             const int rc = builder == RT_REBUILD_SAH
-                ? sahdev::build(who, s, b.rwork.p, t.prims + r.first, r.count, r.first, nNodes, nIdx, t.nodes.p + nNodes, t.primIdx.p + nIdx, nullptr, nullptr, &built)
-                : lbvhdev::build(who, s, b.rwork.p, P, t.prims + r.first, r.count, r.first, nNodes, nIdx, t.nodes.p + nNodes, t.primIdx.p + nIdx, nullptr, nullptr, &built);
+                ? sahdev::build(who, s, b.rwork.p, t.prims.p + r.first, r.count, r.first, nNodes, nIdx, t.nodes.p + nNodes, t.primIdx.p + nIdx, nullptr, nullptr, &built)
+                : lbvhdev::build(who, s, b.rwork.p, P, t.prims.p + r.first, r.count, r.first, nNodes, nIdx, t.nodes.p + nNodes, t.primIdx.p + nIdx, nullptr, nullptr, &built);
             if (rc != RT_OK) return rc;
         }
         if (built.nodes == 0 || (built.nodes & 1u) == 0 || (!sbvh && built.nodes > 2 * r.count - 1))
-            return fail(RT_E_DEVICE, "rt_rebuild_scene: inconsistent builder result (%u nodes for %u primitives)", built.nodes, r.count);
+            return fail(RT_E_DEVICE, "%s: inconsistent builder result (%u nodes for %u primitives)", who, built.nodes, r.count);
         if ((built.depth == 0) != (built.nodes == 1))
-            return fail(RT_E_DEVICE, "rt_rebuild_scene: inconsistent builder result (height %u with %u nodes)", built.depth, built.nodes);
+            return fail(RT_E_DEVICE, "%s: inconsistent builder result (height %u with %u nodes)", who, built.depth, built.nodes);
         if (rebuild::exceeds_stack(built.depth))   // validate_scene's rule
-            return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: the new BLAS %zu needs %u stack entries, at most %d are supported; the scene is unchanged", k,
+            return fail(RT_E_UNSUPPORTED, "%s: the new BLAS %zu needs %u stack entries, at most %d are supported; the scene is unchanged", who, k,
                         built.depth, RT_BVH4_STACK);
         rootOf[k] = nNodes; interiors[k] = (built.nodes - 1) / 2; depth[k] = built.depth;
         maxDepth = std::max(maxDepth, built.depth);
@@ -759,10 +834,15 @@ int scenedev::rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first
     if (bvh4) if (const int rc = collapse_scratch(b, (size_t)nNodes + nR)) return rc;
     const auto t2 = clock::now();
     // ---- the instances (host: at most 256 records), then everything upload derives
-    std::vector<RtBVHInstance> inst = b.inst;
-    if (blas) inst.assign(blas, blas + nBlas);
-    for (int32_t i = 0; i < b.nBlas; i++) inst[(size_t)i].bvhIdx = rootOf[(size_t)b.instBlas[(size_t)i]];
-    HIPCHK(hipMemcpyAsync(t.blas, inst.data(), sizeof(RtBVHInstance) * (size_t)b.nBlas, hipMemcpyHostToDevice, s));
+    std::vector<RtBVHInstance> inst;
+    if (blas) inst.assign(blas, blas + sh.nBlas);
+    else if (!resize) inst = b.inst;
+    else {   // a resize without transforms: BuildBLAS's identity
+        inst.assign((size_t)sh.nBlas, RtBVHInstance{});
+        for (RtBVHInstance& r : inst) r.invT[0] = r.invT[5] = r.invT[10] = r.invT[15] = 1.0f;
+    }
+    for (int32_t i = 0; i < sh.nBlas; i++) inst[(size_t)i].bvhIdx = rootOf[(size_t)instBlas[(size_t)i]];
+    HIPCHK(hipMemcpyAsync(t.blas.p, inst.data(), sizeof(RtBVHInstance) * (size_t)sh.nBlas, hipMemcpyHostToDevice, s));
     HIPCHK(hipEventRecord(b.rev[1], s));
     uint32_t nPairs = 0;
     const bool layout1 = b.layout == 1;
@@ -770,22 +850,22 @@ int scenedev::rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first
         nPairs = (uint32_t)b.nPairs;
         if (layout1 && !bvh4) {
             HIPCHK(hipMemcpyAsync(t.pairs.p, sc.pairs, sizeof(RtFloat4) * 4 * std::max<size_t>(nPairs, 1), hipMemcpyDeviceToDevice, s));
-            HIPCHK(hipMemcpyAsync(t.rootEntry, sc.rootEntry, sizeof(uint32_t) * (size_t)b.nBlas, hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(t.rootEntry.p, sc.rootEntry, sizeof(uint32_t) * (size_t)b.nBlas, hipMemcpyDeviceToDevice, s));
         }
     } else {
         HIPCHK(rebuilddev::begin(s, b.dw, t.parent.p, nNodes));
         {   // pair ids: BLAS by BLAS in the order in which the instances first name them
             std::vector<uint8_t> done(nR, 0);
-            for (int32_t i = 0; i < b.nBlas; i++) {
-                const size_t k = (size_t)b.instBlas[(size_t)i];
+            for (int32_t i = 0; i < sh.nBlas; i++) {
+                const size_t k = (size_t)instBlas[(size_t)i];
                 if (done[k]) continue;
                 done[k] = 1;
                 HIPCHK(rebuilddev::number_blas(s, b.dw, t.nodes.p, nNodes, rootOf[k], interiors[k], depth[k], nPairs, (uint32_t)t.pairNode.cap, t.pairNode.p, t.parent.p));
                 nPairs += interiors[k];
             }
         }
-        HIPCHK(rebuilddev::finish(s, b.dw, t.nodes.p, nNodes, nPairs, nNodes - nPairs, t.blas, (uint32_t)b.nBlas, t.pairNode.p, layout1 && !bvh4 ? t.pairs.p : nullptr,
-                                  t.rootEntry, t.leaves.p));
+        HIPCHK(rebuilddev::finish(s, b.dw, t.nodes.p, nNodes, nPairs, nNodes - nPairs, t.blas.p, (uint32_t)sh.nBlas, t.pairNode.p, layout1 && !bvh4 ? t.pairs.p : nullptr,
+                                  t.rootEntry.p, t.leaves.p));
     }
     const uint32_t nLeaves = refit ? b.nLeaves : nNodes - nPairs;
     uint32_t c4st[collapsedev::kStatusWords] = { 0 };
@@ -807,21 +887,21 @@ int scenedev::rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first
             if (refitPath != 1) HIPCHK(collapsedev::begin(s, w, t.nodes.p, nNodes, t.bvh4.p));   // the fallback: the rebuild's collapse
         }
         std::vector<uint8_t> done(nR, refitPath == 1 ? 1 : 0);
-        for (int32_t i = 0; i < b.nBlas; i++) {
-            const size_t k = (size_t)b.instBlas[(size_t)i];
+        for (int32_t i = 0; i < sh.nBlas; i++) {
+            const size_t k = (size_t)instBlas[(size_t)i];
             if (done[k]) continue;
             done[k] = 1;
             HIPCHK(collapsedev::collapse_blas(s, w, t.nodes.p, nNodes, rootOf[k], interiors[k], depth[k], t.bvh4.p));
         }
-        HIPCHK(collapsedev::finish(s, w, t.bvh4.p, nNodes, nIdx, (const uint32_t*)t.blas, (uint32_t)(sizeof(RtBVHInstance) / 4), (uint32_t)b.nBlas,
-                                   layout1 ? t.quads.p : nullptr, t.rootEntry));
+        HIPCHK(collapsedev::finish(s, w, t.bvh4.p, nNodes, nIdx, (const uint32_t*)t.blas.p, (uint32_t)(sizeof(RtBVHInstance) / 4), (uint32_t)sh.nBlas,
+                                   layout1 ? t.quads.p : nullptr, t.rootEntry.p));
     }
     const bool boxes = refit && layout1 && !bvh4;
-    HIPCHK(refitdev::launch_records(s, t.prims, t.nodes.p, t.primIdx.p, nIdx, sc.lights, (uint32_t)b.nLights, 0u, (uint32_t)b.nPrims,
+    HIPCHK(refitdev::launch_records(s, t.prims.p, t.nodes.p, t.primIdx.p, nIdx, lights, (uint32_t)nLights, 0u, (uint32_t)sh.nPrims,
                                     boxes ? t.pairNode.p : nullptr, boxes ? nPairs : 0u, boxes ? t.pairs.p : nullptr, layout1 ? t.triRecs.p : nullptr,
-                                    t.shadeRecs, t.lightRecs));
+                                    t.shadeRecs.p, t.lightRecs.p));
     HIPCHK(hipEventRecord(b.rev[2], s));
-    HIPCHK(refitdev::launch_tlas(s, t.nodes.p, t.blas, b.nBlas, layout1 ? t.rootEntry : nullptr, t.tlas, t.tp, t.tpP, t.ir, b.rStatus));
+    HIPCHK(refitdev::launch_tlas(s, t.nodes.p, t.blas.p, sh.nBlas, layout1 ? t.rootEntry.p : nullptr, t.tlas.p, t.tp.p, t.tpP.p, t.ir.p, b.rStatus));
     HIPCHK(hipEventRecord(b.rev[3], s));
     int32_t status[2] = { 0, 0 };
     uint32_t walk[2] = { 0, 0 };
@@ -831,7 +911,7 @@ int scenedev::rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first
     if (bvh4 && refitPath != 1) HIPCHK(hipMemcpyAsync(c4st, b.c4.ctr + collapsedev::kStatus, sizeof c4st, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (bvh4 && refitPath == 1) c4st[collapsedev::kNeed - collapsedev::kStatus] = b.c4Need;   // (a top-down figure: carried over with the live ids)
-    if (walk[0]) return fail(RT_E_DEVICE, "rt_rebuild_scene: the breadth-first walk does not match the builder's tree (inconsistent device result)");
+    if (walk[0]) return fail(RT_E_DEVICE, "%s: the breadth-first walk does not match the builder's tree (inconsistent device result)", who);
     if (bvh4) {
         if (const int rc = collapse_status_error(who, c4st, "; the scene is unchanged")) return rc;
         walk[1] = collapse_largest_leaf(c4st);   // the layout rule of a BVH4 looks at the collapsed records
@@ -840,19 +920,39 @@ int scenedev::rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first
     const int stackNeed = bvh4 ? (int)c4st[collapsedev::kNeed - collapsedev::kStatus] : (int)maxDepth;
     // (a refit moves no leaf size: a BVH2 copy keeps its layout, a BVH4 copy's check cannot fail)
     if (!(refit && !bvh4) && rebuild::takes_layout1(b.variantLayout1, (int32_t)nIdx, std::max(walk[1], 1u)) != layout1)
-        return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: the new trees would change the scene's derived layout (largest leaf %u primitives, %u index slots; "
-                    "layout %d is bound): upload the rebuilt scene instead; the scene is unchanged", walk[1], nIdx, b.layout);
+        return fail(RT_E_UNSUPPORTED, "%s: the new trees would change the scene's derived layout (largest leaf %u primitives, %u index slots; "
+                    "layout %d is bound): upload the rebuilt scene instead; the scene is unchanged", who, walk[1], nIdx, b.layout);
+    std::vector<int2> packed;   // a resize: the host's shadow of objType / matIdx, the only per-primitive data that comes back
+    if (resize) {
+        packed.resize((size_t)sh.nPrims);
+        HIPCHK(hipMemcpy(packed.data(), b.rPacked.p, sizeof(int2) * packed.size(), hipMemcpyDeviceToHost));
+    }
     const auto t3 = clock::now();
     // ---- commit: swap the arrays once no kernel of a holder reads the old ones
     if (const int rc = b.wait_holders()) return rc;
     SceneArrays n = b.sc;
-    n.prims = t.prims; n.bvh2 = t.nodes.p; n.primIdx = t.primIdx.p; n.blas = t.blas; n.tlas = t.tlas;
-    n.tlasPairs = t.tp; n.tlasPairsP = t.tpP; n.instRecs = t.ir;
-    n.shadeRecs = t.shadeRecs; n.lightRecs = t.lightRecs;
+    n.prims = t.prims.p; n.bvh2 = t.nodes.p; n.primIdx = t.primIdx.p; n.blas = t.blas.p; n.tlas = t.tlas.p;
+    n.tlasPairs = t.tp.p; n.tlasPairsP = t.tpP.p; n.instRecs = t.ir.p;
+    n.shadeRecs = t.shadeRecs.p; n.lightRecs = t.lightRecs.p;
+    if (resize || b.lightsInSet) n.lights = t.lights.p;
     if (layout1 && !bvh4 && nPairs == 0) HIPCHK(hipMemsetAsync(t.pairs.p, 0, sizeof(RtFloat4) * 4, s));   // no interior node: one zero record, as at upload
     if (layout1 && !bvh4) n.pairs = t.pairs.p;
-    if (layout1) { n.triRecs = t.triRecs.p; n.rootEntry = t.rootEntry; }
+    if (layout1) { n.triRecs = t.triRecs.p; n.rootEntry = t.rootEntry.p; }
     if (bvh4) { n.bvh4 = t.bvh4.p; if (layout1) n.quads = t.quads.p; }
+    if (resize) {   // the new shape: the counts, the TLAS root (a leaf iff there is one instance: TLAS::Build copies it to node 0)
+        n.nPrims = sh.nPrims; n.nLights = nLights; n.nBlas = sh.nBlas;
+        const bool leafRoot = sh.nBlas == 1;
+        n.tlasRoot = leafRoot ? refit::kLeafBit : 0u;
+        n.tlasRootP = leafRoot ? refit::kTagInst : refit::kTagTlas;
+        b.singleBlas = leafRoot; b.lightsInSet = true;
+        b.nPrims = sh.nPrims; b.nLights = nLights; b.nBlas = sh.nBlas; b.nTlas = sh.nTlas();
+        b.primType.resize(packed.size()); b.primMat.resize(packed.size());
+        for (size_t i = 0; i < packed.size(); i++) { b.primType[i] = packed[i].x; b.primMat[i] = packed[i].y; }
+        std::vector<rebuild::BlasRange> bound = ranges;
+        for (size_t k = 0; k < nR; k++) bound[k].root = rootOf[k];
+        const std::vector<int32_t> map = instBlas;   // (sh may alias the bag's own)
+        b.ranges.swap(bound); b.instBlas = map;
+    }
     b.sc = n;
     b.dParent = t.parent.p; b.dLeaves = t.leaves.p; b.dTickets = t.tickets.p; b.dPairNode = t.pairNode.p;
     b.nNodes = (int32_t)nNodes; b.nIdx = (int32_t)nIdx; b.nPairs = layout1 && !bvh4 ? (int32_t)nPairs : 0; b.nLeaves = nLeaves;
@@ -880,11 +980,75 @@ int scenedev::rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first
         stats->stage_ms = ms_between(t0, t1); stats->build_ms = ms_between(t1, t2); stats->derive_ms = derive; stats->tlas_ms = tlas;
         if (refit) { float fit = 0; (void)hipEventElapsedTime(&fit, b.rev[0], b.rev[1]); stats->build_ms = fit; }   // (GPU: the staging copies and the refit)
         stats->commit_ms = ms_between(t3, t4);
-        stats->prims = count; stats->blas_built = refit ? 0 : (int32_t)nR; stats->nodes = (int32_t)nNodes; stats->n_idx = (int32_t)nIdx;
+        stats->prims = resize ? sh.nPrims : count; stats->blas_built = refit ? 0 : (int32_t)nR; stats->nodes = (int32_t)nNodes; stats->n_idx = (int32_t)nIdx;
         stats->max_depth = (int32_t)maxDepth; stats->tlas_nodes = b.nTlas; stats->tlas_depth = status[1]; stats->reconfigured = reconfigure ? 1 : 0;
         stats->spatial_splits = (int32_t)std::min<uint64_t>(spatialSplits, 0x7fffffffu); stats->prims_clipped = (int32_t)std::min<uint64_t>(primsClipped, 0x7fffffffu);
     }
     return RT_OK;
+}
+int scenedev::rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
+                            int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats)
+{
+    const char* who = "rt_rebuild_scene";
+    // ---- refusals that need no device work
+    if (b.refitRefusal) return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: %s", b.refitRefusal);
+    if (b.rebuildRefusal) return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: %s", b.rebuildRefusal);
+    if (const int rc = check_builder(who, builder, opts, true)) return rc;
+    if (const int rc = check_change(who, b, prims, first, count, blas, nBlas, "")) return rc;
+    lbvh::Params P{};
+    if (const int rc = check_ranges(who, builder, opts, b.nPrims, b.ranges, P)) return rc;
+    const Shape sh{ b.nPrims, b.nBlas, b.nLights, &b.ranges, &b.instBlas };
+    return rebuild_body(b, who, sh, nullptr, prims, first, count, blas, builder, opts, P, stats);
+}
+
+// The ranges of a caller's shape as the builders take them (root: assigned by the build)
+static std::vector<rebuild::BlasRange> shape_ranges(const RtSceneShape& shape)
+{
+    std::vector<rebuild::BlasRange> r((size_t)shape.nRanges);
+    uint32_t first = 0;
+    for (int32_t k = 0; k < shape.nRanges; k++) { r[(size_t)k] = rebuild::BlasRange{ 0u, first, (uint32_t)shape.rangeCount[k] }; first += (uint32_t)shape.rangeCount[k]; }
+    return r;
+}
+// What rt_resize_scene checks without a device or a scene (rt_resize_check): the shape, the builder, its options
+// (ranges receives the shape's ranges)
+static int resize_check_args(const char* who, int32_t nPrims, const RtSceneShape* shape, int32_t builder, const RtBuildOptions* opts, lbvh::Params& P,
+                             std::vector<rebuild::BlasRange>& ranges)
+{
+    if (!shape) return fail(RT_E_INVALID, "%s: null shape", who);
+    std::string msg;
+    if (resize::check_shape(nPrims, shape->nRanges, shape->rangeCount, shape->nBlas, shape->instRange, shape->blas, msg)) return fail(RT_E_INVALID, "%s: %s", who, msg.c_str());
+    if (const int rc = check_builder(who, builder, opts, false)) return rc;
+    ranges = shape_ranges(*shape);
+    return check_ranges(who, builder, opts, nPrims, ranges, P);
+}
+extern "C" int rt_resize_check(int32_t nPrims, const RtSceneShape* shape, int32_t builder, const RtBuildOptions* opts)
+{
+    lbvh::Params P{};
+    std::vector<rebuild::BlasRange> ranges;
+    return resize_check_args("rt_resize_scene", nPrims, shape, builder, opts, P, ranges);
+}
+int scenedev::resize_scene(SceneBag& b, const void* prims, int32_t nPrims, const RtSceneShape* shape, int32_t builder, const RtBuildOptions* opts,
+                           RtRebuildStats* stats)
+{
+    const char* who = "rt_resize_scene";
+    // ---- refusals that need no device work
+    lbvh::Params P{};
+    std::vector<rebuild::BlasRange> ranges;
+    if (const int rc = resize_check_args(who, nPrims, shape, builder, opts, P, ranges)) return rc;
+    if (b.refitRefusal) return fail(RT_E_UNSUPPORTED, "rt_resize_scene: %s", b.refitRefusal);
+    if (b.rebuildRefusal) return fail(RT_E_UNSUPPORTED, "rt_resize_scene: %s", b.rebuildRefusal);
+    {   // the bound ranges (in increasing order) must tile the bound primitives
+        uint32_t next = 0;
+        for (const rebuild::BlasRange& r : b.ranges) {
+            if (r.first != next) return fail(RT_E_UNSUPPORTED, "rt_resize_scene: the bound scene's BLAS ranges leave a gap: primitives [%u, %u) belong to no BLAS", next, r.first);
+            next = r.first + r.count;
+        }
+        if (next != (uint32_t)b.nPrims)
+            return fail(RT_E_UNSUPPORTED, "rt_resize_scene: the bound scene's BLAS ranges leave a gap: primitives [%u, %d) belong to no BLAS", next, b.nPrims);
+    }
+    const std::vector<int32_t> instBlas(shape->instRange, shape->instRange + shape->nBlas);
+    const Shape sh{ nPrims, shape->nBlas, 0, &ranges, &instBlas };
+    return rebuild_body(b, who, sh, prims, nullptr, 0, 0, shape->blas, builder, opts, P, stats);
 }
 int64_t scenedev::rebuild_allocations(const SceneBag& b) { return (int64_t)(b.rallocs + sbvhdev::pool_allocations(b.spool)); }
 // The primitive range of every instance's BLAS (rebuild_common.h), for callers that want to know beforehand whether rt_rebuild_scene
@@ -919,6 +1083,7 @@ int scenedev::scene_array(const SceneBag& b, int32_t which, const void** src, si
     case RT_SCENE_INST_RECS:    *src = sc.instRecs; *n = sizeof(RtFloat4) * 4 * (size_t)b.nBlas; break;
     case RT_SCENE_QUADS:        *src = sc.quads; *n = sc.quads ? sizeof(RtFloat4) * 8 * (size_t)std::max(b.nQuads, 1) : 0; break;
     case RT_SCENE_ROOT_ENTRY:   *src = sc.rootEntry; *n = sc.rootEntry ? sizeof(uint32_t) * (size_t)b.nBlas : 0; break;
+    case RT_SCENE_LIGHTS:       *src = sc.lights; *n = sizeof(uint32_t) * (size_t)b.nLights; break;
     case RT_SCENE_BVH2_KEPT:    *src = sc.bvh2; *n = b.keepsBvh2 ? sizeof(RtBVHNode2) * (size_t)b.nNodes : 0; break;
     default: return fail(RT_E_INVALID, "rt_debug_get_scene_array: unknown array %d", which);
     }

@@ -75,9 +75,10 @@ struct SceneBag {
         Grown() = default; Grown(const Grown&) = delete; Grown& operator=(const Grown&) = delete;
         ~Grown() { if (p) (void)hipFree(p); }
     };
-    // staging of an update (allocated by the first one): nothing live is written before the new TLAS has passed
-    RtPrimitive* sPrims = nullptr; RtBVHInstance* sInst = nullptr; RtTLASNode* sTlas = nullptr;
-    RtFloat4 *sTp = nullptr, *sTpP = nullptr, *sIr = nullptr; int32_t* sStatus = nullptr;
+    // staging of an update (allocated by the first one, grown when a resize has changed the counts): nothing live is written before the
+    // new TLAS has passed
+    Grown<RtPrimitive> sPrims; Grown<RtBVHInstance> sInst; Grown<RtTLASNode> sTlas;
+    Grown<RtFloat4> sTp, sTpP, sIr; int32_t* sStatus = nullptr;
     Grown<RtBVHNode2> sNodes;                 // (a rebuild changes the node count)
     hipStream_t stream = nullptr;             // where updates run
     hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };   // brackets of the staging and of the commit
@@ -94,15 +95,17 @@ struct SceneBag {
     uint32_t nLive = 0, c4Need = 0;
     RtRefitInfo refitInfo{};                  // the last successful RT_REBUILD_REFIT (rt_refit_info)
     // Everything a rebuild changes, twice: a rebuild writes the set that is not live and the commit swaps the pointers; the upload's own
-    // arrays stay behind until the copy is freed.  The arrays that scale with the primitives are made once.  Those that scale with the
-    // trees (Grown) have capacities of their own: nPrims index slots and 2 * nPrims nodes at first, which bounds every tree of the SAH
+    // arrays stay behind until the copy is freed.  The arrays that scale with the primitives, the instances and the lights fit the bound
+    // shape exactly at first; rt_resize_scene changes those counts, and an array of the set that is not live that the new shape outgrows
+    // goes to the need plus a quarter (rebuild_fit).  Those that scale with the
+    // trees have capacities of their own: nPrims index slots and 2 * nPrims nodes at first, which bounds every tree of the SAH
     // and the linear builder; an SBVH tree has no such bound, so the set that is not live grows to what the finished trees need plus a
     // quarter (kRebuildHeadroomDiv, rebuild_reserve), what was emitted so far is kept and the arrays it replaces are freed at once.
     struct RebuildSet {
-        bool allocated = false;
-        RtPrimitive* prims = nullptr; RtBVHInstance* blas = nullptr; RtTLASNode* tlas = nullptr;
-        RtFloat4 *tp = nullptr, *tpP = nullptr, *ir = nullptr, *shadeRecs = nullptr, *lightRecs = nullptr;
-        uint32_t* rootEntry = nullptr;
+        Grown<RtPrimitive> prims; Grown<RtFloat4> shadeRecs;                                 // primitives
+        Grown<RtBVHInstance> blas; Grown<RtTLASNode> tlas; Grown<RtFloat4> tp, tpP, ir;      // instances (tlas: 2 per instance; tp, tpP, ir: 4 rows per record)
+        Grown<uint32_t> rootEntry;
+        Grown<uint32_t> lights; Grown<RtFloat4> lightRecs;                                   // lights (lightRecs: 8 rows each, one record at least)
         Grown<uint32_t> primIdx; Grown<RtFloat4> triRecs;                                    // index slots (triRecs: 3 per slot)
         Grown<RtBVHNode2> nodes; Grown<uint32_t> parent, tickets;                            // nodes
         Grown<RtFloat4> pairs; Grown<uint32_t> leaves, pairNode;                             // nodes / 2 (pairs: 4 per interior node)
@@ -120,7 +123,9 @@ struct SceneBag {
     int rnext = 0;                            // the set the next rebuild writes
     Grown<char> rwork;                        // the builders' workspace (bytes)
     rebuilddev::Work dw{};                    // scratch of the derivation
-    int32_t* rStatus = nullptr;               // k_tlas_build's status words
+    int32_t* rStatus = nullptr;               // k_tlas_build's status words (word 0, before that: k_resize_check's lowest refused primitive)
+    Grown<int2> rPacked;                      // rt_resize_scene: (objType, matIdx) per new primitive, what the host reads back for primType / primMat
+    bool lightsInSet = false;                 // a resize has bound a set's light list: rebuilds carry it from set to set from then on
     hipEvent_t rev[4] = { nullptr, nullptr, nullptr, nullptr };
     ~SceneBag()
     {
@@ -146,6 +151,8 @@ int upload_scene(SceneBag& b, int accel, int extendVariant, const HostScene& in,
 int update_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas, RtUpdateStats* stats);
 int rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
                   int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats);
+// rt_resize_scene (include/rt355.h): the caller's shape, checked by resize::check_shape; prims may be host or device memory
+int resize_scene(SceneBag& b, const void* prims, int32_t nPrims, const RtSceneShape* shape, int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats);
 int64_t rebuild_allocations(const SceneBag& b);
 int scene_array(const SceneBag& b, int32_t which, const void** src, size_t* bytes);   // where RT_SCENE_* lies on the device and how long it is
 

@@ -6,6 +6,7 @@
 #include "../../include/rt355.h"
 #include "../../include/rt355_host.h"
 #include "../csrc/collapse_common.h"
+#include "../csrc/resize_common.h"
 #include "rt_host.h"
 
 using namespace rt355;
@@ -251,6 +252,35 @@ int rth_set_instance_transform(RthScene* s, int blas, const float invT[16])
     if (!s || blas < 0 || blas >= (int)s->scene.blasNodes.size()) { g_herr = "rth_set_instance_transform: bad index"; return -1; }
     memcpy(s->scene.blasNodes[blas].invT, invT, sizeof(float) * 16);
     return 0;
+}
+int rth_add_instance(RthScene* s, int blas, const float invT[16])
+{
+    if (!s || blas < 0 || blas >= (int)s->scene.blasNodes.size()) { g_herr = "rth_add_instance: bad index"; return -1; }
+    if (s->scene.blasNodes.size() >= (size_t)refit::kMaxInstances) { g_herr = "rth_add_instance: TLAS::Build takes at most 256 instances"; return -1; }
+    RtBVHInstance inst;
+    memset(&inst, 0, sizeof inst);
+    inst.bvhIdx = s->scene.blasNodes[(size_t)blas].bvhIdx;
+    inst.invT[0] = inst.invT[5] = inst.invT[10] = inst.invT[15] = 1.0f;   // BuildBLAS's identity
+    if (invT) {
+        if (refit::singular(invT)) { g_herr = "rth_add_instance: the transform is singular"; return -1; }
+        memcpy(inst.invT, invT, sizeof(float) * 16);
+    }
+    try { s->scene.blasNodes.push_back(inst); } catch (const std::exception& e) { g_herr = e.what(); return -1; }
+    return (int)s->scene.blasNodes.size() - 1;
+}
+int rth_light_list(const RtPrimitive* prims, int32_t nPrims, const RtMaterial* mats, int32_t nMats, uint32_t* out)
+{
+    if (!prims || !mats || !out || nPrims <= 0 || nMats <= 0) { g_herr = "rth_light_list: missing array"; return RT_E_INVALID; }
+    for (int32_t i = 0; i < nPrims; i++) if (!resize::prim_ok(prims[i].objType, prims[i].matIdx, nMats)) {
+        g_herr = "rth_light_list: primitive " + std::to_string(i) + ": objType " + std::to_string(prims[i].objType) + " / matIdx " + std::to_string(prims[i].matIdx) + " out of range";
+        return RT_E_INVALID;
+    }
+    try {
+        std::vector<uint32_t> lights;
+        resize::light_list(prims, nPrims, mats, lights);
+        if (!lights.empty()) memcpy(out, lights.data(), sizeof(uint32_t) * lights.size());
+        return (int)lights.size();
+    } catch (const std::exception& e) { g_herr = e.what(); return RT_E_NOMEM; }
 }
 
 #define VIEW(vec) do { if (n) *n = (int)(vec).size(); return (vec).data(); } while (0)

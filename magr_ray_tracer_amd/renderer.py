@@ -45,6 +45,36 @@ def _rebuild_dict(st):
     return d
 
 
+def _resize_args(prims, range_counts, inst_range, instances, builder, lbvh_options, alpha):
+    """The arguments of rt_resize_scene: `prims` a numpy array (host memory) or a torch tensor on the context's GPU, used where it lies."""
+    from .scene import build_options, rebuild_builder
+    which = rebuild_builder(builder, lbvh_options, alpha)
+    if isinstance(prims, np.ndarray) or not hasattr(prims, "data_ptr"):
+        p = np.ascontiguousarray(prims, dtype=_lib.Primitive)
+        pp, n = _lib.ptr(p) if len(p) else None, len(p)
+    else:   # a torch tensor: nothing is copied, the library checks where it lies
+        p = prims if prims.is_contiguous() else prims.contiguous()
+        nbytes = p.numel() * p.element_size()
+        if nbytes % _lib.Primitive.itemsize:
+            raise ValueError(f"a primitive tensor of {nbytes} bytes is no whole number of {_lib.Primitive.itemsize}-byte records")
+        pp, n = (C.c_void_p(p.data_ptr()) if nbytes else None), nbytes // _lib.Primitive.itemsize
+        if getattr(p, "is_cuda", False):
+            import torch
+            torch.cuda.current_stream(p.device).synchronize()   # what produced the records (and .contiguous()) has finished; the copy's stream is not torch's
+    counts = np.ascontiguousarray(range_counts, dtype=np.int32).ravel()
+    ir = np.arange(len(counts), dtype=np.int32) if inst_range is None else np.ascontiguousarray(inst_range, dtype=np.int32).ravel()
+    b = None if instances is None else np.ascontiguousarray(instances, dtype=_lib.BVHInstance)
+    if b is not None and len(b) != len(ir):
+        raise ValueError(f"{len(b)} instance records for {len(ir)} instances")
+    shape = np.zeros((), dtype=_lib.SceneShape)
+    shape["nRanges"], shape["rangeCount"] = len(counts), counts.ctypes.data
+    shape["nBlas"], shape["instRange"] = len(ir), ir.ctypes.data
+    shape["blas"] = 0 if b is None else b.ctypes.data
+    opts = build_options(alpha=alpha, **lbvh_options)
+    st = np.zeros((), dtype=_lib.RebuildStats)
+    return (pp, n, _lib.ptr(shape), which, _lib.ptr(opts), _lib.ptr(st)), (p, counts, ir, b, shape, opts), st
+
+
 class Device:
     def __init__(self, width, height, y0=0, y1=None, shading=_lib.SHADING_NEE, sampling=_lib.SAMPLING_COSINE,
                  accel=_lib.ACCEL_BVH2, russian_roulette=True, filter_fireflies=True, max_bounces=_lib.MAX_BOUNCES,
@@ -148,6 +178,17 @@ class Device:
             raise e
         return _rebuild_dict(st)
 
+    def resize_scene(self, prims, range_counts, inst_range=None, instances=None, builder="sah", alpha=None, **lbvh_options):
+        """Give the bound scene a new shape in place on the GPU (rt_resize_scene): `prims` is the whole new primitive array - a numpy
+        array, or a torch tensor on the context's GPU, which is used where it lies (torch's current stream is waited for first) - with free objType / matIdx (the materials and
+        textures stay as bound); range_counts[k] primitives, back to back, form BLAS k; inst_range[i] is the BLAS instance i renders
+        (None: one instance per BLAS) under instances[i]["invT"] (None: the identity).  The light list, every BLAS (builder "sah",
+        "lbvh" or "sbvh_gpu" as for rebuild_scene), the derived arrays and the TLAS are made on the device; every context holding
+        the scene sees the new one.  Returns the stats; a refusal raises RtError (.code) and leaves the scene as it was."""
+        args, keep, st = _resize_args(prims, range_counts, inst_range, instances, builder, lbvh_options, alpha)
+        self._chk_code(self._lib.rt_resize_scene(self._h, *args))
+        return _rebuild_dict(st)
+
     def refit_info(self):
         """The last successful rebuild_scene(builder="refit") of the bound scene copy (rt_refit_info): path (0 none yet, 1 in place,
         2 re-collapsed because changed_nodes > 0, 3 re-collapsed because RT355_REFIT_RECOLLAPSE=1 forced it), live_quads,
@@ -164,7 +205,7 @@ class Device:
 
     def scene_array(self, name):
         """A device array of the bound scene as raw bytes (rt_debug_get_scene_array; names: _lib.SCENE_ARRAYS, _lib.SCENE_ARRAYS_BVH4)."""
-        which = _lib.SCENE_ARRAYS[name] if name in _lib.SCENE_ARRAYS else _lib.SCENE_ARRAYS_BVH4[name]
+        which = {**_lib.SCENE_ARRAYS, **_lib.SCENE_ARRAYS_BVH4, **_lib.SCENE_ARRAYS_RESIZE}[name]
         n = C.c_int64(0)
         self._chk(self._lib.rt_debug_get_scene_array(self._h, which, None, 0, C.byref(n)))
         out = np.zeros(n.value, dtype=np.uint8)
@@ -503,6 +544,16 @@ class Group:
         """Device.rebuild_scene for the group's scene copy (rt_group_rebuild_scene): every lane sees the rebuilt scene."""
         args, keep, st = _rebuild_args(prims, first, instances, builder, lbvh_options, alpha)
         rc = self._lib.rt_group_rebuild_scene(self._h, *args)
+        if rc != 0:
+            e = RtError(self._lib.rt_last_error().decode())
+            e.code = rc
+            raise e
+        return _rebuild_dict(st)
+
+    def resize_scene(self, prims, range_counts, inst_range=None, instances=None, builder="sah", alpha=None, **lbvh_options):
+        """Device.resize_scene for the group's scene copy (rt_group_resize_scene): every lane sees the new shape."""
+        args, keep, st = _resize_args(prims, range_counts, inst_range, instances, builder, lbvh_options, alpha)
+        rc = self._lib.rt_group_resize_scene(self._h, *args)
         if rc != 0:
             e = RtError(self._lib.rt_last_error().decode())
             e.code = rc

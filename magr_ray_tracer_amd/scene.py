@@ -233,6 +233,13 @@ class Scene:
     def SetInstanceTransform(self, blas, invT):
         self._chk(self._lib.rth_set_instance_transform(self._h, int(blas), _lib.fvec(np.asarray(invT, dtype=np.float32).ravel())))
 
+    def AddInstance(self, blas, invT=None):
+        """A further instance of the BLAS that instance `blas` renders (rth_add_instance), under invT (16 floats, row-major; None: the
+        identity): the new record carries that BLAS's root, and the next BuildTLAS() / arrays() gives its TLAS leaf the bounds every
+        instance's gets.  Returns the new instance's index."""
+        t = None if invT is None else _lib.fvec(np.asarray(invT, dtype=np.float32).ravel())
+        return self._chk(self._lib.rth_add_instance(self._h, int(blas), t))
+
     def stats(self):
         u = np.zeros(5, dtype=np.uint32)
         f = np.zeros(2, dtype=np.float32)
@@ -271,6 +278,19 @@ def build_options(max_leaf=None, cost_traverse=None, cost_intersect=None, alpha=
     o["cost_intersect"] = LBVH_DEFAULTS["cost_intersect"] if cost_intersect is None else float(cost_intersect)
     o["alpha"] = 0.0 if alpha is None else float(alpha)
     return o
+
+
+def light_list(prims, mats):
+    """The light list rt_resize_scene derives for `prims` under the materials `mats` (rth_light_list, csrc/resize_common.h): the indices,
+    in increasing order, of the primitives whose material is a light."""
+    lib = _lib.host_lib()
+    p = np.ascontiguousarray(prims, dtype=_lib.Primitive)
+    m = np.ascontiguousarray(mats, dtype=_lib.Material)
+    out = np.zeros(max(len(p), 1), np.uint32)
+    n = lib.rth_light_list(_lib.ptr(p), len(p), _lib.ptr(m), len(m), _lib.ptr(out))
+    if n < 0:
+        raise BuildError(n, lib.rth_last_error().decode())
+    return out[:n].copy()
 
 
 REBUILD_BUILDERS = {"sah": _lib.REBUILD_SAH, "lbvh": _lib.REBUILD_LBVH, "sbvh_gpu": _lib.REBUILD_SBVH, "refit": _lib.REBUILD_REFIT}
