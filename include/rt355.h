@@ -409,7 +409,8 @@ int rt_rebuild_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t first, int32_
  *                     finds no partner, new trees that would change the derived layout), and a bound scene whose BLAS ranges do not
  *                     tile [0, nPrims) without gaps;
  *   RT_E_NOMEM        as for rebuilds (a later call takes the allocation up where it stopped).
- * Deliberately not followed: materials and textures, more than 256 instances, a change of the derived layout, copies without a BVH2. */
+ * Deliberately not followed: more than 256 instances, a change of the derived layout, copies without a BVH2.  (Materials and textures
+ * change through rt_update_materials, below; a resize checks matIdx and flags its lights against the table that is bound then.) */
 typedef struct RtSceneShape {
     int32_t nRanges;              /* distinct BLAS, >= 1 */
     const int32_t* rangeCount;    /* HOST, nRanges entries, each >= 1, sum == nPrims: BLAS k covers primitives
@@ -423,6 +424,57 @@ int rt_resize_scene(RtCtx* ctx, const void* prims, int32_t nPrims, const RtScene
 /* The checks of rt_resize_scene that need neither a device nor a bound scene: nPrims, the shape, the builder and opts.  RT_OK, or
  * RT_E_INVALID with the message rt_resize_scene would give. */
 int rt_resize_check(int32_t nPrims, const RtSceneShape* shape, int32_t builder, const RtBuildOptions* opts);
+/* ---- in-place material updates (a bound scene changes its materials, its texture atlas and its primitives' matIdx on the device) ------
+ * A lamp switched on, a recoloured object, a video texture played from a device buffer, a repainted part of a mesh: no tree changes and
+ * a few hundred bytes do.  The three parts of an update are independent; a part whose pointer is NULL stays as bound, and a call with
+ * all three absent succeeds and touches nothing.
+ *   mats     the whole new table (HOST), checked as rt_upload_scene checks it against the atlas length that will be bound;
+ *   texels   RtFloat4[texCount] in host memory or memory the context's GPU reaches (rt_resize_scene's pointer rule; the copy runs on the
+ *            scene copy's own stream, so device work that produces them must be complete): they replace [texFirst, texFirst + texCount)
+ *            of the NEW atlas, whose length is nTexels (-1: as bound).  Texels [0, min(old, new)) are kept, [old, new) are zero;
+ *   primMat  int32[primCount], host or device-reachable: the new matIdx of primitives [primFirst, primFirst + primCount).
+ * The light list depends on the materials (the indices of the primitives whose material has isLight != 0, in increasing order) and a
+ * light record carries its material's emittance, so with mats or primMat given the call re-derives both on the device by the pipeline of
+ * rt_resize_scene: k_mat_flags (one thread per primitive: matIdx from the new assignment inside the range, from the bound primitive
+ * outside; a value outside [0, nMats) of the new table is refused through atomicMin of the lowest index; the light flag), an exclusive
+ * scan, k_mat_emit (the list and the complete 8-row records, from the same matIdx source).  All of that is staged in memory no holder
+ * reads.  Only then the holders' streams are waited for and the commit writes what is patched in place - k_mat_assign writes
+ * prims[i].matIdx and the shade record, the texel range goes into the atlas, the pad behind it is zeroed - and swaps the table, the
+ * light list, the light records, the atlas (when it had to grow) and the counts.  With only texels given the light list and the light
+ * records stay exactly as bound (a caller's odd but legal list too).  Afterwards every array rt_debug_get_scene_array returns
+ * (RT_SCENE_MATERIALS and RT_SCENE_TEXTURES included), sizes too, is bit for bit that of a fresh rt_upload_scene (a BVH4 copy that keeps
+ * its BVH2: rt_upload_scene_bvh2) of the bound primitives with the new matIdx values, the new table and atlas, that light list and the
+ * bound trees, TLAS and instances; rt_kernel_info and rt_shade_tables of every holder equal the fresh context's (the staged tables of
+ * k_shade follow the new counts).  Synchronous; accumulators, seeds, counters and queues are not touched.  Works on every bound scene,
+ * whatever rt_update_scene or rt_rebuild_scene answer for it; those, rt_resize_scene, rt_trace, rt_share_scene and further material
+ * updates work on the result and check against the new table.
+ * Memory: the table, the light list and the light records exist twice (the set that is not live is written, the commit swaps); an atlas
+ * that outgrows its array moves to one of the need plus a quarter, the replaced one freed at once; every allocation is counted by
+ * rt_debug_rebuild_allocations, and a scene that alternates between two material states stops allocating by the third visit to each.
+ * Refusals change nothing:
+ *   RT_E_INVALID   a null context or update, no scene bound; mats with nMats <= 0; a texture window outside the new atlas (with mats
+ *                  NULL the bound table is checked against a shrinking atlas); nTexels < -1; a negative first or count; a range
+ *                  outside the new atlas or the primitives; a count above zero with a null pointer (an absent part has count 0); a
+ *                  pointer that is neither host memory nor reachable from the context's device for that many elements.  Found on
+ *                  the device: the primitive of lowest index whose matIdx lies outside the new table (the message gives the index,
+ *                  the value and nMats);
+ *   RT_E_NOMEM     device memory (a later call takes the allocation up where it stopped).
+ * stats (may be NULL): gpu_ms the staging and the commit on the device, wall_ms the call; mats, texels, prims: records written; lights:
+ * the light count afterwards; tables_staged_changed: k_shade of this context serves its tables from LDS now and did not before, or the
+ * reverse; atlas_reallocated: the atlas moved to a new array. */
+typedef struct RtMaterialUpdate {
+    const RtMaterial* mats; int32_t nMats;   /* HOST. The whole new table; NULL: the table stays (nMats ignored)            */
+    const void* texels;                      /* RtFloat4[texCount], host or device-reachable; NULL: no texel is written     */
+    int32_t texFirst, texCount;              /* the texels replace [texFirst, texFirst + texCount) of the NEW atlas           */
+    int32_t nTexels;                         /* length of the atlas afterwards; -1: as bound                                  */
+    const void* primMat;                     /* int32[primCount], host or device-reachable; NULL: the assignment stays        */
+    int32_t primFirst, primCount;
+} RtMaterialUpdate;
+typedef struct RtMaterialStats { double gpu_ms, wall_ms; int32_t mats, texels, prims, lights, tables_staged_changed, atlas_reallocated, reserved[2]; } RtMaterialStats;
+int rt_update_materials(RtCtx* ctx, const RtMaterialUpdate* update, RtMaterialStats* stats);
+/* The checks of a material table that need no device: validate_scene's material loop against an atlas of nTexels texels.  RT_OK, or
+ * RT_E_INVALID with the message rt_update_materials would give. */
+int rt_materials_check(const RtMaterial* mats, int32_t nMats, int32_t nTexels);
 /* The last successful RT_REBUILD_REFIT of the context's scene copy.  path: 0 no such call yet; 1 the records were rewritten in place
  * (a BVH2 context always reports 1, with live_quads 0); 2 re-collapsed because changed_nodes live records changed a slot; 3
  * re-collapsed because RT355_REFIT_RECOLLAPSE=1 forced it.  live_quads: the live BVH4 nodes afterwards; stack_need: the traversal's
@@ -430,8 +482,8 @@ int rt_resize_check(int32_t nPrims, const RtSceneShape* shape, int32_t builder, 
  * when no scene is bound. */
 typedef struct RtRefitInfo { int32_t path, live_quads, changed_nodes, stack_need; } RtRefitInfo;
 int rt_refit_info(RtCtx* ctx, RtRefitInfo* out);
-/* Device allocations (hipMalloc calls) that rt_update_scene and rt_rebuild_scene have made for the context's scene copy so far, the
- * SBVH builder's included: a test can see that a repeated rebuild has stopped allocating. */
+/* Device allocations (hipMalloc calls) that rt_update_scene, rt_rebuild_scene, rt_resize_scene and rt_update_materials have made for the
+ * context's scene copy so far, the SBVH builder's included: a test can see that a repeated rebuild has stopped allocating. */
 int rt_debug_rebuild_allocations(RtCtx* ctx, int64_t* count);
 /* The primitive range [first, first + count) of every instance's BLAS in wire arrays, as rt_upload_scene finds them for
  * rt_rebuild_scene (csrc/rebuild_common.h); firstOut / countOut hold nBlas entries (either may be NULL).  RT_E_UNSUPPORTED with the
@@ -455,6 +507,8 @@ int rt_blas_ranges(const RtBVHNode2* nodes, int32_t nNodes, const uint32_t* prim
 #define RT_SCENE_ROOT_ENTRY   12   /* layout-1 root entry per instance                      */
 #define RT_SCENE_BVH2_KEPT    13   /* the BVH2 a BVH4 copy keeps (rt_upload_scene_bvh2); 0 bytes when the copy holds none */
 #define RT_SCENE_LIGHTS       14   /* the light list: uint32 indices of the light primitives, increasing   */
+#define RT_SCENE_MATERIALS    15   /* RtMaterial[nMats]                                                    */
+#define RT_SCENE_TEXTURES     16   /* RtFloat4[nTexels + texPad], the pad included (zero)                  */
 int rt_debug_get_scene_array(RtCtx* ctx, int32_t which, void* out, int64_t capacityBytes, int64_t* bytes);
 
 /* ---- lanes: one accumulation as several interleaved sample streams behind one handle -------------------------------------------
@@ -503,6 +557,7 @@ int rt_group_rebuild_scene(RtGroup* g, const RtPrimitive* prims, int32_t first, 
                            int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats);   /* rt_rebuild_scene for the group's copy */
 int rt_group_resize_scene(RtGroup* g, const void* prims, int32_t nPrims, const RtSceneShape* shape, int32_t builder, const RtBuildOptions* opts,
                           RtRebuildStats* stats);                            /* rt_resize_scene for the group's copy (all lanes)        */
+int rt_group_update_materials(RtGroup* g, const RtMaterialUpdate* update, RtMaterialStats* stats);   /* rt_update_materials, likewise  */
 int rt_group_seed(RtGroup* g, uint64_t firstStream);                         /* a single Renderer: 0 (what rt_group_create leaves);
                                                                               * rank r of a sample split: r*lanes                       */
 int rt_group_reset(RtGroup* g);                                              /* resetKernel on every lane; frames = 0                   */

@@ -124,6 +124,18 @@ int rth_add_instance(RthScene* s, int blas, const float invT[16]);
  * indices, in increasing order, of the primitives whose material has isLight != 0.  out needs room for nPrims entries; returns the
  * count, or RT_E_INVALID for a missing array or the first primitive whose objType / matIdx is out of range (rth_last_error() names it). */
 int rth_light_list(const RtPrimitive* prims, int32_t nPrims, const RtMaterial* mats, int32_t nMats, uint32_t* out);
+/* The host restatement of rt_update_materials (rt355.h), one call per part, with the same checks (csrc/resize_common.h):
+ *   rth_set_materials       replaces the whole table; every texture window must lie inside the atlas and every primitive's matIdx
+ *                           inside the new table (names of materials the new table drops are forgotten);
+ *   rth_set_texels          gives the atlas nTexels texels (-1: as it is; kept texels stay, new ones are zero; the table must still fit)
+ *                           and writes texels[count] at [first, first + count) (texels NULL: nothing is written);
+ *   rth_set_prim_materials  writes matIdx[count] into primitives [first, first + count), each inside the table.
+ * Afterwards the scene's light list is the Scene rule's for the new state (the indices, in increasing order, of the primitives whose
+ * material has isLight != 0); the trees are not touched.  Each returns RT_E_INVALID (rth_last_error() has the reason) and changes nothing
+ * when it refuses. */
+int rth_set_materials(RthScene* s, const RtMaterial* mats, int32_t nMats);
+int rth_set_texels(RthScene* s, const RtFloat4* texels, int32_t first, int32_t count, int32_t nTexels);
+int rth_set_prim_materials(RthScene* s, int32_t first, int32_t count, const int32_t* matIdx);
 
 /* Borrowed views of the arrays (valid until the scene changes). */
 const RtPrimitive*   rth_primitives(RthScene* s, int* n);

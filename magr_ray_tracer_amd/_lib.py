@@ -98,6 +98,15 @@ SCENE_ARRAYS = {"prims": 0, "bvh": 1, "tlas": 2, "instances": 3, "pairs": 4, "tr
 SCENE_ARRAYS_BVH4 = {"quads": 11, "rootEntry": 12, "bvh2Kept": 13}
 # ... and the light list (uint32 primitive indices), which rt_resize_scene derives on the device
 SCENE_ARRAYS_RESIZE = {"lights": 14}
+# ... and the two rt_update_materials changes: the material table (Material records) and the atlas with its zero pad (float4 texels)
+SCENE_ARRAYS_MATERIALS = {"materials": 15, "textures": 16}
+MaterialUpdate = np.dtype([("mats", "<u8"), ("nMats", "<i4"), ("_pad0", "<i4"), ("texels", "<u8"), ("texFirst", "<i4"), ("texCount", "<i4"),
+                           ("nTexels", "<i4"), ("_pad1", "<i4"), ("primMat", "<u8"), ("primFirst", "<i4"), ("primCount", "<i4")])   # RtMaterialUpdate
+assert MaterialUpdate.itemsize == 56
+MaterialStats = np.dtype([("gpu_ms", "<f8"), ("wall_ms", "<f8")] +
+                         [(n, "<i4") for n in ("mats", "texels", "prims", "lights", "tables_staged_changed", "atlas_reallocated")] +
+                         [("reserved", "<i4", 2)])   # RtMaterialStats
+assert MaterialStats.itemsize == 48
 SceneShape = np.dtype([("nRanges", "<i4"), ("_pad0", "<i4"), ("rangeCount", "<u8"), ("nBlas", "<i4"), ("_pad1", "<i4"), ("instRange", "<u8"),
                        ("blas", "<u8")])   # RtSceneShape
 assert SceneShape.itemsize == 40
@@ -125,7 +134,8 @@ DEVICE_SYMBOLS = [
     "rt_build_bvh4", "rt_upload_scene_bvh2", "rt_group_upload_scene_bvh2",
     "rt_group_create", "rt_group_destroy", "rt_group_lanes", "rt_group_concurrency", "rt_group_stream_class", "rt_group_class_concurrency", "rt_group_lane", "rt_group_frames", "rt_group_upload_scene", "rt_group_share_scene",
     "rt_group_seed", "rt_group_reset", "rt_group_render", "rt_group_synchronize", "rt_group_sum", "rt_group_read_accum", "rt_group_focus",
-    "rt_group_postproc", "rt_trace", "rt_trace_window", "rt_resize_scene", "rt_group_resize_scene", "rt_resize_check"]
+    "rt_group_postproc", "rt_trace", "rt_trace_window", "rt_resize_scene", "rt_group_resize_scene", "rt_resize_check",
+    "rt_update_materials", "rt_group_update_materials", "rt_materials_check"]
 HOST_SYMBOLS = [
     "rth_last_error", "rth_scene_create", "rth_scene_destroy", "rth_add_material", "rth_add_texture", "rth_load_texture", "rth_add_sphere",
     "rth_add_plane", "rth_add_triangle", "rth_add_quad", "rth_add_triangles", "rth_build_blas", "rth_build_bvh4",
@@ -136,7 +146,8 @@ HOST_SYMBOLS = [
     "rth_set_build_threads", "rth_renderer_save_frame", "rth_renderer_camera_move", "rth_renderer_camera_mouse", "rth_renderer_camera_zoom", "rth_renderer_frames", "rth_renderer_set_lanes", "rth_renderer_set_builtins", "rth_renderer_builtins",
     "rth_build_blas_lbvh", "rth_build_bvh2_lbvh", "rth_lbvh_stats", "rth_set_primitives", "rth_refit",
     "rth_build_blas_sah_gpu", "rth_build_bvh2_sah", "rth_build_blas_sbvh_gpu", "rth_build_bvh2_sbvh", "rth_rebuild", "rth_blas_ranges",
-    "rth_build_bvh4_gpu", "rth_build_bvh4_levels", "rth_bvh4_refit", "rth_refit_bvh4", "rth_add_instance", "rth_light_list"]
+    "rth_build_bvh4_gpu", "rth_build_bvh4_levels", "rth_bvh4_refit", "rth_refit_bvh4", "rth_add_instance", "rth_light_list",
+    "rth_set_materials", "rth_set_texels", "rth_set_prim_materials"]
 
 _dev = None
 _host = None
@@ -243,6 +254,9 @@ def _bind_device(lib):
         lib.rt_resize_scene.argtypes = [vp, vp, i32, vp, i32, vp, vp]
         lib.rt_group_resize_scene.argtypes = [vp, vp, i32, vp, i32, vp, vp]
         lib.rt_resize_check.argtypes = [i32, vp, i32, vp]
+        lib.rt_update_materials.argtypes = [vp, vp, vp]
+        lib.rt_group_update_materials.argtypes = [vp, vp, vp]
+        lib.rt_materials_check.argtypes = [vp, i32, i32]
         lib.rt_refit_info.argtypes = [vp, vp]
         lib.rt_blas_ranges.argtypes = [vp, i32, vp, i32, i32, vp, i32, vp, vp]
         lib.rt_group_create.argtypes = [vp, i32, C.POINTER(vp)]
@@ -312,6 +326,9 @@ def host_lib():
         lib.rth_set_instance_transform.argtypes = [vp, i32, fp]
         lib.rth_add_instance.argtypes = [vp, i32, fp]
         lib.rth_light_list.argtypes = [vp, C.c_int32, vp, C.c_int32, vp]
+        lib.rth_set_materials.argtypes = [vp, vp, C.c_int32]
+        lib.rth_set_texels.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32]
+        lib.rth_set_prim_materials.argtypes = [vp, C.c_int32, C.c_int32, vp]
         for n in ("rth_primitives", "rth_materials", "rth_textures", "rth_lights", "rth_bvh2_nodes", "rth_bvh4_nodes",
                   "rth_prim_idx", "rth_tlas_nodes", "rth_blas_nodes"):
             getattr(lib, n).argtypes = [vp, C.POINTER(i32)]

@@ -330,6 +330,11 @@ extern "C" int rt_group_resize_scene(RtGroup* g, const void* prims, int32_t nPri
     if (!g) return fail(RT_E_INVALID, "rt_group_resize_scene: null group");
     return rt_resize_scene(rt_group_lane(g, 0), prims, nPrims, shape, builder, opts, stats);   // every lane holds lane 0's copy
 }
+extern "C" int rt_group_update_materials(RtGroup* g, const RtMaterialUpdate* update, RtMaterialStats* stats)
+{
+    if (!g) return fail(RT_E_INVALID, "rt_group_update_materials: null group");
+    return rt_update_materials(rt_group_lane(g, 0), update, stats);   // every lane holds lane 0's copy
+}
 
 // Lane m renders sample stream `firstStream + m`: its seeds are outputs (firstStream + m) * W*H + firstPixel + i + 1 of the reference's
 // host xorshift32 stream (renderer.cpp:195-196).  A single Renderer has firstStream 0; rank r of a sample-partitioned job r * lanes.

@@ -16,6 +16,11 @@
 //   k_resize_check  one thread per primitive: objType / matIdx in range (the lowest refused index through atomicMin), the packed pair the
 //                   host keeps as its shadow, the light flag; a scan ranks the flags
 //   k_light_emit    one thread per primitive: a light writes its index and its complete light record at its rank
+// rt_update_materials runs the same pipeline over the bound primitives under a new table and a new assignment of matIdx values:
+//   k_mat_flags     one thread per primitive: its matIdx afterwards (resize::new_mat) in range of the new table (the lowest refused index
+//                   through atomicMin), the light flag; a scan ranks the flags
+//   k_mat_emit      k_light_emit with that matIdx
+//   k_mat_assign    the commit, one thread per primitive of the range: matIdx and the shade record of the patched primitive
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include "../../include/rt355.h"
@@ -207,6 +212,62 @@ hipError_t light_emit(hipStream_t s, const Work& w, const RtPrimitive* prims, ui
 {
     if (nLights == 0) return hipMemsetAsync(lightRecs, 0, sizeof(RtFloat4) * 8, s);   // one zero record, as at upload
     hipLaunchKernelGGL(k_light_emit, grid(nPrims), dim3(kBlock), 0, s, prims, nPrims, mats, w.flags, w.ranks, nLights, lights, lightRecs);
+    return hipGetLastError();
+}
+
+// ---- rt_update_materials: the light flags, the light list and the light records under a new table and a new assignment; the commit's
+// patch of the live primitives (rules: resize_common.h) -------------------------------------------------------------------------------
+__global__ void __launch_bounds__(kBlock) k_mat_flags(const RtPrimitive* prims, uint32_t nPrims, const int32_t* assign, uint32_t first, uint32_t count,
+                                                      const RtMaterial* mats, int32_t nMats, uint32_t* flags, uint32_t* bad)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= nPrims) return;
+    const int32_t mat = resize::new_mat(prims, i, assign, first, count);
+    const bool ok = mat >= 0 && mat < nMats;
+    flags[i] = ok ? resize::light_flag(mats, mat) : 0u;   // (a refused value's material is never read)
+    if (!ok) atomicMin(bad, i);   // a value, not a position
+}
+__global__ void __launch_bounds__(kBlock) k_mat_emit(const RtPrimitive* prims, uint32_t nPrims, const int32_t* assign, uint32_t first, uint32_t count,
+                                                     const RtMaterial* mats, const uint32_t* flags, const uint32_t* ranks, uint32_t nLights,
+                                                     uint32_t* lights, RtFloat4* lightRecs)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= nPrims || !flags[i]) return;   // (a flag is set only where the matIdx passed k_mat_flags' check)
+    const uint32_t r = ranks[i];
+    if (r >= nLights) return;   // (the host sized both arrays from this scan: never taken)
+    lights[r] = i;
+    resize::light_record_as(prims[i], resize::new_mat(prims, i, assign, first, count), mats, lightRecs + (size_t)r * 8);
+}
+__global__ void __launch_bounds__(kBlock) k_mat_assign(RtPrimitive* prims, const int32_t* assign, uint32_t first, uint32_t count, RtFloat4* shadeRecs)
+{
+    const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
+    if (k >= count) return;
+    RtPrimitive& p = prims[first + k];
+    p.matIdx = assign[k];
+    shadeRecs[first + k] = refit::shade_rec(p);   // the one rule, of the patched record
+}
+
+hipError_t mat_flags(hipStream_t s, const Work& w, const RtPrimitive* prims, uint32_t nPrims, const int32_t* assign, uint32_t first, uint32_t count,
+                     const RtMaterial* mats, int32_t nMats, uint32_t* bad)
+{
+    hipError_t e = hipMemsetAsync(bad, 0xff, sizeof(uint32_t), s);   // resize::kNoBad
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_mat_flags, grid(nPrims), dim3(kBlock), 0, s, prims, nPrims, assign, first, count, mats, nMats, w.flags, bad);
+    size_t scanBytes = w.scanBytes;
+    e = hipcub::DeviceScan::ExclusiveSum(w.scan, scanBytes, w.flags, w.ranks, (int)nPrims, s);
+    return e != hipSuccess ? e : hipGetLastError();
+}
+hipError_t mat_emit(hipStream_t s, const Work& w, const RtPrimitive* prims, uint32_t nPrims, const int32_t* assign, uint32_t first, uint32_t count,
+                    const RtMaterial* mats, uint32_t nLights, uint32_t* lights, RtFloat4* lightRecs)
+{
+    if (nLights == 0) return hipMemsetAsync(lightRecs, 0, sizeof(RtFloat4) * 8, s);   // one zero record, as at upload
+    hipLaunchKernelGGL(k_mat_emit, grid(nPrims), dim3(kBlock), 0, s, prims, nPrims, assign, first, count, mats, w.flags, w.ranks, nLights, lights, lightRecs);
+    return hipGetLastError();
+}
+hipError_t mat_assign(hipStream_t s, RtPrimitive* prims, const int32_t* assign, uint32_t first, uint32_t count, RtFloat4* shadeRecs)
+{
+    if (count == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_mat_assign, grid(count), dim3(kBlock), 0, s, prims, assign, first, count, shadeRecs);
     return hipGetLastError();
 }
 

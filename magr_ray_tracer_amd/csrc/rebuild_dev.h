@@ -37,4 +37,17 @@ hipError_t resize_check(hipStream_t s, const Work& w, const RtPrimitive* prims, 
 hipError_t light_emit(hipStream_t s, const Work& w, const RtPrimitive* prims, uint32_t nPrims, const RtMaterial* mats, uint32_t nLights, uint32_t* lights,
                       RtFloat4* lightRecs);
 
+
+// rt_update_materials (rules: resize_common.h), over the bound primitives.  assign (NULL: none) holds the new matIdx of primitives
+// [first, first + count); every other primitive keeps its own (resize::new_mat: the one source of all three kernels).
+// mat_flags: k_mat_flags writes per primitive the light flag under the table mats[nMats] (w.flags) and puts the lowest index whose matIdx
+//   lies outside that table into *bad (atomicMin: a value, never a position; kNoBad when none); an exclusive scan ranks the flags (w.ranks)
+// mat_emit: k_mat_emit scatters lights[rank] = i and writes the complete 8-row light record at that rank
+// mat_assign (the commit, on live arrays): k_mat_assign writes prims[i].matIdx and shadeRecs[i] (refit::shade_rec of the patched record)
+hipError_t mat_flags(hipStream_t s, const Work& w, const RtPrimitive* prims, uint32_t nPrims, const int32_t* assign, uint32_t first, uint32_t count,
+                     const RtMaterial* mats, int32_t nMats, uint32_t* bad);
+hipError_t mat_emit(hipStream_t s, const Work& w, const RtPrimitive* prims, uint32_t nPrims, const int32_t* assign, uint32_t first, uint32_t count,
+                    const RtMaterial* mats, uint32_t nLights, uint32_t* lights, RtFloat4* lightRecs);
+hipError_t mat_assign(hipStream_t s, RtPrimitive* prims, const int32_t* assign, uint32_t first, uint32_t count, RtFloat4* shadeRecs);
+
 } // namespace rebuilddev

@@ -25,6 +25,30 @@ LB_HD void light_record(const RtPrimitive& p, const RtMaterial* mats, RtFloat4* 
     r[5] = mats[p.matIdx].emittance;
     r[6] = r[7] = refit::f4(0, 0, 0, 0);
 }
+// ... of a primitive that rt_update_materials is about to give the material matIdx (its own matIdx is stale until the commit)
+LB_HD void light_record_as(const RtPrimitive& p, int32_t matIdx, const RtMaterial* mats, RtFloat4* r)
+{
+    refit::light_rec(p, r);
+    r[5] = mats[matIdx].emittance;
+    r[6] = r[7] = refit::f4(0, 0, 0, 0);
+}
+// rt_update_materials: the matIdx primitive i has after the call - assign[i - first] inside [first, first + count), the bound one outside
+LB_HD int32_t new_mat(const RtPrimitive* prims, uint32_t i, const int32_t* assign, uint32_t first, uint32_t count)
+{
+    return assign && i - first < count ? assign[i - first] : prims[i].matIdx;   // (i < first wraps past count)
+}
+// validate_scene's rule for a material table against an atlas of nTexels texels: -1, or the first material whose texture window is not
+// inside it; texPad receives the atlas pad (max(2, texW + 2) over the textured materials)
+inline int32_t check_materials(const RtMaterial* mats, int32_t nMats, int64_t nTexels, int64_t* texPad)
+{
+    int64_t pad = 2;   // the reference's lookup can land one row + one texel past a texture (uv == 1)
+    for (int32_t i = 0; i < nMats; i++) if (mats[i].texIdx != -1) {
+        if (mats[i].texIdx < 0 || mats[i].texW <= 0 || mats[i].texH <= 0 || (int64_t)mats[i].texIdx + (int64_t)mats[i].texW * mats[i].texH > nTexels) return i;
+        pad = pad > (int64_t)mats[i].texW + 2 ? pad : (int64_t)mats[i].texW + 2;
+    }
+    if (texPad) *texPad = pad;
+    return -1;
+}
 
 // ---- host only ----
 // The light list of prims[nPrims] on the host (every record must have passed prim_ok)

@@ -610,7 +610,7 @@ static int configure_traversal(RtCtx* ctx)
         if (bvh4_tlas_trav(ctx) || ctx->tuneConnect.topLevels > 0) { if (const int rc = persist_query(ctx, ST_CONNECT, -1, &perCUc)) return rc; }
         ctx->persistGrid = std::min(ctx->gridMax, persist_blocks(ctx, ST_EXTEND, perCU, tuneBlocks) * prop.multiProcessorCount);
         ctx->persistGridConnect = std::min(ctx->gridMax, persist_blocks(ctx, ST_CONNECT, perCUc, tuneBlocks) * prop.multiProcessorCount);
-    }
+    } else ctx->persistGrid = ctx->persistGridConnect = 0;   // (a resize took the persistent kernels away: rt_kernel_info reports what a fresh context does)
     ctx->q.spill = nullptr; ctx->q.spillStride = 0; ctx->q.stackCap = 0;
     ctx->q.tlasLdsEntries = tlas_trav(ctx) ? (uint32_t)tlas_lds_entries(ctx) : 0u;
     if (spill_trav(ctx)) {   // every SPILL launch runs on a persistent grid (bounce 0 too), so the global columns are bounded by the grids
@@ -772,6 +772,22 @@ extern "C" int rt_resize_scene(RtCtx* ctx, const void* prims, int32_t nPrims, co
         return fail(RT_E_UNSUPPORTED, "rt_resize_scene: a BVH4 copy bound through rt_upload_scene has lost its BVH2 and cannot be rebuilt in place "
                     "(bind the BVH2 with rt_upload_scene_bvh2, or build on the host and upload)");
     return resize_scene(*ctx->scene, prims, nPrims, shape, builder, opts, stats);
+}
+extern "C" int rt_update_materials(RtCtx* ctx, const RtMaterialUpdate* update, RtMaterialStats* stats)
+{
+    if (!ctx || !update) return fail(RT_E_INVALID, "rt_update_materials: null argument (context and update are required)");
+    if (!ctx->sceneLoaded || !ctx->scene) return fail(RT_E_INVALID, "rt_update_materials: no scene uploaded");
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    // rt_resize_scene's pointer rule: both arrays are copied, not followed by a kernel, so host memory passes as well
+    if (update->texels && update->texCount > 0)
+        if (const int rc = device_pointer(ctx, "rt_update_materials", "texels", update->texels, (int64_t)sizeof(RtFloat4) * update->texCount, 4, true)) return rc;
+    if (update->primMat && update->primCount > 0)
+        if (const int rc = device_pointer(ctx, "rt_update_materials", "primMat", update->primMat, (int64_t)sizeof(int32_t) * update->primCount, 4, true)) return rc;
+    SceneBag& b = *ctx->scene;
+    const bool stagedBefore = ctx->var.shadeTables != 0 && shade_tables_fit(b.sc.nLights, b.sc.nMats);
+    if (const int rc = update_materials(b, *update, stats)) return rc;
+    if (stats) stats->tables_staged_changed = (ctx->var.shadeTables != 0 && shade_tables_fit(b.sc.nLights, b.sc.nMats)) != stagedBefore ? 1 : 0;   // k_shade's own rule
+    return RT_OK;
 }
 extern "C" int rt_refit_info(RtCtx* ctx, RtRefitInfo* out)
 {

@@ -66,12 +66,8 @@ int scenedev::validate_scene(int accel, const HostScene& in, int* stackEntriesOu
     for (int32_t i = 0; i < nIdx; i++) if (primIdx[i] >= (uint32_t)nPrims) return fail(RT_E_INVALID, "primIdx[%d] = %u out of range", i, primIdx[i]);
     for (int32_t i = 0; i < nLights; i++) if (lights[i] >= (uint32_t)nPrims) return fail(RT_E_INVALID, "lights[%d] out of range", i);
     int64_t texPad = 2; // the reference's lookup can land one row + one texel past a texture (uv == 1): pad the atlas
-    for (int32_t i = 0; i < nMats; i++) if (mats[i].texIdx != -1) {
-        if (mats[i].texIdx < 0 || mats[i].texW <= 0 || mats[i].texH <= 0 ||
-            (int64_t)mats[i].texIdx + (int64_t)mats[i].texW * mats[i].texH > (int64_t)nTexels)
-            return fail(RT_E_INVALID, "material %d: texture window exceeds the atlas", i);
-        texPad = std::max<int64_t>(texPad, (int64_t)mats[i].texW + 2);
-    }
+    if (const int32_t m = resize::check_materials(mats, nMats, nTexels, &texPad); m >= 0)   // (rt_update_materials holds a new table to the same rule)
+        return fail(RT_E_INVALID, "material %d: texture window exceeds the atlas", m);
     for (int32_t i = 0; i < nTlas; i++) {
         const uint32_t lr = tlas[i].leftRight;
         if (lr == 0) { if (tlas[i].BLASidx >= (uint32_t)nBlas) return fail(RT_E_INVALID, "tlas node %d: BLASidx out of range", i); }
@@ -328,6 +324,7 @@ int scenedev::upload_scene(SceneBag& b, int accel, int extendVariant, const Host
     sc.nLights = nLights; sc.nPrims = nPrims; sc.nBlas = nBlas; sc.nTex = nTexels; sc.nMats = nMats;
     // ---- bind: the copy's facts, and what updates and rebuilds need of this upload
     b.sc = sc;
+    b.hMats.assign(mats, mats + nMats); b.texPad = texPad; b.texCap = (size_t)nTexels + (size_t)texPad;   // (rt_update_materials)
     b.layout = layout; b.stackEntries = stackEntries; b.tlasDepth = tlasDepth; b.nInterior = (int)pairNode.size(); b.singleBlas = leafRoot;
     if (!blas4) b.nQuads = (int32_t)(quads.size() / 8);
     return prepare_update(b, accel, extendVariant, in, pairNode);
@@ -1050,6 +1047,137 @@ int scenedev::resize_scene(SceneBag& b, const void* prims, int32_t nPrims, const
     const Shape sh{ nPrims, shape->nBlas, 0, &ranges, &instBlas };
     return rebuild_body(b, who, sh, prims, nullptr, 0, 0, shape->blas, builder, opts, P, stats);
 }
+
+// ---- in-place material updates (rt_update_materials; kernels: rebuild.hip, rules: resize_common.h) -------------------------------------
+// validate_scene's checks of a material table against an atlas of nTexels texels, with its message; texPad receives the atlas pad
+static int materials_check(const char* who, const RtMaterial* mats, int32_t nMats, int64_t nTexels, int64_t* texPad)
+{
+    if (!mats || nMats <= 0) return fail(RT_E_INVALID, "%s: a material table holds at least one material (nMats %d)", who, nMats);
+    if (nTexels < 0) return fail(RT_E_INVALID, "%s: negative atlas length %lld", who, (long long)nTexels);
+    if (const int32_t m = resize::check_materials(mats, nMats, nTexels, texPad); m >= 0)
+        return fail(RT_E_INVALID, "material %d: texture window exceeds the atlas", m);
+    return RT_OK;
+}
+extern "C" int rt_materials_check(const RtMaterial* mats, int32_t nMats, int32_t nTexels)
+{
+    return materials_check("rt_materials_check", mats, nMats, nTexels, nullptr);
+}
+int scenedev::update_materials(SceneBag& b, const RtMaterialUpdate& u, RtMaterialStats* stats)
+{
+    using clock = std::chrono::steady_clock;
+    const char* who = "rt_update_materials";
+    const auto t0 = clock::now();
+    const SceneArrays& sc = b.sc;
+    // ---- refusals that need no device work: counts and ranges, then the table that will be bound against the atlas that will be bound
+    const bool newTable = u.mats != nullptr;
+    if (newTable && u.nMats <= 0) return fail(RT_E_INVALID, "%s: a material table holds at least one material (nMats %d)", who, u.nMats);
+    if (u.nTexels < -1) return fail(RT_E_INVALID, "%s: nTexels %d (the new atlas length, or -1 to keep the bound one)", who, u.nTexels);
+    if (u.texFirst < 0 || u.texCount < 0) return fail(RT_E_INVALID, "%s: negative texel range (first %d, count %d)", who, u.texFirst, u.texCount);
+    if (u.primFirst < 0 || u.primCount < 0) return fail(RT_E_INVALID, "%s: negative primitive range (first %d, count %d)", who, u.primFirst, u.primCount);
+    if (u.texCount > 0 && !u.texels) return fail(RT_E_INVALID, "%s: texCount %d but texels == NULL", who, u.texCount);
+    if (u.primCount > 0 && !u.primMat) return fail(RT_E_INVALID, "%s: primCount %d but primMat == NULL", who, u.primCount);
+    const int32_t oldTex = sc.nTex, nTex = u.nTexels < 0 ? sc.nTex : u.nTexels;
+    if (u.texels && (int64_t)u.texFirst + u.texCount > (int64_t)nTex)
+        return fail(RT_E_INVALID, "%s: texel range [%d, %lld) outside the new atlas of %d texels", who, u.texFirst, (long long)u.texFirst + u.texCount, nTex);
+    if (u.primMat && (int64_t)u.primFirst + u.primCount > (int64_t)b.nPrims)
+        return fail(RT_E_INVALID, "%s: primitive range [%d, %lld) outside the %d bound", who, u.primFirst, (long long)u.primFirst + u.primCount, b.nPrims);
+    const bool writeTex = u.texels && u.texCount > 0, assign = u.primMat && u.primCount > 0;
+    const int32_t nMats = newTable ? u.nMats : sc.nMats;
+    int64_t texPad = b.texPad;
+    if (newTable || nTex != oldTex)   // (mats NULL: the bound table, from its host shadow, against a new atlas length)
+        if (const int rc = materials_check(who, newTable ? u.mats : b.hMats.data(), nMats, nTex, &texPad)) return rc;
+    const bool lightsChange = newTable || assign, padChange = nTex != oldTex || texPad != b.texPad;
+    if (stats) { *stats = RtMaterialStats{}; stats->lights = b.nLights; }
+    if (!lightsChange && !writeTex && !padChange) return RT_OK;   // nothing to do: nothing is touched
+    HIPCHK(hipSetDevice(b.device));
+    if (!b.stream) HIPCHK(hipStreamCreateWithFlags(&b.stream, hipStreamNonBlocking));
+    for (hipEvent_t& e : b.rev) if (!e) HIPCHK(hipEventCreate(&e));
+    hipStream_t s = b.stream;
+    // ---- device memory: everything is made before anything is written (a call that ran out of memory is taken up where it stopped)
+    SceneBag::Grown<RtMaterial>& M = b.mmats[b.mmatsNext];
+    SceneBag::LightSet& L = b.mlights[b.mlightsNext];
+    SceneBag::Grown<RtFloat4>& T = b.mtex[b.mtexNext];
+    const size_t texNeed = (size_t)nTex + (size_t)texPad;
+    const bool moveTex = texNeed > b.texCap;
+    if (lightsChange) {
+        if (!b.rStatus) { if (const int rc = dalloc(b.allocs, &b.rStatus, 2)) return rc; b.rallocs++; }
+        if (const int rc = rebuild_scratch(b, (size_t)b.nPrims)) return rc;   // (flags and ranks: a word per primitive)
+        if (newTable) if (const int rc = rebuild_fit(b, M, (size_t)nMats, "the material table")) return rc;
+        if (assign) if (const int rc = rebuild_fit(b, b.mAssign, (size_t)u.primCount, "the new matIdx values")) return rc;
+    }
+    if (moveTex) if (const int rc = rebuild_fit(b, T, texNeed, "the texture atlas")) return rc;
+    // ---- stage, in memory no holder reads: the table, the new assignment (one path for host and device input), the light list and the
+    // complete light records under both; an atlas that has to move, whole
+    HIPCHK(hipEventRecord(b.rev[0], s));
+    int32_t nLights = b.nLights;
+    const int32_t* dAssign = nullptr;
+    if (lightsChange) {
+        const RtMaterial* dMats = sc.mats;
+        if (newTable) { HIPCHK(hipMemcpyAsync(M.p, u.mats, sizeof(RtMaterial) * (size_t)nMats, hipMemcpyHostToDevice, s)); dMats = M.p; }
+        if (assign) { HIPCHK(hipMemcpyAsync(b.mAssign.p, u.primMat, sizeof(int32_t) * (size_t)u.primCount, hipMemcpyDefault, s)); dAssign = b.mAssign.p; }
+        uint32_t* bad = (uint32_t*)b.rStatus;
+        const uint32_t first = (uint32_t)u.primFirst, count = assign ? (uint32_t)u.primCount : 0u;
+        HIPCHK(rebuilddev::mat_flags(s, b.dw, sc.prims, (uint32_t)b.nPrims, dAssign, first, count, dMats, nMats, bad));
+        uint32_t firstBad = resize::kNoBad, lastRank = 0, lastFlag = 0;
+        HIPCHK(hipMemcpyAsync(&firstBad, bad, sizeof firstBad, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&lastRank, b.dw.ranks + (b.nPrims - 1), sizeof lastRank, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(&lastFlag, b.dw.flags + (b.nPrims - 1), sizeof lastFlag, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (firstBad != resize::kNoBad) {   // a new value out of range, or a bound primitive the new, shorter table no longer serves
+            int32_t mat = 0;
+            const bool inRange = dAssign && firstBad - first < count;
+            HIPCHK(hipMemcpy(&mat, inRange ? (const void*)(dAssign + (firstBad - first)) : (const void*)&sc.prims[firstBad].matIdx, sizeof mat, hipMemcpyDeviceToHost));
+            return fail(RT_E_INVALID, "%s: primitive %u: matIdx %d outside the new table (nMats %d); the scene is unchanged", who, firstBad, mat, nMats);
+        }
+        nLights = (int32_t)(lastRank + lastFlag);
+        int rc = rebuild_fit(b, L.lights, (size_t)nLights, "the light list");
+        if (rc == RT_OK) rc = rebuild_fit(b, L.lightRecs, std::max<size_t>((size_t)nLights, 1) * 8, "light records");
+        if (rc != RT_OK) return rc;
+        HIPCHK(rebuilddev::mat_emit(s, b.dw, sc.prims, (uint32_t)b.nPrims, dAssign, first, count, dMats, (uint32_t)nLights, L.lights.p, L.lightRecs.p));
+    }
+    if (moveTex) {   // the kept part device to device, the rest and the pad zero, then the range
+        const size_t keep = (size_t)std::min(oldTex, nTex);
+        if (keep) HIPCHK(hipMemcpyAsync(T.p, sc.tex, sizeof(RtFloat4) * keep, hipMemcpyDeviceToDevice, s));
+        HIPCHK(hipMemsetAsync(T.p + keep, 0, sizeof(RtFloat4) * (texNeed - keep), s));
+        if (writeTex) HIPCHK(hipMemcpyAsync(T.p + u.texFirst, u.texels, sizeof(RtFloat4) * (size_t)u.texCount, hipMemcpyDefault, s));
+    }
+    HIPCHK(hipEventRecord(b.rev[1], s));
+    HIPCHK(hipStreamSynchronize(s));
+    // ---- commit: no kernel of a holder may read the arrays while they are patched; then the swap
+    if (const int rc = b.wait_holders()) return rc;
+    HIPCHK(hipEventRecord(b.rev[2], s));
+    if (assign) HIPCHK(rebuilddev::mat_assign(s, sc.prims, dAssign, (uint32_t)u.primFirst, (uint32_t)u.primCount, sc.shadeRecs));
+    if (!moveTex) {   // the live atlas has the room: what an in-place growth uncovers is zeroed, then the range, then the pad
+        if (nTex > oldTex) HIPCHK(hipMemsetAsync(sc.tex + oldTex, 0, sizeof(RtFloat4) * (size_t)(nTex - oldTex), s));
+        if (writeTex) HIPCHK(hipMemcpyAsync(sc.tex + u.texFirst, u.texels, sizeof(RtFloat4) * (size_t)u.texCount, hipMemcpyDefault, s));
+        if (padChange) HIPCHK(hipMemsetAsync(sc.tex + nTex, 0, sizeof(RtFloat4) * (size_t)texPad, s));
+    }
+    HIPCHK(hipEventRecord(b.rev[3], s));
+    HIPCHK(hipStreamSynchronize(s));
+    SceneArrays n = b.sc;
+    if (newTable) { n.mats = M.p; n.nMats = nMats; b.mmatsNext ^= 1; b.hMats.assign(u.mats, u.mats + nMats); }
+    if (lightsChange) {
+        n.lights = L.lights.p; n.lightRecs = L.lightRecs.p; n.nLights = nLights;
+        b.nLights = nLights; b.mlightsNext ^= 1;
+        b.lightsInSet = true;   // later rebuilds carry the list from set to set, as after a resize
+    }
+    if (moveTex) { n.tex = T.p; b.texCap = T.cap; b.mtexNext ^= 1; }
+    n.nTex = nTex; b.texPad = texPad;
+    if (assign && !b.primMat.empty())   // the host shadow of matIdx: the range's values, the only per-primitive data that comes back
+        HIPCHK(hipMemcpy(b.primMat.data() + u.primFirst, dAssign, sizeof(int32_t) * (size_t)u.primCount, hipMemcpyDeviceToHost));
+    const bool rebind = n.mats != sc.mats || n.lights != sc.lights || n.lightRecs != sc.lightRecs || n.tex != sc.tex || n.nMats != sc.nMats ||
+                        n.nLights != sc.nLights || n.nTex != sc.nTex;
+    b.sc = n;
+    if (rebind) b.generation++;   // every holder takes the new arrays and counts before its next launch
+    if (stats) {
+        float ms = 0, ms2 = 0;   // GPU time of both phases (not the wait for the holders in between)
+        (void)hipEventElapsedTime(&ms, b.rev[0], b.rev[1]); (void)hipEventElapsedTime(&ms2, b.rev[2], b.rev[3]);
+        stats->gpu_ms = ms + ms2; stats->wall_ms = ms_between(t0, clock::now());
+        stats->mats = newTable ? nMats : 0; stats->texels = writeTex ? u.texCount : 0; stats->prims = assign ? u.primCount : 0;
+        stats->lights = nLights; stats->atlas_reallocated = moveTex ? 1 : 0;
+    }
+    return RT_OK;
+}
 int64_t scenedev::rebuild_allocations(const SceneBag& b) { return (int64_t)(b.rallocs + sbvhdev::pool_allocations(b.spool)); }
 // The primitive range of every instance's BLAS (rebuild_common.h), for callers that want to know beforehand whether rt_rebuild_scene
 // will take a scene; no device needed.
@@ -1084,6 +1212,8 @@ int scenedev::scene_array(const SceneBag& b, int32_t which, const void** src, si
     case RT_SCENE_QUADS:        *src = sc.quads; *n = sc.quads ? sizeof(RtFloat4) * 8 * (size_t)std::max(b.nQuads, 1) : 0; break;
     case RT_SCENE_ROOT_ENTRY:   *src = sc.rootEntry; *n = sc.rootEntry ? sizeof(uint32_t) * (size_t)b.nBlas : 0; break;
     case RT_SCENE_LIGHTS:       *src = sc.lights; *n = sizeof(uint32_t) * (size_t)b.nLights; break;
+    case RT_SCENE_MATERIALS:    *src = sc.mats; *n = sizeof(RtMaterial) * (size_t)sc.nMats; break;
+    case RT_SCENE_TEXTURES:     *src = sc.tex; *n = sizeof(RtFloat4) * ((size_t)sc.nTex + (size_t)b.texPad); break;
     case RT_SCENE_BVH2_KEPT:    *src = sc.bvh2; *n = b.keepsBvh2 ? sizeof(RtBVHNode2) * (size_t)b.nNodes : 0; break;
     default: return fail(RT_E_INVALID, "rt_debug_get_scene_array: unknown array %d", which);
     }

@@ -125,8 +125,19 @@ struct SceneBag {
     rebuilddev::Work dw{};                    // scratch of the derivation
     int32_t* rStatus = nullptr;               // k_tlas_build's status words (word 0, before that: k_resize_check's lowest refused primitive)
     Grown<int2> rPacked;                      // rt_resize_scene: (objType, matIdx) per new primitive, what the host reads back for primType / primMat
-    bool lightsInSet = false;                 // a resize has bound a set's light list: rebuilds carry it from set to set from then on
+    bool lightsInSet = false;                 // a resize or a material update has bound a light list of its own: rebuilds carry it from set to set from then on
     hipEvent_t rev[4] = { nullptr, nullptr, nullptr, nullptr };
+    // rt_update_materials: the host shadow of the bound table (a shrinking atlas is checked against it), the pad behind the atlas and
+    // the capacity of the live atlas in texels, the pad included.  What depends on the materials exists twice, as the rebuild's sets do:
+    // an update writes the set that is not live and the commit swaps the pointers (the upload's arrays, or a rebuild set's light list and
+    // records, stay behind).  An atlas that outgrows its array moves to the texture array that is not live.
+    std::vector<RtMaterial> hMats;
+    int64_t texPad = 2; size_t texCap = 0;
+    Grown<RtMaterial> mmats[2];
+    struct LightSet { Grown<uint32_t> lights; Grown<RtFloat4> lightRecs; } mlights[2];
+    Grown<RtFloat4> mtex[2];
+    int mmatsNext = 0, mlightsNext = 0, mtexNext = 0;   // which of each the next update writes (flipped when a commit has made it live)
+    Grown<int32_t> mAssign;                   // the new matIdx values of an update's range, host or device input alike
     ~SceneBag()
     {
         (void)hipSetDevice(device);
@@ -153,6 +164,8 @@ int rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t 
                   int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats);
 // rt_resize_scene (include/rt355.h): the caller's shape, checked by resize::check_shape; prims may be host or device memory
 int resize_scene(SceneBag& b, const void* prims, int32_t nPrims, const RtSceneShape* shape, int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats);
+// rt_update_materials (include/rt355.h): texels / primMat may be host or device memory (the caller has applied the pointer rule)
+int update_materials(SceneBag& b, const RtMaterialUpdate& u, RtMaterialStats* stats);
 int64_t rebuild_allocations(const SceneBag& b);
 int scene_array(const SceneBag& b, int32_t which, const void** src, size_t* bytes);   // where RT_SCENE_* lies on the device and how long it is
 

@@ -35,6 +35,17 @@ template <class Build> static int build_bvh2(Build build)
     if (rc != RT_OK) g_herr = err;
     return rc;
 }
+// The host restatement of rt_update_materials: the Scene methods' message goes to rth_last_error() when they refuse
+template <class Set> static int set_materials(const char* who, RthScene* s, Set set)
+{
+    if (!s) { g_herr = std::string(who) + ": null scene"; return RT_E_INVALID; }
+    try {
+        std::string err;
+        const int rc = set(err);
+        if (rc != RT_OK) g_herr = err;
+        return rc;
+    } catch (const std::exception& e) { g_herr = e.what(); return RT_E_NOMEM; }
+}
 
 extern "C" {
 
@@ -281,6 +292,18 @@ int rth_light_list(const RtPrimitive* prims, int32_t nPrims, const RtMaterial* m
         if (!lights.empty()) memcpy(out, lights.data(), sizeof(uint32_t) * lights.size());
         return (int)lights.size();
     } catch (const std::exception& e) { g_herr = e.what(); return RT_E_NOMEM; }
+}
+int rth_set_materials(RthScene* s, const RtMaterial* mats, int32_t nMats)
+{
+    return set_materials("rth_set_materials", s, [&](std::string& err) { return s->scene.SetMaterials(mats, nMats, err); });
+}
+int rth_set_texels(RthScene* s, const RtFloat4* texels, int32_t first, int32_t count, int32_t nTexels)
+{
+    return set_materials("rth_set_texels", s, [&](std::string& err) { return s->scene.SetTexels(texels, first, count, nTexels, err); });
+}
+int rth_set_prim_materials(RthScene* s, int32_t first, int32_t count, const int32_t* matIdx)
+{
+    return set_materials("rth_set_prim_materials", s, [&](std::string& err) { return s->scene.SetPrimMaterials(first, count, matIdx, err); });
 }
 
 #define VIEW(vec) do { if (n) *n = (int)(vec).size(); return (vec).data(); } while (0)

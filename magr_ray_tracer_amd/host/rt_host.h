@@ -190,6 +190,11 @@ public:
     // reference: Scene::LoadTexture (scene.cpp:244-256); PNG, JPEG, TGA and Radiance HDR files (image_io.cpp, jpeg_io.cpp); returns the material index
     int  LoadTexture(const std::string& filename, const std::string& name);
     int  MaterialIndex(const std::string& name);
+    // The host restatement of rt_update_materials (include/rt355_host.h): each checks first, changes nothing when it refuses (the reason
+    // goes to err, the return value is RT_E_INVALID), and leaves `lights` as the Scene rule gives it for the new state
+    int  SetMaterials(const RtMaterial* mats, int32_t nMats, std::string& err);   // the whole table; names of dropped indices are forgotten
+    int  SetTexels(const RtFloat4* texels, int32_t first, int32_t count, int32_t nTexels, std::string& err);
+    int  SetPrimMaterials(int32_t first, int32_t count, const int32_t* matIdx, std::string& err);
     bool HasMaterial(const std::string& name) const { return matMap_.count(name) != 0; }
     // reference: Scene::LoadModel (scene.cpp:178-243), OBJ + MTL diffuse-texture names; returns the triangles added
     int  LoadModel(const std::string& filename, const std::string& defaultMaterial, float3 pos = float3(0, 0, 0), bool forceDefaultMat = false);

@@ -5,6 +5,9 @@
 // scene_io.cpp / image_io.cpp; AddTexture takes texels that are already in memory.
 #include <cmath>
 #include <cstring>
+#include <iterator>
+#include "../../include/rt355.h"
+#include "../csrc/resize_common.h"
 #include "rt_host.h"
 
 namespace rt355 {
@@ -80,6 +83,58 @@ void Scene::AddTriangle(float3 v0, float3 v1, float3 v2, float2 uv0, float2 uv1,
     if (materials[p.matIdx].isLight) lights.push_back((uint32_t)primitives.size() - 1);
 }
 void Scene::BuildBVH4() { delete bvh4; bvh4 = new BVH4(*bvh2); } // scene.cpp:71
+
+// ---- the host restatement of rt_update_materials: the checks of csrc/resize_common.h, the Scene rule for the light list ---------------
+int Scene::SetMaterials(const RtMaterial* mats, int32_t nMats, std::string& err)
+{
+    if (!mats || nMats <= 0) { err = "rth_set_materials: a material table holds at least one material (nMats " + std::to_string(nMats) + ")"; return RT_E_INVALID; }
+    if (const int32_t m = resize::check_materials(mats, nMats, (int64_t)textures.size(), nullptr); m >= 0) {
+        err = "material " + std::to_string(m) + ": texture window exceeds the atlas"; return RT_E_INVALID;
+    }
+    for (size_t i = 0; i < primitives.size(); i++) if (primitives[i].matIdx < 0 || primitives[i].matIdx >= nMats) {
+        err = "rth_set_materials: primitive " + std::to_string(i) + ": matIdx " + std::to_string(primitives[i].matIdx) + " outside the new table (nMats " +
+              std::to_string(nMats) + "); the scene is unchanged";
+        return RT_E_INVALID;
+    }
+    materials.assign(mats, mats + nMats);
+    for (auto it = matMap_.begin(); it != matMap_.end();) it = it->second >= nMats ? matMap_.erase(it) : std::next(it);
+    matIdx_ = nMats;
+    resize::light_list(primitives.data(), (int32_t)primitives.size(), materials.data(), lights);
+    return RT_OK;
+}
+int Scene::SetTexels(const RtFloat4* texels, int32_t first, int32_t count, int32_t nTexels, std::string& err)
+{
+    if (nTexels < -1) { err = "rth_set_texels: nTexels " + std::to_string(nTexels) + " (the new atlas length, or -1 to keep it)"; return RT_E_INVALID; }
+    if (first < 0 || count < 0 || (count > 0 && !texels)) { err = "rth_set_texels: bad texel range / NULL texels"; return RT_E_INVALID; }
+    const int64_t n = nTexels < 0 ? (int64_t)textures.size() : (int64_t)nTexels;
+    if (texels && (int64_t)first + count > n) {
+        err = "rth_set_texels: texel range [" + std::to_string(first) + ", " + std::to_string((int64_t)first + count) + ") outside the new atlas of " + std::to_string(n) + " texels";
+        return RT_E_INVALID;
+    }
+    if (const int32_t m = resize::check_materials(materials.data(), (int32_t)materials.size(), n, nullptr); m >= 0) {
+        err = "material " + std::to_string(m) + ": texture window exceeds the atlas"; return RT_E_INVALID;
+    }
+    textures.resize((size_t)n, RtFloat4{ 0, 0, 0, 0 });   // kept texels stay, new ones are zero
+    if (texels && count) memcpy(textures.data() + first, texels, sizeof(RtFloat4) * (size_t)count);
+    return RT_OK;
+}
+int Scene::SetPrimMaterials(int32_t first, int32_t count, const int32_t* matIdx, std::string& err)
+{
+    if (first < 0 || count < 0 || (count > 0 && !matIdx)) { err = "rth_set_prim_materials: bad primitive range / NULL values"; return RT_E_INVALID; }
+    if (matIdx && (int64_t)first + count > (int64_t)primitives.size()) {
+        err = "rth_set_prim_materials: primitive range [" + std::to_string(first) + ", " + std::to_string((int64_t)first + count) + ") outside the " +
+              std::to_string(primitives.size()) + " primitives";
+        return RT_E_INVALID;
+    }
+    for (int32_t k = 0; k < count; k++) if (matIdx[k] < 0 || matIdx[k] >= (int32_t)materials.size()) {
+        err = "rth_set_prim_materials: primitive " + std::to_string(first + k) + ": matIdx " + std::to_string(matIdx[k]) + " outside the table (nMats " +
+              std::to_string(materials.size()) + "); the scene is unchanged";
+        return RT_E_INVALID;
+    }
+    for (int32_t k = 0; k < count; k++) primitives[(size_t)first + (size_t)k].matIdx = matIdx[k];
+    resize::light_list(primitives.data(), (int32_t)primitives.size(), materials.data(), lights);
+    return RT_OK;
+}
 
 // ------------------------------------------------------------------ camera
 CameraManager::CameraManager(int width, int height, float vfov, int type) // camera.h:24-34

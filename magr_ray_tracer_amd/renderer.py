@@ -75,6 +75,54 @@ def _resize_args(prims, range_counts, inst_range, instances, builder, lbvh_optio
     return (pp, n, _lib.ptr(shape), which, _lib.ptr(opts), _lib.ptr(st)), (p, counts, ir, b, shape, opts), st
 
 
+def _flat_pointer(a, dtype, what):
+    """(void* or None, element count, what keeps it alive) of a numpy array (host memory) or a torch tensor, which is used where it lies
+    (torch's current stream is waited for: the library's copy runs on a stream of its own); `dtype`: the numpy element type."""
+    if isinstance(a, np.ndarray) or not hasattr(a, "data_ptr"):
+        h = np.ascontiguousarray(a, dtype=dtype.base)
+        if h.nbytes % dtype.itemsize:
+            raise ValueError(f"{what}: {h.nbytes} bytes are no whole number of {dtype.itemsize}-byte elements")
+        n = h.nbytes // dtype.itemsize
+        return (_lib.ptr(h) if n else None), n, h
+    t = a if a.is_contiguous() else a.contiguous()
+    nbytes = t.numel() * t.element_size()
+    if str(t.dtype) != {"float32": "torch.float32", "int32": "torch.int32"}[dtype.base.name] or nbytes % dtype.itemsize:
+        raise ValueError(f"{what}: a {dtype.base.name} tensor of whole {dtype.itemsize}-byte elements expected, not {t.dtype} of {nbytes} bytes")
+    if getattr(t, "is_cuda", False):
+        import torch
+        torch.cuda.current_stream(t.device).synchronize()
+    return (C.c_void_p(t.data_ptr()) if nbytes else None), nbytes // dtype.itemsize, t
+
+
+def _materials_args(mats, texels, tex_first, n_texels, prim_mat, prim_first):
+    """The arguments of rt_update_materials: (RtMaterialUpdate*, RtMaterialStats*), what keeps them alive, the stats record."""
+    u = np.zeros((), dtype=_lib.MaterialUpdate)
+    keep = []
+    if mats is not None:
+        m = np.ascontiguousarray(mats, dtype=_lib.Material).ravel()
+        u["mats"], u["nMats"] = m.ctypes.data, len(m)
+        keep.append(m)
+    if texels is not None:
+        p, n, k = _flat_pointer(texels, _lib.f4, "texels")
+        u["texels"], u["texCount"] = (p.value or 0) if p is not None else 0, n
+        keep.append(k)
+    u["texFirst"], u["nTexels"] = int(tex_first), -1 if n_texels is None else int(n_texels)
+    if prim_mat is not None:
+        p, n, k = _flat_pointer(prim_mat, np.dtype(np.int32), "prim_mat")
+        u["primMat"], u["primCount"] = (p.value or 0) if p is not None else 0, n
+        keep.append(k)
+    u["primFirst"] = int(prim_first)
+    st = np.zeros((), dtype=_lib.MaterialStats)
+    return (_lib.ptr(u), _lib.ptr(st)), (u, keep), st
+
+
+def _materials_dict(st):
+    d = {"gpu_ms": float(st["gpu_ms"]), "wall_ms": float(st["wall_ms"])}
+    d.update({n: int(st[n]) for n in ("mats", "texels", "prims", "lights")})
+    d.update({n: bool(st[n]) for n in ("tables_staged_changed", "atlas_reallocated")})
+    return d
+
+
 class Device:
     def __init__(self, width, height, y0=0, y1=None, shading=_lib.SHADING_NEE, sampling=_lib.SAMPLING_COSINE,
                  accel=_lib.ACCEL_BVH2, russian_roulette=True, filter_fireflies=True, max_bounces=_lib.MAX_BOUNCES,
@@ -189,6 +237,18 @@ class Device:
         self._chk_code(self._lib.rt_resize_scene(self._h, *args))
         return _rebuild_dict(st)
 
+    def update_materials(self, mats=None, texels=None, tex_first=0, n_texels=None, prim_mat=None, prim_first=0):
+        """Change the bound scene's materials, texture atlas and material assignment in place on the GPU (rt_update_materials); each part
+        that is None stays as bound.  mats: the whole new table (Material records).  texels: (n, 4) float32 that replace texels
+        [tex_first, tex_first + n) of the atlas, whose new length is n_texels (None: as bound; kept texels stay, new ones are zero).
+        prim_mat: int32 values, the new matIdx of primitives [prim_first, prim_first + len(prim_mat)).  texels and prim_mat may be numpy
+        arrays, or torch tensors on the context's GPU, which are used where they lie (torch's current stream is waited for first).  With
+        mats or prim_mat the light list and the light records are derived anew on the device; every context holding the scene sees the
+        change.  Returns the stats as a dict; a refusal raises RtError (.code) and leaves the scene as it was."""
+        args, keep, st = _materials_args(mats, texels, tex_first, n_texels, prim_mat, prim_first)
+        self._chk_code(self._lib.rt_update_materials(self._h, *args))
+        return _materials_dict(st)
+
     def refit_info(self):
         """The last successful rebuild_scene(builder="refit") of the bound scene copy (rt_refit_info): path (0 none yet, 1 in place,
         2 re-collapsed because changed_nodes > 0, 3 re-collapsed because RT355_REFIT_RECOLLAPSE=1 forced it), live_quads,
@@ -205,7 +265,7 @@ class Device:
 
     def scene_array(self, name):
         """A device array of the bound scene as raw bytes (rt_debug_get_scene_array; names: _lib.SCENE_ARRAYS, _lib.SCENE_ARRAYS_BVH4)."""
-        which = {**_lib.SCENE_ARRAYS, **_lib.SCENE_ARRAYS_BVH4, **_lib.SCENE_ARRAYS_RESIZE}[name]
+        which = {**_lib.SCENE_ARRAYS, **_lib.SCENE_ARRAYS_BVH4, **_lib.SCENE_ARRAYS_RESIZE, **_lib.SCENE_ARRAYS_MATERIALS}[name]
         n = C.c_int64(0)
         self._chk(self._lib.rt_debug_get_scene_array(self._h, which, None, 0, C.byref(n)))
         out = np.zeros(n.value, dtype=np.uint8)
@@ -559,6 +619,16 @@ class Group:
             e.code = rc
             raise e
         return _rebuild_dict(st)
+
+    def update_materials(self, mats=None, texels=None, tex_first=0, n_texels=None, prim_mat=None, prim_first=0):
+        """Device.update_materials for the group's scene copy (rt_group_update_materials): every lane sees the change."""
+        args, keep, st = _materials_args(mats, texels, tex_first, n_texels, prim_mat, prim_first)
+        rc = self._lib.rt_group_update_materials(self._h, *args)
+        if rc != 0:
+            e = RtError(self._lib.rt_last_error().decode())
+            e.code = rc
+            raise e
+        return _materials_dict(st)
 
     def seed(self, first_stream=0):
         self._chk(self._lib.rt_group_seed(self._h, int(first_stream)))

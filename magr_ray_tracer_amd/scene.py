@@ -190,6 +190,32 @@ class Scene:
         p = np.ascontiguousarray(prims, dtype=_lib.Primitive)
         self._chk(self._lib.rth_set_primitives(self._h, int(first), len(p), _lib.ptr(p) if len(p) else None))
 
+    def _chk_build(self, rc):
+        if rc != 0:
+            raise BuildError(rc, self._lib.rth_last_error().decode())
+
+    def SetMaterials(self, mats):
+        """Replace the whole material table (rth_set_materials; Material records), as Device.update_materials(mats=...) does on the GPU:
+        every texture window must lie inside the atlas and every primitive's matIdx inside the new table; the light list follows by
+        the Scene rule.  The trees are not touched.  Raises BuildError (.code RT_E_INVALID) and changes nothing when refused."""
+        m = np.ascontiguousarray(mats, dtype=_lib.Material).ravel()
+        self._chk_build(self._lib.rth_set_materials(self._h, _lib.ptr(m) if len(m) else None, len(m)))
+
+    def SetTexels(self, texels=None, first=0, n_texels=None):
+        """Give the atlas n_texels texels (None: as it is; kept texels stay, new ones are zero) and write `texels` ((n, 4) float32) at
+        [first, first + n) (rth_set_texels), as Device.update_materials(texels=..., tex_first=..., n_texels=...) does on the GPU.  Raises
+        BuildError (.code RT_E_INVALID) and changes nothing when refused."""
+        t = None if texels is None else np.ascontiguousarray(texels, dtype=np.float32).reshape(-1, 4)
+        n = 0 if t is None else len(t)
+        self._chk_build(self._lib.rth_set_texels(self._h, _lib.ptr(t) if n else None, int(first), n, -1 if n_texels is None else int(n_texels)))
+
+    def SetPrimMaterials(self, first, mat_idx):
+        """Write mat_idx (int32) into the matIdx of primitives [first, first + len(mat_idx)) (rth_set_prim_materials), as
+        Device.update_materials(prim_mat=..., prim_first=...) does on the GPU; the light list follows by the Scene rule.  Raises
+        BuildError (.code RT_E_INVALID) and changes nothing when refused."""
+        m = np.ascontiguousarray(mat_idx, dtype=np.int32).ravel()
+        self._chk_build(self._lib.rth_set_prim_materials(self._h, int(first), len(m), _lib.ptr(m) if len(m) else None))
+
     def Refit(self):
         """Refit every BLAS of the BVH2 in place by the rules rt_update_scene runs on the GPU (rth_refit); arrays() / BuildTLAS() then
         rebuild the TLAS (and the BVH4) from the refit tree."""
