@@ -367,6 +367,54 @@ typedef struct RtRebuildStats {
 } RtRebuildStats;
 int rt_rebuild_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
                      int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats);
+/* ---- per-range plans: rebuild only the BLAS that changed -----------------------------------------------------------------------------
+ * rt_rebuild_scene builds every distinct BLAS anew.  One deforming mesh beside a large static one pays for the static tree again on every
+ * call, and one call cannot mix builders.  rt_rebuild_ranges takes a plan: plan[k], one word per distinct BLAS in increasing order of the
+ * primitive ranges (the order of rt_scene_blas_blocks and rt_blas_ranges' ranges), is RT_REBUILD_SAH, RT_REBUILD_LBVH or RT_REBUILD_SBVH -
+ * that BLAS is built by that builder, as rt_rebuild_scene builds it (one opts for all: the LBVH words go to the LBVH ranges, alpha to the
+ * SBVH ranges) - or RT_REBUILD_KEEP: its bound tree stays.  prims / first / count / blas / nBlas mean what they mean for
+ * rt_rebuild_scene.  Afterwards the scene is numbered the way the host appends BLAS after BLAS: the root of range k is the sum of the
+ * node counts of ranges 0..k-1, its first index slot the sum of their slot counts.  A built range holds its builder's tree at that base.
+ * A kept range holds its bound tree relocated, by one rule for the device (k_blas_relocate) and the host mirror (rth_rebuild_ranges;
+ * csrc/rebuild_common.h, relocated_first): node i of the bound block moves to i - oldRoot + newRoot; an interior record (count == 0) gets
+ * first += newRoot - oldRoot, a leaf record first += newIdxBase - oldIdxBase; boxes, counts and pad words are untouched, and its primIdx
+ * slots move unchanged (primitive ids are global and the range did not move).  The builders are functions of their primitive range into
+ * which the bases enter only as these offsets, so that is byte for byte what the builder that made the tree would write there.  Kept BLAS
+ * that are neighbours in both numberings move as one segment, one kernel launch per segment (the node array is read from the live set and
+ * written to the set that is not live: they never alias); a segment that does not move at all - the static mesh in front of the moving
+ * one - is a plain device-to-device copy, as the primIdx slots always are.  Then rt_rebuild_scene's pipeline runs unchanged over all
+ * ranges: bvhIdx from the new roots, pair ids, the collapse of a BVH4 copy that keeps its BVH2, the derived records, TLAS::Build, the
+ * layout check and the commit by pointer swap.  This first version does NOT relocate the derived records of a kept BLAS (pair, triangle
+ * and quad records, refit topology): it derives them again over all ranges, which costs about what a refit of the scene costs; what a
+ * kept BLAS saves is its build.  Afterwards every array rt_debug_get_scene_array returns, sizes included, and rt_kernel_info equal those
+ * of a fresh upload of the host mirror's scene (rth_rebuild_ranges + rth_build_tlas).  stats as for a rebuild: blas_built counts the
+ * ranges actually built, build_ms includes the relocation.
+ * Which bound trees can be kept: a BLAS is compact when the nodes reachable from its root are exactly the ids [root, root + m), m odd,
+ * and its leaves' primIdx ranges tile one interval without gap or overlap.  Everything BuildBLAS, the GPU builders, rt_rebuild_scene,
+ * rt_rebuild_ranges and rt_resize_scene produce is compact; arbitrary arrays handed to rt_upload_scene may not be (found at upload).  A
+ * range that is not compact can be built, not kept.  rt_scene_blas_blocks reports, per distinct BLAS in plan order, its primitive range,
+ * the nodes and index slots of its bound tree (an SBVH tree has more slots than primitives) and whether it is compact: *n receives the
+ * number of distinct BLAS, at most cap entries of each array (any may be NULL) are written.
+ * Room: the set that is not live is given the kept trees' sizes plus count slots and 2 * count - 1 nodes for every range the SAH or the
+ * linear builder builds, before anything runs; SBVH ranges keep their size-then-place path (and leave room for what lies behind them).
+ * The builders' workspace is sized over the built ranges only.
+ * Refusals change nothing (rt_rebuild_scene's guarantee):
+ *   RT_E_INVALID      before any device work: a null plan; nRanges different from the scene's number of distinct BLAS; a plan word that
+ *                     is none of the four; RT_REBUILD_REFIT in a plan (per-range refits are not offered: refit the whole scene with
+ *                     rt_rebuild_scene); a replacement window [first, first + count), count > 0, that intersects a kept range (its boxes
+ *                     would go stale); everything rt_rebuild_scene answers with RT_E_INVALID; bad opts for a builder the plan uses;
+ *   RT_E_UNSUPPORTED  RT_REBUILD_KEEP for a range that is not compact (the message names the range); everything rt_rebuild_scene
+ *                     refuses (a BVH4 copy without its BVH2, a layout change, ...);
+ *   RT_E_NOMEM        as for rebuilds.
+ * rt_rebuild_ranges_check runs the plan checks without a device against caller-given ranges: nBound ranges (rangeFirst / rangeCount, in
+ * increasing order; compact NULL: all compact), the plan, the window, opts.  RT_OK, or the code and message rt_rebuild_ranges would give. */
+#define RT_REBUILD_KEEP  4   /* per-range plans only: the bound tree of this BLAS stays, moved to where the new scene numbers it */
+int rt_rebuild_ranges(RtCtx* ctx, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
+                      const int32_t* plan, int32_t nRanges,   /* HOST: one of RT_REBUILD_SAH / LBVH / SBVH / KEEP per distinct BLAS */
+                      const RtBuildOptions* opts, RtRebuildStats* stats);
+int rt_scene_blas_blocks(RtCtx* ctx, int32_t* n, int32_t* primFirst, int32_t* primCount, int32_t* nodes, int32_t* idxSlots, int32_t* compact, int32_t cap);
+int rt_rebuild_ranges_check(int32_t nPrims, const int32_t* rangeFirst, const int32_t* rangeCount, const int32_t* compact, int32_t nBound,
+                            const int32_t* plan, int32_t nRanges, int32_t first, int32_t count, const RtBuildOptions* opts);
 /* ---- in-place resizes (a bound scene changes its shape without leaving the device) ----------------------------------------------------
  * rt_update_scene and rt_rebuild_scene keep the scene's shape: the primitive count, every primitive's objType and matIdx, the number of
  * BLAS and of instances, the light list.  rt_resize_scene replaces all of it but the materials and textures, which stay as bound:
@@ -490,6 +538,12 @@ int rt_debug_rebuild_allocations(RtCtx* ctx, int64_t* count);
  * reason in rt_last_error() when the scene is not of the shape rt_rebuild_scene takes.  No device needed. */
 int rt_blas_ranges(const RtBVHNode2* nodes, int32_t nNodes, const uint32_t* primIdx, int32_t nIdx, int32_t nPrims,
                    const RtBVHInstance* blas, int32_t nBlas, int32_t* firstOut, int32_t* countOut);
+/* rt_scene_blas_blocks for wire arrays, as rt_upload_scene would find the blocks (csrc/rebuild_common.h): per distinct BLAS, in the order
+ * a plan of rt_rebuild_ranges names them, the primitive range, the nodes and index slots its tree reaches and whether it is compact (can
+ * be kept).  *n receives the number of distinct BLAS; at most cap entries of each array (any may be NULL) are written.  Refused like
+ * rt_blas_ranges.  No device needed. */
+int rt_blas_blocks(const RtBVHNode2* nodes, int32_t nNodes, const uint32_t* primIdx, int32_t nIdx, int32_t nPrims, const RtBVHInstance* blas, int32_t nBlas,
+                   int32_t* n, int32_t* primFirst, int32_t* primCount, int32_t* nodesOut, int32_t* idxSlots, int32_t* compact, int32_t cap);
 /* Device arrays of the context's scene copy, for tests: `which` is one of RT_SCENE_*.  *bytes receives the array's size; out NULL:
  * only that.  Waits for the context's stream. */
 #define RT_SCENE_PRIMS         0   /* the wire primitives                                  */
@@ -555,6 +609,8 @@ int rt_group_update_scene(RtGroup* g, const RtPrimitive* prims, int32_t first, i
                           RtUpdateStats* stats);                             /* rt_update_scene for the group's copy (all lanes)        */
 int rt_group_rebuild_scene(RtGroup* g, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
                            int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats);   /* rt_rebuild_scene for the group's copy */
+int rt_group_rebuild_ranges(RtGroup* g, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
+                            const int32_t* plan, int32_t nRanges, const RtBuildOptions* opts, RtRebuildStats* stats);   /* rt_rebuild_ranges likewise */
 int rt_group_resize_scene(RtGroup* g, const void* prims, int32_t nPrims, const RtSceneShape* shape, int32_t builder, const RtBuildOptions* opts,
                           RtRebuildStats* stats);                            /* rt_resize_scene for the group's copy (all lanes)        */
 int rt_group_update_materials(RtGroup* g, const RtMaterialUpdate* update, RtMaterialStats* stats);   /* rt_update_materials, likewise  */

@@ -85,6 +85,13 @@ int rth_refit(RthScene* s);
  * rth_build_bvh4).  Returns RT_E_* and changes nothing when refused (a scene whose BLAS do not cover contiguous, disjoint, ordered
  * ranges; whatever the builder refuses). */
 int rth_rebuild(RthScene* s, int builder, const RtBuildOptions* opts);
+/* The host restatement of rt_rebuild_ranges (rt355.h): rth_rebuild under a plan, plan[nRanges] with one RT_REBUILD_SAH / LBVH / SBVH /
+ * KEEP per distinct BLAS in increasing order of the ranges.  A built BLAS is appended as rth_rebuild appends it; a kept one as its bound
+ * block of nodes, relocated by the rule the device applies (csrc/rebuild_common.h, relocated_first), with its primIdx slots unchanged.
+ * Refused like rth_rebuild, and by rt_rebuild_ranges' plan rules: RT_E_INVALID for a null plan, a wrong nRanges, an unknown word or
+ * RT_REBUILD_REFIT; RT_E_UNSUPPORTED for RT_REBUILD_KEEP of a BLAS that is not compact.  (The primitives a kept BLAS covers must not
+ * have changed since it was built or refit: the host scene has no window to check that against.) */
+int rth_rebuild_ranges(RthScene* s, const int32_t* plan, int nRanges, const RtBuildOptions* opts);
 /* rt_blas_ranges (rt355.h) of the scene's arrays: the primitive range of every instance's BLAS; RT_E_UNSUPPORTED (rt_last_error() has
  * the reason) when the scene is not of the shape a rebuild takes. */
 int rth_blas_ranges(RthScene* s, int32_t* firstOut, int32_t* countOut);
@@ -120,6 +127,9 @@ int rth_set_instance_transform(RthScene* s, int blas, const float invT[16]); /* 
  * inverse(invT) unless invT is the identity).  What the host needs to state a scene with more instances than BLAS (rt_resize_scene's
  * ground truth).  Returns the new instance's index, or -1: a bad index, a singular invT, 256 instances already. */
 int rth_add_instance(RthScene* s, int blas, const float invT[16]);
+/* Instances a and b trade places (record for record): the order of the instances is free, and the derived pair ids follow the order in
+ * which the instances first name their BLAS, not the order of the BLAS.  -1: a bad index. */
+int rth_swap_instances(RthScene* s, int a, int b);
 /* The light list of prims[nPrims] under mats[nMats] by the Scene rule, as rt_resize_scene derives it (csrc/resize_common.h): the
  * indices, in increasing order, of the primitives whose material has isLight != 0.  out needs room for nPrims entries; returns the
  * count, or RT_E_INVALID for a missing array or the first primitive whose objType / matIdx is out of range (rth_last_error() names it). */

@@ -115,6 +115,7 @@ UpdateStats = np.dtype([("gpu_ms", "<f8"), ("prims", "<i4"), ("nodes", "<i4"), (
 assert UpdateStats.itemsize == 40
 REBUILD_SAH, REBUILD_LBVH, REBUILD_SBVH = 0, 1, 2   # rt_rebuild_scene builders
 REBUILD_REFIT = 3                                   # ... and its refit: no builder runs (the device library only: rth_rebuild refuses it)
+REBUILD_KEEP = 4                                    # per-range plans only (rt_rebuild_ranges): the bound tree of that BLAS stays
 RefitInfo = np.dtype([(n, "<i4") for n in ("path", "live_quads", "changed_nodes", "stack_need")])   # RtRefitInfo
 assert RefitInfo.itemsize == 16
 REFIT_NONE, REFIT_IN_PLACE, REFIT_RECOLLAPSED, REFIT_FORCED = 0, 1, 2, 3   # RtRefitInfo.path
@@ -135,7 +136,8 @@ DEVICE_SYMBOLS = [
     "rt_group_create", "rt_group_destroy", "rt_group_lanes", "rt_group_concurrency", "rt_group_stream_class", "rt_group_class_concurrency", "rt_group_lane", "rt_group_frames", "rt_group_upload_scene", "rt_group_share_scene",
     "rt_group_seed", "rt_group_reset", "rt_group_render", "rt_group_synchronize", "rt_group_sum", "rt_group_read_accum", "rt_group_focus",
     "rt_group_postproc", "rt_trace", "rt_trace_window", "rt_resize_scene", "rt_group_resize_scene", "rt_resize_check",
-    "rt_update_materials", "rt_group_update_materials", "rt_materials_check"]
+    "rt_update_materials", "rt_group_update_materials", "rt_materials_check",
+    "rt_rebuild_ranges", "rt_group_rebuild_ranges", "rt_scene_blas_blocks", "rt_rebuild_ranges_check", "rt_blas_blocks"]
 HOST_SYMBOLS = [
     "rth_last_error", "rth_scene_create", "rth_scene_destroy", "rth_add_material", "rth_add_texture", "rth_load_texture", "rth_add_sphere",
     "rth_add_plane", "rth_add_triangle", "rth_add_quad", "rth_add_triangles", "rth_build_blas", "rth_build_bvh4",
@@ -147,7 +149,7 @@ HOST_SYMBOLS = [
     "rth_build_blas_lbvh", "rth_build_bvh2_lbvh", "rth_lbvh_stats", "rth_set_primitives", "rth_refit",
     "rth_build_blas_sah_gpu", "rth_build_bvh2_sah", "rth_build_blas_sbvh_gpu", "rth_build_bvh2_sbvh", "rth_rebuild", "rth_blas_ranges",
     "rth_build_bvh4_gpu", "rth_build_bvh4_levels", "rth_bvh4_refit", "rth_refit_bvh4", "rth_add_instance", "rth_light_list",
-    "rth_set_materials", "rth_set_texels", "rth_set_prim_materials"]
+    "rth_set_materials", "rth_set_texels", "rth_set_prim_materials", "rth_rebuild_ranges", "rth_swap_instances"]
 
 _dev = None
 _host = None
@@ -251,6 +253,11 @@ def _bind_device(lib):
         lib.rt_rebuild_scene.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp, vp]
         lib.rt_group_rebuild_scene.argtypes = [vp, vp, i32, i32, vp, i32, i32, vp, vp]
         lib.rt_debug_rebuild_allocations.argtypes = [vp, vp]
+        lib.rt_rebuild_ranges.argtypes = [vp, vp, i32, i32, vp, i32, vp, i32, vp, vp]
+        lib.rt_group_rebuild_ranges.argtypes = [vp, vp, i32, i32, vp, i32, vp, i32, vp, vp]
+        lib.rt_scene_blas_blocks.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32]
+        lib.rt_rebuild_ranges_check.argtypes = [i32, vp, vp, vp, i32, vp, i32, i32, i32, vp]
+        lib.rt_blas_blocks.argtypes = [vp, i32, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32]
         lib.rt_resize_scene.argtypes = [vp, vp, i32, vp, i32, vp, vp]
         lib.rt_group_resize_scene.argtypes = [vp, vp, i32, vp, i32, vp, vp]
         lib.rt_resize_check.argtypes = [i32, vp, i32, vp]
@@ -319,12 +326,14 @@ def host_lib():
         lib.rth_set_primitives.argtypes = [vp, i32, i32, vp]
         lib.rth_refit.argtypes = [vp]
         lib.rth_rebuild.argtypes = [vp, i32, vp]
+        lib.rth_rebuild_ranges.argtypes = [vp, vp, i32, vp]
         lib.rth_blas_ranges.argtypes = [vp, vp, vp]
         lib.rth_set_build_threads.argtypes = [vp, i32]
         lib.rth_build_tlas.argtypes = [vp]
         lib.rth_bvh4_from_nodes.argtypes = [vp, i32, vp]
         lib.rth_set_instance_transform.argtypes = [vp, i32, fp]
         lib.rth_add_instance.argtypes = [vp, i32, fp]
+        lib.rth_swap_instances.argtypes = [vp, i32, i32]
         lib.rth_light_list.argtypes = [vp, C.c_int32, vp, C.c_int32, vp]
         lib.rth_set_materials.argtypes = [vp, vp, C.c_int32]
         lib.rth_set_texels.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32]

@@ -324,6 +324,12 @@ extern "C" int rt_group_rebuild_scene(RtGroup* g, const RtPrimitive* prims, int3
     if (!g) return fail(RT_E_INVALID, "rt_group_rebuild_scene: null group");
     return rt_rebuild_scene(rt_group_lane(g, 0), prims, first, count, blas, nBlas, builder, opts, stats);   // every lane holds lane 0's copy
 }
+extern "C" int rt_group_rebuild_ranges(RtGroup* g, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
+                                       const int32_t* plan, int32_t nRanges, const RtBuildOptions* opts, RtRebuildStats* stats)
+{
+    if (!g) return fail(RT_E_INVALID, "rt_group_rebuild_ranges: null group");
+    return rt_rebuild_ranges(rt_group_lane(g, 0), prims, first, count, blas, nBlas, plan, nRanges, opts, stats);   // every lane holds lane 0's copy
+}
 extern "C" int rt_group_resize_scene(RtGroup* g, const void* prims, int32_t nPrims, const RtSceneShape* shape, int32_t builder, const RtBuildOptions* opts,
                                      RtRebuildStats* stats)
 {

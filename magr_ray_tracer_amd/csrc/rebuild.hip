@@ -21,6 +21,11 @@
 //                   through atomicMin), the light flag; a scan ranks the flags
 //   k_mat_emit      k_light_emit with that matIdx
 //   k_mat_assign    the commit, one thread per primitive of the range: matIdx and the shade record of the patched primitive
+// rt_rebuild_ranges keeps the bound tree of a BLAS whose primitives did not change:
+//   k_blas_relocate one thread per 16-byte vector of a kept block of nodes: copied to where the new scene numbers it, the `first` word
+//                   of every record moved by the block's node or index offset (rebuild::relocated_first)
+#include <algorithm>
+#include <cstddef>
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include "../../include/rt355.h"
@@ -268,6 +273,34 @@ hipError_t mat_assign(hipStream_t s, RtPrimitive* prims, const int32_t* assign, 
 {
     if (count == 0) return hipSuccess;
     hipLaunchKernelGGL(k_mat_assign, grid(count), dim3(kBlock), 0, s, prims, assign, first, count, shadeRecs);
+    return hipGetLastError();
+}
+
+// ---- rt_rebuild_ranges: a kept BLAS moves as a block (rule: rebuild::relocated_first) ---------------------------------------------------
+// An RtBVHNode2 is 48 bytes, three 16-byte vectors: two of box, then {first, count, pad, pad}.  One thread per VECTOR, grid-stride: lane l
+// of a wave reads and writes the 16 bytes right behind lane l - 1's, so every load and every store of a wave covers 1 KiB of consecutive
+// memory (a thread per node would stride its three accesses by 48 bytes).  Every third vector gets the add to its first word; nothing
+// else is computed, no LDS, no atomics.  src is the live array, dst the set that is not live: they never alias.
+constexpr uint32_t kRelocateMaxBlocks = 2048;   // 256 CUs x 8 workgroups of 256 threads fill the device; larger blocks loop
+__global__ void __launch_bounds__(kBlock) k_blas_relocate(const uint4* __restrict__ src, uint4* __restrict__ dst, uint32_t nVec, uint32_t nodeDelta,
+                                                          uint32_t idxDelta)
+{
+    const uint32_t stride = gridDim.x * kBlock;
+    for (uint32_t v = blockIdx.x * kBlock + threadIdx.x; v < nVec; v += stride) {
+        uint4 q = src[v];
+        if (v % 3u == 2u) q.x = relocated_first(q.x, q.y, nodeDelta, idxDelta);
+        dst[v] = q;
+    }
+}
+hipError_t relocate(hipStream_t s, const RtBVHNode2* src, RtBVHNode2* dst, uint32_t nNodes, uint32_t nodeDelta, uint32_t idxDelta)
+{
+    static_assert(sizeof(RtBVHNode2) == 48 && offsetof(RtBVHNode2, first) == 32 && offsetof(RtBVHNode2, count) == 36, "k_blas_relocate's vectors");
+    if (nNodes == 0) return hipSuccess;
+    if (nNodes > 0x7fffffffu / 3u) return hipErrorInvalidValue;   // (3 * nNodes vectors are counted in 32 bits: 715 million nodes, 34 GB)
+    if (nodeDelta == 0 && idxDelta == 0) return hipMemcpyAsync(dst, src, sizeof(RtBVHNode2) * (size_t)nNodes, hipMemcpyDeviceToDevice, s);
+    const uint32_t nVec = 3u * nNodes;
+    const uint32_t blocks = std::min<uint32_t>((nVec + kBlock - 1) / kBlock, kRelocateMaxBlocks);
+    hipLaunchKernelGGL(k_blas_relocate, dim3(blocks), dim3(kBlock), 0, s, reinterpret_cast<const uint4*>(src), reinterpret_cast<uint4*>(dst), nVec, nodeDelta, idxDelta);
     return hipGetLastError();
 }
 

@@ -9,8 +9,11 @@
 //   stack        a BLAS of height h (edges, the root counts 0) needs h entries; a context keeps clamp(max h + 1, 6, RT_BVH4_STACK).
 #pragma once
 #include <stdint.h>
+#include <algorithm>
+#include <string>
+#include <utility>
 #include <vector>
-#include "../../include/rt355_types.h"
+#include "../../include/rt355.h"
 #include "refit_common.h"
 
 namespace rebuild {
@@ -133,6 +136,80 @@ inline const char* find_blas_ranges(const RtBVHNode2* n, int32_t nNodes, const u
     ranges.swap(sorted);
     for (int32_t& v : instBlas) v = newOf[(size_t)v];
     return nullptr;
+}
+
+// ---- kept trees (rt_rebuild_ranges, RT_REBUILD_KEEP; host only but for relocated_first) ---------------------------------------------
+// A bound BLAS is compact when the nodes reachable from its root are exactly the ids [root, root + nodes), nodes odd, and its leaves'
+// primIdx ranges tile one interval [idxLo, idxLo + idxSlots) without gap or overlap - what BuildBLAS, the GPU builders and every in-place
+// rebuild or resize produce.  Such a tree moves as a block: node i goes to i - oldRoot + newRoot, and only the `first` word changes.
+struct BlasBlock { uint32_t nodes, idxLo, idxSlots; uint8_t compact; };
+// The relocation rule, one for the kernel (k_blas_relocate) and the host mirror (rth_rebuild_ranges): the `first` word of a record that
+// moves by nodeDelta = newRoot - oldRoot node ids and whose leaves' slots move by idxDelta = newIdxBase - oldIdxBase (both modulo 2^32);
+// an interior record (count == 0) names a child pair, a leaf its first primIdx slot.  Boxes, count and the pad words stay.
+LB_HD uint32_t relocated_first(uint32_t first, uint32_t count, uint32_t nodeDelta, uint32_t idxDelta)
+{
+    return first + (count == 0 ? nodeDelta : idxDelta);
+}
+// The block of every range of a scene find_blas_ranges has accepted (it checked every index followed here and that no node is reachable
+// twice).  A range that is not compact reports the nodes and slots it reaches; naming it RT_REBUILD_KEEP is refused.
+inline void find_blas_blocks(const RtBVHNode2* n, const std::vector<BlasRange>& ranges, std::vector<BlasBlock>& blocks)
+{
+    blocks.assign(ranges.size(), BlasBlock{ 0u, 0u, 0u, 0 });
+    std::vector<uint32_t> stack;
+    std::vector<std::pair<uint32_t, uint32_t>> leaves;
+    for (size_t k = 0; k < ranges.size(); k++) {
+        const uint32_t root = ranges[k].root;
+        uint32_t lo = root, hi = root, m = 0;
+        uint64_t slots = 0;
+        leaves.clear(); stack.assign(1, root);
+        while (!stack.empty()) {
+            const uint32_t i = stack.back(); stack.pop_back();
+            m++; lo = std::min(lo, i); hi = std::max(hi, i);
+            if (n[i].count > 0) { leaves.push_back({ n[i].first, n[i].count }); slots += n[i].count; }
+            else { stack.push_back(n[i].first); stack.push_back(n[i].first + 1); }
+        }
+        std::sort(leaves.begin(), leaves.end());
+        bool tiles = true;
+        for (size_t a = 1; a < leaves.size() && tiles; a++) tiles = leaves[a].first == leaves[a - 1].first + leaves[a - 1].second;
+        blocks[k] = BlasBlock{ m, leaves[0].first, (uint32_t)std::min<uint64_t>(slots, 0xffffffffu),
+                               (uint8_t)(lo == root && hi - lo + 1 == m && (m & 1u) && tiles && slots <= 0x7fffffffu ? 1 : 0) };
+    }
+}
+// The checks of a plan (one RT_REBUILD_* word per range) against the ranges it is for, the blocks where they are known (NULL: every
+// range counts as compact) and the replacement window [first, first + count): RT_OK, or RT_E_INVALID / RT_E_UNSUPPORTED with msg.
+inline int check_plan(const int32_t* plan, int32_t nRanges, const std::vector<BlasRange>& ranges, const BlasBlock* blocks, int32_t first, int32_t count,
+                      std::string& msg)
+{
+    if (!plan) { msg = "null plan"; return RT_E_INVALID; }
+    if (nRanges != (int32_t)ranges.size()) {
+        msg = "the plan has " + std::to_string(nRanges) + " words, the scene " + std::to_string(ranges.size()) + " distinct BLAS";
+        return RT_E_INVALID;
+    }
+    for (int32_t k = 0; k < nRanges; k++) {
+        if (plan[k] == RT_REBUILD_REFIT) { msg = "plan[" + std::to_string(k) + "]: RT_REBUILD_REFIT is not a per-range plan (refit the whole scene with rt_rebuild_scene)"; return RT_E_INVALID; }
+        if (plan[k] != RT_REBUILD_SAH && plan[k] != RT_REBUILD_LBVH && plan[k] != RT_REBUILD_SBVH && plan[k] != RT_REBUILD_KEEP) {
+            msg = "plan[" + std::to_string(k) + "]: unknown word " + std::to_string(plan[k]);
+            return RT_E_INVALID;
+        }
+    }
+    for (int32_t k = 0; k < nRanges; k++) {
+        if (plan[k] != RT_REBUILD_KEEP) continue;
+        const BlasRange& r = ranges[(size_t)k];
+        const std::string name = "BLAS " + std::to_string(k) + " (primitives [" + std::to_string(r.first) + ", " + std::to_string((uint64_t)r.first + r.count) + "))";
+        if (count > 0 && (int64_t)first < (int64_t)r.first + (int64_t)r.count && (int64_t)first + count > (int64_t)r.first) {
+            msg = "the replaced primitives [" + std::to_string(first) + ", " + std::to_string((int64_t)first + count) + ") intersect " + name +
+                  ", which the plan keeps: its boxes would go stale";
+            return RT_E_INVALID;
+        }
+    }
+    for (int32_t k = 0; k < nRanges; k++) {
+        if (plan[k] != RT_REBUILD_KEEP || !blocks || blocks[k].compact) continue;
+        const BlasRange& r = ranges[(size_t)k];
+        msg = "RT_REBUILD_KEEP for BLAS " + std::to_string(k) + " (primitives [" + std::to_string(r.first) + ", " + std::to_string((uint64_t)r.first + r.count) +
+              ")): its bound tree is not compact (its nodes are not exactly the ids [root, root + nodes), or its leaves do not tile one primIdx interval); build it instead";
+        return RT_E_UNSUPPORTED;
+    }
+    return RT_OK;
 }
 
 } // namespace rebuild

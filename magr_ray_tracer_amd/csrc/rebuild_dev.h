@@ -50,4 +50,12 @@ hipError_t mat_emit(hipStream_t s, const Work& w, const RtPrimitive* prims, uint
                     const RtMaterial* mats, uint32_t nLights, uint32_t* lights, RtFloat4* lightRecs);
 hipError_t mat_assign(hipStream_t s, RtPrimitive* prims, const int32_t* assign, uint32_t first, uint32_t count, RtFloat4* shadeRecs);
 
+// rt_rebuild_ranges: one segment of kept nodes - src[0, nNodes) of the live array to dst[0, nNodes) of the set that is not live, every
+// interior record's `first` moved by nodeDelta, every leaf's by idxDelta (rebuild::relocated_first; both modulo 2^32).  The caller merges
+// adjacent kept BLAS with equal deltas into one segment and launches once per segment: after merging a plan has as many segments as
+// runs of kept BLAS between built ones (one or two where one mesh moves beside a static one), so a launch each costs less than
+// uploading a segment table and searching it in every thread, and the deltas stay wave-uniform kernel arguments.  Both deltas zero (the
+// static mesh in front of the moving one): a plain device-to-device copy.
+hipError_t relocate(hipStream_t s, const RtBVHNode2* src, RtBVHNode2* dst, uint32_t nNodes, uint32_t nodeDelta, uint32_t idxDelta);
+
 } // namespace rebuilddev

@@ -758,6 +758,23 @@ extern "C" int rt_rebuild_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t fi
                     "(bind the BVH2 with rt_upload_scene_bvh2, or build on the host and upload)");
     return rebuild_scene(*ctx->scene, prims, first, count, blas, nBlas, builder, opts, stats);
 }
+extern "C" int rt_rebuild_ranges(RtCtx* ctx, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
+                                 const int32_t* plan, int32_t nRanges, const RtBuildOptions* opts, RtRebuildStats* stats)
+{
+    if (!ctx) return fail(RT_E_INVALID, "rt_rebuild_ranges: null context");
+    if (!ctx->sceneLoaded || !ctx->scene) return fail(RT_E_INVALID, "rt_rebuild_ranges: no scene uploaded");
+    if (ctx->cfg.accel != RT_ACCEL_BVH2 && !ctx->scene->keepsBvh2)
+        return fail(RT_E_UNSUPPORTED, "rt_rebuild_ranges: a BVH4 copy bound through rt_upload_scene has lost its BVH2 and cannot rebuild in place "
+                    "(bind the BVH2 with rt_upload_scene_bvh2, or build on the host and upload)");
+    return rebuild_ranges(*ctx->scene, prims, first, count, blas, nBlas, plan, nRanges, opts, stats);
+}
+extern "C" int rt_scene_blas_blocks(RtCtx* ctx, int32_t* n, int32_t* primFirst, int32_t* primCount, int32_t* nodes, int32_t* idxSlots, int32_t* compact, int32_t cap)
+{
+    if (!ctx) return fail(RT_E_INVALID, "rt_scene_blas_blocks: null context");
+    if (!ctx->sceneLoaded || !ctx->scene) return fail(RT_E_INVALID, "rt_scene_blas_blocks: no scene uploaded");
+    if (ctx->cfg.accel != RT_ACCEL_BVH2 && !ctx->scene->keepsBvh2) return fail(RT_E_UNSUPPORTED, "rt_scene_blas_blocks: a BVH4 copy bound through rt_upload_scene has lost its BVH2");
+    return blas_blocks(*ctx->scene, n, primFirst, primCount, nodes, idxSlots, compact, cap);
+}
 static int device_pointer(const RtCtx* ctx, const char* who, const char* name, const void* p, int64_t bytes, int align, bool hostAllowed);   // (below, with rt_trace)
 extern "C" int rt_resize_scene(RtCtx* ctx, const void* prims, int32_t nPrims, const RtSceneShape* shape, int32_t builder, const RtBuildOptions* opts,
                                RtRebuildStats* stats)

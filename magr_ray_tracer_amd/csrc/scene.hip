@@ -147,6 +147,7 @@ static int prepare_update(SceneBag& b, int accel, int extendVariant, const HostS
     if (!b.rebuildRefusal) {   // RT_REBUILD_REFIT: root, interior nodes and height of every BLAS (build_topology has walked the trees: no cycle)
         const RtBVHNode2* n2 = (const RtBVHNode2*)bvhNodes;
         const size_t nR = b.ranges.size();
+        rebuild::find_blas_blocks(n2, b.ranges, b.blasBlock);   // rt_rebuild_ranges: which of them can be kept, and what they occupy
         b.blasRoot.assign(nR, 0u); b.blasInteriors.assign(nR, 0u); b.blasHeight.assign(nR, 0u);
         std::vector<uint8_t> done(nR, 0);
         std::vector<std::pair<uint32_t, uint32_t>> st;
@@ -685,53 +686,81 @@ static int check_builder(const char* who, int32_t builder, const RtBuildOptions*
     if (!(alpha >= 0.0f && alpha <= 1.0f)) return fail(RT_E_INVALID, "%s: alpha must lie in [0, 1]", who);
     return RT_OK;
 }
-// The builders' own argument checks, BLAS by BLAS (node and index ids as the host appends BLAS after BLAS; the SBVH builder's ids
+// The builders' own argument checks, BLAS by BLAS under plan[k], one RT_REBUILD_SAH / LBVH / SBVH / KEEP per range (node and index ids as
+// the host appends BLAS after BLAS: a kept BLAS takes its block's - blocks NULL: a SAH tree's at most - and the ids behind an SBVH tree
 // are known only as the trees are built: its ranges hold at most 2^30 primitives each, and alpha is checked by check_builder)
-static int check_ranges(const char* who, int32_t builder, const RtBuildOptions* opts, int32_t nPrims, const std::vector<rebuild::BlasRange>& ranges, lbvh::Params& P)
+static int check_ranges(const char* who, const int32_t* plan, const RtBuildOptions* opts, int32_t nPrims, const std::vector<rebuild::BlasRange>& ranges,
+                        const rebuild::BlasBlock* blocks, lbvh::Params& P)
 {
-    if (builder == RT_REBUILD_SAH || builder == RT_REBUILD_LBVH) {
-        uint32_t nodeBase = 0, idxBase = 0;
-        for (const rebuild::BlasRange& r : ranges) {
-            const int32_t cap = 2 * (int32_t)r.count - 1;
-            const char* msg = builder == RT_REBUILD_SAH ? sahdev::check_args(nPrims, (int32_t)r.first, (int32_t)r.count, nodeBase, idxBase)
+    uint32_t nodeBase = 0, idxBase = 0;
+    for (size_t k = 0; k < ranges.size(); k++) {
+        const rebuild::BlasRange& r = ranges[k];
+        const uint32_t cap = 2 * r.count - 1;
+        if (plan[k] == RT_REBUILD_SAH || plan[k] == RT_REBUILD_LBVH) {
+            const char* msg = plan[k] == RT_REBUILD_SAH ? sahdev::check_args(nPrims, (int32_t)r.first, (int32_t)r.count, nodeBase, idxBase)
                                                         : lbvhdev::check_args(opts, nPrims, (int32_t)r.first, (int32_t)r.count, nodeBase, idxBase, P);
             if (msg) return fail(RT_E_INVALID, "%s: %s", who, msg);
-            nodeBase += (uint32_t)cap; idxBase += r.count;
+            nodeBase += cap; idxBase += r.count;
+        } else if (plan[k] == RT_REBUILD_SBVH) {
+            if (r.count == 0 || r.count > (1u << 30)) return fail(RT_E_INVALID, "%s: a BLAS of %u primitives", who, r.count);
+        } else {
+            nodeBase += blocks ? blocks[k].nodes : cap; idxBase += blocks ? blocks[k].idxSlots : r.count;
         }
-    } else if (builder == RT_REBUILD_SBVH) {
-        for (const rebuild::BlasRange& r : ranges) if (r.count == 0 || r.count > (1u << 30)) return fail(RT_E_INVALID, "%s: a BLAS of %u primitives", who, r.count);
     }
+    return RT_OK;
+}
+// alpha, when a plan has an SBVH range (check_builder's rule)
+static int check_plan_alpha(const char* who, const int32_t* plan, size_t n, const RtBuildOptions* opts)
+{
+    for (size_t k = 0; k < n; k++) if (plan[k] == RT_REBUILD_SBVH) return check_builder(who, RT_REBUILD_SBVH, opts, false);
     return RT_OK;
 }
 
 // The one body of rt_rebuild_scene and rt_resize_scene.  A rebuild (newPrims NULL) keeps the bound shape `sh` and takes the replacement
 // records prims / first / count and blas as rt_update_scene does; a resize builds the caller's shape over newPrims (host or device memory,
-// sh.nPrims records), blas (NULL: identity) carrying the transforms.  The arguments have passed the checks that need no device.
+// sh.nPrims records), blas (NULL: identity) carrying the transforms.  plan[k] says what becomes of range k: built with RT_REBUILD_SAH /
+// LBVH / SBVH, or (RT_REBUILD_KEEP, a rebuild of a compact bound tree only) its bound tree moved to where the new scene numbers it; an
+// empty plan is RT_REBUILD_REFIT of the whole scene.  The arguments have passed the checks that need no device.
 static int rebuild_body(SceneBag& b, const char* who, const Shape& sh, const void* newPrims, const RtPrimitive* prims, int32_t first, int32_t count,
-                        const RtBVHInstance* blas, int32_t builder, const RtBuildOptions* opts, const lbvh::Params& P, RtRebuildStats* stats)
+                        const RtBVHInstance* blas, const std::vector<int32_t>& plan, const RtBuildOptions* opts, const lbvh::Params& P, RtRebuildStats* stats)
 {
     using clock = std::chrono::steady_clock;
     const auto t0 = clock::now();
     const bool resize = newPrims != nullptr;
-    const bool sbvh = builder == RT_REBUILD_SBVH, refit = builder == RT_REBUILD_REFIT;   // (refit: no builder runs, opts is ignored)
-    const float alpha = sbvh && opts ? opts->alpha : 0.0f;
+    const bool refit = plan.empty();   // (refit: no builder runs, opts is ignored)
+    const float alpha = opts ? opts->alpha : 0.0f;   // (read by SBVH ranges only; check_builder has seen it if there is one)
     const std::vector<rebuild::BlasRange>& ranges = *sh.ranges;
     const std::vector<int32_t>& instBlas = *sh.instBlas;
     const size_t nR = ranges.size();
+    // what the ranges behind range k need that is known beforehand: a kept tree its block, a SAH or LBVH tree count slots and
+    // 2 * count - 1 nodes at most (an SBVH tree is sized when it is built: size, then place)
+    std::vector<size_t> restIdx(nR + 1, 0), restNodes(nR + 1, 0);
+    bool anyKnown = false;
+    for (size_t k = nR; k-- > 0 && !refit;) {
+        const bool keep = plan[k] == RT_REBUILD_KEEP, known = keep || plan[k] != RT_REBUILD_SBVH;
+        restIdx[k] = restIdx[k + 1] + (keep ? b.blasBlock[k].idxSlots : known ? ranges[k].count : 0u);
+        restNodes[k] = restNodes[k + 1] + (keep ? b.blasBlock[k].nodes : known ? 2 * (size_t)ranges[k].count - 1 : 0u);
+        anyKnown = anyKnown || known;
+    }
     HIPCHK(hipSetDevice(b.device));
     SceneBag::RebuildSet& t = b.rset[b.rnext];
     if (const int rc = rebuild_alloc(b, t, sh, resize)) return rc;
     hipStream_t s = b.stream;
     if (refit) {   // room for the bound trees (nR spare nodes: see the SBVH builder below)
         if (const int rc = rebuild_reserve(b, t, nR, (size_t)b.nIdx, (size_t)b.nNodes + nR, 0, 0)) return rc;
-    } else if (!sbvh) {
-        // room for every tree these builders can make (a set or the scratch that started smaller, or has only held SBVH trees so far)
-        if (const int rc = rebuild_reserve(b, t, nR, (size_t)sh.nPrims, 2 * (size_t)sh.nPrims, 0, 0)) return rc;
-        // the builders' workspace
+    } else if (anyKnown) {
+        // room for the kept trees and for every tree the SAH and the linear builder can make (a set or the scratch that started smaller,
+        // or has only held SBVH trees so far); nR spare nodes: see the SBVH builder below.  With every range built by those two this is
+        // nPrims slots and 2 * nPrims nodes for ranges that tile the primitives
+        if (restIdx[0] > 0x7fffffffull || restNodes[0] + nR > 0x7fffffffull)
+            return fail(RT_E_UNSUPPORTED, "%s: the new trees have 2^31 nodes or index slots, or more; the scene is unchanged", who);
+        if (const int rc = rebuild_reserve(b, t, nR, restIdx[0], restNodes[0] + nR, 0, 0)) return rc;
+        // the builders' workspace, over the ranges they build
         size_t need = 0;
-        for (const rebuild::BlasRange& r : ranges) {
+        for (size_t k = 0; k < nR; k++) {
+            if (plan[k] != RT_REBUILD_SAH && plan[k] != RT_REBUILD_LBVH) continue;
             size_t bytes = 0;
-            const int rc = builder == RT_REBUILD_SAH ? sahdev::work_bytes(who, r.count, s, &bytes) : lbvhdev::work_bytes(who, r.count, s, &bytes);
+            const int rc = plan[k] == RT_REBUILD_SAH ? sahdev::work_bytes(who, ranges[k].count, s, &bytes) : lbvhdev::work_bytes(who, ranges[k].count, s, &bytes);
             if (rc != RT_OK) return rc;
             need = std::max(need, bytes);
         }
@@ -777,8 +806,9 @@ static int rebuild_body(SceneBag& b, const char* who, const Shape& sh, const voi
     }
     const auto t1 = clock::now();
     // ---- every BLAS anew, in the order of the ranges (a refit: the bound trees, their boxes anew)
-    std::vector<uint32_t> rootOf(nR), interiors(nR), depth(nR);
+    std::vector<uint32_t> rootOf(nR), interiors(nR), depth(nR), idxOf(nR), slotsOf(nR);
     uint32_t nNodes = 0, nIdx = 0, maxDepth = 0;
+    int32_t nBuilt = 0;
     uint64_t spatialSplits = 0, primsClipped = 0;
     if (refit) {
         // the bound trees and their refit topology into the set, then the boxes anew: no BLAS is built, so node ids, leaf ranges,
@@ -793,10 +823,38 @@ static int rebuild_body(SceneBag& b, const char* who, const Shape& sh, const voi
         rootOf = b.blasRoot; interiors = b.blasInteriors; depth = b.blasHeight;
         for (size_t k = 0; k < nR; k++) maxDepth = std::max(maxDepth, depth[k]);
     }
+    // Kept trees move as segments: adjacent kept BLAS whose node and index offsets agree are one (rebuilddev::relocate), and their
+    // primIdx slots, whose values are global primitive ids of a range that did not move, one plain copy.  A segment is queued when the
+    // next range does not extend it, so before anything else touches the set.
+    struct Segment { uint32_t srcNode = 0, dstNode = 0, nNodes = 0, nodeDelta = 0, srcIdx = 0, dstIdx = 0, nIdx = 0, idxDelta = 0; } seg;
+    auto flush = [&]() -> int {
+        if (!seg.nNodes) return RT_OK;
+        HIPCHK(rebuilddev::relocate(s, sc.bvh2 + seg.srcNode, t.nodes.p + seg.dstNode, seg.nNodes, seg.nodeDelta, seg.idxDelta));
+        HIPCHK(hipMemcpyAsync(t.primIdx.p + seg.dstIdx, sc.primIdx + seg.srcIdx, sizeof(uint32_t) * (size_t)seg.nIdx, hipMemcpyDeviceToDevice, s));
+        seg = Segment{};
+        return RT_OK;
+    };
     for (size_t k = 0; k < nR && !refit; k++) {
         const rebuild::BlasRange& r = ranges[k];
         Built built{};
         uint32_t slots = r.count;
+        const bool sbvh = plan[k] == RT_REBUILD_SBVH;
+        if (plan[k] == RT_REBUILD_KEEP) {   // (room: reserved above; the bound values stand for the builder's)
+            const rebuild::BlasBlock& blk = b.blasBlock[k];
+            const uint32_t nodeDelta = nNodes - b.blasRoot[k], idxDelta = nIdx - blk.idxLo;
+            if (seg.nNodes && seg.nodeDelta == nodeDelta && seg.idxDelta == idxDelta && seg.srcNode + seg.nNodes == b.blasRoot[k] && seg.srcIdx + seg.nIdx == blk.idxLo) {
+                seg.nNodes += blk.nodes; seg.nIdx += blk.idxSlots;
+            } else {
+                if (const int rc = flush()) return rc;
+                seg = Segment{ b.blasRoot[k], nNodes, blk.nodes, nodeDelta, blk.idxLo, nIdx, blk.idxSlots, idxDelta };
+            }
+            rootOf[k] = nNodes; interiors[k] = b.blasInteriors[k]; depth[k] = b.blasHeight[k]; idxOf[k] = nIdx; slotsOf[k] = blk.idxSlots;
+            maxDepth = std::max(maxDepth, depth[k]);
+            nNodes += blk.nodes; nIdx += blk.idxSlots;
+            continue;
+        }
+        if (const int rc = flush()) return rc;
+        nBuilt++;
         if (sbvh) {
             // size, then place: the tree stays in the builder's own memory until the set has room for it (one tree at a time)
             struct TreeGuard { sbvhdev::Tree* p = nullptr; ~TreeGuard() { sbvhdev::destroy(p); } } tree;
@@ -805,12 +863,15 @@ static int rebuild_body(SceneBag& b, const char* who, const Shape& sh, const voi
             if (sb.nIdx == 0 || (uint64_t)nNodes + sb.nodes + nR > 0x7fffffffull || (uint64_t)nIdx + sb.nIdx > 0x7fffffffull)
                 return fail(RT_E_UNSUPPORTED, "%s: the new trees have 2^31 nodes or index slots, or more; the scene is unchanged", who);
             // (nR spare nodes: the leaf and pair arrays hold half the node capacity, and k trees have k leaves more than interior nodes)
-            if (const int rc = rebuild_reserve(b, t, nR, (size_t)nIdx + sb.nIdx, (size_t)nNodes + sb.nodes + nR, nIdx, nNodes)) return rc;
+            // (... and what the ranges behind this one are known to need)
+            if ((uint64_t)nNodes + sb.nodes + restNodes[k + 1] + nR > 0x7fffffffull || (uint64_t)nIdx + sb.nIdx + restIdx[k + 1] > 0x7fffffffull)
+                return fail(RT_E_UNSUPPORTED, "%s: the new trees have 2^31 nodes or index slots, or more; the scene is unchanged", who);
+            if (const int rc = rebuild_reserve(b, t, nR, (size_t)nIdx + sb.nIdx + restIdx[k + 1], (size_t)nNodes + sb.nodes + restNodes[k + 1] + nR, nIdx, nNodes)) return rc;
             if (const int rc = sbvhdev::emit(who, s, tree.p, t.nodes.p + nNodes, t.primIdx.p + nIdx)) return rc;
             built.nodes = sb.nodes; built.depth = sb.depth; slots = sb.nIdx;
             spatialSplits += sb.spatialSplits; primsClipped += sb.primsClipped;
         } else {
-            const int rc = builder == RT_REBUILD_SAH
+            const int rc = plan[k] == RT_REBUILD_SAH
                 ? sahdev::build(who, s, b.rwork.p, t.prims.p + r.first, r.count, r.first, nNodes, nIdx, t.nodes.p + nNodes, t.primIdx.p + nIdx, nullptr, nullptr, &built)
                 : lbvhdev::build(who, s, b.rwork.p, P, t.prims.p + r.first, r.count, r.first, nNodes, nIdx, t.nodes.p + nNodes, t.primIdx.p + nIdx, nullptr, nullptr, &built);
             if (rc != RT_OK) return rc;
@@ -822,10 +883,11 @@ static int rebuild_body(SceneBag& b, const char* who, const Shape& sh, const voi
         if (rebuild::exceeds_stack(built.depth))   // validate_scene's rule
             return fail(RT_E_UNSUPPORTED, "%s: the new BLAS %zu needs %u stack entries, at most %d are supported; the scene is unchanged", who, k,
                         built.depth, RT_BVH4_STACK);
-        rootOf[k] = nNodes; interiors[k] = (built.nodes - 1) / 2; depth[k] = built.depth;
+        rootOf[k] = nNodes; interiors[k] = (built.nodes - 1) / 2; depth[k] = built.depth; idxOf[k] = nIdx; slotsOf[k] = slots;
         maxDepth = std::max(maxDepth, built.depth);
         nNodes += built.nodes; nIdx += slots;
     }
+    if (const int rc = flush()) return rc;
     if (!refit) if (const int rc = rebuild_scratch(b, (size_t)nNodes + nR)) return rc;
     const bool bvh4 = b.accel == RT_ACCEL_BVH4;
     if (bvh4) if (const int rc = collapse_scratch(b, (size_t)nNodes + nR)) return rc;
@@ -955,6 +1017,10 @@ static int rebuild_body(SceneBag& b, const char* who, const Shape& sh, const voi
     b.nNodes = (int32_t)nNodes; b.nIdx = (int32_t)nIdx; b.nPairs = layout1 && !bvh4 ? (int32_t)nPairs : 0; b.nLeaves = nLeaves;
     if (!refit) b.nReach = nNodes;
     b.nQuads = layout1 && bvh4 ? (int32_t)c4st[collapsedev::kLive - collapsedev::kStatus] : 0;
+    if (!refit) {   // (a refit moves no tree: the blocks stay)
+        b.blasBlock.resize(nR);
+        for (size_t k = 0; k < nR; k++) b.blasBlock[k] = rebuild::BlasBlock{ 2 * interiors[k] + 1, idxOf[k], slotsOf[k], 1 };
+    }
     b.blasRoot = rootOf; b.blasInteriors = interiors; b.blasHeight = depth;
     if (bvh4) {   // the live collapse's tables follow the sets
         b.liveNewId = t.newId.p; b.liveQuadNode = t.quadNode.p;
@@ -977,7 +1043,7 @@ static int rebuild_body(SceneBag& b, const char* who, const Shape& sh, const voi
         stats->stage_ms = ms_between(t0, t1); stats->build_ms = ms_between(t1, t2); stats->derive_ms = derive; stats->tlas_ms = tlas;
         if (refit) { float fit = 0; (void)hipEventElapsedTime(&fit, b.rev[0], b.rev[1]); stats->build_ms = fit; }   // (GPU: the staging copies and the refit)
         stats->commit_ms = ms_between(t3, t4);
-        stats->prims = resize ? sh.nPrims : count; stats->blas_built = refit ? 0 : (int32_t)nR; stats->nodes = (int32_t)nNodes; stats->n_idx = (int32_t)nIdx;
+        stats->prims = resize ? sh.nPrims : count; stats->blas_built = nBuilt; stats->nodes = (int32_t)nNodes; stats->n_idx = (int32_t)nIdx;
         stats->max_depth = (int32_t)maxDepth; stats->tlas_nodes = b.nTlas; stats->tlas_depth = status[1]; stats->reconfigured = reconfigure ? 1 : 0;
         stats->spatial_splits = (int32_t)std::min<uint64_t>(spatialSplits, 0x7fffffffu); stats->prims_clipped = (int32_t)std::min<uint64_t>(primsClipped, 0x7fffffffu);
     }
@@ -993,9 +1059,67 @@ int scenedev::rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first
     if (const int rc = check_builder(who, builder, opts, true)) return rc;
     if (const int rc = check_change(who, b, prims, first, count, blas, nBlas, "")) return rc;
     lbvh::Params P{};
-    if (const int rc = check_ranges(who, builder, opts, b.nPrims, b.ranges, P)) return rc;
+    const std::vector<int32_t> plan(builder == RT_REBUILD_REFIT ? 0 : b.ranges.size(), builder);   // every range: `builder`
+    if (!plan.empty()) if (const int rc = check_ranges(who, plan.data(), opts, b.nPrims, b.ranges, nullptr, P)) return rc;
     const Shape sh{ b.nPrims, b.nBlas, b.nLights, &b.ranges, &b.instBlas };
-    return rebuild_body(b, who, sh, nullptr, prims, first, count, blas, builder, opts, P, stats);
+    return rebuild_body(b, who, sh, nullptr, prims, first, count, blas, plan, opts, P, stats);
+}
+// The checks of a plan that need no device: the plan itself (rebuild::check_plan), alpha and the builders' own argument checks
+static int plan_check_args(const char* who, int32_t nPrims, const std::vector<rebuild::BlasRange>& ranges, const rebuild::BlasBlock* blocks, const int32_t* plan,
+                           int32_t nRanges, int32_t first, int32_t count, const RtBuildOptions* opts, lbvh::Params& P)
+{
+    std::string msg;
+    if (const int rc = rebuild::check_plan(plan, nRanges, ranges, blocks, first, count, msg)) return fail(rc, "%s: %s", who, msg.c_str());
+    if (const int rc = check_plan_alpha(who, plan, ranges.size(), opts)) return rc;
+    return check_ranges(who, plan, opts, nPrims, ranges, blocks, P);
+}
+extern "C" int rt_rebuild_ranges_check(int32_t nPrims, const int32_t* rangeFirst, const int32_t* rangeCount, const int32_t* compact, int32_t nBound,
+                                       const int32_t* plan, int32_t nRanges, int32_t first, int32_t count, const RtBuildOptions* opts)
+{
+    const char* who = "rt_rebuild_ranges";
+    if (nPrims <= 0 || nBound <= 0 || !rangeFirst || !rangeCount) return fail(RT_E_INVALID, "%s: the ranges of at least one BLAS are needed (nPrims %d, %d ranges)", who, nPrims, nBound);
+    std::vector<rebuild::BlasRange> ranges((size_t)nBound);
+    std::vector<rebuild::BlasBlock> blocks((size_t)nBound);
+    int64_t next = 0;
+    for (int32_t k = 0; k < nBound; k++) {
+        if (rangeCount[k] < 1 || rangeFirst[k] < next || (int64_t)rangeFirst[k] + rangeCount[k] > (int64_t)nPrims)
+            return fail(RT_E_INVALID, "%s: range %d (first %d, count %d): ranges hold at least one primitive, lie in [0, %d) and come in increasing order without overlap",
+                        who, k, rangeFirst[k], rangeCount[k], nPrims);
+        next = (int64_t)rangeFirst[k] + rangeCount[k];
+        ranges[(size_t)k] = rebuild::BlasRange{ 0u, (uint32_t)rangeFirst[k], (uint32_t)rangeCount[k] };
+        blocks[(size_t)k] = rebuild::BlasBlock{ 2 * (uint32_t)rangeCount[k] - 1, 0u, (uint32_t)rangeCount[k], (uint8_t)(!compact || compact[k] ? 1 : 0) };
+    }
+    if (count < 0 || (count > 0 && (first < 0 || (int64_t)first + count > (int64_t)nPrims)))
+        return fail(RT_E_INVALID, "%s: primitive range [%d, %lld) outside the %d uploaded", who, first, (long long)first + count, nPrims);
+    lbvh::Params P{};
+    return plan_check_args(who, nPrims, ranges, blocks.data(), plan, nRanges, first, count, opts, P);
+}
+int scenedev::rebuild_ranges(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
+                             const int32_t* plan, int32_t nRanges, const RtBuildOptions* opts, RtRebuildStats* stats)
+{
+    const char* who = "rt_rebuild_ranges";
+    // ---- refusals that need no device work
+    if (b.refitRefusal) return fail(RT_E_UNSUPPORTED, "%s: %s", who, b.refitRefusal);
+    if (b.rebuildRefusal) return fail(RT_E_UNSUPPORTED, "%s: %s", who, b.rebuildRefusal);
+    if (const int rc = check_change(who, b, prims, first, count, blas, nBlas, "")) return rc;
+    lbvh::Params P{};
+    if (const int rc = plan_check_args(who, b.nPrims, b.ranges, b.blasBlock.data(), plan, nRanges, first, count, opts, P)) return rc;
+    const Shape sh{ b.nPrims, b.nBlas, b.nLights, &b.ranges, &b.instBlas };
+    return rebuild_body(b, who, sh, nullptr, prims, first, count, blas, std::vector<int32_t>(plan, plan + nRanges), opts, P, stats);
+}
+int scenedev::blas_blocks(const SceneBag& b, int32_t* n, int32_t* primFirst, int32_t* primCount, int32_t* nodes, int32_t* idxSlots, int32_t* compact, int32_t cap)
+{
+    if (b.rebuildRefusal) return fail(RT_E_UNSUPPORTED, "rt_scene_blas_blocks: %s", b.rebuildRefusal);
+    if (b.blasBlock.size() != b.ranges.size()) return fail(RT_E_UNSUPPORTED, "rt_scene_blas_blocks: %s", b.refitRefusal ? b.refitRefusal : "the scene's BLAS ranges are not known");
+    if (n) *n = (int32_t)b.ranges.size();
+    for (size_t k = 0; k < b.ranges.size() && (int64_t)k < (int64_t)cap; k++) {
+        if (primFirst) primFirst[k] = (int32_t)b.ranges[k].first;
+        if (primCount) primCount[k] = (int32_t)b.ranges[k].count;
+        if (nodes) nodes[k] = (int32_t)b.blasBlock[k].nodes;
+        if (idxSlots) idxSlots[k] = (int32_t)b.blasBlock[k].idxSlots;
+        if (compact) compact[k] = b.blasBlock[k].compact;
+    }
+    return RT_OK;
 }
 
 // The ranges of a caller's shape as the builders take them (root: assigned by the build)
@@ -1016,7 +1140,8 @@ static int resize_check_args(const char* who, int32_t nPrims, const RtSceneShape
     if (resize::check_shape(nPrims, shape->nRanges, shape->rangeCount, shape->nBlas, shape->instRange, shape->blas, msg)) return fail(RT_E_INVALID, "%s: %s", who, msg.c_str());
     if (const int rc = check_builder(who, builder, opts, false)) return rc;
     ranges = shape_ranges(*shape);
-    return check_ranges(who, builder, opts, nPrims, ranges, P);
+    const std::vector<int32_t> plan(ranges.size(), builder);
+    return check_ranges(who, plan.data(), opts, nPrims, ranges, nullptr, P);
 }
 extern "C" int rt_resize_check(int32_t nPrims, const RtSceneShape* shape, int32_t builder, const RtBuildOptions* opts)
 {
@@ -1045,7 +1170,7 @@ int scenedev::resize_scene(SceneBag& b, const void* prims, int32_t nPrims, const
     }
     const std::vector<int32_t> instBlas(shape->instRange, shape->instRange + shape->nBlas);
     const Shape sh{ nPrims, shape->nBlas, 0, &ranges, &instBlas };
-    return rebuild_body(b, who, sh, prims, nullptr, 0, 0, shape->blas, builder, opts, P, stats);
+    return rebuild_body(b, who, sh, prims, nullptr, 0, 0, shape->blas, std::vector<int32_t>(ranges.size(), builder), opts, P, stats);   // (never RT_REBUILD_KEEP)
 }
 
 // ---- in-place material updates (rt_update_materials; kernels: rebuild.hip, rules: resize_common.h) -------------------------------------
@@ -1190,6 +1315,25 @@ extern "C" int rt_blas_ranges(const RtBVHNode2* nodes, int32_t nNodes, const uin
     for (int32_t i = 0; i < nBlas; i++) {
         if (firstOut) firstOut[i] = (int32_t)ranges[(size_t)instBlas[(size_t)i]].first;
         if (countOut) countOut[i] = (int32_t)ranges[(size_t)instBlas[(size_t)i]].count;
+    }
+    return RT_OK;
+}
+// ... and the block of every distinct BLAS, in the order a plan names them (rt_rebuild_ranges), as rt_upload_scene finds them
+extern "C" int rt_blas_blocks(const RtBVHNode2* nodes, int32_t nNodes, const uint32_t* primIdx, int32_t nIdx, int32_t nPrims, const RtBVHInstance* blas, int32_t nBlas,
+                              int32_t* n, int32_t* primFirst, int32_t* primCount, int32_t* nodesOut, int32_t* idxSlots, int32_t* compact, int32_t cap)
+{
+    std::vector<rebuild::BlasRange> ranges; std::vector<int32_t> instBlas;
+    if (const char* why = rebuild::find_blas_ranges(nodes, nNodes, primIdx, nIdx, nPrims, blas, nBlas, ranges, instBlas))
+        return fail(why == std::string("missing array") ? RT_E_INVALID : RT_E_UNSUPPORTED, "rt_blas_blocks: %s", why);
+    std::vector<rebuild::BlasBlock> blocks;
+    rebuild::find_blas_blocks(nodes, ranges, blocks);
+    if (n) *n = (int32_t)ranges.size();
+    for (size_t k = 0; k < ranges.size() && (int64_t)k < (int64_t)cap; k++) {
+        if (primFirst) primFirst[k] = (int32_t)ranges[k].first;
+        if (primCount) primCount[k] = (int32_t)ranges[k].count;
+        if (nodesOut) nodesOut[k] = (int32_t)blocks[k].nodes;
+        if (idxSlots) idxSlots[k] = (int32_t)blocks[k].idxSlots;
+        if (compact) compact[k] = blocks[k].compact;
     }
     return RT_OK;
 }

@@ -91,6 +91,9 @@ struct SceneBag {
     // collapse of a BVH4 copy that keeps its BVH2: node -> live id and live id -> node (the upload's own arrays or the live set's, never
     // scratch: a refused call in between must leave them), the live nodes and the stack need as the collapse counted it
     std::vector<uint32_t> blasRoot, blasInteriors, blasHeight;
+    // ... and what RT_REBUILD_KEEP (rt_rebuild_ranges) needs of them: the block of nodes and index slots each live tree occupies (an
+    // SBVH tree has more slots than primitives), and whether it can move as one (rebuild_common.h)
+    std::vector<rebuild::BlasBlock> blasBlock;
     uint32_t *liveNewId = nullptr, *liveQuadNode = nullptr;
     uint32_t nLive = 0, c4Need = 0;
     RtRefitInfo refitInfo{};                  // the last successful RT_REBUILD_REFIT (rt_refit_info)
@@ -162,6 +165,11 @@ int upload_scene(SceneBag& b, int accel, int extendVariant, const HostScene& in,
 int update_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas, RtUpdateStats* stats);
 int rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
                   int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats);
+// rt_rebuild_ranges (include/rt355.h): plan[nRanges], one RT_REBUILD_SAH / LBVH / SBVH / KEEP per distinct BLAS in the order of b.ranges
+int rebuild_ranges(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
+                   const int32_t* plan, int32_t nRanges, const RtBuildOptions* opts, RtRebuildStats* stats);
+// rt_scene_blas_blocks: the ranges and blocks of the bound trees (any output may be NULL; at most cap entries are written)
+int blas_blocks(const SceneBag& b, int32_t* n, int32_t* primFirst, int32_t* primCount, int32_t* nodes, int32_t* idxSlots, int32_t* compact, int32_t cap);
 // rt_resize_scene (include/rt355.h): the caller's shape, checked by resize::check_shape; prims may be host or device memory
 int resize_scene(SceneBag& b, const void* prims, int32_t nPrims, const RtSceneShape* shape, int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats);
 // rt_update_materials (include/rt355.h): texels / primMat may be host or device memory (the caller has applied the pointer rule)

@@ -249,6 +249,13 @@ int rth_rebuild(RthScene* s, int builder, const RtBuildOptions* opts)
     catch (const LbvhError& e) { g_herr = e.what(); return e.code; }
     catch (const std::exception& e) { g_herr = e.what(); return RT_E_NOMEM; }
 }
+int rth_rebuild_ranges(RthScene* s, const int32_t* plan, int nRanges, const RtBuildOptions* opts)
+{
+    if (!s || !s->scene.bvh2) { g_herr = "rth_rebuild_ranges: null scene"; return RT_E_INVALID; }
+    try { s->scene.bvh2->RebuildRanges(plan, nRanges, opts); return 0; }
+    catch (const LbvhError& e) { g_herr = e.what(); return e.code; }
+    catch (const std::exception& e) { g_herr = e.what(); return RT_E_NOMEM; }
+}
 int rth_blas_ranges(RthScene* s, int32_t* firstOut, int32_t* countOut)
 {
     if (!s || !s->scene.bvh2) { g_herr = "rth_blas_ranges: null scene"; return RT_E_INVALID; }
@@ -278,6 +285,13 @@ int rth_add_instance(RthScene* s, int blas, const float invT[16])
     }
     try { s->scene.blasNodes.push_back(inst); } catch (const std::exception& e) { g_herr = e.what(); return -1; }
     return (int)s->scene.blasNodes.size() - 1;
+}
+int rth_swap_instances(RthScene* s, int a, int b)
+{
+    const int n = s ? (int)s->scene.blasNodes.size() : 0;
+    if (a < 0 || b < 0 || a >= n || b >= n) { g_herr = "rth_swap_instances: bad index"; return -1; }
+    std::swap(s->scene.blasNodes[(size_t)a], s->scene.blasNodes[(size_t)b]);
+    return 0;
 }
 int rth_light_list(const RtPrimitive* prims, int32_t nPrims, const RtMaterial* mats, int32_t nMats, uint32_t* out)
 {

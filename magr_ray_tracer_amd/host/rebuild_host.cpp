@@ -1,7 +1,9 @@
 // rebuild_host.cpp — the host restatement of rt_rebuild_scene's BLAS rebuild (BVH2::Rebuild, rth_rebuild, include/rt355_host.h): every
 // distinct BLAS of the scene is built again over the primitive range it covers (csrc/rebuild_common.h finds the ranges), in increasing
 // order of the ranges and appended the way BuildBLAS appends BLAS after BLAS, with the host restatement of the chosen GPU builder.
-// Together with TLAS::Build it is the ground truth the device rebuild must match bit for bit.
+// Together with TLAS::Build it is the ground truth the device rebuild must match bit for bit.  Under a per-range plan
+// (BVH2::RebuildRanges, rth_rebuild_ranges: rt_rebuild_ranges' restatement) a BLAS the plan keeps is appended as its bound block of
+// nodes, relocated by the rule the device kernel applies (rebuild::relocated_first).
 #include <cstring>
 #include <string>
 #include <vector>
@@ -26,21 +28,62 @@ void BVH2::Rebuild(int builder, const RtBuildOptions* opt)
 {
     if (builder != RT_REBUILD_SAH && builder != RT_REBUILD_LBVH && builder != RT_REBUILD_SBVH)
         throw LbvhError(RT_E_INVALID, "rth_rebuild: unknown builder " + std::to_string(builder));
-    const bool sbvh = builder == RT_REBUILD_SBVH;
-    const float a = sbvh && opt ? opt->alpha : 0.0f;   // (NULL or a zero-filled record: the full SBVH)
-    if (!(a >= 0.0f && a <= 1.0f)) throw LbvhError(RT_E_INVALID, "rth_rebuild: alpha must lie in [0, 1]");
-    if (bvhNodes.empty() || blasNodes.empty()) throw LbvhError(RT_E_INVALID, "rth_rebuild: the scene has no BLAS (BuildBLAS comes first)");
+    RebuildPlan("rth_rebuild", &builder, -1, opt);
+}
+// rt_rebuild_ranges' restatement: plan[nRanges], one word per distinct BLAS in increasing order of the ranges; a kept BLAS is appended
+// as its bound block, relocated by the rule the kernel applies (rebuild::relocated_first).
+void BVH2::RebuildRanges(const int32_t* plan, int nRanges, const RtBuildOptions* opt) { RebuildPlan("rth_rebuild_ranges", plan, nRanges, opt); }
+// The one loop of both: nRanges < 0 means "every range: plan[0]" (checked by the caller).
+void BVH2::RebuildPlan(const char* who, const int32_t* plan, int nRanges, const RtBuildOptions* opt)
+{
+    const std::string pre = std::string(who) + ": ";
+    if (nRanges < 0) {   // (rth_rebuild answers a bad alpha before it looks at the scene)
+        const float a0 = plan[0] == RT_REBUILD_SBVH && opt ? opt->alpha : 0.0f;
+        if (!(a0 >= 0.0f && a0 <= 1.0f)) throw LbvhError(RT_E_INVALID, pre + "alpha must lie in [0, 1]");
+    }
+    if (bvhNodes.empty() || blasNodes.empty()) throw LbvhError(RT_E_INVALID, pre + "the scene has no BLAS (BuildBLAS comes first)");
     std::vector<int32_t> instBlas;
-    const std::vector<rebuild::BlasRange> ranges = BlasRangesHost(bvhNodes, primIdx, primitives_.size(), blasNodes, instBlas);
+    std::vector<rebuild::BlasRange> ranges;
+    if (const char* why = rebuild::find_blas_ranges(bvhNodes.data(), (int32_t)bvhNodes.size(), primIdx.data(), (int32_t)primIdx.size(), (int32_t)primitives_.size(),
+                                                    blasNodes.data(), (int32_t)blasNodes.size(), ranges, instBlas))
+        throw LbvhError(RT_E_UNSUPPORTED, pre + why);
+    std::vector<int32_t> words(ranges.size(), nRanges < 0 ? plan[0] : 0);
+    std::vector<rebuild::BlasBlock> blocks;
+    if (nRanges >= 0) {
+        rebuild::find_blas_blocks(bvhNodes.data(), ranges, blocks);
+        std::string msg;
+        if (const int rc = rebuild::check_plan(plan, nRanges, ranges, blocks.data(), 0, 0, msg)) throw LbvhError(rc, pre + msg);
+        words.assign(plan, plan + nRanges);
+    }
+    bool anySbvh = false;
+    for (const int32_t w : words) anySbvh = anySbvh || w == RT_REBUILD_SBVH;
+    const float a = anySbvh && opt ? opt->alpha : 0.0f;   // (NULL or a zero-filled record: the full SBVH)
+    if (!(a >= 0.0f && a <= 1.0f)) throw LbvhError(RT_E_INVALID, pre + "alpha must lie in [0, 1]");
     std::vector<RtBVHNode2> nodes;
     std::vector<uint32_t> idx, roots;
     uint32_t depth = 0, spatialSplits = 0, primsClipped = 0, forcedLeaves = 0; float cost = 0, wall = 0;
-    auto too_deep = [](const rebuild::BlasRange& r, int d) {   // rt_rebuild_scene's rule (validate_scene's): rt_upload_scene would refuse this tree
-        return LbvhError(RT_E_UNSUPPORTED, "rth_rebuild: the new BLAS over primitives [" + std::to_string(r.first) + ", " + std::to_string(r.first + r.count) +
+    auto too_deep = [&pre](const rebuild::BlasRange& r, int d) {   // rt_rebuild_scene's rule (validate_scene's): rt_upload_scene would refuse this tree
+        return LbvhError(RT_E_UNSUPPORTED, pre + "the new BLAS over primitives [" + std::to_string(r.first) + ", " + std::to_string(r.first + r.count) +
                          ") needs " + std::to_string(d) + " stack entries, at most " + std::to_string(RT_BVH4_STACK) + " are supported");
     };
-    for (const rebuild::BlasRange& r : ranges) {
+    for (size_t k = 0; k < ranges.size(); k++) {
+        const rebuild::BlasRange& r = ranges[k];
+        const int builder = words[k];
+        const bool sbvh = builder == RT_REBUILD_SBVH;
         const uint32_t nodeBase = (uint32_t)nodes.size(), idxBase = (uint32_t)idx.size();
+        if (builder == RT_REBUILD_KEEP) {   // the bound block, relocated; its primIdx slots as they are
+            const rebuild::BlasBlock& blk = blocks[k];
+            if (nodes.size() + blk.nodes > 0x7fffffffull || idx.size() + blk.idxSlots > 0x7fffffffull)
+                throw LbvhError(RT_E_UNSUPPORTED, pre + "the new trees have 2^31 nodes or index slots, or more");
+            const uint32_t nodeDelta = nodeBase - r.root, idxDelta = idxBase - blk.idxLo;
+            roots.push_back(nodeBase);
+            nodes.insert(nodes.end(), bvhNodes.begin() + r.root, bvhNodes.begin() + r.root + blk.nodes);
+            for (size_t i = nodeBase; i < nodes.size(); i++) nodes[i].first = rebuild::relocated_first(nodes[i].first, nodes[i].count, nodeDelta, idxDelta);
+            idx.insert(idx.end(), primIdx.begin() + blk.idxLo, primIdx.begin() + blk.idxLo + blk.idxSlots);
+            const uint32_t d = Depth(r.root);
+            if (d > depth) depth = d;
+            continue;
+        }
         if (sbvh) {   // the tree's size is known only once it is built: `written` nodes and nIdx indices are appended
             std::vector<RtBVHNode2> bn;
             std::vector<uint32_t> bi;
@@ -50,7 +93,7 @@ void BVH2::Rebuild(int builder, const RtBuildOptions* opt)
             if (rc != RT_OK) throw LbvhError(rc, err);
             if (rebuild::exceeds_stack(st.depth)) throw too_deep(r, st.depth);
             if (nodes.size() + bn.size() > 0x7fffffffull || idx.size() + bi.size() > 0x7fffffffull)
-                throw LbvhError(RT_E_UNSUPPORTED, "rth_rebuild: the new trees have 2^31 nodes or index slots, or more");
+                throw LbvhError(RT_E_UNSUPPORTED, pre + "the new trees have 2^31 nodes or index slots, or more");
             roots.push_back(nodeBase);
             nodes.insert(nodes.end(), bn.begin(), bn.end());
             idx.insert(idx.end(), bi.begin(), bi.end());
@@ -85,7 +128,7 @@ void BVH2::Rebuild(int builder, const RtBuildOptions* opt)
     stat_build_time = wall; stat_node_count = nodesUsed_; stat_depth = depth; stat_sah_cost = cost;
     stat_prim_count = (uint32_t)primitives_.size();
     stat_spatial_splits = spatialSplits; stat_prims_clipped = primsClipped; stat_forced_leaves = forcedLeaves;   // (0 unless RT_REBUILD_SBVH)
-    if (sbvh) alpha = a;
+    if (anySbvh) alpha = a;
 }
 
 } // namespace rt355

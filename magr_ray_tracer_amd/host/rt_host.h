@@ -80,6 +80,9 @@ public:
     // host restatement of rt_rebuild_scene's builder (RT_REBUILD_SAH / RT_REBUILD_LBVH / RT_REBUILD_SBVH, opt as there); instance transforms stay,
     // bvhIdx follows.  Throws LbvhError and leaves everything unchanged when refused (rebuild_host.cpp).
     void     Rebuild(int builder, const RtBuildOptions* opt);
+    // The same under a plan (rt_rebuild_ranges): plan[nRanges], one RT_REBUILD_SAH / LBVH / SBVH / KEEP per distinct BLAS in increasing
+    // order of the ranges; a kept BLAS is appended as its bound block of nodes, relocated (csrc/rebuild_common.h, relocated_first).
+    void     RebuildRanges(const int32_t* plan, int nRanges, const RtBuildOptions* opt);
     int      buildThreads = 1;   // > 1: subtrees are built by parallel tasks, then numbered in the reference's LIFO order (same arrays)
     uint32_t Depth(uint32_t nodeIdx) const;
     uint32_t Count(uint32_t nodeIdx) const;
@@ -93,6 +96,7 @@ public:
 private:
     using Refs = std::vector<BVHPrimData>;
     void  BuildBLASUnguarded(bool statistics, int startIdx);
+    void  RebuildPlan(const char* who, const int32_t* plan, int nRanges, const RtBuildOptions* opt);   // Rebuild's and RebuildRanges' loop (nRanges < 0: every range plan[0])
     // what BuildBLASLBVH / BuildBLASSAHGPU / BuildBLASSBVHGPU do once their build has succeeded (lbvh_host.cpp)
     void  AppendBuiltBLAS(uint32_t nodeBase, const RtBVHNode2* nodes, size_t nN, const uint32_t* idx, size_t nI, float wall_ms, int32_t depth,
                           float cost);

@@ -37,6 +37,15 @@ def _rebuild_args(prims, first, instances, builder, lbvh_options, alpha=None):
     return (p_, f_, n_, b_, nb_, which, _lib.ptr(opts), _lib.ptr(st)), (keep, opts), st
 
 
+def _ranges_args(plan, prims, first, instances, lbvh_options, alpha):
+    from .scene import build_options, plan_words
+    words = plan_words(plan, lbvh_options, alpha)
+    (p_, f_, n_, b_, nb_, _), keep, _ = _update_args(prims, first, instances)
+    opts = build_options(alpha=alpha, **lbvh_options)
+    st = np.zeros((), dtype=_lib.RebuildStats)
+    return (p_, f_, n_, b_, nb_, _lib.ptr(words) if len(words) else None, len(words), _lib.ptr(opts), _lib.ptr(st)), (keep, opts, words), st
+
+
 def _rebuild_dict(st):
     d = {n: float(st[n]) for n in ("gpu_ms", "wall_ms", "stage_ms", "build_ms", "derive_ms", "tlas_ms", "commit_ms")}
     d.update({n: int(st[n]) for n in ("prims", "blas_built", "nodes", "n_idx", "max_depth", "tlas_nodes", "tlas_depth", "spatial_splits",
@@ -225,6 +234,27 @@ class Device:
             e.code = rc
             raise e
         return _rebuild_dict(st)
+
+    def rebuild_ranges(self, plan, prims=None, first=0, instances=None, alpha=None, **lbvh_options):
+        """Rebuild only the BLAS that changed (rt_rebuild_ranges): plan[k], one of "keep", "sah", "lbvh", "sbvh_gpu" per distinct BLAS in
+        the order of blas_blocks(), says whether that BLAS keeps its bound tree (moved on the GPU to where the new scene numbers it) or
+        is built anew by that builder, as rebuild_scene builds it; builders may differ from BLAS to BLAS (lbvh_options go to the "lbvh"
+        ranges, alpha to the "sbvh_gpu" ranges).  `prims` / `first` / `instances` as for rebuild_scene; replaced primitives must not
+        touch a kept BLAS.  Every context holding the scene sees it.  Returns the stats (blas_built: the BLAS actually built); a refusal
+        raises RtError (.code) and leaves the scene as it was."""
+        args, keep, st = _ranges_args(plan, prims, first, instances, lbvh_options, alpha)
+        self._chk_code(self._lib.rt_rebuild_ranges(self._h, *args))
+        return _rebuild_dict(st)
+
+    def blas_blocks(self):
+        """The distinct BLAS of the bound scene in plan order (rt_scene_blas_blocks): a list of dicts with prim_first, prim_count, nodes
+        and idx_slots of the bound tree, and compact (only a compact tree can be kept by rebuild_ranges)."""
+        n = C.c_int32(0)
+        self._chk_code(self._lib.rt_scene_blas_blocks(self._h, C.byref(n), None, None, None, None, None, 0))
+        a = np.zeros((5, max(n.value, 1)), np.int32)
+        self._chk_code(self._lib.rt_scene_blas_blocks(self._h, C.byref(n), *[C.c_void_p(a[i].ctypes.data) for i in range(5)], n.value))
+        return [dict(prim_first=int(a[0, k]), prim_count=int(a[1, k]), nodes=int(a[2, k]), idx_slots=int(a[3, k]), compact=bool(a[4, k]))
+                for k in range(n.value)]
 
     def resize_scene(self, prims, range_counts, inst_range=None, instances=None, builder="sah", alpha=None, **lbvh_options):
         """Give the bound scene a new shape in place on the GPU (rt_resize_scene): `prims` is the whole new primitive array - a numpy
@@ -604,6 +634,16 @@ class Group:
         """Device.rebuild_scene for the group's scene copy (rt_group_rebuild_scene): every lane sees the rebuilt scene."""
         args, keep, st = _rebuild_args(prims, first, instances, builder, lbvh_options, alpha)
         rc = self._lib.rt_group_rebuild_scene(self._h, *args)
+        if rc != 0:
+            e = RtError(self._lib.rt_last_error().decode())
+            e.code = rc
+            raise e
+        return _rebuild_dict(st)
+
+    def rebuild_ranges(self, plan, prims=None, first=0, instances=None, alpha=None, **lbvh_options):
+        """Device.rebuild_ranges for the group's scene copy (rt_group_rebuild_ranges): every lane sees the rebuilt scene."""
+        args, keep, st = _ranges_args(plan, prims, first, instances, lbvh_options, alpha)
+        rc = self._lib.rt_group_rebuild_ranges(self._h, *args)
         if rc != 0:
             e = RtError(self._lib.rt_last_error().decode())
             e.code = rc

@@ -246,6 +246,17 @@ class Scene:
         if rc != 0:
             raise BuildError(rc, self._lib.rth_last_error().decode())
 
+    def RebuildRanges(self, plan, alpha=None, **lbvh_options):
+        """Rebuild under a per-range plan, as rt_rebuild_ranges does on the GPU (rth_rebuild_ranges): plan[k], one of "keep", "sah",
+        "lbvh", "sbvh_gpu" per distinct BLAS in increasing order of the primitive ranges.  A built BLAS is built as Rebuild builds it
+        (lbvh_options go to the "lbvh" ranges, alpha to the "sbvh_gpu" ranges); a kept BLAS keeps its tree, moved to where the new
+        scene numbers it.  The primitives of a kept BLAS must not have changed.  Raises BuildError (.code) and changes nothing when
+        refused (a BLAS that is not compact cannot be kept)."""
+        words = plan_words(plan, lbvh_options, alpha)
+        rc = self._lib.rth_rebuild_ranges(self._h, _lib.ptr(words) if len(words) else None, len(words), _lib.ptr(build_options(alpha=alpha, **lbvh_options)))
+        if rc != 0:
+            raise BuildError(rc, self._lib.rth_last_error().decode())
+
     def blas_ranges(self):
         """The primitive range (first, count) of every instance's BLAS (rt_blas_ranges); raises BuildError with RT_E_UNSUPPORTED when
         the BLAS do not cover contiguous, disjoint ranges in the order of their roots (such a scene cannot be rebuilt in place)."""
@@ -265,6 +276,10 @@ class Scene:
         instance's gets.  Returns the new instance's index."""
         t = None if invT is None else _lib.fvec(np.asarray(invT, dtype=np.float32).ravel())
         return self._chk(self._lib.rth_add_instance(self._h, int(blas), t))
+
+    def SwapInstances(self, a, b):
+        """Instances a and b trade places (rth_swap_instances): the instance order is free, and need not be the order of the BLAS."""
+        self._chk(self._lib.rth_swap_instances(self._h, int(a), int(b)))
 
     def stats(self):
         u = np.zeros(5, dtype=np.uint32)
@@ -334,6 +349,23 @@ def rebuild_builder(builder, lbvh_options=None, alpha=None):
     return REBUILD_BUILDERS[builder]
 
 
+PLAN_WORDS = {"keep": _lib.REBUILD_KEEP, "sah": _lib.REBUILD_SAH, "lbvh": _lib.REBUILD_LBVH, "sbvh_gpu": _lib.REBUILD_SBVH}
+
+
+def plan_words(plan, lbvh_options=None, alpha=None):
+    """The RT_REBUILD_* words (int32) of a per-range plan, a list of "keep" | "sah" | "lbvh" | "sbvh_gpu" (integers pass through, so a
+    test can hand the library a word it must refuse); the linear builder's options need an "lbvh" range, alpha an "sbvh_gpu" range."""
+    plan = list(plan)
+    for w in plan:
+        if not isinstance(w, (int, np.integer)) and w not in PLAN_WORDS:
+            raise ValueError(f"unknown plan word {w!r} (expected 'keep', 'sah', 'lbvh' or 'sbvh_gpu')")
+    if lbvh_options and "lbvh" not in plan:
+        raise ValueError(f"options {sorted(lbvh_options)} apply to 'lbvh' ranges only")
+    if alpha is not None and "sbvh_gpu" not in plan:
+        raise ValueError("alpha applies to 'sbvh_gpu' ranges only")
+    return np.array([w if isinstance(w, (int, np.integer)) else PLAN_WORDS[w] for w in plan], np.int32)
+
+
 def blas_ranges(sa):
     """rt_blas_ranges of SceneArrays (or anything with bvh2 / primIdx / prims / blas): [(first, count)] per instance; raises BuildError
     (RT_E_UNSUPPORTED) when rt_rebuild_scene would not take the scene."""
@@ -345,6 +377,21 @@ def blas_ranges(sa):
     if rc != 0:
         raise BuildError(rc, L.rt_last_error().decode())
     return [(int(a), int(b)) for a, b in zip(first[:len(inst)], count[:len(inst)])]
+
+
+def blas_blocks(sa):
+    """rt_blas_blocks of SceneArrays: per distinct BLAS in plan order a dict with prim_first, prim_count, nodes, idx_slots and compact
+    (only a compact tree can be kept by Device.rebuild_ranges); raises BuildError like blas_ranges."""
+    L = _lib.device_lib()
+    nodes, idx = np.ascontiguousarray(sa.bvh2, _lib.BVHNode2), np.ascontiguousarray(sa.primIdx, np.uint32)
+    inst = np.ascontiguousarray(sa.blas, _lib.BVHInstance)
+    n, a = C.c_int32(0), np.zeros((5, max(len(inst), 1)), np.int32)
+    rc = L.rt_blas_blocks(_lib.ptr(nodes), len(nodes), _lib.ptr(idx), len(idx), len(sa.prims), _lib.ptr(inst), len(inst), C.byref(n),
+                          *[C.c_void_p(a[i].ctypes.data) for i in range(5)], a.shape[1])
+    if rc != 0:
+        raise BuildError(rc, L.rt_last_error().decode())
+    return [dict(prim_first=int(a[0, k]), prim_count=int(a[1, k]), nodes=int(a[2, k]), idx_slots=int(a[3, k]), compact=bool(a[4, k]))
+            for k in range(n.value)]
 
 
 def _stats_dict(st):
