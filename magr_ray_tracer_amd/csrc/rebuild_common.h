@@ -142,7 +142,8 @@ inline const char* find_blas_ranges(const RtBVHNode2* n, int32_t nNodes, const u
 // A bound BLAS is compact when the nodes reachable from its root are exactly the ids [root, root + nodes), nodes odd, and its leaves'
 // primIdx ranges tile one interval [idxLo, idxLo + idxSlots) without gap or overlap - what BuildBLAS, the GPU builders and every in-place
 // rebuild or resize produce.  Such a tree moves as a block: node i goes to i - oldRoot + newRoot, and only the `first` word changes.
-struct BlasBlock { uint32_t nodes, idxLo, idxSlots; uint8_t compact; };
+// height: of the tree in edges (the root counts 0, so 0 exactly when nodes == 1): the builders' depth.
+struct BlasBlock { uint32_t nodes, idxLo, idxSlots; uint8_t compact; uint32_t height; };
 // The relocation rule, one for the kernel (k_blas_relocate) and the host mirror (rth_rebuild_ranges): the `first` word of a record that
 // moves by nodeDelta = newRoot - oldRoot node ids and whose leaves' slots move by idxDelta = newIdxBase - oldIdxBase (both modulo 2^32);
 // an interior record (count == 0) names a child pair, a leaf its first primIdx slot.  Boxes, count and the pad words stay.
@@ -154,25 +155,25 @@ LB_HD uint32_t relocated_first(uint32_t first, uint32_t count, uint32_t nodeDelt
 // twice).  A range that is not compact reports the nodes and slots it reaches; naming it RT_REBUILD_KEEP is refused.
 inline void find_blas_blocks(const RtBVHNode2* n, const std::vector<BlasRange>& ranges, std::vector<BlasBlock>& blocks)
 {
-    blocks.assign(ranges.size(), BlasBlock{ 0u, 0u, 0u, 0 });
-    std::vector<uint32_t> stack;
+    blocks.assign(ranges.size(), BlasBlock{ 0u, 0u, 0u, 0, 0u });
+    std::vector<std::pair<uint32_t, uint32_t>> stack;   // (node, its depth)
     std::vector<std::pair<uint32_t, uint32_t>> leaves;
     for (size_t k = 0; k < ranges.size(); k++) {
         const uint32_t root = ranges[k].root;
-        uint32_t lo = root, hi = root, m = 0;
+        uint32_t lo = root, hi = root, m = 0, height = 0;
         uint64_t slots = 0;
-        leaves.clear(); stack.assign(1, root);
+        leaves.clear(); stack.assign(1, { root, 0u });
         while (!stack.empty()) {
-            const uint32_t i = stack.back(); stack.pop_back();
-            m++; lo = std::min(lo, i); hi = std::max(hi, i);
+            const auto [i, d] = stack.back(); stack.pop_back();
+            m++; lo = std::min(lo, i); hi = std::max(hi, i); height = std::max(height, d);
             if (n[i].count > 0) { leaves.push_back({ n[i].first, n[i].count }); slots += n[i].count; }
-            else { stack.push_back(n[i].first); stack.push_back(n[i].first + 1); }
+            else { stack.push_back({ n[i].first, d + 1 }); stack.push_back({ n[i].first + 1, d + 1 }); }
         }
         std::sort(leaves.begin(), leaves.end());
         bool tiles = true;
         for (size_t a = 1; a < leaves.size() && tiles; a++) tiles = leaves[a].first == leaves[a - 1].first + leaves[a - 1].second;
         blocks[k] = BlasBlock{ m, leaves[0].first, (uint32_t)std::min<uint64_t>(slots, 0xffffffffu),
-                               (uint8_t)(lo == root && hi - lo + 1 == m && (m & 1u) && tiles && slots <= 0x7fffffffu ? 1 : 0) };
+                               (uint8_t)(lo == root && hi - lo + 1 == m && (m & 1u) && tiles && slots <= 0x7fffffffu ? 1 : 0), height };
     }
 }
 // The checks of a plan (one RT_REBUILD_* word per range) against the ranges it is for, the blocks where they are known (NULL: every

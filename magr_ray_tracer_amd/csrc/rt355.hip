@@ -738,12 +738,23 @@ extern "C" int rt_share_scene(RtCtx* ctx, RtCtx* from)
     return bind_scene(ctx, from->scene);
 }
 
-// ---- in-place updates and rebuilds of the copy a context holds (scene.hip) ---------------------------------------------------------
+// ---- in-place updates and rebuilds of the copy a context holds (scene_rebuild.hip, scene_materials.hip) ---------------------------
+// What the entry points that change or inspect a bound copy ask first: a context (entry points that name their other required
+// arguments in that message have asked already), a copy, and - lostBvh2 != NULL - its BVH2, which a BVH4 copy bound through
+// rt_upload_scene has not kept; lostBvh2 ends that message.
+static int bound_scene(const RtCtx* ctx, const char* who, const char* lostBvh2 = nullptr)
+{
+    if (!ctx) return fail(RT_E_INVALID, "%s: null context", who);
+    if (!ctx->sceneLoaded || !ctx->scene) return fail(RT_E_INVALID, "%s: no scene uploaded", who);
+    if (lostBvh2 && ctx->cfg.accel != RT_ACCEL_BVH2 && !ctx->scene->keepsBvh2)
+        return fail(RT_E_UNSUPPORTED, "%s: a BVH4 copy bound through rt_upload_scene has lost its BVH2%s", who, lostBvh2);
+    return RT_OK;
+}
+static const char* const kCannotRebuild = " and cannot rebuild in place (bind the BVH2 with rt_upload_scene_bvh2, or build on the host and upload)";
 extern "C" int rt_update_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
                                RtUpdateStats* stats)
 {
-    if (!ctx) return fail(RT_E_INVALID, "rt_update_scene: null context");
-    if (!ctx->sceneLoaded || !ctx->scene) return fail(RT_E_INVALID, "rt_update_scene: no scene uploaded");
+    if (const int rc = bound_scene(ctx, "rt_update_scene")) return rc;
     if (ctx->cfg.accel != RT_ACCEL_BVH2)
         return fail(RT_E_UNSUPPORTED, "rt_update_scene: BVH4 contexts cannot refit (rt_rebuild_scene a copy bound with rt_upload_scene_bvh2, or rebuild and upload)");
     return update_scene(*ctx->scene, prims, first, count, blas, nBlas, stats);
@@ -751,28 +762,18 @@ extern "C" int rt_update_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t fir
 extern "C" int rt_rebuild_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
                                 int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats)
 {
-    if (!ctx) return fail(RT_E_INVALID, "rt_rebuild_scene: null context");
-    if (!ctx->sceneLoaded || !ctx->scene) return fail(RT_E_INVALID, "rt_rebuild_scene: no scene uploaded");
-    if (ctx->cfg.accel != RT_ACCEL_BVH2 && !ctx->scene->keepsBvh2)
-        return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: a BVH4 copy bound through rt_upload_scene has lost its BVH2 and cannot rebuild in place "
-                    "(bind the BVH2 with rt_upload_scene_bvh2, or build on the host and upload)");
+    if (const int rc = bound_scene(ctx, "rt_rebuild_scene", kCannotRebuild)) return rc;
     return rebuild_scene(*ctx->scene, prims, first, count, blas, nBlas, builder, opts, stats);
 }
 extern "C" int rt_rebuild_ranges(RtCtx* ctx, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
                                  const int32_t* plan, int32_t nRanges, const RtBuildOptions* opts, RtRebuildStats* stats)
 {
-    if (!ctx) return fail(RT_E_INVALID, "rt_rebuild_ranges: null context");
-    if (!ctx->sceneLoaded || !ctx->scene) return fail(RT_E_INVALID, "rt_rebuild_ranges: no scene uploaded");
-    if (ctx->cfg.accel != RT_ACCEL_BVH2 && !ctx->scene->keepsBvh2)
-        return fail(RT_E_UNSUPPORTED, "rt_rebuild_ranges: a BVH4 copy bound through rt_upload_scene has lost its BVH2 and cannot rebuild in place "
-                    "(bind the BVH2 with rt_upload_scene_bvh2, or build on the host and upload)");
+    if (const int rc = bound_scene(ctx, "rt_rebuild_ranges", kCannotRebuild)) return rc;
     return rebuild_ranges(*ctx->scene, prims, first, count, blas, nBlas, plan, nRanges, opts, stats);
 }
 extern "C" int rt_scene_blas_blocks(RtCtx* ctx, int32_t* n, int32_t* primFirst, int32_t* primCount, int32_t* nodes, int32_t* idxSlots, int32_t* compact, int32_t cap)
 {
-    if (!ctx) return fail(RT_E_INVALID, "rt_scene_blas_blocks: null context");
-    if (!ctx->sceneLoaded || !ctx->scene) return fail(RT_E_INVALID, "rt_scene_blas_blocks: no scene uploaded");
-    if (ctx->cfg.accel != RT_ACCEL_BVH2 && !ctx->scene->keepsBvh2) return fail(RT_E_UNSUPPORTED, "rt_scene_blas_blocks: a BVH4 copy bound through rt_upload_scene has lost its BVH2");
+    if (const int rc = bound_scene(ctx, "rt_scene_blas_blocks", "")) return rc;
     return blas_blocks(*ctx->scene, n, primFirst, primCount, nodes, idxSlots, compact, cap);
 }
 static int device_pointer(const RtCtx* ctx, const char* who, const char* name, const void* p, int64_t bytes, int align, bool hostAllowed);   // (below, with rt_trace)
@@ -780,20 +781,18 @@ extern "C" int rt_resize_scene(RtCtx* ctx, const void* prims, int32_t nPrims, co
                                RtRebuildStats* stats)
 {
     if (!ctx || !prims || !shape) return fail(RT_E_INVALID, "rt_resize_scene: null argument (context, prims and shape are required)");
-    if (!ctx->sceneLoaded || !ctx->scene) return fail(RT_E_INVALID, "rt_resize_scene: no scene uploaded");
+    if (const int rc = bound_scene(ctx, "rt_resize_scene")) return rc;
     if (nPrims <= 0) return fail(RT_E_INVALID, "rt_resize_scene: nPrims must be positive (%d given)", nPrims);
     HIPCHK(hipSetDevice(ctx->cfg.device));
     // rt_trace's pointer rule, with host memory allowed: the records are copied, not followed by a kernel
     if (const int rc = device_pointer(ctx, "rt_resize_scene", "prims", prims, (int64_t)sizeof(RtPrimitive) * nPrims, 4, true)) return rc;
-    if (ctx->cfg.accel != RT_ACCEL_BVH2 && !ctx->scene->keepsBvh2)
-        return fail(RT_E_UNSUPPORTED, "rt_resize_scene: a BVH4 copy bound through rt_upload_scene has lost its BVH2 and cannot be rebuilt in place "
-                    "(bind the BVH2 with rt_upload_scene_bvh2, or build on the host and upload)");
+    if (const int rc = bound_scene(ctx, "rt_resize_scene", " and cannot be rebuilt in place (bind the BVH2 with rt_upload_scene_bvh2, or build on the host and upload)")) return rc;
     return resize_scene(*ctx->scene, prims, nPrims, shape, builder, opts, stats);
 }
 extern "C" int rt_update_materials(RtCtx* ctx, const RtMaterialUpdate* update, RtMaterialStats* stats)
 {
     if (!ctx || !update) return fail(RT_E_INVALID, "rt_update_materials: null argument (context and update are required)");
-    if (!ctx->sceneLoaded || !ctx->scene) return fail(RT_E_INVALID, "rt_update_materials: no scene uploaded");
+    if (const int rc = bound_scene(ctx, "rt_update_materials")) return rc;
     HIPCHK(hipSetDevice(ctx->cfg.device));
     // rt_resize_scene's pointer rule: both arrays are copied, not followed by a kernel, so host memory passes as well
     if (update->texels && update->texCount > 0)
@@ -809,21 +808,21 @@ extern "C" int rt_update_materials(RtCtx* ctx, const RtMaterialUpdate* update, R
 extern "C" int rt_refit_info(RtCtx* ctx, RtRefitInfo* out)
 {
     if (!ctx || !out) return fail(RT_E_INVALID, "rt_refit_info: null argument");
-    if (!ctx->sceneLoaded || !ctx->scene) return fail(RT_E_INVALID, "rt_refit_info: no scene uploaded");
+    if (const int rc = bound_scene(ctx, "rt_refit_info")) return rc;
     *out = ctx->scene->refitInfo;
     return RT_OK;
 }
 extern "C" int rt_debug_rebuild_allocations(RtCtx* ctx, int64_t* count)
 {
     if (!ctx || !count) return fail(RT_E_INVALID, "rt_debug_rebuild_allocations: null argument");
-    if (!ctx->sceneLoaded || !ctx->scene) return fail(RT_E_INVALID, "rt_debug_rebuild_allocations: no scene uploaded");
+    if (const int rc = bound_scene(ctx, "rt_debug_rebuild_allocations")) return rc;
     *count = rebuild_allocations(*ctx->scene);
     return RT_OK;
 }
 extern "C" int rt_debug_get_scene_array(RtCtx* ctx, int32_t which, void* out, int64_t capacityBytes, int64_t* bytes)
 {
     if (!ctx || !bytes) return fail(RT_E_INVALID, "rt_debug_get_scene_array: null argument");
-    if (!ctx->sceneLoaded || !ctx->scene) return fail(RT_E_INVALID, "rt_debug_get_scene_array: no scene uploaded");
+    if (const int rc = bound_scene(ctx, "rt_debug_get_scene_array")) return rc;
     const void* src = nullptr; size_t n = 0;
     if (const int rc = scene_array(*ctx->scene, which, &src, &n)) return rc;
     *bytes = (int64_t)n;

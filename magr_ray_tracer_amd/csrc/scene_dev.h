@@ -1,8 +1,11 @@
-// scene_dev.h — the device copy of a scene (scene.hip) as the contexts of rt355.hip hold it, and what the files of the C-ABI share: error
-// reporting and the allocation helper.  scene.hip knows nothing of a context (RtCtx) but that the holders of a copy can be made to wait.
+// scene_dev.h — the device copy of a scene as the contexts of rt355.hip hold it, what the files of the C-ABI share (error reporting and
+// the allocation helper) and what the three files that own a copy share: scene.hip (checks, upload, views), scene_rebuild.hip (update,
+// rebuild, ranges, resize) and scene_materials.hip.  They know nothing of a context (RtCtx) but that the holders of a copy can be made
+// to wait.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <algorithm>
+#include <chrono>
 #include <cstdarg>
 #include <cstdio>
 #include <vector>
@@ -32,6 +35,16 @@ template <class T> static int dalloc(std::vector<void*>& bag, T** p, size_t coun
     bag.push_back(v);
     *p = (T*)v;
     return RT_OK;
+}
+
+namespace refitdev {   // refit.hip's kernels (rules: refit_common.h)
+hipError_t launch_refit(hipStream_t s, RtBVHNode2* nodes, uint32_t nNodes, const RtPrimitive* prims, const uint32_t* primIdx, const uint32_t* leaves,
+                        uint32_t nLeaves, const uint32_t* parent, uint32_t* tickets);
+hipError_t launch_tlas(hipStream_t s, const RtBVHNode2* nodes, const RtBVHInstance* inst, int n, const uint32_t* rootEntry, RtTLASNode* tlas, RtFloat4* tp,
+                       RtFloat4* tpP, RtFloat4* ir, int32_t* status);
+hipError_t launch_records(hipStream_t s, const RtPrimitive* prims, const RtBVHNode2* nodes, const uint32_t* primIdx, uint32_t nIdx, const uint32_t* lights,
+                          uint32_t nLights, uint32_t first, uint32_t count, const uint32_t* pairNode, uint32_t nPairs, RtFloat4* pairs, RtFloat4* triRecs,
+                          RtFloat4* shadeRecs, RtFloat4* lightRecs);
 }
 
 struct RtCtx;
@@ -69,7 +82,7 @@ struct SceneBag {
     std::vector<RtBVHInstance> inst;          // the instances as last uploaded or updated
     uint32_t *dParent = nullptr, *dLeaves = nullptr, *dPairNode = nullptr, *dTickets = nullptr;   // refit topology (walked from the BLAS roots)
     uint32_t nLeaves = 0, nReach = 0;
-    // A device array that is replaced during the copy's life (scene.hip, rebuild_grow, is the one place that does) and freed with it
+    // A device array that is replaced during the copy's life (rebuild_grow, below, is the one place that does) and freed with it
     template <class T> struct Grown {
         T* p = nullptr; size_t cap = 0;
         Grown() = default; Grown(const Grown&) = delete; Grown& operator=(const Grown&) = delete;
@@ -84,16 +97,17 @@ struct SceneBag {
     hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };   // brackets of the staging and of the commit
     // rt_rebuild_scene: what it needs of the upload, and its device memory (allocated by the first rebuilds, then reused)
     const char* rebuildRefusal = nullptr;     // why this scene cannot be rebuilt in place (NULL: it can)
-    std::vector<rebuild::BlasRange> ranges;   // the primitive range of every distinct BLAS, in increasing order
+    std::vector<rebuild::BlasRange> ranges;   // the primitive range and the root of every distinct BLAS, in increasing order
     std::vector<int32_t> instBlas;            // instance -> its range
     bool variantLayout1 = false;              // the holders' extend_variant admits the derived layout 1
-    // What RT_REBUILD_REFIT needs of the live trees, per range (found at upload, reported by the builders at a rebuild), and of the live
-    // collapse of a BVH4 copy that keeps its BVH2: node -> live id and live id -> node (the upload's own arrays or the live set's, never
-    // scratch: a refused call in between must leave them), the live nodes and the stack need as the collapse counted it
-    std::vector<uint32_t> blasRoot, blasInteriors, blasHeight;
-    // ... and what RT_REBUILD_KEEP (rt_rebuild_ranges) needs of them: the block of nodes and index slots each live tree occupies (an
-    // SBVH tree has more slots than primitives), and whether it can move as one (rebuild_common.h)
+    // One record per bound BLAS, in two halves of rebuild_common.h's types (check_plan and check_ranges take them): ranges[k] its
+    // primitives and its root (above; every commit that moves a tree writes the root), blasBlock[k] the nodes and index slots the live
+    // tree occupies (an SBVH tree has more slots than primitives), whether it can move as one (RT_REBUILD_KEEP) and its height.  Found
+    // at upload, reported by the builders at a rebuild; a refit leaves them.
     std::vector<rebuild::BlasBlock> blasBlock;
+    uint32_t blas_interiors(size_t k) const { return (blasBlock[k].nodes - 1) / 2; }   // interior nodes of BLAS k
+    // The live collapse of a BVH4 copy that keeps its BVH2: node -> live id and live id -> node (the upload's own arrays or the live
+    // set's, never scratch: a refused call in between must leave them), the live nodes and the stack need as the collapse counted it
     uint32_t *liveNewId = nullptr, *liveQuadNode = nullptr;
     uint32_t nLive = 0, c4Need = 0;
     RtRefitInfo refitInfo{};                  // the last successful RT_REBUILD_REFIT (rt_refit_info)
@@ -152,7 +166,7 @@ struct SceneBag {
     }
 };
 
-// scene.hip; messages go to rt_last_error()
+// ---- scene.hip; messages go to rt_last_error()
 struct HostScene {   // the host arrays of rt_upload_scene (include/rt355.h), in its order
     const RtPrimitive* prims; int32_t nPrims; const RtMaterial* mats; int32_t nMats; const RtFloat4* textures; int32_t nTexels; const uint32_t* lights; int32_t nLights;
     const void* bvhNodes; int32_t nNodes; const uint32_t* primIdx; int32_t nIdx; const RtTLASNode* tlas; int32_t nTlas; const RtBVHInstance* blas; int32_t nBlas;
@@ -162,6 +176,7 @@ int validate_scene(int accel, const HostScene& in, int* stackEntriesOut, int64_t
 // blas4 != NULL (a BVH4 context, in.bvhNodes is the BVH2; collapse::check_args gave the BLAS): the BVH2 is kept and collapsed on the device
 int upload_scene(SceneBag& b, int accel, int extendVariant, const HostScene& in, int stackEntries, int64_t texPad, int tlasDepth,
                  const std::vector<collapse::Blas>* blas4 = nullptr);
+// ---- scene_rebuild.hip
 int update_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas, RtUpdateStats* stats);
 int rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
                   int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats);
@@ -172,8 +187,82 @@ int rebuild_ranges(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t
 int blas_blocks(const SceneBag& b, int32_t* n, int32_t* primFirst, int32_t* primCount, int32_t* nodes, int32_t* idxSlots, int32_t* compact, int32_t cap);
 // rt_resize_scene (include/rt355.h): the caller's shape, checked by resize::check_shape; prims may be host or device memory
 int resize_scene(SceneBag& b, const void* prims, int32_t nPrims, const RtSceneShape* shape, int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats);
+// ---- scene_materials.hip
 // rt_update_materials (include/rt355.h): texels / primMat may be host or device memory (the caller has applied the pointer rule)
 int update_materials(SceneBag& b, const RtMaterialUpdate& u, RtMaterialStats* stats);
+
+// ---- what the three files share, each written once (scene.hip defines what is not defined here) ---------------------------------------
+// b.stream, and the four events `ev` (b.ev, b.rev; NULL: none), made by the first call that needs them
+int scene_stream(SceneBag& b, hipEvent_t* ev);
+// Capacities of what scales with the trees (SceneBag::RebuildSet, the derivation's and the collapse's scratch, rt_update_scene's staging
+// nodes): index slots at first, twice as many nodes; RT355_REBUILD_INITIAL_CAP=k (read per call; tests, A/B runs) starts smaller or
+// larger.  An array that a finished tree outgrows goes to the need plus need / kRebuildHeadroomDiv: a quarter covers the frame-to-frame
+// drift of an animated SBVH scene (its slot count moved by a few percent between the deformations tried), so a per-frame rebuild stops
+// allocating once both sets have grown, and costs at most that much idle memory.
+constexpr size_t kRebuildHeadroomDiv = 4;
+inline size_t with_headroom(size_t need) { return need + need / kRebuildHeadroomDiv; }
+// what an array of `cap` records becomes when `need` are asked of it (have: it exists; the first allocation is exact)
+inline size_t grown_cap(size_t need, size_t cap, bool have) { return need <= cap ? cap : have ? with_headroom(need) : need; }
+size_t rebuild_initial_cap(const SceneBag& b);
+// A Grown array to at least `count` records, keeping the first `keep`: the one place that replaces (and frees) a buffer of a copy.
+// `nomem` (a format of `count`) replaces the message of a failed allocation.
+template <class T> static int rebuild_grow(SceneBag& b, SceneBag::Grown<T>& a, size_t count, size_t keep, const char* what, const char* nomem = nullptr)
+{
+    if (count <= a.cap && a.p) return RT_OK;
+    count = std::max<size_t>(count, 1);
+    void* q = nullptr;
+    if (hipMalloc(&q, count * sizeof(T)) != hipSuccess)
+        return nomem ? fail(RT_E_NOMEM, nomem, count) : fail(RT_E_NOMEM, "in-place scene change: %zu bytes of device memory for %s", count * sizeof(T), what);
+    b.rallocs++;
+    if (a.p) {
+        hipError_t e = keep ? hipMemcpyAsync(q, a.p, keep * sizeof(T), hipMemcpyDeviceToDevice, b.stream) : hipSuccess;
+        if (e == hipSuccess) e = hipStreamSynchronize(b.stream);
+        if (e != hipSuccess) { (void)hipFree(q); return fail(RT_E_DEVICE, "in-place scene change: moving %s failed: %s", what, hipGetErrorString(e)); }
+        (void)hipFree(a.p);
+    }
+    a.p = (T*)q; a.cap = count;
+    return RT_OK;
+}
+// An array that scales with the primitives, the instances or the lights (a RebuildSet's, the update's staging): made to fit exactly, and
+// once a resize outgrows it replaced by one of the need plus headroom.  Nothing in it is kept.
+template <class T> static int rebuild_fit(SceneBag& b, SceneBag::Grown<T>& a, size_t need, const char* what)
+{
+    need = std::max<size_t>(need, 1);
+    if (a.p && need <= a.cap) return RT_OK;
+    return rebuild_grow(b, a, a.p ? with_headroom(need) : need, 0, what);
+}
+// The derivation's scratch (b.dw) for trees of nodeNeed nodes in all, or for a flag scan over as many primitives
+int rebuild_scratch(SceneBag& b, size_t nodeNeed);
+// After a flag scan over n primitives (rebuilddev::resize_check, mat_flags; `bad` word: b.rStatus): the lowest refused primitive
+// (resize::kNoBad: none) and the lights the scan counted.  Waits for the stream.
+int flag_scan_result(SceneBag& b, int32_t n, uint32_t* firstBad, int32_t* nLights);
+// The collapse's scratch (b.c4) for trees of nodeNeed nodes in all; b.c4 lacks the tables a collapse leaves behind (newId, quadNode and
+// their capacity): collapse_work adds those of the arrays that are collapsed.
+int collapse_scratch(SceneBag& b, size_t nodeNeed);
+collapsedev::Work collapse_work(const SceneBag& b, uint32_t* newId, uint32_t* quadNode, size_t quadCap);
+// The status words a collapse leaves in its counters (collapse_dev.h), by name
+struct CollapseStatus {
+    uint32_t w[collapsedev::kStatusWords] = { 0 };
+    uint32_t& at(uint32_t word) { return w[word - collapsedev::kStatus]; }
+    uint32_t at(uint32_t word) const { return w[word - collapsedev::kStatus]; }
+    uint32_t walk() const { return at(collapsedev::kWalkWord); }      // a failed walk
+    uint32_t live() const { return at(collapsedev::kLive); }          // live nodes
+    uint32_t need() const { return at(collapsedev::kNeed); }          // stack entries of the deepest BLAS
+    uint32_t changed() const { return at(collapsedev::kChanged); }    // refit_records: live records whose slots differ
+    uint32_t largest_leaf() const { return std::max(std::max(at(collapsedev::kLeaf), at(collapsedev::kLeafAny)), 1u); }
+    hipError_t read(hipStream_t s, const collapsedev::Work& work) { return hipMemcpyAsync(w, work.ctr + collapsedev::kStatus, sizeof w, hipMemcpyDeviceToHost, s); }
+    // a failed walk, a BLAS that needs more stack than there is, as the error of the call `who`; `tail` ends the stack message
+    int error(const char* who, const char* tail) const;
+};
+// "the new trees have 2^31 nodes or index slots, or more": the refusal of a rebuild whose trees outgrow the 31-bit ids
+int too_many_nodes(const char* who);
+// the outputs of rt_blas_blocks / rt_scene_blas_blocks (any may be NULL; at most cap entries are written)
+void write_blocks(const std::vector<rebuild::BlasRange>& ranges, const std::vector<rebuild::BlasBlock>& blocks, int32_t* n, int32_t* primFirst, int32_t* primCount,
+                  int32_t* nodes, int32_t* idxSlots, int32_t* compact, int32_t cap);
+inline double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b)
+{
+    return std::chrono::duration<double, std::milli>(b - a).count();
+}
 int64_t rebuild_allocations(const SceneBag& b);
 int scene_array(const SceneBag& b, int32_t which, const void** src, size_t* bytes);   // where RT_SCENE_* lies on the device and how long it is
 

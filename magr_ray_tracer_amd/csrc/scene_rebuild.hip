@@ -1,0 +1,751 @@
+// scene_rebuild.hip — the in-place changes of a bound scene copy that move its trees: rt_update_scene (refit, committed in place) and the
+// one body of rt_rebuild_scene, rt_rebuild_ranges and rt_resize_scene, which builds into the set that is not live and commits by a
+// pointer swap.  Host code only: the kernels are refit.hip's, rebuild.hip's, collapse.hip's and the builders' (sah.hip / lbvh.hip /
+// sbvh.hip), the rules rebuild_common.h's; what it shares with the upload and the material updates is scene_dev.h's.
+#include <cstdlib>
+#include <string>
+#include "scene_dev.h"
+#include "resize_common.h"
+
+using namespace scenedev;
+
+// What an update and a rebuild refuse alike, before anything is written: `prims` replaces the primitives [first, first + count), `blas`
+// (may be NULL) the instances.  typeSuffix ends the message about a changed objType / matIdx.
+static int check_change(const char* who, const SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
+                        const char* typeSuffix)
+{
+    if (count < 0 || (count > 0 && !prims)) return fail(RT_E_INVALID, "%s: bad primitive count %d / NULL records", who, count);
+    if (count > 0 && (first < 0 || (int64_t)first + count > (int64_t)b.nPrims))
+        return fail(RT_E_INVALID, "%s: primitive range [%d, %lld) outside the %d uploaded", who, first, (long long)first + count, b.nPrims);
+    for (int32_t i = 0; i < count; i++) {
+        const size_t g = (size_t)first + (size_t)i;
+        if (prims[i].objType != b.primType[g] || prims[i].matIdx != b.primMat[g])
+            return fail(RT_E_INVALID, "%s: primitive %zu changes its objType / matIdx (%d / %d -> %d / %d)%s", who, g,
+                        b.primType[g], b.primMat[g], prims[i].objType, prims[i].matIdx, typeSuffix);
+    }
+    if (blas) {
+        if (nBlas != b.nBlas) return fail(RT_E_INVALID, "%s: %d instances given, %d uploaded", who, nBlas, b.nBlas);
+        for (int32_t k = 0; k < nBlas; k++) {
+            if (blas[k].bvhIdx != b.inst[(size_t)k].bvhIdx) return fail(RT_E_INVALID, "%s: instance %d changes its bvhIdx", who, k);
+            if (refit::singular(blas[k].invT)) return fail(RT_E_INVALID, "%s: instance %d: the transform is singular", who, k);
+        }
+    }
+    return RT_OK;
+}
+// k_tlas_build's two status words (what went wrong, the height of the new TLAS) as the error of the call that ran it
+static int tlas_status_error(const char* who, const int32_t status[2])
+{
+    if (status[0] == 1) return fail(RT_E_INVALID, "%s: an instance transform is singular", who);
+    if (status[0] != 0) return fail(RT_E_UNSUPPORTED, "%s: the TLAS clustering found no partner (boxes of area >= RT_REALLYFAR or NaN)", who);
+    if (status[1] > RT_TLAS_STACK)
+        return fail(RT_E_UNSUPPORTED, "%s: the rebuilt TLAS is %d levels deep, the traversal stack holds %d; the scene is unchanged", who, status[1], RT_TLAS_STACK);
+    return RT_OK;
+}
+
+int scenedev::update_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas, RtUpdateStats* stats)
+{
+    const char* who = "rt_update_scene";
+    // ---- refusals: before anything is written
+    if (b.refitRefusal) return fail(RT_E_UNSUPPORTED, "rt_update_scene: %s", b.refitRefusal);
+    if (const int rc = check_change(who, b, prims, first, count, blas, nBlas, ": topology must not change")) return rc;
+    HIPCHK(hipSetDevice(b.device));
+    // ---- staging buffers (the first update makes them; one after a resize that outgrew them replaces them)
+    if (const int rc = scene_stream(b, b.ev)) return rc;   // (a rebuild may have made the stream already)
+    {
+        int rc = rebuild_fit(b, b.sPrims, (size_t)b.nPrims, "the staging primitives");
+        if (rc == RT_OK) rc = rebuild_fit(b, b.sInst, (size_t)b.nBlas, "the staging instances");
+        if (rc == RT_OK) rc = rebuild_fit(b, b.sTlas, (size_t)b.nTlas, "the staging TLAS");
+        if (rc == RT_OK) rc = rebuild_fit(b, b.sTp, (size_t)b.nTlas * 4, "the staging TLAS records");
+        if (rc == RT_OK) rc = rebuild_fit(b, b.sTpP, (size_t)b.nTlas * 4, "the staging TLAS records");
+        if (rc == RT_OK) rc = rebuild_fit(b, b.sIr, (size_t)b.nBlas * 4, "the staging instance records");
+        if (rc == RT_OK && !b.sStatus) { rc = dalloc(b.allocs, &b.sStatus, 2); if (rc == RT_OK) b.rallocs++; }
+        if (rc != RT_OK) return rc;
+    }
+    if (!b.sNodes.p || (size_t)b.nNodes > b.sNodes.cap) {
+        // the staging nodes: at first room for every tree the SAH and the linear builder can bind later; an SBVH rebuild may bind more
+        // nodes than that, then the array grows as the rebuild's sets do (nothing in it outlives a call)
+        const size_t n = (size_t)b.nNodes, cap = b.sNodes.p ? with_headroom(n) : std::max(n, 2 * rebuild_initial_cap(b));
+        if (const int rc = rebuild_grow(b, b.sNodes, cap, 0, "the staging nodes", "rt_update_scene: %zu staging nodes")) return rc;
+    }
+    const SceneArrays& sc = b.sc;
+    hipStream_t s = b.stream;
+    // ---- stage: the new primitives, the refit tree and the rebuilt TLAS in scratch
+    HIPCHK(hipEventRecord(b.ev[0], s));
+    HIPCHK(hipMemcpyAsync(b.sPrims.p, sc.prims, sizeof(RtPrimitive) * (size_t)b.nPrims, hipMemcpyDeviceToDevice, s));
+    if (count) HIPCHK(hipMemcpyAsync(b.sPrims.p + first, prims, sizeof(RtPrimitive) * (size_t)count, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(b.sNodes.p, sc.bvh2, sizeof(RtBVHNode2) * (size_t)b.nNodes, hipMemcpyDeviceToDevice, s));
+    if (blas) HIPCHK(hipMemcpyAsync(b.sInst.p, blas, sizeof(RtBVHInstance) * (size_t)b.nBlas, hipMemcpyHostToDevice, s));
+    else HIPCHK(hipMemcpyAsync(b.sInst.p, sc.blas, sizeof(RtBVHInstance) * (size_t)b.nBlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(refitdev::launch_refit(s, b.sNodes.p, (uint32_t)b.nNodes, b.sPrims.p, sc.primIdx, b.dLeaves, b.nLeaves, b.dParent, b.dTickets));
+    HIPCHK(refitdev::launch_tlas(s, b.sNodes.p, b.sInst.p, b.nBlas, b.layout == 1 ? sc.rootEntry : nullptr, b.sTlas.p, b.sTp.p, b.sTpP.p, b.sIr.p, b.sStatus));
+    int32_t status[2] = { 0, 0 };
+    HIPCHK(hipEventRecord(b.ev[1], s));
+    HIPCHK(hipMemcpyAsync(status, b.sStatus, sizeof status, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (const int rc = tlas_status_error(who, status)) return rc;
+    // ---- commit: no kernel of a context holding this copy may read the arrays while they are rewritten
+    if (const int rc = b.wait_holders()) return rc;
+    HIPCHK(hipEventRecord(b.ev[2], s));
+    if (count) HIPCHK(hipMemcpyAsync(sc.prims + first, b.sPrims.p + first, sizeof(RtPrimitive) * (size_t)count, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(sc.bvh2, b.sNodes.p, sizeof(RtBVHNode2) * (size_t)b.nNodes, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(sc.blas, b.sInst.p, sizeof(RtBVHInstance) * (size_t)b.nBlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(sc.tlas, b.sTlas.p, sizeof(RtTLASNode) * (size_t)b.nTlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(sc.tlasPairs, b.sTp.p, sizeof(RtFloat4) * 4 * (size_t)b.nTlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(sc.tlasPairsP, b.sTpP.p, sizeof(RtFloat4) * 4 * (size_t)b.nTlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(sc.instRecs, b.sIr.p, sizeof(RtFloat4) * 4 * (size_t)b.nBlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(refitdev::launch_records(s, sc.prims, sc.bvh2, sc.primIdx, (uint32_t)b.nIdx, sc.lights, (uint32_t)b.nLights, (uint32_t)std::max(first, 0),
+                                    (uint32_t)count, b.dPairNode, (uint32_t)b.nPairs, b.layout == 1 ? sc.pairs : nullptr,
+                                    b.layout == 1 ? sc.triRecs : nullptr, sc.shadeRecs, sc.lightRecs));
+    HIPCHK(hipEventRecord(b.ev[3], s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (blas) b.inst.assign(blas, blas + nBlas);
+    const bool reconfigure = status[1] != b.tlasDepth;
+    if (reconfigure) { b.tlasDepth = status[1]; b.generation++; }
+    if (stats) {
+        float ms = 0, ms2 = 0;   // GPU time of both phases (not the wait for the holders in between)
+        (void)hipEventElapsedTime(&ms, b.ev[0], b.ev[1]); (void)hipEventElapsedTime(&ms2, b.ev[2], b.ev[3]);
+        ms += ms2;
+        *stats = RtUpdateStats{};
+        stats->gpu_ms = ms; stats->prims = count; stats->nodes = (int32_t)b.nReach; stats->tlas_nodes = b.nTlas; stats->tlas_depth = status[1];
+        stats->reconfigured = reconfigure ? 1 : 0;
+    }
+    return RT_OK;
+}
+
+// ---- in-place rebuilds (rt_rebuild_scene; builders: sah.hip / lbvh.hip / sbvh.hip, derivation: rebuild.hip, rules: rebuild_common.h) ----
+// Room in the set `t` (not live) for idxNeed index slots and nodeNeed nodes, keeping the keepIdx slots and keepNodes records emitted so
+// far; nR: the BLAS the trees belong to.  An array that is too small goes to the need plus kRebuildHeadroomDiv-th of it; one that NOMEM
+// stopped is taken up by a later call.
+static int rebuild_reserve(SceneBag& b, SceneBag::RebuildSet& t, size_t nR, size_t idxNeed, size_t nodeNeed, size_t keepIdx, size_t keepNodes)
+{
+    const bool have = t.nodes.p != nullptr;   // (the first allocation is exact: the initial capacity)
+    const size_t idxCap = grown_cap(idxNeed, t.primIdx.cap, have), nodeCap = (grown_cap(nodeNeed, t.nodes.cap, have) + 1) & ~(size_t)1;
+    int rc = rebuild_grow(b, t.primIdx, idxCap, keepIdx, "primIdx");
+    if (rc == RT_OK) rc = rebuild_grow(b, t.nodes, nodeCap, keepNodes, "nodes");
+    if (rc == RT_OK) rc = rebuild_grow(b, t.triRecs, idxCap * 3, 0, "triangle records");
+    if (rc == RT_OK) rc = rebuild_grow(b, t.parent, nodeCap, 0, "parent links");
+    if (rc == RT_OK) rc = rebuild_grow(b, t.tickets, nodeCap, 0, "tickets");
+    if (rc == RT_OK) rc = rebuild_grow(b, t.pairs, std::max<size_t>(nodeCap / 2, 1) * 4, 0, "pair records");
+    if (rc == RT_OK) rc = rebuild_grow(b, t.leaves, nodeCap / 2, 0, "leaves");
+    if (rc == RT_OK) rc = rebuild_grow(b, t.pairNode, nodeCap / 2, 0, "pair nodes");
+    if (b.accel == RT_ACCEL_BVH4) {   // (a copy that keeps its BVH2: the collapsed records, and a quad record per interior node and leaf root at most)
+        if (rc == RT_OK) rc = rebuild_grow(b, t.bvh4, nodeCap, 0, "BVH4 nodes");
+        if (rc == RT_OK) rc = rebuild_grow(b, t.quads, (nodeCap / 2 + nR) * 8, 0, "quad records");
+        if (rc == RT_OK) rc = rebuild_grow(b, t.newId, nodeCap, 0, "live ids");
+        if (rc == RT_OK) rc = rebuild_grow(b, t.quadNode, nodeCap / 2 + nR, 0, "live nodes");
+    }
+    return rc;
+}
+// What the trees of a call are built over: the bound scene's own shape (a rebuild) or the caller's (a resize)
+struct Shape {
+    int32_t nPrims, nBlas, nLights;                  // (a resize learns nLights on the device: reserve_lights follows)
+    const std::vector<rebuild::BlasRange>* ranges;   // the primitive range of every distinct BLAS, in increasing order (root: the bound one; a resize has none)
+    const std::vector<int32_t>* instBlas;            // instance -> its range
+    int32_t nTlas() const { return 2 * nBlas; }      // TLAS::Build's node count
+};
+// The lights' arrays of the set `t` (not live): one record at least, as at upload
+static int reserve_lights(SceneBag& b, SceneBag::RebuildSet& t, size_t nLights)
+{
+    const int rc = rebuild_fit(b, t.lights, nLights, "the light list");
+    return rc != RT_OK ? rc : rebuild_fit(b, t.lightRecs, std::max<size_t>(nLights, 1) * 8, "light records");
+}
+static int rebuild_alloc(SceneBag& b, SceneBag::RebuildSet& t, const Shape& sh, bool resize)
+{
+    const size_t nP = (size_t)sh.nPrims, nB = (size_t)sh.nBlas, nT = (size_t)sh.nTlas();
+    int rc = RT_OK;
+    // every piece is made on its own: a call that ran out of memory half way is taken up where it stopped
+    auto need = [&](auto** p, size_t count) { if (rc == RT_OK && !*p) { rc = dalloc(b.allocs, p, count); if (rc == RT_OK) b.rallocs++; } };
+    if ((rc = scene_stream(b, b.rev)) != RT_OK) return rc;
+    if (!b.spool) b.spool = sbvhdev::pool_create();
+    const size_t cap0 = rebuild_initial_cap(b);
+    // the scratch both sets share
+    need(&b.rStatus, 2); need(&b.dw.ctr, rebuilddev::kCtrWords);
+    if (rc == RT_OK && !b.dwScan.p) rc = rebuild_scratch(b, 2 * cap0);
+    if (rc != RT_OK) return rc;
+    // what scales with the shape
+    rc = rebuild_fit(b, t.prims, nP, "primitives");
+    if (rc == RT_OK) rc = rebuild_fit(b, t.shadeRecs, nP, "shade records");
+    if (rc == RT_OK) rc = rebuild_fit(b, t.blas, nB, "instances");
+    if (rc == RT_OK) rc = rebuild_fit(b, t.tlas, nT, "TLAS nodes");
+    if (rc == RT_OK) rc = rebuild_fit(b, t.tp, nT * 4, "TLAS records");
+    if (rc == RT_OK) rc = rebuild_fit(b, t.tpP, nT * 4, "TLAS records");
+    if (rc == RT_OK) rc = rebuild_fit(b, t.ir, nB * 4, "instance records");
+    if (rc == RT_OK) rc = rebuild_fit(b, t.rootEntry, nB, "root entries");
+    // (a rebuild carries the bound light records, and the light list only once a resize has put it into a set; a resize sizes both
+    // when its scan has counted the lights)
+    if (rc == RT_OK && !resize) rc = rebuild_fit(b, t.lightRecs, std::max<size_t>((size_t)sh.nLights, 1) * 8, "light records");
+    if (rc == RT_OK && !resize && b.lightsInSet) rc = rebuild_fit(b, t.lights, (size_t)sh.nLights, "the light list");
+    // ... and with the trees (the first allocation: the initial capacity)
+    if (rc == RT_OK && !t.nodes.p) rc = rebuild_reserve(b, t, sh.ranges->size(), std::max(cap0, t.primIdx.cap), std::max(2 * cap0, t.nodes.cap), 0, 0);
+    return rc;
+}
+
+// The checks of the builder and its options that need no scene: an unknown builder, a refit where there is no tree, alpha
+static int check_builder(const char* who, int32_t builder, const RtBuildOptions* opts, bool refitAllowed)
+{
+    if (builder != RT_REBUILD_SAH && builder != RT_REBUILD_LBVH && builder != RT_REBUILD_SBVH && builder != RT_REBUILD_REFIT)
+        return fail(RT_E_INVALID, "%s: unknown builder %d", who, builder);
+    if (builder == RT_REBUILD_REFIT && !refitAllowed) return fail(RT_E_INVALID, "%s: RT_REBUILD_REFIT: a resized scene has no tree to refit", who);
+    const float alpha = builder == RT_REBUILD_SBVH && opts ? opts->alpha : 0.0f;
+    if (!(alpha >= 0.0f && alpha <= 1.0f)) return fail(RT_E_INVALID, "%s: alpha must lie in [0, 1]", who);
+    return RT_OK;
+}
+// The builders' own argument checks, BLAS by BLAS under plan[k], one RT_REBUILD_SAH / LBVH / SBVH / KEEP per range (node and index ids as
+// the host appends BLAS after BLAS: a kept BLAS takes its block's - blocks NULL: a SAH tree's at most - and the ids behind an SBVH tree
+// are known only as the trees are built: its ranges hold at most 2^30 primitives each, and alpha is checked by check_builder)
+static int check_ranges(const char* who, const int32_t* plan, const RtBuildOptions* opts, int32_t nPrims, const std::vector<rebuild::BlasRange>& ranges,
+                        const rebuild::BlasBlock* blocks, lbvh::Params& P)
+{
+    uint32_t nodeBase = 0, idxBase = 0;
+    for (size_t k = 0; k < ranges.size(); k++) {
+        const rebuild::BlasRange& r = ranges[k];
+        const uint32_t cap = 2 * r.count - 1;
+        if (plan[k] == RT_REBUILD_SAH || plan[k] == RT_REBUILD_LBVH) {
+            const char* msg = plan[k] == RT_REBUILD_SAH ? sahdev::check_args(nPrims, (int32_t)r.first, (int32_t)r.count, nodeBase, idxBase)
+                                                        : lbvhdev::check_args(opts, nPrims, (int32_t)r.first, (int32_t)r.count, nodeBase, idxBase, P);
+            if (msg) return fail(RT_E_INVALID, "%s: %s", who, msg);
+            nodeBase += cap; idxBase += r.count;
+        } else if (plan[k] == RT_REBUILD_SBVH) {
+            if (r.count == 0 || r.count > (1u << 30)) return fail(RT_E_INVALID, "%s: a BLAS of %u primitives", who, r.count);
+        } else {
+            nodeBase += blocks ? blocks[k].nodes : cap; idxBase += blocks ? blocks[k].idxSlots : r.count;
+        }
+    }
+    return RT_OK;
+}
+// alpha, when a plan has an SBVH range (check_builder's rule)
+static int check_plan_alpha(const char* who, const int32_t* plan, size_t n, const RtBuildOptions* opts)
+{
+    for (size_t k = 0; k < n; k++) if (plan[k] == RT_REBUILD_SBVH) return check_builder(who, RT_REBUILD_SBVH, opts, false);
+    return RT_OK;
+}
+
+// ---- the one body of rt_rebuild_scene, rt_rebuild_ranges and rt_resize_scene, phase by phase ----------------------------------------------
+// What a call asks for; it has passed the checks that need no device.  A rebuild (newPrims NULL) keeps the bound shape `sh` and takes the
+// replacement records prims / first / count and blas as rt_update_scene does; a resize builds the caller's shape over newPrims (host or
+// device memory, sh.nPrims records), blas (NULL: identity) carrying the transforms.  plan[k] says what becomes of range k: built with
+// RT_REBUILD_SAH / LBVH / SBVH, or (RT_REBUILD_KEEP, a rebuild of a compact bound tree only) its bound tree moved to where the new scene
+// numbers it; an empty plan is RT_REBUILD_REFIT of the whole scene (no builder runs, opts is ignored).
+namespace {
+struct Request {
+    const char* who;
+    Shape sh;
+    const void* newPrims;
+    const RtPrimitive* prims; int32_t first, count;
+    const RtBVHInstance* blas;
+    std::vector<int32_t> plan;
+    const RtBuildOptions* opts;
+    lbvh::Params P;
+};
+// One call: what it has built in the set that is not live and what it has read back of it - everything commit needs -, and the phases
+// that build it, in the order rebuild_body calls them
+struct Pending {
+    SceneBag& b;
+    const Request& rq;
+    const char* const who = rq.who;
+    const Shape& sh = rq.sh;
+    const std::vector<rebuild::BlasRange>& ranges = *sh.ranges;
+    const size_t nR = ranges.size();
+    const bool resize = rq.newPrims != nullptr, refit = rq.plan.empty(), bvh4 = b.accel == RT_ACCEL_BVH4, layout1 = b.layout == 1;
+    SceneBag::RebuildSet& t = b.rset[b.rnext];
+    int size();                  // 1. room for what the plan is known to need, the builders' workspace
+    int stage();                 // 2. the primitives and the lights
+    int trees();                 // 3. refit copy, kept segments, builders
+    int derive();                // 4. numbering, collapse, records, TLAS
+    int read_back(bool timed);   // 5. ... and refuse: walk, collapse, TLAS, layout
+    void commit();               // 6. host memory only
+    struct KeptSegment { uint32_t srcNode = 0, dstNode = 0, nNodes = 0, nodeDelta = 0, srcIdx = 0, dstIdx = 0, nIdx = 0, idxDelta = 0; };
+    int stage_resize(), stage_rebuild(), refit_trees(), flush_kept(KeptSegment& seg), keep_tree(size_t k, KeptSegment& seg), build_tree(size_t k);
+
+    using clock = std::chrono::steady_clock;
+    clock::time_point t0 = clock::now(), t1, t2, t3;   // the call, staged, trees built, read back
+    // size: what the ranges behind range k need that is known beforehand, and the BLAS in the order the instances first name them
+    std::vector<size_t> restIdx, restNodes, order;
+    bool anyKnown = false;
+    // the counts of the new scene, and where its light list lies
+    uint32_t nNodes = 0, nIdx = 0, nPairs = 0, nLeaves = 0;
+    int32_t nLights = 0;
+    const uint32_t* lights = nullptr;
+    // per range: where its tree lies and what it is like
+    std::vector<uint32_t> rootOf, interiors, depth, idxOf, slotsOf;
+    uint32_t maxDepth = 0;
+    int32_t nBuilt = 0;
+    uint64_t spatialSplits = 0, primsClipped = 0;
+    std::vector<RtBVHInstance> inst;
+    // read back: k_tlas_build's status, the derivation's walk status and largest leaf, the collapse's status
+    int32_t tlas[2] = { 0, 0 };
+    uint32_t walk[2] = { 0, 0 }, changed = 0;
+    CollapseStatus c4;
+    int32_t refitPath = 0;
+    int stackNeed = 0;
+    std::vector<int2> packed;   // a resize: the host's shadow of objType / matIdx, the only per-primitive data that comes back
+    float gpuMs = 0, fitMs = 0, deriveMs = 0, tlasMs = 0;   // between the events (read for stats only)
+    bool reconfigured = false;
+    // range k has a tree of `nodes` nodes, height `height`, over `slots` index slots: behind the trees placed so far
+    void place(size_t k, uint32_t nodes, uint32_t height, uint32_t slots)
+    {
+        rootOf[k] = nNodes; interiors[k] = (nodes - 1) / 2; depth[k] = height; idxOf[k] = nIdx; slotsOf[k] = slots;
+        maxDepth = std::max(maxDepth, height);
+        nNodes += nodes; nIdx += slots;
+    }
+};
+} // namespace
+
+// 1. Size: room in the set that is not live for what the plan is known to need, and the builders' workspace
+int Pending::size()
+{
+    // a kept tree needs its block, a SAH or LBVH tree count slots and 2 * count - 1 nodes at most (an SBVH tree is sized when it is
+    // built: size, then place)
+    restIdx.assign(nR + 1, 0); restNodes.assign(nR + 1, 0);
+    for (size_t k = nR; k-- > 0 && !refit;) {
+        const bool keep = rq.plan[k] == RT_REBUILD_KEEP, known = keep || rq.plan[k] != RT_REBUILD_SBVH;
+        restIdx[k] = restIdx[k + 1] + (keep ? b.blasBlock[k].idxSlots : known ? ranges[k].count : 0u);
+        restNodes[k] = restNodes[k + 1] + (keep ? b.blasBlock[k].nodes : known ? 2 * (size_t)ranges[k].count - 1 : 0u);
+        anyKnown = anyKnown || known;
+    }
+    std::vector<uint8_t> named(nR, 0);
+    for (const int32_t k : *sh.instBlas) if (!named[(size_t)k]) { named[(size_t)k] = 1; order.push_back((size_t)k); }
+    HIPCHK(hipSetDevice(b.device));
+    if (const int rc = rebuild_alloc(b, t, sh, resize)) return rc;
+    if (refit) return rebuild_reserve(b, t, nR, (size_t)b.nIdx, (size_t)b.nNodes + nR, 0, 0);   // the bound trees (nR spare nodes: see build_tree)
+    if (!anyKnown) return RT_OK;
+    // room for the kept trees and for every tree the SAH and the linear builder can make (a set or the scratch that started smaller, or
+    // has only held SBVH trees so far); nR spare nodes: see build_tree.  With every range built by those two this is nPrims slots and
+    // 2 * nPrims nodes for ranges that tile the primitives
+    if (restIdx[0] > 0x7fffffffull || restNodes[0] + nR > 0x7fffffffull) return too_many_nodes(who);
+    if (const int rc = rebuild_reserve(b, t, nR, restIdx[0], restNodes[0] + nR, 0, 0)) return rc;
+    size_t need = 0;   // the builders' workspace, over the ranges they build
+    for (size_t k = 0; k < nR; k++) {
+        if (rq.plan[k] != RT_REBUILD_SAH && rq.plan[k] != RT_REBUILD_LBVH) continue;
+        size_t bytes = 0;
+        const int rc = rq.plan[k] == RT_REBUILD_SAH ? sahdev::work_bytes(who, ranges[k].count, b.stream, &bytes) : lbvhdev::work_bytes(who, ranges[k].count, b.stream, &bytes);
+        if (rc != RT_OK) return rc;
+        need = std::max(need, bytes);
+    }
+    if (need > b.rwork.cap) return rebuild_grow(b, b.rwork, need, 0, "the builders' workspace", "in-place scene change: %zu bytes of builder workspace");
+    return RT_OK;
+}
+
+// 2. Stage: the new primitives and the lights into the set that is not live
+int Pending::stage() { return resize ? stage_resize() : stage_rebuild(); }
+// A resize: check, scan, emit - one path for host and device input: copied first (the set is not live, so checking after the copy is
+// safe), then checked where it lies; the light list and the light records come from the same pass
+int Pending::stage_resize()
+{
+    const SceneArrays& sc = b.sc;
+    const int32_t nPrims = sh.nPrims;
+    hipStream_t s = b.stream;
+    if (const int rc = rebuild_scratch(b, (size_t)nPrims)) return rc;   // (flags and ranks: a word per primitive)
+    if (const int rc = rebuild_fit(b, b.rPacked, (size_t)nPrims, "the packed objType / matIdx pairs")) return rc;
+    HIPCHK(hipMemcpyAsync(t.prims.p, rq.newPrims, sizeof(RtPrimitive) * (size_t)nPrims, hipMemcpyDefault, s));
+    HIPCHK(rebuilddev::resize_check(s, b.dw, t.prims.p, (uint32_t)nPrims, sc.mats, sc.nMats, b.rPacked.p, (uint32_t*)b.rStatus));
+    uint32_t firstBad = resize::kNoBad;
+    if (const int rc = flag_scan_result(b, nPrims, &firstBad, &nLights)) return rc;
+    if (firstBad != resize::kNoBad) {
+        int2 pm{ 0, 0 };
+        HIPCHK(hipMemcpy(&pm, b.rPacked.p + firstBad, sizeof pm, hipMemcpyDeviceToHost));
+        return fail(RT_E_INVALID, "%s: primitive %u: objType %d / matIdx %d out of range (objType: one of RT_PRIM_*, matIdx: [0, %d)); the scene is unchanged", who,
+                    firstBad, pm.x, pm.y, sc.nMats);
+    }
+    if (const int rc = reserve_lights(b, t, (size_t)nLights)) return rc;
+    HIPCHK(rebuilddev::light_emit(s, b.dw, t.prims.p, (uint32_t)nPrims, sc.mats, (uint32_t)nLights, t.lights.p, t.lightRecs.p));
+    lights = t.lights.p;
+    return RT_OK;
+}
+// A rebuild: copy, window, carry the lights
+int Pending::stage_rebuild()
+{
+    const SceneArrays& sc = b.sc;
+    hipStream_t s = b.stream;
+    HIPCHK(hipMemcpyAsync(t.prims.p, sc.prims, sizeof(RtPrimitive) * (size_t)b.nPrims, hipMemcpyDeviceToDevice, s));
+    if (rq.count) HIPCHK(hipMemcpyAsync(t.prims.p + rq.first, rq.prims, sizeof(RtPrimitive) * (size_t)rq.count, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(t.lightRecs.p, sc.lightRecs, sizeof(RtFloat4) * 8 * std::max<size_t>((size_t)b.nLights, 1), hipMemcpyDeviceToDevice, s));   // (the emittance words stay)
+    nLights = sh.nLights; lights = sc.lights;
+    if (b.lightsInSet) {   // the light list lives in a set since a resize: it moves on with the arrays
+        if (nLights) HIPCHK(hipMemcpyAsync(t.lights.p, sc.lights, sizeof(uint32_t) * (size_t)nLights, hipMemcpyDeviceToDevice, s));
+        lights = t.lights.p;
+    }
+    return RT_OK;
+}
+
+// 3. The trees, in the order of the ranges.  A refit: the bound trees and their refit topology into the set, then the boxes anew: no BLAS
+// is built, so node ids, leaf ranges, primIdx and pair ids stay
+int Pending::refit_trees()
+{
+    const SceneArrays& sc = b.sc;
+    hipStream_t s = b.stream;
+    nNodes = (uint32_t)b.nNodes; nIdx = (uint32_t)b.nIdx;
+    HIPCHK(hipMemcpyAsync(t.nodes.p, sc.bvh2, sizeof(RtBVHNode2) * (size_t)nNodes, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(t.primIdx.p, sc.primIdx, sizeof(uint32_t) * (size_t)nIdx, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(t.parent.p, b.dParent, sizeof(uint32_t) * (size_t)nNodes, hipMemcpyDeviceToDevice, s));
+    if (b.nLeaves) HIPCHK(hipMemcpyAsync(t.leaves.p, b.dLeaves, sizeof(uint32_t) * (size_t)b.nLeaves, hipMemcpyDeviceToDevice, s));
+    if (b.nPairs) HIPCHK(hipMemcpyAsync(t.pairNode.p, b.dPairNode, sizeof(uint32_t) * (size_t)b.nPairs, hipMemcpyDeviceToDevice, s));
+    HIPCHK(refitdev::launch_refit(s, t.nodes.p, nNodes, t.prims.p, t.primIdx.p, t.leaves.p, b.nLeaves, t.parent.p, t.tickets.p));
+    for (size_t k = 0; k < nR; k++) {
+        rootOf[k] = b.ranges[k].root; interiors[k] = b.blas_interiors(k); depth[k] = b.blasBlock[k].height;
+        maxDepth = std::max(maxDepth, depth[k]);
+    }
+    return RT_OK;
+}
+// Kept trees move as segments: adjacent kept BLAS whose node and index offsets agree are one (rebuilddev::relocate), and their primIdx
+// slots, whose values are global primitive ids of a range that did not move, one plain copy.  A segment is queued when the next range
+// does not extend it, so before anything else touches the set.
+int Pending::flush_kept(KeptSegment& seg)
+{
+    if (!seg.nNodes) return RT_OK;
+    HIPCHK(rebuilddev::relocate(b.stream, b.sc.bvh2 + seg.srcNode, t.nodes.p + seg.dstNode, seg.nNodes, seg.nodeDelta, seg.idxDelta));
+    HIPCHK(hipMemcpyAsync(t.primIdx.p + seg.dstIdx, b.sc.primIdx + seg.srcIdx, sizeof(uint32_t) * (size_t)seg.nIdx, hipMemcpyDeviceToDevice, b.stream));
+    seg = KeptSegment{};
+    return RT_OK;
+}
+// range k keeps its bound tree (room: reserved by size(); the bound values stand for the builder's)
+int Pending::keep_tree(size_t k, KeptSegment& seg)
+{
+    const rebuild::BlasBlock& blk = b.blasBlock[k];
+    const uint32_t root = b.ranges[k].root, nodeDelta = nNodes - root, idxDelta = nIdx - blk.idxLo;
+    if (seg.nNodes && seg.nodeDelta == nodeDelta && seg.idxDelta == idxDelta && seg.srcNode + seg.nNodes == root && seg.srcIdx + seg.nIdx == blk.idxLo) {
+        seg.nNodes += blk.nodes; seg.nIdx += blk.idxSlots;
+    } else {
+        if (const int rc = flush_kept(seg)) return rc;
+        seg = KeptSegment{ root, nNodes, blk.nodes, nodeDelta, blk.idxLo, nIdx, blk.idxSlots, idxDelta };
+    }
+    place(k, blk.nodes, blk.height, blk.idxSlots);
+    return RT_OK;
+}
+// range k is built by plan[k], behind the trees placed so far
+int Pending::build_tree(size_t k)
+{
+    const rebuild::BlasRange& r = ranges[k];
+    const bool sbvh = rq.plan[k] == RT_REBUILD_SBVH;
+    hipStream_t s = b.stream;
+    Built built{};
+    uint32_t slots = r.count;
+    if (sbvh) {
+        // size, then place: the tree stays in the builder's own memory until the set has room for it (one tree at a time)
+        struct TreeGuard { sbvhdev::Tree* p = nullptr; ~TreeGuard() { sbvhdev::destroy(p); } } tree;
+        SbvhBuilt sb{};
+        const float alpha = rq.opts ? rq.opts->alpha : 0.0f;   // (check_builder has seen it)
+        if (const int rc = sbvhdev::build(who, s, alpha, t.prims.p + r.first, r.count, r.first, nNodes, nIdx, nullptr, nullptr, b.spool, &tree.p, &sb)) return rc;
+        // room for this tree and for what the ranges behind it are known to need (nR spare nodes: the leaf and pair arrays hold half the
+        // node capacity, and k trees have k leaves more than interior nodes)
+        const uint64_t nodeNeed = (uint64_t)nNodes + sb.nodes + restNodes[k + 1] + nR, idxNeed = (uint64_t)nIdx + sb.nIdx + restIdx[k + 1];
+        if (sb.nIdx == 0 || nodeNeed > 0x7fffffffull || idxNeed > 0x7fffffffull) return too_many_nodes(who);
+        if (const int rc = rebuild_reserve(b, t, nR, (size_t)idxNeed, (size_t)nodeNeed, nIdx, nNodes)) return rc;
+        if (const int rc = sbvhdev::emit(who, s, tree.p, t.nodes.p + nNodes, t.primIdx.p + nIdx)) return rc;
+        built.nodes = sb.nodes; built.depth = sb.depth; slots = sb.nIdx;
+        spatialSplits += sb.spatialSplits; primsClipped += sb.primsClipped;
+    } else {
+        const int rc = rq.plan[k] == RT_REBUILD_SAH
+            ? sahdev::build(who, s, b.rwork.p, t.prims.p + r.first, r.count, r.first, nNodes, nIdx, t.nodes.p + nNodes, t.primIdx.p + nIdx, nullptr, nullptr, &built)
+            : lbvhdev::build(who, s, b.rwork.p, rq.P, t.prims.p + r.first, r.count, r.first, nNodes, nIdx, t.nodes.p + nNodes, t.primIdx.p + nIdx, nullptr, nullptr, &built);
+        if (rc != RT_OK) return rc;
+    }
+    if (built.nodes == 0 || (built.nodes & 1u) == 0 || (!sbvh && built.nodes > 2 * r.count - 1))
+        return fail(RT_E_DEVICE, "%s: inconsistent builder result (%u nodes for %u primitives)", who, built.nodes, r.count);
+    if ((built.depth == 0) != (built.nodes == 1))
+        return fail(RT_E_DEVICE, "%s: inconsistent builder result (height %u with %u nodes)", who, built.depth, built.nodes);
+    if (rebuild::exceeds_stack(built.depth))   // validate_scene's rule
+        return fail(RT_E_UNSUPPORTED, "%s: the new BLAS %zu needs %u stack entries, at most %d are supported; the scene is unchanged", who, k,
+                    built.depth, RT_BVH4_STACK);
+    nBuilt++;
+    place(k, built.nodes, built.depth, slots);
+    return RT_OK;
+}
+int Pending::trees()
+{
+    rootOf.assign(nR, 0u); interiors.assign(nR, 0u); depth.assign(nR, 0u); idxOf.assign(nR, 0u); slotsOf.assign(nR, 0u);
+    if (refit) {
+        if (const int rc = refit_trees()) return rc;
+    } else {
+        KeptSegment seg;
+        for (size_t k = 0; k < nR; k++) {
+            if (rq.plan[k] == RT_REBUILD_KEEP) { if (const int rc = keep_tree(k, seg)) return rc; continue; }
+            if (const int rc = flush_kept(seg)) return rc;
+            if (const int rc = build_tree(k)) return rc;
+        }
+        if (const int rc = flush_kept(seg)) return rc;
+        if (const int rc = rebuild_scratch(b, (size_t)nNodes + nR)) return rc;
+    }
+    return bvh4 ? collapse_scratch(b, (size_t)nNodes + nR) : RT_OK;
+}
+
+// 4. Derive: the instances (host: at most 256 records), then everything upload derives: numbering, collapse, records, TLAS
+int Pending::derive()
+{
+    const SceneArrays& sc = b.sc;
+    hipStream_t s = b.stream;
+    if (rq.blas) inst.assign(rq.blas, rq.blas + sh.nBlas);
+    else if (!resize) inst = b.inst;
+    else {   // a resize without transforms: BuildBLAS's identity
+        inst.assign((size_t)sh.nBlas, RtBVHInstance{});
+        for (RtBVHInstance& r : inst) r.invT[0] = r.invT[5] = r.invT[10] = r.invT[15] = 1.0f;
+    }
+    for (int32_t i = 0; i < sh.nBlas; i++) inst[(size_t)i].bvhIdx = rootOf[(size_t)(*sh.instBlas)[(size_t)i]];
+    HIPCHK(hipMemcpyAsync(t.blas.p, inst.data(), sizeof(RtBVHInstance) * (size_t)sh.nBlas, hipMemcpyHostToDevice, s));
+    HIPCHK(hipEventRecord(b.rev[1], s));
+    if (refit) {   // the pair records (launch_records rewrites their boxes) and the root entries as they are bound
+        nPairs = (uint32_t)b.nPairs;
+        if (layout1 && !bvh4) {
+            HIPCHK(hipMemcpyAsync(t.pairs.p, sc.pairs, sizeof(RtFloat4) * 4 * std::max<size_t>(nPairs, 1), hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(t.rootEntry.p, sc.rootEntry, sizeof(uint32_t) * (size_t)b.nBlas, hipMemcpyDeviceToDevice, s));
+        }
+    } else {   // pair ids: BLAS by BLAS in the order in which the instances first name them
+        HIPCHK(rebuilddev::begin(s, b.dw, t.parent.p, nNodes));
+        for (const size_t k : order) {
+            HIPCHK(rebuilddev::number_blas(s, b.dw, t.nodes.p, nNodes, rootOf[k], interiors[k], depth[k], nPairs, (uint32_t)t.pairNode.cap, t.pairNode.p, t.parent.p));
+            nPairs += interiors[k];
+        }
+        HIPCHK(rebuilddev::finish(s, b.dw, t.nodes.p, nNodes, nPairs, nNodes - nPairs, t.blas.p, (uint32_t)sh.nBlas, t.pairNode.p, layout1 && !bvh4 ? t.pairs.p : nullptr,
+                                  t.rootEntry.p, t.leaves.p));
+    }
+    if (layout1 && !bvh4 && nPairs == 0) HIPCHK(hipMemsetAsync(t.pairs.p, 0, sizeof(RtFloat4) * 4, s));   // no interior node: one zero record, as at upload
+    nLeaves = refit ? b.nLeaves : nNodes - nPairs;
+    refitPath = refit ? 1 : 0;
+    if (bvh4) {   // the collapse into the set's bvh4, BLAS by BLAS in the same order; quad records and root entries (layout 1)
+        const collapsedev::Work w = collapse_work(b, t.newId.p, t.quadNode.p, std::min(t.quadNode.cap, t.quads.cap / 8));
+        HIPCHK(collapsedev::begin(s, w, t.nodes.p, nNodes, t.bvh4.p));
+        if (refit) {
+            // in place: the live records anew under the bound live ids (the set takes the bound tables over); if no slot of any of
+            // them changed, they are the collapse of the refit trees and the level loop is skipped
+            HIPCHK(hipMemcpyAsync(t.newId.p, b.liveNewId, sizeof(uint32_t) * (size_t)nNodes, hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(t.quadNode.p, b.liveQuadNode, sizeof(uint32_t) * (size_t)b.nLive, hipMemcpyDeviceToDevice, s));
+            HIPCHK(collapsedev::refit_records(s, w, t.nodes.p, nNodes, sc.bvh4, t.quadNode.p, b.nLive, t.bvh4.p));
+            HIPCHK(c4.read(s, w));
+            HIPCHK(hipStreamSynchronize(s));
+            if (const int rc = c4.error(who, "; the scene is unchanged")) return rc;
+            changed = c4.changed();
+            const char* env = getenv("RT355_REFIT_RECOLLAPSE");
+            refitPath = env && atoi(env) == 1 ? 3 : changed ? 2 : 1;
+            if (refitPath != 1) HIPCHK(collapsedev::begin(s, w, t.nodes.p, nNodes, t.bvh4.p));   // the fallback: the rebuild's collapse
+        }
+        if (refitPath != 1)
+            for (const size_t k : order) HIPCHK(collapsedev::collapse_blas(s, w, t.nodes.p, nNodes, rootOf[k], interiors[k], depth[k], t.bvh4.p));
+        HIPCHK(collapsedev::finish(s, w, t.bvh4.p, nNodes, nIdx, (const uint32_t*)t.blas.p, (uint32_t)(sizeof(RtBVHInstance) / 4), (uint32_t)sh.nBlas,
+                                   layout1 ? t.quads.p : nullptr, t.rootEntry.p));
+    }
+    const bool boxes = refit && layout1 && !bvh4;
+    HIPCHK(refitdev::launch_records(s, t.prims.p, t.nodes.p, t.primIdx.p, nIdx, lights, (uint32_t)nLights, 0u, (uint32_t)sh.nPrims,
+                                    boxes ? t.pairNode.p : nullptr, boxes ? nPairs : 0u, boxes ? t.pairs.p : nullptr, layout1 ? t.triRecs.p : nullptr,
+                                    t.shadeRecs.p, t.lightRecs.p));
+    HIPCHK(hipEventRecord(b.rev[2], s));
+    HIPCHK(refitdev::launch_tlas(s, t.nodes.p, t.blas.p, sh.nBlas, layout1 ? t.rootEntry.p : nullptr, t.tlas.p, t.tp.p, t.tpP.p, t.ir.p, b.rStatus));
+    HIPCHK(hipEventRecord(b.rev[3], s));
+    return RT_OK;
+}
+
+// 5. Read back and refuse: the walk, the collapse, the TLAS, the layout; then whatever commit and the stats need of the device
+int Pending::read_back(bool timed)
+{
+    hipStream_t s = b.stream;
+    HIPCHK(hipMemcpyAsync(tlas, b.rStatus, sizeof tlas, hipMemcpyDeviceToHost, s));
+    if (!refit) HIPCHK(hipMemcpyAsync(walk, b.dw.ctr + rebuilddev::kStatus, sizeof walk, hipMemcpyDeviceToHost, s));
+    if (bvh4 && refitPath != 1) HIPCHK(c4.read(s, b.c4));
+    HIPCHK(hipStreamSynchronize(s));
+    if (bvh4 && refitPath == 1) c4.at(collapsedev::kNeed) = b.c4Need;   // (a top-down figure: carried over with the live ids)
+    if (walk[0]) return fail(RT_E_DEVICE, "%s: the breadth-first walk does not match the builder's tree (inconsistent device result)", who);
+    if (bvh4) {
+        if (const int rc = c4.error(who, "; the scene is unchanged")) return rc;
+        walk[1] = c4.largest_leaf();   // the layout rule of a BVH4 looks at the collapsed records
+    }
+    if (const int rc = tlas_status_error(who, tlas)) return rc;
+    stackNeed = bvh4 ? (int)c4.need() : (int)maxDepth;
+    // (a refit moves no leaf size: a BVH2 copy keeps its layout, a BVH4 copy's check cannot fail)
+    if (!(refit && !bvh4) && rebuild::takes_layout1(b.variantLayout1, (int32_t)nIdx, std::max(walk[1], 1u)) != layout1)
+        return fail(RT_E_UNSUPPORTED, "%s: the new trees would change the scene's derived layout (largest leaf %u primitives, %u index slots; "
+                    "layout %d is bound): upload the rebuilt scene instead; the scene is unchanged", who, walk[1], nIdx, b.layout);
+    if (resize) {
+        packed.resize((size_t)sh.nPrims);
+        HIPCHK(hipMemcpy(packed.data(), b.rPacked.p, sizeof(int2) * packed.size(), hipMemcpyDeviceToHost));
+    }
+    if (timed) {   // (the events have passed: the stream is idle)
+        (void)hipEventElapsedTime(&gpuMs, b.rev[0], b.rev[3]); (void)hipEventElapsedTime(&fitMs, b.rev[0], b.rev[1]);
+        (void)hipEventElapsedTime(&deriveMs, b.rev[1], b.rev[2]); (void)hipEventElapsedTime(&tlasMs, b.rev[2], b.rev[3]);
+    }
+    return RT_OK;
+}
+
+// 6. Commit: the holders have been waited for; swap the arrays and take over the new scene's facts.  Host memory only: no device call
+void Pending::commit()
+{
+    SceneArrays n = b.sc;
+    n.prims = t.prims.p; n.bvh2 = t.nodes.p; n.primIdx = t.primIdx.p; n.blas = t.blas.p; n.tlas = t.tlas.p;
+    n.tlasPairs = t.tp.p; n.tlasPairsP = t.tpP.p; n.instRecs = t.ir.p;
+    n.shadeRecs = t.shadeRecs.p; n.lightRecs = t.lightRecs.p;
+    if (resize || b.lightsInSet) n.lights = t.lights.p;
+    if (layout1 && !bvh4) n.pairs = t.pairs.p;
+    if (layout1) { n.triRecs = t.triRecs.p; n.rootEntry = t.rootEntry.p; }
+    if (bvh4) { n.bvh4 = t.bvh4.p; if (layout1) n.quads = t.quads.p; }
+    if (resize) {   // the new shape: the counts, the TLAS root (a leaf iff there is one instance: TLAS::Build copies it to node 0)
+        n.nPrims = sh.nPrims; n.nLights = nLights; n.nBlas = sh.nBlas;
+        const bool leafRoot = sh.nBlas == 1;
+        n.tlasRoot = leafRoot ? refit::kLeafBit : 0u;
+        n.tlasRootP = leafRoot ? refit::kTagInst : refit::kTagTlas;
+        b.singleBlas = leafRoot; b.lightsInSet = true;
+        b.nPrims = sh.nPrims; b.nLights = nLights; b.nBlas = sh.nBlas; b.nTlas = sh.nTlas();
+        b.primType.resize(packed.size()); b.primMat.resize(packed.size());
+        for (size_t i = 0; i < packed.size(); i++) { b.primType[i] = packed[i].x; b.primMat[i] = packed[i].y; }
+        b.ranges = *sh.ranges; b.instBlas = *sh.instBlas;   // (the caller's own vectors: never the bag's)
+    }
+    b.sc = n;
+    b.dParent = t.parent.p; b.dLeaves = t.leaves.p; b.dTickets = t.tickets.p; b.dPairNode = t.pairNode.p;
+    b.nNodes = (int32_t)nNodes; b.nIdx = (int32_t)nIdx; b.nPairs = layout1 && !bvh4 ? (int32_t)nPairs : 0; b.nLeaves = nLeaves;
+    b.nQuads = layout1 && bvh4 ? (int32_t)c4.live() : 0;
+    if (!refit) {   // (a refit moves no tree: roots and blocks stay)
+        b.nReach = nNodes;
+        b.blasBlock.resize(nR);
+        for (size_t k = 0; k < nR; k++) {
+            b.ranges[k].root = rootOf[k];
+            b.blasBlock[k] = rebuild::BlasBlock{ 2 * interiors[k] + 1, idxOf[k], slotsOf[k], 1, depth[k] };
+        }
+    }
+    if (bvh4) {   // the live collapse's tables follow the sets
+        b.liveNewId = t.newId.p; b.liveQuadNode = t.quadNode.p;
+        b.nLive = c4.live(); b.c4Need = c4.need();
+    }
+    if (refit) b.refitInfo = RtRefitInfo{ refitPath, bvh4 ? (int32_t)b.nLive : 0, (int32_t)changed, stackNeed };
+    b.inst = inst;
+    const int stackEntries = rebuild::stack_entries(std::max(stackNeed, 1));   // (a BVH4: the collapsed trees' need, as validate_scene replays it)
+    reconfigured = tlas[1] != b.tlasDepth || stackEntries != b.stackEntries;
+    b.tlasDepth = tlas[1];
+    b.stackEntries = stackEntries;
+    b.nInterior = layout1 && !bvh4 ? (int)nPairs : 0;
+    b.generation++;   // every holder takes the new arrays (and re-derives its traversal kernels) before its next launch
+    b.rnext ^= 1;
+}
+
+static int rebuild_body(SceneBag& b, const Request& rq, RtRebuildStats* stats)
+{
+    Pending pd{ b, rq };
+    if (const int rc = pd.size()) return rc;
+    HIPCHK(hipEventRecord(b.rev[0], b.stream));
+    if (const int rc = pd.stage()) return rc;
+    pd.t1 = Pending::clock::now();
+    if (const int rc = pd.trees()) return rc;
+    pd.t2 = Pending::clock::now();
+    if (const int rc = pd.derive()) return rc;
+    if (const int rc = pd.read_back(stats != nullptr)) return rc;
+    pd.t3 = Pending::clock::now();
+    if (const int rc = b.wait_holders()) return rc;   // no kernel of a holder reads the old arrays any more
+    pd.commit();
+    const auto t4 = Pending::clock::now();
+    if (stats) {
+        *stats = RtRebuildStats{};
+        stats->gpu_ms = pd.gpuMs; stats->wall_ms = ms_between(pd.t0, t4);
+        stats->stage_ms = ms_between(pd.t0, pd.t1); stats->derive_ms = pd.deriveMs; stats->tlas_ms = pd.tlasMs;
+        stats->build_ms = pd.refit ? pd.fitMs : ms_between(pd.t1, pd.t2);   // (a refit: GPU time of the staging copies and the refit)
+        stats->commit_ms = ms_between(pd.t3, t4);
+        stats->prims = pd.resize ? rq.sh.nPrims : rq.count; stats->blas_built = pd.nBuilt; stats->nodes = (int32_t)pd.nNodes; stats->n_idx = (int32_t)pd.nIdx;
+        stats->max_depth = (int32_t)pd.maxDepth; stats->tlas_nodes = b.nTlas; stats->tlas_depth = pd.tlas[1]; stats->reconfigured = pd.reconfigured ? 1 : 0;
+        stats->spatial_splits = (int32_t)std::min<uint64_t>(pd.spatialSplits, 0x7fffffffu); stats->prims_clipped = (int32_t)std::min<uint64_t>(pd.primsClipped, 0x7fffffffu);
+    }
+    return RT_OK;
+}
+int scenedev::rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
+                            int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats)
+{
+    const char* who = "rt_rebuild_scene";
+    // ---- refusals that need no device work
+    if (b.refitRefusal) return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: %s", b.refitRefusal);
+    if (b.rebuildRefusal) return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: %s", b.rebuildRefusal);
+    if (const int rc = check_builder(who, builder, opts, true)) return rc;
+    if (const int rc = check_change(who, b, prims, first, count, blas, nBlas, "")) return rc;
+    lbvh::Params P{};
+    const std::vector<int32_t> plan(builder == RT_REBUILD_REFIT ? 0 : b.ranges.size(), builder);   // every range: `builder`
+    if (!plan.empty()) if (const int rc = check_ranges(who, plan.data(), opts, b.nPrims, b.ranges, nullptr, P)) return rc;
+    const Shape sh{ b.nPrims, b.nBlas, b.nLights, &b.ranges, &b.instBlas };
+    return rebuild_body(b, Request{ who, sh, nullptr, prims, first, count, blas, plan, opts, P }, stats);
+}
+// The checks of a plan that need no device: the plan itself (rebuild::check_plan), alpha and the builders' own argument checks
+static int plan_check_args(const char* who, int32_t nPrims, const std::vector<rebuild::BlasRange>& ranges, const rebuild::BlasBlock* blocks, const int32_t* plan,
+                           int32_t nRanges, int32_t first, int32_t count, const RtBuildOptions* opts, lbvh::Params& P)
+{
+    std::string msg;
+    if (const int rc = rebuild::check_plan(plan, nRanges, ranges, blocks, first, count, msg)) return fail(rc, "%s: %s", who, msg.c_str());
+    if (const int rc = check_plan_alpha(who, plan, ranges.size(), opts)) return rc;
+    return check_ranges(who, plan, opts, nPrims, ranges, blocks, P);
+}
+extern "C" int rt_rebuild_ranges_check(int32_t nPrims, const int32_t* rangeFirst, const int32_t* rangeCount, const int32_t* compact, int32_t nBound,
+                                       const int32_t* plan, int32_t nRanges, int32_t first, int32_t count, const RtBuildOptions* opts)
+{
+    const char* who = "rt_rebuild_ranges";
+    if (nPrims <= 0 || nBound <= 0 || !rangeFirst || !rangeCount) return fail(RT_E_INVALID, "%s: the ranges of at least one BLAS are needed (nPrims %d, %d ranges)", who, nPrims, nBound);
+    std::vector<rebuild::BlasRange> ranges((size_t)nBound);
+    std::vector<rebuild::BlasBlock> blocks((size_t)nBound);
+    int64_t next = 0;
+    for (int32_t k = 0; k < nBound; k++) {
+        if (rangeCount[k] < 1 || rangeFirst[k] < next || (int64_t)rangeFirst[k] + rangeCount[k] > (int64_t)nPrims)
+            return fail(RT_E_INVALID, "%s: range %d (first %d, count %d): ranges hold at least one primitive, lie in [0, %d) and come in increasing order without overlap",
+                        who, k, rangeFirst[k], rangeCount[k], nPrims);
+        next = (int64_t)rangeFirst[k] + rangeCount[k];
+        ranges[(size_t)k] = rebuild::BlasRange{ 0u, (uint32_t)rangeFirst[k], (uint32_t)rangeCount[k] };
+        blocks[(size_t)k] = rebuild::BlasBlock{ 2 * (uint32_t)rangeCount[k] - 1, 0u, (uint32_t)rangeCount[k], (uint8_t)(!compact || compact[k] ? 1 : 0), 0u };
+    }
+    if (count < 0 || (count > 0 && (first < 0 || (int64_t)first + count > (int64_t)nPrims)))
+        return fail(RT_E_INVALID, "%s: primitive range [%d, %lld) outside the %d uploaded", who, first, (long long)first + count, nPrims);
+    lbvh::Params P{};
+    return plan_check_args(who, nPrims, ranges, blocks.data(), plan, nRanges, first, count, opts, P);
+}
+int scenedev::rebuild_ranges(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
+                             const int32_t* plan, int32_t nRanges, const RtBuildOptions* opts, RtRebuildStats* stats)
+{
+    const char* who = "rt_rebuild_ranges";
+    // ---- refusals that need no device work
+    if (b.refitRefusal) return fail(RT_E_UNSUPPORTED, "%s: %s", who, b.refitRefusal);
+    if (b.rebuildRefusal) return fail(RT_E_UNSUPPORTED, "%s: %s", who, b.rebuildRefusal);
+    if (const int rc = check_change(who, b, prims, first, count, blas, nBlas, "")) return rc;
+    lbvh::Params P{};
+    if (const int rc = plan_check_args(who, b.nPrims, b.ranges, b.blasBlock.data(), plan, nRanges, first, count, opts, P)) return rc;
+    const Shape sh{ b.nPrims, b.nBlas, b.nLights, &b.ranges, &b.instBlas };
+    return rebuild_body(b, Request{ who, sh, nullptr, prims, first, count, blas, std::vector<int32_t>(plan, plan + nRanges), opts, P }, stats);
+}
+
+// The ranges of a caller's shape as the builders take them (root: assigned by the build)
+static std::vector<rebuild::BlasRange> shape_ranges(const RtSceneShape& shape)
+{
+    std::vector<rebuild::BlasRange> r((size_t)shape.nRanges);
+    uint32_t first = 0;
+    for (int32_t k = 0; k < shape.nRanges; k++) { r[(size_t)k] = rebuild::BlasRange{ 0u, first, (uint32_t)shape.rangeCount[k] }; first += (uint32_t)shape.rangeCount[k]; }
+    return r;
+}
+// What rt_resize_scene checks without a device or a scene (rt_resize_check): the shape, the builder, its options
+// (ranges receives the shape's ranges)
+static int resize_check_args(const char* who, int32_t nPrims, const RtSceneShape* shape, int32_t builder, const RtBuildOptions* opts, lbvh::Params& P,
+                             std::vector<rebuild::BlasRange>& ranges)
+{
+    if (!shape) return fail(RT_E_INVALID, "%s: null shape", who);
+    std::string msg;
+    if (resize::check_shape(nPrims, shape->nRanges, shape->rangeCount, shape->nBlas, shape->instRange, shape->blas, msg)) return fail(RT_E_INVALID, "%s: %s", who, msg.c_str());
+    if (const int rc = check_builder(who, builder, opts, false)) return rc;
+    ranges = shape_ranges(*shape);
+    const std::vector<int32_t> plan(ranges.size(), builder);
+    return check_ranges(who, plan.data(), opts, nPrims, ranges, nullptr, P);
+}
+extern "C" int rt_resize_check(int32_t nPrims, const RtSceneShape* shape, int32_t builder, const RtBuildOptions* opts)
+{
+    lbvh::Params P{};
+    std::vector<rebuild::BlasRange> ranges;
+    return resize_check_args("rt_resize_scene", nPrims, shape, builder, opts, P, ranges);
+}
+int scenedev::resize_scene(SceneBag& b, const void* prims, int32_t nPrims, const RtSceneShape* shape, int32_t builder, const RtBuildOptions* opts,
+                           RtRebuildStats* stats)
+{
+    const char* who = "rt_resize_scene";
+    // ---- refusals that need no device work
+    lbvh::Params P{};
+    std::vector<rebuild::BlasRange> ranges;
+    if (const int rc = resize_check_args(who, nPrims, shape, builder, opts, P, ranges)) return rc;
+    if (b.refitRefusal) return fail(RT_E_UNSUPPORTED, "rt_resize_scene: %s", b.refitRefusal);
+    if (b.rebuildRefusal) return fail(RT_E_UNSUPPORTED, "rt_resize_scene: %s", b.rebuildRefusal);
+    {   // the bound ranges (in increasing order) must tile the bound primitives
+        uint32_t next = 0;
+        for (const rebuild::BlasRange& r : b.ranges) {
+            if (r.first != next) return fail(RT_E_UNSUPPORTED, "rt_resize_scene: the bound scene's BLAS ranges leave a gap: primitives [%u, %u) belong to no BLAS", next, r.first);
+            next = r.first + r.count;
+        }
+        if (next != (uint32_t)b.nPrims)
+            return fail(RT_E_UNSUPPORTED, "rt_resize_scene: the bound scene's BLAS ranges leave a gap: primitives [%u, %d) belong to no BLAS", next, b.nPrims);
+    }
+    const std::vector<int32_t> instBlas(shape->instRange, shape->instRange + shape->nBlas);
+    const Shape sh{ nPrims, shape->nBlas, 0, &ranges, &instBlas };
+    return rebuild_body(b, Request{ who, sh, prims, nullptr, 0, 0, shape->blas, std::vector<int32_t>(ranges.size(), builder), opts, P }, stats);   // (never RT_REBUILD_KEEP)
+}

@@ -80,8 +80,7 @@ void BVH2::RebuildPlan(const char* who, const int32_t* plan, int nRanges, const 
             nodes.insert(nodes.end(), bvhNodes.begin() + r.root, bvhNodes.begin() + r.root + blk.nodes);
             for (size_t i = nodeBase; i < nodes.size(); i++) nodes[i].first = rebuild::relocated_first(nodes[i].first, nodes[i].count, nodeDelta, idxDelta);
             idx.insert(idx.end(), primIdx.begin() + blk.idxLo, primIdx.begin() + blk.idxLo + blk.idxSlots);
-            const uint32_t d = Depth(r.root);
-            if (d > depth) depth = d;
+            if (blk.height > depth) depth = blk.height;
             continue;
         }
         if (sbvh) {   // the tree's size is known only once it is built: `written` nodes and nIdx indices are appended

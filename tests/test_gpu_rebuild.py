@@ -8,6 +8,7 @@ import sys
 import numpy as np
 import pytest
 
+import ranges_check as RC
 import rebuild_check as RB
 import refit_check as R
 import test_gpu_groundtruth as GT
@@ -599,3 +600,55 @@ def test_scenes_without_a_context_scene_or_of_another_tlas_shape_are_refused():
             assert d.kernel_info() == info
         finally:
             d.close()
+
+
+# ---- the preamble of every entry point that changes or inspects a bound copy -------------------------------------------------------------
+def _calls(sa):
+    """name -> the call on a Device, with arguments that pass every check before the one the table is about."""
+    return {
+        "rt_update_scene": lambda d: d.update_scene(),
+        "rt_rebuild_scene": lambda d: d.rebuild_scene(),
+        "rt_rebuild_ranges": lambda d: d.rebuild_ranges(["sah", "keep", "keep"]),
+        "rt_resize_scene": lambda d: d.resize_scene(sa.prims, list(RC.COUNTS)),
+        "rt_update_materials": lambda d: d.update_materials(mats=sa.mats),
+        "rt_scene_blas_blocks": lambda d: d.blas_blocks(),
+        "rt_refit_info": lambda d: d.refit_info(),
+        "rt_debug_rebuild_allocations": lambda d: d.rebuild_allocations(),
+        "rt_debug_get_scene_array": lambda d: d.scene_array("prims"),
+    }
+
+
+def _refusal(d, call):
+    d._chk = d._chk_code            # (every wrapper then reports the code)
+    with pytest.raises(RtError) as e:
+        call(d)
+    return e.value.code, str(e.value)
+
+
+def test_the_preamble_of_every_entry_point_on_a_bound_copy():
+    """A 16 x 16 context, no frame.  Without a scene each entry point answers RT_E_INVALID '<entry point>: no scene uploaded'; on a BVH4
+    context bound through plain rt_upload_scene those that need the BVH2 answer RT_E_UNSUPPORTED 'lost its BVH2', rt_update_scene 'BVH4
+    contexts cannot refit', and every array stays byte for byte what it was."""
+    sa = RC.scene().arrays()
+    assert len(sa.prims) == sum(RC.COUNTS)
+    calls = _calls(sa)
+    empty = Device(16, 16, **DEFAULT)
+    try:
+        for name, call in calls.items():
+            assert _refusal(empty, call) == (W.RT_E_INVALID, f"{name}: no scene uploaded"), name
+    finally:
+        empty.close()
+    every = [*W.SCENE_ARRAYS, *W.SCENE_ARRAYS_BVH4, *W.SCENE_ARRAYS_RESIZE, *W.SCENE_ARRAYS_MATERIALS]
+    d4 = Device(16, 16, **dict(DEFAULT, accel=W.ACCEL_BVH4))
+    try:
+        d4.upload(sa)
+        before, info = {k: d4.scene_array(k) for k in every}, d4.kernel_info()
+        table = [(name, "lost its BVH2") for name in ("rt_rebuild_scene", "rt_rebuild_ranges", "rt_resize_scene", "rt_scene_blas_blocks")]
+        for name, frag in table + [("rt_update_scene", "BVH4 contexts cannot refit")]:
+            code, text = _refusal(d4, calls[name])
+            assert code == W.RT_E_UNSUPPORTED and text.startswith(name + ": ") and frag in text, (name, code, text)
+            for k in every:
+                assert np.array_equal(d4.scene_array(k), before[k]), (name, k)
+            assert d4.kernel_info() == info, name
+    finally:
+        d4.close()
