@@ -119,6 +119,32 @@ int rt_builtins(RtCtx* ctx);   /* the context's arithmetic, resolved: RT_BUILTIN
 /* Levels of the BLAS that the event loops of extend and of connect descend from a table in LDS when a lane takes a new ray (0..6; 0: no
  * table.  Single-BLAS BVH2 scenes under persistent wavefronts only, else 0; RT355_TOP_LEVELS overrides the defaults) */
 int rt_top_levels(RtCtx* ctx, int32_t* extend, int32_t* connect);
+/* How a context chooses its traversal, for tests (the rules: csrc/trav_common.h, free of the device).  The plan is a function of these
+ * facts and of the RT355_* traversal knobs in the environment. */
+typedef struct RtTraversalFacts {
+    int32_t accel, extend_variant, persist_blocks_per_cu;   /* of RtConfig                                                          */
+    int32_t layout;              /* of the scene copy: RtKernelInfo.layout                                                            */
+    int32_t singleBlas;          /* the TLAS root is a leaf (0 / 1)                                                                    */
+    int32_t tlasDepth;           /* levels of the TLAS                                                                                 */
+    int32_t nInterior, nQuads;   /* records of the pair table (BVH2) and of the quad table (BVH4) in layout 1: ids must fit 29 bits    */
+    int32_t stackEntries;        /* traversal stack entries the deepest BLAS needs                                                     */
+    int32_t sharedMemPerBlock;   /* of the device: bytes of LDS a workgroup may ask for                                                */
+    int32_t xcdFirst;            /* the XCD (0..7) this context's sparse queues start on; handed out per context, passed through       */
+} RtTraversalFacts;
+#define RT_TUNE_FIELDS 11   /* a launch tune as integers: chunk, refill, inner, leafK, fixedChunks, flat, xcdRays, xcdFirst, thin, topLevels, topBase */
+typedef struct RtTraversalPlan {
+    int32_t trav;                /* 0 nested loops, 1 BVH2, 2 TLAS, 3 TLAS with spilling stacks, 4 BVH4, 5 BVH4 TLAS, 6 BVH4 TLAS with spilling stacks */
+    int32_t spillCap;            /* LDS stack entries per lane of a spilling kernel (12, or RT355_SPILL_CAP)                           */
+    int32_t coherent;            /* RT355_COHERENT, default 1                                                                          */
+    int32_t topAuto;             /* 1: no knob named the LDS top table's depth, the context fits it to the device (rt_top_levels)      */
+    int32_t tuneBlocks, connectBlocks;   /* workgroups per CU asked of the persistent grids by RT355_TUNE's fifth field / RT355_CONNECT_BLOCKS, else 0 */
+    int32_t tune[RT_TUNE_FIELDS], tuneConnect[RT_TUNE_FIELDS], tune4[RT_TUNE_FIELDS];   /* extend (BVH2), connect, extend (BVH4), before
+                                  * the context fits topLevels to the device; topBase is set per launch and 0 here                      */
+} RtTraversalPlan;
+/* The plan of `facts` under the knobs as the environment holds them now.  Needs no device and no context. */
+int rt_debug_traversal_plan(const RtTraversalFacts* facts, RtTraversalPlan* out);
+/* The facts this context's configuration is planned from (it takes over a changed scene copy first, as rt_kernel_info does). */
+int rt_debug_traversal_facts(RtCtx* ctx, RtTraversalFacts* out);
 /* What shares a CU when contexts run side by side.  *ldsBytes: the static LDS of a workgroup of this context's k_shade instantiation
  * (256 slots for the lanes of a group, 512 for a context alone).  *traversalBeside: how many workgroups of the context's persistent
  * extend kernel, without a top table, fit a CU beside one such workgroup - by LDS, VGPRs and wave slots, from the kernels' own

@@ -59,6 +59,13 @@ TRACE_CLOSEST, TRACE_ANY = 0, 1
 REALLYFAR = np.float32(1e30)
 KernelInfo = np.dtype([(n, "<i4") for n in ("layout", "persist", "persist4", "stack_entries", "persist_grid", "persist_grid_connect",
                                              "shade_grid", "n_blas")])
+TUNE_FIELDS = ("chunk", "refill", "inner", "leafK", "fixedChunks", "flat", "xcdRays", "xcdFirst", "thin", "topLevels", "topBase")
+TraversalFacts = np.dtype([(n, "<i4") for n in ("accel", "extend_variant", "persist_blocks_per_cu", "layout", "singleBlas", "tlasDepth", "nInterior",
+                                                 "nQuads", "stackEntries", "sharedMemPerBlock", "xcdFirst")])   # RtTraversalFacts
+TraversalPlan = np.dtype([(n, "<i4") for n in ("trav", "spillCap", "coherent", "topAuto", "tuneBlocks", "connectBlocks")] +
+                         [(n, "<i4", len(TUNE_FIELDS)) for n in ("tune", "tuneConnect", "tune4")])   # RtTraversalPlan
+TRAV_NESTED, TRAV_BVH2, TRAV_TLAS, TRAV_TLAS_SPILL, TRAV_BVH4, TRAV_BVH4_TLAS, TRAV_BVH4_TLAS_SPILL = range(7)   # RtTraversalPlan.trav
+assert TraversalFacts.itemsize == 44 and TraversalPlan.itemsize == 156
 
 _SIZES = {"Ray": (Ray, 128), "ShadowRay": (ShadowRay, 96), "Material": (Material, 80), "Primitive": (Primitive, 128),
           "Camera": (Camera, 128), "Settings": (Settings, 40), "BVHNode2": (BVHNode2, 48), "BVHNode4": (BVHNode4, 160),
@@ -137,7 +144,8 @@ DEVICE_SYMBOLS = [
     "rt_group_seed", "rt_group_reset", "rt_group_render", "rt_group_synchronize", "rt_group_sum", "rt_group_read_accum", "rt_group_focus",
     "rt_group_postproc", "rt_trace", "rt_trace_window", "rt_resize_scene", "rt_group_resize_scene", "rt_resize_check",
     "rt_update_materials", "rt_group_update_materials", "rt_materials_check",
-    "rt_rebuild_ranges", "rt_group_rebuild_ranges", "rt_scene_blas_blocks", "rt_rebuild_ranges_check", "rt_blas_blocks"]
+    "rt_rebuild_ranges", "rt_group_rebuild_ranges", "rt_scene_blas_blocks", "rt_rebuild_ranges_check", "rt_blas_blocks",
+    "rt_debug_traversal_plan", "rt_debug_traversal_facts"]
 HOST_SYMBOLS = [
     "rth_last_error", "rth_scene_create", "rth_scene_destroy", "rth_add_material", "rth_add_texture", "rth_load_texture", "rth_add_sphere",
     "rth_add_plane", "rth_add_triangle", "rth_add_quad", "rth_add_triangles", "rth_build_blas", "rth_build_bvh4",
@@ -196,6 +204,8 @@ def _bind_device(lib):
         lib.rt_kernel_info.argtypes = [vp, vp]
         lib.rt_builtins.argtypes = [vp]
         lib.rt_top_levels.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+        lib.rt_debug_traversal_plan.argtypes = [vp, vp]
+        lib.rt_debug_traversal_facts.argtypes = [vp, vp]
         lib.rt_shade_footprint.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
         lib.rt_shade_tables.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
         lib.rt_destroy.argtypes = [vp]

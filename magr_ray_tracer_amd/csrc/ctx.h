@@ -17,6 +17,7 @@ struct RtCtx {
     rt355dev::DevQueues q{};
     rt355dev::DevVariant var{};
     int nPix = 0, firstPixel = 0, gridMax = 0;
+    int cuCount = 0; size_t ldsPerBlock = 0, ldsPerCU = 0;   // of cfg.device, asked once by rt_create: CUs, the LDS a workgroup may ask for, the LDS of a CU
     bool sceneLoaded = false, ownAccum = true;
     std::shared_ptr<scenedev::SceneBag> scene;   // shared by the contexts of rt_share_scene, freed with the last of them
     uint64_t sceneGen = 0;                // the SceneBag generation this context's traversal configuration was derived for
@@ -42,6 +43,7 @@ struct RtCtx {
     bool generated = false;                           // generate launched since the last k_begin_frame
     int stackEntries = RT_BVH2_STACK, persistGrid = 0, persistGridConnect = 0;
     rt355dev::PersistTune tune{}, tuneConnect{}, tune4{};   // extend (BVH2), connect, extend (BVH4): set by configure_traversal
+    int tuneBlocks = 0, connectBlocks = 0;   // workgroups per CU the knobs ask of the persistent grids (TravPlan; persist_blocks)
     float4* dPostF = nullptr; uchar4* dPostB = nullptr;   // post-processing outputs (lazy)
     int32_t* dSteps = nullptr;   // per-ray `steps` buffer, only bound while rt_debug_enable_steps is on
     // rt_trace's own DevQueues view (lazy): count, cursor and fault words and a counter table that no frame reads or writes, and queue

@@ -21,15 +21,8 @@
 using namespace rt355dev;
 using namespace scenedev;
 
-// workgroups of 256 threads the hardware admits per CU whatever the occupancy query says: any kernel / kernels with <= 96 SGPRs
-static constexpr int kAdmitAnySgpr = 6, kAdmit96Sgpr = 7;
-// LDS words per lane of k_trace_persist_tlas: 22 x 1 KB per workgroup is the most with which seven workgroups share a CU's 160 KB; the
-// world ray (O, D, 1/D) and the TLAS level's pruning distance wait in 10 of them while a lane is inside an instance, so a spilling
-// kernel keeps 12 stack entries in LDS
-// levels of the LDS top table of k_trace_persist's event loops, extend and connect, at most: a context takes the deepest table that does
-// not cost its persistent grid a resident workgroup (configure_traversal; EXPERIMENTS.md (59)).  0 = the instantiations without it
-static constexpr int kTopLevelsExtend = 6, kTopLevelsConnect = 6;
-static constexpr int kFitSeven = 22, kBackupWords = 10, kSpillCap = kFitSeven - kBackupWords;
+// (the Traversal kinds, their constants and the column arithmetic: trav_common.h, which cannot see the kernels' own sizes)
+static_assert(kColumnLanes == kBlock && kTopLevelsMax == kTopMaxLevels && sizeof(float4) * 4 == 64, "trav_common.h computes with the kernels' sizes");
 static thread_local std::string g_err;
 int rt355_set_error(int code, const char* msg) { g_err = msg; return code; }   // for every source file of this library (fail, build_fail)
 
@@ -46,20 +39,6 @@ static void choose_builtin_kernels(RtCtx* ctx)   // needs cfg (builtins resolved
     else choose_builtin_kernels_of<false>(ctx);
 }
 enum { ST_GENERATE, ST_EXTEND, ST_SHADE, ST_COMPACT, ST_CONNECT, ST_ACCUM };
-// The traversal kernels of a context (layout 1 only; the first four values are RtKernelInfo.persist):
-enum Traversal {
-    TRAV_NESTED,        // the one-ray-per-lane nested loops (k_extend / k_connect)
-    TRAV_BVH2,          // persistent wavefronts over the BVH2 of a single BLAS (k_trace_persist)
-    TRAV_TLAS,          // ... through a multi-BLAS TLAS (k_trace_persist_tlas)
-    TRAV_TLAS_SPILL,    // ... with the deep end of the traversal stacks in global memory (trees deeper than the LDS share of 7 workgroups per CU)
-    TRAV_BVH4,          // ... over the BVH4 of a single BLAS (k_trace_persist4)
-    TRAV_BVH4_TLAS,     // ... through a multi-BLAS TLAS over BVH4 instances (k_trace_persist4_tlas; extend_variant 6 only)
-    TRAV_BVH4_TLAS_SPILL,   // ... with the deep end of the traversal stacks in global memory
-};
-static bool persistent(const RtCtx* c) { return c->trav != TRAV_NESTED; }
-static bool spill_trav(const RtCtx* c) { return c->trav == TRAV_TLAS_SPILL || c->trav == TRAV_BVH4_TLAS_SPILL; }
-static bool bvh4_tlas_trav(const RtCtx* c) { return c->trav == TRAV_BVH4_TLAS || c->trav == TRAV_BVH4_TLAS_SPILL; }
-static bool tlas_trav(const RtCtx* c) { return c->trav == TRAV_TLAS || c->trav == TRAV_TLAS_SPILL || bvh4_tlas_trav(c); }   // one tagged column per lane, world-ray backup behind it
 
 extern "C" const char* rt_last_error(void) { return g_err.c_str(); }
 extern "C" int rt_device_count(void) { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess) return 0; return n; }
@@ -76,7 +55,7 @@ extern "C" int rt_kernel_info(RtCtx* ctx, RtKernelInfo* out)
     if (const int rc = sync_scene_config(ctx)) return rc;
     const int persist = ctx->trav <= TRAV_TLAS_SPILL ? ctx->trav : 0;
     const int persist4 = ctx->trav == TRAV_BVH4 ? 1 : (ctx->trav == TRAV_BVH4_TLAS ? 2 : (ctx->trav == TRAV_BVH4_TLAS_SPILL ? 3 : 0));
-    *out = RtKernelInfo{ ctx->layout, persist, persist4, spill_trav(ctx) ? ctx->spillCap : ctx->stackEntries, ctx->persistGrid, ctx->persistGridConnect,
+    *out = RtKernelInfo{ ctx->layout, persist, persist4, spill_trav(ctx->trav) ? ctx->spillCap : ctx->stackEntries, ctx->persistGrid, ctx->persistGridConnect,
                          ctx->shadeGrid, ctx->sc.nBlas };
     return RT_OK;
 }
@@ -97,7 +76,7 @@ extern "C" int rt_shade_footprint(RtCtx* ctx, int32_t* ldsBytes, int32_t* traver
     if (!ctx->sceneLoaded) return fail(RT_E_INVALID, "rt_shade_footprint: no scene uploaded");
     if (const int rc = sync_scene_config(ctx)) return rc;
     *ldsBytes = 0; *traversalBeside = 0;
-    if (!persistent(ctx)) {   // no persistent grid to count: the footprint alone
+    if (!persistent(ctx->trav)) {   // no persistent grid to count: the footprint alone
         hipFuncAttributes a{};
         HIPCHK(hipFuncGetAttributes(&a, (const void*)ctx->kShade));
         *ldsBytes = (int32_t)a.sharedSizeBytes;
@@ -145,16 +124,8 @@ int SceneBag::wait_holders() const
     return RT_OK;
 }
 
-// LDS traversal stack: one column per lane; sized at upload to what this scene's trees can need
-// (never more than the reference kernels' 32 / 64 entries).
-static size_t stack_bytes(const RtCtx* c) { return (size_t)c->stackEntries * kBlock * sizeof(uint32_t); }
-// the top table of k_trace_persist<.., TOP> behind them: 2^levels - 1 pair records of 64 bytes
-static size_t top_bytes(int levels) { return levels > 0 ? (((size_t)1 << levels) - 1) * 4 * sizeof(float4) : 0; }
-// k_trace_persist_tlas keeps its pending TLAS siblings (<= one per level) on the same column; with TRAV_TLAS_SPILL only the first spillCap
-// entries of a column live in LDS.  The world-ray backup sits behind them.
-static int tlas_stack_entries(const RtCtx* c) { return c->stackEntries + c->tlasDepth + 1; }
-static int tlas_lds_entries(const RtCtx* c) { return spill_trav(c) ? c->spillCap : tlas_stack_entries(c); }
-static size_t tlas_column_bytes(int entries) { return (size_t)(entries + kBackupWords) * kBlock * sizeof(uint32_t); }
+// The dynamic LDS of a context's TLAS kernels: its column entries (trav_common.h) with the world-ray backup behind them
+static int tlas_lds_entries(const RtCtx* c) { return tlas_lds_entries(c->trav, c->spillCap, c->stackEntries, c->tlasDepth); }
 static size_t tlas_stack_bytes(const RtCtx* c) { return tlas_column_bytes(tlas_lds_entries(c)); }
 
 // The traversal launch of a stage: the one place that maps (stage, bounce, steps wanted) to a kernel instantiation, its grid, its dynamic
@@ -173,7 +144,7 @@ static TraceLaunch trace_launch(const RtCtx* c, int stage, int bounce, bool step
 {
     TraceLaunch L;
     L.grid = grid_for(rays);
-    L.lds = stack_bytes(c);
+    L.lds = stack_bytes(c->stackEntries);
     const bool connect = stage == ST_CONNECT;
     const bool bvh4 = c->cfg.accel == RT_ACCEL_BVH4, l1 = c->layout == 1;
     bool top = false;
@@ -255,15 +226,15 @@ static int persist_query(const RtCtx* c, int stage, int topLevels, int* perCU)
 // Workgroups per CU of a stage's persistent grid, given that answer.  The closest-hit instantiations use ~90 SGPRs, the any-hit ones ~100:
 // the hardware admits 7 resp. 6 workgroups per CU where the query may say more (see rt_create); a surplus workgroup would strand its static
 // first chunk until another exits.  Contexts that share the GPU take RtConfig.persist_blocks_per_cu at most; RT355_TUNE's fifth field and,
-// for connect, RT355_CONNECT_BLOCKS (lab) override both.
-static int persist_blocks(const RtCtx* c, int stage, int perCU, int tuneBlocks)
+// for connect, RT355_CONNECT_BLOCKS (lab) override both (the plan's tuneBlocks and connectBlocks).
+static int persist_blocks(const RtCtx* c, int stage, int perCU)
 {
     const bool connect = stage == ST_CONNECT;
     const int fit = std::max(1, perCU);
     int g = std::max(1, std::min(perCU, connect ? kAdmitAnySgpr : kAdmit96Sgpr));
     if (c->cfg.persist_blocks_per_cu > 0) g = std::min(g, std::min(c->cfg.persist_blocks_per_cu, fit));
-    if (tuneBlocks > 0) g = std::min(tuneBlocks, fit);
-    if (connect) if (const char* t = getenv("RT355_CONNECT_BLOCKS")) { const int d = atoi(t); if (d > 0) g = std::min(d, fit); }
+    if (c->tuneBlocks > 0) g = std::min(c->tuneBlocks, fit);
+    if (connect && c->connectBlocks > 0) g = std::min(c->connectBlocks, fit);
     return g;
 }
 
@@ -279,12 +250,10 @@ static int beside_shade(const RtCtx* c, int stage, int topLevels, int* perCU, in
 {
     const TraceLaunch L = trace_launch(c, stage, stage == ST_CONNECT ? 0 : 1, false, c->nPix, topLevels);
     hipFuncAttributes shade{}, trav{};
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, c->cfg.device));
     HIPCHK(hipFuncGetAttributes(&shade, (const void*)c->kShade));
     HIPCHK(hipFuncGetAttributes(&trav, (const void*)L.persist));
     auto alloc = [](int regs) { return std::max(8, (regs + 7) / 8 * 8); };
-    const size_t ldsCU = std::max(prop.maxSharedMemoryPerMultiProcessor, prop.sharedMemPerBlock);
+    const size_t ldsCU = std::max(c->ldsPerCU, c->ldsPerBlock);
     auto blocks = [](size_t bytes) { return (bytes + kLdsBlock - 1) / kLdsBlock * kLdsBlock; };
     const size_t travLds = blocks(trav.sharedSizeBytes + L.lds), shadeLdsCU = blocks(shade.sharedSizeBytes);
     const int shadeWaves = std::max(1, c->shadeTile / kBlock);   // per SIMD
@@ -386,21 +355,24 @@ extern "C" int rt_create(const RtConfig* cfg, RtCtx** out)
     ctx->gridMax = (ctx->nPix * std::max(1, c.max_bounces) + kBlock - 1) / kBlock; // connect may cover max_bounces*nPix shadow rays
     ctx->gridMax = std::max(ctx->gridMax, 4096);                                    // and the persistent grid (<= 256 CUs x 8 blocks)
     ctx->var = DevVariant{ c.shading, c.sampling, c.accel, c.russian_roulette ? 1 : 0, c.filter_fireflies ? 1 : 0, c.max_bounces, 1 };
-    if (const char* t = getenv("RT355_SHADE_TABLES")) ctx->var.shadeTables = atoi(t) != 0;   // 0: k_shade reads lights and materials from global memory (A/B runs)
+    const ShadeKnobs knobs = read_shade_knobs();
+    if (knobs.tablesSet) ctx->var.shadeTables = knobs.tables;   // 0: k_shade reads lights and materials from global memory (A/B runs)
     {   // k_shade: as many workgroups as the CUs hold at once.  Its ordered scan does not depend on that (tiles go by ticket to
         // running workgroups), so the size only matters for speed.  The occupancy query knows the VGPR, LDS and wave-slot limits
         // but not the SGPR file: 256-thread workgroups are admitted up to min(query, 8, 800 / (ceil16(sgprs) + 16)) per CU
         // (MI355X_MICROARCH.md, residency) = 6 for any kernel (<= 112 SGPRs), 7 up to 96 SGPRs.  k_shade: 2 workgroups of 512 threads (registers; 49.8 KB of LDS each).
         hipDeviceProp_t prop; int perCU = 0;
         HIPCHK(hipGetDeviceProperties(&prop, c.device));
+        // (what this file needs of the device, asked once: a reconfiguration reads it from here)
+        ctx->cuCount = prop.multiProcessorCount; ctx->ldsPerBlock = prop.sharedMemPerBlock; ctx->ldsPerCU = prop.maxSharedMemoryPerMultiProcessor;
         ctx->shadeTile = c.shade_blocks_per_cu > 0 ? 256 : kTile;
-        if (const char* t = getenv("RT355_SHADE_TILE")) { const int v = atoi(t); if (v == 256 || v == 512) ctx->shadeTile = v; }
+        if (knobs.tile) ctx->shadeTile = knobs.tile;
         choose_builtin_kernels(ctx);
         HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, ctx->kShade, ctx->shadeTile, 0));
         perCU = std::min(perCU, kAdmitAnySgpr);
-        ctx->shadeGrid = prop.multiProcessorCount * std::max(1, perCU);
-        if (c.shade_blocks_per_cu > 0 && c.shade_blocks_per_cu <= 16) ctx->shadeGrid = prop.multiProcessorCount * c.shade_blocks_per_cu;
-        if (const char* g = getenv("RT355_SHADE_PER_CU")) { int v = atoi(g); if (v > 0 && v <= 16) ctx->shadeGrid = prop.multiProcessorCount * v; }   // tuning / over-subscription tests
+        ctx->shadeGrid = ctx->cuCount * std::max(1, perCU);
+        if (c.shade_blocks_per_cu > 0 && c.shade_blocks_per_cu <= 16) ctx->shadeGrid = ctx->cuCount * c.shade_blocks_per_cu;
+        if (knobs.perCU) ctx->shadeGrid = ctx->cuCount * knobs.perCU;   // tuning / over-subscription tests
     }
     hipError_t e = hipStreamCreateWithFlags(&ctx->home, hipStreamNonBlocking);
     if (e != hipSuccess) return fail(RT_E_DEVICE, "hipStreamCreate failed: %s", hipGetErrorString(e));
@@ -469,162 +441,96 @@ extern "C" int rt_destroy(RtCtx* ctx)
 }
 
 // ---- the scene: a context holds a device copy (scene.hip) and renders from what it took over of it ------------------------------
-// What a context derives from its configuration once it has a scene: which traversal kernels run, with which launch parameters, and how
-// their persistent grids are sized.  Every RT355_* knob of the traversal is read here.
-static int configure_traversal(RtCtx* ctx)
+// What the traversal plan of a context is a function of (trav_common.h): its configuration, the facts of the copy it holds, its device
+static TravFacts traversal_facts(const RtCtx* ctx)
 {
-    // persistent wavefronts need layout 1: over the BVH2 or the BVH4 of a single BLAS (the TLAS root is a leaf), or through a TLAS with
-    // several BLAS (BASELINE config 5) - TLAS entries ride on the BLAS stack column, so the TLAS must be shallow (<= 8 levels: <= 256
-    // instances in a balanced tree) and the pair-table ids must leave the three tag bits free; extend_variant 4 keeps the one-ray-per-lane
-    // nested loops for multi-BLAS scenes (A/B runs)
-    ctx->trav = TRAV_NESTED;
-    if (ctx->layout == 1 && ctx->cfg.extend_variant != 2) {
-        if (ctx->singleBlas) ctx->trav = ctx->cfg.accel == RT_ACCEL_BVH2 ? TRAV_BVH2 : (ctx->cfg.accel == RT_ACCEL_BVH4 ? TRAV_BVH4 : TRAV_NESTED);
-        else if (ctx->cfg.accel == RT_ACCEL_BVH2 && ctx->cfg.extend_variant != 4 && ctx->tlasDepth <= 8 && ctx->nInterior < (1 << 29)) ctx->trav = TRAV_TLAS;
-    }
-    // extend_variant 6 (opt-in): a multi-BLAS BVH4 scene through k_trace_persist4_tlas, under the TLAS kernel's conditions - quad ids ride on
-    // the tagged column, so the copy must hold fewer than 2^29 quad records; everything else under variant 6 is variant 0
-    const bool bvh4Tlas = ctx->layout == 1 && ctx->cfg.extend_variant == 6 && ctx->cfg.accel == RT_ACCEL_BVH4 && !ctx->singleBlas && ctx->tlasDepth <= 8 &&
-                          ctx->scene && ctx->scene->nQuads < (1 << 29);
-    if (bvh4Tlas) ctx->trav = TRAV_BVH4_TLAS;
-    // deep trees (an SBVH at alpha = 0: config 5's second BLAS has 63 levels): a full LDS column per lane would leave two workgroups per
-    // CU, so the column is capped and its deep end spills to global memory (rt355_kernels.h, stk_push / stk_pop)
-    ctx->spillCap = kSpillCap;
-    bool forceSpill = false;
-    if (const char* t = getenv("RT355_SPILL_CAP")) { const int v = atoi(t); if (v >= 6 && v <= 64) { ctx->spillCap = v; forceSpill = true; } }
-    // (columns of up to 22 entries stay whole in LDS, backup beside them: 5-6 workgroups per CU without the spill branches beat 7 with them,
-    // 1,923 against 1,849 and 1,327 against 1,310 M samples/s on two-BLAS scenes of 16 and 22 entries - tools/middepth_tlas.py)
-    const bool noSpill = getenv("RT355_NO_SPILL") && atoi(getenv("RT355_NO_SPILL"));
-    if (ctx->trav == TRAV_TLAS && (tlas_stack_entries(ctx) > kFitSeven || forceSpill) && tlas_stack_entries(ctx) > ctx->spillCap && !noSpill)
-        ctx->trav = TRAV_TLAS_SPILL;
-    if (ctx->trav == TRAV_TLAS && tlas_stack_entries(ctx) > RT_BVH4_STACK + 9) ctx->trav = TRAV_NESTED;
-    if (ctx->trav == TRAV_BVH4_TLAS) {
-        // the BVH2 rule with the BVH2 numbers (kFitSeven was measured on pair records, not on quad records).  A push-all BVH4 needs many
-        // more entries than a BVH2 of its depth: a column that, with its backup words, exceeds the LDS a workgroup may ask for takes the
-        // spill instantiation too, and the nested loops where RT355_NO_SPILL forbids that - no launch the runtime would reject
-        hipDeviceProp_t prop;
-        HIPCHK(hipGetDeviceProperties(&prop, ctx->cfg.device));
-        const bool fits = tlas_column_bytes(tlas_stack_entries(ctx)) <= prop.sharedMemPerBlock;
-        const bool canSpill = !noSpill && tlas_stack_entries(ctx) > ctx->spillCap && tlas_column_bytes(ctx->spillCap) <= prop.sharedMemPerBlock;
-        if ((tlas_stack_entries(ctx) > kFitSeven || forceSpill || !fits) && canSpill) ctx->trav = TRAV_BVH4_TLAS_SPILL;
-        else if (!fits) ctx->trav = TRAV_NESTED;
-    }
-    // bounce 0 (RT355_COHERENT=2: every bounce of k_trace_persist_tlas, lab; 0: off for A/B runs): wave-uniform node records come through
-    // the scalar cache (traverse_bvh2_packed_coherent, k_trace_persist_tlas<COH>)
-    ctx->coherent = getenv("RT355_COHERENT") ? atoi(getenv("RT355_COHERENT")) : 1;
-
-    // extend (BVH2), connect, extend (BVH4): measured optima (tools/tune_extend.sh, tune_connect.sh, tune_persist.sh)
-    ctx->tune = PersistTune{ 112, 24, 6, 8, 0 }; ctx->tuneConnect = PersistTune{ 128, 32, 6, 16, 0 }; ctx->tune4 = PersistTune{ 64, 20, 6, 8, 0 };
-    if (ctx->cfg.persist_blocks_per_cu > 0) {
-        ctx->tune.leafK = 16;   // contexts sharing the GPU: hold triangle events back until 16 lanes wait on a leaf (+1 % with three lanes, -0.6 % alone)
-    } else {
-        // a context with the GPU to itself: chunks after the first are dealt round-robin too (no atomic, no round trip per dequeue):
-        // 716 -> 725 M samples/s; with three contexts sharing the GPU the dynamic queue is 0.9 % better (profiles/r02_fixed_chunks.txt)
-        ctx->tune.fixedChunks = ctx->tuneConnect.fixedChunks = ctx->tune4.fixedChunks = 1;
-    }
-    int tuneBlocks = 0;
-    if (const char* t = getenv("RT355_TUNE")) { // "chunk,refill,inner,leafK[,blocksPerCU]" (tuning aid)
-        int a = 0, b = 0, c = 0, l = 0, d = 0;
-        int k = sscanf(t, "%d,%d,%d,%d,%d", &a, &b, &c, &l, &d);
-        if (k >= 4 && a > 0 && b > 0 && b <= 64 && c > 0 && l > 0 && l <= 64) ctx->tune = ctx->tuneConnect = ctx->tune4 = PersistTune{ a, b, c, l, 0 };
-        if (k == 5 && d > 0) tuneBlocks = d;
-    }
-    if (const char* t = getenv("RT355_FIXED_CHUNKS")) { int a = 0, b = 0; if (sscanf(t, "%d,%d", &a, &b) == 2) { ctx->tune.fixedChunks = ctx->tune4.fixedChunks = a; ctx->tuneConnect.fixedChunks = b; } }   // extend, connect (tuning aid)
-    if (const char* t = getenv("RT355_TUNE_CONNECT")) { // same fields, connect launches only
-        int a = 0, b = 0, c = 0, l = 0;
-        if (sscanf(t, "%d,%d,%d,%d", &a, &b, &c, &l) == 4 && a > 0 && b > 0 && b <= 64 && c > 0 && l > 0 && l <= 64) ctx->tuneConnect = PersistTune{ a, b, c, l, 0 };
-    }
-    // RT355_TOP_LEVELS="e[,c]" (0..6; one number: both): levels of the BLAS that the event loops of k_trace_persist descend from a table in
-    // LDS when a lane takes a new ray (rt355_kernels.h, top_descent), extend and connect.  0: the instantiation without the table.
-    // Without the knob: the deepest table up to kTopLevels* that leaves the stage's persistent grid as it is (below)
-    ctx->tune.topLevels = ctx->tuneConnect.topLevels = 0;
-    bool topAuto = false;
-    if (ctx->trav == TRAV_BVH2) {
-        ctx->tune.topLevels = kTopLevelsExtend; ctx->tuneConnect.topLevels = kTopLevelsConnect;
-        topAuto = true;
-        if (const char* t = getenv("RT355_TOP_LEVELS")) {
-            int a = 0, b = 0;
-            const int k = sscanf(t, "%d,%d", &a, &b);
-            if (k == 1) b = a;
-            if (k >= 1 && a >= 0 && a <= kTopMaxLevels && b >= 0 && b <= kTopMaxLevels) { ctx->tune.topLevels = a; ctx->tuneConnect.topLevels = b; topAuto = false; }
+    TravFacts f;
+    f.accel = ctx->cfg.accel; f.extend_variant = ctx->cfg.extend_variant; f.persist_blocks_per_cu = ctx->cfg.persist_blocks_per_cu;
+    f.layout = ctx->layout; f.singleBlas = ctx->singleBlas; f.tlasDepth = ctx->tlasDepth; f.nInterior = ctx->nInterior;
+    f.nQuads = ctx->scene->nQuads; f.stackEntries = ctx->stackEntries;
+    f.sharedMemPerBlock = (int)ctx->ldsPerBlock; f.xcdFirst = ctx->xcdFirst;
+    return f;
+}
+static void adopt_plan(RtCtx* ctx, const TravPlan& p)
+{
+    ctx->trav = p.trav; ctx->spillCap = p.spillCap; ctx->coherent = p.coherent;
+    ctx->tune = p.tune; ctx->tuneConnect = p.tuneConnect; ctx->tune4 = p.tune4;
+    ctx->tuneBlocks = p.tuneBlocks; ctx->connectBlocks = p.connectBlocks;
+}
+// The top tables against the device.  One that would not fit behind the stack columns of a very deep tree is left out: no launch the
+// runtime would reject.  Then, where no knob named the depth (topAuto):
+// The table's LDS can cost a resident workgroup, and on the one scene this was measured on (the bench scene, EXPERIMENTS.md (59):
+// alone, 22 KB of stack columns x 7 workgroups leave room for three levels) that costs more than the deeper levels give, while
+// contexts that share the GPU run fewer workgroups per CU and lose none with six.  So without the knob each stage gets the
+// deepest table with which it keeps the workgroups per CU it has without one.
+// The lanes of a group (persist_blocks_per_cu > 0) do not have the CU to themselves: their few workgroups sit there with those of
+// the other lanes and, about half the time, with a k_shade workgroup.  What the table must not cost them is a place beside that
+// workgroup (beside_shade; EXPERIMENTS.md (60)): the deepest table with which as many fit there as with none.
+static int fit_top_tables(RtCtx* ctx, bool topAuto)
+{
+    for (PersistTune* t : { &ctx->tune, &ctx->tuneConnect }) if (stack_bytes(ctx->stackEntries) + top_bytes(t->topLevels) > ctx->ldsPerBlock) t->topLevels = 0;
+    if (topAuto) for (int stage : { ST_EXTEND, ST_CONNECT }) {
+        PersistTune& t = stage == ST_CONNECT ? ctx->tuneConnect : ctx->tune;
+        int q = 0, lv = t.topLevels, beside = 0, shadeLds = 0;
+        const bool shared = ctx->cfg.persist_blocks_per_cu > 0;
+        if (const int rc = persist_query(ctx, stage, 0, &q)) return rc;
+        const int base = persist_blocks(ctx, stage, q);
+        if (shared) { if (const int rc = beside_shade(ctx, stage, 0, &beside, &shadeLds)) return rc; }
+        for (; lv > 0; lv--) {
+            if (const int rc = persist_query(ctx, stage, lv, &q)) return rc;
+            if (persist_blocks(ctx, stage, q) != base) continue;
+            if (!shared) break;
+            int fit = 0;
+            if (const int rc = beside_shade(ctx, stage, lv, &fit, &shadeLds)) return rc;
+            if (fit >= beside) break;
         }
-    }
-    if (tlas_trav(ctx)) {
-        // Multi-BLAS scenes so far are open scenes whose rays take a dozen events (config 5: 1 TLAS visit, 1.5 instance entries, 7.7 box
-        // pairs, 1.9 triangles per ray): extend runs the kernel's one-ray-per-lane branch over every queue (measured per bounce at 4K:
-        // 522 / 446 / 198 us against 654 / 562 / 194 through the event loop and 730 / 643 / 237 through the nested loops at two
-        // workgroups per CU), connect - unoccluded shadow rays cross the whole scene - the event loop (646 against 690 / 1,418 us).
-        // RT355_TLAS_FLAT="e,c" overrides (A/B runs).  profiles/r03_config5_per_bounce.txt
-        // (k_trace_persist4_tlas takes its extend tune from tune4; the flat default was measured on BVH2 instances only)
-        ctx->tune.flat = ctx->tune4.flat = 1; ctx->tuneConnect.flat = 0;
-        if (const char* t = getenv("RT355_TLAS_FLAT")) { int a = 0, b = 0; if (sscanf(t, "%d,%d", &a, &b) == 2) { ctx->tune.flat = ctx->tune4.flat = a; ctx->tuneConnect.flat = b; } }
-    }
-    // sparse queues (the one-ray-per-lane branches) stay on as few XCDs as hold them at 1,024 rays each, so that their rays share an L2
-    // (EXPERIMENTS.md (54): 16,384 before the thinning below made spreading the better default); contexts start on different XCDs
-    {
-        static std::atomic<int> serial{ 0 };
-        if (ctx->xcdFirst < 0) ctx->xcdFirst = serial.fetch_add(1) & 7;
-        int rays = 1024;
-        if (const char* t = getenv("RT355_XCD_RAYS")) rays = std::max(0, atoi(t));
-        ctx->tune.xcdRays = ctx->tuneConnect.xcdRays = ctx->tune4.xcdRays = rays;
-        ctx->tune.xcdFirst = ctx->tuneConnect.xcdFirst = ctx->tune4.xcdFirst = ctx->xcdFirst;
-        // ... and on few lanes of every participating wave when they hold at most 16 rays per wave (sparse_map; RT355_THIN=0: off)
-        int thin = 16;
-        if (const char* t = getenv("RT355_THIN")) thin = std::min(64, std::max(0, atoi(t)));
-        ctx->tune.thin = ctx->tuneConnect.thin = ctx->tune4.thin = thin;
-    }
-
-    if (persistent(ctx)) {
-        int perCU = 0; hipDeviceProp_t prop;
-        HIPCHK(hipGetDeviceProperties(&prop, ctx->cfg.device));
-        // (a top table that would not fit behind the stack columns of a very deep tree is left out: no launch the runtime would reject)
-        for (PersistTune* t : { &ctx->tune, &ctx->tuneConnect }) if (stack_bytes(ctx) + top_bytes(t->topLevels) > prop.sharedMemPerBlock) t->topLevels = 0;
-        // The table's LDS can cost a resident workgroup, and on the one scene this was measured on (the bench scene, EXPERIMENTS.md (59):
-        // alone, 22 KB of stack columns x 7 workgroups leave room for three levels) that costs more than the deeper levels give, while
-        // contexts that share the GPU run fewer workgroups per CU and lose none with six.  So without the knob each stage gets the
-        // deepest table with which it keeps the workgroups per CU it has without one.
-        // The lanes of a group (persist_blocks_per_cu > 0) do not have the CU to themselves: their few workgroups sit there with those of
-        // the other lanes and, about half the time, with a k_shade workgroup.  What the table must not cost them is a place beside that
-        // workgroup (beside_shade; EXPERIMENTS.md (60)): the deepest table with which as many fit there as with none.
-        if (topAuto) for (int stage : { ST_EXTEND, ST_CONNECT }) {
-            PersistTune& t = stage == ST_CONNECT ? ctx->tuneConnect : ctx->tune;
-            int q = 0, lv = t.topLevels, beside = 0, shadeLds = 0;
-            const bool shared = ctx->cfg.persist_blocks_per_cu > 0;
-            if (const int rc = persist_query(ctx, stage, 0, &q)) return rc;
-            const int base = persist_blocks(ctx, stage, q, tuneBlocks);
-            if (shared) { if (const int rc = beside_shade(ctx, stage, 0, &beside, &shadeLds)) return rc; }
-            for (; lv > 0; lv--) {
-                if (const int rc = persist_query(ctx, stage, lv, &q)) return rc;
-                if (persist_blocks(ctx, stage, q, tuneBlocks) != base) continue;
-                if (!shared) break;
-                int fit = 0;
-                if (const int rc = beside_shade(ctx, stage, lv, &fit, &shadeLds)) return rc;
-                if (fit >= beside) break;
-            }
-            t.topLevels = lv;
-        }
-        if (const int rc = persist_query(ctx, ST_EXTEND, -1, &perCU)) return rc;   // what extend runs on the persistent grid
-        // (k_trace_persist4_tlas: its any-hit instantiations need more registers than its closest-hit ones and admit a workgroup fewer, so
-        // connect's grid goes by connect's own kernel; so does k_trace_persist's with a top table for connect: its own LDS size)
-        int perCUc = perCU;
-        if (bvh4_tlas_trav(ctx) || ctx->tuneConnect.topLevels > 0) { if (const int rc = persist_query(ctx, ST_CONNECT, -1, &perCUc)) return rc; }
-        ctx->persistGrid = std::min(ctx->gridMax, persist_blocks(ctx, ST_EXTEND, perCU, tuneBlocks) * prop.multiProcessorCount);
-        ctx->persistGridConnect = std::min(ctx->gridMax, persist_blocks(ctx, ST_CONNECT, perCUc, tuneBlocks) * prop.multiProcessorCount);
-    } else ctx->persistGrid = ctx->persistGridConnect = 0;   // (a resize took the persistent kernels away: rt_kernel_info reports what a fresh context does)
-    ctx->q.spill = nullptr; ctx->q.spillStride = 0; ctx->q.stackCap = 0;
-    ctx->q.tlasLdsEntries = tlas_trav(ctx) ? (uint32_t)tlas_lds_entries(ctx) : 0u;
-    if (spill_trav(ctx)) {   // every SPILL launch runs on a persistent grid (bounce 0 too), so the global columns are bounded by the grids
-        const size_t stride = (size_t)std::max(ctx->persistGrid, ctx->persistGridConnect) * kBlock;
-        const size_t words = stride * (size_t)(tlas_stack_entries(ctx) - ctx->spillCap);
-        if (words > ctx->spillWords) {
-            if (ctx->dSpill) (void)hipFree(ctx->dSpill);
-            ctx->dSpill = nullptr; ctx->spillWords = 0;
-            if (hipMalloc((void**)&ctx->dSpill, words * sizeof(uint32_t)) != hipSuccess) return fail(RT_E_NOMEM, "hipMalloc of the spill stacks (%zu bytes) failed", words * sizeof(uint32_t));
-            ctx->spillWords = words;
-        }
-        ctx->q.spill = ctx->dSpill; ctx->q.spillStride = (uint32_t)stride; ctx->q.stackCap = (uint32_t)ctx->spillCap;
+        t.topLevels = lv;
     }
     return RT_OK;
+}
+static int size_persistent_grids(RtCtx* ctx)
+{
+    int perCU = 0;
+    if (const int rc = persist_query(ctx, ST_EXTEND, -1, &perCU)) return rc;   // what extend runs on the persistent grid
+    // (k_trace_persist4_tlas: its any-hit instantiations need more registers than its closest-hit ones and admit a workgroup fewer, so
+    // connect's grid goes by connect's own kernel; so does k_trace_persist's with a top table for connect: its own LDS size)
+    int perCUc = perCU;
+    if (bvh4_tlas_trav(ctx->trav) || ctx->tuneConnect.topLevels > 0) { if (const int rc = persist_query(ctx, ST_CONNECT, -1, &perCUc)) return rc; }
+    ctx->persistGrid = std::min(ctx->gridMax, persist_blocks(ctx, ST_EXTEND, perCU) * ctx->cuCount);
+    ctx->persistGridConnect = std::min(ctx->gridMax, persist_blocks(ctx, ST_CONNECT, perCUc) * ctx->cuCount);
+    return RT_OK;
+}
+// The global columns of the SPILL kinds, grown to what the grids need, and what the kernels are told of the columns
+static int bind_spill_columns(RtCtx* ctx)
+{
+    ctx->q.spill = nullptr; ctx->q.spillStride = 0; ctx->q.stackCap = 0;
+    ctx->q.tlasLdsEntries = tlas_trav(ctx->trav) ? (uint32_t)tlas_lds_entries(ctx) : 0u;
+    if (!spill_trav(ctx->trav)) return RT_OK;
+    // every SPILL launch runs on a persistent grid (bounce 0 too), so the global columns are bounded by the grids
+    const size_t stride = (size_t)std::max(ctx->persistGrid, ctx->persistGridConnect) * kBlock;
+    const size_t words = stride * (size_t)(tlas_stack_entries(ctx->stackEntries, ctx->tlasDepth) - ctx->spillCap);
+    if (words > ctx->spillWords) {
+        if (ctx->dSpill) (void)hipFree(ctx->dSpill);
+        ctx->dSpill = nullptr; ctx->spillWords = 0;
+        if (hipMalloc((void**)&ctx->dSpill, words * sizeof(uint32_t)) != hipSuccess) return fail(RT_E_NOMEM, "hipMalloc of the spill stacks (%zu bytes) failed", words * sizeof(uint32_t));
+        ctx->spillWords = words;
+    }
+    ctx->q.spill = ctx->dSpill; ctx->q.spillStride = (uint32_t)stride; ctx->q.stackCap = (uint32_t)ctx->spillCap;
+    return RT_OK;
+}
+// What a context derives from its configuration once it has a scene: which traversal kernels run, with which launch parameters
+// (plan_traversal, trav_common.h: the rules, and every RT355_* knob of the traversal), and how their persistent grids are sized.
+static int configure_traversal(RtCtx* ctx)
+{
+    static std::atomic<int> serial{ 0 };   // contexts start their sparse queues on different XCDs
+    if (ctx->xcdFirst < 0) ctx->xcdFirst = serial.fetch_add(1) & 7;
+    const TravPlan plan = plan_traversal(traversal_facts(ctx), read_trav_knobs());
+    adopt_plan(ctx, plan);
+    if (persistent(ctx->trav)) {
+        if (const int rc = fit_top_tables(ctx, plan.topAuto)) return rc;
+        if (const int rc = size_persistent_grids(ctx)) return rc;
+    } else ctx->persistGrid = ctx->persistGridConnect = 0;   // (a resize took the persistent kernels away: rt_kernel_info reports what a fresh context does)
+    return bind_spill_columns(ctx);
 }
 
 // A context takes over the facts of the copy it holds - the arrays, the layout, the stack sizes - and derives its traversal
@@ -663,6 +569,30 @@ static int sync_scene_config(RtCtx* ctx)
 {
     if (!ctx->scene || ctx->sceneGen == ctx->scene->generation) return RT_OK;
     return adopt_scene(ctx);
+}
+// The plan's rules from outside (tests): the facts a context plans from, and the plan of any facts under the knobs of the environment
+static_assert(sizeof(PersistTune) == sizeof(int32_t) * RT_TUNE_FIELDS, "RtTraversalPlan mirrors PersistTune field by field");
+extern "C" int rt_debug_traversal_facts(RtCtx* ctx, RtTraversalFacts* out)
+{
+    if (!ctx || !out) return fail(RT_E_INVALID, "rt_debug_traversal_facts: null argument");
+    if (!ctx->sceneLoaded) return fail(RT_E_INVALID, "rt_debug_traversal_facts: no scene uploaded");
+    if (const int rc = sync_scene_config(ctx)) return rc;
+    const TravFacts f = traversal_facts(ctx);
+    *out = RtTraversalFacts{ f.accel, f.extend_variant, f.persist_blocks_per_cu, f.layout, f.singleBlas, f.tlasDepth, f.nInterior, f.nQuads, f.stackEntries,
+                             f.sharedMemPerBlock, f.xcdFirst };
+    return RT_OK;
+}
+extern "C" int rt_debug_traversal_plan(const RtTraversalFacts* facts, RtTraversalPlan* out)
+{
+    if (!facts || !out) return fail(RT_E_INVALID, "rt_debug_traversal_plan: null argument");
+    TravFacts f;
+    f.accel = facts->accel; f.extend_variant = facts->extend_variant; f.persist_blocks_per_cu = facts->persist_blocks_per_cu;
+    f.layout = facts->layout; f.singleBlas = facts->singleBlas; f.tlasDepth = facts->tlasDepth; f.nInterior = facts->nInterior;
+    f.nQuads = facts->nQuads; f.stackEntries = facts->stackEntries; f.sharedMemPerBlock = facts->sharedMemPerBlock; f.xcdFirst = facts->xcdFirst;
+    const TravPlan p = plan_traversal(f, read_trav_knobs());
+    *out = RtTraversalPlan{ p.trav, p.spillCap, p.coherent, p.topAuto ? 1 : 0, p.tuneBlocks, p.connectBlocks, {}, {}, {} };
+    memcpy(out->tune, &p.tune, sizeof p.tune); memcpy(out->tuneConnect, &p.tuneConnect, sizeof p.tuneConnect); memcpy(out->tune4, &p.tune4, sizeof p.tune4);
+    return RT_OK;
 }
 // The last step of every way to a scene: the context holds `bag` and is usable again once it has taken the copy over
 static int bind_scene(RtCtx* ctx, const std::shared_ptr<SceneBag>& bag)
@@ -937,7 +867,7 @@ extern "C" int rt_stage_extend(RtCtx* ctx, int32_t bounce, int32_t renderBVH)
     int rc = need_scene(ctx, "rt_stage_extend"); if (rc) return rc;
     ctx->queued = true;
     if (bounce < 0 || bounce > ctx->cfg.max_bounces) return fail(RT_E_INVALID, "rt_stage_extend: bounce %d outside [0, %d]", bounce, ctx->cfg.max_bounces);
-    if (persistent(ctx)) { // a queue head is good for one launch per frame; re-arm it if this stage is run again
+    if (persistent(ctx->trav)) { // a queue head is good for one launch per frame; re-arm it if this stage is run again
         if (ctx->cursorUsed[bounce]) HIPCHK(hipMemsetAsync(ctx->q.cursor + bounce, 0, sizeof(int32_t), ctx->stream));
         ctx->cursorUsed[bounce] = true;
     }
@@ -975,7 +905,7 @@ extern "C" int rt_stage_connect(RtCtx* ctx, int32_t b0, int32_t b1)
     int rc = need_scene(ctx, "rt_stage_connect"); if (rc) return rc;
     ctx->queued = true;
     if (b0 < 0 || b1 < b0 || b1 >= ctx->cfg.max_bounces) return fail(RT_E_INVALID, "rt_stage_connect: bounce range [%d,%d] outside [0, %d)", b0, b1, ctx->cfg.max_bounces);
-    if (persistent(ctx)) {
+    if (persistent(ctx->trav)) {
         const int ci = (RT_MAX_BOUNCES + 2) + b0;
         if (ctx->cursorUsed[ci]) HIPCHK(hipMemsetAsync(ctx->q.cursor + ci, 0, sizeof(int32_t), ctx->stream));
         ctx->cursorUsed[ci] = true;
@@ -1171,7 +1101,7 @@ extern "C" int rt_focus(RtCtx* ctx, int32_t x, int32_t y, const RtCamera* cam, f
     int rc = need_scene(ctx, "rt_focus"); if (rc) return rc;
     if (!cam || !t) return fail(RT_E_INVALID, "rt_focus: null argument");
     HIPCHK(hipSetDevice(ctx->cfg.device));
-    hipLaunchKernelGGL(ctx->kFocus, dim3(1), dim3(kBlock), stack_bytes(ctx), ctx->stream, ctx->sc, *cam, x, y, ctx->cfg.width, ctx->cfg.height, ctx->dFocus);
+    hipLaunchKernelGGL(ctx->kFocus, dim3(1), dim3(kBlock), stack_bytes(ctx->stackEntries), ctx->stream, ctx->sc, *cam, x, y, ctx->cfg.width, ctx->cfg.height, ctx->dFocus);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(t, ctx->dFocus, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));

@@ -14,6 +14,23 @@ class RtError(RuntimeError):
     code = None   # the RT_E_* value, where the raising call records it
 
 
+def traversal_plan(facts):
+    """The traversal a context with these facts (Device.traversal_facts(), or a dict of _lib.TraversalFacts' fields; missing ones are 0)
+    chooses under the RT355_* knobs of the environment (rt_debug_traversal_plan; no GPU): trav (_lib.TRAV_*), spillCap, coherent,
+    topAuto, tuneBlocks, connectBlocks and the three tunes as dicts of _lib.TUNE_FIELDS."""
+    lib = _lib.device_lib()
+    f, p = np.zeros((), dtype=_lib.TraversalFacts), np.zeros((), dtype=_lib.TraversalPlan)
+    for n, v in facts.items():
+        f[n] = v
+    if lib.rt_debug_traversal_plan(f.ctypes.data_as(C.c_void_p), p.ctypes.data_as(C.c_void_p)) != 0:
+        raise RtError(lib.rt_last_error().decode())
+    out = {n: int(p[n]) for n in ("trav", "spillCap", "coherent", "tuneBlocks", "connectBlocks")}
+    out["topAuto"] = bool(p["topAuto"])
+    for n in ("tune", "tuneConnect", "tune4"):
+        out[n] = dict(zip(_lib.TUNE_FIELDS, (int(v) for v in p[n])))
+    return out
+
+
 def _update_args(prims, first, instances):
     p = None if prims is None else np.ascontiguousarray(prims, dtype=_lib.Primitive)
     b = None if instances is None else np.ascontiguousarray(instances, dtype=_lib.BVHInstance)
@@ -314,6 +331,12 @@ class Device:
         e, c = C.c_int32(0), C.c_int32(0)
         self._chk(self._lib.rt_top_levels(self._h, C.byref(e), C.byref(c)))
         return int(e.value), int(c.value)
+
+    def traversal_facts(self):
+        """What this context's traversal is planned from (rt_debug_traversal_facts): a dict for traversal_plan()."""
+        f = np.zeros((), dtype=_lib.TraversalFacts)
+        self._chk(self._lib.rt_debug_traversal_facts(self._h, f.ctypes.data_as(C.c_void_p)))
+        return {n: int(f[n]) for n in f.dtype.names}
 
     def shade_footprint(self):
         """(lds_bytes, traversal_beside): the static LDS of a k_shade workgroup of this context, and how many workgroups of its
