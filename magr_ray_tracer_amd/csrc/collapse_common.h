@@ -120,7 +120,11 @@ LB_HD uint32_t largest_leaf(const RtBVHNode4& q)
     for (int k = 0; k < 4; k++) if (q.first[k] != RT_INVALID && q.count[k] > 0 && (uint32_t)q.count[k] > m) m = (uint32_t)q.count[k];
     return m;
 }
-// The quad record of a live node (layout 1 of a BVH4; rt355_kernels.h reads it): newId maps node ids to live ids.
+// The quad record of a live node (layout 1 of a BVH4, 128 B, derived from the unchanged BVHNode4 array; newId maps node ids to live
+// ids): floats 0..23 = {min.xyz, max.xyz} of child slots 0..3 - so q0..q2 hold slots 0 and 1 and q3..q5 slots 2 and 3 exactly as a
+// pair record holds its two children - q6 = the four entries (refit: kNoChild for an unused slot, else the live id or the leaf entry),
+// q7 = 0.  A visit is 7 sixteen-byte loads from two 64-B lines instead of 10 from three, and triangles come from the leaf-ordered
+// triRecs.  The decoders follow refit_common.h's: given the record's vectors in order, K = the slot.
 LB_HD void quad_record(const RtBVHNode4& q, int32_t nNodes, int32_t nIdx, const uint32_t* newId, RtFloat4 out[8])
 {
     float b[24]; uint32_t e[4];
@@ -128,13 +132,28 @@ LB_HD void quad_record(const RtBVHNode4& q, int32_t nNodes, int32_t nIdx, const 
         const RtFloat4& mn = q.aabbMin[k]; const RtFloat4& mx = q.aabbMax[k];
         b[k * 6 + 0] = mn.x; b[k * 6 + 1] = mn.y; b[k * 6 + 2] = mn.z; b[k * 6 + 3] = mx.x; b[k * 6 + 4] = mx.y; b[k * 6 + 5] = mx.z;
         const int slot = rebuild::bvh4_slot(q, k, nNodes, nIdx);
-        if (slot == rebuild::kSlotLeaf) e[k] = refit::kLeafBit | ((uint32_t)q.count[k] << 24) | (uint32_t)q.first[k];
+        if (slot == rebuild::kSlotLeaf) e[k] = refit::leaf_entry((uint32_t)q.first[k], (uint32_t)q.count[k]);
         else if (slot == rebuild::kSlotChild) e[k] = newId[(uint32_t)q.first[k]];
-        else e[k] = 0xffffffffu;   // (unused; validate_scene has refused kSlotBad)
+        else e[k] = refit::kNoChild;   // (unused; validate_scene has refused kSlotBad)
     }
     for (int v = 0; v < 6; v++) out[v] = refit::f4(b[v * 4], b[v * 4 + 1], b[v * 4 + 2], b[v * 4 + 3]);
     out[6] = refit::f4(refit::u2f(e[0]), refit::u2f(e[1]), refit::u2f(e[2]), refit::u2f(e[3]));
     out[7] = refit::f4(0, 0, 0, 0);
+}
+template <int K, class V> LB_DEC V quad_min(const V& q0, const V& q1, const V& q2, const V& q3, const V& q4, const V& q5)
+{
+    static_assert(K >= 0 && K < 4, "a quad record has four child slots");
+    return K == 0 ? refit::pair_min1(q0, q1, q2) : K == 1 ? refit::pair_min2(q0, q1, q2) : K == 2 ? refit::pair_min1(q3, q4, q5) : refit::pair_min2(q3, q4, q5);
+}
+template <int K, class V> LB_DEC V quad_max(const V& q0, const V& q1, const V& q2, const V& q3, const V& q4, const V& q5)
+{
+    static_assert(K >= 0 && K < 4, "a quad record has four child slots");
+    return K == 0 ? refit::pair_max1(q0, q1, q2) : K == 1 ? refit::pair_max2(q0, q1, q2) : K == 2 ? refit::pair_max1(q3, q4, q5) : refit::pair_max2(q3, q4, q5);
+}
+template <int K, class V> LB_DEC uint32_t quad_entry(const V& q6)
+{
+    static_assert(K >= 0 && K < 4, "a quad record has four child slots");
+    return refit::f2u(K == 0 ? q6.x : K == 1 ? q6.y : K == 2 ? q6.z : q6.w);
 }
 
 // ---- argument checks (host only), shared by rt_build_bvh4, rt_upload_scene_bvh2 and rth_build_bvh4_levels ---------------------------

@@ -4,8 +4,8 @@
 //
 //   pair ids     interior nodes are renumbered breadth-first, BLAS by BLAS in the order in which the instances first name their
 //                roots: level by level, parents in frontier order, child `first` before `first + 1`, interior children only.
-//   pair record  both child boxes (refit::pair_boxes) and the children's entries: a leaf is 0x80000000 | count << 24 | first (so a
-//                leaf holds at most kMaxPackedLeaf primitives and primIdx fewer than 2^24 slots), an interior node is its pair id.
+//   pair record  both child boxes (refit::pair_boxes) and the children's entries: a leaf is refit::leaf_entry (so a leaf holds at
+//                most kMaxPackedLeaf primitives and primIdx fewer than kMaxPackedIdx slots), an interior node is its pair id.
 //   stack        a BLAS of height h (edges, the root counts 0) needs h entries; a context keeps clamp(max h + 1, 6, RT_BVH4_STACK).
 #pragma once
 #include <stdint.h>
@@ -22,11 +22,14 @@ constexpr uint32_t kNone = 0xffffffffu;
 constexpr uint32_t kMaxPackedLeaf = 127;          // primitives of a leaf in the packed entry
 constexpr int32_t kMaxPackedIdx = 1 << 24;        // primIdx slots the packed entry addresses
 constexpr int kMinStackEntries = 6;               // flush_counters reuses 36 words of the LDS stack
+static_assert(refit::kLeafCountMask == kMaxPackedLeaf && refit::kLeafFirstMask == (uint32_t)kMaxPackedIdx - 1u &&
+              kMaxPackedIdx == 1 << refit::kLeafCountShift && (refit::kLeafBit >> refit::kLeafCountShift) == kMaxPackedLeaf + 1u,
+              "a leaf entry is the leaf bit, a count of up to kMaxPackedLeaf and a slot below kMaxPackedIdx, with no bit shared or left over");
 
 // the packed entry of node n in layout 1 (newId: its pair id if it is an interior node)
 LB_HD uint32_t child_entry(uint32_t first, uint32_t count, uint32_t newId)
 {
-    return count > 0 ? (refit::kLeafBit | (count << 24) | first) : newId;
+    return count > 0 ? refit::leaf_entry(first, count) : newId;
 }
 LB_HD uint32_t child_entry(const RtBVHNode2& n, uint32_t newId) { return child_entry(n.first, n.count, newId); }
 // the packed entries of both children of interior node `node`; newId maps node ids to pair ids

@@ -26,13 +26,51 @@ namespace refit {
 using lbvh::Box;
 
 constexpr uint32_t kNone = 0xffffffffu;
-constexpr uint32_t kTagTlas = 0x40000000u, kTagInst = 0x60000000u;   // rt355_kernels.h: tagged entries of k_trace_persist_tlas
-constexpr uint32_t kLeafBit = 0x80000000u;                            // the plain encoding of traverse_tlas / layout-1 pairs
 constexpr int kMaxInstances = 256;                                    // TLAS::Build's limit
 
 LB_HD uint32_t f2u(float f) { uint32_t u; __builtin_memcpy(&u, &f, 4); return u; }
 LB_HD float u2f(uint32_t u) { float f; __builtin_memcpy(&f, &u, 4); return f; }
 LB_HD RtFloat4 f4(float x, float y, float z, float w) { RtFloat4 r; r.x = x; r.y = y; r.z = z; r.w = w; return r; }
+// An entry helper or a record decoder is a mask or a lane shuffle: always inlined, like the kernels' own helpers
+#define LB_DEC __attribute__((always_inline)) LB_HD
+
+// ---- entries: the 32-bit words by which a derived record names a child (integers only) -------------------------------------------
+// The one statement of every encoding; the writers below and in rebuild_common.h / collapse_common.h and the traversal kernels
+// (rt355_kernels.h) all go through it, tools/records_main.cpp round-trips it.
+//   BLAS entry   (pair and quad records, the instance record's root, rootEntry[])
+//                  interior   its id in the dense pair (BVH2) or quad (BVH4) table, below 2^29
+//                  leaf       kLeafBit | count << 24 | first    count <= 127 primitives from primIdx / triRecs slot first < 2^24
+//                  unused     kNoChild: an empty slot of a quad record.  No legal entry: as a leaf it would be 127 primitives from slot
+//                             2^24 - 1, and a leaf ends at or below nIdx < 2^24 (rebuild::takes_layout1)
+//   plain TLAS   (tlasPairs, DevScene.tlasRoot: traverse_tlas)
+//                  interior   its TLAS node id            leaf   kLeafBit | instance id
+//                on traverse_tlas' 16-bit stack (tlas_pack16): bit 15 = leaf, the id in bits 14..0
+//   tagged TLAS  (tlasPairsP, DevScene.tlasRootP: the event loops, which keep BLAS and TLAS entries on ONE stack column)
+//                  bits 31..29 = 010 (kTagTlas)  TLAS interior, id in bits 28..0
+//                  bits 31..29 = 011 (kTagInst)  TLAS leaf, instance id in bits 28..0
+//                beside the BLAS entries: 1xx a leaf, 000 an interior node.  kTagInst contains kTagTlas' bit: tagged_tlas answers for
+//                an entry that is neither a leaf nor an instance.
+// What an entry is comes back as the masked word, which the caller compares (plain_leaf(e) != 0, tagged_tag(e) == kTagInst,
+// tagged_tlas(e) != 0): a helper that returns bool changes the traversal kernels' machine code, one that returns the word does not.
+// The event loops write the two tagged tests out, (e & kTagMask) == kTagInst and (e & kTagTlas) != 0, with these constants: inside
+// their && chains even the word-returning helpers change the code (profiles/r20_record_layouts.txt).
+constexpr uint32_t kLeafBit = 0x80000000u, kLeafCountMask = 0x7fu, kLeafFirstMask = 0x00ffffffu, kNoChild = 0xffffffffu;
+constexpr int kLeafCountShift = 24;
+constexpr uint32_t kTagTlas = 0x40000000u, kTagInst = 0x60000000u, kTagMask = 0xe0000000u, kIdMask = 0x1fffffffu;
+LB_DEC uint32_t leaf_entry(uint32_t first, uint32_t count) { return kLeafBit | (count << kLeafCountShift) | first; }
+LB_DEC uint32_t leaf_first(uint32_t e) { return e & kLeafFirstMask; }
+LB_DEC uint32_t leaf_count(uint32_t e) { return (e >> kLeafCountShift) & kLeafCountMask; }
+// the leaf (first, count) without its first primitive (count > 1)
+LB_DEC uint32_t leaf_rest(uint32_t first, uint32_t count) { return kLeafBit | ((count - 1) << kLeafCountShift) | (first + 1); }
+LB_DEC uint32_t tlas_leaf_entry(bool tagged, uint32_t inst) { return (tagged ? kTagInst : kLeafBit) | inst; }
+LB_DEC uint32_t tlas_node_entry(bool tagged, uint32_t node) { return tagged ? (kTagTlas | node) : node; }
+LB_DEC uint32_t plain_leaf(uint32_t e) { return e & kLeafBit; }
+LB_DEC uint32_t plain_inst(uint32_t e) { return e & ~kLeafBit; }
+LB_DEC uint16_t tlas_pack16(uint32_t e) { return (uint16_t)((e >> 16) | (e & 0x7fffu)); }
+LB_DEC uint32_t tlas_unpack16(uint32_t v) { return ((v & 0x8000u) << 16) | (v & 0x7fffu); }
+LB_DEC uint32_t tagged_tag(uint32_t e) { return e & kTagMask; }
+LB_DEC uint32_t tagged_tlas(uint32_t e) { return e & kTagTlas; }
+LB_DEC uint32_t tagged_id(uint32_t e) { return e & kIdMask; }
 
 // ---- node boxes --------------------------------------------------------------------------------------------------------------
 LB_HD Box leaf_init()   // BVH2::UpdateNodeBounds' initial box
@@ -63,16 +101,31 @@ LB_HD Box leaf_box(const RtPrimitive* prims, const uint32_t* primIdx, uint32_t f
 }
 
 // ---- derived records (rt_upload_scene) ----------------------------------------------------------------------------------------
-// layout 1: interior node with children a (first) and b (first + 1): both child boxes in the first three float4 of its pair record
-// (the fourth, the encoded child entries, depends on the topology only)
-LB_HD void pair_boxes(const RtBVHNode2& a, const RtBVHNode2& b, RtFloat4 out[3])
+// Every record is a few 16-byte vectors, and each has its decoders right below its encoder: templates over any vector type V with
+// lanes .x .y .z .w (RtFloat4 here, float4 and the scalar-cache vector in the kernels), given the record's vectors in order.  A
+// decoded box or edge is a V with w = 0.
+//
+// Pair record (layout 1, 64 B: one cache-line-aligned fetch per interior visit) of an interior node with children a (first) and b
+// (first + 1); the node array itself stays as uploaded.  Both child boxes in q0..q2 (pair_boxes: BLAS pairs[], and TLAS tlasPairs[] /
+// tlasPairsP[] from the TLAS node array); q3 = (entry(a), entry(b), 0, 0) depends on the topology only (rebuild::pair_record, tlas_pair)
+//   q0 = (a.min.xyz, a.max.x)   q1 = (a.max.yz, b.min.xy)   q2 = (b.min.z, b.max.xyz)
+template <class N> LB_HD void pair_boxes(const N& a, const N& b, RtFloat4 out[3])
 {
     out[0] = f4(a.aabbMin.x, a.aabbMin.y, a.aabbMin.z, a.aabbMax.x);
     out[1] = f4(a.aabbMax.y, a.aabbMax.z, b.aabbMin.x, b.aabbMin.y);
     out[2] = f4(b.aabbMin.z, b.aabbMax.x, b.aabbMax.y, b.aabbMax.z);
 }
-// triangle record of leaf slot s (primitive `prim` = primIdx[s]): v0 and the edges v1 - v0, v2 - v0 - the first two operations of
-// the reference's triangle test (primitives.cl:49-50), done once with the same IEEE subtraction - the id and the "not plain" flag
+template <class V> LB_DEC V pair_min1(const V& q0, const V&, const V&) { return V{ q0.x, q0.y, q0.z, 0.0f }; }
+template <class V> LB_DEC V pair_max1(const V& q0, const V& q1, const V&) { return V{ q0.w, q1.x, q1.y, 0.0f }; }
+template <class V> LB_DEC V pair_min2(const V&, const V& q1, const V& q2) { return V{ q1.z, q1.w, q2.x, 0.0f }; }
+template <class V> LB_DEC V pair_max2(const V&, const V&, const V& q2) { return V{ q2.y, q2.z, q2.w, 0.0f }; }
+template <class V> LB_DEC uint32_t pair_entry1(const V& q3) { return f2u(q3.x); }
+template <class V> LB_DEC uint32_t pair_entry2(const V& q3) { return f2u(q3.y); }
+// Triangle record (48 B) of leaf slot s (primitive `prim` = primIdx[s]), in leaf order, so that a leaf's triangles are contiguous and
+// the primIdx indirection disappears: v0 and the edges v1 - v0, v2 - v0 - the first two operations of the reference's triangle test
+// (primitives.cl:49-50), done once with the same IEEE subtraction - the id and the "not plain" flag (a sphere, a plane, or a vertex
+// with a non-zero w lane: the reference-layout test)
+//   a = (v0.xyz, e1.x)   b = (e1.yz, e2.xy)   c = (e2.z, prim, not plain, 0)
 LB_HD void tri_rec(const RtPrimitive& p, uint32_t prim, RtFloat4 out[3])
 {
     const RtTriangle& t = p.obj.triangle;
@@ -83,6 +136,11 @@ LB_HD void tri_rec(const RtPrimitive& p, uint32_t prim, RtFloat4 out[3])
     out[1] = f4(e1y, e1z, e2x, e2y);
     out[2] = f4(e2z, u2f(prim), u2f(plain ? 0u : 1u), 0.0f);
 }
+template <class V> LB_DEC V tri_v0(const V& a, const V&, const V&) { return V{ a.x, a.y, a.z, 0.0f }; }
+template <class V> LB_DEC V tri_edge1(const V& a, const V& b, const V&) { return V{ a.w, b.x, b.y, 0.0f }; }
+template <class V> LB_DEC V tri_edge2(const V&, const V& b, const V& c) { return V{ b.z, b.w, c.x, 0.0f }; }
+template <class V> LB_DEC uint32_t tri_prim(const V& c) { return f2u(c.y); }
+template <class V> LB_DEC uint32_t tri_not_plain(const V& c) { return f2u(c.z); }   // != 0 (the word, as for the entries)
 // shading record (k_shade): geometric normal + material id + type
 LB_HD RtFloat4 shade_rec(const RtPrimitive& p)
 {
@@ -99,24 +157,23 @@ LB_HD void light_rec(const RtPrimitive& p, RtFloat4 out[5])
     __builtin_memcpy(out, &p.obj, 64);
     out[4] = f4(u2f((uint32_t)p.objType), p.area, 0.0f, 0.0f);
 }
-// TLAS interior node i (children lr & 0xffff, lr >> 16): both child boxes and the encoded children; tagged: the encoding of
-// k_trace_persist_tlas (tlasPairsP), else the plain one (tlasPairs).  Leaves have an all-zero record.
+// TLAS interior node i (children lr & 0xffff, lr >> 16): a pair record of the TLAS node array - one fetch per interior visit where the
+// reference array costs the node's leftRight word, then the two child nodes, and none per leaf: its instance sits in the parent's
+// record.  tagged: the entries of the event loops (tlasPairsP), else the plain ones (tlasPairs).  Leaves have an all-zero record.
 LB_HD void tlas_pair(const RtTLASNode* t, uint32_t i, bool tagged, RtFloat4 out[4])
 {
     const uint32_t lr = t[i].leftRight;
     if (lr == 0) { for (int k = 0; k < 4; k++) out[k] = f4(0, 0, 0, 0); return; }
-    const RtTLASNode& a = t[lr & 0xffffu]; const RtTLASNode& b = t[lr >> 16];
-    out[0] = f4(a.aabbMin.x, a.aabbMin.y, a.aabbMin.z, a.aabbMax.x);
-    out[1] = f4(a.aabbMax.y, a.aabbMax.z, b.aabbMin.x, b.aabbMin.y);
-    out[2] = f4(b.aabbMin.z, b.aabbMax.x, b.aabbMax.y, b.aabbMax.z);
+    pair_boxes(t[lr & 0xffffu], t[lr >> 16], out);
     uint32_t e[2];
     for (int k = 0; k < 2; k++) {
         const uint32_t n = k == 0 ? (lr & 0xffffu) : (lr >> 16);
-        e[k] = t[n].leftRight == 0 ? ((tagged ? kTagInst : kLeafBit) | t[n].BLASidx) : (tagged ? (kTagTlas | n) : n);
+        e[k] = t[n].leftRight == 0 ? tlas_leaf_entry(tagged, t[n].BLASidx) : tlas_node_entry(tagged, n);
     }
     out[3] = f4(u2f(e[0]), u2f(e[1]), 0.0f, 0.0f);
 }
-// instance record: rows 0..2 of invT, {encoded BLAS root, bvhIdx}
+// Instance record (64 B: one fetch where the reference reads BVHInstance.invT and the root separately): rows 0..2 of invT - row k
+// maps a point p to dot(axis, p) + shift, a direction to dot(axis, d) - then {encoded BLAS root (layout 1; else 0), bvhIdx, 0, 0}
 LB_HD void inst_rec(const RtBVHInstance& inst, uint32_t rootEntry, RtFloat4 out[4])
 {
     const float* T = inst.invT;
@@ -125,6 +182,10 @@ LB_HD void inst_rec(const RtBVHInstance& inst, uint32_t rootEntry, RtFloat4 out[
     out[2] = f4(T[8], T[9], T[10], T[11]);
     out[3] = f4(u2f(rootEntry), u2f(inst.bvhIdx), 0.0f, 0.0f);
 }
+template <class V> LB_DEC V inst_axis(const V& row) { return V{ row.x, row.y, row.z, 0.0f }; }
+template <class V> LB_DEC float inst_shift(const V& row) { return row.w; }
+template <class V> LB_DEC uint32_t inst_root(const V& t3) { return f2u(t3.x); }
+template <class V> LB_DEC uint32_t inst_bvh(const V& t3) { return f2u(t3.y); }
 
 // ---- TLAS::Build ----------------------------------------------------------------------------------------------------------------
 // fminf / fmaxf as TLAS::Build's host build evaluates them (x86-64 glibc: minss / maxss, an equal pair returns the second operand,

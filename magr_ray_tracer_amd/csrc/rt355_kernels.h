@@ -28,8 +28,13 @@
 #include "../../include/rt355_types.h"
 #include "rt355_dev.h"    // the structs and constants shared with the host code
 #include "rt355_math.h"   // the arithmetic: float4 helpers, the two sets of builtins, the texel lookup
+#include "collapse_common.h"   // the derived records' layouts: the encoders upload runs and the decoders the kernels read them with
+                               // (pair, triangle, instance records and every entry: refit_common.h; quad records: collapse_common.h)
 
 namespace rt355dev {
+
+using namespace refit;   // (entries and record decoders)
+using collapse::quad_min; using collapse::quad_max; using collapse::quad_entry;
 
 static constexpr float kEps = RT_EPSILON;
 static constexpr float kFar = RT_REALLYFAR;
@@ -54,14 +59,21 @@ struct TRay {
 };
 struct WorkCtr { uint32_t tlas, inst, node, prim, nodeIss = 0, leafIss = 0, evNode = 0, evPrim = 0; };   // nodeIss / leafIss: wave-level issues of the node path / the triangle path by the event loops (x 64 lanes = the slots those events had); evNode / evPrim: the events they carried
 
-RT_FORCEINLINE float slab(const TRay& r, float4 bmin, float4 bmax) // bvh.cl:3-12
+// The slab test, bvh.cl:3-12: the interval [tmin, tmax] in which the ray is inside the box (xyz of any vector type: a float4 of the
+// node array, or what a record decoder returns).  Three predicates read it: slab, slab_any, slab_both.
+template <class B> RT_FORCEINLINE void slab_interval(const TRay& r, B bmin, B bmax, float& tmin, float& tmax)
 {
     float tx1 = (bmin.x - r.ox) * r.rx, tx2 = (bmax.x - r.ox) * r.rx;
-    float tmin = fminf(tx1, tx2), tmax = fmaxf(tx1, tx2);
+    tmin = fminf(tx1, tx2); tmax = fmaxf(tx1, tx2);
     float ty1 = (bmin.y - r.oy) * r.ry, ty2 = (bmax.y - r.oy) * r.ry;
     tmin = fmaxf(tmin, fminf(ty1, ty2)); tmax = fminf(tmax, fmaxf(ty1, ty2));
     float tz1 = (bmin.z - r.oz) * r.rz, tz2 = (bmax.z - r.oz) * r.rz;
     tmin = fmaxf(tmin, fminf(tz1, tz2)); tmax = fminf(tmax, fmaxf(tz1, tz2));
+}
+template <class B> RT_FORCEINLINE float slab(const TRay& r, B bmin, B bmax)   // the reference's value: the entry distance, or 1e30
+{
+    float tmin, tmax;
+    slab_interval(r, bmin, bmax, tmin, tmax);
     return (tmax >= tmin && tmin < r.t && tmax > 0) ? tmin : kFar;
 }
 
@@ -77,18 +89,24 @@ RT_FORCEINLINE float slab(const TRay& r, float4 bmin, float4 bmax) // bvh.cl:3-1
 // tests/test_edge_rays_cpu.py pins the rays.  The order chosen: the child the ray leaves LATER first - nearer the light, where most occluders of this kind of scene sit - finds
 // an occluder after 27.6 instead of 34.9 node visits per shadow ray on the bench scene (tools/lab/anyhit_lab.c; 85 % of its
 // shadow rays are occluded), with the accumulator unchanged bit for bit.
-RT_FORCEINLINE bool slab_any(const TRay& r, float4 bmin, float4 bmax, float& exitT)
+template <class B> RT_FORCEINLINE bool slab_any(const TRay& r, B bmin, B bmax, float& exitT)
 {
-    float tx1 = (bmin.x - r.ox) * r.rx, tx2 = (bmax.x - r.ox) * r.rx;
-    float tmin = fminf(tx1, tx2), tmax = fmaxf(tx1, tx2);
-    float ty1 = (bmin.y - r.oy) * r.ry, ty2 = (bmax.y - r.oy) * r.ry;
-    tmin = fmaxf(tmin, fminf(ty1, ty2)); tmax = fminf(tmax, fmaxf(ty1, ty2));
-    float tz1 = (bmin.z - r.oz) * r.rz, tz2 = (bmax.z - r.oz) * r.rz;
-    tmin = fmaxf(tmin, fminf(tz1, tz2)); tmax = fminf(tmax, fmaxf(tz1, tz2));
+    float tmin, tmax;
+    slab_interval(r, bmin, bmax, tmin, tmax);
     exitT = tmax;
     return tmax >= tmin && tmin < r.t && tmax > 0;
 }
+// ... and with both ends, for the event loops over a TLAS: their connect orders TLAS children by entry, BLAS children by exit
+template <class B> RT_FORCEINLINE bool slab_both(const TRay& r, B bmin, B bmax, float& tminOut, float& tmaxOut)
+{
+    float tmin, tmax;
+    slab_interval(r, bmin, bmax, tmin, tmax);
+    tminOut = tmin; tmaxOut = tmax;
+    return tmax >= tmin && tmin < r.t && tmax > 0;
+}
 
+// (Möller-Trumbore, primitives.cl:47-70, stands twice, here over the Primitive and in test_tri_packed over a triangle record: as one
+// function called from both it compiles to other code, profiles/r20_record_layouts.txt)
 RT_FORCEINLINE void test_prim(const DevScene& sc, int idx, TRay& r) // primitives.cl:11-89
 {
     const RtPrimitive* p = sc.prims + idx;
@@ -186,18 +204,11 @@ RT_FORCEINLINE int traverse_bvh2(const DevScene& sc, TRay& r, uint32_t root, uin
 }
 
 // ---- layout 1: the same BVH2, re-laid-out at upload for one dependent fetch per step ---------------
-// The reference node array is uploaded unchanged; from it rt_upload_scene derives
-//   pairs[i]   (64 B, one cache-line-aligned fetch) for every interior node i:
-//              q0 = (c1.min.xyz, c1.max.x) q1 = (c1.max.yz, c2.min.xy) q2 = (c2.min.z, c2.max.xyz)
-//              q3 = (entry(c1), entry(c2), -, -) with c1 = nodes[i].first, c2 = c1 + 1
-//   entry(n)   = n                                   interior node id
-//              = 0x80000000 | count << 24 | first    leaf (count <= 127, first < 2^24)
-//   triRecs[s] (48 B) for every primIdx slot s: v0, the edges v1 - v0 and v2 - v0 (xyz) and the primitive id, in leaf
-//              order, so a leaf's triangles are contiguous and the primIdx indirection disappears.
+// The reference node array is uploaded unchanged; from it rt_upload_scene derives pairs[i] for every interior node i and triRecs[s]
+// for every primIdx slot s (the layouts, their entries and their decoders: refit_common.h).
 // Visit order, slab arithmetic, tie rules and `steps` are those of traverse_bvh2 (bvh.cl:13-54): results
 // are bit-identical; what changes is that a step costs one dependent fetch instead of two (node header,
 // then child boxes) and a triangle test one instead of two (index, then 128-byte Primitive).
-static constexpr uint32_t kLeafBit = 0x80000000u;
 RT_FORCEINLINE void test_tri_packed(const DevScene& sc, uint32_t slot, TRay& r)
 {
     const float4* rec = sc.triRecs + (size_t)slot * 3;
@@ -205,12 +216,10 @@ RT_FORCEINLINE void test_tri_packed(const DevScene& sc, uint32_t slot, TRay& r)
     // Keep the three loads of the record together: left alone, the compiler fetches the flag word first, waits, branches on it and only
     // then fetches the vertices - two dependent round trips per triangle instead of one.
     asm volatile("" : : "v"(a.x), "v"(b.x), "v"(c.x));
-    const int idx = __float_as_int(c.y);
-    if (__float_as_int(c.z) != 0) { test_prim(sc, idx, r); return; } // not a plain triangle: reference-layout test
+    const int idx = (int)tri_prim(c);
+    if (tri_not_plain(c) != 0u) { test_prim(sc, idx, r); return; } // the reference-layout test
     const float4 O = mk4(r.ox, r.oy, r.oz, 0.0f), D = mk4(r.dx, r.dy, r.dz, 0.0f);
-    // the record holds v0 and the two edges v1 - v0, v2 - v0 (the reference's first two operations, primitives.cl:49-50, done once at
-    // upload with the same IEEE subtraction)
-    const float4 v0 = mk4(a.x, a.y, a.z, 0.0f), v0v1 = mk4(a.w, b.x, b.y, 0.0f), v0v2 = mk4(b.z, b.w, c.x, 0.0f);
+    const float4 v0 = tri_v0(a, b, c), v0v1 = tri_edge1(a, b, c), v0v2 = tri_edge2(a, b, c);
     float4 pvec = cross4(D, v0v2);
     float det = dot4(v0v1, pvec);
     if (fabsf(det) < 1e-8f) return;
@@ -236,11 +245,11 @@ RT_FORCEINLINE int traverse_bvh2_packed(const DevScene& sc, TRay& r, uint32_t ro
             // ONE triangle of the leaf per iteration (the rest of the leaf stays in `cur`): a wave of this loop runs the leaf body whenever
             // any of its lanes is on a leaf, and with the whole leaf in that body every such iteration cost the lanes on a box pair two or
             // three dependent triangle fetches (config 3's late bounces 195 / 147 / 127 -> 184 / 138 / 116 us, EXPERIMENTS.md (57))
-            const uint32_t first = cur & 0x00ffffffu, count = (cur >> 24) & 0x7fu;
+            const uint32_t first = leaf_first(cur), count = leaf_count(cur);
             wc.prim++;
             test_tri_packed(sc, first, r);
             if (OCC && r.t < tLight) return -1;
-            if (count > 1) { cur = kLeafBit | ((count - 1) << 24) | (first + 1); continue; }
+            if (count > 1) { cur = leaf_rest(first, count); continue; }
             if (sp == 0) break;
             cur = STK(--sp);
             continue;
@@ -248,18 +257,18 @@ RT_FORCEINLINE int traverse_bvh2_packed(const DevScene& sc, TRay& r, uint32_t ro
         wc.node++;
         const float4* p = sc.pairs + (size_t)cur * 4;
         const float4 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
-        uint32_t e1 = __float_as_uint(q3.x), e2 = __float_as_uint(q3.y);
+        uint32_t e1 = pair_entry1(q3), e2 = pair_entry2(q3);
         if (OCC) {   // any-hit: own visit order (see slab_any)
             float x1, x2;
-            const bool h1 = slab_any(r, mk4(q0.x, q0.y, q0.z, 0.0f), mk4(q0.w, q1.x, q1.y, 0.0f), x1);
-            const bool h2 = slab_any(r, mk4(q1.z, q1.w, q2.x, 0.0f), mk4(q2.y, q2.z, q2.w, 0.0f), x2);
+            const bool h1 = slab_any(r, pair_min1(q0, q1, q2), pair_max1(q0, q1, q2), x1);
+            const bool h2 = slab_any(r, pair_min2(q0, q1, q2), pair_max2(q0, q1, q2), x2);
             if (h1 && h2) { const bool firstIs2 = x2 > x1; cur = firstIs2 ? e2 : e1; STK(sp) = firstIs2 ? e1 : e2; sp++; }
             else if (h1 || h2) cur = h1 ? e1 : e2;
             else { if (sp == 0) break; cur = STK(--sp); }
             continue;
         }
-        float d1 = slab(r, mk4(q0.x, q0.y, q0.z, 0.0f), mk4(q0.w, q1.x, q1.y, 0.0f));
-        float d2 = slab(r, mk4(q1.z, q1.w, q2.x, 0.0f), mk4(q2.y, q2.z, q2.w, 0.0f));
+        float d1 = slab(r, pair_min1(q0, q1, q2), pair_max1(q0, q1, q2));
+        float d2 = slab(r, pair_min2(q0, q1, q2), pair_max2(q0, q1, q2));
         if (d1 > d2) { float d = d1; d1 = d2; d2 = d; uint32_t e = e1; e1 = e2; e2 = e; }
         if (d1 >= tLight) {
             if (sp == 0) break;
@@ -286,9 +295,9 @@ RT_FORCEINLINE int traverse_bvh2_packed_coherent(const DevScene& sc, TRay& r, ui
     const ConstF4 cpairs = (ConstF4)(uintptr_t)sc.pairs;
     for (;;) {
         if (cur & kLeafBit) {
-            const uint32_t first = cur & 0x00ffffffu, count = (cur >> 24) & 0x7fu;
+            const uint32_t first = leaf_first(cur), count = leaf_count(cur);
             wc.prim++; test_tri_packed(sc, first, r);        // one triangle per iteration, as in traverse_bvh2_packed
-            if (count > 1) { cur = kLeafBit | ((count - 1) << 24) | (first + 1); continue; }
+            if (count > 1) { cur = leaf_rest(first, count); continue; }
             if (sp == 0) break;
             cur = STK(--sp);
             continue;
@@ -302,15 +311,15 @@ RT_FORCEINLINE int traverse_bvh2_packed_coherent(const DevScene& sc, TRay& r, ui
             // into (joined with the other branch first, the record would be copied into 14 vector registers per lane and step)
             const ConstF4 p = cpairs + (size_t)ucur * 4;
             const fvec4 a = p[0], b = p[1], c = p[2], d = p[3];
-            d1 = slab(r, mk4(a.x, a.y, a.z, 0.0f), mk4(a.w, b.x, b.y, 0.0f));
-            d2 = slab(r, mk4(b.z, b.w, c.x, 0.0f), mk4(c.y, c.z, c.w, 0.0f));
-            e1 = __float_as_uint(d.x); e2 = __float_as_uint(d.y);
+            d1 = slab(r, pair_min1(a, b, c), pair_max1(a, b, c));
+            d2 = slab(r, pair_min2(a, b, c), pair_max2(a, b, c));
+            e1 = pair_entry1(d); e2 = pair_entry2(d);
         } else {
             const float4* p = sc.pairs + (size_t)cur * 4;
             const float4 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
-            d1 = slab(r, mk4(q0.x, q0.y, q0.z, 0.0f), mk4(q0.w, q1.x, q1.y, 0.0f));
-            d2 = slab(r, mk4(q1.z, q1.w, q2.x, 0.0f), mk4(q2.y, q2.z, q2.w, 0.0f));
-            e1 = __float_as_uint(q3.x); e2 = __float_as_uint(q3.y);
+            d1 = slab(r, pair_min1(q0, q1, q2), pair_max1(q0, q1, q2));
+            d2 = slab(r, pair_min2(q0, q1, q2), pair_max2(q0, q1, q2));
+            e1 = pair_entry1(q3); e2 = pair_entry2(q3);
         }
         if (d1 > d2) { float d = d1; d1 = d2; d2 = d; uint32_t e = e1; e1 = e2; e2 = e; }
         if (d1 >= tLight) {
@@ -366,11 +375,13 @@ RT_FORCEINLINE int traverse_bvh4(const DevScene& sc, TRay& r, uint32_t root, uin
     return steps;
 }
 
-// Layout 1 of the BVH4 (derived at upload from the unchanged BVHNode4 array): quads[i] = 128 B,
-//   floats 0..23 = {min.xyz, max.xyz} of child slots 0..3, q6 = entry(slot 0..3) (0xffffffff = unused slot, else as
-//   for the BVH2 layout: interior node id, or leaf bit | count << 24 | first).  7 sixteen-byte loads from two 64-B lines
-// instead of 10 from three, and triangles come from the leaf-ordered triRecs.  Order of evaluation as bvh.cl:55-96.
-static constexpr uint32_t kNoChild = 0xffffffffu;
+// Layout 1 of the BVH4: quads[i], derived at upload from the unchanged BVHNode4 array (the layout and its decoders:
+// collapse_common.h's quad_record).  Order of evaluation as bvh.cl:55-96.
+// The ray's distance to child slot K of the quad record q0..q6 (kFar for an unused slot: the reference's value for a miss)
+template <int K> RT_FORCEINLINE float quad_slab(const TRay& r, float4 q0, float4 q1, float4 q2, float4 q3, float4 q4, float4 q5, float4 q6)
+{
+    return quad_entry<K>(q6) != kNoChild ? slab(r, quad_min<K>(q0, q1, q2, q3, q4, q5), quad_max<K>(q0, q1, q2, q3, q4, q5)) : kFar;
+}
 template <bool OCC>
 RT_FORCEINLINE int traverse_bvh4_packed(const DevScene& sc, TRay& r, uint32_t root, uint32_t* stk, WorkCtr& wc)
 {
@@ -382,18 +393,16 @@ RT_FORCEINLINE int traverse_bvh4_packed(const DevScene& sc, TRay& r, uint32_t ro
         const float4* p = sc.quads + (size_t)node * 8;
         const float4 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3], q4 = p[4], q5 = p[5], q6 = p[6];
         asm volatile("" : : "v"(q0.x), "v"(q1.x), "v"(q2.x), "v"(q3.x), "v"(q4.x), "v"(q5.x), "v"(q6.x));   // one round trip (see test_tri_packed)
-        const uint32_t e[4] = { __float_as_uint(q6.x), __float_as_uint(q6.y), __float_as_uint(q6.z), __float_as_uint(q6.w) };
+        const uint32_t e[4] = { quad_entry<0>(q6), quad_entry<1>(q6), quad_entry<2>(q6), quad_entry<3>(q6) };
         float dist[4];
-        dist[0] = e[0] != kNoChild ? slab(r, mk4(q0.x, q0.y, q0.z, 0.0f), mk4(q0.w, q1.x, q1.y, 0.0f)) : kFar;
-        dist[1] = e[1] != kNoChild ? slab(r, mk4(q1.z, q1.w, q2.x, 0.0f), mk4(q2.y, q2.z, q2.w, 0.0f)) : kFar;
-        dist[2] = e[2] != kNoChild ? slab(r, mk4(q3.x, q3.y, q3.z, 0.0f), mk4(q3.w, q4.x, q4.y, 0.0f)) : kFar;
-        dist[3] = e[3] != kNoChild ? slab(r, mk4(q4.z, q4.w, q5.x, 0.0f), mk4(q5.y, q5.z, q5.w, 0.0f)) : kFar;
+        dist[0] = quad_slab<0>(r, q0, q1, q2, q3, q4, q5, q6); dist[1] = quad_slab<1>(r, q0, q1, q2, q3, q4, q5, q6);
+        dist[2] = quad_slab<2>(r, q0, q1, q2, q3, q4, q5, q6); dist[3] = quad_slab<3>(r, q0, q1, q2, q3, q4, q5, q6);
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             if (e[k] == kNoChild) continue;
             if (dist[k] >= tLight) continue;
             if (e[k] & kLeafBit) {
-                const uint32_t first = e[k] & 0x00ffffffu, count = (e[k] >> 24) & 0x7fu;
+                const uint32_t first = leaf_first(e[k]), count = leaf_count(e[k]);
                 for (uint32_t j = 0; j < count; j++) {
                     wc.prim++;
                     test_tri_packed(sc, first + j, r);
@@ -409,21 +418,39 @@ RT_FORCEINLINE int traverse_bvh4_packed(const DevScene& sc, TRay& r, uint32_t ro
     return steps;
 }
 
-// instanceIntersect, tlas.cl:9-26 with transformRay :3-8 and util.cl:61-87.  The instance record (rows 0..2 of invT + the encoded BLAS
-// root) is one 64-byte fetch; round 1 read BVHInstance.invT and rootEntry[] separately.
+RT_FORCEINLINE void reciprocal_dir(TRay& r) { r.rx = 1.0f / r.dx; r.ry = 1.0f / r.dy; r.rz = 1.0f / r.dz; }   // rD = 1 / D: three IEEE divides
+// The ray from O along D (ray.cl:4-19); world_ray: a fresh one, with nothing hit within tmax
+RT_FORCEINLINE void ray_from(TRay& r, float4 O, float4 D)
+{
+    r.ox = O.x; r.oy = O.y; r.oz = O.z; r.dx = D.x; r.dy = D.y; r.dz = D.z;
+    reciprocal_dir(r);
+}
+RT_FORCEINLINE void no_hit(TRay& r, float tmax) { r.t = tmax; r.prim = -1; r.u = 0.0f; r.v = 0.0f; }
+RT_FORCEINLINE void world_ray(TRay& r, float4 O, float4 D, float tmax) { ray_from(r, O, D); no_hit(r, tmax); }
+// transformRay (tlas.cl:3-8, util.cl:61-87): origin and direction of the ray O, D (w = 0) in the object space of the instance whose
+// record's rows are t0..t2.  r's 1 / D stays the caller's: transform_ray sets it at once, inst_enter saves the world ray's first.
+RT_FORCEINLINE void object_space(TRay& r, float4 O, float4 D, float4 t0, float4 t1, float4 t2)
+{
+    r.dx = dot3(inst_axis(t0), D); r.dy = dot3(inst_axis(t1), D); r.dz = dot3(inst_axis(t2), D);
+    r.ox = dot3(inst_axis(t0), O) + inst_shift(t0); r.oy = dot3(inst_axis(t1), O) + inst_shift(t1);
+    r.oz = dot3(inst_axis(t2), O) + inst_shift(t2);
+}
+RT_FORCEINLINE void transform_ray(TRay& r, float4 t0, float4 t1, float4 t2)
+{
+    object_space(r, mk4(r.ox, r.oy, r.oz, 0.0f), mk4(r.dx, r.dy, r.dz, 0.0f), t0, t1, t2);
+    reciprocal_dir(r);
+}
+
+// instanceIntersect, tlas.cl:9-26.  The instance record is one 64-byte fetch; round 1 read BVHInstance.invT and rootEntry[] separately.
 template <int ACCEL, int LAYOUT, bool OCC>
 RT_FORCEINLINE int traverse_instance(const DevScene& sc, TRay& r, uint32_t instIdx, uint32_t* stk, WorkCtr& wc)
 {
     const float4* ir = sc.instRecs + (size_t)instIdx * 4;
     const float4 t0 = ir[0], t1 = ir[1], t2 = ir[2], t3 = ir[3];
     const float bx = r.ox, by = r.oy, bz = r.oz, bdx = r.dx, bdy = r.dy, bdz = r.dz, brx = r.rx, bry = r.ry, brz = r.rz;
-    const float4 Dv = mk4(bdx, bdy, bdz, 0.0f), Ov = mk4(bx, by, bz, 0.0f);
-    r.dx = dot3(mk4(t0.x, t0.y, t0.z, 0), Dv); r.dy = dot3(mk4(t1.x, t1.y, t1.z, 0), Dv); r.dz = dot3(mk4(t2.x, t2.y, t2.z, 0), Dv);
-    r.ox = dot3(mk4(t0.x, t0.y, t0.z, 0), Ov) + t0.w; r.oy = dot3(mk4(t1.x, t1.y, t1.z, 0), Ov) + t1.w;
-    r.oz = dot3(mk4(t2.x, t2.y, t2.z, 0), Ov) + t2.w;
-    r.rx = 1.0f / r.dx; r.ry = 1.0f / r.dy; r.rz = 1.0f / r.dz;
+    transform_ray(r, t0, t1, t2);
     wc.inst++;
-    const uint32_t rootEnc = __float_as_uint(t3.x), bvhIdx = __float_as_uint(t3.y);
+    const uint32_t rootEnc = inst_root(t3), bvhIdx = inst_bvh(t3);
     int steps;
     if (ACCEL == RT_ACCEL_BVH4) steps = LAYOUT == 1 ? traverse_bvh4_packed<OCC>(sc, r, rootEnc, stk, wc) : traverse_bvh4<OCC>(sc, r, bvhIdx, stk, wc);
     else if (LAYOUT == 1) steps = traverse_bvh2_packed<OCC>(sc, r, rootEnc, stk, wc);
@@ -439,34 +466,32 @@ RT_FORCEINLINE int traverse_instance(const DevScene& sc, TRay& r, uint32_t instI
 template <int ACCEL, int LAYOUT, bool OCC>
 RT_FORCEINLINE int traverse_tlas(const DevScene& sc, TRay& r, uint32_t* stk, WorkCtr& wc)
 {
-    uint16_t tstack[RT_TLAS_STACK];   // 16-bit entries as in the reference (bit 15 = leaf; <= 256 instances, <= 512 nodes)
+    uint16_t tstack[RT_TLAS_STACK];   // 16-bit entries as in the reference (tlas_pack16; <= 256 instances, <= 512 nodes)
     uint32_t cur = sc.tlasRoot, sp = 0;
-    auto pack16 = [](uint32_t c) { return (uint16_t)((c >> 16) | (c & 0x7fffu)); };
-    auto unpack16 = [](uint32_t v) { return ((v & 0x8000u) << 16) | (v & 0x7fffu); };
     int steps = 0;
     const float tLight = r.t;
     for (;;) {
-        if (cur & kLeafBit) {
-            int value = traverse_instance<ACCEL, LAYOUT, OCC>(sc, r, cur & 0x7fffffffu, stk, wc);
+        if (plain_leaf(cur)) {
+            int value = traverse_instance<ACCEL, LAYOUT, OCC>(sc, r, plain_inst(cur), stk, wc);
             if (OCC && value == -1) return -1;
             steps += value;
             if (sp == 0) break;
-            cur = unpack16(tstack[--sp]);
+            cur = tlas_unpack16(tstack[--sp]);
             continue;
         }
         wc.tlas++;
         const float4* p = sc.tlasPairs + (size_t)cur * 4;
         const float4 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
-        float d1 = slab(r, mk4(q0.x, q0.y, q0.z, 0.0f), mk4(q0.w, q1.x, q1.y, 0.0f));
-        float d2 = slab(r, mk4(q1.z, q1.w, q2.x, 0.0f), mk4(q2.y, q2.z, q2.w, 0.0f));
-        uint32_t c1 = __float_as_uint(q3.x), c2 = __float_as_uint(q3.y);
+        float d1 = slab(r, pair_min1(q0, q1, q2), pair_max1(q0, q1, q2));
+        float d2 = slab(r, pair_min2(q0, q1, q2), pair_max2(q0, q1, q2));
+        uint32_t c1 = pair_entry1(q3), c2 = pair_entry2(q3);
         if (d1 > d2) { float d = d1; d1 = d2; d2 = d; uint32_t c = c1; c1 = c2; c2 = c; }
         if (d1 >= tLight) {
             if (sp == 0) break;
-            cur = unpack16(tstack[--sp]);
+            cur = tlas_unpack16(tstack[--sp]);
         } else {
             cur = c1;
-            if (d2 < tLight) tstack[sp++] = pack16(c2);
+            if (d2 < tLight) tstack[sp++] = tlas_pack16(c2);
         }
     }
     return steps;
@@ -558,11 +583,8 @@ __global__ __launch_bounds__(kBlock) void k_extend(DevScene sc, DevQueues q, int
     WorkCtr wc = { 0, 0, 0, 0 };
     uint32_t rays = 0;
     if (i < n) {
-        const float4 O = q.O[bounce & 1][i], D = q.D[bounce & 1][i];
         TRay r;
-        r.ox = O.x; r.oy = O.y; r.oz = O.z; r.dx = D.x; r.dy = D.y; r.dz = D.z;
-        r.rx = 1.0f / D.x; r.ry = 1.0f / D.y; r.rz = 1.0f / D.z;
-        r.t = kFar; r.prim = -1; r.u = 0.0f; r.v = 0.0f;
+        world_ray(r, q.O[bounce & 1][i], q.D[bounce & 1][i], kFar);
         int steps = traverse_tlas<ACCEL, LAYOUT, false>(sc, r, stk, wc);
         rays = 1;
         q.hit[i] = mk4(r.t, __int_as_float(r.prim), r.u, r.v);
@@ -665,30 +687,16 @@ RT_FORCEINLINE OneInstance one_instance(const DevScene& sc)
     return { mk4(T[0], T[1], T[2], T[3]), mk4(T[4], T[5], T[6], T[7]), mk4(T[8], T[9], T[10], T[11]), sc.rootEntry[b] };
 }
 
-// transformRay (tlas.cl:3-8): the ray O, D into the space of the instance with inverse-transform rows t0..t2, rD = 1 / D - the
-// arithmetic of traverse_instance
-RT_FORCEINLINE void transform_ray(TRay& r, float4 O, float4 D, float4 t0, float4 t1, float4 t2)
-{
-    const float4 Dv = mk4(D.x, D.y, D.z, 0.0f), Ov = mk4(O.x, O.y, O.z, 0.0f);
-    r.dx = dot3(mk4(t0.x, t0.y, t0.z, 0), Dv); r.dy = dot3(mk4(t1.x, t1.y, t1.z, 0), Dv); r.dz = dot3(mk4(t2.x, t2.y, t2.z, 0), Dv);
-    r.ox = dot3(mk4(t0.x, t0.y, t0.z, 0), Ov) + t0.w; r.oy = dot3(mk4(t1.x, t1.y, t1.z, 0), Ov) + t1.w;
-    r.oz = dot3(mk4(t2.x, t2.y, t2.z, 0), Ov) + t2.w;
-    r.rx = 1.0f / r.dx; r.ry = 1.0f / r.dy; r.rz = 1.0f / r.dz;
-}
-
 // Queue slot `idx` as a new ray with r.t = its tmax (extend: kFar; connect: t_light): the world ray as k_extend / k_connect build it
-// (rD = 1 / D, three IEEE divides) or, given `inst`, that ray in the instance's object space
+// or, given `inst`, that ray in the instance's object space
 template <bool OCC> RT_FORCEINLINE void queue_ray(TRay& r, const DevQueues& q, int b0, int qFirst, int idx, const OneInstance* inst = nullptr)
 {
     float4 O, D; float tmax;
     if (OCC) { const float4 a = q.sA[qFirst + idx], b = q.sB[qFirst + idx]; O = a; D = b; tmax = a.w; }
     else { O = q.O[b0 & 1][idx]; D = q.D[b0 & 1][idx]; tmax = kFar; }
-    if (inst) transform_ray(r, O, D, inst->t0, inst->t1, inst->t2);
-    else {
-        r.ox = O.x; r.oy = O.y; r.oz = O.z; r.dx = D.x; r.dy = D.y; r.dz = D.z;
-        r.rx = 1.0f / D.x; r.ry = 1.0f / D.y; r.rz = 1.0f / D.z;
-    }
-    r.t = tmax; r.prim = -1; r.u = 0.0f; r.v = 0.0f;
+    if (inst) { object_space(r, mk4(O.x, O.y, O.z, 0.0f), mk4(D.x, D.y, D.z, 0.0f), inst->t0, inst->t1, inst->t2); reciprocal_dir(r); }
+    else ray_from(r, O, D);
+    no_hit(r, tmax);
 }
 
 // What a traced queue slot leaves behind: extend -> the hit record and, where kept, `steps` and the heat map (wavefront.cl:66-67);
@@ -755,19 +763,19 @@ struct ChunkDealer {
 template <bool OCC, bool STEPS>
 RT_FORCEINLINE int node_event(const TRay& r, float tLight, float4 q0, float4 q1, float4 q2, float4 q3, uint32_t* stk, uint32_t& cur, uint32_t& sp, int& steps, bool& done)
 {
-    uint32_t e1 = __float_as_uint(q3.x), e2 = __float_as_uint(q3.y);
+    uint32_t e1 = pair_entry1(q3), e2 = pair_entry2(q3);
     int child = 0;
     if (OCC) {   // any-hit: the child the ray leaves later first (see slab_any); no `steps`, no near / far sort
         float x1, x2;
-        const bool h1 = slab_any(r, mk4(q0.x, q0.y, q0.z, 0.0f), mk4(q0.w, q1.x, q1.y, 0.0f), x1);
-        const bool h2 = slab_any(r, mk4(q1.z, q1.w, q2.x, 0.0f), mk4(q2.y, q2.z, q2.w, 0.0f), x2);
+        const bool h1 = slab_any(r, pair_min1(q0, q1, q2), pair_max1(q0, q1, q2), x1);
+        const bool h2 = slab_any(r, pair_min2(q0, q1, q2), pair_max2(q0, q1, q2), x2);
         if (h1 && h2) { const bool firstIs2 = x2 > x1; cur = firstIs2 ? e2 : e1; STK(sp) = firstIs2 ? e1 : e2; sp++; child = firstIs2 ? 2 : 1; }
         else if (h1 || h2) { cur = h1 ? e1 : e2; child = h1 ? 1 : 2; }
         else if (sp == 0) done = true;
         else cur = STK(--sp);
     } else {
-        float d1 = slab(r, mk4(q0.x, q0.y, q0.z, 0.0f), mk4(q0.w, q1.x, q1.y, 0.0f));
-        float d2 = slab(r, mk4(q1.z, q1.w, q2.x, 0.0f), mk4(q2.y, q2.z, q2.w, 0.0f));
+        float d1 = slab(r, pair_min1(q0, q1, q2), pair_max1(q0, q1, q2));
+        float d2 = slab(r, pair_min2(q0, q1, q2), pair_max2(q0, q1, q2));
         const bool swap = d1 > d2;
         if (swap) { float d = d1; d1 = d2; d2 = d; uint32_t e = e1; e1 = e2; e2 = e; }
         if (d1 >= tLight) {
@@ -798,7 +806,7 @@ RT_FORCEINLINE void fill_top(const DevScene& sc, uint32_t root, float4* top, int
         if (t < n) {
             const int s = n - 1 + t;
             uint32_t e = root;
-            if (l > 0) { const float4 up = top[((s - 1) >> 1) * 4 + 3]; e = __float_as_uint((s & 1) ? up.x : up.y); }
+            if (l > 0) { const float4 up = top[((s - 1) >> 1) * 4 + 3]; e = __float_as_uint((s & 1) ? up.x : up.y); }   // (pair_entry1 / pair_entry2 of the parent's record)
             float4 q0 = splat(0.0f), q1 = q0, q2 = q0, q3 = absent;
             if (!(e & kLeafBit)) { const float4* p = sc.pairs + (size_t)e * 4; q0 = p[0]; q1 = p[1]; q2 = p[2]; q3 = p[3]; }
             float4* o = top + s * 4;
@@ -916,10 +924,10 @@ __global__ __launch_bounds__(kBlock) void k_trace_persist(DevScene sc, DevQueues
             if (doLeaf) {
                 wPrim += (uint32_t)__popcll(lm); if (STEPS) wLeafIss++;
                 if (atLeaf) {
-                    const uint32_t first = cur & 0x00ffffffu, count = (cur >> 24) & 0x7fu;
+                    const uint32_t first = leaf_first(cur), count = leaf_count(cur);
                     test_tri_packed(sc, first, r);
                     if (OCC && r.t < tLight) { done = true; occluded = true; }
-                    else if (count > 1) cur = kLeafBit | ((count - 1) << 24) | (first + 1);
+                    else if (count > 1) cur = leaf_rest(first, count);
                     else if (sp == 0) done = true;
                     else cur = STK(--sp);
                 }
@@ -941,11 +949,7 @@ __global__ __launch_bounds__(kBlock) void k_trace_persist(DevScene sc, DevQueues
 // ------------------------------------------------------------------ k_trace_persist_tlas: persistent wavefronts through a multi-BLAS TLAS (BVH2, layout 1)
 // BASELINE config 5 (two BLAS under a TLAS; tlas.cl:9-77).  Same work distribution and event loop as k_trace_persist; what is new is
 // that a lane's traversal has two levels.  Everything a lane still has to visit lives on ONE LDS stack column, the entries tagged by
-// the space they belong to:
-//     bit 31 set                      BLAS leaf        count << 24 | first          (as in k_trace_persist)
-//     bits 31..29 = 000               BLAS interior    id in the dense pair table
-//     bits 31..29 = 010  (kTagTlas)   TLAS interior    id in tlasPairsP
-//     bits 31..29 = 011  (kTagInst)   TLAS leaf        instance id
+// the space they belong to (refit_common.h, "tagged TLAS": BLAS leaf, BLAS interior, kTagTlas, kTagInst).
 // A lane is either in TLAS space (world ray in its registers, spBase = 0) or inside an instance (object-space ray in its registers;
 // spBase = the stack height at entry, so "sp == spBase" means the instance's tree is exhausted).  The ray is transformed ONCE, at the
 // moment the lane enters the instance (transformRay, tlas.cl:3-8, the arithmetic of traverse_instance), kept in registers over all
@@ -957,18 +961,6 @@ __global__ __launch_bounds__(kBlock) void k_trace_persist(DevScene sc, DevQueues
 // connect (OCC): inside an instance the any-hit order of k_trace_persist (later exit first); TLAS nodes keep the reference's
 // near-first order, so the TLAS-visit and instance-visit counts stay the reference's (which instance is entered first decides whether
 // the second one is entered at all).
-static constexpr uint32_t kTagTlas = 0x40000000u, kTagInst = 0x60000000u, kTagMask = 0xe0000000u, kIdMask = 0x1fffffffu;
-RT_FORCEINLINE bool slab_both(const TRay& r, float4 bmin, float4 bmax, float& tminOut, float& tmaxOut)
-{
-    float tx1 = (bmin.x - r.ox) * r.rx, tx2 = (bmax.x - r.ox) * r.rx;
-    float tmin = fminf(tx1, tx2), tmax = fmaxf(tx1, tx2);
-    float ty1 = (bmin.y - r.oy) * r.ry, ty2 = (bmax.y - r.oy) * r.ry;
-    tmin = fmaxf(tmin, fminf(ty1, ty2)); tmax = fminf(tmax, fmaxf(ty1, ty2));
-    float tz1 = (bmin.z - r.oz) * r.rz, tz2 = (bmax.z - r.oz) * r.rz;
-    tmin = fmaxf(tmin, fminf(tz1, tz2)); tmax = fminf(tmax, fmaxf(tz1, tz2));
-    tminOut = tmin; tmaxOut = tmax;
-    return tmax >= tmin && tmin < r.t && tmax > 0;
-}
 // SPILL: the LDS column holds the first q.stackCap entries of a lane's stack, deeper ones live in a global per-lane column (q.spill,
 // entry-major so that the lanes of a wave write neighbouring words).  An SBVH at alpha = 0 gets DEEP (config 5's terrarium: 63 levels):
 // 64 entries x 1 KB per workgroup would leave two workgroups per CU; capped at 20 entries seven fit, and the traversal - a chain of
@@ -992,19 +984,17 @@ template <bool SPILL> RT_FORCEINLINE uint32_t stk_pop(const uint32_t* stk, const
 RT_FORCEINLINE void inst_enter(const DevScene& sc, const DevQueues& q, uint32_t* stk, TRay& r, uint32_t& cur, uint32_t sp, uint32_t& spBase,
                                bool& inInst, float& tLight)
 {
-    const float4* ir = sc.instRecs + (size_t)(cur & kIdMask) * 4;
+    const float4* ir = sc.instRecs + (size_t)tagged_id(cur) * 4;
     const float4 t0 = ir[0], t1 = ir[1], t2 = ir[2], t3 = ir[3];
     const float4 Dv = mk4(r.dx, r.dy, r.dz, 0.0f), Ov = mk4(r.ox, r.oy, r.oz, 0.0f);
-    r.dx = dot3(mk4(t0.x, t0.y, t0.z, 0), Dv); r.dy = dot3(mk4(t1.x, t1.y, t1.z, 0), Dv); r.dz = dot3(mk4(t2.x, t2.y, t2.z, 0), Dv);
-    r.ox = dot3(mk4(t0.x, t0.y, t0.z, 0), Ov) + t0.w; r.oy = dot3(mk4(t1.x, t1.y, t1.z, 0), Ov) + t1.w;
-    r.oz = dot3(mk4(t2.x, t2.y, t2.z, 0), Ov) + t2.w;
+    object_space(r, Ov, Dv, t0, t1, t2);
     uint32_t* bk = stk + q.tlasLdsEntries * kBlock + threadIdx.x;
     bk[0] = __float_as_uint(Ov.x); bk[kBlock] = __float_as_uint(Ov.y); bk[2 * kBlock] = __float_as_uint(Ov.z);
     bk[3 * kBlock] = __float_as_uint(Dv.x); bk[4 * kBlock] = __float_as_uint(Dv.y); bk[5 * kBlock] = __float_as_uint(Dv.z);
     bk[6 * kBlock] = __float_as_uint(r.rx); bk[7 * kBlock] = __float_as_uint(r.ry); bk[8 * kBlock] = __float_as_uint(r.rz);
     bk[9 * kBlock] = __float_as_uint(tLight);   // (extend: 1e30; connect: t_light)
-    r.rx = 1.0f / r.dx; r.ry = 1.0f / r.dy; r.rz = 1.0f / r.dz;   // (transform_ray, written out: the world ray's 1/D goes to LDS first)
-    cur = __float_as_uint(t3.x);
+    reciprocal_dir(r);   // (transform_ray in two steps: the world ray's 1/D goes to LDS first)
+    cur = inst_root(t3);
     spBase = sp; inInst = true; tLight = r.t;
 }
 // ... and leave it, its tree exhausted: back to the world ray and the TLAS level's pruning distance (tlas.cl:21-23, :31)
@@ -1029,12 +1019,12 @@ RT_FORCEINLINE bool tlas_node(const DevScene& sc, const DevQueues& q, uint32_t* 
 {
     const bool isT = (cur & kTagTlas) != 0u;
     if (OCC) {
-        const float4* p = (isT ? sc.tlasPairsP : sc.pairs) + (size_t)(cur & kIdMask) * 4;
+        const float4* p = (isT ? sc.tlasPairsP : sc.pairs) + (size_t)tagged_id(cur) * 4;
         const float4 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
-        const uint32_t e1 = __float_as_uint(q3.x), e2 = __float_as_uint(q3.y);
+        const uint32_t e1 = pair_entry1(q3), e2 = pair_entry2(q3);
         float n1, x1, n2, x2;
-        const bool h1 = slab_both(r, mk4(q0.x, q0.y, q0.z, 0.0f), mk4(q0.w, q1.x, q1.y, 0.0f), n1, x1);
-        const bool h2 = slab_both(r, mk4(q1.z, q1.w, q2.x, 0.0f), mk4(q2.y, q2.z, q2.w, 0.0f), n2, x2);
+        const bool h1 = slab_both(r, pair_min1(q0, q1, q2), pair_max1(q0, q1, q2), n1, x1);
+        const bool h2 = slab_both(r, pair_min2(q0, q1, q2), pair_max2(q0, q1, q2), n2, x2);
         if (h1 && h2) { const bool firstIs2 = isT ? (n2 < n1) : (x2 > x1); cur = firstIs2 ? e2 : e1; stk_push<SPILL>(stk, q, gl, sp, firstIs2 ? e1 : e2); }
         else if (h1 || h2) cur = h1 ? e1 : e2;
         else return true;
@@ -1044,17 +1034,17 @@ RT_FORCEINLINE bool tlas_node(const DevScene& sc, const DevQueues& q, uint32_t* 
     uint32_t e1, e2;
     const uint32_t ucur = COH ? __builtin_amdgcn_readfirstlane(cur) : 0u;
     if (COH && __ballot(cur != ucur) == 0ull) {   // (the slab tests are written out here too: they read the record from scalar registers)
-        const ConstF4 cp = (ConstF4)(uintptr_t)((ucur & kTagTlas) != 0u ? sc.tlasPairsP : sc.pairs) + (size_t)(ucur & kIdMask) * 4;
+        const ConstF4 cp = (ConstF4)(uintptr_t)((ucur & kTagTlas) != 0u ? sc.tlasPairsP : sc.pairs) + (size_t)tagged_id(ucur) * 4;
         const fvec4 a = cp[0], b = cp[1], c = cp[2], d = cp[3];
-        d1 = slab(r, mk4(a.x, a.y, a.z, 0.0f), mk4(a.w, b.x, b.y, 0.0f));
-        d2 = slab(r, mk4(b.z, b.w, c.x, 0.0f), mk4(c.y, c.z, c.w, 0.0f));
-        e1 = __float_as_uint(d.x); e2 = __float_as_uint(d.y);
+        d1 = slab(r, pair_min1(a, b, c), pair_max1(a, b, c));
+        d2 = slab(r, pair_min2(a, b, c), pair_max2(a, b, c));
+        e1 = pair_entry1(d); e2 = pair_entry2(d);
     } else {
-        const float4* p = (isT ? sc.tlasPairsP : sc.pairs) + (size_t)(cur & kIdMask) * 4;
+        const float4* p = (isT ? sc.tlasPairsP : sc.pairs) + (size_t)tagged_id(cur) * 4;
         const float4 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3];
-        d1 = slab(r, mk4(q0.x, q0.y, q0.z, 0.0f), mk4(q0.w, q1.x, q1.y, 0.0f));
-        d2 = slab(r, mk4(q1.z, q1.w, q2.x, 0.0f), mk4(q2.y, q2.z, q2.w, 0.0f));
-        e1 = __float_as_uint(q3.x); e2 = __float_as_uint(q3.y);
+        d1 = slab(r, pair_min1(q0, q1, q2), pair_max1(q0, q1, q2));
+        d2 = slab(r, pair_min2(q0, q1, q2), pair_max2(q0, q1, q2));
+        e1 = pair_entry1(q3); e2 = pair_entry2(q3);
     }
     if (d1 > d2) { float d = d1; d1 = d2; d2 = d; uint32_t e = e1; e1 = e2; e2 = e; }
     if (d1 >= tLight) return true;
@@ -1097,7 +1087,7 @@ __global__ __launch_bounds__(kBlock, 7) void k_trace_persist_tlas(DevScene sc, D
             for (;;) {
                 bool needPop = false;
                 if (cur & kLeafBit) {
-                    const uint32_t first = cur & 0x00ffffffu, count = (cur >> 24) & 0x7fu;
+                    const uint32_t first = leaf_first(cur), count = leaf_count(cur);
                     for (uint32_t i = 0; i < count; i++) {
                         wc.prim++;
                         test_tri_packed(sc, first + i, r);
@@ -1145,9 +1135,10 @@ __global__ __launch_bounds__(kBlock, 7) void k_trace_persist_tlas(DevScene sc, D
             if ((lm | im | xm) == 0ull) break;
             if (xm != 0ull) {   // entering an instance is rare (<= nBlas per ray) and short, so it goes first and alone
                 wInst += (uint32_t)__popcll(xm);
-                // (inst_enter, inst_exit and store_result written out: with all three shared the any-hit instantiations exceed 72 VGPRs)
+                // (inst_enter, inst_exit and store_result written out: with all three shared the any-hit instantiations exceed 72 VGPRs.
+                // Lane for lane, too: with object_space, reciprocal_dir or inst_root in this block the kernel compiles to other code)
                 if (atInst) {
-                    const float4* ir = sc.instRecs + (size_t)(cur & kIdMask) * 4;
+                    const float4* ir = sc.instRecs + (size_t)tagged_id(cur) * 4;
                     const float4 t0 = ir[0], t1 = ir[1], t2 = ir[2], t3 = ir[3];
                     const float4 Dv = mk4(r.dx, r.dy, r.dz, 0.0f), Ov = mk4(r.ox, r.oy, r.oz, 0.0f);
                     r.dx = dot3(mk4(t0.x, t0.y, t0.z, 0), Dv); r.dy = dot3(mk4(t1.x, t1.y, t1.z, 0), Dv); r.dz = dot3(mk4(t2.x, t2.y, t2.z, 0), Dv);
@@ -1171,10 +1162,10 @@ __global__ __launch_bounds__(kBlock, 7) void k_trace_persist_tlas(DevScene sc, D
             if (doLeaf) {
                 wPrim += (uint32_t)__popcll(lm); if (STEPS) wLeafIss++;
                 if (atLeaf) {
-                    const uint32_t first = cur & 0x00ffffffu, count = (cur >> 24) & 0x7fu;
+                    const uint32_t first = leaf_first(cur), count = leaf_count(cur);
                     test_tri_packed(sc, first, r);
                     if (OCC && r.t < tLight) { done = true; occluded = true; }
-                    else if (count > 1) cur = kLeafBit | ((count - 1) << 24) | (first + 1);
+                    else if (count > 1) cur = leaf_rest(first, count);
                     else needPop = true;
                 }
             } else {
@@ -1253,12 +1244,12 @@ __global__ __launch_bounds__(kBlock) void k_trace_persist4(DevScene sc, DevQueue
                 if (atLeaf) {
                     const int k = __ffs((int)leafMask) - 1;
                     uint32_t ek = k == 0 ? e0 : (k == 1 ? e1 : (k == 2 ? e2 : e3));
-                    const uint32_t first = ek & 0x00ffffffu, count = (ek >> 24) & 0x7fu;
+                    const uint32_t first = leaf_first(ek), count = leaf_count(ek);
                     wc.prim++;
                     test_tri_packed(sc, first, r);
                     if (OCC && r.t < tLight) { done = true; occluded = true; }
                     else if (count > 1) {
-                        ek = kLeafBit | ((count - 1) << 24) | (first + 1);
+                        ek = leaf_rest(first, count);
                         if (k == 0) e0 = ek; else if (k == 1) e1 = ek; else if (k == 2) e2 = ek; else e3 = ek;
                     } else {
                         leafMask &= leafMask - 1u;
@@ -1270,6 +1261,7 @@ __global__ __launch_bounds__(kBlock) void k_trace_persist4(DevScene sc, DevQueue
                 const float4* p = sc.quads + (size_t)cur * 8;
                 const float4 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3], q4 = p[4], q5 = p[5], q6 = p[6];
                 asm volatile("" : : "v"(q0.x), "v"(q1.x), "v"(q2.x), "v"(q3.x), "v"(q4.x), "v"(q5.x), "v"(q6.x));   // one round trip (see test_tri_packed)
+                // (quad_entry<K> and quad_slab<K>, lane by lane: through the decoders, the entries or the boxes alone, this kernel compiles to other code)
                 e0 = __float_as_uint(q6.x); e1 = __float_as_uint(q6.y); e2 = __float_as_uint(q6.z); e3 = __float_as_uint(q6.w);
                 const float d0 = e0 != kNoChild ? slab(r, mk4(q0.x, q0.y, q0.z, 0.0f), mk4(q0.w, q1.x, q1.y, 0.0f)) : kFar;
                 const float d1 = e1 != kNoChild ? slab(r, mk4(q1.z, q1.w, q2.x, 0.0f), mk4(q2.y, q2.z, q2.w, 0.0f)) : kFar;
@@ -1293,10 +1285,7 @@ __global__ __launch_bounds__(kBlock) void k_trace_persist4(DevScene sc, DevQueue
 
 // ------------------------------------------------------------------ k_trace_persist4_tlas: persistent wavefronts through a multi-BLAS TLAS over BVH4 instances (layout 1)
 // The state machine of k_trace_persist_tlas with the instances of k_trace_persist4.  One stack column per lane (LDS; SPILL: its deep end
-// in q.spill) holds
-//     bits 31..29 = 000               BVH4 interior    id in the dense quad table
-//     bits 31..29 = 010  (kTagTlas)   TLAS interior    id in tlasPairsP
-//     bits 31..29 = 011  (kTagInst)   TLAS leaf        instance id
+// in q.spill) holds BVH4 interior entries (ids in the dense quad table) and the tagged TLAS entries (refit_common.h).
 // BVH4 leaf children never reach the column: the ones a quad visit hit wait in e0..e3 under leafMask, as in k_trace_persist4, so an
 // instance is exhausted when leafMask == 0 && sp == spBase.  Instance entry and exit are inst_enter / inst_exit (ray transformed once,
 // world ray + TLAS-level tLight in the 10 backup words, cur = the instance record's quad root, tLight = r.t on entry); TLAS interior
@@ -1317,11 +1306,9 @@ RT_FORCEINLINE uint32_t quad_node(const DevScene& sc, const DevQueues& q, uint32
     const float4* p = sc.quads + (size_t)cur * 8;
     const float4 q0 = p[0], q1 = p[1], q2 = p[2], q3 = p[3], q4 = p[4], q5 = p[5], q6 = p[6];
     asm volatile("" : : "v"(q0.x), "v"(q1.x), "v"(q2.x), "v"(q3.x), "v"(q4.x), "v"(q5.x), "v"(q6.x));   // one round trip (see test_tri_packed)
-    e0 = __float_as_uint(q6.x); e1 = __float_as_uint(q6.y); e2 = __float_as_uint(q6.z); e3 = __float_as_uint(q6.w);
-    const float d0 = e0 != kNoChild ? slab(r, mk4(q0.x, q0.y, q0.z, 0.0f), mk4(q0.w, q1.x, q1.y, 0.0f)) : kFar;
-    const float d1 = e1 != kNoChild ? slab(r, mk4(q1.z, q1.w, q2.x, 0.0f), mk4(q2.y, q2.z, q2.w, 0.0f)) : kFar;
-    const float d2 = e2 != kNoChild ? slab(r, mk4(q3.x, q3.y, q3.z, 0.0f), mk4(q3.w, q4.x, q4.y, 0.0f)) : kFar;
-    const float d3 = e3 != kNoChild ? slab(r, mk4(q4.z, q4.w, q5.x, 0.0f), mk4(q5.y, q5.z, q5.w, 0.0f)) : kFar;
+    e0 = quad_entry<0>(q6); e1 = quad_entry<1>(q6); e2 = quad_entry<2>(q6); e3 = quad_entry<3>(q6);
+    const float d0 = quad_slab<0>(r, q0, q1, q2, q3, q4, q5, q6), d1 = quad_slab<1>(r, q0, q1, q2, q3, q4, q5, q6);
+    const float d2 = quad_slab<2>(r, q0, q1, q2, q3, q4, q5, q6), d3 = quad_slab<3>(r, q0, q1, q2, q3, q4, q5, q6);
     uint32_t m = 0;
     if (e0 != kNoChild && d0 < tLight) { if (e0 & kLeafBit) m |= 1u; else stk_push<SPILL>(stk, q, gl, sp, e0); }
     if (e1 != kNoChild && d1 < tLight) { if (e1 & kLeafBit) m |= 2u; else stk_push<SPILL>(stk, q, gl, sp, e1); }
@@ -1370,7 +1357,7 @@ __global__ __launch_bounds__(kBlock) void k_trace_persist4_tlas(DevScene sc, Dev
                     while (lm != 0u) {   // the leaf children that were hit, in slot order
                         const int k = __ffs((int)lm) - 1;
                         const uint32_t ek = k == 0 ? e0 : (k == 1 ? e1 : (k == 2 ? e2 : e3));
-                        const uint32_t first = ek & 0x00ffffffu, count = (ek >> 24) & 0x7fu;
+                        const uint32_t first = leaf_first(ek), count = leaf_count(ek);
                         for (uint32_t i = 0; i < count; i++) {
                             wc.prim++;
                             test_tri_packed(sc, first + i, r);
@@ -1424,11 +1411,11 @@ __global__ __launch_bounds__(kBlock) void k_trace_persist4_tlas(DevScene sc, Dev
                 if (atLeaf) {
                     const int k = __ffs((int)leafMask) - 1;
                     uint32_t ek = k == 0 ? e0 : (k == 1 ? e1 : (k == 2 ? e2 : e3));
-                    const uint32_t first = ek & 0x00ffffffu, count = (ek >> 24) & 0x7fu;
+                    const uint32_t first = leaf_first(ek), count = leaf_count(ek);
                     test_tri_packed(sc, first, r);
                     if (OCC && r.t < tLight) { done = true; occluded = true; }
                     else if (count > 1) {
-                        ek = kLeafBit | ((count - 1) << 24) | (first + 1);
+                        ek = leaf_rest(first, count);
                         if (k == 0) e0 = ek; else if (k == 1) e1 = ek; else if (k == 2) e2 = ek; else e3 = ek;
                     } else {
                         leafMask &= leafMask - 1u;
@@ -2002,9 +1989,7 @@ __global__ __launch_bounds__(kBlock) void k_connect(DevScene sc, DevQueues q, in
     if (i < n) {
         const float4 a = q.sA[first + i], b = q.sB[first + i];
         TRay r;
-        r.ox = a.x; r.oy = a.y; r.oz = a.z; r.dx = b.x; r.dy = b.y; r.dz = b.z;
-        r.rx = 1.0f / b.x; r.ry = 1.0f / b.y; r.rz = 1.0f / b.z;
-        r.t = a.w; r.prim = -1; r.u = 0.0f; r.v = 0.0f;
+        world_ray(r, a, b, a.w);
         rays = 1;
         if (traverse_tlas<ACCEL, LAYOUT, true>(sc, r, stk, wc) == -1) q.sC[first + i] = splat(0.0f); // occluded: contributes nothing
     }
@@ -2037,9 +2022,7 @@ __global__ void k_focus(DevScene sc, RtCamera cam, int x, int y, int W, int H, f
     float4 D = normalize4<REFB>(sub4(P, ld4(cam.origin)));
     float4 O = ld4(cam.origin);
     TRay r;
-    r.ox = O.x; r.oy = O.y; r.oz = O.z; r.dx = D.x; r.dy = D.y; r.dz = D.z;
-    r.rx = 1.0f / D.x; r.ry = 1.0f / D.y; r.rz = 1.0f / D.z;
-    r.t = kFar; r.prim = -1; r.u = r.v = 0.0f;
+    world_ray(r, O, D, kFar);
     WorkCtr wc = { 0, 0, 0, 0 };
     traverse_tlas<ACCEL, 0, false>(sc, r, stk, wc);
     *out = r.t;

@@ -270,7 +270,7 @@ int scenedev::upload_scene(SceneBag& b, int accel, int extendVariant, const Host
         if (rebuild::takes_layout1(extendVariant != 1, nIdx, largestLeaf)) { pairs = pair_records(n2, nNodes, blas, nBlas, pairNode, roots); layout = 1; }
     } else if (blas4) {
         // (the layout follows from the collapse on the device, below)
-    } else if (extendVariant != 1 && nIdx < (1 << 24)) {
+    } else if (extendVariant != 1 && nIdx < rebuild::kMaxPackedIdx) {
         bool fits = true;
         for (int32_t i = 0; i < nNodes && fits; i++) for (int k = 0; k < 4; k++) if (n4[i].first[k] != RT_INVALID && n4[i].count[k] > (int32_t)rebuild::kMaxPackedLeaf) fits = false;
         if (fits) { quads = quad_records(n4, nNodes, nIdx, blas, nBlas, roots); layout = 1; }
@@ -302,8 +302,8 @@ int scenedev::upload_scene(SceneBag& b, int accel, int extendVariant, const Host
     if (rc == RT_OK) rc = upload(b, &sc.tlasPairsP, tlas_records(tlas, nTlas, true));
     if (rc != RT_OK) return rc;
     const bool leafRoot = tlas[0].leftRight == 0;
-    sc.tlasRoot = leafRoot ? (refit::kLeafBit | tlas[0].BLASidx) : 0u;
-    sc.tlasRootP = leafRoot ? (refit::kTagInst | tlas[0].BLASidx) : refit::kTagTlas;
+    sc.tlasRoot = leafRoot ? refit::tlas_leaf_entry(false, tlas[0].BLASidx) : refit::tlas_node_entry(false, 0u);
+    sc.tlasRootP = leafRoot ? refit::tlas_leaf_entry(true, tlas[0].BLASidx) : refit::tlas_node_entry(true, 0u);
     sc.nLights = nLights; sc.nPrims = nPrims; sc.nBlas = nBlas; sc.nTex = nTexels; sc.nMats = nMats;
     // ---- bind: the copy's facts, and what updates and rebuilds need of this upload
     b.sc = sc;

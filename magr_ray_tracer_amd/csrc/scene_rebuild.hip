@@ -578,8 +578,8 @@ void Pending::commit()
     if (resize) {   // the new shape: the counts, the TLAS root (a leaf iff there is one instance: TLAS::Build copies it to node 0)
         n.nPrims = sh.nPrims; n.nLights = nLights; n.nBlas = sh.nBlas;
         const bool leafRoot = sh.nBlas == 1;
-        n.tlasRoot = leafRoot ? refit::kLeafBit : 0u;
-        n.tlasRootP = leafRoot ? refit::kTagInst : refit::kTagTlas;
+        n.tlasRoot = leafRoot ? refit::tlas_leaf_entry(false, 0u) : refit::tlas_node_entry(false, 0u);   // (instance 0, or TLAS node 0)
+        n.tlasRootP = leafRoot ? refit::tlas_leaf_entry(true, 0u) : refit::tlas_node_entry(true, 0u);
         b.singleBlas = leafRoot; b.lightsInSet = true;
         b.nPrims = sh.nPrims; b.nLights = nLights; b.nBlas = sh.nBlas; b.nTlas = sh.nTlas();
         b.primType.resize(packed.size()); b.primMat.resize(packed.size());

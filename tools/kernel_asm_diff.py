@@ -7,7 +7,8 @@ PARENT_TREE is a checkout of the commit to compare with (git worktree add, or gi
 build.DEVICE_SRCS of both trees is compiled to gfx950 assembly with build.DEVICE_FLAGS (minus -shared), in both builtin modes
 (plain and -DRT355_REF_BUILTINS); needs hipcc, no GPU.  A kernel is compared by its instructions and its .amdhsa_ descriptor, from
 its entry label to .end_amdhsa_kernel, after normalising only what a kernel's position in a file changes: the __hip_cuid_<hash>
-symbol and the function index in local labels (.LBB<n>_<m>, .Lfunc_end<n>); comments are dropped.  Every kernel must exist exactly once on each side.
+symbol and the function index in local labels (.LBB<n>_<m>, .Lfunc_end<n>); comments are dropped.  A kernel must exist exactly once on
+each side, or - a library template that several files instantiate, each its own copy - in the same files on both sides, file by file the same.
 Prints which file holds each kernel on either side and its -Rpass-analysis=kernel-resource-usage figures; exit status 1 on any
 difference.  With --only, both sides compile just the named files (those the parent lacks are skipped there).
 """
@@ -128,12 +129,12 @@ def main():
         rows.append("%-9s %-16s %-16s %s   | kernel" % ("verdict", "parent file", "branch file", " / ".join(FIGURES)))
         for k in names:
             p, b = P.get(k, []), B.get(k, [])
-            if len(p) != 1 or len(b) != 1:
-                verdict = "COUNT %d:%d" % (len(p), len(b))
-            elif p[0][1] != b[0][1]:
-                verdict = "DIFFERS"
+            if len(p) == 1 and len(b) == 1:   # (wherever it is now)
+                verdict = "same" if p[0][1] == b[0][1] else "DIFFERS"
+            elif p and sorted(e[0] for e in p) == sorted(e[0] for e in b):   # a library template that several files instantiate, each its own copy
+                verdict = "same" if sorted(e[:2] for e in p) == sorted(e[:2] for e in b) else "DIFFERS"
             else:
-                verdict = "same"
+                verdict = "COUNT %d:%d" % (len(p), len(b))
             same += verdict == "same"
             bad += verdict != "same"
             fig = lambda e: " ".join(e[0][2].get(f, "?") for f in FIGURES) if e else "-"
