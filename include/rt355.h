@@ -398,7 +398,7 @@ int rt_rebuild_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t first, int32_
  * call, and one call cannot mix builders.  rt_rebuild_ranges takes a plan: plan[k], one word per distinct BLAS in increasing order of the
  * primitive ranges (the order of rt_scene_blas_blocks and rt_blas_ranges' ranges), is RT_REBUILD_SAH, RT_REBUILD_LBVH or RT_REBUILD_SBVH -
  * that BLAS is built by that builder, as rt_rebuild_scene builds it (one opts for all: the LBVH words go to the LBVH ranges, alpha to the
- * SBVH ranges) - or RT_REBUILD_KEEP: its bound tree stays.  prims / first / count / blas / nBlas mean what they mean for
+ * SBVH ranges) -, RT_REBUILD_KEEP: its bound tree stays, or RT_REBUILD_REFIT_RANGE: its bound tree stays and takes new boxes.  prims / first / count / blas / nBlas mean what they mean for
  * rt_rebuild_scene.  Afterwards the scene is numbered the way the host appends BLAS after BLAS: the root of range k is the sum of the
  * node counts of ranges 0..k-1, its first index slot the sum of their slot counts.  A built range holds its builder's tree at that base.
  * A kept range holds its bound tree relocated, by one rule for the device (k_blas_relocate) and the host mirror (rth_rebuild_ranges;
@@ -410,11 +410,27 @@ int rt_rebuild_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t first, int32_
  * written to the set that is not live: they never alias); a segment that does not move at all - the static mesh in front of the moving
  * one - is a plain device-to-device copy, as the primIdx slots always are.  Then rt_rebuild_scene's pipeline runs unchanged over all
  * ranges: bvhIdx from the new roots, pair ids, the collapse of a BVH4 copy that keeps its BVH2, the derived records, TLAS::Build, the
- * layout check and the commit by pointer swap.  This first version does NOT relocate the derived records of a kept BLAS (pair, triangle
- * and quad records, refit topology): it derives them again over all ranges, which costs about what a refit of the scene costs; what a
- * kept BLAS saves is its build.  Afterwards every array rt_debug_get_scene_array returns, sizes included, and rt_kernel_info equal those
+ * layout check and the commit by pointer swap.
+ * RT_REBUILD_REFIT_RANGE refits one BLAS: its bound tree stays - node ids relative to its root, leaf ranges, primIdx - and is moved
+ * exactly as a kept one is; then its boxes are made anew from the primitives as they are after the replacement window, by
+ * rt_update_scene's rules: a leaf is the unclipped union of its primitives, an interior node the union of its children.  A refit SBVH
+ * tree therefore loses its clipped boxes, for that BLAS only: its neighbours keep theirs, which a refit of the whole scene does not
+ * offer.  The window may intersect refit and built ranges, never a kept one.
+ * The derived data of a kept or refit BLAS move as blocks too (BVH2 copies, both layouts): nothing walks such a tree.  Per BLAS the
+ * pair records move by one thread per 16-byte vector, the three box vectors copied and the two entries of the fourth patched by
+ * rebuild::relocated_entry (a leaf entry moves by the index offset, an interior one by the offset of the BLAS's run of pair ids); the
+ * run of pair id -> node id, the parent links and the run of leaves move by the node offset; a kept BLAS's triangle records are a
+ * device-to-device copy of its slot run, its instances' root entries host arithmetic; the shade records are copied and recomputed
+ * over the window only.  A refit BLAS then runs rt_update_scene's refit kernel over its own leaves, with the tickets of its own block
+ * zeroed, and rewrites its pair records' boxes and its triangle records.  Pair ids, the leaf list and the records of the built ranges
+ * alone are derived by rt_rebuild_scene's kernels.  A plan without a kept or refit range queues exactly what rt_rebuild_scene queues.
+ * (A BVH2 copy bound in layout 0 although its extend_variant admits layout 1 derives over all ranges, as a BVH4 copy does: the layout
+ * check needs every leaf's size.)  A BVH4 copy that keeps its BVH2 takes every word: its BVH2 blocks are relocated and refit as
+ * above, but its refit topology, the collapse, the quad records and the root entries are derived over all ranges; relocating
+ * collapsed records is out of scope.  rt_ranges_info reports what the last successful rt_rebuild_ranges of the scene copy queued.
+ * Afterwards every array rt_debug_get_scene_array returns, sizes included, and rt_kernel_info equal those
  * of a fresh upload of the host mirror's scene (rth_rebuild_ranges + rth_build_tlas).  stats as for a rebuild: blas_built counts the
- * ranges actually built, build_ms includes the relocation.
+ * ranges a builder built (neither kept nor refit ones), build_ms includes the relocation.
  * Which bound trees can be kept: a BLAS is compact when the nodes reachable from its root are exactly the ids [root, root + m), m odd,
  * and its leaves' primIdx ranges tile one interval without gap or overlap.  Everything BuildBLAS, the GPU builders, rt_rebuild_scene,
  * rt_rebuild_ranges and rt_resize_scene produce is compact; arbitrary arrays handed to rt_upload_scene may not be (found at upload).  A
@@ -426,17 +442,18 @@ int rt_rebuild_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t first, int32_
  * The builders' workspace is sized over the built ranges only.
  * Refusals change nothing (rt_rebuild_scene's guarantee):
  *   RT_E_INVALID      before any device work: a null plan; nRanges different from the scene's number of distinct BLAS; a plan word that
- *                     is none of the four; RT_REBUILD_REFIT in a plan (per-range refits are not offered: refit the whole scene with
- *                     rt_rebuild_scene); a replacement window [first, first + count), count > 0, that intersects a kept range (its boxes
+ *                     is none of the five; RT_REBUILD_REFIT in a plan (the per-range word is RT_REBUILD_REFIT_RANGE; the whole scene is
+ *                     refit with rt_rebuild_scene); a replacement window [first, first + count), count > 0, that intersects a kept range (its boxes
  *                     would go stale); everything rt_rebuild_scene answers with RT_E_INVALID; bad opts for a builder the plan uses;
- *   RT_E_UNSUPPORTED  RT_REBUILD_KEEP for a range that is not compact (the message names the range); everything rt_rebuild_scene
+ *   RT_E_UNSUPPORTED  RT_REBUILD_KEEP or RT_REBUILD_REFIT_RANGE for a range that is not compact (the message names the range); everything rt_rebuild_scene
  *                     refuses (a BVH4 copy without its BVH2, a layout change, ...);
  *   RT_E_NOMEM        as for rebuilds.
  * rt_rebuild_ranges_check runs the plan checks without a device against caller-given ranges: nBound ranges (rangeFirst / rangeCount, in
  * increasing order; compact NULL: all compact), the plan, the window, opts.  RT_OK, or the code and message rt_rebuild_ranges would give. */
 #define RT_REBUILD_KEEP  4   /* per-range plans only: the bound tree of this BLAS stays, moved to where the new scene numbers it */
+#define RT_REBUILD_REFIT_RANGE 5   /* per-range plans only: ... and its boxes are made anew from the primitives (rt_update_scene's rules) */
 int rt_rebuild_ranges(RtCtx* ctx, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
-                      const int32_t* plan, int32_t nRanges,   /* HOST: one of RT_REBUILD_SAH / LBVH / SBVH / KEEP per distinct BLAS */
+                      const int32_t* plan, int32_t nRanges,   /* HOST: one of RT_REBUILD_SAH / LBVH / SBVH / KEEP / REFIT_RANGE per distinct BLAS */
                       const RtBuildOptions* opts, RtRebuildStats* stats);
 int rt_scene_blas_blocks(RtCtx* ctx, int32_t* n, int32_t* primFirst, int32_t* primCount, int32_t* nodes, int32_t* idxSlots, int32_t* compact, int32_t cap);
 int rt_rebuild_ranges_check(int32_t nPrims, const int32_t* rangeFirst, const int32_t* rangeCount, const int32_t* compact, int32_t nBound,
@@ -556,6 +573,21 @@ int rt_materials_check(const RtMaterial* mats, int32_t nMats, int32_t nTexels);
  * when no scene is bound. */
 typedef struct RtRefitInfo { int32_t path, live_quads, changed_nodes, stack_need; } RtRefitInfo;
 int rt_refit_info(RtCtx* ctx, RtRefitInfo* out);
+/* The last successful rt_rebuild_ranges of the context's scene copy, counted from the arguments of the launches and copies it queued
+ * (all zero before any such call): ranges built / kept / refit; pair records derived (k_rb_pairs) and relocated; triangle-record slots
+ * derived (k_tri_recs) and relocated (copied); the nodes of the trees the breadth-first numbering walked; the leaves the refit kernel
+ * started from.  RT_E_INVALID for a null argument or when no scene is bound. */
+typedef struct RtRangesInfo {
+    int32_t built, kept, refit, pairs_derived, pairs_relocated, slots_derived, slots_relocated, nodes_numbered, leaves_refit, reserved[3];
+} RtRangesInfo;
+int rt_ranges_info(RtCtx* ctx, RtRangesInfo* out);
+/* Two device-free entries that pin the relocation rule of the derived pair records (no GPU, no context).  rt_debug_derive_pairs: the
+ * upload's own host derivation of layout 1 from wire arrays - pairs receives 4 RtFloat4 per interior node reachable (pairCap records of
+ * room), pairNode its node id, rootEntry every instance's entry (any may be NULL), *nPairs the count.  rt_debug_relocate_pairs:
+ * rebuild::relocated_entry applied to both entries of n records, everything else copied (in and out may be the same array). */
+int rt_debug_derive_pairs(const RtBVHNode2* nodes, int32_t nNodes, const RtBVHInstance* blas, int32_t nBlas, RtFloat4* pairs, uint32_t* pairNode,
+                          int32_t pairCap, uint32_t* rootEntry, int32_t* nPairs);
+int rt_debug_relocate_pairs(const RtFloat4* in, int32_t n, uint32_t pairDelta, uint32_t idxDelta, RtFloat4* out);
 /* Device allocations (hipMalloc calls) that rt_update_scene, rt_rebuild_scene, rt_resize_scene and rt_update_materials have made for the
  * context's scene copy so far, the SBVH builder's included: a test can see that a repeated rebuild has stopped allocating. */
 int rt_debug_rebuild_allocations(RtCtx* ctx, int64_t* count);

@@ -86,10 +86,11 @@ int rth_refit(RthScene* s);
  * ranges; whatever the builder refuses). */
 int rth_rebuild(RthScene* s, int builder, const RtBuildOptions* opts);
 /* The host restatement of rt_rebuild_ranges (rt355.h): rth_rebuild under a plan, plan[nRanges] with one RT_REBUILD_SAH / LBVH / SBVH /
- * KEEP per distinct BLAS in increasing order of the ranges.  A built BLAS is appended as rth_rebuild appends it; a kept one as its bound
- * block of nodes, relocated by the rule the device applies (csrc/rebuild_common.h, relocated_first), with its primIdx slots unchanged.
+ * KEEP / REFIT_RANGE per distinct BLAS in increasing order of the ranges.  A built BLAS is appended as rth_rebuild appends it; a kept one as
+ * its bound block of nodes, relocated by the rule the device applies (csrc/rebuild_common.h, relocated_first), with its primIdx slots
+ * unchanged; a refit one likewise, then its boxes are made anew from the scene's primitives by rth_refit's rules over that block alone.
  * Refused like rth_rebuild, and by rt_rebuild_ranges' plan rules: RT_E_INVALID for a null plan, a wrong nRanges, an unknown word or
- * RT_REBUILD_REFIT; RT_E_UNSUPPORTED for RT_REBUILD_KEEP of a BLAS that is not compact.  (The primitives a kept BLAS covers must not
+ * RT_REBUILD_REFIT; RT_E_UNSUPPORTED for RT_REBUILD_KEEP or RT_REBUILD_REFIT_RANGE of a BLAS that is not compact.  (The primitives a kept BLAS covers must not
  * have changed since it was built or refit: the host scene has no window to check that against.) */
 int rth_rebuild_ranges(RthScene* s, const int32_t* plan, int nRanges, const RtBuildOptions* opts);
 /* rt_blas_ranges (rt355.h) of the scene's arrays: the primitive range of every instance's BLAS; RT_E_UNSUPPORTED (rt_last_error() has

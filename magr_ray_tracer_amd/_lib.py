@@ -123,6 +123,10 @@ assert UpdateStats.itemsize == 40
 REBUILD_SAH, REBUILD_LBVH, REBUILD_SBVH = 0, 1, 2   # rt_rebuild_scene builders
 REBUILD_REFIT = 3                                   # ... and its refit: no builder runs (the device library only: rth_rebuild refuses it)
 REBUILD_KEEP = 4                                    # per-range plans only (rt_rebuild_ranges): the bound tree of that BLAS stays
+REBUILD_REFIT_RANGE = 5                             # per-range plans only: ... and its boxes are made anew from the primitives
+RANGES_INFO_FIELDS = ("built", "kept", "refit", "pairs_derived", "pairs_relocated", "slots_derived", "slots_relocated", "nodes_numbered", "leaves_refit")
+RangesInfo = np.dtype([(n, "<i4") for n in RANGES_INFO_FIELDS] + [("reserved", "<i4", 3)])   # RtRangesInfo
+assert RangesInfo.itemsize == 48
 RefitInfo = np.dtype([(n, "<i4") for n in ("path", "live_quads", "changed_nodes", "stack_need")])   # RtRefitInfo
 assert RefitInfo.itemsize == 16
 REFIT_NONE, REFIT_IN_PLACE, REFIT_RECOLLAPSED, REFIT_FORCED = 0, 1, 2, 3   # RtRefitInfo.path
@@ -145,7 +149,7 @@ DEVICE_SYMBOLS = [
     "rt_group_postproc", "rt_trace", "rt_trace_window", "rt_resize_scene", "rt_group_resize_scene", "rt_resize_check",
     "rt_update_materials", "rt_group_update_materials", "rt_materials_check",
     "rt_rebuild_ranges", "rt_group_rebuild_ranges", "rt_scene_blas_blocks", "rt_rebuild_ranges_check", "rt_blas_blocks",
-    "rt_debug_traversal_plan", "rt_debug_traversal_facts"]
+    "rt_debug_traversal_plan", "rt_debug_traversal_facts", "rt_ranges_info", "rt_debug_derive_pairs", "rt_debug_relocate_pairs"]
 HOST_SYMBOLS = [
     "rth_last_error", "rth_scene_create", "rth_scene_destroy", "rth_add_material", "rth_add_texture", "rth_load_texture", "rth_add_sphere",
     "rth_add_plane", "rth_add_triangle", "rth_add_quad", "rth_add_triangles", "rth_build_blas", "rth_build_bvh4",
@@ -275,6 +279,9 @@ def _bind_device(lib):
         lib.rt_group_update_materials.argtypes = [vp, vp, vp]
         lib.rt_materials_check.argtypes = [vp, i32, i32]
         lib.rt_refit_info.argtypes = [vp, vp]
+        lib.rt_ranges_info.argtypes = [vp, vp]
+        lib.rt_debug_derive_pairs.argtypes = [vp, i32, vp, i32, vp, vp, i32, vp, C.POINTER(i32)]
+        lib.rt_debug_relocate_pairs.argtypes = [vp, i32, C.c_uint32, C.c_uint32, vp]
         lib.rt_blas_ranges.argtypes = [vp, i32, vp, i32, i32, vp, i32, vp, vp]
         lib.rt_group_create.argtypes = [vp, i32, C.POINTER(vp)]
         lib.rt_group_destroy.argtypes = [vp]

@@ -24,6 +24,11 @@
 // rt_rebuild_ranges keeps the bound tree of a BLAS whose primitives did not change:
 //   k_blas_relocate one thread per 16-byte vector of a kept block of nodes: copied to where the new scene numbers it, the `first` word
 //                   of every record moved by the block's node or index offset (rebuild::relocated_first)
+// ... and moves what is derived from it, so that nothing walks a kept or refit tree:
+//   k_pairs_relocate one thread per 16-byte vector of the BLAS's run of pair records: the three box vectors copied, both entries of the
+//                   fourth moved by the index or the pair-id offset (rebuild::relocated_entry)
+//   k_ids_relocate  one thread per word of the BLAS's parent links, its run of pair id -> node id and its run of leaves: + the node
+//                   offset (kNone, a root's parent, stays)
 #include <algorithm>
 #include <cstddef>
 #include <hip/hip_runtime.h>
@@ -110,13 +115,14 @@ __global__ void __launch_bounds__(kBlock) k_rb_leaf_flag(const RtBVHNode2* nodes
     flags[i] = c > 0 ? 1u : 0u;
     if (c > kMaxPackedLeaf) atomicMax(&ctr[kLargestLeaf], c);   // a value, not a position
 }
+// (nodeBase: the id of node 0 of the nNodes flagged - 0 over a whole scene, a BLAS's root over its block)
 __global__ void __launch_bounds__(kBlock) k_rb_leaf_list(const uint32_t* flags, const uint32_t* ranks, uint32_t nNodes, uint32_t nLeaves,
-                                                         uint32_t* leaves, uint32_t* ctr)
+                                                         uint32_t nodeBase, uint32_t* leaves, uint32_t* ctr)
 {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= nNodes) return;
     if (i == nNodes - 1 && ranks[i] + flags[i] != nLeaves) atomicOr(&ctr[kStatus], kWalk);
-    if (flags[i] && ranks[i] < nLeaves) leaves[ranks[i]] = i;
+    if (flags[i] && ranks[i] < nLeaves) leaves[ranks[i]] = nodeBase + i;
 }
 
 __global__ void __launch_bounds__(kBlock) k_rb_roots(const RtBVHNode2* nodes, const RtBVHInstance* inst, uint32_t nInst, const uint32_t* newId,
@@ -171,11 +177,26 @@ hipError_t finish(hipStream_t s, const Work& w, const RtBVHNode2* nodes, uint32_
     size_t scanBytes = w.scanBytes;
     hipError_t e = hipcub::DeviceScan::ExclusiveSum(w.scan, scanBytes, w.flags, w.ranks, (int)nNodes, s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_rb_leaf_list, grid(nNodes), dim3(kBlock), 0, s, w.flags, w.ranks, nNodes, nLeaves, leaves, w.ctr);
+    hipLaunchKernelGGL(k_rb_leaf_list, grid(nNodes), dim3(kBlock), 0, s, w.flags, w.ranks, nNodes, nLeaves, 0u, leaves, w.ctr);
     if (pairs) {
         if (nPairs) hipLaunchKernelGGL(k_rb_pairs, grid(nPairs), dim3(kBlock), 0, s, nodes, pairNode, w.newId, nPairs, pairs);
         hipLaunchKernelGGL(k_rb_roots, grid(nInst), dim3(kBlock), 0, s, nodes, inst, nInst, w.newId, rootEntry);
     }
+    return hipGetLastError();
+}
+
+// One built BLAS among kept or refit ones: its leaves (node order) at their place in the leaf list, its pair records at its run of pair ids
+hipError_t finish_blas(hipStream_t s, const Work& w, const RtBVHNode2* nodes, uint32_t root, uint32_t nBlasNodes, uint32_t pairBase, uint32_t interiors,
+                       const uint32_t* pairNode, RtFloat4* pairs, uint32_t* leafRun)
+{
+    const uint32_t nLeaves = nBlasNodes - interiors;
+    hipLaunchKernelGGL(k_rb_leaf_flag, grid(nBlasNodes), dim3(kBlock), 0, s, nodes + root, nBlasNodes, w.flags, w.ctr);
+    size_t scanBytes = w.scanBytes;
+    hipError_t e = hipcub::DeviceScan::ExclusiveSum(w.scan, scanBytes, w.flags, w.ranks, (int)nBlasNodes, s);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_rb_leaf_list, grid(nBlasNodes), dim3(kBlock), 0, s, w.flags, w.ranks, nBlasNodes, nLeaves, root, leafRun, w.ctr);
+    if (pairs && interiors)
+        hipLaunchKernelGGL(k_rb_pairs, grid(interiors), dim3(kBlock), 0, s, nodes, pairNode + pairBase, w.newId, interiors, pairs + (size_t)pairBase * 4);
     return hipGetLastError();
 }
 
@@ -301,6 +322,53 @@ hipError_t relocate(hipStream_t s, const RtBVHNode2* src, RtBVHNode2* dst, uint3
     const uint32_t nVec = 3u * nNodes;
     const uint32_t blocks = std::min<uint32_t>((nVec + kBlock - 1) / kBlock, kRelocateMaxBlocks);
     hipLaunchKernelGGL(k_blas_relocate, dim3(blocks), dim3(kBlock), 0, s, reinterpret_cast<const uint4*>(src), reinterpret_cast<uint4*>(dst), nVec, nodeDelta, idxDelta);
+    return hipGetLastError();
+}
+
+// ---- ... and so does what is derived from it (rules: rebuild::relocated_entry; ids move by the node offset) ---------------------------------
+// A pair record is 64 bytes, four 16-byte vectors: three of boxes, then {entry, entry, 0, 0}.  One thread per VECTOR, grid-stride, as
+// k_blas_relocate: every load and every store of a wave covers 1 KiB of consecutive memory.  Every fourth vector gets both entries
+// patched; no LDS, no atomics.  src is the live array, dst the set that is not live: they never alias.
+__global__ void __launch_bounds__(kBlock) k_pairs_relocate(const uint4* __restrict__ src, uint4* __restrict__ dst, uint32_t nVec, uint32_t pairDelta,
+                                                           uint32_t idxDelta)
+{
+    const uint32_t stride = gridDim.x * kBlock;
+    for (uint32_t v = blockIdx.x * kBlock + threadIdx.x; v < nVec; v += stride) {
+        uint4 q = src[v];
+        if ((v & 3u) == 3u) { q.x = relocated_entry(q.x, pairDelta, idxDelta); q.y = relocated_entry(q.y, pairDelta, idxDelta); }
+        dst[v] = q;
+    }
+}
+hipError_t relocate_pairs(hipStream_t s, const RtFloat4* src, RtFloat4* dst, uint32_t nPairs, uint32_t pairDelta, uint32_t idxDelta)
+{
+    static_assert(sizeof(RtFloat4) == 16, "k_pairs_relocate's vectors");
+    if (nPairs == 0) return hipSuccess;
+    if (nPairs > 0x7fffffffu / 4u) return hipErrorInvalidValue;   // (4 * nPairs vectors are counted in 32 bits)
+    if (pairDelta == 0 && idxDelta == 0) return hipMemcpyAsync(dst, src, sizeof(RtFloat4) * 4 * (size_t)nPairs, hipMemcpyDeviceToDevice, s);
+    const uint32_t nVec = 4u * nPairs;
+    const uint32_t blocks = std::min<uint32_t>((nVec + kBlock - 1) / kBlock, kRelocateMaxBlocks);
+    hipLaunchKernelGGL(k_pairs_relocate, dim3(blocks), dim3(kBlock), 0, s, reinterpret_cast<const uint4*>(src), reinterpret_cast<uint4*>(dst), nVec, pairDelta, idxDelta);
+    return hipGetLastError();
+}
+// The three runs of node ids a BLAS owns, in one launch: thread i takes word i of the runs laid end to end (the run is wave-uniform
+// but for the two waves that straddle a boundary)
+struct IdRuns { const uint32_t* src[3]; uint32_t* dst[3]; uint32_t end[3]; };   // end: the running sum of the lengths
+__global__ void __launch_bounds__(kBlock) k_ids_relocate(IdRuns r, uint32_t nodeDelta)
+{
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= r.end[2]) return;
+    const int run = i < r.end[0] ? 0 : i < r.end[1] ? 1 : 2;
+    const uint32_t at = i - (run == 0 ? 0u : r.end[run - 1]);
+    const uint32_t v = r.src[run][at];
+    r.dst[run][at] = v == kNone ? kNone : v + nodeDelta;
+}
+hipError_t relocate_ids(hipStream_t s, const uint32_t* parentSrc, uint32_t* parentDst, uint32_t nNodes, const uint32_t* pairNodeSrc, uint32_t* pairNodeDst,
+                        uint32_t nPairs, const uint32_t* leavesSrc, uint32_t* leavesDst, uint32_t nLeaves, uint32_t nodeDelta)
+{
+    if ((uint64_t)nNodes + nPairs + nLeaves > 0x7fffffffull) return hipErrorInvalidValue;
+    IdRuns r{ { parentSrc, pairNodeSrc, leavesSrc }, { parentDst, pairNodeDst, leavesDst }, { nNodes, nNodes + nPairs, nNodes + nPairs + nLeaves } };
+    if (r.end[2] == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_ids_relocate, grid(r.end[2]), dim3(kBlock), 0, s, r, nodeDelta);
     return hipGetLastError();
 }
 

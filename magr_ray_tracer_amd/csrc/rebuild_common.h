@@ -154,6 +154,16 @@ LB_HD uint32_t relocated_first(uint32_t first, uint32_t count, uint32_t nodeDelt
 {
     return first + (count == 0 ? nodeDelta : idxDelta);
 }
+// ... and the same for the derived pair record of a kept or refit BLAS (k_pairs_relocate, rt_debug_relocate_pairs): one of the two
+// entries of its fourth vector.  A leaf entry (leaf bit set) adds idxDelta to its 24-bit slot field, an interior entry adds pairDelta =
+// newPairBase - oldPairBase to its pair id (both modulo 2^32).  No carry leaves the slot field: the bound entry's slot lies below the
+// bound nIdx, the moved one below the new nIdx, and both scenes passed the layout check (takes_layout1: nIdx < kMaxPackedIdx), so the
+// sum modulo 2^24 is the new slot itself and the count and leaf bits above it stay.
+LB_HD uint32_t relocated_entry(uint32_t entry, uint32_t pairDelta, uint32_t idxDelta)
+{
+    if (entry & refit::kLeafBit) return (entry & ~refit::kLeafFirstMask) | ((entry + idxDelta) & refit::kLeafFirstMask);
+    return entry + pairDelta;
+}
 // The block of every range of a scene find_blas_ranges has accepted (it checked every index followed here and that no node is reachable
 // twice).  A range that is not compact reports the nodes and slots it reaches; naming it RT_REBUILD_KEEP is refused.
 inline void find_blas_blocks(const RtBVHNode2* n, const std::vector<BlasRange>& ranges, std::vector<BlasBlock>& blocks)
@@ -179,6 +189,7 @@ inline void find_blas_blocks(const RtBVHNode2* n, const std::vector<BlasRange>& 
                                (uint8_t)(lo == root && hi - lo + 1 == m && (m & 1u) && tiles && slots <= 0x7fffffffu ? 1 : 0), height };
     }
 }
+// (The replacement window may intersect built and refit ranges: a refit range takes its boxes from the primitives as they are afterwards.)
 // The checks of a plan (one RT_REBUILD_* word per range) against the ranges it is for, the blocks where they are known (NULL: every
 // range counts as compact) and the replacement window [first, first + count): RT_OK, or RT_E_INVALID / RT_E_UNSUPPORTED with msg.
 inline int check_plan(const int32_t* plan, int32_t nRanges, const std::vector<BlasRange>& ranges, const BlasBlock* blocks, int32_t first, int32_t count,
@@ -190,8 +201,11 @@ inline int check_plan(const int32_t* plan, int32_t nRanges, const std::vector<Bl
         return RT_E_INVALID;
     }
     for (int32_t k = 0; k < nRanges; k++) {
-        if (plan[k] == RT_REBUILD_REFIT) { msg = "plan[" + std::to_string(k) + "]: RT_REBUILD_REFIT is not a per-range plan (refit the whole scene with rt_rebuild_scene)"; return RT_E_INVALID; }
-        if (plan[k] != RT_REBUILD_SAH && plan[k] != RT_REBUILD_LBVH && plan[k] != RT_REBUILD_SBVH && plan[k] != RT_REBUILD_KEEP) {
+        if (plan[k] == RT_REBUILD_REFIT) {
+            msg = "plan[" + std::to_string(k) + "]: RT_REBUILD_REFIT is not a per-range plan (refit one BLAS with RT_REBUILD_REFIT_RANGE, the whole scene with rt_rebuild_scene)";
+            return RT_E_INVALID;
+        }
+        if (plan[k] != RT_REBUILD_SAH && plan[k] != RT_REBUILD_LBVH && plan[k] != RT_REBUILD_SBVH && plan[k] != RT_REBUILD_KEEP && plan[k] != RT_REBUILD_REFIT_RANGE) {
             msg = "plan[" + std::to_string(k) + "]: unknown word " + std::to_string(plan[k]);
             return RT_E_INVALID;
         }
@@ -206,10 +220,10 @@ inline int check_plan(const int32_t* plan, int32_t nRanges, const std::vector<Bl
             return RT_E_INVALID;
         }
     }
-    for (int32_t k = 0; k < nRanges; k++) {
-        if (plan[k] != RT_REBUILD_KEEP || !blocks || blocks[k].compact) continue;
+    for (int32_t k = 0; k < nRanges; k++) {   // a kept and a refit tree alike move as a block
+        if ((plan[k] != RT_REBUILD_KEEP && plan[k] != RT_REBUILD_REFIT_RANGE) || !blocks || blocks[k].compact) continue;
         const BlasRange& r = ranges[(size_t)k];
-        msg = "RT_REBUILD_KEEP for BLAS " + std::to_string(k) + " (primitives [" + std::to_string(r.first) + ", " + std::to_string((uint64_t)r.first + r.count) +
+        msg = std::string(plan[k] == RT_REBUILD_KEEP ? "RT_REBUILD_KEEP" : "RT_REBUILD_REFIT_RANGE") + " for BLAS " + std::to_string(k) + " (primitives [" + std::to_string(r.first) + ", " + std::to_string((uint64_t)r.first + r.count) +
               ")): its bound tree is not compact (its nodes are not exactly the ids [root, root + nodes), or its leaves do not tile one primIdx interval); build it instead";
         return RT_E_UNSUPPORTED;
     }

@@ -57,5 +57,15 @@ hipError_t mat_assign(hipStream_t s, RtPrimitive* prims, const int32_t* assign, 
 // uploading a segment table and searching it in every thread, and the deltas stay wave-uniform kernel arguments.  Both deltas zero (the
 // static mesh in front of the moving one): a plain device-to-device copy.
 hipError_t relocate(hipStream_t s, const RtBVHNode2* src, RtBVHNode2* dst, uint32_t nNodes, uint32_t nodeDelta, uint32_t idxDelta);
+// ... and what is derived from it.  relocate_pairs: the BLAS's run of nPairs pair records, src of the live array to dst of the set that is
+// not live, the entries moved by rebuild::relocated_entry (both deltas zero: a plain copy).  relocate_ids: its parent links (nNodes
+// words), its run of pair id -> node id (nPairs words; 0 in layout 0) and its run of leaves, every id + nodeDelta, kNone kept.
+hipError_t relocate_pairs(hipStream_t s, const RtFloat4* src, RtFloat4* dst, uint32_t nPairs, uint32_t pairDelta, uint32_t idxDelta);
+hipError_t relocate_ids(hipStream_t s, const uint32_t* parentSrc, uint32_t* parentDst, uint32_t nNodes, const uint32_t* pairNodeSrc, uint32_t* pairNodeDst,
+                        uint32_t nPairs, const uint32_t* leavesSrc, uint32_t* leavesDst, uint32_t nLeaves, uint32_t nodeDelta);
+// finish() for one built BLAS beside kept or refit ones: the leaves of the block [root, root + nBlasNodes) in node order into leafRun
+// (its place in the leaf list), and (pairs != NULL) its `interiors` pair records from pair id pairBase on; number_blas has run for it
+hipError_t finish_blas(hipStream_t s, const Work& w, const RtBVHNode2* nodes, uint32_t root, uint32_t nBlasNodes, uint32_t pairBase, uint32_t interiors,
+                       const uint32_t* pairNode, RtFloat4* pairs, uint32_t* leafRun);
 
 } // namespace rebuilddev

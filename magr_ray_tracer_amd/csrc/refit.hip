@@ -178,6 +178,25 @@ hipError_t launch_refit(hipStream_t s, RtBVHNode2* nodes, uint32_t nNodes, const
     hipLaunchKernelGGL(k_refit_nodes, grid(nLeaves), dim3(kBlock), 0, s, nodes, prims, primIdx, leaves, nLeaves, parent, tickets);
     return hipGetLastError();
 }
+// One BLAS of a scene (RT_REBUILD_REFIT_RANGE): the tickets of its block [root, root + nBlasNodes) alone are zeroed, the kernel starts
+// from its own run of leaves and climbs until parent == kNone, which is its root's
+hipError_t launch_refit_blas(hipStream_t s, RtBVHNode2* nodes, uint32_t root, uint32_t nBlasNodes, const RtPrimitive* prims, const uint32_t* primIdx,
+                             const uint32_t* leafRun, uint32_t nLeaves, const uint32_t* parent, uint32_t* tickets)
+{
+    hipError_t e = hipMemsetAsync(tickets + root, 0, sizeof(uint32_t) * nBlasNodes, s);
+    if (e != hipSuccess || nLeaves == 0) return e;
+    hipLaunchKernelGGL(k_refit_nodes, grid(nLeaves), dim3(kBlock), 0, s, nodes, prims, primIdx, leafRun, nLeaves, parent, tickets);
+    return hipGetLastError();
+}
+// ... then the boxes of its run of pair records (pairNode / pairs: at the run's start) and the triangle records of its slot run
+// (primIdx / triRecs: at the run's start); either may be NULL
+hipError_t launch_blas_records(hipStream_t s, const RtPrimitive* prims, const RtBVHNode2* nodes, const uint32_t* pairNode, uint32_t nPairs, RtFloat4* pairs,
+                               const uint32_t* primIdx, uint32_t nSlots, RtFloat4* triRecs)
+{
+    if (pairs && nPairs) hipLaunchKernelGGL(k_pair_boxes, grid(nPairs), dim3(kBlock), 0, s, nodes, pairNode, nPairs, pairs);
+    if (triRecs && nSlots) hipLaunchKernelGGL(k_tri_recs, grid(nSlots), dim3(kBlock), 0, s, prims, primIdx, nSlots, triRecs);
+    return hipGetLastError();
+}
 hipError_t launch_tlas(hipStream_t s, const RtBVHNode2* nodes, const RtBVHInstance* inst, int n, const uint32_t* rootEntry,
                        RtTLASNode* tlas, RtFloat4* tp, RtFloat4* tpP, RtFloat4* ir, int32_t* status)
 {

@@ -742,6 +742,13 @@ extern "C" int rt_refit_info(RtCtx* ctx, RtRefitInfo* out)
     *out = ctx->scene->refitInfo;
     return RT_OK;
 }
+extern "C" int rt_ranges_info(RtCtx* ctx, RtRangesInfo* out)
+{
+    if (!ctx || !out) return fail(RT_E_INVALID, "rt_ranges_info: null argument");
+    if (const int rc = bound_scene(ctx, "rt_ranges_info")) return rc;
+    *out = ctx->scene->rangesInfo;
+    return RT_OK;
+}
 extern "C" int rt_debug_rebuild_allocations(RtCtx* ctx, int64_t* count)
 {
     if (!ctx || !count) return fail(RT_E_INVALID, "rt_debug_rebuild_allocations: null argument");

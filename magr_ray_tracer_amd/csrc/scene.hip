@@ -146,7 +146,19 @@ static int prepare_update(SceneBag& b, int accel, int extendVariant, const HostS
     b.rebuildRefusal = rebuild::find_blas_ranges((const RtBVHNode2*)bvhNodes, nNodes, primIdx, nIdx, nPrims, blas, nBlas, b.ranges, b.instBlas);
     // ... and what it occupies: nodes, index slots, height, and whether it can be kept (rt_rebuild_ranges); build_topology has walked
     // the trees: no cycle
-    if (!b.rebuildRefusal) rebuild::find_blas_blocks((const RtBVHNode2*)bvhNodes, b.ranges, b.blasBlock);
+    if (!b.rebuildRefusal) {
+        rebuild::find_blas_blocks((const RtBVHNode2*)bvhNodes, b.ranges, b.blasBlock);
+        // where each BLAS's pair ids (pair_records) and leaves (build_topology) lie: both go root by root as the instances first name them
+        b.blasPairLo.assign(b.ranges.size(), 0u); b.blasLeafLo.assign(b.ranges.size(), 0u);
+        std::vector<uint8_t> named(b.ranges.size(), 0);
+        uint32_t pairLo = 0, leafLo = 0;
+        for (const int32_t k : b.instBlas) {
+            if (named[(size_t)k]) continue;
+            named[(size_t)k] = 1;
+            b.blasPairLo[(size_t)k] = pairLo; b.blasLeafLo[(size_t)k] = leafLo;
+            pairLo += b.blas_interiors((size_t)k); leafLo += b.blas_interiors((size_t)k) + 1;
+        }
+    }
     b.nLeaves = (uint32_t)t.leaves.size(); b.nReach = (uint32_t)t.order.size();
     int rc = dalloc(b.allocs, &b.dParent, t.parent.size());
     if (rc == RT_OK) rc = dalloc(b.allocs, &b.dLeaves, t.leaves.size());
@@ -213,6 +225,33 @@ static std::vector<RtFloat4> pair_records(const RtBVHNode2* n2, int32_t nNodes, 
     for (size_t k = 0; k < order.size(); k++) rebuild::pair_record(n2, order[k], newId.data(), &pairs[k * 4]);   // (k_pair_boxes rewrites the boxes)
     for (int32_t b = 0; b < nBlas; b++) roots[(size_t)b] = rebuild::child_entry(n2[blas[b].bvhIdx], newId[blas[b].bvhIdx]);
     return pairs;
+}
+// The two device-free entries that pin the relocation of pair records (include/rt355.h)
+extern "C" int rt_debug_derive_pairs(const RtBVHNode2* nodes, int32_t nNodes, const RtBVHInstance* blas, int32_t nBlas, RtFloat4* pairs, uint32_t* pairNode,
+                                     int32_t pairCap, uint32_t* rootEntry, int32_t* nPairs)
+{
+    if (!nodes || !blas || nNodes <= 0 || nBlas <= 0 || !nPairs) return fail(RT_E_INVALID, "rt_debug_derive_pairs: null argument");
+    refit::Topology t;   // (checks every index pair_records follows)
+    if (const char* why = refit::build_topology(nodes, nNodes, blas, nBlas, t)) return fail(RT_E_INVALID, "rt_debug_derive_pairs: %s", why);
+    std::vector<uint32_t> order, roots((size_t)nBlas, 0u);
+    const std::vector<RtFloat4> recs = pair_records(nodes, nNodes, blas, nBlas, order, roots);
+    *nPairs = (int32_t)order.size();
+    if ((pairs || pairNode) && (int64_t)order.size() > (int64_t)pairCap) return fail(RT_E_INVALID, "rt_debug_derive_pairs: %zu pair records, room for %d", order.size(), pairCap);
+    if (pairs) std::copy(recs.begin(), recs.begin() + (ptrdiff_t)order.size() * 4, pairs);
+    if (pairNode) std::copy(order.begin(), order.end(), pairNode);
+    if (rootEntry) std::copy(roots.begin(), roots.end(), rootEntry);
+    return RT_OK;
+}
+extern "C" int rt_debug_relocate_pairs(const RtFloat4* in, int32_t n, uint32_t pairDelta, uint32_t idxDelta, RtFloat4* out)
+{
+    if (n < 0 || (n > 0 && (!in || !out))) return fail(RT_E_INVALID, "rt_debug_relocate_pairs: null argument");
+    for (int32_t k = 0; k < n; k++) {
+        for (int w = 0; w < 3; w++) out[(size_t)k * 4 + w] = in[(size_t)k * 4 + w];
+        const RtFloat4 q = in[(size_t)k * 4 + 3];
+        out[(size_t)k * 4 + 3] = refit::f4(refit::u2f(rebuild::relocated_entry(refit::f2u(q.x), pairDelta, idxDelta)),
+                                           refit::u2f(rebuild::relocated_entry(refit::f2u(q.y), pairDelta, idxDelta)), q.z, q.w);
+    }
+    return RT_OK;
 }
 // Layout 1 of a BVH4: four child boxes + four encoded child entries per node.  The collapse (bvh.cpp:695-803) leaves the absorbed BVH2
 // nodes in the array: only the nodes still reachable from a BLAS root are kept (on the bench scene 1 node in 4 is alive).

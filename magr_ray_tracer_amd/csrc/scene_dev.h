@@ -40,6 +40,10 @@ template <class T> static int dalloc(std::vector<void*>& bag, T** p, size_t coun
 namespace refitdev {   // refit.hip's kernels (rules: refit_common.h)
 hipError_t launch_refit(hipStream_t s, RtBVHNode2* nodes, uint32_t nNodes, const RtPrimitive* prims, const uint32_t* primIdx, const uint32_t* leaves,
                         uint32_t nLeaves, const uint32_t* parent, uint32_t* tickets);
+hipError_t launch_refit_blas(hipStream_t s, RtBVHNode2* nodes, uint32_t root, uint32_t nBlasNodes, const RtPrimitive* prims, const uint32_t* primIdx,
+                             const uint32_t* leafRun, uint32_t nLeaves, const uint32_t* parent, uint32_t* tickets);
+hipError_t launch_blas_records(hipStream_t s, const RtPrimitive* prims, const RtBVHNode2* nodes, const uint32_t* pairNode, uint32_t nPairs, RtFloat4* pairs,
+                               const uint32_t* primIdx, uint32_t nSlots, RtFloat4* triRecs);
 hipError_t launch_tlas(hipStream_t s, const RtBVHNode2* nodes, const RtBVHInstance* inst, int n, const uint32_t* rootEntry, RtTLASNode* tlas, RtFloat4* tp,
                        RtFloat4* tpP, RtFloat4* ir, int32_t* status);
 hipError_t launch_records(hipStream_t s, const RtPrimitive* prims, const RtBVHNode2* nodes, const uint32_t* primIdx, uint32_t nIdx, const uint32_t* lights,
@@ -106,6 +110,12 @@ struct SceneBag {
     // at upload, reported by the builders at a rebuild; a refit leaves them.
     std::vector<rebuild::BlasBlock> blasBlock;
     uint32_t blas_interiors(size_t k) const { return (blasBlock[k].nodes - 1) / 2; }   // interior nodes of BLAS k
+    // ... and beside it where the derived data of BLAS k lie: the start of its run of pair ids (interiors of them; BLAS by BLAS in the order
+    // in which the instances first name them) and the start of its run in the leaf list (interiors + 1 of them; after an upload the
+    // runs come in that same order, after a rebuild in range order - the order inside a run is no contract).  Written at upload and by
+    // every commit that moves a tree; rt_rebuild_ranges moves a kept or refit BLAS's derived data by them.
+    std::vector<uint32_t> blasPairLo, blasLeafLo;
+    RtRangesInfo rangesInfo{};                // the last successful rt_rebuild_ranges (rt_ranges_info)
     // The live collapse of a BVH4 copy that keeps its BVH2: node -> live id and live id -> node (the upload's own arrays or the live
     // set's, never scratch: a refused call in between must leave them), the live nodes and the stack need as the collapse counted it
     uint32_t *liveNewId = nullptr, *liveQuadNode = nullptr;
@@ -180,7 +190,7 @@ int upload_scene(SceneBag& b, int accel, int extendVariant, const HostScene& in,
 int update_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas, RtUpdateStats* stats);
 int rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
                   int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats);
-// rt_rebuild_ranges (include/rt355.h): plan[nRanges], one RT_REBUILD_SAH / LBVH / SBVH / KEEP per distinct BLAS in the order of b.ranges
+// rt_rebuild_ranges (include/rt355.h): plan[nRanges], one RT_REBUILD_SAH / LBVH / SBVH / KEEP / REFIT_RANGE per distinct BLAS in the order of b.ranges
 int rebuild_ranges(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
                    const int32_t* plan, int32_t nRanges, const RtBuildOptions* opts, RtRebuildStats* stats);
 // rt_scene_blas_blocks: the ranges and blocks of the bound trees (any output may be NULL; at most cap entries are written)

@@ -190,8 +190,8 @@ static int check_builder(const char* who, int32_t builder, const RtBuildOptions*
     if (!(alpha >= 0.0f && alpha <= 1.0f)) return fail(RT_E_INVALID, "%s: alpha must lie in [0, 1]", who);
     return RT_OK;
 }
-// The builders' own argument checks, BLAS by BLAS under plan[k], one RT_REBUILD_SAH / LBVH / SBVH / KEEP per range (node and index ids as
-// the host appends BLAS after BLAS: a kept BLAS takes its block's - blocks NULL: a SAH tree's at most - and the ids behind an SBVH tree
+// The builders' own argument checks, BLAS by BLAS under plan[k], one RT_REBUILD_SAH / LBVH / SBVH / KEEP / REFIT_RANGE per range (node and index
+// ids as the host appends BLAS after BLAS: a kept or refit BLAS takes its block's - blocks NULL: a SAH tree's at most - and the ids behind an SBVH tree
 // are known only as the trees are built: its ranges hold at most 2^30 primitives each, and alpha is checked by check_builder)
 static int check_ranges(const char* who, const int32_t* plan, const RtBuildOptions* opts, int32_t nPrims, const std::vector<rebuild::BlasRange>& ranges,
                         const rebuild::BlasBlock* blocks, lbvh::Params& P)
@@ -225,7 +225,8 @@ static int check_plan_alpha(const char* who, const int32_t* plan, size_t n, cons
 // replacement records prims / first / count and blas as rt_update_scene does; a resize builds the caller's shape over newPrims (host or
 // device memory, sh.nPrims records), blas (NULL: identity) carrying the transforms.  plan[k] says what becomes of range k: built with
 // RT_REBUILD_SAH / LBVH / SBVH, or (RT_REBUILD_KEEP, a rebuild of a compact bound tree only) its bound tree moved to where the new scene
-// numbers it; an empty plan is RT_REBUILD_REFIT of the whole scene (no builder runs, opts is ignored).
+// numbers it, or (RT_REBUILD_REFIT_RANGE, likewise) moved and then given new boxes; an empty plan is RT_REBUILD_REFIT of the whole scene
+// (no builder runs, opts is ignored).  perRange: the call is rt_rebuild_ranges (rt_ranges_info describes it).
 namespace {
 struct Request {
     const char* who;
@@ -236,6 +237,7 @@ struct Request {
     std::vector<int32_t> plan;
     const RtBuildOptions* opts;
     lbvh::Params P;
+    bool perRange = false;
 };
 // One call: what it has built in the set that is not live and what it has read back of it - everything commit needs -, and the phases
 // that build it, in the order rebuild_body calls them
@@ -256,6 +258,16 @@ struct Pending {
     void commit();               // 6. host memory only
     struct KeptSegment { uint32_t srcNode = 0, dstNode = 0, nNodes = 0, nodeDelta = 0, srcIdx = 0, dstIdx = 0, nIdx = 0, idxDelta = 0; };
     int stage_resize(), stage_rebuild(), refit_trees(), flush_kept(KeptSegment& seg), keep_tree(size_t k, KeptSegment& seg), build_tree(size_t k);
+    int derive_ids(), derive_records();
+    // range k keeps its bound tree as a block: kept, or refit (new boxes afterwards)
+    bool refits(size_t k) const { return !refit && rq.plan[k] == RT_REBUILD_REFIT_RANGE; }
+    bool moves(size_t k) const { return !refit && (rq.plan[k] == RT_REBUILD_KEEP || rq.plan[k] == RT_REBUILD_REFIT_RANGE); }
+    // A BVH2 copy with a block that moves takes the derived data of such blocks from the bound arrays and derives the built ranges'
+    // alone.  (Not a copy bound in layout 0 that could take layout 1: the layout check needs every leaf's size, which only the leaf scan
+    // over all ranges gives.  Not a BVH4 copy: its collapse is derived over all ranges.)
+    bool blockwise = false;
+    std::vector<uint32_t> pairLo, leafLo, hostRoots;   // per range: its run of pair ids, its run of leaves; per instance: its root entry
+    RtRangesInfo info{};                                // counted as the launches are queued
 
     using clock = std::chrono::steady_clock;
     clock::time_point t0 = clock::now(), t1, t2, t3;   // the call, staged, trees built, read back
@@ -294,11 +306,11 @@ struct Pending {
 // 1. Size: room in the set that is not live for what the plan is known to need, and the builders' workspace
 int Pending::size()
 {
-    // a kept tree needs its block, a SAH or LBVH tree count slots and 2 * count - 1 nodes at most (an SBVH tree is sized when it is
+    // a kept or refit tree needs its block, a SAH or LBVH tree count slots and 2 * count - 1 nodes at most (an SBVH tree is sized when it is
     // built: size, then place)
     restIdx.assign(nR + 1, 0); restNodes.assign(nR + 1, 0);
     for (size_t k = nR; k-- > 0 && !refit;) {
-        const bool keep = rq.plan[k] == RT_REBUILD_KEEP, known = keep || rq.plan[k] != RT_REBUILD_SBVH;
+        const bool keep = moves(k), known = keep || rq.plan[k] != RT_REBUILD_SBVH;
         restIdx[k] = restIdx[k + 1] + (keep ? b.blasBlock[k].idxSlots : known ? ranges[k].count : 0u);
         restNodes[k] = restNodes[k + 1] + (keep ? b.blasBlock[k].nodes : known ? 2 * (size_t)ranges[k].count - 1 : 0u);
         anyKnown = anyKnown || known;
@@ -368,7 +380,7 @@ int Pending::stage_rebuild()
     return RT_OK;
 }
 
-// 3. The trees, in the order of the ranges.  A refit: the bound trees and their refit topology into the set, then the boxes anew: no BLAS
+// 3. The trees, in the order of the ranges.  A refit of the whole scene: the bound trees and their refit topology into the set, then the boxes anew: no BLAS
 // is built, so node ids, leaf ranges, primIdx and pair ids stay
 int Pending::refit_trees()
 {
@@ -398,7 +410,8 @@ int Pending::flush_kept(KeptSegment& seg)
     seg = KeptSegment{};
     return RT_OK;
 }
-// range k keeps its bound tree (room: reserved by size(); the bound values stand for the builder's)
+// range k keeps its bound tree, to stay as it is or to be refit once its leaves and parent links are in the set (derive): room is
+// reserved by size(); the bound values stand for the builder's
 int Pending::keep_tree(size_t k, KeptSegment& seg)
 {
     const rebuild::BlasBlock& blk = b.blasBlock[k];
@@ -410,6 +423,7 @@ int Pending::keep_tree(size_t k, KeptSegment& seg)
         seg = KeptSegment{ root, nNodes, blk.nodes, nodeDelta, blk.idxLo, nIdx, blk.idxSlots, idxDelta };
     }
     place(k, blk.nodes, blk.height, blk.idxSlots);
+    if (!refits(k)) info.kept++;
     return RT_OK;
 }
 // range k is built by plan[k], behind the trees placed so far
@@ -459,7 +473,7 @@ int Pending::trees()
     } else {
         KeptSegment seg;
         for (size_t k = 0; k < nR; k++) {
-            if (rq.plan[k] == RT_REBUILD_KEEP) { if (const int rc = keep_tree(k, seg)) return rc; continue; }
+            if (moves(k)) { if (const int rc = keep_tree(k, seg)) return rc; blockwise = !bvh4 && (layout1 || !b.variantLayout1); continue; }
             if (const int rc = flush_kept(seg)) return rc;
             if (const int rc = build_tree(k)) return rc;
         }
@@ -489,15 +503,7 @@ int Pending::derive()
             HIPCHK(hipMemcpyAsync(t.pairs.p, sc.pairs, sizeof(RtFloat4) * 4 * std::max<size_t>(nPairs, 1), hipMemcpyDeviceToDevice, s));
             HIPCHK(hipMemcpyAsync(t.rootEntry.p, sc.rootEntry, sizeof(uint32_t) * (size_t)b.nBlas, hipMemcpyDeviceToDevice, s));
         }
-    } else {   // pair ids: BLAS by BLAS in the order in which the instances first name them
-        HIPCHK(rebuilddev::begin(s, b.dw, t.parent.p, nNodes));
-        for (const size_t k : order) {
-            HIPCHK(rebuilddev::number_blas(s, b.dw, t.nodes.p, nNodes, rootOf[k], interiors[k], depth[k], nPairs, (uint32_t)t.pairNode.cap, t.pairNode.p, t.parent.p));
-            nPairs += interiors[k];
-        }
-        HIPCHK(rebuilddev::finish(s, b.dw, t.nodes.p, nNodes, nPairs, nNodes - nPairs, t.blas.p, (uint32_t)sh.nBlas, t.pairNode.p, layout1 && !bvh4 ? t.pairs.p : nullptr,
-                                  t.rootEntry.p, t.leaves.p));
-    }
+    } else if (const int rc = derive_ids()) return rc;
     if (layout1 && !bvh4 && nPairs == 0) HIPCHK(hipMemsetAsync(t.pairs.p, 0, sizeof(RtFloat4) * 4, s));   // no interior node: one zero record, as at upload
     nLeaves = refit ? b.nLeaves : nNodes - nPairs;
     refitPath = refit ? 1 : 0;
@@ -523,13 +529,97 @@ int Pending::derive()
         HIPCHK(collapsedev::finish(s, w, t.bvh4.p, nNodes, nIdx, (const uint32_t*)t.blas.p, (uint32_t)(sizeof(RtBVHInstance) / 4), (uint32_t)sh.nBlas,
                                    layout1 ? t.quads.p : nullptr, t.rootEntry.p));
     }
-    const bool boxes = refit && layout1 && !bvh4;
-    HIPCHK(refitdev::launch_records(s, t.prims.p, t.nodes.p, t.primIdx.p, nIdx, lights, (uint32_t)nLights, 0u, (uint32_t)sh.nPrims,
-                                    boxes ? t.pairNode.p : nullptr, boxes ? nPairs : 0u, boxes ? t.pairs.p : nullptr, layout1 ? t.triRecs.p : nullptr,
-                                    t.shadeRecs.p, t.lightRecs.p));
+    if (const int rc = derive_records()) return rc;
     HIPCHK(hipEventRecord(b.rev[2], s));
     HIPCHK(refitdev::launch_tlas(s, t.nodes.p, t.blas.p, sh.nBlas, layout1 ? t.rootEntry.p : nullptr, t.tlas.p, t.tp.p, t.tpP.p, t.ir.p, b.rStatus));
     HIPCHK(hipEventRecord(b.rev[3], s));
+    return RT_OK;
+}
+
+// The pair ids, the refit topology and the pair records of a call that is no whole-scene refit.  Pair ids go BLAS by BLAS in the order in
+// which the instances first name them, the leaf list range by range (node order).  Without a block that moves (rt_rebuild_scene,
+// rt_resize_scene, an all-built plan) and on the copies `blockwise` leaves out: number every BLAS, then one finish over all ranges.
+// Otherwise a BLAS that moves has its runs taken from the bound arrays by the offsets of its block, a built one is numbered and finished
+// on its own, and the root entries are host arithmetic.  Then the refit ranges' boxes, once their leaves and parent links are in the set.
+int Pending::derive_ids()
+{
+    const SceneArrays& sc = b.sc;
+    hipStream_t s = b.stream;
+    RtFloat4* const pairs = layout1 && !bvh4 ? t.pairs.p : nullptr;
+    pairLo.assign(nR, 0u); leafLo.assign(nR, 0u);
+    for (size_t k = 0, at = 0; k < nR; k++) { leafLo[k] = (uint32_t)at; at += interiors[k] + 1; }
+    HIPCHK(rebuilddev::begin(s, b.dw, t.parent.p, nNodes));
+    for (const size_t k : order) {
+        const uint32_t m = 2 * interiors[k] + 1;
+        pairLo[k] = nPairs;
+        if (blockwise && moves(k)) {
+            const uint32_t oldRoot = b.ranges[k].root, oldPair = b.blasPairLo[k];
+            HIPCHK(rebuilddev::relocate_ids(s, b.dParent + oldRoot, t.parent.p + rootOf[k], m, b.dPairNode + oldPair, t.pairNode.p + nPairs, pairs ? interiors[k] : 0u,
+                                            b.dLeaves + b.blasLeafLo[k], t.leaves.p + leafLo[k], interiors[k] + 1, rootOf[k] - oldRoot));
+            if (pairs) {
+                HIPCHK(rebuilddev::relocate_pairs(s, sc.pairs + (size_t)oldPair * 4, pairs + (size_t)nPairs * 4, interiors[k], nPairs - oldPair, idxOf[k] - b.blasBlock[k].idxLo));
+                info.pairs_relocated += (int32_t)interiors[k];
+            }
+        } else {
+            HIPCHK(rebuilddev::number_blas(s, b.dw, t.nodes.p, nNodes, rootOf[k], interiors[k], depth[k], nPairs, (uint32_t)t.pairNode.cap, t.pairNode.p, t.parent.p));
+            info.nodes_numbered += (int32_t)m;
+            if (blockwise) {
+                HIPCHK(rebuilddev::finish_blas(s, b.dw, t.nodes.p, rootOf[k], m, nPairs, interiors[k], t.pairNode.p, pairs, t.leaves.p + leafLo[k]));
+                if (pairs) info.pairs_derived += (int32_t)interiors[k];
+            }
+        }
+        nPairs += interiors[k];
+    }
+    if (!blockwise) {
+        HIPCHK(rebuilddev::finish(s, b.dw, t.nodes.p, nNodes, nPairs, nNodes - nPairs, t.blas.p, (uint32_t)sh.nBlas, t.pairNode.p, pairs, t.rootEntry.p, t.leaves.p));
+        if (pairs) info.pairs_derived += (int32_t)nPairs;
+    } else if (pairs) {   // a leaf root: the leaf entry at its index base; otherwise the start of its run of pair ids (the root is the walk's first node)
+        hostRoots.resize((size_t)sh.nBlas);
+        for (int32_t i = 0; i < sh.nBlas; i++) {
+            const size_t k = (size_t)(*sh.instBlas)[(size_t)i];
+            hostRoots[(size_t)i] = rebuild::child_entry(idxOf[k], interiors[k] ? 0u : slotsOf[k], pairLo[k]);
+        }
+        HIPCHK(hipMemcpyAsync(t.rootEntry.p, hostRoots.data(), sizeof(uint32_t) * hostRoots.size(), hipMemcpyHostToDevice, s));
+    }
+    for (size_t k = 0; k < nR; k++) {   // (before anything reads a box: the collapse, the pair boxes below, the TLAS)
+        if (!refits(k)) continue;
+        HIPCHK(refitdev::launch_refit_blas(s, t.nodes.p, rootOf[k], 2 * interiors[k] + 1, t.prims.p, t.primIdx.p, t.leaves.p + leafLo[k], interiors[k] + 1, t.parent.p,
+                                           t.tickets.p));
+        info.refit++; info.leaves_refit += (int32_t)interiors[k] + 1;
+    }
+    return RT_OK;
+}
+// The records that follow the primitives.  Over everything as at upload; with blocks that move: the shade records as bound and the
+// window's anew (the light records: stage_rebuild's copy, anew when there is a window), and BLAS by BLAS the triangle records - a kept
+// BLAS's are a copy of its slot run, a refit BLAS also gets the boxes of its pair records rewritten
+int Pending::derive_records()
+{
+    const SceneArrays& sc = b.sc;
+    hipStream_t s = b.stream;
+    if (!blockwise) {
+        const bool boxes = refit && layout1 && !bvh4;
+        HIPCHK(refitdev::launch_records(s, t.prims.p, t.nodes.p, t.primIdx.p, nIdx, lights, (uint32_t)nLights, 0u, (uint32_t)sh.nPrims,
+                                        boxes ? t.pairNode.p : nullptr, boxes ? nPairs : 0u, boxes ? t.pairs.p : nullptr, layout1 ? t.triRecs.p : nullptr,
+                                        t.shadeRecs.p, t.lightRecs.p));
+        if (layout1) info.slots_derived += (int32_t)nIdx;
+        return RT_OK;
+    }
+    HIPCHK(hipMemcpyAsync(t.shadeRecs.p, sc.shadeRecs, sizeof(RtFloat4) * (size_t)sh.nPrims, hipMemcpyDeviceToDevice, s));
+    HIPCHK(refitdev::launch_records(s, t.prims.p, t.nodes.p, t.primIdx.p, 0u, lights, (uint32_t)nLights, (uint32_t)std::max(rq.first, 0), (uint32_t)rq.count,
+                                    nullptr, 0u, nullptr, nullptr, t.shadeRecs.p, t.lightRecs.p));
+    if (!layout1) return RT_OK;
+    for (size_t k = 0; k < nR; k++) {
+        RtFloat4* const recs = t.triRecs.p + (size_t)idxOf[k] * 3;
+        if (moves(k) && !refits(k)) {
+            HIPCHK(hipMemcpyAsync(recs, sc.triRecs + (size_t)b.blasBlock[k].idxLo * 3, sizeof(RtFloat4) * 3 * (size_t)slotsOf[k], hipMemcpyDeviceToDevice, s));
+            info.slots_relocated += (int32_t)slotsOf[k];
+            continue;
+        }
+        const uint32_t boxes = refits(k) ? interiors[k] : 0u;   // (a built BLAS: k_rb_pairs wrote them)
+        HIPCHK(refitdev::launch_blas_records(s, t.prims.p, t.nodes.p, t.pairNode.p + pairLo[k], boxes, boxes ? t.pairs.p + (size_t)pairLo[k] * 4 : nullptr,
+                                             t.primIdx.p + idxOf[k], slotsOf[k], recs));
+        info.slots_derived += (int32_t)slotsOf[k];
+    }
     return RT_OK;
 }
 
@@ -593,6 +683,7 @@ void Pending::commit()
     if (!refit) {   // (a refit moves no tree: roots and blocks stay)
         b.nReach = nNodes;
         b.blasBlock.resize(nR);
+        b.blasPairLo = pairLo; b.blasLeafLo = leafLo;
         for (size_t k = 0; k < nR; k++) {
             b.ranges[k].root = rootOf[k];
             b.blasBlock[k] = rebuild::BlasBlock{ 2 * interiors[k] + 1, idxOf[k], slotsOf[k], 1, depth[k] };
@@ -602,6 +693,7 @@ void Pending::commit()
         b.liveNewId = t.newId.p; b.liveQuadNode = t.quadNode.p;
         b.nLive = c4.live(); b.c4Need = c4.need();
     }
+    if (rq.perRange) { info.built = nBuilt; b.rangesInfo = info; }
     if (refit) b.refitInfo = RtRefitInfo{ refitPath, bvh4 ? (int32_t)b.nLive : 0, (int32_t)changed, stackNeed };
     b.inst = inst;
     const int stackEntries = rebuild::stack_entries(std::max(stackNeed, 1));   // (a BVH4: the collapsed trees' need, as validate_scene replays it)
@@ -696,7 +788,7 @@ int scenedev::rebuild_ranges(SceneBag& b, const RtPrimitive* prims, int32_t firs
     lbvh::Params P{};
     if (const int rc = plan_check_args(who, b.nPrims, b.ranges, b.blasBlock.data(), plan, nRanges, first, count, opts, P)) return rc;
     const Shape sh{ b.nPrims, b.nBlas, b.nLights, &b.ranges, &b.instBlas };
-    return rebuild_body(b, Request{ who, sh, nullptr, prims, first, count, blas, std::vector<int32_t>(plan, plan + nRanges), opts, P }, stats);
+    return rebuild_body(b, Request{ who, sh, nullptr, prims, first, count, blas, std::vector<int32_t>(plan, plan + nRanges), opts, P, true }, stats);
 }
 
 // The ranges of a caller's shape as the builders take them (root: assigned by the build)

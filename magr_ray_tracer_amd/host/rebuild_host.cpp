@@ -3,7 +3,8 @@
 // order of the ranges and appended the way BuildBLAS appends BLAS after BLAS, with the host restatement of the chosen GPU builder.
 // Together with TLAS::Build it is the ground truth the device rebuild must match bit for bit.  Under a per-range plan
 // (BVH2::RebuildRanges, rth_rebuild_ranges: rt_rebuild_ranges' restatement) a BLAS the plan keeps is appended as its bound block of
-// nodes, relocated by the rule the device kernel applies (rebuild::relocated_first).
+// nodes, relocated by the rule the device kernel applies (rebuild::relocated_first); a BLAS it refits (RT_REBUILD_REFIT_RANGE) likewise,
+// and then takes the boxes refit_common.h's rules give it over the primitives as they are.
 #include <cstring>
 #include <string>
 #include <vector>
@@ -71,7 +72,7 @@ void BVH2::RebuildPlan(const char* who, const int32_t* plan, int nRanges, const 
         const int builder = words[k];
         const bool sbvh = builder == RT_REBUILD_SBVH;
         const uint32_t nodeBase = (uint32_t)nodes.size(), idxBase = (uint32_t)idx.size();
-        if (builder == RT_REBUILD_KEEP) {   // the bound block, relocated; its primIdx slots as they are
+        if (builder == RT_REBUILD_KEEP || builder == RT_REBUILD_REFIT_RANGE) {   // the bound block, relocated; its primIdx slots as they are
             const rebuild::BlasBlock& blk = blocks[k];
             if (nodes.size() + blk.nodes > 0x7fffffffull || idx.size() + blk.idxSlots > 0x7fffffffull)
                 throw LbvhError(RT_E_UNSUPPORTED, pre + "the new trees have 2^31 nodes or index slots, or more");
@@ -81,6 +82,18 @@ void BVH2::RebuildPlan(const char* who, const int32_t* plan, int nRanges, const 
             for (size_t i = nodeBase; i < nodes.size(); i++) nodes[i].first = rebuild::relocated_first(nodes[i].first, nodes[i].count, nodeDelta, idxDelta);
             idx.insert(idx.end(), primIdx.begin() + blk.idxLo, primIdx.begin() + blk.idxLo + blk.idxSlots);
             if (blk.height > depth) depth = blk.height;
+            if (builder == RT_REBUILD_REFIT_RANGE) {
+                // ... and its boxes anew from the primitives as they are now, by rt_update_scene's rules (refit_common.h): breadth-first
+                // from the root, then backwards, so every child comes before its parent
+                std::vector<uint32_t> bfs(1, nodeBase);
+                for (size_t head = 0; head < bfs.size(); head++)
+                    if (nodes[bfs[head]].count == 0) { bfs.push_back(nodes[bfs[head]].first); bfs.push_back(nodes[bfs[head]].first + 1); }
+                for (size_t a = bfs.size(); a-- > 0;) {
+                    RtBVHNode2& n = nodes[bfs[a]];
+                    if (n.count > 0) refit::set_box(n, refit::leaf_box(primitives_.data(), idx.data(), n.first, n.count));
+                    else refit::set_box(n, lbvh::box_union(refit::node_box(nodes[n.first]), refit::node_box(nodes[n.first + 1])));
+                }
+            }
             continue;
         }
         if (sbvh) {   // the tree's size is known only once it is built: `written` nodes and nIdx indices are appended

@@ -80,7 +80,7 @@ public:
     // host restatement of rt_rebuild_scene's builder (RT_REBUILD_SAH / RT_REBUILD_LBVH / RT_REBUILD_SBVH, opt as there); instance transforms stay,
     // bvhIdx follows.  Throws LbvhError and leaves everything unchanged when refused (rebuild_host.cpp).
     void     Rebuild(int builder, const RtBuildOptions* opt);
-    // The same under a plan (rt_rebuild_ranges): plan[nRanges], one RT_REBUILD_SAH / LBVH / SBVH / KEEP per distinct BLAS in increasing
+    // The same under a plan (rt_rebuild_ranges): plan[nRanges], one RT_REBUILD_SAH / LBVH / SBVH / KEEP / REFIT_RANGE per distinct BLAS in increasing
     // order of the ranges; a kept BLAS is appended as its bound block of nodes, relocated (csrc/rebuild_common.h, relocated_first).
     void     RebuildRanges(const int32_t* plan, int nRanges, const RtBuildOptions* opt);
     int      buildThreads = 1;   // > 1: subtrees are built by parallel tasks, then numbered in the reference's LIFO order (same arrays)

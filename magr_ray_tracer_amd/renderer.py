@@ -253,15 +253,25 @@ class Device:
         return _rebuild_dict(st)
 
     def rebuild_ranges(self, plan, prims=None, first=0, instances=None, alpha=None, **lbvh_options):
-        """Rebuild only the BLAS that changed (rt_rebuild_ranges): plan[k], one of "keep", "sah", "lbvh", "sbvh_gpu" per distinct BLAS in
-        the order of blas_blocks(), says whether that BLAS keeps its bound tree (moved on the GPU to where the new scene numbers it) or
+        """Rebuild only the BLAS that changed (rt_rebuild_ranges): plan[k], one of "keep", "refit", "sah", "lbvh", "sbvh_gpu" per distinct
+        BLAS in the order of blas_blocks(), says whether that BLAS keeps its bound tree (moved on the GPU to where the new scene numbers
+        it; "refit": and given new boxes from the primitives as they are afterwards, by update_scene's rules, for that BLAS alone) or
         is built anew by that builder, as rebuild_scene builds it; builders may differ from BLAS to BLAS (lbvh_options go to the "lbvh"
         ranges, alpha to the "sbvh_gpu" ranges).  `prims` / `first` / `instances` as for rebuild_scene; replaced primitives must not
-        touch a kept BLAS.  Every context holding the scene sees it.  Returns the stats (blas_built: the BLAS actually built); a refusal
-        raises RtError (.code) and leaves the scene as it was."""
+        touch a kept BLAS (a refit or built one they may).  Every context holding the scene sees it.  Returns the stats (blas_built: the
+        BLAS a builder built); ranges_info() tells what was derived and what was moved.  A refusal raises RtError (.code) and leaves
+        the scene as it was."""
         args, keep, st = _ranges_args(plan, prims, first, instances, lbvh_options, alpha)
         self._chk_code(self._lib.rt_rebuild_ranges(self._h, *args))
         return _rebuild_dict(st)
+
+    def ranges_info(self):
+        """The last successful rebuild_ranges of the bound scene copy (rt_ranges_info), counted from what it queued: ranges built, kept
+        and refit; pairs_derived / pairs_relocated; slots_derived / slots_relocated (triangle-record slots); nodes_numbered (nodes of
+        the trees the breadth-first numbering walked); leaves_refit.  All zero before any such call."""
+        r = np.zeros((), _lib.RangesInfo)
+        self._chk(self._lib.rt_ranges_info(self._h, _lib.ptr(r)))
+        return {n: int(r[n]) for n in _lib.RANGES_INFO_FIELDS}
 
     def blas_blocks(self):
         """The distinct BLAS of the bound scene in plan order (rt_scene_blas_blocks): a list of dicts with prim_first, prim_count, nodes

@@ -247,11 +247,12 @@ class Scene:
             raise BuildError(rc, self._lib.rth_last_error().decode())
 
     def RebuildRanges(self, plan, alpha=None, **lbvh_options):
-        """Rebuild under a per-range plan, as rt_rebuild_ranges does on the GPU (rth_rebuild_ranges): plan[k], one of "keep", "sah",
-        "lbvh", "sbvh_gpu" per distinct BLAS in increasing order of the primitive ranges.  A built BLAS is built as Rebuild builds it
-        (lbvh_options go to the "lbvh" ranges, alpha to the "sbvh_gpu" ranges); a kept BLAS keeps its tree, moved to where the new
-        scene numbers it.  The primitives of a kept BLAS must not have changed.  Raises BuildError (.code) and changes nothing when
-        refused (a BLAS that is not compact cannot be kept)."""
+        """Rebuild under a per-range plan, as rt_rebuild_ranges does on the GPU (rth_rebuild_ranges): plan[k], one of "keep", "refit",
+        "sah", "lbvh", "sbvh_gpu" per distinct BLAS in increasing order of the primitive ranges.  A built BLAS is built as Rebuild builds
+        it (lbvh_options go to the "lbvh" ranges, alpha to the "sbvh_gpu" ranges); a kept BLAS keeps its tree, moved to where the new
+        scene numbers it; a "refit" BLAS keeps its tree likewise and takes new boxes from the primitives as they are, by Refit()'s rules,
+        so only that BLAS loses the clipped boxes of an SBVH tree.  The primitives of a kept BLAS must not have changed.  Raises
+        BuildError (.code) and changes nothing when refused (a BLAS that is not compact can be neither kept nor refit)."""
         words = plan_words(plan, lbvh_options, alpha)
         rc = self._lib.rth_rebuild_ranges(self._h, _lib.ptr(words) if len(words) else None, len(words), _lib.ptr(build_options(alpha=alpha, **lbvh_options)))
         if rc != 0:
@@ -349,16 +350,16 @@ def rebuild_builder(builder, lbvh_options=None, alpha=None):
     return REBUILD_BUILDERS[builder]
 
 
-PLAN_WORDS = {"keep": _lib.REBUILD_KEEP, "sah": _lib.REBUILD_SAH, "lbvh": _lib.REBUILD_LBVH, "sbvh_gpu": _lib.REBUILD_SBVH}
+PLAN_WORDS = {"keep": _lib.REBUILD_KEEP, "refit": _lib.REBUILD_REFIT_RANGE, "sah": _lib.REBUILD_SAH, "lbvh": _lib.REBUILD_LBVH, "sbvh_gpu": _lib.REBUILD_SBVH}
 
 
 def plan_words(plan, lbvh_options=None, alpha=None):
-    """The RT_REBUILD_* words (int32) of a per-range plan, a list of "keep" | "sah" | "lbvh" | "sbvh_gpu" (integers pass through, so a
+    """The RT_REBUILD_* words (int32) of a per-range plan, a list of "keep" | "refit" | "sah" | "lbvh" | "sbvh_gpu" (integers pass through, so a
     test can hand the library a word it must refuse); the linear builder's options need an "lbvh" range, alpha an "sbvh_gpu" range."""
     plan = list(plan)
     for w in plan:
         if not isinstance(w, (int, np.integer)) and w not in PLAN_WORDS:
-            raise ValueError(f"unknown plan word {w!r} (expected 'keep', 'sah', 'lbvh' or 'sbvh_gpu')")
+            raise ValueError(f"unknown plan word {w!r} (expected 'keep', 'refit', 'sah', 'lbvh' or 'sbvh_gpu')")
     if lbvh_options and "lbvh" not in plan:
         raise ValueError(f"options {sorted(lbvh_options)} apply to 'lbvh' ranges only")
     if alpha is not None and "sbvh_gpu" not in plan:

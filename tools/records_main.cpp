@@ -161,9 +161,39 @@ static void instance_records()
     EXPECT("instance record", f2u(t[3].z) | f2u(t[3].w), 0u);
 }
 
+// rebuild::relocated_entry (the derived pair records of a kept or refit BLAS): a leaf entry moves inside its slot field, up and down and
+// to both ends of it, and keeps its count and leaf bit; an interior entry moves by the pair offset; the offsets are taken modulo 2^32.
+// A plan with the per-range refit word passes check_plan's rules as a kept one does.
+static void relocated_entries()
+{
+    const uint32_t maxFirst = (uint32_t)rebuild::kMaxPackedIdx - 1u, maxCount = rebuild::kMaxPackedLeaf;
+    for (uint32_t count : { 1u, maxCount }) for (uint32_t from : { 0u, 5u, maxFirst }) for (uint32_t to : { 0u, 7u, maxFirst }) {
+        const uint32_t idxDelta = to - from;   // (wraps when the block moves down)
+        for (uint32_t pairDelta : { 0u, 3u, 0xfffffffdu })
+            EXPECT("relocated leaf entry", rebuild::relocated_entry(leaf_entry(from, count), pairDelta, idxDelta), leaf_entry(to, count));
+    }
+    for (uint32_t id : { 3u, 1000u, kIdMask - 3u }) for (uint32_t idxDelta : { 0u, 9u, 0xfffffff7u }) {
+        EXPECT("relocated interior entry", rebuild::relocated_entry(id, 3u, idxDelta), id + 3u);
+        EXPECT("relocated interior entry", rebuild::relocated_entry(id, 0xfffffffdu, idxDelta), id - 3u);
+    }
+    EXPECT("relocated_first, interior", rebuild::relocated_first(10u, 0u, 0xfffffffeu, 5u), 8u);
+    EXPECT("relocated_first, leaf", rebuild::relocated_first(10u, 2u, 0xfffffffeu, 5u), 15u);
+    const std::vector<rebuild::BlasRange> ranges = { { 0u, 0u, 1u }, { 1u, 1u, 37u }, { 40u, 38u, 220u } };
+    const rebuild::BlasBlock blocks[3] = { { 1u, 0u, 1u, 1, 0u }, { 39u, 1u, 37u, 0, 6u }, { 261u, 38u, 220u, 1, 9u } };
+    std::string msg;
+    const int32_t refit3[3] = { RT_REBUILD_KEEP, RT_REBUILD_SAH, RT_REBUILD_REFIT_RANGE }, notCompact[3] = { RT_REBUILD_KEEP, RT_REBUILD_REFIT_RANGE, RT_REBUILD_KEEP };
+    const int32_t word3[3] = { RT_REBUILD_KEEP, RT_REBUILD_REFIT, RT_REBUILD_REFIT_RANGE };
+    EXPECT("check_plan, a window in a refit range", rebuild::check_plan(refit3, 3, ranges, blocks, 1, 257, msg), RT_OK);
+    EXPECT("check_plan, a window in a kept range", rebuild::check_plan(refit3, 3, ranges, blocks, 0, 5, msg), RT_E_INVALID);
+    EXPECT("check_plan, a refit range that is not compact", rebuild::check_plan(notCompact, 3, ranges, blocks, 0, 0, msg), RT_E_UNSUPPORTED);
+    EXPECT("check_plan names the range", msg.find("BLAS 1 (primitives [1, 38))") != std::string::npos, 1);
+    EXPECT("check_plan, RT_REBUILD_REFIT", rebuild::check_plan(word3, 3, ranges, blocks, 0, 0, msg), RT_E_INVALID);
+}
+
 int main()
 {
     entries();
+    relocated_entries();
     pair_records();
     quad_records();
     triangle_records();
