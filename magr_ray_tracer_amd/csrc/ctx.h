@@ -21,7 +21,7 @@ struct RtCtx {
     bool sceneLoaded = false, ownAccum = true;
     std::shared_ptr<scenedev::SceneBag> scene;   // shared by the contexts of rt_share_scene, freed with the last of them
     uint64_t sceneGen = 0;                // the SceneBag generation this context's traversal configuration was derived for
-    bool singleBlas = false;              // the TLAS root is a leaf (this, sc, layout, stackEntries, tlasDepth, nInterior: the copy's facts, assigned by adopt_scene only)
+    scenedev::SceneFacts facts;           // what the traversal is planned from (this and sc: the copy's, assigned whole by adopt_scene only)
     std::vector<void*> queueAllocs;
     float* dFocus = nullptr;
     RtRay* dRayIO = nullptr; // debug import/export staging (lazy)
@@ -30,18 +30,15 @@ struct RtCtx {
     struct Ev { hipEvent_t a, b; int stage; };
     std::vector<Ev> evPool; size_t evUsed = 0;
     RtStageTimes times{};
-    int tlasDepth = 0;
-    int layout = 0;   // 0 = traverse the reference arrays as uploaded, 1 = derived pair/triangle-record layout
     int trav = 0;           // the traversal kernels (Traversal, set by configure_traversal)
     int coherent = 1;       // RT355_COHERENT: wave-uniform node records through the scalar cache on bounce 0 (1), every bounce of the TLAS kernel (2, lab), off (0)
     uint32_t* dSpill = nullptr; size_t spillWords = 0;
     int xcdFirst = -1;      // the XCD this context's sparse queues start on (PersistTune.xcdFirst)
     int spillCap = 0;       // LDS stack entries per lane of a spilling kernel, set by configure_traversal (RT355_SPILL_CAP: tests force the spill path with a tiny cap, >= 6)
-    int nInterior = 0;          // records of the dense pair table (their ids must fit the 29-bit field of the tagged stack entries)
     bool cursorUsed[2 * (RT_MAX_BOUNCES + 2)] = {};   // work-queue heads consumed since the last k_begin_frame
     bool shadeRun[RT_MAX_BOUNCES + 1] = {};           // shade(b) launched since the last k_begin_frame
     bool generated = false;                           // generate launched since the last k_begin_frame
-    int stackEntries = RT_BVH2_STACK, persistGrid = 0, persistGridConnect = 0;
+    int persistGrid = 0, persistGridConnect = 0;
     rt355dev::PersistTune tune{}, tuneConnect{}, tune4{};   // extend (BVH2), connect, extend (BVH4): set by configure_traversal
     int tuneBlocks = 0, connectBlocks = 0;   // workgroups per CU the knobs ask of the persistent grids (TravPlan; persist_blocks)
     float4* dPostF = nullptr; uchar4* dPostB = nullptr;   // post-processing outputs (lazy)

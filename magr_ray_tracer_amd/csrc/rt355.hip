@@ -55,7 +55,7 @@ extern "C" int rt_kernel_info(RtCtx* ctx, RtKernelInfo* out)
     if (const int rc = sync_scene_config(ctx)) return rc;
     const int persist = ctx->trav <= TRAV_TLAS_SPILL ? ctx->trav : 0;
     const int persist4 = ctx->trav == TRAV_BVH4 ? 1 : (ctx->trav == TRAV_BVH4_TLAS ? 2 : (ctx->trav == TRAV_BVH4_TLAS_SPILL ? 3 : 0));
-    *out = RtKernelInfo{ ctx->layout, persist, persist4, spill_trav(ctx->trav) ? ctx->spillCap : ctx->stackEntries, ctx->persistGrid, ctx->persistGridConnect,
+    *out = RtKernelInfo{ ctx->facts.layout, persist, persist4, spill_trav(ctx->trav) ? ctx->spillCap : ctx->facts.stackEntries, ctx->persistGrid, ctx->persistGridConnect,
                          ctx->shadeGrid, ctx->sc.nBlas };
     return RT_OK;
 }
@@ -125,7 +125,7 @@ int SceneBag::wait_holders() const
 }
 
 // The dynamic LDS of a context's TLAS kernels: its column entries (trav_common.h) with the world-ray backup behind them
-static int tlas_lds_entries(const RtCtx* c) { return tlas_lds_entries(c->trav, c->spillCap, c->stackEntries, c->tlasDepth); }
+static int tlas_lds_entries(const RtCtx* c) { return tlas_lds_entries(c->trav, c->spillCap, c->facts.stackEntries, c->facts.tlasDepth); }
 static size_t tlas_stack_bytes(const RtCtx* c) { return tlas_column_bytes(tlas_lds_entries(c)); }
 
 // The traversal launch of a stage: the one place that maps (stage, bounce, steps wanted) to a kernel instantiation, its grid, its dynamic
@@ -144,9 +144,9 @@ static TraceLaunch trace_launch(const RtCtx* c, int stage, int bounce, bool step
 {
     TraceLaunch L;
     L.grid = grid_for(rays);
-    L.lds = stack_bytes(c->stackEntries);
+    L.lds = stack_bytes(c->facts.stackEntries);
     const bool connect = stage == ST_CONNECT;
-    const bool bvh4 = c->cfg.accel == RT_ACCEL_BVH4, l1 = c->layout == 1;
+    const bool bvh4 = c->cfg.accel == RT_ACCEL_BVH4, l1 = c->facts.layout == 1;
     bool top = false;
     switch (c->trav) {
     case TRAV_NESTED:
@@ -168,7 +168,7 @@ static TraceLaunch trace_launch(const RtCtx* c, int stage, int bounce, bool step
         // bounce 0 through the same kernel with one workgroup per 256 rays: its "queue not longer than the grid" branch is the plain
         // one-ray-per-lane loop without the TLAS code of k_extend (60 instead of 86 VGPRs: 8 instead of 5 waves per SIMD)
         else L.persist = c->coherent ? k_trace_persist<false, true> : (steps ? k_trace_persist<false, false, true> : k_trace_persist<false>);
-        if (top) { L.tune.topBase = c->stackEntries * kBlock; L.lds += top_bytes(L.tune.topLevels); }
+        if (top) { L.tune.topBase = c->facts.stackEntries * kBlock; L.lds += top_bytes(L.tune.topLevels); }
         break;
     case TRAV_BVH4:
         L.tune = connect ? c->tuneConnect : c->tune4;
@@ -444,12 +444,9 @@ extern "C" int rt_destroy(RtCtx* ctx)
 // What the traversal plan of a context is a function of (trav_common.h): its configuration, the facts of the copy it holds, its device
 static TravFacts traversal_facts(const RtCtx* ctx)
 {
-    TravFacts f;
-    f.accel = ctx->cfg.accel; f.extend_variant = ctx->cfg.extend_variant; f.persist_blocks_per_cu = ctx->cfg.persist_blocks_per_cu;
-    f.layout = ctx->layout; f.singleBlas = ctx->singleBlas; f.tlasDepth = ctx->tlasDepth; f.nInterior = ctx->nInterior;
-    f.nQuads = ctx->scene->nQuads; f.stackEntries = ctx->stackEntries;
-    f.sharedMemPerBlock = (int)ctx->ldsPerBlock; f.xcdFirst = ctx->xcdFirst;
-    return f;
+    const SceneFacts& s = ctx->facts;   // (what the context adopted, never the live bag's)
+    return TravFacts{ ctx->cfg.accel, ctx->cfg.extend_variant, ctx->cfg.persist_blocks_per_cu, s.layout, s.singleBlas, s.tlasDepth, s.nInterior, s.nQuads, s.stackEntries,
+                      (int)ctx->ldsPerBlock, ctx->xcdFirst };
 }
 static void adopt_plan(RtCtx* ctx, const TravPlan& p)
 {
@@ -468,7 +465,7 @@ static void adopt_plan(RtCtx* ctx, const TravPlan& p)
 // workgroup (beside_shade; EXPERIMENTS.md (60)): the deepest table with which as many fit there as with none.
 static int fit_top_tables(RtCtx* ctx, bool topAuto)
 {
-    for (PersistTune* t : { &ctx->tune, &ctx->tuneConnect }) if (stack_bytes(ctx->stackEntries) + top_bytes(t->topLevels) > ctx->ldsPerBlock) t->topLevels = 0;
+    for (PersistTune* t : { &ctx->tune, &ctx->tuneConnect }) if (stack_bytes(ctx->facts.stackEntries) + top_bytes(t->topLevels) > ctx->ldsPerBlock) t->topLevels = 0;
     if (topAuto) for (int stage : { ST_EXTEND, ST_CONNECT }) {
         PersistTune& t = stage == ST_CONNECT ? ctx->tuneConnect : ctx->tune;
         int q = 0, lv = t.topLevels, beside = 0, shadeLds = 0;
@@ -508,7 +505,7 @@ static int bind_spill_columns(RtCtx* ctx)
     if (!spill_trav(ctx->trav)) return RT_OK;
     // every SPILL launch runs on a persistent grid (bounce 0 too), so the global columns are bounded by the grids
     const size_t stride = (size_t)std::max(ctx->persistGrid, ctx->persistGridConnect) * kBlock;
-    const size_t words = stride * (size_t)(tlas_stack_entries(ctx->stackEntries, ctx->tlasDepth) - ctx->spillCap);
+    const size_t words = stride * (size_t)(tlas_stack_entries(ctx->facts.stackEntries, ctx->facts.tlasDepth) - ctx->spillCap);
     if (words > ctx->spillWords) {
         if (ctx->dSpill) (void)hipFree(ctx->dSpill);
         ctx->dSpill = nullptr; ctx->spillWords = 0;
@@ -559,7 +556,7 @@ static int adopt_scene(RtCtx* ctx)
     auto f4 = [](const RtFloat4* p) { return (const float4*)p; };
     ctx->sc = DevScene{ a.prims, a.mats, f4(a.tex), a.lights, a.bvh2, a.bvh4, a.primIdx, a.tlas, a.blas, f4(a.pairs), f4(a.triRecs), a.rootEntry, f4(a.shadeRecs),
                         f4(a.tlasPairs), f4(a.instRecs), a.tlasRoot, f4(a.tlasPairsP), a.tlasRootP, f4(a.lightRecs), f4(a.quads), a.nLights, a.nPrims, a.nBlas, a.nTex, a.nMats };
-    ctx->layout = b.layout; ctx->stackEntries = b.stackEntries; ctx->tlasDepth = b.tlasDepth; ctx->nInterior = b.nInterior; ctx->singleBlas = b.singleBlas;
+    ctx->facts = b.facts;
     const int rc = configure_traversal(ctx);
     if (rc == RT_OK) ctx->sceneGen = b.generation;
     return rc;
@@ -612,16 +609,16 @@ extern "C" int rt_upload_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t nPr
 {
     if (!ctx) return fail(RT_E_INVALID, "rt_upload_scene: null context");
     const HostScene in{ prims, nPrims, mats, nMats, textures, nTexels, lights, nLights, bvhNodes, nNodes, primIdx, nIdx, tlas, nTlas, blas, nBlas };
-    int stackEntries = RT_BVH2_STACK, tlasDepth = 0; int64_t texPad = 2;
+    SceneFacts facts; int64_t texPad = 2;   // (validate_scene begins the facts: the stack entries, the TLAS height)
     // nothing of the context changes until the arrays have passed (a failed upload leaves the bound scene usable)
-    if (const int rc = validate_scene(ctx->cfg.accel, in, &stackEntries, &texPad, &tlasDepth)) return rc;
+    if (const int rc = validate_scene(ctx->cfg.accel, in, &facts, &texPad)) return rc;
     HIPCHK(hipSetDevice(ctx->cfg.device));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     scene_release(ctx);   // the bound copy goes before the new one is made (one shared with other contexts lives on with them)
     ctx->sceneLoaded = false; ctx->trav = TRAV_NESTED;   // nothing usable until this upload has succeeded
     auto bag = std::make_shared<SceneBag>();
     bag->device = ctx->cfg.device;
-    if (const int rc = upload_scene(*bag, ctx->cfg.accel, ctx->cfg.extend_variant, in, stackEntries, texPad, tlasDepth)) return rc;
+    if (const int rc = upload_scene(*bag, ctx->cfg.accel, ctx->cfg.extend_variant, in, facts, texPad)) return rc;
     return bind_scene(ctx, bag);
 }
 
@@ -636,8 +633,8 @@ extern "C" int rt_upload_scene_bvh2(RtCtx* ctx, const RtPrimitive* prims, int32_
     if (ctx->cfg.accel == RT_ACCEL_BVH2)
         return rt_upload_scene(ctx, prims, nPrims, mats, nMats, textures, nTexels, lights, nLights, bvhNodes, nNodes, primIdx, nIdx, tlas, nTlas, blas, nBlas);
     const HostScene in{ prims, nPrims, mats, nMats, textures, nTexels, lights, nLights, bvhNodes, nNodes, primIdx, nIdx, tlas, nTlas, blas, nBlas };
-    int stackEntries = RT_BVH2_STACK, tlasDepth = 0; int64_t texPad = 2;
-    if (const int rc = validate_scene(RT_ACCEL_BVH2, in, &stackEntries, &texPad, &tlasDepth)) return rc;   // the BVH2 rules ...
+    SceneFacts facts; int64_t texPad = 2;   // (validate_scene begins the facts: the stack entries, the TLAS height)
+    if (const int rc = validate_scene(RT_ACCEL_BVH2, in, &facts, &texPad)) return rc;   // the BVH2 rules ...
     std::vector<uint32_t> roots((size_t)nBlas);
     for (int32_t b = 0; b < nBlas; b++) roots[(size_t)b] = blas[b].bvhIdx;
     std::vector<collapse::Blas> blas4;
@@ -648,7 +645,7 @@ extern "C" int rt_upload_scene_bvh2(RtCtx* ctx, const RtPrimitive* prims, int32_
     HIPCHK(hipStreamSynchronize(ctx->stream));
     auto bag = std::make_shared<SceneBag>();
     bag->device = ctx->cfg.device;
-    if (const int rc = upload_scene(*bag, ctx->cfg.accel, ctx->cfg.extend_variant, in, stackEntries, texPad, tlasDepth, &blas4)) return rc;
+    if (const int rc = upload_scene(*bag, ctx->cfg.accel, ctx->cfg.extend_variant, in, facts, texPad, &blas4)) return rc;
     return bind_scene(ctx, bag);
 }
 
@@ -1108,7 +1105,7 @@ extern "C" int rt_focus(RtCtx* ctx, int32_t x, int32_t y, const RtCamera* cam, f
     int rc = need_scene(ctx, "rt_focus"); if (rc) return rc;
     if (!cam || !t) return fail(RT_E_INVALID, "rt_focus: null argument");
     HIPCHK(hipSetDevice(ctx->cfg.device));
-    hipLaunchKernelGGL(ctx->kFocus, dim3(1), dim3(kBlock), stack_bytes(ctx->stackEntries), ctx->stream, ctx->sc, *cam, x, y, ctx->cfg.width, ctx->cfg.height, ctx->dFocus);
+    hipLaunchKernelGGL(ctx->kFocus, dim3(1), dim3(kBlock), stack_bytes(ctx->facts.stackEntries), ctx->stream, ctx->sc, *cam, x, y, ctx->cfg.width, ctx->cfg.height, ctx->dFocus);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(t, ctx->dFocus, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));

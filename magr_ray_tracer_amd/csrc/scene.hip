@@ -47,7 +47,7 @@ static int bvh4_stack_need(const RtBVHNode4* n, int32_t nNodes, int32_t nIdx, ui
 
 // Host-side shape checks of a scene (no device needed; rt_upload_scene runs them first): a kernel that walks a malformed tree can
 // fault the GPU.  Also sizes the LDS traversal stack and the texture padding.
-int scenedev::validate_scene(int accel, const HostScene& in, int* stackEntriesOut, int64_t* texPadOut, int* tlasDepthOut)
+int scenedev::validate_scene(int accel, const HostScene& in, SceneFacts* factsOut, int64_t* texPadOut)
 {
     const auto& [prims, nPrims, mats, nMats, textures, nTexels, lights, nLights, bvhNodes, nNodes, primIdx, nIdx, tlas, nTlas, blas, nBlas] = in;
     if (accel != RT_ACCEL_BVH2 && accel != RT_ACCEL_BVH4) return fail(RT_E_INVALID, "rt_upload_scene: unknown accel %d", accel);
@@ -110,9 +110,8 @@ int scenedev::validate_scene(int accel, const HostScene& in, int* stackEntriesOu
         for (int32_t i = 0; i < nNodes; i++) if (n2[i].count > 0 && (uint64_t)n2[i].first + n2[i].count > (uint64_t)nIdx)
             return fail(RT_E_INVALID, "bvh node %d: leaf range exceeds primIdx", i);
     }
-    if (stackEntriesOut) *stackEntriesOut = rebuild::stack_entries(stackNeed);   // (rebuild_common.h: rt_rebuild_scene sizes it the same way)
+    if (factsOut) { factsOut->stackEntries = rebuild::stack_entries(stackNeed); factsOut->tlasDepth = tlasDepth; }   // (rebuild_common.h: rt_rebuild_scene sizes it the same way)
     if (texPadOut) *texPadOut = texPad;
-    if (tlasDepthOut) *tlasDepthOut = tlasDepth;
     return RT_OK;
 }
 extern "C" int rt_validate_scene(int32_t accel, const RtPrimitive* prims, int32_t nPrims, const RtMaterial* mats, int32_t nMats,
@@ -121,18 +120,18 @@ extern "C" int rt_validate_scene(int32_t accel, const RtPrimitive* prims, int32_
                                  const RtTLASNode* tlas, int32_t nTlas, const RtBVHInstance* blas, int32_t nBlas)
 {
     return validate_scene(accel, HostScene{ prims, nPrims, mats, nMats, textures, nTexels, lights, nLights, bvhNodes, nNodes, primIdx, nIdx, tlas, nTlas, blas, nBlas },
-                          nullptr, nullptr, nullptr);
+                          nullptr, nullptr);
 }
 
-// What rt_update_scene needs of an upload: the counts, the host shadow of the fields an update must keep, and the refit topology on
-// the device (parents, reachable leaves, pair id -> node id).  A scene the update cannot handle records why (refitRefusal).
+// What rt_update_scene needs of an upload: the host shadow of the fields an update must keep, and in `live` the trees' counts, their refit
+// topology on the device (parents, reachable leaves, pair id -> node id) and one record per BLAS.  A scene the update cannot handle
+// records why (refitRefusal).
 // (a BVH4 copy that keeps its BVH2 - in.bvhNodes is the BVH2 - is prepared like a BVH2 copy: it can be rebuilt; rt_update_scene refuses
 // every BVH4 context before it comes here)
-static int prepare_update(SceneBag& b, int accel, int extendVariant, const HostScene& in, const std::vector<uint32_t>& pairNode)
+static int prepare_update(SceneBag& b, LiveTrees& live, int accel, int extendVariant, const HostScene& in, const std::vector<uint32_t>& pairNode)
 {
     const auto& [prims, nPrims, mats, nMats, textures, nTexels, lights, nLights, bvhNodes, nNodes, primIdx, nIdx, tlas, nTlas, blas, nBlas] = in;
-    b.nPrims = nPrims; b.nNodes = nNodes; b.nIdx = nIdx; b.nLights = nLights; b.nTlas = nTlas; b.nBlas = nBlas;
-    b.nPairs = (int32_t)pairNode.size(); b.accel = accel;
+    live.nNodes = nNodes; live.nIdx = nIdx; live.nTlas = nTlas; live.nPairs = (uint32_t)pairNode.size(); b.accel = accel;
     if (accel != RT_ACCEL_BVH2 && !b.keepsBvh2) { b.refitRefusal = "BVH4 scenes cannot be refit"; return RT_OK; }
     if (nBlas > refit::kMaxInstances) { b.refitRefusal = "more than 256 instances (TLAS::Build's limit)"; return RT_OK; }
     if (nTlas != 2 * nBlas) { b.refitRefusal = "the TLAS does not have TLAS::Build's 2 x instances nodes"; return RT_OK; }
@@ -143,31 +142,31 @@ static int prepare_update(SceneBag& b, int accel, int extendVariant, const HostS
     b.inst.assign(blas, blas + nBlas);
     b.variantLayout1 = extendVariant != 1;
     // rt_rebuild_scene: the primitive range of each BLAS (rebuild_common.h)
-    b.rebuildRefusal = rebuild::find_blas_ranges((const RtBVHNode2*)bvhNodes, nNodes, primIdx, nIdx, nPrims, blas, nBlas, b.ranges, b.instBlas);
+    b.rebuildRefusal = rebuild::find_blas_ranges((const RtBVHNode2*)bvhNodes, nNodes, primIdx, nIdx, nPrims, blas, nBlas, live.ranges, live.instBlas);
     // ... and what it occupies: nodes, index slots, height, and whether it can be kept (rt_rebuild_ranges); build_topology has walked
     // the trees: no cycle
     if (!b.rebuildRefusal) {
-        rebuild::find_blas_blocks((const RtBVHNode2*)bvhNodes, b.ranges, b.blasBlock);
+        rebuild::find_blas_blocks((const RtBVHNode2*)bvhNodes, live.ranges, live.block);
         // where each BLAS's pair ids (pair_records) and leaves (build_topology) lie: both go root by root as the instances first name them
-        b.blasPairLo.assign(b.ranges.size(), 0u); b.blasLeafLo.assign(b.ranges.size(), 0u);
-        std::vector<uint8_t> named(b.ranges.size(), 0);
+        live.pairLo.assign(live.ranges.size(), 0u); live.leafLo.assign(live.ranges.size(), 0u);
+        std::vector<uint8_t> named(live.ranges.size(), 0);
         uint32_t pairLo = 0, leafLo = 0;
-        for (const int32_t k : b.instBlas) {
+        for (const int32_t k : live.instBlas) {
             if (named[(size_t)k]) continue;
             named[(size_t)k] = 1;
-            b.blasPairLo[(size_t)k] = pairLo; b.blasLeafLo[(size_t)k] = leafLo;
-            pairLo += b.blas_interiors((size_t)k); leafLo += b.blas_interiors((size_t)k) + 1;
+            live.pairLo[(size_t)k] = pairLo; live.leafLo[(size_t)k] = leafLo;
+            pairLo += live.interiors((size_t)k); leafLo += live.interiors((size_t)k) + 1;
         }
     }
-    b.nLeaves = (uint32_t)t.leaves.size(); b.nReach = (uint32_t)t.order.size();
-    int rc = dalloc(b.allocs, &b.dParent, t.parent.size());
-    if (rc == RT_OK) rc = dalloc(b.allocs, &b.dLeaves, t.leaves.size());
-    if (rc == RT_OK) rc = dalloc(b.allocs, &b.dTickets, (size_t)nNodes);
-    if (rc == RT_OK) rc = dalloc(b.allocs, &b.dPairNode, pairNode.size());
+    live.nLeaves = (uint32_t)t.leaves.size(); live.nReach = (uint32_t)t.order.size();
+    int rc = dalloc(b.allocs, &live.parent, t.parent.size());
+    if (rc == RT_OK) rc = dalloc(b.allocs, &live.leaves, t.leaves.size());
+    if (rc == RT_OK) rc = dalloc(b.allocs, &live.tickets, (size_t)nNodes);
+    if (rc == RT_OK) rc = dalloc(b.allocs, &live.pairNode, pairNode.size());
     if (rc != RT_OK) return rc;
-    HIPCHK(hipMemcpy(b.dParent, t.parent.data(), sizeof(uint32_t) * t.parent.size(), hipMemcpyHostToDevice));
-    if (!t.leaves.empty()) HIPCHK(hipMemcpy(b.dLeaves, t.leaves.data(), sizeof(uint32_t) * t.leaves.size(), hipMemcpyHostToDevice));
-    if (!pairNode.empty()) HIPCHK(hipMemcpy(b.dPairNode, pairNode.data(), sizeof(uint32_t) * pairNode.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(live.parent, t.parent.data(), sizeof(uint32_t) * t.parent.size(), hipMemcpyHostToDevice));
+    if (!t.leaves.empty()) HIPCHK(hipMemcpy(live.leaves, t.leaves.data(), sizeof(uint32_t) * t.leaves.size(), hipMemcpyHostToDevice));
+    if (!pairNode.empty()) HIPCHK(hipMemcpy(live.pairNode, pairNode.data(), sizeof(uint32_t) * pairNode.size(), hipMemcpyHostToDevice));
     return RT_OK;
 }
 
@@ -290,11 +289,10 @@ template <class T> static int upload(SceneBag& b, T** dst, const T* src, size_t 
 }
 template <class T> static int upload(SceneBag& b, T** dst, const std::vector<T>& v) { return upload(b, dst, v.data(), v.size()); }
 
-static int collapse_uploaded(SceneBag& b, SceneArrays& sc, int extendVariant, const HostScene& in, const std::vector<collapse::Blas>& blas4, int& layout,
-                             int& stackEntries, std::vector<uint32_t>& roots);   // (below)
+static int collapse_uploaded(SceneBag& b, SceneArrays& sc, SceneFacts& facts, LiveTrees& live, int extendVariant, const HostScene& in,
+                             const std::vector<collapse::Blas>& blas4, std::vector<uint32_t>& roots);   // (below)
 
-int scenedev::upload_scene(SceneBag& b, int accel, int extendVariant, const HostScene& in, int stackEntries, int64_t texPad, int tlasDepth,
-                           const std::vector<collapse::Blas>* blas4)
+int scenedev::upload_scene(SceneBag& b, int accel, int extendVariant, const HostScene& in, SceneFacts facts, int64_t texPad, const std::vector<collapse::Blas>* blas4)
 {
     const auto& [prims, nPrims, mats, nMats, textures, nTexels, lights, nLights, bvhNodes, nNodes, primIdx, nIdx, tlas, nTlas, blas, nBlas] = in;
     // ---- derive.  Layout 1 (pair or quad records, triangle records, encoded roots) only when the encodings fit (rebuild_common.h,
@@ -302,17 +300,17 @@ int scenedev::upload_scene(SceneBag& b, int accel, int extendVariant, const Host
     const RtBVHNode2* n2 = (const RtBVHNode2*)bvhNodes; const RtBVHNode4* n4 = (const RtBVHNode4*)bvhNodes;
     std::vector<uint32_t> pairNode, roots((size_t)nBlas, 0u);
     std::vector<RtFloat4> pairs, quads;
-    int layout = 0;
+    LiveTrees live;
     if (accel == RT_ACCEL_BVH2) {
         uint32_t largestLeaf = 0;
         for (int32_t i = 0; i < nNodes; i++) largestLeaf = std::max(largestLeaf, n2[i].count);
-        if (rebuild::takes_layout1(extendVariant != 1, nIdx, largestLeaf)) { pairs = pair_records(n2, nNodes, blas, nBlas, pairNode, roots); layout = 1; }
+        if (rebuild::takes_layout1(extendVariant != 1, nIdx, largestLeaf)) { pairs = pair_records(n2, nNodes, blas, nBlas, pairNode, roots); facts.layout = 1; }
     } else if (blas4) {
         // (the layout follows from the collapse on the device, below)
     } else if (extendVariant != 1 && nIdx < rebuild::kMaxPackedIdx) {
         bool fits = true;
         for (int32_t i = 0; i < nNodes && fits; i++) for (int k = 0; k < 4; k++) if (n4[i].first[k] != RT_INVALID && n4[i].count[k] > (int32_t)rebuild::kMaxPackedLeaf) fits = false;
-        if (fits) { quads = quad_records(n4, nNodes, nIdx, blas, nBlas, roots); layout = 1; }
+        if (fits) { quads = quad_records(n4, nNodes, nIdx, blas, nBlas, roots); facts.layout = 1; facts.nQuads = (int32_t)(quads.size() / 8); }
     }
     // ---- copy to device
     SceneArrays sc{};
@@ -330,8 +328,8 @@ int scenedev::upload_scene(SceneBag& b, int accel, int extendVariant, const Host
     if (rc == RT_OK) rc = upload(b, &sc.blas, blas, (size_t)nBlas);
     if (rc == RT_OK) rc = upload(b, &sc.shadeRecs, shade_records(prims, nPrims));
     if (rc == RT_OK) rc = upload(b, &sc.lightRecs, light_records(prims, mats, lights, nLights));
-    if (rc == RT_OK && blas4) rc = collapse_uploaded(b, sc, extendVariant, in, *blas4, layout, stackEntries, roots);
-    else if (rc == RT_OK && layout == 1) {
+    if (rc == RT_OK && blas4) rc = collapse_uploaded(b, sc, facts, live, extendVariant, in, *blas4, roots);
+    else if (rc == RT_OK && facts.layout == 1) {
         rc = accel == RT_ACCEL_BVH4 ? upload(b, &sc.quads, quads) : upload(b, &sc.pairs, pairs);
         if (rc == RT_OK) rc = upload(b, &sc.triRecs, triangle_records(prims, primIdx, nIdx));
         if (rc == RT_OK) rc = upload(b, &sc.rootEntry, roots);
@@ -344,18 +342,18 @@ int scenedev::upload_scene(SceneBag& b, int accel, int extendVariant, const Host
     sc.tlasRoot = leafRoot ? refit::tlas_leaf_entry(false, tlas[0].BLASidx) : refit::tlas_node_entry(false, 0u);
     sc.tlasRootP = leafRoot ? refit::tlas_leaf_entry(true, tlas[0].BLASidx) : refit::tlas_node_entry(true, 0u);
     sc.nLights = nLights; sc.nPrims = nPrims; sc.nBlas = nBlas; sc.nTex = nTexels; sc.nMats = nMats;
-    // ---- bind: the copy's facts, and what updates and rebuilds need of this upload
-    b.sc = sc;
+    facts.nInterior = (int)pairNode.size(); facts.singleBlas = leafRoot;
+    // ---- bind: what updates and rebuilds need of this upload, then the arrays, the facts and the trees, each assigned once
     b.hMats.assign(mats, mats + nMats); b.texPad = texPad; b.texCap = (size_t)nTexels + (size_t)texPad;   // (rt_update_materials)
-    b.layout = layout; b.stackEntries = stackEntries; b.tlasDepth = tlasDepth; b.nInterior = (int)pairNode.size(); b.singleBlas = leafRoot;
-    if (!blas4) b.nQuads = (int32_t)(quads.size() / 8);
-    return prepare_update(b, accel, extendVariant, in, pairNode);
+    if ((rc = prepare_update(b, live, accel, extendVariant, in, pairNode)) != RT_OK) return rc;
+    b.sc = sc; b.facts = facts; b.live = std::move(live);
+    return RT_OK;
 }
 
 // rt_upload_scene_bvh2 on a BVH4 context, after the wire arrays are on the device: the collapse into sc.bvh4, then the layout, the stack
 // size and the layout-1 records (quads, root entries, triangle records) as rt_upload_scene derives them from the host's collapse
-static int collapse_uploaded(SceneBag& b, SceneArrays& sc, int extendVariant, const HostScene& in, const std::vector<collapse::Blas>& blas4, int& layout,
-                             int& stackEntries, std::vector<uint32_t>& roots)
+static int collapse_uploaded(SceneBag& b, SceneArrays& sc, SceneFacts& facts, LiveTrees& live, int extendVariant, const HostScene& in,
+                             const std::vector<collapse::Blas>& blas4, std::vector<uint32_t>& roots)
 {
     using namespace collapsedev;
     const char* who = "rt_upload_scene_bvh2";
@@ -365,29 +363,28 @@ static int collapse_uploaded(SceneBag& b, SceneArrays& sc, int extendVariant, co
     size_t quadCap = 0;   // a live node per interior node and leaf root at most
     for (const collapse::Blas& k : blas4) quadCap += std::max(k.interiors, 1u);
     int rc = dalloc(b.allocs, &sc.bvh4, (size_t)nNodes);
-    if (rc == RT_OK) rc = dalloc(b.allocs, &b.liveNewId, (size_t)nNodes);   // the copy's own: RT_REBUILD_REFIT reads them
-    if (rc == RT_OK) rc = dalloc(b.allocs, &b.liveQuadNode, quadCap);
+    if (rc == RT_OK) rc = dalloc(b.allocs, &live.newId, (size_t)nNodes);   // the copy's own: RT_REBUILD_REFIT reads them
+    if (rc == RT_OK) rc = dalloc(b.allocs, &live.quadNode, quadCap);
     if (rc == RT_OK) rc = collapse_scratch(b, (size_t)nNodes);
     if (rc != RT_OK) return rc;
-    Work w = collapse_work(b, b.liveNewId, b.liveQuadNode, quadCap);
+    Work w = collapse_work(b, live.newId, live.quadNode, quadCap);
     HIPCHK(begin(s, w, sc.bvh2, (uint32_t)nNodes, sc.bvh4));
     for (const collapse::Blas& k : blas4) HIPCHK(collapse_blas(s, w, sc.bvh2, (uint32_t)nNodes, k.root, k.interiors, k.height, sc.bvh4));
     CollapseStatus st;
     HIPCHK(st.read(s, w));
     HIPCHK(hipStreamSynchronize(s));
     if ((rc = st.error(who, "")) != RT_OK) return rc;
-    const uint32_t live = st.live();
-    b.nLive = live; b.c4Need = st.need();
-    layout = rebuild::takes_layout1(extendVariant != 1, nIdx, st.largest_leaf()) ? 1 : 0;
-    stackEntries = rebuild::stack_entries((int)std::max(st.need(), 1u));
-    b.nQuads = layout == 1 ? (int32_t)live : 0;
+    live.nLive = st.live(); live.c4Need = st.need();
+    facts.layout = rebuild::takes_layout1(extendVariant != 1, nIdx, st.largest_leaf()) ? 1 : 0;
+    facts.stackEntries = rebuild::stack_entries((int)std::max(st.need(), 1u));
+    facts.nQuads = facts.layout == 1 ? (int32_t)live.nLive : 0;
     b.keepsBvh2 = true;
-    if (layout != 1) return RT_OK;
-    rc = dalloc(b.allocs, &sc.quads, (size_t)std::max(live, 1u) * 8);
+    if (facts.layout != 1) return RT_OK;
+    rc = dalloc(b.allocs, &sc.quads, (size_t)std::max(live.nLive, 1u) * 8);
     if (rc == RT_OK) rc = dalloc(b.allocs, &sc.rootEntry, (size_t)nBlas);
     if (rc == RT_OK) rc = dalloc(b.allocs, &sc.triRecs, (size_t)nIdx * 3);
     if (rc != RT_OK) return rc;
-    w.quadCap = std::min(w.quadCap, std::max(live, 1u));   // what sc.quads holds
+    w.quadCap = std::min(w.quadCap, std::max(live.nLive, 1u));   // what sc.quads holds
     HIPCHK(finish(s, w, sc.bvh4, (uint32_t)nNodes, (uint32_t)nIdx, (const uint32_t*)sc.blas, (uint32_t)(sizeof(RtBVHInstance) / 4), (uint32_t)nBlas, sc.quads, sc.rootEntry));
     HIPCHK(refitdev::launch_records(s, sc.prims, sc.bvh2, sc.primIdx, (uint32_t)nIdx, sc.lights, (uint32_t)in.nLights, 0u, (uint32_t)in.nPrims, nullptr, 0u, nullptr,
                                     sc.triRecs, sc.shadeRecs, sc.lightRecs));
@@ -409,7 +406,7 @@ size_t scenedev::rebuild_initial_cap(const SceneBag& b)
         const long long k = atoll(env);
         if (k > 0) return (size_t)std::min<long long>(k, 1ll << 30);
     }
-    return (size_t)std::max(b.nPrims, 1);
+    return (size_t)std::max(b.sc.nPrims, 1);
 }
 // (flags / ranks / newId: a word per node, the frontiers: per interior node)
 int scenedev::rebuild_scratch(SceneBag& b, size_t nodeNeed)
@@ -482,16 +479,15 @@ int scenedev::too_many_nodes(const char* who)
 {
     return fail(RT_E_UNSUPPORTED, "%s: the new trees have 2^31 nodes or index slots, or more; the scene is unchanged", who);
 }
-void scenedev::write_blocks(const std::vector<rebuild::BlasRange>& ranges, const std::vector<rebuild::BlasBlock>& blocks, int32_t* n, int32_t* primFirst,
-                            int32_t* primCount, int32_t* nodes, int32_t* idxSlots, int32_t* compact, int32_t cap)
+void scenedev::write_blocks(const LiveTrees& t, int32_t* n, int32_t* primFirst, int32_t* primCount, int32_t* nodes, int32_t* idxSlots, int32_t* compact, int32_t cap)
 {
-    if (n) *n = (int32_t)ranges.size();
-    for (size_t k = 0; k < ranges.size() && (int64_t)k < (int64_t)cap; k++) {
-        if (primFirst) primFirst[k] = (int32_t)ranges[k].first;
-        if (primCount) primCount[k] = (int32_t)ranges[k].count;
-        if (nodes) nodes[k] = (int32_t)blocks[k].nodes;
-        if (idxSlots) idxSlots[k] = (int32_t)blocks[k].idxSlots;
-        if (compact) compact[k] = blocks[k].compact;
+    if (n) *n = (int32_t)t.ranges.size();
+    for (size_t k = 0; k < t.ranges.size() && (int64_t)k < (int64_t)cap; k++) {
+        if (primFirst) primFirst[k] = (int32_t)t.ranges[k].first;
+        if (primCount) primCount[k] = (int32_t)t.ranges[k].count;
+        if (nodes) nodes[k] = (int32_t)t.block[k].nodes;
+        if (idxSlots) idxSlots[k] = (int32_t)t.block[k].idxSlots;
+        if (compact) compact[k] = t.block[k].compact;
     }
 }
 
@@ -500,8 +496,8 @@ void scenedev::write_blocks(const std::vector<rebuild::BlasRange>& ranges, const
 int scenedev::blas_blocks(const SceneBag& b, int32_t* n, int32_t* primFirst, int32_t* primCount, int32_t* nodes, int32_t* idxSlots, int32_t* compact, int32_t cap)
 {
     if (b.rebuildRefusal) return fail(RT_E_UNSUPPORTED, "rt_scene_blas_blocks: %s", b.rebuildRefusal);
-    if (b.blasBlock.size() != b.ranges.size()) return fail(RT_E_UNSUPPORTED, "rt_scene_blas_blocks: %s", b.refitRefusal ? b.refitRefusal : "the scene's BLAS ranges are not known");
-    write_blocks(b.ranges, b.blasBlock, n, primFirst, primCount, nodes, idxSlots, compact, cap);
+    if (b.live.block.size() != b.live.ranges.size()) return fail(RT_E_UNSUPPORTED, "rt_scene_blas_blocks: %s", b.refitRefusal ? b.refitRefusal : "the scene's BLAS ranges are not known");
+    write_blocks(b.live, n, primFirst, primCount, nodes, idxSlots, compact, cap);
     return RT_OK;
 }
 int64_t scenedev::rebuild_allocations(const SceneBag& b) { return (int64_t)(b.rallocs + sbvhdev::pool_allocations(b.spool)); }
@@ -523,36 +519,36 @@ extern "C" int rt_blas_ranges(const RtBVHNode2* nodes, int32_t nNodes, const uin
 extern "C" int rt_blas_blocks(const RtBVHNode2* nodes, int32_t nNodes, const uint32_t* primIdx, int32_t nIdx, int32_t nPrims, const RtBVHInstance* blas, int32_t nBlas,
                               int32_t* n, int32_t* primFirst, int32_t* primCount, int32_t* nodesOut, int32_t* idxSlots, int32_t* compact, int32_t cap)
 {
-    std::vector<rebuild::BlasRange> ranges; std::vector<int32_t> instBlas;
-    if (const char* why = rebuild::find_blas_ranges(nodes, nNodes, primIdx, nIdx, nPrims, blas, nBlas, ranges, instBlas))
+    LiveTrees t;
+    if (const char* why = rebuild::find_blas_ranges(nodes, nNodes, primIdx, nIdx, nPrims, blas, nBlas, t.ranges, t.instBlas))
         return fail(why == std::string("missing array") ? RT_E_INVALID : RT_E_UNSUPPORTED, "rt_blas_blocks: %s", why);
-    std::vector<rebuild::BlasBlock> blocks;
-    rebuild::find_blas_blocks(nodes, ranges, blocks);
-    write_blocks(ranges, blocks, n, primFirst, primCount, nodesOut, idxSlots, compact, cap);
+    rebuild::find_blas_blocks(nodes, t.ranges, t.block);
+    write_blocks(t, n, primFirst, primCount, nodesOut, idxSlots, compact, cap);
     return RT_OK;
 }
 int scenedev::scene_array(const SceneBag& b, int32_t which, const void** src, size_t* n)
 {
     const SceneArrays& sc = b.sc;
+    const LiveTrees& t = b.live;
     switch (which) {
-    case RT_SCENE_PRIMS:        *src = sc.prims; *n = sizeof(RtPrimitive) * (size_t)b.nPrims; break;
+    case RT_SCENE_PRIMS:        *src = sc.prims; *n = sizeof(RtPrimitive) * (size_t)sc.nPrims; break;
     case RT_SCENE_BVH:          *src = b.accel == RT_ACCEL_BVH4 ? (const void*)sc.bvh4 : (const void*)sc.bvh2;
-                                *n = (b.accel == RT_ACCEL_BVH4 ? sizeof(RtBVHNode4) : sizeof(RtBVHNode2)) * (size_t)b.nNodes; break;
-    case RT_SCENE_TLAS:         *src = sc.tlas; *n = sizeof(RtTLASNode) * (size_t)b.nTlas; break;
-    case RT_SCENE_INSTANCES:    *src = sc.blas; *n = sizeof(RtBVHInstance) * (size_t)b.nBlas; break;
-    case RT_SCENE_PAIRS:        *src = sc.pairs; *n = sc.pairs ? sizeof(RtFloat4) * 4 * (size_t)b.nPairs : 0; break;
-    case RT_SCENE_TRI_RECS:     *src = sc.triRecs; *n = sc.triRecs ? sizeof(RtFloat4) * 3 * (size_t)b.nIdx : 0; break;
-    case RT_SCENE_SHADE_RECS:   *src = sc.shadeRecs; *n = sizeof(RtFloat4) * (size_t)b.nPrims; break;
-    case RT_SCENE_LIGHT_RECS:   *src = sc.lightRecs; *n = sizeof(RtFloat4) * 8 * (size_t)b.nLights; break;
-    case RT_SCENE_TLAS_PAIRS:   *src = sc.tlasPairs; *n = sizeof(RtFloat4) * 4 * (size_t)b.nTlas; break;
-    case RT_SCENE_TLAS_PAIRS_P: *src = sc.tlasPairsP; *n = sizeof(RtFloat4) * 4 * (size_t)b.nTlas; break;
-    case RT_SCENE_INST_RECS:    *src = sc.instRecs; *n = sizeof(RtFloat4) * 4 * (size_t)b.nBlas; break;
-    case RT_SCENE_QUADS:        *src = sc.quads; *n = sc.quads ? sizeof(RtFloat4) * 8 * (size_t)std::max(b.nQuads, 1) : 0; break;
-    case RT_SCENE_ROOT_ENTRY:   *src = sc.rootEntry; *n = sc.rootEntry ? sizeof(uint32_t) * (size_t)b.nBlas : 0; break;
-    case RT_SCENE_LIGHTS:       *src = sc.lights; *n = sizeof(uint32_t) * (size_t)b.nLights; break;
+                                *n = (b.accel == RT_ACCEL_BVH4 ? sizeof(RtBVHNode4) : sizeof(RtBVHNode2)) * (size_t)t.nNodes; break;
+    case RT_SCENE_TLAS:         *src = sc.tlas; *n = sizeof(RtTLASNode) * (size_t)t.nTlas; break;
+    case RT_SCENE_INSTANCES:    *src = sc.blas; *n = sizeof(RtBVHInstance) * (size_t)sc.nBlas; break;
+    case RT_SCENE_PAIRS:        *src = sc.pairs; *n = sc.pairs ? sizeof(RtFloat4) * 4 * (size_t)t.nPairs : 0; break;
+    case RT_SCENE_TRI_RECS:     *src = sc.triRecs; *n = sc.triRecs ? sizeof(RtFloat4) * 3 * (size_t)t.nIdx : 0; break;
+    case RT_SCENE_SHADE_RECS:   *src = sc.shadeRecs; *n = sizeof(RtFloat4) * (size_t)sc.nPrims; break;
+    case RT_SCENE_LIGHT_RECS:   *src = sc.lightRecs; *n = sizeof(RtFloat4) * 8 * (size_t)sc.nLights; break;
+    case RT_SCENE_TLAS_PAIRS:   *src = sc.tlasPairs; *n = sizeof(RtFloat4) * 4 * (size_t)t.nTlas; break;
+    case RT_SCENE_TLAS_PAIRS_P: *src = sc.tlasPairsP; *n = sizeof(RtFloat4) * 4 * (size_t)t.nTlas; break;
+    case RT_SCENE_INST_RECS:    *src = sc.instRecs; *n = sizeof(RtFloat4) * 4 * (size_t)sc.nBlas; break;
+    case RT_SCENE_QUADS:        *src = sc.quads; *n = sc.quads ? sizeof(RtFloat4) * 8 * (size_t)std::max(b.facts.nQuads, 1) : 0; break;
+    case RT_SCENE_ROOT_ENTRY:   *src = sc.rootEntry; *n = sc.rootEntry ? sizeof(uint32_t) * (size_t)sc.nBlas : 0; break;
+    case RT_SCENE_LIGHTS:       *src = sc.lights; *n = sizeof(uint32_t) * (size_t)sc.nLights; break;
     case RT_SCENE_MATERIALS:    *src = sc.mats; *n = sizeof(RtMaterial) * (size_t)sc.nMats; break;
     case RT_SCENE_TEXTURES:     *src = sc.tex; *n = sizeof(RtFloat4) * ((size_t)sc.nTex + (size_t)b.texPad); break;
-    case RT_SCENE_BVH2_KEPT:    *src = sc.bvh2; *n = b.keepsBvh2 ? sizeof(RtBVHNode2) * (size_t)b.nNodes : 0; break;
+    case RT_SCENE_BVH2_KEPT:    *src = sc.bvh2; *n = b.keepsBvh2 ? sizeof(RtBVHNode2) * (size_t)t.nNodes : 0; break;
     default: return fail(RT_E_INVALID, "rt_debug_get_scene_array: unknown array %d", which);
     }
     return RT_OK;

@@ -54,8 +54,8 @@ hipError_t launch_records(hipStream_t s, const RtPrimitive* prims, const RtBVHNo
 struct RtCtx;
 namespace scenedev __attribute__((visibility("hidden"))) {   // (nothing of this interface is exported from the library)
 
-// The arrays of a copy as their owner writes them: DevScene (rt355_dev.h, a header without kernels that this file could include: the
-// twin is not needed for that any more) field for field and in its order, writable and in the wire types; a context turns them into the kernels' read-only view when it takes the copy over (rt355.hip, adopt_scene).
+// The arrays of a copy as their owner writes them: DevScene (rt355_dev.h) field for field and in its order, writable and in the wire types.
+// A context turns them into the kernels' read-only view when it takes the copy over (rt355.hip, adopt_scene).
 struct SceneArrays {
     RtPrimitive* prims; RtMaterial* mats; RtFloat4* tex; uint32_t* lights; RtBVHNode2* bvh2; RtBVHNode4* bvh4; uint32_t* primIdx;
     RtTLASNode* tlas; RtBVHInstance* blas;
@@ -63,29 +63,47 @@ struct SceneArrays {
     RtFloat4* tlasPairsP; uint32_t tlasRootP; RtFloat4 *lightRecs, *quads;
     int32_t nLights, nPrims, nBlas, nTex, nMats;
 };
-
+// What a holder plans its traversal from (trav_common.h): the bag has one, a context (RtCtx) the one it adopted
+struct SceneFacts {
+    int layout = 0;                           // 0 = traverse the reference arrays as uploaded, 1 = derived pair/triangle-record layout
+    int stackEntries = RT_BVH2_STACK, tlasDepth = 0, nInterior = 0;   // LDS stack entries the trees need; TLAS height; records of the dense pair table
+    int32_t nQuads = 0; bool singleBlas = false;   // quad records (the surviving nodes of a BVH4 in layout 1); the TLAS root is a leaf
+};
+// The trees a copy renders from: found at upload, built anew by a rebuild (Pending::next, scene_rebuild.hip) and committed whole
+struct LiveTrees {
+    uint32_t nNodes = 0, nIdx = 0, nPairs = 0, nTlas = 0, nLeaves = 0, nReach = 0;   // (nPairs: of the bound pair table; nReach: nodes a refit visits)
+    uint32_t *parent = nullptr, *leaves = nullptr, *pairNode = nullptr, *tickets = nullptr;   // refit topology (walked from the BLAS roots)
+    // One record per bound BLAS, in two halves of rebuild_common.h's types (check_plan and check_ranges take them): ranges[k] its
+    // primitives (in increasing order) and its root, block[k] the nodes and index slots the live tree occupies (an SBVH tree has more
+    // slots than primitives), whether it can move as one (RT_REBUILD_KEEP) and its height.  A refit leaves them.
+    std::vector<rebuild::BlasRange> ranges; std::vector<rebuild::BlasBlock> block;
+    std::vector<int32_t> instBlas;            // instance -> its range
+    uint32_t interiors(size_t k) const { return (block[k].nodes - 1) / 2; }   // interior nodes of BLAS k
+    // ... and beside it where the derived data of BLAS k lie: the start of its run of pair ids (interiors of them; BLAS by BLAS in the order
+    // in which the instances first name them) and the start of its run in the leaf list (interiors + 1 of them; after an upload the
+    // runs come in that same order, after a rebuild in range order - the order inside a run is no contract).  rt_rebuild_ranges moves a
+    // kept or refit BLAS's derived data by them.
+    std::vector<uint32_t> pairLo, leafLo;
+    // The live collapse of a BVH4 copy that keeps its BVH2: node -> live id and live id -> node (the upload's own arrays or the live
+    // set's, never scratch: a refused call in between must leave them), the live nodes and the stack need as the collapse counted it
+    uint32_t *newId = nullptr, *quadNode = nullptr, nLive = 0, c4Need = 0;
+};
 // The device copy of a scene (uploaded arrays + derived layouts).  Contexts that render the same scene - sample-stream lanes, the
 // row bands of one frame - can hold ONE copy (rt_share_scene): less HBM, and one working set in the L2s / Infinity Cache instead of one per context.
 struct SceneBag {
-    std::vector<void*> allocs;                // what is made once and lives as long as the copy
-    int device = 0;
-    // What a holder renders with, written by upload, update and rebuild only; a context takes these over in adopt_scene (rt355.hip)
-    SceneArrays sc{};                         // the device arrays (an update rewrites them in place, a rebuild swaps them)
-    int layout = 0;                           // 0 = traverse the reference arrays as uploaded, 1 = derived pair/triangle-record layout
-    int stackEntries = RT_BVH2_STACK, tlasDepth = 0, nInterior = 0;   // LDS stack entries the trees need; TLAS height; records of the dense pair table
-    bool singleBlas = false;                  // the TLAS root is a leaf
+    std::vector<void*> allocs; int device = 0;   // what is made once and lives as long as the copy; the device it lies on
+    // What a holder renders with, each written whole by upload and by the commits of update, rebuild and material update only; a context
+    // takes sc and facts over in adopt_scene (rt355.hip)
+    SceneArrays sc{};                         // the device arrays and their counts (an update rewrites them in place, a rebuild swaps them)
+    SceneFacts facts; LiveTrees live;
     uint64_t generation = 0;                  // bumped when an update or a rebuild changes any of them
     std::vector<RtCtx*> holders;              // the contexts rendering from this copy
     int wait_holders() const;                 // rt355.hip: until `stream` and `home` of every holder are idle (before a commit)
     // rt_update_scene: what an in-place update needs of the upload, kept beside the device copy
     const char* refitRefusal = nullptr;       // why this scene cannot be updated in place (NULL: it can)
-    int32_t nPrims = 0, nNodes = 0, nIdx = 0, nLights = 0, nTlas = 0, nBlas = 0, nPairs = 0, accel = 0;
-    int32_t nQuads = 0;                       // quad records (the surviving nodes of a BVH4 in layout 1)
-    bool keepsBvh2 = false;                   // a BVH4 copy bound with its BVH2 (rt_upload_scene_bvh2): sc.bvh2 is kept, the copy can be rebuilt
+    int32_t accel = 0; bool keepsBvh2 = false;   // a BVH4 copy bound with its BVH2 (rt_upload_scene_bvh2): sc.bvh2 is kept, the copy can be rebuilt
     std::vector<int32_t> primType, primMat;   // host shadow of every primitive's objType / matIdx (the light list and materials depend on them)
     std::vector<RtBVHInstance> inst;          // the instances as last uploaded or updated
-    uint32_t *dParent = nullptr, *dLeaves = nullptr, *dPairNode = nullptr, *dTickets = nullptr;   // refit topology (walked from the BLAS roots)
-    uint32_t nLeaves = 0, nReach = 0;
     // A device array that is replaced during the copy's life (rebuild_grow, below, is the one place that does) and freed with it
     template <class T> struct Grown {
         T* p = nullptr; size_t cap = 0;
@@ -101,25 +119,8 @@ struct SceneBag {
     hipEvent_t ev[4] = { nullptr, nullptr, nullptr, nullptr };   // brackets of the staging and of the commit
     // rt_rebuild_scene: what it needs of the upload, and its device memory (allocated by the first rebuilds, then reused)
     const char* rebuildRefusal = nullptr;     // why this scene cannot be rebuilt in place (NULL: it can)
-    std::vector<rebuild::BlasRange> ranges;   // the primitive range and the root of every distinct BLAS, in increasing order
-    std::vector<int32_t> instBlas;            // instance -> its range
     bool variantLayout1 = false;              // the holders' extend_variant admits the derived layout 1
-    // One record per bound BLAS, in two halves of rebuild_common.h's types (check_plan and check_ranges take them): ranges[k] its
-    // primitives and its root (above; every commit that moves a tree writes the root), blasBlock[k] the nodes and index slots the live
-    // tree occupies (an SBVH tree has more slots than primitives), whether it can move as one (RT_REBUILD_KEEP) and its height.  Found
-    // at upload, reported by the builders at a rebuild; a refit leaves them.
-    std::vector<rebuild::BlasBlock> blasBlock;
-    uint32_t blas_interiors(size_t k) const { return (blasBlock[k].nodes - 1) / 2; }   // interior nodes of BLAS k
-    // ... and beside it where the derived data of BLAS k lie: the start of its run of pair ids (interiors of them; BLAS by BLAS in the order
-    // in which the instances first name them) and the start of its run in the leaf list (interiors + 1 of them; after an upload the
-    // runs come in that same order, after a rebuild in range order - the order inside a run is no contract).  Written at upload and by
-    // every commit that moves a tree; rt_rebuild_ranges moves a kept or refit BLAS's derived data by them.
-    std::vector<uint32_t> blasPairLo, blasLeafLo;
     RtRangesInfo rangesInfo{};                // the last successful rt_rebuild_ranges (rt_ranges_info)
-    // The live collapse of a BVH4 copy that keeps its BVH2: node -> live id and live id -> node (the upload's own arrays or the live
-    // set's, never scratch: a refused call in between must leave them), the live nodes and the stack need as the collapse counted it
-    uint32_t *liveNewId = nullptr, *liveQuadNode = nullptr;
-    uint32_t nLive = 0, c4Need = 0;
     RtRefitInfo refitInfo{};                  // the last successful RT_REBUILD_REFIT (rt_refit_info)
     // Everything a rebuild changes, twice: a rebuild writes the set that is not live and the commit swaps the pointers; the upload's own
     // arrays stay behind until the copy is freed.  The arrays that scale with the primitives, the instances and the lights fit the bound
@@ -181,16 +182,15 @@ struct HostScene {   // the host arrays of rt_upload_scene (include/rt355.h), in
     const RtPrimitive* prims; int32_t nPrims; const RtMaterial* mats; int32_t nMats; const RtFloat4* textures; int32_t nTexels; const uint32_t* lights; int32_t nLights;
     const void* bvhNodes; int32_t nNodes; const uint32_t* primIdx; int32_t nIdx; const RtTLASNode* tlas; int32_t nTlas; const RtBVHInstance* blas; int32_t nBlas;
 };
-int validate_scene(int accel, const HostScene& in, int* stackEntriesOut, int64_t* texPadOut, int* tlasDepthOut);
-// fills a fresh copy on the current device from arrays that have passed validate_scene, which gave the last three arguments
+int validate_scene(int accel, const HostScene& in, SceneFacts* factsOut, int64_t* texPadOut);   // (of the facts: stackEntries and tlasDepth)
+// fills a fresh copy on the current device from arrays that have passed validate_scene, which began `facts` and gave texPad
 // blas4 != NULL (a BVH4 context, in.bvhNodes is the BVH2; collapse::check_args gave the BLAS): the BVH2 is kept and collapsed on the device
-int upload_scene(SceneBag& b, int accel, int extendVariant, const HostScene& in, int stackEntries, int64_t texPad, int tlasDepth,
-                 const std::vector<collapse::Blas>* blas4 = nullptr);
+int upload_scene(SceneBag& b, int accel, int extendVariant, const HostScene& in, SceneFacts facts, int64_t texPad, const std::vector<collapse::Blas>* blas4 = nullptr);
 // ---- scene_rebuild.hip
 int update_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas, RtUpdateStats* stats);
 int rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
                   int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats);
-// rt_rebuild_ranges (include/rt355.h): plan[nRanges], one RT_REBUILD_SAH / LBVH / SBVH / KEEP / REFIT_RANGE per distinct BLAS in the order of b.ranges
+// rt_rebuild_ranges (include/rt355.h): plan[nRanges], one RT_REBUILD_SAH / LBVH / SBVH / KEEP / REFIT_RANGE per distinct BLAS in the order of b.live.ranges
 int rebuild_ranges(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
                    const int32_t* plan, int32_t nRanges, const RtBuildOptions* opts, RtRebuildStats* stats);
 // rt_scene_blas_blocks: the ranges and blocks of the bound trees (any output may be NULL; at most cap entries are written)
@@ -267,8 +267,7 @@ struct CollapseStatus {
 // "the new trees have 2^31 nodes or index slots, or more": the refusal of a rebuild whose trees outgrow the 31-bit ids
 int too_many_nodes(const char* who);
 // the outputs of rt_blas_blocks / rt_scene_blas_blocks (any may be NULL; at most cap entries are written)
-void write_blocks(const std::vector<rebuild::BlasRange>& ranges, const std::vector<rebuild::BlasBlock>& blocks, int32_t* n, int32_t* primFirst, int32_t* primCount,
-                  int32_t* nodes, int32_t* idxSlots, int32_t* compact, int32_t cap);
+void write_blocks(const LiveTrees& t, int32_t* n, int32_t* primFirst, int32_t* primCount, int32_t* nodes, int32_t* idxSlots, int32_t* compact, int32_t cap);
 inline double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b)
 {
     return std::chrono::duration<double, std::milli>(b - a).count();

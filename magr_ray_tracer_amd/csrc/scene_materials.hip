@@ -36,15 +36,15 @@ int scenedev::update_materials(SceneBag& b, const RtMaterialUpdate& u, RtMateria
     const int32_t oldTex = sc.nTex, nTex = u.nTexels < 0 ? sc.nTex : u.nTexels;
     if (u.texels && (int64_t)u.texFirst + u.texCount > (int64_t)nTex)
         return fail(RT_E_INVALID, "%s: texel range [%d, %lld) outside the new atlas of %d texels", who, u.texFirst, (long long)u.texFirst + u.texCount, nTex);
-    if (u.primMat && (int64_t)u.primFirst + u.primCount > (int64_t)b.nPrims)
-        return fail(RT_E_INVALID, "%s: primitive range [%d, %lld) outside the %d bound", who, u.primFirst, (long long)u.primFirst + u.primCount, b.nPrims);
+    if (u.primMat && (int64_t)u.primFirst + u.primCount > (int64_t)sc.nPrims)
+        return fail(RT_E_INVALID, "%s: primitive range [%d, %lld) outside the %d bound", who, u.primFirst, (long long)u.primFirst + u.primCount, sc.nPrims);
     const bool writeTex = u.texels && u.texCount > 0, assign = u.primMat && u.primCount > 0;
     const int32_t nMats = newTable ? u.nMats : sc.nMats;
     int64_t texPad = b.texPad;
     if (newTable || nTex != oldTex)   // (mats NULL: the bound table, from its host shadow, against a new atlas length)
         if (const int rc = materials_check(who, newTable ? u.mats : b.hMats.data(), nMats, nTex, &texPad)) return rc;
     const bool lightsChange = newTable || assign, padChange = nTex != oldTex || texPad != b.texPad;
-    if (stats) { *stats = RtMaterialStats{}; stats->lights = b.nLights; }
+    if (stats) { *stats = RtMaterialStats{}; stats->lights = sc.nLights; }
     if (!lightsChange && !writeTex && !padChange) return RT_OK;   // nothing to do: nothing is touched
     HIPCHK(hipSetDevice(b.device));
     if (const int rc = scene_stream(b, b.rev)) return rc;
@@ -57,7 +57,7 @@ int scenedev::update_materials(SceneBag& b, const RtMaterialUpdate& u, RtMateria
     const bool moveTex = texNeed > b.texCap;
     if (lightsChange) {
         if (!b.rStatus) { if (const int rc = dalloc(b.allocs, &b.rStatus, 2)) return rc; b.rallocs++; }
-        if (const int rc = rebuild_scratch(b, (size_t)b.nPrims)) return rc;   // (flags and ranks: a word per primitive)
+        if (const int rc = rebuild_scratch(b, (size_t)sc.nPrims)) return rc;   // (flags and ranks: a word per primitive)
         if (newTable) if (const int rc = rebuild_fit(b, M, (size_t)nMats, "the material table")) return rc;
         if (assign) if (const int rc = rebuild_fit(b, b.mAssign, (size_t)u.primCount, "the new matIdx values")) return rc;
     }
@@ -65,7 +65,7 @@ int scenedev::update_materials(SceneBag& b, const RtMaterialUpdate& u, RtMateria
     // ---- stage, in memory no holder reads: the table, the new assignment (one path for host and device input), the light list and the
     // complete light records under both; an atlas that has to move, whole
     HIPCHK(hipEventRecord(b.rev[0], s));
-    int32_t nLights = b.nLights;
+    int32_t nLights = sc.nLights;
     const int32_t* dAssign = nullptr;
     if (lightsChange) {
         const RtMaterial* dMats = sc.mats;
@@ -73,9 +73,9 @@ int scenedev::update_materials(SceneBag& b, const RtMaterialUpdate& u, RtMateria
         if (assign) { HIPCHK(hipMemcpyAsync(b.mAssign.p, u.primMat, sizeof(int32_t) * (size_t)u.primCount, hipMemcpyDefault, s)); dAssign = b.mAssign.p; }
         uint32_t* bad = (uint32_t*)b.rStatus;
         const uint32_t first = (uint32_t)u.primFirst, count = assign ? (uint32_t)u.primCount : 0u;
-        HIPCHK(rebuilddev::mat_flags(s, b.dw, sc.prims, (uint32_t)b.nPrims, dAssign, first, count, dMats, nMats, bad));
+        HIPCHK(rebuilddev::mat_flags(s, b.dw, sc.prims, (uint32_t)sc.nPrims, dAssign, first, count, dMats, nMats, bad));
         uint32_t firstBad = resize::kNoBad;
-        if (const int rc = flag_scan_result(b, b.nPrims, &firstBad, &nLights)) return rc;
+        if (const int rc = flag_scan_result(b, sc.nPrims, &firstBad, &nLights)) return rc;
         if (firstBad != resize::kNoBad) {   // a new value out of range, or a bound primitive the new, shorter table no longer serves
             int32_t mat = 0;
             const bool inRange = dAssign && firstBad - first < count;
@@ -85,7 +85,7 @@ int scenedev::update_materials(SceneBag& b, const RtMaterialUpdate& u, RtMateria
         int rc = rebuild_fit(b, L.lights, (size_t)nLights, "the light list");
         if (rc == RT_OK) rc = rebuild_fit(b, L.lightRecs, std::max<size_t>((size_t)nLights, 1) * 8, "light records");
         if (rc != RT_OK) return rc;
-        HIPCHK(rebuilddev::mat_emit(s, b.dw, sc.prims, (uint32_t)b.nPrims, dAssign, first, count, dMats, (uint32_t)nLights, L.lights.p, L.lightRecs.p));
+        HIPCHK(rebuilddev::mat_emit(s, b.dw, sc.prims, (uint32_t)sc.nPrims, dAssign, first, count, dMats, (uint32_t)nLights, L.lights.p, L.lightRecs.p));
     }
     if (moveTex) {   // the kept part device to device, the rest and the pad zero, then the range
         const size_t keep = (size_t)std::min(oldTex, nTex);
@@ -109,8 +109,7 @@ int scenedev::update_materials(SceneBag& b, const RtMaterialUpdate& u, RtMateria
     SceneArrays n = b.sc;
     if (newTable) { n.mats = M.p; n.nMats = nMats; b.mmatsNext ^= 1; b.hMats.assign(u.mats, u.mats + nMats); }
     if (lightsChange) {
-        n.lights = L.lights.p; n.lightRecs = L.lightRecs.p; n.nLights = nLights;
-        b.nLights = nLights; b.mlightsNext ^= 1;
+        n.lights = L.lights.p; n.lightRecs = L.lightRecs.p; n.nLights = nLights; b.mlightsNext ^= 1;
         b.lightsInSet = true;   // later rebuilds carry the list from set to set, as after a resize
     }
     if (moveTex) { n.tex = T.p; b.texCap = T.cap; b.mtexNext ^= 1; }

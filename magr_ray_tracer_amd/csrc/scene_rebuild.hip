@@ -15,8 +15,8 @@ static int check_change(const char* who, const SceneBag& b, const RtPrimitive* p
                         const char* typeSuffix)
 {
     if (count < 0 || (count > 0 && !prims)) return fail(RT_E_INVALID, "%s: bad primitive count %d / NULL records", who, count);
-    if (count > 0 && (first < 0 || (int64_t)first + count > (int64_t)b.nPrims))
-        return fail(RT_E_INVALID, "%s: primitive range [%d, %lld) outside the %d uploaded", who, first, (long long)first + count, b.nPrims);
+    if (count > 0 && (first < 0 || (int64_t)first + count > (int64_t)b.sc.nPrims))
+        return fail(RT_E_INVALID, "%s: primitive range [%d, %lld) outside the %d uploaded", who, first, (long long)first + count, b.sc.nPrims);
     for (int32_t i = 0; i < count; i++) {
         const size_t g = (size_t)first + (size_t)i;
         if (prims[i].objType != b.primType[g] || prims[i].matIdx != b.primMat[g])
@@ -24,7 +24,7 @@ static int check_change(const char* who, const SceneBag& b, const RtPrimitive* p
                         b.primType[g], b.primMat[g], prims[i].objType, prims[i].matIdx, typeSuffix);
     }
     if (blas) {
-        if (nBlas != b.nBlas) return fail(RT_E_INVALID, "%s: %d instances given, %d uploaded", who, nBlas, b.nBlas);
+        if (nBlas != b.sc.nBlas) return fail(RT_E_INVALID, "%s: %d instances given, %d uploaded", who, nBlas, b.sc.nBlas);
         for (int32_t k = 0; k < nBlas; k++) {
             if (blas[k].bvhIdx != b.inst[(size_t)k].bvhIdx) return fail(RT_E_INVALID, "%s: instance %d changes its bvhIdx", who, k);
             if (refit::singular(blas[k].invT)) return fail(RT_E_INVALID, "%s: instance %d: the transform is singular", who, k);
@@ -45,6 +45,9 @@ static int tlas_status_error(const char* who, const int32_t status[2])
 int scenedev::update_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas, RtUpdateStats* stats)
 {
     const char* who = "rt_update_scene";
+    const SceneArrays& sc = b.sc;
+    const LiveTrees& lt = b.live;
+    const bool layout1 = b.facts.layout == 1;
     // ---- refusals: before anything is written
     if (b.refitRefusal) return fail(RT_E_UNSUPPORTED, "rt_update_scene: %s", b.refitRefusal);
     if (const int rc = check_change(who, b, prims, first, count, blas, nBlas, ": topology must not change")) return rc;
@@ -52,32 +55,31 @@ int scenedev::update_scene(SceneBag& b, const RtPrimitive* prims, int32_t first,
     // ---- staging buffers (the first update makes them; one after a resize that outgrew them replaces them)
     if (const int rc = scene_stream(b, b.ev)) return rc;   // (a rebuild may have made the stream already)
     {
-        int rc = rebuild_fit(b, b.sPrims, (size_t)b.nPrims, "the staging primitives");
-        if (rc == RT_OK) rc = rebuild_fit(b, b.sInst, (size_t)b.nBlas, "the staging instances");
-        if (rc == RT_OK) rc = rebuild_fit(b, b.sTlas, (size_t)b.nTlas, "the staging TLAS");
-        if (rc == RT_OK) rc = rebuild_fit(b, b.sTp, (size_t)b.nTlas * 4, "the staging TLAS records");
-        if (rc == RT_OK) rc = rebuild_fit(b, b.sTpP, (size_t)b.nTlas * 4, "the staging TLAS records");
-        if (rc == RT_OK) rc = rebuild_fit(b, b.sIr, (size_t)b.nBlas * 4, "the staging instance records");
+        int rc = rebuild_fit(b, b.sPrims, (size_t)sc.nPrims, "the staging primitives");
+        if (rc == RT_OK) rc = rebuild_fit(b, b.sInst, (size_t)sc.nBlas, "the staging instances");
+        if (rc == RT_OK) rc = rebuild_fit(b, b.sTlas, (size_t)lt.nTlas, "the staging TLAS");
+        if (rc == RT_OK) rc = rebuild_fit(b, b.sTp, (size_t)lt.nTlas * 4, "the staging TLAS records");
+        if (rc == RT_OK) rc = rebuild_fit(b, b.sTpP, (size_t)lt.nTlas * 4, "the staging TLAS records");
+        if (rc == RT_OK) rc = rebuild_fit(b, b.sIr, (size_t)sc.nBlas * 4, "the staging instance records");
         if (rc == RT_OK && !b.sStatus) { rc = dalloc(b.allocs, &b.sStatus, 2); if (rc == RT_OK) b.rallocs++; }
         if (rc != RT_OK) return rc;
     }
-    if (!b.sNodes.p || (size_t)b.nNodes > b.sNodes.cap) {
+    if (!b.sNodes.p || (size_t)lt.nNodes > b.sNodes.cap) {
         // the staging nodes: at first room for every tree the SAH and the linear builder can bind later; an SBVH rebuild may bind more
         // nodes than that, then the array grows as the rebuild's sets do (nothing in it outlives a call)
-        const size_t n = (size_t)b.nNodes, cap = b.sNodes.p ? with_headroom(n) : std::max(n, 2 * rebuild_initial_cap(b));
+        const size_t n = (size_t)lt.nNodes, cap = b.sNodes.p ? with_headroom(n) : std::max(n, 2 * rebuild_initial_cap(b));
         if (const int rc = rebuild_grow(b, b.sNodes, cap, 0, "the staging nodes", "rt_update_scene: %zu staging nodes")) return rc;
     }
-    const SceneArrays& sc = b.sc;
     hipStream_t s = b.stream;
     // ---- stage: the new primitives, the refit tree and the rebuilt TLAS in scratch
     HIPCHK(hipEventRecord(b.ev[0], s));
-    HIPCHK(hipMemcpyAsync(b.sPrims.p, sc.prims, sizeof(RtPrimitive) * (size_t)b.nPrims, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(b.sPrims.p, sc.prims, sizeof(RtPrimitive) * (size_t)sc.nPrims, hipMemcpyDeviceToDevice, s));
     if (count) HIPCHK(hipMemcpyAsync(b.sPrims.p + first, prims, sizeof(RtPrimitive) * (size_t)count, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(b.sNodes.p, sc.bvh2, sizeof(RtBVHNode2) * (size_t)b.nNodes, hipMemcpyDeviceToDevice, s));
-    if (blas) HIPCHK(hipMemcpyAsync(b.sInst.p, blas, sizeof(RtBVHInstance) * (size_t)b.nBlas, hipMemcpyHostToDevice, s));
-    else HIPCHK(hipMemcpyAsync(b.sInst.p, sc.blas, sizeof(RtBVHInstance) * (size_t)b.nBlas, hipMemcpyDeviceToDevice, s));
-    HIPCHK(refitdev::launch_refit(s, b.sNodes.p, (uint32_t)b.nNodes, b.sPrims.p, sc.primIdx, b.dLeaves, b.nLeaves, b.dParent, b.dTickets));
-    HIPCHK(refitdev::launch_tlas(s, b.sNodes.p, b.sInst.p, b.nBlas, b.layout == 1 ? sc.rootEntry : nullptr, b.sTlas.p, b.sTp.p, b.sTpP.p, b.sIr.p, b.sStatus));
+    HIPCHK(hipMemcpyAsync(b.sNodes.p, sc.bvh2, sizeof(RtBVHNode2) * (size_t)lt.nNodes, hipMemcpyDeviceToDevice, s));
+    if (blas) HIPCHK(hipMemcpyAsync(b.sInst.p, blas, sizeof(RtBVHInstance) * (size_t)sc.nBlas, hipMemcpyHostToDevice, s));
+    else HIPCHK(hipMemcpyAsync(b.sInst.p, sc.blas, sizeof(RtBVHInstance) * (size_t)sc.nBlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(refitdev::launch_refit(s, b.sNodes.p, lt.nNodes, b.sPrims.p, sc.primIdx, lt.leaves, lt.nLeaves, lt.parent, lt.tickets));
+    HIPCHK(refitdev::launch_tlas(s, b.sNodes.p, b.sInst.p, sc.nBlas, layout1 ? sc.rootEntry : nullptr, b.sTlas.p, b.sTp.p, b.sTpP.p, b.sIr.p, b.sStatus));
     int32_t status[2] = { 0, 0 };
     HIPCHK(hipEventRecord(b.ev[1], s));
     HIPCHK(hipMemcpyAsync(status, b.sStatus, sizeof status, hipMemcpyDeviceToHost, s));
@@ -87,26 +89,25 @@ int scenedev::update_scene(SceneBag& b, const RtPrimitive* prims, int32_t first,
     if (const int rc = b.wait_holders()) return rc;
     HIPCHK(hipEventRecord(b.ev[2], s));
     if (count) HIPCHK(hipMemcpyAsync(sc.prims + first, b.sPrims.p + first, sizeof(RtPrimitive) * (size_t)count, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(sc.bvh2, b.sNodes.p, sizeof(RtBVHNode2) * (size_t)b.nNodes, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(sc.blas, b.sInst.p, sizeof(RtBVHInstance) * (size_t)b.nBlas, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(sc.tlas, b.sTlas.p, sizeof(RtTLASNode) * (size_t)b.nTlas, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(sc.tlasPairs, b.sTp.p, sizeof(RtFloat4) * 4 * (size_t)b.nTlas, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(sc.tlasPairsP, b.sTpP.p, sizeof(RtFloat4) * 4 * (size_t)b.nTlas, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(sc.instRecs, b.sIr.p, sizeof(RtFloat4) * 4 * (size_t)b.nBlas, hipMemcpyDeviceToDevice, s));
-    HIPCHK(refitdev::launch_records(s, sc.prims, sc.bvh2, sc.primIdx, (uint32_t)b.nIdx, sc.lights, (uint32_t)b.nLights, (uint32_t)std::max(first, 0),
-                                    (uint32_t)count, b.dPairNode, (uint32_t)b.nPairs, b.layout == 1 ? sc.pairs : nullptr,
-                                    b.layout == 1 ? sc.triRecs : nullptr, sc.shadeRecs, sc.lightRecs));
+    HIPCHK(hipMemcpyAsync(sc.bvh2, b.sNodes.p, sizeof(RtBVHNode2) * (size_t)lt.nNodes, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(sc.blas, b.sInst.p, sizeof(RtBVHInstance) * (size_t)sc.nBlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(sc.tlas, b.sTlas.p, sizeof(RtTLASNode) * (size_t)lt.nTlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(sc.tlasPairs, b.sTp.p, sizeof(RtFloat4) * 4 * (size_t)lt.nTlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(sc.tlasPairsP, b.sTpP.p, sizeof(RtFloat4) * 4 * (size_t)lt.nTlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(sc.instRecs, b.sIr.p, sizeof(RtFloat4) * 4 * (size_t)sc.nBlas, hipMemcpyDeviceToDevice, s));
+    HIPCHK(refitdev::launch_records(s, sc.prims, sc.bvh2, sc.primIdx, lt.nIdx, sc.lights, (uint32_t)sc.nLights, (uint32_t)std::max(first, 0), (uint32_t)count,
+                                    lt.pairNode, lt.nPairs, layout1 ? sc.pairs : nullptr, layout1 ? sc.triRecs : nullptr, sc.shadeRecs, sc.lightRecs));
     HIPCHK(hipEventRecord(b.ev[3], s));
     HIPCHK(hipStreamSynchronize(s));
     if (blas) b.inst.assign(blas, blas + nBlas);
-    const bool reconfigure = status[1] != b.tlasDepth;
-    if (reconfigure) { b.tlasDepth = status[1]; b.generation++; }
+    const bool reconfigure = status[1] != b.facts.tlasDepth;
+    if (reconfigure) { b.facts.tlasDepth = status[1]; b.generation++; }
     if (stats) {
         float ms = 0, ms2 = 0;   // GPU time of both phases (not the wait for the holders in between)
         (void)hipEventElapsedTime(&ms, b.ev[0], b.ev[1]); (void)hipEventElapsedTime(&ms2, b.ev[2], b.ev[3]);
         ms += ms2;
         *stats = RtUpdateStats{};
-        stats->gpu_ms = ms; stats->prims = count; stats->nodes = (int32_t)b.nReach; stats->tlas_nodes = b.nTlas; stats->tlas_depth = status[1];
+        stats->gpu_ms = ms; stats->prims = count; stats->nodes = (int32_t)lt.nReach; stats->tlas_nodes = lt.nTlas; stats->tlas_depth = status[1];
         stats->reconfigured = reconfigure ? 1 : 0;
     }
     return RT_OK;
@@ -136,22 +137,16 @@ static int rebuild_reserve(SceneBag& b, SceneBag::RebuildSet& t, size_t nR, size
     }
     return rc;
 }
-// What the trees of a call are built over: the bound scene's own shape (a rebuild) or the caller's (a resize)
-struct Shape {
-    int32_t nPrims, nBlas, nLights;                  // (a resize learns nLights on the device: reserve_lights follows)
-    const std::vector<rebuild::BlasRange>* ranges;   // the primitive range of every distinct BLAS, in increasing order (root: the bound one; a resize has none)
-    const std::vector<int32_t>* instBlas;            // instance -> its range
-    int32_t nTlas() const { return 2 * nBlas; }      // TLAS::Build's node count
-};
 // The lights' arrays of the set `t` (not live): one record at least, as at upload
 static int reserve_lights(SceneBag& b, SceneBag::RebuildSet& t, size_t nLights)
 {
     const int rc = rebuild_fit(b, t.lights, nLights, "the light list");
     return rc != RT_OK ? rc : rebuild_fit(b, t.lightRecs, std::max<size_t>(nLights, 1) * 8, "light records");
 }
-static int rebuild_alloc(SceneBag& b, SceneBag::RebuildSet& t, const Shape& sh, bool resize)
+// Room in the set `t` (not live) for a scene of nPrims primitives, nBlas instances and the trees `next` describes so far (its ranges, its TLAS)
+static int rebuild_alloc(SceneBag& b, SceneBag::RebuildSet& t, int32_t nPrims, int32_t nBlas, const LiveTrees& next, bool resize)
 {
-    const size_t nP = (size_t)sh.nPrims, nB = (size_t)sh.nBlas, nT = (size_t)sh.nTlas();
+    const size_t nP = (size_t)nPrims, nB = (size_t)nBlas, nT = next.nTlas, nL = (size_t)b.sc.nLights;
     int rc = RT_OK;
     // every piece is made on its own: a call that ran out of memory half way is taken up where it stopped
     auto need = [&](auto** p, size_t count) { if (rc == RT_OK && !*p) { rc = dalloc(b.allocs, p, count); if (rc == RT_OK) b.rallocs++; } };
@@ -173,10 +168,10 @@ static int rebuild_alloc(SceneBag& b, SceneBag::RebuildSet& t, const Shape& sh, 
     if (rc == RT_OK) rc = rebuild_fit(b, t.rootEntry, nB, "root entries");
     // (a rebuild carries the bound light records, and the light list only once a resize has put it into a set; a resize sizes both
     // when its scan has counted the lights)
-    if (rc == RT_OK && !resize) rc = rebuild_fit(b, t.lightRecs, std::max<size_t>((size_t)sh.nLights, 1) * 8, "light records");
-    if (rc == RT_OK && !resize && b.lightsInSet) rc = rebuild_fit(b, t.lights, (size_t)sh.nLights, "the light list");
+    if (rc == RT_OK && !resize) rc = rebuild_fit(b, t.lightRecs, std::max<size_t>(nL, 1) * 8, "light records");
+    if (rc == RT_OK && !resize && b.lightsInSet) rc = rebuild_fit(b, t.lights, nL, "the light list");
     // ... and with the trees (the first allocation: the initial capacity)
-    if (rc == RT_OK && !t.nodes.p) rc = rebuild_reserve(b, t, sh.ranges->size(), std::max(cap0, t.primIdx.cap), std::max(2 * cap0, t.nodes.cap), 0, 0);
+    if (rc == RT_OK && !t.nodes.p) rc = rebuild_reserve(b, t, next.ranges.size(), std::max(cap0, t.primIdx.cap), std::max(2 * cap0, t.nodes.cap), 0, 0);
     return rc;
 }
 
@@ -221,16 +216,16 @@ static int check_plan_alpha(const char* who, const int32_t* plan, size_t n, cons
 }
 
 // ---- the one body of rt_rebuild_scene, rt_rebuild_ranges and rt_resize_scene, phase by phase ----------------------------------------------
-// What a call asks for; it has passed the checks that need no device.  A rebuild (newPrims NULL) keeps the bound shape `sh` and takes the
-// replacement records prims / first / count and blas as rt_update_scene does; a resize builds the caller's shape over newPrims (host or
-// device memory, sh.nPrims records), blas (NULL: identity) carrying the transforms.  plan[k] says what becomes of range k: built with
-// RT_REBUILD_SAH / LBVH / SBVH, or (RT_REBUILD_KEEP, a rebuild of a compact bound tree only) its bound tree moved to where the new scene
-// numbers it, or (RT_REBUILD_REFIT_RANGE, likewise) moved and then given new boxes; an empty plan is RT_REBUILD_REFIT of the whole scene
-// (no builder runs, opts is ignored).  perRange: the call is rt_rebuild_ranges (rt_ranges_info describes it).
+// What a call asks for; it has passed the checks that need no device.  A rebuild (newPrims NULL) keeps the bound counts and ranges and takes
+// the replacement records prims / first / count and blas as rt_update_scene does; a resize builds the caller's shape - nPrims records at
+// newPrims (host or device memory), nBlas instances, newRanges, newInstBlas - with blas (NULL: identity) carrying the transforms.  plan[k]
+// says what becomes of range k: built with RT_REBUILD_SAH / LBVH / SBVH, or (RT_REBUILD_KEEP, a rebuild of a compact bound tree only) its
+// bound tree moved to where the new scene numbers it, or (RT_REBUILD_REFIT_RANGE, likewise) moved and then given new boxes; an empty plan is
+// RT_REBUILD_REFIT of the whole scene (no builder runs, opts is ignored).  perRange: the call is rt_rebuild_ranges (rt_ranges_info describes it).
 namespace {
 struct Request {
     const char* who;
-    Shape sh;
+    int32_t nPrims, nBlas;
     const void* newPrims;
     const RtPrimitive* prims; int32_t first, count;
     const RtBVHInstance* blas;
@@ -238,18 +233,33 @@ struct Request {
     const RtBuildOptions* opts;
     lbvh::Params P;
     bool perRange = false;
+    std::vector<rebuild::BlasRange> newRanges;   // a resize: the primitive range of every distinct BLAS, in increasing order ...
+    std::vector<int32_t> newInstBlas;            // ... and instance -> its range
 };
-// One call: what it has built in the set that is not live and what it has read back of it - everything commit needs -, and the phases
-// that build it, in the order rebuild_body calls them
+// One call: the trees (`next`), the facts and the host shadows of the scene it builds in the set that is not live - everything commit moves
+// into the bag - and the phases that build them, in the order rebuild_body calls them
 struct Pending {
     SceneBag& b;
     const Request& rq;
     const char* const who = rq.who;
-    const Shape& sh = rq.sh;
-    const std::vector<rebuild::BlasRange>& ranges = *sh.ranges;
-    const size_t nR = ranges.size();
-    const bool resize = rq.newPrims != nullptr, refit = rq.plan.empty(), bvh4 = b.accel == RT_ACCEL_BVH4, layout1 = b.layout == 1;
+    const int32_t nPrims = rq.nPrims, nBlas = rq.nBlas;
+    const bool resize = rq.newPrims != nullptr, refit = rq.plan.empty(), bvh4 = b.accel == RT_ACCEL_BVH4, layout1 = b.facts.layout == 1;
     SceneBag::RebuildSet& t = b.rset[b.rnext];
+    // The next live trees: a rebuild starts from the bound ones (a whole-scene refit leaves all but the pointers), a resize from the
+    // caller's ranges.  place() writes the roots and the blocks, derive_ids() the runs, read_back() the set's pointers and the collapse's
+    LiveTrees next = start();
+    const size_t nR = next.ranges.size();
+    SceneFacts facts = b.facts;                  // (the layout stays: read_back refuses a change)
+    std::vector<int32_t> primType, primMat;      // a resize: the host's shadow of objType / matIdx, the only per-primitive data that comes back
+    std::vector<RtBVHInstance> inst;
+    LiveTrees start() const
+    {
+        LiveTrees n;
+        if (!resize) n = b.live;
+        else { n.ranges = rq.newRanges; n.instBlas = rq.newInstBlas; n.nTlas = 2 * (uint32_t)nBlas; }   // (TLAS::Build's node count)
+        if (!refit) { n.nNodes = n.nIdx = n.nPairs = 0; n.block.assign(n.ranges.size(), rebuild::BlasBlock{}); }
+        return n;
+    }
     int size();                  // 1. room for what the plan is known to need, the builders' workspace
     int stage();                 // 2. the primitives and the lights
     int trees();                 // 3. refit copy, kept segments, builders
@@ -266,7 +276,7 @@ struct Pending {
     // alone.  (Not a copy bound in layout 0 that could take layout 1: the layout check needs every leaf's size, which only the leaf scan
     // over all ranges gives.  Not a BVH4 copy: its collapse is derived over all ranges.)
     bool blockwise = false;
-    std::vector<uint32_t> pairLo, leafLo, hostRoots;   // per range: its run of pair ids, its run of leaves; per instance: its root entry
+    std::vector<uint32_t> hostRoots;                    // per instance: its root entry
     RtRangesInfo info{};                                // counted as the launches are queued
 
     using clock = std::chrono::steady_clock;
@@ -274,31 +284,27 @@ struct Pending {
     // size: what the ranges behind range k need that is known beforehand, and the BLAS in the order the instances first name them
     std::vector<size_t> restIdx, restNodes, order;
     bool anyKnown = false;
-    // the counts of the new scene, and where its light list lies
-    uint32_t nNodes = 0, nIdx = 0, nPairs = 0, nLeaves = 0;
+    // the lights of the new scene, and where their list lies
     int32_t nLights = 0;
     const uint32_t* lights = nullptr;
-    // per range: where its tree lies and what it is like
-    std::vector<uint32_t> rootOf, interiors, depth, idxOf, slotsOf;
     uint32_t maxDepth = 0;
     int32_t nBuilt = 0;
     uint64_t spatialSplits = 0, primsClipped = 0;
-    std::vector<RtBVHInstance> inst;
     // read back: k_tlas_build's status, the derivation's walk status and largest leaf, the collapse's status
     int32_t tlas[2] = { 0, 0 };
     uint32_t walk[2] = { 0, 0 }, changed = 0;
     CollapseStatus c4;
     int32_t refitPath = 0;
     int stackNeed = 0;
-    std::vector<int2> packed;   // a resize: the host's shadow of objType / matIdx, the only per-primitive data that comes back
     float gpuMs = 0, fitMs = 0, deriveMs = 0, tlasMs = 0;   // between the events (read for stats only)
     bool reconfigured = false;
-    // range k has a tree of `nodes` nodes, height `height`, over `slots` index slots: behind the trees placed so far
+    // range k has a tree of `nodes` nodes, height `height`, over `slots` index slots: behind the trees placed so far, one block
     void place(size_t k, uint32_t nodes, uint32_t height, uint32_t slots)
     {
-        rootOf[k] = nNodes; interiors[k] = (nodes - 1) / 2; depth[k] = height; idxOf[k] = nIdx; slotsOf[k] = slots;
+        next.ranges[k].root = next.nNodes;
+        next.block[k] = rebuild::BlasBlock{ nodes, next.nIdx, slots, 1, height };
         maxDepth = std::max(maxDepth, height);
-        nNodes += nodes; nIdx += slots;
+        next.nNodes += nodes; next.nIdx += slots;
     }
 };
 } // namespace
@@ -311,15 +317,15 @@ int Pending::size()
     restIdx.assign(nR + 1, 0); restNodes.assign(nR + 1, 0);
     for (size_t k = nR; k-- > 0 && !refit;) {
         const bool keep = moves(k), known = keep || rq.plan[k] != RT_REBUILD_SBVH;
-        restIdx[k] = restIdx[k + 1] + (keep ? b.blasBlock[k].idxSlots : known ? ranges[k].count : 0u);
-        restNodes[k] = restNodes[k + 1] + (keep ? b.blasBlock[k].nodes : known ? 2 * (size_t)ranges[k].count - 1 : 0u);
+        restIdx[k] = restIdx[k + 1] + (keep ? b.live.block[k].idxSlots : known ? next.ranges[k].count : 0u);
+        restNodes[k] = restNodes[k + 1] + (keep ? b.live.block[k].nodes : known ? 2 * (size_t)next.ranges[k].count - 1 : 0u);
         anyKnown = anyKnown || known;
     }
     std::vector<uint8_t> named(nR, 0);
-    for (const int32_t k : *sh.instBlas) if (!named[(size_t)k]) { named[(size_t)k] = 1; order.push_back((size_t)k); }
+    for (const int32_t k : next.instBlas) if (!named[(size_t)k]) { named[(size_t)k] = 1; order.push_back((size_t)k); }
     HIPCHK(hipSetDevice(b.device));
-    if (const int rc = rebuild_alloc(b, t, sh, resize)) return rc;
-    if (refit) return rebuild_reserve(b, t, nR, (size_t)b.nIdx, (size_t)b.nNodes + nR, 0, 0);   // the bound trees (nR spare nodes: see build_tree)
+    if (const int rc = rebuild_alloc(b, t, nPrims, nBlas, next, resize)) return rc;
+    if (refit) return rebuild_reserve(b, t, nR, (size_t)next.nIdx, (size_t)next.nNodes + nR, 0, 0);   // the bound trees (nR spare nodes: see build_tree)
     if (!anyKnown) return RT_OK;
     // room for the kept trees and for every tree the SAH and the linear builder can make (a set or the scratch that started smaller, or
     // has only held SBVH trees so far); nR spare nodes: see build_tree.  With every range built by those two this is nPrims slots and
@@ -330,7 +336,7 @@ int Pending::size()
     for (size_t k = 0; k < nR; k++) {
         if (rq.plan[k] != RT_REBUILD_SAH && rq.plan[k] != RT_REBUILD_LBVH) continue;
         size_t bytes = 0;
-        const int rc = rq.plan[k] == RT_REBUILD_SAH ? sahdev::work_bytes(who, ranges[k].count, b.stream, &bytes) : lbvhdev::work_bytes(who, ranges[k].count, b.stream, &bytes);
+        const int rc = rq.plan[k] == RT_REBUILD_SAH ? sahdev::work_bytes(who, next.ranges[k].count, b.stream, &bytes) : lbvhdev::work_bytes(who, next.ranges[k].count, b.stream, &bytes);
         if (rc != RT_OK) return rc;
         need = std::max(need, bytes);
     }
@@ -345,7 +351,6 @@ int Pending::stage() { return resize ? stage_resize() : stage_rebuild(); }
 int Pending::stage_resize()
 {
     const SceneArrays& sc = b.sc;
-    const int32_t nPrims = sh.nPrims;
     hipStream_t s = b.stream;
     if (const int rc = rebuild_scratch(b, (size_t)nPrims)) return rc;   // (flags and ranks: a word per primitive)
     if (const int rc = rebuild_fit(b, b.rPacked, (size_t)nPrims, "the packed objType / matIdx pairs")) return rc;
@@ -369,10 +374,10 @@ int Pending::stage_rebuild()
 {
     const SceneArrays& sc = b.sc;
     hipStream_t s = b.stream;
-    HIPCHK(hipMemcpyAsync(t.prims.p, sc.prims, sizeof(RtPrimitive) * (size_t)b.nPrims, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(t.prims.p, sc.prims, sizeof(RtPrimitive) * (size_t)sc.nPrims, hipMemcpyDeviceToDevice, s));
     if (rq.count) HIPCHK(hipMemcpyAsync(t.prims.p + rq.first, rq.prims, sizeof(RtPrimitive) * (size_t)rq.count, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(t.lightRecs.p, sc.lightRecs, sizeof(RtFloat4) * 8 * std::max<size_t>((size_t)b.nLights, 1), hipMemcpyDeviceToDevice, s));   // (the emittance words stay)
-    nLights = sh.nLights; lights = sc.lights;
+    HIPCHK(hipMemcpyAsync(t.lightRecs.p, sc.lightRecs, sizeof(RtFloat4) * 8 * std::max<size_t>((size_t)sc.nLights, 1), hipMemcpyDeviceToDevice, s));   // (the emittance words stay)
+    nLights = sc.nLights; lights = sc.lights;
     if (b.lightsInSet) {   // the light list lives in a set since a resize: it moves on with the arrays
         if (nLights) HIPCHK(hipMemcpyAsync(t.lights.p, sc.lights, sizeof(uint32_t) * (size_t)nLights, hipMemcpyDeviceToDevice, s));
         lights = t.lights.p;
@@ -386,17 +391,13 @@ int Pending::refit_trees()
 {
     const SceneArrays& sc = b.sc;
     hipStream_t s = b.stream;
-    nNodes = (uint32_t)b.nNodes; nIdx = (uint32_t)b.nIdx;
-    HIPCHK(hipMemcpyAsync(t.nodes.p, sc.bvh2, sizeof(RtBVHNode2) * (size_t)nNodes, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(t.primIdx.p, sc.primIdx, sizeof(uint32_t) * (size_t)nIdx, hipMemcpyDeviceToDevice, s));
-    HIPCHK(hipMemcpyAsync(t.parent.p, b.dParent, sizeof(uint32_t) * (size_t)nNodes, hipMemcpyDeviceToDevice, s));
-    if (b.nLeaves) HIPCHK(hipMemcpyAsync(t.leaves.p, b.dLeaves, sizeof(uint32_t) * (size_t)b.nLeaves, hipMemcpyDeviceToDevice, s));
-    if (b.nPairs) HIPCHK(hipMemcpyAsync(t.pairNode.p, b.dPairNode, sizeof(uint32_t) * (size_t)b.nPairs, hipMemcpyDeviceToDevice, s));
-    HIPCHK(refitdev::launch_refit(s, t.nodes.p, nNodes, t.prims.p, t.primIdx.p, t.leaves.p, b.nLeaves, t.parent.p, t.tickets.p));
-    for (size_t k = 0; k < nR; k++) {
-        rootOf[k] = b.ranges[k].root; interiors[k] = b.blas_interiors(k); depth[k] = b.blasBlock[k].height;
-        maxDepth = std::max(maxDepth, depth[k]);
-    }
+    HIPCHK(hipMemcpyAsync(t.nodes.p, sc.bvh2, sizeof(RtBVHNode2) * (size_t)next.nNodes, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(t.primIdx.p, sc.primIdx, sizeof(uint32_t) * (size_t)next.nIdx, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(t.parent.p, b.live.parent, sizeof(uint32_t) * (size_t)next.nNodes, hipMemcpyDeviceToDevice, s));
+    if (next.nLeaves) HIPCHK(hipMemcpyAsync(t.leaves.p, b.live.leaves, sizeof(uint32_t) * (size_t)next.nLeaves, hipMemcpyDeviceToDevice, s));
+    if (next.nPairs) HIPCHK(hipMemcpyAsync(t.pairNode.p, b.live.pairNode, sizeof(uint32_t) * (size_t)next.nPairs, hipMemcpyDeviceToDevice, s));
+    HIPCHK(refitdev::launch_refit(s, t.nodes.p, next.nNodes, t.prims.p, t.primIdx.p, t.leaves.p, next.nLeaves, t.parent.p, t.tickets.p));
+    for (const rebuild::BlasBlock& blk : next.block) maxDepth = std::max(maxDepth, blk.height);
     return RT_OK;
 }
 // Kept trees move as segments: adjacent kept BLAS whose node and index offsets agree are one (rebuilddev::relocate), and their primIdx
@@ -414,13 +415,13 @@ int Pending::flush_kept(KeptSegment& seg)
 // reserved by size(); the bound values stand for the builder's
 int Pending::keep_tree(size_t k, KeptSegment& seg)
 {
-    const rebuild::BlasBlock& blk = b.blasBlock[k];
-    const uint32_t root = b.ranges[k].root, nodeDelta = nNodes - root, idxDelta = nIdx - blk.idxLo;
+    const rebuild::BlasBlock& blk = b.live.block[k];
+    const uint32_t root = b.live.ranges[k].root, nodeDelta = next.nNodes - root, idxDelta = next.nIdx - blk.idxLo;
     if (seg.nNodes && seg.nodeDelta == nodeDelta && seg.idxDelta == idxDelta && seg.srcNode + seg.nNodes == root && seg.srcIdx + seg.nIdx == blk.idxLo) {
         seg.nNodes += blk.nodes; seg.nIdx += blk.idxSlots;
     } else {
         if (const int rc = flush_kept(seg)) return rc;
-        seg = KeptSegment{ root, nNodes, blk.nodes, nodeDelta, blk.idxLo, nIdx, blk.idxSlots, idxDelta };
+        seg = KeptSegment{ root, next.nNodes, blk.nodes, nodeDelta, blk.idxLo, next.nIdx, blk.idxSlots, idxDelta };
     }
     place(k, blk.nodes, blk.height, blk.idxSlots);
     if (!refits(k)) info.kept++;
@@ -429,7 +430,7 @@ int Pending::keep_tree(size_t k, KeptSegment& seg)
 // range k is built by plan[k], behind the trees placed so far
 int Pending::build_tree(size_t k)
 {
-    const rebuild::BlasRange& r = ranges[k];
+    const rebuild::BlasRange& r = next.ranges[k];
     const bool sbvh = rq.plan[k] == RT_REBUILD_SBVH;
     hipStream_t s = b.stream;
     Built built{};
@@ -439,19 +440,19 @@ int Pending::build_tree(size_t k)
         struct TreeGuard { sbvhdev::Tree* p = nullptr; ~TreeGuard() { sbvhdev::destroy(p); } } tree;
         SbvhBuilt sb{};
         const float alpha = rq.opts ? rq.opts->alpha : 0.0f;   // (check_builder has seen it)
-        if (const int rc = sbvhdev::build(who, s, alpha, t.prims.p + r.first, r.count, r.first, nNodes, nIdx, nullptr, nullptr, b.spool, &tree.p, &sb)) return rc;
+        if (const int rc = sbvhdev::build(who, s, alpha, t.prims.p + r.first, r.count, r.first, next.nNodes, next.nIdx, nullptr, nullptr, b.spool, &tree.p, &sb)) return rc;
         // room for this tree and for what the ranges behind it are known to need (nR spare nodes: the leaf and pair arrays hold half the
         // node capacity, and k trees have k leaves more than interior nodes)
-        const uint64_t nodeNeed = (uint64_t)nNodes + sb.nodes + restNodes[k + 1] + nR, idxNeed = (uint64_t)nIdx + sb.nIdx + restIdx[k + 1];
+        const uint64_t nodeNeed = (uint64_t)next.nNodes + sb.nodes + restNodes[k + 1] + nR, idxNeed = (uint64_t)next.nIdx + sb.nIdx + restIdx[k + 1];
         if (sb.nIdx == 0 || nodeNeed > 0x7fffffffull || idxNeed > 0x7fffffffull) return too_many_nodes(who);
-        if (const int rc = rebuild_reserve(b, t, nR, (size_t)idxNeed, (size_t)nodeNeed, nIdx, nNodes)) return rc;
-        if (const int rc = sbvhdev::emit(who, s, tree.p, t.nodes.p + nNodes, t.primIdx.p + nIdx)) return rc;
+        if (const int rc = rebuild_reserve(b, t, nR, (size_t)idxNeed, (size_t)nodeNeed, next.nIdx, next.nNodes)) return rc;
+        if (const int rc = sbvhdev::emit(who, s, tree.p, t.nodes.p + next.nNodes, t.primIdx.p + next.nIdx)) return rc;
         built.nodes = sb.nodes; built.depth = sb.depth; slots = sb.nIdx;
         spatialSplits += sb.spatialSplits; primsClipped += sb.primsClipped;
     } else {
         const int rc = rq.plan[k] == RT_REBUILD_SAH
-            ? sahdev::build(who, s, b.rwork.p, t.prims.p + r.first, r.count, r.first, nNodes, nIdx, t.nodes.p + nNodes, t.primIdx.p + nIdx, nullptr, nullptr, &built)
-            : lbvhdev::build(who, s, b.rwork.p, rq.P, t.prims.p + r.first, r.count, r.first, nNodes, nIdx, t.nodes.p + nNodes, t.primIdx.p + nIdx, nullptr, nullptr, &built);
+            ? sahdev::build(who, s, b.rwork.p, t.prims.p + r.first, r.count, r.first, next.nNodes, next.nIdx, t.nodes.p + next.nNodes, t.primIdx.p + next.nIdx, nullptr, nullptr, &built)
+            : lbvhdev::build(who, s, b.rwork.p, rq.P, t.prims.p + r.first, r.count, r.first, next.nNodes, next.nIdx, t.nodes.p + next.nNodes, t.primIdx.p + next.nIdx, nullptr, nullptr, &built);
         if (rc != RT_OK) return rc;
     }
     if (built.nodes == 0 || (built.nodes & 1u) == 0 || (!sbvh && built.nodes > 2 * r.count - 1))
@@ -467,7 +468,6 @@ int Pending::build_tree(size_t k)
 }
 int Pending::trees()
 {
-    rootOf.assign(nR, 0u); interiors.assign(nR, 0u); depth.assign(nR, 0u); idxOf.assign(nR, 0u); slotsOf.assign(nR, 0u);
     if (refit) {
         if (const int rc = refit_trees()) return rc;
     } else {
@@ -478,9 +478,9 @@ int Pending::trees()
             if (const int rc = build_tree(k)) return rc;
         }
         if (const int rc = flush_kept(seg)) return rc;
-        if (const int rc = rebuild_scratch(b, (size_t)nNodes + nR)) return rc;
+        if (const int rc = rebuild_scratch(b, (size_t)next.nNodes + nR)) return rc;
     }
-    return bvh4 ? collapse_scratch(b, (size_t)nNodes + nR) : RT_OK;
+    return bvh4 ? collapse_scratch(b, (size_t)next.nNodes + nR) : RT_OK;
 }
 
 // 4. Derive: the instances (host: at most 256 records), then everything upload derives: numbering, collapse, records, TLAS
@@ -488,50 +488,49 @@ int Pending::derive()
 {
     const SceneArrays& sc = b.sc;
     hipStream_t s = b.stream;
-    if (rq.blas) inst.assign(rq.blas, rq.blas + sh.nBlas);
+    if (rq.blas) inst.assign(rq.blas, rq.blas + nBlas);
     else if (!resize) inst = b.inst;
     else {   // a resize without transforms: BuildBLAS's identity
-        inst.assign((size_t)sh.nBlas, RtBVHInstance{});
+        inst.assign((size_t)nBlas, RtBVHInstance{});
         for (RtBVHInstance& r : inst) r.invT[0] = r.invT[5] = r.invT[10] = r.invT[15] = 1.0f;
     }
-    for (int32_t i = 0; i < sh.nBlas; i++) inst[(size_t)i].bvhIdx = rootOf[(size_t)(*sh.instBlas)[(size_t)i]];
-    HIPCHK(hipMemcpyAsync(t.blas.p, inst.data(), sizeof(RtBVHInstance) * (size_t)sh.nBlas, hipMemcpyHostToDevice, s));
+    for (int32_t i = 0; i < nBlas; i++) inst[(size_t)i].bvhIdx = next.ranges[(size_t)next.instBlas[(size_t)i]].root;
+    HIPCHK(hipMemcpyAsync(t.blas.p, inst.data(), sizeof(RtBVHInstance) * (size_t)nBlas, hipMemcpyHostToDevice, s));
     HIPCHK(hipEventRecord(b.rev[1], s));
     if (refit) {   // the pair records (launch_records rewrites their boxes) and the root entries as they are bound
-        nPairs = (uint32_t)b.nPairs;
         if (layout1 && !bvh4) {
-            HIPCHK(hipMemcpyAsync(t.pairs.p, sc.pairs, sizeof(RtFloat4) * 4 * std::max<size_t>(nPairs, 1), hipMemcpyDeviceToDevice, s));
-            HIPCHK(hipMemcpyAsync(t.rootEntry.p, sc.rootEntry, sizeof(uint32_t) * (size_t)b.nBlas, hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(t.pairs.p, sc.pairs, sizeof(RtFloat4) * 4 * std::max<size_t>(next.nPairs, 1), hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(t.rootEntry.p, sc.rootEntry, sizeof(uint32_t) * (size_t)b.sc.nBlas, hipMemcpyDeviceToDevice, s));
         }
     } else if (const int rc = derive_ids()) return rc;
-    if (layout1 && !bvh4 && nPairs == 0) HIPCHK(hipMemsetAsync(t.pairs.p, 0, sizeof(RtFloat4) * 4, s));   // no interior node: one zero record, as at upload
-    nLeaves = refit ? b.nLeaves : nNodes - nPairs;
+    if (layout1 && !bvh4 && next.nPairs == 0) HIPCHK(hipMemsetAsync(t.pairs.p, 0, sizeof(RtFloat4) * 4, s));   // no interior node: one zero record, as at upload
+    if (!refit) { next.nLeaves = next.nNodes - next.nPairs; next.nReach = next.nNodes; }
     refitPath = refit ? 1 : 0;
     if (bvh4) {   // the collapse into the set's bvh4, BLAS by BLAS in the same order; quad records and root entries (layout 1)
         const collapsedev::Work w = collapse_work(b, t.newId.p, t.quadNode.p, std::min(t.quadNode.cap, t.quads.cap / 8));
-        HIPCHK(collapsedev::begin(s, w, t.nodes.p, nNodes, t.bvh4.p));
+        HIPCHK(collapsedev::begin(s, w, t.nodes.p, next.nNodes, t.bvh4.p));
         if (refit) {
             // in place: the live records anew under the bound live ids (the set takes the bound tables over); if no slot of any of
             // them changed, they are the collapse of the refit trees and the level loop is skipped
-            HIPCHK(hipMemcpyAsync(t.newId.p, b.liveNewId, sizeof(uint32_t) * (size_t)nNodes, hipMemcpyDeviceToDevice, s));
-            HIPCHK(hipMemcpyAsync(t.quadNode.p, b.liveQuadNode, sizeof(uint32_t) * (size_t)b.nLive, hipMemcpyDeviceToDevice, s));
-            HIPCHK(collapsedev::refit_records(s, w, t.nodes.p, nNodes, sc.bvh4, t.quadNode.p, b.nLive, t.bvh4.p));
+            HIPCHK(hipMemcpyAsync(t.newId.p, b.live.newId, sizeof(uint32_t) * (size_t)next.nNodes, hipMemcpyDeviceToDevice, s));
+            HIPCHK(hipMemcpyAsync(t.quadNode.p, b.live.quadNode, sizeof(uint32_t) * (size_t)b.live.nLive, hipMemcpyDeviceToDevice, s));
+            HIPCHK(collapsedev::refit_records(s, w, t.nodes.p, next.nNodes, sc.bvh4, t.quadNode.p, b.live.nLive, t.bvh4.p));
             HIPCHK(c4.read(s, w));
             HIPCHK(hipStreamSynchronize(s));
             if (const int rc = c4.error(who, "; the scene is unchanged")) return rc;
             changed = c4.changed();
             const char* env = getenv("RT355_REFIT_RECOLLAPSE");
             refitPath = env && atoi(env) == 1 ? 3 : changed ? 2 : 1;
-            if (refitPath != 1) HIPCHK(collapsedev::begin(s, w, t.nodes.p, nNodes, t.bvh4.p));   // the fallback: the rebuild's collapse
+            if (refitPath != 1) HIPCHK(collapsedev::begin(s, w, t.nodes.p, next.nNodes, t.bvh4.p));   // the fallback: the rebuild's collapse
         }
         if (refitPath != 1)
-            for (const size_t k : order) HIPCHK(collapsedev::collapse_blas(s, w, t.nodes.p, nNodes, rootOf[k], interiors[k], depth[k], t.bvh4.p));
-        HIPCHK(collapsedev::finish(s, w, t.bvh4.p, nNodes, nIdx, (const uint32_t*)t.blas.p, (uint32_t)(sizeof(RtBVHInstance) / 4), (uint32_t)sh.nBlas,
+            for (const size_t k : order) HIPCHK(collapsedev::collapse_blas(s, w, t.nodes.p, next.nNodes, next.ranges[k].root, next.interiors(k), next.block[k].height, t.bvh4.p));
+        HIPCHK(collapsedev::finish(s, w, t.bvh4.p, next.nNodes, next.nIdx, (const uint32_t*)t.blas.p, (uint32_t)(sizeof(RtBVHInstance) / 4), (uint32_t)nBlas,
                                    layout1 ? t.quads.p : nullptr, t.rootEntry.p));
     }
     if (const int rc = derive_records()) return rc;
     HIPCHK(hipEventRecord(b.rev[2], s));
-    HIPCHK(refitdev::launch_tlas(s, t.nodes.p, t.blas.p, sh.nBlas, layout1 ? t.rootEntry.p : nullptr, t.tlas.p, t.tp.p, t.tpP.p, t.ir.p, b.rStatus));
+    HIPCHK(refitdev::launch_tlas(s, t.nodes.p, t.blas.p, nBlas, layout1 ? t.rootEntry.p : nullptr, t.tlas.p, t.tp.p, t.tpP.p, t.ir.p, b.rStatus));
     HIPCHK(hipEventRecord(b.rev[3], s));
     return RT_OK;
 }
@@ -546,46 +545,46 @@ int Pending::derive_ids()
     const SceneArrays& sc = b.sc;
     hipStream_t s = b.stream;
     RtFloat4* const pairs = layout1 && !bvh4 ? t.pairs.p : nullptr;
-    pairLo.assign(nR, 0u); leafLo.assign(nR, 0u);
-    for (size_t k = 0, at = 0; k < nR; k++) { leafLo[k] = (uint32_t)at; at += interiors[k] + 1; }
-    HIPCHK(rebuilddev::begin(s, b.dw, t.parent.p, nNodes));
+    next.pairLo.assign(nR, 0u); next.leafLo.assign(nR, 0u);
+    for (size_t k = 0, at = 0; k < nR; k++) { next.leafLo[k] = (uint32_t)at; at += next.interiors(k) + 1; }
+    HIPCHK(rebuilddev::begin(s, b.dw, t.parent.p, next.nNodes));
     for (const size_t k : order) {
-        const uint32_t m = 2 * interiors[k] + 1;
-        pairLo[k] = nPairs;
+        const uint32_t m = 2 * next.interiors(k) + 1;
+        next.pairLo[k] = next.nPairs;
         if (blockwise && moves(k)) {
-            const uint32_t oldRoot = b.ranges[k].root, oldPair = b.blasPairLo[k];
-            HIPCHK(rebuilddev::relocate_ids(s, b.dParent + oldRoot, t.parent.p + rootOf[k], m, b.dPairNode + oldPair, t.pairNode.p + nPairs, pairs ? interiors[k] : 0u,
-                                            b.dLeaves + b.blasLeafLo[k], t.leaves.p + leafLo[k], interiors[k] + 1, rootOf[k] - oldRoot));
+            const uint32_t oldRoot = b.live.ranges[k].root, oldPair = b.live.pairLo[k];
+            HIPCHK(rebuilddev::relocate_ids(s, b.live.parent + oldRoot, t.parent.p + next.ranges[k].root, m, b.live.pairNode + oldPair, t.pairNode.p + next.nPairs, pairs ? next.interiors(k) : 0u,
+                                            b.live.leaves + b.live.leafLo[k], t.leaves.p + next.leafLo[k], next.interiors(k) + 1, next.ranges[k].root - oldRoot));
             if (pairs) {
-                HIPCHK(rebuilddev::relocate_pairs(s, sc.pairs + (size_t)oldPair * 4, pairs + (size_t)nPairs * 4, interiors[k], nPairs - oldPair, idxOf[k] - b.blasBlock[k].idxLo));
-                info.pairs_relocated += (int32_t)interiors[k];
+                HIPCHK(rebuilddev::relocate_pairs(s, sc.pairs + (size_t)oldPair * 4, pairs + (size_t)next.nPairs * 4, next.interiors(k), next.nPairs - oldPair, next.block[k].idxLo - b.live.block[k].idxLo));
+                info.pairs_relocated += (int32_t)next.interiors(k);
             }
         } else {
-            HIPCHK(rebuilddev::number_blas(s, b.dw, t.nodes.p, nNodes, rootOf[k], interiors[k], depth[k], nPairs, (uint32_t)t.pairNode.cap, t.pairNode.p, t.parent.p));
+            HIPCHK(rebuilddev::number_blas(s, b.dw, t.nodes.p, next.nNodes, next.ranges[k].root, next.interiors(k), next.block[k].height, next.nPairs, (uint32_t)t.pairNode.cap, t.pairNode.p, t.parent.p));
             info.nodes_numbered += (int32_t)m;
             if (blockwise) {
-                HIPCHK(rebuilddev::finish_blas(s, b.dw, t.nodes.p, rootOf[k], m, nPairs, interiors[k], t.pairNode.p, pairs, t.leaves.p + leafLo[k]));
-                if (pairs) info.pairs_derived += (int32_t)interiors[k];
+                HIPCHK(rebuilddev::finish_blas(s, b.dw, t.nodes.p, next.ranges[k].root, m, next.nPairs, next.interiors(k), t.pairNode.p, pairs, t.leaves.p + next.leafLo[k]));
+                if (pairs) info.pairs_derived += (int32_t)next.interiors(k);
             }
         }
-        nPairs += interiors[k];
+        next.nPairs += next.interiors(k);
     }
     if (!blockwise) {
-        HIPCHK(rebuilddev::finish(s, b.dw, t.nodes.p, nNodes, nPairs, nNodes - nPairs, t.blas.p, (uint32_t)sh.nBlas, t.pairNode.p, pairs, t.rootEntry.p, t.leaves.p));
-        if (pairs) info.pairs_derived += (int32_t)nPairs;
+        HIPCHK(rebuilddev::finish(s, b.dw, t.nodes.p, next.nNodes, next.nPairs, next.nNodes - next.nPairs, t.blas.p, (uint32_t)nBlas, t.pairNode.p, pairs, t.rootEntry.p, t.leaves.p));
+        if (pairs) info.pairs_derived += (int32_t)next.nPairs;
     } else if (pairs) {   // a leaf root: the leaf entry at its index base; otherwise the start of its run of pair ids (the root is the walk's first node)
-        hostRoots.resize((size_t)sh.nBlas);
-        for (int32_t i = 0; i < sh.nBlas; i++) {
-            const size_t k = (size_t)(*sh.instBlas)[(size_t)i];
-            hostRoots[(size_t)i] = rebuild::child_entry(idxOf[k], interiors[k] ? 0u : slotsOf[k], pairLo[k]);
+        hostRoots.resize((size_t)nBlas);
+        for (int32_t i = 0; i < nBlas; i++) {
+            const size_t k = (size_t)next.instBlas[(size_t)i];
+            hostRoots[(size_t)i] = rebuild::child_entry(next.block[k].idxLo, next.interiors(k) ? 0u : next.block[k].idxSlots, next.pairLo[k]);
         }
         HIPCHK(hipMemcpyAsync(t.rootEntry.p, hostRoots.data(), sizeof(uint32_t) * hostRoots.size(), hipMemcpyHostToDevice, s));
     }
     for (size_t k = 0; k < nR; k++) {   // (before anything reads a box: the collapse, the pair boxes below, the TLAS)
         if (!refits(k)) continue;
-        HIPCHK(refitdev::launch_refit_blas(s, t.nodes.p, rootOf[k], 2 * interiors[k] + 1, t.prims.p, t.primIdx.p, t.leaves.p + leafLo[k], interiors[k] + 1, t.parent.p,
+        HIPCHK(refitdev::launch_refit_blas(s, t.nodes.p, next.ranges[k].root, 2 * next.interiors(k) + 1, t.prims.p, t.primIdx.p, t.leaves.p + next.leafLo[k], next.interiors(k) + 1, t.parent.p,
                                            t.tickets.p));
-        info.refit++; info.leaves_refit += (int32_t)interiors[k] + 1;
+        info.refit++; info.leaves_refit += (int32_t)next.interiors(k) + 1;
     }
     return RT_OK;
 }
@@ -598,27 +597,27 @@ int Pending::derive_records()
     hipStream_t s = b.stream;
     if (!blockwise) {
         const bool boxes = refit && layout1 && !bvh4;
-        HIPCHK(refitdev::launch_records(s, t.prims.p, t.nodes.p, t.primIdx.p, nIdx, lights, (uint32_t)nLights, 0u, (uint32_t)sh.nPrims,
-                                        boxes ? t.pairNode.p : nullptr, boxes ? nPairs : 0u, boxes ? t.pairs.p : nullptr, layout1 ? t.triRecs.p : nullptr,
+        HIPCHK(refitdev::launch_records(s, t.prims.p, t.nodes.p, t.primIdx.p, next.nIdx, lights, (uint32_t)nLights, 0u, (uint32_t)nPrims,
+                                        boxes ? t.pairNode.p : nullptr, boxes ? next.nPairs : 0u, boxes ? t.pairs.p : nullptr, layout1 ? t.triRecs.p : nullptr,
                                         t.shadeRecs.p, t.lightRecs.p));
-        if (layout1) info.slots_derived += (int32_t)nIdx;
+        if (layout1) info.slots_derived += (int32_t)next.nIdx;
         return RT_OK;
     }
-    HIPCHK(hipMemcpyAsync(t.shadeRecs.p, sc.shadeRecs, sizeof(RtFloat4) * (size_t)sh.nPrims, hipMemcpyDeviceToDevice, s));
+    HIPCHK(hipMemcpyAsync(t.shadeRecs.p, sc.shadeRecs, sizeof(RtFloat4) * (size_t)nPrims, hipMemcpyDeviceToDevice, s));
     HIPCHK(refitdev::launch_records(s, t.prims.p, t.nodes.p, t.primIdx.p, 0u, lights, (uint32_t)nLights, (uint32_t)std::max(rq.first, 0), (uint32_t)rq.count,
                                     nullptr, 0u, nullptr, nullptr, t.shadeRecs.p, t.lightRecs.p));
     if (!layout1) return RT_OK;
     for (size_t k = 0; k < nR; k++) {
-        RtFloat4* const recs = t.triRecs.p + (size_t)idxOf[k] * 3;
+        RtFloat4* const recs = t.triRecs.p + (size_t)next.block[k].idxLo * 3;
         if (moves(k) && !refits(k)) {
-            HIPCHK(hipMemcpyAsync(recs, sc.triRecs + (size_t)b.blasBlock[k].idxLo * 3, sizeof(RtFloat4) * 3 * (size_t)slotsOf[k], hipMemcpyDeviceToDevice, s));
-            info.slots_relocated += (int32_t)slotsOf[k];
+            HIPCHK(hipMemcpyAsync(recs, sc.triRecs + (size_t)b.live.block[k].idxLo * 3, sizeof(RtFloat4) * 3 * (size_t)next.block[k].idxSlots, hipMemcpyDeviceToDevice, s));
+            info.slots_relocated += (int32_t)next.block[k].idxSlots;
             continue;
         }
-        const uint32_t boxes = refits(k) ? interiors[k] : 0u;   // (a built BLAS: k_rb_pairs wrote them)
-        HIPCHK(refitdev::launch_blas_records(s, t.prims.p, t.nodes.p, t.pairNode.p + pairLo[k], boxes, boxes ? t.pairs.p + (size_t)pairLo[k] * 4 : nullptr,
-                                             t.primIdx.p + idxOf[k], slotsOf[k], recs));
-        info.slots_derived += (int32_t)slotsOf[k];
+        const uint32_t boxes = refits(k) ? next.interiors(k) : 0u;   // (a built BLAS: k_rb_pairs wrote them)
+        HIPCHK(refitdev::launch_blas_records(s, t.prims.p, t.nodes.p, t.pairNode.p + next.pairLo[k], boxes, boxes ? t.pairs.p + (size_t)next.pairLo[k] * 4 : nullptr,
+                                             t.primIdx.p + next.block[k].idxLo, next.block[k].idxSlots, recs));
+        info.slots_derived += (int32_t)next.block[k].idxSlots;
     }
     return RT_OK;
 }
@@ -631,7 +630,7 @@ int Pending::read_back(bool timed)
     if (!refit) HIPCHK(hipMemcpyAsync(walk, b.dw.ctr + rebuilddev::kStatus, sizeof walk, hipMemcpyDeviceToHost, s));
     if (bvh4 && refitPath != 1) HIPCHK(c4.read(s, b.c4));
     HIPCHK(hipStreamSynchronize(s));
-    if (bvh4 && refitPath == 1) c4.at(collapsedev::kNeed) = b.c4Need;   // (a top-down figure: carried over with the live ids)
+    if (bvh4 && refitPath == 1) c4.at(collapsedev::kNeed) = b.live.c4Need;   // (a top-down figure: carried over with the live ids)
     if (walk[0]) return fail(RT_E_DEVICE, "%s: the breadth-first walk does not match the builder's tree (inconsistent device result)", who);
     if (bvh4) {
         if (const int rc = c4.error(who, "; the scene is unchanged")) return rc;
@@ -640,13 +639,22 @@ int Pending::read_back(bool timed)
     if (const int rc = tlas_status_error(who, tlas)) return rc;
     stackNeed = bvh4 ? (int)c4.need() : (int)maxDepth;
     // (a refit moves no leaf size: a BVH2 copy keeps its layout, a BVH4 copy's check cannot fail)
-    if (!(refit && !bvh4) && rebuild::takes_layout1(b.variantLayout1, (int32_t)nIdx, std::max(walk[1], 1u)) != layout1)
+    if (!(refit && !bvh4) && rebuild::takes_layout1(b.variantLayout1, (int32_t)next.nIdx, std::max(walk[1], 1u)) != layout1)
         return fail(RT_E_UNSUPPORTED, "%s: the new trees would change the scene's derived layout (largest leaf %u primitives, %u index slots; "
-                    "layout %d is bound): upload the rebuilt scene instead; the scene is unchanged", who, walk[1], nIdx, b.layout);
+                    "layout %d is bound): upload the rebuilt scene instead; the scene is unchanged", who, walk[1], next.nIdx, b.facts.layout);
     if (resize) {
-        packed.resize((size_t)sh.nPrims);
+        std::vector<int2> packed((size_t)nPrims);
         HIPCHK(hipMemcpy(packed.data(), b.rPacked.p, sizeof(int2) * packed.size(), hipMemcpyDeviceToHost));
+        primType.resize(packed.size()); primMat.resize(packed.size());
+        for (size_t i = 0; i < packed.size(); i++) { primType[i] = packed[i].x; primMat[i] = packed[i].y; }
     }
+    // the trees and the facts are complete: the set's arrays lie where they will stay, the collapse has counted
+    next.parent = t.parent.p; next.leaves = t.leaves.p; next.tickets = t.tickets.p; next.pairNode = t.pairNode.p;
+    if (!(layout1 && !bvh4)) next.nPairs = 0;   // (no pair table is bound)
+    if (bvh4) { next.newId = t.newId.p; next.quadNode = t.quadNode.p; next.nLive = c4.live(); next.c4Need = c4.need(); }
+    facts.stackEntries = rebuild::stack_entries(std::max(stackNeed, 1));   // (a BVH4: the collapsed trees' need, as validate_scene replays it)
+    facts.tlasDepth = tlas[1]; facts.nInterior = (int)next.nPairs; facts.nQuads = layout1 && bvh4 ? (int32_t)c4.live() : 0;
+    if (resize) facts.singleBlas = nBlas == 1;   // (the TLAS root is a leaf iff there is one instance: TLAS::Build copies it to node 0)
     if (timed) {   // (the events have passed: the stream is idle)
         (void)hipEventElapsedTime(&gpuMs, b.rev[0], b.rev[3]); (void)hipEventElapsedTime(&fitMs, b.rev[0], b.rev[1]);
         (void)hipEventElapsedTime(&deriveMs, b.rev[1], b.rev[2]); (void)hipEventElapsedTime(&tlasMs, b.rev[2], b.rev[3]);
@@ -654,7 +662,8 @@ int Pending::read_back(bool timed)
     return RT_OK;
 }
 
-// 6. Commit: the holders have been waited for; swap the arrays and take over the new scene's facts.  Host memory only: no device call
+// 6. Commit: the holders have been waited for.  Swap the arrays, assign the facts, move the trees and the host shadows in.  Host memory
+// only: no device call
 void Pending::commit()
 {
     SceneArrays n = b.sc;
@@ -665,42 +674,17 @@ void Pending::commit()
     if (layout1 && !bvh4) n.pairs = t.pairs.p;
     if (layout1) { n.triRecs = t.triRecs.p; n.rootEntry = t.rootEntry.p; }
     if (bvh4) { n.bvh4 = t.bvh4.p; if (layout1) n.quads = t.quads.p; }
-    if (resize) {   // the new shape: the counts, the TLAS root (a leaf iff there is one instance: TLAS::Build copies it to node 0)
-        n.nPrims = sh.nPrims; n.nLights = nLights; n.nBlas = sh.nBlas;
-        const bool leafRoot = sh.nBlas == 1;
-        n.tlasRoot = leafRoot ? refit::tlas_leaf_entry(false, 0u) : refit::tlas_node_entry(false, 0u);   // (instance 0, or TLAS node 0)
-        n.tlasRootP = leafRoot ? refit::tlas_leaf_entry(true, 0u) : refit::tlas_node_entry(true, 0u);
-        b.singleBlas = leafRoot; b.lightsInSet = true;
-        b.nPrims = sh.nPrims; b.nLights = nLights; b.nBlas = sh.nBlas; b.nTlas = sh.nTlas();
-        b.primType.resize(packed.size()); b.primMat.resize(packed.size());
-        for (size_t i = 0; i < packed.size(); i++) { b.primType[i] = packed[i].x; b.primMat[i] = packed[i].y; }
-        b.ranges = *sh.ranges; b.instBlas = *sh.instBlas;   // (the caller's own vectors: never the bag's)
+    if (resize) {   // the new shape: the counts, the TLAS root (instance 0, or TLAS node 0)
+        n.nPrims = nPrims; n.nLights = nLights; n.nBlas = nBlas;
+        n.tlasRoot = facts.singleBlas ? refit::tlas_leaf_entry(false, 0u) : refit::tlas_node_entry(false, 0u);
+        n.tlasRootP = facts.singleBlas ? refit::tlas_leaf_entry(true, 0u) : refit::tlas_node_entry(true, 0u);
     }
-    b.sc = n;
-    b.dParent = t.parent.p; b.dLeaves = t.leaves.p; b.dTickets = t.tickets.p; b.dPairNode = t.pairNode.p;
-    b.nNodes = (int32_t)nNodes; b.nIdx = (int32_t)nIdx; b.nPairs = layout1 && !bvh4 ? (int32_t)nPairs : 0; b.nLeaves = nLeaves;
-    b.nQuads = layout1 && bvh4 ? (int32_t)c4.live() : 0;
-    if (!refit) {   // (a refit moves no tree: roots and blocks stay)
-        b.nReach = nNodes;
-        b.blasBlock.resize(nR);
-        b.blasPairLo = pairLo; b.blasLeafLo = leafLo;
-        for (size_t k = 0; k < nR; k++) {
-            b.ranges[k].root = rootOf[k];
-            b.blasBlock[k] = rebuild::BlasBlock{ 2 * interiors[k] + 1, idxOf[k], slotsOf[k], 1, depth[k] };
-        }
-    }
-    if (bvh4) {   // the live collapse's tables follow the sets
-        b.liveNewId = t.newId.p; b.liveQuadNode = t.quadNode.p;
-        b.nLive = c4.live(); b.c4Need = c4.need();
-    }
+    reconfigured = facts.tlasDepth != b.facts.tlasDepth || facts.stackEntries != b.facts.stackEntries;
+    b.sc = n; b.facts = facts; b.live = std::move(next);
+    if (resize) { b.primType = std::move(primType); b.primMat = std::move(primMat); b.lightsInSet = true; }
+    b.inst = std::move(inst);
     if (rq.perRange) { info.built = nBuilt; b.rangesInfo = info; }
-    if (refit) b.refitInfo = RtRefitInfo{ refitPath, bvh4 ? (int32_t)b.nLive : 0, (int32_t)changed, stackNeed };
-    b.inst = inst;
-    const int stackEntries = rebuild::stack_entries(std::max(stackNeed, 1));   // (a BVH4: the collapsed trees' need, as validate_scene replays it)
-    reconfigured = tlas[1] != b.tlasDepth || stackEntries != b.stackEntries;
-    b.tlasDepth = tlas[1];
-    b.stackEntries = stackEntries;
-    b.nInterior = layout1 && !bvh4 ? (int)nPairs : 0;
+    if (refit) b.refitInfo = RtRefitInfo{ refitPath, bvh4 ? (int32_t)b.live.nLive : 0, (int32_t)changed, stackNeed };
     b.generation++;   // every holder takes the new arrays (and re-derives its traversal kernels) before its next launch
     b.rnext ^= 1;
 }
@@ -726,8 +710,8 @@ static int rebuild_body(SceneBag& b, const Request& rq, RtRebuildStats* stats)
         stats->stage_ms = ms_between(pd.t0, pd.t1); stats->derive_ms = pd.deriveMs; stats->tlas_ms = pd.tlasMs;
         stats->build_ms = pd.refit ? pd.fitMs : ms_between(pd.t1, pd.t2);   // (a refit: GPU time of the staging copies and the refit)
         stats->commit_ms = ms_between(pd.t3, t4);
-        stats->prims = pd.resize ? rq.sh.nPrims : rq.count; stats->blas_built = pd.nBuilt; stats->nodes = (int32_t)pd.nNodes; stats->n_idx = (int32_t)pd.nIdx;
-        stats->max_depth = (int32_t)pd.maxDepth; stats->tlas_nodes = b.nTlas; stats->tlas_depth = pd.tlas[1]; stats->reconfigured = pd.reconfigured ? 1 : 0;
+        stats->prims = pd.resize ? rq.nPrims : rq.count; stats->blas_built = pd.nBuilt; stats->nodes = (int32_t)b.live.nNodes; stats->n_idx = (int32_t)b.live.nIdx;
+        stats->max_depth = (int32_t)pd.maxDepth; stats->tlas_nodes = b.live.nTlas; stats->tlas_depth = pd.tlas[1]; stats->reconfigured = pd.reconfigured ? 1 : 0;
         stats->spatial_splits = (int32_t)std::min<uint64_t>(pd.spatialSplits, 0x7fffffffu); stats->prims_clipped = (int32_t)std::min<uint64_t>(pd.primsClipped, 0x7fffffffu);
     }
     return RT_OK;
@@ -742,10 +726,9 @@ int scenedev::rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first
     if (const int rc = check_builder(who, builder, opts, true)) return rc;
     if (const int rc = check_change(who, b, prims, first, count, blas, nBlas, "")) return rc;
     lbvh::Params P{};
-    const std::vector<int32_t> plan(builder == RT_REBUILD_REFIT ? 0 : b.ranges.size(), builder);   // every range: `builder`
-    if (!plan.empty()) if (const int rc = check_ranges(who, plan.data(), opts, b.nPrims, b.ranges, nullptr, P)) return rc;
-    const Shape sh{ b.nPrims, b.nBlas, b.nLights, &b.ranges, &b.instBlas };
-    return rebuild_body(b, Request{ who, sh, nullptr, prims, first, count, blas, plan, opts, P }, stats);
+    const std::vector<int32_t> plan(builder == RT_REBUILD_REFIT ? 0 : b.live.ranges.size(), builder);   // every range: `builder`
+    if (!plan.empty()) if (const int rc = check_ranges(who, plan.data(), opts, b.sc.nPrims, b.live.ranges, nullptr, P)) return rc;
+    return rebuild_body(b, Request{ who, b.sc.nPrims, b.sc.nBlas, nullptr, prims, first, count, blas, plan, opts, P }, stats);
 }
 // The checks of a plan that need no device: the plan itself (rebuild::check_plan), alpha and the builders' own argument checks
 static int plan_check_args(const char* who, int32_t nPrims, const std::vector<rebuild::BlasRange>& ranges, const rebuild::BlasBlock* blocks, const int32_t* plan,
@@ -786,9 +769,8 @@ int scenedev::rebuild_ranges(SceneBag& b, const RtPrimitive* prims, int32_t firs
     if (b.rebuildRefusal) return fail(RT_E_UNSUPPORTED, "%s: %s", who, b.rebuildRefusal);
     if (const int rc = check_change(who, b, prims, first, count, blas, nBlas, "")) return rc;
     lbvh::Params P{};
-    if (const int rc = plan_check_args(who, b.nPrims, b.ranges, b.blasBlock.data(), plan, nRanges, first, count, opts, P)) return rc;
-    const Shape sh{ b.nPrims, b.nBlas, b.nLights, &b.ranges, &b.instBlas };
-    return rebuild_body(b, Request{ who, sh, nullptr, prims, first, count, blas, std::vector<int32_t>(plan, plan + nRanges), opts, P, true }, stats);
+    if (const int rc = plan_check_args(who, b.sc.nPrims, b.live.ranges, b.live.block.data(), plan, nRanges, first, count, opts, P)) return rc;
+    return rebuild_body(b, Request{ who, b.sc.nPrims, b.sc.nBlas, nullptr, prims, first, count, blas, std::vector<int32_t>(plan, plan + nRanges), opts, P, true }, stats);
 }
 
 // The ranges of a caller's shape as the builders take them (root: assigned by the build)
@@ -830,14 +812,14 @@ int scenedev::resize_scene(SceneBag& b, const void* prims, int32_t nPrims, const
     if (b.rebuildRefusal) return fail(RT_E_UNSUPPORTED, "rt_resize_scene: %s", b.rebuildRefusal);
     {   // the bound ranges (in increasing order) must tile the bound primitives
         uint32_t next = 0;
-        for (const rebuild::BlasRange& r : b.ranges) {
+        for (const rebuild::BlasRange& r : b.live.ranges) {
             if (r.first != next) return fail(RT_E_UNSUPPORTED, "rt_resize_scene: the bound scene's BLAS ranges leave a gap: primitives [%u, %u) belong to no BLAS", next, r.first);
             next = r.first + r.count;
         }
-        if (next != (uint32_t)b.nPrims)
-            return fail(RT_E_UNSUPPORTED, "rt_resize_scene: the bound scene's BLAS ranges leave a gap: primitives [%u, %d) belong to no BLAS", next, b.nPrims);
+        if (next != (uint32_t)b.sc.nPrims)
+            return fail(RT_E_UNSUPPORTED, "rt_resize_scene: the bound scene's BLAS ranges leave a gap: primitives [%u, %d) belong to no BLAS", next, b.sc.nPrims);
     }
-    const std::vector<int32_t> instBlas(shape->instRange, shape->instRange + shape->nBlas);
-    const Shape sh{ nPrims, shape->nBlas, 0, &ranges, &instBlas };
-    return rebuild_body(b, Request{ who, sh, prims, nullptr, 0, 0, shape->blas, std::vector<int32_t>(ranges.size(), builder), opts, P }, stats);   // (never RT_REBUILD_KEEP)
+    const std::vector<int32_t> plan(ranges.size(), builder);   // (never RT_REBUILD_KEEP)
+    return rebuild_body(b, Request{ who, nPrims, shape->nBlas, prims, nullptr, 0, 0, shape->blas, plan, opts, P, false, std::move(ranges),
+                                    std::vector<int32_t>(shape->instRange, shape->instRange + shape->nBlas) }, stats);
 }
