@@ -515,6 +515,56 @@ int rt_resize_scene(RtCtx* ctx, const void* prims, int32_t nPrims, const RtScene
 /* The checks of rt_resize_scene that need neither a device nor a bound scene: nPrims, the shape, the builder and opts.  RT_OK, or
  * RT_E_INVALID with the message rt_resize_scene would give. */
 int rt_resize_check(int32_t nPrims, const RtSceneShape* shape, int32_t builder, const RtBuildOptions* opts);
+/* ---- replacement geometry from the GPU (rt_update_geometry, rt_rebuild_geometry, rt_rebuild_geometry_ranges) ---------------------------
+ * rt_update_scene, rt_rebuild_scene and rt_rebuild_ranges take RtPrimitive[count] in host memory.  Skinning, cloth or a simulation
+ * produce vertex positions on the device; RtGeometry describes the replacement of the window [first, first + count) in either form, and
+ * wherever it lies:
+ *   records form  (prims)      what the old calls take, in host memory or in memory the context's GPU reaches.  objType and matIdx must
+ *                              stay; the rule is checked where the records lie: host records by the old calls' loop, device-reachable
+ *                              records by k_window_check (one thread per record against the bound one, the lowest offending index
+ *                              found through atomicMin), with the old calls' message from the values read back for that one record.
+ *   vertex form   (positions)  every primitive of the window must be a triangle (checked on the host, before any device work).  Triangle
+ *                              i of the window takes vertices indices[3i .. 3i+2], or 3i .. 3i+2 without indices.  k_tri_from_vertices,
+ *                              one thread per triangle, writes v0, v1, v2, N, centroid and area by Scene::AddTriangle's rule
+ *                              (csrc/geometry_common.h, which the host mirror rth_set_vertices compiles too); uv*, objType, matIdx and
+ *                              the pad words stay as bound.  AddTriangle's flip is not stored in a record: the new N is negated iff
+ *                              dot(bound N, cross(bound v1 - bound v0, bound v2 - bound v0)) < 0, which is false for zero and NaN (a
+ *                              bound triangle without a normal counts as not flipped).  An index >= nVertices is never followed: the
+ *                              triangle of lowest index that has one is reported, and nothing is bound.
+ *                              A triangle whose cross product is zero or not finite gets NaN in N and may get NaN in area; x86 and the
+ *                              GPU make NaNs of different sign, so for such a triangle the promise is "NaN where the host has NaN", not
+ *                              equal bits.  Every other word is bit for bit the host mirror's.
+ * With count > 0 exactly one of prims / positions is given.  Where memory may lie is rt_resize_scene's rule (host memory, or device,
+ * managed or pinned memory the context's GPU reaches); alignment (4 bytes) and the end of an allocation the runtime knows are rt_trace's
+ * rule.  The copies and kernels run on the scene copy's own stream, which waits for no other: device work that produces the data must be
+ * complete, or ordered before the call by the caller (Device.update_geometry waits for torch's current stream).
+ * The contract in one sentence: each call leaves the scene copy as its counterpart - rt_update_scene, rt_rebuild_scene,
+ * rt_rebuild_ranges - leaves it for host records over the same window: the given ones in records form, the bound ones rewritten by
+ * geometry_common.h's rule in vertex form.  That covers every array of rt_debug_get_scene_array with its size, rt_kernel_info, the
+ * stats and rt_ranges_info; so everything the counterparts promise carries over: equality with a fresh upload of the host mirror's
+ * scene, refusals that change nothing, the window rule of a range plan, the wait for the holders, the allocation counting of
+ * rt_debug_rebuild_allocations (index and status scratch grows as the staging arrays do: a repeated call stops allocating).  BVH4
+ * contexts answer as their counterparts do.  The old entry points are these with a host-records RtGeometry.
+ * Refusals beyond the counterparts', all RT_E_INVALID and before anything is bound: a null geometry, a negative first or count, a window
+ * outside the bound primitives, both sources or neither with count > 0, a positionStride below 12 or no multiple of 4, nVertices < 0,
+ * nVertices < 3 * count without indices, a non-triangle in the window (vertex form), a pointer that breaks the rules above, and - found
+ * on the device - a record that changes objType / matIdx or an index >= nVertices. */
+typedef struct RtGeometry {
+    int32_t     first, count;     /* the window [first, first + count) of the bound primitives; count 0: geometry unchanged        */
+    const void* prims;            /* RtPrimitive[count], host memory or memory the context's GPU reaches; or NULL                  */
+    const void* positions;        /* vertex j's x, y, z (float32) at positions + j * positionStride, host or device-reachable; or NULL */
+    int64_t     positionStride;   /* bytes, >= 12 and a multiple of 4                                                              */
+    int64_t     nVertices;        /* vertices behind `positions`                                                                    */
+    const void* indices;          /* uint32[3 * count], host or device-reachable; NULL: triangle i takes vertices 3i, 3i+1, 3i+2   */
+} RtGeometry;
+int rt_update_geometry(RtCtx* ctx, const RtGeometry* geometry, const RtBVHInstance* blas, int32_t nBlas, RtUpdateStats* stats);
+int rt_rebuild_geometry(RtCtx* ctx, const RtGeometry* geometry, const RtBVHInstance* blas, int32_t nBlas, int32_t builder, const RtBuildOptions* opts,
+                        RtRebuildStats* stats);
+int rt_rebuild_geometry_ranges(RtCtx* ctx, const RtGeometry* geometry, const RtBVHInstance* blas, int32_t nBlas, const int32_t* plan, int32_t nRanges,
+                               const RtBuildOptions* opts, RtRebuildStats* stats);
+/* The checks of an RtGeometry that need no device: nPrims primitives are bound, objType[nPrims] their types (NULL: all triangles).
+ * RT_OK, or the code and message the device calls give. */
+int rt_geometry_check(const RtGeometry* geometry, int32_t nPrims, const int32_t* objType);
 /* ---- in-place material updates (a bound scene changes its materials, its texture atlas and its primitives' matIdx on the device) ------
  * A lamp switched on, a recoloured object, a video texture played from a device buffer, a repainted part of a mesh: no tree changes and
  * a few hundred bytes do.  The three parts of an update are independent; a part whose pointer is NULL stays as bound, and a call with
@@ -672,6 +722,11 @@ int rt_group_rebuild_ranges(RtGroup* g, const RtPrimitive* prims, int32_t first,
 int rt_group_resize_scene(RtGroup* g, const void* prims, int32_t nPrims, const RtSceneShape* shape, int32_t builder, const RtBuildOptions* opts,
                           RtRebuildStats* stats);                            /* rt_resize_scene for the group's copy (all lanes)        */
 int rt_group_update_materials(RtGroup* g, const RtMaterialUpdate* update, RtMaterialStats* stats);   /* rt_update_materials, likewise  */
+int rt_group_update_geometry(RtGroup* g, const RtGeometry* geometry, const RtBVHInstance* blas, int32_t nBlas, RtUpdateStats* stats);   /* rt_update_geometry for the group's copy */
+int rt_group_rebuild_geometry(RtGroup* g, const RtGeometry* geometry, const RtBVHInstance* blas, int32_t nBlas, int32_t builder, const RtBuildOptions* opts,
+                              RtRebuildStats* stats);                        /* rt_rebuild_geometry likewise                            */
+int rt_group_rebuild_geometry_ranges(RtGroup* g, const RtGeometry* geometry, const RtBVHInstance* blas, int32_t nBlas, const int32_t* plan, int32_t nRanges,
+                                     const RtBuildOptions* opts, RtRebuildStats* stats);   /* rt_rebuild_geometry_ranges likewise       */
 int rt_group_seed(RtGroup* g, uint64_t firstStream);                         /* a single Renderer: 0 (what rt_group_create leaves);
                                                                               * rank r of a sample split: r*lanes                       */
 int rt_group_reset(RtGroup* g);                                              /* resetKernel on every lane; frames = 0                   */

@@ -76,6 +76,12 @@ int rth_build_bvh2_sbvh(float alpha, const RtPrimitive* prims, int32_t nPrims, i
  * change nothing when refused. */
 int rth_set_primitives(RthScene* s, int first, int count, const RtPrimitive* prims);
 int rth_refit(RthScene* s);
+/* The host restatement of RtGeometry's vertex form (rt355.h): triangles [first, first + count) move to the vertices at positions
+ * (vertex j at positions + j * strideBytes; nVertices of them) named by indices (3 * count of them; NULL: 3i, 3i + 1, 3i + 2), by the
+ * rule of csrc/geometry_common.h that k_tri_from_vertices compiles too: v0, v1, v2, N, centroid and area anew, everything else of the
+ * record as it is.  The refusals are the device call's (a non-triangle in the window, a bad stride, too few vertices, an index >=
+ * nVertices, ...): RT_E_INVALID, and nothing has changed.  rth_refit next, as after rth_set_primitives. */
+int rth_set_vertices(RthScene* s, int first, int count, const float* positions, int64_t strideBytes, int64_t nVertices, const uint32_t* indices);
 /* The host restatement of rt_rebuild_scene's BLAS rebuild (rt355.h): discards the scene's BVH2 and builds every distinct BLAS again
  * over the primitive range it covers (in increasing order of the ranges, appended as BuildBLAS appends BLAS after BLAS) with the host
  * restatement of the chosen builder: RT_REBUILD_SAH (rth_build_bvh2_sah; opts ignored), RT_REBUILD_LBVH (rth_build_bvh2_lbvh, opts

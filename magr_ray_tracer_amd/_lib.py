@@ -117,6 +117,9 @@ assert MaterialStats.itemsize == 48
 SceneShape = np.dtype([("nRanges", "<i4"), ("_pad0", "<i4"), ("rangeCount", "<u8"), ("nBlas", "<i4"), ("_pad1", "<i4"), ("instRange", "<u8"),
                        ("blas", "<u8")])   # RtSceneShape
 assert SceneShape.itemsize == 40
+Geometry = np.dtype([("first", "<i4"), ("count", "<i4"), ("prims", "<u8"), ("positions", "<u8"), ("positionStride", "<i8"), ("nVertices", "<i8"),
+                     ("indices", "<u8")])   # RtGeometry
+assert Geometry.itemsize == 48
 UpdateStats = np.dtype([("gpu_ms", "<f8"), ("prims", "<i4"), ("nodes", "<i4"), ("tlas_nodes", "<i4"), ("tlas_depth", "<i4"),
                         ("reconfigured", "<i4"), ("reserved", "<i4", 3)])
 assert UpdateStats.itemsize == 40
@@ -149,7 +152,9 @@ DEVICE_SYMBOLS = [
     "rt_group_postproc", "rt_trace", "rt_trace_window", "rt_resize_scene", "rt_group_resize_scene", "rt_resize_check",
     "rt_update_materials", "rt_group_update_materials", "rt_materials_check",
     "rt_rebuild_ranges", "rt_group_rebuild_ranges", "rt_scene_blas_blocks", "rt_rebuild_ranges_check", "rt_blas_blocks",
-    "rt_debug_traversal_plan", "rt_debug_traversal_facts", "rt_ranges_info", "rt_debug_derive_pairs", "rt_debug_relocate_pairs"]
+    "rt_debug_traversal_plan", "rt_debug_traversal_facts", "rt_ranges_info", "rt_debug_derive_pairs", "rt_debug_relocate_pairs",
+    "rt_update_geometry", "rt_rebuild_geometry", "rt_rebuild_geometry_ranges", "rt_group_update_geometry", "rt_group_rebuild_geometry",
+    "rt_group_rebuild_geometry_ranges", "rt_geometry_check"]
 HOST_SYMBOLS = [
     "rth_last_error", "rth_scene_create", "rth_scene_destroy", "rth_add_material", "rth_add_texture", "rth_load_texture", "rth_add_sphere",
     "rth_add_plane", "rth_add_triangle", "rth_add_quad", "rth_add_triangles", "rth_build_blas", "rth_build_bvh4",
@@ -161,7 +166,7 @@ HOST_SYMBOLS = [
     "rth_build_blas_lbvh", "rth_build_bvh2_lbvh", "rth_lbvh_stats", "rth_set_primitives", "rth_refit",
     "rth_build_blas_sah_gpu", "rth_build_bvh2_sah", "rth_build_blas_sbvh_gpu", "rth_build_bvh2_sbvh", "rth_rebuild", "rth_blas_ranges",
     "rth_build_bvh4_gpu", "rth_build_bvh4_levels", "rth_bvh4_refit", "rth_refit_bvh4", "rth_add_instance", "rth_light_list",
-    "rth_set_materials", "rth_set_texels", "rth_set_prim_materials", "rth_rebuild_ranges", "rth_swap_instances"]
+    "rth_set_materials", "rth_set_texels", "rth_set_prim_materials", "rth_rebuild_ranges", "rth_swap_instances", "rth_set_vertices"]
 
 _dev = None
 _host = None
@@ -272,6 +277,13 @@ def _bind_device(lib):
         lib.rt_scene_blas_blocks.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32]
         lib.rt_rebuild_ranges_check.argtypes = [i32, vp, vp, vp, i32, vp, i32, i32, i32, vp]
         lib.rt_blas_blocks.argtypes = [vp, i32, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32]
+        lib.rt_update_geometry.argtypes = [vp, vp, vp, i32, vp]
+        lib.rt_group_update_geometry.argtypes = [vp, vp, vp, i32, vp]
+        lib.rt_rebuild_geometry.argtypes = [vp, vp, vp, i32, i32, vp, vp]
+        lib.rt_group_rebuild_geometry.argtypes = [vp, vp, vp, i32, i32, vp, vp]
+        lib.rt_rebuild_geometry_ranges.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp]
+        lib.rt_group_rebuild_geometry_ranges.argtypes = [vp, vp, vp, i32, vp, i32, vp, vp]
+        lib.rt_geometry_check.argtypes = [vp, i32, vp]
         lib.rt_resize_scene.argtypes = [vp, vp, i32, vp, i32, vp, vp]
         lib.rt_group_resize_scene.argtypes = [vp, vp, i32, vp, i32, vp, vp]
         lib.rt_resize_check.argtypes = [i32, vp, i32, vp]
@@ -341,6 +353,7 @@ def host_lib():
         lib.rth_build_bvh2_sbvh.argtypes = [C.c_float, vp, C.c_int32, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, vp, C.c_int32,
                                             C.POINTER(C.c_int32), vp, C.c_int32, C.POINTER(C.c_int32), vp]
         lib.rth_set_primitives.argtypes = [vp, i32, i32, vp]
+        lib.rth_set_vertices.argtypes = [vp, i32, i32, vp, C.c_int64, C.c_int64, vp]
         lib.rth_refit.argtypes = [vp]
         lib.rth_rebuild.argtypes = [vp, i32, vp]
         lib.rth_rebuild_ranges.argtypes = [vp, vp, i32, vp]

@@ -29,9 +29,9 @@ CSRC = os.path.join(PKG, "csrc")
 # (math_debug.hip), the device copy of a scene (host code, no kernel: scene.hip uploads it, scene_rebuild.hip holds rt_update_scene and the
 # in-place rebuilds, scene_materials.hip rt_update_materials; they drive the kernels of the files below), then rt_build_bvh2 (linear BVH
 # builder), the refit kernels, rt_build_bvh2_sah (SAH builder), the kernels of what upload derives from a BVH2 (rebuild),
-# rt_build_bvh2_sbvh (SBVH builder) and rt_build_bvh4 (the BVH2 -> BVH4 collapse)
+# rt_build_bvh2_sbvh (SBVH builder), rt_build_bvh4 (the BVH2 -> BVH4 collapse) and the kernels behind an RtGeometry on the device (geometry)
 DEVICE_SRCS = [os.path.join(CSRC, f) for f in ("rt355.hip", "group.hip", "math_debug.hip", "scene.hip", "scene_rebuild.hip", "scene_materials.hip", "lbvh.hip",
-                                               "refit.hip", "sah.hip", "rebuild.hip", "sbvh.hip", "collapse.hip")]
+                                               "refit.hip", "sah.hip", "rebuild.hip", "sbvh.hip", "collapse.hip", "geometry.hip")]
 
 
 def _headers(*dirs):

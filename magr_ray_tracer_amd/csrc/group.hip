@@ -330,6 +330,23 @@ extern "C" int rt_group_rebuild_ranges(RtGroup* g, const RtPrimitive* prims, int
     if (!g) return fail(RT_E_INVALID, "rt_group_rebuild_ranges: null group");
     return rt_rebuild_ranges(rt_group_lane(g, 0), prims, first, count, blas, nBlas, plan, nRanges, opts, stats);   // every lane holds lane 0's copy
 }
+extern "C" int rt_group_update_geometry(RtGroup* g, const RtGeometry* geometry, const RtBVHInstance* blas, int32_t nBlas, RtUpdateStats* stats)
+{
+    if (!g) return fail(RT_E_INVALID, "rt_group_update_geometry: null group");
+    return rt_update_geometry(rt_group_lane(g, 0), geometry, blas, nBlas, stats);   // every lane holds lane 0's copy
+}
+extern "C" int rt_group_rebuild_geometry(RtGroup* g, const RtGeometry* geometry, const RtBVHInstance* blas, int32_t nBlas, int32_t builder, const RtBuildOptions* opts,
+                                         RtRebuildStats* stats)
+{
+    if (!g) return fail(RT_E_INVALID, "rt_group_rebuild_geometry: null group");
+    return rt_rebuild_geometry(rt_group_lane(g, 0), geometry, blas, nBlas, builder, opts, stats);   // every lane holds lane 0's copy
+}
+extern "C" int rt_group_rebuild_geometry_ranges(RtGroup* g, const RtGeometry* geometry, const RtBVHInstance* blas, int32_t nBlas, const int32_t* plan, int32_t nRanges,
+                                                const RtBuildOptions* opts, RtRebuildStats* stats)
+{
+    if (!g) return fail(RT_E_INVALID, "rt_group_rebuild_geometry_ranges: null group");
+    return rt_rebuild_geometry_ranges(rt_group_lane(g, 0), geometry, blas, nBlas, plan, nRanges, opts, stats);   // every lane holds lane 0's copy
+}
 extern "C" int rt_group_resize_scene(RtGroup* g, const void* prims, int32_t nPrims, const RtSceneShape* shape, int32_t builder, const RtBuildOptions* opts,
                                      RtRebuildStats* stats)
 {

@@ -17,6 +17,7 @@
 #include "../../include/rt355.h"
 #include "rt355_kernels.h"
 #include "ctx.h"
+#include "geometry_common.h"
 
 using namespace rt355dev;
 using namespace scenedev;
@@ -684,26 +685,26 @@ extern "C" int rt_update_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t fir
     if (const int rc = bound_scene(ctx, "rt_update_scene")) return rc;
     if (ctx->cfg.accel != RT_ACCEL_BVH2)
         return fail(RT_E_UNSUPPORTED, "rt_update_scene: BVH4 contexts cannot refit (rt_rebuild_scene a copy bound with rt_upload_scene_bvh2, or rebuild and upload)");
-    return update_scene(*ctx->scene, prims, first, count, blas, nBlas, stats);
+    return update_scene(*ctx->scene, "rt_update_scene", Geometry::host_records(prims, first, count), blas, nBlas, stats);
 }
 extern "C" int rt_rebuild_scene(RtCtx* ctx, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
                                 int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats)
 {
     if (const int rc = bound_scene(ctx, "rt_rebuild_scene", kCannotRebuild)) return rc;
-    return rebuild_scene(*ctx->scene, prims, first, count, blas, nBlas, builder, opts, stats);
+    return rebuild_scene(*ctx->scene, "rt_rebuild_scene", Geometry::host_records(prims, first, count), blas, nBlas, builder, opts, stats);
 }
 extern "C" int rt_rebuild_ranges(RtCtx* ctx, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
                                  const int32_t* plan, int32_t nRanges, const RtBuildOptions* opts, RtRebuildStats* stats)
 {
     if (const int rc = bound_scene(ctx, "rt_rebuild_ranges", kCannotRebuild)) return rc;
-    return rebuild_ranges(*ctx->scene, prims, first, count, blas, nBlas, plan, nRanges, opts, stats);
+    return rebuild_ranges(*ctx->scene, "rt_rebuild_ranges", Geometry::host_records(prims, first, count), blas, nBlas, plan, nRanges, opts, stats);
 }
 extern "C" int rt_scene_blas_blocks(RtCtx* ctx, int32_t* n, int32_t* primFirst, int32_t* primCount, int32_t* nodes, int32_t* idxSlots, int32_t* compact, int32_t cap)
 {
     if (const int rc = bound_scene(ctx, "rt_scene_blas_blocks", "")) return rc;
     return blas_blocks(*ctx->scene, n, primFirst, primCount, nodes, idxSlots, compact, cap);
 }
-static int device_pointer(const RtCtx* ctx, const char* who, const char* name, const void* p, int64_t bytes, int align, bool hostAllowed);   // (below, with rt_trace)
+static int device_pointer(const RtCtx* ctx, const char* who, const char* name, const void* p, int64_t bytes, int align, bool hostAllowed, bool* onDevice = nullptr);   // (below, with rt_trace)
 extern "C" int rt_resize_scene(RtCtx* ctx, const void* prims, int32_t nPrims, const RtSceneShape* shape, int32_t builder, const RtBuildOptions* opts,
                                RtRebuildStats* stats)
 {
@@ -731,6 +732,59 @@ extern "C" int rt_update_materials(RtCtx* ctx, const RtMaterialUpdate* update, R
     if (const int rc = update_materials(b, *update, stats)) return rc;
     if (stats) stats->tables_staged_changed = (ctx->var.shadeTables != 0 && shade_tables_fit(b.sc.nLights, b.sc.nMats)) != stagedBefore ? 1 : 0;   // k_shade's own rule
     return RT_OK;
+}
+// ---- rt_update_geometry / rt_rebuild_geometry / rt_rebuild_geometry_ranges: the same three calls fed from an RtGeometry ------------
+// The checks of an RtGeometry that need no device, then rt_resize_scene's pointer rule for every source it names (host memory passes:
+// it is copied; 4-byte alignment and the end of a known allocation are rt_trace's rule); out: the geometry with where its sources lie
+static int locate_geometry(const RtCtx* ctx, const char* who, const RtGeometry* g, Geometry& out)
+{
+    const SceneBag& b = *ctx->scene;
+    std::string msg;
+    if (b.refitRefusal) return fail(RT_E_UNSUPPORTED, "%s: %s", who, b.refitRefusal);   // (such a copy has no shadow of the types)
+    if (const int rc = geometry::check_args(g, b.sc.nPrims, b.primType.data(), msg)) return fail(rc, "%s: %s", who, msg.c_str());
+    out.g = *g;
+    if (g->count == 0) return RT_OK;
+    HIPCHK(hipSetDevice(ctx->cfg.device));
+    if (g->prims) return device_pointer(ctx, who, "prims", g->prims, (int64_t)sizeof(RtPrimitive) * g->count, 4, true, &out.primsOnDevice);
+    if (g->indices)
+        if (const int rc = device_pointer(ctx, who, "indices", g->indices, (int64_t)sizeof(uint32_t) * 3 * g->count, 4, true, &out.indicesOnDevice)) return rc;
+    const int64_t bytes = g->nVertices > 0 ? (g->nVertices - 1) * g->positionStride + 12 : 0;   // to the last vertex's z
+    return device_pointer(ctx, who, "positions", g->positions, bytes, 4, true, &out.positionsOnDevice);
+}
+extern "C" int rt_geometry_check(const RtGeometry* geometry, int32_t nPrims, const int32_t* objType)
+{
+    std::string msg;
+    if (nPrims < 0) return fail(RT_E_INVALID, "rt_geometry_check: nPrims %d is negative", nPrims);
+    if (const int rc = geometry::check_args(geometry, nPrims, objType, msg)) return fail(rc, "rt_geometry_check: %s", msg.c_str());
+    return RT_OK;
+}
+extern "C" int rt_update_geometry(RtCtx* ctx, const RtGeometry* geometry, const RtBVHInstance* blas, int32_t nBlas, RtUpdateStats* stats)
+{
+    const char* who = "rt_update_geometry";
+    if (const int rc = bound_scene(ctx, who)) return rc;
+    if (ctx->cfg.accel != RT_ACCEL_BVH2)
+        return fail(RT_E_UNSUPPORTED, "%s: BVH4 contexts cannot refit (rt_rebuild_geometry a copy bound with rt_upload_scene_bvh2, or rebuild and upload)", who);
+    Geometry geo;
+    if (const int rc = locate_geometry(ctx, who, geometry, geo)) return rc;
+    return update_scene(*ctx->scene, who, geo, blas, nBlas, stats);
+}
+extern "C" int rt_rebuild_geometry(RtCtx* ctx, const RtGeometry* geometry, const RtBVHInstance* blas, int32_t nBlas, int32_t builder, const RtBuildOptions* opts,
+                                   RtRebuildStats* stats)
+{
+    const char* who = "rt_rebuild_geometry";
+    if (const int rc = bound_scene(ctx, who, kCannotRebuild)) return rc;
+    Geometry geo;
+    if (const int rc = locate_geometry(ctx, who, geometry, geo)) return rc;
+    return rebuild_scene(*ctx->scene, who, geo, blas, nBlas, builder, opts, stats);
+}
+extern "C" int rt_rebuild_geometry_ranges(RtCtx* ctx, const RtGeometry* geometry, const RtBVHInstance* blas, int32_t nBlas, const int32_t* plan, int32_t nRanges,
+                                          const RtBuildOptions* opts, RtRebuildStats* stats)
+{
+    const char* who = "rt_rebuild_geometry_ranges";
+    if (const int rc = bound_scene(ctx, who, kCannotRebuild)) return rc;
+    Geometry geo;
+    if (const int rc = locate_geometry(ctx, who, geometry, geo)) return rc;
+    return rebuild_ranges(*ctx->scene, who, geo, blas, nBlas, plan, nRanges, opts, stats);
 }
 extern "C" int rt_refit_info(RtCtx* ctx, RtRefitInfo* out)
 {
@@ -948,7 +1002,8 @@ extern "C" int64_t rt_trace_window(RtCtx* ctx)
 // A pointer the kernels will follow for `bytes` bytes: it must be memory the context's device can reach (a host pointer passed by
 // mistake is an error message here, not a fault there), aligned for the accesses, and - where the runtime knows the allocation - inside it.
 // hostAllowed (rt_resize_scene, which copies from it): memory the runtime does not know, or knows as host memory, passes as well.
-static int device_pointer(const RtCtx* ctx, const char* who, const char* name, const void* p, int64_t bytes, int align, bool hostAllowed)
+// onDevice (may be NULL) receives whether a kernel can follow the pointer.
+static int device_pointer(const RtCtx* ctx, const char* who, const char* name, const void* p, int64_t bytes, int align, bool hostAllowed, bool* onDevice)
 {
     if ((uintptr_t)p % (uintptr_t)align) return fail(RT_E_INVALID, "%s: %s (%p) is not aligned to %d bytes", who, name, p, align);
     hipPointerAttribute_t a{};
@@ -966,6 +1021,7 @@ static int device_pointer(const RtCtx* ctx, const char* who, const char* name, c
             return fail(RT_E_INVALID, "%s: %s needs %lld bytes from %p, its allocation ends %lld bytes earlier", who, name, (long long)bytes, p,
                         (long long)(((const char*)p + bytes) - ((const char*)base + size)));
     }
+    if (onDevice) *onDevice = device || shared;
     return RT_OK;
 }
 static int trace_pointer(const RtCtx* ctx, const char* name, const void* p, int64_t bytes, int align) { return device_pointer(ctx, "rt_trace", name, p, bytes, align, false); }

@@ -15,6 +15,7 @@
 #include "rebuild_dev.h"
 #include "collapse_dev.h"
 #include "build_cores.h"
+#include "geometry_dev.h"
 
 int rt355_set_error(int code, const char* msg);   // rt355.hip: sets the text rt_last_error() returns
 static int fail(int code, const char* fmt, ...)
@@ -152,6 +153,9 @@ struct SceneBag {
     Grown<char> rwork;                        // the builders' workspace (bytes)
     rebuilddev::Work dw{};                    // scratch of the derivation
     int32_t* rStatus = nullptr;               // k_tlas_build's status words (word 0, before that: k_resize_check's lowest refused primitive)
+    // RtGeometry: the status word of its kernels (the lowest refused index of the window), and host positions / host indices of the vertex
+    // form on their way to k_tri_from_vertices; made by the first call that needs them and grown as the staging arrays are
+    Grown<uint32_t> gStatus, gIdx; Grown<char> gPos;
     Grown<int2> rPacked;                      // rt_resize_scene: (objType, matIdx) per new primitive, what the host reads back for primType / primMat
     bool lightsInSet = false;                 // a resize or a material update has bound a light list of its own: rebuilds carry it from set to set from then on
     hipEvent_t rev[4] = { nullptr, nullptr, nullptr, nullptr };
@@ -187,11 +191,25 @@ int validate_scene(int accel, const HostScene& in, SceneFacts* factsOut, int64_t
 // blas4 != NULL (a BVH4 context, in.bvhNodes is the BVH2; collapse::check_args gave the BLAS): the BVH2 is kept and collapsed on the device
 int upload_scene(SceneBag& b, int accel, int extendVariant, const HostScene& in, SceneFacts facts, int64_t texPad, const std::vector<collapse::Blas>* blas4 = nullptr);
 // ---- scene_rebuild.hip
-int update_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas, RtUpdateStats* stats);
-int rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
+// The replacement geometry of an update or a rebuild (RtGeometry, include/rt355.h) and where each of its sources lies: on the host, or
+// in memory the copy's device reaches (the caller has applied the pointer rule).  `who` names the entry point in every message.
+struct Geometry {
+    RtGeometry g{};
+    bool primsOnDevice = false, positionsOnDevice = false, indicesOnDevice = false;
+    // what rt_update_scene, rt_rebuild_scene and rt_rebuild_ranges take: records in host memory (a window without records keeps `first`
+    // out of the checks, as those calls always have)
+    static Geometry host_records(const RtPrimitive* prims, int32_t first, int32_t count)
+    {
+        Geometry G;
+        G.g.first = count != 0 ? first : 0; G.g.count = count; G.g.prims = prims;
+        return G;
+    }
+};
+int update_scene(SceneBag& b, const char* who, const Geometry& geo, const RtBVHInstance* blas, int32_t nBlas, RtUpdateStats* stats);
+int rebuild_scene(SceneBag& b, const char* who, const Geometry& geo, const RtBVHInstance* blas, int32_t nBlas,
                   int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats);
 // rt_rebuild_ranges (include/rt355.h): plan[nRanges], one RT_REBUILD_SAH / LBVH / SBVH / KEEP / REFIT_RANGE per distinct BLAS in the order of b.live.ranges
-int rebuild_ranges(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
+int rebuild_ranges(SceneBag& b, const char* who, const Geometry& geo, const RtBVHInstance* blas, int32_t nBlas,
                    const int32_t* plan, int32_t nRanges, const RtBuildOptions* opts, RtRebuildStats* stats);
 // rt_scene_blas_blocks: the ranges and blocks of the bound trees (any output may be NULL; at most cap entries are written)
 int blas_blocks(const SceneBag& b, int32_t* n, int32_t* primFirst, int32_t* primCount, int32_t* nodes, int32_t* idxSlots, int32_t* compact, int32_t cap);

@@ -6,22 +6,26 @@
 #include <string>
 #include "scene_dev.h"
 #include "resize_common.h"
+#include "geometry_common.h"
 
 using namespace scenedev;
 
-// What an update and a rebuild refuse alike, before anything is written: `prims` replaces the primitives [first, first + count), `blas`
+// What an update and a rebuild refuse alike, before anything is written: `geo` replaces the primitives [first, first + count), `blas`
 // (may be NULL) the instances.  typeSuffix ends the message about a changed objType / matIdx.
-static int check_change(const char* who, const SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
-                        const char* typeSuffix)
+static int changed_type(const char* who, const SceneBag& b, size_t g, int32_t objType, int32_t matIdx, const char* typeSuffix)
 {
-    if (count < 0 || (count > 0 && !prims)) return fail(RT_E_INVALID, "%s: bad primitive count %d / NULL records", who, count);
-    if (count > 0 && (first < 0 || (int64_t)first + count > (int64_t)b.sc.nPrims))
-        return fail(RT_E_INVALID, "%s: primitive range [%d, %lld) outside the %d uploaded", who, first, (long long)first + count, b.sc.nPrims);
-    for (int32_t i = 0; i < count; i++) {
-        const size_t g = (size_t)first + (size_t)i;
-        if (prims[i].objType != b.primType[g] || prims[i].matIdx != b.primMat[g])
-            return fail(RT_E_INVALID, "%s: primitive %zu changes its objType / matIdx (%d / %d -> %d / %d)%s", who, g,
-                        b.primType[g], b.primMat[g], prims[i].objType, prims[i].matIdx, typeSuffix);
+    return fail(RT_E_INVALID, "%s: primitive %zu changes its objType / matIdx (%d / %d -> %d / %d)%s", who, g, b.primType[g], b.primMat[g], objType, matIdx, typeSuffix);
+}
+static int check_change(const char* who, const SceneBag& b, const Geometry& geo, const RtBVHInstance* blas, int32_t nBlas, const char* typeSuffix)
+{
+    // the geometry: what needs no device (geometry_common.h; a vertex form moves triangles only), then host records against the shadow
+    // of objType / matIdx (records on the device are checked there: stage_geometry)
+    std::string msg;
+    if (const int rc = geometry::check_args(&geo.g, b.sc.nPrims, b.primType.data(), msg)) return fail(rc, "%s: %s", who, msg.c_str());
+    const RtPrimitive* prims = geo.primsOnDevice ? nullptr : (const RtPrimitive*)geo.g.prims;
+    for (int32_t i = 0; prims && i < geo.g.count; i++) {
+        const size_t g = (size_t)geo.g.first + (size_t)i;
+        if (prims[i].objType != b.primType[g] || prims[i].matIdx != b.primMat[g]) return changed_type(who, b, g, prims[i].objType, prims[i].matIdx, typeSuffix);
     }
     if (blas) {
         if (nBlas != b.sc.nBlas) return fail(RT_E_INVALID, "%s: %d instances given, %d uploaded", who, nBlas, b.sc.nBlas);
@@ -42,15 +46,68 @@ static int tlas_status_error(const char* who, const int32_t status[2])
     return RT_OK;
 }
 
-int scenedev::update_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas, RtUpdateStats* stats)
+// The one place a call's replacement geometry reaches the device: fills the window of the staged primitives `dst` (the whole array; the
+// device-to-device copy of the bound primitives into it has been queued on the copy's stream) from geo, which has passed check_change.
+//   host records     the copy rt_update_scene has always queued, and nothing else
+//   device records   a copy where they lie, then k_window_check against the bound records
+//   vertices         k_tri_from_vertices over the staged records; host positions / indices go through scratch first
+// The two device forms wait for their status word: a refusal found there returns before anything is derived from the window (dst is
+// staging or the set that is not live: nothing bound has changed).
+static int stage_geometry(const char* who, SceneBag& b, const Geometry& geo, RtPrimitive* dst, const char* typeSuffix)
 {
-    const char* who = "rt_update_scene";
+    const RtGeometry& g = geo.g;
+    if (g.count == 0) return RT_OK;
+    hipStream_t s = b.stream;
+    const size_t count = (size_t)g.count;
+    RtPrimitive* const win = dst + g.first;
+    if (g.prims && !geo.primsOnDevice) {
+        HIPCHK(hipMemcpyAsync(win, g.prims, sizeof(RtPrimitive) * count, hipMemcpyHostToDevice, s));
+        return RT_OK;
+    }
+    if (const int rc = rebuild_fit(b, b.gStatus, 1, "the geometry status word")) return rc;
+    uint32_t bad = geometrydev::kNoBad;
+    if (g.prims) {
+        HIPCHK(hipMemcpyAsync(win, g.prims, sizeof(RtPrimitive) * count, hipMemcpyDefault, s));
+        HIPCHK(geometrydev::window_check(s, win, b.sc.prims + g.first, (uint32_t)g.count, b.gStatus.p));
+        HIPCHK(hipMemcpyAsync(&bad, b.gStatus.p, sizeof bad, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        if (bad == geometrydev::kNoBad) return RT_OK;
+        int32_t tm[2] = { 0, 0 };   // the one record's objType, matIdx
+        HIPCHK(hipMemcpy(tm, &win[bad].objType, sizeof tm, hipMemcpyDeviceToHost));
+        return changed_type(who, b, (size_t)g.first + bad, tm[0], tm[1], typeSuffix);
+    }
+    // the vertex form
+    const float* positions = (const float*)g.positions;
+    const uint32_t* indices = (const uint32_t*)g.indices;
+    if (indices && !geo.indicesOnDevice) {
+        if (const int rc = rebuild_fit(b, b.gIdx, 3 * count, "the geometry indices")) return rc;
+        HIPCHK(hipMemcpyAsync(b.gIdx.p, indices, sizeof(uint32_t) * 3 * count, hipMemcpyHostToDevice, s));
+        indices = b.gIdx.p;
+    }
+    if (!geo.positionsOnDevice && g.nVertices > 0) {
+        const size_t bytes = (size_t)(g.nVertices - 1) * (size_t)g.positionStride + 12;   // to the last vertex's z
+        if (const int rc = rebuild_fit(b, b.gPos, bytes, "the geometry positions")) return rc;
+        HIPCHK(hipMemcpyAsync(b.gPos.p, positions, bytes, hipMemcpyHostToDevice, s));
+        positions = (const float*)b.gPos.p;
+    }
+    HIPCHK(geometrydev::tri_from_vertices(s, win, (uint32_t)g.count, positions, g.positionStride, g.nVertices, indices, b.gStatus.p));
+    HIPCHK(hipMemcpyAsync(&bad, b.gStatus.p, sizeof bad, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (bad == geometrydev::kNoBad) return RT_OK;
+    uint32_t idx[3] = { 0, 0, 0 };   // (only a triangle with indices can be refused: check_change has counted the vertices otherwise)
+    if (indices) HIPCHK(hipMemcpy(idx, indices + 3 * (size_t)bad, sizeof idx, hipMemcpyDefault));
+    return fail(RT_E_INVALID, "%s: indices: %s", who, geometry::bad_index_message((int64_t)bad, idx, g.nVertices).c_str());
+}
+
+int scenedev::update_scene(SceneBag& b, const char* who, const Geometry& geo, const RtBVHInstance* blas, int32_t nBlas, RtUpdateStats* stats)
+{
+    const int32_t first = geo.g.first, count = geo.g.count;
     const SceneArrays& sc = b.sc;
     const LiveTrees& lt = b.live;
     const bool layout1 = b.facts.layout == 1;
     // ---- refusals: before anything is written
-    if (b.refitRefusal) return fail(RT_E_UNSUPPORTED, "rt_update_scene: %s", b.refitRefusal);
-    if (const int rc = check_change(who, b, prims, first, count, blas, nBlas, ": topology must not change")) return rc;
+    if (b.refitRefusal) return fail(RT_E_UNSUPPORTED, "%s: %s", who, b.refitRefusal);
+    if (const int rc = check_change(who, b, geo, blas, nBlas, ": topology must not change")) return rc;
     HIPCHK(hipSetDevice(b.device));
     // ---- staging buffers (the first update makes them; one after a resize that outgrew them replaces them)
     if (const int rc = scene_stream(b, b.ev)) return rc;   // (a rebuild may have made the stream already)
@@ -74,7 +131,7 @@ int scenedev::update_scene(SceneBag& b, const RtPrimitive* prims, int32_t first,
     // ---- stage: the new primitives, the refit tree and the rebuilt TLAS in scratch
     HIPCHK(hipEventRecord(b.ev[0], s));
     HIPCHK(hipMemcpyAsync(b.sPrims.p, sc.prims, sizeof(RtPrimitive) * (size_t)sc.nPrims, hipMemcpyDeviceToDevice, s));
-    if (count) HIPCHK(hipMemcpyAsync(b.sPrims.p + first, prims, sizeof(RtPrimitive) * (size_t)count, hipMemcpyHostToDevice, s));
+    if (const int rc = stage_geometry(who, b, geo, b.sPrims.p, ": topology must not change")) return rc;
     HIPCHK(hipMemcpyAsync(b.sNodes.p, sc.bvh2, sizeof(RtBVHNode2) * (size_t)lt.nNodes, hipMemcpyDeviceToDevice, s));
     if (blas) HIPCHK(hipMemcpyAsync(b.sInst.p, blas, sizeof(RtBVHInstance) * (size_t)sc.nBlas, hipMemcpyHostToDevice, s));
     else HIPCHK(hipMemcpyAsync(b.sInst.p, sc.blas, sizeof(RtBVHInstance) * (size_t)sc.nBlas, hipMemcpyDeviceToDevice, s));
@@ -217,7 +274,7 @@ static int check_plan_alpha(const char* who, const int32_t* plan, size_t n, cons
 
 // ---- the one body of rt_rebuild_scene, rt_rebuild_ranges and rt_resize_scene, phase by phase ----------------------------------------------
 // What a call asks for; it has passed the checks that need no device.  A rebuild (newPrims NULL) keeps the bound counts and ranges and takes
-// the replacement records prims / first / count and blas as rt_update_scene does; a resize builds the caller's shape - nPrims records at
+// the replacement geometry geo and blas as rt_update_scene does; a resize builds the caller's shape - nPrims records at
 // newPrims (host or device memory), nBlas instances, newRanges, newInstBlas - with blas (NULL: identity) carrying the transforms.  plan[k]
 // says what becomes of range k: built with RT_REBUILD_SAH / LBVH / SBVH, or (RT_REBUILD_KEEP, a rebuild of a compact bound tree only) its
 // bound tree moved to where the new scene numbers it, or (RT_REBUILD_REFIT_RANGE, likewise) moved and then given new boxes; an empty plan is
@@ -227,7 +284,7 @@ struct Request {
     const char* who;
     int32_t nPrims, nBlas;
     const void* newPrims;
-    const RtPrimitive* prims; int32_t first, count;
+    Geometry geo;
     const RtBVHInstance* blas;
     std::vector<int32_t> plan;
     const RtBuildOptions* opts;
@@ -375,7 +432,7 @@ int Pending::stage_rebuild()
     const SceneArrays& sc = b.sc;
     hipStream_t s = b.stream;
     HIPCHK(hipMemcpyAsync(t.prims.p, sc.prims, sizeof(RtPrimitive) * (size_t)sc.nPrims, hipMemcpyDeviceToDevice, s));
-    if (rq.count) HIPCHK(hipMemcpyAsync(t.prims.p + rq.first, rq.prims, sizeof(RtPrimitive) * (size_t)rq.count, hipMemcpyHostToDevice, s));
+    if (const int rc = stage_geometry(who, b, rq.geo, t.prims.p, "")) return rc;
     HIPCHK(hipMemcpyAsync(t.lightRecs.p, sc.lightRecs, sizeof(RtFloat4) * 8 * std::max<size_t>((size_t)sc.nLights, 1), hipMemcpyDeviceToDevice, s));   // (the emittance words stay)
     nLights = sc.nLights; lights = sc.lights;
     if (b.lightsInSet) {   // the light list lives in a set since a resize: it moves on with the arrays
@@ -604,7 +661,7 @@ int Pending::derive_records()
         return RT_OK;
     }
     HIPCHK(hipMemcpyAsync(t.shadeRecs.p, sc.shadeRecs, sizeof(RtFloat4) * (size_t)nPrims, hipMemcpyDeviceToDevice, s));
-    HIPCHK(refitdev::launch_records(s, t.prims.p, t.nodes.p, t.primIdx.p, 0u, lights, (uint32_t)nLights, (uint32_t)std::max(rq.first, 0), (uint32_t)rq.count,
+    HIPCHK(refitdev::launch_records(s, t.prims.p, t.nodes.p, t.primIdx.p, 0u, lights, (uint32_t)nLights, (uint32_t)std::max(rq.geo.g.first, 0), (uint32_t)rq.geo.g.count,
                                     nullptr, 0u, nullptr, nullptr, t.shadeRecs.p, t.lightRecs.p));
     if (!layout1) return RT_OK;
     for (size_t k = 0; k < nR; k++) {
@@ -710,25 +767,24 @@ static int rebuild_body(SceneBag& b, const Request& rq, RtRebuildStats* stats)
         stats->stage_ms = ms_between(pd.t0, pd.t1); stats->derive_ms = pd.deriveMs; stats->tlas_ms = pd.tlasMs;
         stats->build_ms = pd.refit ? pd.fitMs : ms_between(pd.t1, pd.t2);   // (a refit: GPU time of the staging copies and the refit)
         stats->commit_ms = ms_between(pd.t3, t4);
-        stats->prims = pd.resize ? rq.nPrims : rq.count; stats->blas_built = pd.nBuilt; stats->nodes = (int32_t)b.live.nNodes; stats->n_idx = (int32_t)b.live.nIdx;
+        stats->prims = pd.resize ? rq.nPrims : rq.geo.g.count; stats->blas_built = pd.nBuilt; stats->nodes = (int32_t)b.live.nNodes; stats->n_idx = (int32_t)b.live.nIdx;
         stats->max_depth = (int32_t)pd.maxDepth; stats->tlas_nodes = b.live.nTlas; stats->tlas_depth = pd.tlas[1]; stats->reconfigured = pd.reconfigured ? 1 : 0;
         stats->spatial_splits = (int32_t)std::min<uint64_t>(pd.spatialSplits, 0x7fffffffu); stats->prims_clipped = (int32_t)std::min<uint64_t>(pd.primsClipped, 0x7fffffffu);
     }
     return RT_OK;
 }
-int scenedev::rebuild_scene(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
+int scenedev::rebuild_scene(SceneBag& b, const char* who, const Geometry& geo, const RtBVHInstance* blas, int32_t nBlas,
                             int32_t builder, const RtBuildOptions* opts, RtRebuildStats* stats)
 {
-    const char* who = "rt_rebuild_scene";
     // ---- refusals that need no device work
-    if (b.refitRefusal) return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: %s", b.refitRefusal);
-    if (b.rebuildRefusal) return fail(RT_E_UNSUPPORTED, "rt_rebuild_scene: %s", b.rebuildRefusal);
+    if (b.refitRefusal) return fail(RT_E_UNSUPPORTED, "%s: %s", who, b.refitRefusal);
+    if (b.rebuildRefusal) return fail(RT_E_UNSUPPORTED, "%s: %s", who, b.rebuildRefusal);
     if (const int rc = check_builder(who, builder, opts, true)) return rc;
-    if (const int rc = check_change(who, b, prims, first, count, blas, nBlas, "")) return rc;
+    if (const int rc = check_change(who, b, geo, blas, nBlas, "")) return rc;
     lbvh::Params P{};
     const std::vector<int32_t> plan(builder == RT_REBUILD_REFIT ? 0 : b.live.ranges.size(), builder);   // every range: `builder`
     if (!plan.empty()) if (const int rc = check_ranges(who, plan.data(), opts, b.sc.nPrims, b.live.ranges, nullptr, P)) return rc;
-    return rebuild_body(b, Request{ who, b.sc.nPrims, b.sc.nBlas, nullptr, prims, first, count, blas, plan, opts, P }, stats);
+    return rebuild_body(b, Request{ who, b.sc.nPrims, b.sc.nBlas, nullptr, geo, blas, plan, opts, P }, stats);
 }
 // The checks of a plan that need no device: the plan itself (rebuild::check_plan), alpha and the builders' own argument checks
 static int plan_check_args(const char* who, int32_t nPrims, const std::vector<rebuild::BlasRange>& ranges, const rebuild::BlasBlock* blocks, const int32_t* plan,
@@ -760,17 +816,16 @@ extern "C" int rt_rebuild_ranges_check(int32_t nPrims, const int32_t* rangeFirst
     lbvh::Params P{};
     return plan_check_args(who, nPrims, ranges, blocks.data(), plan, nRanges, first, count, opts, P);
 }
-int scenedev::rebuild_ranges(SceneBag& b, const RtPrimitive* prims, int32_t first, int32_t count, const RtBVHInstance* blas, int32_t nBlas,
+int scenedev::rebuild_ranges(SceneBag& b, const char* who, const Geometry& geo, const RtBVHInstance* blas, int32_t nBlas,
                              const int32_t* plan, int32_t nRanges, const RtBuildOptions* opts, RtRebuildStats* stats)
 {
-    const char* who = "rt_rebuild_ranges";
     // ---- refusals that need no device work
     if (b.refitRefusal) return fail(RT_E_UNSUPPORTED, "%s: %s", who, b.refitRefusal);
     if (b.rebuildRefusal) return fail(RT_E_UNSUPPORTED, "%s: %s", who, b.rebuildRefusal);
-    if (const int rc = check_change(who, b, prims, first, count, blas, nBlas, "")) return rc;
+    if (const int rc = check_change(who, b, geo, blas, nBlas, "")) return rc;
     lbvh::Params P{};
-    if (const int rc = plan_check_args(who, b.sc.nPrims, b.live.ranges, b.live.block.data(), plan, nRanges, first, count, opts, P)) return rc;
-    return rebuild_body(b, Request{ who, b.sc.nPrims, b.sc.nBlas, nullptr, prims, first, count, blas, std::vector<int32_t>(plan, plan + nRanges), opts, P, true }, stats);
+    if (const int rc = plan_check_args(who, b.sc.nPrims, b.live.ranges, b.live.block.data(), plan, nRanges, geo.g.first, geo.g.count, opts, P)) return rc;
+    return rebuild_body(b, Request{ who, b.sc.nPrims, b.sc.nBlas, nullptr, geo, blas, std::vector<int32_t>(plan, plan + nRanges), opts, P, true }, stats);
 }
 
 // The ranges of a caller's shape as the builders take them (root: assigned by the build)
@@ -820,6 +875,6 @@ int scenedev::resize_scene(SceneBag& b, const void* prims, int32_t nPrims, const
             return fail(RT_E_UNSUPPORTED, "rt_resize_scene: the bound scene's BLAS ranges leave a gap: primitives [%u, %d) belong to no BLAS", next, b.sc.nPrims);
     }
     const std::vector<int32_t> plan(ranges.size(), builder);   // (never RT_REBUILD_KEEP)
-    return rebuild_body(b, Request{ who, nPrims, shape->nBlas, prims, nullptr, 0, 0, shape->blas, plan, opts, P, false, std::move(ranges),
+    return rebuild_body(b, Request{ who, nPrims, shape->nBlas, prims, Geometry{}, shape->blas, plan, opts, P, false, std::move(ranges),
                                     std::vector<int32_t>(shape->instRange, shape->instRange + shape->nBlas) }, stats);
 }

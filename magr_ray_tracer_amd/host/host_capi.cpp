@@ -7,6 +7,7 @@
 #include "../../include/rt355_host.h"
 #include "../csrc/collapse_common.h"
 #include "../csrc/resize_common.h"
+#include "../csrc/geometry_common.h"
 #include "rt_host.h"
 
 using namespace rt355;
@@ -233,6 +234,30 @@ int rth_set_primitives(RthScene* s, int first, int count, const RtPrimitive* pri
     const int rc = SetPrimitivesHost(s->scene.primitives, first, count, prims, err);
     if (rc != RT_OK) g_herr = err;
     return rc;
+}
+int rth_set_vertices(RthScene* s, int first, int count, const float* positions, int64_t strideBytes, int64_t nVertices, const uint32_t* indices)
+{
+    if (!s) { g_herr = "rth_set_vertices: null scene"; return RT_E_INVALID; }
+    std::vector<RtPrimitive>& prims = s->scene.primitives;
+    try {
+        RtGeometry g{};
+        g.first = first; g.count = count; g.positions = positions; g.positionStride = strideBytes; g.nVertices = nVertices; g.indices = indices;
+        std::vector<int32_t> types(prims.size());
+        for (size_t i = 0; i < prims.size(); i++) types[i] = prims[i].objType;
+        std::string err;
+        if (const int rc = geometry::check_args(&g, (int64_t)prims.size(), types.data(), err)) { g_herr = "rth_set_vertices: " + err; return rc; }
+        // every index before any record: a refusal changes nothing
+        for (int64_t i = 0; indices && i < count; i++) {
+            const uint32_t* t = indices + 3 * i;
+            if (t[0] >= nVertices || t[1] >= nVertices || t[2] >= nVertices) { g_herr = "rth_set_vertices: indices: " + geometry::bad_index_message(i, t, nVertices); return RT_E_INVALID; }
+        }
+        for (int64_t i = 0; i < count; i++) {
+            const uint64_t j0 = indices ? indices[3 * i] : 3 * (uint64_t)i, j1 = indices ? indices[3 * i + 1] : j0 + 1, j2 = indices ? indices[3 * i + 2] : j0 + 2;
+            geometry::set_triangle(prims[(size_t)first + (size_t)i], geometry::vertex(positions, strideBytes, j0), geometry::vertex(positions, strideBytes, j1),
+                                   geometry::vertex(positions, strideBytes, j2));
+        }
+        return RT_OK;
+    } catch (const std::exception& e) { g_herr = e.what(); return RT_E_NOMEM; }
 }
 int rth_refit(RthScene* s)
 {

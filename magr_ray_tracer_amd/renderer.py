@@ -120,6 +120,130 @@ def _flat_pointer(a, dtype, what):
     return (C.c_void_p(t.data_ptr()) if nbytes else None), nbytes // dtype.itemsize, t
 
 
+def _is_tensor(a):
+    return not isinstance(a, np.ndarray) and hasattr(a, "data_ptr")
+
+
+def _wait_for_torch(t):
+    if getattr(t, "is_cuda", False):
+        import torch
+        torch.cuda.current_stream(t.device).synchronize()   # the library's copies and kernels run on a stream of its own
+
+
+def _position_rows(a):
+    """(address, stride in bytes, vertices, what keeps it alive) of positions: (n, 3) or (count, 3, 3) float32, a numpy array or a torch
+    tensor, used where it lies.  Rows that are 4-byte-aligned slices of a wider row (x[:, :3] of an (n, 4) array) go through as they
+    are, with the wider row as the stride; anything else that is not contiguous is copied."""
+    if _is_tensor(a):
+        if str(a.dtype) != "torch.float32" or a.dim() not in (2, 3) or tuple(a.shape[1:]) not in ((3,), (3, 3)):
+            raise ValueError(f"positions: a float32 tensor of shape (n, 3) or (count, 3, 3) expected, not {a.dtype} {tuple(a.shape)}")
+        if a.dim() == 2 and a.shape[0] > 0 and a.stride(1) == 1 and a.stride(0) >= 3:
+            t, stride = a, a.stride(0) * 4
+        else:
+            t, stride = a.contiguous().view(-1, 3), 12
+        return t.data_ptr(), stride, t.shape[0], t
+    h = np.asarray(a, dtype=np.float32)
+    if h.ndim not in (2, 3) or h.shape[1:] not in ((3,), (3, 3)):
+        raise ValueError(f"positions: float32 of shape (n, 3) or (count, 3, 3) expected, not {h.shape}")
+    if not (h.ndim == 2 and len(h) and h.strides[1] == 4 and h.strides[0] >= 12 and h.strides[0] % 4 == 0):
+        h = np.ascontiguousarray(h).reshape(-1, 3)
+    return h.ctypes.data, (h.strides[0] if len(h) else 12), len(h), h
+
+
+def _geometry(first, prims, positions, indices):
+    """An RtGeometry (a _lib.Geometry record) for the window that starts at `first`, and what keeps its memory alive.  prims: Primitive
+    records; positions (+ indices: 3 per triangle, uint32 / int32): the vertex form; numpy arrays (host memory) or torch tensors, which
+    are used where they lie after torch's current stream has been waited for."""
+    g = np.zeros((), dtype=_lib.Geometry)
+    g["first"] = int(first)
+    keep = []
+    if prims is not None and positions is not None:
+        raise ValueError("both prims and positions are given: exactly one source of geometry is taken")
+    if indices is not None and positions is None:
+        raise ValueError("indices without positions")
+    if prims is not None:
+        if _is_tensor(prims):
+            p = prims if prims.is_contiguous() else prims.contiguous()
+            nbytes = p.numel() * p.element_size()
+            if nbytes % _lib.Primitive.itemsize:
+                raise ValueError(f"a primitive tensor of {nbytes} bytes is no whole number of {_lib.Primitive.itemsize}-byte records")
+            g["prims"], g["count"] = (p.data_ptr() if nbytes else 0), nbytes // _lib.Primitive.itemsize
+        else:
+            p = np.ascontiguousarray(prims, dtype=_lib.Primitive)
+            g["prims"], g["count"] = (p.ctypes.data if len(p) else 0), len(p)
+        keep.append(p)
+    elif positions is not None:
+        addr, stride, n, k = _position_rows(positions)
+        keep.append(k)
+        corners = n
+        if indices is not None:
+            if _is_tensor(indices):
+                i = indices if indices.is_contiguous() else indices.contiguous()
+                if i.is_floating_point() or i.element_size() != 4:
+                    raise ValueError(f"indices: a 32-bit integer tensor expected, not {i.dtype}")
+                g["indices"], corners = i.data_ptr(), i.numel()
+            else:
+                i = np.ascontiguousarray(indices, dtype=np.uint32).ravel()
+                g["indices"], corners = i.ctypes.data, len(i)
+            keep.append(i)
+        if corners % 3:
+            raise ValueError(f"{corners} corners are no whole number of triangles")
+        g["count"] = corners // 3
+        if g["count"]:
+            g["positions"], g["positionStride"], g["nVertices"] = addr, stride, n
+        else:
+            g["indices"] = 0
+    for k in keep:
+        if _is_tensor(k):
+            _wait_for_torch(k)
+    return g, keep
+
+
+def _instances_arg(instances):
+    b = None if instances is None else np.ascontiguousarray(instances, dtype=_lib.BVHInstance)
+    return (_lib.ptr(b) if b is not None else None, 0 if b is None else len(b)), b
+
+
+def _update_geometry_args(first, prims, positions, indices, instances):
+    g, keep = _geometry(first, prims, positions, indices)
+    inst, b = _instances_arg(instances)
+    st = np.zeros((), dtype=_lib.UpdateStats)
+    return (_lib.ptr(g), *inst, _lib.ptr(st)), (g, keep, b), st
+
+
+def _rebuild_geometry_args(first, prims, positions, indices, instances, builder, lbvh_options, alpha):
+    from .scene import build_options, rebuild_builder
+    which = rebuild_builder(builder, lbvh_options, alpha)
+    g, keep = _geometry(first, prims, positions, indices)
+    inst, b = _instances_arg(instances)
+    opts = build_options(alpha=alpha, **lbvh_options)
+    st = np.zeros((), dtype=_lib.RebuildStats)
+    return (_lib.ptr(g), *inst, which, _lib.ptr(opts), _lib.ptr(st)), (g, keep, b, opts), st
+
+
+def _geometry_ranges_args(plan, first, prims, positions, indices, instances, lbvh_options, alpha):
+    from .scene import build_options, plan_words
+    words = plan_words(plan, lbvh_options, alpha)
+    g, keep = _geometry(first, prims, positions, indices)
+    inst, b = _instances_arg(instances)
+    opts = build_options(alpha=alpha, **lbvh_options)
+    st = np.zeros((), dtype=_lib.RebuildStats)
+    return (_lib.ptr(g), *inst, _lib.ptr(words) if len(words) else None, len(words), _lib.ptr(opts), _lib.ptr(st)), (g, keep, b, opts, words), st
+
+
+def geometry_check(n_prims, first=0, prims=None, positions=None, indices=None, obj_types=None):
+    """The checks of a replacement geometry that need no GPU (rt_geometry_check) against a scene of n_prims primitives whose objType
+    values are obj_types (None: all triangles): raises RtError (.code) with the message the device calls would give."""
+    lib = _lib.device_lib()
+    g, keep = _geometry(first, prims, positions, indices)
+    t = None if obj_types is None else np.ascontiguousarray(obj_types, dtype=np.int32)
+    rc = lib.rt_geometry_check(_lib.ptr(g), int(n_prims), _lib.ptr(t))
+    if rc != 0:
+        e = RtError(lib.rt_last_error().decode())
+        e.code = rc
+        raise e
+
+
 def _materials_args(mats, texels, tex_first, n_texels, prim_mat, prim_first):
     """The arguments of rt_update_materials: (RtMaterialUpdate*, RtMaterialStats*), what keeps them alive, the stats record."""
     u = np.zeros((), dtype=_lib.MaterialUpdate)
@@ -263,6 +387,31 @@ class Device:
         the scene as it was."""
         args, keep, st = _ranges_args(plan, prims, first, instances, lbvh_options, alpha)
         self._chk_code(self._lib.rt_rebuild_ranges(self._h, *args))
+        return _rebuild_dict(st)
+
+    def update_geometry(self, first=0, prims=None, positions=None, indices=None, instances=None):
+        """update_scene fed from wherever the geometry lies (rt_update_geometry).  The window starts at primitive `first`.  Either
+        `prims` (Primitive records, as for update_scene) or `positions` gives it: positions is (n, 3) float32, and triangle i of the
+        window takes vertices indices[3i .. 3i + 2] (indices: 3 integers per triangle), or without indices vertices 3i .. 3i + 2
+        (positions may then be (count, 3, 3)).  From positions the GPU writes v0, v1, v2, N, centroid and area of each triangle by
+        Scene.AddTriangle's rule (Scene.SetVertices is the host mirror); the window must hold triangles only.  Each of the three may be
+        a numpy array or a torch tensor; a tensor on the context's GPU is used where it lies (torch's current stream is waited for
+        first), and x[:, :3] of an (n, 4) float32 tensor goes through without a copy.  Returns update_scene's stats; a refusal raises
+        RtError (.code) and leaves the scene as it was."""
+        args, keep, st = _update_geometry_args(first, prims, positions, indices, instances)
+        self._chk_code(self._lib.rt_update_geometry(self._h, *args))
+        return _update_dict(st)
+
+    def rebuild_geometry(self, first=0, prims=None, positions=None, indices=None, instances=None, builder="sah", alpha=None, **lbvh_options):
+        """rebuild_scene fed as update_geometry is (rt_rebuild_geometry); builder, alpha and lbvh_options as for rebuild_scene."""
+        args, keep, st = _rebuild_geometry_args(first, prims, positions, indices, instances, builder, lbvh_options, alpha)
+        self._chk_code(self._lib.rt_rebuild_geometry(self._h, *args))
+        return _rebuild_dict(st)
+
+    def rebuild_geometry_ranges(self, plan, first=0, prims=None, positions=None, indices=None, instances=None, alpha=None, **lbvh_options):
+        """rebuild_ranges fed as update_geometry is (rt_rebuild_geometry_ranges); plan, alpha and lbvh_options as for rebuild_ranges."""
+        args, keep, st = _geometry_ranges_args(plan, first, prims, positions, indices, instances, lbvh_options, alpha)
+        self._chk_code(self._lib.rt_rebuild_geometry_ranges(self._h, *args))
         return _rebuild_dict(st)
 
     def ranges_info(self):
@@ -702,6 +851,30 @@ class Group:
             e.code = rc
             raise e
         return _materials_dict(st)
+
+    def _chk_code(self, rc):
+        if rc != 0:
+            e = RtError(self._lib.rt_last_error().decode())
+            e.code = rc
+            raise e
+
+    def update_geometry(self, first=0, prims=None, positions=None, indices=None, instances=None):
+        """Device.update_geometry for the group's scene copy (rt_group_update_geometry): every lane sees the update."""
+        args, keep, st = _update_geometry_args(first, prims, positions, indices, instances)
+        self._chk_code(self._lib.rt_group_update_geometry(self._h, *args))
+        return _update_dict(st)
+
+    def rebuild_geometry(self, first=0, prims=None, positions=None, indices=None, instances=None, builder="sah", alpha=None, **lbvh_options):
+        """Device.rebuild_geometry for the group's scene copy (rt_group_rebuild_geometry): every lane sees the rebuilt scene."""
+        args, keep, st = _rebuild_geometry_args(first, prims, positions, indices, instances, builder, lbvh_options, alpha)
+        self._chk_code(self._lib.rt_group_rebuild_geometry(self._h, *args))
+        return _rebuild_dict(st)
+
+    def rebuild_geometry_ranges(self, plan, first=0, prims=None, positions=None, indices=None, instances=None, alpha=None, **lbvh_options):
+        """Device.rebuild_geometry_ranges for the group's scene copy (rt_group_rebuild_geometry_ranges): every lane sees the rebuilt scene."""
+        args, keep, st = _geometry_ranges_args(plan, first, prims, positions, indices, instances, lbvh_options, alpha)
+        self._chk_code(self._lib.rt_group_rebuild_geometry_ranges(self._h, *args))
+        return _rebuild_dict(st)
 
     def seed(self, first_stream=0):
         self._chk(self._lib.rt_group_seed(self._h, int(first_stream)))

@@ -190,6 +190,24 @@ class Scene:
         p = np.ascontiguousarray(prims, dtype=_lib.Primitive)
         self._chk(self._lib.rth_set_primitives(self._h, int(first), len(p), _lib.ptr(p) if len(p) else None))
 
+    def SetVertices(self, first, positions, indices=None):
+        """Move the triangles from primitive `first` on to new vertices (rth_set_vertices), as Device.update_geometry(positions=...)
+        does on the GPU by the same rule (csrc/geometry_common.h, Scene::AddTriangle's): positions is (n, 3) float32 - rows of a wider
+        row, such as x[:, :3], are taken as they lie - and triangle i takes vertices indices[3i .. 3i + 2], or 3i .. 3i + 2 without
+        indices (positions may then be (count, 3, 3)).  v0, v1, v2, N, centroid and area are written anew, everything else stays.  The
+        trees are not touched: Refit() next.  Raises BuildError (.code RT_E_INVALID) and changes nothing when refused."""
+        p = np.asarray(positions, dtype=np.float32)
+        if p.ndim not in (2, 3) or p.shape[1:] not in ((3,), (3, 3)):
+            raise ValueError(f"positions: float32 of shape (n, 3) or (count, 3, 3) expected, not {p.shape}")
+        if not (p.ndim == 2 and len(p) and p.strides[1] == 4 and p.strides[0] >= 12 and p.strides[0] % 4 == 0):
+            p = np.ascontiguousarray(p).reshape(-1, 3)
+        i = None if indices is None else np.ascontiguousarray(indices, dtype=np.uint32).ravel()
+        corners = len(p) if i is None else len(i)
+        if corners % 3:
+            raise ValueError(f"{corners} corners are no whole number of triangles")
+        self._chk_build(self._lib.rth_set_vertices(self._h, int(first), corners // 3, C.c_void_p(p.ctypes.data), p.strides[0] if len(p) else 12, len(p),
+                                                   _lib.ptr(i) if i is not None and len(i) else None))
+
     def _chk_build(self, rc):
         if rc != 0:
             raise BuildError(rc, self._lib.rth_last_error().decode())
