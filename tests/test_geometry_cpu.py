@@ -1,6 +1,8 @@
 """Replacement geometry from vertex positions on the host (Scene.SetVertices / rth_set_vertices, rt_geometry_check): the one rule of
 csrc/geometry_common.h held to Scene::AddTriangle - a scene built from moved vertices through AddTriangle gives the records that
-SetVertices must produce from those vertices, byte for byte - and every refusal, after which nothing has changed."""
+SetVertices must produce from those vertices, byte for byte - and every refusal, after which nothing has changed; then the same
+mirror at the floats' edges (geometry_check's hard classes: NaN where AddTriangle has NaN, every other word bit for bit), the
+conditions that keep those classes hard, the flip that a degenerate state loses, and AddTriangle's records against float64."""
 import ctypes as C
 
 import numpy as np
@@ -152,3 +154,193 @@ def test_a_zero_area_triangle_has_nan_where_add_triangle_has():
     GC.same_records(a, b, "the words beside N")
     GC.same_records(got[:k], p0[:k], "the records before")
     GC.same_records(got[k + 1:], p0[k + 1:], "the records behind")
+
+
+# ---- the rule at the floats' edges: geometry_check's hard classes ---------------------------------------------------------------------
+_E = {}
+
+
+def _expected(name, flip):
+    """AddTriangle's records of a class (flip: one flipNormal for all), made once."""
+    if (name, flip) not in _E:
+        _E[name, flip] = GC.records(GC.added(GC.hard(name), flip))
+        _E[name, flip].setflags(write=False)
+    return _E[name, flip]
+
+
+@pytest.mark.parametrize("flip", [False, True])
+@pytest.mark.parametrize("name", list(GC.CLASSES))
+def test_set_vertices_is_add_triangle_on_hard_inputs(name, flip):
+    v, want = GC.hard(name), _expected(name, flip)
+    s = GC.added(GC.benign(len(v)), flip)
+    bound = GC.records(s)
+    assert np.array_equal(GC.is_flipped(bound), np.full(len(v), flip))
+    s.SetVertices(0, v)
+    GC.same_records_nan(GC.records(s), want, f"{name}, packed")
+    s.SetPrimitives(0, bound)
+    s.SetVertices(0, *GC.indexed(v))                                              # indexed by bit pattern: NaNs and +-0 survive
+    GC.same_records_nan(GC.records(s), want, f"{name}, indexed")
+    assert np.array_equal(GC.verts(want).view(np.uint32), v.view(np.uint32))      # AddTriangle copies the vertices bit for bit
+    assert np.array_equal(np.signbit(want["N"][:, 3]), np.full(len(v), flip)) and np.all(want["N"][:, 3] == 0)   # N.w: -0 after a flip
+    print(name, "flipped" if flip else "unflipped", GC.census(want))
+
+
+def test_the_comparison_takes_any_nan_for_a_nan_and_nothing_else():
+    want = _expected("non_finite", True).copy()
+    got = want.copy()
+    w = got.view(np.uint32).reshape(-1, 32)
+    nan = np.isnan(w[:, GC.COMPUTED].view(np.float32))
+    assert nan.any(axis=0).all()                                                  # every computed word is NaN in some record
+    w[:, GC.COMPUTED] = np.where(nan, w[:, GC.COMPUTED] ^ 0x80000001, w[:, GC.COMPUTED])      # other sign, other payload
+    GC.same_records_nan(got, want, "NaNs of another sign and payload")
+    with pytest.raises(AssertionError):
+        GC.same_records(got, want, "bytes")
+    for word in (0, 3, 15, 19, 20, 28, 29, 31):                                   # a copied word, w words, uv, objType, matIdx, padding
+        bad = want.copy()
+        bad.view(np.uint32).reshape(-1, 32)[5, word] ^= 1
+        with pytest.raises(AssertionError, match=f"first 5 in words \\[{word}\\]"):
+            GC.same_records_nan(bad, want, "one bit")
+    k = len(want) - 1                                                             # v0 of the last record is NaN: its payload counts
+    bad = want.copy()
+    bad.view(np.uint32).reshape(-1, 32)[k, 0] = 0x7FC00000
+    assert np.isnan(bad["v0"][k, 0]) and np.isnan(want["v0"][k, 0])
+    with pytest.raises(AssertionError):
+        GC.same_records_nan(bad, want, "a copied NaN")
+    fin = np.nonzero(np.isfinite(want["N"][:, :3]).all(axis=1))[0]
+    assert len(fin) == 0                                                          # (non_finite has no finite N; take one from the needles)
+    want = _expected("needles", False)
+    bad = want.copy()
+    i = int(np.nonzero(np.isfinite(want["N"][:, 0]))[0][0])
+    bad["N"][i, 0] = np.nan
+    with pytest.raises(AssertionError):
+        GC.same_records_nan(bad, want, "NaN for a number")
+
+
+def test_the_classes_hit_what_they_are_there_for():
+    """Conditions on AddTriangle's records, not on SetVertices': they keep the tests above from becoming vacuous."""
+    def N(p):
+        return p["N"][:, :3]
+    p = _expected("points", False)
+    assert np.isnan(N(p)).all() and np.all(p["area"] == 0)
+    p = _expected("collinear_exact", False)
+    assert np.isnan(N(p)).all() and (p["area"] == 0).sum() >= len(p) // 2      # (Heron's lengths are rounded: some areas are NaN or tiny)
+    p = _expected("collinear_rounded", False)
+    finite = np.isfinite(N(p)).all(axis=1)
+    assert (finite & (p["area"] == 0)).sum() >= len(p) // 8 and np.isnan(N(p)).all(axis=1).sum() >= len(p) // 8
+    p = _expected("needles", False)
+    n = len(p)
+    nz = np.isfinite(N(p)).all(axis=1) & (N(p) != 0).any(axis=1)
+    share = dict(nan_area=np.isnan(p["area"]).sum() / n, nan_N=np.isnan(N(p)).any(axis=1).sum() / n, zero_area=(p["area"] == 0).sum() / n,
+                 finite_N_zero_area=(nz & (p["area"] == 0)).sum() / n)
+    print("needles", share)
+    assert share["nan_area"] >= 0.05 and share["nan_N"] >= 0.05 and share["zero_area"] >= 0.5 and share["finite_N_zero_area"] >= 0.05, share
+    p = _expected("offset", False)
+    far, high = p[:len(p) // 2], p[len(p) // 2:]
+    assert np.all(np.abs(GC.verts(far)).max(axis=(1, 2)) > 1e4) and 0 < (far["area"] == 0).sum() < len(far) // 2
+    assert np.isinf(high["centroid"][:, 0]).all() and np.isfinite(N(high)).all() and np.all(np.isfinite(high["area"]) & (high["area"] > 0))
+    p = _expected("non_finite", False)
+    assert len(p) == 29 and np.isnan(N(p)).any(axis=1).all() and np.isnan(p["area"]).all()       # (so none of them reads as flipped)
+    assert np.isinf(p["centroid"][:, :3]).any() and np.isnan(p["centroid"][:, :3]).any()
+    assert {int(w) for w in p[27:].view(np.uint32).reshape(-1, 32)[:, :12].ravel()} >= {GC.NAN_A, GC.NAN_B}
+    for flip in (False, True):
+        p = _expected("signed_zero", flip)
+        assert np.isfinite(N(p)).all() and np.all(np.abs(p["area"] - 0.5) < 1e-6)
+        for rows in (N(p), p["centroid"][:, :3]):
+            zero = rows == 0
+            assert (zero & np.signbit(rows)).any() and (flip or (zero & ~np.signbit(rows)).any())
+
+
+def _ladder_rows(p):
+    return p.reshape(len(GC.LADDER_K), GC.LADDER_M)
+
+
+def test_the_ladder_passes_every_regime_and_is_scale_free_between():
+    p = _ladder_rows(_expected("ladder", False))
+    ks = np.array(GC.LADDER_K)
+    v, N, area, cen = GC.verts(p.ravel()).reshape(len(ks), GC.LADDER_M, 9), p["N"][:, :, :3], p["area"], p["centroid"][:, :, :3]
+    tiny = np.float32(2.0 ** -126)
+    unit = np.isfinite(N).all(axis=2) & (np.abs(np.linalg.norm(N.astype(np.float64), axis=2) - 1) < 1e-6)
+    regimes = {
+        "subnormal vertices and centroid": ((np.abs(v) < tiny) & (v != 0)).any(axis=2) & ((np.abs(cen) < tiny) & (cen != 0)).any(axis=2),
+        "the cross product underflows: N NaN, area 0": np.isnan(N).all(axis=2) & (area == 0) & (v != 0).any(axis=2),
+        "dot(cross, cross) underflows: 1 / sqrt is inf": np.isinf(N).any(axis=2) & (area == 0),
+        "dot(cross, cross) is subnormal: N finite, not unit": np.isfinite(N).all(axis=2) & (N != 0).any(axis=2) & ~unit,
+        "normal": unit & np.isfinite(area) & (area > 0),
+        "dot(cross, cross) overflows: N 0, area inf": (N == 0).all(axis=2) & np.isinf(area),
+        "the cross product overflows: N NaN": np.isnan(N).any(axis=2) & np.isfinite(v).all(axis=2) & (ks > 0)[:, None],
+        "a length overflows: area NaN": np.isnan(area) & np.isfinite(v).all(axis=2),
+    }
+    for what, hit in regimes.items():
+        k = ks[hit.any(axis=1)]
+        assert len(k), what
+        print(f"{what}: k = {k.min()} .. {k.max()} (all {GC.LADDER_M} triangles: {[int(x) for x in ks[hit.all(axis=1)][[0, -1]]] if hit.all(axis=1).any() else 'never'})")
+    k_unit = ks[(unit & np.isfinite(area) & (area > 0)).all(axis=1)]
+    assert np.array_equal(k_unit, np.arange(k_unit.min(), k_unit.max() + 1))
+    print(f"a finite unit N and a finite positive area for every triangle of the ladder: k = {k_unit.min()} .. {k_unit.max()}")
+    assert (k_unit.min(), k_unit.max()) == GC.LADDER_UNIT
+    # between: nothing depends on the scale
+    base = GC.ladder_base().astype(np.float64)
+    c2 = (np.cross(base[:, 1] - base[:, 0], base[:, 2] - base[:, 0]) ** 2).sum(axis=1)        # at k = 0; times 2^4k at scale k
+    zero = int(np.nonzero(ks == 0)[0][0])
+    checked = 0
+    for i, k in enumerate(ks):
+        scale_free = (c2 * 2.0 ** (4 * int(k)) >= 2.0 ** -100) & (c2 * 2.0 ** (4 * int(k)) <= 2.0 ** 100)
+        if not scale_free.any():
+            continue
+        checked += 1
+        assert np.array_equal(N[i][scale_free].view(np.uint32), N[zero][scale_free].view(np.uint32)), k
+        assert np.array_equal(np.ldexp(cen[i][scale_free], -int(k)).view(np.uint32), cen[zero][scale_free].view(np.uint32)), k
+    assert checked >= 49                                                          # k = -24 .. 24 at the least
+
+
+def test_records_of_well_conditioned_triangles_against_float64():
+    """The constants of geometry_check.BOUNDS are twice what this test measures on AddTriangle's records; SetVertices' are held to them."""
+    v = GC.well_conditioned()
+    assert GC.min_angle(v).min() >= GC.MIN_ANGLE
+    for flip in (False, True):
+        ref = GC.errors64(GC.records(GC.added(v, flip)))
+        print("AddTriangle", flip, ref)
+        for k, bound in GC.BOUNDS.items():
+            assert bound / 4 <= ref[k] <= bound / 2 * 1.001, (k, ref[k], bound)                 # the comment beside BOUNDS is still true
+        s = GC.added(GC.benign(len(v)), flip)
+        s.SetVertices(0, v)
+        got = GC.errors64(GC.records(s))
+        for k, bound in GC.BOUNDS.items():
+            assert got[k] <= bound, (k, got[k], bound)
+
+
+def _flip_sequence(through):
+    """[(vertices, AddTriangle's flipNormal per triangle)] of: bound with every flip_pattern triangle flipped -> `through` -> back.  The
+    documented rule: the flip is read from the bound record and is false once its N is NaN or zero, as it is after `through`."""
+    n = 64
+    first, flips = GC.benign(n), GC.flip_pattern(n)
+    mid = GC.tiled(GC.hard(through), n)
+    want_mid = GC.records(GC.added(mid, flips))
+    assert (np.isnan(want_mid["N"][:, :3]).any(axis=1) | (want_mid["N"][:, :3] == 0).all(axis=1)).all() and flips.any()
+    return [(first, flips), (mid, flips), (first, np.zeros(n, bool))]
+
+
+@pytest.mark.parametrize("through", ["points", "non_finite"])
+def test_a_flip_is_lost_through_a_degenerate_state(through):
+    steps = _flip_sequence(through)
+    s = GC.added(*steps[0])
+    for i, (v, flips) in enumerate(steps):
+        s.SetVertices(0, v)
+        GC.same_records_nan(GC.records(s), GC.records(GC.added(v, flips)), f"through {through}, step {i}")
+    assert not GC.is_flipped(GC.records(s)).any()
+
+
+def test_a_bound_triangle_whose_cross_product_underflows_counts_as_not_flipped():
+    """Edges around 1e-25: the bound cross product is (0, 0, 0) in float32, so the dot product with any N is no negative number."""
+    tiny = (GC.benign(16) * np.float32(1e-25)).astype(np.float32)
+    s = GC.added(tiny, True)
+    bound = GC.records(s)
+    assert np.isnan(bound["N"][:, :3]).all()
+    n64 = GC.truth64(tiny)[0]
+    assert np.isfinite(n64).all()
+    bound["N"][:, :3] = -n64                                                      # a flipped unit normal, as a caller might have written it
+    s.SetPrimitives(0, bound)
+    assert GC.is_flipped(GC.records(s)).all()                                     # float64 calls it flipped; the rule's float32 cannot
+    v = GC.benign(16, seed=30)
+    s.SetVertices(0, v)
+    GC.same_records_nan(GC.records(s), GC.records(GC.added(v, False)), "from a bound triangle without a cross product")
