@@ -155,6 +155,14 @@ int rt_shade_footprint(RtCtx* ctx, int32_t* ldsBytes, int32_t* traversalBeside);
  * this context's k_shade launches read the uploaded scene's light records and materials from LDS - all of both fit the rows - and 0 if
  * they read them from global memory (the scene needs more rows, or RT355_SHADE_TABLES=0).  The results are the same bits either way. */
 int rt_shade_tables(RtCtx* ctx, int32_t* capacityRows, int32_t* staged);
+/* The fused primary path of rt_render.  *fused: 1 if this context's frames launch no k_generate - bounce 0's extend launch computes each
+ * pixel's primary ray from the camera and the pixel's seed instead of loading it, bounce 0's shade launch computes it again, and the
+ * primary queue (origin, direction, intensity, meta) is never stored; 0 if they generate and store it first.  Fused are single-BLAS
+ * scenes under persistent wavefronts, BVH2 (not with extend_variant 3 or 5) and BVH4; multi-BLAS scenes and the nested kernels are not;
+ * RT355_FUSE_PRIMARY=0 keeps every context on k_generate.  The results are the same bits either way: accumulators, seeds, queue lengths,
+ * counters.  The stage-level calls never fuse: rt_stage_generate stores the queue that rt_stage_extend(0) and rt_stage_shade(0) read, and
+ * after a fused frame the stored queue of bounce 0 is NOT that frame's - generate before running bounce 0's stages by hand. */
+int rt_primary_fused(RtCtx* ctx, int32_t* fused);
 
 /* new Buffer(...) x11 + new Kernel(...) x6 (renderer.cpp:145-157, :218-223). */
 int rt_create(const RtConfig* cfg, RtCtx** out);

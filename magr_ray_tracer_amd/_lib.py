@@ -139,7 +139,7 @@ RebuildStats = np.dtype([(n, "<f8") for n in ("gpu_ms", "wall_ms", "stage_ms", "
 assert RebuildStats.itemsize == 96
 
 DEVICE_SYMBOLS = [
-    "rt_last_error", "rt_device_count", "rt_kernel_info", "rt_builtins", "rt_top_levels", "rt_shade_footprint", "rt_shade_tables", "rt_create", "rt_destroy", "rt_upload_scene", "rt_share_scene", "rt_set_seeds", "rt_seed_default",
+    "rt_last_error", "rt_device_count", "rt_kernel_info", "rt_builtins", "rt_top_levels", "rt_shade_footprint", "rt_shade_tables", "rt_primary_fused", "rt_create", "rt_destroy", "rt_upload_scene", "rt_share_scene", "rt_set_seeds", "rt_seed_default",
     "rt_get_seeds", "rt_bind_accum", "rt_accum_device_ptr", "rt_stream", "rt_reset", "rt_render", "rt_synchronize", "rt_focus",
     "rt_read_accum", "rt_write_accum", "rt_postproc", "rt_read_counters", "rt_reset_counters", "rt_read_stage_times", "rt_reset_stage_times", "rt_set_profile",
     "rt_stage_begin_frame", "rt_stage_generate", "rt_stage_extend", "rt_stage_shade", "rt_stage_connect",
@@ -217,6 +217,7 @@ def _bind_device(lib):
         lib.rt_debug_traversal_facts.argtypes = [vp, vp]
         lib.rt_shade_footprint.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
         lib.rt_shade_tables.argtypes = [vp, C.POINTER(i32), C.POINTER(i32)]
+        lib.rt_primary_fused.argtypes = [vp, C.POINTER(i32)]
         lib.rt_destroy.argtypes = [vp]
         lib.rt_upload_scene.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32, vp, i32]
         lib.rt_upload_scene_bvh2.argtypes = lib.rt_upload_scene.argtypes

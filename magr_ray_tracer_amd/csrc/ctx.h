@@ -51,8 +51,14 @@ struct RtCtx {
     // The instantiations of the kernels that reach one of the seven builtins, for this context's arithmetic (cfg.builtins, resolved to
     // RT_BUILTINS_IEEE or RT_BUILTINS_REFERENCE), shading, tile and accel: chosen once by choose_builtin_kernels (rt_create)
     void (*kGenerate)(rt355dev::DevQueues, RtCamera, int, int) = nullptr;
-    void (*kShade)(rt355dev::DevScene, rt355dev::DevQueues, rt355dev::DevVariant, int) = nullptr;
+    void (*kShade)(rt355dev::DevScene, rt355dev::DevQueues, rt355dev::DevVariant, rt355dev::ShadeArg<false>) = nullptr;
     void (*kFocus)(rt355dev::DevScene, RtCamera, int, int, int, int, float*) = nullptr;
+    // ... and of the fused primary path of rt_render (fusePrimary, set by configure_traversal from the plan): bounce 0's traversal launch
+    // that computes its rays - plain, coherent, BVH4 - and bounce 0's shade launch that computes them again
+    enum { PRIMARY_PLAIN, PRIMARY_COHERENT, PRIMARY_BVH4, PRIMARY_KINDS };
+    void (*kTracePrimary[PRIMARY_KINDS])(rt355dev::DevScene, rt355dev::DevQueues, RtCamera, int, int, rt355dev::PersistTune) = {};
+    void (*kShadePrimary)(rt355dev::DevScene, rt355dev::DevQueues, rt355dev::DevVariant, rt355dev::ShadeArg<true>) = nullptr;
+    bool fusePrimary = false;   // rt_render runs no k_generate: bounce 0's extend and shade launches make the primary rays themselves
 };
 
 static inline dim3 grid_for(int n) { return dim3((unsigned)std::max(1, (n + rt355dev::kBlock - 1) / rt355dev::kBlock)); }

@@ -33,6 +33,10 @@ template <bool REFB> static void choose_builtin_kernels_of(RtCtx* ctx)
     ctx->kGenerate = k_generate<REFB>;
     ctx->kShade = nee ? (small ? k_shade<true, 256, REFB> : k_shade<true, kTile, REFB>) : (small ? k_shade<false, 256, REFB> : k_shade<false, kTile, REFB>);
     ctx->kFocus = ctx->cfg.accel == RT_ACCEL_BVH4 ? k_focus<RT_ACCEL_BVH4, REFB> : k_focus<RT_ACCEL_BVH2, REFB>;
+    ctx->kTracePrimary[RtCtx::PRIMARY_PLAIN] = k_trace_primary<REFB, false, false>;
+    ctx->kTracePrimary[RtCtx::PRIMARY_COHERENT] = k_trace_primary<REFB, true, false>;
+    ctx->kTracePrimary[RtCtx::PRIMARY_BVH4] = k_trace_primary<REFB, false, true>;
+    ctx->kShadePrimary = nee ? (small ? k_shade<true, 256, REFB, true> : k_shade<true, kTile, REFB, true>) : (small ? k_shade<false, 256, REFB, true> : k_shade<false, kTile, REFB, true>);
 }
 static void choose_builtin_kernels(RtCtx* ctx)   // needs cfg (builtins resolved) and shadeTile
 {
@@ -99,6 +103,15 @@ extern "C" int rt_shade_tables(RtCtx* ctx, int32_t* capacityRows, int32_t* stage
     return RT_OK;
 }
 
+extern "C" int rt_primary_fused(RtCtx* ctx, int32_t* fused)
+{
+    if (!ctx || !fused) return fail(RT_E_INVALID, "rt_primary_fused: null argument");
+    if (!ctx->sceneLoaded) return fail(RT_E_INVALID, "rt_primary_fused: no scene uploaded");
+    if (const int rc = sync_scene_config(ctx)) return rc;
+    *fused = ctx->fusePrimary ? 1 : 0;   // what rt_render reads
+    return RT_OK;
+}
+
 static void free_bag(std::vector<void*>& bag) { for (void* p : bag) (void)hipFree(p); bag.clear(); }
 
 // A context holds at most one device copy of a scene; the copy knows its holders (rt_update_scene waits for them and reconfigures them).
@@ -134,14 +147,17 @@ static size_t tlas_stack_bytes(const RtCtx* c) { return tlas_column_bytes(tlas_l
 // kernel takes (scene, queues, bounce, renderBVH) for extend and (scene, queues, b0, b1) for connect.  `rays`: the stage's queue capacity.
 using PersistKernel = void (*)(DevScene, DevQueues, int, int, int, PersistTune);
 using NestedKernel = void (*)(DevScene, DevQueues, int, int);
+using PrimaryKernel = void (*)(DevScene, DevQueues, RtCamera, int, int, PersistTune);   // (scene, queues, camera, antiAliasing, renderBVH, tune)
 struct TraceLaunch {
     PersistKernel persist = nullptr;
     NestedKernel nested = nullptr;
+    PrimaryKernel primary = nullptr;   // set INSTEAD of `persist`, only where asked for (`primary`) and the context fuses (RtCtx.fusePrimary)
     dim3 grid;
     size_t lds = 0;
     PersistTune tune{};
 };
-static TraceLaunch trace_launch(const RtCtx* c, int stage, int bounce, bool steps, int rays, int topLevels = -1 /* >= 0: as if the stage's PersistTune.topLevels were this */)
+static TraceLaunch trace_launch(const RtCtx* c, int stage, int bounce, bool steps, int rays, int topLevels = -1 /* >= 0: as if the stage's PersistTune.topLevels were this */,
+                                bool primary = false /* rt_render's extend(0): the launch that computes the primary rays, where the context fuses */)
 {
     TraceLaunch L;
     L.grid = grid_for(rays);
@@ -168,6 +184,7 @@ static TraceLaunch trace_launch(const RtCtx* c, int stage, int bounce, bool step
         else if (c->cfg.extend_variant == 5) L.nested = k_extend<RT_ACCEL_BVH2, 1>;
         // bounce 0 through the same kernel with one workgroup per 256 rays: its "queue not longer than the grid" branch is the plain
         // one-ray-per-lane loop without the TLAS code of k_extend (60 instead of 86 VGPRs: 8 instead of 5 waves per SIMD)
+        else if (primary && c->fusePrimary) L.primary = c->kTracePrimary[c->coherent ? RtCtx::PRIMARY_COHERENT : RtCtx::PRIMARY_PLAIN];   // (the same branch, rays computed)
         else L.persist = c->coherent ? k_trace_persist<false, true> : (steps ? k_trace_persist<false, false, true> : k_trace_persist<false>);
         if (top) { L.tune.topBase = c->facts.stackEntries * kBlock; L.lds += top_bytes(L.tune.topLevels); }
         break;
@@ -175,6 +192,7 @@ static TraceLaunch trace_launch(const RtCtx* c, int stage, int bounce, bool step
         L.tune = connect ? c->tuneConnect : c->tune4;
         L.persist = connect ? k_trace_persist4<true> : k_trace_persist4<false>;
         if (connect || bounce > 0) L.grid = dim3(connect ? c->persistGridConnect : c->persistGrid);
+        else if (primary && c->fusePrimary) { L.persist = nullptr; L.primary = c->kTracePrimary[RtCtx::PRIMARY_BVH4]; }
         break;
     case TRAV_TLAS:
     case TRAV_TLAS_SPILL: {
@@ -454,6 +472,7 @@ static void adopt_plan(RtCtx* ctx, const TravPlan& p)
     ctx->trav = p.trav; ctx->spillCap = p.spillCap; ctx->coherent = p.coherent;
     ctx->tune = p.tune; ctx->tuneConnect = p.tuneConnect; ctx->tune4 = p.tune4;
     ctx->tuneBlocks = p.tuneBlocks; ctx->connectBlocks = p.connectBlocks;
+    ctx->fusePrimary = p.fusePrimary;
 }
 // The top tables against the device.  One that would not fit behind the stack columns of a very deep tree is left out: no launch the
 // runtime would reject.  Then, where no knob named the depth (topAuto):
@@ -936,7 +955,25 @@ extern "C" int rt_stage_extend(RtCtx* ctx, int32_t bounce, int32_t renderBVH)
     HIPCHK(hipGetLastError());
     return RT_OK;
 }
-extern "C" int rt_stage_shade(RtCtx* ctx, int32_t bounce)
+// The first launch of a fused frame of rt_render: generate, the frame's counter reset and extend(0) in one (k_trace_primary).  The
+// host's frame state is what generate(.., 1) and rt_stage_extend(0) leave: to every later stage the frame looks the same.
+static int extend_primary(RtCtx* ctx, const RtCamera* cam, const RtSettings* s, int renderBVH)
+{
+    frame_state_reset(ctx);
+    ctx->queued = true;
+    const TraceLaunch L = trace_launch(ctx, ST_EXTEND, 0, false, ctx->nPix, -1, true);
+    if (!L.primary) return fail(RT_E_INVALID, "rt_render: no fused primary launch for this context's traversal");
+    LAUNCH(ctx, ST_EXTEND, L.primary, L.grid, L.lds, ctx->sc, ctx->q, *cam, s ? s->antiAliasing : 1, renderBVH, L.tune);
+    HIPCHK(hipGetLastError());
+    ctx->primaryRays += (uint64_t)ctx->nPix;
+    ctx->generated = true;
+    ctx->cursorUsed[0] = true;
+    return RT_OK;
+}
+static int stage_shade(RtCtx* ctx, int32_t bounce, const RtCamera* primaryCam, int aa);
+extern "C" int rt_stage_shade(RtCtx* ctx, int32_t bounce) { return stage_shade(ctx, bounce, nullptr, 0); }
+// primaryCam: bounce 0 of a fused frame - the launch computes its queue entries from the camera (k_shade<.., PRIMARY>)
+static int stage_shade(RtCtx* ctx, int32_t bounce, const RtCamera* primaryCam, int aa)
 {
     int rc = need_scene(ctx, "rt_stage_shade"); if (rc) return rc;
     ctx->queued = true;
@@ -953,7 +990,8 @@ extern "C" int rt_stage_shade(RtCtx* ctx, int32_t bounce)
     }
     const int tileSz = ctx->shadeTile;
     const dim3 sg((unsigned)std::max(1, std::min(ctx->shadeGrid, (ctx->nPix + tileSz - 1) / tileSz)));
-    LAUNCHB(ctx, ST_SHADE, ctx->kShade, sg, tileSz, 0, ctx->sc, ctx->q, ctx->var, bounce);
+    if (primaryCam) LAUNCHB(ctx, ST_SHADE, ctx->kShadePrimary, sg, tileSz, 0, ctx->sc, ctx->q, ctx->var, ShadeArg<true>{ { *primaryCam, aa } });
+    else LAUNCHB(ctx, ST_SHADE, ctx->kShade, sg, tileSz, 0, ctx->sc, ctx->q, ctx->var, ShadeArg<false>{ bounce });
     ctx->shadeRun[bounce] = true;
     HIPCHK(hipGetLastError());
     return RT_OK;
@@ -1124,12 +1162,15 @@ extern "C" int rt_render(RtCtx* ctx, const RtCamera* cam, const RtSettings* sett
     HIPCHK(hipSetDevice(ctx->cfg.device));
     const bool nee = ctx->cfg.shading == RT_SHADING_NEE, rr = ctx->cfg.russian_roulette != 0;
     const int renderBVH = settings ? settings->renderBVH : 0;
+    const bool fused = ctx->fusePrimary;   // decided with the traversal (plan_traversal): bounce 0's two launches compute the primary rays, no k_generate
+    const int aa = settings ? settings->antiAliasing : 1;
     for (int f = 0; f < frames; f++) {
-        if ((rc = generate(ctx, cam, settings, 1))) return rc;   // the frame's counter reset rides in k_generate's first workgroup
+        // the frame's counter reset rides in the first workgroup of its first launch
+        if ((rc = fused ? extend_primary(ctx, cam, settings, renderBVH) : generate(ctx, cam, settings, 1))) return rc;
         for (int b = 0; b < ctx->cfg.max_bounces; b++) {
-            if ((rc = rt_stage_extend(ctx, b, renderBVH))) return rc;
+            if (b > 0 || !fused) if ((rc = rt_stage_extend(ctx, b, renderBVH))) return rc;
             if (renderBVH) break;                                  // renderer.cpp:79
-            if ((rc = rt_stage_shade(ctx, b))) return rc;
+            if ((rc = stage_shade(ctx, b, fused && b == 0 ? cam : nullptr, aa))) return rc;
             if (!rr && nee) if ((rc = rt_stage_connect(ctx, b, b))) return rc;   // renderer.cpp:85-87
         }
         if (rr && nee && !renderBVH) if ((rc = rt_stage_connect(ctx, 0, ctx->cfg.max_bounces - 1))) return rc; // renderer.cpp:91-92

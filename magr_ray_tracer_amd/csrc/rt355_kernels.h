@@ -532,8 +532,11 @@ RT_FORCEINLINE void begin_frame(const DevQueues& q) // renderer.cpp:66-69 (one w
 __global__ void k_begin_frame(DevQueues q) { begin_frame(q); }   // stage-level API; rt_render folds it into k_generate
 
 // ------------------------------------------------------------------ k_generate
+// (both results are assigned once, at the end, in one order: where the two branches ended in stores to different ones of the two, the
+// compiler merged those stores into one through a selected address, and O and D lived in scratch memory instead of registers)
 template <bool REFB> RT_FORCEINLINE void primary_ray(const RtCamera& cam, int x, int y, int W, int H, int aa, uint32_t& seed, float4& O, float4& D)
 {
+    float4 o = splat(0.0f), d = splat(0.0f);
     if (cam.type == RT_CAM_PROJECTION) { // camera.cl:9-24
         float u = (float)x * (1.0f / (float)W);
         float v = (float)y * (1.0f / (float)H);
@@ -541,21 +544,23 @@ template <bool REFB> RT_FORCEINLINE void primary_ray(const RtCamera& cam, int x,
         float4 P = add4(add4(ld4(cam.topLeft), muls(ld4(cam.horizontal), u)), muls(ld4(cam.vertical), v));
         float4 dir = normalize4<REFB>(sub4(P, ld4(cam.origin)));
         float4 focalPoint = add4(ld4(cam.origin), muls(dir, cam.focalLength));
-        O = add4(ld4(cam.origin), muls(sub4(rnd_float3(seed), splat(0.5f)), cam.aperture));
-        D = normalize4<REFB>(sub4(focalPoint, O));
+        o = add4(ld4(cam.origin), muls(sub4(rnd_float3(seed), splat(0.5f)), cam.aperture));
+        d = normalize4<REFB>(sub4(focalPoint, o));
     } else { // camera.cl:25-44
         float u = ((float)x - (float)W * .5f) * (2.f / (float)W);
         float v = ((float)y - (float)H * .5f) * (2.f / (float)H);
         if (aa) { u += rnd_float(seed) / (float)W; v += rnd_float(seed) / (float)H; }
         float r2 = u * u + v * v;
-        if (r2 > 1.0f) { O = splat(0.0f); D = splat(0.0f); return; }
-        float rr = sqrtf(r2);
-        float psi = rr * cam.fov * kPi / 180.0f;
-        float sinPsi = rt_sinf<REFB>(psi), cosPsi = rt_cosf<REFB>(psi);
-        float sinAlpha = u / rr, cosAlpha = v / rr;
-        D = sub4(add4(muls(ld4(cam.up), sinPsi * cosAlpha), muls(ld4(cam.right), sinPsi * sinAlpha)), muls(ld4(cam.forward), cosPsi));
-        O = ld4(cam.origin);
+        if (!(r2 > 1.0f)) {   // (outside the unit circle: the zero ray)
+            float rr = sqrtf(r2);
+            float psi = rr * cam.fov * kPi / 180.0f;
+            float sinPsi = rt_sinf<REFB>(psi), cosPsi = rt_cosf<REFB>(psi);
+            float sinAlpha = u / rr, cosAlpha = v / rr;
+            d = sub4(add4(muls(ld4(cam.up), sinPsi * cosAlpha), muls(ld4(cam.right), sinPsi * sinAlpha)), muls(ld4(cam.forward), cosPsi));
+            o = ld4(cam.origin);
+        }
     }
+    O = o; D = d;
 }
 template <bool REFB>
 __global__ __launch_bounds__(kBlock) void k_generate(DevQueues q, RtCamera cam, int aa, int beginFrame)
@@ -689,14 +694,31 @@ RT_FORCEINLINE OneInstance one_instance(const DevScene& sc)
 
 // Queue slot `idx` as a new ray with r.t = its tmax (extend: kFar; connect: t_light): the world ray as k_extend / k_connect build it
 // or, given `inst`, that ray in the instance's object space
+RT_FORCEINLINE void new_ray(TRay& r, const float4& O, const float4& D, float tmax, const OneInstance* inst)
+{
+    if (inst) { object_space(r, mk4(O.x, O.y, O.z, 0.0f), mk4(D.x, D.y, D.z, 0.0f), inst->t0, inst->t1, inst->t2); reciprocal_dir(r); }
+    else ray_from(r, O, D);
+    no_hit(r, tmax);
+}
 template <bool OCC> RT_FORCEINLINE void queue_ray(TRay& r, const DevQueues& q, int b0, int qFirst, int idx, const OneInstance* inst = nullptr)
 {
     float4 O, D; float tmax;
     if (OCC) { const float4 a = q.sA[qFirst + idx], b = q.sB[qFirst + idx]; O = a; D = b; tmax = a.w; }
     else { O = q.O[b0 & 1][idx]; D = q.D[b0 & 1][idx]; tmax = kFar; }
-    if (inst) { object_space(r, mk4(O.x, O.y, O.z, 0.0f), mk4(D.x, D.y, D.z, 0.0f), inst->t0, inst->t1, inst->t2); reciprocal_dir(r); }
-    else ray_from(r, O, D);
-    no_hit(r, tmax);
+    new_ray(r, O, D, tmax, inst);
+}
+// The primary ray of queue slot `idx` of bounce 0 as a new ray, computed where it is used instead of loaded: what k_generate would have
+// stored in q.O[0][idx] / q.D[0][idx] from q.seeds[idx], bit for bit (the same primary_ray, compiled without contraction), so the fused
+// frame of rt_render never stores the record.  The advanced seed is written back only where no shade launch follows that would do it
+// (`keepSeed`: a renderBVH frame); otherwise k_shade<.., PRIMARY> draws the same numbers again from the same state and stores what follows.
+template <bool REFB> RT_FORCEINLINE void primary_queue_ray(TRay& r, const DevQueues& q, const RtCamera& cam, int aa, int keepSeed, int idx, const OneInstance* inst)
+{
+    const int pix = q.firstPixel + idx;
+    uint32_t seed = q.seeds[idx];
+    float4 O, D;
+    primary_ray<REFB>(cam, pix % q.width, pix / q.width, q.width, q.height, aa, seed, O, D);
+    if (keepSeed) q.seeds[idx] = seed;
+    new_ray(r, O, D, kFar, inst);
 }
 
 // What a traced queue slot leaves behind: extend -> the hit record and, where kept, `steps` and the heat map (wavefront.cl:66-67);
@@ -846,16 +868,18 @@ RT_FORCEINLINE void top_descent(const DevQueues& q, const QueueWindow& w, int re
 
 // Short queue (late bounces, and bounce 0 when it is launched with one workgroup per 256 rays): every wave gets at most one 64-ray chunk
 // and nothing is left to refill from, so run the plain one-ray-per-lane loop, which has less per-step overhead than the refill machine.
-template <bool OCC, bool COH, bool BVH4 = false>
+// PRIMARY (k_trace_primary): the queue is bounce 0's pixel grid and a lane computes its ray instead of loading it (primary_queue_ray).
+template <bool OCC, bool COH, bool BVH4 = false, bool PRIMARY = false, bool REFB = false>
 RT_FORCEINLINE void trace_short_queue(const DevScene& sc, const DevQueues& q, int b0, const QueueWindow& w, int renderBVH, const OneInstance& one,
-                                      uint32_t* stk, int waveId, int lane, const PersistTune& tune)
+                                      uint32_t* stk, int waveId, int lane, const PersistTune& tune, const RtCamera* cam = nullptr, int aa = 0)
 {
     WorkCtr wc = { 0, 0, 0, 0 };
     uint32_t rays = 0;
     const int idx = short_queue_slot<OCC>(q, b0, w.n, tune, waveId, lane);
     if (idx < w.n) {
         TRay r;
-        queue_ray<OCC>(r, q, b0, w.first, idx, &one);
+        if (PRIMARY) primary_queue_ray<REFB>(r, q, *cam, aa, renderBVH, idx, &one);   // (a renderBVH frame has no shade launch: keep the seed)
+        else queue_ray<OCC>(r, q, b0, w.first, idx, &one);
         rays = 1; wc.inst = 1;
         const int st = BVH4 ? traverse_bvh4_packed<OCC>(sc, r, one.root, stk, wc)
                      : COH ? traverse_bvh2_packed_coherent(sc, r, one.root, stk, wc) : traverse_bvh2_packed<OCC>(sc, r, one.root, stk, wc);
@@ -864,6 +888,24 @@ RT_FORCEINLINE void trace_short_queue(const DevScene& sc, const DevQueues& q, in
     flush_counters(OCC ? q.ctrConnect : q.ctrExtend, rays, wc, stk);
 }
 
+// ------------------------------------------------------------------ k_trace_primary: generate and extend(0) of a fused frame in one launch
+// rt_render's bounce 0 over a single BLAS (BVH2 or BVH4), one workgroup per 256 pixels: the one-ray-per-lane branch above with every
+// lane computing its own primary ray, so k_generate's launch, its 56 bytes per pixel and extend's 32 bytes read back are not in the frame.
+// The launch takes over k_generate's two side jobs under the same block indices: the frame's counter reset (workgroup 0) and the arming
+// of shade(0)'s scan words (a workgroup for the 256 slots of one of them, as there).
+// The queue length is q.nPix, NOT q.nRays[0]: begin_frame writes that word in workgroup 0 of this very launch, and the other workgroups
+// would race with it.  Nothing else begin_frame writes - the dequeue heads, the tickets, nShadow[0] - is read here: this branch takes no
+// chunk from a cursor, and tickets and shadow counts belong to k_shade and connect, which are later launches of the stream.
+template <bool REFB, bool COH, bool BVH4>
+__global__ __launch_bounds__(kBlock) void k_trace_primary(DevScene sc, DevQueues q, RtCamera cam, int aa, int renderBVH, PersistTune tune)
+{
+    extern __shared__ uint32_t stk[];
+    if (blockIdx.x == 0) begin_frame(q);
+    if (threadIdx.x == 0) { q.tile[0][1 + blockIdx.x] = 0ull; if ((blockIdx.x & 63) == 0) { q.super[0][blockIdx.x >> 6] = 0ull; q.supAcc[0][blockIdx.x >> 6] = 0ull; } }   // arm shade(0)'s scan
+    const QueueWindow w = { 0, q.nPix, q.cursor };
+    const OneInstance one = one_instance(sc);
+    trace_short_queue<false, COH, BVH4, true, REFB>(sc, q, 0, w, renderBVH, one, stk, blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6), threadIdx.x & 63, tune, &cam, aa);
+}
 
 // STEPS: the per-ray `steps` value of the heat map (wavefront.cl:66-67) is kept only by the instantiation that has a reader for it
 // (renderBVH or rt_debug_enable_steps); the work counters of a wave are kept in scalar registers (population counts of the masks the
@@ -1731,9 +1773,14 @@ RT_FORCEINLINE unsigned long long wait_word(const unsigned long long* p, unsigne
 static_assert(RT_MAX_BOUNCES < 0x40 && kMetaInside == 0x100u && kMetaLastSpec == 0x200u, "park_meta packs meta.y into one byte");
 RT_FORCEINLINE uint8_t park_meta(uint32_t y) { return (uint8_t)((y & 0x3fu) | ((y & (kMetaInside | kMetaLastSpec)) >> 2)); }
 RT_FORCEINLINE uint32_t unpark_meta(uint8_t b) { return ((uint32_t)b & 0x3fu) | (((uint32_t)b & 0xc0u) << 2); }
-template <bool NEE, int TILE, bool REFB>
-__global__ __launch_bounds__(TILE, 4) void k_shade(DevScene sc, DevQueues q, DevVariant var, int bounce)
+// PRIMARY (bounce 0 of a fused frame of rt_render): the queue entries were never stored (k_trace_primary).  A lane
+// computes its entry again at the start of its shading, where few registers are live - the same primary_ray from the same seed, which
+// also advances the seed exactly as k_generate would have; intensity 1, pixel = firstPixel + slot, lastSpecular - and its tile fetch
+// loads the hit record and the seed only.  Without PRIMARY none of that is compiled in: the other bounces keep their code.
+template <bool NEE, int TILE, bool REFB, bool PRIMARY = false>
+__global__ __launch_bounds__(TILE, 4) void k_shade(DevScene sc, DevQueues q, DevVariant var, ShadeArg<PRIMARY> arg)
 {
+    const int bounce = arg.bounce;
     // [2]: a tile's outputs are written one tile late (see the loop), so the counts of two tiles are alive
     __shared__ uint32_t sWaveE[2][TILE / 64], sWaveS[2][TILE / 64], sBaseE, sBaseS;
     // Survivors wait in LDS (97 B per lane, each lane its own slots) while the next tile is shaded and the ordered scan resolves, instead
@@ -1819,7 +1866,8 @@ __global__ __launch_bounds__(TILE, 4) void k_shade(DevScene sc, DevQueues q, Dev
     auto fetch = [&](uint32_t t, TileIn& in) {
         const int j = (int)t * TILE + threadIdx.x;
         if (t < numTiles && j < n) {
-            in.hit = ldnt4(&q.hit[j]); in.meta = ldnt2(&q.meta[cur][j]); in.O = ldnt4(&q.O[cur][j]); in.D = ldnt4(&q.D[cur][j]); in.inten = ldnt4(&q.inten[cur][j]);   // last use
+            in.hit = ldnt4(&q.hit[j]);   // last use (as the four below)
+            if (!PRIMARY) { in.meta = ldnt2(&q.meta[cur][j]); in.O = ldnt4(&q.O[cur][j]); in.D = ldnt4(&q.D[cur][j]); in.inten = ldnt4(&q.inten[cur][j]); }
             in.seed = q.seeds[j];
         }
     };
@@ -1866,15 +1914,23 @@ __global__ __launch_bounds__(TILE, 4) void k_shade(DevScene sc, DevQueues q, Dev
         uint2 extMeta = make_uint2(0u, 0u);
         if (i < n) {
             const float4 hit = in.hit;
-            const uint2 meta = in.meta;
             SRay ray;
-            ray.O = in.O; ray.D = in.D; ray.inten = in.inten;
+            uint32_t seed = in.seed;
+            if (PRIMARY) {   // k_generate's record of this slot, made again (see above)
+                ray.pixel = q.firstPixel + i; ray.bounces = 0; ray.inside = false; ray.lastSpec = true;
+                if constexpr (PRIMARY) primary_ray<REFB>(arg.gen.cam, ray.pixel % q.width, ray.pixel / q.width, q.width, q.height, arg.gen.aa, seed, ray.O, ray.D);
+                ray.inten = splat(1.0f);
+            } else {
+                const uint2 meta = in.meta;
+                ray.O = in.O; ray.D = in.D; ray.inten = in.inten;
+                ray.pixel = (int)meta.x; ray.bounces = (int)(meta.y & kMetaBounceMask);
+                ray.inside = (meta.y & kMetaInside) != 0; ray.lastSpec = (meta.y & kMetaLastSpec) != 0;
+            }
             ray.t = hit.x; ray.prim = __float_as_int(hit.y); ray.u = hit.z; ray.v = hit.w;
-            ray.pixel = (int)meta.x; ray.bounces = (int)(meta.y & kMetaBounceMask);
-            ray.inside = (meta.y & kMetaInside) != 0; ray.lastSpec = (meta.y & kMetaLastSpec) != 0;
             if (ray.prim == -1) { // wavefront.cl:109-112, sky = skydome.cl:7
                 float4 c = mul4(ray.inten, mk4(0.0784f, 0.0941f, 0.3215f, 0.0f));
                 q.accum[ray.pixel] = add4(q.accum[ray.pixel], c);
+                if (PRIMARY) q.seeds[i] = seed;   // k_generate stored the advanced seed of every pixel, a miss included
             } else {
                 // what extend() leaves in the ray (wavefront.cl:69-72)
                 ray.I = add4(ray.O, muls(ray.D, ray.t));
@@ -1887,7 +1943,6 @@ __global__ __launch_bounds__(TILE, 4) void k_shade(DevScene sc, DevQueues q, Dev
                 ray.N = (tag >> 28) == RT_PRIM_SPHERE ? prim_normal(sc.prims + ray.prim, ray.I)
                                                       : mk4(rec.x, rec.y, rec.z, (tag & 0x08000000u) ? -0.0f : 0.0f);   // flipped normals carry w = -0
                 if (dot4(ray.N, neg4(ray.D)) < 0) ray.N = muls(ray.N, -1.0f);
-                uint32_t seed = in.seed;
                 float4 color = shade_hit<NEE, REFB>(sc, tab, var, ray, seed, ext, sh);
                 q.seeds[i] = seed;
                 color = firefly<REFB>(var.fireflies, color);

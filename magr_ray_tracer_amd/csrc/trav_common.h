@@ -82,6 +82,7 @@ struct TravKnobs {
     bool xcdRaysSet = false; int xcdRays = 0;        // RT355_XCD_RAYS (>= 0)
     bool thinSet = false; int thin = 0;              // RT355_THIN (0..64; 0: off)
     int connectBlocks = 0;                           // RT355_CONNECT_BLOCKS (> 0; lab): workgroups per CU of connect's persistent grid
+    bool noFusePrimary = false;                      // RT355_FUSE_PRIMARY=0: rt_render keeps k_generate and the stored primary queue (A/B runs, tests)
 };
 
 // The only place that reads them.  Not cached: tests change the environment between a context's uploads.
@@ -113,6 +114,7 @@ static inline TravKnobs read_trav_knobs()
     if (const char* t = getenv("RT355_XCD_RAYS")) { k.xcdRays = std::max(0, atoi(t)); k.xcdRaysSet = true; }
     if (const char* t = getenv("RT355_THIN")) { k.thin = std::min(64, std::max(0, atoi(t))); k.thinSet = true; }
     if (const char* t = getenv("RT355_CONNECT_BLOCKS")) { const int d = atoi(t); if (d > 0) k.connectBlocks = d; }
+    if (const char* t = getenv("RT355_FUSE_PRIMARY")) k.noFusePrimary = atoi(t) == 0;
     return k;
 }
 
@@ -124,6 +126,7 @@ struct TravPlan {
     PersistTune tune{}, tuneConnect{}, tune4{};   // extend (BVH2), connect, extend (BVH4), before the top table is fitted to the device
     bool topAuto = false;       // no knob named the top table's depth: each stage takes the deepest that costs it no workgroup
     int tuneBlocks = 0, connectBlocks = 0;   // workgroups per CU of the persistent grids that the knobs ask for (0: none asked)
+    bool fusePrimary = false;   // rt_render's bounce 0 computes the primary rays in its extend and shade launches: no k_generate, no stored queue
 };
 
 static inline TravPlan plan_traversal(const TravFacts& f, const TravKnobs& k)
@@ -163,6 +166,11 @@ static inline TravPlan plan_traversal(const TravFacts& f, const TravKnobs& k)
     // bounce 0 (RT355_COHERENT=2: every bounce of k_trace_persist_tlas, lab; 0: off for A/B runs): wave-uniform node records come through
     // the scalar cache (traverse_bvh2_packed_coherent, k_trace_persist_tlas<COH>)
     p.coherent = k.coherentSet ? k.coherent : 1;
+    // The fused primary path: where bounce 0's extend launch is one workgroup per 256 pixels through the one-ray-per-lane branch of a
+    // single-BLAS kernel (trace_short_queue of k_trace_persist, not under extend_variant 3 or 5, and of k_trace_persist4), that launch
+    // computes its rays itself (k_trace_primary).  The TLAS kernels' short-queue branches are their own code and the nested kernels have
+    // none: those contexts stay on k_generate.  RT355_FUSE_PRIMARY=0 keeps every context there.
+    p.fusePrimary = !k.noFusePrimary && ((p.trav == TRAV_BVH2 && f.extend_variant != 3 && f.extend_variant != 5) || p.trav == TRAV_BVH4);
 
     // extend (BVH2), connect, extend (BVH4): measured optima (tools/tune_extend.sh, tune_connect.sh, tune_persist.sh)
     p.tune = PersistTune{ 112, 24, 6, 8, 0 }; p.tuneConnect = PersistTune{ 128, 32, 6, 16, 0 }; p.tune4 = PersistTune{ 64, 20, 6, 8, 0 };

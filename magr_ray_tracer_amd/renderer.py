@@ -511,6 +511,13 @@ class Device:
         self._chk(self._lib.rt_shade_tables(self._h, C.byref(r), C.byref(s)))
         return int(r.value), bool(s.value)
 
+    def primary_fused(self):
+        """Whether this context's render() frames launch no k_generate: bounce 0's extend and shade launches compute the primary rays
+        themselves (rt_primary_fused; RT355_FUSE_PRIMARY=0 turns it off).  Same bits either way."""
+        f = C.c_int32(0)
+        self._chk(self._lib.rt_primary_fused(self._h, C.byref(f)))
+        return bool(f.value)
+
     @property
     def builtins(self):
         """The context's arithmetic as resolved by the library (rt_builtins): _lib.BUILTINS_IEEE or _lib.BUILTINS_REFERENCE."""
